@@ -1,19 +1,23 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json metric "train tokens/sec/GPU (TransfoXL seq2048 bf16) at 1/2/4/8 GPUs; AR decode tok/s").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 * N > 1 and no launcher environment: this process touches no GPU; it starts N ranks with
   `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one process per GPU, RCCL),
   relays rank 0's JSON line and exits with the children's code.  Started under a launcher (WORLD_SIZE set) it is one rank.
 * The headline leg (`value`) is the SURVEY C3 training step: forward + backward + gradient all-reduce + clip + AdamW on one
-  batch of (B, T) synthetic ids per GPU (weak scaling).  At N = 1 the same process then runs the other two legs of the
+  batch of (B, T) synthetic ids per GPU (weak scaling).  A plain run does that leg alone: set-up, W untimed steps, K timed
+  steps, the JSON line.
+* `--full` adds everything else the benchmark measures.  At N = 1 the same process then runs the other two legs of the
   metric and attaches them to the same JSON line: `"decode"` (cached-mem AR decode, batch 64, top-k 8, one
-  hipGraph replay per token) and `"reformer"` (Reformer 6L/512d, T = 8192).  Decode and eval are replicas only
-  (DESIGN 6), so at N > 1 only the training leg runs.
-* Every leg carries `roofline` (dominant kernel, HIP events on the launch stream inside the timed region) and, at N = 1,
-  `cpu_baseline`: the CPU oracle (oracle/*.py, the reference-style fp32 path; `kind: "port"`) on the host cores on a
-  bounded sample of the same workload.
+  hipGraph replay per token) and `"reformer"` (Reformer 6L/512d, T = 8192), then the context legs (`"context"`).
+  Decode and eval are replicas only, so at N > 1 only the training leg runs.  Every leg carries `roofline`
+  (dominant kernel, HIP events on the launch stream inside the timed region) and, at N = 1, `cpu_baseline`: the CPU oracle
+  (oracle/*.py, the reference-style fp32 path; `kind: "port"`) on the host cores on a bounded sample of the same workload.
+  Without `--full`, `--no-cpu-baseline --no-roofline --no-context-legs` are implied and the decode leg skips its full-ring window.
+* `--dump-outputs DIR`: after the timed steps, what the last timed step handed its caller, as DIR/<name>.npy (float32; token
+  ids float64): see `dump_outputs`.  Inputs and weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -57,7 +61,7 @@ def parse_args(argv=None):
     ap.add_argument('--workload', default='c3', choices=list(WORKLOADS))
     ap.add_argument('--batch', type=int, default=None, help='per-GPU batch (sequences)')
     ap.add_argument('--mode', default='all', choices=['all', 'train', 'decode', 'reformer'],
-                    help='all = train leg + (at one GPU) the decode and Reformer legs on the same JSON line')
+                    help='all = train leg (+ with --full, at one GPU, the decode and Reformer legs on the same JSON line)')
     ap.add_argument('--eager', action='store_true', help='decode leg without hipGraph replay (PMC passes: rocprofv3 cannot '
                                                          'collect counters over graph replays)')
     ap.add_argument('--decode-steps', type=int, default=0, help='decode steps to time (0 = the whole C5 generation)')
@@ -65,11 +69,18 @@ def parse_args(argv=None):
                     '                    longer one so that their short eager window sits at the mean ring occupancy of the generation)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--no-context-legs', action='store_true', help='skip the C2 / mode-S / published-config legs of the default line')
+    ap.add_argument('--no-context-legs', action='store_true', help='skip the C2 / mode-S / published-config legs of the --full line')
     ap.add_argument('--grad-exchange', default='fp32', choices=['fp32', 'bf16'],
                     help='dtype of the data-parallel gradient all-reduce (fp32 = what HF DDP exchanges in the reference stack)')
     ap.add_argument('--master-port', type=int, default=29533)
-    return ap.parse_args(argv)
+    ap.add_argument('--full', action='store_true', help='also the decode / Reformer / context legs (mode all, one GPU), the CPU '
+                                                        'baselines, the roofline objects and the full-ring decode window')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy')
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_roofline = args.no_context_legs = True
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -168,6 +179,27 @@ class EventBracket:
         return sum(s.elapsed_time(e) for s, e in self.ev)
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+def train_step_outputs(out, eng):
+    """What one training step hands its caller: the model output's `loss` and per-token `losses` (TransfoXL), and the step's
+    pre-clip gradient norm.  Not the engine's gradient and weight buffers: the split-K weight gradients add fp32 partial sums
+    with atomics in whatever order the workgroups finish, and AdamW's update (~ lr * sign(g) while the moments are young) turns
+    that last-bit noise in near-zero gradient elements into weights a few lr apart from one run to the next.  The outputs kept
+    are smooth functions of all of them: two runs agree to within one bf16 rounding step.  Not the Reformer's logits either:
+    its LSH bucket ids are discrete, so those weight differences move a few positions into other buckets."""
+    arrays = {'loss': out.loss.detach().float().cpu().numpy(), 'grad_norm': eng.grad_norm().float().cpu().numpy().reshape(())}
+    if getattr(out, 'losses', None) is not None:
+        arrays['losses'] = out.losses.detach().float().cpu().numpy()
+    return arrays
+
+
+def dump_outputs(path: str, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + '.npy'), np.asarray(a))
+
+
 # ------------------------------------------------------------------------------------------------ legs
 def train_leg(args, ranks: Ranks):
     from symbolic_music_generation_amd.transformer_xl import MyTransfoXLConfig, MyTransfoXLLMHeadModel
@@ -207,19 +239,25 @@ def train_leg(args, ranks: Ranks):
         if not args.no_roofline:
             ops.ktime_enable(on)
 
+    last = {}
+
     def step():
         with torch.no_grad():          # the fused path: explicit engine backward, no autograd node needed
             eng.zero_grad()
-            model(input_ids=ids, labels=labels)
+            last['out'] = model(input_ids=ids, labels=labels)
             eng.backward(layer_done=sync.layer_done)
             sync.finish()
             eng.optimizer_step(lr=lr, weight_decay=wd, max_grad_norm=1.0, grad_scale=1.0 / world)
 
     dt = timed_steps(ranks, step, args.steps, args.warmup, on_timed=on_timed)
     ops.relattn_bwd, ops.relattn_bwd_fused = orig_bwd, orig_fused
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_step_outputs(last['out'], eng))
     kt = ops.ktime_collect() if not args.no_roofline else {}
-    with torch.no_grad():
-        loss = model(input_ids=ids, labels=labels).loss.item()
+    loss = None
+    if args.full:
+        with torch.no_grad():
+            loss = model(input_ids=ids, labels=labels).loss.item()
     out = None
     if rank == 0:
         tokens = B * T * world * args.steps
@@ -231,10 +269,12 @@ def train_leg(args, ranks: Ranks):
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
             'rccl_ranks': ranks.rccl_ranks(), 'grad_exchange_dtype': sync.dtype,
             'config': {'workload': wl['name'], 'per_gpu_batch': B, 'global_batch': B * world, 'seq_len': T, 'mem_len': M,
-                       'parallelism': f'dp{world}', 'dropout': cfg.dropout, 'final_loss': loss,
+                       'parallelism': f'dp{world}', 'dropout': cfg.dropout,
                        'train_flops_per_token': 3 * f_fwd,
                        'whole_step_mfma_frac': 3 * f_fwd * tokens / dt / world / (MFMA_BF16_PEAK_TFLOPS * 1e12)},
         }
+        if loss is not None:            # one more forward after the timed steps: --full only
+            out['config']['final_loss'] = loss
         if br.ev:
             ms = br.total_ms() / len(br.ev)
             # algorithmic flops of ONE attention-backward call (one layer, this rank's batch): backward = 2 x forward of the
@@ -336,10 +376,12 @@ def reformer_leg(args, ranks: Ranks, steps: int, warmup: int):
     if not args.no_roofline:
         ops.gemm = timed_gemm
 
+    last = {}
+
     def step():
         with torch.no_grad():
             eng.zero_grad()
-            model(input_ids=ids, labels=ids)
+            last['out'] = model(input_ids=ids, labels=ids)
             eng.backward(layer_done=sync.layer_done)
             sync.finish()
             eng.optimizer_step(lr=3e-4, weight_decay=0.01, max_grad_norm=1.0, grad_scale=1.0 / world)
@@ -351,6 +393,8 @@ def reformer_leg(args, ranks: Ranks, steps: int, warmup: int):
 
     dt = timed_steps(ranks, step, steps, warmup, on_timed=on_timed)
     ops.gemm = orig_gemm
+    if args.dump_outputs and args.mode == 'reformer' and rank == 0:
+        dump_outputs(args.dump_outputs, train_step_outputs(last['out'], eng))
     kt = ops.ktime_collect() if not args.no_roofline else {}
     out = None
     if rank == 0:
@@ -530,7 +574,7 @@ def decode_leg(args, ranks: Ranks, warmup: int):
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         # steady state with every ring slot written: positions 2048 .. 2048 + FULL
-        full_steps = FULL if args.decode_steps <= 0 else 0
+        full_steps = FULL if args.decode_steps <= 0 and args.full else 0
         dt_full = None
         if full_steps:
             t0 = time.perf_counter()
@@ -538,6 +582,10 @@ def decode_leg(args, ranks: Ranks, warmup: int):
                 replay()
             torch.cuda.synchronize()
             dt_full = time.perf_counter() - t0
+    if args.dump_outputs and args.mode == 'decode' and rank == 0:
+        # the generated sequences: prompt, then one sampled id per position (token ids are exact in float64)
+        ids = torch.cat([ln.ids for ln in dec.lanes], 0) if lanes > 1 else dec.ids
+        dump_outputs(args.dump_outputs, {'ids': ids[:, :done + steps + full_steps].double().cpu().numpy()})
     d, L = cfg.d_model, cfg.n_layer
     # algorithmic bytes per step: weights once + the WRITTEN part of the projected K/V ring per sequence, averaged
     # over the timed steps; `full_ring` is the figure for a full memory (2 M d 2 B per layer)
@@ -818,7 +866,7 @@ def main(argv=None):
                 out.update(higher_is_better=True, scaling='weak', vs_baseline=None, rccl_ranks=ranks.rccl_ranks())
         else:
             out = train_leg(args, ranks)
-            if args.mode == 'all' and world == 1 and args.workload == 'c3':
+            if args.full and args.mode == 'all' and world == 1 and args.workload == 'c3':
                 dec = decode_leg(args, ranks, 3)
                 ref = reformer_leg(args, ranks, min(args.steps, 10), min(args.warmup, 3))
                 out['decode'], out['reformer'] = dec, ref

@@ -9,20 +9,20 @@ OUT=gpurun_out/prof_$TAG
 ROOT=$(pwd)
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $ROOT
-TRAIN="bench.py --mode train --no-cpu-baseline"
+TRAIN="bench.py --full --mode train --no-cpu-baseline"
 # the decode PMC window (40 eager steps) sits at the generation's mean ring occupancy (~1153 written slots), not behind the 256-token prompt
 DPROMPT=${DPROMPT:-1130}
 run() { local name=$1; shift; echo "== $name"; "$@" > $OUT/$name.log 2>&1 || { tail -20 $OUT/$name.log; exit 1; }; }
 run train_stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/train -o t -- python3 $TRAIN --steps 5 --warmup 2
-run decode_stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/decode -o t -- python3 bench.py --mode decode --no-cpu-baseline
-run reformer_stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/reformer -o t -- python3 bench.py --mode reformer --no-cpu-baseline --steps 5 --warmup 2
+run decode_stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/decode -o t -- python3 bench.py --full --mode decode --no-cpu-baseline
+run reformer_stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/reformer -o t -- python3 bench.py --full --mode reformer --no-cpu-baseline --steps 5 --warmup 2
 run train_fetch rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o f -- python3 $TRAIN --steps 2 --warmup 1
 run train_write rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o w -- python3 $TRAIN --steps 2 --warmup 1
 run train_mfma rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/mfma -o m -- python3 $TRAIN --steps 2 --warmup 1
-run reformer_fetch rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/rfetch -o f -- python3 bench.py --mode reformer --no-cpu-baseline --steps 2 --warmup 1
-run reformer_write rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/rwrite -o w -- python3 bench.py --mode reformer --no-cpu-baseline --steps 2 --warmup 1
-run decode_fetch rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/dfetch -o f -- python3 bench.py --mode decode --eager --decode-steps 40 --decode-prompt $DPROMPT --no-cpu-baseline
-run decode_write rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/dwrite -o w -- python3 bench.py --mode decode --eager --decode-steps 40 --decode-prompt $DPROMPT --no-cpu-baseline
+run reformer_fetch rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/rfetch -o f -- python3 bench.py --full --mode reformer --no-cpu-baseline --steps 2 --warmup 1
+run reformer_write rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/rwrite -o w -- python3 bench.py --full --mode reformer --no-cpu-baseline --steps 2 --warmup 1
+run decode_fetch rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/dfetch -o f -- python3 bench.py --full --mode decode --eager --decode-steps 40 --decode-prompt $DPROMPT --no-cpu-baseline
+run decode_write rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/dwrite -o w -- python3 bench.py --full --mode decode --eager --decode-steps 40 --decode-prompt $DPROMPT --no-cpu-baseline
 B=$(python3 -c "import bench; print(bench.WORKLOADS['c3']['B'])")
 f() { find $1 -name "$2" | head -1; }
 python3 scripts/pmc_traffic.py $(f $OUT/fetch '*counter_collection.csv') $(f $OUT/write '*counter_collection.csv') $OUT/${TAG}_c3_pmc_traffic.json $B

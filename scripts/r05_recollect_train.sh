@@ -6,7 +6,7 @@ OUT=gpurun_out/prof_r05t
 ROOT=$(pwd)
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $ROOT
-TRAIN="bench.py --mode train --no-cpu-baseline"
+TRAIN="bench.py --full --mode train --no-cpu-baseline"
 run() { local name=$1; shift; echo "== $name"; "$@" > $OUT/$name.log 2>&1 || { tail -20 $OUT/$name.log; exit 1; }; }
 run train_stats rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/train -o t -- python3 $TRAIN --steps 5 --warmup 2
 run train_fetch rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o f -- python3 $TRAIN --steps 2 --warmup 1

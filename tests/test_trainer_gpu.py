@@ -97,7 +97,7 @@ def test_bench_rccl_path_single_rank():
     env = dict(os.environ, MXL_DIST_FORCE='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-           '--workload', 'tiny', '--no-cpu-baseline']
+           '--workload', 'tiny', '--no-cpu-baseline', '--full']
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]
