@@ -379,6 +379,10 @@ int mxl_kv_append(const void* qkv, void* kcache, void* vcache, const int* t_dev,
                   const float* r_r_bias, void* qr_out, void* stream);   /* qr_out (B, d) bf16 = q + r_r_bias, or NULL */
 /* after the prompt forward: cache slots <- K/V rows of the last min(T, M) positions of a (B, T, 3d) qkv buffer */
 int mxl_kv_fill(const void* qkv, void* kcache, void* vcache, int B, int T, int M, int d, int dh, void* stream);
+/* left-padded prompts: k = v = 0 (columns [d, 3d)) in rows j < n_pad[b] of a (B, T, 3d) bf16 qkv buffer, so every pad column is
+ * one more zero-memory slot of the prompt pass (qkv_net has no bias).  n_pad (B,) int32 on the device, each in [0, T]; q columns
+ * and rows j >= n_pad[b] are not touched.  Capture-safe (no host read of n_pad). */
+int mxl_kv_zero_pad(void* qkv, const int* n_pad, int B, int T, int d, void* stream);
 /* positional term of a decode step for the whole batch: bd[b][h][r] = sum_e qr[b][h*dh + e] * rd[r][h*dh + e], r < M.
  * qr (B <= 64, ld_qr) bf16 = q + r_r_bias (mxl_decode_qkv / mxl_kv_append), rd (M, ld_rd) bf16 = r_net(pos_emb) of the layer
  * (rows = distances), bd (B, H, M) f32.  dh = 64.  Replaces the `BD = einsum("ibnd,jnd->ijbn", rr_head_q, r_head_k)` of

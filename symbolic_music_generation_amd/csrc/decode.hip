@@ -73,6 +73,19 @@ __global__ void kv_fill_kernel(const bf16_t* qkv, bf16_t* kc, bf16_t* vc, int B,
     *reinterpret_cast<u32x4*>(vc + o) = *reinterpret_cast<const u32x4*>(row + 2 * d + c * 8);
 }
 
+// left-padded prompt pass: k = v = 0 in rows j < n_pad[b] of a (B, T, 3d) qkv buffer, i.e. every pad column becomes one more
+// zero-memory slot (qkv_net has no bias, so a zero mem projects to k = v = 0).  Columns [d, 3d) only; queries are left alone.
+// grid (ceil(T * 2d/8 / 256), B): one thread per 8 elements, n_pad read on the device (no host sync, capture-safe)
+__global__ void kv_zero_pad_kernel(bf16_t* qkv, const int* n_pad, int T, int d) {
+    const int chunks = (2 * d) >> 3;
+    const int b = blockIdx.y;
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)T * chunks) return;
+    const int j = (int)(gid / chunks), c = (int)(gid % chunks);
+    if (j >= n_pad[b]) return;                          // not a pad row
+    *reinterpret_cast<u32x4*>(qkv + ((size_t)b * T + j) * 3 * d + d + c * 8) = u32x4{0u, 0u, 0u, 0u};
+}
+
 // one workgroup per (head, batch row, ring piece); dh = 8 * LPK, LPK lanes share one key row, 64/LPK keys per wave instruction.
 // gridDim.z = NS pieces of the ring (round 5).  A CU streams HBM at ~24 GB/s however many workgroups it holds, so a launch of
 // B * H workgroups that is not a multiple of the CU count is as slow as its fullest CU: 384 rings (a lane's 32 sequences x 12
@@ -612,6 +625,16 @@ extern "C" int mxl_kv_fill(const void* qkv, void* kcache, void* vcache, int B, i
     const long long n = (long long)B * (T < M ? T : M) * (d / 8);
     hipLaunchKernelGGL(kv_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)qkv, (bf16_t*)kcache, (bf16_t*)vcache, B, T, M, d, dh);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_kv_zero_pad(void* qkv, const int* n_pad, int B, int T, int d, void* stream) {
+    MXL_CHECK_ARG(qkv && n_pad && B > 0 && B <= 65535 && T > 0 && d > 0 && (d % 8) == 0);
+    MXL_CHECK_ARG(((uintptr_t)qkv % 16) == 0);
+    const long long n = (long long)T * (2 * d / 8);
+    hipLaunchKernelGGL(kv_zero_pad_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                       (bf16_t*)qkv, n_pad, T, d);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }

@@ -79,9 +79,12 @@ class XLDecoder:
         self.graph = None
 
     # ---------------------------------------------------------------- prompt
-    def prefill(self, prompt: torch.Tensor, sampling: dict):
+    def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None):
         """Whole prompt through the training-shape kernels with zero mems (upstream first step), rings filled from the
-        per-layer qkv buffers, first new token sampled from the last position."""
+        per-layer qkv buffers, first new token sampled from the last position.
+        n_pad: (B,) int32 device tensor, left-padded prompts: the first n_pad[b] columns of row b are pads.  Their K / V are zero
+        in every layer (= extra zero-memory slots, so each row computes what it computes alone), they are embedded as id 0 and
+        held as -1 in `ids`, which the samplers' repetition penalty skips."""
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
@@ -90,12 +93,18 @@ class XLDecoder:
             k.zero_()
         self.ids.zero_()
         self.ids[:, :Tp].copy_(prompt)
+        x = prompt.to(e.dev)
+        if n_pad is not None:
+            n_pad = n_pad.to(e.dev, torch.int32).contiguous()
+            pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
+            self.ids[:, :Tp].masked_fill_(pad, -1)
+            x = x.masked_fill(pad, 0)
         sink_kc, sink_vc = self.kc, self.vc
 
         def kv_sink(l, qkv):
             ops.kv_fill(qkv, sink_kc[l], sink_vc[l], Tp)
 
-        out = e.forward(prompt.to(e.dev), mems=None, labels=None, train=False, want_logprobs=False, kv_sink=kv_sink)
+        out = e.forward(x, mems=None, labels=None, train=False, want_logprobs=False, kv_sink=kv_sink, n_pad=n_pad)
         ws = e._last
         N = B * Tp
         # log-probs of the last prompt position only
@@ -220,17 +229,22 @@ class XLDecoder:
             self.trace.index_copy_(1, self.t_dev.to(torch.int64), self.logp.unsqueeze(1))
 
     # ---------------------------------------------------------------- loop
-    def begin(self, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool = True) -> int:
+    def begin(self, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool = True,
+              n_pad: Optional[torch.Tensor] = None) -> int:
         """prompt pass + first sampled token + (use_graph) capture of one decode step; returns the number of `replay_once()`
-        calls that complete the generation to max_length"""
+        calls that complete the generation to max_length.  n_pad: left-padded prompts (prefill); the decode step is the same,
+        every row's last prompt token sits at column Tp - 1"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         self._sampling = sampling
         self._use_graph = use_graph
-        self.prefill(prompt, sampling)
+        self.prefill(prompt, sampling, n_pad)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
-            key = tuple(sorted(sampling.items()))
+            # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
+            # itself is written by the captured launches): a graph captured without a trace would replay without writing one
+            key = (tuple(sorted(sampling.items())), self.fused_sampler,
+                   None if self.trace is None else self.trace.data_ptr())
             if self.graph is None or self._graph_key != key:
                 # warm-up on a side stream (first launches set function attributes), then capture one step
                 state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(),
@@ -262,18 +276,22 @@ class XLDecoder:
 
     def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
-                 typical_p: Optional[float] = None, use_graph: bool = True) -> torch.Tensor:
+                 typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
-        [OMIT]) decoding runs to max_length."""
+        [OMIT]) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (prefill); the
+        prompt columns, pads included, come back as given."""
         sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0,
                         temperature=temperature, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
                         typical_p=1.0 if typical_p is None else typical_p)
         Tp = prompt.shape[1]
         if max_length - Tp <= 0:
             return prompt[:, :max_length]
-        for _ in range(self.begin(prompt, max_length, sampling, use_graph)):
+        for _ in range(self.begin(prompt, max_length, sampling, use_graph, n_pad)):
             self.replay_once()
-        return self.ids[:, :max_length].clone()
+        out = self.ids[:, :max_length].clone()
+        if n_pad is not None:
+            out[:, :Tp].copy_(prompt)
+        return out
 
 
 class XLDecoderLanes:
@@ -296,8 +314,9 @@ class XLDecoderLanes:
         for d in self.lanes:
             d.invalidate_tables()
 
-    def begin(self, prompt, max_length, sampling, use_graph=True) -> int:
-        steps = [d.begin(prompt[self.offs[i]:self.offs[i + 1]], max_length, sampling, use_graph) for i, d in enumerate(self.lanes)]
+    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None) -> int:
+        steps = [d.begin(prompt[self.offs[i]:self.offs[i + 1]], max_length, sampling, use_graph,
+                         None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]]) for i, d in enumerate(self.lanes)]
         for s in self.streams:                       # the lanes start from the prompt passes and captures issued above
             s.wait_stream(torch.cuda.current_stream())
         return steps[0]
@@ -312,16 +331,19 @@ class XLDecoderLanes:
             torch.cuda.current_stream().wait_stream(s)
 
     def generate(self, prompt, max_length, do_sample=False, top_k=None, top_p=None, temperature=1.0, repetition_penalty=None,
-                 typical_p=None, use_graph=True) -> torch.Tensor:
+                 typical_p=None, use_graph=True, n_pad=None) -> torch.Tensor:
         sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0,
                         temperature=temperature, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
                         typical_p=1.0 if typical_p is None else typical_p)
         if max_length - prompt.shape[1] <= 0:
             return prompt[:, :max_length]
-        for _ in range(self.begin(prompt, max_length, sampling, use_graph)):
+        for _ in range(self.begin(prompt, max_length, sampling, use_graph, n_pad)):
             self.replay_once()
         self.join()
-        return torch.cat([d.ids[:, :max_length] for d in self.lanes], 0)
+        out = torch.cat([d.ids[:, :max_length] for d in self.lanes], 0)
+        if n_pad is not None:
+            out[:, :prompt.shape[1]].copy_(prompt)
+        return out
 
 
 class _BeamHyps:
@@ -666,3 +688,52 @@ def truncate_first_n_bar(ids: torch.Tensor, sob_token_id: int, n_bar: int = 8) -
     if cut < 0:
         raise MusicXLError(f'the sequence has fewer than {n_bar + 1} bars')     # the reference raises IndexError here
     return torch.cat([ids[:cut], ids.new_tensor([sob_token_id])])
+
+
+# -------------------------------------------------------------------- left-padded batches of prompts of different lengths
+def left_pad(prompts, pad_token_id: int):
+    """Prompts of different lengths (a list of 1-D id tensors, e.g. `truncate_first_n_bar` outputs) -> (input_ids, attention_mask),
+    both (B, Tp) int64 with Tp the longest prompt: row b holds Tp - len(prompts[b]) columns of pad_token_id on the left, then the
+    prompt; the mask is 0 on the pads and 1 on the prompt (the HF decoder-only layout `model.generate(attention_mask=...)` takes)."""
+    if not len(prompts):
+        raise MusicXLError('left_pad needs at least one prompt')
+    if any(p.dim() != 1 or p.numel() == 0 for p in prompts):
+        raise MusicXLError('left_pad takes non-empty 1-D id tensors')
+    Tp = max(p.numel() for p in prompts)
+    dev = prompts[0].device
+    ids = torch.full((len(prompts), Tp), int(pad_token_id), dtype=torch.int64, device=dev)
+    mask = torch.zeros(len(prompts), Tp, dtype=torch.int64, device=dev)
+    for b, p in enumerate(prompts):
+        ids[b, Tp - p.numel():] = p.to(dev, torch.int64)
+        mask[b, Tp - p.numel():] = 1
+    return ids, mask
+
+
+def strip_left_pad(ids: torch.Tensor, attention_mask: torch.Tensor):
+    """Inverse of `left_pad` on a generated batch: (B, L) ids and the (B, Tp) prompt mask -> list of B 1-D tensors, row b without
+    its left pad columns (prompt + continuation, e.g. for `truncate_last_bar` per row)"""
+    n_pad = left_pad_counts(attention_mask, (ids.shape[0], attention_mask.shape[1]))
+    return [ids[b, s:] for b, s in enumerate(n_pad)]
+
+
+def left_pad_counts(attention_mask: torch.Tensor, shape) -> list:
+    """Checks a (B, Tp) attention mask on the host and returns the number of left pad columns of every row.  The mask must hold
+    0 / 1 only, and every row must be zeros then ones (left padding) with at least one 1: the prompt's last token is the column
+    generation continues from."""
+    B, Tp = shape
+    m = torch.as_tensor(attention_mask).detach().cpu()
+    if tuple(m.shape) != (B, Tp):
+        raise MusicXLError(f'attention_mask has shape {tuple(m.shape)}, input_ids {(B, Tp)}')
+    if m.dtype == torch.bool:
+        m = m.to(torch.int64)
+    if not bool(((m == 0) | (m == 1)).all()):
+        raise MusicXLError('attention_mask must hold only 0 (pad) and 1 (token)')
+    m = m.to(torch.int64)
+    if not bool(m[:, -1].all()):
+        if bool((m.sum(1) == 0).any()):
+            raise MusicXLError('attention_mask has a row without any token')
+        raise MusicXLError('right-padding was detected in attention_mask: this decoder-only model generates from left-padded '
+                           "prompts only (padding_side='left'; generate.left_pad)")
+    if bool((m[:, 1:] < m[:, :-1]).any()):
+        raise MusicXLError('attention_mask rows must be zeros (left padding) then ones; a pad column inside a prompt is not supported')
+    return (Tp - m.sum(1)).tolist()

@@ -580,6 +580,16 @@ def kv_fill(qkv, kc, vc, T):
     check(lib().mxl_kv_fill(_p(qkv), _p(kc), _p(vc), B, T, M, H * dh, dh, _stream()), 'mxl_kv_fill')
 
 
+def kv_zero_pad(qkv, n_pad, B, T, d):
+    """left-padded prompt pass: k = v = 0 in the first n_pad[b] rows of every sequence of the (B, T, 3d) bf16 qkv buffer.
+    n_pad: (B,) int32 on the device"""
+    _req(qkv, torch.bfloat16, 'kv_zero_pad qkv')
+    _req(n_pad, torch.int32, 'kv_zero_pad n_pad')
+    if not qkv.is_contiguous() or qkv.numel() != B * T * 3 * d or n_pad.numel() != B or not n_pad.is_contiguous():
+        raise MusicXLError(f'kv_zero_pad: expected a contiguous ({B}, {T}, {3 * d}) qkv buffer and ({B},) n_pad')
+    check(lib().mxl_kv_zero_pad(_p(qkv), _p(n_pad), B, T, d, _stream()), 'mxl_kv_zero_pad')
+
+
 def decode_ring_pieces(B: int, H: int, M: int) -> int:
     """workgroups per (sequence, head) ring of a decode step (mxl_relattn_decode_split).  With fewer rings than CUs a ring per
     workgroup leaves CUs idle and every workgroup streaming 512 KB alone: two pieces up to 256 rings, four up to 96 (measured on

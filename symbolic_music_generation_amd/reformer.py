@@ -8,6 +8,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
+from ._lib import MusicXLError
 from .module import EngineModule
 from .rf_engine import RFEngine
 
@@ -159,6 +160,12 @@ class MyReformerModelWithLMHead(EngineModule):
         use_cache=False: every step is a full forward over the tokens so far, right-padded to a multiple of the chunk length
         (pads sit after every real token, so the causal mask keeps them out), with the rotations redrawn each forward."""
         from . import ops
+        from .generate import left_pad_counts
+        mask = unsupported.pop('attention_mask', None)
+        if mask is not None and input_ids is not None and any(left_pad_counts(mask, tuple(input_ids.shape))):
+            # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
+            raise MusicXLError(f'{type(self).__name__}.generate does not support padded prompts (attention_mask with zeros); '
+                               'generate prompts of different lengths one length at a time')
         top_k = getattr(self.config, 'top_k', 50) if top_k is None else top_k        # HF fills it from the config: default 50
         if unsupported.get('penalty_alpha') and not do_sample and top_k is not None and top_k > 1:
             # HF 4.25.1 contrastive_search takes `past_buckets_states` as its cache and indexes past[0][0].shape: the bucket entry

@@ -13,6 +13,7 @@ from typing import Any, Dict, List, Optional
 
 import torch
 
+from ._lib import MusicXLError
 from .module import EngineModule
 from .xl_engine import XLEngine
 
@@ -195,19 +196,36 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: float = 1.0, num_beams: int = 1,
                  penalty_alpha=None, typical_p=None, repetition_penalty=None, early_stopping=None,
                  renormalize_logits=None, num_return_sequences: int = 1, num_beam_groups: int = 1, length_penalty: float = 1.0,
-                 use_graph: bool = True, seed: int = 77, **unused) -> torch.Tensor:
+                 use_graph: bool = True, seed: int = 77, attention_mask: Optional[torch.Tensor] = None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
-        `penalty_alpha > 0`, `top_k > 1`, `do_sample` false and one beam; group beam search when `num_beam_groups > 1`."""
-        from .generate import XLDecoder, XLDecoderLanes, beam_search, contrastive_search, group_beam_search
+        `penalty_alpha > 0`, `top_k > 1`, `do_sample` false and one beam; group beam search when `num_beam_groups > 1`.
+
+        `attention_mask` (B, Tp) in HF's decoder-only layout: prompts of different lengths left-padded to one width (0 on the pad
+        columns, then 1 on the prompt; `generate.left_pad` builds it).  Greedy and sampling decode every row as if it were alone:
+        row b without its pad columns equals `generate(input_ids=ids[b:b+1, s_b:], max_length=max_length - s_b)` (DESIGN.md,
+        ragged prompts).  The output keeps the input columns as given, pad ids included.  Beam, group-beam and contrastive
+        search take no padded mask."""
+        from .generate import XLDecoder, XLDecoderLanes, beam_search, contrastive_search, group_beam_search, left_pad_counts
+        n_pad = None
+        if attention_mask is not None:
+            pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
+            if any(pads):
+                n_pad = torch.tensor(pads, dtype=torch.int32)
         # HF 4.25.1 fills unspecified generation arguments from the model config; PretrainedConfig's default top_k is 50, so
         # `generate(do_sample=True)` without top_k samples from the 50 best tokens (the reference relies on these defaults)
         top_k = getattr(self.config, 'top_k', 50) if top_k is None else top_k
         diversity_penalty = unused.pop('diversity_penalty', None)
         self._maybe_resync()
         max_length = max_length or self.config.max_length_
-        if penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and not do_sample and num_beams == 1:
+        contrastive = penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and not do_sample and num_beams == 1
+        if n_pad is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
+            raise MusicXLError('padded prompts (attention_mask with zeros) are supported for greedy decoding and sampling only, not '
+                               'for beam, group-beam or contrastive search')
+        if n_pad is not None and (unused.get('max_new_tokens') is not None or unused.get('stopping_criteria') is not None):
+            raise MusicXLError('padded prompts run every row to max_length: max_new_tokens and per-row stopping are not supported')
+        if contrastive:
             dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
                                       eos_token_id=self.config.eos_token_id, pad_token_id=self.config.pad_token_id)
@@ -234,6 +252,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
             if not do_sample:
                 raise ValueError('num_return_sequences has to be 1 when doing greedy search')       # HF's message
             input_ids = input_ids.repeat_interleave(num_return_sequences, 0)
+            if n_pad is not None:
+                n_pad = n_pad.repeat_interleave(num_return_sequences, 0)
         B = input_ids.shape[0]
         dec = getattr(self, '_decoder', None)
         # two free-running half-batch lanes from 32 rows on (generate.XLDecoderLanes); MXL_DECODE_LANES=1 keeps one decoder
@@ -244,4 +264,4 @@ class MyTransfoXLLMHeadModel(EngineModule):
         dec.invalidate_tables()
         return dec.generate(input_ids.to(self.device), max_length, do_sample=do_sample, top_k=top_k, top_p=top_p,
                             temperature=temperature, repetition_penalty=repetition_penalty, typical_p=typical_p,
-                            use_graph=use_graph)
+                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device))

@@ -217,18 +217,40 @@ class MusicTokenizer:
             toks = [t for t in toks if t != self.pad_token]
         return ' '.join(toks)
 
-    def __call__(self, text, padding=False, truncation=False, max_length: Optional[int] = None, return_tensors=None):
+    def __call__(self, text, padding=False, truncation=False, max_length: Optional[int] = None, return_tensors=None,
+                 return_attention_mask: Optional[bool] = None):
+        """HF tokenizer call.  Pads go on `self.padding_side` ('right' by default, as in the reference; 'left' for batched
+        generation from prompts of different lengths).  return_attention_mask=True adds `attention_mask`: 1 on tokens, 0 on pads
+        (by default none is returned: model_input_names holds input_ids only)."""
         texts = [text] if isinstance(text, str) else list(text)
         enc = [self.encode(t) for t in texts]
         max_length = max_length or self.model_max_length
         if truncation:
             enc = [e[:max_length] for e in enc]
+        if self.padding_side not in ('right', 'left'):
+            raise ValueError(f"padding_side must be 'right' or 'left', got {self.padding_side!r}")
+        width = None
         if padding == 'max_length':
-            enc = [e + [self.pad_token_id] * (max_length - len(e)) for e in enc]
+            width = max_length
         elif padding in (True, 'longest'):
-            m = max(len(e) for e in enc)
-            enc = [e + [self.pad_token_id] * (m - len(e)) for e in enc]
+            width = max(len(e) for e in enc)
+        n_tok = [len(e) for e in enc]
+        if width is not None:
+            if self.padding_side == 'left':
+                enc = [[self.pad_token_id] * (width - len(e)) + e for e in enc]
+            else:
+                enc = [e + [self.pad_token_id] * (width - len(e)) for e in enc]
+        mask = None
+        if return_attention_mask:
+            mask = [([0] * (len(e) - n) + [1] * n) if self.padding_side == 'left' else ([1] * n + [0] * (len(e) - n))
+                    for e, n in zip(enc, n_tok)]
         if return_tensors == 'pt':
             import torch
-            return {'input_ids': torch.tensor(enc, dtype=torch.long)}
-        return {'input_ids': enc[0] if isinstance(text, str) else enc}
+            out = {'input_ids': torch.tensor(enc, dtype=torch.long)}
+            if mask is not None:
+                out['attention_mask'] = torch.tensor(mask, dtype=torch.long)
+            return out
+        out = {'input_ids': enc[0] if isinstance(text, str) else enc}
+        if mask is not None:
+            out['attention_mask'] = mask[0] if isinstance(text, str) else mask
+        return out

@@ -284,11 +284,17 @@ class XLEngine:
         return 8 + 8 * l + k
 
     def forward(self, input_ids: torch.Tensor, mems: Optional[Sequence[torch.Tensor]] = None,
-                labels: Optional[torch.Tensor] = None, train: bool = False, want_logprobs: bool = True, kv_sink=None):
+                labels: Optional[torch.Tensor] = None, train: bool = False, want_logprobs: bool = True, kv_sink=None,
+                n_pad: Optional[torch.Tensor] = None):
         """input_ids (B, T) int64 on device; mems: list of L tensors (B, M, d) bf16 (batch-major) or None (= zero mems).
-        Returns dict(loss, losses, logprobs, mems).  In train mode activations are kept for `backward()`."""
+        Returns dict(loss, losses, logprobs, mems).  In train mode activations are kept for `backward()`.
+        n_pad: (B,) int32 device tensor for left-padded prompts (eval, zero mems only): the first n_pad[b] columns of row b are
+        pads, their K / V are zeroed in every layer so that each one is one more zero-memory slot (DESIGN.md, ragged prompts);
+        the outputs at pad columns are computed and meaningless."""
         c = self.cfg
         B, T = input_ids.shape
+        if n_pad is not None and (train or mems is not None):
+            raise MusicXLError('n_pad (left-padded prompts) is only supported for an eval forward from zero mems')
         d, H, dh, L, M, Fi = c.d_model, c.n_head, c.d_head, c.n_layer, c.mem_len, c.d_inner
         V, cut = c.vocab_size, tuple(c.cutoffs)
         N = B * T
@@ -328,6 +334,8 @@ class XLEngine:
                     new_mems.append(nm)
             qkv = ws.qkv[s]
             ops.gemm(x_qkv, self._lw(l, 'dec_attn.qkv_net.weight'), qkv.view(B * Kc, 3 * d), B * Kc, 3 * d, d)
+            if n_pad is not None:
+                ops.kv_zero_pad(qkv, n_pad, B, T, d)
             if kv_sink is not None:
                 kv_sink(l, qkv)   # decode prefill: projected K/V rows go to the per-layer rings
             ops.gemm(ws.phi, self._lw(l, 'dec_attn.r_net.weight'), ws.rd[s], M, d, d)
