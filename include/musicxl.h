@@ -402,6 +402,12 @@ size_t mxl_relattn_decode_split_ws_bytes(int B, int H, int dh, int pieces);
 int mxl_relattn_decode_split(const void* qkv, const void* kcache, const void* vcache, const float* bd, const float* r_w_bias,
                              void* out, const int* t_dev, int B, int H, int dh, int M, float scale, int pieces, float* ws,
                              int* arrived, void* stream);
+/* mxl_relattn_decode_split with per-row stop state: unfinished (B,) int32 on the device, 0 = the row is finished (eos emitted).
+ * A finished row's workgroups read no K / V and leave zeros in its output slice (B, H*dh); live rows are bit-identical to
+ * mxl_relattn_decode_split.  unfinished = NULL: every row is live. */
+int mxl_relattn_decode_split_live(const void* qkv, const void* kcache, const void* vcache, const float* bd, const float* r_w_bias,
+                                  void* out, const int* t_dev, int B, int H, int dh, int M, float scale, int pieces, float* ws,
+                                  int* arrived, const int* unfinished, void* stream);
 /* next token from log-probs (B, ldl): repetition penalty over the ids already in the row (positions 0..*t_dev; HF's
  * RepetitionPenaltyLogitsProcessor, 1.0 = off), then greedy argmax (do_sample=0) or temperature -> top-k -> top-p ->
  * typical-p (HF's TypicalLogitsWarper, 1.0 = off) -> renormalise -> multinomial (do_sample=1), as HF's logits warpers with
@@ -429,6 +435,22 @@ int mxl_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, 
                     unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                     float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale, int* counter,
                     void* stream);
+/* Stopping at eos (HF greedy_search / sample with an eos_token_id), for generation.  State on the device: unfinished (B,) int32
+ * (1 = live; set to 1 before the first sampled token) and alive, one int32 = the number of live rows after the launch.
+ * Per row: next = live ? token : pad_id, then live &= (next != eos_id).  min_length (HF MinLengthLogitsProcessor, after the
+ * repetition penalty): the score of eos_id is -inf while the row (columns 0..*t_dev) is shorter than min_length; 0 = off.
+ * mxl_sample_step_stop: mxl_sample_step plus that state in the same launch (B <= 32767); the last workgroup to finish writes
+ * *alive.  The embedding row written is that of the token after the rule (pad for a finished row). */
+int mxl_sample_step_stop(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                         unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                         float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale, int* counter,
+                         int eos_id, int pad_id, int min_length, int* unfinished, int* alive, void* stream);
+/* The same state for mxl_sample / mxl_sample_large: mxl_decode_stop runs after the sampler and mxl_decode_advance (the token just
+ * written is ids[b][*t_dev]) and applies the rule to it; mxl_mask_eos_below runs before the sampler and sets
+ * scores[b][eos_id] = -inf for every row while *t_dev + 1 < min_length (no launch when min_length <= 0). */
+int mxl_decode_stop(void* ids, int ld_ids, const int* t_dev, int B, int eos_id, int pad_id, int* unfinished, int* alive,
+                    void* stream);
+int mxl_mask_eos_below(float* scores, int ldl, int B, int V, int eos_id, int min_length, const int* t_dev, void* stream);
 /* Contrastive search (the reference's 'contrastive' strategy, musicnlp/trainer/eval.py:296-302, over the mems patch of
  * musicnlp/models/transformer_xl.py:229-234; HF 4.25.1 GenerationMixin.contrastive_search with `_ranking_fast`):
  *   score[b*K + k] = (1 - alpha) * probs[b*K + k] - alpha * max_{s < S} cos(hid[b*K + k], ctx[b][s]);  sel[b] = argmax_k score

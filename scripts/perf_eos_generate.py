@@ -1,0 +1,93 @@
+"""What stopping at eos buys at the C5 model shape (12L/768d, M = 2048, V = 1190): 64 prompts of 256 tokens generated to
+max_length 2048 with top_k = 8, through model.generate (two decode lanes).
+
+  (a) no eos: every row runs to 2048 (today's loop)
+  (b) eos_token_id = an id whose first generated occurrences spread over the rows (of the ids every row emits in (a), the one
+      whose median first-occurrence column is nearest the middle of the generation); the same seed gives the same tokens up to
+      each row's eos, so (b) == generate.finish_at_eos((a)) -- checked
+
+Reports the wall time of both calls, the live row-steps of (b) as a fraction of all row-steps issued, and the ms per decode step
+of one decoder (64 rows) with every row live and with every row finished (ring attention skipped).
+
+    python3 scripts/perf_eos_generate.py                 # env: SEED (77)
+    python3 scripts/perf_eos_generate.py --finished-only  # only the all-finished steps: for rocprofv3 --kernel-trace --stats
+"""
+import os
+import sys
+import time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from symbolic_music_generation_amd.transformer_xl import MyTransfoXLConfig, MyTransfoXLLMHeadModel
+from symbolic_music_generation_amd.generate import XLDecoder, finish_at_eos
+
+dev = torch.device('cuda:0')
+V, M, B, Tp, L = 1190, 2048, 64, 256, 2048
+SEED = int(os.environ.get('SEED', 77))
+FINISHED_ONLY = '--finished-only' in sys.argv
+cfg = MyTransfoXLConfig('base', max_length=L, vocab_size=V, mem_len=M, cutoffs=[])
+model = MyTransfoXLLMHeadModel(cfg, device=dev, seed=77).eval()
+g = torch.Generator().manual_seed(SEED)
+ids = torch.randint(4, V, (B, Tp), generator=g).to(dev)
+kw = dict(do_sample=True, top_k=8)
+samp = dict(do_sample=True, top_k=8, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def step_ms(live: bool, n: int = 200) -> float:
+    """ms per replayed decode step of one 64-row decoder with the stop state on, right after the prompt pass (ring slots
+    Tp .. Tp + n), every row live or every row finished"""
+    dec = XLDecoder(model.engine, B, L, seed=5)
+    steps = dec.begin(ids, L, samp, use_graph=True, stop=(V + 1, 0, 0))    # an eos no row can emit
+    assert steps >= n
+    if not live:
+        dec.unfinished.zero_()
+        dec.alive.zero_()
+    for _ in range(10):
+        dec.replay_once()
+    t, _ = timed(lambda: [dec.replay_once() for _ in range(n)])
+    return 1e3 * t / n
+
+
+with torch.no_grad():
+    if FINISHED_ONLY:
+        print(f'all-finished decode step, 64 rows: {step_ms(False, 400):.3f} ms', flush=True)
+        sys.exit(0)
+    model.generate(input_ids=ids, max_length=Tp + 16, **kw)                 # warm-up: library attributes, workspaces
+    model._decoder = None
+    t_a, full = timed(lambda: model.generate(input_ids=ids, max_length=L, **kw))
+    gen = full[:, Tp:].cpu()
+    first = {}
+    for tok in torch.unique(gen).tolist():
+        hit = gen == tok
+        if bool(hit.any(1).all()):
+            first[tok] = hit.int().argmax(1)
+    mid = (L - Tp) / 2
+    eos = min(first, key=lambda tok: abs(float(first[tok].float().median()) - mid))
+    cols = first[eos]
+    print(f'64 prompts x {Tp}, max_length {L}, top_k 8; {len(first)} ids are emitted by every row; eos = {eos}: first generated '
+          f'occurrence per row at steps {int(cols.min())}..{int(cols.max())} (median {float(cols.float().median()):.0f}) of '
+          f'{L - Tp}', flush=True)
+    model._decoder = None
+    model.generate(input_ids=ids, max_length=Tp + 16, eos_token_id=eos, **kw)    # warm-up of the stop graph
+    model._decoder = None
+    t_b, out = timed(lambda: model.generate(input_ids=ids, max_length=L, eos_token_id=eos, **kw))
+    ok = torch.equal(out, finish_at_eos(full, Tp, eos, eos))
+    issued = max(d.steps_run for d in model._decoder.lanes)
+    live = int((cols + 1).sum())                   # row b is live for the steps up to and including its eos
+    all_steps = B * (issued + 1)                   # the prompt pass's token + the replayed steps
+    print(f'(a) no eos:   {t_a:.3f} s, width {full.shape[1]}, {L - Tp - 1} steps', flush=True)
+    print(f'(b) eos {eos}:  {t_b:.3f} s, width {out.shape[1]}, steps issued per lane '
+          f'{[d.steps_run for d in model._decoder.lanes]}; equals finish_at_eos((a)): {ok}', flush=True)
+    print(f'live row-steps {live} of {all_steps} issued = {100 * live / all_steps:.1f} %; (b) / (a) wall time = '
+          f'{t_b / t_a:.3f}', flush=True)
+    model._decoder = None
+    ms_live, ms_fin = step_ms(True), step_ms(False)
+    print(f'one decoder of 64 rows, ring slots {Tp}..{Tp + 200}: {ms_live:.3f} ms per step with every row live, '
+          f'{ms_fin:.3f} ms with every row finished', flush=True)

@@ -97,7 +97,7 @@ template <int DH>
 __global__ __launch_bounds__(256) void decode_attn_kernel(const bf16_t* qkv, const bf16_t* kc, const bf16_t* vc,
                                                           const float* bd, const float* rwb,
                                                           bf16_t* out, const int* t_dev, int B, int H, int M, float scale,
-                                                          float* ws, int* arrived) {
+                                                          float* ws, int* arrived, const int* live) {
     constexpr int LPK = DH / 8;          // lanes per key row
     constexpr int KPW = 64 / LPK;        // keys per wave per iteration
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -108,6 +108,13 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(const bf16_t* qkv, con
     const int tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
     const int c8 = lane % LPK, ksub = lane / LPK;
     const int d = H * DH;
+    // a finished row (live[b] == 0, mxl_relattn_decode_split_live): no K / V byte is read; piece 0 leaves zeros in the output slice
+    // so that the GEMMs after it never see an uninitialised row, and the other pieces leave at once (the arrival counter of the
+    // (sequence, head) is not touched: it stays zero)
+    if (live != nullptr && live[b] == 0) {
+        if (blockIdx.z == 0 && tid < DH) out[(size_t)b * d + h * DH + tid] = f2bf(0.f);
+        return;
+    }
     const int t = *t_dev;
     const int tm = t % M;
     // ring slots that have never been written (t < M - 1: the sequence is shorter than the memory) are HF's zero-initialised
@@ -356,7 +363,8 @@ constexpr int SORT_N = 2048;
 __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, const long long* ids, int ld_ids,
                                           const int* t_dev, const unsigned long long* rng_ctr, unsigned long long seed,
                                           int do_sample, int top_k, float top_p, float temperature,
-                                          float repetition_penalty, float typical_p, float* out_probs) {
+                                          float repetition_penalty, float typical_p, float* out_probs, int eos_id = -1,
+                                          int min_length = 0) {
     __shared__ float key[SORT_N];
     __shared__ int idx[SORT_N];
     __shared__ int sh_pick;
@@ -381,6 +389,12 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
                 key[tok] = (v < 0.f ? v * repetition_penalty : v / repetition_penalty) * invt;
             }
         }
+        __syncthreads();
+    }
+    if (min_length > 0 && eos_id >= 0 && eos_id < V) {
+        // HF MinLengthLogitsProcessor (after the repetition penalty, before the warpers): eos is barred while the row is
+        // shorter than min_length -- the row holds columns 0..t, t + 1 of them
+        if (tid == 0 && *t_dev + 1 < min_length) key[eos_id] = -INFINITY;
         __syncthreads();
     }
     // Small supports (greedy, or top-k <= 64) need only the first few entries of the sorted order: take them by repeated
@@ -567,10 +581,26 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
                                                           int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                           int do_sample, int top_k, float top_p, float temperature,
                                                           float repetition_penalty, float typical_p, const bf16_t* E, bf16_t* emb_out,
-                                                          int d, float scale, int* counter) {
-    const int tok = sample_row(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
-                               repetition_penalty, typical_p, nullptr);
+                                                          int d, float scale, int* counter, int eos_id, int pad_id,
+                                                          int min_length, int* unfinished, int* alive) {
+    int tok = sample_row(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
+                         repetition_penalty, typical_p, nullptr, unfinished ? eos_id : -1, unfinished ? min_length : 0);
     const int b = blockIdx.x, tid = threadIdx.x;
+    __shared__ int sh_tok, sh_live;
+    if (unfinished) {
+        // stop state (HF greedy_search / sample): a finished row emits pad; a live row that emits eos is finished from now on
+        if (tid == 0) {
+            int live = unfinished[b];
+            int tk = tok;
+            if (!live) tk = pad_id;
+            else if (tk == eos_id) live = 0;
+            unfinished[b] = live;
+            sh_tok = tk;
+            sh_live = live;
+        }
+        __syncthreads();
+        tok = sh_tok;
+    }
     if (tid == 0) ids[(size_t)b * ld_ids + *t_dev + 1] = tok;
     const int id = (tok < 0 || tok >= V) ? 0 : tok;
     for (int c = tid; c < (d >> 3); c += 256) {
@@ -582,7 +612,17 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         *reinterpret_cast<u32x4*>(emb_out + (size_t)b * d + c * 8) = o;
     }
     __syncthreads();                            // every thread of the workgroup is past its reads of *t_dev / *rng_ctr
-    if (tid == 0) {
+    if (tid == 0 && unfinished) {
+        // arrival and the row's live bit in one atomic word (arrivals in bits 0-15, live rows from bit 16): the last arrival
+        // takes the number of live rows from the value it gets back, no other memory is read across workgroups
+        const int old = __hip_atomic_fetch_add(counter, 1 + (sh_live << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((old & 0xffff) == (int)gridDim.x - 1) {
+            __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            *alive = (old >> 16) + sh_live;
+            *t_dev += 1;
+            *rng_ctr += 1;
+        }
+    } else if (tid == 0) {
         const int old = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (old == (int)gridDim.x - 1) {
             __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -595,6 +635,36 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
 __global__ void advance_kernel(int* t_dev, unsigned long long* rng_ctr) {
     *t_dev += 1;
     *rng_ctr += 1;
+}
+
+// stop state after mxl_sample / mxl_sample_large and the counter advance (the unfused and large-vocabulary paths): the token
+// just written sits at column *t_dev.  One workgroup walks the rows and writes the number of live rows to *alive.
+__global__ __launch_bounds__(256) void decode_stop_kernel(long long* ids, int ld_ids, const int* t_dev, int B, int eos_id,
+                                                          int pad_id, int* unfinished, int* alive) {
+    __shared__ int part[4];
+    const int tid = threadIdx.x;
+    const int t = *t_dev;
+    int n = 0;
+    for (int b = tid; b < B; b += 256) {
+        long long* p = ids + (size_t)b * ld_ids + t;
+        int live = unfinished[b];
+        if (!live) *p = pad_id;
+        else if (*p == eos_id) live = 0;
+        unfinished[b] = live;
+        n += live;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if ((tid & 63) == 0) part[tid >> 6] = n;
+    __syncthreads();
+    if (tid == 0) *alive = part[0] + part[1] + part[2] + part[3];
+}
+
+// min_length before mxl_sample / mxl_sample_large: eos barred while the rows (columns 0..*t_dev) are shorter than min_length
+__global__ __launch_bounds__(256) void mask_eos_below_kernel(float* scores, int ldl, int B, int eos_id, int min_length,
+                                                             const int* t_dev) {
+    if (*t_dev + 1 >= min_length) return;
+    for (int b = threadIdx.x; b < B; b += 256) scores[(size_t)b * ldl + eos_id] = -INFINITY;
 }
 
 }  // namespace
@@ -653,12 +723,12 @@ extern "C" int mxl_decode_bd(const void* qr, const void* rd, float* bd, int B, i
 
 static int relattn_decode_launch(const void* qkv, const void* kcache, const void* vcache, const float* bd, const float* r_w_bias,
                                  void* out, const int* t_dev, int B, int H, int dh, int M, float scale, int pieces, float* ws,
-                                 int* arrived, void* stream);
+                                 int* arrived, const int* live, void* stream);
 
 extern "C" int mxl_relattn_decode(const void* qkv, const void* kcache, const void* vcache, const float* bd,
                                   const float* r_w_bias, void* out, const int* t_dev, int B, int H,
                                   int dh, int M, float scale, void* stream) {
-    return relattn_decode_launch(qkv, kcache, vcache, bd, r_w_bias, out, t_dev, B, H, dh, M, scale, 1, nullptr, nullptr, stream);
+    return relattn_decode_launch(qkv, kcache, vcache, bd, r_w_bias, out, t_dev, B, H, dh, M, scale, 1, nullptr, nullptr, nullptr, stream);
 }
 
 extern "C" size_t mxl_relattn_decode_split_ws_bytes(int B, int H, int dh, int pieces) {
@@ -671,19 +741,29 @@ extern "C" int mxl_relattn_decode_split(const void* qkv, const void* kcache, con
                                         int pieces, float* ws, int* arrived, void* stream) {
     MXL_CHECK_ARG(pieces >= 1 && pieces <= 8);
     if (pieces > 1) MXL_CHECK_ARG(ws && arrived);
-    return relattn_decode_launch(qkv, kcache, vcache, bd, r_w_bias, out, t_dev, B, H, dh, M, scale, pieces, ws, arrived, stream);
+    return relattn_decode_launch(qkv, kcache, vcache, bd, r_w_bias, out, t_dev, B, H, dh, M, scale, pieces, ws, arrived, nullptr,
+                                 stream);
+}
+
+extern "C" int mxl_relattn_decode_split_live(const void* qkv, const void* kcache, const void* vcache, const float* bd,
+                                             const float* r_w_bias, void* out, const int* t_dev, int B, int H, int dh, int M,
+                                             float scale, int pieces, float* ws, int* arrived, const int* unfinished, void* stream) {
+    MXL_CHECK_ARG(pieces >= 1 && pieces <= 8);
+    if (pieces > 1) MXL_CHECK_ARG(ws && arrived);
+    return relattn_decode_launch(qkv, kcache, vcache, bd, r_w_bias, out, t_dev, B, H, dh, M, scale, pieces, ws, arrived, unfinished,
+                                 stream);
 }
 
 static int relattn_decode_launch(const void* qkv, const void* kcache, const void* vcache, const float* bd, const float* r_w_bias,
                                  void* out, const int* t_dev, int B, int H, int dh, int M, float scale, int pieces, float* ws,
-                                 int* arrived, void* stream) {
+                                 int* arrived, const int* live, void* stream) {
     MXL_CHECK_ARG(qkv && kcache && vcache && bd && r_w_bias && out && t_dev && B > 0 && H > 0 && M > 0);
     const size_t shm = (size_t)M * 4 + 4 * 64 * 4;
     MXL_CHECK_ARG(shm <= 64 * 1024);
     dim3 grid(H, B, pieces);
     hipStream_t s = (hipStream_t)stream;
 #define LAUNCH(DH) hipLaunchKernelGGL((decode_attn_kernel<DH>), grid, dim3(256), shm, s, (const bf16_t*)qkv, (const bf16_t*)kcache, \
-                                      (const bf16_t*)vcache, bd, r_w_bias, (bf16_t*)out, t_dev, B, H, M, scale, ws, arrived)
+                                      (const bf16_t*)vcache, bd, r_w_bias, (bf16_t*)out, t_dev, B, H, M, scale, ws, arrived, live)
     switch (dh) {
         case 16: LAUNCH(16); break;
         case 32: LAUNCH(32); break;
@@ -715,7 +795,40 @@ extern "C" int mxl_sample_step(const float* scores, int ldl, int V, void* ids, i
     MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
     hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
                        t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
-                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter);
+                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, -1, 0, 0, (int*)nullptr, (int*)nullptr);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_sample_step_stop(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev,
+                                    unsigned long long* rng_ctr, unsigned long long seed, int B, int do_sample, int top_k, float top_p,
+                                    float temperature, float repetition_penalty, float typical_p, const void* E, void* emb_out, int d,
+                                    float scale, int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive,
+                                    void* stream) {
+    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
+    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
+    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
+    MXL_CHECK_ARG(unfinished && alive && B <= 32767);          // arrivals and live rows share one 32-bit atomic word
+    hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
+                       t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
+                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id, min_length, unfinished, alive);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_decode_stop(void* ids, int ld_ids, const int* t_dev, int B, int eos_id, int pad_id, int* unfinished, int* alive,
+                               void* stream) {
+    MXL_CHECK_ARG(ids && t_dev && unfinished && alive && B > 0);
+    hipLaunchKernelGGL(decode_stop_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long long*)ids, ld_ids, t_dev, B, eos_id,
+                       pad_id, unfinished, alive);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_mask_eos_below(float* scores, int ldl, int B, int V, int eos_id, int min_length, const int* t_dev, void* stream) {
+    MXL_CHECK_ARG(scores && t_dev && B > 0 && V > 0 && ldl >= V);
+    if (min_length <= 0 || eos_id < 0 || eos_id >= V) return MXL_OK;         // nothing to bar
+    hipLaunchKernelGGL(mask_eos_below_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, eos_id, min_length, t_dev);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }

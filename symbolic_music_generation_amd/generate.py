@@ -14,12 +14,125 @@ TransfoXL (`mems`) nor Reformer (`past_buckets_states`) returns, so that strateg
 """
 import math
 import os
+from collections import deque
+from contextlib import nullcontext
 from typing import Optional
 
 import torch
 
 from . import ops
 from ._lib import MusicXLError
+
+
+STOP_CHUNK = 16          # decode steps per chunk between reads of the live-row count (run_until_finished)
+
+
+def stop_config(eos_token_id: Optional[int], pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
+                config_pad_token_id: Optional[int] = None) -> Optional[tuple]:
+    """(eos, pad, min_length) of a generation that stops at eos, or None when no eos is given: stopping is opt-in, an explicit
+    `eos_token_id=` argument.  pad: the argument, else the config's pad_token_id, else eos (HF 4.25.1).  min_length (HF
+    MinLengthLogitsProcessor) acts only together with an eos; 0 = off."""
+    if eos_token_id is None:
+        return None
+    eos = int(eos_token_id)
+    pad = pad_token_id if pad_token_id is not None else config_pad_token_id
+    pad = eos if pad is None else int(pad)
+    return eos, pad, max(int(min_length or 0), 0)
+
+
+def resolve_max_length(max_length: Optional[int], max_new_tokens: Optional[int], prompt_len: int, default: int) -> int:
+    """HF 4.25.1: max_new_tokens = n stands for max_length = prompt length + n; giving both raises ValueError"""
+    if max_new_tokens is not None:
+        if max_length is not None:
+            raise ValueError('Both `max_new_tokens` and `max_length` have been set but they serve the same purpose -- setting a '
+                             'limit to the generated output length. Remove one of those arguments.')
+        return int(prompt_len) + int(max_new_tokens)
+    return int(max_length or default)
+
+
+def finish_at_eos(ids: torch.Tensor, prompt_len: int, eos: int, pad: int) -> torch.Tensor:
+    """Host reference of stopping at eos, applied to the output of a run without it: in every row, each column after the first
+    GENERATED eos (column >= prompt_len) becomes pad; the result is cut to W = (last such eos column over the rows) + 1 when
+    every row has one, else kept whole.  Rows are independent and sampling draws per (seed, row, step), so a run with
+    eos_token_id returns exactly this (HF greedy_search / sample: next = next * unfinished + pad * (1 - unfinished))."""
+    out = ids.clone()
+    gen = out[:, prompt_len:]
+    if gen.shape[1] == 0:
+        return out
+    hit = gen == eos
+    has = hit.any(1)
+    first = torch.where(has, hit.int().argmax(1), torch.full_like(has, gen.shape[1], dtype=torch.int64))
+    col = torch.arange(gen.shape[1], device=ids.device)[None, :]
+    gen.masked_fill_(col > first[:, None], pad)
+    if bool(has.all()):
+        return out[:, :prompt_len + int(first.max()) + 1]
+    return out
+
+
+def stop_width(ids: torch.Tensor, unfinished: torch.Tensor, prompt_len: int, max_length: int, eos: int) -> int:
+    """returned width of a generation with stopping: max_length if a row is still live, else the last first-eos column + 1"""
+    if bool((unfinished != 0).any()):
+        return max_length
+    first = (ids[:, prompt_len:max_length] == eos).int().argmax(1)
+    return prompt_len + int(first.max()) + 1
+
+
+class _AlivePoll:
+    """live-row counts of one decoder read back without stalling its stream: after each chunk of steps a non-blocking copy of
+    `alive` into pinned host memory and an event; `wait(keep)` blocks until at most `keep` such reads are outstanding"""
+
+    def __init__(self, alive: torch.Tensor):
+        self.alive = alive
+        self.bufs = [torch.empty(1, dtype=torch.int32, pin_memory=True) for _ in range(3)]
+        self.pend, self.i, self.done = deque(), 0, False
+
+    def mark(self):
+        buf = self.bufs[self.i % 3]
+        self.i += 1
+        buf.copy_(self.alive, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.pend.append((ev, buf))
+
+    def wait(self, keep: int) -> bool:
+        while len(self.pend) > keep:
+            ev, buf = self.pend.popleft()
+            ev.synchronize()
+            if int(buf[0]) == 0:
+                self.done = True
+        return self.done
+
+
+def run_until_finished(decoders, n: int, chunk: int = STOP_CHUNK) -> list:
+    """Early exit without a per-step sync.  decoders: [(decoder, stream or None)] after `begin(..., stop=...)`; each one replays
+    up to n steps in chunks of `chunk` on its stream, its live-row count is copied back after the prompt pass and after every
+    chunk, and chunk i + 2 is enqueued only once chunk i's count has been read: a decoder stops when that count is 0.  At most two
+    chunks are in flight, and the steps beyond the last live one skip the ring attention.  The count after the prompt pass is
+    waited for, so a batch whose first tokens are all eos replays nothing.  Returns the steps issued per decoder."""
+    chunk = max(1, int(chunk))
+    polls = []
+    for dec, s in decoders:
+        with (torch.cuda.stream(s) if s is not None else nullcontext()):
+            p = _AlivePoll(dec.alive)
+            p.mark()
+        polls.append(p)
+    issued = [0] * len(decoders)
+    for p in polls:
+        p.wait(0)
+    live = True
+    while live:
+        live = False
+        for i, (dec, s) in enumerate(decoders):
+            if issued[i] >= n or polls[i].wait(1):
+                continue
+            k = min(chunk, n - issued[i])
+            with (torch.cuda.stream(s) if s is not None else nullcontext()):
+                for _ in range(k):
+                    dec.replay_once()
+                polls[i].mark()
+            issued[i] += k
+            live = True
+    return issued
 
 
 class XLDecoder:
@@ -62,6 +175,12 @@ class XLDecoder:
         # optional (B, Tmax, V) f32 buffer: row t receives the log-probs computed FROM position t (parity tests compare them
         # with a one-shot forward); written on the device by position, so it also works under hipGraph replay
         self.trace = None
+        # stopping at eos (generate(eos_token_id=...)): per-row live flags and the live-row count, both on the device and written
+        # by the sampler launch; `_stop` = (eos, pad, min_length) of the current generation, None = every row runs to max_length
+        self.unfinished = torch.ones(batch, device=dev, dtype=torch.int32)
+        self.alive = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._stop = None
+        self.steps_run = 0                              # decode steps issued by the last generate() (early exit: fewer)
 
     def _tables(self):
         if self.rd is None:
@@ -79,16 +198,20 @@ class XLDecoder:
         self.graph = None
 
     # ---------------------------------------------------------------- prompt
-    def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None):
+    def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None):
         """Whole prompt through the training-shape kernels with zero mems (upstream first step), rings filled from the
         per-layer qkv buffers, first new token sampled from the last position.
         n_pad: (B,) int32 device tensor, left-padded prompts: the first n_pad[b] columns of row b are pads.  Their K / V are zero
         in every layer (= extra zero-memory slots, so each row computes what it computes alone), they are embedded as id 0 and
-        held as -1 in `ids`, which the samplers' repetition penalty skips."""
+        held as -1 in `ids`, which the samplers' repetition penalty skips.
+        stop: (eos, pad, min_length) or None (stop_config); every row starts live, and the first token sampled here counts."""
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
         self._tables()
+        self._stop = stop
+        self.unfinished.fill_(1)
+        self.alive.fill_(B)
         for k in self.kc + self.vc:
             k.zero_()
         self.ids.zero_()
@@ -124,14 +247,23 @@ class XLDecoder:
         """next token of every row from `scores` (log-probabilities, or the head's logits: see mxl_sample_step) -> ids[:, t + 1];
         position and RNG counters advanced.  Short chain: the same launch leaves the token's embedding row in h[0] for the next step."""
         c = self.eng.cfg
-        if self.fused_sampler:
+        stop = self._stop
+        if self.fused_sampler and stop is None:
             ops.sample_step(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
                             self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model), self.step_ctr,
                             **sampling)
+        elif self.fused_sampler:          # the stop rule and the live-row count ride on the same launch
+            ops.sample_step_stop(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
+                                 self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model),
+                                 self.step_ctr, stop, self.unfinished, self.alive, **sampling)
         else:
-            ops.sample(scores[:, :c.vocab_size] if scores.shape[1] != c.vocab_size else scores, self.ids, self.t_dev, self.rng,
-                       self.seed, **sampling)
+            sc = scores[:, :c.vocab_size] if scores.shape[1] != c.vocab_size else scores
+            if stop is not None:
+                ops.mask_eos_below(sc, c.vocab_size, self.t_dev, stop)
+            ops.sample(sc, self.ids, self.t_dev, self.rng, self.seed, **sampling)
             ops.decode_advance(self.t_dev, self.rng)
+            if stop is not None:
+                ops.decode_stop(self.ids, self.t_dev, stop, self.unfinished, self.alive)
 
     # ---------------------------------------------------------------- one token
     def force_tokens(self, tokens: torch.Tensor):
@@ -172,7 +304,8 @@ class XLDecoder:
                 G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
                 ops.kv_append(self.qkv, self.kc[l], self.vc[l], self.t_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
             ops.relattn_decode(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P),
-                               rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces)
+                               rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces,
+                               unfinished=None if self._stop is None else self.unfinished)
             G(self.av, e._lw(l, 'dec_attn.o_net.weight'), self.tmp, B, d, d)
             ops.ln_residual_fwd(self.tmp, h_in, e._lw(l, 'dec_attn.layer_norm.weight', e.P),
                                 e._lw(l, 'dec_attn.layer_norm.bias', e.P), self.h1, eps=c.layer_norm_epsilon)
@@ -230,25 +363,26 @@ class XLDecoder:
 
     # ---------------------------------------------------------------- loop
     def begin(self, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool = True,
-              n_pad: Optional[torch.Tensor] = None) -> int:
+              n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None) -> int:
         """prompt pass + first sampled token + (use_graph) capture of one decode step; returns the number of `replay_once()`
         calls that complete the generation to max_length.  n_pad: left-padded prompts (prefill); the decode step is the same,
-        every row's last prompt token sits at column Tp - 1"""
+        every row's last prompt token sits at column Tp - 1.  stop: (eos, pad, min_length) (stop_config) or None"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         self._sampling = sampling
         self._use_graph = use_graph
-        self.prefill(prompt, sampling, n_pad)
+        self.prefill(prompt, sampling, n_pad, stop)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
             # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
             # itself is written by the captured launches): a graph captured without a trace would replay without writing one
             key = (tuple(sorted(sampling.items())), self.fused_sampler,
-                   None if self.trace is None else self.trace.data_ptr())
+                   None if self.trace is None else self.trace.data_ptr(), stop)
             if self.graph is None or self._graph_key != key:
                 # warm-up on a side stream (first launches set function attributes), then capture one step
                 state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(),
-                         [k.clone() for k in self.kc], [v.clone() for v in self.vc], self.h[0].clone())
+                         [k.clone() for k in self.kc], [v.clone() for v in self.vc], self.h[0].clone(),
+                         self.unfinished.clone(), self.alive.clone())
                 s = torch.cuda.Stream()
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
@@ -265,6 +399,7 @@ class XLDecoder:
                 for a, b in zip(self.vc, state[4]):
                     a.copy_(b)
                 self.h[0].copy_(state[5])         # (short chain: the next step's embedding row is step state too)
+                self.unfinished.copy_(state[6]); self.alive.copy_(state[7])
         return max(steps, 0)
 
     def replay_once(self):
@@ -276,19 +411,33 @@ class XLDecoder:
 
     def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
-                 typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None,
+                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
+                 stop_chunk: int = STOP_CHUNK) -> torch.Tensor:
         """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
         [OMIT]) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (prefill); the
-        prompt columns, pads included, come back as given."""
+        prompt columns, pads included, come back as given.
+        eos_token_id (opt-in): HF greedy_search / sample stopping -- a row that emits eos is finished and emits pad_token_id
+        (default: eos) from then on, the call ends once every row has finished, and the output is cut to the width of the
+        longest row (finish_at_eos); min_length bars eos below that width.  The decode steps are replayed in chunks of
+        `stop_chunk` with the live-row count read back one chunk late (run_until_finished): no per-step host round trip."""
         sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0,
                         temperature=temperature, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
                         typical_p=1.0 if typical_p is None else typical_p)
+        stop = stop_config(eos_token_id, pad_token_id, min_length)
         Tp = prompt.shape[1]
         if max_length - Tp <= 0:
             return prompt[:, :max_length]
-        for _ in range(self.begin(prompt, max_length, sampling, use_graph, n_pad)):
-            self.replay_once()
-        out = self.ids[:, :max_length].clone()
+        n = self.begin(prompt, max_length, sampling, use_graph, n_pad, stop)
+        if stop is None:
+            for _ in range(n):
+                self.replay_once()
+            self.steps_run = n
+            W = max_length
+        else:
+            self.steps_run = run_until_finished([(self, None)], n, stop_chunk)[0]
+            W = stop_width(self.ids, self.unfinished, Tp, max_length, stop[0])
+        out = self.ids[:, :W].clone()
         if n_pad is not None:
             out[:, :Tp].copy_(prompt)
         return out
@@ -314,9 +463,9 @@ class XLDecoderLanes:
         for d in self.lanes:
             d.invalidate_tables()
 
-    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None) -> int:
+    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None) -> int:
         steps = [d.begin(prompt[self.offs[i]:self.offs[i + 1]], max_length, sampling, use_graph,
-                         None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]]) for i, d in enumerate(self.lanes)]
+                         None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]], stop) for i, d in enumerate(self.lanes)]
         for s in self.streams:                       # the lanes start from the prompt passes and captures issued above
             s.wait_stream(torch.cuda.current_stream())
         return steps[0]
@@ -331,18 +480,37 @@ class XLDecoderLanes:
             torch.cuda.current_stream().wait_stream(s)
 
     def generate(self, prompt, max_length, do_sample=False, top_k=None, top_p=None, temperature=1.0, repetition_penalty=None,
-                 typical_p=None, use_graph=True, n_pad=None) -> torch.Tensor:
+                 typical_p=None, use_graph=True, n_pad=None, eos_token_id=None, pad_token_id=None, min_length=None,
+                 stop_chunk=STOP_CHUNK) -> torch.Tensor:
+        """XLDecoder.generate over the lanes.  With eos_token_id every lane stops on its own; the output is the lanes' rows cut to
+        the common width and right-filled with pad where a lane stopped earlier."""
         sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0,
                         temperature=temperature, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
                         typical_p=1.0 if typical_p is None else typical_p)
-        if max_length - prompt.shape[1] <= 0:
+        stop = stop_config(eos_token_id, pad_token_id, min_length)
+        Tp = prompt.shape[1]
+        if max_length - Tp <= 0:
             return prompt[:, :max_length]
-        for _ in range(self.begin(prompt, max_length, sampling, use_graph, n_pad)):
-            self.replay_once()
-        self.join()
-        out = torch.cat([d.ids[:, :max_length] for d in self.lanes], 0)
+        n = self.begin(prompt, max_length, sampling, use_graph, n_pad, stop)
+        if stop is None:
+            for _ in range(n):
+                self.replay_once()
+            self.join()
+            self.steps_run = n
+            out = torch.cat([d.ids[:, :max_length] for d in self.lanes], 0)
+        else:
+            steps = run_until_finished(list(zip(self.lanes, self.streams)), n, stop_chunk)
+            self.join()
+            for d, k in zip(self.lanes, steps):
+                d.steps_run = k
+            self.steps_run = max(steps)
+            widths = [stop_width(d.ids, d.unfinished, Tp, max_length, stop[0]) for d in self.lanes]
+            W = max(widths)
+            out = torch.cat([d.ids[:, :W] for d in self.lanes], 0)
+            for i, w in enumerate(widths):
+                out[self.offs[i]:self.offs[i + 1], w:] = stop[1]
         if n_pad is not None:
-            out[:, :prompt.shape[1]].copy_(prompt)
+            out[:, :Tp].copy_(prompt)
         return out
 
 

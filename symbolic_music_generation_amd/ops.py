@@ -145,6 +145,36 @@ def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter
                                 float(scale), _p(counter), _stream()), 'mxl_sample_step')
 
 
+def sample_step_stop(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, stop, unfinished, alive, do_sample=False,
+                     top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0):
+    """sample_step with the stop state of generation: stop = (eos_id, pad_id, min_length); unfinished (B,) int32 and alive (1,)
+    int32 on the device (mxl_sample_step_stop).  Same single launch."""
+    B = scores.shape[0]
+    eos, pad, min_length = stop
+    check(lib().mxl_sample_step_stop(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
+                                     int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
+                                     float(repetition_penalty if repetition_penalty is not None else 1.0),
+                                     float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
+                                     float(scale), _p(counter), int(eos), int(pad), int(min_length or 0), _p(unfinished), _p(alive),
+                                     _stream()), 'mxl_sample_step_stop')
+
+
+def decode_stop(ids, t_dev, stop, unfinished, alive):
+    """after sample + decode_advance: the token at ids[:, t] through the stop rule (mxl_decode_stop); stop = (eos, pad, min_length)"""
+    _req(unfinished, torch.int32, 'decode_stop unfinished')
+    check(lib().mxl_decode_stop(_p(ids), ids.stride(0), _p(t_dev), ids.shape[0], int(stop[0]), int(stop[1]), _p(unfinished), _p(alive),
+                                _stream()), 'mxl_decode_stop')
+
+
+def mask_eos_below(scores, V, t_dev, stop):
+    """before sample: eos barred (-inf) while the rows are shorter than min_length (mxl_mask_eos_below); no launch without one"""
+    eos, _, min_length = stop
+    if not min_length or min_length <= 0:
+        return
+    check(lib().mxl_mask_eos_below(_p(scores), scores.stride(0), scores.shape[0], int(V), int(eos), int(min_length), _p(t_dev),
+                                   _stream()), 'mxl_mask_eos_below')
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, relu=False, out=None,
            out_f32=False, drop_p=0.0, seed=0, site=0) -> torch.Tensor:
     """y = x @ w.T (+bias)(relu)(dropout); x (N, K) bf16, w (O, K) bf16."""
@@ -612,10 +642,12 @@ def relattn_decode_split_scratch(B: int, H: int, dh: int, pieces: int, dev):
     return torch.empty(n, device=dev, dtype=torch.float32), torch.zeros(B * H, device=dev, dtype=torch.int32)
 
 
-def relattn_decode(qkv, kc, vc, rd, rwb, rrb, out, t_dev, H, dh, qr_buf, bd_buf, scale=None, qr_ready=False, split=None, pieces=1):
+def relattn_decode(qkv, kc, vc, rd, rwb, rrb, out, t_dev, H, dh, qr_buf, bd_buf, scale=None, qr_ready=False, split=None, pieces=1,
+                   unfinished=None):
     """qr_buf (B, H*dh) bf16 and bd_buf (B, H, M) f32 are scratch: BD = (q + r_r_bias) . rd^T for the whole batch.
     qr_ready: qr_buf already holds q + r_r_bias (written by kv_append).  split = relattn_decode_split_scratch(...) with the same
-    `pieces`: the ring of every (sequence, head) goes to that many workgroups."""
+    `pieces`: the ring of every (sequence, head) goes to that many workgroups.  unfinished: (B,) int32 device stop state of
+    generation -- finished rows (0) read no ring and get zeros in `out` (mxl_relattn_decode_split_live)."""
     B, _, M, _ = kc.shape
     d = H * dh
     scale = scale if scale is not None else 1.0 / math.sqrt(dh)
@@ -626,6 +658,13 @@ def relattn_decode(qkv, kc, vc, rd, rwb, rrb, out, t_dev, H, dh, qr_buf, bd_buf,
     else:
         gemm_batched(qr_buf, rd, bd_buf, B, M, dh, lda=d, ldb=d, ldc=H * M, flags=GEMM_OUT_F32, batch=H, bdiv=1,
                      sA=(dh, 0), sB=(dh, 0), sC=(M, 0))
+    if unfinished is not None:
+        _req(unfinished, torch.int32, 'relattn_decode unfinished')
+        n = pieces if (split is not None and pieces > 1) else 1
+        check(lib().mxl_relattn_decode_split_live(_p(qkv), _p(kc), _p(vc), _p(bd_buf), _p(rwb), _p(out), _p(t_dev), B, H, dh, M,
+                                                  float(scale), n, _p(split[0]) if n > 1 else 0, _p(split[1]) if n > 1 else 0,
+                                                  _p(unfinished), _stream()), 'mxl_relattn_decode_split_live')
+        return
     if split is not None and pieces > 1:
         check(lib().mxl_relattn_decode_split(_p(qkv), _p(kc), _p(vc), _p(bd_buf), _p(rwb), _p(out), _p(t_dev), B, H, dh, M,
                                              C.c_float(float(scale)), pieces, _p(split[0]), _p(split[1]), _stream()),

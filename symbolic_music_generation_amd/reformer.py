@@ -158,9 +158,21 @@ class MyReformerModelWithLMHead(EngineModule):
         `rotations` ({lsh layer: (H, dh, n_h, rot/2)}) fixes the hash rotations (HF `config.hash_seed`); by default one seeded
         draw serves the whole generation.
         use_cache=False: every step is a full forward over the tokens so far, right-padded to a multiple of the chunk length
-        (pads sit after every real token, so the causal mask keeps them out), with the rotations redrawn each forward."""
+        (pads sit after every real token, so the causal mask keeps them out), with the rotations redrawn each forward.
+
+        eos_token_id / pad_token_id / min_length / max_new_tokens: stopping at eos for greedy decoding and sampling, opt-in, as
+        MyTransfoXLLMHeadModel.generate (HF greedy_search / sample: finished rows emit pad, the call ends once every row has
+        finished, the output is cut to the longest row).  Beam and group-beam search take an explicit eos / pad in place of the
+        config's."""
         from . import ops
-        from .generate import left_pad_counts
+        from .generate import STOP_CHUNK, left_pad_counts, resolve_max_length, stop_config, stop_width
+        eos_token_id = unsupported.pop('eos_token_id', None)
+        pad_token_id = unsupported.pop('pad_token_id', None)
+        min_length = unsupported.pop('min_length', None)
+        max_new_tokens = unsupported.pop('max_new_tokens', None)
+        stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
+        eos_b = self.config.eos_token_id if eos_token_id is None else eos_token_id          # beam / group-beam search
+        pad_b = self.config.pad_token_id if pad_token_id is None else pad_token_id
         mask = unsupported.pop('attention_mask', None)
         if mask is not None and input_ids is not None and any(left_pad_counts(mask, tuple(input_ids.shape))):
             # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
@@ -176,6 +188,8 @@ class MyReformerModelWithLMHead(EngineModule):
             if not do_sample:
                 raise ValueError('num_return_sequences has to be 1 when doing greedy search')
             input_ids = input_ids.repeat_interleave(int(unsupported.pop('num_return_sequences')), 0)
+        if max_new_tokens is not None:
+            max_length = resolve_max_length(max_length, max_new_tokens, input_ids.shape[1], None)
         num_beams = unsupported.pop('num_beams', 1) or 1
         num_beam_groups = unsupported.pop('num_beam_groups', 1) or 1
         diversity_penalty = unsupported.pop('diversity_penalty', None)
@@ -198,8 +212,7 @@ class MyReformerModelWithLMHead(EngineModule):
                                          diversity_penalty=diversity_penalty or 0.0,
                                          early_stopping=bool(unsupported.get('early_stopping')),
                                          length_penalty=float(unsupported.get('length_penalty', 1.0) or 1.0),
-                                         num_return_sequences=nrs, eos_token_id=self.config.eos_token_id,
-                                         pad_token_id=self.config.pad_token_id)
+                                         num_return_sequences=nrs, eos_token_id=eos_b, pad_token_id=pad_b)
             finally:
                 if was:
                     self.train()
@@ -221,12 +234,12 @@ class MyReformerModelWithLMHead(EngineModule):
                                    early_stopping=bool(unsupported.get('early_stopping')),
                                    length_penalty=float(unsupported.get('length_penalty', 1.0) or 1.0),
                                    renormalize_logits=bool(unsupported.get('renormalize_logits')), num_return_sequences=nrs,
-                                   eos_token_id=self.config.eos_token_id, pad_token_id=self.config.pad_token_id, generator=gen)
+                                   eos_token_id=eos_b, pad_token_id=pad_b, generator=gen)
             finally:
                 if was:
                     self.train()
         if unsupported:
-            ok = {'early_stopping', 'renormalize_logits'}      # no effect: eos never ends a row; the sampler always renormalises
+            ok = {'early_stopping', 'renormalize_logits'}      # no effect: no beams here; the sampler always renormalises
             bad = [k for k, v in unsupported.items() if k not in ok and v not in (None, False, 1, 1.0)]
             if bad:
                 raise NotImplementedError(f'generation options not covered: {bad}')
@@ -251,7 +264,7 @@ class MyReformerModelWithLMHead(EngineModule):
                 dec.rotations = rotations
                 dec.seed = seed
                 return dec.generate(ids0, max_length, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
-                                    repetition_penalty=repetition_penalty, typical_p=typical_p)
+                                    repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop)
             V = c.vocab_size
             pad = getattr(c, 'pad_token_id', None)
             pad = 0 if pad is None else int(pad)
@@ -259,16 +272,27 @@ class MyReformerModelWithLMHead(EngineModule):
             buf[:, :Tp] = ids0
             t_dev = torch.full((1,), Tp - 1, device=self.device, dtype=torch.int32)
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
+            unfinished = torch.ones(B, device=self.device, dtype=torch.int32)
+            alive = torch.zeros(1, device=self.device, dtype=torch.int32)
             for cur in range(Tp, max_length):
                 Tf = cur if cur <= 64 else (cur + 63) // 64 * 64
                 out = self.engine.forward(buf[:, :Tf].contiguous(), labels=None, train=False)
                 last = out['logits'][:, cur - 1].contiguous()
+                if stop is not None:
+                    ops.mask_eos_below(last[:, :V], V, t_dev, stop)
                 ops.sample(last, buf, t_dev, rng, seed, do_sample=do_sample, top_k=top_k or 0,
                            top_p=top_p if top_p is not None else 1.0, temperature=temperature,
                            repetition_penalty=repetition_penalty, typical_p=typical_p)
                 ops.decode_advance(t_dev, rng)
+                if stop is not None:
+                    ops.decode_stop(buf, t_dev, stop, unfinished, alive)
                 if Tf > cur:
                     buf[:, cur + 1:Tf] = pad          # keep the padding clean (the sampler wrote position `cur` only)
+                # a whole forward per token: reading the live-row count every STOP_CHUNK tokens costs nothing in comparison
+                if stop is not None and (cur - Tp) % STOP_CHUNK == 0 and int(alive.item()) == 0:
+                    break
+            if stop is not None:
+                return buf[:, :stop_width(buf, unfinished, Tp, max_length, stop[0])].clone()
             return buf[:, :max_length].clone()
         finally:
             if was_training:

@@ -66,6 +66,11 @@ class RFDecoder:
         self.logits = torch.empty(batch, engine.layout.head_rows_padded, device=dev, dtype=torch.float32)
         self.raw_bk = torch.empty(batch * H, self.n_h, device=dev, dtype=torch.int32)
         self.trace = None                   # optional (B, Tmax, V) f32: row t = logits computed FROM position t (parity tests)
+        # stopping at eos (generate(stop=...)): per-row live flags and the live-row count on the device (generate.XLDecoder)
+        self.unfinished = torch.ones(batch, device=dev, dtype=torch.int32)
+        self.alive = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._stop = None
+        self.steps_run = 0
 
     # ---------------------------------------------------------------- hashing helpers
     def _factors(self, T_hint: Optional[int] = None):
@@ -94,10 +99,13 @@ class RFDecoder:
         return r
 
     # ---------------------------------------------------------------- prompt
-    def prefill(self, prompt: torch.Tensor, sampling: dict):
+    def prefill(self, prompt: torch.Tensor, sampling: dict, stop: Optional[tuple] = None):
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and 1 <= Tp <= self.Tmax
+        self._stop = stop
+        self.unfinished.fill_(1)
+        self.alive.fill_(B)
         d, H = c.hidden_size, c.num_attention_heads
         self.ids.zero_()
         self.ids[:, :Tp].copy_(prompt)
@@ -137,8 +145,13 @@ class RFDecoder:
         self._last = logits
         if sampling is None:                 # the caller picks the token (beam search)
             return
-        ops.sample(logits[:, :self.eng.cfg.vocab_size], self.ids, self.t_dev, self.rng, self.seed, **sampling)
+        V = self.eng.cfg.vocab_size
+        if self._stop is not None:          # min_length: eos barred below it (after the trace above)
+            ops.mask_eos_below(logits[:, :V], V, self.t_dev, self._stop)
+        ops.sample(logits[:, :V], self.ids, self.t_dev, self.rng, self.seed, **sampling)
         ops.decode_advance(self.t_dev, self.rng)
+        if self._stop is not None:
+            ops.decode_stop(self.ids, self.t_dev, self._stop, self.unfinished, self.alive)
 
     # ---------------------------------------------------------------- one token
     def step(self, t: int, sampling: dict):
@@ -244,7 +257,11 @@ class RFDecoder:
     @torch.no_grad()
     def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
-                 typical_p: Optional[float] = None) -> torch.Tensor:
+                 typical_p: Optional[float] = None, stop: Optional[tuple] = None, stop_chunk: int = 16) -> torch.Tensor:
+        """(B, max_length) ids = prompt + continuation.  stop = (eos, pad, min_length) (generate.stop_config): rows finish at eos
+        and the loop ends once none is live -- the live-row count is read back every `stop_chunk` steps, one chunk late
+        (generate.run_until_finished) -- and the output is cut to the longest row."""
+        from .generate import run_until_finished, stop_width
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0, temperature=temperature,
@@ -252,7 +269,17 @@ class RFDecoder:
         Tp = prompt.shape[1]
         if max_length <= Tp:
             return prompt[:, :max_length]
-        self.prefill(prompt.to(self.eng.dev), sampling)
-        for t in range(Tp, max_length - 1):
-            self.step(t, sampling)
-        return self.ids[:, :max_length].clone()
+        self.prefill(prompt.to(self.eng.dev), sampling, stop)
+        if stop is None:
+            for t in range(Tp, max_length - 1):
+                self.step(t, sampling)
+            self.steps_run = max(max_length - 1 - Tp, 0)
+            return self.ids[:, :max_length].clone()
+        self._next_t, self._sampling = Tp, sampling
+        self.steps_run = run_until_finished([(self, None)], max(max_length - 1 - Tp, 0), stop_chunk)[0]
+        return self.ids[:, :stop_width(self.ids, self.unfinished, Tp, max_length, stop[0])].clone()
+
+    def replay_once(self):
+        """the next step of generate() with stopping (run_until_finished drives it)"""
+        self.step(self._next_t, self._sampling)
+        self._next_t += 1

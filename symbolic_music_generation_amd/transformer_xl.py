@@ -196,7 +196,9 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: float = 1.0, num_beams: int = 1,
                  penalty_alpha=None, typical_p=None, repetition_penalty=None, early_stopping=None,
                  renormalize_logits=None, num_return_sequences: int = 1, num_beam_groups: int = 1, length_penalty: float = 1.0,
-                 use_graph: bool = True, seed: int = 77, attention_mask: Optional[torch.Tensor] = None, **unused) -> torch.Tensor:
+                 use_graph: bool = True, seed: int = 77, attention_mask: Optional[torch.Tensor] = None,
+                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
+                 min_length: Optional[int] = None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -206,8 +208,16 @@ class MyTransfoXLLMHeadModel(EngineModule):
         columns, then 1 on the prompt; `generate.left_pad` builds it).  Greedy and sampling decode every row as if it were alone:
         row b without its pad columns equals `generate(input_ids=ids[b:b+1, s_b:], max_length=max_length - s_b)` (DESIGN.md,
         ragged prompts).  The output keeps the input columns as given, pad ids included.  Beam, group-beam and contrastive
-        search take no padded mask."""
-        from .generate import XLDecoder, XLDecoderLanes, beam_search, contrastive_search, group_beam_search, left_pad_counts
+        search take no padded mask.
+
+        Stopping at eos is opt-in: only an explicit `eos_token_id=` turns it on (the config's eos, 0 = [OMIT], is not adopted, so
+        a call without it runs every row to max_length as before).  Then greedy decoding and sampling follow HF greedy_search /
+        sample: a row that emits eos emits pad from then on (`pad_token_id`, else the config's, else eos), the call returns once
+        every row has finished, cut to the longest row; `min_length` bars eos while a row is shorter.  `max_new_tokens` = n on an
+        unpadded batch is max_length = prompt length + n (both given: ValueError, as HF).  Beam, group-beam and contrastive search
+        keep their own eos handling, with an explicit eos_token_id / pad_token_id in place of the config's."""
+        from .generate import (XLDecoder, XLDecoderLanes, beam_search, contrastive_search, group_beam_search, left_pad_counts,
+                               resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -217,18 +227,22 @@ class MyTransfoXLLMHeadModel(EngineModule):
         # `generate(do_sample=True)` without top_k samples from the 50 best tokens (the reference relies on these defaults)
         top_k = getattr(self.config, 'top_k', 50) if top_k is None else top_k
         diversity_penalty = unused.pop('diversity_penalty', None)
+        if n_pad is not None and (max_new_tokens is not None or unused.get('stopping_criteria') is not None):
+            raise MusicXLError('padded prompts: max_new_tokens and stopping_criteria are not supported (give max_length; '
+                               'eos_token_id stops rows)')
+        stop = stop_config(eos_token_id, pad_token_id, min_length, self.config.pad_token_id)
+        eos_b = self.config.eos_token_id if eos_token_id is None else eos_token_id          # beam / group-beam / contrastive
+        pad_b = self.config.pad_token_id if pad_token_id is None else pad_token_id
         self._maybe_resync()
-        max_length = max_length or self.config.max_length_
+        max_length = resolve_max_length(max_length, max_new_tokens, input_ids.shape[1], self.config.max_length_)
         contrastive = penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and not do_sample and num_beams == 1
         if n_pad is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('padded prompts (attention_mask with zeros) are supported for greedy decoding and sampling only, not '
                                'for beam, group-beam or contrastive search')
-        if n_pad is not None and (unused.get('max_new_tokens') is not None or unused.get('stopping_criteria') is not None):
-            raise MusicXLError('padded prompts run every row to max_length: max_new_tokens and per-row stopping are not supported')
         if contrastive:
             dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
-                                      eos_token_id=self.config.eos_token_id, pad_token_id=self.config.pad_token_id)
+                                      eos_token_id=eos_b, pad_token_id=pad_b)
         if num_beam_groups != 1:
             if num_beams <= 1 or num_beam_groups > num_beams:
                 raise ValueError('`num_beam_groups` has to be smaller or equal to `num_beams`')               # HF's message
@@ -238,7 +252,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
             return group_beam_search(dec, input_ids, max_length, num_beams=num_beams, num_beam_groups=num_beam_groups,
                                      diversity_penalty=diversity_penalty or 0.0, early_stopping=bool(early_stopping),
                                      length_penalty=length_penalty, num_return_sequences=num_return_sequences,
-                                     eos_token_id=self.config.eos_token_id, pad_token_id=self.config.pad_token_id)
+                                     eos_token_id=eos_b, pad_token_id=pad_b)
         if num_beams > 1:
             rows = input_ids.shape[0] * num_beams * (num_return_sequences if do_sample else 1)
             dec = XLDecoder(self.engine, rows, max_length, seed=seed)
@@ -247,7 +261,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                                temperature=temperature, typical_p=typical_p, early_stopping=bool(early_stopping),
                                renormalize_logits=bool(renormalize_logits),
                                length_penalty=length_penalty, num_return_sequences=num_return_sequences,
-                               eos_token_id=self.config.eos_token_id, pad_token_id=self.config.pad_token_id, generator=gen)
+                               eos_token_id=eos_b, pad_token_id=pad_b, generator=gen)
         if num_return_sequences > 1:
             if not do_sample:
                 raise ValueError('num_return_sequences has to be 1 when doing greedy search')       # HF's message
@@ -264,4 +278,5 @@ class MyTransfoXLLMHeadModel(EngineModule):
         dec.invalidate_tables()
         return dec.generate(input_ids.to(self.device), max_length, do_sample=do_sample, top_k=top_k, top_p=top_p,
                             temperature=temperature, repetition_penalty=repetition_penalty, typical_p=typical_p,
-                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device))
+                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device),
+                            **({} if stop is None else dict(eos_token_id=stop[0], pad_token_id=stop[1], min_length=stop[2])))
