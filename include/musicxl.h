@@ -451,6 +451,33 @@ int mxl_sample_step_stop(const float* scores, int ldl, int V, void* ids, int ld_
 int mxl_decode_stop(void* ids, int ld_ids, const int* t_dev, int B, int eos_id, int pad_id, int* unfinished, int* alive,
                     void* stream);
 int mxl_mask_eos_below(float* scores, int ldl, int B, int V, int eos_id, int min_length, const int* t_dev, void* stream);
+/* Grammar-constrained decoding: every row may only emit tokens that a token-class automaton allows in the row's state.
+ * Tables (device): cls (V,) uint8 token -> class (C <= 32 classes); allow (S,) uint32, bit c set <=> class c may be emitted in
+ * state s (S <= 256); next (S, C) uint8 successor state (entries of barred classes hold s itself).  gstate (B,) int32 is the state
+ * of every row, kept and advanced on the device.  A barred token's score is -inf after the repetition penalty and min_length and
+ * before temperature / top-k / top-p / typical-p (HF's logits-processor order), so the warpers and the renormalised draw see
+ * allowed tokens only.  The caller guarantees that no reachable state bars every token.
+ * mxl_sample_step_grammar: mxl_sample_step_stop with the mask applied where the row enters LDS and gstate[b] moved along the token
+ * the row keeps, in the same launch.  unfinished = alive = NULL: no eos rule (eos_id / pad_id / min_length ignored).  With the eos
+ * rule the state moves after it: a row that was finished before the step emits pad and keeps its state; the step in which a row
+ * emits eos still moves it. */
+int mxl_sample_step_grammar(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                            unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                            float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                            int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
+                            const void* allow, const void* next, int C, int* gstate, void* stream);
+/* The same around mxl_sample / mxl_sample_large.  mxl_grammar_mask: scores[b][v] = -inf in place wherever allow[gstate[b]] bars
+ * cls[v] (one thread per score), before the sampler -- whose repetition penalty leaves -inf at -inf, so the result is that of
+ * masking after the penalty.  mxl_grammar_advance: after the sampler and mxl_decode_advance and BEFORE mxl_decode_stop of the same
+ * step: gstate[b] moves along ids[b][*t_dev]; rows with unfinished[b] == 0 (optional; finished before this step) keep theirs. */
+int mxl_grammar_mask(float* scores, int ldl, int B, int V, const void* cls, const void* allow, const int* gstate, void* stream);
+int mxl_grammar_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, const void* next, int C,
+                        int* gstate, const int* unfinished, void* stream);
+/* State of every row after its prompt: ids (B, ld_ids) int64, columns 0..Tp-1 walked from `start`; a column holding an id < 0 is
+ * skipped (left pad).  first_bad[b] = column of the first token the state bars (or an id >= V), where the walk of that row stops;
+ * -1 = the prompt obeys the grammar. */
+int mxl_grammar_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* allow, const void* next, int C,
+                     int start, int* gstate, int* first_bad, void* stream);
 /* Contrastive search (the reference's 'contrastive' strategy, musicnlp/trainer/eval.py:296-302, over the mems patch of
  * musicnlp/models/transformer_xl.py:229-234; HF 4.25.1 GenerationMixin.contrastive_search with `_ranking_fast`):
  *   score[b*K + k] = (1 - alpha) * probs[b*K + k] - alpha * max_{s < S} cos(hid[b*K + k], ctx[b][s]);  sel[b] = argmax_k score

@@ -359,12 +359,16 @@ __global__ __launch_bounds__(256) void decode_bd_kernel(const bf16_t* qr, const 
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int SORT_N = 2048;
 
-// the row's next token (returned to every thread of the workgroup)
+// the row's next token (returned to every thread of the workgroup).
+// G: grammar-constrained (mxl_sample_step_grammar) -- a token whose class bit is clear in `gallow` (the allow mask of the row's
+// grammar state) is -inf from the moment the row enters LDS and is never rewritten by the repetition penalty, which is HF's
+// processor order "penalty, min_length, grammar, then the warpers": every warper and the renormalisation see allowed tokens only.
+template <bool G = false>
 __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, const long long* ids, int ld_ids,
                                           const int* t_dev, const unsigned long long* rng_ctr, unsigned long long seed,
                                           int do_sample, int top_k, float top_p, float temperature,
                                           float repetition_penalty, float typical_p, float* out_probs, int eos_id = -1,
-                                          int min_length = 0) {
+                                          int min_length = 0, const unsigned char* gcls = nullptr, uint32_t gallow = 0u) {
     __shared__ float key[SORT_N];
     __shared__ int idx[SORT_N];
     __shared__ int sh_pick;
@@ -372,7 +376,8 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
     const float* row = logp + (size_t)b * ldl;
     const float invt = 1.f / temperature;
     for (int i = tid; i < SORT_N; i += 256) {
-        key[i] = i < V ? row[i] * invt : -INFINITY;
+        if (G) key[i] = (i < V && ((gallow >> gcls[i]) & 1u)) ? row[i] * invt : -INFINITY;
+        else key[i] = i < V ? row[i] * invt : -INFINITY;
         idx[i] = i;
     }
     __syncthreads();
@@ -384,7 +389,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
         const long long* hist = ids + (size_t)b * ld_ids;
         for (int j = tid; j <= tcur; j += 256) {
             const long long tok = hist[j];
-            if (tok >= 0 && tok < V) {
+            if (tok >= 0 && tok < V && (!G || ((gallow >> gcls[tok]) & 1u))) {
                 const float v = row[tok];
                 key[tok] = (v < 0.f ? v * repetition_penalty : v / repetition_penalty) * invt;
             }
@@ -577,21 +582,33 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl,
 // advances the position and RNG counters (mxl_decode_advance): every other workgroup has read them by then.  `scores` may be the
 // head's raw logits instead of log-probabilities when no repetition penalty is in force: every other warper, the argmax and the
 // renormalised draw are invariant under the per-row shift log-softmax applies.
+//
+// G (mxl_sample_step_grammar): the row's grammar state gstate[b] selects the allow mask the sampler applies, and thread 0 moves the
+// state along the token the row keeps.  The move sits AFTER the eos rule: a row that was finished before this step emits pad and
+// its state stays frozen (the pad is not the row's choice and need not be a token the state allows); the step in which a live row
+// emits eos still moves it, so a finished row of the music grammar rests in END.
+template <bool G>
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, int ldl, int V, long long* ids, int ld_ids,
                                                           int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                           int do_sample, int top_k, float top_p, float temperature,
                                                           float repetition_penalty, float typical_p, const bf16_t* E, bf16_t* emb_out,
                                                           int d, float scale, int* counter, int eos_id, int pad_id,
-                                                          int min_length, int* unfinished, int* alive) {
-    int tok = sample_row(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
-                         repetition_penalty, typical_p, nullptr, unfinished ? eos_id : -1, unfinished ? min_length : 0);
+                                                          int min_length, int* unfinished, int* alive,
+                                                          const unsigned char* gcls = nullptr, const uint32_t* gallow = nullptr,
+                                                          const unsigned char* gnext = nullptr, int C = 0, int* gstate = nullptr) {
+    const int gs = G ? gstate[blockIdx.x] : 0;
+    int tok = sample_row<G>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
+                            repetition_penalty, typical_p, nullptr, unfinished ? eos_id : -1, unfinished ? min_length : 0,
+                            gcls, G ? gallow[gs] : 0u);
     const int b = blockIdx.x, tid = threadIdx.x;
     __shared__ int sh_tok, sh_live;
+    bool was_live = true;                       // (thread 0) the token is the row's own choice
     if (unfinished) {
         // stop state (HF greedy_search / sample): a finished row emits pad; a live row that emits eos is finished from now on
         if (tid == 0) {
             int live = unfinished[b];
             int tk = tok;
+            was_live = live != 0;
             if (!live) tk = pad_id;
             else if (tk == eos_id) live = 0;
             unfinished[b] = live;
@@ -601,6 +618,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         __syncthreads();
         tok = sh_tok;
     }
+    if (G && tid == 0 && was_live && tok >= 0 && tok < V) gstate[b] = gnext[gs * C + gcls[tok]];
     if (tid == 0) ids[(size_t)b * ld_ids + *t_dev + 1] = tok;
     const int id = (tok < 0 || tok >= V) ? 0 : tok;
     for (int c = tid; c < (d >> 3); c += 256) {
@@ -665,6 +683,61 @@ __global__ __launch_bounds__(256) void mask_eos_below_kernel(float* scores, int 
                                                              const int* t_dev) {
     if (*t_dev + 1 >= min_length) return;
     for (int b = threadIdx.x; b < B; b += 256) scores[(size_t)b * ldl + eos_id] = -INFINITY;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Grammar-constrained decoding around the samplers that do not carry it themselves (mxl_sample, mxl_sample_large): a token class
+// automaton, cls (V,) token -> class, allow (S,) bit c = class c may follow in state s, next (S, C) successor.
+// ---------------------------------------------------------------------------------------------------------------
+// before the sampler: -inf on every token the row's state bars; one thread per score
+__global__ __launch_bounds__(256) void grammar_mask_kernel(float* scores, int ldl, int B, int V, const unsigned char* cls,
+                                                           const uint32_t* allow, const int* gstate) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * V) return;
+    const int b = (int)(i / V), v = (int)(i - (long long)b * V);
+    if (!((allow[gstate[b]] >> cls[v]) & 1u)) scores[(size_t)b * ldl + v] = -INFINITY;
+}
+
+// after the sampler and the counter advance, BEFORE the stop rule of this step (mxl_decode_stop): the token just written sits at
+// column *t_dev; `unfinished` (optional) still holds which rows were live when they chose it -- the others stay frozen
+__global__ __launch_bounds__(256) void grammar_advance_kernel(const long long* ids, int ld_ids, const int* t_dev, int B, int V,
+                                                              const unsigned char* cls, const unsigned char* next, int C,
+                                                              int* gstate, const int* unfinished) {
+    const int t = *t_dev;
+    for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) {
+        if (unfinished && !unfinished[b]) continue;
+        const long long tok = ids[(size_t)b * ld_ids + t];
+        if (tok >= 0 && tok < V) gstate[b] = next[gstate[b] * C + cls[tok]];
+    }
+}
+
+// state of every row after its prompt.  One wave per row: the lanes load 64 columns at a time and their classes, then every lane
+// walks the 64 classes (the walk is uniform over the wave: table look-ups only, no dependent load of ids).  Columns holding an id
+// < 0 are skipped (left pads); first_bad[b] = column of the first token the state bars (or beyond the vocabulary), -1 = none.
+__global__ __launch_bounds__(64) void grammar_scan_kernel(const long long* ids, int ld_ids, int Tp, int B, int V,
+                                                          const unsigned char* cls, const uint32_t* allow,
+                                                          const unsigned char* next, int C, int start, int* gstate,
+                                                          int* first_bad) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long* row = ids + (size_t)b * ld_ids;
+    int s = start, bad = -1;
+    for (int base = 0; base < Tp && bad < 0; base += 64) {
+        const int col = base + lane;
+        int c = -1;                                              // -1 skip, -2 outside the vocabulary
+        if (col < Tp) {
+            const long long tok = row[col];
+            if (tok >= V) c = -2;
+            else if (tok >= 0) c = cls[tok];
+        }
+        const int n = min(64, Tp - base);
+        for (int j = 0; j < n; j++) {
+            const int cj = __shfl(c, j, 64);
+            if (cj == -1) continue;
+            if (cj < 0 || !((allow[s] >> cj) & 1u)) { bad = base + j; break; }
+            s = next[s * C + cj];
+        }
+    }
+    if (lane == 0) { gstate[b] = s; first_bad[b] = bad; }
 }
 
 }  // namespace
@@ -793,7 +866,7 @@ extern "C" int mxl_sample_step(const float* scores, int ldl, int V, void* ids, i
     MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
     MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
     MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
-    hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
+    hipLaunchKernelGGL(sample_step_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
                        t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
                        (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, -1, 0, 0, (int*)nullptr, (int*)nullptr);
     MXL_LAUNCH_CHECK();
@@ -809,9 +882,63 @@ extern "C" int mxl_sample_step_stop(const float* scores, int ldl, int V, void* i
     MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
     MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
     MXL_CHECK_ARG(unfinished && alive && B <= 32767);          // arrivals and live rows share one 32-bit atomic word
-    hipLaunchKernelGGL(sample_step_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
+    hipLaunchKernelGGL(sample_step_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
                        t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
                        (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id, min_length, unfinished, alive);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+static bool grammar_tables_ok(const void* cls, const void* allow, const void* next, int C, const void* gstate) {
+    return cls && allow && next && gstate && C >= 1 && C <= 32;
+}
+
+extern "C" int mxl_sample_step_grammar(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev,
+                                       unsigned long long* rng_ctr, unsigned long long seed, int B, int do_sample, int top_k,
+                                       float top_p, float temperature, float repetition_penalty, float typical_p, const void* E,
+                                       void* emb_out, int d, float scale, int* counter, int eos_id, int pad_id, int min_length,
+                                       int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C,
+                                       int* gstate, void* stream) {
+    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
+    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
+    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
+    MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr) && B <= 32767);     // unfinished = NULL: no eos rule
+    MXL_CHECK_ARG(grammar_tables_ok(cls, allow, next, C, gstate));
+    if (!unfinished) { eos_id = -1; pad_id = 0; min_length = 0; }
+    hipLaunchKernelGGL(sample_step_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
+                       t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
+                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id, min_length, unfinished, alive,
+                       (const unsigned char*)cls, (const uint32_t*)allow, (const unsigned char*)next, C, gstate);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_grammar_mask(float* scores, int ldl, int B, int V, const void* cls, const void* allow, const int* gstate,
+                                void* stream) {
+    MXL_CHECK_ARG(scores && cls && allow && gstate && B > 0 && V > 0 && ldl >= V);
+    const long long n = (long long)B * V;
+    MXL_CHECK_ARG(n <= (1LL << 38));
+    hipLaunchKernelGGL(grammar_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V,
+                       (const unsigned char*)cls, (const uint32_t*)allow, gstate);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_grammar_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, const void* next,
+                                   int C, int* gstate, const int* unfinished, void* stream) {
+    MXL_CHECK_ARG(ids && t_dev && B > 0 && V > 0 && cls && next && gstate && C >= 1 && C <= 32);
+    hipLaunchKernelGGL(grammar_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const long long*)ids, ld_ids,
+                       t_dev, B, V, (const unsigned char*)cls, (const unsigned char*)next, C, gstate, unfinished);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_grammar_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* allow,
+                                const void* next, int C, int start, int* gstate, int* first_bad, void* stream) {
+    MXL_CHECK_ARG(ids && B > 0 && V > 0 && Tp >= 0 && ld_ids >= Tp && first_bad && start >= 0 && start < 256);
+    MXL_CHECK_ARG(grammar_tables_ok(cls, allow, next, C, gstate));
+    hipLaunchKernelGGL(grammar_scan_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const long long*)ids, ld_ids, Tp, B, V,
+                       (const unsigned char*)cls, (const uint32_t*)allow, (const unsigned char*)next, C, start, gstate, first_bad);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }

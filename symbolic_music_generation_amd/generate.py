@@ -77,6 +77,52 @@ def stop_width(ids: torch.Tensor, unfinished: torch.Tensor, prompt_len: int, max
     return prompt_len + int(first.max()) + 1
 
 
+def check_grammar_args(grammar, vocab_size: int, stop: Optional[tuple]):
+    """what generation under a grammar (grammar.TokenGrammar) needs on the host: the grammar classifies exactly the model's
+    vocabulary, and with min_length no reachable state allows the eos token alone -- min_length bars eos, which would leave such a
+    row with every token barred"""
+    if grammar is None:
+        return
+    if grammar.vocab_size != int(vocab_size):
+        raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the model has vocab_size {int(vocab_size)}')
+    if stop is not None and stop[2] > 0:
+        only = grammar.only_token_states(stop[0])
+        if only:
+            raise ValueError(f'min_length with a grammar whose state {grammar.state_names[only[0]]} allows only the eos token '
+                             f'{stop[0]}: below min_length that row would have every token barred')
+
+
+def raise_on_bad_prompt(grammar, ids: torch.Tensor, first_bad: torch.Tensor):
+    """first_bad (B,) from ops.grammar_scan over ids: raises MusicXLError naming row, column and token of the first prompt that
+    breaks the grammar (a constraint that starts from an undefined state guarantees nothing)"""
+    bad = first_bad.tolist()
+    for b, col in enumerate(bad):
+        if col >= 0:
+            tok = int(ids[b, col])
+            raise MusicXLError(f'the prompt of row {b} breaks the grammar at column {col}: token {tok} is not allowed there '
+                               f'({sum(1 for c in bad if c >= 0)} of {len(bad)} rows break it)')
+
+
+def check_grammar(ids: torch.Tensor, grammar, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B,) int64 on the CPU: for every row of ids (B, T) the column of the first token the grammar does not allow, -1 = the row
+    obeys it -- e.g. to verify the output of an unconstrained run.  attention_mask (B, Tp): left-pad columns (0) are skipped.  Rows
+    on the GPU are walked there (mxl_grammar_scan), host tensors by TokenGrammar.walk."""
+    ids = torch.as_tensor(ids)
+    if ids.dim() == 1:
+        ids = ids.view(1, -1)
+    x = ids.to(torch.int64).clone()
+    if attention_mask is not None:
+        m = torch.as_tensor(attention_mask).to(x.device)
+        x[:, :m.shape[1]].masked_fill_(m == 0, -1)
+    if not x.is_cuda:
+        return torch.tensor([grammar.walk(r)[1] for r in x], dtype=torch.int64)
+    x = x.contiguous()
+    gstate = torch.empty(x.shape[0], device=x.device, dtype=torch.int32)
+    bad = torch.empty_like(gstate)
+    ops.grammar_scan(x, x.shape[1], grammar, gstate, bad)
+    return bad.cpu().to(torch.int64)
+
+
 class _AlivePoll:
     """live-row counts of one decoder read back without stalling its stream: after each chunk of steps a non-blocking copy of
     `alive` into pinned host memory and an event; `wait(keep)` blocks until at most `keep` such reads are outstanding"""
@@ -181,6 +227,11 @@ class XLDecoder:
         self.alive = torch.zeros(1, device=dev, dtype=torch.int32)
         self._stop = None
         self.steps_run = 0                              # decode steps issued by the last generate() (early exit: fewer)
+        # grammar-constrained decoding (generate(grammar=...)): the automaton state of every row, advanced by the sampler launch;
+        # `gbad`: first prompt column that breaks the grammar (read once after the prompt pass)
+        self.gstate = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self.gbad = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self._grammar = None
 
     def _tables(self):
         if self.rd is None:
@@ -198,14 +249,19 @@ class XLDecoder:
         self.graph = None
 
     # ---------------------------------------------------------------- prompt
-    def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None):
+    def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None,
+                grammar=None):
         """Whole prompt through the training-shape kernels with zero mems (upstream first step), rings filled from the
         per-layer qkv buffers, first new token sampled from the last position.
         n_pad: (B,) int32 device tensor, left-padded prompts: the first n_pad[b] columns of row b are pads.  Their K / V are zero
         in every layer (= extra zero-memory slots, so each row computes what it computes alone), they are embedded as id 0 and
         held as -1 in `ids`, which the samplers' repetition penalty skips.
-        stop: (eos, pad, min_length) or None (stop_config); every row starts live, and the first token sampled here counts."""
+        stop: (eos, pad, min_length) or None (stop_config); every row starts live, and the first token sampled here counts.
+        grammar: a grammar.TokenGrammar or None; every row's state after its prompt is computed on the device (pads skipped), and a
+        prompt that breaks the grammar raises."""
         e, c = self.eng, self.eng.cfg
+        check_grammar_args(grammar, c.vocab_size, stop)
+        self._grammar = grammar
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
         self._tables()
@@ -222,6 +278,8 @@ class XLDecoder:
             pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
             self.ids[:, :Tp].masked_fill_(pad, -1)
             x = x.masked_fill(pad, 0)
+        if grammar is not None:
+            ops.grammar_scan(self.ids, Tp, grammar, self.gstate, self.gbad)
         sink_kc, sink_vc = self.kc, self.vc
 
         def kv_sink(l, qkv):
@@ -239,6 +297,8 @@ class XLDecoder:
             ops.adaptive_logprob(last, self.logp, B, c.vocab_size, tuple(c.cutoffs))
         self.t_dev.fill_(Tp - 1)
         self._trace()
+        if grammar is not None:
+            raise_on_bad_prompt(grammar, self.ids, self.gbad)
         if sampling is not None:                       # None: the caller picks the token from self.logp (beam search)
             self._sample_advance(self.logp, sampling)  # t = Tp: position of the token just sampled
         return out
@@ -248,7 +308,25 @@ class XLDecoder:
         position and RNG counters advanced.  Short chain: the same launch leaves the token's embedding row in h[0] for the next step."""
         c = self.eng.cfg
         stop = self._stop
-        if self.fused_sampler and stop is None:
+        g = self._grammar
+        if g is not None and self.fused_sampler:     # mask, eos rule and state advance ride on the sampler launch
+            ops.sample_step_grammar(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
+                                    self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model),
+                                    self.step_ctr, g, self.gstate, stop, self.unfinished, self.alive, **sampling)
+        elif g is not None:
+            # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the
+            # mask: -inf stays -inf under it, so the result is the same
+            sc = scores[:, :c.vocab_size] if scores.shape[1] != c.vocab_size else scores
+            if stop is not None:
+                ops.mask_eos_below(sc, c.vocab_size, self.t_dev, stop)
+            ops.grammar_mask(sc, c.vocab_size, g, self.gstate)
+            ops.sample(sc, self.ids, self.t_dev, self.rng, self.seed, **sampling)
+            ops.decode_advance(self.t_dev, self.rng)
+            # before the stop rule: `unfinished` still tells which rows chose their token (the others stay frozen)
+            ops.grammar_advance(self.ids, self.t_dev, g, self.gstate, None if stop is None else self.unfinished)
+            if stop is not None:
+                ops.decode_stop(self.ids, self.t_dev, stop, self.unfinished, self.alive)
+        elif self.fused_sampler and stop is None:
             ops.sample_step(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
                             self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model), self.step_ctr,
                             **sampling)
@@ -363,26 +441,28 @@ class XLDecoder:
 
     # ---------------------------------------------------------------- loop
     def begin(self, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool = True,
-              n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None) -> int:
+              n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None, grammar=None) -> int:
         """prompt pass + first sampled token + (use_graph) capture of one decode step; returns the number of `replay_once()`
         calls that complete the generation to max_length.  n_pad: left-padded prompts (prefill); the decode step is the same,
-        every row's last prompt token sits at column Tp - 1.  stop: (eos, pad, min_length) (stop_config) or None"""
+        every row's last prompt token sits at column Tp - 1.  stop: (eos, pad, min_length) (stop_config) or None.  grammar: a
+        grammar.TokenGrammar or None; the captured step reads its device tables, so their identity is part of the graph key"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         self._sampling = sampling
         self._use_graph = use_graph
-        self.prefill(prompt, sampling, n_pad, stop)
+        self.prefill(prompt, sampling, n_pad, stop, grammar)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
             # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
             # itself is written by the captured launches): a graph captured without a trace would replay without writing one
             key = (tuple(sorted(sampling.items())), self.fused_sampler,
-                   None if self.trace is None else self.trace.data_ptr(), stop)
+                   None if self.trace is None else self.trace.data_ptr(), stop,
+                   None if grammar is None else tuple(t.data_ptr() for t in grammar.to(self.eng.dev)) + (grammar.n_classes,))
             if self.graph is None or self._graph_key != key:
                 # warm-up on a side stream (first launches set function attributes), then capture one step
                 state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(),
                          [k.clone() for k in self.kc], [v.clone() for v in self.vc], self.h[0].clone(),
-                         self.unfinished.clone(), self.alive.clone())
+                         self.unfinished.clone(), self.alive.clone(), self.gstate.clone())
                 s = torch.cuda.Stream()
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
@@ -399,7 +479,7 @@ class XLDecoder:
                 for a, b in zip(self.vc, state[4]):
                     a.copy_(b)
                 self.h[0].copy_(state[5])         # (short chain: the next step's embedding row is step state too)
-                self.unfinished.copy_(state[6]); self.alive.copy_(state[7])
+                self.unfinished.copy_(state[6]); self.alive.copy_(state[7]); self.gstate.copy_(state[8])
         return max(steps, 0)
 
     def replay_once(self):
@@ -413,14 +493,16 @@ class XLDecoder:
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
                  typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
-                 stop_chunk: int = STOP_CHUNK) -> torch.Tensor:
+                 stop_chunk: int = STOP_CHUNK, grammar=None) -> torch.Tensor:
         """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
         [OMIT]) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (prefill); the
         prompt columns, pads included, come back as given.
         eos_token_id (opt-in): HF greedy_search / sample stopping -- a row that emits eos is finished and emits pad_token_id
         (default: eos) from then on, the call ends once every row has finished, and the output is cut to the width of the
         longest row (finish_at_eos); min_length bars eos below that width.  The decode steps are replayed in chunks of
-        `stop_chunk` with the live-row count read back one chunk late (run_until_finished): no per-step host round trip."""
+        `stop_chunk` with the live-row count read back one chunk late (run_until_finished): no per-step host round trip.
+        grammar (a grammar.TokenGrammar, e.g. `tokenizer.grammar()`): every row may only emit tokens its grammar state allows; the
+        state lives on the device and moves inside the sampler launch of the captured step.  The prompts must obey the grammar."""
         sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0,
                         temperature=temperature, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
                         typical_p=1.0 if typical_p is None else typical_p)
@@ -428,7 +510,7 @@ class XLDecoder:
         Tp = prompt.shape[1]
         if max_length - Tp <= 0:
             return prompt[:, :max_length]
-        n = self.begin(prompt, max_length, sampling, use_graph, n_pad, stop)
+        n = self.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar)
         if stop is None:
             for _ in range(n):
                 self.replay_once()
@@ -463,9 +545,10 @@ class XLDecoderLanes:
         for d in self.lanes:
             d.invalidate_tables()
 
-    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None) -> int:
+    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None, grammar=None) -> int:
         steps = [d.begin(prompt[self.offs[i]:self.offs[i + 1]], max_length, sampling, use_graph,
-                         None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]], stop) for i, d in enumerate(self.lanes)]
+                         None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]], stop, grammar)
+                 for i, d in enumerate(self.lanes)]
         for s in self.streams:                       # the lanes start from the prompt passes and captures issued above
             s.wait_stream(torch.cuda.current_stream())
         return steps[0]
@@ -481,8 +564,8 @@ class XLDecoderLanes:
 
     def generate(self, prompt, max_length, do_sample=False, top_k=None, top_p=None, temperature=1.0, repetition_penalty=None,
                  typical_p=None, use_graph=True, n_pad=None, eos_token_id=None, pad_token_id=None, min_length=None,
-                 stop_chunk=STOP_CHUNK) -> torch.Tensor:
-        """XLDecoder.generate over the lanes.  With eos_token_id every lane stops on its own; the output is the lanes' rows cut to
+                 stop_chunk=STOP_CHUNK, grammar=None) -> torch.Tensor:
+        """XLDecoder.generate over the lanes (each lane keeps the grammar state of its own rows).  With eos_token_id every lane stops on its own; the output is the lanes' rows cut to
         the common width and right-filled with pad where a lane stopped earlier."""
         sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0,
                         temperature=temperature, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
@@ -491,7 +574,7 @@ class XLDecoderLanes:
         Tp = prompt.shape[1]
         if max_length - Tp <= 0:
             return prompt[:, :max_length]
-        n = self.begin(prompt, max_length, sampling, use_graph, n_pad, stop)
+        n = self.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar)
         if stop is None:
             for _ in range(n):
                 self.replay_once()

@@ -175,6 +175,70 @@ def mask_eos_below(scores, V, t_dev, stop):
                                    _stream()), 'mxl_mask_eos_below')
 
 
+def _grammar_tables(grammar, device, V):
+    """(cls, allow, next) device tensors of a grammar.TokenGrammar, checked against the vocabulary the scores span"""
+    if grammar.vocab_size != int(V):
+        raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
+    return grammar.to(device)
+
+
+def sample_step_grammar(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, grammar, gstate, stop=None, unfinished=None,
+                        alive=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0):
+    """sample_step / sample_step_stop under a grammar.TokenGrammar: barred tokens masked and gstate (B,) int32 advanced in the same
+    single launch (mxl_sample_step_grammar).  stop = (eos, pad, min_length) with unfinished / alive, or None: no eos rule."""
+    B = scores.shape[0]
+    _req(gstate, torch.int32, 'sample_step_grammar gstate')
+    if gstate.numel() != B:
+        raise MusicXLError(f'gstate holds {gstate.numel()} rows, the scores {B}')
+    cls, allow, nxt = _grammar_tables(grammar, scores.device, V)
+    eos, pad, min_length = stop if stop is not None else (-1, 0, 0)
+    if stop is not None and (unfinished is None or alive is None):
+        raise MusicXLError('sample_step_grammar: the eos rule needs unfinished and alive')
+    check(lib().mxl_sample_step_grammar(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
+                                        int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0),
+                                        float(temperature), float(repetition_penalty if repetition_penalty is not None else 1.0),
+                                        float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
+                                        float(scale), _p(counter), int(eos), int(pad), int(min_length or 0),
+                                        _p(unfinished) if stop is not None else 0, _p(alive) if stop is not None else 0,
+                                        _p(cls), _p(allow), _p(nxt), grammar.n_classes, _p(gstate), _stream()),
+          'mxl_sample_step_grammar')
+
+
+def grammar_mask(scores, V, grammar, gstate):
+    """before sample: scores[b, v] = -inf in place for every token the grammar bars in state gstate[b] (mxl_grammar_mask)"""
+    _req(scores, torch.float32, 'grammar_mask scores'); _req(gstate, torch.int32, 'grammar_mask gstate')
+    B = scores.shape[0]
+    if scores.shape[1] < V or scores.stride(1) != 1 or gstate.numel() != B:
+        raise MusicXLError('grammar_mask: scores must be (B, >= V) with unit column stride and gstate (B,)')
+    cls, allow, _ = _grammar_tables(grammar, scores.device, V)
+    check(lib().mxl_grammar_mask(_p(scores), scores.stride(0), B, int(V), _p(cls), _p(allow), _p(gstate), _stream()), 'mxl_grammar_mask')
+
+
+def grammar_advance(ids, t_dev, grammar, gstate, unfinished=None):
+    """after sample + decode_advance and before decode_stop: gstate[b] moves along the token at ids[b, t]; rows with
+    unfinished[b] == 0 keep their state (mxl_grammar_advance)"""
+    _req(gstate, torch.int32, 'grammar_advance gstate')
+    B = ids.shape[0]
+    if gstate.numel() != B or ids.dtype != torch.int64:
+        raise MusicXLError('grammar_advance: ids must be (B, .) int64 and gstate (B,)')
+    cls, _, nxt = grammar.to(ids.device)
+    check(lib().mxl_grammar_advance(_p(ids), ids.stride(0), _p(t_dev), B, grammar.vocab_size, _p(cls), _p(nxt), grammar.n_classes,
+                                    _p(gstate), _p(unfinished), _stream()), 'mxl_grammar_advance')
+
+
+def grammar_scan(ids, Tp, grammar, gstate, first_bad, start=None):
+    """gstate[b] = state of row b after columns 0..Tp-1 of ids (ids < 0 skipped), first_bad[b] = column of its first violation or
+    -1 (mxl_grammar_scan); the host reference is TokenGrammar.walk"""
+    _req(gstate, torch.int32, 'grammar_scan gstate'); _req(first_bad, torch.int32, 'grammar_scan first_bad')
+    B = ids.shape[0]
+    if ids.dtype != torch.int64 or ids.stride(1) != 1 or Tp > ids.shape[1] or gstate.numel() != B or first_bad.numel() != B:
+        raise MusicXLError('grammar_scan: ids must be (B, >= Tp) int64 rows, gstate and first_bad (B,)')
+    cls, allow, nxt = grammar.to(ids.device)
+    check(lib().mxl_grammar_scan(_p(ids), ids.stride(0), int(Tp), B, grammar.vocab_size, _p(cls), _p(allow), _p(nxt),
+                                 grammar.n_classes, grammar.start if start is None else int(start), _p(gstate), _p(first_bad),
+                                 _stream()), 'mxl_grammar_scan')
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, relu=False, out=None,
            out_f32=False, drop_p=0.0, seed=0, site=0) -> torch.Tensor:
     """y = x @ w.T (+bias)(relu)(dropout); x (N, K) bf16, w (O, K) bf16."""

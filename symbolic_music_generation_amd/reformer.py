@@ -163,14 +163,22 @@ class MyReformerModelWithLMHead(EngineModule):
         eos_token_id / pad_token_id / min_length / max_new_tokens: stopping at eos for greedy decoding and sampling, opt-in, as
         MyTransfoXLLMHeadModel.generate (HF greedy_search / sample: finished rows emit pad, the call ends once every row has
         finished, the output is cut to the longest row).  Beam and group-beam search take an explicit eos / pad in place of the
-        config's."""
+        config's.
+
+        grammar (a `grammar.TokenGrammar`): greedy decoding and sampling in which every row may only emit tokens its grammar state
+        allows, as MyTransfoXLLMHeadModel.generate: the mask runs on the device before the sampler, the state advance after it."""
         from . import ops
-        from .generate import STOP_CHUNK, left_pad_counts, resolve_max_length, stop_config, stop_width
+        from .generate import (STOP_CHUNK, check_grammar_args, left_pad_counts, raise_on_bad_prompt, resolve_max_length, stop_config,
+                               stop_width)
         eos_token_id = unsupported.pop('eos_token_id', None)
         pad_token_id = unsupported.pop('pad_token_id', None)
         min_length = unsupported.pop('min_length', None)
         max_new_tokens = unsupported.pop('max_new_tokens', None)
+        grammar = unsupported.pop('grammar', None)
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
+        check_grammar_args(grammar, self.config.vocab_size, stop)
+        if grammar is not None and ((unsupported.get('num_beams', 1) or 1) > 1 or (unsupported.get('num_beam_groups', 1) or 1) != 1):
+            raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam or group-beam search')
         eos_b = self.config.eos_token_id if eos_token_id is None else eos_token_id          # beam / group-beam search
         pad_b = self.config.pad_token_id if pad_token_id is None else pad_token_id
         mask = unsupported.pop('attention_mask', None)
@@ -264,7 +272,7 @@ class MyReformerModelWithLMHead(EngineModule):
                 dec.rotations = rotations
                 dec.seed = seed
                 return dec.generate(ids0, max_length, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
-                                    repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop)
+                                    repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop, grammar=grammar)
             V = c.vocab_size
             pad = getattr(c, 'pad_token_id', None)
             pad = 0 if pad is None else int(pad)
@@ -274,16 +282,25 @@ class MyReformerModelWithLMHead(EngineModule):
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
             unfinished = torch.ones(B, device=self.device, dtype=torch.int32)
             alive = torch.zeros(1, device=self.device, dtype=torch.int32)
+            if grammar is not None:
+                gstate = torch.empty(B, device=self.device, dtype=torch.int32)
+                gbad = torch.empty(B, device=self.device, dtype=torch.int32)
+                ops.grammar_scan(buf, Tp, grammar, gstate, gbad)
+                raise_on_bad_prompt(grammar, buf, gbad)
             for cur in range(Tp, max_length):
                 Tf = cur if cur <= 64 else (cur + 63) // 64 * 64
                 out = self.engine.forward(buf[:, :Tf].contiguous(), labels=None, train=False)
                 last = out['logits'][:, cur - 1].contiguous()
                 if stop is not None:
                     ops.mask_eos_below(last[:, :V], V, t_dev, stop)
+                if grammar is not None:
+                    ops.grammar_mask(last[:, :V], V, grammar, gstate)
                 ops.sample(last, buf, t_dev, rng, seed, do_sample=do_sample, top_k=top_k or 0,
                            top_p=top_p if top_p is not None else 1.0, temperature=temperature,
                            repetition_penalty=repetition_penalty, typical_p=typical_p)
                 ops.decode_advance(t_dev, rng)
+                if grammar is not None:
+                    ops.grammar_advance(buf, t_dev, grammar, gstate, None if stop is None else unfinished)
                 if stop is not None:
                     ops.decode_stop(buf, t_dev, stop, unfinished, alive)
                 if Tf > cur:

@@ -71,6 +71,10 @@ class RFDecoder:
         self.alive = torch.zeros(1, device=dev, dtype=torch.int32)
         self._stop = None
         self.steps_run = 0
+        # grammar-constrained decoding (generate(grammar=...)): the automaton state of every row (generate.XLDecoder)
+        self.gstate = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self.gbad = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self._grammar = None
 
     # ---------------------------------------------------------------- hashing helpers
     def _factors(self, T_hint: Optional[int] = None):
@@ -99,16 +103,21 @@ class RFDecoder:
         return r
 
     # ---------------------------------------------------------------- prompt
-    def prefill(self, prompt: torch.Tensor, sampling: dict, stop: Optional[tuple] = None):
+    def prefill(self, prompt: torch.Tensor, sampling: dict, stop: Optional[tuple] = None, grammar=None):
+        from .generate import check_grammar_args, raise_on_bad_prompt
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and 1 <= Tp <= self.Tmax
+        check_grammar_args(grammar, c.vocab_size, stop)
         self._stop = stop
+        self._grammar = grammar
         self.unfinished.fill_(1)
         self.alive.fill_(B)
         d, H = c.hidden_size, c.num_attention_heads
         self.ids.zero_()
         self.ids[:, :Tp].copy_(prompt)
+        if grammar is not None:
+            ops.grammar_scan(self.ids, Tp, grammar, self.gstate, self.gbad)
         for l in self.bk:
             self.n_bucketed[l] = 0
             self.bkmax[l].zero_()
@@ -136,6 +145,8 @@ class RFDecoder:
         out = e.forward(buf, labels=None, train=False, rotations=rot, n_real=Tp if Tf > Tp else None, layer_sink=sink)
         last = out['logits'][:, Tp - 1].contiguous()
         self.t_dev.fill_(Tp - 1)
+        if grammar is not None:
+            raise_on_bad_prompt(grammar, self.ids, self.gbad)
         self._sample(last, sampling)
         return out
 
@@ -148,8 +159,13 @@ class RFDecoder:
         V = self.eng.cfg.vocab_size
         if self._stop is not None:          # min_length: eos barred below it (after the trace above)
             ops.mask_eos_below(logits[:, :V], V, self.t_dev, self._stop)
+        g = self._grammar
+        if g is not None:                    # barred tokens -inf before the sampler (its repetition penalty keeps -inf at -inf)
+            ops.grammar_mask(logits[:, :V], V, g, self.gstate)
         ops.sample(logits[:, :V], self.ids, self.t_dev, self.rng, self.seed, **sampling)
         ops.decode_advance(self.t_dev, self.rng)
+        if g is not None:                    # before the stop rule: rows finished before this step keep their state
+            ops.grammar_advance(self.ids, self.t_dev, g, self.gstate, None if self._stop is None else self.unfinished)
         if self._stop is not None:
             ops.decode_stop(self.ids, self.t_dev, self._stop, self.unfinished, self.alive)
 
@@ -257,10 +273,12 @@ class RFDecoder:
     @torch.no_grad()
     def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
-                 typical_p: Optional[float] = None, stop: Optional[tuple] = None, stop_chunk: int = 16) -> torch.Tensor:
+                 typical_p: Optional[float] = None, stop: Optional[tuple] = None, stop_chunk: int = 16,
+                 grammar=None) -> torch.Tensor:
         """(B, max_length) ids = prompt + continuation.  stop = (eos, pad, min_length) (generate.stop_config): rows finish at eos
         and the loop ends once none is live -- the live-row count is read back every `stop_chunk` steps, one chunk late
-        (generate.run_until_finished) -- and the output is cut to the longest row."""
+        (generate.run_until_finished) -- and the output is cut to the longest row.  grammar: a grammar.TokenGrammar; every row may
+        only emit tokens its grammar state allows (mask before the sampler, state advance after it, both on the device)."""
         from .generate import run_until_finished, stop_width
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
@@ -269,7 +287,7 @@ class RFDecoder:
         Tp = prompt.shape[1]
         if max_length <= Tp:
             return prompt[:, :max_length]
-        self.prefill(prompt.to(self.eng.dev), sampling, stop)
+        self.prefill(prompt.to(self.eng.dev), sampling, stop, grammar)
         if stop is None:
             for t in range(Tp, max_length - 1):
                 self.step(t, sampling)

@@ -137,6 +137,10 @@ class PairMergeTokenizer(MusicTokenizer):
             raise ValueError('the tokenizer file was trained on a different base vocabulary')
         return ret
 
+    def grammar(self):
+        raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders (a pitch with its '
+                                  'duration, a whole tuplet), so the music grammar over token classes does not apply')
+
     @property
     def vocab_size(self) -> int:
         return self.original_vocab_size + self.added_vocab_size
@@ -314,6 +318,10 @@ class WordPieceMusicTokenizer(MusicTokenizer):
         if meta.get('tok2id') and meta['tok2id'] != ret.vocab.tok2id:
             raise ValueError('the tokenizer file was trained on a different base vocabulary')
         return ret
+
+    def grammar(self):
+        raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders (a pitch with its '
+                                  'duration, a whole tuplet), so the music grammar over token classes does not apply')
 
     @property
     def vocab_size(self) -> int:

@@ -198,7 +198,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  renormalize_logits=None, num_return_sequences: int = 1, num_beam_groups: int = 1, length_penalty: float = 1.0,
                  use_graph: bool = True, seed: int = 77, attention_mask: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
-                 min_length: Optional[int] = None, **unused) -> torch.Tensor:
+                 min_length: Optional[int] = None, grammar=None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -215,9 +215,17 @@ class MyTransfoXLLMHeadModel(EngineModule):
         sample: a row that emits eos emits pad from then on (`pad_token_id`, else the config's, else eos), the call returns once
         every row has finished, cut to the longest row; `min_length` bars eos while a row is shorter.  `max_new_tokens` = n on an
         unpadded batch is max_length = prompt length + n (both given: ValueError, as HF).  Beam, group-beam and contrastive search
-        keep their own eos handling, with an explicit eos_token_id / pad_token_id in place of the config's."""
-        from .generate import (XLDecoder, XLDecoderLanes, beam_search, contrastive_search, group_beam_search, left_pad_counts,
-                               resolve_max_length, stop_config)
+        keep their own eos handling, with an explicit eos_token_id / pad_token_id in place of the config's.
+
+        `grammar` (a `grammar.TokenGrammar`, e.g. `tokenizer.grammar()`): greedy decoding and sampling in which every row may only
+        emit tokens that its grammar state allows, so the output parses (`TimeSig Tempo [Key] (<bar> <melody> .. <bass> ..)* </s>`,
+        a pitch before its duration, closed tuplets).  The state of every row is kept on the device and moves inside the sampler
+        launch; barred tokens are masked after the repetition penalty and `min_length` and before the warpers, as an HF logits
+        processor would.  It combines with `num_return_sequences`, padded prompts, `eos_token_id` / `min_length` /
+        `max_new_tokens`; the prompts must obey the grammar themselves (MusicXLError otherwise).  The constraint is syntactic: it
+        does not make the durations of a bar add up.  Beam, group-beam and contrastive search take no grammar."""
+        from .generate import (XLDecoder, XLDecoderLanes, beam_search, check_grammar_args, contrastive_search, group_beam_search,
+                               left_pad_counts, resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -235,10 +243,14 @@ class MyTransfoXLLMHeadModel(EngineModule):
         pad_b = self.config.pad_token_id if pad_token_id is None else pad_token_id
         self._maybe_resync()
         max_length = resolve_max_length(max_length, max_new_tokens, input_ids.shape[1], self.config.max_length_)
+        check_grammar_args(grammar, self.config.vocab_size, stop)
         contrastive = penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and not do_sample and num_beams == 1
         if n_pad is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('padded prompts (attention_mask with zeros) are supported for greedy decoding and sampling only, not '
                                'for beam, group-beam or contrastive search')
+        if grammar is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
+            raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam, group-beam or '
+                               'contrastive search')
         if contrastive:
             dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
@@ -278,5 +290,5 @@ class MyTransfoXLLMHeadModel(EngineModule):
         dec.invalidate_tables()
         return dec.generate(input_ids.to(self.device), max_length, do_sample=do_sample, top_k=top_k, top_p=top_p,
                             temperature=temperature, repetition_penalty=repetition_penalty, typical_p=typical_p,
-                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device),
+                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device), grammar=grammar,
                             **({} if stop is None else dict(eos_token_id=stop[0], pad_token_id=stop[1], min_length=stop[2])))

@@ -172,6 +172,11 @@ class MusicVocabulary:
     def i2t(self, id_: int) -> str:
         return self.id2tok[int(id_)]
 
+    def grammar(self):
+        """the token grammar of a well-formed song over this vocabulary (grammar.music_grammar), for `generate(grammar=...)`"""
+        from .grammar import music_grammar
+        return music_grammar(self)
+
 
 class MusicTokenizer:
     """Whitespace split -> `t2i`; `model_input_names = ['input_ids']` so no attention mask is ever produced
@@ -197,6 +202,10 @@ class MusicTokenizer:
 
     def __len__(self):
         return len(self.vocab)
+
+    def grammar(self):
+        """the token grammar of a well-formed song (`MusicVocabulary.grammar`), for `model.generate(grammar=...)`"""
+        return self.vocab.grammar()
 
     def tokenize(self, text: str) -> List[str]:
         return text.split()

@@ -1,0 +1,437 @@
+"""Grammar-constrained generation (`generate(grammar=...)`): every row may only emit tokens its grammar state allows, with the
+state kept and advanced on the device inside the sampler launch.  Small random-weight models (V = 1190, the degree vocabulary):
+unconstrained they break the music grammar at once, constrained every row walks clean under the walker spelled out in
+tests/test_grammar_cpu.py; the graph-replayed fused run equals, bit for bit, an eager loop that masks the log-probabilities on the
+host and calls the plain sampler; and the paths (fused / unfused / large vocabulary / Reformer, graph / eager, lanes, padded
+prompts, eos) agree with one another."""
+import numpy as np
+import pytest
+import torch
+
+from symbolic_music_generation_amd.generate import finish_at_eos
+from symbolic_music_generation_amd.vocab import MusicVocabulary
+from tests.test_grammar_cpu import GOLD, TABLE, token_class, walk
+
+pytestmark = pytest.mark.gpu
+
+V = 1190
+NEAR_TIE = 5e-2          # tests/test_ragged_generate_gpu.py: a fork between batch shapes is legitimate only at a bf16 near-tie
+VOC = MusicVocabulary(pitch_kind='degree')
+CLASS_OF = [token_class(VOC, i) for i in range(V)]
+HEADER = [VOC.t2i(t) for t in ('TimeSig_4/4', 'Tempo_120', 'Key_CMajor', '<bar>')]
+EOS, PAD, BAR, BASS = (VOC.t2i(t) for t in ('</s>', '[PAD]', '<bar>', '<bass>'))
+
+
+def _model(dev, seed, closing_bias=0.0, **kw):
+    """the test pair of tests/test_xl_model_gpu.py; closing_bias raises the head's bias of <bass>, <bar> and </s>, so that rows
+    close their bars and reach the end of the song within a few dozen tokens"""
+    from tests.test_xl_model_gpu import _pair
+    kw.setdefault('max_length', 200)
+    ref, m = _pair(dev, n_layer=2, mem_len=64, seed=seed, **kw)
+    if closing_bias:
+        with torch.no_grad():
+            b = ref.crit.out_layers[0].bias
+            b[BASS] += closing_bias
+            b[BAR] += closing_bias - 2.0
+            b[EOS] += closing_bias
+        m.load_state_dict(ref.state_dict())
+    return ref, m
+
+
+def _header(B, dev):
+    return torch.tensor([HEADER] * B, dtype=torch.int64, device=dev)
+
+
+def _bad_columns(out, mask=None):
+    """first violation of every row under the test's walker (-1 = clean); mask: left-pad columns are skipped"""
+    rows = out.cpu().clone()
+    if mask is not None:
+        rows[:, :mask.shape[1]].masked_fill_(mask.cpu() == 0, -1)
+    return [walk(VOC, r)[1] for r in rows.tolist()]
+
+
+def _states(out):
+    return [walk(VOC, r)[0] for r in out.cpu().tolist()]
+
+
+def _allowed_mask(state):
+    ok = set(TABLE[state])
+    return torch.tensor([c in ok for c in CLASS_OF])
+
+
+def _fresh(m, B, L, seed=5):
+    from symbolic_music_generation_amd.generate import XLDecoder
+    return XLDecoder(m.engine, B, L, seed=seed)
+
+
+SAMPLE = dict(do_sample=True, temperature=1.5, top_k=0)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the feature
+@pytest.mark.parametrize('kw', [SAMPLE, dict(do_sample=False)], ids=['sample', 'greedy'])
+def test_rows_walk_clean_only_with_the_grammar(dev, kw):
+    """fails without the feature: `grammar=` used to be swallowed by generate's **unused"""
+    ref, m = _model(dev, 300)
+    m.eval()
+    B, Tp, N = 16, len(HEADER), 130
+    ids = _header(B, dev)
+    g = VOC.grammar()
+    m._decoder = None
+    got = m.generate(input_ids=ids, max_new_tokens=N, grammar=g, **kw)
+    assert got.shape == (B, Tp + N) and torch.equal(got[:, :Tp], ids)
+    assert _bad_columns(got) == [-1] * B
+    m._decoder = None
+    free = m.generate(input_ids=ids, max_new_tokens=N, **kw)
+    bad = _bad_columns(free)
+    assert all(c >= Tp for c in bad), bad                          # every unconstrained row breaks the grammar
+    # generate.check_grammar: the same columns, computed on the device
+    from symbolic_music_generation_amd.generate import check_grammar
+    assert check_grammar(free, g).tolist() == bad and check_grammar(got, g).tolist() == [-1] * B
+    assert check_grammar(free.cpu(), g).tolist() == bad
+
+
+# ---------------------------------------------------------------------------------------------------------------- exactness
+def _host_masked_loop(m, prompt, L, seed, sampling):
+    """the reference: per step the decoder's log-probabilities, masked on the host with the test's walker, through the existing
+    unfused sampler and counter advance"""
+    from symbolic_music_generation_amd import ops
+    dec = _fresh(m, prompt.shape[0], L, seed)
+    Tp = prompt.shape[1]
+    dec.prefill(prompt, None)                                       # prompt pass only: dec.logp = log-probs of position Tp
+    masks = {s: _allowed_mask(s).to(prompt.device) for s in TABLE}
+    states = _states(prompt)
+    for t in range(Tp, L):
+        lp = dec.logp.clone()
+        keep = torch.stack([masks[s] for s in states])
+        lp.masked_fill_(~keep, float('-inf'))
+        ops.sample(lp, dec.ids, dec.t_dev, dec.rng, dec.seed, **sampling)
+        ops.decode_advance(dec.t_dev, dec.rng)
+        toks = dec.ids[:, t].tolist()
+        states = [TABLE[s][CLASS_OF[k]] for s, k in zip(states, toks)]
+        if t + 1 < L:
+            dec._forward_token(embed=True, want_logp=True)
+    return dec.ids[:, :L].clone()
+
+
+@pytest.mark.parametrize('kw', [dict(do_sample=False), dict(do_sample=True, temperature=1.5, top_k=0),
+                                dict(do_sample=True, top_k=40, top_p=0.9, repetition_penalty=1.2)],
+                         ids=['greedy', 'sample', 'sample-topk-topp-penalty'])
+def test_fused_graph_run_equals_host_masked_eager_loop(dev, kw):
+    ref, m = _model(dev, 301)
+    m.eval()
+    B, L = 6, 110
+    prompt = _header(B, dev)
+    sampling = dict(do_sample=kw['do_sample'], top_k=kw.get('top_k', 0), top_p=kw.get('top_p', 1.0),
+                    temperature=kw.get('temperature', 1.0), repetition_penalty=kw.get('repetition_penalty', 1.0), typical_p=1.0)
+    want = _host_masked_loop(m, prompt, L, 5, sampling)
+    assert _bad_columns(want) == [-1] * B
+    dec = _fresh(m, B, L, 5)
+    assert dec.fused_sampler
+    got = dec.generate(prompt, L, use_graph=True, grammar=VOC.grammar(), **kw)
+    assert dec.graph is not None
+    assert torch.equal(got, want)
+    # the state the device holds is the state of the walk
+    names = VOC.grammar().state_names
+    assert [names[s] for s in dec.gstate.tolist()] == _states(got)
+
+
+def test_equal_across_fused_unfused_graph_eager(dev, monkeypatch):
+    ref, m = _model(dev, 302)
+    m.eval()
+    B, L = 6, 120
+    prompt = _header(B, dev)
+    g = VOC.grammar()
+    for kw in (dict(do_sample=False), SAMPLE, dict(do_sample=True, top_k=8, typical_p=0.9)):
+        outs = []
+        for unfused in (False, True):
+            monkeypatch.setenv('MXL_DECODE_UNFUSED', '1' if unfused else '0')
+            for use_graph in (True, False):
+                dec = _fresh(m, B, L, 7)
+                assert dec.fused_sampler == (not unfused)
+                outs.append(dec.generate(prompt, L, use_graph=use_graph, grammar=g, **kw))
+        assert _bad_columns(outs[0]) == [-1] * B, kw
+        for o in outs[1:]:
+            assert torch.equal(o, outs[0]), kw
+
+
+def test_lanes_equal_their_decoders(dev):
+    """B = 32 through model.generate takes two lanes; each lane keeps the state of its own rows and equals a single decoder with
+    the lane's seed on the lane's rows"""
+    from symbolic_music_generation_amd.generate import XLDecoderLanes
+    ref, m = _model(dev, 303)
+    m.eval()
+    B, L = 32, 100
+    prompt = _header(B, dev)
+    prompt[1::2, 2] = VOC.t2i('Key_AMinor')
+    g = VOC.grammar()
+    for kw in (SAMPLE, dict(do_sample=False)):
+        m._decoder = None
+        out = m.generate(input_ids=prompt, max_length=L, seed=11, grammar=g, **kw)
+        assert type(m._decoder).__name__ == 'XLDecoderLanes'
+        assert _bad_columns(out) == [-1] * B
+        lanes = XLDecoderLanes(m.engine, B, L, seed=11, lanes=2)
+        assert torch.equal(lanes.generate(prompt, L, grammar=g, **kw), out)
+        for i in range(2):
+            rows = slice(lanes.offs[i], lanes.offs[i + 1])
+            one = _fresh(m, lanes.sizes[i], L, 11 + 7919 * i).generate(prompt[rows], L, grammar=g, **kw)
+            assert torch.equal(out[rows], one), (kw, i)
+
+
+def test_left_padded_rows_equal_the_prompt_alone(dev):
+    from symbolic_music_generation_amd.generate import left_pad
+    ref, m = _model(dev, 304)
+    ref.eval(); m.eval()
+    song = torch.from_numpy(np.load(GOLD)['sample_full_degree'].astype(np.int64))
+    prompts = [song[:n] for n in (4, 9, 17, 30, 12, 6)]
+    ids, mask = left_pad(prompts, PAD)
+    ids, mask = ids.to(dev), mask.to(dev)
+    Tp, L = ids.shape[1], 100
+    g = VOC.grammar()
+    m._decoder = None
+    out = m.generate(input_ids=ids, attention_mask=mask, max_length=L, do_sample=False, grammar=g)
+    assert torch.equal(out[:, :Tp], ids) and _bad_columns(out, mask) == [-1] * len(prompts)
+    m._decoder = None
+    smp = m.generate(input_ids=ids, attention_mask=mask, max_length=L, grammar=g, **SAMPLE)
+    assert _bad_columns(smp, mask) == [-1] * len(prompts)
+    for b, p in enumerate(prompts):
+        s = Tp - len(p)
+        m._decoder = None
+        one = m.generate(input_ids=p[None].to(dev), max_length=L - s, do_sample=False, grammar=g)[0].cpu()
+        row = out[b, s:].cpu()
+        mism = (row != one).nonzero()
+        if mism.numel():                                            # legitimate only at a near-tie of the masked oracle scores
+            t0 = int(mism[0, 0])
+            with torch.no_grad():
+                lp = ref(one[None, :t0]).prediction_scores[0, -1].float()
+            lp = lp.masked_fill(~_allowed_mask(walk(VOC, one[:t0].tolist())[0]), float('-inf'))
+            top2 = lp.topk(2).values
+            print(f'row {b}: fork at {t0}, margin {(top2[0] - top2[1]).item():.4f}')
+            assert (top2[0] - top2[1]).item() < NEAR_TIE, (b, t0)
+
+
+# ---------------------------------------------------------------------------------------------------------------- op level
+def test_mask_then_sampler_probabilities(dev):
+    """mxl_sample's out_probs after mxl_grammar_mask: zero on every barred token, sums to 1, the softmax of the allowed scores"""
+    from symbolic_music_generation_amd import ops
+    torch.manual_seed(1)
+    g = VOC.grammar()
+    B = g.n_states
+    logp = torch.log_softmax(torch.randn(B, V) * 2, -1)
+    lp = logp.to(dev)
+    gstate = torch.arange(B, device=dev, dtype=torch.int32)        # one row per state
+    ids = torch.zeros(B, 8, device=dev, dtype=torch.int64)
+    t = torch.zeros(1, device=dev, dtype=torch.int32)
+    rng = torch.zeros(1, device=dev, dtype=torch.int64)
+    probs = torch.zeros(B, V, device=dev)
+    ops.grammar_mask(lp, V, g, gstate)
+    keep = torch.stack([_allowed_mask(n) for n in g.state_names])
+    assert torch.equal(torch.isinf(lp).cpu(), ~keep) and torch.equal(lp.cpu()[keep], logp[keep])
+    for temp in (1.0, 1.5):
+        ops.sample(lp, ids, t, rng, 123, do_sample=True, top_k=0, top_p=1.0, temperature=temp, out_probs=probs)
+        got = probs.cpu()
+        want = (logp / temp).masked_fill(~keep, float('-inf')).softmax(-1)
+        assert (got[~keep] == 0).all()
+        assert (got.sum(-1) - 1).abs().max().item() < 1e-5
+        assert (got - want).abs().max().item() < 1e-5, temp
+        assert keep[torch.arange(B), ids[:, 1].cpu()].all()
+    # advance: the sampled tokens move the states as the table says; a finished row keeps its state
+    ops.decode_advance(t, rng)
+    live = torch.ones(B, device=dev, dtype=torch.int32)
+    live[3] = 0
+    before = gstate.clone()
+    ops.grammar_advance(ids, t, g, gstate, live)
+    toks = ids[:, 1].tolist()
+    want = [g.state(TABLE[n][CLASS_OF[k]]) for n, k in zip(g.state_names, toks)]
+    want[3] = int(before[3])
+    assert gstate.tolist() == want
+
+
+def test_scan_equals_walk_on_padded_rows(dev):
+    from symbolic_music_generation_amd import ops
+    g = VOC.grammar()
+    song = np.load(GOLD)['sample_full_degree'].astype(np.int64)
+    rng = np.random.default_rng(0)
+    T = 300
+    rows = []
+    for b in range(12):
+        n = int(rng.integers(1, T))
+        r = np.full(T, -1, dtype=np.int64)
+        r[T - n:] = song[:n]
+        if b % 3 == 1:                                              # break it somewhere
+            r[T - n + int(rng.integers(0, n))] = VOC.t2i('[OMIT]')
+        if b % 3 == 2 and n > 70:
+            r[T - n + 65] = V + 5                                   # an id beyond the vocabulary
+        rows.append(r)
+    rows.append(np.concatenate([song[:T - 6], np.full(6, -1)]))     # skipped columns anywhere
+    ids = torch.from_numpy(np.stack(rows)).to(dev)
+    gstate = torch.empty(len(rows), device=dev, dtype=torch.int32)
+    bad = torch.empty_like(gstate)
+    ops.grammar_scan(ids, T, g, gstate, bad)
+    want = [g.walk(r) for r in rows]
+    assert list(zip(gstate.tolist(), bad.tolist())) == want
+    assert any(c >= 0 for _, c in want) and any(c < 0 for _, c in want)
+
+
+def test_prompt_that_breaks_the_grammar_raises(dev):
+    from symbolic_music_generation_amd._lib import MusicXLError
+    ref, m = _model(dev, 305)
+    m.eval()
+    ids = _header(4, dev)
+    ids[2, 3] = VOC.t2i('<melody>')                                 # <melody> without <bar>
+    with pytest.raises(MusicXLError, match=r'row 2 .*column 3'):
+        m.generate(input_ids=ids, max_new_tokens=10, do_sample=False, grammar=VOC.grammar())
+    with pytest.raises(MusicXLError):                               # a grammar over another vocabulary
+        m.generate(input_ids=_header(2, dev), max_new_tokens=10, grammar=MusicVocabulary(pitch_kind='midi').grammar())
+    for kw in (dict(num_beams=2), dict(num_beams=4, num_beam_groups=2), dict(penalty_alpha=0.6, top_k=4)):
+        with pytest.raises(MusicXLError, match='grammar'):
+            m.generate(input_ids=_header(2, dev), max_length=20, grammar=VOC.grammar(), **kw)
+
+
+# ---------------------------------------------------------------------------------------------------------------- with eos
+def test_eos_and_min_length_with_the_grammar(dev):
+    ref, m = _model(dev, 306, closing_bias=9.0)
+    m.eval()
+    B, L = 8, 160
+    Tp = len(HEADER)
+    prompt = _header(B, dev)
+    g = VOC.grammar()
+    END = g.state('END')
+    for kw in (dict(do_sample=True, temperature=1.5, top_k=0), dict(do_sample=False)):
+        dec = _fresh(m, B, L, 9)
+        full = dec.generate(prompt, L, grammar=g, **kw)
+        assert _bad_columns(full) == [-1] * B
+        ended = (full[:, Tp:] == EOS).any(1)
+        assert ended.any(), kw                                      # the bias makes rows reach </s> ...
+        assert (full[ended][:, -1] == PAD).all()                    # ... after which END allows [PAD] alone
+        for pad in (PAD, 0):                                        # 0 = [OMIT], which END bars: a finished row's pad is not its choice
+            dec2 = _fresh(m, B, L, 9)
+            got = dec2.generate(prompt, L, grammar=g, eos_token_id=EOS, pad_token_id=pad, **kw)
+            assert torch.equal(got, finish_at_eos(full, Tp, EOS, pad)), (kw, pad)
+            done = dec2.unfinished.cpu() == 0
+            assert torch.equal(done, ended.cpu())
+            assert (dec2.gstate.cpu()[done] == END).all()
+        # min_length still bars </s> where the grammar allows it (B_D)
+        first = int((full[:, Tp:] == EOS).int().argmax(1)[ended].min()) + Tp
+        m_len = first + 12
+        got = _fresh(m, B, L, 9).generate(prompt, L, grammar=g, eos_token_id=EOS, pad_token_id=PAD, min_length=m_len, **kw)
+        assert not (got[:, :m_len] == EOS).any() and _bad_columns(got) == [-1] * B, kw
+    # through the model, with num_return_sequences
+    m._decoder = None
+    out = m.generate(input_ids=prompt[:3], max_length=L, grammar=g, eos_token_id=EOS, pad_token_id=PAD, num_return_sequences=2,
+                     **SAMPLE)
+    assert out.shape[0] == 6 and _bad_columns(out) == [-1] * 6
+
+
+def test_min_length_refuses_a_state_that_allows_eos_alone(dev):
+    from symbolic_music_generation_amd.grammar import from_transitions
+    ref, m = _model(dev, 307)
+    m.eval()
+    cls = np.zeros(V, dtype=np.uint8)
+    cls[7] = 1
+    g = from_transitions(cls, ['a', 'e'], [('X', 'a', 'Y'), ('Y', 'e', 'X')], 'X')
+    ids = torch.tensor([[5, 7, 9]], device=dev)
+    with pytest.raises(ValueError, match='min_length'):
+        m.generate(input_ids=ids, max_length=20, grammar=g, eos_token_id=7, min_length=10)
+    out = m.generate(input_ids=ids, max_length=20, grammar=g)                        # fine without min_length
+    assert (out[0, 3::2] == 7).all() and (out[0, 4::2] != 7).all()
+    out = m.generate(input_ids=ids, max_length=20, grammar=g, eos_token_id=7)
+    assert out.shape == (1, 4) and int(out[0, 3]) == 7
+
+
+# ---------------------------------------------------------------------------------------------------------------- other paths
+def _three_class(vocab):
+    """a < b < c thirds of the vocabulary: (a b+ c)* with c optional after b"""
+    from symbolic_music_generation_amd.grammar import from_transitions
+    cls = (np.arange(vocab) * 3 // vocab).astype(np.uint8)
+    tab = {'X': {0: 'Y'}, 'Y': {1: 'Z'}, 'Z': {1: 'Z', 2: 'X', 0: 'Y'}}
+    g = from_transitions(cls, ['a', 'b', 'c'], [(s, 'abc'[c], n) for s, row in tab.items() for c, n in row.items()], 'X')
+    return g, cls, tab
+
+
+def _walk3(cls, tab, ids, state='X'):
+    for i, t in enumerate(ids):
+        if t < 0:
+            continue
+        nxt = tab[state].get(int(cls[t]))
+        if nxt is None:
+            return state, i
+        state = nxt
+    return state, -1
+
+
+def test_large_vocabulary_sampler(dev):
+    vocab = 3000
+    ref, m = _model(dev, 308, vocab=vocab, cutoffs=(1000,))
+    m.eval()
+    g, cls, tab = _three_class(vocab)
+    B, L = 5, 70
+    prompt = torch.tensor([[10, 1500, 2500, 20]] * B, device=dev)
+    for kw in (dict(do_sample=False), dict(do_sample=True, temperature=1.5, top_k=0), dict(do_sample=True, top_k=50, top_p=0.9)):
+        dec = _fresh(m, B, L, 3)
+        assert not dec.fused_sampler
+        got = dec.generate(prompt, L, grammar=g, **kw)
+        assert [_walk3(cls, tab, r)[1] for r in got.tolist()] == [-1] * B, kw
+        free = _fresh(m, B, L, 3).generate(prompt, L, **kw)
+        assert any(_walk3(cls, tab, r)[1] >= 0 for r in free.tolist()), kw
+        eager = _fresh(m, B, L, 3).generate(prompt, L, grammar=g, use_graph=False, **kw)
+        assert torch.equal(eager, got), kw
+
+
+def test_reformer(dev):
+    from symbolic_music_generation_amd.reformer import MyReformerConfig, MyReformerModelWithLMHead
+    cfg = MyReformerConfig('debug-large', vocab_size=120, max_position_embeddings=512, axial_pos_shape=(16, 32),
+                           attn_layers=['local'] * 4)
+    rf = MyReformerModelWithLMHead(cfg, device=dev, seed=9).eval()
+    g, cls, tab = _three_class(120)
+    B, L = 4, 120
+    prompt = torch.tensor([[3, 50, 100, 7]] * B, device=dev)
+    for kw in (dict(do_sample=False), dict(do_sample=True, temperature=1.5, top_k=0)):
+        rf._decoder = None
+        got = rf.generate(input_ids=prompt, max_length=L, grammar=g, **kw)
+        assert got.shape == (B, L) and [_walk3(cls, tab, r)[1] for r in got.tolist()] == [-1] * B, kw
+        rf._decoder = None
+        free = rf.generate(input_ids=prompt, max_length=L, **kw)
+        assert any(_walk3(cls, tab, r)[1] >= 0 for r in free.tolist()), kw
+    # the uncached loop, and eos: rows finished keep their state
+    got = rf.generate(input_ids=prompt, max_length=40, grammar=g, use_cache=False, do_sample=True, temperature=1.5, top_k=0)
+    assert [_walk3(cls, tab, r)[1] for r in got.tolist()] == [-1] * B
+    rf._decoder = None
+    full = rf.generate(input_ids=prompt, max_length=L, grammar=g, do_sample=True, temperature=1.5, top_k=0)
+    eos = int(full[0, 10])
+    rf._decoder = None
+    got = rf.generate(input_ids=prompt, max_length=L, grammar=g, do_sample=True, temperature=1.5, top_k=0, eos_token_id=eos,
+                      pad_token_id=0)
+    assert torch.equal(got, finish_at_eos(full, 4, eos, 0))
+    from symbolic_music_generation_amd._lib import MusicXLError
+    with pytest.raises(MusicXLError, match='grammar'):
+        rf.generate(input_ids=prompt, max_length=20, grammar=g, num_beams=2)
+
+
+def test_graph_key_covers_the_grammar(dev):
+    """one decoder: grammar -> none -> another grammar -> the first, each equal to a fresh decoder's result"""
+    ref, m = _model(dev, 309)
+    m.eval()
+    B, L = 5, 90
+    prompt = _header(B, dev)
+    g = VOC.grammar()
+    g3, cls3, tab3 = _three_class(V)
+    p3 = torch.tensor([[10, 500, 900, 20]] * B, device=dev)
+    kw = dict(do_sample=True, top_k=8)
+
+    def fresh(p, **k):
+        return _fresh(m, B, L, 4).generate(p, L, **kw, **k)
+
+    dec = _fresh(m, B, L, 4)
+
+    def again(p, **k):
+        dec.rng.zero_()
+        return dec.generate(p, L, **kw, **k)
+
+    a = again(prompt, grammar=g)
+    assert torch.equal(a, fresh(prompt, grammar=g)) and _bad_columns(a) == [-1] * B
+    b = again(prompt)
+    assert torch.equal(b, fresh(prompt)) and not torch.equal(a, b)
+    c = again(p3, grammar=g3)
+    assert torch.equal(c, fresh(p3, grammar=g3)) and [_walk3(cls3, tab3, r)[1] for r in c.tolist()] == [-1] * B
+    assert torch.equal(again(prompt, grammar=g), a)
+    assert torch.equal(again(prompt, grammar=g, eos_token_id=EOS, pad_token_id=PAD), finish_at_eos(a, len(HEADER), EOS, PAD))
