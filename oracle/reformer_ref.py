@@ -354,6 +354,75 @@ def _rf_prefill(self, ids, rotations):
     return logits[:, :Tp], cache
 
 
+def cached_range_attend(q, k_all, v_all, start, count, lsh, t):
+    """the cached step over a contiguous range of positions (local layers, HF515:1136-1169, 1327-1329; LSH layers before their
+    first hashing, HF515:513-517, 840-845).  q (B, H, dh); k_all / v_all (B, H, N, dh) PROJECTED vectors of every position (for an
+    LSH layer k_all is the shared qk); the keys are positions start .. start + count - 1.  `lsh`: shared-QK key normalisation
+    qk * rsqrt(mean(qk^2) + 1e-6) / sqrt(dh) (HF515:1052-1066) and the self mask -1e5 at position `t`; otherwise keys / sqrt(dh).
+    Computes in the dtype it is given.  -> (B, H, dh)"""
+    dh = q.shape[-1]
+    k, v = k_all[:, :, start:start + count], v_all[:, :, start:start + count]
+    if lsh:
+        key = k * torch.rsqrt(torch.mean(k ** 2, -1, keepdim=True) + 1e-6) / math.sqrt(dh)
+    else:
+        key = k / math.sqrt(dh)
+    dots = torch.einsum('bhe,bhle->bhl', q, key)
+    if lsh:
+        dots = dots.masked_fill(torch.arange(start, start + count) == t, -1e5)
+    return torch.einsum('bhl,bhle->bhe', torch.softmax(dots, -1), v)
+
+
+def cached_lsh_window(rank, n, chunk=64):
+    """sorted slots a cached LSH query attends to: the chunk that holds it (sorted slot `rank`) and the chunk before, modulo the
+    row length n (HF515:1000-1020).  With n < 2 * chunk, or when the window wraps, a slot can appear twice: HF does the same.
+    rank (...) int64 -> (..., 2 * chunk)"""
+    start = (torch.div(rank, chunk, rounding_mode='floor') - 1) * chunk
+    return (start.unsqueeze(-1) + torch.arange(2 * chunk)) % n
+
+
+def cached_lsh_attend(q, qk_all, v_all, order, t, return_lse=False):
+    """the cached LSH step once buckets exist (HF515:482-511, 946-1050).  q (B, H, dh); qk_all / v_all (B, H, N, dh) projected
+    vectors of positions 0 .. t (N > t allowed); order (B, H, n_h, n = t + 1) the stable bucket-sort permutation per hash round.
+    Every round attends to the window of `cached_lsh_window` around the new token (position t); no causal mask (everything is
+    in the past), self mask -1e5, rounds merged by softmax over their logsumexp.  Computes in the dtype it is given.
+    -> (B, H, dh) (and, on request, the per-round logsumexp (B, H, n_h))"""
+    B, H, n_h, n = order.shape
+    dh = q.shape[-1]
+    rank = (order == t).float().argmax(-1)                              # sorted slot of the new token
+    posn = order.gather(-1, cached_lsh_window(rank, n))                 # (B, H, n_h, 128) original positions
+    bi, hi = torch.arange(B).view(B, 1, 1, 1), torch.arange(H).view(1, H, 1, 1)
+    qk, v = qk_all[bi, hi, posn], v_all[bi, hi, posn]                   # (B, H, n_h, 128, dh)
+    key = qk * torch.rsqrt(torch.mean(qk ** 2, -1, keepdim=True) + 1e-6) / math.sqrt(dh)
+    dots = torch.einsum('bhe,bhrle->bhrl', q, key).masked_fill(posn == t, -1e5)
+    lse = torch.logsumexp(dots, -1, keepdim=True)
+    out = torch.einsum('bhrl,bhrle->bhre', torch.exp(dots - lse), v)
+    if n_h > 1:
+        out = (out * torch.exp(lse - torch.logsumexp(lse, 2, keepdim=True))).sum(2)
+    else:
+        out = out[:, :, 0]
+    return (out, lse.squeeze(-1)) if return_lse else out
+
+
+def query_bucket(raw, past_max, n_h, NB):
+    """bucket ids of the new token as they enter the cache.  raw (..., n_h) = r * NB + b (what `lsh_buckets` gives for NB
+    buckets); the per-round offsets widen to NB + 1 when the cache already holds an id above n_h * NB - 1, i.e. a pad bucket
+    was cached (HF515:961-970 `increase_num_buckets`) -- strictly above: at equality nothing changes."""
+    r = torch.arange(n_h)
+    inc = 1 if int(past_max) > n_h * NB - 1 else 0
+    return raw - r * NB + r * (NB + inc)
+
+
+def fix_buckets(buckets, T, T_real, n_h, NB):
+    """padded prefill (HF515:746-756): buckets (rows, n_h * T) with entry (row, r, t) = r * NB + b; positions t >= T_real are
+    pads and go to the one extra bucket NB, and the per-round offsets become r * (NB + 1)"""
+    rows = buckets.shape[0]
+    bk = buckets.view(rows, n_h, T)
+    r = torch.arange(n_h).view(1, n_h, 1)
+    b = bk - r * NB
+    b = torch.where(torch.arange(T).view(1, 1, T) < T_real, b, torch.full_like(b, NB))
+    return (r * (NB + 1) + b).view(rows, n_h * T)
+
+
 def _rf_step(self, tok, cache, rotations):
     """one token (B, 1) against the cache -> logits (B, V); the cache grows by one position"""
     c, p = self.c, self.p
@@ -371,24 +440,21 @@ def _rf_step(self, tok, cache, rotations):
         h = F.layer_norm(x2, (d,), p[pre + 'attention.layer_norm.weight'], p[pre + 'attention.layer_norm.bias'], c.layer_norm_eps)
         past = cache.states[l]
         if kind == 'local':
-            start = ((past.shape[1] // ch) - 1) * ch                # HF515:1327-1329 (a negative start slices from the end)
-            kv = torch.cat([past[:, start:], h], 1)
+            start = max(((t // ch) - 1) * ch, 0)                    # HF515:1327-1329 (a negative start slices from the end: everything)
+            allh = torch.cat([past, h], 1)                          # projecting gathered rows == gathering projected rows
             q = self._split(h @ p[sa + 'query.weight'].t())
-            k = self._split(kv @ p[sa + 'key.weight'].t()) / math.sqrt(dh)
-            v = self._split(kv @ p[sa + 'value.weight'].t())
-            a = self._merge(torch.softmax(q @ k.transpose(-1, -2), -1) @ v)
+            k = self._split(allh @ p[sa + 'key.weight'].t())
+            v = self._split(allh @ p[sa + 'value.weight'].t())
+            a = self._merge(cached_range_attend(q[:, :, 0], k, v, start, t + 1 - start, False, t).unsqueeze(2))
         else:
             rot = rotations[l]
             n_h = rot.shape[2]
             q = self._split(h @ p[sa + 'query_key.weight'].t())    # (B, H, 1, dh)
             allh = torch.cat([past, h], 1)                          # (B, t+1, d)
+            qk = self._split(allh @ p[sa + 'query_key.weight'].t())    # (B, H, t+1, dh)
+            v = self._split(allh @ p[sa + 'value.weight'].t())
             if cache.buckets[l] is None:
-                qk = self._split(allh @ p[sa + 'query_key.weight'].t())
-                v = self._split(allh @ p[sa + 'value.weight'].t())
-                key = qk * torch.rsqrt(torch.mean(qk ** 2, -1, keepdim=True) + 1e-6) / math.sqrt(dh)
-                dots = q @ key.transpose(-1, -2)                    # (B, H, 1, t+1)
-                dots[..., -1] = -1e5                                # self mask on the token itself (HF515:840-845)
-                a = self._merge(torch.softmax(dots, -1) @ v)
+                a = self._merge(cached_range_attend(q[:, :, 0], qk, v, 0, t + 1, True, t).unsqueeze(2))
                 if t + 1 >= ch:                                     # HF515:532-534: from now on the buckets are cached
                     if self.num_buckets is None:
                         raise RuntimeError('num_buckets must be set before cached decoding hashes (HF sets it in the first chunked forward)')
@@ -396,31 +462,10 @@ def _rf_step(self, tok, cache, rotations):
             else:
                 pb = cache.buckets[l]
                 nbk = self.num_buckets if isinstance(self.num_buckets, int) else math.prod(self.num_buckets)
-                inc = bool(pb.max() > n_h * nbk - 1)                # pad bucket was cached (HF515:961-965)
-                qb = lsh_buckets(q, rot, self.num_buckets, increase_num_buckets=inc).view(B, H, n_h, 1)
+                raw = lsh_buckets(q, rot, self.num_buckets).view(B, H, n_h)
+                qb = query_bucket(raw, pb.max(), n_h, nbk).unsqueeze(-1)   # pad bucket was cached -> wider offsets (HF515:961-965)
                 cb = torch.cat([pb, qb], -1)                        # (B, H, n_h, t+1)
-                order = _stable_argsort(cb)
-                n = t + 1
-                rank = (order == n - 1).float().argmax(-1)          # sorted slot of the new token
-                start = ((rank // ch) - 1) * ch
-                slots = (start.unsqueeze(-1) + torch.arange(2 * ch)) % n
-                posn = order.gather(-1, slots)                      # (B, H, n_h, 128) original positions
-                hs = allh[torch.arange(B).view(B, 1, 1, 1), posn]   # (B, H, n_h, 128, d)
-                wqk = p[sa + 'query_key.weight'].view(H, dh, d)
-                wv = p[sa + 'value.weight'].view(H, dh, d)
-                qk = torch.einsum('bhrld,hed->bhrle', hs, wqk)
-                v = torch.einsum('bhrld,hed->bhrle', hs, wv)
-                key = qk * torch.rsqrt(torch.mean(qk ** 2, -1, keepdim=True) + 1e-6) / math.sqrt(dh)
-                dots = torch.einsum('bhe,bhrle->bhrl', q[:, :, 0], key)
-                dots = torch.where(posn != n - 1, dots, torch.tensor(-1e5))
-                lse = torch.logsumexp(dots, -1, keepdim=True)
-                out = torch.einsum('bhrl,bhrle->bhre', torch.exp(dots - lse), v)
-                if n_h > 1:
-                    wgt = torch.exp(lse - torch.logsumexp(lse, 2, keepdim=True))
-                    out = (out * wgt).sum(2)
-                else:
-                    out = out[:, :, 0]
-                a = self._merge(out.unsqueeze(2))
+                a = self._merge(cached_lsh_attend(q[:, :, 0], qk, v, _stable_argsort(cb), t).unsqueeze(2))
                 cache.buckets[l] = cb
         cache.states[l] = torch.cat([past, h], 1)
         y1 = x1 + a @ p[pre + 'attention.output.dense.weight'].t()

@@ -92,7 +92,10 @@ __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const bf16_t* src
     }
 }
 
-// one wave per logit row: running (max, sum) per lane over the row, merged across the wave at the end -- the row is read once
+// one wave per logit row: running (max, sum) per lane over the row, merged across the wave at the end -- the row is read once.
+// Contract: every logit is finite.  A lane whose first piece is all -inf would take exp(-inf - -inf) = NaN in the running sum; the
+// heads here never produce -inf (GEMM outputs), and a caller that masks logits must use a large negative finite value (entries
+// far below the maximum contribute exactly 0, tested down to -1e4).
 __global__ __launch_bounds__(256) void rows_lse_pick_kernel(const float* logits, long long ld, int ncols, int n_rows, const int* rows_idx,
                                                             int row0, const int* tgt, float* lse_out, float* pick_out) {
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
