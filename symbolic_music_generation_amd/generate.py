@@ -8,7 +8,7 @@ reference calls it (musicnlp/trainer/eval.py:277-333; HF 4.25.1 GenerationMixin.
 Strategies mirrored from `MusicGenerator` (eval.py:277-326): greedy (do_sample=False) and sampling with
 `top_k`, `top_p`, `typical_p`, `temperature`, `repetition_penalty` and renormalised logits -- every key the `sample`
 strategy accepts (eval.py:279) -- and beam search (`strategy='beam'`, eval.py:302-321: HF `beam_search` / `beam_sample` with
-`BeamSearchScorer`), which runs the same per-token kernels eagerly with the beam bookkeeping between steps (XLDecoder.beam_search).
+`BeamSearchScorer`), which runs the same per-token kernels eagerly with the beam bookkeeping between steps (beam_search).
 Contrastive search raises: HF 4.25.1's `contrastive_search` requires `past_key_values` in the model output, which neither
 TransfoXL (`mems`) nor Reformer (`past_buckets_states`) returns, so that strategy fails in the reference too.
 """
@@ -38,6 +38,39 @@ def stop_config(eos_token_id: Optional[int], pad_token_id: Optional[int] = None,
     pad = pad_token_id if pad_token_id is not None else config_pad_token_id
     pad = eos if pad is None else int(pad)
     return eos, pad, max(int(min_length or 0), 0)
+
+
+def sampling_config(do_sample: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: float = 1.0,
+                    repetition_penalty: Optional[float] = None, typical_p: Optional[float] = None) -> dict:
+    """the sampler arguments of one generation as every decoder passes them on (`begin`, `step`, ops.sample / ops.sample_step): a
+    plain dict of these six keys with the 'off' values filled in (top_k 0; top_p, repetition_penalty, typical_p 1.0).  Its sorted
+    items are part of XLDecoder's graph key."""
+    return dict(do_sample=do_sample, top_k=top_k or 0, top_p=1.0 if top_p is None else top_p, temperature=temperature,
+                repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
+                typical_p=1.0 if typical_p is None else typical_p)
+
+
+def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch.Tensor, rng: torch.Tensor, seed: int, sampling: dict,
+                   stop: Optional[tuple] = None, unfinished: Optional[torch.Tensor] = None, alive: Optional[torch.Tensor] = None,
+                   grammar=None, gstate: Optional[torch.Tensor] = None):
+    """The sampler tail as separate launches (what mxl_sample_step* does in one): next token of every row from the first V columns
+    of `scores` -> ids[:, t + 1], position and RNG counters advanced.  stop = (eos, pad, min_length) with unfinished / alive and
+    grammar with gstate are optional; the masks write into `scores` in place."""
+    sc = scores[:, :V] if scores.shape[1] != V else scores
+    if stop is not None:
+        ops.mask_eos_below(sc, V, t_dev, stop)
+    if grammar is not None:
+        # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the
+        # masks: -inf stays -inf under it, so the result is the same
+        ops.grammar_mask(sc, V, grammar, gstate)
+    ops.sample(sc, ids, t_dev, rng, seed, **sampling)
+    ops.decode_advance(t_dev, rng)
+    if grammar is not None:
+        # before the stop rule rewrites it: `unfinished` still tells which rows chose their token (rows finished before this step
+        # keep their state)
+        ops.grammar_advance(ids, t_dev, grammar, gstate, None if stop is None else unfinished)
+    if stop is not None:
+        ops.decode_stop(ids, t_dev, stop, unfinished, alive)
 
 
 def resolve_max_length(max_length: Optional[int], max_new_tokens: Optional[int], prompt_len: int, default: int) -> int:
@@ -181,6 +214,42 @@ def run_until_finished(decoders, n: int, chunk: int = STOP_CHUNK) -> list:
     return issued
 
 
+def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool, n_pad, stop, stop_chunk,
+                 grammar) -> torch.Tensor:
+    """The body of `generate` for one decoder (lanes = [dec], streams = [None]) or for an XLDecoderLanes with its lanes and their
+    streams: `dec.begin`, then every remaining step through `dec.replay_once` -- or, with stop = (eos, pad, min_length), each lane
+    on its own until its rows have finished (run_until_finished) -- then the lanes' rows in order, cut to the width of the longest
+    lane and right-filled with pad where a lane stopped earlier.  Sets `steps_run` on every lane and on dec (the most of any
+    lane).  The prompt columns of left-padded prompts (n_pad) come back as given."""
+    Tp = prompt.shape[1]
+    if max_length - Tp <= 0:
+        return prompt[:, :max_length]
+    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar)
+    if stop is None:
+        for _ in range(n):
+            dec.replay_once()
+        steps = [n] * len(lanes)
+    else:
+        steps = run_until_finished(list(zip(lanes, streams)), n, stop_chunk)
+    for s in streams:
+        if s is not None:
+            torch.cuda.current_stream().wait_stream(s)
+    for d, k in zip(lanes, steps):
+        d.steps_run = k
+    dec.steps_run = max(steps)
+    widths = [max_length if stop is None else stop_width(d.ids, d.unfinished, Tp, max_length, stop[0]) for d in lanes]
+    W = max(widths)
+    out = torch.cat([d.ids[:, :W] for d in lanes], 0) if len(lanes) > 1 else dec.ids[:, :W].clone()
+    row = 0
+    for d, w in zip(lanes, widths):
+        if w < W:
+            out[row:row + d.B, w:] = stop[1]
+        row += d.B
+    if n_pad is not None:
+        out[:, :Tp].copy_(prompt)
+    return out
+
+
 class XLDecoder:
     def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77):
         self.eng = engine
@@ -307,41 +376,13 @@ class XLDecoder:
         """next token of every row from `scores` (log-probabilities, or the head's logits: see mxl_sample_step) -> ids[:, t + 1];
         position and RNG counters advanced.  Short chain: the same launch leaves the token's embedding row in h[0] for the next step."""
         c = self.eng.cfg
-        stop = self._stop
-        g = self._grammar
-        if g is not None and self.fused_sampler:     # mask, eos rule and state advance ride on the sampler launch
-            ops.sample_step_grammar(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
-                                    self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model),
-                                    self.step_ctr, g, self.gstate, stop, self.unfinished, self.alive, **sampling)
-        elif g is not None:
-            # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the
-            # mask: -inf stays -inf under it, so the result is the same
-            sc = scores[:, :c.vocab_size] if scores.shape[1] != c.vocab_size else scores
-            if stop is not None:
-                ops.mask_eos_below(sc, c.vocab_size, self.t_dev, stop)
-            ops.grammar_mask(sc, c.vocab_size, g, self.gstate)
-            ops.sample(sc, self.ids, self.t_dev, self.rng, self.seed, **sampling)
-            ops.decode_advance(self.t_dev, self.rng)
-            # before the stop rule: `unfinished` still tells which rows chose their token (the others stay frozen)
-            ops.grammar_advance(self.ids, self.t_dev, g, self.gstate, None if stop is None else self.unfinished)
-            if stop is not None:
-                ops.decode_stop(self.ids, self.t_dev, stop, self.unfinished, self.alive)
-        elif self.fused_sampler and stop is None:
+        state = dict(stop=self._stop, unfinished=self.unfinished, alive=self.alive, grammar=self._grammar, gstate=self.gstate)
+        if self.fused_sampler:      # the masks, the stop rule, the live-row count and the state advance ride on the sampler launch
             ops.sample_step(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
                             self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model), self.step_ctr,
-                            **sampling)
-        elif self.fused_sampler:          # the stop rule and the live-row count ride on the same launch
-            ops.sample_step_stop(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
-                                 self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model),
-                                 self.step_ctr, stop, self.unfinished, self.alive, **sampling)
+                            **state, **sampling)
         else:
-            sc = scores[:, :c.vocab_size] if scores.shape[1] != c.vocab_size else scores
-            if stop is not None:
-                ops.mask_eos_below(sc, c.vocab_size, self.t_dev, stop)
-            ops.sample(sc, self.ids, self.t_dev, self.rng, self.seed, **sampling)
-            ops.decode_advance(self.t_dev, self.rng)
-            if stop is not None:
-                ops.decode_stop(self.ids, self.t_dev, stop, self.unfinished, self.alive)
+            sample_unfused(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, **state)
 
     # ---------------------------------------------------------------- one token
     def force_tokens(self, tokens: torch.Tensor):
@@ -358,7 +399,7 @@ class XLDecoder:
         # the log-softmax launch is only needed for what reads log-probabilities: the trace, an adaptive (clustered) head, and the
         # repetition penalty (sign-dependent); every other warper and the draw itself are shift-invariant (mxl_sample_step)
         raw = (self.fused_sampler and self.trace is None and not want_logp and not tuple(self.eng.cfg.cutoffs)
-               and float(sampling.get('repetition_penalty', 1.0) or 1.0) == 1.0)
+               and sampling.get('repetition_penalty', 1.0) == 1.0)
         self._forward_token(embed=not self.fused_sampler, want_logp=not raw)
         self._sample_advance(self.logits if raw else self.logp, sampling)
 
@@ -503,26 +544,9 @@ class XLDecoder:
         `stop_chunk` with the live-row count read back one chunk late (run_until_finished): no per-step host round trip.
         grammar (a grammar.TokenGrammar, e.g. `tokenizer.grammar()`): every row may only emit tokens its grammar state allows; the
         state lives on the device and moves inside the sampler launch of the captured step.  The prompts must obey the grammar."""
-        sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0,
-                        temperature=temperature, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
-                        typical_p=1.0 if typical_p is None else typical_p)
-        stop = stop_config(eos_token_id, pad_token_id, min_length)
-        Tp = prompt.shape[1]
-        if max_length - Tp <= 0:
-            return prompt[:, :max_length]
-        n = self.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar)
-        if stop is None:
-            for _ in range(n):
-                self.replay_once()
-            self.steps_run = n
-            W = max_length
-        else:
-            self.steps_run = run_until_finished([(self, None)], n, stop_chunk)[0]
-            W = stop_width(self.ids, self.unfinished, Tp, max_length, stop[0])
-        out = self.ids[:, :W].clone()
-        if n_pad is not None:
-            out[:, :Tp].copy_(prompt)
-        return out
+        return decode_lanes(self, [self], [None], prompt, max_length,
+                            sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
+                            stop_config(eos_token_id, pad_token_id, min_length), stop_chunk, grammar)
 
 
 class XLDecoderLanes:
@@ -565,36 +589,11 @@ class XLDecoderLanes:
     def generate(self, prompt, max_length, do_sample=False, top_k=None, top_p=None, temperature=1.0, repetition_penalty=None,
                  typical_p=None, use_graph=True, n_pad=None, eos_token_id=None, pad_token_id=None, min_length=None,
                  stop_chunk=STOP_CHUNK, grammar=None) -> torch.Tensor:
-        """XLDecoder.generate over the lanes (each lane keeps the grammar state of its own rows).  With eos_token_id every lane stops on its own; the output is the lanes' rows cut to
-        the common width and right-filled with pad where a lane stopped earlier."""
-        sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0,
-                        temperature=temperature, repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
-                        typical_p=1.0 if typical_p is None else typical_p)
-        stop = stop_config(eos_token_id, pad_token_id, min_length)
-        Tp = prompt.shape[1]
-        if max_length - Tp <= 0:
-            return prompt[:, :max_length]
-        n = self.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar)
-        if stop is None:
-            for _ in range(n):
-                self.replay_once()
-            self.join()
-            self.steps_run = n
-            out = torch.cat([d.ids[:, :max_length] for d in self.lanes], 0)
-        else:
-            steps = run_until_finished(list(zip(self.lanes, self.streams)), n, stop_chunk)
-            self.join()
-            for d, k in zip(self.lanes, steps):
-                d.steps_run = k
-            self.steps_run = max(steps)
-            widths = [stop_width(d.ids, d.unfinished, Tp, max_length, stop[0]) for d in self.lanes]
-            W = max(widths)
-            out = torch.cat([d.ids[:, :W] for d in self.lanes], 0)
-            for i, w in enumerate(widths):
-                out[self.offs[i]:self.offs[i + 1], w:] = stop[1]
-        if n_pad is not None:
-            out[:, :Tp].copy_(prompt)
-        return out
+        """XLDecoder.generate over the lanes (each lane keeps the grammar state of its own rows).  With eos_token_id every lane stops
+        on its own; the output is the lanes' rows cut to the common width and right-filled with pad where a lane stopped earlier."""
+        return decode_lanes(self, self.lanes, self.streams, prompt, max_length,
+                            sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
+                            stop_config(eos_token_id, pad_token_id, min_length), stop_chunk, grammar)
 
 
 class _BeamHyps:
@@ -603,6 +602,7 @@ class _BeamHyps:
     def __init__(self, num_beams: int, length_penalty: float, early_stopping: bool):
         self.num_beams, self.length_penalty, self.early_stopping = num_beams, length_penalty, early_stopping
         self.beams, self.worst_score = [], 1e9
+        self.done = False                   # HF BeamSearchScorer._done of this item
 
     def add(self, hyp: torch.Tensor, sum_logprobs: float):
         score = sum_logprobs / (hyp.shape[-1] ** self.length_penalty)
@@ -621,6 +621,50 @@ class _BeamHyps:
         if self.early_stopping:
             return True
         return self.worst_score >= best_sum_logprobs / cur_len ** self.length_penalty
+
+    def walk(self, toks, scores, rows, n: int, eos: int, ids: torch.Tensor, cur_len: int):
+        """HF `BeamSearchScorer.process` for this item: its 2 * n candidates in score order (token, running score, decoder row of
+        the beam each continues).  An eos among the first n ranks puts that beam's ids[row, :cur_len] on the heap, the first n
+        other candidates continue: returns their (scores, tokens, rows), and `done` is updated."""
+        n_s, n_t, n_i = [], [], []
+        for rank, (tok, s_, src) in enumerate(zip(toks, scores, rows)):
+            if tok == eos:
+                if rank >= n:
+                    continue
+                self.add(ids[src, :cur_len].clone(), s_)
+            else:
+                n_s.append(s_); n_t.append(tok); n_i.append(src)
+            if len(n_s) == n:
+                break
+        if len(n_s) < n:
+            raise MusicXLError(f'at most {n} tokens in the top {2 * n} can be eos')
+        self.done = self.done or self.is_done(max(scores), cur_len)
+        return n_s, n_t, n_i
+
+
+def _beam_finalize(hyps, nb: int, keep: int, ids: torch.Tensor, cur_len: int, beam_scores: torch.Tensor, max_length: int, eos: int,
+                   pad: int, return_scores: bool):
+    """HF `BeamSearchScorer.finalize`: the open beams (rows b * nb .. of ids, their running scores) of every item that is not done
+    join its heap, the best `keep` of each heap are returned as (len(hyps) * keep, L) ids, each followed by eos where there is
+    room and padded with pad, L = the longest + 1 capped at max_length"""
+    final = beam_scores.tolist()
+    for b, hyp in enumerate(hyps):
+        if not hyp.done:
+            for j in range(nb):
+                hyp.add(ids[b * nb + j, :cur_len].clone(), final[b * nb + j])
+    best, scores = [], []
+    for hyp in hyps:
+        ranked = sorted(hyp.beams, key=lambda x: x[0])
+        for _ in range(keep):
+            sc_, h = ranked.pop()
+            best.append(h); scores.append(sc_)
+    L = min(max(len(h) for h in best) + 1, max_length)
+    out = torch.full((len(best), L), pad, dtype=torch.int64, device=ids.device)
+    for i, h in enumerate(best):
+        out[i, :len(h)] = h
+        if len(h) < L:
+            out[i, len(h)] = eos
+    return (out, torch.tensor(scores)) if return_scores else out
 
 
 def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, do_sample: bool = False,
@@ -656,7 +700,6 @@ def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, 
     beam_scores[:, 1:] = -1e9
     beam_scores = beam_scores.view(-1)
     hyps = [_BeamHyps(nb, length_penalty, early_stopping) for _ in range(Bs)]
-    done = [False] * Bs
     cur_len = Tp
     ident = torch.arange(rows, device=dev)
     while True:
@@ -673,51 +716,19 @@ def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, 
         top_sl = top_s.tolist()
         n_s, n_t, n_i = [[0.0] * nb for _ in range(Bs)], [[pad] * nb for _ in range(Bs)], [[0] * nb for _ in range(Bs)]
         for b in range(Bs):
-            if done[b]:
-                continue
-            k = 0
-            for rank in range(2 * nb):
-                tok, s_, src = top_t[b][rank], top_sl[b][rank], b * nb + top_b[b][rank]
-                if tok == eos_token_id:
-                    if rank >= nb:
-                        continue
-                    hyps[b].add(dec.ids[src, :cur_len].clone(), s_)
-                else:
-                    n_s[b][k], n_t[b][k], n_i[b][k] = s_, tok, src
-                    k += 1
-                if k == nb:
-                    break
-            if k < nb:
-                raise MusicXLError(f'at most {nb} tokens in the top {2 * nb} can be eos')
-            done[b] = done[b] or hyps[b].is_done(max(top_sl[b]), cur_len)
+            if not hyps[b].done:
+                n_s[b], n_t[b], n_i[b] = hyps[b].walk(top_t[b], top_sl[b], [b * nb + j for j in top_b[b]], nb, eos_token_id, dec.ids,
+                                                      cur_len)
         beam_scores = torch.tensor(n_s, device=dev).view(-1)
         beam_idx = torch.tensor(n_i, device=dev).view(-1)
         if not torch.equal(beam_idx, ident):
             dec.beam_reorder(beam_idx)
         dec.ids[:, cur_len] = torch.tensor(n_t, device=dev).view(-1)
         cur_len += 1
-        if all(done) or cur_len >= max_length:
+        if all(h.done for h in hyps) or cur_len >= max_length:
             break
         dec.beam_advance(cur_len)
-    final = beam_scores.tolist()
-    for b in range(Bs):
-        if done[b]:
-            continue
-        for j in range(nb):
-            hyps[b].add(dec.ids[b * nb + j, :cur_len].clone(), final[b * nb + j])
-    best, scores = [], []
-    for b in range(Bs):
-        ranked = sorted(hyps[b].beams, key=lambda x: x[0])
-        for _ in range(keep):
-            sc_, h = ranked.pop()
-            best.append(h); scores.append(sc_)
-    L = min(max(len(h) for h in best) + 1, max_length)
-    out = torch.full((len(best), L), pad, dtype=torch.int64, device=dev)
-    for i, h in enumerate(best):
-        out[i, :len(h)] = h
-        if len(h) < L:
-            out[i, len(h)] = eos_token_id
-    return (out, torch.tensor(scores)) if return_scores else out
+    return _beam_finalize(hyps, nb, keep, dec.ids, cur_len, beam_scores, max_length, eos_token_id, pad, return_scores)
 
 
 def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 4, num_beam_groups: int = 2,
@@ -749,7 +760,6 @@ def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int
     beam_scores[:, ::gs] = 0
     beam_scores = beam_scores.view(-1)
     hyps = [_BeamHyps(nb, length_penalty, early_stopping) for _ in range(B0)]
-    done = [False] * B0
     cur_len = Tp
     ident = torch.arange(rows, device=dev)
     while True:
@@ -771,24 +781,11 @@ def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int
             top_b, top_t, top_sl = (top_i // V).tolist(), (top_i % V).tolist(), top_s.tolist()
             n_s, n_t, n_i = [[0.0] * gs for _ in range(B0)], [[pad] * gs for _ in range(B0)], [[0] * gs for _ in range(B0)]
             for b in range(B0):
-                if done[b]:
+                if hyps[b].done:
                     n_i[b] = [b * nb + g0 + j for j in range(gs)]
-                    continue
-                k = 0
-                for rank in range(2 * gs):
-                    tok, s_, src = top_t[b][rank], top_sl[b][rank], b * nb + g0 + top_b[b][rank]
-                    if tok == eos_token_id:
-                        if rank >= gs:
-                            continue
-                        hyps[b].add(dec.ids[src, :cur_len].clone(), s_)
-                    else:
-                        n_s[b][k], n_t[b][k], n_i[b][k] = s_, tok, src
-                        k += 1
-                    if k == gs:
-                        break
-                if k < gs:
-                    raise MusicXLError(f'at most {gs} tokens in the top {2 * gs} can be eos')
-                done[b] = done[b] or hyps[b].is_done(max(top_sl[b]), cur_len)
+                else:
+                    n_s[b], n_t[b], n_i[b] = hyps[b].walk(top_t[b], top_sl[b], [b * nb + g0 + j for j in top_b[b]], gs, eos_token_id,
+                                                          dec.ids, cur_len)
             new_scores[gidx] = torch.tensor(n_s, device=dev).view(-1)
             current[gidx] = torch.tensor(n_t, device=dev).view(-1)
             reorder[gidx] = torch.tensor(n_i, device=dev).view(-1)
@@ -797,28 +794,32 @@ def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int
             dec.beam_reorder(reorder)
         dec.ids[:, cur_len] = current
         cur_len += 1
-        if all(done) or cur_len >= max_length:
+        if all(h.done for h in hyps) or cur_len >= max_length:
             break
         dec.beam_advance(cur_len)
-    final = beam_scores.tolist()
-    for b in range(B0):
-        if done[b]:
-            continue
-        for j in range(nb):
-            hyps[b].add(dec.ids[b * nb + j, :cur_len].clone(), final[b * nb + j])
-    best, scores = [], []
-    for b in range(B0):
-        ranked = sorted(hyps[b].beams, key=lambda x: x[0])
-        for _ in range(num_return_sequences):
-            sc_, h = ranked.pop()
-            best.append(h); scores.append(sc_)
-    L = min(max(len(h) for h in best) + 1, max_length)
-    out = torch.full((len(best), L), pad, dtype=torch.int64, device=dev)
-    for i, h in enumerate(best):
-        out[i, :len(h)] = h
-        if len(h) < L:
-            out[i, len(h)] = eos_token_id
-    return (out, torch.tensor(scores)) if return_scores else out
+    return _beam_finalize(hyps, nb, num_return_sequences, dec.ids, cur_len, beam_scores, max_length, eos_token_id, pad, return_scores)
+
+
+def beam_generate(make_decoder, input_ids: torch.Tensor, max_length: int, *, num_beams: int, num_beam_groups: int, do_sample: bool,
+                  num_return_sequences: int, eos_token_id: int, pad_token_id: Optional[int], seed: int, top_k=None, top_p=None,
+                  temperature=1.0, typical_p=None, early_stopping=None, renormalize_logits=None, length_penalty: float = 1.0,
+                  diversity_penalty=None) -> torch.Tensor:
+    """The beam arms of both models' `generate`: group beam search when num_beam_groups != 1, else beam search / beam sample.
+    make_decoder(rows) builds the model's decoder with one row per beam; eos / pad are what the model resolved from the arguments
+    and its config.  beam_sample draws from a generator seeded with `seed`."""
+    common = dict(num_beams=num_beams, early_stopping=bool(early_stopping), length_penalty=length_penalty,
+                  num_return_sequences=num_return_sequences, eos_token_id=eos_token_id, pad_token_id=pad_token_id)
+    if num_beam_groups != 1:
+        if num_beams <= 1 or num_beam_groups > num_beams:
+            raise ValueError('`num_beam_groups` has to be smaller or equal to `num_beams`')               # HF's message
+        if do_sample:
+            raise ValueError('Diverse beam search cannot be used in sampling mode. Make sure that `do_sample` is set to `False`.')
+        return group_beam_search(make_decoder(input_ids.shape[0] * num_beams), input_ids, max_length, num_beam_groups=num_beam_groups,
+                                 diversity_penalty=diversity_penalty or 0.0, **common)
+    dec = make_decoder(input_ids.shape[0] * num_beams * (num_return_sequences if do_sample else 1))
+    gen = torch.Generator(device=dec.eng.dev).manual_seed(seed) if do_sample else None
+    return beam_search(dec, input_ids, max_length, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
+                       typical_p=typical_p, renormalize_logits=bool(renormalize_logits), generator=gen, **common)
 
 
 def contrastive_search(dec, prompt: torch.Tensor, max_length: int, top_k: int = 4, penalty_alpha: float = 0.6,

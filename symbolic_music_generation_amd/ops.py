@@ -133,30 +133,36 @@ def decode_qkv(x, wqkv, qkv, kc, vc, t_dev, rrb, qr_out, dh):
                                _stream()), 'mxl_decode_qkv')
 
 
-def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, do_sample=False, top_k=0, top_p=1.0,
-                temperature=1.0, repetition_penalty=1.0, typical_p=1.0):
+def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
+                grammar=None, gstate=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0,
+                typical_p=1.0):
     """sampler + embedding row of the sampled token (-> emb_out (B, d) bf16) + counter advance, one launch (V <= 2048).
-    scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1."""
+    scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1.
+    stop = (eos_id, pad_id, min_length) with unfinished (B,) int32 and alive (1,) int32 on the device: the stop state of generation
+    rides on the same launch (mxl_sample_step_stop).  grammar (a grammar.TokenGrammar) with gstate (B,) int32: barred tokens masked
+    and gstate advanced in the same launch, with or without the eos rule (mxl_sample_step_grammar)."""
     B = scores.shape[0]
-    check(lib().mxl_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
-                                int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
-                                float(repetition_penalty if repetition_penalty is not None else 1.0),
-                                float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
-                                float(scale), _p(counter), _stream()), 'mxl_sample_step')
-
-
-def sample_step_stop(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, stop, unfinished, alive, do_sample=False,
-                     top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0):
-    """sample_step with the stop state of generation: stop = (eos_id, pad_id, min_length); unfinished (B,) int32 and alive (1,)
-    int32 on the device (mxl_sample_step_stop).  Same single launch."""
-    B = scores.shape[0]
-    eos, pad, min_length = stop
-    check(lib().mxl_sample_step_stop(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
-                                     int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
-                                     float(repetition_penalty if repetition_penalty is not None else 1.0),
-                                     float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
-                                     float(scale), _p(counter), int(eos), int(pad), int(min_length or 0), _p(unfinished), _p(alive),
-                                     _stream()), 'mxl_sample_step_stop')
+    args = [_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B, int(do_sample),
+            int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
+            float(repetition_penalty if repetition_penalty is not None else 1.0),
+            float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1], float(scale), _p(counter)]
+    name = 'mxl_sample_step'
+    if grammar is not None:
+        _req(gstate, torch.int32, 'sample_step_grammar gstate')
+        if gstate.numel() != B:
+            raise MusicXLError(f'gstate holds {gstate.numel()} rows, the scores {B}')
+        cls, allow, nxt = _grammar_tables(grammar, scores.device, V)
+        if stop is not None and (unfinished is None or alive is None):
+            raise MusicXLError('sample_step_grammar: the eos rule needs unfinished and alive')
+    if stop is not None or grammar is not None:
+        eos, pad, min_length = stop if stop is not None else (-1, 0, 0)
+        args += [int(eos), int(pad), int(min_length or 0), _p(unfinished) if stop is not None else 0,
+                 _p(alive) if stop is not None else 0]
+        name = 'mxl_sample_step_stop'
+    if grammar is not None:
+        args += [_p(cls), _p(allow), _p(nxt), grammar.n_classes, _p(gstate)]
+        name = 'mxl_sample_step_grammar'
+    check(getattr(lib(), name)(*args, _stream()), name)
 
 
 def decode_stop(ids, t_dev, stop, unfinished, alive):
@@ -180,28 +186,6 @@ def _grammar_tables(grammar, device, V):
     if grammar.vocab_size != int(V):
         raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
     return grammar.to(device)
-
-
-def sample_step_grammar(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, grammar, gstate, stop=None, unfinished=None,
-                        alive=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0):
-    """sample_step / sample_step_stop under a grammar.TokenGrammar: barred tokens masked and gstate (B,) int32 advanced in the same
-    single launch (mxl_sample_step_grammar).  stop = (eos, pad, min_length) with unfinished / alive, or None: no eos rule."""
-    B = scores.shape[0]
-    _req(gstate, torch.int32, 'sample_step_grammar gstate')
-    if gstate.numel() != B:
-        raise MusicXLError(f'gstate holds {gstate.numel()} rows, the scores {B}')
-    cls, allow, nxt = _grammar_tables(grammar, scores.device, V)
-    eos, pad, min_length = stop if stop is not None else (-1, 0, 0)
-    if stop is not None and (unfinished is None or alive is None):
-        raise MusicXLError('sample_step_grammar: the eos rule needs unfinished and alive')
-    check(lib().mxl_sample_step_grammar(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
-                                        int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0),
-                                        float(temperature), float(repetition_penalty if repetition_penalty is not None else 1.0),
-                                        float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
-                                        float(scale), _p(counter), int(eos), int(pad), int(min_length or 0),
-                                        _p(unfinished) if stop is not None else 0, _p(alive) if stop is not None else 0,
-                                        _p(cls), _p(allow), _p(nxt), grammar.n_classes, _p(gstate), _stream()),
-          'mxl_sample_step_grammar')
 
 
 def grammar_mask(scores, V, grammar, gstate):

@@ -8,6 +8,7 @@ from typing import Any, Dict, Optional
 
 import torch
 
+from . import ops
 from ._lib import MusicXLError
 from .module import EngineModule
 from .rf_engine import RFEngine
@@ -148,7 +149,12 @@ class MyReformerModelWithLMHead(EngineModule):
     @torch.no_grad()
     def generate(self, input_ids=None, max_length: Optional[int] = None, do_sample: bool = False, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
-                 typical_p: Optional[float] = None, seed: int = 77, use_cache: bool = True, rotations=None, **unsupported):
+                 typical_p: Optional[float] = None, seed: int = 77, use_cache: bool = True, rotations=None, num_beams: int = 1,
+                 penalty_alpha=None, early_stopping=None, renormalize_logits=None, num_return_sequences: int = 1,
+                 num_beam_groups: int = 1, length_penalty: float = 1.0, diversity_penalty=None,
+                 attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
+                 pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
+                 grammar=None, **unsupported):
         """`model.generate(...)` as the reference drives it (musicnlp/trainer/eval.py:277-333): greedy, or sampling with
         top-k / top-p / typical-p / temperature / repetition penalty (applied, as HF does, to the raw logits); token selection
         runs on the device (the TransfoXL decoder's sampler kernel).
@@ -167,90 +173,55 @@ class MyReformerModelWithLMHead(EngineModule):
 
         grammar (a `grammar.TokenGrammar`): greedy decoding and sampling in which every row may only emit tokens its grammar state
         allows, as MyTransfoXLLMHeadModel.generate: the mask runs on the device before the sampler, the state advance after it."""
-        from . import ops
-        from .generate import (STOP_CHUNK, check_grammar_args, left_pad_counts, raise_on_bad_prompt, resolve_max_length, stop_config,
-                               stop_width)
-        eos_token_id = unsupported.pop('eos_token_id', None)
-        pad_token_id = unsupported.pop('pad_token_id', None)
-        min_length = unsupported.pop('min_length', None)
-        max_new_tokens = unsupported.pop('max_new_tokens', None)
-        grammar = unsupported.pop('grammar', None)
+        from .generate import (STOP_CHUNK, beam_generate, check_grammar_args, left_pad_counts, raise_on_bad_prompt, resolve_max_length,
+                               sample_unfused, sampling_config, stop_config, stop_width)
+        from .rf_generate import RFDecoder
+        num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
         check_grammar_args(grammar, self.config.vocab_size, stop)
-        if grammar is not None and ((unsupported.get('num_beams', 1) or 1) > 1 or (unsupported.get('num_beam_groups', 1) or 1) != 1):
+        if grammar is not None and (num_beams > 1 or num_beam_groups != 1):
             raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam or group-beam search')
-        eos_b = self.config.eos_token_id if eos_token_id is None else eos_token_id          # beam / group-beam search
-        pad_b = self.config.pad_token_id if pad_token_id is None else pad_token_id
-        mask = unsupported.pop('attention_mask', None)
-        if mask is not None and input_ids is not None and any(left_pad_counts(mask, tuple(input_ids.shape))):
+        if attention_mask is not None and input_ids is not None and any(left_pad_counts(attention_mask, tuple(input_ids.shape))):
             # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
             raise MusicXLError(f'{type(self).__name__}.generate does not support padded prompts (attention_mask with zeros); '
                                'generate prompts of different lengths one length at a time')
         top_k = getattr(self.config, 'top_k', 50) if top_k is None else top_k        # HF fills it from the config: default 50
-        if unsupported.get('penalty_alpha') and not do_sample and top_k is not None and top_k > 1:
+        if penalty_alpha and not do_sample and top_k is not None and top_k > 1:
             # HF 4.25.1 contrastive_search takes `past_buckets_states` as its cache and indexes past[0][0].shape: the bucket entry
             # of a local layer is None, so the reference stack fails there too; the ValueError is this package's
             raise ValueError(f"{type(self).__name__} **can't** be used for contrastive search: its cache (past_buckets_states) "
                              'is not a per-layer tensor cache that HF\'s routine can replicate per candidate')
-        if unsupported.get('num_return_sequences', 1) not in (None, 1) and (unsupported.get('num_beams', 1) or 1) == 1:
+        if nrs != 1 and num_beams == 1:
             if not do_sample:
                 raise ValueError('num_return_sequences has to be 1 when doing greedy search')
-            input_ids = input_ids.repeat_interleave(int(unsupported.pop('num_return_sequences')), 0)
+            input_ids = input_ids.repeat_interleave(nrs, 0)
         if max_new_tokens is not None:
             max_length = resolve_max_length(max_length, max_new_tokens, input_ids.shape[1], None)
-        num_beams = unsupported.pop('num_beams', 1) or 1
-        num_beam_groups = unsupported.pop('num_beam_groups', 1) or 1
-        diversity_penalty = unsupported.pop('diversity_penalty', None)
-        if num_beam_groups != 1:
-            # diverse (group) beam search (eval.py:303-317) over the cached decoder's beam hooks
-            if num_beams <= 1 or num_beam_groups > num_beams:
-                raise ValueError('`num_beam_groups` has to be smaller or equal to `num_beams`')
-            if do_sample:
-                raise ValueError('Diverse beam search cannot be used in sampling mode. Make sure that `do_sample` is set to `False`.')
-            from .generate import group_beam_search
-            from .rf_generate import RFDecoder
-            nrs = int(unsupported.pop('num_return_sequences', 1) or 1)
+        if num_beams > 1 or num_beam_groups != 1:
+            # the reference's 'beam' strategy (eval.py:302-321) and its diverse (group) form over the cached decoder's beam hooks,
+            # with an explicit eos / pad in place of the config's
             self._maybe_resync()
             was = self.training
             self.eval()
             try:
                 max_length = int(max_length or c_max_len(self.config))
-                dec = RFDecoder(self.engine, input_ids.shape[0] * num_beams, max_length, rotations=rotations, seed=seed)
-                return group_beam_search(dec, input_ids, max_length, num_beams=num_beams, num_beam_groups=num_beam_groups,
-                                         diversity_penalty=diversity_penalty or 0.0,
-                                         early_stopping=bool(unsupported.get('early_stopping')),
-                                         length_penalty=float(unsupported.get('length_penalty', 1.0) or 1.0),
-                                         num_return_sequences=nrs, eos_token_id=eos_b, pad_token_id=pad_b)
+                return beam_generate(lambda rows: RFDecoder(self.engine, rows, max_length, rotations=rotations, seed=seed), input_ids,
+                                     max_length, num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample,
+                                     num_return_sequences=nrs,
+                                     eos_token_id=self.config.eos_token_id if eos_token_id is None else eos_token_id,
+                                     pad_token_id=self.config.pad_token_id if pad_token_id is None else pad_token_id, seed=seed,
+                                     top_k=top_k, top_p=top_p, temperature=temperature, typical_p=typical_p,
+                                     early_stopping=early_stopping, renormalize_logits=renormalize_logits,
+                                     length_penalty=float(length_penalty or 1.0), diversity_penalty=diversity_penalty)
             finally:
                 if was:
                     self.train()
-        if num_beams > 1:
-            # the reference's 'beam' strategy (eval.py:302-321): HF beam_search / beam_sample over the cached decoder
-            from .generate import beam_search
-            from .rf_generate import RFDecoder
-            nrs = int(unsupported.pop('num_return_sequences', 1) or 1)
-            self._maybe_resync()
-            was = self.training
-            self.eval()
-            try:
-                max_length = int(max_length or c_max_len(self.config))
-                dec = RFDecoder(self.engine, input_ids.shape[0] * num_beams * (nrs if do_sample else 1), max_length,
-                                rotations=rotations, seed=seed)
-                gen = torch.Generator(device=self.device).manual_seed(seed) if do_sample else None
-                return beam_search(dec, input_ids, max_length, num_beams=num_beams, do_sample=do_sample, top_k=top_k, top_p=top_p,
-                                   temperature=temperature, typical_p=typical_p,
-                                   early_stopping=bool(unsupported.get('early_stopping')),
-                                   length_penalty=float(unsupported.get('length_penalty', 1.0) or 1.0),
-                                   renormalize_logits=bool(unsupported.get('renormalize_logits')), num_return_sequences=nrs,
-                                   eos_token_id=eos_b, pad_token_id=pad_b, generator=gen)
-            finally:
-                if was:
-                    self.train()
-        if unsupported:
-            ok = {'early_stopping', 'renormalize_logits'}      # no effect: no beams here; the sampler always renormalises
-            bad = [k for k, v in unsupported.items() if k not in ok and v not in (None, False, 1, 1.0)]
-            if bad:
-                raise NotImplementedError(f'generation options not covered: {bad}')
+        # no beams here: early_stopping has no effect and the sampler always renormalises; a penalty_alpha that did not select
+        # contrastive search and a length_penalty are options this path does not cover
+        bad = [k for k, v in dict(penalty_alpha=penalty_alpha, length_penalty=length_penalty, **unsupported).items()
+               if v not in (None, False, 1, 1.0)]
+        if bad:
+            raise NotImplementedError(f'generation options not covered: {bad}')
         self._maybe_resync()
         c = self.config
         was_training = self.training
@@ -265,7 +236,6 @@ class MyReformerModelWithLMHead(EngineModule):
             return ids0[:, :max_length]
         try:
             if use_cache:
-                from .rf_generate import RFDecoder
                 dec = getattr(self, '_decoder', None)
                 if dec is None or dec.B != B or dec.Tmax < max_length:
                     dec = self._decoder = RFDecoder(self.engine, B, max_length, seed=seed)
@@ -282,27 +252,18 @@ class MyReformerModelWithLMHead(EngineModule):
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
             unfinished = torch.ones(B, device=self.device, dtype=torch.int32)
             alive = torch.zeros(1, device=self.device, dtype=torch.int32)
+            gstate = None
             if grammar is not None:
                 gstate = torch.empty(B, device=self.device, dtype=torch.int32)
                 gbad = torch.empty(B, device=self.device, dtype=torch.int32)
                 ops.grammar_scan(buf, Tp, grammar, gstate, gbad)
                 raise_on_bad_prompt(grammar, buf, gbad)
+            sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
             for cur in range(Tp, max_length):
                 Tf = cur if cur <= 64 else (cur + 63) // 64 * 64
                 out = self.engine.forward(buf[:, :Tf].contiguous(), labels=None, train=False)
                 last = out['logits'][:, cur - 1].contiguous()
-                if stop is not None:
-                    ops.mask_eos_below(last[:, :V], V, t_dev, stop)
-                if grammar is not None:
-                    ops.grammar_mask(last[:, :V], V, grammar, gstate)
-                ops.sample(last, buf, t_dev, rng, seed, do_sample=do_sample, top_k=top_k or 0,
-                           top_p=top_p if top_p is not None else 1.0, temperature=temperature,
-                           repetition_penalty=repetition_penalty, typical_p=typical_p)
-                ops.decode_advance(t_dev, rng)
-                if grammar is not None:
-                    ops.grammar_advance(buf, t_dev, grammar, gstate, None if stop is None else unfinished)
-                if stop is not None:
-                    ops.decode_stop(buf, t_dev, stop, unfinished, alive)
+                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, stop, unfinished, alive, grammar, gstate)
                 if Tf > cur:
                     buf[:, cur + 1:Tf] = pad          # keep the padding clean (the sampler wrote position `cur` only)
                 # a whole forward per token: reading the live-row count every STOP_CHUNK tokens costs nothing in comparison

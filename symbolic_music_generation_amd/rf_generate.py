@@ -26,6 +26,7 @@ import torch
 
 from . import ops
 from ._lib import MusicXLError
+from .generate import check_grammar_args, decode_lanes, raise_on_bad_prompt, sample_unfused, sampling_config
 
 
 class RFDecoder:
@@ -104,7 +105,6 @@ class RFDecoder:
 
     # ---------------------------------------------------------------- prompt
     def prefill(self, prompt: torch.Tensor, sampling: dict, stop: Optional[tuple] = None, grammar=None):
-        from .generate import check_grammar_args, raise_on_bad_prompt
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and 1 <= Tp <= self.Tmax
@@ -156,18 +156,9 @@ class RFDecoder:
         self._last = logits
         if sampling is None:                 # the caller picks the token (beam search)
             return
-        V = self.eng.cfg.vocab_size
-        if self._stop is not None:          # min_length: eos barred below it (after the trace above)
-            ops.mask_eos_below(logits[:, :V], V, self.t_dev, self._stop)
-        g = self._grammar
-        if g is not None:                    # barred tokens -inf before the sampler (its repetition penalty keeps -inf at -inf)
-            ops.grammar_mask(logits[:, :V], V, g, self.gstate)
-        ops.sample(logits[:, :V], self.ids, self.t_dev, self.rng, self.seed, **sampling)
-        ops.decode_advance(self.t_dev, self.rng)
-        if g is not None:                    # before the stop rule: rows finished before this step keep their state
-            ops.grammar_advance(self.ids, self.t_dev, g, self.gstate, None if self._stop is None else self.unfinished)
-        if self._stop is not None:
-            ops.decode_stop(self.ids, self.t_dev, self._stop, self.unfinished, self.alive)
+        # (min_length and the grammar mask write into the logits: after the trace above)
+        sample_unfused(logits, self.eng.cfg.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, self._stop,
+                       self.unfinished, self.alive, self._grammar, self.gstate)
 
     # ---------------------------------------------------------------- one token
     def step(self, t: int, sampling: dict):
@@ -279,25 +270,22 @@ class RFDecoder:
         and the loop ends once none is live -- the live-row count is read back every `stop_chunk` steps, one chunk late
         (generate.run_until_finished) -- and the output is cut to the longest row.  grammar: a grammar.TokenGrammar; every row may
         only emit tokens its grammar state allows (mask before the sampler, state advance after it, both on the device)."""
-        from .generate import run_until_finished, stop_width
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
-        sampling = dict(do_sample=do_sample, top_k=top_k or 0, top_p=top_p if top_p is not None else 1.0, temperature=temperature,
-                        repetition_penalty=repetition_penalty, typical_p=typical_p)
+        return decode_lanes(self, [self], [None], prompt, max_length,
+                            sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), False, None, stop,
+                            stop_chunk, grammar)
+
+    def begin(self, prompt, max_length, sampling, use_graph=False, n_pad=None, stop=None, grammar=None) -> int:
+        """generate.decode_lanes' entry: prompt pass and first token; returns the `replay_once()` calls left to max_length.  There
+        is no graph to capture here, and padded prompts are not supported."""
+        assert not use_graph and n_pad is None
         Tp = prompt.shape[1]
-        if max_length <= Tp:
-            return prompt[:, :max_length]
         self.prefill(prompt.to(self.eng.dev), sampling, stop, grammar)
-        if stop is None:
-            for t in range(Tp, max_length - 1):
-                self.step(t, sampling)
-            self.steps_run = max(max_length - 1 - Tp, 0)
-            return self.ids[:, :max_length].clone()
         self._next_t, self._sampling = Tp, sampling
-        self.steps_run = run_until_finished([(self, None)], max(max_length - 1 - Tp, 0), stop_chunk)[0]
-        return self.ids[:, :stop_width(self.ids, self.unfinished, Tp, max_length, stop[0])].clone()
+        return max(max_length - 1 - Tp, 0)
 
     def replay_once(self):
-        """the next step of generate() with stopping (run_until_finished drives it)"""
+        """the next step of generate() (decode_lanes and run_until_finished drive it)"""
         self.step(self._next_t, self._sampling)
         self._next_t += 1

@@ -224,8 +224,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
         processor would.  It combines with `num_return_sequences`, padded prompts, `eos_token_id` / `min_length` /
         `max_new_tokens`; the prompts must obey the grammar themselves (MusicXLError otherwise).  The constraint is syntactic: it
         does not make the durations of a bar add up.  Beam, group-beam and contrastive search take no grammar."""
-        from .generate import (XLDecoder, XLDecoderLanes, beam_search, check_grammar_args, contrastive_search, group_beam_search,
-                               left_pad_counts, resolve_max_length, stop_config)
+        from .generate import (XLDecoder, XLDecoderLanes, beam_generate, check_grammar_args, contrastive_search, left_pad_counts,
+                               resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -255,25 +255,13 @@ class MyTransfoXLLMHeadModel(EngineModule):
             dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
                                       eos_token_id=eos_b, pad_token_id=pad_b)
-        if num_beam_groups != 1:
-            if num_beams <= 1 or num_beam_groups > num_beams:
-                raise ValueError('`num_beam_groups` has to be smaller or equal to `num_beams`')               # HF's message
-            if do_sample:
-                raise ValueError('Diverse beam search cannot be used in sampling mode. Make sure that `do_sample` is set to `False`.')
-            dec = XLDecoder(self.engine, input_ids.shape[0] * num_beams, max_length, seed=seed)
-            return group_beam_search(dec, input_ids, max_length, num_beams=num_beams, num_beam_groups=num_beam_groups,
-                                     diversity_penalty=diversity_penalty or 0.0, early_stopping=bool(early_stopping),
-                                     length_penalty=length_penalty, num_return_sequences=num_return_sequences,
-                                     eos_token_id=eos_b, pad_token_id=pad_b)
-        if num_beams > 1:
-            rows = input_ids.shape[0] * num_beams * (num_return_sequences if do_sample else 1)
-            dec = XLDecoder(self.engine, rows, max_length, seed=seed)
-            gen = torch.Generator(device=self.device).manual_seed(seed) if do_sample else None
-            return beam_search(dec, input_ids, max_length, num_beams=num_beams, do_sample=do_sample, top_k=top_k, top_p=top_p,
-                               temperature=temperature, typical_p=typical_p, early_stopping=bool(early_stopping),
-                               renormalize_logits=bool(renormalize_logits),
-                               length_penalty=length_penalty, num_return_sequences=num_return_sequences,
-                               eos_token_id=eos_b, pad_token_id=pad_b, generator=gen)
+        if num_beam_groups != 1 or num_beams > 1:
+            return beam_generate(lambda rows: XLDecoder(self.engine, rows, max_length, seed=seed), input_ids, max_length,
+                                 num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample,
+                                 num_return_sequences=num_return_sequences, eos_token_id=eos_b, pad_token_id=pad_b, seed=seed,
+                                 top_k=top_k, top_p=top_p, temperature=temperature, typical_p=typical_p,
+                                 early_stopping=early_stopping, renormalize_logits=renormalize_logits,
+                                 length_penalty=length_penalty, diversity_penalty=diversity_penalty)
         if num_return_sequences > 1:
             if not do_sample:
                 raise ValueError('num_return_sequences has to be 1 when doing greedy search')       # HF's message
