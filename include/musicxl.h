@@ -478,6 +478,33 @@ int mxl_grammar_advance(const void* ids, int ld_ids, const int* t_dev, int B, in
  * -1 = the prompt obeys the grammar. */
 int mxl_grammar_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* allow, const void* next, int C,
                      int start, int* gstate, int* first_bad, void* stream);
+/* Bar budget on top of the grammar: every channel of a generated bar is exactly as long as the row's time signature.  Per row two
+ * int32 words kept on the device: gbar (bar length in slots; 0 = the row is unconstrained) and grem (slots still free in the open
+ * channel).  Tables (device): slots (V,) uint16, duration token -> slots, 0 = not a duration, 0xFFFF = a duration of unknown length;
+ * bars (V,) uint16, time signature token -> bar length in slots (0 = unconstrained), 0xFFFF = not a time signature; class bit masks
+ * opens (rem = bar), need_free (allowed only while rem > 0) and need_full (allowed only at rem == 0), over the classes of `cls`.
+ * In a row with bar > 0 a token is barred if its slots entry exceeds rem or its class is in need_free at rem == 0 or in need_full
+ * at rem > 0; rows with bar == 0 are untouched.  A token moves the row: a bars entry sets bar (rem = 0), a class in opens sets
+ * rem = bar, a slots entry k takes k from rem.  The rule never reads the grammar state.
+ * mxl_sample_step_budget: mxl_sample_step_grammar with the budget mask applied together with the grammar mask where the row enters
+ * LDS, and (gbar[b], grem[b]) moved where gstate[b] moves (after the eos rule; a row finished before the step keeps them).  Row b's
+ * workgroup is the only one that touches its words: no ordering between workgroups is needed for them. */
+int mxl_sample_step_budget(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                           unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                           float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                           int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
+                           const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
+                           unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, void* stream);
+/* The same around mxl_sample / mxl_sample_large: mxl_budget_mask after mxl_grammar_mask (in place, one thread per score),
+ * mxl_budget_advance beside mxl_grammar_advance, before mxl_decode_stop of the same step. */
+int mxl_budget_mask(float* scores, int ldl, int B, int V, const void* cls, const void* slots, unsigned need_free,
+                    unsigned need_full, const int* gbar, const int* grem, void* stream);
+int mxl_budget_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, const void* slots,
+                       const void* bars, unsigned opens, int* gbar, int* grem, const int* unfinished, void* stream);
+/* (gbar, grem) of every row after its prompt, from (0, 0): columns 0..Tp-1, ids < 0 (left pads) and ids >= V (mxl_grammar_scan
+ * reports those) skipped.  first_bad[b] = column of the first token the budget bars, where the walk of that row stops; -1 = none. */
+int mxl_budget_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* slots, const void* bars,
+                    unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, int* first_bad, void* stream);
 /* Contrastive search (the reference's 'contrastive' strategy, musicnlp/trainer/eval.py:296-302, over the mems patch of
  * musicnlp/models/transformer_xl.py:229-234; HF 4.25.1 GenerationMixin.contrastive_search with `_ranking_fast`):
  *   score[b*K + k] = (1 - alpha) * probs[b*K + k] - alpha * max_{s < S} cos(hid[b*K + k], ctx[b][s]);  sel[b] = argmax_k score

@@ -363,12 +363,16 @@ constexpr int SORT_N = 2048;
 // G: grammar-constrained (mxl_sample_step_grammar) -- a token whose class bit is clear in `gallow` (the allow mask of the row's
 // grammar state) is -inf from the moment the row enters LDS and is never rewritten by the repetition penalty, which is HF's
 // processor order "penalty, min_length, grammar, then the warpers": every warper and the renormalisation see allowed tokens only.
-template <bool G = false>
+// BUD (with G): the bar budget on top (mxl_sample_step_budget) -- the caller has already cleared from `gallow` the classes the row's
+// (bar, rem) bars, and a token whose `bslots` entry exceeds `remcap` (the slots still free; 0xFFFF in an unconstrained row, which
+// admits every entry) is -inf in the same place.
+template <bool G = false, bool BUD = false>
 __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, const long long* ids, int ld_ids,
                                           const int* t_dev, const unsigned long long* rng_ctr, unsigned long long seed,
                                           int do_sample, int top_k, float top_p, float temperature,
                                           float repetition_penalty, float typical_p, float* out_probs, int eos_id = -1,
-                                          int min_length = 0, const unsigned char* gcls = nullptr, uint32_t gallow = 0u) {
+                                          int min_length = 0, const unsigned char* gcls = nullptr, uint32_t gallow = 0u,
+                                          const unsigned short* bslots = nullptr, int remcap = 0) {
     __shared__ float key[SORT_N];
     __shared__ int idx[SORT_N];
     __shared__ int sh_pick;
@@ -376,7 +380,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
     const float* row = logp + (size_t)b * ldl;
     const float invt = 1.f / temperature;
     for (int i = tid; i < SORT_N; i += 256) {
-        if (G) key[i] = (i < V && ((gallow >> gcls[i]) & 1u)) ? row[i] * invt : -INFINITY;
+        if (G) key[i] = (i < V && ((gallow >> gcls[i]) & 1u) && (!BUD || (int)bslots[i] <= remcap)) ? row[i] * invt : -INFINITY;
         else key[i] = i < V ? row[i] * invt : -INFINITY;
         idx[i] = i;
     }
@@ -389,7 +393,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
         const long long* hist = ids + (size_t)b * ld_ids;
         for (int j = tid; j <= tcur; j += 256) {
             const long long tok = hist[j];
-            if (tok >= 0 && tok < V && (!G || ((gallow >> gcls[tok]) & 1u))) {
+            if (tok >= 0 && tok < V && (!G || (((gallow >> gcls[tok]) & 1u) && (!BUD || (int)bslots[tok] <= remcap)))) {
                 const float v = row[tok];
                 key[tok] = (v < 0.f ? v * repetition_penalty : v / repetition_penalty) * invt;
             }
@@ -568,6 +572,35 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
     return sh_pick;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Bar budget on top of the grammar (grammar.BarBudget): per row `bar` (bar length in slots, 0 = unconstrained) and `rem` (slots
+// still free in the open channel).  slots (V,) uint16: duration token -> slots, 0 = no duration, 0xFFFF = unknown length; bars (V,)
+// uint16: time signature token -> bar length, 0xFFFF = no time signature; opens / need_free / need_full: class bit masks.  The rule
+// reads the token's class and the two integers only, never the automaton state.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int BUDGET_NONE = 0xFFFF;          // slots: unknown length (beyond any rem); bars: not a time signature
+
+struct BudgetArgs {
+    const unsigned short* slots;
+    const unsigned short* bars;
+    uint32_t opens, need_free, need_full;
+    int* gbar;
+    int* grem;
+};
+
+// classes a row at (bar, rem) bars: the closers while slots are free, the note starters once none is
+__device__ __forceinline__ uint32_t budget_deny(int bar, int rem, uint32_t need_free, uint32_t need_full) {
+    return bar > 0 ? (rem > 0 ? need_full : need_free) : 0u;
+}
+// the largest `slots` entry the row admits
+__device__ __forceinline__ int budget_remcap(int bar, int rem) { return bar > 0 ? rem : BUDGET_NONE; }
+// (bar, rem) after a token of class c with slots entry k and bars entry sig (BarBudget.move)
+__device__ __forceinline__ void budget_move(int& bar, int& rem, int c, int k, int sig, uint32_t opens) {
+    if (sig != BUDGET_NONE) { bar = sig; rem = 0; }
+    if ((opens >> c) & 1u) rem = bar;
+    if (bar > 0 && k != BUDGET_NONE) rem = max(rem - k, 0);
+}
+
 __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl, int V, long long* ids, int ld_ids,
                                                      const int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                      int do_sample, int top_k, float top_p, float temperature,
@@ -587,7 +620,14 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl,
 // state along the token the row keeps.  The move sits AFTER the eos rule: a row that was finished before this step emits pad and
 // its state stays frozen (the pad is not the row's choice and need not be a token the state allows); the step in which a live row
 // emits eos still moves it, so a finished row of the music grammar rests in END.
-template <bool G>
+//
+// BUD (mxl_sample_step_budget, with G): the row's (gbar[b], grem[b]) narrow that mask further (budget_deny, budget_remcap), and
+// thread 0 moves them in the same place and under the same condition as the grammar state.  gbar / grem are per-row words: row b's
+// workgroup is their only reader and writer within a launch, and the next launch on the stream sees them by stream order -- there is
+// no hand-off between workgroups here beyond the arrival counter below.
+// It is a compile-time variant: `budget` is one trailing BudgetArgs kernel argument that only the BUD instantiation has, so the
+// kernels behind mxl_sample_step, _stop and _grammar keep their arguments and their code.
+template <bool G, bool BUD = false, typename... BA>
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, int ldl, int V, long long* ids, int ld_ids,
                                                           int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                           int do_sample, int top_k, float top_p, float temperature,
@@ -595,11 +635,18 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
                                                           int d, float scale, int* counter, int eos_id, int pad_id,
                                                           int min_length, int* unfinished, int* alive,
                                                           const unsigned char* gcls = nullptr, const uint32_t* gallow = nullptr,
-                                                          const unsigned char* gnext = nullptr, int C = 0, int* gstate = nullptr) {
+                                                          const unsigned char* gnext = nullptr, int C = 0, int* gstate = nullptr,
+                                                          BA... budget) {
+    static_assert(sizeof...(BA) == (BUD ? 1 : 0) && (G || !BUD), "the bar budget rides on the grammar: one BudgetArgs argument");
     const int gs = G ? gstate[blockIdx.x] : 0;
-    int tok = sample_row<G>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
-                            repetition_penalty, typical_p, nullptr, unfinished ? eos_id : -1, unfinished ? min_length : 0,
-                            gcls, G ? gallow[gs] : 0u);
+    BudgetArgs bud{};
+    if constexpr (BUD) bud = BudgetArgs{budget...};
+    int bbar = 0, brem = 0;
+    if (BUD) { bbar = bud.gbar[blockIdx.x]; brem = bud.grem[blockIdx.x]; }
+    int tok = sample_row<G, BUD>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
+                                 repetition_penalty, typical_p, nullptr, unfinished ? eos_id : -1, unfinished ? min_length : 0,
+                                 gcls, G ? (BUD ? gallow[gs] & ~budget_deny(bbar, brem, bud.need_free, bud.need_full) : gallow[gs]) : 0u,
+                                 BUD ? bud.slots : nullptr, BUD ? budget_remcap(bbar, brem) : 0);
     const int b = blockIdx.x, tid = threadIdx.x;
     __shared__ int sh_tok, sh_live;
     bool was_live = true;                       // (thread 0) the token is the row's own choice
@@ -619,6 +666,11 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         tok = sh_tok;
     }
     if (G && tid == 0 && was_live && tok >= 0 && tok < V) gstate[b] = gnext[gs * C + gcls[tok]];
+    if (BUD && tid == 0 && was_live && tok >= 0 && tok < V) {
+        budget_move(bbar, brem, gcls[tok], bud.slots[tok], bud.bars[tok], bud.opens);
+        bud.gbar[b] = bbar;
+        bud.grem[b] = brem;
+    }
     if (tid == 0) ids[(size_t)b * ld_ids + *t_dev + 1] = tok;
     const int id = (tok < 0 || tok >= V) ? 0 : tok;
     for (int c = tid; c < (d >> 3); c += 256) {
@@ -738,6 +790,66 @@ __global__ __launch_bounds__(64) void grammar_scan_kernel(const long long* ids, 
         }
     }
     if (lane == 0) { gstate[b] = s; first_bad[b] = bad; }
+}
+
+// The bar budget around the same samplers.  After mxl_grammar_mask: -inf on every token the row's (bar, rem) bars; one thread per
+// score (the order of the two masks does not matter to the result: each only writes -inf).
+__global__ __launch_bounds__(256) void budget_mask_kernel(float* scores, int ldl, int B, int V, const unsigned char* cls,
+                                                          const unsigned short* slots, uint32_t need_free, uint32_t need_full,
+                                                          const int* gbar, const int* grem) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * V) return;
+    const int b = (int)(i / V), v = (int)(i - (long long)b * V);
+    const int bar = gbar[b], rem = grem[b];
+    if (((budget_deny(bar, rem, need_free, need_full) >> cls[v]) & 1u) || (int)slots[v] > budget_remcap(bar, rem))
+        scores[(size_t)b * ldl + v] = -INFINITY;
+}
+
+// beside mxl_grammar_advance (before the stop rule of the step): (bar, rem) of every row that chose its token move along it
+__global__ __launch_bounds__(256) void budget_advance_kernel(const long long* ids, int ld_ids, const int* t_dev, int B, int V,
+                                                             const unsigned char* cls, const unsigned short* slots,
+                                                             const unsigned short* bars, uint32_t opens, int* gbar, int* grem,
+                                                             const int* unfinished) {
+    const int t = *t_dev;
+    for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) {
+        if (unfinished && !unfinished[b]) continue;
+        const long long tok = ids[(size_t)b * ld_ids + t];
+        if (tok < 0 || tok >= V) continue;
+        int bar = gbar[b], rem = grem[b];
+        budget_move(bar, rem, cls[tok], slots[tok], bars[tok], opens);
+        gbar[b] = bar;
+        grem[b] = rem;
+    }
+}
+
+// (bar, rem) of every row after its prompt, as grammar_scan_kernel: one wave per row, 64 columns at a time, the walk uniform over
+// the wave.  Ids < 0 (left pads) and ids beyond the vocabulary (the grammar scan reports those) are skipped; first_bad[b] = column
+// of the first token the budget bars, -1 = none.
+__global__ __launch_bounds__(64) void budget_scan_kernel(const long long* ids, int ld_ids, int Tp, int B, int V,
+                                                         const unsigned char* cls, const unsigned short* slots,
+                                                         const unsigned short* bars, uint32_t opens, uint32_t need_free,
+                                                         uint32_t need_full, int* gbar, int* grem, int* first_bad) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long* row = ids + (size_t)b * ld_ids;
+    int bar = 0, rem = 0, bad = -1;
+    for (int base = 0; base < Tp && bad < 0; base += 64) {
+        const int col = base + lane;
+        int c = -1, ks = 0;                                      // c = -1: skip; ks = slots entry | bars entry << 16
+        if (col < Tp) {
+            const long long tok = row[col];
+            if (tok >= 0 && tok < V) { c = cls[tok]; ks = (int)slots[tok] | ((int)bars[tok] << 16); }
+        }
+        const int n = min(64, Tp - base);
+        for (int j = 0; j < n; j++) {
+            const int cj = __shfl(c, j, 64);
+            const int kj = __shfl(ks, j, 64);
+            if (cj < 0) continue;
+            const int k = kj & 0xFFFF, sig = (kj >> 16) & 0xFFFF;
+            if (((budget_deny(bar, rem, need_free, need_full) >> cj) & 1u) || k > budget_remcap(bar, rem)) { bad = base + j; break; }
+            budget_move(bar, rem, cj, k, sig, opens);
+        }
+    }
+    if (lane == 0) { gbar[b] = bar; grem[b] = rem; first_bad[b] = bad; }
 }
 
 }  // namespace
@@ -939,6 +1051,68 @@ extern "C" int mxl_grammar_scan(const void* ids, int ld_ids, int Tp, int B, int 
     MXL_CHECK_ARG(grammar_tables_ok(cls, allow, next, C, gstate));
     hipLaunchKernelGGL(grammar_scan_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const long long*)ids, ld_ids, Tp, B, V,
                        (const unsigned char*)cls, (const uint32_t*)allow, (const unsigned char*)next, C, start, gstate, first_bad);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+static bool budget_tables_ok(const void* cls, const void* slots, const void* bars, unsigned opens, unsigned need_free,
+                             unsigned need_full, const void* gbar, const void* grem) {
+    (void)opens; (void)need_free; (void)need_full;               // any masks are meaningful: bits beyond the classes never match
+    return cls && slots && bars && gbar && grem;
+}
+
+extern "C" int mxl_sample_step_budget(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev,
+                                      unsigned long long* rng_ctr, unsigned long long seed, int B, int do_sample, int top_k,
+                                      float top_p, float temperature, float repetition_penalty, float typical_p, const void* E,
+                                      void* emb_out, int d, float scale, int* counter, int eos_id, int pad_id, int min_length,
+                                      int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C,
+                                      int* gstate, const void* slots, const void* bars, unsigned opens, unsigned need_free,
+                                      unsigned need_full, int* gbar, int* grem, void* stream) {
+    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
+    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
+    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
+    MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr) && B <= 32767);     // unfinished = NULL: no eos rule
+    MXL_CHECK_ARG(grammar_tables_ok(cls, allow, next, C, gstate));
+    MXL_CHECK_ARG(budget_tables_ok(cls, slots, bars, opens, need_free, need_full, gbar, grem));
+    if (!unfinished) { eos_id = -1; pad_id = 0; min_length = 0; }
+    const BudgetArgs bud{(const unsigned short*)slots, (const unsigned short*)bars, opens, need_free, need_full, gbar, grem};
+    hipLaunchKernelGGL((sample_step_kernel<true, true, BudgetArgs>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
+                       t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
+                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id, min_length, unfinished, alive,
+                       (const unsigned char*)cls, (const uint32_t*)allow, (const unsigned char*)next, C, gstate, bud);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_budget_mask(float* scores, int ldl, int B, int V, const void* cls, const void* slots, unsigned need_free,
+                               unsigned need_full, const int* gbar, const int* grem, void* stream) {
+    MXL_CHECK_ARG(scores && cls && slots && gbar && grem && B > 0 && V > 0 && ldl >= V);
+    const long long n = (long long)B * V;
+    MXL_CHECK_ARG(n <= (1LL << 38));
+    hipLaunchKernelGGL(budget_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V,
+                       (const unsigned char*)cls, (const unsigned short*)slots, need_free, need_full, gbar, grem);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_budget_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, const void* slots,
+                                  const void* bars, unsigned opens, int* gbar, int* grem, const int* unfinished, void* stream) {
+    MXL_CHECK_ARG(ids && t_dev && B > 0 && V > 0 && cls && slots && bars && gbar && grem);
+    hipLaunchKernelGGL(budget_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const long long*)ids, ld_ids,
+                       t_dev, B, V, (const unsigned char*)cls, (const unsigned short*)slots, (const unsigned short*)bars, opens, gbar,
+                       grem, unfinished);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_budget_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* slots, const void* bars,
+                               unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, int* first_bad,
+                               void* stream) {
+    MXL_CHECK_ARG(ids && B > 0 && V > 0 && Tp >= 0 && ld_ids >= Tp && first_bad);
+    MXL_CHECK_ARG(budget_tables_ok(cls, slots, bars, opens, need_free, need_full, gbar, grem));
+    hipLaunchKernelGGL(budget_scan_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const long long*)ids, ld_ids, Tp, B, V,
+                       (const unsigned char*)cls, (const unsigned short*)slots, (const unsigned short*)bars, opens, need_free,
+                       need_full, gbar, grem, first_bad);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }

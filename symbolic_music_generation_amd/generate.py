@@ -52,10 +52,13 @@ def sampling_config(do_sample: bool = False, top_k: Optional[int] = None, top_p:
 
 def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch.Tensor, rng: torch.Tensor, seed: int, sampling: dict,
                    stop: Optional[tuple] = None, unfinished: Optional[torch.Tensor] = None, alive: Optional[torch.Tensor] = None,
-                   grammar=None, gstate: Optional[torch.Tensor] = None):
+                   grammar=None, gstate: Optional[torch.Tensor] = None, gbar: Optional[torch.Tensor] = None,
+                   grem: Optional[torch.Tensor] = None):
     """The sampler tail as separate launches (what mxl_sample_step* does in one): next token of every row from the first V columns
     of `scores` -> ids[:, t + 1], position and RNG counters advanced.  stop = (eos, pad, min_length) with unfinished / alive and
-    grammar with gstate are optional; the masks write into `scores` in place."""
+    grammar with gstate are optional, and a grammar with a bar budget takes gbar / grem as well; the masks write into `scores` in
+    place."""
+    budget = grammar is not None and grammar.budget is not None
     sc = scores[:, :V] if scores.shape[1] != V else scores
     if stop is not None:
         ops.mask_eos_below(sc, V, t_dev, stop)
@@ -63,12 +66,16 @@ def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch
         # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the
         # masks: -inf stays -inf under it, so the result is the same
         ops.grammar_mask(sc, V, grammar, gstate)
+        if budget:
+            ops.budget_mask(sc, V, grammar, gbar, grem)
     ops.sample(sc, ids, t_dev, rng, seed, **sampling)
     ops.decode_advance(t_dev, rng)
     if grammar is not None:
         # before the stop rule rewrites it: `unfinished` still tells which rows chose their token (rows finished before this step
         # keep their state)
         ops.grammar_advance(ids, t_dev, grammar, gstate, None if stop is None else unfinished)
+        if budget:
+            ops.budget_advance(ids, t_dev, grammar, gbar, grem, None if stop is None else unfinished)
     if stop is not None:
         ops.decode_stop(ids, t_dev, stop, unfinished, alive)
 
@@ -123,17 +130,40 @@ def check_grammar_args(grammar, vocab_size: int, stop: Optional[tuple]):
         if only:
             raise ValueError(f'min_length with a grammar whose state {grammar.state_names[only[0]]} allows only the eos token '
                              f'{stop[0]}: below min_length that row would have every token barred')
+        only = grammar.budget.only_token_states(stop[0]) if grammar.budget is not None else []
+        if only:
+            s, bar, rem = only[0]
+            raise ValueError(f'min_length with a bar budget under which state {grammar.state_names[s]} with bar {bar} and {rem} slots '
+                             f'free allows only the eos token {stop[0]}: below min_length that row would have every token barred')
+
+
+def scan_prompt(grammar, ids: torch.Tensor, Tp: int, gstate: torch.Tensor, gbad: torch.Tensor, gbar: torch.Tensor, grem: torch.Tensor):
+    """every row's grammar state and, under a bar budget, its bar length and free slots after columns 0..Tp-1 of ids, on the device.
+    gbad (2, B) int32: the first column that breaks the grammar / the budget (-1 = none), for raise_on_bad_prompt to read at once."""
+    ops.grammar_scan(ids, Tp, grammar, gstate, gbad[0])
+    if grammar.budget is not None:
+        ops.budget_scan(ids, Tp, grammar, gbar, grem, gbad[1])
+    else:
+        gbad[1].fill_(-1)
 
 
 def raise_on_bad_prompt(grammar, ids: torch.Tensor, first_bad: torch.Tensor):
-    """first_bad (B,) from ops.grammar_scan over ids: raises MusicXLError naming row, column and token of the first prompt that
-    breaks the grammar (a constraint that starts from an undefined state guarantees nothing)"""
+    """first_bad (B,) from ops.grammar_scan over ids, or (2, B) from scan_prompt (one read either way): raises MusicXLError naming
+    row, column and token of the first prompt that breaks the grammar (a constraint that starts from an undefined state guarantees
+    nothing), or whose bars the budget does not accept"""
     bad = first_bad.tolist()
+    bad, over = bad if first_bad.dim() == 2 else (bad, [])
     for b, col in enumerate(bad):
         if col >= 0:
             tok = int(ids[b, col])
             raise MusicXLError(f'the prompt of row {b} breaks the grammar at column {col}: token {tok} is not allowed there '
                                f'({sum(1 for c in bad if c >= 0)} of {len(bad)} rows break it)')
+    for b, col in enumerate(over):
+        if col >= 0:
+            tok = int(ids[b, col])
+            how = 'overfills' if int(grammar.budget.slots[tok]) > 0 else 'underfills'
+            raise MusicXLError(f'the prompt of row {b} {how} a bar at column {col}: token {tok} does not fit the slots its time '
+                               f'signature leaves there ({sum(1 for c in over if c >= 0)} of {len(over)} rows break the bar budget)')
 
 
 def check_grammar(ids: torch.Tensor, grammar, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -153,6 +183,30 @@ def check_grammar(ids: torch.Tensor, grammar, attention_mask: Optional[torch.Ten
     gstate = torch.empty(x.shape[0], device=x.device, dtype=torch.int32)
     bad = torch.empty_like(gstate)
     ops.grammar_scan(x, x.shape[1], grammar, gstate, bad)
+    return bad.cpu().to(torch.int64)
+
+
+def check_bar_lengths(ids: torch.Tensor, grammar, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B,) int64 on the CPU, as check_grammar: for every row of ids (B, T) the column of the first token the bar budget of
+    `grammar` (tokenizer.grammar(bar_budget=True)) does not allow -- a duration that overfills its channel, a channel closed before
+    it is full, a duration of unknown length -- and -1 where every channel is as long as the row's time signature says.  Rows whose
+    time signature sets no bar length are reported clean.  Rows on the GPU are walked there (mxl_budget_scan), host tensors by
+    TokenGrammar.walk_budget."""
+    if grammar.budget is None:
+        raise ValueError('check_bar_lengths needs a grammar with a bar budget: tokenizer.grammar(bar_budget=True)')
+    ids = torch.as_tensor(ids)
+    if ids.dim() == 1:
+        ids = ids.view(1, -1)
+    x = ids.to(torch.int64).clone()
+    if attention_mask is not None:
+        m = torch.as_tensor(attention_mask).to(x.device)
+        x[:, :m.shape[1]].masked_fill_(m == 0, -1)
+    if not x.is_cuda:
+        return torch.tensor([grammar.walk_budget(r)[2] for r in x], dtype=torch.int64)
+    x = x.contiguous()
+    gbar = torch.empty(x.shape[0], device=x.device, dtype=torch.int32)
+    grem, bad = torch.empty_like(gbar), torch.empty_like(gbar)
+    ops.budget_scan(x, x.shape[1], grammar, gbar, grem, bad)
     return bad.cpu().to(torch.int64)
 
 
@@ -299,8 +353,11 @@ class XLDecoder:
         # grammar-constrained decoding (generate(grammar=...)): the automaton state of every row, advanced by the sampler launch;
         # `gbad`: first prompt column that breaks the grammar (read once after the prompt pass)
         self.gstate = torch.zeros(batch, device=dev, dtype=torch.int32)
-        self.gbad = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self.gbad = torch.zeros(2, batch, device=dev, dtype=torch.int32)     # (grammar, bar budget)
         self._grammar = None
+        # bar budget of such a grammar (grammar.BarBudget): bar length and free slots of every row, moved where gstate moves
+        self.gbar = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self.grem = torch.zeros(batch, device=dev, dtype=torch.int32)
 
     def _tables(self):
         if self.rd is None:
@@ -327,7 +384,8 @@ class XLDecoder:
         held as -1 in `ids`, which the samplers' repetition penalty skips.
         stop: (eos, pad, min_length) or None (stop_config); every row starts live, and the first token sampled here counts.
         grammar: a grammar.TokenGrammar or None; every row's state after its prompt is computed on the device (pads skipped), and a
-        prompt that breaks the grammar raises."""
+        prompt that breaks the grammar raises.  With a bar budget the same holds for the rows' bar lengths and free slots, and a
+        prompt that overfills or underfills a bar raises."""
         e, c = self.eng, self.eng.cfg
         check_grammar_args(grammar, c.vocab_size, stop)
         self._grammar = grammar
@@ -348,7 +406,7 @@ class XLDecoder:
             self.ids[:, :Tp].masked_fill_(pad, -1)
             x = x.masked_fill(pad, 0)
         if grammar is not None:
-            ops.grammar_scan(self.ids, Tp, grammar, self.gstate, self.gbad)
+            scan_prompt(grammar, self.ids, Tp, self.gstate, self.gbad, self.gbar, self.grem)
         sink_kc, sink_vc = self.kc, self.vc
 
         def kv_sink(l, qkv):
@@ -376,7 +434,8 @@ class XLDecoder:
         """next token of every row from `scores` (log-probabilities, or the head's logits: see mxl_sample_step) -> ids[:, t + 1];
         position and RNG counters advanced.  Short chain: the same launch leaves the token's embedding row in h[0] for the next step."""
         c = self.eng.cfg
-        state = dict(stop=self._stop, unfinished=self.unfinished, alive=self.alive, grammar=self._grammar, gstate=self.gstate)
+        state = dict(stop=self._stop, unfinished=self.unfinished, alive=self.alive, grammar=self._grammar, gstate=self.gstate,
+                     gbar=self.gbar, grem=self.grem)
         if self.fused_sampler:      # the masks, the stop rule, the live-row count and the state advance ride on the sampler launch
             ops.sample_step(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
                             self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model), self.step_ctr,
@@ -486,7 +545,8 @@ class XLDecoder:
         """prompt pass + first sampled token + (use_graph) capture of one decode step; returns the number of `replay_once()`
         calls that complete the generation to max_length.  n_pad: left-padded prompts (prefill); the decode step is the same,
         every row's last prompt token sits at column Tp - 1.  stop: (eos, pad, min_length) (stop_config) or None.  grammar: a
-        grammar.TokenGrammar or None; the captured step reads its device tables, so their identity is part of the graph key"""
+        grammar.TokenGrammar or None; the captured step reads its device tables and, under a bar budget, the budget's tables and
+        class masks, so their identity is part of the graph key"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         self._sampling = sampling
@@ -498,12 +558,15 @@ class XLDecoder:
             # itself is written by the captured launches): a graph captured without a trace would replay without writing one
             key = (tuple(sorted(sampling.items())), self.fused_sampler,
                    None if self.trace is None else self.trace.data_ptr(), stop,
-                   None if grammar is None else tuple(t.data_ptr() for t in grammar.to(self.eng.dev)) + (grammar.n_classes,))
+                   None if grammar is None else tuple(t.data_ptr() for t in grammar.to(self.eng.dev)) + (grammar.n_classes,),
+                   None if grammar is None or grammar.budget is None else
+                   tuple(t.data_ptr() for t in grammar.budget.to(self.eng.dev))
+                   + (grammar.budget.opens, grammar.budget.need_free, grammar.budget.need_full))
             if self.graph is None or self._graph_key != key:
                 # warm-up on a side stream (first launches set function attributes), then capture one step
                 state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(),
                          [k.clone() for k in self.kc], [v.clone() for v in self.vc], self.h[0].clone(),
-                         self.unfinished.clone(), self.alive.clone(), self.gstate.clone())
+                         self.unfinished.clone(), self.alive.clone(), self.gstate.clone(), self.gbar.clone(), self.grem.clone())
                 s = torch.cuda.Stream()
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
@@ -521,6 +584,7 @@ class XLDecoder:
                     a.copy_(b)
                 self.h[0].copy_(state[5])         # (short chain: the next step's embedding row is step state too)
                 self.unfinished.copy_(state[6]); self.alive.copy_(state[7]); self.gstate.copy_(state[8])
+                self.gbar.copy_(state[9]); self.grem.copy_(state[10])
         return max(steps, 0)
 
     def replay_once(self):
@@ -543,7 +607,9 @@ class XLDecoder:
         longest row (finish_at_eos); min_length bars eos below that width.  The decode steps are replayed in chunks of
         `stop_chunk` with the live-row count read back one chunk late (run_until_finished): no per-step host round trip.
         grammar (a grammar.TokenGrammar, e.g. `tokenizer.grammar()`): every row may only emit tokens its grammar state allows; the
-        state lives on the device and moves inside the sampler launch of the captured step.  The prompts must obey the grammar."""
+        state lives on the device and moves inside the sampler launch of the captured step.  The prompts must obey the grammar.
+        A grammar with a bar budget (`tokenizer.grammar(bar_budget=True)`) also keeps every channel of every generated bar exactly as
+        long as the row's time signature: the free slots of the open channel live and move beside the state."""
         return decode_lanes(self, [self], [None], prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
                             stop_config(eos_token_id, pad_token_id, min_length), stop_chunk, grammar)

@@ -16,6 +16,19 @@ are tested against); `to(device)` uploads them once.  Building a grammar needs n
 
 It is SYNTACTIC: what `MusicConverter.str2score` needs to parse a stream.  It does not make the durations of a bar add up to the
 time signature -- a stream that is broken only in its durations passes -- and it bans no rare token.
+
+`music_grammar(vocab, bar_budget=True)` attaches a `BarBudget` (`grammar.budget`) that does: two integers per row ride on the
+automaton, `bar` (the bar length in slots of 4 / 2**precision quarters, set by the TimeSig token; 0 = unconstrained) and `rem` (the
+slots still free in the open channel).  Its tables sit beside the grammar's:
+
+    slots      (V,)   uint16   duration token -> slots, 0 = not a duration, RARE_SLOTS = a duration of unknown length (d_rare)
+    bars       (V,)   uint16   time signature token -> bar length in slots (0 = unconstrained), NO_SIG = not a time signature
+    opens      class bit mask  classes that open a channel (<melody>, <bass>): rem = bar
+    need_free  class bit mask  classes that start a note (pitch, <tup>): allowed only while rem > 0
+    need_full  class bit mask  classes that close a channel (<bass>, <bar>, </s>): allowed only at rem == 0
+
+and a duration of k slots is allowed only if k <= rem.  The rule looks at the token's class and the two integers alone, never at the
+automaton state, so it needs no state of its own and composes with any mask the grammar applies.
 """
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -23,6 +36,8 @@ import numpy as np
 
 MAX_CLASSES = 32
 MAX_STATES = 256
+RARE_SLOTS = 0xFFFF        # `slots` entry of a duration token of unknown length: barred in a constrained bar
+NO_SIG = 0xFFFF            # `bars` entry of a token that is no time signature
 
 
 class TokenGrammar:
@@ -75,6 +90,7 @@ class TokenGrammar:
                 raise ValueError(f'state {self.state_names[s]} can be reached from the start state and allows no class that has '
                                  'a token: generation would face a row with every token barred')
         self._dev: Dict[str, tuple] = {}
+        self.budget: Optional['BarBudget'] = None        # the duration budget riding on this grammar (BarBudget attaches itself)
 
     # ---------------------------------------------------------------- shape
     @property
@@ -138,6 +154,13 @@ class TokenGrammar:
             s = int(self.next[s, c])
         return s, -1
 
+    def walk_budget(self, ids, bar: int = 0, rem: int = 0) -> Tuple[int, int, int]:
+        """(bar, rem, index of the first token the duration budget bars or -1) for a 1-D id sequence (BarBudget.walk): the host
+        reference of mxl_budget_scan.  Ids < 0 are skipped, ids beyond the vocabulary are `walk`'s to report."""
+        if self.budget is None:
+            raise ValueError('this grammar carries no bar budget: build it with grammar(bar_budget=True)')
+        return self.budget.walk(ids, bar, rem)
+
     def accepts(self, ids) -> bool:
         s, bad = self.walk(ids)
         return bad < 0 and (self.accepting is None or s in self.accepting)
@@ -157,9 +180,140 @@ class TokenGrammar:
         return f'TokenGrammar(V={self.vocab_size}, classes={self.n_classes}, states={self.n_states}, start={self.state_names[self.start]})'
 
 
+class BarBudget:
+    def __init__(self, grammar: TokenGrammar, slots, bars, opens, need_free, need_full):
+        """The duration budget of `grammar` (module docstring) from explicit tables: slots / bars (V,) and three sets of classes,
+        each a bit mask or an iterable of class names.  Attaches itself as `grammar.budget`.  Raises ValueError when the tables do
+        not fit the grammar, or when some (state, bar, rem) that can be reached from the start state leaves no token allowed by
+        grammar and budget together: the sampler must never face a row with every token barred."""
+        V, C = grammar.vocab_size, grammar.n_classes
+        slots_a, bars_a = np.asarray(slots), np.asarray(bars)
+        if slots_a.shape != (V,) or bars_a.shape != (V,):
+            raise ValueError(f'slots and bars must be ({V},): one entry per token of the grammar')
+        if slots_a.min() < 0 or slots_a.max() > RARE_SLOTS or bars_a.min() < 0 or bars_a.max() > NO_SIG:
+            raise ValueError('slots / bars entries must fit 16 bits')
+        self.slots = np.ascontiguousarray(slots_a, dtype=np.uint16)
+        self.bars = np.ascontiguousarray(bars_a, dtype=np.uint16)
+
+        def mask(x):
+            if isinstance(x, (int, np.integer)):
+                m = int(x)
+            else:
+                m = 0
+                for name in x:
+                    if name not in grammar.class_names:
+                        raise ValueError(f'unknown token class {name!r}')
+                    m |= 1 << grammar.class_names.index(name)
+            if m < 0 or m >> C:
+                raise ValueError(f'a class mask has a bit set beyond class {C - 1}')
+            return m
+
+        self.opens, self.need_free, self.need_full = mask(opens), mask(need_free), mask(need_full)
+        self.grammar = grammar
+        # the distinct (slots, bars) pairs among the tokens of each class, with the number of tokens that share them
+        self._kinds: List[Dict[Tuple[int, int], int]] = [dict() for _ in range(C)]
+        for c, k, sig in zip(grammar.cls.tolist(), self.slots.tolist(), self.bars.tolist()):
+            self._kinds[c][(k, sig)] = self._kinds[c].get((k, sig), 0) + 1
+        self._reach = self._reachable()
+        for (s, bar, rem), n in self._reach.items():
+            if n == 0:
+                raise ValueError(f'state {grammar.state_names[s]} with bar {bar} and {rem} slots free can be reached from the start '
+                                 'state and allows no token under the bar budget: generation would face a row with every token barred')
+        self._dev: Dict[str, tuple] = {}
+        grammar.budget = self
+
+    # ---------------------------------------------------------------- the rule
+    def allows(self, bar: int, rem: int, c: int, k: int) -> bool:
+        """may a token of class c and `slots` entry k follow in a row at (bar, rem)?  (what the grammar state says comes on top)"""
+        if bar <= 0:
+            return True
+        if k > rem:                                      # a duration that overfills the channel; RARE_SLOTS is beyond any rem
+            return False
+        if (self.need_free >> c) & 1 and rem <= 0:
+            return False
+        if (self.need_full >> c) & 1 and rem != 0:
+            return False
+        return True
+
+    def move(self, bar: int, rem: int, c: int, k: int, sig: int) -> Tuple[int, int]:
+        """(bar, rem) after a token of class c with `slots` entry k and `bars` entry sig"""
+        if sig != NO_SIG:
+            bar, rem = sig, 0
+        if (self.opens >> c) & 1:
+            rem = bar
+        if bar > 0 and k != RARE_SLOTS:
+            rem = max(rem - k, 0)
+        return bar, rem
+
+    def _reachable(self) -> Dict[Tuple[int, int, int], int]:
+        """{(state, bar, rem): tokens allowed there by grammar and budget together} over everything the start state reaches"""
+        g = self.grammar
+        start = (g.start, 0, 0)
+        seen, todo = {}, [start]
+        while todo:
+            node = todo.pop()
+            if node in seen:
+                continue
+            s, bar, rem = node
+            n = 0
+            for c in range(g.n_classes):
+                if not (int(g.allow[s]) >> c) & 1:
+                    continue
+                nxt = int(g.next[s, c])
+                for (k, sig), count in self._kinds[c].items():
+                    if self.allows(bar, rem, c, k):
+                        n += count
+                        succ = (nxt, *self.move(bar, rem, c, k, sig))
+                        if succ not in seen:
+                            todo.append(succ)
+            seen[node] = n
+        return seen
+
+    def only_token_states(self, token: int) -> List[Tuple[int, int, int]]:
+        """reachable (state, bar, rem) in which `token` is the only token allowed (TokenGrammar.only_token_states under the budget)"""
+        g = self.grammar
+        if not 0 <= int(token) < g.vocab_size:
+            return []
+        c, k = int(g.cls[int(token)]), int(self.slots[int(token)])
+        return [node for node, n in self._reach.items()
+                if n == 1 and (int(g.allow[node[0]]) >> c) & 1 and self.allows(node[1], node[2], c, k)]
+
+    # ---------------------------------------------------------------- host reference
+    def walk(self, ids, bar: int = 0, rem: int = 0) -> Tuple[int, int, int]:
+        """(bar, rem, index of the first token the budget bars or -1); the walk stops there.  Ids < 0 (left pads) and ids beyond
+        the vocabulary are skipped: the latter are the grammar's to report."""
+        seq = ids.tolist() if hasattr(ids, 'tolist') else list(ids)
+        V = int(self.slots.shape[0])
+        cls, slots, bars = self.grammar.cls, self.slots, self.bars
+        bar, rem = int(bar), int(rem)
+        for i, tok in enumerate(seq):
+            tok = int(tok)
+            if tok < 0 or tok >= V:
+                continue
+            c, k = int(cls[tok]), int(slots[tok])
+            if not self.allows(bar, rem, c, k):
+                return bar, rem, i
+            bar, rem = self.move(bar, rem, c, k, int(bars[tok]))
+        return bar, rem, -1
+
+    # ---------------------------------------------------------------- device tables
+    def to(self, device):
+        """(slots, bars) on `device`, uploaded once per device: (V,) int16 each, holding the uint16 bit patterns"""
+        import torch
+        key = str(torch.device(device))
+        if key not in self._dev:
+            self._dev[key] = (torch.from_numpy(self.slots.view(np.int16).copy()).to(device),
+                              torch.from_numpy(self.bars.view(np.int16).copy()).to(device))
+        return self._dev[key]
+
+    def __repr__(self):
+        return f'BarBudget(bars={sorted(set(self.bars.tolist()) - {NO_SIG})}, durations={int(((self.slots > 0) & (self.slots < RARE_SLOTS)).sum())})'
+
+
 def from_transitions(cls, class_names: Sequence[str], transitions: Sequence[Tuple[str, str, str]], start: str,
-                     accepting: Optional[Iterable[str]] = None) -> TokenGrammar:
-    """a TokenGrammar from (state, class, successor) triples by name; states are numbered in order of appearance, `start` first"""
+                     accepting: Optional[Iterable[str]] = None, budget: Optional[dict] = None) -> TokenGrammar:
+    """a TokenGrammar from (state, class, successor) triples by name; states are numbered in order of appearance, `start` first.
+    budget: the explicit tables of a BarBudget to attach, as its keyword arguments (slots, bars, opens, need_free, need_full)"""
     states = [start]
     for a, _, b in transitions:
         for s in (a, b):
@@ -178,7 +332,10 @@ def from_transitions(cls, class_names: Sequence[str], transitions: Sequence[Tupl
         allow[i] |= np.uint32(1 << cid[c])
         nxt[i, cid[c]] = states.index(b)
     acc = None if accepting is None else [states.index(s) for s in accepting]
-    return TokenGrammar(cls, allow, nxt, 0, acc, class_names, states)
+    g = TokenGrammar(cls, allow, nxt, 0, acc, class_names, states)
+    if budget is not None:
+        BarBudget(g, **budget)
+    return g
 
 
 # -------------------------------------------------------------------- the music token stream
@@ -205,9 +362,34 @@ MUSIC_TRANSITIONS = [
 ]
 
 
-def music_grammar(vocab) -> TokenGrammar:
+MUSIC_BUDGET_CLASSES = dict(opens=('<melody>', '<bass>'), need_free=('pitch', '<tup>'), need_full=('<bass>', '<bar>', '</s>'))
+
+
+def music_budget_tables(vocab) -> dict:
+    """slots and bars of a MusicVocabulary: a duration token d_x is x / (4 / 2**precision) slots (always whole: that is how the
+    vocabulary lists its durations), d_rare is RARE_SLOTS; TimeSig_n/d is a bar of 2**precision * n / d slots, and TimeSig_rare or a
+    bar that is no whole number of slots is 0 = unconstrained"""
+    from fractions import Fraction
+    V = len(vocab)
+    slot = Fraction(4, 2 ** vocab.precision)
+    slots, bars = np.zeros(V, dtype=np.uint16), np.full(V, NO_SIG, dtype=np.uint16)
+    for tok, i in vocab.tok2id.items():
+        typ = vocab.type(tok)
+        if typ == 'duration':
+            n = None if tok == vocab.rare_duration else Fraction(tok[2:]) / slot
+            if n is not None and (n.denominator != 1 or not 0 < n < RARE_SLOTS):
+                raise ValueError(f'duration token {tok!r} is no whole number of slots')
+            slots[i] = RARE_SLOTS if n is None else int(n)
+        elif typ == 'time_sig':
+            n = Fraction(0) if tok == vocab.rare_time_sig else Fraction(tok[len('TimeSig_'):]) * 2 ** vocab.precision
+            bars[i] = int(n) if n.denominator == 1 and n < NO_SIG else 0
+    return dict(slots=slots, bars=bars, **MUSIC_BUDGET_CLASSES)
+
+
+def music_grammar(vocab, bar_budget: bool = False) -> TokenGrammar:
     """the grammar above for a MusicVocabulary of any pitch kind: the class of a token is its `vocab.type`, and every special
-    token ([PAD] and [OMIT] included) is a class of its own"""
+    token ([PAD] and [OMIT] included) is a class of its own.  bar_budget: attach the duration budget (`grammar.budget`), so that
+    every channel of a bar generated under the grammar is exactly as long as the prompt's time signature says"""
     cid = {c: i for i, c in enumerate(MUSIC_CLASSES)}
     cls = np.zeros(len(vocab), dtype=np.uint8)
     for tok, i in vocab.tok2id.items():
@@ -216,4 +398,5 @@ def music_grammar(vocab) -> TokenGrammar:
         if name not in cid:
             raise ValueError(f'token {tok!r} has no class in the music grammar')
         cls[i] = cid[name]
-    return from_transitions(cls, MUSIC_CLASSES, MUSIC_TRANSITIONS, 'S0', accepting=['END'])
+    return from_transitions(cls, MUSIC_CLASSES, MUSIC_TRANSITIONS, 'S0', accepting=['END'],
+                            budget=music_budget_tables(vocab) if bar_budget else None)

@@ -134,13 +134,14 @@ def decode_qkv(x, wqkv, qkv, kc, vc, t_dev, rrb, qr_out, dh):
 
 
 def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
-                grammar=None, gstate=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0,
-                typical_p=1.0):
+                grammar=None, gstate=None, gbar=None, grem=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0,
+                repetition_penalty=1.0, typical_p=1.0):
     """sampler + embedding row of the sampled token (-> emb_out (B, d) bf16) + counter advance, one launch (V <= 2048).
     scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1.
     stop = (eos_id, pad_id, min_length) with unfinished (B,) int32 and alive (1,) int32 on the device: the stop state of generation
     rides on the same launch (mxl_sample_step_stop).  grammar (a grammar.TokenGrammar) with gstate (B,) int32: barred tokens masked
-    and gstate advanced in the same launch, with or without the eos rule (mxl_sample_step_grammar)."""
+    and gstate advanced in the same launch, with or without the eos rule (mxl_sample_step_grammar).  A grammar with a bar budget
+    (grammar.budget) needs gbar and grem (B,) int32 as well and takes mxl_sample_step_budget; without one the launch is unchanged."""
     B = scores.shape[0]
     args = [_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B, int(do_sample),
             int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
@@ -162,6 +163,11 @@ def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter
     if grammar is not None:
         args += [_p(cls), _p(allow), _p(nxt), grammar.n_classes, _p(gstate)]
         name = 'mxl_sample_step_grammar'
+        if grammar.budget is not None:
+            bud = grammar.budget
+            slots, bars = _budget_state(bud, scores.device, B, gbar, grem, 'sample_step_budget')
+            args += [_p(slots), _p(bars), bud.opens, bud.need_free, bud.need_full, _p(gbar), _p(grem)]
+            name = 'mxl_sample_step_budget'
     check(getattr(lib(), name)(*args, _stream()), name)
 
 
@@ -221,6 +227,59 @@ def grammar_scan(ids, Tp, grammar, gstate, first_bad, start=None):
     check(lib().mxl_grammar_scan(_p(ids), ids.stride(0), int(Tp), B, grammar.vocab_size, _p(cls), _p(allow), _p(nxt),
                                  grammar.n_classes, grammar.start if start is None else int(start), _p(gstate), _p(first_bad),
                                  _stream()), 'mxl_grammar_scan')
+
+
+def _budget_state(budget, device, B, gbar, grem, what):
+    """(slots, bars) device tables of a grammar.BarBudget, with the per-row words gbar / grem checked"""
+    if budget is None:
+        raise MusicXLError(f'{what}: the grammar carries no bar budget (tokenizer.grammar(bar_budget=True))')
+    if gbar is None or grem is None:
+        raise MusicXLError(f'{what}: a grammar with a bar budget needs gbar and grem')
+    _req(gbar, torch.int32, f'{what} gbar'); _req(grem, torch.int32, f'{what} grem')
+    if gbar.numel() != B or grem.numel() != B or not gbar.is_contiguous() or not grem.is_contiguous():
+        raise MusicXLError(f'{what}: gbar and grem must be contiguous ({B},) int32')
+    return budget.to(device)
+
+
+def budget_mask(scores, V, grammar, gbar, grem):
+    """after grammar_mask, before sample: scores[b, v] = -inf in place for every token the bar budget of `grammar` bars in a row at
+    (gbar[b], grem[b]) (mxl_budget_mask)"""
+    _req(scores, torch.float32, 'budget_mask scores')
+    B = scores.shape[0]
+    if scores.shape[1] < V or scores.stride(1) != 1:
+        raise MusicXLError('budget_mask: scores must be (B, >= V) with unit column stride')
+    cls, _, _ = _grammar_tables(grammar, scores.device, V)
+    bud = grammar.budget
+    slots, _ = _budget_state(bud, scores.device, B, gbar, grem, 'budget_mask')
+    check(lib().mxl_budget_mask(_p(scores), scores.stride(0), B, int(V), _p(cls), _p(slots), bud.need_free, bud.need_full, _p(gbar),
+                                _p(grem), _stream()), 'mxl_budget_mask')
+
+
+def budget_advance(ids, t_dev, grammar, gbar, grem, unfinished=None):
+    """beside grammar_advance (after sample + decode_advance, before decode_stop): (gbar[b], grem[b]) move along the token at
+    ids[b, t]; rows with unfinished[b] == 0 keep theirs (mxl_budget_advance)"""
+    B = ids.shape[0]
+    if ids.dtype != torch.int64:
+        raise MusicXLError('budget_advance: ids must be (B, .) int64')
+    cls, _, _ = grammar.to(ids.device)
+    bud = grammar.budget
+    slots, bars = _budget_state(bud, ids.device, B, gbar, grem, 'budget_advance')
+    check(lib().mxl_budget_advance(_p(ids), ids.stride(0), _p(t_dev), B, grammar.vocab_size, _p(cls), _p(slots), _p(bars), bud.opens,
+                                   _p(gbar), _p(grem), _p(unfinished), _stream()), 'mxl_budget_advance')
+
+
+def budget_scan(ids, Tp, grammar, gbar, grem, first_bad):
+    """(gbar[b], grem[b]) = bar length and free slots of row b after columns 0..Tp-1 of ids (ids < 0 skipped), first_bad[b] = column
+    of the first token the bar budget bars or -1 (mxl_budget_scan); the host reference is TokenGrammar.walk_budget"""
+    _req(first_bad, torch.int32, 'budget_scan first_bad')
+    B = ids.shape[0]
+    if ids.dtype != torch.int64 or ids.stride(1) != 1 or Tp > ids.shape[1] or first_bad.numel() != B or not first_bad.is_contiguous():
+        raise MusicXLError('budget_scan: ids must be (B, >= Tp) int64 rows and first_bad contiguous (B,)')
+    cls, _, _ = grammar.to(ids.device)
+    bud = grammar.budget
+    slots, bars = _budget_state(bud, ids.device, B, gbar, grem, 'budget_scan')
+    check(lib().mxl_budget_scan(_p(ids), ids.stride(0), int(Tp), B, grammar.vocab_size, _p(cls), _p(slots), _p(bars), bud.opens,
+                                bud.need_free, bud.need_full, _p(gbar), _p(grem), _p(first_bad), _stream()), 'mxl_budget_scan')
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, relu=False, out=None,

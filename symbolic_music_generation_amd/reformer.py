@@ -172,9 +172,10 @@ class MyReformerModelWithLMHead(EngineModule):
         config's.
 
         grammar (a `grammar.TokenGrammar`): greedy decoding and sampling in which every row may only emit tokens its grammar state
-        allows, as MyTransfoXLLMHeadModel.generate: the mask runs on the device before the sampler, the state advance after it."""
+        allows, as MyTransfoXLLMHeadModel.generate: the mask runs on the device before the sampler, the state advance after it.  A
+        grammar with a bar budget (`tokenizer.grammar(bar_budget=True)`) keeps every generated bar as long as its time signature."""
         from .generate import (STOP_CHUNK, beam_generate, check_grammar_args, left_pad_counts, raise_on_bad_prompt, resolve_max_length,
-                               sample_unfused, sampling_config, stop_config, stop_width)
+                               sample_unfused, sampling_config, scan_prompt, stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
@@ -252,18 +253,18 @@ class MyReformerModelWithLMHead(EngineModule):
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
             unfinished = torch.ones(B, device=self.device, dtype=torch.int32)
             alive = torch.zeros(1, device=self.device, dtype=torch.int32)
-            gstate = None
+            gstate = gbar = grem = None
             if grammar is not None:
-                gstate = torch.empty(B, device=self.device, dtype=torch.int32)
-                gbad = torch.empty(B, device=self.device, dtype=torch.int32)
-                ops.grammar_scan(buf, Tp, grammar, gstate, gbad)
+                gstate, gbar, grem = (torch.zeros(B, device=self.device, dtype=torch.int32) for _ in range(3))
+                gbad = torch.empty(2, B, device=self.device, dtype=torch.int32)
+                scan_prompt(grammar, buf, Tp, gstate, gbad, gbar, grem)
                 raise_on_bad_prompt(grammar, buf, gbad)
             sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
             for cur in range(Tp, max_length):
                 Tf = cur if cur <= 64 else (cur + 63) // 64 * 64
                 out = self.engine.forward(buf[:, :Tf].contiguous(), labels=None, train=False)
                 last = out['logits'][:, cur - 1].contiguous()
-                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, stop, unfinished, alive, grammar, gstate)
+                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, stop, unfinished, alive, grammar, gstate, gbar, grem)
                 if Tf > cur:
                     buf[:, cur + 1:Tf] = pad          # keep the padding clean (the sampler wrote position `cur` only)
                 # a whole forward per token: reading the live-row count every STOP_CHUNK tokens costs nothing in comparison

@@ -26,7 +26,7 @@ import torch
 
 from . import ops
 from ._lib import MusicXLError
-from .generate import check_grammar_args, decode_lanes, raise_on_bad_prompt, sample_unfused, sampling_config
+from .generate import check_grammar_args, decode_lanes, raise_on_bad_prompt, sample_unfused, sampling_config, scan_prompt
 
 
 class RFDecoder:
@@ -74,8 +74,10 @@ class RFDecoder:
         self.steps_run = 0
         # grammar-constrained decoding (generate(grammar=...)): the automaton state of every row (generate.XLDecoder)
         self.gstate = torch.zeros(batch, device=dev, dtype=torch.int32)
-        self.gbad = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self.gbad = torch.zeros(2, batch, device=dev, dtype=torch.int32)
         self._grammar = None
+        self.gbar = torch.zeros(batch, device=dev, dtype=torch.int32)     # bar budget of such a grammar: bar length, free slots
+        self.grem = torch.zeros(batch, device=dev, dtype=torch.int32)
 
     # ---------------------------------------------------------------- hashing helpers
     def _factors(self, T_hint: Optional[int] = None):
@@ -117,7 +119,7 @@ class RFDecoder:
         self.ids.zero_()
         self.ids[:, :Tp].copy_(prompt)
         if grammar is not None:
-            ops.grammar_scan(self.ids, Tp, grammar, self.gstate, self.gbad)
+            scan_prompt(grammar, self.ids, Tp, self.gstate, self.gbad, self.gbar, self.grem)
         for l in self.bk:
             self.n_bucketed[l] = 0
             self.bkmax[l].zero_()
@@ -158,7 +160,7 @@ class RFDecoder:
             return
         # (min_length and the grammar mask write into the logits: after the trace above)
         sample_unfused(logits, self.eng.cfg.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, self._stop,
-                       self.unfinished, self.alive, self._grammar, self.gstate)
+                       self.unfinished, self.alive, self._grammar, self.gstate, self.gbar, self.grem)
 
     # ---------------------------------------------------------------- one token
     def step(self, t: int, sampling: dict):
@@ -269,7 +271,8 @@ class RFDecoder:
         """(B, max_length) ids = prompt + continuation.  stop = (eos, pad, min_length) (generate.stop_config): rows finish at eos
         and the loop ends once none is live -- the live-row count is read back every `stop_chunk` steps, one chunk late
         (generate.run_until_finished) -- and the output is cut to the longest row.  grammar: a grammar.TokenGrammar; every row may
-        only emit tokens its grammar state allows (mask before the sampler, state advance after it, both on the device)."""
+        only emit tokens its grammar state allows (mask before the sampler, state advance after it, both on the device); a bar budget
+        on the grammar is kept the same way."""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         return decode_lanes(self, [self], [None], prompt, max_length,

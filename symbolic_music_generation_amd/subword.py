@@ -137,7 +137,7 @@ class PairMergeTokenizer(MusicTokenizer):
             raise ValueError('the tokenizer file was trained on a different base vocabulary')
         return ret
 
-    def grammar(self):
+    def grammar(self, bar_budget: bool = False):
         raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders (a pitch with its '
                                   'duration, a whole tuplet), so the music grammar over token classes does not apply')
 
@@ -319,7 +319,7 @@ class WordPieceMusicTokenizer(MusicTokenizer):
             raise ValueError('the tokenizer file was trained on a different base vocabulary')
         return ret
 
-    def grammar(self):
+    def grammar(self, bar_budget: bool = False):
         raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders (a pitch with its '
                                   'duration, a whole tuplet), so the music grammar over token classes does not apply')
 

@@ -222,8 +222,9 @@ class MyTransfoXLLMHeadModel(EngineModule):
         a pitch before its duration, closed tuplets).  The state of every row is kept on the device and moves inside the sampler
         launch; barred tokens are masked after the repetition penalty and `min_length` and before the warpers, as an HF logits
         processor would.  It combines with `num_return_sequences`, padded prompts, `eos_token_id` / `min_length` /
-        `max_new_tokens`; the prompts must obey the grammar themselves (MusicXLError otherwise).  The constraint is syntactic: it
-        does not make the durations of a bar add up.  Beam, group-beam and contrastive search take no grammar."""
+        `max_new_tokens`; the prompts must obey the grammar themselves (MusicXLError otherwise).  That constraint is syntactic;
+        `tokenizer.grammar(bar_budget=True)` adds the bar budget, under which every channel of every generated bar is also exactly
+        as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Beam, group-beam and contrastive search take no grammar."""
         from .generate import (XLDecoder, XLDecoderLanes, beam_generate, check_grammar_args, contrastive_search, left_pad_counts,
                                resolve_max_length, stop_config)
         n_pad = None

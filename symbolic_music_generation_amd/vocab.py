@@ -172,10 +172,11 @@ class MusicVocabulary:
     def i2t(self, id_: int) -> str:
         return self.id2tok[int(id_)]
 
-    def grammar(self):
-        """the token grammar of a well-formed song over this vocabulary (grammar.music_grammar), for `generate(grammar=...)`"""
+    def grammar(self, bar_budget: bool = False):
+        """the token grammar of a well-formed song over this vocabulary (grammar.music_grammar), for `generate(grammar=...)`;
+        bar_budget=True: with the duration budget attached, so that every generated bar is as long as its time signature"""
         from .grammar import music_grammar
-        return music_grammar(self)
+        return music_grammar(self, bar_budget=bar_budget)
 
 
 class MusicTokenizer:
@@ -203,9 +204,9 @@ class MusicTokenizer:
     def __len__(self):
         return len(self.vocab)
 
-    def grammar(self):
+    def grammar(self, bar_budget: bool = False):
         """the token grammar of a well-formed song (`MusicVocabulary.grammar`), for `model.generate(grammar=...)`"""
-        return self.vocab.grammar()
+        return self.vocab.grammar(bar_budget=bar_budget)
 
     def tokenize(self, text: str) -> List[str]:
         return text.split()
