@@ -1,0 +1,301 @@
+"""ORACLE-side statement of the banded relative-position attention, forward AND backward, in float64 (test infrastructure, NOT
+product code), the operand-rounded model of the kernels' arithmetic, and the cases a CPU test and a GPU test share.
+
+`relattn_ref64(c)` is the closed form at the head of csrc/relattn_bwd_fused.hip in float64:
+
+    x[i,p] = ((q_i + r_w_bias) . k_p + (q_i + r_r_bias) . Rd[i - p]) * scale,   visible iff 0 <= i - p <= M - 1
+    P = softmax_p(x),  out = P v,  lse = logsumexp_p(x),  delta_i = dO_i . out_i,  dP[i,p] = dO_i . v_p
+    dS = scale * P * (dP - delta)            dG[i,d] = dS[i, i - d]
+    dv_p = sum_i P[i,p] dO_i                 dk_p = sum_i dS[i,p] (q_i + r_w_bias)
+    dq_i = sum_p dS[i,p] k_p + sum_d dG[i,d] Rd[d]                      d_rd[d] = sum_{b,i} dG[i,d] (q_i + r_r_bias)
+    d_rwb = sum_{b,i} sum_p dS[i,p] k_p      d_rrb = sum_{b,i} sum_d dG[i,d] Rd[d]
+
+tests/test_relattn_cases_cpu.py pins it on double-precision autograd through oracle/relattn_ref.py (itself pinned on HF XLNet).
+
+`relattn_ref64(c, rounded=True, arm=...)` is the same evaluation with every rounding the kernel sources apply to an MFMA operand
+or to a stored intermediate, and nothing else (sums stay in float64).  It is NOT the expected value: `gap(model, ref)` measures
+what those roundings cost on a case, and 4 x the largest gap is the absolute term `b` of the tolerance rule of
+oracle/kernel_cases.py.  The roundings, with their sources (csrc/ = symbolic_music_generation_amd/csrc/):
+
+  every arm
+    (q + r_w_bias) * scale*log2e and (q + r_r_bias) * scale*log2e -> bf16, the sum and the product in float32
+        relattn_fwd.hip:219-220, relattn_bwd.hip:222-223 / 682-683 / 1313-1314, relattn_bwd_fused.hip:400, relattn_drd_phantom.hip:91-92
+    G = Qr Rd^T -> fp16 in the skew buffers, for the cells of key positions >= pz (the first stored 64-key tile)
+        relattn_fwd.hip:584 / 615-616, relattn_bwd.hip:443 / 963 / 1414, relattn_bwd_fused.hip:433 / 845 / 861
+        (the cells of lower key positions -- the phantom cells of zero memories -- take G straight from the float32 accumulators:
+        relattn_fwd.hip:416, relattn_bwd.hip:328, relattn_drd_phantom.hip:225)
+    forward P~ = 2^(x - m) -> bf16 as the operand of out (its float32 values enter the denominator)     relattn_fwd.hip:701-702
+    out -> bf16 (stored), read back for delta; lse, delta stored in float32      relattn_fwd.hip:744-751, relattn_bwd.hip:87, relattn_bwd_fused.hip:246
+    dO * scale -> bf16 (exact when scale is a power of two), operand of dP and dv     relattn_bwd.hip:224 / 684 / 1315, relattn_bwd_fused.hip:410
+    P -> bf16, operand of dv                                                     relattn_bwd.hip:1441-1442, relattn_bwd_fused.hip:703
+    dS = P * (scale dP - scale delta) -> bf16, operand of dq, dk, d_rd and the stored dG
+        relattn_bwd.hip:349 / 359-379 / 498 / 830 / 1040 / 1443-1444, relattn_bwd_fused.hip:703
+    dk is accumulated against the bf16 (q + r_w_bias) * scale*log2e and divided by scale*log2e at the end
+        relattn_bwd.hip:1455-1462 / 1477, relattn_bwd_fused.hip:893
+  arm 'three' (mxl_relattn_bwd + mxl_relattn_drd or the batched GEMM)
+    q + r_r_bias -> bf16 (mxl_add_rowbias_bf16, ops.relattn_drd), the operand of d_rd beside the bf16 dG
+  arm 'sparse' (mxl_relattn_bwd_sparse_dg + mxl_relattn_drd_recompute): as 'three', and in the (32 queries x 256 distances) blocks that
+    lie on phantom distances only, d_rd / d_rrb use dG rebuilt from bf16(q + r_r_bias) . bf16(Rd * scale*log2e)      relattn_bwd.hip:1619 / 1690
+  arm 'sparse_oph' (mxl_relattn_fwd_phantom + mxl_relattn_bwd_sparse_dg_oph): as 'sparse', and the dq part of those blocks is
+    -scale delta 2^(mph - lse2) oph with oph = sum bf16(2^(G - mph)) Rd -> bf16        relattn_fwd.hip:467-468 / 517, relattn_bwd.hip:1126-1129
+  arm 'fused' (mxl_relattn_bwd_fused + mxl_relattn_dq_finish + mxl_relattn_drd_phantom)
+    partial dq of each 256-key block -> bf16 slab, the slabs summed in float32             relattn_bwd_fused.hip:818 / 981
+    dq part of ALL phantom cells from the bf16 oph (oph_all = 1)                          relattn_bwd_fused.hip:1003-1008
+    d_rd of the stored cells against the bf16 (q + r_r_bias) * scale*log2e, divided back   relattn_bwd_fused.hip:507
+    d_rd of the phantom cells: bf16(P delta) against the same rows, times -1 / log2e        relattn_drd_phantom.hip:234-246 / 329
+The lazy softmax reference m of the forward is modelled by the row maximum (bf16 rounding is relative: the choice moves nothing).
+"""
+import functools
+import math
+
+import numpy as np
+import torch
+
+from oracle.kernel_cases import bf16_exact
+
+LN2 = math.log(2.0)
+LOG2E_F32 = float(np.float32(1.4426950408889634))
+ARMS = ('three', 'sparse', 'sparse_oph', 'fused')
+OUTPUTS = ('out', 'lse', 'dq', 'dk', 'dv', 'd_rd', 'd_rwb', 'd_rrb')
+
+
+def _bf(x):
+    return x.float().to(torch.bfloat16).double()
+
+
+def _f16(x):
+    return x.float().to(torch.float16).double()
+
+
+def _f32(x):
+    return x.float().double()
+
+
+def _id(x):
+    return x
+
+
+def floordiv64(p0):
+    return (p0 // 64) * 64
+
+
+def phantom_sets(T, M, Kc):
+    """-> (all, blk): bool (T, M) over (query, distance).  all: key position i - d below pz, the first stored 64-key tile (what
+    mxl_relattn_fwd_phantom2 sums with oph_all = 1); blk: the (32-query, 256-distance) blocks lying on such cells only (what
+    mxl_relattn_fwd_phantom sums and mxl_relattn_bwd_sparse_dg leaves unwritten)"""
+    pz = floordiv64(T - Kc)
+    i = torch.arange(T)[:, None]
+    d = torch.arange(M)[None, :]
+    return (i - d) < pz, (d & ~255) > ((i | 31) - pz)
+
+
+def relattn_ref64(c, rounded=False, arm='three', valid_edit=None, dg_edit=None, drd_edit=None):
+    """c: a case (dict from `build_case`).  -> dict of float64 tensors: out (B,T,H,dh), lse (B,H,T), dq (B,T,H,dh), dk, dv (B,Kc,H,dh),
+    d_rd (M,H,dh), d_rwb, d_rrb (H,dh); P, dS (B,H,T,M+T) over key positions -M .. T-1, dG (B,H,T,M); delta; and oph_all / oph_blk
+    (B,T,H,dh): sum over the phantom cells of a set of P[i,d] Rd[d] -- the reference-free form of the forward's value-sum.
+    `*_edit`: hooks of the CPU "teeth" test (a visibility mask, dG or d_rd altered the way a kernel fault would)."""
+    assert arm in ARMS
+    rb, rh, rf = (_bf, _f16, _f32) if rounded else (_id, _id, _id)
+    q, k, v, rd, rwb, rrb, dout = (c[n].double() for n in ('q', 'k', 'v', 'rd', 'rwb', 'rrb', 'dout'))
+    B, T, H, dh = q.shape
+    Kc, M, scale = k.shape[1], rd.shape[0], c['scale']
+    J = M + T
+    p0 = T - Kc
+    pz = floordiv64(p0)
+    if rounded:      # the float32 arithmetic of the operand staging
+        sc = float(np.float32(scale))
+        sl = float(np.float32(sc) * np.float32(LOG2E_F32))
+        aw = ((c['q'].float() + c['rwb'].float()) * sl).to(torch.bfloat16).double()
+        ar = ((c['q'].float() + c['rrb'].float()) * sl).to(torch.bfloat16).double()
+        dos = (c['dout'].float() * sc).to(torch.bfloat16).double()
+        qrb = (c['q'].float() + c['rrb'].float()).to(torch.bfloat16).double()
+    else:
+        sc, sl = scale, scale / LN2
+        aw, ar, dos, qrb = (q + rwb) * sl, (q + rrb) * sl, dout * sc, q + rrb
+    kf = torch.zeros(B, J, H, dh, dtype=torch.float64)
+    vf = torch.zeros(B, J, H, dh, dtype=torch.float64)
+    kf[:, J - Kc:] = k
+    vf[:, J - Kc:] = v
+    i = torch.arange(T)[:, None]
+    dist = i + M - torch.arange(J)[None, :]                         # (T, J): distance of column j (key position j - M)
+    valid = (dist >= 0) & (dist <= M - 1)
+    if valid_edit is not None:
+        valid = valid_edit(valid, dist)
+    gidx = dist.clamp(0, M - 1)[None, None].expand(B, H, T, J)
+    jidx = (i + M - torch.arange(M)[None, :])[None, None].expand(B, H, T, M)     # column of (query, distance): always inside [1, J)
+    ph_col = (torch.arange(J) - M < pz)[None, None, None, :]
+
+    S2 = torch.einsum('bihe,bjhe->bhij', aw, kf)
+    G2 = torch.einsum('bihe,dhe->bhid', ar, rd)
+    x = S2 + torch.where(ph_col, torch.gather(G2, 3, gidx), torch.gather(rh(G2), 3, gidx))       # log2 units
+    x = x.masked_fill(~valid[None, None], float('-inf'))
+    m = x.max(-1, keepdim=True).values
+    Pt = torch.exp2(x - m)
+    l = Pt.sum(-1)
+    out = torch.einsum('bhij,bjhe->bihe', rb(Pt), vf) / l.transpose(1, 2)[..., None]
+    lse = rf((m[..., 0] + torch.log2(l)) * LN2)
+
+    lse2 = (lse / LN2)[..., None]
+    P = torch.exp2(x - lse2)
+    delta = rf(torch.einsum('bihe,bihe->bhi', dout, rb(out)))
+    nd = -sc * delta[..., None]
+    dS = P * (torch.einsum('bihe,bjhe->bhij', dos, vf) + nd)                                    # masked cells: P = 0
+    dSb, Pb = rb(dS), rb(P)
+    dv = torch.einsum('bhij,bihe->bjhe', Pb, dos)[:, J - Kc:] / sc
+    dk = torch.einsum('bhij,bihe->bjhe', dSb, aw)[:, J - Kc:] / sl
+    dG = torch.gather(dSb, 3, jidx)
+    if dg_edit is not None:
+        dG = dg_edit(dG)
+    dQw = torch.einsum('bhij,bjhe->bihe', dSb, kf)
+    dQr = torch.einsum('bhid,dhe->bihe', dG, rd)
+    d_rwb, d_rrb = dQw.sum((0, 1)), dQr.sum((0, 1))
+    dq = dQw + dQr
+    d_rd = torch.einsum('bhid,bihe->dhe', dG, qrb)
+
+    # the forward's phantom value-sums (reference-free form) and, in the model, their bf16 images
+    s_all, s_blk = phantom_sets(T, M, Kc)
+    Pd = torch.gather(P, 3, jidx)
+    oph = {}
+    ophb = {}
+    for nm, st in (('all', s_all), ('blk', s_blk)):
+        oph[nm] = torch.einsum('bhid,dhe->bihe', Pd * st, rd)
+        if rounded:
+            gm = G2.masked_fill(~st, float('-inf'))
+            mph = gm.max(-1, keepdim=True).values
+            mph = torch.where(torch.isinf(mph), torch.zeros_like(mph), mph)
+            sm = torch.einsum('bhid,dhe->bihe', rb(torch.exp2(gm - mph)), rd)
+            f = torch.exp2(mph - lse2)[..., 0].transpose(1, 2)[..., None]
+            oph[nm] = f * sm
+            ophb[nm] = f * rb(sm)
+
+    if rounded and arm in ('sparse', 'sparse_oph'):
+        # d_rd / d_rrb of the all-phantom blocks from the recomputed dG; with oph also their part of dq
+        G2r = torch.einsum('bihe,dhe->bhid', qrb, _bf(c['rd'].float() * sl))
+        dGr = rb(torch.exp2(G2r - lse2) * nd)
+        dGd = torch.where(s_blk, dGr, dG)
+        d_rd = torch.einsum('bhid,bihe->dhe', dGd, qrb)
+        if arm == 'sparse_oph':
+            dQr = torch.einsum('bhid,dhe->bihe', dG * ~s_blk, rd) + nd[..., 0].transpose(1, 2)[..., None] * ophb['blk']
+            dq = dQw + dQr
+        tot = dq.sum((0, 1))
+        d_rrb = torch.einsum('bhid,dhe->he', dGd, rd)
+        d_rwb = tot - d_rrb                              # the 8-wave kernel leaves the sum, the contraction takes d_rrb out
+    if rounded and arm == 'fused':
+        assert p0 == pz
+        st = ~s_all                                      # the stored keys' cells
+        nkb = (Kc + 255) // 256
+        dq = torch.zeros_like(dq)
+        for kb in range(nkb):
+            col = torch.zeros(J, dtype=torch.bool)
+            col[J - Kc + 256 * kb: J - Kc + 256 * (kb + 1)] = True
+            part = torch.einsum('bhij,bjhe->bihe', dSb * col, kf) + torch.einsum('bhid,dhe->bihe', dG * (st & col[jidx[0, 0]]), rd)
+            dq = dq + rb(part)
+        phq = nd[..., 0].transpose(1, 2)[..., None] * ophb['all']
+        dq = dq + phq
+        dQr_st = torch.einsum('bhid,dhe->bihe', dG * st, rd)
+        d_rrb = dQr_st.sum((0, 1)) + phq.sum((0, 1))
+        dGp = rb(Pd * delta[..., None]) * s_all
+        d_rd = torch.einsum('bhid,bihe->dhe', dG * st, ar) / sl + torch.einsum('bhid,bihe->dhe', dGp, ar) * (-sc / sl)
+    if drd_edit is not None:
+        d_rd = drd_edit(d_rd)
+    return dict(out=out, lse=lse, dq=dq, dk=dk, dv=dv, d_rd=d_rd, d_rwb=d_rwb, d_rrb=d_rrb, P=P, dS=dS, dG=dG, delta=delta,
+                oph_all=oph['all'], oph_blk=oph['blk'])
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# Cases.  Shapes (B, T, H, dh, M, Kc, scale): the smallest at which the tiling can go wrong -- T of one, two, three and ten
+# 32-query tiles (and ragged / T = 1 for the forward), M of one distance block, fewer than a window's nine, one 256-key block and
+# two dq slabs, Kc = T (zero memories), T + 64 (partial) and M + T (full carried memory), B = 3.
+# ----------------------------------------------------------------------------------------------------------------------------
+SHAPES = {
+    't32_m32_zero': (3, 32, 2, 64, 32, 32, None),
+    't64_m96_part': (2, 64, 2, 64, 96, 64 + 64, None),
+    't96_m256_zero': (2, 96, 2, 64, 256, 96, None),
+    't96_m256_full': (2, 96, 2, 64, 256, 96 + 256, None),
+    't320_m288_zero': (2, 320, 2, 64, 288, 320, None),
+    't320_m256_part': (3, 320, 2, 64, 256, 320 + 64, None),
+    't320_m288_part128': (3, 320, 2, 64, 288, 320 + 128, None),      # B = 3; distance blocks of unequal phantom work
+    't70_dh16_zero': (2, 70, 8, 16, 96, 70, None),                 # ragged T, T < M on zero memories
+    't100_dh32_part_scale': (2, 100, 2, 32, 96, 100 + 40, 0.2),    # ragged T, first stored key off the 64-key tiles, own scale
+    't1_full': (2, 1, 2, 64, 32, 33, None),                        # T = 1 (forward only: the backward kernels need no such shape)
+    't96_dh32_m256_zero': (2, 96, 2, 32, 256, 96, None),           # the phantom value-sum at dh = 32
+}
+FAMILIES = ('random', 'far-edge', 'diagonal', 'position-coded')
+STRUCTURED_SHAPES = ('t96_m256_zero', 't320_m256_part', 't100_dh32_part_scale')
+CASES = [(s, f) for s in SHAPES for f in ('random', 'far-edge')] + [(s, f) for s in STRUCTURED_SHAPES for f in ('diagonal', 'position-coded')]
+DOUT_ROWS = (31, 32, 63, 64)          # position-coded: the seams of the 32-query and 64-key tiles (and the last row)
+
+
+def favoured_distance(family, M):
+    return {'diagonal': 0, 'far-edge': M - 1}.get(family)
+
+
+def build_case(shape, family):
+    """bf16-exact inputs of one case: q (B,T,H,dh), k, v (B,Kc,H,dh) for key positions T-Kc .. T-1, rd (M,H,dh), rwb, rrb (H,dh), dout"""
+    import zlib
+    B, T, H, dh, M, Kc, scale = SHAPES[shape]
+    g = torch.Generator().manual_seed(zlib.crc32(f'{shape}/{family}'.encode()))
+    rn = lambda *s: torch.randn(*s, generator=g)
+    q, k, v, rd = rn(B, T, H, dh) * 0.8, rn(B, Kc, H, dh) * 0.8, rn(B, Kc, H, dh) * 0.8, rn(M, H, dh) * 0.8
+    rwb, rrb, dout = rn(H, dh) * 0.5, rn(H, dh) * 0.5, rn(B, T, H, dh)
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    fav = favoured_distance(family, M)
+    if fav is not None:
+        # Rd[fav] = a u_h, q = 0.24 randn + u_h with u_h a sign vector, k halved: the favoured cell's score leads by L = a (u_h + r_r_bias) . u_h scale nats.
+        # The other M - 1 cells have scores of variance about (0.06 + 1 + 0.25) * (0.16 + 0.64) = 1.05: their exponentials sum to about
+        # 1.7 M, so L = ln(1.7 M) + 0.8 puts about 0.7 of a typical row's mass on the favoured cell, and the row-to-row scatter of the
+        # lead (about 0.6 nats) leaves 90 % of the rows above one half -- without driving P to 1, where dS = P (dP - delta) is all
+        # cancellation and a gradient test measures the rounding of `out` inside delta and nothing else.
+        u = torch.where(torch.rand(H, dh, generator=g) < 0.5, -1.0, 1.0)
+        q, k = 0.3 * q + u, 0.5 * k
+        rd[fav] = u * ((math.log(1.7 * M) + 0.8) / (scale * ((u + rrb) * u).sum(-1, keepdim=True)))      # (the head's bias counted in)
+    if family == 'position-coded':
+        pos = torch.arange(T - Kc, T, dtype=torch.float32) + M
+        v[..., 0] = (pos / (M + T)).view(1, Kc, 1)
+        keep = torch.zeros(T, dtype=torch.bool)
+        keep[[r for r in DOUT_ROWS if r < T] + [T - 1]] = True
+        dout = dout * keep.view(1, T, 1, 1)
+    c = dict(shape=shape, family=family, B=B, T=T, H=H, dh=dh, M=M, Kc=Kc, scale=scale)
+    c.update({n: bf16_exact(t) for n, t in dict(q=q, k=k, v=v, rd=rd, rwb=rwb, rrb=rrb, dout=dout).items()})
+    return c
+
+
+@functools.lru_cache(maxsize=None)
+def case_ref(shape, family):
+    """-> (case, float64 reference): built once per process and shared; callers must leave both unchanged"""
+    c = build_case(shape, family)
+    r = relattn_ref64(c)
+    fav = favoured_distance(family, c['M'])
+    if fav is not None:
+        assert favoured_share(c, r['P'], fav) >= 0.9, (shape, family)
+    return c, r
+
+
+def favoured_share(c, P, fav):
+    """fraction of the rows whose favoured cell (distance `fav`) holds at least half of the probability"""
+    T, M = c['T'], c['M']
+    col = torch.arange(T) + M - fav
+    return (P[:, :, torch.arange(T), col] >= 0.5).double().mean().item()
+
+
+def dims(shape):
+    B, T, H, dh, M, Kc, _ = SHAPES[shape]
+    return dict(B=B, T=T, H=H, dh=dh, M=M, Kc=Kc)
+
+
+def arms_of(c):
+    """the backward arms a case's shape (a case or `dims(shape)`) can take: 'three' always; the others as ops.relattn_bwd /
+    ops.fused_bwd_applies choose"""
+    B, T, H, dh, M, Kc = (c[n] for n in ('B', 'T', 'H', 'dh', 'M', 'Kc'))
+    arms = ['three']
+    if dh == 64 and T % 32 == 0 and M % 256 == 0 and Kc < M + T:
+        arms += ['sparse', 'sparse_oph']
+    if dh == 64 and T % 32 == 0 and M % 32 == 0 and Kc % 32 == 0 and (T - Kc) % 64 == 0:
+        arms.append('fused')
+    return arms
+
+
+@functools.lru_cache(maxsize=None)
+def case_model(shape, family, arm):
+    c, _ = case_ref(shape, family)
+    return relattn_ref64(c, rounded=True, arm=arm)
