@@ -120,6 +120,48 @@ def pair_keep_mask(seed, site, M, N, p):
     return half >= _U32(dropout_thresh(p) >> 16)
 
 
+def chunk_drop_mask(seed, site, slots, p, n_keys=128, swap_parity=False):
+    """the ChunkDrop rule of the chunked Reformer attention kernels (csrc/reformer.hip:377-403): keep decisions (len(slots), n_keys)
+    of the cells (query slot s = (b * H + h) * S + qslot, key index kw in that slot's window).  One hash per 2 x 2 block of cells:
+    the block row's key is the spread of blk = (s >> 1) * 64 PLUS the seed / site mix; block column kw >> 1 adds its multiple of
+    0x9E3779B1 and gives two words (the hash, and a multiply-xorshift of it); the key's parity picks the word, the slot's parity the
+    16-bit half (odd: the high one), kept iff >= (p * 2^32) >> 16.  `swap_parity`: the halves taken the other way round (a fault the
+    CPU test plants)"""
+    slots = np.asarray(slots).astype(np.uint64).reshape(-1)
+    blk = (slots >> np.uint64(1)) * np.uint64(64)
+    lo = (blk & np.uint64(0xFFFFFFFF)).astype(_U32)
+    hi = (blk >> np.uint64(32)).astype(_U32)
+    kw = np.arange(n_keys, dtype=_U32)
+    with np.errstate(over='ignore'):
+        key = ((lo * _U32(0x9E3779B1)) ^ (hi * _U32(0x85EBCA77))) + _U32(_mix(seed, site))
+        w0 = mxl_hash32(key[:, None] + (kw >> _U32(1))[None, :] * _U32(0x9E3779B1))
+        w1 = (w0 * _U32(0x85EBCA77)) ^ (w0 >> _U32(13))
+    w = np.where((kw & _U32(1))[None, :] == 1, w1, w0)
+    odd = ((slots & np.uint64(1)) == 1)[:, None] ^ bool(swap_parity)
+    half = np.where(odd, w >> _U32(16), w & _U32(0xFFFF))
+    return half >= _U32(dropout_thresh(p) >> 16)
+
+
+def single_drop_mask(seed, site, B, H, T, p):
+    """the single-chunk attention kernels' cells (csrc/reformer.hip:1212-1215): flat index ((b * H + h) * T + i) * 64 + j -> (B, H, T, T)"""
+    bh = np.arange(B * H, dtype=np.uint64).reshape(B, H, 1, 1)
+    i = np.arange(T, dtype=np.uint64).reshape(1, 1, T, 1)
+    j = np.arange(T, dtype=np.uint64).reshape(1, 1, 1, T)
+    return keep_mask(seed, site, ((bh * np.uint64(T) + i) * np.uint64(64) + j), p)
+
+
+def axial_pos_mask(seed, site, B, T, A1, p):
+    """the axial embedding's 2-D position dropout (csrc/reformer.hip:31): one decision per (sequence, t % A1) -> (B, T)"""
+    b = np.arange(B, dtype=np.uint64)[:, None]
+    t = np.arange(T, dtype=np.uint64)[None, :]
+    return keep_mask(seed, site, b * np.uint64(A1) + t % np.uint64(A1), p)
+
+
+def axial_emb_mask(seed, site, B, T, d, p):
+    """the axial embedding's word-vector dropout (csrc/reformer.hip:30): one decision per flat element -> (B, T, d)"""
+    return keep_mask(seed, site, np.arange(B * T * d, dtype=np.uint64), p).reshape(B, T, d)
+
+
 # ----------------------------------------------------------------------------------------------------------------------------
 # GEMM references.  Flags as in include/musicxl.h.
 # ----------------------------------------------------------------------------------------------------------------------------
