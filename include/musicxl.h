@@ -505,6 +505,28 @@ int mxl_budget_advance(const void* ids, int ld_ids, const int* t_dev, int B, int
  * reports those) skipped.  first_bad[b] = column of the first token the budget bars, where the walk of that row stops; -1 = none. */
 int mxl_budget_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* slots, const void* bars,
                     unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, int* first_bad, void* stream);
+/* Bar count on top of the grammar: a row opens exactly as many further bars as it was asked for.  Per row one more int32 word kept on
+ * the device: gleft, the bars the row may still open; < 0 = no limit, the row is untouched.  count and end are class bit masks over the
+ * classes of `cls` (the music grammar: <bar> and </s>).  A class in count is barred at gleft == 0, a class in end while gleft > 0, and a
+ * kept token of a count class takes 1 from a positive gleft.  Under a bar budget the end class is thereby the only one left when the
+ * last bar is full; without one the rule cannot force the end, it only bars a further bar and an early end.
+ * mxl_sample_step_bars: mxl_sample_step_grammar (slots = bars = gbar = grem = NULL) or mxl_sample_step_budget with that mask folded
+ * into the same allow word, and gleft[b] moved where gstate[b] moves (after the eos rule; a row finished before the step keeps it).
+ * Row b's workgroup is the only one that touches gleft[b]. */
+int mxl_sample_step_bars(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                         unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                         float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                         int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
+                         const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
+                         unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
+                         int* gleft, void* stream);
+/* The same around mxl_sample / mxl_sample_large: mxl_barcount_mask after mxl_grammar_mask and mxl_budget_mask (in place, one thread
+ * per score), mxl_barcount_advance beside mxl_grammar_advance and mxl_budget_advance, before mxl_decode_stop of the same step
+ * (unfinished: optional, rows with unfinished[b] == 0 keep their word). */
+int mxl_barcount_mask(float* scores, int ldl, int B, int V, const void* cls, unsigned count, unsigned end, const int* gleft,
+                      void* stream);
+int mxl_barcount_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, unsigned count, int* gleft,
+                         const int* unfinished, void* stream);
 /* Contrastive search (the reference's 'contrastive' strategy, musicnlp/trainer/eval.py:296-302, over the mems patch of
  * musicnlp/models/transformer_xl.py:229-234; HF 4.25.1 GenerationMixin.contrastive_search with `_ranking_fast`):
  *   score[b*K + k] = (1 - alpha) * probs[b*K + k] - alpha * max_{s < S} cos(hid[b*K + k], ctx[b][s]);  sel[b] = argmax_k score

@@ -6,6 +6,15 @@ the same process on the same device; the spread is each variant's max - min over
     python3 scripts/perf_decode_grammar.py                     # env: ROUNDS (6), STEPS (400)
     python3 scripts/perf_decode_grammar.py --only grammar      # one variant, 50 steps: for rocprofv3 --kernel-trace --stats
     python3 scripts/perf_decode_grammar.py --only plain
+
+`--n-bars K`: what `generate(n_bars=)` costs on top of the bar budget, at the same shape.  Three arms alternate, all under
+`tokenizer.grammar(bar_budget=True)` over prompts whose bars are full: `budget` (no eos rule: the arm of
+scripts/perf_decode_budget.py), `budget+eos` (the eos rule that n_bars needs, no count; min_length = max_length keeps eos barred, as
+the count does in the third arm, so that all 64 rows stay live) and `bars` (the eos rule and n_bars = K for every row; give a K no
+row reaches inside the window, e.g. 1000).  `bars - budget+eos` is the cost of the count, `budget+eos - budget` that of the eos rule.
+
+    python3 scripts/perf_decode_grammar.py --n-bars 1000
+    python3 scripts/perf_decode_grammar.py --n-bars 1000 --only bars      # or budget, budget+eos: for rocprofv3 --kernel-trace --stats
 """
 import os
 import statistics
@@ -21,6 +30,7 @@ dev = torch.device('cuda:0')
 V, M, B, Tp, L = 1190, 2048, 64, 256, 2048
 ROUNDS, STEPS = int(os.environ.get('ROUNDS', 6)), int(os.environ.get('STEPS', 400))
 ONLY = sys.argv[sys.argv.index('--only') + 1] if '--only' in sys.argv else None
+N_BARS = int(sys.argv[sys.argv.index('--n-bars') + 1]) if '--n-bars' in sys.argv else None
 
 vocab = MusicVocabulary(pitch_kind='degree')
 assert len(vocab) == V
@@ -41,9 +51,9 @@ def prompts():
         row = [t('TimeSig_4/4'), t('Tempo_120'), t('Key_CMajor')]
         while len(row) < Tp:
             row += [t('<bar>'), t('<melody>')]
-            for _ in range(4):
-                row += [pick(pitch), pick(dur)]
-            row += [t('<bass>'), pick(pitch), pick(dur)]
+            for _ in range(4):                                     # (--n-bars: full bars, four quarter notes over one whole note)
+                row += [pick(pitch), pick(dur) if N_BARS is None else t('d_1')]
+            row += [t('<bass>'), pick(pitch), pick(dur) if N_BARS is None else t('d_4')]
         rows.append(row[:Tp])
     return torch.tensor(rows, dtype=torch.int64, device=dev)
 
@@ -52,9 +62,9 @@ ids = prompts()
 samp = dict(do_sample=True, top_k=8, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0)
 
 
-def window(dec, g, steps):
+def window(dec, g, steps, stop=None, n_bars=None):
     """ms per replayed step over `steps` steps right after the prompt pass (ring slots Tp .. Tp + 20 + steps)"""
-    n = dec.begin(ids, L, samp, use_graph=True, grammar=g)
+    n = dec.begin(ids, L, samp, use_graph=True, grammar=g, stop=stop, n_bars=n_bars)
     assert n >= steps + 20
     for _ in range(20):
         dec.replay_once()
@@ -68,8 +78,46 @@ def window(dec, g, steps):
     return 1e3 * (time.perf_counter() - t0) / steps
 
 
+def bars_arms():
+    """the --n-bars comparison (module docstring)"""
+    from symbolic_music_generation_amd.generate import bar_count_config, bars_after_prompt, check_bar_lengths, stop_config
+    g = vocab.grammar(bar_budget=True)
+    stop = stop_config(vocab.t2i('</s>'), vocab.t2i('[PAD]'))
+    arms = {'budget': {}, 'budget+eos': dict(stop=stop[:2] + (L,)), 'bars': dict(stop=stop, n_bars=bar_count_config(N_BARS, B, g, stop))}
+    assert check_bar_lengths(ids, g).tolist() == [-1] * B
+    if ONLY:
+        dec = XLDecoderLanes(model.engine, B, L, seed=5, lanes=2)
+        print(f'{ONLY}: {window(dec, g, 50, **arms[ONLY]):.3f} ms per step (50 steps)', flush=True)
+        return
+    decs = {k: XLDecoderLanes(model.engine, B, L, seed=5, lanes=2) for k in arms}
+    for name, dec in decs.items():                                  # warm-up: library attributes, workspaces, graph capture
+        window(dec, g, 20, **arms[name])
+    ms = {k: [] for k in arms}
+    names = list(arms)
+    for r in range(ROUNDS):
+        for name in names[r % 3:] + names[:r % 3]:
+            ms[name].append(window(decs[name], g, STEPS, **arms[name]))
+        print(f'round {r}: ' + ', '.join(f'{k} {ms[k][-1]:.4f}' for k in names) + ' ms/step', flush=True)
+    for k in names:
+        out = torch.cat([d.ids[:, :Tp + 20 + STEPS] for d in decs[k].lanes], 0)
+        live = sum(int(d.alive) for d in decs[k].lanes) if k != 'budget' else B
+        print(f'{k:10s}: rows whose bars are all full {int((check_bar_lengths(out, g) < 0).sum())} of {B}, live rows {live}, '
+              f'bars opened per row {bars_after_prompt(out, g, prompt_len=Tp).float().mean():.1f}')
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = {k: max(v) - min(v) for k, v in ms.items()}
+    print(f'C5 decode step, {B} rows, 2 lanes, {STEPS} replayed steps x {ROUNDS} alternating rounds, n_bars = {N_BARS}')
+    for k in names:
+        print(f'  {k:10s} median {med[k]:.4f} ms/step  min {min(ms[k]):.4f}  max {max(ms[k]):.4f}  spread {spread[k]:.4f}')
+    for a, b in (('bars', 'budget+eos'), ('budget+eos', 'budget'), ('bars', 'budget')):
+        d = med[a] - med[b]
+        print(f'  {a} - {b} = {d:+.4f} ms/step ({100 * d / med[b]:+.2f} %); run-to-run spread {max(spread.values()):.4f} ms')
+
+
 with torch.no_grad():
     assert check_grammar(ids, grammar).tolist() == [-1] * B
+    if N_BARS is not None:
+        bars_arms()
+        sys.exit(0)
     if ONLY:
         dec = XLDecoderLanes(model.engine, B, L, seed=5, lanes=2)
         print(f'{ONLY}: {window(dec, grammar if ONLY == "grammar" else None, 50):.3f} ms per step (50 steps)', flush=True)

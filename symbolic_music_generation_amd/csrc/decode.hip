@@ -601,6 +601,32 @@ __device__ __forceinline__ void budget_move(int& bar, int& rem, int c, int k, in
     if (bar > 0 && k != BUDGET_NONE) rem = max(rem - k, 0);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Bar count on top of the grammar (grammar.BarCount): per row `left`, the bars the row may still open (< 0 = no limit, the row is
+// untouched).  count / end: class bit masks.  A class in `count` (<bar>) is barred at left == 0, a class in `end` (</s>) while
+// left > 0, and a kept token of a `count` class takes 1 from a positive left.  Like the budget the rule reads the token's class and
+// the row's integer only.
+// ---------------------------------------------------------------------------------------------------------------
+struct CountArgs {
+    uint32_t count, end;
+    int* gleft;
+};
+
+// classes a row with `left` bars to go bars: the end while bars are owed, another bar once none is
+__device__ __forceinline__ uint32_t barcount_deny(int left, uint32_t count, uint32_t end) {
+    return left > 0 ? end : (left == 0 ? count : 0u);
+}
+// left after a token of class c (BarCount.move)
+__device__ __forceinline__ int barcount_move(int left, int c, uint32_t count) {
+    return (left > 0 && ((count >> c) & 1u)) ? left - 1 : left;
+}
+
+// the trailing arguments of sample_step_kernel, in the order (BudgetArgs, CountArgs), each present or not
+__device__ __forceinline__ void step_extras(BudgetArgs&, CountArgs&) {}
+__device__ __forceinline__ void step_extras(BudgetArgs& b, CountArgs&, const BudgetArgs& x) { b = x; }
+__device__ __forceinline__ void step_extras(BudgetArgs&, CountArgs& c, const CountArgs& y) { c = y; }
+__device__ __forceinline__ void step_extras(BudgetArgs& b, CountArgs& c, const BudgetArgs& x, const CountArgs& y) { b = x; c = y; }
+
 __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl, int V, long long* ids, int ld_ids,
                                                      const int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                      int do_sample, int top_k, float top_p, float temperature,
@@ -627,7 +653,12 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl,
 // no hand-off between workgroups here beyond the arrival counter below.
 // It is a compile-time variant: `budget` is one trailing BudgetArgs kernel argument that only the BUD instantiation has, so the
 // kernels behind mxl_sample_step, _stop and _grammar keep their arguments and their code.
-template <bool G, bool BUD = false, typename... BA>
+//
+// CNT (mxl_sample_step_bars, with G, with or without BUD): the row's gleft[b] (bars it may still open) clears `count` or `end`
+// classes from the same allow word (barcount_deny), and thread 0 moves it where gstate[b] moves.  The same kind of variant: one
+// more trailing argument, a CountArgs after the BudgetArgs if there is one, that only the CNT instantiations have.  gleft is a
+// per-row word like gbar / grem: row b's workgroup alone reads and writes it.
+template <bool G, bool BUD = false, bool CNT = false, typename... BA>
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, int ldl, int V, long long* ids, int ld_ids,
                                                           int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                           int do_sample, int top_k, float top_p, float temperature,
@@ -636,17 +667,22 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
                                                           int min_length, int* unfinished, int* alive,
                                                           const unsigned char* gcls = nullptr, const uint32_t* gallow = nullptr,
                                                           const unsigned char* gnext = nullptr, int C = 0, int* gstate = nullptr,
-                                                          BA... budget) {
-    static_assert(sizeof...(BA) == (BUD ? 1 : 0) && (G || !BUD), "the bar budget rides on the grammar: one BudgetArgs argument");
+                                                          BA... extras) {
+    static_assert(sizeof...(BA) == (BUD ? 1 : 0) + (CNT ? 1 : 0) && (G || !(BUD || CNT)),
+                  "the bar budget and the bar count ride on the grammar: one BudgetArgs and / or one CountArgs argument");
     const int gs = G ? gstate[blockIdx.x] : 0;
     BudgetArgs bud{};
-    if constexpr (BUD) bud = BudgetArgs{budget...};
-    int bbar = 0, brem = 0;
+    CountArgs cnt{};
+    step_extras(bud, cnt, extras...);
+    int bbar = 0, brem = 0, left = -1;
     if (BUD) { bbar = bud.gbar[blockIdx.x]; brem = bud.grem[blockIdx.x]; }
+    if (CNT) left = cnt.gleft[blockIdx.x];
+    uint32_t allow = G ? gallow[gs] : 0u;
+    if (BUD) allow &= ~budget_deny(bbar, brem, bud.need_free, bud.need_full);
+    if (CNT) allow &= ~barcount_deny(left, cnt.count, cnt.end);
     int tok = sample_row<G, BUD>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
                                  repetition_penalty, typical_p, nullptr, unfinished ? eos_id : -1, unfinished ? min_length : 0,
-                                 gcls, G ? (BUD ? gallow[gs] & ~budget_deny(bbar, brem, bud.need_free, bud.need_full) : gallow[gs]) : 0u,
-                                 BUD ? bud.slots : nullptr, BUD ? budget_remcap(bbar, brem) : 0);
+                                 gcls, allow, BUD ? bud.slots : nullptr, BUD ? budget_remcap(bbar, brem) : 0);
     const int b = blockIdx.x, tid = threadIdx.x;
     __shared__ int sh_tok, sh_live;
     bool was_live = true;                       // (thread 0) the token is the row's own choice
@@ -671,6 +707,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         bud.gbar[b] = bbar;
         bud.grem[b] = brem;
     }
+    if (CNT && tid == 0 && was_live && tok >= 0 && tok < V) cnt.gleft[b] = barcount_move(left, gcls[tok], cnt.count);
     if (tid == 0) ids[(size_t)b * ld_ids + *t_dev + 1] = tok;
     const int id = (tok < 0 || tok >= V) ? 0 : tok;
     for (int c = tid; c < (d >> 3); c += 256) {
@@ -819,6 +856,28 @@ __global__ __launch_bounds__(256) void budget_advance_kernel(const long long* id
         budget_move(bar, rem, cls[tok], slots[tok], bars[tok], opens);
         gbar[b] = bar;
         grem[b] = rem;
+    }
+}
+
+// The bar count around the same samplers.  After mxl_grammar_mask and mxl_budget_mask: -inf on every token whose class the row's
+// `left` bars; one thread per score.
+__global__ __launch_bounds__(256) void barcount_mask_kernel(float* scores, int ldl, int B, int V, const unsigned char* cls,
+                                                            uint32_t count, uint32_t end, const int* gleft) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * V) return;
+    const int b = (int)(i / V), v = (int)(i - (long long)b * V);
+    if ((barcount_deny(gleft[b], count, end) >> cls[v]) & 1u) scores[(size_t)b * ldl + v] = -INFINITY;
+}
+
+// beside mxl_grammar_advance and mxl_budget_advance (before the stop rule of the step): `left` of every row that chose its token
+__global__ __launch_bounds__(256) void barcount_advance_kernel(const long long* ids, int ld_ids, const int* t_dev, int B, int V,
+                                                               const unsigned char* cls, uint32_t count, int* gleft,
+                                                               const int* unfinished) {
+    const int t = *t_dev;
+    for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) {
+        if (unfinished && !unfinished[b]) continue;
+        const long long tok = ids[(size_t)b * ld_ids + t];
+        if (tok >= 0 && tok < V) gleft[b] = barcount_move(gleft[b], cls[tok], count);
     }
 }
 
@@ -1076,7 +1135,7 @@ extern "C" int mxl_sample_step_budget(const float* scores, int ldl, int V, void*
     MXL_CHECK_ARG(budget_tables_ok(cls, slots, bars, opens, need_free, need_full, gbar, grem));
     if (!unfinished) { eos_id = -1; pad_id = 0; min_length = 0; }
     const BudgetArgs bud{(const unsigned short*)slots, (const unsigned short*)bars, opens, need_free, need_full, gbar, grem};
-    hipLaunchKernelGGL((sample_step_kernel<true, true, BudgetArgs>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
+    hipLaunchKernelGGL((sample_step_kernel<true, true, false, BudgetArgs>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
                        t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
                        (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id, min_length, unfinished, alive,
                        (const unsigned char*)cls, (const uint32_t*)allow, (const unsigned char*)next, C, gstate, bud);
@@ -1101,6 +1160,61 @@ extern "C" int mxl_budget_advance(const void* ids, int ld_ids, const int* t_dev,
     hipLaunchKernelGGL(budget_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const long long*)ids, ld_ids,
                        t_dev, B, V, (const unsigned char*)cls, (const unsigned short*)slots, (const unsigned short*)bars, opens, gbar,
                        grem, unfinished);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_sample_step_bars(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev,
+                                    unsigned long long* rng_ctr, unsigned long long seed, int B, int do_sample, int top_k,
+                                    float top_p, float temperature, float repetition_penalty, float typical_p, const void* E,
+                                    void* emb_out, int d, float scale, int* counter, int eos_id, int pad_id, int min_length,
+                                    int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C,
+                                    int* gstate, const void* slots, const void* bars, unsigned opens, unsigned need_free,
+                                    unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end, int* gleft,
+                                    void* stream) {
+    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
+    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
+    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
+    MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr) && B <= 32767);     // unfinished = NULL: no eos rule
+    MXL_CHECK_ARG(grammar_tables_ok(cls, allow, next, C, gstate) && gleft);
+    const bool budget = slots || bars || gbar || grem;                              // all four NULL: no bar budget
+    MXL_CHECK_ARG(!budget || budget_tables_ok(cls, slots, bars, opens, need_free, need_full, gbar, grem));
+    if (!unfinished) { eos_id = -1; pad_id = 0; min_length = 0; }
+    const CountArgs cnt{count, end, gleft};
+    if (budget) {
+        const BudgetArgs bud{(const unsigned short*)slots, (const unsigned short*)bars, opens, need_free, need_full, gbar, grem};
+        hipLaunchKernelGGL((sample_step_kernel<true, true, true, BudgetArgs, CountArgs>), dim3(B), dim3(256), 0, (hipStream_t)stream,
+                           scores, ldl, V, (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
+                           repetition_penalty, typical_p, (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id,
+                           min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
+                           (const unsigned char*)next, C, gstate, bud, cnt);
+    } else {
+        hipLaunchKernelGGL((sample_step_kernel<true, false, true, CountArgs>), dim3(B), dim3(256), 0, (hipStream_t)stream,
+                           scores, ldl, V, (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
+                           repetition_penalty, typical_p, (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id,
+                           min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
+                           (const unsigned char*)next, C, gstate, cnt);
+    }
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_barcount_mask(float* scores, int ldl, int B, int V, const void* cls, unsigned count, unsigned end,
+                                 const int* gleft, void* stream) {
+    MXL_CHECK_ARG(scores && cls && gleft && B > 0 && V > 0 && ldl >= V);
+    const long long n = (long long)B * V;
+    MXL_CHECK_ARG(n <= (1LL << 38));
+    hipLaunchKernelGGL(barcount_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V,
+                       (const unsigned char*)cls, count, end, gleft);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_barcount_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, unsigned count,
+                                    int* gleft, const int* unfinished, void* stream) {
+    MXL_CHECK_ARG(ids && t_dev && B > 0 && V > 0 && cls && gleft);
+    hipLaunchKernelGGL(barcount_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const long long*)ids,
+                       ld_ids, t_dev, B, V, (const unsigned char*)cls, count, gleft, unfinished);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }

@@ -53,11 +53,11 @@ def sampling_config(do_sample: bool = False, top_k: Optional[int] = None, top_p:
 def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch.Tensor, rng: torch.Tensor, seed: int, sampling: dict,
                    stop: Optional[tuple] = None, unfinished: Optional[torch.Tensor] = None, alive: Optional[torch.Tensor] = None,
                    grammar=None, gstate: Optional[torch.Tensor] = None, gbar: Optional[torch.Tensor] = None,
-                   grem: Optional[torch.Tensor] = None):
+                   grem: Optional[torch.Tensor] = None, gleft: Optional[torch.Tensor] = None):
     """The sampler tail as separate launches (what mxl_sample_step* does in one): next token of every row from the first V columns
     of `scores` -> ids[:, t + 1], position and RNG counters advanced.  stop = (eos, pad, min_length) with unfinished / alive and
-    grammar with gstate are optional, and a grammar with a bar budget takes gbar / grem as well; the masks write into `scores` in
-    place."""
+    grammar with gstate are optional, and a grammar with a bar budget takes gbar / grem as well; gleft (the bars every row may
+    still open) turns the grammar's bar count on.  The masks write into `scores` in place."""
     budget = grammar is not None and grammar.budget is not None
     sc = scores[:, :V] if scores.shape[1] != V else scores
     if stop is not None:
@@ -68,6 +68,8 @@ def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch
         ops.grammar_mask(sc, V, grammar, gstate)
         if budget:
             ops.budget_mask(sc, V, grammar, gbar, grem)
+        if gleft is not None:
+            ops.barcount_mask(sc, V, grammar, gleft)
     ops.sample(sc, ids, t_dev, rng, seed, **sampling)
     ops.decode_advance(t_dev, rng)
     if grammar is not None:
@@ -76,6 +78,8 @@ def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch
         ops.grammar_advance(ids, t_dev, grammar, gstate, None if stop is None else unfinished)
         if budget:
             ops.budget_advance(ids, t_dev, grammar, gbar, grem, None if stop is None else unfinished)
+        if gleft is not None:
+            ops.barcount_advance(ids, t_dev, grammar, gleft, None if stop is None else unfinished)
     if stop is not None:
         ops.decode_stop(ids, t_dev, stop, unfinished, alive)
 
@@ -135,6 +139,53 @@ def check_grammar_args(grammar, vocab_size: int, stop: Optional[tuple]):
             s, bar, rem = only[0]
             raise ValueError(f'min_length with a bar budget under which state {grammar.state_names[s]} with bar {bar} and {rem} slots '
                              f'free allows only the eos token {stop[0]}: below min_length that row would have every token barred')
+
+
+def bar_count_config(n_bars, batch: int, grammar, stop: Optional[tuple], repeat: int = 1) -> Optional[torch.Tensor]:
+    """`n_bars` of a generation as the decoders take it: None, or a (batch * repeat,) int32 CPU tensor of the bars every row may
+    still open, negative = no limit.  n_bars: an int, or a sequence or tensor of `batch` ints, one per prompt; `repeat` =
+    num_return_sequences (every prompt's value repeated, as the prompts are).  Raises ValueError for what the rule cannot work
+    with: no grammar or a grammar without a bar count; no explicit eos (only the eos rule finishes a row: stopping stays opt-in);
+    an eos that is no `end` token of the grammar (the rule would bar it while bars are left and have no say over the real end);
+    min_length (it bars eos where the count may leave nothing else: a row with every token barred); a wrong length."""
+    if n_bars is None:
+        return None
+    if grammar is None:
+        raise ValueError('n_bars needs grammar=: bars are counted by the token grammar (tokenizer.grammar(bar_budget=True))')
+    cnt = grammar.bar_count
+    if cnt is None:
+        raise ValueError('n_bars needs a grammar with a bar count (grammar.BarCount; the music grammar has one), this one has none')
+    if stop is None:
+        raise ValueError('n_bars needs an explicit eos_token_id=: a row ends by emitting eos, and stopping at eos is opt-in')
+    eos = stop[0]
+    if not 0 <= eos < grammar.vocab_size or not (cnt.end >> int(grammar.cls[eos])) & 1:
+        raise ValueError(f'n_bars: eos_token_id {eos} is no `end` token of the grammar\'s bar count {cnt!r}')
+    if stop[2] > 0:
+        raise ValueError('n_bars together with min_length: min_length bars eos where the bar count may allow nothing else, which '
+                         'would leave a row with every token barred')
+    if isinstance(n_bars, (bool, float)) or (isinstance(n_bars, torch.Tensor) and (n_bars.is_floating_point() or n_bars.dtype == torch.bool)):
+        raise ValueError('n_bars must be an int or a sequence or tensor of ints')
+    if isinstance(n_bars, int):
+        k = torch.full((batch,), n_bars, dtype=torch.int64)
+    else:
+        k = torch.as_tensor(n_bars).detach().cpu().to(torch.int64).reshape(-1)
+        if k.numel() != batch:
+            raise ValueError(f'n_bars holds {k.numel()} entries for {batch} prompts: give an int or one per prompt')
+    return k.clamp(-1, 2 ** 31 - 1).to(torch.int32).repeat_interleave(int(repeat), 0).contiguous()
+
+
+def check_bar_count_start(grammar, n_bars: torch.Tensor, gstate: torch.Tensor):
+    """rows asked for n_bars = 0 whose prompt stops where only a bar can follow (BarCount.needs_bar: the music grammar's header
+    states -- no bar is open yet, and a song has one): MusicXLError naming the row, since every token would be barred there.
+    Reads gstate (after the prompt scan) only when some row has 0."""
+    zero = [b for b, k in enumerate(n_bars.tolist()) if k == 0]
+    if not zero:
+        return
+    states = gstate.tolist()
+    for b in zero:
+        if states[b] in grammar.bar_count.needs_bar:
+            raise MusicXLError(f'n_bars = 0 for row {b}, whose prompt ends in state {grammar.state_names[states[b]]}: no bar is open '
+                               'there to finish and only a new bar can follow; give that row n_bars >= 1')
 
 
 def scan_prompt(grammar, ids: torch.Tensor, Tp: int, gstate: torch.Tensor, gbad: torch.Tensor, gbar: torch.Tensor, grem: torch.Tensor):
@@ -210,6 +261,27 @@ def check_bar_lengths(ids: torch.Tensor, grammar, attention_mask: Optional[torch
     return bad.cpu().to(torch.int64)
 
 
+def bars_after_prompt(ids: torch.Tensor, grammar, prompt_len: Optional[int] = None,
+                      attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B,) int64 on the CPU, as check_bar_lengths: for every row of ids (B, T) the number of tokens after the prompt that open a
+    bar -- tokens of a `count` class of the grammar's bar count (<bar>) from column prompt_len on -- which is what
+    `generate(n_bars=)` sets.  prompt_len: the width of the prompt; default the width of attention_mask (the mask given to
+    generate), else 0 = the whole row.  Ids < 0 and ids beyond the vocabulary count nothing.  The count runs where ids lives."""
+    if grammar.bar_count is None:
+        raise ValueError('bars_after_prompt needs a grammar with a bar count (grammar.BarCount; the music grammar has one)')
+    ids = torch.as_tensor(ids)
+    if ids.dim() == 1:
+        ids = ids.view(1, -1)
+    if prompt_len is None:
+        prompt_len = 0 if attention_mask is None else int(torch.as_tensor(attention_mask).shape[1])
+    x = ids[:, int(prompt_len):].to(torch.int64)
+    V = grammar.vocab_size
+    cls = grammar.to(x.device)[0].to(torch.int64)
+    ok = (x >= 0) & (x < V)
+    hit = (torch.bitwise_right_shift(torch.full_like(x, grammar.bar_count.count), cls[x.clamp(0, V - 1)]) & 1).bool() & ok
+    return hit.sum(1).cpu().to(torch.int64)
+
+
 class _AlivePoll:
     """live-row counts of one decoder read back without stalling its stream: after each chunk of steps a non-blocking copy of
     `alive` into pinned host memory and an event; `wait(keep)` blocks until at most `keep` such reads are outstanding"""
@@ -269,16 +341,17 @@ def run_until_finished(decoders, n: int, chunk: int = STOP_CHUNK) -> list:
 
 
 def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool, n_pad, stop, stop_chunk,
-                 grammar) -> torch.Tensor:
+                 grammar, n_bars=None) -> torch.Tensor:
     """The body of `generate` for one decoder (lanes = [dec], streams = [None]) or for an XLDecoderLanes with its lanes and their
     streams: `dec.begin`, then every remaining step through `dec.replay_once` -- or, with stop = (eos, pad, min_length), each lane
     on its own until its rows have finished (run_until_finished) -- then the lanes' rows in order, cut to the width of the longest
     lane and right-filled with pad where a lane stopped earlier.  Sets `steps_run` on every lane and on dec (the most of any
-    lane).  The prompt columns of left-padded prompts (n_pad) come back as given."""
+    lane).  The prompt columns of left-padded prompts (n_pad) come back as given.  n_bars: None or one int32 per row
+    (bar_count_config); each lane takes its rows' entries."""
     Tp = prompt.shape[1]
     if max_length - Tp <= 0:
         return prompt[:, :max_length]
-    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar)
+    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar, n_bars)
     if stop is None:
         for _ in range(n):
             dec.replay_once()
@@ -358,6 +431,10 @@ class XLDecoder:
         # bar budget of such a grammar (grammar.BarBudget): bar length and free slots of every row, moved where gstate moves
         self.gbar = torch.zeros(batch, device=dev, dtype=torch.int32)
         self.grem = torch.zeros(batch, device=dev, dtype=torch.int32)
+        # bar count of such a grammar (grammar.BarCount, generate(n_bars=)): the bars every row may still open, < 0 = no limit;
+        # `_bars`: the current generation runs under the rule (the sampler launch that carries it)
+        self.gleft = torch.full((batch,), -1, device=dev, dtype=torch.int32)
+        self._bars = False
 
     def _tables(self):
         if self.rd is None:
@@ -376,7 +453,7 @@ class XLDecoder:
 
     # ---------------------------------------------------------------- prompt
     def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None,
-                grammar=None):
+                grammar=None, n_bars: Optional[torch.Tensor] = None):
         """Whole prompt through the training-shape kernels with zero mems (upstream first step), rings filled from the
         per-layer qkv buffers, first new token sampled from the last position.
         n_pad: (B,) int32 device tensor, left-padded prompts: the first n_pad[b] columns of row b are pads.  Their K / V are zero
@@ -385,10 +462,19 @@ class XLDecoder:
         stop: (eos, pad, min_length) or None (stop_config); every row starts live, and the first token sampled here counts.
         grammar: a grammar.TokenGrammar or None; every row's state after its prompt is computed on the device (pads skipped), and a
         prompt that breaks the grammar raises.  With a bar budget the same holds for the rows' bar lengths and free slots, and a
-        prompt that overfills or underfills a bar raises."""
+        prompt that overfills or underfills a bar raises.
+        n_bars: None, or (B,) int32 from bar_count_config: the bars every row may still open (the grammar's bar count); it is the
+        start value of `gleft`, which the sampler launches move."""
         e, c = self.eng, self.eng.cfg
         check_grammar_args(grammar, c.vocab_size, stop)
         self._grammar = grammar
+        if n_bars is not None and (grammar is None or grammar.bar_count is None or stop is None or n_bars.numel() != self.B):
+            raise MusicXLError('n_bars needs a grammar with a bar count, the eos rule and one entry per row (bar_count_config)')
+        self._bars = n_bars is not None
+        if self._bars:
+            self.gleft.copy_(n_bars.to(torch.int32))
+        else:
+            self.gleft.fill_(-1)
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
         self._tables()
@@ -426,6 +512,8 @@ class XLDecoder:
         self._trace()
         if grammar is not None:
             raise_on_bad_prompt(grammar, self.ids, self.gbad)
+        if self._bars:
+            check_bar_count_start(grammar, n_bars, self.gstate)
         if sampling is not None:                       # None: the caller picks the token from self.logp (beam search)
             self._sample_advance(self.logp, sampling)  # t = Tp: position of the token just sampled
         return out
@@ -435,7 +523,7 @@ class XLDecoder:
         position and RNG counters advanced.  Short chain: the same launch leaves the token's embedding row in h[0] for the next step."""
         c = self.eng.cfg
         state = dict(stop=self._stop, unfinished=self.unfinished, alive=self.alive, grammar=self._grammar, gstate=self.gstate,
-                     gbar=self.gbar, grem=self.grem)
+                     gbar=self.gbar, grem=self.grem, gleft=self.gleft if self._bars else None)
         if self.fused_sampler:      # the masks, the stop rule, the live-row count and the state advance ride on the sampler launch
             ops.sample_step(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
                             self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model), self.step_ctr,
@@ -541,17 +629,20 @@ class XLDecoder:
 
     # ---------------------------------------------------------------- loop
     def begin(self, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool = True,
-              n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None, grammar=None) -> int:
+              n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None, grammar=None,
+              n_bars: Optional[torch.Tensor] = None) -> int:
         """prompt pass + first sampled token + (use_graph) capture of one decode step; returns the number of `replay_once()`
         calls that complete the generation to max_length.  n_pad: left-padded prompts (prefill); the decode step is the same,
         every row's last prompt token sits at column Tp - 1.  stop: (eos, pad, min_length) (stop_config) or None.  grammar: a
         grammar.TokenGrammar or None; the captured step reads its device tables and, under a bar budget, the budget's tables and
-        class masks, so their identity is part of the graph key"""
+        class masks, so their identity is part of the graph key.  n_bars: None or (B,) int32 (prefill); the step captured under the
+        bar count is another launch with two more class masks, so the presence of the rule and its masks are in the key too, while
+        the counts themselves are step state (`gleft`)"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         self._sampling = sampling
         self._use_graph = use_graph
-        self.prefill(prompt, sampling, n_pad, stop, grammar)
+        self.prefill(prompt, sampling, n_pad, stop, grammar, n_bars)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
             # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
@@ -561,12 +652,14 @@ class XLDecoder:
                    None if grammar is None else tuple(t.data_ptr() for t in grammar.to(self.eng.dev)) + (grammar.n_classes,),
                    None if grammar is None or grammar.budget is None else
                    tuple(t.data_ptr() for t in grammar.budget.to(self.eng.dev))
-                   + (grammar.budget.opens, grammar.budget.need_free, grammar.budget.need_full))
+                   + (grammar.budget.opens, grammar.budget.need_free, grammar.budget.need_full),
+                   (grammar.bar_count.count, grammar.bar_count.end) if self._bars else None)
             if self.graph is None or self._graph_key != key:
                 # warm-up on a side stream (first launches set function attributes), then capture one step
                 state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(),
                          [k.clone() for k in self.kc], [v.clone() for v in self.vc], self.h[0].clone(),
-                         self.unfinished.clone(), self.alive.clone(), self.gstate.clone(), self.gbar.clone(), self.grem.clone())
+                         self.unfinished.clone(), self.alive.clone(), self.gstate.clone(), self.gbar.clone(), self.grem.clone(),
+                         self.gleft.clone())
                 s = torch.cuda.Stream()
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
@@ -584,7 +677,7 @@ class XLDecoder:
                     a.copy_(b)
                 self.h[0].copy_(state[5])         # (short chain: the next step's embedding row is step state too)
                 self.unfinished.copy_(state[6]); self.alive.copy_(state[7]); self.gstate.copy_(state[8])
-                self.gbar.copy_(state[9]); self.grem.copy_(state[10])
+                self.gbar.copy_(state[9]); self.grem.copy_(state[10]); self.gleft.copy_(state[11])
         return max(steps, 0)
 
     def replay_once(self):
@@ -598,7 +691,7 @@ class XLDecoder:
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
                  typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
-                 stop_chunk: int = STOP_CHUNK, grammar=None) -> torch.Tensor:
+                 stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None) -> torch.Tensor:
         """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
         [OMIT]) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (prefill); the
         prompt columns, pads included, come back as given.
@@ -609,10 +702,14 @@ class XLDecoder:
         grammar (a grammar.TokenGrammar, e.g. `tokenizer.grammar()`): every row may only emit tokens its grammar state allows; the
         state lives on the device and moves inside the sampler launch of the captured step.  The prompts must obey the grammar.
         A grammar with a bar budget (`tokenizer.grammar(bar_budget=True)`) also keeps every channel of every generated bar exactly as
-        long as the row's time signature: the free slots of the open channel live and move beside the state."""
+        long as the row's time signature: the free slots of the open channel live and move beside the state.
+        n_bars (an int or one per row, negative = no limit; needs grammar and eos_token_id): every row opens exactly that many
+        further bars -- the bar open at the end of its prompt is finished and not counted -- and, under a bar budget, emits eos
+        when the last of them is full.  Without a budget the rule bars a further bar and an early eos but cannot force the end."""
+        stop = stop_config(eos_token_id, pad_token_id, min_length)
         return decode_lanes(self, [self], [None], prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
-                            stop_config(eos_token_id, pad_token_id, min_length), stop_chunk, grammar)
+                            stop, stop_chunk, grammar, bar_count_config(n_bars, self.B, grammar, stop))
 
 
 class XLDecoderLanes:
@@ -635,9 +732,10 @@ class XLDecoderLanes:
         for d in self.lanes:
             d.invalidate_tables()
 
-    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None, grammar=None) -> int:
+    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None, grammar=None, n_bars=None) -> int:
         steps = [d.begin(prompt[self.offs[i]:self.offs[i + 1]], max_length, sampling, use_graph,
-                         None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]], stop, grammar)
+                         None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]], stop, grammar,
+                         None if n_bars is None else n_bars[self.offs[i]:self.offs[i + 1]])
                  for i, d in enumerate(self.lanes)]
         for s in self.streams:                       # the lanes start from the prompt passes and captures issued above
             s.wait_stream(torch.cuda.current_stream())
@@ -654,12 +752,13 @@ class XLDecoderLanes:
 
     def generate(self, prompt, max_length, do_sample=False, top_k=None, top_p=None, temperature=1.0, repetition_penalty=None,
                  typical_p=None, use_graph=True, n_pad=None, eos_token_id=None, pad_token_id=None, min_length=None,
-                 stop_chunk=STOP_CHUNK, grammar=None) -> torch.Tensor:
-        """XLDecoder.generate over the lanes (each lane keeps the grammar state of its own rows).  With eos_token_id every lane stops
+                 stop_chunk=STOP_CHUNK, grammar=None, n_bars=None) -> torch.Tensor:
+        """XLDecoder.generate over the lanes (each lane keeps the grammar state and the bar counts of its own rows).  With eos_token_id every lane stops
         on its own; the output is the lanes' rows cut to the common width and right-filled with pad where a lane stopped earlier."""
+        stop = stop_config(eos_token_id, pad_token_id, min_length)
         return decode_lanes(self, self.lanes, self.streams, prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
-                            stop_config(eos_token_id, pad_token_id, min_length), stop_chunk, grammar)
+                            stop, stop_chunk, grammar, bar_count_config(n_bars, self.B, grammar, stop))
 
 
 class _BeamHyps:

@@ -29,6 +29,15 @@ slots still free in the open channel).  Its tables sit beside the grammar's:
 
 and a duration of k slots is allowed only if k <= rem.  The rule looks at the token's class and the two integers alone, never at the
 automaton state, so it needs no state of its own and composes with any mask the grammar applies.
+
+Both forms of the music grammar also carry a `BarCount` (`grammar.bar_count`), the rule behind `generate(..., n_bars=k)`: one more
+integer per row, `left` = the bars the row may still open (negative = no limit, the row is untouched), and two class bit masks
+
+    count      class bit mask  classes that open a bar (<bar>): barred at left == 0, a kept one takes 1 from a positive left
+    end        class bit mask  classes that end the stream (</s>): barred while left > 0
+
+Under the bar budget a row whose last bar is full may emit only <bar> or </s>, so the count decides which: the row ends exactly when
+its k-th bar is full.  Without a budget the rule still bars a further bar and an early end, but nothing forces the end.
 """
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -91,6 +100,7 @@ class TokenGrammar:
                                  'a token: generation would face a row with every token barred')
         self._dev: Dict[str, tuple] = {}
         self.budget: Optional['BarBudget'] = None        # the duration budget riding on this grammar (BarBudget attaches itself)
+        self.bar_count: Optional['BarCount'] = None      # the bar count rule of generate(n_bars=) (BarCount attaches itself)
 
     # ---------------------------------------------------------------- shape
     @property
@@ -160,6 +170,13 @@ class TokenGrammar:
         if self.budget is None:
             raise ValueError('this grammar carries no bar budget: build it with grammar(bar_budget=True)')
         return self.budget.walk(ids, bar, rem)
+
+    def walk_bars(self, ids, left: int) -> Tuple[int, int]:
+        """(left, index of the first token the bar count bars or -1) for a 1-D id sequence that starts with `left` bars to go
+        (BarCount.walk): the host reference of the device rule.  Ids < 0 and ids beyond the vocabulary are skipped."""
+        if self.bar_count is None:
+            raise ValueError('this grammar carries no bar count: attach a grammar.BarCount (the music grammar has one)')
+        return self.bar_count.walk(ids, left)
 
     def accepts(self, ids) -> bool:
         s, bad = self.walk(ids)
@@ -310,10 +327,119 @@ class BarBudget:
         return f'BarBudget(bars={sorted(set(self.bars.tolist()) - {NO_SIG})}, durations={int(((self.slots > 0) & (self.slots < RARE_SLOTS)).sum())})'
 
 
+def _class_mask(grammar: TokenGrammar, x) -> int:
+    """a class bit mask of `grammar` from a mask or an iterable of class names"""
+    if isinstance(x, (int, np.integer)):
+        m = int(x)
+    else:
+        m = 0
+        for name in ([x] if isinstance(x, str) else x):
+            if name not in grammar.class_names:
+                raise ValueError(f'unknown token class {name!r}')
+            m |= 1 << grammar.class_names.index(name)
+    if m < 0 or m >> grammar.n_classes:
+        raise ValueError(f'a class mask has a bit set beyond class {grammar.n_classes - 1}')
+    return m
+
+
+class BarCount:
+    def __init__(self, grammar: TokenGrammar, count, end):
+        """The bar count rule of `grammar` (module docstring): `count` and `end`, each a class bit mask or an iterable of class
+        names.  Attaches itself as `grammar.bar_count`; attach it after the grammar's BarBudget, if it gets one.
+        The sampler must never face a row with every token barred, so the constructor looks at every state the start state reaches
+        (under the budget: every (state, bar, rem)).  One that allows only `end` tokens would be stuck while left > 0: ValueError.
+        One that allows only `count` tokens is stuck at left == 0 (the music grammar's S3: after the key only <bar> may follow, a
+        song has a bar).  `needs_bar` holds the states from which such a state is reached without a `count` token: a row may not
+        START there with n_bars = 0, which `generate` refuses per row.  A `count` token that leads into `needs_bar` could bring a
+        row there with left == 0: ValueError."""
+        self.count, self.end = _class_mask(grammar, count), _class_mask(grammar, end)
+        if not self.count or not self.end:
+            raise ValueError('count and end each need at least one class')
+        if self.count & self.end:
+            raise ValueError('a class cannot both open a bar and end the stream')
+        self.grammar = grammar
+        g, stuck = grammar, set()
+        for s, name, classes in self._nodes():
+            if classes and not classes & ~self.end:
+                raise ValueError(f'{name} can be reached from the start state and allows only `end` classes: while bars are left '
+                                 'to open that row would have every token barred')
+            if classes and not classes & ~self.count:
+                stuck.add(s)
+        reach = g.reachable()
+        needs, grew = set(stuck), True
+        while grew:                                      # backwards from the stuck states over the transitions of other classes
+            grew = False
+            for s in reach:
+                if s not in needs and any((int(g.allow[s]) & g.populated & ~self.count) >> c & 1 and int(g.next[s, c]) in needs
+                                          for c in range(g.n_classes)):
+                    needs.add(s)
+                    grew = True
+        self.needs_bar = frozenset(needs)
+        for s in reach:
+            for c in range(g.n_classes):
+                if (int(g.allow[s]) & g.populated & self.count) >> c & 1 and int(g.next[s, c]) in needs:
+                    raise ValueError(f'a `count` token in state {g.state_names[s]} leads to state {g.state_names[int(g.next[s, c])]}, '
+                                     'from which only a further `count` token leads on: after its last bar that row would have '
+                                     'every token barred')
+        grammar.bar_count = self
+
+    def _nodes(self):
+        """(state, name, mask of the classes that have an allowed token) of everything the start state reaches"""
+        g = self.grammar
+        if g.budget is None:
+            for s in g.reachable():
+                yield s, f'state {g.state_names[s]}', int(g.allow[s]) & g.populated
+            return
+        bud = g.budget
+        for s, bar, rem in bud._reach:
+            m = 0
+            for c in range(g.n_classes):
+                if (int(g.allow[s]) >> c) & 1 and any(bud.allows(bar, rem, c, k) for k, _ in bud._kinds[c]):
+                    m |= 1 << c
+            yield s, f'state {g.state_names[s]} with bar {bar} and {rem} slots free', m
+
+    # ---------------------------------------------------------------- the rule
+    def allows(self, left: int, c: int) -> bool:
+        """may a token of class c follow in a row with `left` bars to go?  (what the grammar and the budget say comes on top)"""
+        if left < 0:
+            return True
+        if (self.count >> c) & 1 and left == 0:
+            return False
+        if (self.end >> c) & 1 and left > 0:
+            return False
+        return True
+
+    def move(self, left: int, c: int) -> int:
+        """`left` after a token of class c"""
+        return left - 1 if left > 0 and (self.count >> c) & 1 else left
+
+    # ---------------------------------------------------------------- host reference
+    def walk(self, ids, left: int) -> Tuple[int, int]:
+        """(left, index of the first token the rule bars or -1); the walk stops there.  Ids < 0 (left pads) and ids beyond the
+        vocabulary are skipped: the latter are the grammar's to report."""
+        seq = ids.tolist() if hasattr(ids, 'tolist') else list(ids)
+        cls, V, left = self.grammar.cls, self.grammar.vocab_size, int(left)
+        for i, tok in enumerate(seq):
+            tok = int(tok)
+            if tok < 0 or tok >= V:
+                continue
+            c = int(cls[tok])
+            if not self.allows(left, c):
+                return left, i
+            left = self.move(left, c)
+        return left, -1
+
+    def __repr__(self):
+        names = lambda m: [n for i, n in enumerate(self.grammar.class_names) if (m >> i) & 1]
+        return f'BarCount(count={names(self.count)}, end={names(self.end)})'
+
+
 def from_transitions(cls, class_names: Sequence[str], transitions: Sequence[Tuple[str, str, str]], start: str,
-                     accepting: Optional[Iterable[str]] = None, budget: Optional[dict] = None) -> TokenGrammar:
+                     accepting: Optional[Iterable[str]] = None, budget: Optional[dict] = None,
+                     bar_count: Optional[dict] = None) -> TokenGrammar:
     """a TokenGrammar from (state, class, successor) triples by name; states are numbered in order of appearance, `start` first.
-    budget: the explicit tables of a BarBudget to attach, as its keyword arguments (slots, bars, opens, need_free, need_full)"""
+    budget: the explicit tables of a BarBudget to attach, as its keyword arguments (slots, bars, opens, need_free, need_full).
+    bar_count: the classes of a BarCount to attach, as its keyword arguments (count, end)"""
     states = [start]
     for a, _, b in transitions:
         for s in (a, b):
@@ -335,6 +461,8 @@ def from_transitions(cls, class_names: Sequence[str], transitions: Sequence[Tupl
     g = TokenGrammar(cls, allow, nxt, 0, acc, class_names, states)
     if budget is not None:
         BarBudget(g, **budget)
+    if bar_count is not None:
+        BarCount(g, **bar_count)
     return g
 
 
@@ -362,6 +490,7 @@ MUSIC_TRANSITIONS = [
 ]
 
 
+MUSIC_BAR_COUNT_CLASSES = dict(count=('<bar>',), end=('</s>',))
 MUSIC_BUDGET_CLASSES = dict(opens=('<melody>', '<bass>'), need_free=('pitch', '<tup>'), need_full=('<bass>', '<bar>', '</s>'))
 
 
@@ -389,7 +518,8 @@ def music_budget_tables(vocab) -> dict:
 def music_grammar(vocab, bar_budget: bool = False) -> TokenGrammar:
     """the grammar above for a MusicVocabulary of any pitch kind: the class of a token is its `vocab.type`, and every special
     token ([PAD] and [OMIT] included) is a class of its own.  bar_budget: attach the duration budget (`grammar.budget`), so that
-    every channel of a bar generated under the grammar is exactly as long as the prompt's time signature says"""
+    every channel of a bar generated under the grammar is exactly as long as the prompt's time signature says.  Either form
+    carries the bar count rule of `generate(n_bars=)` (`grammar.bar_count`: count = <bar>, end = </s>)"""
     cid = {c: i for i, c in enumerate(MUSIC_CLASSES)}
     cls = np.zeros(len(vocab), dtype=np.uint8)
     for tok, i in vocab.tok2id.items():
@@ -399,4 +529,4 @@ def music_grammar(vocab, bar_budget: bool = False) -> TokenGrammar:
             raise ValueError(f'token {tok!r} has no class in the music grammar')
         cls[i] = cid[name]
     return from_transitions(cls, MUSIC_CLASSES, MUSIC_TRANSITIONS, 'S0', accepting=['END'],
-                            budget=music_budget_tables(vocab) if bar_budget else None)
+                            budget=music_budget_tables(vocab) if bar_budget else None, bar_count=MUSIC_BAR_COUNT_CLASSES)

@@ -134,14 +134,16 @@ def decode_qkv(x, wqkv, qkv, kc, vc, t_dev, rrb, qr_out, dh):
 
 
 def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
-                grammar=None, gstate=None, gbar=None, grem=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0,
+                grammar=None, gstate=None, gbar=None, grem=None, gleft=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0,
                 repetition_penalty=1.0, typical_p=1.0):
     """sampler + embedding row of the sampled token (-> emb_out (B, d) bf16) + counter advance, one launch (V <= 2048).
     scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1.
     stop = (eos_id, pad_id, min_length) with unfinished (B,) int32 and alive (1,) int32 on the device: the stop state of generation
     rides on the same launch (mxl_sample_step_stop).  grammar (a grammar.TokenGrammar) with gstate (B,) int32: barred tokens masked
     and gstate advanced in the same launch, with or without the eos rule (mxl_sample_step_grammar).  A grammar with a bar budget
-    (grammar.budget) needs gbar and grem (B,) int32 as well and takes mxl_sample_step_budget; without one the launch is unchanged."""
+    (grammar.budget) needs gbar and grem (B,) int32 as well and takes mxl_sample_step_budget; without one the launch is unchanged.
+    gleft (B,) int32, the bars every row may still open (< 0 = no limit): the bar count of the grammar (grammar.bar_count) is applied
+    and gleft moved in the same launch, with or without the budget (mxl_sample_step_bars); None = no such rule, the launches above."""
     B = scores.shape[0]
     args = [_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B, int(do_sample),
             int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
@@ -168,6 +170,14 @@ def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter
             slots, bars = _budget_state(bud, scores.device, B, gbar, grem, 'sample_step_budget')
             args += [_p(slots), _p(bars), bud.opens, bud.need_free, bud.need_full, _p(gbar), _p(grem)]
             name = 'mxl_sample_step_budget'
+        if gleft is not None:
+            cnt = _barcount_state(grammar, B, gleft, 'sample_step_bars')
+            if grammar.budget is None:
+                args += [0, 0, 0, 0, 0, 0, 0]
+            args += [cnt.count, cnt.end, _p(gleft)]
+            name = 'mxl_sample_step_bars'
+    elif gleft is not None:
+        raise MusicXLError('sample_step_bars: the bar count rides on a grammar')
     check(getattr(lib(), name)(*args, _stream()), name)
 
 
@@ -280,6 +290,41 @@ def budget_scan(ids, Tp, grammar, gbar, grem, first_bad):
     slots, bars = _budget_state(bud, ids.device, B, gbar, grem, 'budget_scan')
     check(lib().mxl_budget_scan(_p(ids), ids.stride(0), int(Tp), B, grammar.vocab_size, _p(cls), _p(slots), _p(bars), bud.opens,
                                 bud.need_free, bud.need_full, _p(gbar), _p(grem), _p(first_bad), _stream()), 'mxl_budget_scan')
+
+
+def _barcount_state(grammar, B, gleft, what):
+    """the grammar.BarCount of a grammar, with the per-row word gleft checked"""
+    if grammar is None or grammar.bar_count is None:
+        raise MusicXLError(f'{what}: the grammar carries no bar count (grammar.BarCount; the music grammar has one)')
+    _req(gleft, torch.int32, f'{what} gleft')
+    if gleft.numel() != B or not gleft.is_contiguous():
+        raise MusicXLError(f'{what}: gleft must be contiguous ({B},) int32')
+    return grammar.bar_count
+
+
+def barcount_mask(scores, V, grammar, gleft):
+    """after grammar_mask and budget_mask, before sample: scores[b, v] = -inf in place for every token the bar count of `grammar`
+    bars in a row with gleft[b] bars to go (mxl_barcount_mask)"""
+    _req(scores, torch.float32, 'barcount_mask scores')
+    B = scores.shape[0]
+    if scores.shape[1] < V or scores.stride(1) != 1:
+        raise MusicXLError('barcount_mask: scores must be (B, >= V) with unit column stride')
+    cnt = _barcount_state(grammar, B, gleft, 'barcount_mask')
+    cls, _, _ = _grammar_tables(grammar, scores.device, V)
+    check(lib().mxl_barcount_mask(_p(scores), scores.stride(0), B, int(V), _p(cls), cnt.count, cnt.end, _p(gleft), _stream()),
+          'mxl_barcount_mask')
+
+
+def barcount_advance(ids, t_dev, grammar, gleft, unfinished=None):
+    """beside grammar_advance and budget_advance (after sample + decode_advance, before decode_stop): gleft[b] moves along the token
+    at ids[b, t]; rows with unfinished[b] == 0 keep theirs (mxl_barcount_advance)"""
+    B = ids.shape[0]
+    if ids.dtype != torch.int64:
+        raise MusicXLError('barcount_advance: ids must be (B, .) int64')
+    cnt = _barcount_state(grammar, B, gleft, 'barcount_advance')
+    cls, _, _ = grammar.to(ids.device)
+    check(lib().mxl_barcount_advance(_p(ids), ids.stride(0), _p(t_dev), B, grammar.vocab_size, _p(cls), cnt.count, _p(gleft),
+                                     _p(unfinished), _stream()), 'mxl_barcount_advance')
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, relu=False, out=None,

@@ -154,7 +154,7 @@ class MyReformerModelWithLMHead(EngineModule):
                  num_beam_groups: int = 1, length_penalty: float = 1.0, diversity_penalty=None,
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
-                 grammar=None, **unsupported):
+                 grammar=None, n_bars=None, **unsupported):
         """`model.generate(...)` as the reference drives it (musicnlp/trainer/eval.py:277-333): greedy, or sampling with
         top-k / top-p / typical-p / temperature / repetition penalty (applied, as HF does, to the raw logits); token selection
         runs on the device (the TransfoXL decoder's sampler kernel).
@@ -173,15 +173,24 @@ class MyReformerModelWithLMHead(EngineModule):
 
         grammar (a `grammar.TokenGrammar`): greedy decoding and sampling in which every row may only emit tokens its grammar state
         allows, as MyTransfoXLLMHeadModel.generate: the mask runs on the device before the sampler, the state advance after it.  A
-        grammar with a bar budget (`tokenizer.grammar(bar_budget=True)`) keeps every generated bar as long as its time signature."""
-        from .generate import (STOP_CHUNK, beam_generate, check_grammar_args, left_pad_counts, raise_on_bad_prompt, resolve_max_length,
-                               sample_unfused, sampling_config, scan_prompt, stop_config, stop_width)
+        grammar with a bar budget (`tokenizer.grammar(bar_budget=True)`) keeps every generated bar as long as its time signature.
+
+        n_bars (an int, or one per prompt; negative = no limit; with grammar and eos_token_id, greedy decoding and sampling): every
+        row opens exactly that many further bars, as MyTransfoXLLMHeadModel.generate -- under the bar budget it ends with eos when
+        the last of them is full; under a grammar without one the rule cannot force the end and a row may run to max_length."""
+        from .generate import (STOP_CHUNK, bar_count_config, beam_generate, check_bar_count_start, check_grammar_args, left_pad_counts,
+                               raise_on_bad_prompt, resolve_max_length, sample_unfused, sampling_config, scan_prompt, stop_config,
+                               stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
         check_grammar_args(grammar, self.config.vocab_size, stop)
         if grammar is not None and (num_beams > 1 or num_beam_groups != 1):
             raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam or group-beam search')
+        if n_bars is not None and (num_beams > 1 or num_beam_groups != 1 or (penalty_alpha and not do_sample)):
+            raise MusicXLError('n_bars= is supported for greedy decoding and sampling only, not for beam, group-beam or contrastive '
+                               'search')
+        n_bars = bar_count_config(n_bars, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, nrs)
         if attention_mask is not None and input_ids is not None and any(left_pad_counts(attention_mask, tuple(input_ids.shape))):
             # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
             raise MusicXLError(f'{type(self).__name__}.generate does not support padded prompts (attention_mask with zeros); '
@@ -243,7 +252,7 @@ class MyReformerModelWithLMHead(EngineModule):
                 dec.rotations = rotations
                 dec.seed = seed
                 return dec.generate(ids0, max_length, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
-                                    repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop, grammar=grammar)
+                                    repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop, grammar=grammar, n_bars=n_bars)
             V = c.vocab_size
             pad = getattr(c, 'pad_token_id', None)
             pad = 0 if pad is None else int(pad)
@@ -253,18 +262,21 @@ class MyReformerModelWithLMHead(EngineModule):
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
             unfinished = torch.ones(B, device=self.device, dtype=torch.int32)
             alive = torch.zeros(1, device=self.device, dtype=torch.int32)
-            gstate = gbar = grem = None
+            gstate = gbar = grem = gleft = None
             if grammar is not None:
                 gstate, gbar, grem = (torch.zeros(B, device=self.device, dtype=torch.int32) for _ in range(3))
                 gbad = torch.empty(2, B, device=self.device, dtype=torch.int32)
                 scan_prompt(grammar, buf, Tp, gstate, gbad, gbar, grem)
                 raise_on_bad_prompt(grammar, buf, gbad)
+            if n_bars is not None:
+                gleft = n_bars.to(self.device)
+                check_bar_count_start(grammar, n_bars, gstate)
             sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
             for cur in range(Tp, max_length):
                 Tf = cur if cur <= 64 else (cur + 63) // 64 * 64
                 out = self.engine.forward(buf[:, :Tf].contiguous(), labels=None, train=False)
                 last = out['logits'][:, cur - 1].contiguous()
-                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, stop, unfinished, alive, grammar, gstate, gbar, grem)
+                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, stop, unfinished, alive, grammar, gstate, gbar, grem, gleft)
                 if Tf > cur:
                     buf[:, cur + 1:Tf] = pad          # keep the padding clean (the sampler wrote position `cur` only)
                 # a whole forward per token: reading the live-row count every STOP_CHUNK tokens costs nothing in comparison

@@ -26,7 +26,8 @@ import torch
 
 from . import ops
 from ._lib import MusicXLError
-from .generate import check_grammar_args, decode_lanes, raise_on_bad_prompt, sample_unfused, sampling_config, scan_prompt
+from .generate import (bar_count_config, check_bar_count_start, check_grammar_args, decode_lanes, raise_on_bad_prompt, sample_unfused,
+                       sampling_config, scan_prompt)
 
 
 class RFDecoder:
@@ -78,6 +79,8 @@ class RFDecoder:
         self._grammar = None
         self.gbar = torch.zeros(batch, device=dev, dtype=torch.int32)     # bar budget of such a grammar: bar length, free slots
         self.grem = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self.gleft = torch.full((batch,), -1, device=dev, dtype=torch.int32)   # bar count (generate(n_bars=)): bars left to open
+        self._bars = False
 
     # ---------------------------------------------------------------- hashing helpers
     def _factors(self, T_hint: Optional[int] = None):
@@ -106,13 +109,21 @@ class RFDecoder:
         return r
 
     # ---------------------------------------------------------------- prompt
-    def prefill(self, prompt: torch.Tensor, sampling: dict, stop: Optional[tuple] = None, grammar=None):
+    def prefill(self, prompt: torch.Tensor, sampling: dict, stop: Optional[tuple] = None, grammar=None,
+                n_bars: Optional[torch.Tensor] = None):
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and 1 <= Tp <= self.Tmax
         check_grammar_args(grammar, c.vocab_size, stop)
         self._stop = stop
         self._grammar = grammar
+        if n_bars is not None and (grammar is None or grammar.bar_count is None or stop is None or n_bars.numel() != B):
+            raise MusicXLError('n_bars needs a grammar with a bar count, the eos rule and one entry per row (bar_count_config)')
+        self._bars = n_bars is not None
+        if self._bars:
+            self.gleft.copy_(n_bars.to(torch.int32))
+        else:
+            self.gleft.fill_(-1)
         self.unfinished.fill_(1)
         self.alive.fill_(B)
         d, H = c.hidden_size, c.num_attention_heads
@@ -149,6 +160,8 @@ class RFDecoder:
         self.t_dev.fill_(Tp - 1)
         if grammar is not None:
             raise_on_bad_prompt(grammar, self.ids, self.gbad)
+        if self._bars:
+            check_bar_count_start(grammar, n_bars, self.gstate)
         self._sample(last, sampling)
         return out
 
@@ -160,7 +173,8 @@ class RFDecoder:
             return
         # (min_length and the grammar mask write into the logits: after the trace above)
         sample_unfused(logits, self.eng.cfg.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, self._stop,
-                       self.unfinished, self.alive, self._grammar, self.gstate, self.gbar, self.grem)
+                       self.unfinished, self.alive, self._grammar, self.gstate, self.gbar, self.grem,
+                       self.gleft if self._bars else None)
 
     # ---------------------------------------------------------------- one token
     def step(self, t: int, sampling: dict):
@@ -267,24 +281,25 @@ class RFDecoder:
     def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
                  typical_p: Optional[float] = None, stop: Optional[tuple] = None, stop_chunk: int = 16,
-                 grammar=None) -> torch.Tensor:
+                 grammar=None, n_bars=None) -> torch.Tensor:
         """(B, max_length) ids = prompt + continuation.  stop = (eos, pad, min_length) (generate.stop_config): rows finish at eos
         and the loop ends once none is live -- the live-row count is read back every `stop_chunk` steps, one chunk late
         (generate.run_until_finished) -- and the output is cut to the longest row.  grammar: a grammar.TokenGrammar; every row may
         only emit tokens its grammar state allows (mask before the sampler, state advance after it, both on the device); a bar budget
-        on the grammar is kept the same way."""
+        on the grammar is kept the same way, and n_bars (an int or one per row, negative = no limit) turns its bar count on: every row
+        opens exactly that many further bars (generate.XLDecoder.generate)."""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         return decode_lanes(self, [self], [None], prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), False, None, stop,
-                            stop_chunk, grammar)
+                            stop_chunk, grammar, bar_count_config(n_bars, self.B, grammar, stop))
 
-    def begin(self, prompt, max_length, sampling, use_graph=False, n_pad=None, stop=None, grammar=None) -> int:
+    def begin(self, prompt, max_length, sampling, use_graph=False, n_pad=None, stop=None, grammar=None, n_bars=None) -> int:
         """generate.decode_lanes' entry: prompt pass and first token; returns the `replay_once()` calls left to max_length.  There
         is no graph to capture here, and padded prompts are not supported."""
         assert not use_graph and n_pad is None
         Tp = prompt.shape[1]
-        self.prefill(prompt.to(self.eng.dev), sampling, stop, grammar)
+        self.prefill(prompt.to(self.eng.dev), sampling, stop, grammar, n_bars)
         self._next_t, self._sampling = Tp, sampling
         return max(max_length - 1 - Tp, 0)
 

@@ -198,7 +198,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  renormalize_logits=None, num_return_sequences: int = 1, num_beam_groups: int = 1, length_penalty: float = 1.0,
                  use_graph: bool = True, seed: int = 77, attention_mask: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
-                 min_length: Optional[int] = None, grammar=None, **unused) -> torch.Tensor:
+                 min_length: Optional[int] = None, grammar=None, n_bars=None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -224,9 +224,19 @@ class MyTransfoXLLMHeadModel(EngineModule):
         processor would.  It combines with `num_return_sequences`, padded prompts, `eos_token_id` / `min_length` /
         `max_new_tokens`; the prompts must obey the grammar themselves (MusicXLError otherwise).  That constraint is syntactic;
         `tokenizer.grammar(bar_budget=True)` adds the bar budget, under which every channel of every generated bar is also exactly
-        as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Beam, group-beam and contrastive search take no grammar."""
-        from .generate import (XLDecoder, XLDecoderLanes, beam_generate, check_grammar_args, contrastive_search, left_pad_counts,
-                               resolve_max_length, stop_config)
+        as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Beam, group-beam and contrastive search take no grammar.
+
+        `n_bars` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): length in bars.  An int, or a
+        sequence or tensor of one int per prompt (repeated per prompt under `num_return_sequences`); a negative entry leaves that
+        row unlimited.  A row with k >= 0 emits exactly k `<bar>` tokens: the bar that is open at the end of its prompt is
+        completed and not counted, so 0 means "finish the open bar and stop".  While the row may still open bars eos is barred,
+        once it has opened k a further `<bar>` is; under `tokenizer.grammar(bar_budget=True)` the row therefore emits eos exactly
+        when its k-th bar is full, and pad from then on.  Without a budget (`tokenizer.grammar()`, or a row with TimeSig_rare)
+        the rule still bars a further `<bar>` and an early eos but cannot force the stop: such a row may run to `max_length`.  A
+        row that reaches `max_length` first is cut there.  The count lives on the device beside the grammar state and moves in the
+        same sampler launch.  It combines with everything `grammar` combines with except `min_length` (ValueError)."""
+        from .generate import (XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, check_grammar_args, contrastive_search,
+                               left_pad_counts, resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -252,6 +262,10 @@ class MyTransfoXLLMHeadModel(EngineModule):
         if grammar is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
+        if n_bars is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
+            raise MusicXLError('n_bars= is supported for greedy decoding and sampling only, not for beam, group-beam or '
+                               'contrastive search')
+        n_bars = bar_count_config(n_bars, input_ids.shape[0], grammar, stop, num_return_sequences)
         if contrastive:
             dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
@@ -279,5 +293,5 @@ class MyTransfoXLLMHeadModel(EngineModule):
         dec.invalidate_tables()
         return dec.generate(input_ids.to(self.device), max_length, do_sample=do_sample, top_k=top_k, top_p=top_p,
                             temperature=temperature, repetition_penalty=repetition_penalty, typical_p=typical_p,
-                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device), grammar=grammar,
+                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device), grammar=grammar, n_bars=n_bars,
                             **({} if stop is None else dict(eos_token_id=stop[0], pad_token_id=stop[1], min_length=stop[2])))

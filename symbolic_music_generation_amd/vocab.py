@@ -174,7 +174,9 @@ class MusicVocabulary:
 
     def grammar(self, bar_budget: bool = False):
         """the token grammar of a well-formed song over this vocabulary (grammar.music_grammar), for `generate(grammar=...)`;
-        bar_budget=True: with the duration budget attached, so that every generated bar is as long as its time signature"""
+        bar_budget=True: with the duration budget attached, so that every generated bar is as long as its time signature.  Both
+        forms carry the bar count (`grammar.bar_count`) that `generate(..., n_bars=k)` runs under; only with the budget does a
+        row end exactly when its k-th bar is full"""
         from .grammar import music_grammar
         return music_grammar(self, bar_budget=bar_budget)
 
