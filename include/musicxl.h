@@ -238,7 +238,8 @@ int mxl_relattn_drd_phantom(const void* ws, const float* delta, float* d_rd, int
 /* upstream PositionalEmbedding + drop(pos_emb): out[dist][0:d/2]=sin, [d/2:d]=cos of min(dist,clamp)*inv_freq; (M,d) bf16 */
 int mxl_sinusoid_table(void* out, int M, int d, int clamp_len, float drop_p, unsigned long long seed, unsigned site,
                        void* stream);
-/* upstream AdaptiveEmbedding (div_val=1) + drop: out[n] = drop(E[ids[n]] * scale); ids int64, E (V,d) bf16 */
+/* upstream AdaptiveEmbedding (div_val=1) + drop: out[n] = drop(E[ids[n]] * scale); ids int64, E (V,d) bf16.
+ * An id outside [0, V) never indexes out of the table: the forward writes the row of id 0 for it, the backward adds nothing. */
 int mxl_embed_fwd(const void* ids, const void* E, void* out, int N, int d, int V, float scale, float drop_p,
                   unsigned long long seed, unsigned site, void* stream);
 /* its backward: dE[ids[n]] += keep * scale * (dout[n] + dout2[n])  (f32 atomics; dout2 may be NULL) */
