@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MXL_ABI_VERSION 1
+#define MXL_ABI_VERSION 2
 
 int mxl_abi_version(void);
 /* human-readable text for a negative libmusicxl code or a positive hipError_t */
@@ -427,107 +427,76 @@ int mxl_sample_large(const float* logprobs, int ldl, int V, void* ids, int ld_id
                      void* stream);
 /* t_dev += 1; rng_ctr += 1 */
 int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
-/* Round 6: mxl_sample + mxl_decode_embed of the sampled token + mxl_decode_advance in one launch -- the tail of one decode step and
- * the head of the next.  The row's workgroup writes ids[b][t + 1] and emb_out[b] = E[token] * scale (bf16, (B, d)); the workgroup
- * that finishes last advances *t_dev and *rng_ctr (counter: one int, zero before the first call, left zero).  `scores` (B, ldl) may
- * be log-probabilities or, when repetition_penalty == 1, the head's raw logits: argmax, top-k / top-p / typical-p and the
- * renormalised draw do not change under the per-row shift that separates the two.  V <= 2048. */
+/* ------------------------------------------------------------------------------------------------------------
+ * Rules of a generation.  Four optional groups of per-row state on the device, applied around every sampled token; three entries take
+ * them as the same flat argument list (below): mxl_sample_step, mxl_rules_mask, mxl_rules_advance.  A group is off when its state
+ * pointer is NULL: unfinished (with alive), gstate (with allow, next), gbar (with grem, slots, bars), gleft.  Within a group either
+ * every pointer is given or none; the budget and the count need `cls`; anything else is MXL_EINVAL.
+ *
+ * stop: eos_id, pad_id, min_length, unfinished, alive -- stopping at eos (HF greedy_search / sample with an eos_token_id).
+ *   unfinished (B,) int32 (1 = live; set to 1 before the first sampled token) and alive, one int32 = the number of live rows after
+ *   the launch.  Per row: next = live ? token : pad_id, then live &= (next != eos_id).  min_length (HF MinLengthLogitsProcessor,
+ *   after the repetition penalty): the score of eos_id is -inf while the row (columns 0..*t_dev) is shorter than min_length; 0 = off.
+ * grammar: cls, allow, next, C, gstate -- every row may only emit tokens that a token-class automaton allows in the row's state.
+ *   Tables: cls (V,) uint8 token -> class (C <= 32 classes); allow (S,) uint32, bit c set <=> class c may be emitted in state s
+ *   (S <= 256); next (S, C) uint8 successor state (entries of barred classes hold s itself).  gstate (B,) int32 is the state of
+ *   every row.  A barred token's score is -inf after the repetition penalty and min_length and before temperature / top-k / top-p /
+ *   typical-p (HF's logits-processor order), so the warpers and the renormalised draw see allowed tokens only.  The caller
+ *   guarantees that no reachable state bars every token.
+ * budget: slots, bars, opens, need_free, need_full, gbar, grem -- every channel of a generated bar is exactly as long as the row's
+ *   time signature.  Per row two int32 words: gbar (bar length in slots; 0 = the row is unconstrained) and grem (slots still free in
+ *   the open channel).  Tables: slots (V,) uint16, duration token -> slots, 0 = not a duration, 0xFFFF = a duration of unknown
+ *   length; bars (V,) uint16, time signature token -> bar length in slots (0 = unconstrained), 0xFFFF = not a time signature; class
+ *   bit masks opens (rem = bar), need_free (allowed only while rem > 0) and need_full (allowed only at rem == 0), over the classes of
+ *   `cls`.  In a row with bar > 0 a token is barred if its slots entry exceeds rem or its class is in need_free at rem == 0 or in
+ *   need_full at rem > 0; rows with bar == 0 are untouched.  A token moves the row: a bars entry sets bar (rem = 0), a class in opens
+ *   sets rem = bar, a slots entry k takes k from rem.  The rule never reads the grammar state.
+ * count: count, end, gleft -- a row opens exactly as many further bars as it was asked for.  Per row one int32 word: gleft, the bars
+ *   the row may still open; < 0 = no limit, the row is untouched.  count and end are class bit masks over the classes of `cls` (the
+ *   music grammar: <bar> and </s>).  A class in count is barred at gleft == 0, a class in end while gleft > 0, and a kept token of a
+ *   count class takes 1 from a positive gleft.  Under a bar budget the end class is thereby the only one left when the last bar is
+ *   full; without one the rule cannot force the end, it only bars a further bar and an early end.
+ *
+ * The words move along the token a row keeps, after the stop rule: a row that was finished before the step emits pad and keeps its
+ * words; the step in which a row emits eos still moves them.  Each row's words are read and written for that row alone.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* mxl_sample + mxl_decode_embed of the sampled token + mxl_decode_advance + the rules in one launch -- the tail of one decode step
+ * and the head of the next.  The row's workgroup writes ids[b][t + 1] and emb_out[b] = E[token] * scale (bf16, (B, d)), the token
+ * being the one after the stop rule (pad for a finished row); the workgroup that finishes last advances *t_dev and *rng_ctr and
+ * writes *alive (counter: one int, zero before the first call, left zero).  `scores` (B, ldl) may be log-probabilities or, when
+ * repetition_penalty == 1, the head's raw logits: argmax, top-k / top-p / typical-p and the renormalised draw do not change under the
+ * per-row shift that separates the two.  The masks are applied where the row enters LDS.  V <= 2048; with the stop group B <= 32767;
+ * the budget and the count need the grammar group here.  Without the stop group eos_id / pad_id / min_length are ignored. */
 int mxl_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
                     unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                    float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale, int* counter,
-                    void* stream);
-/* Stopping at eos (HF greedy_search / sample with an eos_token_id), for generation.  State on the device: unfinished (B,) int32
- * (1 = live; set to 1 before the first sampled token) and alive, one int32 = the number of live rows after the launch.
- * Per row: next = live ? token : pad_id, then live &= (next != eos_id).  min_length (HF MinLengthLogitsProcessor, after the
- * repetition penalty): the score of eos_id is -inf while the row (columns 0..*t_dev) is shorter than min_length; 0 = off.
- * mxl_sample_step_stop: mxl_sample_step plus that state in the same launch (B <= 32767); the last workgroup to finish writes
- * *alive.  The embedding row written is that of the token after the rule (pad for a finished row). */
-int mxl_sample_step_stop(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                         unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                         float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale, int* counter,
-                         int eos_id, int pad_id, int min_length, int* unfinished, int* alive, void* stream);
-/* The same state for mxl_sample / mxl_sample_large: mxl_decode_stop runs after the sampler and mxl_decode_advance (the token just
- * written is ids[b][*t_dev]) and applies the rule to it; mxl_mask_eos_below runs before the sampler and sets
- * scores[b][eos_id] = -inf for every row while *t_dev + 1 < min_length (no launch when min_length <= 0). */
-int mxl_decode_stop(void* ids, int ld_ids, const int* t_dev, int B, int eos_id, int pad_id, int* unfinished, int* alive,
-                    void* stream);
-int mxl_mask_eos_below(float* scores, int ldl, int B, int V, int eos_id, int min_length, const int* t_dev, void* stream);
-/* Grammar-constrained decoding: every row may only emit tokens that a token-class automaton allows in the row's state.
- * Tables (device): cls (V,) uint8 token -> class (C <= 32 classes); allow (S,) uint32, bit c set <=> class c may be emitted in
- * state s (S <= 256); next (S, C) uint8 successor state (entries of barred classes hold s itself).  gstate (B,) int32 is the state
- * of every row, kept and advanced on the device.  A barred token's score is -inf after the repetition penalty and min_length and
- * before temperature / top-k / top-p / typical-p (HF's logits-processor order), so the warpers and the renormalised draw see
- * allowed tokens only.  The caller guarantees that no reachable state bars every token.
- * mxl_sample_step_grammar: mxl_sample_step_stop with the mask applied where the row enters LDS and gstate[b] moved along the token
- * the row keeps, in the same launch.  unfinished = alive = NULL: no eos rule (eos_id / pad_id / min_length ignored).  With the eos
- * rule the state moves after it: a row that was finished before the step emits pad and keeps its state; the step in which a row
- * emits eos still moves it. */
-int mxl_sample_step_grammar(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                            unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                            float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                            int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
-                            const void* allow, const void* next, int C, int* gstate, void* stream);
-/* The same around mxl_sample / mxl_sample_large.  mxl_grammar_mask: scores[b][v] = -inf in place wherever allow[gstate[b]] bars
- * cls[v] (one thread per score), before the sampler -- whose repetition penalty leaves -inf at -inf, so the result is that of
- * masking after the penalty.  mxl_grammar_advance: after the sampler and mxl_decode_advance and BEFORE mxl_decode_stop of the same
- * step: gstate[b] moves along ids[b][*t_dev]; rows with unfinished[b] == 0 (optional; finished before this step) keep theirs. */
-int mxl_grammar_mask(float* scores, int ldl, int B, int V, const void* cls, const void* allow, const int* gstate, void* stream);
-int mxl_grammar_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, const void* next, int C,
-                        int* gstate, const int* unfinished, void* stream);
-/* State of every row after its prompt: ids (B, ld_ids) int64, columns 0..Tp-1 walked from `start`; a column holding an id < 0 is
- * skipped (left pad).  first_bad[b] = column of the first token the state bars (or an id >= V), where the walk of that row stops;
+                    float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                    int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
+                    const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
+                    unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
+                    int* gleft, void* stream);
+/* The same rules around mxl_sample / mxl_sample_large, one launch on either side.  mxl_rules_mask, before the sampler:
+ * scores[b][v] = -inf in place wherever an enabled group bars token v, one thread per score, every other score untouched (the
+ * sampler's repetition penalty leaves -inf at -inf, so the result is that of masking after the penalty).  It reads no stop state:
+ * eos_id is barred while *t_dev + 1 < min_length whenever min_length > 0.  No launch when nothing can be barred.
+ * mxl_rules_advance, after the sampler and mxl_decode_advance (the token just written is ids[b][*t_dev]): every row that chose its
+ * token moves its words along it, then the stop rule is applied to the token and *alive written.  No launch when every group is off. */
+int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length, int* unfinished,
+                   int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate, const void* slots,
+                   const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count,
+                   unsigned end, int* gleft, void* stream);
+int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length, int* unfinished,
+                      int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate, const void* slots,
+                      const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count,
+                      unsigned end, int* gleft, void* stream);
+/* Grammar state of every row after its prompt: ids (B, ld_ids) int64, columns 0..Tp-1 walked from `start`; a column holding an id < 0
+ * is skipped (left pad).  first_bad[b] = column of the first token the state bars (or an id >= V), where the walk of that row stops;
  * -1 = the prompt obeys the grammar. */
 int mxl_grammar_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* allow, const void* next, int C,
                      int start, int* gstate, int* first_bad, void* stream);
-/* Bar budget on top of the grammar: every channel of a generated bar is exactly as long as the row's time signature.  Per row two
- * int32 words kept on the device: gbar (bar length in slots; 0 = the row is unconstrained) and grem (slots still free in the open
- * channel).  Tables (device): slots (V,) uint16, duration token -> slots, 0 = not a duration, 0xFFFF = a duration of unknown length;
- * bars (V,) uint16, time signature token -> bar length in slots (0 = unconstrained), 0xFFFF = not a time signature; class bit masks
- * opens (rem = bar), need_free (allowed only while rem > 0) and need_full (allowed only at rem == 0), over the classes of `cls`.
- * In a row with bar > 0 a token is barred if its slots entry exceeds rem or its class is in need_free at rem == 0 or in need_full
- * at rem > 0; rows with bar == 0 are untouched.  A token moves the row: a bars entry sets bar (rem = 0), a class in opens sets
- * rem = bar, a slots entry k takes k from rem.  The rule never reads the grammar state.
- * mxl_sample_step_budget: mxl_sample_step_grammar with the budget mask applied together with the grammar mask where the row enters
- * LDS, and (gbar[b], grem[b]) moved where gstate[b] moves (after the eos rule; a row finished before the step keeps them).  Row b's
- * workgroup is the only one that touches its words: no ordering between workgroups is needed for them. */
-int mxl_sample_step_budget(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                           unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                           float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                           int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
-                           const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
-                           unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, void* stream);
-/* The same around mxl_sample / mxl_sample_large: mxl_budget_mask after mxl_grammar_mask (in place, one thread per score),
- * mxl_budget_advance beside mxl_grammar_advance, before mxl_decode_stop of the same step. */
-int mxl_budget_mask(float* scores, int ldl, int B, int V, const void* cls, const void* slots, unsigned need_free,
-                    unsigned need_full, const int* gbar, const int* grem, void* stream);
-int mxl_budget_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, const void* slots,
-                       const void* bars, unsigned opens, int* gbar, int* grem, const int* unfinished, void* stream);
 /* (gbar, grem) of every row after its prompt, from (0, 0): columns 0..Tp-1, ids < 0 (left pads) and ids >= V (mxl_grammar_scan
  * reports those) skipped.  first_bad[b] = column of the first token the budget bars, where the walk of that row stops; -1 = none. */
 int mxl_budget_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* slots, const void* bars,
                     unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, int* first_bad, void* stream);
-/* Bar count on top of the grammar: a row opens exactly as many further bars as it was asked for.  Per row one more int32 word kept on
- * the device: gleft, the bars the row may still open; < 0 = no limit, the row is untouched.  count and end are class bit masks over the
- * classes of `cls` (the music grammar: <bar> and </s>).  A class in count is barred at gleft == 0, a class in end while gleft > 0, and a
- * kept token of a count class takes 1 from a positive gleft.  Under a bar budget the end class is thereby the only one left when the
- * last bar is full; without one the rule cannot force the end, it only bars a further bar and an early end.
- * mxl_sample_step_bars: mxl_sample_step_grammar (slots = bars = gbar = grem = NULL) or mxl_sample_step_budget with that mask folded
- * into the same allow word, and gleft[b] moved where gstate[b] moves (after the eos rule; a row finished before the step keeps it).
- * Row b's workgroup is the only one that touches gleft[b]. */
-int mxl_sample_step_bars(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                         unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                         float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                         int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
-                         const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
-                         unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
-                         int* gleft, void* stream);
-/* The same around mxl_sample / mxl_sample_large: mxl_barcount_mask after mxl_grammar_mask and mxl_budget_mask (in place, one thread
- * per score), mxl_barcount_advance beside mxl_grammar_advance and mxl_budget_advance, before mxl_decode_stop of the same step
- * (unfinished: optional, rows with unfinished[b] == 0 keep their word). */
-int mxl_barcount_mask(float* scores, int ldl, int B, int V, const void* cls, unsigned count, unsigned end, const int* gleft,
-                      void* stream);
-int mxl_barcount_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, unsigned count, int* gleft,
-                         const int* unfinished, void* stream);
 /* Contrastive search (the reference's 'contrastive' strategy, musicnlp/trainer/eval.py:296-302, over the mems patch of
  * musicnlp/models/transformer_xl.py:229-234; HF 4.25.1 GenerationMixin.contrastive_search with `_ranking_fast`):
  *   score[b*K + k] = (1 - alpha) * probs[b*K + k] - alpha * max_{s < S} cos(hid[b*K + k], ctx[b][s]);  sel[b] = argmax_k score

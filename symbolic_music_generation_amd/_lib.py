@@ -62,7 +62,7 @@ def lib():
             fn = getattr(_lib, name)  # AttributeError if the header declares something the .so lacks
             fn.restype = restype
             fn.argtypes = argtypes
-        if _lib.mxl_abi_version() != 1:
+        if _lib.mxl_abi_version() != 2:
             raise MusicXLError('libmusicxl ABI version mismatch')
     return _lib
 

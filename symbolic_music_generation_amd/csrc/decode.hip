@@ -359,13 +359,18 @@ __global__ __launch_bounds__(256) void decode_bd_kernel(const bf16_t* qr, const 
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int SORT_N = 2048;
 
+// token v under a row's allow word (rules_load below) and, with the bar budget, the slots the row still has free
+__device__ __forceinline__ bool token_allowed(const unsigned char* cls, uint32_t allow, const unsigned short* slots, int remcap,
+                                              long long v, bool bud) {
+    return ((allow >> cls[v]) & 1u) && (!bud || (int)slots[v] <= remcap);
+}
+
 // the row's next token (returned to every thread of the workgroup).
-// G: grammar-constrained (mxl_sample_step_grammar) -- a token whose class bit is clear in `gallow` (the allow mask of the row's
-// grammar state) is -inf from the moment the row enters LDS and is never rewritten by the repetition penalty, which is HF's
+// G: under class rules -- a token that `gallow` (the row's allow word: its grammar state's mask less what the budget and the count
+// bar) does not admit is -inf from the moment the row enters LDS and is never rewritten by the repetition penalty, which is HF's
 // processor order "penalty, min_length, grammar, then the warpers": every warper and the renormalisation see allowed tokens only.
-// BUD (with G): the bar budget on top (mxl_sample_step_budget) -- the caller has already cleared from `gallow` the classes the row's
-// (bar, rem) bars, and a token whose `bslots` entry exceeds `remcap` (the slots still free; 0xFFFF in an unconstrained row, which
-// admits every entry) is -inf in the same place.
+// BUD (with G): a token whose `bslots` entry exceeds `remcap` (the slots still free; 0xFFFF in an unconstrained row, which admits
+// every entry) is -inf in the same place.
 template <bool G = false, bool BUD = false>
 __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, const long long* ids, int ld_ids,
                                           const int* t_dev, const unsigned long long* rng_ctr, unsigned long long seed,
@@ -380,7 +385,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
     const float* row = logp + (size_t)b * ldl;
     const float invt = 1.f / temperature;
     for (int i = tid; i < SORT_N; i += 256) {
-        if (G) key[i] = (i < V && ((gallow >> gcls[i]) & 1u) && (!BUD || (int)bslots[i] <= remcap)) ? row[i] * invt : -INFINITY;
+        if (G) key[i] = (i < V && token_allowed(gcls, gallow, bslots, remcap, i, BUD)) ? row[i] * invt : -INFINITY;
         else key[i] = i < V ? row[i] * invt : -INFINITY;
         idx[i] = i;
     }
@@ -393,7 +398,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
         const long long* hist = ids + (size_t)b * ld_ids;
         for (int j = tid; j <= tcur; j += 256) {
             const long long tok = hist[j];
-            if (tok >= 0 && tok < V && (!G || (((gallow >> gcls[tok]) & 1u) && (!BUD || (int)bslots[tok] <= remcap)))) {
+            if (tok >= 0 && tok < V && (!G || token_allowed(gcls, gallow, bslots, remcap, tok, BUD))) {
                 const float v = row[tok];
                 key[tok] = (v < 0.f ? v * repetition_penalty : v / repetition_penalty) * invt;
             }
@@ -573,20 +578,38 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Bar budget on top of the grammar (grammar.BarBudget): per row `bar` (bar length in slots, 0 = unconstrained) and `rem` (slots
-// still free in the open channel).  slots (V,) uint16: duration token -> slots, 0 = no duration, 0xFFFF = unknown length; bars (V,)
-// uint16: time signature token -> bar length, 0xFFFF = no time signature; opens / need_free / need_full: class bit masks.  The rule
-// reads the token's class and the two integers only, never the automaton state.
+// The rules of one generation (include/musicxl.h, "Rules of a generation"), passed to kernels by value.  Four groups, each off when
+// its state pointer (unfinished / gstate / gbar / gleft) is NULL; the budget and the count read the token classes `cls` of the
+// grammar group and nothing else of it.
+//   stop     HF greedy_search / sample: a finished row emits pad, a live row that emits eos is finished; eos barred below min_length
+//   grammar  a token class automaton: cls (V,) token -> class, allow (S,) bit c = class c may follow in state s, next (S, C) successor
+//   budget   grammar.BarBudget: per row `bar` (bar length in slots, 0 = unconstrained) and `rem` (slots still free in the open
+//            channel).  slots (V,) uint16: duration token -> slots, 0 = no duration, 0xFFFF = unknown length; bars (V,) uint16: time
+//            signature token -> bar length, 0xFFFF = no time signature; opens / need_free / need_full: class bit masks
+//   count    grammar.BarCount: per row `left`, the bars the row may still open (< 0 = no limit, the row is untouched).  A class in
+//            `count` (<bar>) is barred at left == 0, a class in `end` (</s>) while left > 0, and a kept token of a `count` class
+//            takes 1 from a positive left
+// The next rule is one more group here, one line in each of rules_load / rules_move and one in make_rules.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int BUDGET_NONE = 0xFFFF;          // slots: unknown length (beyond any rem); bars: not a time signature
-
-struct BudgetArgs {
+struct DecodeRules {
+    int eos_id, pad_id, min_length;
+    int* unfinished;
+    int* alive;
+    const unsigned char* cls;
+    const uint32_t* allow;
+    const unsigned char* next;
+    int C;
+    int* gstate;
     const unsigned short* slots;
     const unsigned short* bars;
     uint32_t opens, need_free, need_full;
     int* gbar;
     int* grem;
+    uint32_t count, end;
+    int* gleft;
 };
+
+constexpr int BUDGET_NONE = 0xFFFF;          // slots: unknown length (beyond any rem); bars: not a time signature
 
 // classes a row at (bar, rem) bars: the closers while slots are free, the note starters once none is
 __device__ __forceinline__ uint32_t budget_deny(int bar, int rem, uint32_t need_free, uint32_t need_full) {
@@ -600,18 +623,6 @@ __device__ __forceinline__ void budget_move(int& bar, int& rem, int c, int k, in
     if ((opens >> c) & 1u) rem = bar;
     if (bar > 0 && k != BUDGET_NONE) rem = max(rem - k, 0);
 }
-
-// ---------------------------------------------------------------------------------------------------------------
-// Bar count on top of the grammar (grammar.BarCount): per row `left`, the bars the row may still open (< 0 = no limit, the row is
-// untouched).  count / end: class bit masks.  A class in `count` (<bar>) is barred at left == 0, a class in `end` (</s>) while
-// left > 0, and a kept token of a `count` class takes 1 from a positive left.  Like the budget the rule reads the token's class and
-// the row's integer only.
-// ---------------------------------------------------------------------------------------------------------------
-struct CountArgs {
-    uint32_t count, end;
-    int* gleft;
-};
-
 // classes a row with `left` bars to go bars: the end while bars are owed, another bar once none is
 __device__ __forceinline__ uint32_t barcount_deny(int left, uint32_t count, uint32_t end) {
     return left > 0 ? end : (left == 0 ? count : 0u);
@@ -621,11 +632,38 @@ __device__ __forceinline__ int barcount_move(int left, int c, uint32_t count) {
     return (left > 0 && ((count >> c) & 1u)) ? left - 1 : left;
 }
 
-// the trailing arguments of sample_step_kernel, in the order (BudgetArgs, CountArgs), each present or not
-__device__ __forceinline__ void step_extras(BudgetArgs&, CountArgs&) {}
-__device__ __forceinline__ void step_extras(BudgetArgs& b, CountArgs&, const BudgetArgs& x) { b = x; }
-__device__ __forceinline__ void step_extras(BudgetArgs&, CountArgs& c, const CountArgs& y) { c = y; }
-__device__ __forceinline__ void step_extras(BudgetArgs& b, CountArgs& c, const BudgetArgs& x, const CountArgs& y) { b = x; c = y; }
+// The words of row b and what they admit: `allow` has a bit per class the row may emit (every bit without a grammar), `remcap` is
+// the largest slots entry.  g / bud / cnt: which groups are on -- compile-time constants in the fused kernel, pointer tests in the
+// unfused pair; everything here inlines and folds on them.
+struct RowWords {
+    int gs, bar, rem, left;
+    uint32_t allow;
+    int remcap;
+};
+__device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool g, bool bud, bool cnt) {
+    RowWords w{0, 0, 0, -1, ~0u, BUDGET_NONE};
+    if (g) { w.gs = r.gstate[b]; w.allow = r.allow[w.gs]; }
+    if (bud) {
+        w.bar = r.gbar[b];
+        w.rem = r.grem[b];
+        w.allow &= ~budget_deny(w.bar, w.rem, r.need_free, r.need_full);
+        w.remcap = budget_remcap(w.bar, w.rem);
+    }
+    if (cnt) { w.left = r.gleft[b]; w.allow &= ~barcount_deny(w.left, r.count, r.end); }
+    return w;
+}
+// row b moves along `tok`, a token of the vocabulary that the row chose itself (a row finished before the step emits pad, which is
+// not its choice and need not be a token its state allows: such a row keeps its words)
+__device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int b, long long tok, bool g, bool bud, bool cnt) {
+    const int c = r.cls[tok];
+    if (g) r.gstate[b] = r.next[w.gs * r.C + c];
+    if (bud) {
+        budget_move(w.bar, w.rem, c, r.slots[tok], r.bars[tok], r.opens);
+        r.gbar[b] = w.bar;
+        r.grem[b] = w.rem;
+    }
+    if (cnt) r.gleft[b] = barcount_move(w.left, c, r.count);
+}
 
 __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl, int V, long long* ids, int ld_ids,
                                                      const int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
@@ -642,47 +680,25 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl,
 // head's raw logits instead of log-probabilities when no repetition penalty is in force: every other warper, the argmax and the
 // renormalised draw are invariant under the per-row shift log-softmax applies.
 //
-// G (mxl_sample_step_grammar): the row's grammar state gstate[b] selects the allow mask the sampler applies, and thread 0 moves the
-// state along the token the row keeps.  The move sits AFTER the eos rule: a row that was finished before this step emits pad and
-// its state stays frozen (the pad is not the row's choice and need not be a token the state allows); the step in which a live row
-// emits eos still moves it, so a finished row of the music grammar rests in END.
-//
-// BUD (mxl_sample_step_budget, with G): the row's (gbar[b], grem[b]) narrow that mask further (budget_deny, budget_remcap), and
-// thread 0 moves them in the same place and under the same condition as the grammar state.  gbar / grem are per-row words: row b's
-// workgroup is their only reader and writer within a launch, and the next launch on the stream sees them by stream order -- there is
-// no hand-off between workgroups here beyond the arrival counter below.
-// It is a compile-time variant: `budget` is one trailing BudgetArgs kernel argument that only the BUD instantiation has, so the
-// kernels behind mxl_sample_step, _stop and _grammar keep their arguments and their code.
-//
-// CNT (mxl_sample_step_bars, with G, with or without BUD): the row's gleft[b] (bars it may still open) clears `count` or `end`
-// classes from the same allow word (barcount_deny), and thread 0 moves it where gstate[b] moves.  The same kind of variant: one
-// more trailing argument, a CountArgs after the BudgetArgs if there is one, that only the CNT instantiations have.  gleft is a
-// per-row word like gbar / grem: row b's workgroup alone reads and writes it.
-template <bool G, bool BUD = false, bool CNT = false, typename... BA>
+// G / BUD / CNT: the grammar, budget and count groups of `r` as compile-time variants (BUD and CNT ride on G); the stop group is
+// the runtime test of r.unfinished it has always been.  The row's words select the allow word and remcap the sampler applies
+// (rules_load), and thread 0 moves them along the token the row keeps (rules_move).  The move sits AFTER the eos rule: a row that
+// was finished before this step emits pad and its words stay frozen; the step in which a live row emits eos still moves them, so a
+// finished row of the music grammar rests in END.  The words are per-row: row b's workgroup is their only reader and writer within a
+// launch, and the next launch on the stream sees them by stream order -- there is no hand-off between workgroups here beyond the
+// arrival counter below.
+template <bool G, bool BUD, bool CNT>
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, int ldl, int V, long long* ids, int ld_ids,
                                                           int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                           int do_sample, int top_k, float top_p, float temperature,
                                                           float repetition_penalty, float typical_p, const bf16_t* E, bf16_t* emb_out,
-                                                          int d, float scale, int* counter, int eos_id, int pad_id,
-                                                          int min_length, int* unfinished, int* alive,
-                                                          const unsigned char* gcls = nullptr, const uint32_t* gallow = nullptr,
-                                                          const unsigned char* gnext = nullptr, int C = 0, int* gstate = nullptr,
-                                                          BA... extras) {
-    static_assert(sizeof...(BA) == (BUD ? 1 : 0) + (CNT ? 1 : 0) && (G || !(BUD || CNT)),
-                  "the bar budget and the bar count ride on the grammar: one BudgetArgs and / or one CountArgs argument");
-    const int gs = G ? gstate[blockIdx.x] : 0;
-    BudgetArgs bud{};
-    CountArgs cnt{};
-    step_extras(bud, cnt, extras...);
-    int bbar = 0, brem = 0, left = -1;
-    if (BUD) { bbar = bud.gbar[blockIdx.x]; brem = bud.grem[blockIdx.x]; }
-    if (CNT) left = cnt.gleft[blockIdx.x];
-    uint32_t allow = G ? gallow[gs] : 0u;
-    if (BUD) allow &= ~budget_deny(bbar, brem, bud.need_free, bud.need_full);
-    if (CNT) allow &= ~barcount_deny(left, cnt.count, cnt.end);
+                                                          int d, float scale, int* counter, DecodeRules r) {
+    static_assert(G || !(BUD || CNT), "the bar budget and the bar count ride on the grammar");
+    int* const unfinished = r.unfinished;
+    const RowWords w = rules_load(r, blockIdx.x, G, BUD, CNT);
     int tok = sample_row<G, BUD>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
-                                 repetition_penalty, typical_p, nullptr, unfinished ? eos_id : -1, unfinished ? min_length : 0,
-                                 gcls, allow, BUD ? bud.slots : nullptr, BUD ? budget_remcap(bbar, brem) : 0);
+                                 repetition_penalty, typical_p, nullptr, unfinished ? r.eos_id : -1, unfinished ? r.min_length : 0,
+                                 r.cls, w.allow, r.slots, w.remcap);
     const int b = blockIdx.x, tid = threadIdx.x;
     __shared__ int sh_tok, sh_live;
     bool was_live = true;                       // (thread 0) the token is the row's own choice
@@ -692,8 +708,8 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
             int live = unfinished[b];
             int tk = tok;
             was_live = live != 0;
-            if (!live) tk = pad_id;
-            else if (tk == eos_id) live = 0;
+            if (!live) tk = r.pad_id;
+            else if (tk == r.eos_id) live = 0;
             unfinished[b] = live;
             sh_tok = tk;
             sh_live = live;
@@ -701,13 +717,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         __syncthreads();
         tok = sh_tok;
     }
-    if (G && tid == 0 && was_live && tok >= 0 && tok < V) gstate[b] = gnext[gs * C + gcls[tok]];
-    if (BUD && tid == 0 && was_live && tok >= 0 && tok < V) {
-        budget_move(bbar, brem, gcls[tok], bud.slots[tok], bud.bars[tok], bud.opens);
-        bud.gbar[b] = bbar;
-        bud.grem[b] = brem;
-    }
-    if (CNT && tid == 0 && was_live && tok >= 0 && tok < V) cnt.gleft[b] = barcount_move(left, gcls[tok], cnt.count);
+    if (G && tid == 0 && was_live && tok >= 0 && tok < V) rules_move(r, w, b, tok, G, BUD, CNT);
     if (tid == 0) ids[(size_t)b * ld_ids + *t_dev + 1] = tok;
     const int id = (tok < 0 || tok >= V) ? 0 : tok;
     for (int c = tid; c < (d >> 3); c += 256) {
@@ -725,7 +735,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         const int old = __hip_atomic_fetch_add(counter, 1 + (sh_live << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((old & 0xffff) == (int)gridDim.x - 1) {
             __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *alive = (old >> 16) + sh_live;
+            *r.alive = (old >> 16) + sh_live;
             *t_dev += 1;
             *rng_ctr += 1;
         }
@@ -744,60 +754,54 @@ __global__ void advance_kernel(int* t_dev, unsigned long long* rng_ctr) {
     *rng_ctr += 1;
 }
 
-// stop state after mxl_sample / mxl_sample_large and the counter advance (the unfused and large-vocabulary paths): the token
-// just written sits at column *t_dev.  One workgroup walks the rows and writes the number of live rows to *alive.
-__global__ __launch_bounds__(256) void decode_stop_kernel(long long* ids, int ld_ids, const int* t_dev, int B, int eos_id,
-                                                          int pad_id, int* unfinished, int* alive) {
+// ---------------------------------------------------------------------------------------------------------------
+// The same rules around the samplers that do not carry them (mxl_sample, mxl_sample_large: the unfused, large-vocabulary and
+// Reformer paths): one launch before the sampler and one after it and the counter advance.
+// ---------------------------------------------------------------------------------------------------------------
+// before the sampler: -inf on every token that an enabled group bars, eos below min_length (rows hold columns 0..*t_dev) included;
+// one thread per score, every other score untouched.  The sampler's repetition penalty leaves -inf at -inf, so the result is that of
+// masking after the penalty.
+__global__ __launch_bounds__(256) void rules_mask_kernel(float* scores, int ldl, int B, int V, const int* t_dev, DecodeRules r) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * V) return;
+    const int b = (int)(i / V), v = (int)(i - (long long)b * V);
+    const bool bud = r.gbar != nullptr;
+    bool ok = true;
+    if (r.cls) {
+        const RowWords w = rules_load(r, b, r.gstate != nullptr, bud, r.gleft != nullptr);
+        ok = token_allowed(r.cls, w.allow, r.slots, w.remcap, v, bud);
+    }
+    if (r.min_length > 0 && v == r.eos_id && *t_dev + 1 < r.min_length) ok = false;
+    if (!ok) scores[(size_t)b * ldl + v] = -INFINITY;
+}
+
+// after the sampler and the counter advance: the token just written sits at column *t_dev.  One workgroup walks the rows: a row that
+// chose its token (live before the step, or no stop group) moves its words along it, then the stop rule is applied to the token --
+// `unfinished` still tells which rows were live when they chose it -- and the number of live rows goes to *alive.
+__global__ __launch_bounds__(256) void rules_advance_kernel(long long* ids, int ld_ids, const int* t_dev, int B, int V, DecodeRules r) {
     __shared__ int part[4];
     const int tid = threadIdx.x;
     const int t = *t_dev;
+    const bool g = r.gstate != nullptr, bud = r.gbar != nullptr, cnt = r.gleft != nullptr;
     int n = 0;
     for (int b = tid; b < B; b += 256) {
         long long* p = ids + (size_t)b * ld_ids + t;
-        int live = unfinished[b];
-        if (!live) *p = pad_id;
-        else if (*p == eos_id) live = 0;
-        unfinished[b] = live;
-        n += live;
+        const long long tok = *p;
+        int live = r.unfinished ? r.unfinished[b] : 1;
+        if (live && r.cls && tok >= 0 && tok < V) rules_move(r, rules_load(r, b, g, bud, cnt), b, tok, g, bud, cnt);
+        if (r.unfinished) {
+            if (!live) *p = r.pad_id;
+            else if (tok == r.eos_id) live = 0;
+            r.unfinished[b] = live;
+            n += live;
+        }
     }
+    if (!r.unfinished) return;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
     if ((tid & 63) == 0) part[tid >> 6] = n;
     __syncthreads();
-    if (tid == 0) *alive = part[0] + part[1] + part[2] + part[3];
-}
-
-// min_length before mxl_sample / mxl_sample_large: eos barred while the rows (columns 0..*t_dev) are shorter than min_length
-__global__ __launch_bounds__(256) void mask_eos_below_kernel(float* scores, int ldl, int B, int eos_id, int min_length,
-                                                             const int* t_dev) {
-    if (*t_dev + 1 >= min_length) return;
-    for (int b = threadIdx.x; b < B; b += 256) scores[(size_t)b * ldl + eos_id] = -INFINITY;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Grammar-constrained decoding around the samplers that do not carry it themselves (mxl_sample, mxl_sample_large): a token class
-// automaton, cls (V,) token -> class, allow (S,) bit c = class c may follow in state s, next (S, C) successor.
-// ---------------------------------------------------------------------------------------------------------------
-// before the sampler: -inf on every token the row's state bars; one thread per score
-__global__ __launch_bounds__(256) void grammar_mask_kernel(float* scores, int ldl, int B, int V, const unsigned char* cls,
-                                                           const uint32_t* allow, const int* gstate) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)B * V) return;
-    const int b = (int)(i / V), v = (int)(i - (long long)b * V);
-    if (!((allow[gstate[b]] >> cls[v]) & 1u)) scores[(size_t)b * ldl + v] = -INFINITY;
-}
-
-// after the sampler and the counter advance, BEFORE the stop rule of this step (mxl_decode_stop): the token just written sits at
-// column *t_dev; `unfinished` (optional) still holds which rows were live when they chose it -- the others stay frozen
-__global__ __launch_bounds__(256) void grammar_advance_kernel(const long long* ids, int ld_ids, const int* t_dev, int B, int V,
-                                                              const unsigned char* cls, const unsigned char* next, int C,
-                                                              int* gstate, const int* unfinished) {
-    const int t = *t_dev;
-    for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) {
-        if (unfinished && !unfinished[b]) continue;
-        const long long tok = ids[(size_t)b * ld_ids + t];
-        if (tok >= 0 && tok < V) gstate[b] = next[gstate[b] * C + cls[tok]];
-    }
+    if (tid == 0) *r.alive = part[0] + part[1] + part[2] + part[3];
 }
 
 // state of every row after its prompt.  One wave per row: the lanes load 64 columns at a time and their classes, then every lane
@@ -827,58 +831,6 @@ __global__ __launch_bounds__(64) void grammar_scan_kernel(const long long* ids, 
         }
     }
     if (lane == 0) { gstate[b] = s; first_bad[b] = bad; }
-}
-
-// The bar budget around the same samplers.  After mxl_grammar_mask: -inf on every token the row's (bar, rem) bars; one thread per
-// score (the order of the two masks does not matter to the result: each only writes -inf).
-__global__ __launch_bounds__(256) void budget_mask_kernel(float* scores, int ldl, int B, int V, const unsigned char* cls,
-                                                          const unsigned short* slots, uint32_t need_free, uint32_t need_full,
-                                                          const int* gbar, const int* grem) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)B * V) return;
-    const int b = (int)(i / V), v = (int)(i - (long long)b * V);
-    const int bar = gbar[b], rem = grem[b];
-    if (((budget_deny(bar, rem, need_free, need_full) >> cls[v]) & 1u) || (int)slots[v] > budget_remcap(bar, rem))
-        scores[(size_t)b * ldl + v] = -INFINITY;
-}
-
-// beside mxl_grammar_advance (before the stop rule of the step): (bar, rem) of every row that chose its token move along it
-__global__ __launch_bounds__(256) void budget_advance_kernel(const long long* ids, int ld_ids, const int* t_dev, int B, int V,
-                                                             const unsigned char* cls, const unsigned short* slots,
-                                                             const unsigned short* bars, uint32_t opens, int* gbar, int* grem,
-                                                             const int* unfinished) {
-    const int t = *t_dev;
-    for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) {
-        if (unfinished && !unfinished[b]) continue;
-        const long long tok = ids[(size_t)b * ld_ids + t];
-        if (tok < 0 || tok >= V) continue;
-        int bar = gbar[b], rem = grem[b];
-        budget_move(bar, rem, cls[tok], slots[tok], bars[tok], opens);
-        gbar[b] = bar;
-        grem[b] = rem;
-    }
-}
-
-// The bar count around the same samplers.  After mxl_grammar_mask and mxl_budget_mask: -inf on every token whose class the row's
-// `left` bars; one thread per score.
-__global__ __launch_bounds__(256) void barcount_mask_kernel(float* scores, int ldl, int B, int V, const unsigned char* cls,
-                                                            uint32_t count, uint32_t end, const int* gleft) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long long)B * V) return;
-    const int b = (int)(i / V), v = (int)(i - (long long)b * V);
-    if ((barcount_deny(gleft[b], count, end) >> cls[v]) & 1u) scores[(size_t)b * ldl + v] = -INFINITY;
-}
-
-// beside mxl_grammar_advance and mxl_budget_advance (before the stop rule of the step): `left` of every row that chose its token
-__global__ __launch_bounds__(256) void barcount_advance_kernel(const long long* ids, int ld_ids, const int* t_dev, int B, int V,
-                                                               const unsigned char* cls, uint32_t count, int* gleft,
-                                                               const int* unfinished) {
-    const int t = *t_dev;
-    for (int b = blockIdx.x * 256 + threadIdx.x; b < B; b += gridDim.x * 256) {
-        if (unfinished && !unfinished[b]) continue;
-        const long long tok = ids[(size_t)b * ld_ids + t];
-        if (tok >= 0 && tok < V) gleft[b] = barcount_move(gleft[b], cls[tok], count);
-    }
 }
 
 // (bar, rem) of every row after its prompt, as grammar_scan_kernel: one wave per row, 64 columns at a time, the walk uniform over
@@ -1030,191 +982,84 @@ extern "C" int mxl_sample(const float* logprobs, int ldl, int V, void* ids, int 
     return MXL_OK;
 }
 
+// the flat rules arguments of the three entries that take them (include/musicxl.h), in the header's order
+#define RULES_PARAMS                                                                                                              \
+    int eos_id, int pad_id, int min_length, int *unfinished, int *alive, const void *cls, const void *allow, const void *next, int C, \
+        int *gstate, const void *slots, const void *bars, unsigned opens, unsigned need_free, unsigned need_full, int *gbar,        \
+        int *grem, unsigned count, unsigned end, int *gleft
+#define RULES_ARGS \
+    eos_id, pad_id, min_length, unfinished, alive, cls, allow, next, C, gstate, slots, bars, opens, need_free, need_full, gbar, grem, count, end, gleft
+
+// the one check of those arguments, before any launch: within a group all pointers or none; budget and count read `cls`.
+// fused: the launch that also samples -- budget and count ride on the grammar there, and arrivals and live rows share one 32-bit word
+static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS) {
+    MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr));
+    MXL_CHECK_ARG((allow == nullptr) == (gstate == nullptr) && (next == nullptr) == (gstate == nullptr));
+    MXL_CHECK_ARG(!gstate || (cls && C >= 1 && C <= 32));
+    MXL_CHECK_ARG((slots == nullptr) == (gbar == nullptr) && (bars == nullptr) == (gbar == nullptr) && (grem == nullptr) == (gbar == nullptr));
+    MXL_CHECK_ARG(!(gbar || gleft) || cls);
+    if (fused) MXL_CHECK_ARG(!(gbar || gleft) || gstate);
+    if (fused && unfinished) MXL_CHECK_ARG(B <= 32767);
+    if (!unfinished && fused) { eos_id = -1; pad_id = 0; min_length = 0; }
+    *r = DecodeRules{eos_id, pad_id, min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
+                     (const unsigned char*)next, C, gstate, (const unsigned short*)slots, (const unsigned short*)bars, opens, need_free,
+                     need_full, gbar, grem, count, end, gleft};
+    return MXL_OK;
+}
+
 extern "C" int mxl_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
                                unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                                float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                               int* counter, void* stream) {
+                               int* counter, RULES_PARAMS, void* stream) {
     MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
     MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
     MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
-    hipLaunchKernelGGL(sample_step_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
-                       t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
-                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, -1, 0, 0, (int*)nullptr, (int*)nullptr);
+    DecodeRules r;
+    if (const int e = make_rules(&r, B, true, RULES_ARGS)) return e;
+#define LAUNCH(G, BUD, CNT)                                                                                                          \
+    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, \
+                       ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,             \
+                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, r)
+    if (!gstate) LAUNCH(false, false, false);
+    else if (!gbar && !gleft) LAUNCH(true, false, false);
+    else if (!gleft) LAUNCH(true, true, false);
+    else if (!gbar) LAUNCH(true, false, true);
+    else LAUNCH(true, true, true);
+#undef LAUNCH
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
 
-extern "C" int mxl_sample_step_stop(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev,
-                                    unsigned long long* rng_ctr, unsigned long long seed, int B, int do_sample, int top_k, float top_p,
-                                    float temperature, float repetition_penalty, float typical_p, const void* E, void* emb_out, int d,
-                                    float scale, int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive,
-                                    void* stream) {
-    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
-    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
-    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
-    MXL_CHECK_ARG(unfinished && alive && B <= 32767);          // arrivals and live rows share one 32-bit atomic word
-    hipLaunchKernelGGL(sample_step_kernel<false>, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
-                       t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
-                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id, min_length, unfinished, alive);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-static bool grammar_tables_ok(const void* cls, const void* allow, const void* next, int C, const void* gstate) {
-    return cls && allow && next && gstate && C >= 1 && C <= 32;
-}
-
-extern "C" int mxl_sample_step_grammar(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev,
-                                       unsigned long long* rng_ctr, unsigned long long seed, int B, int do_sample, int top_k,
-                                       float top_p, float temperature, float repetition_penalty, float typical_p, const void* E,
-                                       void* emb_out, int d, float scale, int* counter, int eos_id, int pad_id, int min_length,
-                                       int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C,
-                                       int* gstate, void* stream) {
-    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
-    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
-    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
-    MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr) && B <= 32767);     // unfinished = NULL: no eos rule
-    MXL_CHECK_ARG(grammar_tables_ok(cls, allow, next, C, gstate));
-    if (!unfinished) { eos_id = -1; pad_id = 0; min_length = 0; }
-    hipLaunchKernelGGL(sample_step_kernel<true>, dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
-                       t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
-                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id, min_length, unfinished, alive,
-                       (const unsigned char*)cls, (const uint32_t*)allow, (const unsigned char*)next, C, gstate);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-extern "C" int mxl_grammar_mask(float* scores, int ldl, int B, int V, const void* cls, const void* allow, const int* gstate,
-                                void* stream) {
-    MXL_CHECK_ARG(scores && cls && allow && gstate && B > 0 && V > 0 && ldl >= V);
+extern "C" int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, void* stream) {
+    MXL_CHECK_ARG(scores && B > 0 && V > 0 && ldl >= V && (t_dev || min_length <= 0));
     const long long n = (long long)B * V;
     MXL_CHECK_ARG(n <= (1LL << 38));
-    hipLaunchKernelGGL(grammar_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V,
-                       (const unsigned char*)cls, (const uint32_t*)allow, gstate);
+    DecodeRules r;
+    if (const int e = make_rules(&r, B, false, RULES_ARGS)) return e;
+    if (!r.cls && (r.min_length <= 0 || r.eos_id < 0 || r.eos_id >= V)) return MXL_OK;          // nothing to bar
+    hipLaunchKernelGGL(rules_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V, t_dev, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
 
-extern "C" int mxl_grammar_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, const void* next,
-                                   int C, int* gstate, const int* unfinished, void* stream) {
-    MXL_CHECK_ARG(ids && t_dev && B > 0 && V > 0 && cls && next && gstate && C >= 1 && C <= 32);
-    hipLaunchKernelGGL(grammar_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const long long*)ids, ld_ids,
-                       t_dev, B, V, (const unsigned char*)cls, (const unsigned char*)next, C, gstate, unfinished);
+extern "C" int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, void* stream) {
+    MXL_CHECK_ARG(ids && t_dev && B > 0 && (V > 0 || !cls));
+    DecodeRules r;
+    if (const int e = make_rules(&r, B, false, RULES_ARGS)) return e;
+    if (!r.cls && !r.unfinished) return MXL_OK;                                                  // nothing to move
+    hipLaunchKernelGGL(rules_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long long*)ids, ld_ids, t_dev, B, V, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
+#undef RULES_PARAMS
+#undef RULES_ARGS
 
 extern "C" int mxl_grammar_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* allow,
                                 const void* next, int C, int start, int* gstate, int* first_bad, void* stream) {
     MXL_CHECK_ARG(ids && B > 0 && V > 0 && Tp >= 0 && ld_ids >= Tp && first_bad && start >= 0 && start < 256);
-    MXL_CHECK_ARG(grammar_tables_ok(cls, allow, next, C, gstate));
+    MXL_CHECK_ARG(cls && allow && next && gstate && C >= 1 && C <= 32);
     hipLaunchKernelGGL(grammar_scan_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const long long*)ids, ld_ids, Tp, B, V,
                        (const unsigned char*)cls, (const uint32_t*)allow, (const unsigned char*)next, C, start, gstate, first_bad);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-static bool budget_tables_ok(const void* cls, const void* slots, const void* bars, unsigned opens, unsigned need_free,
-                             unsigned need_full, const void* gbar, const void* grem) {
-    (void)opens; (void)need_free; (void)need_full;               // any masks are meaningful: bits beyond the classes never match
-    return cls && slots && bars && gbar && grem;
-}
-
-extern "C" int mxl_sample_step_budget(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev,
-                                      unsigned long long* rng_ctr, unsigned long long seed, int B, int do_sample, int top_k,
-                                      float top_p, float temperature, float repetition_penalty, float typical_p, const void* E,
-                                      void* emb_out, int d, float scale, int* counter, int eos_id, int pad_id, int min_length,
-                                      int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C,
-                                      int* gstate, const void* slots, const void* bars, unsigned opens, unsigned need_free,
-                                      unsigned need_full, int* gbar, int* grem, void* stream) {
-    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
-    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
-    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
-    MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr) && B <= 32767);     // unfinished = NULL: no eos rule
-    MXL_CHECK_ARG(grammar_tables_ok(cls, allow, next, C, gstate));
-    MXL_CHECK_ARG(budget_tables_ok(cls, slots, bars, opens, need_free, need_full, gbar, grem));
-    if (!unfinished) { eos_id = -1; pad_id = 0; min_length = 0; }
-    const BudgetArgs bud{(const unsigned short*)slots, (const unsigned short*)bars, opens, need_free, need_full, gbar, grem};
-    hipLaunchKernelGGL((sample_step_kernel<true, true, false, BudgetArgs>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, ld_ids,
-                       t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,
-                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id, min_length, unfinished, alive,
-                       (const unsigned char*)cls, (const uint32_t*)allow, (const unsigned char*)next, C, gstate, bud);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-extern "C" int mxl_budget_mask(float* scores, int ldl, int B, int V, const void* cls, const void* slots, unsigned need_free,
-                               unsigned need_full, const int* gbar, const int* grem, void* stream) {
-    MXL_CHECK_ARG(scores && cls && slots && gbar && grem && B > 0 && V > 0 && ldl >= V);
-    const long long n = (long long)B * V;
-    MXL_CHECK_ARG(n <= (1LL << 38));
-    hipLaunchKernelGGL(budget_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V,
-                       (const unsigned char*)cls, (const unsigned short*)slots, need_free, need_full, gbar, grem);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-extern "C" int mxl_budget_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, const void* slots,
-                                  const void* bars, unsigned opens, int* gbar, int* grem, const int* unfinished, void* stream) {
-    MXL_CHECK_ARG(ids && t_dev && B > 0 && V > 0 && cls && slots && bars && gbar && grem);
-    hipLaunchKernelGGL(budget_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const long long*)ids, ld_ids,
-                       t_dev, B, V, (const unsigned char*)cls, (const unsigned short*)slots, (const unsigned short*)bars, opens, gbar,
-                       grem, unfinished);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-extern "C" int mxl_sample_step_bars(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev,
-                                    unsigned long long* rng_ctr, unsigned long long seed, int B, int do_sample, int top_k,
-                                    float top_p, float temperature, float repetition_penalty, float typical_p, const void* E,
-                                    void* emb_out, int d, float scale, int* counter, int eos_id, int pad_id, int min_length,
-                                    int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C,
-                                    int* gstate, const void* slots, const void* bars, unsigned opens, unsigned need_free,
-                                    unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end, int* gleft,
-                                    void* stream) {
-    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
-    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
-    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
-    MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr) && B <= 32767);     // unfinished = NULL: no eos rule
-    MXL_CHECK_ARG(grammar_tables_ok(cls, allow, next, C, gstate) && gleft);
-    const bool budget = slots || bars || gbar || grem;                              // all four NULL: no bar budget
-    MXL_CHECK_ARG(!budget || budget_tables_ok(cls, slots, bars, opens, need_free, need_full, gbar, grem));
-    if (!unfinished) { eos_id = -1; pad_id = 0; min_length = 0; }
-    const CountArgs cnt{count, end, gleft};
-    if (budget) {
-        const BudgetArgs bud{(const unsigned short*)slots, (const unsigned short*)bars, opens, need_free, need_full, gbar, grem};
-        hipLaunchKernelGGL((sample_step_kernel<true, true, true, BudgetArgs, CountArgs>), dim3(B), dim3(256), 0, (hipStream_t)stream,
-                           scores, ldl, V, (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
-                           repetition_penalty, typical_p, (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id,
-                           min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
-                           (const unsigned char*)next, C, gstate, bud, cnt);
-    } else {
-        hipLaunchKernelGGL((sample_step_kernel<true, false, true, CountArgs>), dim3(B), dim3(256), 0, (hipStream_t)stream,
-                           scores, ldl, V, (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
-                           repetition_penalty, typical_p, (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, eos_id, pad_id,
-                           min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
-                           (const unsigned char*)next, C, gstate, cnt);
-    }
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-extern "C" int mxl_barcount_mask(float* scores, int ldl, int B, int V, const void* cls, unsigned count, unsigned end,
-                                 const int* gleft, void* stream) {
-    MXL_CHECK_ARG(scores && cls && gleft && B > 0 && V > 0 && ldl >= V);
-    const long long n = (long long)B * V;
-    MXL_CHECK_ARG(n <= (1LL << 38));
-    hipLaunchKernelGGL(barcount_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V,
-                       (const unsigned char*)cls, count, end, gleft);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-extern "C" int mxl_barcount_advance(const void* ids, int ld_ids, const int* t_dev, int B, int V, const void* cls, unsigned count,
-                                    int* gleft, const int* unfinished, void* stream) {
-    MXL_CHECK_ARG(ids && t_dev && B > 0 && V > 0 && cls && gleft);
-    hipLaunchKernelGGL(barcount_advance_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const long long*)ids,
-                       ld_ids, t_dev, B, V, (const unsigned char*)cls, count, gleft, unfinished);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
@@ -1223,27 +1068,10 @@ extern "C" int mxl_budget_scan(const void* ids, int ld_ids, int Tp, int B, int V
                                unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, int* first_bad,
                                void* stream) {
     MXL_CHECK_ARG(ids && B > 0 && V > 0 && Tp >= 0 && ld_ids >= Tp && first_bad);
-    MXL_CHECK_ARG(budget_tables_ok(cls, slots, bars, opens, need_free, need_full, gbar, grem));
+    MXL_CHECK_ARG(cls && slots && bars && gbar && grem);       // any masks are meaningful: bits beyond the classes never match
     hipLaunchKernelGGL(budget_scan_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const long long*)ids, ld_ids, Tp, B, V,
                        (const unsigned char*)cls, (const unsigned short*)slots, (const unsigned short*)bars, opens, need_free,
                        need_full, gbar, grem, first_bad);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-extern "C" int mxl_decode_stop(void* ids, int ld_ids, const int* t_dev, int B, int eos_id, int pad_id, int* unfinished, int* alive,
-                               void* stream) {
-    MXL_CHECK_ARG(ids && t_dev && unfinished && alive && B > 0);
-    hipLaunchKernelGGL(decode_stop_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long long*)ids, ld_ids, t_dev, B, eos_id,
-                       pad_id, unfinished, alive);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-extern "C" int mxl_mask_eos_below(float* scores, int ldl, int B, int V, int eos_id, int min_length, const int* t_dev, void* stream) {
-    MXL_CHECK_ARG(scores && t_dev && B > 0 && V > 0 && ldl >= V);
-    if (min_length <= 0 || eos_id < 0 || eos_id >= V) return MXL_OK;         // nothing to bar
-    hipLaunchKernelGGL(mask_eos_below_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, eos_id, min_length, t_dev);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }

@@ -54,34 +54,20 @@ def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch
                    stop: Optional[tuple] = None, unfinished: Optional[torch.Tensor] = None, alive: Optional[torch.Tensor] = None,
                    grammar=None, gstate: Optional[torch.Tensor] = None, gbar: Optional[torch.Tensor] = None,
                    grem: Optional[torch.Tensor] = None, gleft: Optional[torch.Tensor] = None):
-    """The sampler tail as separate launches (what mxl_sample_step* does in one): next token of every row from the first V columns
+    """The sampler tail as separate launches (what mxl_sample_step does in one): next token of every row from the first V columns
     of `scores` -> ids[:, t + 1], position and RNG counters advanced.  stop = (eos, pad, min_length) with unfinished / alive and
     grammar with gstate are optional, and a grammar with a bar budget takes gbar / grem as well; gleft (the bars every row may
-    still open) turns the grammar's bar count on.  The masks write into `scores` in place."""
-    budget = grammar is not None and grammar.budget is not None
+    still open) turns the grammar's bar count on (ops.rules_in_force).  The mask writes into `scores` in place.  Four launches, two
+    where no rule is in force."""
+    rules = ops.rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft)
     sc = scores[:, :V] if scores.shape[1] != V else scores
-    if stop is not None:
-        ops.mask_eos_below(sc, V, t_dev, stop)
-    if grammar is not None:
-        # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the
-        # masks: -inf stays -inf under it, so the result is the same
-        ops.grammar_mask(sc, V, grammar, gstate)
-        if budget:
-            ops.budget_mask(sc, V, grammar, gbar, grem)
-        if gleft is not None:
-            ops.barcount_mask(sc, V, grammar, gleft)
+    # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the mask: -inf
+    # stays -inf under it, so the result is the same
+    ops.rules_mask(sc, V, t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
     ops.sample(sc, ids, t_dev, rng, seed, **sampling)
     ops.decode_advance(t_dev, rng)
-    if grammar is not None:
-        # before the stop rule rewrites it: `unfinished` still tells which rows chose their token (rows finished before this step
-        # keep their state)
-        ops.grammar_advance(ids, t_dev, grammar, gstate, None if stop is None else unfinished)
-        if budget:
-            ops.budget_advance(ids, t_dev, grammar, gbar, grem, None if stop is None else unfinished)
-        if gleft is not None:
-            ops.barcount_advance(ids, t_dev, grammar, gleft, None if stop is None else unfinished)
-    if stop is not None:
-        ops.decode_stop(ids, t_dev, stop, unfinished, alive)
+    # the words move before the stop rule rewrites `unfinished`, which still tells which rows chose their token
+    ops.rules_advance(ids, t_dev, **rules)
 
 
 def resolve_max_length(max_length: Optional[int], max_new_tokens: Optional[int], prompt_len: int, default: int) -> int:
@@ -188,18 +174,8 @@ def check_bar_count_start(grammar, n_bars: torch.Tensor, gstate: torch.Tensor):
                                'there to finish and only a new bar can follow; give that row n_bars >= 1')
 
 
-def scan_prompt(grammar, ids: torch.Tensor, Tp: int, gstate: torch.Tensor, gbad: torch.Tensor, gbar: torch.Tensor, grem: torch.Tensor):
-    """every row's grammar state and, under a bar budget, its bar length and free slots after columns 0..Tp-1 of ids, on the device.
-    gbad (2, B) int32: the first column that breaks the grammar / the budget (-1 = none), for raise_on_bad_prompt to read at once."""
-    ops.grammar_scan(ids, Tp, grammar, gstate, gbad[0])
-    if grammar.budget is not None:
-        ops.budget_scan(ids, Tp, grammar, gbar, grem, gbad[1])
-    else:
-        gbad[1].fill_(-1)
-
-
 def raise_on_bad_prompt(grammar, ids: torch.Tensor, first_bad: torch.Tensor):
-    """first_bad (B,) from ops.grammar_scan over ids, or (2, B) from scan_prompt (one read either way): raises MusicXLError naming
+    """first_bad (B,) from ops.grammar_scan over ids, or (2, B) from RowRules.start (one read either way): raises MusicXLError naming
     row, column and token of the first prompt that breaks the grammar (a constraint that starts from an undefined state guarantees
     nothing), or whose bars the budget does not accept"""
     bad = first_bad.tolist()
@@ -215,6 +191,79 @@ def raise_on_bad_prompt(grammar, ids: torch.Tensor, first_bad: torch.Tensor):
             how = 'overfills' if int(grammar.budget.slots[tok]) > 0 else 'underfills'
             raise MusicXLError(f'the prompt of row {b} {how} a bar at column {col}: token {tok} does not fit the slots its time '
                                f'signature leaves there ({sum(1 for c in over if c >= 0)} of {len(over)} rows break the bar budget)')
+
+
+class RowRules:
+    """The rules of one generation and their per-row state on the device, as every decoder keeps them: `stop` = (eos, pad,
+    min_length) or None, `grammar` (with its bar budget, if it has one) or None, `bars` = the grammar's bar count is on.  One packed
+    int32 buffer holds the words the sampler launches move -- unfinished (1 = live), gstate (automaton state), gbar / grem (bar
+    length and free slots), gleft (bars the row may still open, < 0 = no limit), each (B,) -- then gbad (2, B), the first prompt
+    column that breaks the grammar / the budget, and alive (1,), the live-row count.  A further rule is a row here, a line in `start`
+    and a key in `kwargs` / `graph_key`."""
+    WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft')
+    STATE = WORDS + ('alive',)
+
+    def __init__(self, batch: int, dev):
+        self.B, n = batch, len(self.WORDS)
+        self.buf = torch.zeros((n + 2) * batch + 1, device=dev, dtype=torch.int32)
+        for k, row in zip(self.WORDS, self.buf[:n * batch].view(n, batch)):
+            setattr(self, k, row)
+        self.gbad = self.buf[n * batch:(n + 2) * batch].view(2, batch)
+        self.alive = self.buf[(n + 2) * batch:]
+        self.unfinished.fill_(1)
+        self.gleft.fill_(-1)
+        self.stop = self.grammar = self.n_bars = None
+        self.bars = False
+
+    def start(self, ids: torch.Tensor, Tp: int, vocab_size: int, stop: Optional[tuple], grammar, n_bars: Optional[torch.Tensor]):
+        """the rules of a new generation over the prompts in columns 0..Tp-1 of ids (ids < 0: left pads, skipped): every row live,
+        its grammar state and, under a bar budget, its bar length and free slots after its prompt computed on the device, gleft =
+        n_bars ((B,) int32 from bar_count_config, or None: no bar count)"""
+        check_grammar_args(grammar, vocab_size, stop)
+        if n_bars is not None and (grammar is None or grammar.bar_count is None or stop is None or n_bars.numel() != self.B):
+            raise MusicXLError('n_bars needs a grammar with a bar count, the eos rule and one entry per row (bar_count_config)')
+        self.stop, self.grammar, self.n_bars, self.bars = stop, grammar, n_bars, n_bars is not None
+        self.unfinished.fill_(1)
+        self.alive.fill_(self.B)
+        if self.bars:
+            self.gleft.copy_(n_bars.to(torch.int32))
+        else:
+            self.gleft.fill_(-1)
+        if grammar is not None:
+            ops.grammar_scan(ids, Tp, grammar, self.gstate, self.gbad[0])
+            if grammar.budget is not None:
+                ops.budget_scan(ids, Tp, grammar, self.gbar, self.grem, self.gbad[1])
+            else:
+                self.gbad[1].fill_(-1)
+
+    def check_prompt(self, ids: torch.Tensor):
+        """after `start`: raises for a prompt that breaks the grammar or the bar budget, or that leaves a row asked for 0 bars where
+        only a bar can follow (one device read, one more only if some row has n_bars = 0)"""
+        if self.grammar is not None:
+            raise_on_bad_prompt(self.grammar, ids, self.gbad)
+        if self.bars:
+            check_bar_count_start(self.grammar, self.n_bars, self.gstate)
+
+    def kwargs(self) -> dict:
+        """the rules keywords of ops.sample_step and sample_unfused"""
+        return dict(stop=self.stop, unfinished=self.unfinished, alive=self.alive, grammar=self.grammar, gstate=self.gstate,
+                    gbar=self.gbar, grem=self.grem, gleft=self.gleft if self.bars else None)
+
+    def graph_key(self, dev) -> tuple:
+        """what a captured sampler launch holds of the rules: which of them are on, the identity of the grammar's and the budget's
+        device tables and their class masks.  The per-row words are step state and not part of it."""
+        g = self.grammar
+        return (self.stop,
+                None if g is None else tuple(t.data_ptr() for t in g.to(dev)) + (g.n_classes,),
+                None if g is None or g.budget is None else
+                tuple(t.data_ptr() for t in g.budget.to(dev)) + (g.budget.opens, g.budget.need_free, g.budget.need_full),
+                (g.bar_count.count, g.bar_count.end) if self.bars else None)
+
+    def snapshot(self) -> torch.Tensor:
+        return self.buf.clone()
+
+    def restore(self, saved: torch.Tensor):
+        self.buf.copy_(saved)
 
 
 def check_grammar(ids: torch.Tensor, grammar, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -417,24 +466,11 @@ class XLDecoder:
         # optional (B, Tmax, V) f32 buffer: row t receives the log-probs computed FROM position t (parity tests compare them
         # with a one-shot forward); written on the device by position, so it also works under hipGraph replay
         self.trace = None
-        # stopping at eos (generate(eos_token_id=...)): per-row live flags and the live-row count, both on the device and written
-        # by the sampler launch; `_stop` = (eos, pad, min_length) of the current generation, None = every row runs to max_length
-        self.unfinished = torch.ones(batch, device=dev, dtype=torch.int32)
-        self.alive = torch.zeros(1, device=dev, dtype=torch.int32)
-        self._stop = None
         self.steps_run = 0                              # decode steps issued by the last generate() (early exit: fewer)
-        # grammar-constrained decoding (generate(grammar=...)): the automaton state of every row, advanced by the sampler launch;
-        # `gbad`: first prompt column that breaks the grammar (read once after the prompt pass)
-        self.gstate = torch.zeros(batch, device=dev, dtype=torch.int32)
-        self.gbad = torch.zeros(2, batch, device=dev, dtype=torch.int32)     # (grammar, bar budget)
-        self._grammar = None
-        # bar budget of such a grammar (grammar.BarBudget): bar length and free slots of every row, moved where gstate moves
-        self.gbar = torch.zeros(batch, device=dev, dtype=torch.int32)
-        self.grem = torch.zeros(batch, device=dev, dtype=torch.int32)
-        # bar count of such a grammar (grammar.BarCount, generate(n_bars=)): the bars every row may still open, < 0 = no limit;
-        # `_bars`: the current generation runs under the rule (the sampler launch that carries it)
-        self.gleft = torch.full((batch,), -1, device=dev, dtype=torch.int32)
-        self._bars = False
+        # the rules of the current generation (eos, grammar, bar budget, bar count) and their per-row words, which the sampler
+        # launch reads and moves; the words are readable here under their names
+        self.rules = RowRules(batch, dev)
+        self.unfinished, self.gstate, self.gbar, self.grem, self.gleft, self.alive = (getattr(self.rules, k) for k in RowRules.STATE)
 
     def _tables(self):
         if self.rd is None:
@@ -466,21 +502,9 @@ class XLDecoder:
         n_bars: None, or (B,) int32 from bar_count_config: the bars every row may still open (the grammar's bar count); it is the
         start value of `gleft`, which the sampler launches move."""
         e, c = self.eng, self.eng.cfg
-        check_grammar_args(grammar, c.vocab_size, stop)
-        self._grammar = grammar
-        if n_bars is not None and (grammar is None or grammar.bar_count is None or stop is None or n_bars.numel() != self.B):
-            raise MusicXLError('n_bars needs a grammar with a bar count, the eos rule and one entry per row (bar_count_config)')
-        self._bars = n_bars is not None
-        if self._bars:
-            self.gleft.copy_(n_bars.to(torch.int32))
-        else:
-            self.gleft.fill_(-1)
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
         self._tables()
-        self._stop = stop
-        self.unfinished.fill_(1)
-        self.alive.fill_(B)
         for k in self.kc + self.vc:
             k.zero_()
         self.ids.zero_()
@@ -491,8 +515,7 @@ class XLDecoder:
             pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
             self.ids[:, :Tp].masked_fill_(pad, -1)
             x = x.masked_fill(pad, 0)
-        if grammar is not None:
-            scan_prompt(grammar, self.ids, Tp, self.gstate, self.gbad, self.gbar, self.grem)
+        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars)
         sink_kc, sink_vc = self.kc, self.vc
 
         def kv_sink(l, qkv):
@@ -510,10 +533,7 @@ class XLDecoder:
             ops.adaptive_logprob(last, self.logp, B, c.vocab_size, tuple(c.cutoffs))
         self.t_dev.fill_(Tp - 1)
         self._trace()
-        if grammar is not None:
-            raise_on_bad_prompt(grammar, self.ids, self.gbad)
-        if self._bars:
-            check_bar_count_start(grammar, n_bars, self.gstate)
+        self.rules.check_prompt(self.ids)
         if sampling is not None:                       # None: the caller picks the token from self.logp (beam search)
             self._sample_advance(self.logp, sampling)  # t = Tp: position of the token just sampled
         return out
@@ -522,8 +542,7 @@ class XLDecoder:
         """next token of every row from `scores` (log-probabilities, or the head's logits: see mxl_sample_step) -> ids[:, t + 1];
         position and RNG counters advanced.  Short chain: the same launch leaves the token's embedding row in h[0] for the next step."""
         c = self.eng.cfg
-        state = dict(stop=self._stop, unfinished=self.unfinished, alive=self.alive, grammar=self._grammar, gstate=self.gstate,
-                     gbar=self.gbar, grem=self.grem, gleft=self.gleft if self._bars else None)
+        state = self.rules.kwargs()
         if self.fused_sampler:      # the masks, the stop rule, the live-row count and the state advance ride on the sampler launch
             ops.sample_step(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
                             self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model), self.step_ctr,
@@ -571,7 +590,7 @@ class XLDecoder:
                 ops.kv_append(self.qkv, self.kc[l], self.vc[l], self.t_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
             ops.relattn_decode(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P),
                                rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces,
-                               unfinished=None if self._stop is None else self.unfinished)
+                               unfinished=None if self.rules.stop is None else self.unfinished)
             G(self.av, e._lw(l, 'dec_attn.o_net.weight'), self.tmp, B, d, d)
             ops.ln_residual_fwd(self.tmp, h_in, e._lw(l, 'dec_attn.layer_norm.weight', e.P),
                                 e._lw(l, 'dec_attn.layer_norm.bias', e.P), self.h1, eps=c.layer_norm_epsilon)
@@ -648,18 +667,11 @@ class XLDecoder:
             # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
             # itself is written by the captured launches): a graph captured without a trace would replay without writing one
             key = (tuple(sorted(sampling.items())), self.fused_sampler,
-                   None if self.trace is None else self.trace.data_ptr(), stop,
-                   None if grammar is None else tuple(t.data_ptr() for t in grammar.to(self.eng.dev)) + (grammar.n_classes,),
-                   None if grammar is None or grammar.budget is None else
-                   tuple(t.data_ptr() for t in grammar.budget.to(self.eng.dev))
-                   + (grammar.budget.opens, grammar.budget.need_free, grammar.budget.need_full),
-                   (grammar.bar_count.count, grammar.bar_count.end) if self._bars else None)
+                   None if self.trace is None else self.trace.data_ptr()) + self.rules.graph_key(self.eng.dev)
             if self.graph is None or self._graph_key != key:
                 # warm-up on a side stream (first launches set function attributes), then capture one step
                 state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(),
-                         [k.clone() for k in self.kc], [v.clone() for v in self.vc], self.h[0].clone(),
-                         self.unfinished.clone(), self.alive.clone(), self.gstate.clone(), self.gbar.clone(), self.grem.clone(),
-                         self.gleft.clone())
+                         [k.clone() for k in self.kc], [v.clone() for v in self.vc], self.h[0].clone(), self.rules.snapshot())
                 s = torch.cuda.Stream()
                 s.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(s):
@@ -676,8 +688,7 @@ class XLDecoder:
                 for a, b in zip(self.vc, state[4]):
                     a.copy_(b)
                 self.h[0].copy_(state[5])         # (short chain: the next step's embedding row is step state too)
-                self.unfinished.copy_(state[6]); self.alive.copy_(state[7]); self.gstate.copy_(state[8])
-                self.gbar.copy_(state[9]); self.grem.copy_(state[10]); self.gleft.copy_(state[11])
+                self.rules.restore(state[6])
         return max(steps, 0)
 
     def replay_once(self):

@@ -133,97 +133,107 @@ def decode_qkv(x, wqkv, qkv, kc, vc, t_dev, rrb, qr_out, dh):
                                _stream()), 'mxl_decode_qkv')
 
 
+def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None) -> dict:
+    """The rules of a generation as its decoders describe them -> the keywords of rules_mask / rules_advance, where a group is on
+    exactly when its state tensor is given.  The decoders say which rules hold with `stop` (the eos rule), `grammar` (the grammar,
+    and its bar budget if it has one) and `gleft` (the bar count) and may hand over state tensors of rules that are off: those are
+    dropped here, and a rule that is on without its state raises."""
+    budget = grammar is not None and grammar.budget is not None
+    if stop is not None and (unfinished is None or alive is None):
+        raise MusicXLError('the eos rule needs unfinished and alive')
+    if grammar is None and gleft is not None:
+        raise MusicXLError('the bar count rides on a grammar')
+    if grammar is not None and gstate is None:
+        raise MusicXLError('a grammar needs gstate')
+    if budget and (gbar is None or grem is None):
+        raise MusicXLError('a grammar with a bar budget needs gbar and grem')
+    return dict(stop=stop, unfinished=unfinished if stop is not None else None, alive=alive if stop is not None else None,
+                grammar=grammar, gstate=gstate if grammar is not None else None, gbar=gbar if budget else None,
+                grem=grem if budget else None, gleft=gleft)
+
+
+def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None,
+                gleft=None) -> list:
+    """the flat rules arguments of mxl_sample_step / mxl_rules_mask / mxl_rules_advance (include/musicxl.h, "Rules of a generation"),
+    checked: a group is on exactly when its state tensor is given -- unfinished (with alive and stop = (eos, pad, min_length)),
+    gstate, gbar (with grem), gleft; the last three take their tables from `grammar`, which must classify the V tokens of the scores"""
+    eos, pad, min_length = stop if stop is not None else (-1, 0, 0)
+    if unfinished is not None:
+        if stop is None:
+            raise MusicXLError(f'{what}: unfinished needs stop = (eos, pad, min_length)')
+        _req(unfinished, torch.int32, f'{what} unfinished')
+    cls = allow = nxt = slots = bars = None
+    bud = cnt = None
+    if gstate is not None or gbar is not None or grem is not None or gleft is not None:
+        if grammar is None:
+            raise MusicXLError(f'{what}: gstate, gbar / grem and gleft ride on a grammar')
+        if V is not None and grammar.vocab_size != int(V):
+            raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
+        cls, allow, nxt = grammar.to(device)
+    if gstate is None:
+        allow = nxt = None
+    else:
+        _req(gstate, torch.int32, f'{what} gstate')
+        if gstate.numel() != B:
+            raise MusicXLError(f'gstate holds {gstate.numel()} rows, the scores {B}')
+    if gbar is not None or grem is not None:
+        bud = grammar.budget
+        slots, bars = _budget_state(bud, device, B, gbar, grem, what)
+    if gleft is not None:
+        cnt = grammar.bar_count
+        if cnt is None:
+            raise MusicXLError(f'{what}: the grammar carries no bar count (grammar.BarCount; the music grammar has one)')
+        _req(gleft, torch.int32, f'{what} gleft')
+        if gleft.numel() != B or not gleft.is_contiguous():
+            raise MusicXLError(f'{what}: gleft must be contiguous ({B},) int32')
+    masks = (bud.opens, bud.need_free, bud.need_full) if bud is not None else (0, 0, 0)
+    ends = (cnt.count, cnt.end) if cnt is not None else (0, 0)
+    return [int(eos), int(pad), int(min_length or 0), _p(unfinished), _p(alive), _p(cls), _p(allow), _p(nxt),
+            grammar.n_classes if cls is not None else 0, _p(gstate), _p(slots), _p(bars), *masks, _p(gbar), _p(grem), *ends, _p(gleft)]
+
+
 def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
                 grammar=None, gstate=None, gbar=None, grem=None, gleft=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0,
                 repetition_penalty=1.0, typical_p=1.0):
     """sampler + embedding row of the sampled token (-> emb_out (B, d) bf16) + counter advance, one launch (V <= 2048).
     scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1.
-    stop = (eos_id, pad_id, min_length) with unfinished (B,) int32 and alive (1,) int32 on the device: the stop state of generation
-    rides on the same launch (mxl_sample_step_stop).  grammar (a grammar.TokenGrammar) with gstate (B,) int32: barred tokens masked
-    and gstate advanced in the same launch, with or without the eos rule (mxl_sample_step_grammar).  A grammar with a bar budget
-    (grammar.budget) needs gbar and grem (B,) int32 as well and takes mxl_sample_step_budget; without one the launch is unchanged.
-    gleft (B,) int32, the bars every row may still open (< 0 = no limit): the bar count of the grammar (grammar.bar_count) is applied
-    and gleft moved in the same launch, with or without the budget (mxl_sample_step_bars); None = no such rule, the launches above."""
+    The rules of the generation ride on the same launch (rules_in_force): stop = (eos_id, pad_id, min_length) with unfinished (B,)
+    int32 and alive (1,) int32 on the device; grammar (a grammar.TokenGrammar) with gstate (B,) int32, barred tokens masked and gstate
+    advanced, with or without the eos rule; a grammar with a bar budget (grammar.budget) needs gbar and grem (B,) int32 as well;
+    gleft (B,) int32, the bars every row may still open (< 0 = no limit), turns the grammar's bar count on."""
     B = scores.shape[0]
-    args = [_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B, int(do_sample),
-            int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
-            float(repetition_penalty if repetition_penalty is not None else 1.0),
-            float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1], float(scale), _p(counter)]
-    name = 'mxl_sample_step'
-    if grammar is not None:
-        _req(gstate, torch.int32, 'sample_step_grammar gstate')
-        if gstate.numel() != B:
-            raise MusicXLError(f'gstate holds {gstate.numel()} rows, the scores {B}')
-        cls, allow, nxt = _grammar_tables(grammar, scores.device, V)
-        if stop is not None and (unfinished is None or alive is None):
-            raise MusicXLError('sample_step_grammar: the eos rule needs unfinished and alive')
-    if stop is not None or grammar is not None:
-        eos, pad, min_length = stop if stop is not None else (-1, 0, 0)
-        args += [int(eos), int(pad), int(min_length or 0), _p(unfinished) if stop is not None else 0,
-                 _p(alive) if stop is not None else 0]
-        name = 'mxl_sample_step_stop'
-    if grammar is not None:
-        args += [_p(cls), _p(allow), _p(nxt), grammar.n_classes, _p(gstate)]
-        name = 'mxl_sample_step_grammar'
-        if grammar.budget is not None:
-            bud = grammar.budget
-            slots, bars = _budget_state(bud, scores.device, B, gbar, grem, 'sample_step_budget')
-            args += [_p(slots), _p(bars), bud.opens, bud.need_free, bud.need_full, _p(gbar), _p(grem)]
-            name = 'mxl_sample_step_budget'
-        if gleft is not None:
-            cnt = _barcount_state(grammar, B, gleft, 'sample_step_bars')
-            if grammar.budget is None:
-                args += [0, 0, 0, 0, 0, 0, 0]
-            args += [cnt.count, cnt.end, _p(gleft)]
-            name = 'mxl_sample_step_bars'
-    elif gleft is not None:
-        raise MusicXLError('sample_step_bars: the bar count rides on a grammar')
-    check(getattr(lib(), name)(*args, _stream()), name)
+    rules = _rules_args('sample_step', scores.device, B, V, **rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft))
+    check(lib().mxl_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
+                                int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
+                                float(repetition_penalty if repetition_penalty is not None else 1.0),
+                                float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1], float(scale),
+                                _p(counter), *rules, _stream()), 'mxl_sample_step')
 
 
-def decode_stop(ids, t_dev, stop, unfinished, alive):
-    """after sample + decode_advance: the token at ids[:, t] through the stop rule (mxl_decode_stop); stop = (eos, pad, min_length)"""
-    _req(unfinished, torch.int32, 'decode_stop unfinished')
-    check(lib().mxl_decode_stop(_p(ids), ids.stride(0), _p(t_dev), ids.shape[0], int(stop[0]), int(stop[1]), _p(unfinished), _p(alive),
-                                _stream()), 'mxl_decode_stop')
-
-
-def mask_eos_below(scores, V, t_dev, stop):
-    """before sample: eos barred (-inf) while the rows are shorter than min_length (mxl_mask_eos_below); no launch without one"""
-    eos, _, min_length = stop
-    if not min_length or min_length <= 0:
-        return
-    check(lib().mxl_mask_eos_below(_p(scores), scores.stride(0), scores.shape[0], int(V), int(eos), int(min_length), _p(t_dev),
-                                   _stream()), 'mxl_mask_eos_below')
-
-
-def _grammar_tables(grammar, device, V):
-    """(cls, allow, next) device tensors of a grammar.TokenGrammar, checked against the vocabulary the scores span"""
-    if grammar.vocab_size != int(V):
-        raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
-    return grammar.to(device)
-
-
-def grammar_mask(scores, V, grammar, gstate):
-    """before sample: scores[b, v] = -inf in place for every token the grammar bars in state gstate[b] (mxl_grammar_mask)"""
-    _req(scores, torch.float32, 'grammar_mask scores'); _req(gstate, torch.int32, 'grammar_mask gstate')
+def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None):
+    """before sample: scores[b, v] = -inf in place for every token a rule bars (mxl_rules_mask).  A rule is applied exactly when its
+    state is given: gstate (the grammar in state gstate[b]), gbar and grem (its bar budget), gleft (its bar count), each with
+    `grammar` for the tables; stop = (eos, pad, min_length) bars eos while the rows are shorter than min_length.  No launch when
+    nothing is given."""
+    _req(scores, torch.float32, 'rules_mask scores')
     B = scores.shape[0]
-    if scores.shape[1] < V or scores.stride(1) != 1 or gstate.numel() != B:
-        raise MusicXLError('grammar_mask: scores must be (B, >= V) with unit column stride and gstate (B,)')
-    cls, allow, _ = _grammar_tables(grammar, scores.device, V)
-    check(lib().mxl_grammar_mask(_p(scores), scores.stride(0), B, int(V), _p(cls), _p(allow), _p(gstate), _stream()), 'mxl_grammar_mask')
+    if scores.shape[1] < V or scores.stride(1) != 1:
+        raise MusicXLError('rules_mask: scores must be (B, >= V) with unit column stride')
+    rules = _rules_args('rules_mask', scores.device, B, V, stop=stop, grammar=grammar, gstate=gstate, gbar=gbar, grem=grem, gleft=gleft)
+    check(lib().mxl_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, _stream()), 'mxl_rules_mask')
 
 
-def grammar_advance(ids, t_dev, grammar, gstate, unfinished=None):
-    """after sample + decode_advance and before decode_stop: gstate[b] moves along the token at ids[b, t]; rows with
-    unfinished[b] == 0 keep their state (mxl_grammar_advance)"""
-    _req(gstate, torch.int32, 'grammar_advance gstate')
+def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None):
+    """after sample + decode_advance: the words given (as rules_mask) move along the token at ids[b, t] in every row that chose it,
+    then, with unfinished and alive, that token goes through the stop rule stop = (eos, pad, min_length): rows with unfinished[b] == 0
+    get pad and keep their words (mxl_rules_advance).  No launch when nothing is given."""
     B = ids.shape[0]
-    if gstate.numel() != B or ids.dtype != torch.int64:
-        raise MusicXLError('grammar_advance: ids must be (B, .) int64 and gstate (B,)')
-    cls, _, nxt = grammar.to(ids.device)
-    check(lib().mxl_grammar_advance(_p(ids), ids.stride(0), _p(t_dev), B, grammar.vocab_size, _p(cls), _p(nxt), grammar.n_classes,
-                                    _p(gstate), _p(unfinished), _stream()), 'mxl_grammar_advance')
+    if ids.dtype != torch.int64:
+        raise MusicXLError('rules_advance: ids must be (B, .) int64')
+    rules = _rules_args('rules_advance', ids.device, B, stop=stop, unfinished=unfinished, alive=alive, grammar=grammar, gstate=gstate,
+                        gbar=gbar, grem=grem, gleft=gleft)
+    check(lib().mxl_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, grammar.vocab_size if grammar is not None else 0, *rules,
+                                  _stream()), 'mxl_rules_advance')
 
 
 def grammar_scan(ids, Tp, grammar, gstate, first_bad, start=None):
@@ -251,33 +261,6 @@ def _budget_state(budget, device, B, gbar, grem, what):
     return budget.to(device)
 
 
-def budget_mask(scores, V, grammar, gbar, grem):
-    """after grammar_mask, before sample: scores[b, v] = -inf in place for every token the bar budget of `grammar` bars in a row at
-    (gbar[b], grem[b]) (mxl_budget_mask)"""
-    _req(scores, torch.float32, 'budget_mask scores')
-    B = scores.shape[0]
-    if scores.shape[1] < V or scores.stride(1) != 1:
-        raise MusicXLError('budget_mask: scores must be (B, >= V) with unit column stride')
-    cls, _, _ = _grammar_tables(grammar, scores.device, V)
-    bud = grammar.budget
-    slots, _ = _budget_state(bud, scores.device, B, gbar, grem, 'budget_mask')
-    check(lib().mxl_budget_mask(_p(scores), scores.stride(0), B, int(V), _p(cls), _p(slots), bud.need_free, bud.need_full, _p(gbar),
-                                _p(grem), _stream()), 'mxl_budget_mask')
-
-
-def budget_advance(ids, t_dev, grammar, gbar, grem, unfinished=None):
-    """beside grammar_advance (after sample + decode_advance, before decode_stop): (gbar[b], grem[b]) move along the token at
-    ids[b, t]; rows with unfinished[b] == 0 keep theirs (mxl_budget_advance)"""
-    B = ids.shape[0]
-    if ids.dtype != torch.int64:
-        raise MusicXLError('budget_advance: ids must be (B, .) int64')
-    cls, _, _ = grammar.to(ids.device)
-    bud = grammar.budget
-    slots, bars = _budget_state(bud, ids.device, B, gbar, grem, 'budget_advance')
-    check(lib().mxl_budget_advance(_p(ids), ids.stride(0), _p(t_dev), B, grammar.vocab_size, _p(cls), _p(slots), _p(bars), bud.opens,
-                                   _p(gbar), _p(grem), _p(unfinished), _stream()), 'mxl_budget_advance')
-
-
 def budget_scan(ids, Tp, grammar, gbar, grem, first_bad):
     """(gbar[b], grem[b]) = bar length and free slots of row b after columns 0..Tp-1 of ids (ids < 0 skipped), first_bad[b] = column
     of the first token the bar budget bars or -1 (mxl_budget_scan); the host reference is TokenGrammar.walk_budget"""
@@ -290,41 +273,6 @@ def budget_scan(ids, Tp, grammar, gbar, grem, first_bad):
     slots, bars = _budget_state(bud, ids.device, B, gbar, grem, 'budget_scan')
     check(lib().mxl_budget_scan(_p(ids), ids.stride(0), int(Tp), B, grammar.vocab_size, _p(cls), _p(slots), _p(bars), bud.opens,
                                 bud.need_free, bud.need_full, _p(gbar), _p(grem), _p(first_bad), _stream()), 'mxl_budget_scan')
-
-
-def _barcount_state(grammar, B, gleft, what):
-    """the grammar.BarCount of a grammar, with the per-row word gleft checked"""
-    if grammar is None or grammar.bar_count is None:
-        raise MusicXLError(f'{what}: the grammar carries no bar count (grammar.BarCount; the music grammar has one)')
-    _req(gleft, torch.int32, f'{what} gleft')
-    if gleft.numel() != B or not gleft.is_contiguous():
-        raise MusicXLError(f'{what}: gleft must be contiguous ({B},) int32')
-    return grammar.bar_count
-
-
-def barcount_mask(scores, V, grammar, gleft):
-    """after grammar_mask and budget_mask, before sample: scores[b, v] = -inf in place for every token the bar count of `grammar`
-    bars in a row with gleft[b] bars to go (mxl_barcount_mask)"""
-    _req(scores, torch.float32, 'barcount_mask scores')
-    B = scores.shape[0]
-    if scores.shape[1] < V or scores.stride(1) != 1:
-        raise MusicXLError('barcount_mask: scores must be (B, >= V) with unit column stride')
-    cnt = _barcount_state(grammar, B, gleft, 'barcount_mask')
-    cls, _, _ = _grammar_tables(grammar, scores.device, V)
-    check(lib().mxl_barcount_mask(_p(scores), scores.stride(0), B, int(V), _p(cls), cnt.count, cnt.end, _p(gleft), _stream()),
-          'mxl_barcount_mask')
-
-
-def barcount_advance(ids, t_dev, grammar, gleft, unfinished=None):
-    """beside grammar_advance and budget_advance (after sample + decode_advance, before decode_stop): gleft[b] moves along the token
-    at ids[b, t]; rows with unfinished[b] == 0 keep theirs (mxl_barcount_advance)"""
-    B = ids.shape[0]
-    if ids.dtype != torch.int64:
-        raise MusicXLError('barcount_advance: ids must be (B, .) int64')
-    cnt = _barcount_state(grammar, B, gleft, 'barcount_advance')
-    cls, _, _ = grammar.to(ids.device)
-    check(lib().mxl_barcount_advance(_p(ids), ids.stride(0), _p(t_dev), B, grammar.vocab_size, _p(cls), cnt.count, _p(gleft),
-                                     _p(unfinished), _stream()), 'mxl_barcount_advance')
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, relu=False, out=None,

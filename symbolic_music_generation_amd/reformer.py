@@ -178,9 +178,8 @@ class MyReformerModelWithLMHead(EngineModule):
         n_bars (an int, or one per prompt; negative = no limit; with grammar and eos_token_id, greedy decoding and sampling): every
         row opens exactly that many further bars, as MyTransfoXLLMHeadModel.generate -- under the bar budget it ends with eos when
         the last of them is full; under a grammar without one the rule cannot force the end and a row may run to max_length."""
-        from .generate import (STOP_CHUNK, bar_count_config, beam_generate, check_bar_count_start, check_grammar_args, left_pad_counts,
-                               raise_on_bad_prompt, resolve_max_length, sample_unfused, sampling_config, scan_prompt, stop_config,
-                               stop_width)
+        from .generate import (STOP_CHUNK, RowRules, bar_count_config, beam_generate, check_grammar_args, left_pad_counts,
+                               resolve_max_length, sample_unfused, sampling_config, stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
@@ -260,30 +259,22 @@ class MyReformerModelWithLMHead(EngineModule):
             buf[:, :Tp] = ids0
             t_dev = torch.full((1,), Tp - 1, device=self.device, dtype=torch.int32)
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
-            unfinished = torch.ones(B, device=self.device, dtype=torch.int32)
-            alive = torch.zeros(1, device=self.device, dtype=torch.int32)
-            gstate = gbar = grem = gleft = None
-            if grammar is not None:
-                gstate, gbar, grem = (torch.zeros(B, device=self.device, dtype=torch.int32) for _ in range(3))
-                gbad = torch.empty(2, B, device=self.device, dtype=torch.int32)
-                scan_prompt(grammar, buf, Tp, gstate, gbad, gbar, grem)
-                raise_on_bad_prompt(grammar, buf, gbad)
-            if n_bars is not None:
-                gleft = n_bars.to(self.device)
-                check_bar_count_start(grammar, n_bars, gstate)
+            rules = RowRules(B, self.device)
+            rules.start(buf, Tp, V, stop, grammar, n_bars)
+            rules.check_prompt(buf)
             sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
             for cur in range(Tp, max_length):
                 Tf = cur if cur <= 64 else (cur + 63) // 64 * 64
                 out = self.engine.forward(buf[:, :Tf].contiguous(), labels=None, train=False)
                 last = out['logits'][:, cur - 1].contiguous()
-                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, stop, unfinished, alive, grammar, gstate, gbar, grem, gleft)
+                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, **rules.kwargs())
                 if Tf > cur:
                     buf[:, cur + 1:Tf] = pad          # keep the padding clean (the sampler wrote position `cur` only)
                 # a whole forward per token: reading the live-row count every STOP_CHUNK tokens costs nothing in comparison
-                if stop is not None and (cur - Tp) % STOP_CHUNK == 0 and int(alive.item()) == 0:
+                if stop is not None and (cur - Tp) % STOP_CHUNK == 0 and int(rules.alive.item()) == 0:
                     break
             if stop is not None:
-                return buf[:, :stop_width(buf, unfinished, Tp, max_length, stop[0])].clone()
+                return buf[:, :stop_width(buf, rules.unfinished, Tp, max_length, stop[0])].clone()
             return buf[:, :max_length].clone()
         finally:
             if was_training:

@@ -26,8 +26,7 @@ import torch
 
 from . import ops
 from ._lib import MusicXLError
-from .generate import (bar_count_config, check_bar_count_start, check_grammar_args, decode_lanes, raise_on_bad_prompt, sample_unfused,
-                       sampling_config, scan_prompt)
+from .generate import RowRules, bar_count_config, decode_lanes, sample_unfused, sampling_config
 
 
 class RFDecoder:
@@ -68,19 +67,10 @@ class RFDecoder:
         self.logits = torch.empty(batch, engine.layout.head_rows_padded, device=dev, dtype=torch.float32)
         self.raw_bk = torch.empty(batch * H, self.n_h, device=dev, dtype=torch.int32)
         self.trace = None                   # optional (B, Tmax, V) f32: row t = logits computed FROM position t (parity tests)
-        # stopping at eos (generate(stop=...)): per-row live flags and the live-row count on the device (generate.XLDecoder)
-        self.unfinished = torch.ones(batch, device=dev, dtype=torch.int32)
-        self.alive = torch.zeros(1, device=dev, dtype=torch.int32)
-        self._stop = None
         self.steps_run = 0
-        # grammar-constrained decoding (generate(grammar=...)): the automaton state of every row (generate.XLDecoder)
-        self.gstate = torch.zeros(batch, device=dev, dtype=torch.int32)
-        self.gbad = torch.zeros(2, batch, device=dev, dtype=torch.int32)
-        self._grammar = None
-        self.gbar = torch.zeros(batch, device=dev, dtype=torch.int32)     # bar budget of such a grammar: bar length, free slots
-        self.grem = torch.zeros(batch, device=dev, dtype=torch.int32)
-        self.gleft = torch.full((batch,), -1, device=dev, dtype=torch.int32)   # bar count (generate(n_bars=)): bars left to open
-        self._bars = False
+        # the rules of the current generation and their per-row words (generate.RowRules), readable here under their names
+        self.rules = RowRules(batch, dev)
+        self.unfinished, self.gstate, self.gbar, self.grem, self.gleft, self.alive = (getattr(self.rules, k) for k in RowRules.STATE)
 
     # ---------------------------------------------------------------- hashing helpers
     def _factors(self, T_hint: Optional[int] = None):
@@ -114,23 +104,10 @@ class RFDecoder:
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and 1 <= Tp <= self.Tmax
-        check_grammar_args(grammar, c.vocab_size, stop)
-        self._stop = stop
-        self._grammar = grammar
-        if n_bars is not None and (grammar is None or grammar.bar_count is None or stop is None or n_bars.numel() != B):
-            raise MusicXLError('n_bars needs a grammar with a bar count, the eos rule and one entry per row (bar_count_config)')
-        self._bars = n_bars is not None
-        if self._bars:
-            self.gleft.copy_(n_bars.to(torch.int32))
-        else:
-            self.gleft.fill_(-1)
-        self.unfinished.fill_(1)
-        self.alive.fill_(B)
         d, H = c.hidden_size, c.num_attention_heads
         self.ids.zero_()
         self.ids[:, :Tp].copy_(prompt)
-        if grammar is not None:
-            scan_prompt(grammar, self.ids, Tp, self.gstate, self.gbad, self.gbar, self.grem)
+        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars)
         for l in self.bk:
             self.n_bucketed[l] = 0
             self.bkmax[l].zero_()
@@ -158,10 +135,7 @@ class RFDecoder:
         out = e.forward(buf, labels=None, train=False, rotations=rot, n_real=Tp if Tf > Tp else None, layer_sink=sink)
         last = out['logits'][:, Tp - 1].contiguous()
         self.t_dev.fill_(Tp - 1)
-        if grammar is not None:
-            raise_on_bad_prompt(grammar, self.ids, self.gbad)
-        if self._bars:
-            check_bar_count_start(grammar, n_bars, self.gstate)
+        self.rules.check_prompt(self.ids)
         self._sample(last, sampling)
         return out
 
@@ -172,9 +146,7 @@ class RFDecoder:
         if sampling is None:                 # the caller picks the token (beam search)
             return
         # (min_length and the grammar mask write into the logits: after the trace above)
-        sample_unfused(logits, self.eng.cfg.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, self._stop,
-                       self.unfinished, self.alive, self._grammar, self.gstate, self.gbar, self.grem,
-                       self.gleft if self._bars else None)
+        sample_unfused(logits, self.eng.cfg.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, **self.rules.kwargs())
 
     # ---------------------------------------------------------------- one token
     def step(self, t: int, sampling: dict):

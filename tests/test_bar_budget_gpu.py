@@ -119,7 +119,7 @@ def test_mask_and_advance_equal_the_host_rule(dev, vocab_size):
         lp = logp.to(dev)[:, :vocab_size]                           # a row stride that is not V
         gbar = torch.tensor([s[0] for s in states], device=dev, dtype=torch.int32)
         grem = torch.tensor([s[1] for s in states], device=dev, dtype=torch.int32)
-        ops.budget_mask(lp, vocab_size, g, gbar, grem)
+        ops.rules_mask(lp, vocab_size, None, grammar=g, gbar=gbar, grem=grem)    # the budget alone
         keep = torch.tensor([[bud.allows(bar, rem, int(g.cls[v]), int(bud.slots[v])) for v in range(vocab_size)]
                              for bar, rem in states])
         got = lp.cpu()
@@ -136,7 +136,7 @@ def test_mask_and_advance_equal_the_host_rule(dev, vocab_size):
         grem = torch.full((n,), rem, device=dev, dtype=torch.int32)
         live = torch.ones(n, device=dev, dtype=torch.int32)
         live[-1] = 0
-        ops.budget_advance(ids, t, g, gbar, grem, live)
+        ops.rules_advance(ids, t, stop=(EOS, PAD, 0), unfinished=live, alive=torch.zeros_like(t), grammar=g, gbar=gbar, grem=grem)
         want = [bud.move(bar, rem, int(g.cls[k]), int(bud.slots[k]), int(bud.bars[k])) for k in toks] + [(bar, rem)]
         assert list(zip(gbar.tolist(), grem.tolist())) == want, (bar, rem)
 

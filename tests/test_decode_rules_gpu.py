@@ -1,0 +1,105 @@
+"""The rules of a generation around the unfused samplers (`ops.rules_mask` before, `ops.rules_advance` after): the eos rule, the
+grammar, its bar budget and its bar count in ONE launch each, against the host rules of grammar.TokenGrammar / BarBudget / BarCount.
+The single rules (one group given at a time) are covered beside their features in tests/test_grammar_generate_gpu.py,
+tests/test_bar_budget_gpu.py and tests/test_bar_count_gpu.py; the fused launch against this pair in tests/test_bar_count_gpu.py."""
+import pytest
+import torch
+
+from symbolic_music_generation_amd.grammar import MUSIC_BAR_COUNT_CLASSES, BarCount
+from tests.test_bar_budget_gpu import BAR, EOS, PAD, V, VOC, _padded_grammar
+
+pytestmark = pytest.mark.gpu
+
+
+def _grammar(vocab_size):
+    """the midi grammar with its bar budget and bar count, over a vocabulary padded to vocab_size"""
+    g = _padded_grammar(vocab_size)
+    if g.bar_count is None:
+        BarCount(g, **MUSIC_BAR_COUNT_CLASSES)
+    return g
+
+
+def _allowed(g, state, bar, rem, left, v):
+    """the AND of the three host predicates for token v in a row at (state, bar, rem, left)"""
+    c = int(g.cls[v])
+    return bool((int(g.allow[state]) >> c) & 1) and g.budget.allows(bar, rem, c, int(g.budget.slots[v])) and g.bar_count.allows(left, c)
+
+
+@pytest.mark.parametrize('vocab_size', [V, 2049])
+def test_mask_applies_every_group_in_one_pass(dev, vocab_size):
+    """five rows, one per state of interest; a score row stride that is not V; min_length above and below the rows' length"""
+    from symbolic_music_generation_amd import ops
+    g = _grammar(vocab_size)
+    #        state    bar rem left
+    rows = [('B_D',    0,  0, -1),                                 # bar == 0: the budget leaves the row alone, and so does the count
+            ('B_D',   32,  0,  2),                                 # rem == 0: closers only; bars are owed, so no eos
+            ('M_P',   32,  5, -1),                                 # 0 < rem < bar: durations of at most 5 slots
+            ('B_D',   24,  0,  0),                                 # left == 0: no further bar, eos is the way on
+            ('M_T1',  32,  8,  3)]                                 # left > 0 inside a tuplet
+    i32 = dict(device=dev, dtype=torch.int32)
+    words = [torch.tensor(col, **i32) for col in zip(*[(g.state(s), bar, rem, left) for s, bar, rem, left in rows])]
+    gstate, gbar, grem, gleft = words
+    before = [w.clone() for w in words]
+    rule = torch.tensor([[_allowed(g, g.state(s), bar, rem, left, v) for v in range(vocab_size)] for s, bar, rem, left in rows])
+    assert rule[0, EOS] and not rule[1, EOS] and rule[1, BAR] and rule[3, EOS] and not rule[3, BAR] and not rule[4].all()
+    assert 0 < int(rule[2].sum()) < int((torch.from_numpy(g.cls.astype('int64')) == g.class_names.index('duration')).sum())
+    t = 6
+    t_dev = torch.full((1,), t, **i32)
+    torch.manual_seed(4)
+    for min_length in (t + 1 + 5, t + 1, 0):
+        logp = torch.randn(len(rows), vocab_size + 3)
+        full = logp.to(dev)
+        ops.rules_mask(full[:, :vocab_size], vocab_size, t_dev, stop=(EOS, PAD, min_length), grammar=g, gstate=gstate, gbar=gbar,
+                       grem=grem, gleft=gleft)
+        keep = rule.clone()
+        if t + 1 < min_length:
+            keep[:, EOS] = False                                   # the eos bar
+        got = full.cpu()
+        assert torch.equal(torch.isinf(got[:, :vocab_size]) & (got[:, :vocab_size] < 0), ~keep), min_length
+        want = logp.clone()
+        want[:, :vocab_size][~keep] = float('-inf')
+        assert torch.equal(got.view(torch.int32), want.view(torch.int32)), min_length      # every other score: the same bits
+        assert keep[0, EOS] == (min_length != t + 6)
+    assert all(torch.equal(w, b) for w, b in zip(words, before))   # the mask reads the words only
+
+
+def test_advance_moves_every_word_then_applies_the_stop_rule(dev):
+    """300 rows (more than the 256 threads of the one workgroup), one token each: every kind of token from every kind of row, rows
+    that were finished before the step, rows that emit eos in it, ids beyond the vocabulary"""
+    from symbolic_music_generation_amd import ops
+    g = _grammar(V)
+    bud, cnt = g.budget, g.bar_count
+    toks = [VOC.t2i(t) for t in ('TimeSig_3/4', 'TimeSig_rare', '<melody>', '<bass>', 'd_1/8', 'd_6', 'd_rare', 'p_r', '<bar>', '</tup>',
+                                 '</s>')] + [V + 7]
+    n = 300
+    row_tok = [toks[b % len(toks)] for b in range(n)]
+    states = [(b * 5) % g.n_states for b in range(n)]
+    bars = [((32, 5), (0, 0), (24, 24), (48, 0), (16, 16))[(b // 3) % 5] for b in range(n)]
+    lefts = [(-1, 0, 1, 3)[(b // 2) % 4] for b in range(n)]
+    live = [0 if b % 7 == 3 else 1 for b in range(n)]
+    assert any(k == EOS and u for k, u in zip(row_tok, live)) and any(k == EOS and not u for k, u in zip(row_tok, live))
+    i32 = dict(device=dev, dtype=torch.int32)
+    ids = torch.zeros(n, 5, device=dev, dtype=torch.int64)
+    ids[:, 2] = torch.tensor(row_tok, device=dev)
+    t = torch.full((1,), 2, **i32)
+    gstate, gleft, unfinished = torch.tensor(states, **i32), torch.tensor(lefts, **i32), torch.tensor(live, **i32)
+    gbar, grem = torch.tensor([x[0] for x in bars], **i32), torch.tensor([x[1] for x in bars], **i32)
+    alive = torch.full((1,), -5, **i32)
+    ops.rules_advance(ids, t, stop=(EOS, PAD, 0), unfinished=unfinished, alive=alive, grammar=g, gstate=gstate, gbar=gbar, grem=grem,
+                      gleft=gleft)
+    want_tok, want_words, want_live = [], [], []
+    for b, k in enumerate(row_tok):
+        words = (states[b],) + bars[b] + (lefts[b],)
+        if live[b] and k < V:                                      # the row chose a token of the vocabulary: its words move
+            c = int(g.cls[k])
+            words = (int(g.next[states[b], c]),) + bud.move(*bars[b], c, int(bud.slots[k]), int(bud.bars[k])) + (cnt.move(lefts[b], c),)
+        want_words.append(words)
+        want_tok.append(k if live[b] else PAD)                     # a finished row holds pad and its old words
+        want_live.append(1 if live[b] and k != EOS else 0)
+    assert list(zip(gstate.tolist(), gbar.tolist(), grem.tolist(), gleft.tolist())) == want_words
+    assert unfinished.tolist() == want_live and alive.tolist() == [sum(want_live)]
+    assert ids[:, 2].tolist() == want_tok
+    ids[:, 2] = 0
+    assert not ids.any()                                           # no other column was written
+    moved = [w != (states[b],) + bars[b] + (lefts[b],) for b, w in enumerate(want_words)]
+    assert sum(moved) > n // 3 and not any(m for m, u in zip(moved, live) if not u)
