@@ -428,10 +428,11 @@ int mxl_sample_large(const float* logprobs, int ldl, int V, void* ids, int ld_id
 /* t_dev += 1; rng_ctr += 1 */
 int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
 /* ------------------------------------------------------------------------------------------------------------
- * Rules of a generation.  Four optional groups of per-row state on the device, applied around every sampled token; three entries take
- * them as the same flat argument list (below): mxl_sample_step, mxl_rules_mask, mxl_rules_advance.  A group is off when its state
- * pointer is NULL: unfinished (with alive), gstate (with allow, next), gbar (with grem, slots, bars), gleft.  Within a group either
- * every pointer is given or none; the budget and the count need `cls`; anything else is MXL_EINVAL.
+ * Rules of a generation.  Five optional groups of per-row state on the device, applied around every sampled token; three entries take
+ * the first four as the same flat argument list (below): mxl_sample_step, mxl_rules_mask, mxl_rules_advance, and their mxl_keyed_*
+ * forms take the fifth after it.  A group is off when its state pointer is NULL: unfinished (with alive), gstate (with allow, next),
+ * gbar (with grem, slots, bars), gleft, gkey (with keys, pcs, inkey).  Within a group either every pointer is given or none; the
+ * budget and the count need `cls`; anything else is MXL_EINVAL.
  *
  * stop: eos_id, pad_id, min_length, unfinished, alive -- stopping at eos (HF greedy_search / sample with an eos_token_id).
  *   unfinished (B,) int32 (1 = live; set to 1 before the first sampled token) and alive, one int32 = the number of live rows after
@@ -456,6 +457,18 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  *   music grammar: <bar> and </s>).  A class in count is barred at gleft == 0, a class in end while gleft > 0, and a kept token of a
  *   count class takes 1 from a positive gleft.  Under a bar budget the end class is thereby the only one left when the last bar is
  *   full; without one the rule cannot force the end, it only bars a further bar and an early end.
+ * key: keys, pcs, inkey, gkey (the mxl_keyed_* entries) -- a row whose key is known emits only pitches of that key.  Per row one int32
+ *   word: gkey, -1 = the row has no key and is untouched, 0..23 = the ordinal of its key (the order of the reference's key enum, which
+ *   the in-key ratio metric uses).  Tables: keys (V,) uint8, key token -> ordinal, 0xFF = any other token; pcs (V,) uint8, pitch token
+ *   -> pitch class 0..11, 0xFF = anything the metric does not count as a pitch (rests and the rare-pitch token included: they are never
+ *   barred); inkey (24,) uint16, bit pc of inkey[k] set <=> pitch class pc belongs to key k.  In a row with gkey >= 0 token v is barred
+ *   iff pcs[v] != 0xFF and bit pcs[v] of inkey[gkey] is clear; the group reads neither `cls` nor the grammar state, and works with
+ *   every other group off.  The token is -inf in the same place as under the grammar, the budget and the count.  A kept token with
+ *   keys[tok] != 0xFF sets gkey = keys[tok]; nothing else changes gkey.
+ *   No dead end: every key holds 7 of the 12 pitch classes, and every pitch class has tokens in each of the music vocabularies (midi,
+ *   step, degree), so wherever the grammar or the budget allows "a pitch" -- they judge the class of a token, never which pitch it is --
+ *   a pitch of the row's key remains (besides the rest, which the rule never bars).  The host checks it when the tables are built: every
+ *   key keeps at least one pitch token.
  *
  * The words move along the token a row keeps, after the stop rule: a row that was finished before the step emits pad and keeps its
  * words; the step in which a row emits eos still moves them.  Each row's words are read and written for that row alone.
@@ -488,6 +501,32 @@ int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int
                       int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate, const void* slots,
                       const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count,
                       unsigned end, int* gleft, void* stream);
+/* The three entries above with the key group after the flat rules arguments; with keys = pcs = inkey = gkey = NULL they are those
+ * entries.  In the fused launch the key group is a variant of its own and needs no grammar.  out_probs (B, V) f32 optional, with
+ * do_sample: the renormalised distribution the rows were drawn from, as mxl_sample's (test hook). */
+int mxl_keyed_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                          unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                          float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                          int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
+                          const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
+                          unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
+                          int* gleft, const void* keys, const void* pcs, const void* inkey, int* gkey, float* out_probs, void* stream);
+int mxl_keyed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length,
+                         int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
+                         const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
+                         int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
+                         int* gkey, void* stream);
+int mxl_keyed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length,
+                            int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
+                            const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
+                            int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
+                            int* gkey, void* stream);
+/* Key of every row after columns 0..Tp-1 of ids (B, ld_ids) int64, walked from the key gkey[b] holds at the launch (-1 = none): a
+ * key token sets it.  Ids < 0 (left pads) and ids >= V are skipped.  Columns before `from` only move the key -- a prompt supplies its
+ * key, its pitches are not judged; first_bad[b] = the first column >= from that holds a pitch outside the row's key, where the walk
+ * of that row stops, -1 = none.  from = Tp: the key after the prompt, nothing judged. */
+int mxl_key_scan(const void* ids, int ld_ids, int Tp, int from, int B, int V, const void* keys, const void* pcs, const void* inkey,
+                 int* gkey, int* first_bad, void* stream);
 /* Grammar state of every row after its prompt: ids (B, ld_ids) int64, columns 0..Tp-1 walked from `start`; a column holding an id < 0
  * is skipped (left pad).  first_bad[b] = column of the first token the state bars (or an id >= V), where the walk of that row stops;
  * -1 = the prompt obeys the grammar. */

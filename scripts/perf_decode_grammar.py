@@ -15,6 +15,12 @@ row reaches inside the window, e.g. 1000).  `bars - budget+eos` is the cost of t
 
     python3 scripts/perf_decode_grammar.py --n-bars 1000
     python3 scripts/perf_decode_grammar.py --n-bars 1000 --only bars      # or budget, budget+eos: for rocprofv3 --kernel-trace --stats
+
+`--in-key`: what `generate(in_key=)` costs, at the same shape, without a grammar: `plain` against `key` (the key rule over prompts
+in C major, every row constrained), alternating as above; the tokens per second of each arm are printed beside the step times.
+
+    python3 scripts/perf_decode_grammar.py --in-key
+    python3 scripts/perf_decode_grammar.py --in-key --only key            # or plain
 """
 import os
 import statistics
@@ -31,6 +37,7 @@ V, M, B, Tp, L = 1190, 2048, 64, 256, 2048
 ROUNDS, STEPS = int(os.environ.get('ROUNDS', 6)), int(os.environ.get('STEPS', 400))
 ONLY = sys.argv[sys.argv.index('--only') + 1] if '--only' in sys.argv else None
 N_BARS = int(sys.argv[sys.argv.index('--n-bars') + 1]) if '--n-bars' in sys.argv else None
+IN_KEY = '--in-key' in sys.argv
 
 vocab = MusicVocabulary(pitch_kind='degree')
 assert len(vocab) == V
@@ -62,9 +69,9 @@ ids = prompts()
 samp = dict(do_sample=True, top_k=8, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0)
 
 
-def window(dec, g, steps, stop=None, n_bars=None):
+def window(dec, g, steps, stop=None, n_bars=None, in_key=None):
     """ms per replayed step over `steps` steps right after the prompt pass (ring slots Tp .. Tp + 20 + steps)"""
-    n = dec.begin(ids, L, samp, use_graph=True, grammar=g, stop=stop, n_bars=n_bars)
+    n = dec.begin(ids, L, samp, use_graph=True, grammar=g, stop=stop, n_bars=n_bars, in_key=in_key)
     assert n >= steps + 20
     for _ in range(20):
         dec.replay_once()
@@ -113,8 +120,41 @@ def bars_arms():
         print(f'  {a} - {b} = {d:+.4f} ms/step ({100 * d / med[b]:+.2f} %); run-to-run spread {max(spread.values()):.4f} ms')
 
 
+def key_arms():
+    """the --in-key comparison (module docstring)"""
+    from symbolic_music_generation_amd.generate import check_in_key
+    rule = vocab.key_rule()
+    arms = {'plain': {}, 'key': dict(in_key=rule)}
+    if ONLY:
+        dec = XLDecoderLanes(model.engine, B, L, seed=5, lanes=2)
+        print(f'{ONLY}: {window(dec, None, 50, **arms[ONLY]):.3f} ms per step (50 steps)', flush=True)
+        return
+    decs = {k: XLDecoderLanes(model.engine, B, L, seed=5, lanes=2) for k in arms}
+    for name, dec in decs.items():                                  # warm-up: library attributes, workspaces, graph capture
+        window(dec, None, 20, **arms[name])
+    ms = {k: [] for k in arms}
+    for r in range(ROUNDS):
+        for name in (('plain', 'key') if r % 2 == 0 else ('key', 'plain')):
+            ms[name].append(window(decs[name], None, STEPS, **arms[name]))
+        print(f'round {r}: plain {ms["plain"][-1]:.4f} ms/step, key {ms["key"][-1]:.4f} ms/step', flush=True)
+    for k in arms:
+        out = torch.cat([d.ids[:, :Tp + 20 + STEPS] for d in decs[k].lanes], 0)
+        print(f'{k:6s}: rows that stay in key {int((check_in_key(out, rule, prompt_len=Tp) < 0).sum())} of {B}')
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = {k: max(v) - min(v) for k, v in ms.items()}
+    print(f'C5 decode step, {B} rows, 2 lanes, {STEPS} replayed steps x {ROUNDS} alternating rounds')
+    for k in arms:
+        print(f'  {k:6s} median {med[k]:.4f} ms/step = {1e3 * B / med[k]:.0f} tok/s  min {min(ms[k]):.4f}  max {max(ms[k]):.4f}  '
+              f'spread {spread[k]:.4f}')
+    d = med['key'] - med['plain']
+    print(f'  key - plain = {d:+.4f} ms/step ({100 * d / med["plain"]:+.2f} %); run-to-run spread {max(spread.values()):.4f} ms')
+
+
 with torch.no_grad():
     assert check_grammar(ids, grammar).tolist() == [-1] * B
+    if IN_KEY:
+        key_arms()
+        sys.exit(0)
     if N_BARS is not None:
         bars_arms()
         sys.exit(0)

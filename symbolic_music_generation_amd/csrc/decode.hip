@@ -359,10 +359,12 @@ __global__ __launch_bounds__(256) void decode_bd_kernel(const bf16_t* qr, const 
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int SORT_N = 2048;
 
-// token v under a row's allow word (rules_load below) and, with the bar budget, the slots the row still has free
+// token v under a row's words (rules_load below): its class under the allow word (c: a rule over classes is on), with the bar budget
+// the slots the row still has free, with the key rule the pitch classes of the row's key.  `inkey` has bits 12..31 set, and a token
+// that is no pitch has pcs 0xFF, which tests bit 31: one byte load and one shift, no branch.
 __device__ __forceinline__ bool token_allowed(const unsigned char* cls, uint32_t allow, const unsigned short* slots, int remcap,
-                                              long long v, bool bud) {
-    return ((allow >> cls[v]) & 1u) && (!bud || (int)slots[v] <= remcap);
+                                              const unsigned char* pcs, uint32_t inkey, long long v, bool c, bool bud, bool ink) {
+    return (!c || ((allow >> cls[v]) & 1u)) && (!bud || (int)slots[v] <= remcap) && (!ink || ((inkey >> (pcs[v] & 31)) & 1u));
 }
 
 // the row's next token (returned to every thread of the workgroup).
@@ -371,13 +373,16 @@ __device__ __forceinline__ bool token_allowed(const unsigned char* cls, uint32_t
 // processor order "penalty, min_length, grammar, then the warpers": every warper and the renormalisation see allowed tokens only.
 // BUD (with G): a token whose `bslots` entry exceeds `remcap` (the slots still free; 0xFFFF in an unconstrained row, which admits
 // every entry) is -inf in the same place.
-template <bool G = false, bool BUD = false>
+// INK (with or without G): a pitch token whose class `pcs` is not a bit of `inkey` (the row's key; every bit in a row without one)
+// is -inf in the same place.
+template <bool G = false, bool BUD = false, bool INK = false>
 __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, const long long* ids, int ld_ids,
                                           const int* t_dev, const unsigned long long* rng_ctr, unsigned long long seed,
                                           int do_sample, int top_k, float top_p, float temperature,
                                           float repetition_penalty, float typical_p, float* out_probs, int eos_id = -1,
                                           int min_length = 0, const unsigned char* gcls = nullptr, uint32_t gallow = 0u,
-                                          const unsigned short* bslots = nullptr, int remcap = 0) {
+                                          const unsigned short* bslots = nullptr, int remcap = 0,
+                                          const unsigned char* pcs = nullptr, uint32_t inkey = ~0u) {
     __shared__ float key[SORT_N];
     __shared__ int idx[SORT_N];
     __shared__ int sh_pick;
@@ -385,7 +390,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
     const float* row = logp + (size_t)b * ldl;
     const float invt = 1.f / temperature;
     for (int i = tid; i < SORT_N; i += 256) {
-        if (G) key[i] = (i < V && token_allowed(gcls, gallow, bslots, remcap, i, BUD)) ? row[i] * invt : -INFINITY;
+        if (G || INK) key[i] = (i < V && token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, i, G, BUD, INK)) ? row[i] * invt : -INFINITY;
         else key[i] = i < V ? row[i] * invt : -INFINITY;
         idx[i] = i;
     }
@@ -398,7 +403,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
         const long long* hist = ids + (size_t)b * ld_ids;
         for (int j = tid; j <= tcur; j += 256) {
             const long long tok = hist[j];
-            if (tok >= 0 && tok < V && (!G || token_allowed(gcls, gallow, bslots, remcap, tok, BUD))) {
+            if (tok >= 0 && tok < V && (!(G || INK) || token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, tok, G, BUD, INK))) {
                 const float v = row[tok];
                 key[tok] = (v < 0.f ? v * repetition_penalty : v / repetition_penalty) * invt;
             }
@@ -578,9 +583,9 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The rules of one generation (include/musicxl.h, "Rules of a generation"), passed to kernels by value.  Four groups, each off when
-// its state pointer (unfinished / gstate / gbar / gleft) is NULL; the budget and the count read the token classes `cls` of the
-// grammar group and nothing else of it.
+// The rules of one generation (include/musicxl.h, "Rules of a generation"), passed to kernels by value.  Five groups, each off when
+// its state pointer (unfinished / gstate / gbar / gleft / gkey) is NULL; the budget and the count read the token classes `cls` of the
+// grammar group and nothing else of it, the key reads nothing of it at all.
 //   stop     HF greedy_search / sample: a finished row emits pad, a live row that emits eos is finished; eos barred below min_length
 //   grammar  a token class automaton: cls (V,) token -> class, allow (S,) bit c = class c may follow in state s, next (S, C) successor
 //   budget   grammar.BarBudget: per row `bar` (bar length in slots, 0 = unconstrained) and `rem` (slots still free in the open
@@ -589,6 +594,10 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 //   count    grammar.BarCount: per row `left`, the bars the row may still open (< 0 = no limit, the row is untouched).  A class in
 //            `count` (<bar>) is barred at left == 0, a class in `end` (</s>) while left > 0, and a kept token of a `count` class
 //            takes 1 from a positive left
+//   key      grammar.KeyRule: per row `key`, the ordinal 0..23 of the row's key (< 0 = none, the row is untouched).  keys (V,) uint8:
+//            Key_* token -> ordinal, 0xFF = no key token; pcs (V,) uint8: pitch token -> pitch class 0..11, 0xFF = no pitch (rests and
+//            the rare pitch included); inkey (24,) uint16: bit pc = pitch class pc belongs to the key.  A pitch outside the row's key is
+//            barred, and a kept key token sets the row's key
 // The next rule is one more group here, one line in each of rules_load / rules_move and one in make_rules.
 // ---------------------------------------------------------------------------------------------------------------
 struct DecodeRules {
@@ -607,6 +616,10 @@ struct DecodeRules {
     int* grem;
     uint32_t count, end;
     int* gleft;
+    const unsigned char* keys;
+    const unsigned char* pcs;
+    const unsigned short* inkey;
+    int* gkey;
 };
 
 constexpr int BUDGET_NONE = 0xFFFF;          // slots: unknown length (beyond any rem); bars: not a time signature
@@ -631,17 +644,25 @@ __device__ __forceinline__ uint32_t barcount_deny(int left, uint32_t count, uint
 __device__ __forceinline__ int barcount_move(int left, int c, uint32_t count) {
     return (left > 0 && ((count >> c) & 1u)) ? left - 1 : left;
 }
+constexpr int N_KEYS = 24;
+constexpr uint32_t KEY_ANY = ~0u;            // the pitch-class word of a row without a key
+constexpr int KEY_NONE = 0xFF;               // keys: no key token; pcs: no pitch
+// the pitch classes a row in `key` admits, as token_allowed reads them: bits 0..11 from the table, every bit above them set
+__device__ __forceinline__ uint32_t key_word(const unsigned short* inkey, int key) {
+    return (unsigned)key < (unsigned)N_KEYS ? ((uint32_t)inkey[key] | 0xFFFFF000u) : KEY_ANY;
+}
 
 // The words of row b and what they admit: `allow` has a bit per class the row may emit (every bit without a grammar), `remcap` is
-// the largest slots entry.  g / bud / cnt: which groups are on -- compile-time constants in the fused kernel, pointer tests in the
-// unfused pair; everything here inlines and folds on them.
+// the largest slots entry, `inkey` a bit per pitch class (key_word).  g / bud / cnt / ink: which groups are on -- compile-time
+// constants in the fused kernel, pointer tests in the unfused pair; everything here inlines and folds on them.
 struct RowWords {
     int gs, bar, rem, left;
     uint32_t allow;
     int remcap;
+    uint32_t inkey;
 };
-__device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool g, bool bud, bool cnt) {
-    RowWords w{0, 0, 0, -1, ~0u, BUDGET_NONE};
+__device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool g, bool bud, bool cnt, bool ink) {
+    RowWords w{0, 0, 0, -1, ~0u, BUDGET_NONE, KEY_ANY};
     if (g) { w.gs = r.gstate[b]; w.allow = r.allow[w.gs]; }
     if (bud) {
         w.bar = r.gbar[b];
@@ -650,12 +671,13 @@ __device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool
         w.remcap = budget_remcap(w.bar, w.rem);
     }
     if (cnt) { w.left = r.gleft[b]; w.allow &= ~barcount_deny(w.left, r.count, r.end); }
+    if (ink) w.inkey = key_word(r.inkey, r.gkey[b]);
     return w;
 }
 // row b moves along `tok`, a token of the vocabulary that the row chose itself (a row finished before the step emits pad, which is
 // not its choice and need not be a token its state allows: such a row keeps its words)
-__device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int b, long long tok, bool g, bool bud, bool cnt) {
-    const int c = r.cls[tok];
+__device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int b, long long tok, bool g, bool bud, bool cnt, bool ink) {
+    const int c = (g || bud || cnt) ? r.cls[tok] : 0;
     if (g) r.gstate[b] = r.next[w.gs * r.C + c];
     if (bud) {
         budget_move(w.bar, w.rem, c, r.slots[tok], r.bars[tok], r.opens);
@@ -663,6 +685,10 @@ __device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int
         r.grem[b] = w.rem;
     }
     if (cnt) r.gleft[b] = barcount_move(w.left, c, r.count);
+    if (ink) {
+        const int k = r.keys[tok];
+        if (k != KEY_NONE) r.gkey[b] = k;            // KeyRule.move: a key token sets the row's key, nothing else changes it
+    }
 }
 
 __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl, int V, long long* ids, int ld_ids,
@@ -680,25 +706,25 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl,
 // head's raw logits instead of log-probabilities when no repetition penalty is in force: every other warper, the argmax and the
 // renormalised draw are invariant under the per-row shift log-softmax applies.
 //
-// G / BUD / CNT: the grammar, budget and count groups of `r` as compile-time variants (BUD and CNT ride on G); the stop group is
-// the runtime test of r.unfinished it has always been.  The row's words select the allow word and remcap the sampler applies
+// G / BUD / CNT / INK: the grammar, budget, count and key groups of `r` as compile-time variants (BUD and CNT ride on G, INK stands
+// alone); the stop group is the runtime test of r.unfinished it has always been.  The row's words select the allow word and remcap the sampler applies
 // (rules_load), and thread 0 moves them along the token the row keeps (rules_move).  The move sits AFTER the eos rule: a row that
 // was finished before this step emits pad and its words stay frozen; the step in which a live row emits eos still moves them, so a
 // finished row of the music grammar rests in END.  The words are per-row: row b's workgroup is their only reader and writer within a
 // launch, and the next launch on the stream sees them by stream order -- there is no hand-off between workgroups here beyond the
 // arrival counter below.
-template <bool G, bool BUD, bool CNT>
+template <bool G, bool BUD, bool CNT, bool INK>
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, int ldl, int V, long long* ids, int ld_ids,
                                                           int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                           int do_sample, int top_k, float top_p, float temperature,
                                                           float repetition_penalty, float typical_p, const bf16_t* E, bf16_t* emb_out,
-                                                          int d, float scale, int* counter, DecodeRules r) {
+                                                          int d, float scale, int* counter, float* out_probs, DecodeRules r) {
     static_assert(G || !(BUD || CNT), "the bar budget and the bar count ride on the grammar");
     int* const unfinished = r.unfinished;
-    const RowWords w = rules_load(r, blockIdx.x, G, BUD, CNT);
-    int tok = sample_row<G, BUD>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
-                                 repetition_penalty, typical_p, nullptr, unfinished ? r.eos_id : -1, unfinished ? r.min_length : 0,
-                                 r.cls, w.allow, r.slots, w.remcap);
+    const RowWords w = rules_load(r, blockIdx.x, G, BUD, CNT, INK);
+    int tok = sample_row<G, BUD, INK>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
+                                      repetition_penalty, typical_p, out_probs, unfinished ? r.eos_id : -1,
+                                      unfinished ? r.min_length : 0, r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey);
     const int b = blockIdx.x, tid = threadIdx.x;
     __shared__ int sh_tok, sh_live;
     bool was_live = true;                       // (thread 0) the token is the row's own choice
@@ -717,7 +743,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         __syncthreads();
         tok = sh_tok;
     }
-    if (G && tid == 0 && was_live && tok >= 0 && tok < V) rules_move(r, w, b, tok, G, BUD, CNT);
+    if ((G || INK) && tid == 0 && was_live && tok >= 0 && tok < V) rules_move(r, w, b, tok, G, BUD, CNT, INK);
     if (tid == 0) ids[(size_t)b * ld_ids + *t_dev + 1] = tok;
     const int id = (tok < 0 || tok >= V) ? 0 : tok;
     for (int c = tid; c < (d >> 3); c += 256) {
@@ -765,11 +791,11 @@ __global__ __launch_bounds__(256) void rules_mask_kernel(float* scores, int ldl,
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)B * V) return;
     const int b = (int)(i / V), v = (int)(i - (long long)b * V);
-    const bool bud = r.gbar != nullptr;
+    const bool bud = r.gbar != nullptr, ink = r.gkey != nullptr;
     bool ok = true;
-    if (r.cls) {
-        const RowWords w = rules_load(r, b, r.gstate != nullptr, bud, r.gleft != nullptr);
-        ok = token_allowed(r.cls, w.allow, r.slots, w.remcap, v, bud);
+    if (r.cls || ink) {
+        const RowWords w = rules_load(r, b, r.gstate != nullptr, bud, r.gleft != nullptr, ink);
+        ok = token_allowed(r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, v, r.cls != nullptr, bud, ink);
     }
     if (r.min_length > 0 && v == r.eos_id && *t_dev + 1 < r.min_length) ok = false;
     if (!ok) scores[(size_t)b * ldl + v] = -INFINITY;
@@ -782,13 +808,13 @@ __global__ __launch_bounds__(256) void rules_advance_kernel(long long* ids, int 
     __shared__ int part[4];
     const int tid = threadIdx.x;
     const int t = *t_dev;
-    const bool g = r.gstate != nullptr, bud = r.gbar != nullptr, cnt = r.gleft != nullptr;
+    const bool g = r.gstate != nullptr, bud = r.gbar != nullptr, cnt = r.gleft != nullptr, ink = r.gkey != nullptr;
     int n = 0;
     for (int b = tid; b < B; b += 256) {
         long long* p = ids + (size_t)b * ld_ids + t;
         const long long tok = *p;
         int live = r.unfinished ? r.unfinished[b] : 1;
-        if (live && r.cls && tok >= 0 && tok < V) rules_move(r, rules_load(r, b, g, bud, cnt), b, tok, g, bud, cnt);
+        if (live && (r.cls || ink) && tok >= 0 && tok < V) rules_move(r, rules_load(r, b, g, bud, cnt, ink), b, tok, g, bud, cnt, ink);
         if (r.unfinished) {
             if (!live) *p = r.pad_id;
             else if (tok == r.eos_id) live = 0;
@@ -861,6 +887,34 @@ __global__ __launch_bounds__(64) void budget_scan_kernel(const long long* ids, i
         }
     }
     if (lane == 0) { gbar[b] = bar; grem[b] = rem; first_bad[b] = bad; }
+}
+
+// key of every row after columns 0..Tp-1, from the key gkey[b] holds at the launch (KeyRule.walk), as the two scans above: one wave
+// per row, 64 columns at a time.  Ids < 0 (left pads) and ids beyond the vocabulary are skipped.  Columns before `from` only move the
+// key (a prompt supplies its key, its pitches are not judged); first_bad[b] = the first column >= from holding a pitch outside the
+// row's key, where the walk of that row stops, -1 = none.
+__global__ __launch_bounds__(64) void key_scan_kernel(const long long* ids, int ld_ids, int Tp, int from, int B, int V,
+                                                      const unsigned char* keys, const unsigned char* pcs,
+                                                      const unsigned short* inkey, int* gkey, int* first_bad) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long* row = ids + (size_t)b * ld_ids;
+    int key = gkey[b], bad = -1;
+    for (int base = 0; base < Tp && bad < 0; base += 64) {
+        const int col = base + lane;
+        int kp = KEY_NONE | (KEY_NONE << 8);                     // keys entry | pcs entry << 8
+        if (col < Tp) {
+            const long long tok = row[col];
+            if (tok >= 0 && tok < V) kp = (int)keys[tok] | ((int)pcs[tok] << 8);
+        }
+        const int n = min(64, Tp - base);
+        for (int j = 0; j < n; j++) {
+            const int kj = __shfl(kp, j, 64);
+            const int k = kj & 0xFF, pc = kj >> 8;
+            if (base + j >= from && !((key_word(inkey, key) >> (pc & 31)) & 1u)) { bad = base + j; break; }
+            if (k != KEY_NONE) key = k;
+        }
+    }
+    if (lane == 0) { gkey[b] = key; first_bad[b] = bad; }
 }
 
 }  // namespace
@@ -989,21 +1043,56 @@ extern "C" int mxl_sample(const float* logprobs, int ldl, int V, void* ids, int 
         int *grem, unsigned count, unsigned end, int *gleft
 #define RULES_ARGS \
     eos_id, pad_id, min_length, unfinished, alive, cls, allow, next, C, gstate, slots, bars, opens, need_free, need_full, gbar, grem, count, end, gleft
+// the key group, which follows them in the mxl_keyed_* entries
+#define KEY_PARAMS const void *keys, const void *pcs, const void *inkey, int *gkey
+#define KEY_ARGS keys, pcs, inkey, gkey
+#define KEY_OFF nullptr, nullptr, nullptr, nullptr
 
 // the one check of those arguments, before any launch: within a group all pointers or none; budget and count read `cls`.
 // fused: the launch that also samples -- budget and count ride on the grammar there, and arrivals and live rows share one 32-bit word
-static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS) {
+static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS, KEY_PARAMS) {
     MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr));
     MXL_CHECK_ARG((allow == nullptr) == (gstate == nullptr) && (next == nullptr) == (gstate == nullptr));
     MXL_CHECK_ARG(!gstate || (cls && C >= 1 && C <= 32));
     MXL_CHECK_ARG((slots == nullptr) == (gbar == nullptr) && (bars == nullptr) == (gbar == nullptr) && (grem == nullptr) == (gbar == nullptr));
     MXL_CHECK_ARG(!(gbar || gleft) || cls);
+    MXL_CHECK_ARG((keys == nullptr) == (gkey == nullptr) && (pcs == nullptr) == (gkey == nullptr) && (inkey == nullptr) == (gkey == nullptr));
     if (fused) MXL_CHECK_ARG(!(gbar || gleft) || gstate);
     if (fused && unfinished) MXL_CHECK_ARG(B <= 32767);
     if (!unfinished && fused) { eos_id = -1; pad_id = 0; min_length = 0; }
     *r = DecodeRules{eos_id, pad_id, min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
                      (const unsigned char*)next, C, gstate, (const unsigned short*)slots, (const unsigned short*)bars, opens, need_free,
-                     need_full, gbar, grem, count, end, gleft};
+                     need_full, gbar, grem, count, end, gleft, (const unsigned char*)keys, (const unsigned char*)pcs,
+                     (const unsigned short*)inkey, gkey};
+    return MXL_OK;
+}
+
+extern "C" int mxl_keyed_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                                     unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                                     float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                                     int* counter, RULES_PARAMS, KEY_PARAMS, float* out_probs, void* stream) {
+    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
+    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
+    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
+    DecodeRules r;
+    if (const int e = make_rules(&r, B, true, RULES_ARGS, KEY_ARGS)) return e;
+#define LAUNCH_K(G, BUD, CNT, INK)                                                                                                       \
+    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT, INK>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V,               \
+                       (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p, \
+                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, out_probs, r)
+#define LAUNCH(G, BUD, CNT)                   \
+    do {                                      \
+        if (gkey) LAUNCH_K(G, BUD, CNT, true); \
+        else LAUNCH_K(G, BUD, CNT, false);    \
+    } while (0)
+    if (!gstate) LAUNCH(false, false, false);
+    else if (!gbar && !gleft) LAUNCH(true, false, false);
+    else if (!gleft) LAUNCH(true, true, false);
+    else if (!gbar) LAUNCH(true, false, true);
+    else LAUNCH(true, true, true);
+#undef LAUNCH
+#undef LAUNCH_K
+    MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
 
@@ -1011,48 +1100,53 @@ extern "C" int mxl_sample_step(const float* scores, int ldl, int V, void* ids, i
                                unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                                float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
                                int* counter, RULES_PARAMS, void* stream) {
-    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
-    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
-    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
-    DecodeRules r;
-    if (const int e = make_rules(&r, B, true, RULES_ARGS)) return e;
-#define LAUNCH(G, BUD, CNT)                                                                                                          \
-    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V, (long long*)ids, \
-                       ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p,             \
-                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, r)
-    if (!gstate) LAUNCH(false, false, false);
-    else if (!gbar && !gleft) LAUNCH(true, false, false);
-    else if (!gleft) LAUNCH(true, true, false);
-    else if (!gbar) LAUNCH(true, false, true);
-    else LAUNCH(true, true, true);
-#undef LAUNCH
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
+    return mxl_keyed_sample_step(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, B, do_sample, top_k, top_p, temperature,
+                                 repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_OFF, nullptr, stream);
 }
 
-extern "C" int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, void* stream) {
+extern "C" int mxl_keyed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, void* stream) {
     MXL_CHECK_ARG(scores && B > 0 && V > 0 && ldl >= V && (t_dev || min_length <= 0));
     const long long n = (long long)B * V;
     MXL_CHECK_ARG(n <= (1LL << 38));
     DecodeRules r;
-    if (const int e = make_rules(&r, B, false, RULES_ARGS)) return e;
-    if (!r.cls && (r.min_length <= 0 || r.eos_id < 0 || r.eos_id >= V)) return MXL_OK;          // nothing to bar
+    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS)) return e;
+    if (!r.cls && !r.gkey && (r.min_length <= 0 || r.eos_id < 0 || r.eos_id >= V)) return MXL_OK;          // nothing to bar
     hipLaunchKernelGGL(rules_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V, t_dev, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
 
-extern "C" int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, void* stream) {
-    MXL_CHECK_ARG(ids && t_dev && B > 0 && (V > 0 || !cls));
+extern "C" int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, void* stream) {
+    return mxl_keyed_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_OFF, stream);
+}
+
+extern "C" int mxl_keyed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, void* stream) {
+    MXL_CHECK_ARG(ids && t_dev && B > 0 && (V > 0 || !(cls || gkey)));
     DecodeRules r;
-    if (const int e = make_rules(&r, B, false, RULES_ARGS)) return e;
-    if (!r.cls && !r.unfinished) return MXL_OK;                                                  // nothing to move
+    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS)) return e;
+    if (!r.cls && !r.gkey && !r.unfinished) return MXL_OK;                                       // nothing to move
     hipLaunchKernelGGL(rules_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long long*)ids, ld_ids, t_dev, B, V, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
+
+extern "C" int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, void* stream) {
+    return mxl_keyed_rules_advance(ids, ld_ids, t_dev, B, V, RULES_ARGS, KEY_OFF, stream);
+}
 #undef RULES_PARAMS
 #undef RULES_ARGS
+#undef KEY_PARAMS
+#undef KEY_ARGS
+#undef KEY_OFF
+
+extern "C" int mxl_key_scan(const void* ids, int ld_ids, int Tp, int from, int B, int V, const void* keys, const void* pcs,
+                            const void* inkey, int* gkey, int* first_bad, void* stream) {
+    MXL_CHECK_ARG(ids && B > 0 && V > 0 && Tp >= 0 && ld_ids >= Tp && from >= 0 && keys && pcs && inkey && gkey && first_bad);
+    hipLaunchKernelGGL(key_scan_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const long long*)ids, ld_ids, Tp, from, B, V,
+                       (const unsigned char*)keys, (const unsigned char*)pcs, (const unsigned short*)inkey, gkey, first_bad);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
 
 extern "C" int mxl_grammar_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* allow,
                                 const void* next, int C, int start, int* gstate, int* first_bad, void* stream) {

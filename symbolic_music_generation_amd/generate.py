@@ -53,13 +53,14 @@ def sampling_config(do_sample: bool = False, top_k: Optional[int] = None, top_p:
 def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch.Tensor, rng: torch.Tensor, seed: int, sampling: dict,
                    stop: Optional[tuple] = None, unfinished: Optional[torch.Tensor] = None, alive: Optional[torch.Tensor] = None,
                    grammar=None, gstate: Optional[torch.Tensor] = None, gbar: Optional[torch.Tensor] = None,
-                   grem: Optional[torch.Tensor] = None, gleft: Optional[torch.Tensor] = None):
+                   grem: Optional[torch.Tensor] = None, gleft: Optional[torch.Tensor] = None, in_key=None,
+                   gkey: Optional[torch.Tensor] = None):
     """The sampler tail as separate launches (what mxl_sample_step does in one): next token of every row from the first V columns
     of `scores` -> ids[:, t + 1], position and RNG counters advanced.  stop = (eos, pad, min_length) with unfinished / alive and
     grammar with gstate are optional, and a grammar with a bar budget takes gbar / grem as well; gleft (the bars every row may
-    still open) turns the grammar's bar count on (ops.rules_in_force).  The mask writes into `scores` in place.  Four launches, two
-    where no rule is in force."""
-    rules = ops.rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft)
+    still open) turns the grammar's bar count on, in_key (a grammar.KeyRule) with gkey the key rule (ops.rules_in_force).  The mask
+    writes into `scores` in place.  Four launches, two where no rule is in force."""
+    rules = ops.rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey)
     sc = scores[:, :V] if scores.shape[1] != V else scores
     # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the mask: -inf
     # stays -inf under it, so the result is the same
@@ -160,6 +161,30 @@ def bar_count_config(n_bars, batch: int, grammar, stop: Optional[tuple], repeat:
     return k.clamp(-1, 2 ** 31 - 1).to(torch.int32).repeat_interleave(int(repeat), 0).contiguous()
 
 
+def key_config(in_key, key, batch: int, vocab_size: int, repeat: int = 1) -> Optional[torch.Tensor]:
+    """`in_key` / `key` of a generation as the decoders take them: None (no rule, or every row takes the key of its prompt), or a
+    (batch * repeat,) int32 CPU tensor of key ordinals, -1 = the row is unconstrained -- it overrides the prompts' keys.  key: a key
+    name ('AMinor' or 'Key_AMinor') or ordinal in vocab.KEY_NAMES, or a sequence or tensor of `batch` of them, one per prompt, with
+    None / -1 for an unconstrained row; `repeat` = num_return_sequences.  Raises MusicXLError for a rule over another vocabulary and
+    ValueError for a key without the rule, an unknown key or a wrong length."""
+    from .grammar import key_ordinal
+    if in_key is None:
+        if key is not None:
+            raise ValueError('key= needs in_key=, the key rule (tokenizer.key_rule())')
+        return None
+    if in_key.vocab_size != int(vocab_size):
+        raise MusicXLError(f'the key rule spans {in_key.vocab_size} tokens, the model has vocab_size {int(vocab_size)}')
+    if key is None:
+        return None
+    if isinstance(key, torch.Tensor):
+        key = key.detach().cpu().reshape(-1).tolist() if key.dim() else int(key)
+    one = isinstance(key, (str, int)) and not isinstance(key, bool)
+    ks = [key_ordinal(key)] * batch if one else [key_ordinal(k) for k in key]
+    if len(ks) != batch:
+        raise ValueError(f'key holds {len(ks)} entries for {batch} prompts: give one key or one per prompt')
+    return torch.tensor(ks, dtype=torch.int32).repeat_interleave(int(repeat), 0).contiguous()
+
+
 def check_bar_count_start(grammar, n_bars: torch.Tensor, gstate: torch.Tensor):
     """rows asked for n_bars = 0 whose prompt stops where only a bar can follow (BarCount.needs_bar: the music grammar's header
     states -- no bar is open yet, and a song has one): MusicXLError naming the row, since every token would be barred there.
@@ -197,10 +222,11 @@ class RowRules:
     """The rules of one generation and their per-row state on the device, as every decoder keeps them: `stop` = (eos, pad,
     min_length) or None, `grammar` (with its bar budget, if it has one) or None, `bars` = the grammar's bar count is on.  One packed
     int32 buffer holds the words the sampler launches move -- unfinished (1 = live), gstate (automaton state), gbar / grem (bar
-    length and free slots), gleft (bars the row may still open, < 0 = no limit), each (B,) -- then gbad (2, B), the first prompt
+    length and free slots), gleft (bars the row may still open, < 0 = no limit), gkey (the row's key under `in_key`, a
+    grammar.KeyRule; < 0 = none), each (B,) -- then gbad (2, B), the first prompt
     column that breaks the grammar / the budget, and alive (1,), the live-row count.  A further rule is a row here, a line in `start`
     and a key in `kwargs` / `graph_key`."""
-    WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft')
+    WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey')
     STATE = WORDS + ('alive',)
 
     def __init__(self, batch: int, dev):
@@ -212,14 +238,23 @@ class RowRules:
         self.alive = self.buf[(n + 2) * batch:]
         self.unfinished.fill_(1)
         self.gleft.fill_(-1)
-        self.stop = self.grammar = self.n_bars = None
+        self.gkey.fill_(-1)
+        self.stop = self.grammar = self.n_bars = self.in_key = None
         self.bars = False
 
-    def start(self, ids: torch.Tensor, Tp: int, vocab_size: int, stop: Optional[tuple], grammar, n_bars: Optional[torch.Tensor]):
+    def start(self, ids: torch.Tensor, Tp: int, vocab_size: int, stop: Optional[tuple], grammar, n_bars: Optional[torch.Tensor],
+              in_key=None, keys: Optional[torch.Tensor] = None):
         """the rules of a new generation over the prompts in columns 0..Tp-1 of ids (ids < 0: left pads, skipped): every row live,
         its grammar state and, under a bar budget, its bar length and free slots after its prompt computed on the device, gleft =
-        n_bars ((B,) int32 from bar_count_config, or None: no bar count)"""
+        n_bars ((B,) int32 from bar_count_config, or None: no bar count).  in_key (a grammar.KeyRule, or None: no key rule): gkey =
+        keys ((B,) int32 from key_config), or, without them, the last key token of every row's prompt, found on the device (-1 in a
+        row without one); the prompt's pitches are not judged."""
         check_grammar_args(grammar, vocab_size, stop)
+        if in_key is not None and in_key.vocab_size != int(vocab_size):
+            raise MusicXLError(f'the key rule spans {in_key.vocab_size} tokens, the model has vocab_size {int(vocab_size)}')
+        if keys is not None and (in_key is None or keys.numel() != self.B):
+            raise MusicXLError('keys need the key rule and one entry per row (key_config)')
+        self.in_key = in_key
         if n_bars is not None and (grammar is None or grammar.bar_count is None or stop is None or n_bars.numel() != self.B):
             raise MusicXLError('n_bars needs a grammar with a bar count, the eos rule and one entry per row (bar_count_config)')
         self.stop, self.grammar, self.n_bars, self.bars = stop, grammar, n_bars, n_bars is not None
@@ -235,6 +270,12 @@ class RowRules:
                 ops.budget_scan(ids, Tp, grammar, self.gbar, self.grem, self.gbad[1])
             else:
                 self.gbad[1].fill_(-1)
+        if keys is not None:
+            self.gkey.copy_(keys.to(torch.int32))
+        else:
+            self.gkey.fill_(-1)
+            if in_key is not None:
+                ops.key_scan(ids, Tp, in_key, self.gkey, torch.empty_like(self.gkey))
 
     def check_prompt(self, ids: torch.Tensor):
         """after `start`: raises for a prompt that breaks the grammar or the bar budget, or that leaves a row asked for 0 bars where
@@ -247,17 +288,19 @@ class RowRules:
     def kwargs(self) -> dict:
         """the rules keywords of ops.sample_step and sample_unfused"""
         return dict(stop=self.stop, unfinished=self.unfinished, alive=self.alive, grammar=self.grammar, gstate=self.gstate,
-                    gbar=self.gbar, grem=self.grem, gleft=self.gleft if self.bars else None)
+                    gbar=self.gbar, grem=self.grem, gleft=self.gleft if self.bars else None, in_key=self.in_key, gkey=self.gkey)
 
     def graph_key(self, dev) -> tuple:
         """what a captured sampler launch holds of the rules: which of them are on, the identity of the grammar's and the budget's
-        device tables and their class masks.  The per-row words are step state and not part of it."""
+        device tables and their class masks, the presence of the key rule and the identity of its tables.  The per-row words, the
+        keys among them, are step state and not part of it."""
         g = self.grammar
         return (self.stop,
                 None if g is None else tuple(t.data_ptr() for t in g.to(dev)) + (g.n_classes,),
                 None if g is None or g.budget is None else
                 tuple(t.data_ptr() for t in g.budget.to(dev)) + (g.budget.opens, g.budget.need_free, g.budget.need_full),
-                (g.bar_count.count, g.bar_count.end) if self.bars else None)
+                (g.bar_count.count, g.bar_count.end) if self.bars else None,
+                None if self.in_key is None else tuple(t.data_ptr() for t in self.in_key.to(dev)))
 
     def snapshot(self) -> torch.Tensor:
         return self.buf.clone()
@@ -331,6 +374,42 @@ def bars_after_prompt(ids: torch.Tensor, grammar, prompt_len: Optional[int] = No
     return hit.sum(1).cpu().to(torch.int64)
 
 
+def check_in_key(ids: torch.Tensor, rule, prompt_len: Optional[int] = None, attention_mask: Optional[torch.Tensor] = None,
+                 key=None) -> torch.Tensor:
+    """(B,) int64 on the CPU, as check_grammar: for every row of ids (B, T) the first generated column (>= prompt_len) that holds a
+    pitch outside the row's key under `rule` (a grammar.KeyRule, `tokenizer.key_rule()`), -1 = none -- what `generate(in_key=rule)`
+    keeps at -1.  The row's key is the last key token before that column, the generated ones included; the prompt only supplies
+    the key, its pitches are not judged, and a row without a key is clean.  prompt_len: the width of the prompt; default the width
+    of attention_mask (the mask given to generate), else 0 = every column is judged.  attention_mask (B, Tp): left-pad columns (0)
+    are skipped.  key: as generate's `key=` (one key or one per row, None / -1 = unconstrained): the rows start the generated part
+    in these keys whatever their prompts say.  Rows on the GPU are walked there (mxl_key_scan), host tensors by KeyRule.walk."""
+    ids = torch.as_tensor(ids)
+    if ids.dim() == 1:
+        ids = ids.view(1, -1)
+    x = ids.to(torch.int64).clone()
+    if attention_mask is not None:
+        m = torch.as_tensor(attention_mask).to(x.device)
+        x[:, :m.shape[1]].masked_fill_(m == 0, -1)
+    if prompt_len is None:
+        prompt_len = 0 if attention_mask is None else int(torch.as_tensor(attention_mask).shape[1])
+    prompt_len = int(prompt_len)
+    start = key_config(rule, key, x.shape[0], rule.vocab_size)
+    if start is not None:                                # the given keys stand for the prompt
+        x, off = x[:, prompt_len:], prompt_len
+        prompt_len = 0
+    else:
+        start, off = torch.full((x.shape[0],), -1, dtype=torch.int32), 0
+    if not x.is_cuda:
+        bad = torch.tensor([rule.walk(r, int(k), prompt_len)[1] for r, k in zip(x, start.tolist())], dtype=torch.int64)
+    else:
+        x = x.contiguous()
+        gkey = start.to(x.device)
+        first = torch.empty_like(gkey)
+        ops.key_scan(x, x.shape[1], rule, gkey, first, check_from=prompt_len)
+        bad = first.cpu().to(torch.int64)
+    return torch.where(bad >= 0, bad + off, bad)
+
+
 class _AlivePoll:
     """live-row counts of one decoder read back without stalling its stream: after each chunk of steps a non-blocking copy of
     `alive` into pinned host memory and an event; `wait(keep)` blocks until at most `keep` such reads are outstanding"""
@@ -390,17 +469,18 @@ def run_until_finished(decoders, n: int, chunk: int = STOP_CHUNK) -> list:
 
 
 def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool, n_pad, stop, stop_chunk,
-                 grammar, n_bars=None) -> torch.Tensor:
+                 grammar, n_bars=None, in_key=None, keys=None) -> torch.Tensor:
     """The body of `generate` for one decoder (lanes = [dec], streams = [None]) or for an XLDecoderLanes with its lanes and their
     streams: `dec.begin`, then every remaining step through `dec.replay_once` -- or, with stop = (eos, pad, min_length), each lane
     on its own until its rows have finished (run_until_finished) -- then the lanes' rows in order, cut to the width of the longest
     lane and right-filled with pad where a lane stopped earlier.  Sets `steps_run` on every lane and on dec (the most of any
     lane).  The prompt columns of left-padded prompts (n_pad) come back as given.  n_bars: None or one int32 per row
-    (bar_count_config); each lane takes its rows' entries."""
+    (bar_count_config); each lane takes its rows' entries.  in_key / keys: the key rule and None or one int32 per row (key_config),
+    handed on the same way."""
     Tp = prompt.shape[1]
     if max_length - Tp <= 0:
         return prompt[:, :max_length]
-    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar, n_bars)
+    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar, n_bars, in_key, keys)
     if stop is None:
         for _ in range(n):
             dec.replay_once()
@@ -470,7 +550,7 @@ class XLDecoder:
         # the rules of the current generation (eos, grammar, bar budget, bar count) and their per-row words, which the sampler
         # launch reads and moves; the words are readable here under their names
         self.rules = RowRules(batch, dev)
-        self.unfinished, self.gstate, self.gbar, self.grem, self.gleft, self.alive = (getattr(self.rules, k) for k in RowRules.STATE)
+        self.unfinished, self.gstate, self.gbar, self.grem, self.gleft, self.gkey, self.alive = (getattr(self.rules, k) for k in RowRules.STATE)
 
     def _tables(self):
         if self.rd is None:
@@ -489,7 +569,7 @@ class XLDecoder:
 
     # ---------------------------------------------------------------- prompt
     def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None,
-                grammar=None, n_bars: Optional[torch.Tensor] = None):
+                grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None):
         """Whole prompt through the training-shape kernels with zero mems (upstream first step), rings filled from the
         per-layer qkv buffers, first new token sampled from the last position.
         n_pad: (B,) int32 device tensor, left-padded prompts: the first n_pad[b] columns of row b are pads.  Their K / V are zero
@@ -500,7 +580,9 @@ class XLDecoder:
         prompt that breaks the grammar raises.  With a bar budget the same holds for the rows' bar lengths and free slots, and a
         prompt that overfills or underfills a bar raises.
         n_bars: None, or (B,) int32 from bar_count_config: the bars every row may still open (the grammar's bar count); it is the
-        start value of `gleft`, which the sampler launches move."""
+        start value of `gleft`, which the sampler launches move.
+        in_key: a grammar.KeyRule or None; keys: None (every row starts in the key of its prompt, found on the device, pads
+        skipped) or (B,) int32 from key_config; the start value of `gkey`, which a generated key token moves."""
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
@@ -515,7 +597,7 @@ class XLDecoder:
             pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
             self.ids[:, :Tp].masked_fill_(pad, -1)
             x = x.masked_fill(pad, 0)
-        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars)
+        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars, in_key, keys)
         sink_kc, sink_vc = self.kc, self.vc
 
         def kv_sink(l, qkv):
@@ -649,19 +731,20 @@ class XLDecoder:
     # ---------------------------------------------------------------- loop
     def begin(self, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool = True,
               n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None, grammar=None,
-              n_bars: Optional[torch.Tensor] = None) -> int:
+              n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None) -> int:
         """prompt pass + first sampled token + (use_graph) capture of one decode step; returns the number of `replay_once()`
         calls that complete the generation to max_length.  n_pad: left-padded prompts (prefill); the decode step is the same,
         every row's last prompt token sits at column Tp - 1.  stop: (eos, pad, min_length) (stop_config) or None.  grammar: a
         grammar.TokenGrammar or None; the captured step reads its device tables and, under a bar budget, the budget's tables and
         class masks, so their identity is part of the graph key.  n_bars: None or (B,) int32 (prefill); the step captured under the
         bar count is another launch with two more class masks, so the presence of the rule and its masks are in the key too, while
-        the counts themselves are step state (`gleft`)"""
+        the counts themselves are step state (`gleft`).  in_key / keys (prefill): the step captured under the key rule is another
+        launch that reads the rule's tables, so its presence and their identity are in the key; the keys are step state (`gkey`)"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         self._sampling = sampling
         self._use_graph = use_graph
-        self.prefill(prompt, sampling, n_pad, stop, grammar, n_bars)
+        self.prefill(prompt, sampling, n_pad, stop, grammar, n_bars, in_key, keys)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
             # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
@@ -702,7 +785,7 @@ class XLDecoder:
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
                  typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
-                 stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None) -> torch.Tensor:
+                 stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None) -> torch.Tensor:
         """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
         [OMIT]) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (prefill); the
         prompt columns, pads included, come back as given.
@@ -716,11 +799,15 @@ class XLDecoder:
         long as the row's time signature: the free slots of the open channel live and move beside the state.
         n_bars (an int or one per row, negative = no limit; needs grammar and eos_token_id): every row opens exactly that many
         further bars -- the bar open at the end of its prompt is finished and not counted -- and, under a bar budget, emits eos
-        when the last of them is full.  Without a budget the rule bars a further bar and an early eos but cannot force the end."""
+        when the last of them is full.  Without a budget the rule bars a further bar and an early eos but cannot force the end.
+        in_key (a grammar.KeyRule, e.g. `tokenizer.key_rule()`; needs no grammar): a row whose key is known emits only pitches of
+        that key.  key=None: every row's key is the last key token of its prompt (none: the row is unconstrained); key = a key name
+        or ordinal, or one per row with None / -1 = unconstrained, overrides the prompts.  A generated key token sets the row's key."""
         stop = stop_config(eos_token_id, pad_token_id, min_length)
         return decode_lanes(self, [self], [None], prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
-                            stop, stop_chunk, grammar, bar_count_config(n_bars, self.B, grammar, stop))
+                            stop, stop_chunk, grammar, bar_count_config(n_bars, self.B, grammar, stop), in_key,
+                            key_config(in_key, key, self.B, self.eng.cfg.vocab_size))
 
 
 class XLDecoderLanes:
@@ -743,10 +830,12 @@ class XLDecoderLanes:
         for d in self.lanes:
             d.invalidate_tables()
 
-    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None, grammar=None, n_bars=None) -> int:
+    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None, grammar=None, n_bars=None, in_key=None,
+              keys=None) -> int:
         steps = [d.begin(prompt[self.offs[i]:self.offs[i + 1]], max_length, sampling, use_graph,
                          None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]], stop, grammar,
-                         None if n_bars is None else n_bars[self.offs[i]:self.offs[i + 1]])
+                         None if n_bars is None else n_bars[self.offs[i]:self.offs[i + 1]], in_key,
+                         None if keys is None else keys[self.offs[i]:self.offs[i + 1]])
                  for i, d in enumerate(self.lanes)]
         for s in self.streams:                       # the lanes start from the prompt passes and captures issued above
             s.wait_stream(torch.cuda.current_stream())
@@ -763,13 +852,14 @@ class XLDecoderLanes:
 
     def generate(self, prompt, max_length, do_sample=False, top_k=None, top_p=None, temperature=1.0, repetition_penalty=None,
                  typical_p=None, use_graph=True, n_pad=None, eos_token_id=None, pad_token_id=None, min_length=None,
-                 stop_chunk=STOP_CHUNK, grammar=None, n_bars=None) -> torch.Tensor:
-        """XLDecoder.generate over the lanes (each lane keeps the grammar state and the bar counts of its own rows).  With eos_token_id every lane stops
+                 stop_chunk=STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None) -> torch.Tensor:
+        """XLDecoder.generate over the lanes (each lane keeps the grammar state, the bar counts and the keys of its own rows).  With eos_token_id every lane stops
         on its own; the output is the lanes' rows cut to the common width and right-filled with pad where a lane stopped earlier."""
         stop = stop_config(eos_token_id, pad_token_id, min_length)
         return decode_lanes(self, self.lanes, self.streams, prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
-                            stop, stop_chunk, grammar, bar_count_config(n_bars, self.B, grammar, stop))
+                            stop, stop_chunk, grammar, bar_count_config(n_bars, self.B, grammar, stop), in_key,
+                            key_config(in_key, key, self.B, self.lanes[0].eng.cfg.vocab_size))
 
 
 class _BeamHyps:

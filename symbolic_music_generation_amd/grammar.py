@@ -38,6 +38,17 @@ integer per row, `left` = the bars the row may still open (negative = no limit, 
 
 Under the bar budget a row whose last bar is full may emit only <bar> or </s>, so the count decides which: the row ends exactly when
 its k-th bar is full.  Without a budget the rule still bars a further bar and an early end, but nothing forces the end.
+
+`KeyRule` (`MusicVocabulary.key_rule()` / `MusicTokenizer.key_rule()`) is the harmonic rule behind `generate(..., in_key=rule)`.  It
+stands beside the grammar, not on it: one more integer per row, `key` = the ordinal of the row's key in `vocab.KEY_NAMES` (negative =
+no key, the row is untouched), and three tables
+
+    keys       (V,)   uint8    Key_* token -> ordinal, NO_KEY = any other token
+    pcs        (V,)   uint8    pitch token -> pitch class 0..11, NO_PITCH = no pitch (rests and the rare pitch included)
+    inkey      (24,)  uint16   bit pc set <=> pitch class pc belongs to the key (metrics.in_key_table, the table of the IKR metric)
+
+A pitch outside the row's key is barred, and a kept Key_* token sets the row's key.  It reads neither token classes nor the automaton
+state, so it needs no grammar and composes with all of the above.
 """
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -47,6 +58,9 @@ MAX_CLASSES = 32
 MAX_STATES = 256
 RARE_SLOTS = 0xFFFF        # `slots` entry of a duration token of unknown length: barred in a constrained bar
 NO_SIG = 0xFFFF            # `bars` entry of a token that is no time signature
+NO_KEY = 0xFF              # `keys` entry of a token that is no key token
+NO_PITCH = 0xFF            # `pcs` entry of a token that is no pitch
+N_KEYS = 24
 
 
 class TokenGrammar:
@@ -432,6 +446,123 @@ class BarCount:
     def __repr__(self):
         names = lambda m: [n for i, n in enumerate(self.grammar.class_names) if (m >> i) & 1]
         return f'BarCount(count={names(self.count)}, end={names(self.end)})'
+
+
+class KeyRule:
+    def __init__(self, keys, pcs, inkey=None):
+        """The key rule (module docstring) from explicit tables: keys / pcs (V,) with NO_KEY / NO_PITCH for "none", inkey (24,) bit
+        masks over the 12 pitch classes (default: metrics.in_key_table()).  Raises ValueError when the tables are out of range, or
+        when some key keeps no pitch token at all -- with pitch tokens in the vocabulary, a row in that key would have every pitch
+        barred wherever only a pitch may follow."""
+        keys_a, pcs_a = np.asarray(keys), np.asarray(pcs)
+        if keys_a.ndim != 1 or keys_a.size == 0 or pcs_a.shape != keys_a.shape:
+            raise ValueError('keys and pcs must be non-empty (V,) arrays: one entry per token')
+        if inkey is None:
+            from .metrics import in_key_table
+            inkey = in_key_masks(in_key_table())
+        inkey_a = np.asarray(inkey)
+        if inkey_a.shape != (N_KEYS,) or int(inkey_a.min()) < 0 or int(inkey_a.max()) >> 12:
+            raise ValueError(f'inkey must be ({N_KEYS},) bit masks over the 12 pitch classes')
+        if ((keys_a < 0) | ((keys_a >= N_KEYS) & (keys_a != NO_KEY))).any():
+            raise ValueError(f'keys holds an entry outside 0..{N_KEYS - 1} and NO_KEY')
+        if ((pcs_a < 0) | ((pcs_a >= 12) & (pcs_a != NO_PITCH))).any():
+            raise ValueError('pcs holds an entry outside 0..11 and NO_PITCH')
+        self.keys = np.ascontiguousarray(keys_a, dtype=np.uint8)
+        self.pcs = np.ascontiguousarray(pcs_a, dtype=np.uint8)
+        self.inkey = np.ascontiguousarray(inkey_a, dtype=np.uint16)
+        have = 0                                         # bit pc set <=> pitch class pc has a token
+        for pc in np.unique(self.pcs[self.pcs != NO_PITCH]).tolist():
+            have |= 1 << int(pc)
+        for k in range(N_KEYS):
+            if have and not int(self.inkey[k]) & have:
+                raise ValueError(f'key {k} keeps no pitch token of this vocabulary: a row in that key would have every pitch barred')
+        self._dev: Dict[str, tuple] = {}
+
+    @property
+    def vocab_size(self) -> int:
+        return int(self.keys.shape[0])
+
+    # ---------------------------------------------------------------- the rule
+    def allows(self, key: int, tok: int) -> bool:
+        """may token `tok` follow in a row in `key`?  (what the grammar, the budget and the count say comes on top)"""
+        pc = int(self.pcs[int(tok)])
+        return key < 0 or pc == NO_PITCH or bool((int(self.inkey[int(key)]) >> pc) & 1)
+
+    def move(self, key: int, tok: int) -> int:
+        """`key` after token `tok`: a key token sets it, nothing else changes it"""
+        k = int(self.keys[int(tok)])
+        return int(key) if k == NO_KEY else k
+
+    def allowed(self, key: int) -> np.ndarray:
+        """(V,) bool: `allows(key, v)` for every token v"""
+        if key < 0:
+            return np.ones(self.vocab_size, dtype=bool)
+        return (self.pcs == NO_PITCH) | (((int(self.inkey[int(key)]) >> (self.pcs & 15).astype(np.int64)) & 1) == 1)
+
+    # ---------------------------------------------------------------- host reference
+    def walk(self, ids, key: int = -1, check_from: int = 0) -> Tuple[int, int]:
+        """(key, index of the first pitch outside the row's key or -1) for a 1-D id sequence that starts in `key`; the walk stops
+        there.  Entries before `check_from` only move the key (a prompt supplies its key, its pitches are not judged).  Ids < 0
+        (left pads) and ids beyond the vocabulary are skipped.  The host reference of mxl_key_scan."""
+        seq = ids.tolist() if hasattr(ids, 'tolist') else list(ids)
+        V, key = self.vocab_size, int(key)
+        for i, tok in enumerate(seq):
+            tok = int(tok)
+            if tok < 0 or tok >= V:
+                continue
+            if i >= check_from and not self.allows(key, tok):
+                return key, i
+            key = self.move(key, tok)
+        return key, -1
+
+    # ---------------------------------------------------------------- device tables
+    def to(self, device):
+        """(keys, pcs, inkey) on `device`, uploaded once per device: uint8 (V,) twice and int16 (24,) holding the uint16 bit patterns"""
+        import torch
+        dk = str(torch.device(device))
+        if dk not in self._dev:
+            self._dev[dk] = (torch.from_numpy(self.keys.copy()).to(device), torch.from_numpy(self.pcs.copy()).to(device),
+                             torch.from_numpy(self.inkey.view(np.int16).copy()).to(device))
+        return self._dev[dk]
+
+    def __repr__(self):
+        return f'KeyRule(V={self.vocab_size}, key tokens={int((self.keys != NO_KEY).sum())}, pitches={int((self.pcs != NO_PITCH).sum())})'
+
+
+def in_key_masks(table) -> np.ndarray:
+    """(24,) uint16 from a (24, 12) 0/1 table (metrics.in_key_table): bit pc of entry k set <=> table[k, pc] == 1"""
+    tab = np.asarray(table)
+    return np.array([sum(1 << pc for pc in range(tab.shape[1]) if tab[k, pc] == 1) for k in range(tab.shape[0])], dtype=np.uint16)
+
+
+def key_ordinal(key) -> int:
+    """a key as `generate(key=)` takes it -> its ordinal in vocab.KEY_NAMES, -1 = none: None, an ordinal, or a name with or without
+    the token prefix ('AMinor', 'Key_AMinor')"""
+    from .vocab import KEY_NAMES
+    if key is None:
+        return -1
+    if isinstance(key, str):
+        name = key[len('Key_'):] if key.startswith('Key_') else key
+        if name not in KEY_NAMES:
+            raise ValueError(f'unknown key {key!r}')
+        return KEY_NAMES.index(name)
+    if isinstance(key, (bool, float)) or not -1 <= int(key) < N_KEYS:
+        raise ValueError(f'a key is a name, None or an ordinal in -1..{N_KEYS - 1}, got {key!r}')
+    return int(key)
+
+
+def music_key_rule(vocab) -> KeyRule:
+    """the key rule of a MusicVocabulary of any pitch kind, from the tables of the IKR metric (metrics.pitch_class_table,
+    metrics.in_key_table): what the metric counts as an off-key pitch is what the rule bars.  For the `degree` pitch kind that is the
+    token's pitch class alone; the scale-degree suffix is not checked against the key."""
+    from .metrics import pitch_class_table
+    from .vocab import KEY_NAMES
+    pc = pitch_class_table(vocab).astype(np.int64)
+    keys = np.full(len(vocab), NO_KEY, dtype=np.uint8)
+    for o, name in enumerate(KEY_NAMES):
+        if f'Key_{name}' in vocab:
+            keys[vocab.tok2id[f'Key_{name}']] = o
+    return KeyRule(keys, np.where(pc < 0, NO_PITCH, pc).astype(np.uint8))
 
 
 def from_transitions(cls, class_names: Sequence[str], transitions: Sequence[Tuple[str, str, str]], start: str,

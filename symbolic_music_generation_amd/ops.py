@@ -133,11 +133,12 @@ def decode_qkv(x, wqkv, qkv, kc, vc, t_dev, rrb, qr_out, dh):
                                _stream()), 'mxl_decode_qkv')
 
 
-def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None) -> dict:
+def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None,
+                   gkey=None) -> dict:
     """The rules of a generation as its decoders describe them -> the keywords of rules_mask / rules_advance, where a group is on
     exactly when its state tensor is given.  The decoders say which rules hold with `stop` (the eos rule), `grammar` (the grammar,
-    and its bar budget if it has one) and `gleft` (the bar count) and may hand over state tensors of rules that are off: those are
-    dropped here, and a rule that is on without its state raises."""
+    and its bar budget if it has one), `gleft` (the bar count) and `in_key` (the key rule) and may hand over state tensors of rules
+    that are off: those are dropped here, and a rule that is on without its state raises."""
     budget = grammar is not None and grammar.budget is not None
     if stop is not None and (unfinished is None or alive is None):
         raise MusicXLError('the eos rule needs unfinished and alive')
@@ -147,9 +148,26 @@ def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=
         raise MusicXLError('a grammar needs gstate')
     if budget and (gbar is None or grem is None):
         raise MusicXLError('a grammar with a bar budget needs gbar and grem')
+    if in_key is not None and gkey is None:
+        raise MusicXLError('the key rule needs gkey')
     return dict(stop=stop, unfinished=unfinished if stop is not None else None, alive=alive if stop is not None else None,
                 grammar=grammar, gstate=gstate if grammar is not None else None, gbar=gbar if budget else None,
-                grem=grem if budget else None, gleft=gleft)
+                grem=grem if budget else None, gleft=gleft, in_key=in_key, gkey=gkey if in_key is not None else None)
+
+
+def _key_args(what, device, B, V=None, *, in_key=None, gkey=None) -> list:
+    """the key group of the mxl_keyed_* entries (include/musicxl.h, "Rules of a generation"), checked: on exactly when gkey is given,
+    with its tables from `in_key` (a grammar.KeyRule), which must span the V tokens of the scores"""
+    if gkey is None:
+        return [None, None, None, None]
+    if in_key is None:
+        raise MusicXLError(f'{what}: gkey needs in_key, the key rule that holds its tables')
+    if V is not None and in_key.vocab_size != int(V):
+        raise MusicXLError(f'the key rule spans {in_key.vocab_size} tokens, the scores span {int(V)}')
+    _req(gkey, torch.int32, f'{what} gkey')
+    if gkey.numel() != B or not gkey.is_contiguous():
+        raise MusicXLError(f'{what}: gkey must be contiguous ({B},) int32')
+    return [_p(t) for t in in_key.to(device)] + [_p(gkey)]
 
 
 def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None,
@@ -193,37 +211,47 @@ def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=No
 
 
 def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
-                grammar=None, gstate=None, gbar=None, grem=None, gleft=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0,
-                repetition_penalty=1.0, typical_p=1.0):
+                grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None, do_sample=False, top_k=0,
+                top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0, out_probs=None):
     """sampler + embedding row of the sampled token (-> emb_out (B, d) bf16) + counter advance, one launch (V <= 2048).
     scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1.
     The rules of the generation ride on the same launch (rules_in_force): stop = (eos_id, pad_id, min_length) with unfinished (B,)
     int32 and alive (1,) int32 on the device; grammar (a grammar.TokenGrammar) with gstate (B,) int32, barred tokens masked and gstate
     advanced, with or without the eos rule; a grammar with a bar budget (grammar.budget) needs gbar and grem (B,) int32 as well;
-    gleft (B,) int32, the bars every row may still open (< 0 = no limit), turns the grammar's bar count on."""
+    gleft (B,) int32, the bars every row may still open (< 0 = no limit), turns the grammar's bar count on; in_key (a grammar.KeyRule)
+    with gkey (B,) int32, the key of every row (< 0 = none), bars the pitches outside it, with or without a grammar.
+    out_probs (B, V) f32, with do_sample: the renormalised distribution the tokens were drawn from (test hook)."""
     B = scores.shape[0]
-    rules = _rules_args('sample_step', scores.device, B, V, **rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft))
-    check(lib().mxl_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
-                                int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
-                                float(repetition_penalty if repetition_penalty is not None else 1.0),
-                                float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1], float(scale),
-                                _p(counter), *rules, _stream()), 'mxl_sample_step')
+    force = rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey)
+    keyed = _key_args('sample_step', scores.device, B, V, in_key=force.pop('in_key'), gkey=force.pop('gkey'))
+    rules = _rules_args('sample_step', scores.device, B, V, **force)
+    if out_probs is not None:
+        _req(out_probs, torch.float32, 'sample_step out_probs')
+        if tuple(out_probs.shape) != (B, int(V)) or not out_probs.is_contiguous():
+            raise MusicXLError(f'sample_step: out_probs must be contiguous ({B}, {int(V)}) f32')
+    check(lib().mxl_keyed_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
+                                      int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
+                                      float(repetition_penalty if repetition_penalty is not None else 1.0),
+                                      float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
+                                      float(scale), _p(counter), *rules, *keyed, _p(out_probs), _stream()), 'mxl_keyed_sample_step')
 
 
-def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None):
+def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None):
     """before sample: scores[b, v] = -inf in place for every token a rule bars (mxl_rules_mask).  A rule is applied exactly when its
     state is given: gstate (the grammar in state gstate[b]), gbar and grem (its bar budget), gleft (its bar count), each with
-    `grammar` for the tables; stop = (eos, pad, min_length) bars eos while the rows are shorter than min_length.  No launch when
-    nothing is given."""
+    `grammar` for the tables, and gkey (the key rule in key gkey[b]) with `in_key` for its tables; stop = (eos, pad, min_length) bars
+    eos while the rows are shorter than min_length.  No launch when nothing is given."""
     _req(scores, torch.float32, 'rules_mask scores')
     B = scores.shape[0]
     if scores.shape[1] < V or scores.stride(1) != 1:
         raise MusicXLError('rules_mask: scores must be (B, >= V) with unit column stride')
     rules = _rules_args('rules_mask', scores.device, B, V, stop=stop, grammar=grammar, gstate=gstate, gbar=gbar, grem=grem, gleft=gleft)
-    check(lib().mxl_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, _stream()), 'mxl_rules_mask')
+    keyed = _key_args('rules_mask', scores.device, B, V, in_key=in_key, gkey=gkey)
+    check(lib().mxl_keyed_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, *keyed, _stream()), 'mxl_keyed_rules_mask')
 
 
-def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None):
+def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None,
+                  in_key=None, gkey=None):
     """after sample + decode_advance: the words given (as rules_mask) move along the token at ids[b, t] in every row that chose it,
     then, with unfinished and alive, that token goes through the stop rule stop = (eos, pad, min_length): rows with unfinished[b] == 0
     get pad and keep their words (mxl_rules_advance).  No launch when nothing is given."""
@@ -232,8 +260,26 @@ def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar
         raise MusicXLError('rules_advance: ids must be (B, .) int64')
     rules = _rules_args('rules_advance', ids.device, B, stop=stop, unfinished=unfinished, alive=alive, grammar=grammar, gstate=gstate,
                         gbar=gbar, grem=grem, gleft=gleft)
-    check(lib().mxl_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, grammar.vocab_size if grammar is not None else 0, *rules,
-                                  _stream()), 'mxl_rules_advance')
+    if grammar is not None and in_key is not None and gkey is not None and grammar.vocab_size != in_key.vocab_size:
+        raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the key rule spans {in_key.vocab_size}')
+    keyed = _key_args('rules_advance', ids.device, B, in_key=in_key, gkey=gkey)
+    V = grammar.vocab_size if grammar is not None else (in_key.vocab_size if gkey is not None else 0)
+    check(lib().mxl_keyed_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, *rules, *keyed, _stream()), 'mxl_keyed_rules_advance')
+
+
+def key_scan(ids, Tp, in_key, gkey, first_bad, check_from=None):
+    """gkey[b] = key of row b after columns 0..Tp-1 of ids, walked from the key gkey[b] holds now (ids < 0 skipped); columns before
+    check_from (default Tp: none is judged) only move the key, first_bad[b] = the first column from there on that holds a pitch
+    outside the row's key, or -1 (mxl_key_scan); the host reference is KeyRule.walk"""
+    _req(gkey, torch.int32, 'key_scan gkey'); _req(first_bad, torch.int32, 'key_scan first_bad')
+    B = ids.shape[0]
+    if ids.dtype != torch.int64 or ids.stride(1) != 1 or Tp > ids.shape[1] or gkey.numel() != B or first_bad.numel() != B:
+        raise MusicXLError('key_scan: ids must be (B, >= Tp) int64 with unit column stride, gkey and first_bad (B,)')
+    if not gkey.is_contiguous() or not first_bad.is_contiguous():
+        raise MusicXLError('key_scan: gkey and first_bad must be contiguous')
+    keys, pcs, inkey = in_key.to(ids.device)
+    check(lib().mxl_key_scan(_p(ids), ids.stride(0), int(Tp), int(Tp if check_from is None else check_from), B, in_key.vocab_size,
+                             _p(keys), _p(pcs), _p(inkey), _p(gkey), _p(first_bad), _stream()), 'mxl_key_scan')
 
 
 def grammar_scan(ids, Tp, grammar, gstate, first_bad, start=None):

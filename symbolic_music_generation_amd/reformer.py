@@ -154,7 +154,7 @@ class MyReformerModelWithLMHead(EngineModule):
                  num_beam_groups: int = 1, length_penalty: float = 1.0, diversity_penalty=None,
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
-                 grammar=None, n_bars=None, **unsupported):
+                 grammar=None, n_bars=None, in_key=None, key=None, **unsupported):
         """`model.generate(...)` as the reference drives it (musicnlp/trainer/eval.py:277-333): greedy, or sampling with
         top-k / top-p / typical-p / temperature / repetition penalty (applied, as HF does, to the raw logits); token selection
         runs on the device (the TransfoXL decoder's sampler kernel).
@@ -177,8 +177,12 @@ class MyReformerModelWithLMHead(EngineModule):
 
         n_bars (an int, or one per prompt; negative = no limit; with grammar and eos_token_id, greedy decoding and sampling): every
         row opens exactly that many further bars, as MyTransfoXLLMHeadModel.generate -- under the bar budget it ends with eos when
-        the last of them is full; under a grammar without one the rule cannot force the end and a row may run to max_length."""
-        from .generate import (STOP_CHUNK, RowRules, bar_count_config, beam_generate, check_grammar_args, left_pad_counts,
+        the last of them is full; under a grammar without one the rule cannot force the end and a row may run to max_length.
+
+        in_key (a `grammar.KeyRule`, `tokenizer.key_rule()`) with key (None = the last key token of every prompt; a key name or
+        ordinal, or one per prompt, None / -1 = unconstrained): greedy decoding and sampling in which a row whose key is known emits
+        only pitches of that key, as MyTransfoXLLMHeadModel.generate; it needs no grammar."""
+        from .generate import (STOP_CHUNK, RowRules, bar_count_config, beam_generate, check_grammar_args, key_config, left_pad_counts,
                                resolve_max_length, sample_unfused, sampling_config, stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
@@ -189,7 +193,11 @@ class MyReformerModelWithLMHead(EngineModule):
         if n_bars is not None and (num_beams > 1 or num_beam_groups != 1 or (penalty_alpha and not do_sample)):
             raise MusicXLError('n_bars= is supported for greedy decoding and sampling only, not for beam, group-beam or contrastive '
                                'search')
+        if (in_key is not None or key is not None) and (num_beams > 1 or num_beam_groups != 1 or (penalty_alpha and not do_sample)):
+            raise MusicXLError('in_key= is supported for greedy decoding and sampling only, not for beam, group-beam or contrastive '
+                               'search')
         n_bars = bar_count_config(n_bars, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, nrs)
+        keys = key_config(in_key, key, input_ids.shape[0] if input_ids is not None else 0, self.config.vocab_size, nrs)
         if attention_mask is not None and input_ids is not None and any(left_pad_counts(attention_mask, tuple(input_ids.shape))):
             # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
             raise MusicXLError(f'{type(self).__name__}.generate does not support padded prompts (attention_mask with zeros); '
@@ -251,7 +259,8 @@ class MyReformerModelWithLMHead(EngineModule):
                 dec.rotations = rotations
                 dec.seed = seed
                 return dec.generate(ids0, max_length, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
-                                    repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop, grammar=grammar, n_bars=n_bars)
+                                    repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop, grammar=grammar, n_bars=n_bars,
+                                    in_key=in_key, key=keys)
             V = c.vocab_size
             pad = getattr(c, 'pad_token_id', None)
             pad = 0 if pad is None else int(pad)
@@ -260,7 +269,7 @@ class MyReformerModelWithLMHead(EngineModule):
             t_dev = torch.full((1,), Tp - 1, device=self.device, dtype=torch.int32)
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
             rules = RowRules(B, self.device)
-            rules.start(buf, Tp, V, stop, grammar, n_bars)
+            rules.start(buf, Tp, V, stop, grammar, n_bars, in_key, keys)
             rules.check_prompt(buf)
             sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
             for cur in range(Tp, max_length):

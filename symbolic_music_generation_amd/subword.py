@@ -141,6 +141,10 @@ class PairMergeTokenizer(MusicTokenizer):
         raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders (a pitch with its '
                                   'duration, a whole tuplet), so the music grammar over token classes does not apply')
 
+    def key_rule(self):
+        raise NotImplementedError(f'{type(self).__name__}: a sub-word token may hold several pitches, so the key rule over single '
+                                  'pitch tokens does not apply')
+
     @property
     def vocab_size(self) -> int:
         return self.original_vocab_size + self.added_vocab_size
@@ -322,6 +326,10 @@ class WordPieceMusicTokenizer(MusicTokenizer):
     def grammar(self, bar_budget: bool = False):
         raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders (a pitch with its '
                                   'duration, a whole tuplet), so the music grammar over token classes does not apply')
+
+    def key_rule(self):
+        raise NotImplementedError(f'{type(self).__name__}: a sub-word token may hold several pitches, so the key rule over single '
+                                  'pitch tokens does not apply')
 
     @property
     def vocab_size(self) -> int:

@@ -198,7 +198,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  renormalize_logits=None, num_return_sequences: int = 1, num_beam_groups: int = 1, length_penalty: float = 1.0,
                  use_graph: bool = True, seed: int = 77, attention_mask: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
-                 min_length: Optional[int] = None, grammar=None, n_bars=None, **unused) -> torch.Tensor:
+                 min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -234,9 +234,19 @@ class MyTransfoXLLMHeadModel(EngineModule):
         when its k-th bar is full, and pad from then on.  Without a budget (`tokenizer.grammar()`, or a row with TimeSig_rare)
         the rule still bars a further `<bar>` and an early eos but cannot force the stop: such a row may run to `max_length`.  A
         row that reaches `max_length` first is cut there.  The count lives on the device beside the grammar state and moves in the
-        same sampler launch.  It combines with everything `grammar` combines with except `min_length` (ValueError)."""
+        same sampler launch.  It combines with everything `grammar` combines with except `min_length` (ValueError).
+
+        `in_key` (a `grammar.KeyRule`, `tokenizer.key_rule()`; greedy decoding and sampling): a row whose key is known emits only
+        pitches of that key -- the pitches the in-key ratio (`metrics.ComputeMetrics`) counts as in key; rests and the rare-pitch
+        token are never barred.  With `key=None` the key of a row is the last `Key_*` token of its prompt (pad columns skipped); a
+        row without one stays unconstrained.  `key` = a key name ('AMinor', 'Key_AMinor') or ordinal in `vocab.KEY_NAMES`, or a
+        sequence of one per prompt with None / -1 = unconstrained (repeated per prompt under `num_return_sequences`), overrides the
+        prompts' keys.  The prompt only supplies the key: its own pitches are not judged.  A generated `Key_*` token sets the row's
+        key from then on.  The key lives on the device beside the other rules' words and the mask sits in the same sampler launch,
+        in the same place.  It needs no `grammar` and combines with everything greedy decoding and sampling take.  Beam,
+        group-beam and contrastive search take no `in_key`."""
         from .generate import (XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, check_grammar_args, contrastive_search,
-                               left_pad_counts, resolve_max_length, stop_config)
+                               key_config, left_pad_counts, resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -265,7 +275,11 @@ class MyTransfoXLLMHeadModel(EngineModule):
         if n_bars is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('n_bars= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
+        if (in_key is not None or key is not None) and (contrastive or num_beam_groups != 1 or num_beams > 1):
+            raise MusicXLError('in_key= is supported for greedy decoding and sampling only, not for beam, group-beam or '
+                               'contrastive search')
         n_bars = bar_count_config(n_bars, input_ids.shape[0], grammar, stop, num_return_sequences)
+        keys = key_config(in_key, key, input_ids.shape[0], self.config.vocab_size, num_return_sequences)
         if contrastive:
             dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
@@ -294,4 +308,5 @@ class MyTransfoXLLMHeadModel(EngineModule):
         return dec.generate(input_ids.to(self.device), max_length, do_sample=do_sample, top_k=top_k, top_p=top_p,
                             temperature=temperature, repetition_penalty=repetition_penalty, typical_p=typical_p,
                             use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device), grammar=grammar, n_bars=n_bars,
+                            in_key=in_key, key=keys,
                             **({} if stop is None else dict(eos_token_id=stop[0], pad_token_id=stop[1], min_length=stop[2])))

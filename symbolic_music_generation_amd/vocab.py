@@ -180,6 +180,12 @@ class MusicVocabulary:
         from .grammar import music_grammar
         return music_grammar(self, bar_budget=bar_budget)
 
+    def key_rule(self):
+        """the key rule over this vocabulary (grammar.music_key_rule), for `generate(in_key=...)`: a row whose key is known emits
+        only pitches of that key"""
+        from .grammar import music_key_rule
+        return music_key_rule(self)
+
 
 class MusicTokenizer:
     """Whitespace split -> `t2i`; `model_input_names = ['input_ids']` so no attention mask is ever produced
@@ -209,6 +215,10 @@ class MusicTokenizer:
     def grammar(self, bar_budget: bool = False):
         """the token grammar of a well-formed song (`MusicVocabulary.grammar`), for `model.generate(grammar=...)`"""
         return self.vocab.grammar(bar_budget=bar_budget)
+
+    def key_rule(self):
+        """the key rule (`MusicVocabulary.key_rule`), for `model.generate(in_key=...)`"""
+        return self.vocab.key_rule()
 
     def tokenize(self, text: str) -> List[str]:
         return text.split()
