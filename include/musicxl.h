@@ -428,11 +428,12 @@ int mxl_sample_large(const float* logprobs, int ldl, int V, void* ids, int ld_id
 /* t_dev += 1; rng_ctr += 1 */
 int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
 /* ------------------------------------------------------------------------------------------------------------
- * Rules of a generation.  Five optional groups of per-row state on the device, applied around every sampled token; three entries take
- * the first four as the same flat argument list (below): mxl_sample_step, mxl_rules_mask, mxl_rules_advance, and their mxl_keyed_*
- * forms take the fifth after it.  A group is off when its state pointer is NULL: unfinished (with alive), gstate (with allow, next),
- * gbar (with grem, slots, bars), gleft, gkey (with keys, pcs, inkey).  Within a group either every pointer is given or none; the
- * budget and the count need `cls`; anything else is MXL_EINVAL.
+ * Rules of a generation.  Six optional groups of per-row state on the device, applied around every sampled token; three entries take
+ * the first four as the same flat argument list (below): mxl_sample_step, mxl_rules_mask, mxl_rules_advance, their mxl_keyed_*
+ * forms take the fifth after it and their mxl_guided_* forms the sixth after that.  A group is off when its state pointer is NULL:
+ * unfinished (with alive), gstate (with allow, next), gbar (with grem, slots, bars), gleft, gkey (with keys, pcs, inkey), gpos (with
+ * gforce, guide, glen).  Within a group either every pointer is given or none; the budget, the count and the guide need `cls`;
+ * anything else is MXL_EINVAL.
  *
  * stop: eos_id, pad_id, min_length, unfinished, alive -- stopping at eos (HF greedy_search / sample with an eos_token_id).
  *   unfinished (B,) int32 (1 = live; set to 1 before the first sampled token) and alive, one int32 = the number of live rows after
@@ -469,6 +470,19 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  *   step, degree), so wherever the grammar or the budget allows "a pitch" -- they judge the class of a token, never which pitch it is --
  *   a pitch of the row's key remains (besides the rest, which the rule never bars).  The host checks it when the tables are built: every
  *   key keeps at least one pitch token.
+ * guide: guide, ld_guide, glen, enter, leave, gpos, gforce (the mxl_guided_* entries) -- part of a row's output is given, not chosen:
+ *   in the music grammar the <bar> <melody> ... <bass> span of every bar, under which the row writes the bass.  Per row two int32
+ *   words: gpos, the next index into the row's guide, and gforce, 1 = the row is being fed from its guide, 0 = it chooses freely.
+ *   Tables: guide (B, ld_guide) int32, each row's guide tokens; glen (B,) int32, each row's guide length (<= ld_guide), 0 = the row
+ *   has no guide and is untouched; enter and leave, class bit masks over the classes of `cls` (the music grammar: <bar> and <bass>).
+ *   In a row with gforce == 1 and gpos < glen every token except guide[b][gpos] is barred and that token is never barred: the group
+ *   overrides the grammar, the budget, the count, the key and min_length (the caller guarantees that the guide is legal and holds
+ *   token ids below V); the token is -inf in the same place as under the other groups, so greedy and sampled rows both keep it.  A row
+ *   with gforce == 0 is masked by the other groups alone.  A kept token moves the row: under gforce == 1, gpos += 1 and a token whose
+ *   class is in leave sets gforce = 0; under gforce == 0 a token whose class is in enter, while gpos < glen, sets gforce = 1 and gpos
+ *   += 1 -- it is the guide's own <bar>.  The words of every other group move along a forced token as along a chosen one.  The group
+ *   does not stop a row: the caller sets gleft to the number of bars in the guide, so the count group bars the end while guided bars
+ *   are owed and a further bar once none is.
  *
  * The words move along the token a row keeps, after the stop rule: a row that was finished before the step emits pad and keeps its
  * words; the step in which a row emits eos still moves them.  Each row's words are read and written for that row alone.
@@ -479,7 +493,7 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  * writes *alive (counter: one int, zero before the first call, left zero).  `scores` (B, ldl) may be log-probabilities or, when
  * repetition_penalty == 1, the head's raw logits: argmax, top-k / top-p / typical-p and the renormalised draw do not change under the
  * per-row shift that separates the two.  The masks are applied where the row enters LDS.  V <= 2048; with the stop group B <= 32767;
- * the budget and the count need the grammar group here.  Without the stop group eos_id / pad_id / min_length are ignored. */
+ * the budget, the count and the guide need the grammar group here.  Without the stop group eos_id / pad_id / min_length are ignored. */
 int mxl_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
                     unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                     float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
@@ -521,6 +535,29 @@ int mxl_keyed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int 
                             const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
                             int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
                             int* gkey, void* stream);
+/* The keyed entries with the guide group after the key group; with guide = glen = gpos = gforce = NULL they are those entries.  In
+ * the fused launch the guide group is one more variant, on top of the grammar.  The state words are written by the row's thread 0. */
+int mxl_guided_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                           unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                           float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                           int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
+                           const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
+                           unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
+                           int* gleft, const void* keys, const void* pcs, const void* inkey, int* gkey, const void* guide,
+                           int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos, int* gforce, float* out_probs,
+                           void* stream);
+int mxl_guided_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length,
+                          int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
+                          const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
+                          int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
+                          int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
+                          int* gforce, void* stream);
+int mxl_guided_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length,
+                             int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
+                             const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
+                             int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
+                             int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
+                             int* gforce, void* stream);
 /* Key of every row after columns 0..Tp-1 of ids (B, ld_ids) int64, walked from the key gkey[b] holds at the launch (-1 = none): a
  * key token sets it.  Ids < 0 (left pads) and ids >= V are skipped.  Columns before `from` only move the key -- a prompt supplies its
  * key, its pitches are not judged; first_bad[b] = the first column >= from that holds a pitch outside the row's key, where the walk

@@ -361,9 +361,12 @@ constexpr int SORT_N = 2048;
 
 // token v under a row's words (rules_load below): its class under the allow word (c: a rule over classes is on), with the bar budget
 // the slots the row still has free, with the key rule the pitch classes of the row's key.  `inkey` has bits 12..31 set, and a token
-// that is no pitch has pcs 0xFF, which tests bit 31: one byte load and one shift, no branch.
+// that is no pitch has pcs 0xFF, which tests bit 31: one byte load and one shift, no branch.  `forced` >= 0 (gd: the guide group is
+// on): the row is fed that token from its guide -- it alone is allowed, whatever the other groups say.
 __device__ __forceinline__ bool token_allowed(const unsigned char* cls, uint32_t allow, const unsigned short* slots, int remcap,
-                                              const unsigned char* pcs, uint32_t inkey, long long v, bool c, bool bud, bool ink) {
+                                              const unsigned char* pcs, uint32_t inkey, long long v, bool c, bool bud, bool ink,
+                                              bool gd = false, int forced = -1) {
+    if (gd && forced >= 0) return v == forced;
     return (!c || ((allow >> cls[v]) & 1u)) && (!bud || (int)slots[v] <= remcap) && (!ink || ((inkey >> (pcs[v] & 31)) & 1u));
 }
 
@@ -375,14 +378,16 @@ __device__ __forceinline__ bool token_allowed(const unsigned char* cls, uint32_t
 // every entry) is -inf in the same place.
 // INK (with or without G): a pitch token whose class `pcs` is not a bit of `inkey` (the row's key; every bit in a row without one)
 // is -inf in the same place.
-template <bool G = false, bool BUD = false, bool INK = false>
+// GD (with G): in a row with `forced` >= 0 every token but that one is -inf in the same place, the other groups and min_length
+// have no say, and the sampler -- greedy or not -- is left with a one-token support.
+template <bool G = false, bool BUD = false, bool INK = false, bool GD = false>
 __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, const long long* ids, int ld_ids,
                                           const int* t_dev, const unsigned long long* rng_ctr, unsigned long long seed,
                                           int do_sample, int top_k, float top_p, float temperature,
                                           float repetition_penalty, float typical_p, float* out_probs, int eos_id = -1,
                                           int min_length = 0, const unsigned char* gcls = nullptr, uint32_t gallow = 0u,
                                           const unsigned short* bslots = nullptr, int remcap = 0,
-                                          const unsigned char* pcs = nullptr, uint32_t inkey = ~0u) {
+                                          const unsigned char* pcs = nullptr, uint32_t inkey = ~0u, int forced = -1) {
     __shared__ float key[SORT_N];
     __shared__ int idx[SORT_N];
     __shared__ int sh_pick;
@@ -390,7 +395,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
     const float* row = logp + (size_t)b * ldl;
     const float invt = 1.f / temperature;
     for (int i = tid; i < SORT_N; i += 256) {
-        if (G || INK) key[i] = (i < V && token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, i, G, BUD, INK)) ? row[i] * invt : -INFINITY;
+        if (G || INK) key[i] = (i < V && token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, i, G, BUD, INK, GD, forced)) ? row[i] * invt : -INFINITY;
         else key[i] = i < V ? row[i] * invt : -INFINITY;
         idx[i] = i;
     }
@@ -403,14 +408,14 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
         const long long* hist = ids + (size_t)b * ld_ids;
         for (int j = tid; j <= tcur; j += 256) {
             const long long tok = hist[j];
-            if (tok >= 0 && tok < V && (!(G || INK) || token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, tok, G, BUD, INK))) {
+            if (tok >= 0 && tok < V && (!(G || INK) || token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, tok, G, BUD, INK, GD, forced))) {
                 const float v = row[tok];
                 key[tok] = (v < 0.f ? v * repetition_penalty : v / repetition_penalty) * invt;
             }
         }
         __syncthreads();
     }
-    if (min_length > 0 && eos_id >= 0 && eos_id < V) {
+    if (min_length > 0 && eos_id >= 0 && eos_id < V && !(GD && forced >= 0)) {
         // HF MinLengthLogitsProcessor (after the repetition penalty, before the warpers): eos is barred while the row is
         // shorter than min_length -- the row holds columns 0..t, t + 1 of them
         if (tid == 0 && *t_dev + 1 < min_length) key[eos_id] = -INFINITY;
@@ -583,9 +588,9 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The rules of one generation (include/musicxl.h, "Rules of a generation"), passed to kernels by value.  Five groups, each off when
-// its state pointer (unfinished / gstate / gbar / gleft / gkey) is NULL; the budget and the count read the token classes `cls` of the
-// grammar group and nothing else of it, the key reads nothing of it at all.
+// The rules of one generation (include/musicxl.h, "Rules of a generation"), passed to kernels by value.  Six groups, each off when
+// its state pointer (unfinished / gstate / gbar / gleft / gkey / gpos) is NULL; the budget, the count and the guide read the token
+// classes `cls` of the grammar group and nothing else of it, the key reads nothing of it at all.
 //   stop     HF greedy_search / sample: a finished row emits pad, a live row that emits eos is finished; eos barred below min_length
 //   grammar  a token class automaton: cls (V,) token -> class, allow (S,) bit c = class c may follow in state s, next (S, C) successor
 //   budget   grammar.BarBudget: per row `bar` (bar length in slots, 0 = unconstrained) and `rem` (slots still free in the open
@@ -598,6 +603,12 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 //            Key_* token -> ordinal, 0xFF = no key token; pcs (V,) uint8: pitch token -> pitch class 0..11, 0xFF = no pitch (rests and
 //            the rare pitch included); inkey (24,) uint16: bit pc = pitch class pc belongs to the key.  A pitch outside the row's key is
 //            barred, and a kept key token sets the row's key
+//   guide    grammar.MelodyGuide: per row `pos`, the next index into the row's guide, and `force`, 1 = the row is fed from its guide.
+//            guide (B, ld_guide) int32: the rows' guide tokens; glen (B,) int32: their lengths, 0 = no guide, the row is untouched;
+//            enter / leave: class bit masks (<bar> / <bass>).  A row with force == 1 and pos < glen may emit guide[b][pos] alone, and
+//            that token is never barred: the group overrides every other one and min_length.  A kept token under force takes pos one
+//            on and, if its class is in `leave`, clears force; a kept `enter` token of a free row with pos < glen sets force and
+//            takes pos one on (it is the guide's own <bar>)
 // The next rule is one more group here, one line in each of rules_load / rules_move and one in make_rules.
 // ---------------------------------------------------------------------------------------------------------------
 struct DecodeRules {
@@ -620,6 +631,12 @@ struct DecodeRules {
     const unsigned char* pcs;
     const unsigned short* inkey;
     int* gkey;
+    const int* guide;
+    int ld_guide;
+    const int* glen;
+    uint32_t enter, leave;
+    int* gpos;
+    int* gforce;
 };
 
 constexpr int BUDGET_NONE = 0xFFFF;          // slots: unknown length (beyond any rem); bars: not a time signature
@@ -653,16 +670,18 @@ __device__ __forceinline__ uint32_t key_word(const unsigned short* inkey, int ke
 }
 
 // The words of row b and what they admit: `allow` has a bit per class the row may emit (every bit without a grammar), `remcap` is
-// the largest slots entry, `inkey` a bit per pitch class (key_word).  g / bud / cnt / ink: which groups are on -- compile-time
-// constants in the fused kernel, pointer tests in the unfused pair; everything here inlines and folds on them.
+// the largest slots entry, `inkey` a bit per pitch class (key_word), `forced` the guide token the row is fed at this step (-1 = none:
+// the row chooses).  g / bud / cnt / ink / gd: which groups are on -- compile-time constants in the fused kernel, pointer tests in
+// the unfused pair; everything here inlines and folds on them.
 struct RowWords {
     int gs, bar, rem, left;
     uint32_t allow;
     int remcap;
     uint32_t inkey;
+    int pos, force, forced;
 };
-__device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool g, bool bud, bool cnt, bool ink) {
-    RowWords w{0, 0, 0, -1, ~0u, BUDGET_NONE, KEY_ANY};
+__device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool g, bool bud, bool cnt, bool ink, bool gd = false) {
+    RowWords w{0, 0, 0, -1, ~0u, BUDGET_NONE, KEY_ANY, 0, 0, -1};
     if (g) { w.gs = r.gstate[b]; w.allow = r.allow[w.gs]; }
     if (bud) {
         w.bar = r.gbar[b];
@@ -672,12 +691,18 @@ __device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool
     }
     if (cnt) { w.left = r.gleft[b]; w.allow &= ~barcount_deny(w.left, r.count, r.end); }
     if (ink) w.inkey = key_word(r.inkey, r.gkey[b]);
+    if (gd) {
+        w.pos = r.gpos[b];
+        w.force = r.gforce[b];
+        if (w.force && w.pos >= 0 && w.pos < min(r.glen[b], r.ld_guide)) w.forced = r.guide[(size_t)b * r.ld_guide + w.pos];
+    }
     return w;
 }
 // row b moves along `tok`, a token of the vocabulary that the row chose itself (a row finished before the step emits pad, which is
 // not its choice and need not be a token its state allows: such a row keeps its words)
-__device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int b, long long tok, bool g, bool bud, bool cnt, bool ink) {
-    const int c = (g || bud || cnt) ? r.cls[tok] : 0;
+__device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int b, long long tok, bool g, bool bud, bool cnt, bool ink,
+                                           bool gd = false) {
+    const int c = (g || bud || cnt || gd) ? r.cls[tok] : 0;
     if (g) r.gstate[b] = r.next[w.gs * r.C + c];
     if (bud) {
         budget_move(w.bar, w.rem, c, r.slots[tok], r.bars[tok], r.opens);
@@ -688,6 +713,15 @@ __device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int
     if (ink) {
         const int k = r.keys[tok];
         if (k != KEY_NONE) r.gkey[b] = k;            // KeyRule.move: a key token sets the row's key, nothing else changes it
+    }
+    if (gd) {                                        // MelodyGuide.move
+        if (w.force) {
+            r.gpos[b] = w.pos + 1;
+            if ((r.leave >> c) & 1u) r.gforce[b] = 0;
+        } else if (((r.enter >> c) & 1u) && w.pos < r.glen[b]) {
+            r.gpos[b] = w.pos + 1;
+            r.gforce[b] = 1;
+        }
     }
 }
 
@@ -706,25 +740,25 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl,
 // head's raw logits instead of log-probabilities when no repetition penalty is in force: every other warper, the argmax and the
 // renormalised draw are invariant under the per-row shift log-softmax applies.
 //
-// G / BUD / CNT / INK: the grammar, budget, count and key groups of `r` as compile-time variants (BUD and CNT ride on G, INK stands
-// alone); the stop group is the runtime test of r.unfinished it has always been.  The row's words select the allow word and remcap the sampler applies
+// G / BUD / CNT / INK / GD: the grammar, budget, count, key and guide groups of `r` as compile-time variants (BUD, CNT and GD ride on
+// G, INK stands alone); the stop group is the runtime test of r.unfinished it has always been.  The row's words select the allow word and remcap the sampler applies
 // (rules_load), and thread 0 moves them along the token the row keeps (rules_move).  The move sits AFTER the eos rule: a row that
 // was finished before this step emits pad and its words stay frozen; the step in which a live row emits eos still moves them, so a
 // finished row of the music grammar rests in END.  The words are per-row: row b's workgroup is their only reader and writer within a
 // launch, and the next launch on the stream sees them by stream order -- there is no hand-off between workgroups here beyond the
 // arrival counter below.
-template <bool G, bool BUD, bool CNT, bool INK>
+template <bool G, bool BUD, bool CNT, bool INK, bool GD>
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, int ldl, int V, long long* ids, int ld_ids,
                                                           int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                           int do_sample, int top_k, float top_p, float temperature,
                                                           float repetition_penalty, float typical_p, const bf16_t* E, bf16_t* emb_out,
                                                           int d, float scale, int* counter, float* out_probs, DecodeRules r) {
-    static_assert(G || !(BUD || CNT), "the bar budget and the bar count ride on the grammar");
+    static_assert(G || !(BUD || CNT || GD), "the bar budget, the bar count and the guide ride on the grammar");
     int* const unfinished = r.unfinished;
-    const RowWords w = rules_load(r, blockIdx.x, G, BUD, CNT, INK);
-    int tok = sample_row<G, BUD, INK>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
+    const RowWords w = rules_load(r, blockIdx.x, G, BUD, CNT, INK, GD);
+    int tok = sample_row<G, BUD, INK, GD>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
                                       repetition_penalty, typical_p, out_probs, unfinished ? r.eos_id : -1,
-                                      unfinished ? r.min_length : 0, r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey);
+                                      unfinished ? r.min_length : 0, r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, w.forced);
     const int b = blockIdx.x, tid = threadIdx.x;
     __shared__ int sh_tok, sh_live;
     bool was_live = true;                       // (thread 0) the token is the row's own choice
@@ -743,7 +777,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         __syncthreads();
         tok = sh_tok;
     }
-    if ((G || INK) && tid == 0 && was_live && tok >= 0 && tok < V) rules_move(r, w, b, tok, G, BUD, CNT, INK);
+    if ((G || INK) && tid == 0 && was_live && tok >= 0 && tok < V) rules_move(r, w, b, tok, G, BUD, CNT, INK, GD);
     if (tid == 0) ids[(size_t)b * ld_ids + *t_dev + 1] = tok;
     const int id = (tok < 0 || tok >= V) ? 0 : tok;
     for (int c = tid; c < (d >> 3); c += 256) {
@@ -791,13 +825,15 @@ __global__ __launch_bounds__(256) void rules_mask_kernel(float* scores, int ldl,
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)B * V) return;
     const int b = (int)(i / V), v = (int)(i - (long long)b * V);
-    const bool bud = r.gbar != nullptr, ink = r.gkey != nullptr;
+    const bool bud = r.gbar != nullptr, ink = r.gkey != nullptr, gd = r.gpos != nullptr;
     bool ok = true;
+    int forced = -1;
     if (r.cls || ink) {
-        const RowWords w = rules_load(r, b, r.gstate != nullptr, bud, r.gleft != nullptr, ink);
-        ok = token_allowed(r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, v, r.cls != nullptr, bud, ink);
+        const RowWords w = rules_load(r, b, r.gstate != nullptr, bud, r.gleft != nullptr, ink, gd);
+        ok = token_allowed(r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, v, r.cls != nullptr, bud, ink, gd, w.forced);
+        forced = w.forced;
     }
-    if (r.min_length > 0 && v == r.eos_id && *t_dev + 1 < r.min_length) ok = false;
+    if (forced < 0 && r.min_length > 0 && v == r.eos_id && *t_dev + 1 < r.min_length) ok = false;
     if (!ok) scores[(size_t)b * ldl + v] = -INFINITY;
 }
 
@@ -809,12 +845,13 @@ __global__ __launch_bounds__(256) void rules_advance_kernel(long long* ids, int 
     const int tid = threadIdx.x;
     const int t = *t_dev;
     const bool g = r.gstate != nullptr, bud = r.gbar != nullptr, cnt = r.gleft != nullptr, ink = r.gkey != nullptr;
+    const bool gd = r.gpos != nullptr;
     int n = 0;
     for (int b = tid; b < B; b += 256) {
         long long* p = ids + (size_t)b * ld_ids + t;
         const long long tok = *p;
         int live = r.unfinished ? r.unfinished[b] : 1;
-        if (live && (r.cls || ink) && tok >= 0 && tok < V) rules_move(r, rules_load(r, b, g, bud, cnt, ink), b, tok, g, bud, cnt, ink);
+        if (live && (r.cls || ink) && tok >= 0 && tok < V) rules_move(r, rules_load(r, b, g, bud, cnt, ink, gd), b, tok, g, bud, cnt, ink, gd);
         if (r.unfinished) {
             if (!live) *p = r.pad_id;
             else if (tok == r.eos_id) live = 0;
@@ -1047,23 +1084,65 @@ extern "C" int mxl_sample(const float* logprobs, int ldl, int V, void* ids, int 
 #define KEY_PARAMS const void *keys, const void *pcs, const void *inkey, int *gkey
 #define KEY_ARGS keys, pcs, inkey, gkey
 #define KEY_OFF nullptr, nullptr, nullptr, nullptr
+// the guide group, which follows the key group in the mxl_guided_* entries
+#define GUIDE_PARAMS const void *guide, int ld_guide, const void *glen, unsigned enter, unsigned leave, int *gpos, int *gforce
+#define GUIDE_ARGS guide, ld_guide, glen, enter, leave, gpos, gforce
+#define GUIDE_OFF nullptr, 0, nullptr, 0u, 0u, nullptr, nullptr
 
-// the one check of those arguments, before any launch: within a group all pointers or none; budget and count read `cls`.
-// fused: the launch that also samples -- budget and count ride on the grammar there, and arrivals and live rows share one 32-bit word
-static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS, KEY_PARAMS) {
+// the one check of those arguments, before any launch: within a group all pointers or none; budget, count and guide read `cls`.
+// fused: the launch that also samples -- budget, count and guide ride on the grammar there, and arrivals and live rows share one
+// 32-bit word
+static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS) {
     MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr));
     MXL_CHECK_ARG((allow == nullptr) == (gstate == nullptr) && (next == nullptr) == (gstate == nullptr));
     MXL_CHECK_ARG(!gstate || (cls && C >= 1 && C <= 32));
     MXL_CHECK_ARG((slots == nullptr) == (gbar == nullptr) && (bars == nullptr) == (gbar == nullptr) && (grem == nullptr) == (gbar == nullptr));
     MXL_CHECK_ARG(!(gbar || gleft) || cls);
     MXL_CHECK_ARG((keys == nullptr) == (gkey == nullptr) && (pcs == nullptr) == (gkey == nullptr) && (inkey == nullptr) == (gkey == nullptr));
-    if (fused) MXL_CHECK_ARG(!(gbar || gleft) || gstate);
+    MXL_CHECK_ARG((guide == nullptr) == (gpos == nullptr) && (glen == nullptr) == (gpos == nullptr) && (gforce == nullptr) == (gpos == nullptr));
+    MXL_CHECK_ARG(!gpos || (cls && ld_guide >= 1));
+    if (fused) MXL_CHECK_ARG(!(gbar || gleft || gpos) || gstate);
     if (fused && unfinished) MXL_CHECK_ARG(B <= 32767);
     if (!unfinished && fused) { eos_id = -1; pad_id = 0; min_length = 0; }
     *r = DecodeRules{eos_id, pad_id, min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
                      (const unsigned char*)next, C, gstate, (const unsigned short*)slots, (const unsigned short*)bars, opens, need_free,
                      need_full, gbar, grem, count, end, gleft, (const unsigned char*)keys, (const unsigned char*)pcs,
-                     (const unsigned short*)inkey, gkey};
+                     (const unsigned short*)inkey, gkey, (const int*)guide, ld_guide, (const int*)glen, enter, leave, gpos, gforce};
+    return MXL_OK;
+}
+
+extern "C" int mxl_guided_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                                      unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                                      float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, float* out_probs, void* stream) {
+    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
+    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
+    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
+    DecodeRules r;
+    if (const int e = make_rules(&r, B, true, RULES_ARGS, KEY_ARGS, GUIDE_ARGS)) return e;
+#define LAUNCH_K(G, BUD, CNT, INK, GD)                                                                                                   \
+    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT, INK, GD>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V,           \
+                       (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p, \
+                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, out_probs, r)
+#define LAUNCH_D(G, BUD, CNT, GD)                   \
+    do {                                            \
+        if (gkey) LAUNCH_K(G, BUD, CNT, true, GD);  \
+        else LAUNCH_K(G, BUD, CNT, false, GD);      \
+    } while (0)
+#define LAUNCH(BUD, CNT)                            \
+    do {                                            \
+        if (gpos) LAUNCH_D(true, BUD, CNT, true);   \
+        else LAUNCH_D(true, BUD, CNT, false);       \
+    } while (0)
+    if (!gstate) LAUNCH_D(false, false, false, false);
+    else if (!gbar && !gleft) LAUNCH(false, false);
+    else if (!gleft) LAUNCH(true, false);
+    else if (!gbar) LAUNCH(false, true);
+    else LAUNCH(true, true);
+#undef LAUNCH
+#undef LAUNCH_D
+#undef LAUNCH_K
+    MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
 
@@ -1071,29 +1150,9 @@ extern "C" int mxl_keyed_sample_step(const float* scores, int ldl, int V, void* 
                                      unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                                      float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
                                      int* counter, RULES_PARAMS, KEY_PARAMS, float* out_probs, void* stream) {
-    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
-    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
-    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
-    DecodeRules r;
-    if (const int e = make_rules(&r, B, true, RULES_ARGS, KEY_ARGS)) return e;
-#define LAUNCH_K(G, BUD, CNT, INK)                                                                                                       \
-    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT, INK>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V,               \
-                       (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p, \
-                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, out_probs, r)
-#define LAUNCH(G, BUD, CNT)                   \
-    do {                                      \
-        if (gkey) LAUNCH_K(G, BUD, CNT, true); \
-        else LAUNCH_K(G, BUD, CNT, false);    \
-    } while (0)
-    if (!gstate) LAUNCH(false, false, false);
-    else if (!gbar && !gleft) LAUNCH(true, false, false);
-    else if (!gleft) LAUNCH(true, true, false);
-    else if (!gbar) LAUNCH(true, false, true);
-    else LAUNCH(true, true, true);
-#undef LAUNCH
-#undef LAUNCH_K
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
+    return mxl_guided_sample_step(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, B, do_sample, top_k, top_p, temperature,
+                                  repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_ARGS, GUIDE_OFF, out_probs,
+                                  stream);
 }
 
 extern "C" int mxl_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
@@ -1104,30 +1163,40 @@ extern "C" int mxl_sample_step(const float* scores, int ldl, int V, void* ids, i
                                  repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_OFF, nullptr, stream);
 }
 
-extern "C" int mxl_keyed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, void* stream) {
+extern "C" int mxl_guided_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                     void* stream) {
     MXL_CHECK_ARG(scores && B > 0 && V > 0 && ldl >= V && (t_dev || min_length <= 0));
     const long long n = (long long)B * V;
     MXL_CHECK_ARG(n <= (1LL << 38));
     DecodeRules r;
-    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS)) return e;
+    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS)) return e;
     if (!r.cls && !r.gkey && (r.min_length <= 0 || r.eos_id < 0 || r.eos_id >= V)) return MXL_OK;          // nothing to bar
     hipLaunchKernelGGL(rules_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V, t_dev, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
 
+extern "C" int mxl_keyed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, void* stream) {
+    return mxl_guided_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_ARGS, GUIDE_OFF, stream);
+}
+
 extern "C" int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, void* stream) {
     return mxl_keyed_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_OFF, stream);
 }
 
-extern "C" int mxl_keyed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, void* stream) {
+extern "C" int mxl_guided_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                        void* stream) {
     MXL_CHECK_ARG(ids && t_dev && B > 0 && (V > 0 || !(cls || gkey)));
     DecodeRules r;
-    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS)) return e;
+    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS)) return e;
     if (!r.cls && !r.gkey && !r.unfinished) return MXL_OK;                                       // nothing to move
     hipLaunchKernelGGL(rules_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long long*)ids, ld_ids, t_dev, B, V, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
+}
+
+extern "C" int mxl_keyed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, void* stream) {
+    return mxl_guided_rules_advance(ids, ld_ids, t_dev, B, V, RULES_ARGS, KEY_ARGS, GUIDE_OFF, stream);
 }
 
 extern "C" int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, void* stream) {
@@ -1138,6 +1207,9 @@ extern "C" int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B,
 #undef KEY_PARAMS
 #undef KEY_ARGS
 #undef KEY_OFF
+#undef GUIDE_PARAMS
+#undef GUIDE_ARGS
+#undef GUIDE_OFF
 
 extern "C" int mxl_key_scan(const void* ids, int ld_ids, int Tp, int from, int B, int V, const void* keys, const void* pcs,
                             const void* inkey, int* gkey, int* first_bad, void* stream) {

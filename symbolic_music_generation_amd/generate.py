@@ -54,13 +54,16 @@ def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch
                    stop: Optional[tuple] = None, unfinished: Optional[torch.Tensor] = None, alive: Optional[torch.Tensor] = None,
                    grammar=None, gstate: Optional[torch.Tensor] = None, gbar: Optional[torch.Tensor] = None,
                    grem: Optional[torch.Tensor] = None, gleft: Optional[torch.Tensor] = None, in_key=None,
-                   gkey: Optional[torch.Tensor] = None):
+                   gkey: Optional[torch.Tensor] = None, melody=None, guide: Optional[torch.Tensor] = None,
+                   glen: Optional[torch.Tensor] = None, gpos: Optional[torch.Tensor] = None, gforce: Optional[torch.Tensor] = None):
     """The sampler tail as separate launches (what mxl_sample_step does in one): next token of every row from the first V columns
     of `scores` -> ids[:, t + 1], position and RNG counters advanced.  stop = (eos, pad, min_length) with unfinished / alive and
     grammar with gstate are optional, and a grammar with a bar budget takes gbar / grem as well; gleft (the bars every row may
-    still open) turns the grammar's bar count on, in_key (a grammar.KeyRule) with gkey the key rule (ops.rules_in_force).  The mask
-    writes into `scores` in place.  Four launches, two where no rule is in force."""
-    rules = ops.rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey)
+    still open) turns the grammar's bar count on, in_key (a grammar.KeyRule) with gkey the key rule, melody (a grammar.MelodyGuide)
+    with guide / glen / gpos / gforce the guide rule (ops.rules_in_force).  The mask writes into `scores` in place.  Four launches, two
+    where no rule is in force."""
+    rules = ops.rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos,
+                               gforce)
     sc = scores[:, :V] if scores.shape[1] != V else scores
     # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the mask: -inf
     # stays -inf under it, so the result is the same
@@ -185,6 +188,132 @@ def key_config(in_key, key, batch: int, vocab_size: int, repeat: int = 1) -> Opt
     return torch.tensor(ks, dtype=torch.int32).repeat_interleave(int(repeat), 0).contiguous()
 
 
+def _guides_per_row(melody, batch: int) -> list:
+    """`melody` as generate takes it -> one entry per prompt, each None or a list of token ids: one guide (a 1-D tensor or a flat
+    sequence of ints) stands for every prompt, a sequence of guides (None = that row is unguided) gives one per prompt"""
+    def flat(g):
+        if g is None:
+            return None
+        if isinstance(g, torch.Tensor):
+            if g.dim() != 1 or g.is_floating_point():
+                raise ValueError('a guide is a 1-D sequence of token ids')
+            return [int(t) for t in g.detach().cpu().tolist()]
+        if isinstance(g, (str, bytes)) or not hasattr(g, '__iter__'):
+            raise ValueError('a guide is a 1-D sequence of token ids')
+        out = list(g)
+        if any(isinstance(t, (bool, float, str)) or not hasattr(t, '__index__') for t in out):
+            raise ValueError('a guide is a 1-D sequence of token ids')
+        return [int(t) for t in out]
+    if isinstance(melody, torch.Tensor) and melody.dim() == 2:
+        melody = list(melody)
+    one = isinstance(melody, torch.Tensor) or (isinstance(melody, (list, tuple)) and len(melody) > 0
+                                                and all(hasattr(t, '__index__') and not isinstance(t, torch.Tensor) for t in melody))
+    if one:
+        return [flat(melody)] * batch
+    if not isinstance(melody, (list, tuple)):
+        raise ValueError('melody is one guide (a sequence of token ids) or a list of one guide per prompt')
+    if len(melody) != batch:
+        raise ValueError(f'melody holds {len(melody)} guides for {batch} prompts: give one guide or one per prompt')
+    return [flat(g) for g in melody]
+
+
+class MelodyPlan:
+    """The guides of one generation as the decoders take them (melody_config): `rule` (the grammar's MelodyGuide), per row `guides`
+    (None or the guide's tokens) and `bars` (None or the guide split into bars), and `n_bars` (B,) int32, the start value of gleft:
+    the number of bars in the row's guide, -1 in an unguided row"""
+
+    def __init__(self, rule, guides: list, bars: list):
+        self.rule, self.guides, self.bars = rule, guides, bars
+        self.n_bars = torch.tensor([-1 if b is None else len(b) for b in bars], dtype=torch.int32)
+
+    @property
+    def B(self) -> int:
+        return len(self.guides)
+
+    def rows(self, lo: int, hi: int) -> 'MelodyPlan':
+        return MelodyPlan(self.rule, self.guides[lo:hi], self.bars[lo:hi])
+
+    def tables(self):
+        """(guide (B, W) int32, glen (B,) int32) on the CPU: the rows' guides, right-filled with 0; W >= 1"""
+        W = max([1] + [len(g) for g in self.guides if g is not None])
+        tok = torch.zeros(self.B, W, dtype=torch.int32)
+        for b, g in enumerate(self.guides):
+            if g is not None:
+                tok[b, :len(g)] = torch.tensor(g, dtype=torch.int32)
+        return tok, torch.tensor([0 if g is None else len(g) for g in self.guides], dtype=torch.int32)
+
+    def check_budget(self, grammar, gbar: list):
+        """under a bar budget, rows with a known bar length gbar[b] > 0: every guide bar walked through BarBudget.walk from (bar, 0)
+        must fit -- a melody that overfills or underfills its bar would leave the row where nothing is allowed, so it raises
+        MusicXLError naming the row, the guide index and the token"""
+        bud = grammar.budget
+        for b, bars in enumerate(self.bars):
+            if bars is None or gbar[b] <= 0:
+                continue
+            at = 0
+            for bar in bars:
+                _, _, bad = bud.walk(bar, gbar[b], 0)
+                if bad >= 0:
+                    tok = bar[bad]
+                    how = 'underfills' if (bud.need_full >> int(grammar.cls[tok])) & 1 else 'overfills'
+                    raise MusicXLError(f'the guide of row {b} {how} its bar at guide index {at + bad}: token {tok} does not fit the '
+                                       f'{gbar[b]} slots of the row\'s time signature')
+                at += len(bar)
+
+
+def melody_config(melody, batch: int, grammar, stop: Optional[tuple], n_bars=None, repeat: int = 1) -> Optional[MelodyPlan]:
+    """`melody` of a generation as the decoders take it: None, or a MelodyPlan over batch * repeat rows (`repeat` =
+    num_return_sequences: every prompt's guide repeated, as the prompts are).  melody: one guide for every prompt or a list of one
+    per prompt, None = that row is unguided (_guides_per_row); a MelodyPlan passes through.  Raises ValueError for what the rule
+    cannot work with -- no grammar, a grammar without a MelodyGuide or a bar count, no explicit eos, n_bars (the guide sets the
+    count), min_length, a wrong number of guides -- and MusicXLError for a guide that does not split into bars or whose bars the
+    grammar does not accept after a token that opens a bar."""
+    if melody is None:
+        return None
+    if isinstance(melody, MelodyPlan):
+        if melody.B != batch * int(repeat):
+            raise ValueError(f'the melody plan holds {melody.B} rows, the batch {batch * int(repeat)}')
+        return melody
+    if grammar is None:
+        raise ValueError('melody needs grammar=: the guide is fed by the token grammar (tokenizer.grammar(bar_budget=True))')
+    rule = getattr(grammar, 'guide', None)
+    if rule is None:
+        raise ValueError('melody needs a grammar with a guide rule (grammar.MelodyGuide; the music grammar has one), this one has none')
+    if grammar.bar_count is None:
+        raise ValueError('melody needs a grammar with a bar count (grammar.BarCount): the count of the guide\'s bars ends the row')
+    if stop is None:
+        raise ValueError('melody needs an explicit eos_token_id=: a row ends by emitting eos, and stopping at eos is opt-in')
+    if n_bars is not None:
+        raise ValueError('n_bars together with melody: the guide sets the number of bars')
+    if stop[2] > 0:
+        raise ValueError('melody together with min_length: the bar count ends a guided row, and min_length may bar eos where '
+                         'nothing else is allowed')
+    guides = _guides_per_row(melody, batch)
+    enters = [s for s in grammar.reachable() if int(grammar.allow[s]) & grammar.populated & rule.enter]
+    bars = []
+    for b, g in enumerate(guides):
+        if g is None:
+            bars.append(None)
+            continue
+        try:
+            split = rule.split(g)
+        except ValueError as e:
+            raise MusicXLError(f'the guide of row {b} does not split into bars: {e}') from None
+        at = 0
+        for bar in split:
+            for s0 in enters:
+                _, bad = grammar.walk(bar, s0)
+                if bad >= 0:
+                    raise MusicXLError(f'the guide of row {b} breaks the grammar at guide index {at + bad}: token {bar[bad]} is not '
+                                       f'allowed there (bar walked from state {grammar.state_names[s0]})')
+            at += len(bar)
+        bars.append(split)
+    plan = MelodyPlan(rule, guides, bars)
+    bar_count_config(plan.n_bars, batch, grammar, stop)               # the eos must be an `end` token of the count
+    r = int(repeat)
+    return plan if r == 1 else MelodyPlan(rule, [g for g in guides for _ in range(r)], [x for x in bars for _ in range(r)])
+
+
 def check_bar_count_start(grammar, n_bars: torch.Tensor, gstate: torch.Tensor):
     """rows asked for n_bars = 0 whose prompt stops where only a bar can follow (BarCount.needs_bar: the music grammar's header
     states -- no bar is open yet, and a song has one): MusicXLError naming the row, since every token would be barred there.
@@ -223,10 +352,13 @@ class RowRules:
     min_length) or None, `grammar` (with its bar budget, if it has one) or None, `bars` = the grammar's bar count is on.  One packed
     int32 buffer holds the words the sampler launches move -- unfinished (1 = live), gstate (automaton state), gbar / grem (bar
     length and free slots), gleft (bars the row may still open, < 0 = no limit), gkey (the row's key under `in_key`, a
-    grammar.KeyRule; < 0 = none), each (B,) -- then gbad (2, B), the first prompt
-    column that breaks the grammar / the budget, and alive (1,), the live-row count.  A further rule is a row here, a line in `start`
+    grammar.KeyRule; < 0 = none), gpos / gforce (the next index into the row's guide and whether the row is being fed from it, under
+    `melody`, a grammar.MelodyGuide), each (B,) -- then gbad (2, B), the first prompt
+    column that breaks the grammar / the budget, and alive (1,), the live-row count.  The guide group also keeps two tables of its
+    own here, `guide` (B, ld) int32 and `glen` (B,) int32, refilled by every `start` and regrown only for a longer guide, so that a
+    captured step finds the next generation's guides where it found the last one's.  A further rule is a row here, a line in `start`
     and a key in `kwargs` / `graph_key`."""
-    WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey')
+    WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey', 'gpos', 'gforce')
     STATE = WORDS + ('alive',)
 
     def __init__(self, batch: int, dev):
@@ -239,17 +371,36 @@ class RowRules:
         self.unfinished.fill_(1)
         self.gleft.fill_(-1)
         self.gkey.fill_(-1)
-        self.stop = self.grammar = self.n_bars = self.in_key = None
+        self.stop = self.grammar = self.n_bars = self.in_key = self.melody = self.plan = None
         self.bars = False
+        self.guide = torch.zeros(batch, 64, device=dev, dtype=torch.int32)
+        self.glen = torch.zeros(batch, device=dev, dtype=torch.int32)
 
     def start(self, ids: torch.Tensor, Tp: int, vocab_size: int, stop: Optional[tuple], grammar, n_bars: Optional[torch.Tensor],
-              in_key=None, keys: Optional[torch.Tensor] = None):
+              in_key=None, keys: Optional[torch.Tensor] = None, melody: Optional[MelodyPlan] = None):
         """the rules of a new generation over the prompts in columns 0..Tp-1 of ids (ids < 0: left pads, skipped): every row live,
         its grammar state and, under a bar budget, its bar length and free slots after its prompt computed on the device, gleft =
         n_bars ((B,) int32 from bar_count_config, or None: no bar count).  in_key (a grammar.KeyRule, or None: no key rule): gkey =
         keys ((B,) int32 from key_config), or, without them, the last key token of every row's prompt, found on the device (-1 in a
-        row without one); the prompt's pitches are not judged."""
+        row without one); the prompt's pitches are not judged.  melody (a MelodyPlan from melody_config, or None: no guide): the
+        rows' guides and their lengths go to the device tables, every row starts free at guide index 0 -- a bar open at the end of
+        the prompt is finished freely, the guide engages at the next bar -- and n_bars must be the plan's."""
         check_grammar_args(grammar, vocab_size, stop)
+        if melody is not None and (grammar is None or melody.rule is not getattr(grammar, 'guide', None) or melody.B != self.B
+                                   or n_bars is None or n_bars.tolist() != melody.n_bars.tolist()):
+            raise MusicXLError('melody needs the grammar its guide rule belongs to, one guide entry per row and n_bars = the bars '
+                               'of the guides (melody_config)')
+        self.plan, self.melody = melody, None if melody is None else melody.rule
+        self.gpos.zero_()
+        self.gforce.zero_()
+        if melody is not None:
+            tok, glen = melody.tables()
+            if tok.shape[1] > self.guide.shape[1]:
+                self.guide = torch.zeros(self.B, (tok.shape[1] + 63) // 64 * 64, device=self.guide.device, dtype=torch.int32)
+            self.guide[:, :tok.shape[1]].copy_(tok)
+            self.glen.copy_(glen)
+        else:
+            self.glen.zero_()
         if in_key is not None and in_key.vocab_size != int(vocab_size):
             raise MusicXLError(f'the key rule spans {in_key.vocab_size} tokens, the model has vocab_size {int(vocab_size)}')
         if keys is not None and (in_key is None or keys.numel() != self.B):
@@ -279,8 +430,14 @@ class RowRules:
 
     def check_prompt(self, ids: torch.Tensor):
         """after `start`: raises for a prompt that breaks the grammar or the bar budget, or that leaves a row asked for 0 bars where
-        only a bar can follow (one device read, one more only if some row has n_bars = 0)"""
-        if self.grammar is not None:
+        only a bar can follow, or for a guide that does not fit the bar length of its row (one device read, one more only if some
+        row has n_bars = 0)"""
+        if self.grammar is not None and self.plan is not None and self.grammar.budget is not None:
+            host, n = self.buf.cpu(), len(self.WORDS)                 # the words and gbad in the one read
+            raise_on_bad_prompt(self.grammar, ids, host[n * self.B:(n + 2) * self.B].view(2, self.B))
+            at = self.WORDS.index('gbar') * self.B
+            self.plan.check_budget(self.grammar, host[at:at + self.B].tolist())
+        elif self.grammar is not None:
             raise_on_bad_prompt(self.grammar, ids, self.gbad)
         if self.bars:
             check_bar_count_start(self.grammar, self.n_bars, self.gstate)
@@ -288,19 +445,23 @@ class RowRules:
     def kwargs(self) -> dict:
         """the rules keywords of ops.sample_step and sample_unfused"""
         return dict(stop=self.stop, unfinished=self.unfinished, alive=self.alive, grammar=self.grammar, gstate=self.gstate,
-                    gbar=self.gbar, grem=self.grem, gleft=self.gleft if self.bars else None, in_key=self.in_key, gkey=self.gkey)
+                    gbar=self.gbar, grem=self.grem, gleft=self.gleft if self.bars else None, in_key=self.in_key, gkey=self.gkey,
+                    melody=self.melody, guide=self.guide, glen=self.glen, gpos=self.gpos, gforce=self.gforce)
 
     def graph_key(self, dev) -> tuple:
         """what a captured sampler launch holds of the rules: which of them are on, the identity of the grammar's and the budget's
-        device tables and their class masks, the presence of the key rule and the identity of its tables.  The per-row words, the
-        keys among them, are step state and not part of it."""
+        device tables and their class masks, the presence of the key rule and the identity of its tables, the presence of the guide
+        rule with its class masks and the identity of its guide buffer.  The per-row words, the keys and the guide positions among
+        them, and the guide tokens themselves are step state and not part of it."""
         g = self.grammar
         return (self.stop,
                 None if g is None else tuple(t.data_ptr() for t in g.to(dev)) + (g.n_classes,),
                 None if g is None or g.budget is None else
                 tuple(t.data_ptr() for t in g.budget.to(dev)) + (g.budget.opens, g.budget.need_free, g.budget.need_full),
                 (g.bar_count.count, g.bar_count.end) if self.bars else None,
-                None if self.in_key is None else tuple(t.data_ptr() for t in self.in_key.to(dev)))
+                None if self.in_key is None else tuple(t.data_ptr() for t in self.in_key.to(dev)),
+                None if self.melody is None else (self.melody.enter, self.melody.leave, self.guide.data_ptr(), self.guide.stride(0),
+                                                  self.glen.data_ptr()))
 
     def snapshot(self) -> torch.Tensor:
         return self.buf.clone()
@@ -410,6 +571,38 @@ def check_in_key(ids: torch.Tensor, rule, prompt_len: Optional[int] = None, atte
     return torch.where(bad >= 0, bad + off, bad)
 
 
+def check_melody(ids: torch.Tensor, grammar, melody, prompt_len: Optional[int] = None,
+                 attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B,) int64 on the CPU, as check_grammar: for every row of ids (B, T) the first generated column (>= prompt_len) that departs
+    from the row's guide, -1 = none -- what `generate(melody=)` keeps at -1.  melody: as generate's (one guide or one per row, None
+    = the row is unguided and clean).  A column departs if it holds another token than the guide feeds there (the span from a
+    `<bar>` to its `<bass>`), if it opens a bar beyond the guide, or if it ends the row (a token of an `end` class of the grammar's
+    bar count) while guided bars were never opened.  A row cut by max_length is judged up to the cut.  prompt_len: the width of the
+    prompt; default the width of attention_mask, else 0.  The walk runs on the host (MelodyGuide.walk)."""
+    rule = getattr(grammar, 'guide', None)
+    if rule is None or grammar.bar_count is None:
+        raise ValueError('check_melody needs a grammar with a guide rule and a bar count (the music grammar has both)')
+    ids = torch.as_tensor(ids)
+    if ids.dim() == 1:
+        ids = ids.view(1, -1)
+    if prompt_len is None:
+        prompt_len = 0 if attention_mask is None else int(torch.as_tensor(attention_mask).shape[1])
+    prompt_len = int(prompt_len)
+    guides = _guides_per_row(melody, ids.shape[0])
+    end, cls, V = grammar.bar_count.end, grammar.cls, grammar.vocab_size
+    out = []
+    for row, g in zip(ids[:, prompt_len:].cpu().tolist(), guides):
+        if g is None:
+            out.append(-1)
+            continue
+        stop_at = next((i for i, t in enumerate(row) if 0 <= t < V and (end >> int(cls[t])) & 1), None)
+        pos, _, bad = rule.walk(row if stop_at is None else row[:stop_at], g)
+        if bad < 0 and stop_at is not None and pos < len(g):
+            bad = stop_at
+        out.append(bad + prompt_len if bad >= 0 else -1)
+    return torch.tensor(out, dtype=torch.int64)
+
+
 class _AlivePoll:
     """live-row counts of one decoder read back without stalling its stream: after each chunk of steps a non-blocking copy of
     `alive` into pinned host memory and an event; `wait(keep)` blocks until at most `keep` such reads are outstanding"""
@@ -469,18 +662,18 @@ def run_until_finished(decoders, n: int, chunk: int = STOP_CHUNK) -> list:
 
 
 def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool, n_pad, stop, stop_chunk,
-                 grammar, n_bars=None, in_key=None, keys=None) -> torch.Tensor:
+                 grammar, n_bars=None, in_key=None, keys=None, melody=None) -> torch.Tensor:
     """The body of `generate` for one decoder (lanes = [dec], streams = [None]) or for an XLDecoderLanes with its lanes and their
     streams: `dec.begin`, then every remaining step through `dec.replay_once` -- or, with stop = (eos, pad, min_length), each lane
     on its own until its rows have finished (run_until_finished) -- then the lanes' rows in order, cut to the width of the longest
     lane and right-filled with pad where a lane stopped earlier.  Sets `steps_run` on every lane and on dec (the most of any
     lane).  The prompt columns of left-padded prompts (n_pad) come back as given.  n_bars: None or one int32 per row
     (bar_count_config); each lane takes its rows' entries.  in_key / keys: the key rule and None or one int32 per row (key_config),
-    handed on the same way."""
+    handed on the same way, as is melody (a MelodyPlan or None)."""
     Tp = prompt.shape[1]
     if max_length - Tp <= 0:
         return prompt[:, :max_length]
-    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar, n_bars, in_key, keys)
+    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar, n_bars, in_key, keys, melody)
     if stop is None:
         for _ in range(n):
             dec.replay_once()
@@ -550,7 +743,8 @@ class XLDecoder:
         # the rules of the current generation (eos, grammar, bar budget, bar count) and their per-row words, which the sampler
         # launch reads and moves; the words are readable here under their names
         self.rules = RowRules(batch, dev)
-        self.unfinished, self.gstate, self.gbar, self.grem, self.gleft, self.gkey, self.alive = (getattr(self.rules, k) for k in RowRules.STATE)
+        (self.unfinished, self.gstate, self.gbar, self.grem, self.gleft, self.gkey, self.gpos, self.gforce,
+         self.alive) = (getattr(self.rules, k) for k in RowRules.STATE)
 
     def _tables(self):
         if self.rd is None:
@@ -569,7 +763,8 @@ class XLDecoder:
 
     # ---------------------------------------------------------------- prompt
     def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None,
-                grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None):
+                grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None,
+                melody: Optional[MelodyPlan] = None):
         """Whole prompt through the training-shape kernels with zero mems (upstream first step), rings filled from the
         per-layer qkv buffers, first new token sampled from the last position.
         n_pad: (B,) int32 device tensor, left-padded prompts: the first n_pad[b] columns of row b are pads.  Their K / V are zero
@@ -582,7 +777,9 @@ class XLDecoder:
         n_bars: None, or (B,) int32 from bar_count_config: the bars every row may still open (the grammar's bar count); it is the
         start value of `gleft`, which the sampler launches move.
         in_key: a grammar.KeyRule or None; keys: None (every row starts in the key of its prompt, found on the device, pads
-        skipped) or (B,) int32 from key_config; the start value of `gkey`, which a generated key token moves."""
+        skipped) or (B,) int32 from key_config; the start value of `gkey`, which a generated key token moves.
+        melody: None or a MelodyPlan from melody_config (with n_bars = its bar counts): the rows' guides go to the device, and a
+        guide that does not fit its row's bar length raises with the prompt checks."""
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
@@ -597,7 +794,7 @@ class XLDecoder:
             pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
             self.ids[:, :Tp].masked_fill_(pad, -1)
             x = x.masked_fill(pad, 0)
-        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars, in_key, keys)
+        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars, in_key, keys, melody)
         sink_kc, sink_vc = self.kc, self.vc
 
         def kv_sink(l, qkv):
@@ -731,7 +928,8 @@ class XLDecoder:
     # ---------------------------------------------------------------- loop
     def begin(self, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool = True,
               n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None, grammar=None,
-              n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None) -> int:
+              n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None,
+              melody: Optional[MelodyPlan] = None) -> int:
         """prompt pass + first sampled token + (use_graph) capture of one decode step; returns the number of `replay_once()`
         calls that complete the generation to max_length.  n_pad: left-padded prompts (prefill); the decode step is the same,
         every row's last prompt token sits at column Tp - 1.  stop: (eos, pad, min_length) (stop_config) or None.  grammar: a
@@ -739,12 +937,15 @@ class XLDecoder:
         class masks, so their identity is part of the graph key.  n_bars: None or (B,) int32 (prefill); the step captured under the
         bar count is another launch with two more class masks, so the presence of the rule and its masks are in the key too, while
         the counts themselves are step state (`gleft`).  in_key / keys (prefill): the step captured under the key rule is another
-        launch that reads the rule's tables, so its presence and their identity are in the key; the keys are step state (`gkey`)"""
+        launch that reads the rule's tables, so its presence and their identity are in the key; the keys are step state (`gkey`).
+        melody (prefill): the step captured under the guide rule is another launch that reads the decoder's guide buffer, so the
+        rule's presence, its masks and the buffer's identity are in the key; the guide tokens and `gpos` / `gforce` are step state,
+        and a later generation with another guide that fits the buffer replays the same graph"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         self._sampling = sampling
         self._use_graph = use_graph
-        self.prefill(prompt, sampling, n_pad, stop, grammar, n_bars, in_key, keys)
+        self.prefill(prompt, sampling, n_pad, stop, grammar, n_bars, in_key, keys, melody)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
             # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
@@ -785,7 +986,7 @@ class XLDecoder:
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
                  typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
-                 stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None) -> torch.Tensor:
+                 stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None) -> torch.Tensor:
         """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
         [OMIT]) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (prefill); the
         prompt columns, pads included, come back as given.
@@ -802,12 +1003,16 @@ class XLDecoder:
         when the last of them is full.  Without a budget the rule bars a further bar and an early eos but cannot force the end.
         in_key (a grammar.KeyRule, e.g. `tokenizer.key_rule()`; needs no grammar): a row whose key is known emits only pitches of
         that key.  key=None: every row's key is the last key token of its prompt (none: the row is unconstrained); key = a key name
-        or ordinal, or one per row with None / -1 = unconstrained, overrides the prompts.  A generated key token sets the row's key."""
+        or ordinal, or one per row with None / -1 = unconstrained, overrides the prompts.  A generated key token sets the row's key.
+        melody (one guide or one per row, None = unguided; needs grammar and eos_token_id, takes no n_bars or min_length): each
+        guide is the `<bar> <melody> ... <bass>` spans of its bars (`tokenizer.melody_guide`); the row is fed them bar by bar inside
+        the sampler launch and chooses the bass under each, then ends (melody_config, MyTransfoXLLMHeadModel.generate)."""
         stop = stop_config(eos_token_id, pad_token_id, min_length)
+        plan = melody_config(melody, self.B, grammar, stop, n_bars)
         return decode_lanes(self, [self], [None], prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
-                            stop, stop_chunk, grammar, bar_count_config(n_bars, self.B, grammar, stop), in_key,
-                            key_config(in_key, key, self.B, self.eng.cfg.vocab_size))
+                            stop, stop_chunk, grammar, bar_count_config(n_bars if plan is None else plan.n_bars, self.B, grammar, stop),
+                            in_key, key_config(in_key, key, self.B, self.eng.cfg.vocab_size), plan)
 
 
 class XLDecoderLanes:
@@ -831,11 +1036,12 @@ class XLDecoderLanes:
             d.invalidate_tables()
 
     def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None, grammar=None, n_bars=None, in_key=None,
-              keys=None) -> int:
+              keys=None, melody=None) -> int:
         steps = [d.begin(prompt[self.offs[i]:self.offs[i + 1]], max_length, sampling, use_graph,
                          None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]], stop, grammar,
                          None if n_bars is None else n_bars[self.offs[i]:self.offs[i + 1]], in_key,
-                         None if keys is None else keys[self.offs[i]:self.offs[i + 1]])
+                         None if keys is None else keys[self.offs[i]:self.offs[i + 1]],
+                         None if melody is None else melody.rows(self.offs[i], self.offs[i + 1]))
                  for i, d in enumerate(self.lanes)]
         for s in self.streams:                       # the lanes start from the prompt passes and captures issued above
             s.wait_stream(torch.cuda.current_stream())
@@ -852,14 +1058,15 @@ class XLDecoderLanes:
 
     def generate(self, prompt, max_length, do_sample=False, top_k=None, top_p=None, temperature=1.0, repetition_penalty=None,
                  typical_p=None, use_graph=True, n_pad=None, eos_token_id=None, pad_token_id=None, min_length=None,
-                 stop_chunk=STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None) -> torch.Tensor:
-        """XLDecoder.generate over the lanes (each lane keeps the grammar state, the bar counts and the keys of its own rows).  With eos_token_id every lane stops
+                 stop_chunk=STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None) -> torch.Tensor:
+        """XLDecoder.generate over the lanes (each lane keeps the grammar state, the bar counts, the keys and the guides of its own rows).  With eos_token_id every lane stops
         on its own; the output is the lanes' rows cut to the common width and right-filled with pad where a lane stopped earlier."""
         stop = stop_config(eos_token_id, pad_token_id, min_length)
+        plan = melody_config(melody, self.B, grammar, stop, n_bars)
         return decode_lanes(self, self.lanes, self.streams, prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
-                            stop, stop_chunk, grammar, bar_count_config(n_bars, self.B, grammar, stop), in_key,
-                            key_config(in_key, key, self.B, self.lanes[0].eng.cfg.vocab_size))
+                            stop, stop_chunk, grammar, bar_count_config(n_bars if plan is None else plan.n_bars, self.B, grammar, stop),
+                            in_key, key_config(in_key, key, self.B, self.lanes[0].eng.cfg.vocab_size), plan)
 
 
 class _BeamHyps:

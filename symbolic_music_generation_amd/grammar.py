@@ -49,6 +49,18 @@ no key, the row is untouched), and three tables
 
 A pitch outside the row's key is barred, and a kept Key_* token sets the row's key.  It reads neither token classes nor the automaton
 state, so it needs no grammar and composes with all of the above.
+
+`MelodyGuide` (`grammar.guide`; both forms of the music grammar carry one) is the rule behind `generate(..., melody=m)`: part of a
+row's output is given, not chosen.  A guide is the concatenation of `<bar> <melody> notes <bass>` spans, one per bar; the row is fed
+each span token by token and writes the bass under it.  Two more integers per row, `pos` = the next index into the row's guide and
+`force` = 1 while the row is being fed, and two class bit masks
+
+    enter      class bit mask  classes that open a guided span (<bar>): a free row that keeps one while guide tokens are left is
+                               fed from then on; the token is the guide's own
+    leave      class bit mask  classes that close a guided span (<bass>): a fed row that keeps one chooses freely from then on
+
+A fed row may emit the guide's next token alone, whatever the grammar, the budget, the count and the key say -- `generate` checks the
+guide against the grammar and the budget on the host -- and the bar count, set to the number of bars in the guide, ends the row.
 """
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -115,6 +127,7 @@ class TokenGrammar:
         self._dev: Dict[str, tuple] = {}
         self.budget: Optional['BarBudget'] = None        # the duration budget riding on this grammar (BarBudget attaches itself)
         self.bar_count: Optional['BarCount'] = None      # the bar count rule of generate(n_bars=) (BarCount attaches itself)
+        self.guide: Optional['MelodyGuide'] = None       # the guide rule of generate(melody=) (MelodyGuide attaches itself)
 
     # ---------------------------------------------------------------- shape
     @property
@@ -448,6 +461,101 @@ class BarCount:
         return f'BarCount(count={names(self.count)}, end={names(self.end)})'
 
 
+class MelodyGuide:
+    def __init__(self, grammar: TokenGrammar, enter, leave):
+        """The guide rule of `grammar` (module docstring): `enter` and `leave`, each a class bit mask or an iterable of class
+        names.  Attaches itself as `grammar.guide`."""
+        self.enter, self.leave = _class_mask(grammar, enter), _class_mask(grammar, leave)
+        if not self.enter or not self.leave:
+            raise ValueError('enter and leave each need at least one class')
+        if self.enter & self.leave:
+            raise ValueError('a class cannot both open and close a guided span')
+        self.grammar = grammar
+        grammar.guide = self
+
+    # ---------------------------------------------------------------- the rule
+    def forced(self, pos: int, force: int, guide) -> int:
+        """the token a row at (pos, force) is fed from `guide` at this step, -1 = none: the row chooses"""
+        return int(guide[pos]) if force and 0 <= pos < len(guide) else -1
+
+    def allows(self, pos: int, force: int, guide, tok: int) -> bool:
+        """may token `tok` follow in a row at (pos, force)?  A fed row may emit its guide token alone -- and that one whatever
+        the other rules say; a free row is theirs to judge"""
+        f = self.forced(pos, force, guide)
+        return f < 0 or int(tok) == f
+
+    def move(self, pos: int, force: int, glen: int, c: int) -> Tuple[int, int]:
+        """(pos, force) after a kept token of class c in a row whose guide holds glen tokens"""
+        if force:
+            return pos + 1, 0 if (self.leave >> c) & 1 else 1
+        if (self.enter >> c) & 1 and pos < glen:
+            return pos + 1, 1
+        return pos, 0
+
+    def split(self, guide) -> List[List[int]]:
+        """the bars of a guide: each starts with an `enter` token and ends at its first `leave` token, and nothing lies between
+        them.  Raises ValueError naming the index where that fails, or for an empty guide or a token outside the vocabulary."""
+        seq = [int(t) for t in (guide.tolist() if hasattr(guide, 'tolist') else list(guide))]
+        cls, V = self.grammar.cls, self.grammar.vocab_size
+        if not seq:
+            raise ValueError('an empty guide holds no bar')
+        bars, i = [], 0
+        while i < len(seq):
+            for j in range(i, len(seq)):
+                if not 0 <= seq[j] < V:
+                    raise ValueError(f'guide index {j}: token {seq[j]} is outside the vocabulary of {V} tokens')
+            if not (self.enter >> int(cls[seq[i]])) & 1:
+                raise ValueError(f'guide index {i}: token {seq[i]} opens no guided span (a bar starts with an `enter` token)')
+            j = next((j for j in range(i + 1, len(seq)) if (self.leave >> int(cls[seq[j]])) & 1), None)
+            if j is None:
+                raise ValueError(f'guide index {i}: the bar that starts here never reaches a `leave` token')
+            bars.append(seq[i:j + 1])
+            i = j + 1
+        return bars
+
+    def extract(self, ids, first_bar: int = 0, n_bars: Optional[int] = None) -> List[int]:
+        """the guide of a piece: over bars first_bar .. first_bar + n_bars - 1 of `ids` (default: to the last one), the tokens of
+        each from its `enter` token up to and including its first `leave` token, concatenated.  Ids < 0 are skipped."""
+        seq = [int(t) for t in (ids.tolist() if hasattr(ids, 'tolist') else list(ids)) if int(t) >= 0]
+        cls = self.grammar.cls
+        starts = [i for i, t in enumerate(seq) if (self.enter >> int(cls[t])) & 1]
+        if first_bar < 0 or (n_bars is not None and n_bars < 0):
+            raise ValueError('first_bar and n_bars must not be negative')
+        chosen = starts[first_bar:] if n_bars is None else starts[first_bar:first_bar + n_bars]
+        if n_bars is not None and len(chosen) != n_bars:
+            raise ValueError(f'bars {first_bar}..{first_bar + n_bars - 1} asked of a piece with {len(starts)} bars')
+        out = []
+        for i in chosen:
+            j = next((j for j in range(i + 1, len(seq)) if (self.leave >> int(cls[seq[j]])) & 1), None)
+            if j is None or any((self.enter >> int(cls[t])) & 1 for t in seq[i + 1:j]):
+                raise ValueError(f'the bar at index {i} never reaches a `leave` token')
+            out += seq[i:j + 1]
+        return out
+
+    # ---------------------------------------------------------------- host reference
+    def walk(self, ids, guide, gpos: int = 0, gforce: int = 0) -> Tuple[int, int, int]:
+        """(pos, force, index of the first token that departs from the guide or -1) for a 1-D id sequence in a row that starts at
+        (gpos, gforce); the walk stops there.  A token departs if the row is fed another one, or if it opens a span (`enter`) in
+        a free row whose guide is used up.  Ids < 0 (left pads) and ids beyond the vocabulary are skipped.  The host reference of
+        the device rule."""
+        seq = ids.tolist() if hasattr(ids, 'tolist') else list(ids)
+        g = [int(t) for t in (guide.tolist() if hasattr(guide, 'tolist') else list(guide))]
+        cls, V, pos, force = self.grammar.cls, self.grammar.vocab_size, int(gpos), int(gforce)
+        for i, tok in enumerate(seq):
+            tok = int(tok)
+            if tok < 0 or tok >= V:
+                continue
+            c = int(cls[tok])
+            if not self.allows(pos, force, g, tok) or (not force and (self.enter >> c) & 1 and pos >= len(g)):
+                return pos, force, i
+            pos, force = self.move(pos, force, len(g), c)
+        return pos, force, -1
+
+    def __repr__(self):
+        names = lambda m: [n for i, n in enumerate(self.grammar.class_names) if (m >> i) & 1]
+        return f'MelodyGuide(enter={names(self.enter)}, leave={names(self.leave)})'
+
+
 class KeyRule:
     def __init__(self, keys, pcs, inkey=None):
         """The key rule (module docstring) from explicit tables: keys / pcs (V,) with NO_KEY / NO_PITCH for "none", inkey (24,) bit
@@ -567,10 +675,11 @@ def music_key_rule(vocab) -> KeyRule:
 
 def from_transitions(cls, class_names: Sequence[str], transitions: Sequence[Tuple[str, str, str]], start: str,
                      accepting: Optional[Iterable[str]] = None, budget: Optional[dict] = None,
-                     bar_count: Optional[dict] = None) -> TokenGrammar:
+                     bar_count: Optional[dict] = None, guide: Optional[dict] = None) -> TokenGrammar:
     """a TokenGrammar from (state, class, successor) triples by name; states are numbered in order of appearance, `start` first.
     budget: the explicit tables of a BarBudget to attach, as its keyword arguments (slots, bars, opens, need_free, need_full).
-    bar_count: the classes of a BarCount to attach, as its keyword arguments (count, end)"""
+    bar_count: the classes of a BarCount to attach, as its keyword arguments (count, end).
+    guide: the classes of a MelodyGuide to attach, as its keyword arguments (enter, leave)"""
     states = [start]
     for a, _, b in transitions:
         for s in (a, b):
@@ -594,6 +703,8 @@ def from_transitions(cls, class_names: Sequence[str], transitions: Sequence[Tupl
         BarBudget(g, **budget)
     if bar_count is not None:
         BarCount(g, **bar_count)
+    if guide is not None:
+        MelodyGuide(g, **guide)
     return g
 
 
@@ -622,6 +733,7 @@ MUSIC_TRANSITIONS = [
 
 
 MUSIC_BAR_COUNT_CLASSES = dict(count=('<bar>',), end=('</s>',))
+MUSIC_GUIDE_CLASSES = dict(enter=('<bar>',), leave=('<bass>',))
 MUSIC_BUDGET_CLASSES = dict(opens=('<melody>', '<bass>'), need_free=('pitch', '<tup>'), need_full=('<bass>', '<bar>', '</s>'))
 
 
@@ -650,7 +762,8 @@ def music_grammar(vocab, bar_budget: bool = False) -> TokenGrammar:
     """the grammar above for a MusicVocabulary of any pitch kind: the class of a token is its `vocab.type`, and every special
     token ([PAD] and [OMIT] included) is a class of its own.  bar_budget: attach the duration budget (`grammar.budget`), so that
     every channel of a bar generated under the grammar is exactly as long as the prompt's time signature says.  Either form
-    carries the bar count rule of `generate(n_bars=)` (`grammar.bar_count`: count = <bar>, end = </s>)"""
+    carries the bar count rule of `generate(n_bars=)` (`grammar.bar_count`: count = <bar>, end = </s>) and the guide rule of
+    `generate(melody=)` (`grammar.guide`: enter = <bar>, leave = <bass>)"""
     cid = {c: i for i, c in enumerate(MUSIC_CLASSES)}
     cls = np.zeros(len(vocab), dtype=np.uint8)
     for tok, i in vocab.tok2id.items():
@@ -660,4 +773,5 @@ def music_grammar(vocab, bar_budget: bool = False) -> TokenGrammar:
             raise ValueError(f'token {tok!r} has no class in the music grammar')
         cls[i] = cid[name]
     return from_transitions(cls, MUSIC_CLASSES, MUSIC_TRANSITIONS, 'S0', accepting=['END'],
-                            budget=music_budget_tables(vocab) if bar_budget else None, bar_count=MUSIC_BAR_COUNT_CLASSES)
+                            budget=music_budget_tables(vocab) if bar_budget else None, bar_count=MUSIC_BAR_COUNT_CLASSES,
+                            guide=MUSIC_GUIDE_CLASSES)

@@ -134,11 +134,12 @@ def decode_qkv(x, wqkv, qkv, kc, vc, t_dev, rrb, qr_out, dh):
 
 
 def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None,
-                   gkey=None) -> dict:
+                   gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None) -> dict:
     """The rules of a generation as its decoders describe them -> the keywords of rules_mask / rules_advance, where a group is on
     exactly when its state tensor is given.  The decoders say which rules hold with `stop` (the eos rule), `grammar` (the grammar,
-    and its bar budget if it has one), `gleft` (the bar count) and `in_key` (the key rule) and may hand over state tensors of rules
-    that are off: those are dropped here, and a rule that is on without its state raises."""
+    and its bar budget if it has one), `gleft` (the bar count), `in_key` (the key rule) and `melody` (the guide rule, a
+    grammar.MelodyGuide) and may hand over state tensors of rules that are off: those are dropped here, and a rule that is on without
+    its state raises."""
     budget = grammar is not None and grammar.budget is not None
     if stop is not None and (unfinished is None or alive is None):
         raise MusicXLError('the eos rule needs unfinished and alive')
@@ -150,9 +151,42 @@ def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=
         raise MusicXLError('a grammar with a bar budget needs gbar and grem')
     if in_key is not None and gkey is None:
         raise MusicXLError('the key rule needs gkey')
+    if melody is not None and (grammar is None or guide is None or glen is None or gpos is None or gforce is None):
+        raise MusicXLError('the guide rides on a grammar and needs guide, glen, gpos and gforce')
+    on = melody is not None
     return dict(stop=stop, unfinished=unfinished if stop is not None else None, alive=alive if stop is not None else None,
                 grammar=grammar, gstate=gstate if grammar is not None else None, gbar=gbar if budget else None,
-                grem=grem if budget else None, gleft=gleft, in_key=in_key, gkey=gkey if in_key is not None else None)
+                grem=grem if budget else None, gleft=gleft, in_key=in_key, gkey=gkey if in_key is not None else None,
+                melody=melody, guide=guide if on else None, glen=glen if on else None, gpos=gpos if on else None,
+                gforce=gforce if on else None)
+
+
+GUIDE_KEYS = ('melody', 'guide', 'glen', 'gpos', 'gforce')
+
+
+def _guide_args(what, device, B, V=None, *, grammar=None, melody=None, guide=None, glen=None, gpos=None, gforce=None) -> list:
+    """the guide group of the mxl_guided_* entries (include/musicxl.h, "Rules of a generation"), checked: on exactly when gpos is
+    given, with the class masks of `melody` (a grammar.MelodyGuide over `grammar`), the rows' guide tokens guide (B, ld) int32 and
+    their lengths glen (B,) int32, and the second word gforce"""
+    if gpos is None:
+        if gforce is not None:
+            raise MusicXLError(f'{what}: gforce needs gpos')
+        return [None, 0, None, 0, 0, None, None]
+    if melody is None or grammar is None or melody.grammar is not grammar:
+        raise MusicXLError(f'{what}: gpos needs melody, the guide rule of the grammar (grammar.guide)')
+    if guide is None or glen is None or gforce is None:
+        raise MusicXLError(f'{what}: the guide group needs guide, glen, gpos and gforce')
+    if V is not None and grammar.vocab_size != int(V):
+        raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
+    for t, name in ((guide, 'guide'), (glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
+        _req(t, torch.int32, f'{what} {name}')
+    if guide.dim() != 2 or guide.shape[0] != B or guide.shape[1] < 1 or guide.stride(1) != 1 or guide.stride(0) < guide.shape[1]:
+        raise MusicXLError(f'{what}: guide must be ({B}, >= 1) int32 rows with unit column stride')
+    for t, name in ((glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
+        if t.numel() != B or not t.is_contiguous():
+            raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
+    # (glen[b] <= the row width is the caller's to keep; the kernels clamp to ld_guide as well)
+    return [_p(guide), guide.stride(0), _p(glen), melody.enter, melody.leave, _p(gpos), _p(gforce)]
 
 
 def _key_args(what, device, B, V=None, *, in_key=None, gkey=None) -> list:
@@ -171,10 +205,11 @@ def _key_args(what, device, B, V=None, *, in_key=None, gkey=None) -> list:
 
 
 def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None,
-                gleft=None) -> list:
+                gleft=None, guided=False) -> list:
     """the flat rules arguments of mxl_sample_step / mxl_rules_mask / mxl_rules_advance (include/musicxl.h, "Rules of a generation"),
     checked: a group is on exactly when its state tensor is given -- unfinished (with alive and stop = (eos, pad, min_length)),
-    gstate, gbar (with grem), gleft; the last three take their tables from `grammar`, which must classify the V tokens of the scores"""
+    gstate, gbar (with grem), gleft; the last three take their tables from `grammar`, which must classify the V tokens of the scores.
+    guided: the guide group is on (_guide_args), which reads the token classes as well"""
     eos, pad, min_length = stop if stop is not None else (-1, 0, 0)
     if unfinished is not None:
         if stop is None:
@@ -182,9 +217,9 @@ def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=No
         _req(unfinished, torch.int32, f'{what} unfinished')
     cls = allow = nxt = slots = bars = None
     bud = cnt = None
-    if gstate is not None or gbar is not None or grem is not None or gleft is not None:
+    if gstate is not None or gbar is not None or grem is not None or gleft is not None or guided:
         if grammar is None:
-            raise MusicXLError(f'{what}: gstate, gbar / grem and gleft ride on a grammar')
+            raise MusicXLError(f'{what}: gstate, gbar / grem, gleft and the guide ride on a grammar')
         if V is not None and grammar.vocab_size != int(V):
             raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
         cls, allow, nxt = grammar.to(device)
@@ -211,47 +246,56 @@ def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=No
 
 
 def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
-                grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None, do_sample=False, top_k=0,
-                top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0, out_probs=None):
+                grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None, melody=None, guide=None,
+                glen=None, gpos=None, gforce=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0,
+                typical_p=1.0, out_probs=None):
     """sampler + embedding row of the sampled token (-> emb_out (B, d) bf16) + counter advance, one launch (V <= 2048).
     scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1.
     The rules of the generation ride on the same launch (rules_in_force): stop = (eos_id, pad_id, min_length) with unfinished (B,)
     int32 and alive (1,) int32 on the device; grammar (a grammar.TokenGrammar) with gstate (B,) int32, barred tokens masked and gstate
     advanced, with or without the eos rule; a grammar with a bar budget (grammar.budget) needs gbar and grem (B,) int32 as well;
     gleft (B,) int32, the bars every row may still open (< 0 = no limit), turns the grammar's bar count on; in_key (a grammar.KeyRule)
-    with gkey (B,) int32, the key of every row (< 0 = none), bars the pitches outside it, with or without a grammar.
+    with gkey (B,) int32, the key of every row (< 0 = none), bars the pitches outside it, with or without a grammar; melody (a
+    grammar.MelodyGuide, `grammar.guide`) with guide (B, ld) int32, glen, gpos and gforce (B,) int32 feeds rows from their guides.
     out_probs (B, V) f32, with do_sample: the renormalised distribution the tokens were drawn from (test hook)."""
     B = scores.shape[0]
-    force = rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey)
+    force = rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos, gforce)
     keyed = _key_args('sample_step', scores.device, B, V, in_key=force.pop('in_key'), gkey=force.pop('gkey'))
-    rules = _rules_args('sample_step', scores.device, B, V, **force)
+    guided = _guide_args('sample_step', scores.device, B, V, grammar=grammar, **{k: force.pop(k) for k in GUIDE_KEYS})
+    rules = _rules_args('sample_step', scores.device, B, V, guided=guided[0] is not None, **force)
     if out_probs is not None:
         _req(out_probs, torch.float32, 'sample_step out_probs')
         if tuple(out_probs.shape) != (B, int(V)) or not out_probs.is_contiguous():
             raise MusicXLError(f'sample_step: out_probs must be contiguous ({B}, {int(V)}) f32')
-    check(lib().mxl_keyed_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
+    check(lib().mxl_guided_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
                                       int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
                                       float(repetition_penalty if repetition_penalty is not None else 1.0),
                                       float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
-                                      float(scale), _p(counter), *rules, *keyed, _p(out_probs), _stream()), 'mxl_keyed_sample_step')
+                                      float(scale), _p(counter), *rules, *keyed, *guided, _p(out_probs), _stream()),
+          'mxl_guided_sample_step')
 
 
-def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None):
+def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None,
+               melody=None, guide=None, glen=None, gpos=None, gforce=None):
     """before sample: scores[b, v] = -inf in place for every token a rule bars (mxl_rules_mask).  A rule is applied exactly when its
     state is given: gstate (the grammar in state gstate[b]), gbar and grem (its bar budget), gleft (its bar count), each with
-    `grammar` for the tables, and gkey (the key rule in key gkey[b]) with `in_key` for its tables; stop = (eos, pad, min_length) bars
-    eos while the rows are shorter than min_length.  No launch when nothing is given."""
+    `grammar` for the tables, gkey (the key rule in key gkey[b]) with `in_key` for its tables, and gpos with gforce, guide, glen and
+    `melody` (the guide rule: a row fed from its guide keeps that one token); stop = (eos, pad, min_length) bars eos while the rows are
+    shorter than min_length.  No launch when nothing is given."""
     _req(scores, torch.float32, 'rules_mask scores')
     B = scores.shape[0]
     if scores.shape[1] < V or scores.stride(1) != 1:
         raise MusicXLError('rules_mask: scores must be (B, >= V) with unit column stride')
-    rules = _rules_args('rules_mask', scores.device, B, V, stop=stop, grammar=grammar, gstate=gstate, gbar=gbar, grem=grem, gleft=gleft)
+    rules = _rules_args('rules_mask', scores.device, B, V, stop=stop, grammar=grammar, gstate=gstate, gbar=gbar, grem=grem, gleft=gleft,
+                        guided=gpos is not None)
     keyed = _key_args('rules_mask', scores.device, B, V, in_key=in_key, gkey=gkey)
-    check(lib().mxl_keyed_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, *keyed, _stream()), 'mxl_keyed_rules_mask')
+    guided = _guide_args('rules_mask', scores.device, B, V, grammar=grammar, melody=melody, guide=guide, glen=glen, gpos=gpos, gforce=gforce)
+    check(lib().mxl_guided_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, *keyed, *guided, _stream()),
+          'mxl_guided_rules_mask')
 
 
 def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None,
-                  in_key=None, gkey=None):
+                  in_key=None, gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None):
     """after sample + decode_advance: the words given (as rules_mask) move along the token at ids[b, t] in every row that chose it,
     then, with unfinished and alive, that token goes through the stop rule stop = (eos, pad, min_length): rows with unfinished[b] == 0
     get pad and keep their words (mxl_rules_advance).  No launch when nothing is given."""
@@ -259,12 +303,14 @@ def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar
     if ids.dtype != torch.int64:
         raise MusicXLError('rules_advance: ids must be (B, .) int64')
     rules = _rules_args('rules_advance', ids.device, B, stop=stop, unfinished=unfinished, alive=alive, grammar=grammar, gstate=gstate,
-                        gbar=gbar, grem=grem, gleft=gleft)
+                        gbar=gbar, grem=grem, gleft=gleft, guided=gpos is not None)
     if grammar is not None and in_key is not None and gkey is not None and grammar.vocab_size != in_key.vocab_size:
         raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the key rule spans {in_key.vocab_size}')
     keyed = _key_args('rules_advance', ids.device, B, in_key=in_key, gkey=gkey)
     V = grammar.vocab_size if grammar is not None else (in_key.vocab_size if gkey is not None else 0)
-    check(lib().mxl_keyed_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, *rules, *keyed, _stream()), 'mxl_keyed_rules_advance')
+    guided = _guide_args('rules_advance', ids.device, B, grammar=grammar, melody=melody, guide=guide, glen=glen, gpos=gpos, gforce=gforce)
+    check(lib().mxl_guided_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, *rules, *keyed, *guided, _stream()),
+          'mxl_guided_rules_advance')
 
 
 def key_scan(ids, Tp, in_key, gkey, first_bad, check_from=None):

@@ -154,7 +154,7 @@ class MyReformerModelWithLMHead(EngineModule):
                  num_beam_groups: int = 1, length_penalty: float = 1.0, diversity_penalty=None,
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
-                 grammar=None, n_bars=None, in_key=None, key=None, **unsupported):
+                 grammar=None, n_bars=None, in_key=None, key=None, melody=None, **unsupported):
         """`model.generate(...)` as the reference drives it (musicnlp/trainer/eval.py:277-333): greedy, or sampling with
         top-k / top-p / typical-p / temperature / repetition penalty (applied, as HF does, to the raw logits); token selection
         runs on the device (the TransfoXL decoder's sampler kernel).
@@ -181,13 +181,21 @@ class MyReformerModelWithLMHead(EngineModule):
 
         in_key (a `grammar.KeyRule`, `tokenizer.key_rule()`) with key (None = the last key token of every prompt; a key name or
         ordinal, or one per prompt, None / -1 = unconstrained): greedy decoding and sampling in which a row whose key is known emits
-        only pitches of that key, as MyTransfoXLLMHeadModel.generate; it needs no grammar."""
+        only pitches of that key, as MyTransfoXLLMHeadModel.generate; it needs no grammar.
+
+        melody (one guide for every prompt or a list of one per prompt, None = unguided; with grammar and eos_token_id, greedy
+        decoding and sampling; no n_bars or min_length beside it): every guided row is fed the `<bar> <melody> ... <bass>` spans
+        of its guide (`tokenizer.melody_guide`) bar by bar and writes the bass under each, then ends, as
+        MyTransfoXLLMHeadModel.generate -- here through the mask launch before the sampler and the advance after it."""
         from .generate import (STOP_CHUNK, RowRules, bar_count_config, beam_generate, check_grammar_args, key_config, left_pad_counts,
-                               resolve_max_length, sample_unfused, sampling_config, stop_config, stop_width)
+                               melody_config, resolve_max_length, sample_unfused, sampling_config, stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
         check_grammar_args(grammar, self.config.vocab_size, stop)
+        if melody is not None and (num_beams > 1 or num_beam_groups != 1 or (penalty_alpha and not do_sample)):
+            raise MusicXLError('melody= is supported for greedy decoding and sampling only, not for beam, group-beam or contrastive '
+                               'search')
         if grammar is not None and (num_beams > 1 or num_beam_groups != 1):
             raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam or group-beam search')
         if n_bars is not None and (num_beams > 1 or num_beam_groups != 1 or (penalty_alpha and not do_sample)):
@@ -196,7 +204,9 @@ class MyReformerModelWithLMHead(EngineModule):
         if (in_key is not None or key is not None) and (num_beams > 1 or num_beam_groups != 1 or (penalty_alpha and not do_sample)):
             raise MusicXLError('in_key= is supported for greedy decoding and sampling only, not for beam, group-beam or contrastive '
                                'search')
-        n_bars = bar_count_config(n_bars, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, nrs)
+        plan = melody_config(melody, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, n_bars, nrs)
+        n_bars = (bar_count_config(n_bars, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, nrs) if plan is None
+                  else plan.n_bars)
         keys = key_config(in_key, key, input_ids.shape[0] if input_ids is not None else 0, self.config.vocab_size, nrs)
         if attention_mask is not None and input_ids is not None and any(left_pad_counts(attention_mask, tuple(input_ids.shape))):
             # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
@@ -260,7 +270,7 @@ class MyReformerModelWithLMHead(EngineModule):
                 dec.seed = seed
                 return dec.generate(ids0, max_length, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
                                     repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop, grammar=grammar, n_bars=n_bars,
-                                    in_key=in_key, key=keys)
+                                    in_key=in_key, key=keys, melody=plan)
             V = c.vocab_size
             pad = getattr(c, 'pad_token_id', None)
             pad = 0 if pad is None else int(pad)
@@ -269,7 +279,7 @@ class MyReformerModelWithLMHead(EngineModule):
             t_dev = torch.full((1,), Tp - 1, device=self.device, dtype=torch.int32)
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
             rules = RowRules(B, self.device)
-            rules.start(buf, Tp, V, stop, grammar, n_bars, in_key, keys)
+            rules.start(buf, Tp, V, stop, grammar, n_bars, in_key, keys, plan)
             rules.check_prompt(buf)
             sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
             for cur in range(Tp, max_length):

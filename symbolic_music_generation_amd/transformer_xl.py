@@ -198,7 +198,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  renormalize_logits=None, num_return_sequences: int = 1, num_beam_groups: int = 1, length_penalty: float = 1.0,
                  use_graph: bool = True, seed: int = 77, attention_mask: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
-                 min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, **unused) -> torch.Tensor:
+                 min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, melody=None,
+                 **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -244,9 +245,23 @@ class MyTransfoXLLMHeadModel(EngineModule):
         prompts' keys.  The prompt only supplies the key: its own pitches are not judged.  A generated `Key_*` token sets the row's
         key from then on.  The key lives on the device beside the other rules' words and the mask sits in the same sampler launch,
         in the same place.  It needs no `grammar` and combines with everything greedy decoding and sampling take.  Beam,
-        group-beam and contrastive search take no `in_key`."""
+        group-beam and contrastive search take no `in_key`.
+
+        `melody` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): here is a melody, write the bass
+        under it.  A guide is the concatenation of the `<bar> <melody> ... <bass>` spans of its bars, each bar up to and including
+        its `<bass>` token (`tokenizer.melody_guide(ids, first_bar, n_bars)` cuts one from a piece); `melody` is one guide for every
+        prompt or a list of one per prompt (repeated per prompt under `num_return_sequences`), where None leaves that row unguided.
+        In every guided bar the span is fed to the row, not sampled -- on the device, inside the sampler launch of the captured
+        step, as the mask "every token but this one is barred" -- and the row chooses the bass given all of it.  A bar that is open
+        at the end of the prompt is finished freely; the guide engages at the next `<bar>`.  The row opens exactly the guide's bars
+        and then ends: the guide sets the bar count, so `n_bars` is refused beside it, as is `min_length` (ValueError); under
+        `tokenizer.grammar(bar_budget=True)` the row emits eos exactly when the bass of its last guided bar is full.  The guide must
+        split into such bars, the grammar must accept them, and under a bar budget a guided melody must fill its bar exactly in a
+        row whose time signature is known (MusicXLError naming row, guide index and token).  Guide tokens are not judged by
+        `in_key`: real melodies hold off-key notes, as prompts do.  It combines with everything `grammar` combines with;
+        `generate.check_melody` verifies an output.  Beam, group-beam and contrastive search take no `melody`."""
         from .generate import (XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, check_grammar_args, contrastive_search,
-                               key_config, left_pad_counts, resolve_max_length, stop_config)
+                               key_config, left_pad_counts, melody_config, resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -269,6 +284,9 @@ class MyTransfoXLLMHeadModel(EngineModule):
         if n_pad is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('padded prompts (attention_mask with zeros) are supported for greedy decoding and sampling only, not '
                                'for beam, group-beam or contrastive search')
+        if melody is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
+            raise MusicXLError('melody= is supported for greedy decoding and sampling only, not for beam, group-beam or '
+                               'contrastive search')
         if grammar is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
@@ -278,7 +296,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
         if (in_key is not None or key is not None) and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('in_key= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
-        n_bars = bar_count_config(n_bars, input_ids.shape[0], grammar, stop, num_return_sequences)
+        plan = melody_config(melody, input_ids.shape[0], grammar, stop, n_bars, num_return_sequences)
+        n_bars = bar_count_config(n_bars, input_ids.shape[0], grammar, stop, num_return_sequences) if plan is None else None
         keys = key_config(in_key, key, input_ids.shape[0], self.config.vocab_size, num_return_sequences)
         if contrastive:
             dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
@@ -308,5 +327,5 @@ class MyTransfoXLLMHeadModel(EngineModule):
         return dec.generate(input_ids.to(self.device), max_length, do_sample=do_sample, top_k=top_k, top_p=top_p,
                             temperature=temperature, repetition_penalty=repetition_penalty, typical_p=typical_p,
                             use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device), grammar=grammar, n_bars=n_bars,
-                            in_key=in_key, key=keys,
+                            in_key=in_key, key=keys, melody=plan,
                             **({} if stop is None else dict(eos_token_id=stop[0], pad_token_id=stop[1], min_length=stop[2])))

@@ -220,6 +220,19 @@ class MusicTokenizer:
         """the key rule (`MusicVocabulary.key_rule`), for `model.generate(in_key=...)`"""
         return self.vocab.key_rule()
 
+    def melody_guide(self, ids, first_bar: int = 0, n_bars: Optional[int] = None) -> List[int]:
+        """the guide of `model.generate(melody=...)` from the token ids of a whole piece (a list or a 1-D tensor): over bars
+        first_bar .. first_bar + n_bars - 1 (default: to the last bar) the concatenation of `<bar> <melody> ... <bass>`, each bar up
+        to and including its `<bass>` token -- the melody to write a new bass under.  Raises MusicXLError if `ids` breaks the
+        grammar, ValueError if the piece has no such bars."""
+        from ._lib import MusicXLError
+        g = self.grammar()
+        seq = [int(t) for t in (ids.tolist() if hasattr(ids, 'tolist') else list(ids))]
+        _, bad = g.walk(seq)
+        if bad >= 0:
+            raise MusicXLError(f'melody_guide: the piece breaks the grammar at index {bad}: token {seq[bad]} is not allowed there')
+        return g.guide.extract(seq, first_bar, n_bars)
+
     def tokenize(self, text: str) -> List[str]:
         return text.split()
 
