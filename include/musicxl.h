@@ -573,6 +573,42 @@ int mxl_grammar_scan(const void* ids, int ld_ids, int Tp, int B, int V, const vo
  * reports those) skipped.  first_bad[b] = column of the first token the budget bars, where the walk of that row stops; -1 = none. */
 int mxl_budget_scan(const void* ids, int ld_ids, int Tp, int B, int V, const void* cls, const void* slots, const void* bars,
                     unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, int* first_bad, void* stream);
+/* ------------------------------------------------------------------------------------------------------------
+ * Beam search on the device (HF 4.25.1 beam_search + BeamSearchScorer.process).  An item is the nb <= 16 decoder rows of one prompt,
+ * rows b * nb .. b * nb + nb - 1 of rows = Bs * nb; one workgroup per item, one launch per decode step, between mxl_rules_mask and
+ * mxl_decode_advance / mxl_rules_advance.  cur_len = *t_dev + 1: the rows hold columns 0..cur_len-1, the chosen token goes to cur_len.
+ *
+ * select: the 2 * nb best of the nb * V candidates logp[r][v] + beam_scores[r] (logp (rows, ldl) f32, ldl >= V >= 2, already masked
+ *   by the rules: -inf = barred), ordered by score descending, then by flat index j * V + v ascending (j = the beam within the item);
+ *   that order is part of the contract.  -inf takes part like any number and sorts last.  Exact for any V.
+ * walk: the candidates in rank order.  An eos at rank < nb joins the item's hypothesis store with score s / cur_len ** length_penalty:
+ *   a free slot takes it, a full store replaces its worst entry (the lowest slot among equals) only if the newcomer beats it; an eos at
+ *   rank >= nb is skipped; the first nb other candidates continue: beam_scores[row] = s, beam_idx[row] = the row they continue (int32,
+ *   a row of the whole batch), their token -> ids[row][cur_len].  Then done |= (the store is full) && (early_stopping || worst stored
+ *   score >= rank-0 score / cur_len ** length_penalty), and *n_done counts the items that became done.  An item done before the launch
+ *   is frozen: identity beam_idx, pad_id tokens, scores and store untouched.
+ * store: hyp_ids (Bs, nb, ld_ids) int64 with hyp_len (Bs, nb) int32 and hyp_score (Bs, nb) f32, slots 0..hyp_n[b]-1 of item b in use;
+ *   hyp_n (Bs,), done (Bs,) and n_done (1,) int32, all zero before the first step.  The added hypotheses ids[src][:cur_len] are copied
+ *   before anything in ids moves.
+ * reorder: ids (rows, ld_ids) int64 follows beam_idx in place, columns 0..cur_len-1; moved[b] = 0 when item b's beam_idx is the
+ *   identity.  words (optional, with n_words <= 256 and word_stride >= rows): packed per-row int32 words, word w of row r at
+ *   words[w * word_stride + r] (the rules' state words); every word of every row follows beam_idx the same way.
+ * dead rows: a row that continues from a -inf candidate -- a barred token, or the child of a dead row -- gets pad_id and keeps -inf.
+ *   With words given its word 0, the stop group's `unfinished`, is cleared, as are those of the rows of a done item: the advance
+ *   launch with the stop group on then leaves the row's words alone, the mask launch keeps a valid state, the ring attention skips it.
+ * Every pointer of the store group is needed; words == NULL exactly when n_words == 0; nb > 16 and anything else amiss is MXL_EINVAL. */
+int mxl_beam_step(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs, int nb, int V,
+                  int eos_id, int pad_id, float length_penalty, int early_stopping, void* hyp_ids, int* hyp_len, float* hyp_score,
+                  int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved, int* words, int n_words, int word_stride,
+                  void* stream);
+/* Contiguous (rows, row_bytes) buffers follow beam_idx in place, item by item (the K/V rings of a decoder: HF _reorder_cache without
+ * the second buffer).  buf: one buffer (n_bufs = 1), or table: a device array of n_bufs buffer addresses, one launch for all of them;
+ * exactly one of the two is given.  A thread owns one 16-byte column of an item, reads the sources of the rows that change into
+ * registers, then writes them: a swap or a cycle needs no copy.  A workgroup whose item has moved[b] == 0 returns before touching
+ * memory, rows with beam_idx[r] == r are not written, an index outside the row's item counts as r.  row_bytes % 16 == 0, buffers
+ * 16-byte aligned, nb <= 16, Bs and n_bufs <= 65535; else MXL_EINVAL. */
+int mxl_beam_reorder(void* buf, const void* table, int n_bufs, int Bs, int nb, long long row_bytes, const int* beam_idx,
+                     const int* moved, void* stream);
 /* Contrastive search (the reference's 'contrastive' strategy, musicnlp/trainer/eval.py:296-302, over the mems patch of
  * musicnlp/models/transformer_xl.py:229-234; HF 4.25.1 GenerationMixin.contrastive_search with `_ranking_fast`):
  *   score[b*K + k] = (1 - alpha) * probs[b*K + k] - alpha * max_{s < S} cos(hid[b*K + k], ctx[b][s]);  sel[b] = argmax_k score

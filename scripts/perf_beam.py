@@ -1,0 +1,84 @@
+"""Beam search with the scorer on the device against the host scorer, at the C5 decode shape of bench.py (12L/768d, M = 2048,
+V = 1190): 8 prompts of 256 tokens, num_beams = 4 (32 decoder rows), 256 new tokens, an eos that never fires, through
+model.generate.
+
+  device  generate.beam_search_device: rules mask, mxl_beam_step, mxl_beam_reorder over the ring table, advance, model -- one
+          captured graph per step, the done count read a chunk late
+  host    MXL_BEAM_HOST=1, generate.beam_search: topk, three .tolist() reads, the Python walk, three uploads, index_select + copy_
+          over ids and the 2 * n_layer rings, eager launches
+
+The two are alternated in one process on one device, RUNS (5) times each after one warm-up call each; reports the median and the
+min..max of the tokens per second (new tokens of the best hypothesis per prompt: 8 x 256 per call) and the library launches per
+step of either path (the host path's torch launches -- topk, the index_select / copy_ pairs, the uploads -- come on top).
+
+    python3 scripts/perf_beam.py                  # env: RUNS (5), NEW (256)
+"""
+import os
+import statistics
+import sys
+import time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from symbolic_music_generation_amd import ops
+from symbolic_music_generation_amd.transformer_xl import MyTransfoXLConfig, MyTransfoXLLMHeadModel
+
+dev = torch.device('cuda:0')
+V, M, B, Tp, NB = 1190, 2048, 8, 256, 4
+NEW, RUNS = int(os.environ.get('NEW', 256)), int(os.environ.get('RUNS', 5))
+L = Tp + NEW
+cfg = MyTransfoXLConfig('base', max_length=2048, vocab_size=V, mem_len=M, cutoffs=[])
+model = MyTransfoXLLMHeadModel(cfg, device=dev, seed=77).eval()
+ids = torch.randint(4, V, (B, Tp), generator=torch.Generator().manual_seed(77)).to(dev)
+kw = dict(input_ids=ids, max_length=L, num_beams=NB, early_stopping=True, eos_token_id=V + 1, pad_token_id=0)
+
+calls = [0]
+_check = ops.check
+
+
+def counting_check(code, what=''):
+    calls[0] += 1
+    return _check(code, what)
+
+
+def run(host: bool, **extra):
+    if host:
+        os.environ['MXL_BEAM_HOST'] = '1'
+    else:
+        os.environ.pop('MXL_BEAM_HOST', None)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = model.generate(**{**kw, **extra})
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+with torch.no_grad():
+    # library launches per step: one short eager call of either path, the prompt pass's share taken off with a second, shorter one
+    ops.check = counting_check
+    per_step = {}
+    for host in (False, True):
+        n = []
+        for new in (3, 11):
+            calls[0] = 0
+            run(host, max_length=Tp + new, use_graph=False)
+            n.append(calls[0])
+        per_step[host] = (n[1] - n[0]) / 8
+    ops.check = _check
+    (_, a), (_, b) = run(False), run(True)                                     # warm-up of both paths; they return the same ids
+    same = torch.equal(a, b)
+    times = {False: [], True: []}
+    for _ in range(RUNS):
+        for host in (False, True):
+            times[host].append(run(host)[0])
+    print(f'beam search, C5 decode shape: {B} prompts x {Tp}, num_beams {NB} ({B * NB} rows), {NEW} new tokens, eos never fires; '
+          f'device ids == host ids: {same}')
+    for host, name in ((False, 'device'), (True, 'host  ')):
+        tps = sorted(B * NEW / t for t in times[host])
+        print(f'{name}: {statistics.median(tps):9.1f} tok/s median of {RUNS} (min {tps[0]:.1f}, max {tps[-1]:.1f}); '
+              f'{statistics.median(times[host]):.3f} s per call; {per_step[host]:.1f} library launches per step, '
+              f'{"3 host reads + 3 uploads + 1 sync per step" if host else "no host read per step, one graph replay"}')
+    d, h = sorted(B * NEW / t for t in times[False]), sorted(B * NEW / t for t in times[True])
+    gap = statistics.median(d) / statistics.median(h)
+    clear = d[0] > h[-1]
+    print(f'device / host = {gap:.3f}x; the slowest device run is {"above" if clear else "NOT above"} the fastest host run '
+          f'({d[0]:.1f} vs {h[-1]:.1f} tok/s): the gap {"exceeds" if clear else "does not exceed"} the run-to-run spread')

@@ -1,4 +1,5 @@
-"""Build libmusicxl.so (every HIP translation unit under csrc/) for gfx950 with hipcc, in-tree.
+"""Build libmusicxl.so (every HIP translation unit under csrc/, beam.hip among them: the list is the directory) for gfx950 with
+hipcc, in-tree.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU-only build container as well as on the MI355X box.
 The resulting .so is git-ignored but travels with the repo snapshot.

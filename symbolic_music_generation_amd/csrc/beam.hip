@@ -1,0 +1,254 @@
+// Beam search on the device (HF 4.25.1 `beam_search` + `BeamSearchScorer.process`, as generate.beam_search / _BeamHyps state them on
+// the host): one launch per decode step that selects, walks, stores and reorders, and one that makes the K/V rings follow their beams.
+//
+// An item is the nb decoder rows of one prompt, rows b * nb .. b * nb + nb - 1.  One workgroup per item:
+//   select   the 2 * nb best of the nb * V candidates logp[r][v] + beam_scores[r], ordered by score descending, then by flat index
+//            j * V + v ascending.  2 * nb rounds of a workgroup arg-max over the keys that come strictly after the previous round's
+//            key: score and index are packed into one 64-bit word whose unsigned order is that order, so a round is one max
+//            reduction, exact for any V, with no marking and no sort.  -inf takes part like any number and sorts last.
+//   walk     thread 0, over a handful of scalars in LDS: an eos among the first nb ranks joins the item's hypothesis store (a free
+//            slot, else it replaces the worst entry if it beats it), an eos behind them is skipped, the first nb other candidates
+//            continue; then the done test, both early_stopping arms.  A done item is frozen: identity, pad tokens, nothing else moves.
+//   copy     the added hypotheses ids[src][:cur_len] -> the store, by the whole workgroup, before anything in ids moves
+//   reorder  ids rows in place: a thread owns columns, reads the nb sources of a column into registers, then writes them, so a swap
+//            needs no second buffer; the chosen tokens go to column cur_len.  The packed per-row rule words follow the same way.
+//   dead     a row that continues from a -inf candidate (a barred token, or the child of a dead row) gets pad and keeps -inf; its
+//            `unfinished` word (word 0) is cleared, so the rules' advance launch -- with its stop group on -- leaves its words alone,
+//            the mask launch keeps finding a valid state, and the ring attention skips it.  The rows of a done item are cleared too.
+#include "common.h"
+#include "musicxl_internal.h"
+
+namespace {
+
+constexpr int BEAM_MAX = 16;                 // beams per item: the register rows of the reorder
+constexpr int BEAM_T = 256;
+
+// (score, flat index) -> a word whose unsigned order is "score ascending, then index descending": the best candidate is the max
+__device__ __forceinline__ unsigned long long beam_key(float s, uint32_t idx) {
+    uint32_t u = __float_as_uint(s + 0.0f);                          // (-0 -> +0: equal scores must tie)
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
+}
+__device__ __forceinline__ float beam_key_score(unsigned long long k) {
+    const uint32_t u = (uint32_t)(k >> 32);
+    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+}
+__device__ __forceinline__ uint32_t beam_key_index(unsigned long long k) { return 0xFFFFFFFFu - (uint32_t)k; }
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)k, o, 64), hi = __shfl_xor((uint32_t)(k >> 32), o, 64);
+        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
+        k = other > k ? other : k;
+    }
+    return k;
+}
+
+__global__ __launch_bounds__(BEAM_T) void beam_step_kernel(const float* logp, int ldl, float* beam_scores, long long* ids, int ld_ids,
+                                                           const int* t_dev, int nb, int V, int eos_id, int pad_id,
+                                                           float length_penalty, int early_stopping, long long* hyp_ids, int* hyp_len,
+                                                           float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx,
+                                                           int* moved, int* words, int n_words, int word_stride) {
+    __shared__ unsigned long long sh_part[BEAM_T / 64];
+    __shared__ unsigned long long sh_cand[2 * BEAM_MAX];
+    __shared__ float sh_score[BEAM_MAX], hs[BEAM_MAX];               // hs: the scores of the item's store (thread 0)
+    __shared__ int sh_src[BEAM_MAX], sh_tok[BEAM_MAX], sh_dead[BEAM_MAX], sh_add[BEAM_MAX];
+    __shared__ int sh_moved, sh_clear;
+    const int b = blockIdx.x, tid = threadIdx.x, row0 = b * nb;
+    const int cur_len = *t_dev + 1;                                  // columns 0..cur_len-1 hold the rows; the new token goes to cur_len
+    if (cur_len < 1 || cur_len >= ld_ids) return;                    // (the host keeps max_length within the buffer)
+    const bool frozen = done[b] != 0;
+
+    if (!frozen) {
+        if (tid < nb) sh_score[tid] = beam_scores[row0 + tid];
+        __syncthreads();
+        unsigned long long prev = ~0ull;
+        for (int round = 0; round < 2 * nb; round++) {
+            unsigned long long best = 0;
+            for (int j = 0; j < nb; j++) {
+                const float* row = logp + (size_t)(row0 + j) * ldl;
+                const float bs = sh_score[j];
+                const uint32_t base = (uint32_t)j * (uint32_t)V;
+                for (int v = tid; v < V; v += BEAM_T) {
+                    const unsigned long long k = beam_key(row[v] + bs, base + v);
+                    if (k < prev && k > best) best = k;
+                }
+            }
+            best = wave_max_u64(best);
+            if ((tid & 63) == 0) sh_part[tid >> 6] = best;
+            __syncthreads();
+            best = sh_part[0];
+#pragma unroll
+            for (int w = 1; w < BEAM_T / 64; w++) best = sh_part[w] > best ? sh_part[w] : best;
+            if (tid == 0) sh_cand[round] = best;
+            prev = best;
+            __syncthreads();                                         // sh_part is rewritten by the next round
+        }
+    }
+
+    if (tid == 0) {
+        int mv = 0;
+        if (frozen) {
+            for (int j = 0; j < nb; j++) { sh_src[j] = j; sh_tok[j] = pad_id; sh_dead[j] = 0; sh_add[j] = -1; }
+            sh_clear = 1;
+        } else {
+            int n = hyp_n[b], cnt = 0;
+            for (int j = 0; j < nb; j++) { hs[j] = j < n ? hyp_score[row0 + j] : 0.f; sh_add[j] = -1; }
+            const float norm = powf((float)cur_len, length_penalty);
+            for (int rank = 0; rank < 2 * nb && cnt < nb; rank++) {
+                const float s = beam_key_score(sh_cand[rank]);
+                const uint32_t idx = beam_key_index(sh_cand[rank]);
+                const int j = (int)(idx / (uint32_t)V), v = (int)(idx - (uint32_t)j * (uint32_t)V);
+                if (j >= nb) continue;                               // (no candidate was left for this round: not reached for V >= 2)
+                if (v == eos_id) {
+                    if (rank >= nb) continue;
+                    const float sc = s / norm;                       // _BeamHyps.add
+                    int slot = -1;
+                    if (n < nb) slot = n++;
+                    else {
+                        int worst = 0;
+                        for (int i = 1; i < nb; i++) if (hs[i] < hs[worst]) worst = i;
+                        if (sc > hs[worst]) slot = worst;
+                    }
+                    if (slot >= 0) { hs[slot] = sc; sh_add[slot] = j; }
+                } else {
+                    const bool dead = s == -INFINITY;
+                    sh_src[cnt] = j;
+                    sh_tok[cnt] = dead ? pad_id : v;
+                    sh_dead[cnt] = dead;
+                    sh_score[cnt] = s;                               // (every old score is in the keys by now)
+                    mv |= j != cnt;
+                    cnt++;
+                }
+            }
+            for (; cnt < nb; cnt++) {                                // (not reached: at most nb of 2 * nb candidates are eos)
+                sh_src[cnt] = cnt; sh_tok[cnt] = pad_id; sh_dead[cnt] = 1; sh_score[cnt] = -INFINITY;
+            }
+            bool d = false;                                          // _BeamHyps.is_done
+            if (n >= nb) {
+                if (early_stopping) d = true;
+                else {
+                    float worst = hs[0];
+                    for (int i = 1; i < nb; i++) worst = fminf(worst, hs[i]);
+                    d = worst >= beam_key_score(sh_cand[0]) / norm;
+                }
+            }
+            for (int j = 0; j < nb; j++) {
+                beam_scores[row0 + j] = sh_score[j];
+                if (sh_add[j] >= 0) { hyp_score[row0 + j] = hs[j]; hyp_len[row0 + j] = cur_len; }
+            }
+            hyp_n[b] = n;
+            if (d) {
+                done[b] = 1;
+                atomicAdd(n_done, 1);
+            }
+            sh_clear = d;
+        }
+        for (int j = 0; j < nb; j++) beam_idx[row0 + j] = row0 + sh_src[j];
+        moved[b] = mv;
+        sh_moved = mv;
+    }
+    __syncthreads();
+
+    // the added hypotheses, before ids moves
+    for (int slot = 0; slot < nb; slot++) {
+        const int src = sh_add[slot];
+        if (src < 0) continue;
+        const long long* from = ids + (size_t)(row0 + src) * ld_ids;
+        long long* to = hyp_ids + (size_t)(row0 + slot) * ld_ids;
+        for (int c = tid; c < cur_len; c += BEAM_T) to[c] = from[c];
+    }
+    __syncthreads();
+
+    if (sh_moved) {
+        int src[BEAM_MAX];
+#pragma unroll
+        for (int j = 0; j < BEAM_MAX; j++) src[j] = j < nb ? sh_src[j] : j;
+        for (int c = tid; c < cur_len; c += BEAM_T) {
+            long long v[BEAM_MAX];
+#pragma unroll
+            for (int j = 0; j < BEAM_MAX; j++)
+                if (j < nb && src[j] != j) v[j] = ids[(size_t)(row0 + src[j]) * ld_ids + c];
+#pragma unroll
+            for (int j = 0; j < BEAM_MAX; j++)
+                if (j < nb && src[j] != j) ids[(size_t)(row0 + j) * ld_ids + c] = v[j];
+        }
+        if (words && tid < n_words) {
+            int* w = words + (size_t)tid * word_stride + row0;
+            int v[BEAM_MAX];
+#pragma unroll
+            for (int j = 0; j < BEAM_MAX; j++)
+                if (j < nb && src[j] != j) v[j] = w[src[j]];
+#pragma unroll
+            for (int j = 0; j < BEAM_MAX; j++)
+                if (j < nb && src[j] != j) w[j] = v[j];
+        }
+    }
+    if (tid < nb) ids[(size_t)(row0 + tid) * ld_ids + cur_len] = sh_tok[tid];
+    if (words && tid == 0) {                                         // word 0 = unfinished; thread 0 moved it above
+        for (int j = 0; j < nb; j++)
+            if (sh_dead[j] || sh_clear) words[row0 + j] = 0;
+    }
+}
+
+// One (rows, row_bytes) buffer, or each of a table of them, follows beam_idx in place, item by item.  grid (column blocks, items,
+// buffers); a thread owns one 16-byte column of its item: it reads the sources of the rows that change into registers, then writes
+// them.  An item with moved == 0 returns before touching memory; an index outside its item counts as "stays".
+__global__ __launch_bounds__(BEAM_T) void beam_reorder_kernel(char* buf, char* const* table, long long row_bytes, int nb,
+                                                              const int* beam_idx, const int* moved) {
+    const int b = blockIdx.y, row0 = b * nb;
+    if (moved[b] == 0) return;
+    const long long c = (long long)blockIdx.x * BEAM_T + threadIdx.x;
+    if (c >= (row_bytes >> 4)) return;
+    char* base = (table ? table[blockIdx.z] : buf) + c * 16;
+    int src[BEAM_MAX];
+#pragma unroll
+    for (int j = 0; j < BEAM_MAX; j++) {
+        src[j] = j;
+        if (j < nb) {
+            const int s = beam_idx[row0 + j] - row0;
+            if (s >= 0 && s < nb) src[j] = s;
+        }
+    }
+    u32x4 v[BEAM_MAX];
+#pragma unroll
+    for (int j = 0; j < BEAM_MAX; j++)
+        if (src[j] != j) v[j] = *reinterpret_cast<const u32x4*>(base + (long long)(row0 + src[j]) * row_bytes);
+#pragma unroll
+    for (int j = 0; j < BEAM_MAX; j++)
+        if (src[j] != j) *reinterpret_cast<u32x4*>(base + (long long)(row0 + j) * row_bytes) = v[j];
+}
+
+}  // namespace
+
+extern "C" int mxl_beam_step(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs, int nb,
+                             int V, int eos_id, int pad_id, float length_penalty, int early_stopping, void* hyp_ids, int* hyp_len,
+                             float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved, int* words, int n_words,
+                             int word_stride, void* stream) {
+    MXL_CHECK_ARG(logp && beam_scores && ids && t_dev && beam_idx && moved);
+    MXL_CHECK_ARG(hyp_ids && hyp_len && hyp_score && hyp_n && done && n_done);
+    MXL_CHECK_ARG(Bs > 0 && nb >= 1 && nb <= BEAM_MAX && V >= 2 && ldl >= V && ld_ids >= 2);
+    MXL_CHECK_ARG((long long)nb * V < (1LL << 31) && (long long)Bs * nb < (1LL << 31));
+    MXL_CHECK_ARG((words == nullptr) == (n_words == 0));
+    MXL_CHECK_ARG(!words || (n_words >= 1 && n_words <= BEAM_T && (long long)word_stride >= (long long)Bs * nb));
+    hipLaunchKernelGGL(beam_step_kernel, dim3(Bs), dim3(BEAM_T), 0, (hipStream_t)stream, logp, ldl, beam_scores, (long long*)ids, ld_ids,
+                       t_dev, nb, V, eos_id, pad_id, length_penalty, early_stopping, (long long*)hyp_ids, hyp_len, hyp_score, hyp_n, done,
+                       n_done, beam_idx, moved, words, n_words, word_stride);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_beam_reorder(void* buf, const void* table, int n_bufs, int Bs, int nb, long long row_bytes, const int* beam_idx,
+                                const int* moved, void* stream) {
+    MXL_CHECK_ARG((buf == nullptr) != (table == nullptr) && beam_idx && moved);
+    MXL_CHECK_ARG(n_bufs >= 1 && n_bufs <= 65535 && (table || n_bufs == 1));
+    MXL_CHECK_ARG(Bs > 0 && Bs <= 65535 && nb >= 1 && nb <= BEAM_MAX);
+    MXL_CHECK_ARG(row_bytes > 0 && (row_bytes % 16) == 0 && ((uintptr_t)buf % 16) == 0);
+    const long long blocks = ((row_bytes >> 4) + BEAM_T - 1) / BEAM_T;
+    MXL_CHECK_ARG(blocks < (1LL << 31));
+    hipLaunchKernelGGL(beam_reorder_kernel, dim3((unsigned)blocks, Bs, n_bufs), dim3(BEAM_T), 0, (hipStream_t)stream, (char*)buf,
+                       (char* const*)table, row_bytes, nb, beam_idx, moved);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}

@@ -607,8 +607,8 @@ class _AlivePoll:
     """live-row counts of one decoder read back without stalling its stream: after each chunk of steps a non-blocking copy of
     `alive` into pinned host memory and an event; `wait(keep)` blocks until at most `keep` such reads are outstanding"""
 
-    def __init__(self, alive: torch.Tensor):
-        self.alive = alive
+    def __init__(self, alive: torch.Tensor, target: int = 0):
+        self.alive, self.target = alive, target       # target: the count at which the decoder is finished (beam search: n_done == items)
         self.bufs = [torch.empty(1, dtype=torch.int32, pin_memory=True) for _ in range(3)]
         self.pend, self.i, self.done = deque(), 0, False
 
@@ -624,7 +624,7 @@ class _AlivePoll:
         while len(self.pend) > keep:
             ev, buf = self.pend.popleft()
             ev.synchronize()
-            if int(buf[0]) == 0:
+            if int(buf[0]) == self.target:
                 self.done = True
         return self.done
 
@@ -699,6 +699,41 @@ def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sam
     return out
 
 
+BEAM_MAX = 16            # beams per item of mxl_beam_step / mxl_beam_reorder
+
+
+class BeamStore:
+    """The scorer's state of a beam search on the device, as mxl_beam_step reads and writes it: `scores` (rows,) f32, the running
+    score of every row; the finished hypotheses of every item, `hyp_ids` (Bs, nb, ld) int64 with `hyp_len` and `hyp_score` (Bs, nb),
+    slots 0..hyp_n[b]-1 in use; `hyp_n` and `done` (Bs,) and `n_done` (1,), the number of done items, which the host reads a chunk
+    late; and what a step hands to the ring reorder, `beam_idx` (rows,) and `moved` (Bs,).  The int32 words share one buffer."""
+
+    def __init__(self, Bs: int, nb: int, ld_ids: int, dev):
+        self.Bs, self.nb = Bs, nb
+        rows = Bs * nb
+        self.scores = torch.zeros(rows, device=dev, dtype=torch.float32)
+        self.hyp_ids = torch.zeros(Bs, nb, ld_ids, device=dev, dtype=torch.int64)
+        self.hyp_score = torch.zeros(Bs, nb, device=dev, dtype=torch.float32)
+        self.ints = torch.zeros(rows + 2 * Bs + 1, device=dev, dtype=torch.int32)
+        self.hyp_len = self.ints[:rows].view(Bs, nb)
+        self.hyp_n, self.done, self.n_done = self.ints[rows:rows + Bs], self.ints[rows + Bs:rows + 2 * Bs], self.ints[rows + 2 * Bs:]
+        self.beam_idx = torch.zeros(rows, device=dev, dtype=torch.int32)
+        self.moved = torch.zeros(Bs, device=dev, dtype=torch.int32)
+
+    def start(self):
+        """an empty store; the first beam of every item starts at score 0, the others at -1e9 (HF beam_search)"""
+        self.ints.zero_()
+        self.scores.fill_(-1e9)
+        self.scores.view(self.Bs, self.nb)[:, 0] = 0
+
+    def snapshot(self):
+        return self.scores.clone(), self.hyp_ids.clone(), self.hyp_score.clone(), self.ints.clone()
+
+    def restore(self, saved):
+        for t, v in zip((self.scores, self.hyp_ids, self.hyp_score, self.ints), saved):
+            t.copy_(v)
+
+
 class XLDecoder:
     def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77):
         self.eng = engine
@@ -740,6 +775,7 @@ class XLDecoder:
         # with a one-shot forward); written on the device by position, so it also works under hipGraph replay
         self.trace = None
         self.steps_run = 0                              # decode steps issued by the last generate() (early exit: fewer)
+        self.beam = None                                # BeamStore of a beam search on the device (beam_begin)
         # the rules of the current generation (eos, grammar, bar budget, bar count) and their per-row words, which the sampler
         # launch reads and moves; the words are readable here under their names
         self.rules = RowRules(batch, dev)
@@ -920,6 +956,76 @@ class XLDecoder:
         """the token at position cur_len - 1 through the model -> log-probs of position cur_len"""
         self.t_dev.fill_(cur_len - 1)
         self._forward_token()
+
+    # ---------------------------------------------------------------- beam search on the device (beam_search_device below)
+    def beam_begin(self, prompt: torch.Tensor, max_length: int, nb: int, eos: int, pad: int, length_penalty: float,
+                   early_stopping: bool, use_graph: bool = True, grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None,
+                   keys: Optional[torch.Tensor] = None) -> int:
+        """prompt pass (one row per beam, the rules started as `prefill` starts them, with the stop group (eos, pad, 0) always on:
+        its `unfinished` word is how mxl_beam_step retires dead rows and done items) + the scorer's state + (use_graph) capture of
+        one beam step; returns the number of `beam_replay_once()` calls before the last selection (`beam_select`).  The snapshot
+        that the warm-up and the capture consume is `begin`'s, joined by the hypothesis store and the running scores."""
+        if max_length > self.Tmax:
+            raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
+        if nb < 2 or nb > BEAM_MAX or self.B % nb:
+            raise MusicXLError(f'beam search on the device takes 2..{BEAM_MAX} beams and one decoder row per beam')
+        self.prefill(prompt, None, None, (int(eos), int(pad), 0), grammar, n_bars, in_key, keys)
+        if self.beam is None or self.beam.nb != nb:
+            self.beam = BeamStore(self.B // nb, nb, self.ids.shape[1], self.eng.dev)
+            self.ring_table = ops.beam_table(self.kc + self.vc)
+        self.beam.start()
+        self._beam_args = (int(nb), int(eos), int(pad), float(length_penalty), bool(early_stopping))
+        self._use_graph = use_graph
+        steps = max_length - prompt.shape[1] - 1
+        if steps > 0 and use_graph:
+            key = ('beam',) + self._beam_args + (None if self.trace is None else self.trace.data_ptr(),) + self.rules.graph_key(self.eng.dev)
+            if self.graph is None or self._graph_key != key:
+                state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(), [k.clone() for k in self.kc + self.vc],
+                         self.rules.snapshot(), self.beam.snapshot(), self.logp.clone())
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    self.beam_step()
+                torch.cuda.current_stream().wait_stream(s)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self.beam_step()
+                self._graph_key = key
+                self.t_dev.copy_(state[0]); self.rng.copy_(state[1]); self.ids.copy_(state[2])
+                for a, b in zip(self.kc + self.vc, state[3]):
+                    a.copy_(b)
+                self.rules.restore(state[4])
+                self.beam.restore(state[5])
+                self.logp.copy_(state[6])             # (the step starts from the log-probabilities the last one left)
+        return max(steps, 0)
+
+    def beam_select(self):
+        """rules mask -> mxl_beam_step: the beams of every item chosen, finished hypotheses stored, ids and the rule words
+        reordered, the chosen tokens at column t + 1"""
+        V, st = self.eng.cfg.vocab_size, self.beam
+        nb, eos, pad, lp, early = self._beam_args
+        rules = ops.rules_in_force(**self.rules.kwargs())
+        ops.rules_mask(self.logp, V, self.t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
+        ops.beam_step(self.logp, V, st.scores, self.ids, self.t_dev, nb, eos, pad, lp, early, st.hyp_ids, st.hyp_len, st.hyp_score,
+                      st.hyp_n, st.done, st.n_done, st.beam_idx, st.moved, words=self.rules.buf, n_words=len(RowRules.WORDS))
+        return rules
+
+    def beam_step(self):
+        """one whole beam step, no host read: beam_select, the K/V rings of every layer follow their beams (one launch over a
+        table of the rings), the position moves on, the rule words move along the chosen tokens (rows that mxl_beam_step retired
+        keep theirs), and the chosen tokens go through the model"""
+        rules = self.beam_select()
+        ops.beam_reorder(self.kc + self.vc, self._beam_args[0], self.beam.beam_idx, self.beam.moved, table=self.ring_table)
+        ops.decode_advance(self.t_dev, self.rng)
+        if rules['grammar'] is not None or rules['in_key'] is not None:
+            ops.rules_advance(self.ids, self.t_dev, **rules)
+        self._forward_token()
+
+    def beam_replay_once(self):
+        if self._use_graph:
+            self.graph.replay()
+        else:
+            self.beam_step()
 
     def _trace(self):
         if self.trace is not None:
@@ -1144,7 +1250,8 @@ def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, 
                 top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: float = 1.0,
                 typical_p: Optional[float] = None, early_stopping: bool = True, length_penalty: float = 1.0,
                 num_return_sequences: int = 1, eos_token_id: int = 0, pad_token_id: Optional[int] = None,
-                renormalize_logits: bool = True, generator: Optional[torch.Generator] = None, return_scores: bool = False):
+                renormalize_logits: bool = True, generator: Optional[torch.Generator] = None, return_scores: bool = False,
+                allowed=None):
     """HF 4.25.1 `beam_search` (do_sample=False) / `beam_sample` (do_sample=True) with `BeamSearchScorer.process / finalize`,
     as `model.generate(num_beams=...)` reaches them from musicnlp/trainer/eval.py:302-333.  `dec` is an XLDecoder or an
     rf_generate.RFDecoder (anything with beam_prefill / beam_logp / beam_reorder / beam_advance and `ids`) with one row per beam:
@@ -1152,7 +1259,9 @@ def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, 
     log-probabilities of every beam's next token (the same kernels as `step`), the 2 * num_beams best (or sampled) continuations
     per item are taken on the device, the scorer's walk over them runs on the host (it is a data-dependent loop over a handful
     of scalars, as in HF), and the K/V rings and the id history follow their beams (HF `_reorder_cache`).
-    Returns (B * num_return_sequences, L) ids, padded with pad_token_id (= eos when the config has none, as HF does)."""
+    Returns (B * num_return_sequences, L) ids, padded with pad_token_id (= eos when the config has none, as HF does).
+    allowed: None, or a callable (ids[:, :cur_len]) -> (rows, V) bool; a token it bars has its log-probability set to -inf before
+    the running scores are added, as a logits processor would -- the host reference of the rules under beam_search_device."""
     e, c = dec.eng, dec.eng.cfg
     dev, V = e.dev, c.vocab_size
     nb = num_beams
@@ -1176,7 +1285,10 @@ def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, 
     cur_len = Tp
     ident = torch.arange(rows, device=dev)
     while True:
-        sc = dec.beam_logp() + beam_scores[:, None]
+        sc = dec.beam_logp()
+        if allowed is not None:
+            sc = sc.masked_fill(~torch.as_tensor(allowed(dec.ids[:, :cur_len])).to(sc.device, torch.bool), float('-inf'))
+        sc = sc + beam_scores[:, None]
         if do_sample:              # HF beam_sample: warp log p + beam score, renormalise, draw 2 * num_beams, sort
             sc = _warp(sc, top_k, top_p, typical_p, temperature, min_keep=2, renormalize=renormalize_logits)
             flat = sc.view(Bs, nb * V)
@@ -1202,6 +1314,64 @@ def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, 
             break
         dec.beam_advance(cur_len)
     return _beam_finalize(hyps, nb, keep, dec.ids, cur_len, beam_scores, max_length, eos_token_id, pad, return_scores)
+
+
+def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, early_stopping: bool = True,
+                       length_penalty: float = 1.0, num_return_sequences: int = 1, eos_token_id: int = 0,
+                       pad_token_id: Optional[int] = None, use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None,
+                       n_bars=None, in_key=None, key=None, return_scores: bool = False):
+    """`beam_search` (do_sample=False) with the scorer on the device: per step the rules mask, mxl_beam_step (select, walk, store,
+    reorder ids and the rule words), mxl_beam_reorder over the K/V rings, the position advance, the rules advance and the model --
+    no host read, captured once under use_graph (XLDecoder.beam_begin / beam_step).  The steps are replayed in chunks of
+    `stop_chunk`; the number of done items is read back one chunk late (as run_until_finished reads the live rows) and the loop
+    ends when every item is done or at max_length.  Then the store and the running scores are read once and `_beam_finalize`
+    builds the output, as beam_search does.  dec: an XLDecoder with prompt rows x num_beams rows, num_beams <= 16.
+    grammar / n_bars / in_key / key: the rules of `XLDecoder.generate`, one value per prompt where they are per row (each prompt's
+    is shared by its beams); a barred token is -inf before the running scores are added, the rules' words follow the beams, and a
+    row that can only continue from a barred token is dead: it emits pad at score -inf and never returns.  An item that ends with
+    fewer than num_return_sequences hypotheses of finite score raises MusicXLError."""
+    V = dec.eng.cfg.vocab_size
+    nb = int(num_beams)
+    pad = eos_token_id if pad_token_id is None else pad_token_id
+    B0, Tp = prompt.shape
+    keep = int(num_return_sequences)
+    if keep > nb:
+        raise MusicXLError('num_return_sequences has to be smaller or equal to num_beams')
+    rows = B0 * nb
+    if dec.B != rows or max_length > dec.Tmax:
+        raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, beam search needs {rows} x {max_length}')
+    stop = (int(eos_token_id), int(pad), 0)
+    n = dec.beam_begin(prompt.repeat_interleave(nb, 0).to(dec.eng.dev), max_length, nb, eos_token_id, pad, length_penalty,
+                       early_stopping, use_graph, grammar, bar_count_config(n_bars, B0, grammar, stop, nb), in_key,
+                       key_config(in_key, key, B0, V, nb))
+    st = dec.beam
+    poll, issued, chunk = _AlivePoll(st.n_done, target=B0), 0, max(1, int(stop_chunk))
+    while issued < n and not poll.wait(1):
+        k = min(chunk, n - issued)
+        for _ in range(k):
+            dec.beam_replay_once()
+        poll.mark()
+        issued += k
+    dec.beam_select()                   # the last selection needs no forward after it; items that are done ignore it
+    dec.steps_run = issued
+    cur_len = Tp + issued + 1
+    ints, hyp_score, final = st.ints.cpu(), st.hyp_score.cpu().tolist(), st.scores.cpu()
+    hyp_len = ints[:rows].view(B0, nb).tolist()
+    hyp_n, done = ints[rows:rows + B0].tolist(), ints[rows + B0:rows + 2 * B0].tolist()
+    hyps = []
+    for b in range(B0):
+        h = _BeamHyps(nb, length_penalty, early_stopping)
+        h.beams = [(hyp_score[b][j], st.hyp_ids[b, j, :hyp_len[b][j]]) for j in range(hyp_n[b])]
+        h.worst_score = min([sc for sc, _ in h.beams], default=1e9)
+        h.done = bool(done[b])
+        finite = sum(math.isfinite(sc) for sc, _ in h.beams)
+        if not h.done:
+            finite += sum(math.isfinite(x) for x in final[b * nb:(b + 1) * nb].tolist())
+        if finite < keep:
+            raise MusicXLError(f'beam search found {finite} hypotheses for item {b}, fewer than num_return_sequences = {keep}: the '
+                               'rules bar every continuation of its other beams')
+        hyps.append(h)
+    return _beam_finalize(hyps, nb, keep, dec.ids, cur_len, final, max_length, eos_token_id, pad, return_scores)
 
 
 def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 4, num_beam_groups: int = 2,

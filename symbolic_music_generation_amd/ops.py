@@ -367,6 +367,67 @@ def budget_scan(ids, Tp, grammar, gbar, grem, first_bad):
                                 bud.need_free, bud.need_full, _p(gbar), _p(grem), _p(first_bad), _stream()), 'mxl_budget_scan')
 
 
+def beam_step(logp, V, beam_scores, ids, t_dev, nb, eos_id, pad_id, length_penalty, early_stopping, hyp_ids, hyp_len, hyp_score, hyp_n,
+              done, n_done, beam_idx, moved, words=None, n_words=0):
+    """one step of beam search for every item (the nb rows of one prompt), one launch (mxl_beam_step): the 2 * nb best candidates of
+    logp (rows, >= V) f32 + beam_scores (rows,) f32 in (score descending, flat index ascending) order, the scorer's walk over them --
+    finished hypotheses into the store hyp_ids (Bs, nb, ld) int64 / hyp_len / hyp_score (Bs, nb) / hyp_n / done (Bs,) / n_done (1,) --
+    and ids (rows, ld) int64 reordered in place along beam_idx (rows,) int32 with the chosen tokens at column t + 1; moved (Bs,) int32.
+    words: the packed per-row int32 rule words (RowRules.buf), n_words words of `rows` entries each, which follow beam_idx."""
+    rows = ids.shape[0]
+    _req(logp, torch.float32, 'beam_step logp'); _req(beam_scores, torch.float32, 'beam_step beam_scores')
+    _req(hyp_score, torch.float32, 'beam_step hyp_score')
+    for t, name in ((hyp_len, 'hyp_len'), (hyp_n, 'hyp_n'), (done, 'done'), (n_done, 'n_done'), (beam_idx, 'beam_idx'), (moved, 'moved')):
+        _req(t, torch.int32, f'beam_step {name}')
+    if nb < 1 or rows % nb or ids.dtype != torch.int64 or hyp_ids.dtype != torch.int64 or ids.stride(1) != 1 or logp.stride(1) != 1:
+        raise MusicXLError('beam_step: ids and hyp_ids must be int64 rows of nb per item, logp with unit column stride')
+    Bs = rows // nb
+    if logp.shape[0] != rows or logp.shape[1] < V or beam_scores.numel() != rows or beam_idx.numel() != rows:
+        raise MusicXLError(f'beam_step: logp must be ({rows}, >= {V}), beam_scores and beam_idx ({rows},)')
+    if (tuple(hyp_ids.shape) != (Bs, nb, ids.shape[1]) or not hyp_ids.is_contiguous() or ids.stride(0) != ids.shape[1]
+            or any(t.numel() != rows or not t.is_contiguous() for t in (hyp_len, hyp_score))
+            or any(t.numel() != Bs or not t.is_contiguous() for t in (hyp_n, done, moved)) or n_done.numel() != 1):
+        raise MusicXLError(f'beam_step: the store must be hyp_ids ({Bs}, {nb}, {ids.shape[1]}), hyp_len / hyp_score ({Bs}, {nb}), '
+                           f'hyp_n / done / moved ({Bs},), n_done (1,), all contiguous, over contiguous ids')
+    if not beam_scores.is_contiguous() or not beam_idx.is_contiguous():
+        raise MusicXLError('beam_step: beam_scores and beam_idx must be contiguous')
+    if words is not None:
+        _req(words, torch.int32, 'beam_step words')
+        if n_words < 1 or words.numel() < n_words * rows or not words.is_contiguous():
+            raise MusicXLError(f'beam_step: words must hold n_words x {rows} contiguous int32')
+    check(lib().mxl_beam_step(_p(logp), logp.stride(0), _p(beam_scores), _p(ids), ids.stride(0), _p(t_dev), Bs, int(nb), int(V),
+                              int(eos_id), int(pad_id), float(length_penalty), int(bool(early_stopping)), _p(hyp_ids), _p(hyp_len),
+                              _p(hyp_score), _p(hyp_n), _p(done), _p(n_done), _p(beam_idx), _p(moved), _p(words),
+                              int(n_words) if words is not None else 0, rows, _stream()), 'mxl_beam_step')
+
+
+def beam_reorder(bufs, nb, beam_idx, moved, table=None):
+    """rows follow their beams in place (mxl_beam_reorder): bufs = one contiguous (rows, ...) tensor, or a list of them of one shape
+    with `table`, their addresses as a device int64 tensor (beam_table) -- one launch for all.  Items with moved[b] == 0 are skipped
+    whole, rows with beam_idx[r] == r are not written."""
+    one = isinstance(bufs, torch.Tensor)
+    first = bufs if one else bufs[0]
+    rows = first.shape[0]
+    row_bytes = first[0].numel() * first.element_size()
+    _req(beam_idx, torch.int32, 'beam_reorder beam_idx'); _req(moved, torch.int32, 'beam_reorder moved')
+    if nb < 1 or rows % nb or beam_idx.numel() != rows or moved.numel() != rows // nb:
+        raise MusicXLError(f'beam_reorder: {rows} rows need nb rows per item, beam_idx ({rows},) and moved (rows / nb,)')
+    for t in ([bufs] if one else bufs):
+        if not t.is_cuda or not t.is_contiguous() or t.shape != first.shape or t.dtype != first.dtype or t.data_ptr() % 16:
+            raise MusicXLError('beam_reorder: the buffers must be contiguous device tensors of one shape, 16-byte aligned')
+    if row_bytes % 16:
+        raise MusicXLError(f'beam_reorder: rows of {row_bytes} bytes are no multiple of 16')
+    if not one and (table is None or table.dtype != torch.int64 or table.numel() != len(bufs) or not table.is_cuda):
+        raise MusicXLError('beam_reorder: a list of buffers needs its table (beam_table)')
+    check(lib().mxl_beam_reorder(_p(bufs) if one else None, None if one else _p(table), 1 if one else len(bufs), rows // nb, int(nb),
+                                 row_bytes, _p(beam_idx), _p(moved), _stream()), 'mxl_beam_reorder')
+
+
+def beam_table(bufs) -> torch.Tensor:
+    """the addresses of `bufs` as a device int64 tensor, the pointer table of beam_reorder"""
+    return torch.tensor([t.data_ptr() for t in bufs], dtype=torch.int64, device=bufs[0].device)
+
+
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, relu=False, out=None,
            out_f32=False, drop_p=0.0, seed=0, site=0) -> torch.Tensor:
     """y = x @ w.T (+bias)(relu)(dropout); x (N, K) bf16, w (O, K) bf16."""

@@ -225,7 +225,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         processor would.  It combines with `num_return_sequences`, padded prompts, `eos_token_id` / `min_length` /
         `max_new_tokens`; the prompts must obey the grammar themselves (MusicXLError otherwise).  That constraint is syntactic;
         `tokenizer.grammar(bar_budget=True)` adds the bar budget, under which every channel of every generated bar is also exactly
-        as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Beam, group-beam and contrastive search take no grammar.
+        as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Plain beam search takes it too (below); beam-sample, group-beam and contrastive search take no grammar.
 
         `n_bars` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): length in bars.  An int, or a
         sequence or tensor of one int per prompt (repeated per prompt under `num_return_sequences`); a negative entry leaves that
@@ -244,8 +244,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
         sequence of one per prompt with None / -1 = unconstrained (repeated per prompt under `num_return_sequences`), overrides the
         prompts' keys.  The prompt only supplies the key: its own pitches are not judged.  A generated `Key_*` token sets the row's
         key from then on.  The key lives on the device beside the other rules' words and the mask sits in the same sampler launch,
-        in the same place.  It needs no `grammar` and combines with everything greedy decoding and sampling take.  Beam,
-        group-beam and contrastive search take no `in_key`.
+        in the same place.  It needs no `grammar` and combines with everything greedy decoding and sampling take, and with
+        plain beam search; beam-sample, group-beam and contrastive search take no `in_key`.
 
         `melody` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): here is a melody, write the bass
         under it.  A guide is the concatenation of the `<bar> <melody> ... <bass>` spans of its bars, each bar up to and including
@@ -259,9 +259,16 @@ class MyTransfoXLLMHeadModel(EngineModule):
         split into such bars, the grammar must accept them, and under a bar budget a guided melody must fill its bar exactly in a
         row whose time signature is known (MusicXLError naming row, guide index and token).  Guide tokens are not judged by
         `in_key`: real melodies hold off-key notes, as prompts do.  It combines with everything `grammar` combines with;
-        `generate.check_melody` verifies an output.  Beam, group-beam and contrastive search take no `melody`."""
-        from .generate import (XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, check_grammar_args, contrastive_search,
-                               key_config, left_pad_counts, melody_config, resolve_max_length, stop_config)
+        `generate.check_melody` verifies an output.  Beam, group-beam and contrastive search take no `melody`.
+
+        Plain beam search (`num_beams` 2..16, `num_beam_groups=1`, `do_sample=False`) runs with its scorer on the device
+        (`generate.beam_search_device`: mxl_beam_step / mxl_beam_reorder inside the captured step) and takes `grammar`, `n_bars` and
+        `in_key` / `key` with the checks above, given an explicit `eos_token_id=` (without one they stay refused, as before); per-prompt values are shared by the prompt's beams, a barred token is -inf before
+        the running scores are added, and a prompt left with fewer than `num_return_sequences` hypotheses raises MusicXLError.
+        `MXL_BEAM_HOST=1` keeps the host scorer (`generate.beam_search`), which takes no rules."""
+        from .generate import (BEAM_MAX, XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, beam_search_device,
+                               check_grammar_args, contrastive_search, key_config, left_pad_counts, melody_config, resolve_max_length,
+                               stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -281,21 +288,31 @@ class MyTransfoXLLMHeadModel(EngineModule):
         max_length = resolve_max_length(max_length, max_new_tokens, input_ids.shape[1], self.config.max_length_)
         check_grammar_args(grammar, self.config.vocab_size, stop)
         contrastive = penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and not do_sample and num_beams == 1
+        # plain beam search runs with its scorer on the device and takes the rules (generate.beam_search_device); MXL_BEAM_HOST=1
+        # keeps the host scorer (generate.beam_search), which takes none
+        device_beam = (num_beams > 1 and num_beam_groups == 1 and not do_sample and not contrastive and num_beams <= BEAM_MAX
+                       and os.environ.get('MXL_BEAM_HOST') != '1')
+        # the rules under beam search need an explicit eos_token_id=, as n_bars and melody do everywhere: a hypothesis ends only by
+        # emitting eos, the config's eos (0 = [OMIT]) is no end token of the grammar, and the stop group that the explicit eos turns on
+        # is how the device scorer retires rows.  Without one, and for n_bars without the grammar that counts the bars, a beam call
+        # keeps the refusal it has always had
+        no_rules = contrastive or num_beam_groups != 1 or (num_beams > 1 and not (device_beam and stop is not None))
         if n_pad is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('padded prompts (attention_mask with zeros) are supported for greedy decoding and sampling only, not '
                                'for beam, group-beam or contrastive search')
         if melody is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('melody= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
-        if grammar is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
+        if grammar is not None and no_rules:
             raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
-        if n_bars is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
+        if n_bars is not None and (no_rules or (num_beams > 1 and grammar is None)):
             raise MusicXLError('n_bars= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
-        if (in_key is not None or key is not None) and (contrastive or num_beam_groups != 1 or num_beams > 1):
+        if (in_key is not None or key is not None) and no_rules:
             raise MusicXLError('in_key= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
+        n_bars_arg = n_bars                                 # (the device beam search repeats it per beam, not per returned sequence)
         plan = melody_config(melody, input_ids.shape[0], grammar, stop, n_bars, num_return_sequences)
         n_bars = bar_count_config(n_bars, input_ids.shape[0], grammar, stop, num_return_sequences) if plan is None else None
         keys = key_config(in_key, key, input_ids.shape[0], self.config.vocab_size, num_return_sequences)
@@ -303,6 +320,11 @@ class MyTransfoXLLMHeadModel(EngineModule):
             dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
                                       eos_token_id=eos_b, pad_token_id=pad_b)
+        if device_beam:
+            dec = XLDecoder(self.engine, input_ids.shape[0] * num_beams, max_length, seed=seed)
+            return beam_search_device(dec, input_ids, max_length, num_beams, bool(early_stopping), length_penalty,
+                                      num_return_sequences, eos_b, pad_b, use_graph=use_graph, grammar=grammar, n_bars=n_bars_arg,
+                                      in_key=in_key, key=key)
         if num_beam_groups != 1 or num_beams > 1:
             return beam_generate(lambda rows: XLDecoder(self.engine, rows, max_length, seed=seed), input_ids, max_length,
                                  num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample,

@@ -1,0 +1,203 @@
+"""Beam search with the scorer on the device, end to end on TransfoXL: generate.beam_search_device against the host scorer
+generate.beam_search on a second decoder, the public `generate(num_beams=)` on either path, and the rules under beam search against
+the host scorer with a mask built from grammar.py's host walkers."""
+import numpy as np
+import pytest
+import torch
+
+from symbolic_music_generation_amd.generate import (XLDecoder, bars_after_prompt, beam_search, beam_search_device, check_bar_lengths,
+                                                    check_grammar, check_in_key)
+
+pytestmark = pytest.mark.gpu
+
+# chosen on the CPU with generate.beam_search over the oracle model (tests/test_beam_cpu.py's decoder): the model of seed 13 repeats
+# one token per prompt, 571 after prompt 0 and 1121 after prompt 1 of generator seed 21.  With eos = 1121 prompt 1 finishes a
+# hypothesis at once and fills its store within a few steps while prompt 0 stays open to max_length; eos = -1 is never emitted.
+SEED, PROMPT_SEED, TP, L = 13, 21, 12, 40
+EOS_EMITTED, EOS_NEVER = 1121, -1
+
+
+@pytest.fixture(scope='module')
+def plain(dev):
+    from tests.test_xl_model_gpu import _pair
+    _, m = _pair(dev, n_layer=2, mem_len=64, max_length=64, seed=SEED)
+    prompt = torch.randint(4, 1190, (2, TP), generator=torch.Generator().manual_seed(PROMPT_SEED)).to(dev)
+    return m.eval(), prompt
+
+
+@pytest.mark.parametrize('early', [True, False])
+@pytest.mark.parametrize('nb', [2, 3, 4])
+def test_device_scorer_equals_host_scorer(plain, nb, early):
+    m, prompt = plain
+    finished = 0
+    for eos in (EOS_EMITTED, EOS_NEVER):
+        for keep in (1, 2):
+            kw = dict(num_beams=nb, early_stopping=early, num_return_sequences=keep, eos_token_id=eos, pad_token_id=0, return_scores=True)
+            want, w_sc = beam_search(XLDecoder(m.engine, 2 * nb, L), prompt, L, **kw)
+            dec = XLDecoder(m.engine, 2 * nb, L)
+            got, g_sc = beam_search_device(dec, prompt, L, use_graph=True, stop_chunk=5, **kw)
+            assert got.shape == want.shape and torch.equal(got, want), (eos, keep)
+            assert (g_sc - w_sc).abs().max().item() < 1e-4, (eos, keep, g_sc.tolist(), w_sc.tolist())
+            eager, e_sc = beam_search_device(XLDecoder(m.engine, 2 * nb, L), prompt, L, use_graph=False, **kw)
+            assert torch.equal(eager, got) and torch.equal(e_sc, g_sc), (eos, keep)
+            again, _ = beam_search_device(dec, prompt, L, use_graph=True, **kw)          # the captured step, replayed from a new start
+            assert torch.equal(again, got)
+            finished += int((got[:, TP:] == eos).any())
+            if eos == EOS_NEVER:
+                assert dec.steps_run == L - TP - 1 and int(dec.beam.n_done) == 0
+    assert finished == 2                                                   # the emitted eos ended hypotheses, the other none
+
+
+def test_generate_takes_either_path(plain, monkeypatch):
+    m, prompt = plain
+    kw = dict(input_ids=prompt, max_length=L, num_beams=3, num_return_sequences=2, early_stopping=True, eos_token_id=EOS_EMITTED,
+              pad_token_id=0)
+    dev_ids = m.generate(**kw)
+    monkeypatch.setenv('MXL_BEAM_HOST', '1')
+    host_ids = m.generate(**kw)
+    assert dev_ids.shape == (4, host_ids.shape[1]) and torch.equal(dev_ids, host_ids)
+    monkeypatch.delenv('MXL_BEAM_HOST')
+    assert torch.equal(m.generate(**kw, use_graph=False), dev_ids)
+
+
+# ---------------------------------------------------------------------------------------------------------------- rules
+def host_allowed(grammar, Tp, n_bars=None, rule=None, keys=None):
+    """the `allowed` callable of generate.beam_search for these rules, from the host walkers: every row of ids[:, :cur_len] is walked
+    from its start by TokenGrammar.walk, walk_budget, walk_bars (the generated part, from n_bars) and KeyRule.walk, and the words
+    they end in admit what mxl_rules_mask admits.  A row that the walk itself rejects (the kept -inf continuation of a dead row) is
+    barred whole: it is dead on either side."""
+    V = (grammar.vocab_size if grammar is not None else rule.vocab_size)
+
+    def allowed(ids):
+        out = np.ones((ids.shape[0], V), dtype=bool)
+        for r, row in enumerate(ids.tolist()):
+            if grammar is not None:
+                cls = grammar.cls.astype(np.int64)
+                s, bad = grammar.walk(row)
+                if bad >= 0:
+                    out[r] = False
+                    continue
+                out[r] &= ((int(grammar.allow[s]) >> cls) & 1) == 1
+                bud = grammar.budget
+                if bud is not None:
+                    bar, rem, bad = grammar.walk_budget(row)
+                    if bad >= 0:
+                        out[r] = False
+                        continue
+                    if bar > 0:
+                        out[r] &= bud.slots.astype(np.int64) <= rem
+                        deny = bud.need_free if rem <= 0 else bud.need_full
+                        out[r] &= ((deny >> cls) & 1) == 0
+                if n_bars is not None:
+                    left, bad = grammar.walk_bars(row[Tp:], n_bars)
+                    if bad >= 0:
+                        out[r] = False
+                        continue
+                    cnt = grammar.bar_count
+                    deny = cnt.end if left > 0 else (cnt.count if left == 0 else 0)
+                    out[r] &= ((deny >> cls) & 1) == 0
+            if rule is not None:
+                key, _ = rule.walk(row, -1 if keys is None else keys[r], len(row))
+                out[r] &= rule.allowed(key)
+        return torch.from_numpy(out)
+    return allowed
+
+
+def _rules_case(dev, seed, budget, n_bars, in_key, nb=3, keep=2):
+    from tests.test_key_rule_gpu import BAR_TOKENS, EOS, FULL_BAR, PAD, RULE, TOK, _model, _prompts
+    m = _model(dev, seed, closing_bias=4.0)
+    ids, _ = _prompts(3, dev, FULL_BAR, keyless=False)
+    Tp = ids.shape[1]
+    W = Tp + (2 * BAR_TOKENS + 1 if n_bars is not None else 40)
+    g = TOK.grammar(bar_budget=budget)
+    rule = RULE if in_key else None
+    kw = dict(num_beams=nb, num_return_sequences=keep, early_stopping=True, eos_token_id=EOS, pad_token_id=PAD)
+    got = m.generate(input_ids=ids, max_length=W, grammar=g, n_bars=n_bars, in_key=rule, **kw)
+    dec = XLDecoder(m.engine, ids.shape[0] * nb, W)
+    want = beam_search(dec, ids, W, allowed=host_allowed(g, Tp, n_bars, rule), **kw)
+    return got, want, g, rule, ids, keep, EOS
+
+
+def _assert_clean(got, ids, keep, g, rule, EOS):
+    """every returned row: its prompt, then a continuation that every rule accepts up to and including the eos finalize writes"""
+    Tp = ids.shape[1]
+    assert torch.equal(got[:, :Tp], ids.repeat_interleave(keep, 0))
+    body = [row[:(row.index(EOS) + 1) if EOS in row else len(row)] for row in got.tolist()]
+    for row in body:
+        t = torch.tensor(row)
+        assert check_grammar(t, g).tolist() == [-1]
+        if g.budget is not None:
+            assert check_bar_lengths(t, g).tolist() == [-1]
+        if rule is not None:
+            assert check_in_key(t, rule, prompt_len=Tp).tolist() == [-1]
+    return body
+
+
+@pytest.mark.parametrize('budget', [False, True])
+def test_grammar_under_beam_search_equals_the_masked_host_scorer(dev, budget):
+    """fails without the feature: generate(num_beams=3, grammar=) raises MusicXLError there"""
+    got, want, g, rule, ids, keep, EOS = _rules_case(dev, 601, budget, None, False)
+    assert got.shape == want.shape and torch.equal(got, want)
+    _assert_clean(got, ids, keep, g, rule, EOS)
+
+
+def test_n_bars_and_in_key_under_beam_search(dev):
+    """grammar with its bar budget, n_bars = 2 and the key rule at once: the masked host scorer's output, every row clean under the
+    four checks and two bars long"""
+    got, want, g, rule, ids, keep, EOS = _rules_case(dev, 602, True, 2, True)
+    assert got.shape == want.shape and torch.equal(got, want)
+    body = _assert_clean(got, ids, keep, g, rule, EOS)
+    for row in body:
+        assert row[-1] == EOS and bars_after_prompt(torch.tensor(row), g, prompt_len=ids.shape[1]).tolist() == [2]
+
+
+def test_in_key_alone_under_beam_search(dev):
+    from tests.test_key_rule_gpu import EOS, PAD, RULE, _model, _prompts
+    m = _model(dev, 603)
+    ids, _ = _prompts(3, dev, keyless=False)
+    Tp, W = ids.shape[1], ids.shape[1] + 30
+    kw = dict(num_beams=3, early_stopping=True, eos_token_id=EOS, pad_token_id=PAD)
+    free = m.generate(input_ids=ids, max_length=W, **kw)
+    assert (check_in_key(free, RULE, prompt_len=Tp) >= Tp).all()           # the model leaves the key without the rule
+    got = m.generate(input_ids=ids, max_length=W, in_key=RULE, **kw)
+    want = beam_search(XLDecoder(m.engine, 9, W), ids, W, allowed=host_allowed(None, Tp, None, RULE), **kw)
+    assert torch.equal(got, want) and check_in_key(got, RULE, prompt_len=Tp).tolist() == [-1] * 3
+
+
+# ---------------------------------------------------------------------------------------------------------------- refusals
+def test_refusals_keep_their_messages(dev, monkeypatch):
+    from symbolic_music_generation_amd._lib import MusicXLError
+    from tests.test_key_rule_gpu import EOS, PAD, RULE, TOK, _model, _prompts
+    m = _model(dev, 604)
+    ids, _ = _prompts(2, dev, keyless=False)
+    g = TOK.grammar(bar_budget=True)
+    stop = dict(eos_token_id=EOS, pad_token_id=PAD)
+    rules = (('grammar', dict(grammar=g)), ('n_bars', dict(grammar=g, n_bars=1, **stop)), ('in_key', dict(in_key=RULE)))
+    arms = (dict(num_beams=2, do_sample=True), dict(num_beams=4, num_beam_groups=2), dict(penalty_alpha=0.6, top_k=4),
+            dict(num_beams=17))
+    for name, rk in rules:
+        for arm in arms:
+            with pytest.raises(MusicXLError, match=f'(grammar|{name})= is supported for greedy decoding and sampling only'):
+                m.generate(input_ids=ids, max_length=20, **rk, **arm)
+    monkeypatch.setenv('MXL_BEAM_HOST', '1')
+    for name, rk in rules:
+        with pytest.raises(MusicXLError, match=f'(grammar|{name})= is supported for greedy decoding and sampling only'):
+            m.generate(input_ids=ids, max_length=20, num_beams=2, **{**stop, **rk})
+    monkeypatch.delenv('MXL_BEAM_HOST')
+    with pytest.raises(MusicXLError, match='melody= is supported for greedy decoding and sampling only'):
+        m.generate(input_ids=ids, max_length=40, grammar=g, melody=[1, 2, 3], num_beams=2, **stop)
+    mask = torch.ones_like(ids)
+    mask[0, 0] = 0
+    with pytest.raises(MusicXLError, match='padded prompts'):
+        m.generate(input_ids=ids, attention_mask=mask, max_length=20, num_beams=2)
+    # without an explicit eos_token_id the rules stay refused under plain beam search too, as does n_bars without a grammar
+    for name, rk in (('grammar', dict(grammar=g)), ('in_key', dict(in_key=RULE)), ('in_key', dict(key='CMajor'))):
+        with pytest.raises(MusicXLError, match=f'{name}= is supported for greedy decoding and sampling only'):
+            m.generate(input_ids=ids, max_length=20, num_beams=2, **rk)
+    with pytest.raises(MusicXLError, match='n_bars= is supported for greedy decoding and sampling only'):
+        m.generate(input_ids=ids, max_length=20, n_bars=1, num_beams=2, **stop)
+    # with one, the argument checks of the sampling path hold under beam search
+    with pytest.raises(ValueError, match='needs in_key='):
+        m.generate(input_ids=ids, max_length=20, key='CMajor', num_beams=2, **stop)
+    with pytest.raises(ValueError, match='3 entries for 2 prompts'):
+        m.generate(input_ids=ids, max_length=20, grammar=g, n_bars=[1, 2, 3], num_beams=2, **stop)

@@ -1,0 +1,303 @@
+"""mxl_beam_step and mxl_beam_reorder at kernel level.  The reference of the step is a plain-Python restatement, below, of what
+generate.beam_search / _BeamHyps.walk do for one item on the host -- HF 4.25.1 beam_search + BeamSearchScorer.process -- over a
+slot store, with the candidate order (score descending, flat index ascending) that the kernel promises.  The log-probabilities are
+synthetic and pairwise distinct unless a case says otherwise; the sums are formed in f32 on both sides, so indices, tokens, ids,
+store contents and flags are compared exactly and only the length-normalised scores (powf against Python's **) to rtol 1e-6."""
+
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+NEG = float('-inf')
+MXL_EINVAL = -1
+
+
+# ---------------------------------------------------------------------------------------------------------------- reference
+class RefState:
+    """the state one step reads and writes, on the host: ids (rows, ld) int64, scores (rows,) f32, the store as per item a list of
+    [score, tokens] slots, done flags, words (n_words, rows) int"""
+
+    def __init__(self, ids, scores, Bs, nb, words):
+        self.ids, self.scores, self.Bs, self.nb = ids.clone(), scores.clone(), Bs, nb
+        self.hyp = [[] for _ in range(Bs)]
+        self.done = [False] * Bs
+        self.n_done = 0
+        self.words = words.clone()
+        self.events = set()
+
+
+def ref_step(st: RefState, logp: torch.Tensor, V: int, cur_len: int, eos: int, pad: int, lp: float, early: bool):
+    """one mxl_beam_step on the host; returns (beam_idx, moved)"""
+    nb = st.nb
+    beam_idx, moved = [], []
+    sums = logp[:, :V] + st.scores[:, None]                      # f32, the one rounding the kernel makes
+    new_ids, new_words, new_scores = st.ids.clone(), st.words.clone(), st.scores.clone()
+    for b in range(st.Bs):
+        r0 = b * nb
+        if st.done[b]:
+            st.events.add('frozen')
+            beam_idx += list(range(r0, r0 + nb))
+            moved.append(0)
+            new_ids[r0:r0 + nb, cur_len] = pad
+            new_words[0, r0:r0 + nb] = 0
+            continue
+        flat = sums[r0:r0 + nb].reshape(-1).tolist()
+        order = sorted(range(nb * V), key=lambda i: (-(flat[i] + 0.0), i))[:2 * nb]
+        src, toks, scs, dead = [], [], [], []
+        hyp = st.hyp[b]
+        for rank, i in enumerate(order):
+            j, v, s = i // V, i % V, flat[i]
+            if v == eos:
+                if rank >= nb:
+                    st.events.add('skipped')
+                    continue
+                sc = s / cur_len ** lp
+                row = st.ids[r0 + j, :cur_len].tolist()
+                if len(hyp) < nb:
+                    hyp.append([sc, row])
+                    st.events.add('added')
+                else:
+                    worst = min(range(nb), key=lambda k: (hyp[k][0], k))
+                    if sc > hyp[worst][0]:
+                        hyp[worst] = [sc, row]
+                        st.events.add('replaced')
+                    else:
+                        st.events.add('rejected')
+            else:
+                src.append(j); scs.append(s); dead.append(s == NEG); toks.append(pad if s == NEG else v)
+            if len(src) == nb:
+                break
+        assert len(src) == nb
+        d = False
+        if len(hyp) >= nb:
+            d = True if early else min(h[0] for h in hyp) >= flat[order[0]] / cur_len ** lp
+        for j in range(nb):
+            new_ids[r0 + j, :cur_len] = st.ids[r0 + src[j], :cur_len]
+            new_ids[r0 + j, cur_len] = toks[j]
+            new_words[:, r0 + j] = st.words[:, r0 + src[j]]
+            new_scores[r0 + j] = scs[j]
+        for j in range(nb):
+            if dead[j] or d:
+                new_words[0, r0 + j] = 0
+        if any(dead):
+            st.events.add('dead')
+        if d:
+            st.done[b] = True
+            st.n_done += 1
+        beam_idx += [r0 + j for j in src]
+        moved.append(int(src != list(range(nb))))
+    st.ids, st.words, st.scores = new_ids, new_words, new_scores
+    return beam_idx, moved
+
+
+# ---------------------------------------------------------------------------------------------------------------- device side
+class DevState:
+    def __init__(self, ref: RefState, ld: int, dev):
+        Bs, nb = ref.Bs, ref.nb
+        rows = Bs * nb
+        i32 = dict(device=dev, dtype=torch.int32)
+        self.ids, self.scores, self.words = ref.ids.to(dev), ref.scores.to(dev), ref.words.to(dev, torch.int32).contiguous()
+        self.hyp_ids = torch.full((Bs, nb, ld), -7, device=dev, dtype=torch.int64)
+        self.hyp_len, self.hyp_score = torch.zeros(Bs, nb, **i32), torch.zeros(Bs, nb, device=dev)
+        self.hyp_n, self.done, self.n_done = torch.zeros(Bs, **i32), torch.zeros(Bs, **i32), torch.zeros(1, **i32)
+        self.beam_idx, self.moved = torch.full((rows,), -1, **i32), torch.full((Bs,), -1, **i32)
+        self.t = torch.zeros(1, **i32)
+
+    def step(self, logp, V, cur_len, eos, pad, lp, early, words=True):
+        from symbolic_music_generation_amd import ops
+        self.t.fill_(cur_len - 1)
+        ops.beam_step(logp, V, self.scores, self.ids, self.t, self.hyp_len.shape[1], eos, pad, lp, early, self.hyp_ids, self.hyp_len,
+                      self.hyp_score, self.hyp_n, self.done, self.n_done, self.beam_idx, self.moved,
+                      words=self.words if words else None, n_words=self.words.shape[0] if words else 0)
+
+
+def _compare(ref: RefState, d: DevState, beam_idx, moved, what):
+    assert d.beam_idx.tolist() == beam_idx, what
+    assert d.moved.tolist() == moved, what
+    assert torch.equal(d.ids.cpu(), ref.ids), what
+    assert torch.equal(d.words.cpu().to(torch.int64), ref.words), what
+    got, want = d.scores.cpu(), ref.scores
+    assert torch.equal(got == NEG, want == NEG), what
+    fin = want != NEG
+    assert torch.equal(got[fin], want[fin]), what                          # the sums are the same single f32 additions
+    assert d.done.tolist() == [int(x) for x in ref.done] and int(d.n_done) == ref.n_done, what
+    assert d.hyp_n.tolist() == [len(h) for h in ref.hyp], what
+    hyp_ids, hyp_len, hyp_score = d.hyp_ids.cpu(), d.hyp_len.tolist(), d.hyp_score.tolist()
+    for b, hyp in enumerate(ref.hyp):
+        for k, (sc, row) in enumerate(hyp):
+            assert hyp_len[b][k] == len(row) and hyp_ids[b, k, :len(row)].tolist() == row, (what, b, k)
+            if sc == NEG:
+                assert hyp_score[b][k] == NEG, (what, b, k)
+            else:
+                assert abs(hyp_score[b][k] - sc) <= 1e-6 * abs(sc), (what, b, k, hyp_score[b][k], sc)
+
+
+def _distinct_logp(rows, ldl, g):
+    """pairwise distinct values in (-6, -1), spaced 5 / (rows * ldl) apart"""
+    n = rows * ldl
+    return (-1.0 - 5.0 * torch.randperm(n, generator=g).to(torch.float64) / n).to(torch.float32).view(rows, ldl)
+
+
+@pytest.mark.parametrize('early', [True, False])
+@pytest.mark.parametrize('lp', [1.0, 0.6])
+@pytest.mark.parametrize('nb,V', [(2, 7), (3, 300), (5, 2500), (5, 7), (2, 2500), (3, 7), (2, 300), (5, 300), (3, 2500)])
+def test_beam_step_follows_the_scorer(dev, nb, V, lp, early):
+    """five consecutive steps on one state: a plain step; an eos at rank 0 (stored) with a second eos placed at rank nb (skipped);
+    every beam's eos on top (the store fills, and the last of them replaces the worst entry, which it beats); two more steps, on
+    which an item that is done stays frozen (early_stopping) or further hypotheses are weighed against a full store"""
+    Bs, ldl, ld, Tp = 3, V + 3, 12, 4
+    rows, eos, pad = Bs * nb, V - 2, 1
+    g = torch.Generator().manual_seed(1000 * nb + V)
+    ids = torch.randint(0, V, (rows, ld), generator=g)
+    # far below what a step adds, so that a hypothesis stored late beats one stored early
+    scores = (-100.0 - torch.randperm(rows, generator=g).to(torch.float32) * 0.01)
+    words = torch.randperm(3 * rows, generator=g).view(3, rows) + 1
+    ref = RefState(ids, scores, Bs, nb, words)
+    d = DevState(ref, ld, dev)
+    for step in range(5):
+        cur_len = Tp + step
+        logp = _distinct_logp(rows, ldl, g)
+        logp[:, eos] = -50.0 - torch.arange(rows) * 0.1
+        if step == 1:
+            for b in range(Bs):
+                r0 = b * nb
+                logp[r0, eos] = 0.5                                        # rank 0
+                rest = (logp[r0:r0 + nb, :V] + ref.scores[r0:r0 + nb, None])
+                rest[:, eos] = NEG
+                top = rest.reshape(-1).sort(descending=True).values
+                target = (top[nb - 2].item() + top[nb - 1].item()) / 2    # behind nb - 1 others: rank nb
+                logp[r0 + 1, eos] = target - ref.scores[r0 + 1].item()
+        if step == 2 or (step == 3 and not early):
+            logp[:, eos] = -0.01 * (1 + torch.arange(rows) % nb)
+        beam_idx, moved = ref_step(ref, logp, V, cur_len, eos, pad, lp, early)
+        d.step(logp.to(dev), V, cur_len, eos, pad, lp, early)
+        _compare(ref, d, beam_idx, moved, (step, nb, V, lp, early))
+    assert {'added', 'skipped', 'replaced'} <= ref.events, ref.events
+    if early:
+        assert 'frozen' in ref.events and all(ref.done)
+
+
+def test_ties_masked_rows_and_dead_children(dev):
+    """the lower flat index wins a tie; a row masked down to one finite token keeps it; the child of a -inf candidate gets pad, a
+    -inf score, its source's words with `unfinished` cleared, and stays dead on the next step"""
+    nb, V, ld, pad, eos = 3, 11, 8, 2, 9
+    rows = 2 * nb
+    g = torch.Generator().manual_seed(5)
+    ids = torch.randint(0, V, (rows, ld), generator=g)
+    scores = torch.full((rows,), -1.0)
+    words = torch.randperm(4 * rows, generator=g).view(4, rows) + 1
+    ref = RefState(ids, scores, 2, nb, words)
+    d = DevState(ref, ld, dev)
+    logp = _distinct_logp(rows, V + 3, g) - 10
+    logp[0, 6] = logp[2, 4] = logp[1, 7] = -0.5                           # item 0: three exactly equal best candidates
+    logp[3:6] = NEG                                                       # item 1: two finite candidates for three beams
+    logp[3, 4], logp[5, 0] = -0.25, -0.75
+    beam_idx, moved = ref_step(ref, logp, V, 4, eos, pad, 1.0, True)
+    assert beam_idx[:3] == [0, 1, 2] and ref.ids[:3, 4].tolist() == [6, 7, 4]         # flat indices 6 < 11 + 7 < 22 + 4
+    assert beam_idx[3:] == [3, 5, 3] and ref.ids[3:, 4].tolist() == [4, 0, pad] and 'dead' in ref.events
+    d.step(logp.to(dev), V, 4, eos, pad, 1.0, True)
+    _compare(ref, d, beam_idx, moved, 'ties')
+    assert d.scores[5].item() == NEG and d.words[0, 5].item() == 0
+    assert d.words[1:, 5].tolist() == words[1:, 3].tolist()               # the other words are the source's, and nothing moves them
+    # a dead row's children are dead whatever its log-probabilities say: row 3 is dead, rows 4 and 5 keep one token each
+    words2 = words.clone()
+    words2[0, 3] = 0
+    ref = RefState(ids, torch.tensor([-1.0, -1.0, -1.0, NEG, -1.0, -1.0]), 2, nb, words2)
+    d = DevState(ref, ld, dev)
+    logp = _distinct_logp(rows, V + 3, g)
+    logp[4:6, :V] = NEG
+    logp[4, 5], logp[5, 6] = -0.1, -0.2
+    beam_idx, moved = ref_step(ref, logp, V, 4, eos, pad, 1.0, True)
+    assert beam_idx[3:] == [4, 5, 3] and ref.ids[3:, 4].tolist() == [5, 6, pad] and ref.scores[5].item() == NEG
+    d.step(logp.to(dev), V, 4, eos, pad, 1.0, True)
+    _compare(ref, d, beam_idx, moved, 'dead children')
+    assert d.words[:, 5].tolist() == words2[:, 3].tolist()
+
+
+def test_rule_words_follow_a_swap_and_a_duplicate(dev):
+    nb, V, ld = 3, 40, 8
+    g = torch.Generator().manual_seed(6)
+    ids = torch.randint(0, V, (nb, ld), generator=g)
+    words = torch.randperm(8 * nb, generator=g).view(8, nb) + 1
+    ref = RefState(ids, torch.full((nb,), -1.0), 1, nb, words)
+    d = DevState(ref, ld, dev)
+    logp = _distinct_logp(nb, V + 3, g) - 10
+    logp[1, 30], logp[0, 31], logp[1, 5] = -0.1, -0.2, -0.3
+    beam_idx, moved = ref_step(ref, logp, V, 4, V - 1, 0, 1.0, True)
+    assert beam_idx == [1, 0, 1] and moved == [1]
+    d.step(logp.to(dev), V, 4, V - 1, 0, 1.0, True)
+    _compare(ref, d, beam_idx, moved, 'words')
+    assert d.words.cpu().tolist() == words[:, [1, 0, 1]].tolist()
+    # without the word buffer the same step leaves it alone
+    d2 = DevState(RefState(ids, torch.full((nb,), -1.0), 1, nb, words), ld, dev)
+    d2.step(logp.to(dev), V, 4, V - 1, 0, 1.0, True, words=False)
+    assert d2.beam_idx.tolist() == [1, 0, 1] and torch.equal(d2.words.cpu().to(torch.int64), words)
+
+
+# ---------------------------------------------------------------------------------------------------------------- reorder
+def _patterns(nb):
+    pats = [list(range(nb)), [1, 0] + list(range(2, nb))]
+    if nb >= 3:
+        pats += [[1, 2, 0] + list(range(3, nb)), [0, 0, 1] + list(range(3, nb))]
+    if nb == 16:
+        pats += [list(range(15, -1, -1)), [5] * 16]
+    return pats
+
+
+@pytest.mark.parametrize('nb', [2, 3, 16])
+@pytest.mark.parametrize('shape', [(2, 5, 16), (2, 37, 32)])
+def test_beam_reorder_equals_index_select(dev, nb, shape):
+    """rows of 320 and 4736 bytes (20 and 296 vectors: less than a block, and more than one with a ragged tail); per item the
+    identity, a swap, a 3-cycle and a duplicate; one buffer and a table of two"""
+    from symbolic_music_generation_amd import ops
+    pats = _patterns(nb)
+    Bs, rows = len(pats), len(pats) * nb
+    g = torch.Generator().manual_seed(nb)
+    bufs = [torch.randn((rows,) + shape, generator=g).to(dev, torch.bfloat16) for _ in range(3)]
+    idx = torch.tensor([b * nb + j for b, p in enumerate(pats) for j in p], dtype=torch.int32, device=dev)
+    moved = torch.tensor([int(p != list(range(nb))) for p in pats], dtype=torch.int32, device=dev)
+    want = [t.index_select(0, idx.to(torch.int64)) for t in bufs]
+    ops.beam_reorder(bufs[0], nb, idx, moved)
+    assert torch.equal(bufs[0], want[0])
+    ops.beam_reorder(bufs[1:], nb, idx, moved, table=ops.beam_table(bufs[1:]))
+    assert torch.equal(bufs[1], want[1]) and torch.equal(bufs[2], want[2])
+
+
+def test_beam_reorder_skips_an_item_that_did_not_move(dev):
+    """moved == 0 returns before any access: an item handed a non-identity beam_idx by mistake keeps every byte"""
+    from symbolic_music_generation_amd import ops
+    nb, shape = 3, (2, 37, 32)
+    buf = (torch.arange(2 * nb * 2 * 37 * 32) % 251).to(torch.bfloat16).view((2 * nb,) + shape).to(dev)
+    before = buf.clone()
+    idx = torch.tensor([1, 0, 2, 4, 5, 3], dtype=torch.int32, device=dev)
+    ops.beam_reorder(buf, nb, idx, torch.tensor([0, 1], dtype=torch.int32, device=dev))
+    assert torch.equal(buf[:nb].view(torch.int16), before[:nb].view(torch.int16))
+    assert torch.equal(buf[nb:], before[nb:].index_select(0, torch.tensor([1, 2, 0], device=dev)))
+
+
+# ---------------------------------------------------------------------------------------------------------------- arguments
+def test_argument_errors(dev):
+    from symbolic_music_generation_amd._lib import lib
+    L = lib()
+    i32 = dict(device=dev, dtype=torch.int32)
+    f = torch.zeros(64, 16, device=dev)
+    ids = torch.zeros(64, 8, device=dev, dtype=torch.int64)
+    z = torch.zeros(64, **i32)
+    P = lambda t: t.data_ptr()
+
+    def step(nb=2, Bs=2, hyp_n=P(z), n_done=P(z), words=None, n_words=0, V=16):
+        return L.mxl_beam_step(P(f), 16, P(f), P(ids), 8, P(z), Bs, nb, V, 3, 0, 1.0, 1, P(ids), P(z), P(f), hyp_n, P(z), n_done, P(z),
+                               P(z), words, n_words, 64, None)
+    assert step(nb=17) == MXL_EINVAL
+    assert step(hyp_n=None) == MXL_EINVAL and step(n_done=None) == MXL_EINVAL       # the store is one group
+    assert step(words=None, n_words=2) == MXL_EINVAL and step(words=P(z), n_words=0) == MXL_EINVAL
+    assert step(V=1) == MXL_EINVAL
+
+    def reorder(buf=P(f), table=None, n_bufs=1, nb=2, row_bytes=64):
+        return L.mxl_beam_reorder(buf, table, n_bufs, 2, nb, row_bytes, P(z), P(z), None)
+    assert reorder(nb=17) == MXL_EINVAL
+    assert reorder(buf=None) == MXL_EINVAL and reorder(table=P(ids)) == MXL_EINVAL  # one of the two, not both
+    assert reorder(row_bytes=24) == MXL_EINVAL and reorder(buf=P(f) + 4) == MXL_EINVAL
+    torch.cuda.synchronize()
+    assert not f.any() and not ids.any() and not z.any()                            # nothing was launched
