@@ -618,6 +618,33 @@ int mxl_beam_reorder(void* buf, const void* table, int n_bufs, int Bs, int nb, l
 int mxl_row_inv_norm_bf16(const void* x, long long ld, int n, int d, float* out, void* stream);
 int mxl_contrastive_select(const void* ctx, long long ctx_bs, const float* ctx_inv_norm, int inv_bs, int S, const void* hid,
                            const float* probs, float alpha, int B, int K, int d, float* score, void* sel, void* stream);
+/* Contrastive search with the step on the device (csrc/contrastive.hip; the invariant that makes it cheap is stated there).  A
+ * sequence is the K decoder rows b*K .. b*K + K-1 of one prompt, 2 <= K <= 32, rows = B * K; every position is read from *t_dev.
+ *
+ * mxl_contrastive_topk, before mxl_decode_advance (the rows hold columns 0..*t_dev): one workgroup per sequence reads the
+ *   log-probabilities of its picked row, logp[b*K + sel[b]] (logp (rows, ldl) f32, ldl >= V, already masked by the rules; sel (B) int32,
+ *   0 before the first step), takes the K best tokens in (value descending, token id ascending) order -- exact for any V -- and the
+ *   softmax over those K values (TopKLogitsWarper, then softmax): token k -> ids[b*K + k][*t_dev + 1], probs[b*K + k].  A candidate at
+ *   -inf is dead: probs 0, dead[b*K + k] = 1 (else 0), and it carries candidate 0's token.  unfinished (rows) int32 or NULL: a sequence
+ *   with unfinished[b*K] == 0 gets pad_id in all K rows.
+ * mxl_contrastive_step, after the model has run the candidates (*t_dev = their column): score[b*K + k] = the formula of
+ *   mxl_contrastive_select over the S = *t_dev context positions of ctx / ctx_inv_norm, same arithmetic and summation order (scores
+ *   are bit-identical), -inf for a dead candidate; sel[b] = the first maximum; the picked row's token, or pad_id for a sequence with
+ *   unfinished[b*K] == 0, goes to column *t_dev of all K rows; a picked eos_id of a live sequence adds 1 to *n_done (optional) and
+ *   clears unfinished of its K rows -- unless stop_later != 0: then mxl_rules_advance with the stop group follows and clears it
+ *   itself, after moving the words.  hid[b*K + sel[b]] -> ctx[b][*t_dev], its reciprocal norm (mxl_row_inv_norm_bf16's bits) ->
+ *   ctx_inv_norm[b][*t_dev].  ctx (B, Smax, d) bf16 with batch stride ctx_bs >= Smax * d, ctx_inv_norm batch stride inv_bs >= Smax;
+ *   nothing is written when *t_dev >= Smax or >= ld_ids.  unfinished == NULL: no stop rule.  Two launches.
+ * mxl_ring_slot_broadcast: table = device array of n_bufs addresses of (rows, H, M, dh) bf16 rings (the K and V rings of every
+ *   layer); slot *t_dev mod M of row b*K + sel[b] is copied into the other K - 1 rows of the sequence, for every ring, head and
+ *   sequence, in one launch.  No other slot is touched.  dh % 8 == 0, B and n_bufs <= 65535. */
+int mxl_contrastive_topk(const float* logp, int ldl, int V, int B, int K, const int* sel, void* ids, int ld_ids, const int* t_dev,
+                         float* probs, int* dead, const int* unfinished, int pad_id, void* stream);
+int mxl_contrastive_step(void* ctx, long long ctx_bs, float* ctx_inv_norm, int inv_bs, int Smax, const int* t_dev, const void* hid,
+                         const float* probs, const int* dead, float alpha, int B, int K, int d, float* score, int* sel, void* ids,
+                         int ld_ids, int* unfinished, int* n_done, int eos_id, int pad_id, int stop_later, void* stream);
+int mxl_ring_slot_broadcast(const void* table, int n_bufs, int B, int K, int H, int M, int dh, const int* t_dev, const int* sel,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Reformer path (A6-A8): replaces HuggingFace modeling_reformer.py as reached through

@@ -8,6 +8,7 @@
 // upstream, because the cache is zero-initialised and BD is evaluated for all M distances.
 #include "common.h"
 #include "musicxl_internal.h"
+#include "contrastive_score.h"
 
 namespace {
 
@@ -1258,50 +1259,20 @@ namespace {
 __global__ __launch_bounds__(256) void row_inv_norm_kernel(const bf16_t* x, long long ld, int d, float* out, int n) {
     const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (j >= n) return;
-    const bf16_t* r = x + (size_t)j * ld;
-    float s = 0.f;
-    for (int c = lane * 8; c < d; c += 512) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(r + c);
-#pragma unroll
-        for (int k = 0; k < 8; k++) { const float f = bf2f((bf16_t)v[k]); s += f * f; }
-    }
-    s = wave_sum(s);
-    if (lane == 0) out[j] = rsqrtf(s);
+    const float r = row_inv_norm_wave(x + (size_t)j * ld, d, lane);
+    if (lane == 0) out[j] = r;
 }
 
 // one workgroup per candidate row: four waves stride over the context positions, 8 bf16 per lane per pass over d
+// (contrastive_score_row, shared with mxl_contrastive_step)
 __global__ __launch_bounds__(256) void contrastive_score_kernel(const bf16_t* ctx, long long ctx_bs, const float* ctx_inv, int inv_bs,
                                                                 int S, const bf16_t* hid, int d, const float* probs, float alpha,
                                                                 int K, float* score) {
     __shared__ float wmax[4];
-    const int row = blockIdx.x, b = row / K, wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const bf16_t* h = hid + (size_t)row * d;
-    float hn = 0.f;
-    for (int c = lane * 8; c < d; c += 512) {
-        const bf16x8 v = *reinterpret_cast<const bf16x8*>(h + c);
-#pragma unroll
-        for (int k = 0; k < 8; k++) { const float f = bf2f((bf16_t)v[k]); hn += f * f; }
-    }
-    hn = rsqrtf(wave_sum(hn));
-    float best = -INFINITY;
-    for (int s = wid; s < S; s += 4) {
-        const bf16_t* c_ = ctx + (size_t)b * ctx_bs + (size_t)s * d;
-        float dot = 0.f;
-        for (int c = lane * 8; c < d; c += 512) {
-            const bf16x8 a = *reinterpret_cast<const bf16x8*>(h + c);
-            const bf16x8 v = *reinterpret_cast<const bf16x8*>(c_ + c);
-#pragma unroll
-            for (int k = 0; k < 8; k++) dot += bf2f((bf16_t)a[k]) * bf2f((bf16_t)v[k]);
-        }
-        dot = wave_sum(dot) * hn * ctx_inv[(size_t)b * inv_bs + s];
-        best = fmaxf(best, dot);
-    }
-    if (lane == 0) wmax[wid] = best;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float pen = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-        score[row] = (1.f - alpha) * probs[row] - alpha * pen;
-    }
+    const int row = blockIdx.x, b = row / K;
+    const float sc = contrastive_score_row(ctx + (size_t)b * ctx_bs, ctx_inv + (size_t)b * inv_bs, S, hid + (size_t)row * d, d,
+                                           probs[row], alpha, wmax);
+    if (threadIdx.x == 0) score[row] = sc;
 }
 
 __global__ void contrastive_pick_kernel(const float* score, int K, long long* sel, int B) {

@@ -9,8 +9,9 @@ Strategies mirrored from `MusicGenerator` (eval.py:277-326): greedy (do_sample=F
 `top_k`, `top_p`, `typical_p`, `temperature`, `repetition_penalty` and renormalised logits -- every key the `sample`
 strategy accepts (eval.py:279) -- and beam search (`strategy='beam'`, eval.py:302-321: HF `beam_search` / `beam_sample` with
 `BeamSearchScorer`), which runs the same per-token kernels eagerly with the beam bookkeeping between steps (beam_search).
-Contrastive search raises: HF 4.25.1's `contrastive_search` requires `past_key_values` in the model output, which neither
-TransfoXL (`mems`) nor Reformer (`past_buckets_states`) returns, so that strategy fails in the reference too.
+Contrastive search (`strategy='contrastive'`, eval.py:296-302) runs over the Transformer-XL mems with one decoder row per
+candidate: its whole step on the device, captured like the sampling step (contrastive_search_device), with the host-driven loop
+(contrastive_search) as the reference.  The Reformer (`past_buckets_states`) cannot serve it, as in the reference.
 """
 import math
 import os
@@ -700,6 +701,7 @@ def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sam
 
 
 BEAM_MAX = 16            # beams per item of mxl_beam_step / mxl_beam_reorder
+CONTRASTIVE_MAX = ops.CONTRASTIVE_MAX     # candidates per sequence of contrastive search on the device
 
 
 class BeamStore:
@@ -732,6 +734,33 @@ class BeamStore:
     def restore(self, saved):
         for t, v in zip((self.scores, self.hyp_ids, self.hyp_score, self.ints), saved):
             t.copy_(v)
+
+
+class ContrastiveStore:
+    """The state of a contrastive search on the device, as mxl_contrastive_topk / mxl_contrastive_step read and write it: `ctx`
+    (B0, Smax, d) bf16 and `inv` (B0, Smax) f32, the last-layer hidden state of every position of every sequence and its reciprocal
+    norm; `probs` (B0, K) and `score` (B0 * K,) f32 of the step's candidates; and the int32 words `dead` (B0, K), `sel` (B0,), the
+    candidate picked last, and `n_done` (1,), the number of finished sequences, which the host reads a chunk late.  The words share
+    one buffer."""
+
+    def __init__(self, B0: int, K: int, Smax: int, d: int, dev):
+        self.B0, self.K = B0, K
+        self.ctx = torch.zeros(B0, Smax, d, device=dev, dtype=torch.bfloat16)
+        self.inv = torch.zeros(B0, Smax, device=dev, dtype=torch.float32)
+        self.probs = torch.zeros(B0, K, device=dev, dtype=torch.float32)
+        self.score = torch.zeros(B0 * K, device=dev, dtype=torch.float32)
+        self.ints = torch.zeros(B0 * K + B0 + 1, device=dev, dtype=torch.int32)
+        self.dead = self.ints[:B0 * K].view(B0, K)
+        self.sel, self.n_done = self.ints[B0 * K:B0 * K + B0], self.ints[B0 * K + B0:]
+
+    def start(self, hid: torch.Tensor):
+        """a new search: hid (B0, Tp, d) = the last-layer hidden states of the prompts; every word zero (sel = 0: the K rows of a
+        sequence are equal after the prompt pass, its first candidates come from row 0)"""
+        Tp = hid.shape[1]
+        self.ints.zero_()
+        self.ctx[:, :Tp].copy_(hid)
+        for b in range(self.B0):
+            ops.row_inv_norm(self.ctx[b, :Tp], self.inv[b, :Tp], Tp)
 
 
 class XLDecoder:
@@ -776,6 +805,7 @@ class XLDecoder:
         self.trace = None
         self.steps_run = 0                              # decode steps issued by the last generate() (early exit: fewer)
         self.beam = None                                # BeamStore of a beam search on the device (beam_begin)
+        self.cs = None                                  # ContrastiveStore of a contrastive search on the device (contrastive_begin)
         # the rules of the current generation (eos, grammar, bar budget, bar count) and their per-row words, which the sampler
         # launch reads and moves; the words are readable here under their names
         self.rules = RowRules(batch, dev)
@@ -1026,6 +1056,80 @@ class XLDecoder:
             self.graph.replay()
         else:
             self.beam_step()
+
+    # ---------------------------------------------------------------- contrastive search on the device (contrastive_search_device)
+    def contrastive_begin(self, prompt: torch.Tensor, max_length: int, K: int, alpha: float, eos: Optional[int], pad: int,
+                          use_graph: bool = True, grammar=None, in_key=None, keys: Optional[torch.Tensor] = None) -> int:
+        """prompt pass (one row per candidate: the K rows of a sequence hold the same prompt; the rules started as `prefill` starts
+        them, with the stop group (eos, pad, 0) always on -- eos None: -1, never emitted) + the store + (use_graph) capture of one
+        contrastive step + the first token, chosen by one step run here; returns the number of `contrastive_replay_once()` calls that
+        complete the generation to max_length.  Graph key, snapshot and restore around the warm-up and the capture are beam_begin's;
+        the store's words join the snapshot (its context rows need none: a step writes position t and reads those below it)."""
+        if max_length > self.Tmax:
+            raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
+        if K < 2 or K > CONTRASTIVE_MAX or self.B % K:
+            raise MusicXLError(f'contrastive search on the device takes 2..{CONTRASTIVE_MAX} candidates and one decoder row per '
+                               'candidate')
+        c, Tp = self.eng.cfg, prompt.shape[1]
+        self.prefill(prompt, None, None, (-1 if eos is None else int(eos), int(pad), 0), grammar, None, in_key, keys)
+        if self.cs is None or self.cs.K != K:
+            self.cs = ContrastiveStore(self.B // K, K, self.Tmax, c.d_model, self.eng.dev)
+            self.ring_table = ops.beam_table(self.kc + self.vc)
+        self.cs.start(self.eng._last.h[c.n_layer & 1].view(self.B, Tp, c.d_model)[::K])
+        self._cs_args = (int(K), float(alpha), self.rules.stop[0], int(pad))
+        self._use_graph = use_graph
+        steps = max_length - Tp - 1
+        if steps > 0 and use_graph:
+            key = (('contrastive',) + self._cs_args + (None if self.trace is None else self.trace.data_ptr(),)
+                   + self.rules.graph_key(self.eng.dev))
+            if self.graph is None or self._graph_key != key:
+                state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(), [k.clone() for k in self.kc + self.vc],
+                         self.rules.snapshot(), self.cs.ints.clone(), self.logp.clone())
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    self.contrastive_step()
+                torch.cuda.current_stream().wait_stream(s)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self.contrastive_step()
+                self._graph_key = key
+                self.t_dev.copy_(state[0]); self.rng.copy_(state[1]); self.ids.copy_(state[2])
+                for a, b in zip(self.kc + self.vc, state[3]):
+                    a.copy_(b)
+                self.rules.restore(state[4])
+                self.cs.ints.copy_(state[5])
+                self.logp.copy_(state[6])             # (the step starts from the log-probabilities the last one left)
+        self.contrastive_step()                       # the first token: column Tp
+        return max(steps, 0)
+
+    def contrastive_step(self):
+        """one whole contrastive step, no host read: the rules mask on the log-probabilities, the K candidates of every sequence
+        from its picked row (mxl_contrastive_topk), the position moves on, the candidates go through the model, one is picked and
+        written to all K rows (mxl_contrastive_step), the rule words move along it, and the one ring slot the step wrote follows the
+        pick in every layer (mxl_ring_slot_broadcast; the invariant is stated in csrc/contrastive.hip)"""
+        c, cs = self.eng.cfg, self.cs
+        K, alpha, eos, pad = self._cs_args
+        rules = ops.rules_in_force(**self.rules.kwargs())
+        ruled = rules['grammar'] is not None or rules['in_key'] is not None
+        if ruled:
+            ops.rules_mask(self.logp, c.vocab_size, self.t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
+        ops.contrastive_topk(self.logp, c.vocab_size, cs.sel, self.ids, self.t_dev, cs.probs, cs.dead, self.unfinished, pad)
+        ops.decode_advance(self.t_dev, self.rng)
+        self._forward_token()
+        # under a rule the advance launch applies the stop rule to `unfinished` itself, after it has moved the words of the rows
+        # that were live when they chose the token
+        ops.contrastive_step(cs.ctx, cs.inv, self.t_dev, self.h[c.n_layer & 1], cs.probs, cs.dead, alpha, cs.score, cs.sel, self.ids,
+                             self.unfinished, cs.n_done, eos, pad, stop_later=ruled)
+        if ruled:
+            ops.rules_advance(self.ids, self.t_dev, **rules)
+        ops.ring_slot_broadcast(self.kc + self.vc, K, self.t_dev, cs.sel, table=self.ring_table)
+
+    def contrastive_replay_once(self):
+        if self._use_graph:
+            self.graph.replay()
+        else:
+            self.contrastive_step()
 
     def _trace(self):
         if self.trace is not None:
@@ -1466,7 +1570,8 @@ def beam_generate(make_decoder, input_ids: torch.Tensor, max_length: int, *, num
 
 
 def contrastive_search(dec, prompt: torch.Tensor, max_length: int, top_k: int = 4, penalty_alpha: float = 0.6,
-                       eos_token_id: Optional[int] = 0, pad_token_id: Optional[int] = None) -> torch.Tensor:
+                       eos_token_id: Optional[int] = 0, pad_token_id: Optional[int] = None, allowed=None,
+                       trace: Optional[list] = None) -> torch.Tensor:
     """HF 4.25.1 `GenerationMixin.contrastive_search` over Transformer-XL mems -- the reference's 'contrastive' strategy
     (musicnlp/trainer/eval.py:296-302); the reference's `prepare_inputs_for_generation` re-stacks the per-row mems lists that
     routine builds ("to work with cosine sim generation", musicnlp/models/transformer_xl.py:229-234).  One decoder row per
@@ -1474,7 +1579,12 @@ def contrastive_search(dec, prompt: torch.Tensor, max_length: int, top_k: int = 
     log-probabilities and their probabilities renormalised over those k (TopKLogitsWarper, then softmax); (2) all B * K
     candidates through one cached decode step; (3) mxl_contrastive_select scores each candidate (1 - alpha) * p - alpha * max
     cosine similarity between its last-layer hidden state and those of every earlier position, and picks the best; (4) the K
-    rows of the sequence take over the picked candidate's rings and history, its log-probabilities open the next step."""
+    rows of the sequence take over the picked candidate's rings and history, its log-probabilities open the next step.
+    This is the host-driven reference of contrastive_search_device.  allowed: None, or a callable (ids[:, :cur_len]) -> (rows, V)
+    bool, as beam_search takes it; a token it bars is -inf before the top-k, where HF's logits processors sit, and a candidate at
+    -inf is dead: it scores -inf and is never picked.  trace: a list that receives, per step, (live (B0,) bool, the gap between the
+    two best contrastive scores (B0,), the gap between the K-th and the (K+1)-th log-probability (B0,)) -- what decides whether
+    another implementation may be held to the same tokens."""
     e, c = dec.eng, dec.eng.cfg
     dev, d, L = e.dev, c.d_model, c.n_layer
     K = int(top_k)
@@ -1496,16 +1606,29 @@ def contrastive_search(dec, prompt: torch.Tensor, max_length: int, top_k: int = 
     logp = dec.beam_logp()[::K].clone()                                  # (B0, V)
     score = torch.empty(rows, device=dev, dtype=torch.float32)
     sel = torch.empty(B0, device=dev, dtype=torch.int64)
+    norm = torch.empty(B0, device=dev, dtype=torch.float32)
     grp = torch.arange(B0, device=dev) * K
     unfinished = torch.ones(B0, dtype=torch.bool, device=dev)
     cur_len = Tp
     while cur_len < max_length:
+        if allowed is not None:
+            ok = torch.as_tensor(allowed(dec.ids[:, :cur_len]))[::K].to(dev, torch.bool)
+            logp = logp.masked_fill(~ok, float('-inf'))
         top_lp, top_ids = logp.topk(K, dim=-1)
         probs = torch.softmax(top_lp.float(), dim=-1).contiguous()
         dec.ids[:, cur_len] = top_ids.reshape(-1)
         dec.beam_advance(cur_len + 1)                                    # every candidate at position cur_len
         hid = dec.h[L & 1]
         ops.contrastive_select(ctx, inv, cur_len, hid, probs, penalty_alpha, score, sel)
+        if allowed is not None:                                          # dead candidates score -inf; the first maximum again
+            sc = score.view(B0, K).masked_fill(top_lp == float('-inf'), float('-inf'))
+            best = sc == sc.max(1, keepdim=True).values
+            # (a finished sequence whose rows the mask bars whole scores NaN everywhere: it emits pad, any candidate will do)
+            sel = torch.where(best, torch.arange(K, device=dev)[None, :], K - 1).min(1).values
+        if trace is not None:
+            two = (sc if allowed is not None else score.view(B0, K)).topk(2, dim=1).values
+            edge = logp.topk(K + 1, dim=-1).values
+            trace.append((unfinished.clone(), two[:, 0] - two[:, 1], edge[:, K - 1] - edge[:, K]))
         src = grp + sel
         if eos_token_id is not None:                                     # finished sequences emit pad from now on
             tok = dec.ids[src, cur_len]
@@ -1515,12 +1638,51 @@ def contrastive_search(dec, prompt: torch.Tensor, max_length: int, top_k: int = 
             dec.ids[:, cur_len] = tok.repeat_interleave(K)
             unfinished = unfinished & (tok != eos_token_id)
         ctx[:, cur_len].copy_(hid.index_select(0, src))
-        ops.row_inv_norm(ctx[:, cur_len], inv[:, cur_len], B0)
+        inv[:, cur_len] = ops.row_inv_norm(ctx[:, cur_len], norm, B0)     # (the kernel writes a contiguous (B0,) vector)
         logp = dec.beam_logp().index_select(0, src)
         cur_len += 1
         if eos_token_id is not None and not bool(unfinished.any()):
             break
     return dec.ids[::K, :cur_len].clone()
+
+
+def contrastive_search_device(dec, prompt: torch.Tensor, max_length: int, top_k: int = 4, penalty_alpha: float = 0.6,
+                              eos_token_id: Optional[int] = 0, pad_token_id: Optional[int] = None, use_graph: bool = True,
+                              stop_chunk: int = STOP_CHUNK, grammar=None, in_key=None, key=None) -> torch.Tensor:
+    """`contrastive_search` with the whole step on the device: per step the rules mask, mxl_contrastive_topk, the position advance,
+    the model, mxl_contrastive_step, the rules advance and mxl_ring_slot_broadcast -- no host read, no whole-ring copy, captured once
+    under use_graph (XLDecoder.contrastive_begin / contrastive_step).  The steps are replayed in chunks of `stop_chunk`; the number
+    of finished sequences is read back one chunk late (as beam_search_device reads its done items) and the loop ends when every
+    sequence has finished or at max_length.  Returns what the host path returns: ids[::K] cut at the step in which the last sequence
+    finished, else at max_length; the steps run beyond it inside the last chunk emit pad and are cut off.  dec: an XLDecoder with
+    prompt rows x top_k rows, 2 <= top_k <= 32.  grammar (with or without a bar budget) / in_key / key: the rules of
+    `XLDecoder.generate`, one value per prompt where they are per row (each prompt's is shared by its K rows); a barred token is -inf
+    before the top-k, and a candidate that is barred is never picked."""
+    V = dec.eng.cfg.vocab_size
+    K = int(top_k)
+    if K < 2 or not penalty_alpha or penalty_alpha <= 0:
+        raise ValueError('contrastive search needs top_k > 1 and penalty_alpha > 0')
+    B0, Tp = prompt.shape
+    rows = B0 * K
+    if dec.B != rows or max_length > dec.Tmax:
+        raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, contrastive search needs {rows} x {max_length}')
+    if max_length <= Tp:
+        return prompt.to(dec.eng.dev).clone()
+    pad = eos_token_id if pad_token_id is None else pad_token_id
+    n = dec.contrastive_begin(prompt.repeat_interleave(K, 0).to(dec.eng.dev), max_length, K, penalty_alpha, eos_token_id,
+                              0 if pad is None else pad, use_graph, grammar, in_key, key_config(in_key, key, B0, V, K))
+    poll, issued, chunk = _AlivePoll(dec.cs.n_done, target=B0), 0, max(1, int(stop_chunk))
+    poll.mark()
+    poll.wait(0)                        # the first token is chosen: sequences that all start with eos replay nothing
+    while issued < n and not poll.wait(1):
+        k = min(chunk, n - issued)
+        for _ in range(k):
+            dec.contrastive_replay_once()
+        poll.mark()
+        issued += k
+    dec.steps_run = issued
+    width = stop_width(dec.ids[::K], dec.unfinished[::K], Tp, max_length, dec.rules.stop[0])
+    return dec.ids[::K, :width].clone()
 
 
 def _warp(scores: torch.Tensor, top_k, top_p, typical_p, temperature, min_keep: int, renormalize: bool = True) -> torch.Tensor:

@@ -977,6 +977,80 @@ def contrastive_select(ctx, ctx_inv, S, hid, probs, alpha, score, sel):
     return sel
 
 
+CONTRASTIVE_MAX = 32     # candidates per sequence of mxl_contrastive_topk / mxl_contrastive_step / mxl_ring_slot_broadcast
+
+
+def _contrastive_rows(what, probs, dead, sel, ids, unfinished):
+    """(B, K) of a contrastive launch from probs (B, K) f32, with the shapes and types of the other per-row tensors checked"""
+    _req(probs, torch.float32, f'{what} probs'); _req(dead, torch.int32, f'{what} dead'); _req(sel, torch.int32, f'{what} sel')
+    if probs.dim() != 2 or not probs.is_contiguous():
+        raise MusicXLError(f'{what}: probs must be contiguous (B, K) f32')
+    B, K = probs.shape
+    if K < 2 or K > CONTRASTIVE_MAX:
+        raise MusicXLError(f'{what}: 2..{CONTRASTIVE_MAX} candidates per sequence, got {K}')
+    if dead.numel() != B * K or not dead.is_contiguous() or sel.numel() != B or not sel.is_contiguous():
+        raise MusicXLError(f'{what}: dead must be contiguous ({B}, {K}) int32 and sel ({B},) int32')
+    if not ids.is_cuda or ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[0] != B * K or ids.stride(1) != 1:
+        raise MusicXLError(f'{what}: ids must be ({B * K}, .) int64 device rows with unit column stride')
+    if unfinished is not None:
+        _req(unfinished, torch.int32, f'{what} unfinished')
+        if unfinished.numel() != B * K or not unfinished.is_contiguous():
+            raise MusicXLError(f'{what}: unfinished must be contiguous ({B * K},) int32, one word per row')
+    return B, K
+
+
+def contrastive_topk(logp, V, sel, ids, t_dev, probs, dead, unfinished=None, pad_id=0):
+    """see mxl_contrastive_topk: the K = probs.shape[1] best tokens of logp[b*K + sel[b], :V] -> ids[b*K + k, t + 1], their softmax ->
+    probs (B, K) f32, dead (B, K) int32; logp (B*K, >= V) f32, sel (B,) int32, unfinished (B*K,) int32 or None"""
+    B, K = _contrastive_rows('contrastive_topk', probs, dead, sel, ids, unfinished)
+    _req(logp, torch.float32, 'contrastive_topk logp')
+    if logp.dim() != 2 or logp.shape[0] != B * K or logp.shape[1] < V or logp.stride(1) != 1:
+        raise MusicXLError(f'contrastive_topk: logp must be ({B * K}, >= {V}) f32 with unit column stride')
+    check(lib().mxl_contrastive_topk(_p(logp), logp.stride(0), int(V), B, K, _p(sel), _p(ids), ids.stride(0), _p(t_dev), _p(probs),
+                                     _p(dead), _p(unfinished), int(pad_id), _stream()), 'mxl_contrastive_topk')
+
+
+def contrastive_step(ctx, ctx_inv, t_dev, hid, probs, dead, alpha, score, sel, ids, unfinished=None, n_done=None, eos_id=-1, pad_id=0,
+                     stop_later=False):
+    """see mxl_contrastive_step: ctx (B, Smax, d) bf16 and ctx_inv (B, Smax) f32 (read below position t, written at it), hid (B*K, d)
+    bf16, probs / dead (B, K), score (B*K,) f32 and sel (B,) int32 out, the picked token -> ids[b*K .. b*K + K-1, t]; unfinished (B*K,)
+    int32 or None, n_done (1,) int32 or None; stop_later: rules_advance with the stop group follows and clears `unfinished` itself"""
+    B, K = _contrastive_rows('contrastive_step', probs, dead, sel, ids, unfinished)
+    _req(ctx, torch.bfloat16, 'contrastive_step ctx'); _req(hid, torch.bfloat16, 'contrastive_step hid')
+    _req(ctx_inv, torch.float32, 'contrastive_step ctx_inv'); _req(score, torch.float32, 'contrastive_step score')
+    d = hid.shape[-1]
+    if ctx.dim() != 3 or ctx.shape[0] != B or ctx.shape[2] != d or ctx.stride(2) != 1 or ctx.stride(1) != d:
+        raise MusicXLError(f'contrastive_step: ctx must be ({B}, Smax, {d}) bf16 with contiguous positions')
+    if tuple(ctx_inv.shape) != (B, ctx.shape[1]) or ctx_inv.stride(1) != 1:
+        raise MusicXLError(f'contrastive_step: ctx_inv must be ({B}, {ctx.shape[1]}) f32 with unit column stride')
+    if tuple(hid.shape) != (B * K, d) or not hid.is_contiguous() or score.numel() != B * K or not score.is_contiguous():
+        raise MusicXLError(f'contrastive_step: hid must be contiguous ({B * K}, {d}) bf16 and score ({B * K},) f32')
+    if n_done is not None:
+        _req(n_done, torch.int32, 'contrastive_step n_done')
+    check(lib().mxl_contrastive_step(_p(ctx), ctx.stride(0), _p(ctx_inv), ctx_inv.stride(0), ctx.shape[1], _p(t_dev), _p(hid), _p(probs),
+                                     _p(dead), float(alpha), B, K, d, _p(score), _p(sel), _p(ids), ids.stride(0), _p(unfinished),
+                                     _p(n_done), int(eos_id), int(pad_id), int(bool(stop_later)), _stream()), 'mxl_contrastive_step')
+
+
+def ring_slot_broadcast(rings, K, t_dev, sel, table=None):
+    """see mxl_ring_slot_broadcast: rings = a list of contiguous (rows, H, M, dh) bf16 tensors of one shape with `table`, their
+    addresses (beam_table); slot t mod M of row b*K + sel[b] -> the other K - 1 rows of sequence b, one launch for all"""
+    first = rings[0]
+    _req(sel, torch.int32, 'ring_slot_broadcast sel')
+    if first.dim() != 4 or K < 2 or K > CONTRASTIVE_MAX or first.shape[0] % K or sel.numel() != first.shape[0] // K:
+        raise MusicXLError(f'ring_slot_broadcast: (rows, H, M, dh) rings of K = 2..{CONTRASTIVE_MAX} rows per sequence and sel (rows / K,)')
+    for t in rings:
+        if not t.is_cuda or not t.is_contiguous() or t.shape != first.shape or t.dtype != torch.bfloat16 or t.data_ptr() % 16:
+            raise MusicXLError('ring_slot_broadcast: the rings must be contiguous bf16 device tensors of one shape, 16-byte aligned')
+    if table is None:
+        table = beam_table(rings)
+    if table.dtype != torch.int64 or table.numel() != len(rings) or not table.is_cuda:
+        raise MusicXLError('ring_slot_broadcast: the table must hold one device address per ring (beam_table)')
+    rows, H, M, dh = first.shape
+    check(lib().mxl_ring_slot_broadcast(_p(table), len(rings), rows // K, int(K), H, M, dh, _p(t_dev), _p(sel), _stream()),
+          'mxl_ring_slot_broadcast')
+
+
 # ------------------------------------------------------------------ reformer
 def axial_embed_fwd(ids, E, W0, W1, out, A0, A1, drop_p=0.0, seed=0, site_emb=0, site_pos=1):
     B, T = ids.shape

@@ -225,7 +225,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
         processor would.  It combines with `num_return_sequences`, padded prompts, `eos_token_id` / `min_length` /
         `max_new_tokens`; the prompts must obey the grammar themselves (MusicXLError otherwise).  That constraint is syntactic;
         `tokenizer.grammar(bar_budget=True)` adds the bar budget, under which every channel of every generated bar is also exactly
-        as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Plain beam search takes it too (below); beam-sample, group-beam and contrastive search take no grammar.
+        as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Plain beam search and contrastive search take it too
+        (below); beam-sample and group-beam search take no grammar.
 
         `n_bars` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): length in bars.  An int, or a
         sequence or tensor of one int per prompt (repeated per prompt under `num_return_sequences`); a negative entry leaves that
@@ -245,7 +246,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         prompts' keys.  The prompt only supplies the key: its own pitches are not judged.  A generated `Key_*` token sets the row's
         key from then on.  The key lives on the device beside the other rules' words and the mask sits in the same sampler launch,
         in the same place.  It needs no `grammar` and combines with everything greedy decoding and sampling take, and with
-        plain beam search; beam-sample, group-beam and contrastive search take no `in_key`.
+        plain beam search and contrastive search (below); beam-sample and group-beam search take no `in_key`.
 
         `melody` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): here is a melody, write the bass
         under it.  A guide is the concatenation of the `<bar> <melody> ... <bass>` spans of its bars, each bar up to and including
@@ -265,10 +266,18 @@ class MyTransfoXLLMHeadModel(EngineModule):
         (`generate.beam_search_device`: mxl_beam_step / mxl_beam_reorder inside the captured step) and takes `grammar`, `n_bars` and
         `in_key` / `key` with the checks above, given an explicit `eos_token_id=` (without one they stay refused, as before); per-prompt values are shared by the prompt's beams, a barred token is -inf before
         the running scores are added, and a prompt left with fewer than `num_return_sequences` hypotheses raises MusicXLError.
-        `MXL_BEAM_HOST=1` keeps the host scorer (`generate.beam_search`), which takes no rules."""
-        from .generate import (BEAM_MAX, XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, beam_search_device,
-                               check_grammar_args, contrastive_search, key_config, left_pad_counts, melody_config, resolve_max_length,
-                               stop_config)
+        `MXL_BEAM_HOST=1` keeps the host scorer (`generate.beam_search`), which takes no rules.
+
+        Contrastive search (`penalty_alpha > 0`, `top_k` 2..32) runs with its whole step on the device
+        (`generate.contrastive_search_device`: mxl_contrastive_topk / mxl_contrastive_step / mxl_ring_slot_broadcast inside the captured
+        step; `use_graph` is honoured) and returns what the host path returns.  It takes `grammar` (with or without a bar budget) and
+        `in_key` / `key` with the checks above, given an explicit `eos_token_id=` (without one they stay refused, as before): per-prompt
+        values are shared by the prompt's `top_k` rows, a barred token is -inf before the top-k, where HF's logits processors sit, and
+        a barred candidate is never picked.  `n_bars`, `melody` and padded prompts stay refused.  `top_k > 32` or
+        `MXL_CONTRASTIVE_HOST=1` keeps the host-driven loop (`generate.contrastive_search`), which takes no rules here."""
+        from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, beam_search_device,
+                               check_grammar_args, contrastive_search, contrastive_search_device, key_config, left_pad_counts,
+                               melody_config, resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -296,7 +305,11 @@ class MyTransfoXLLMHeadModel(EngineModule):
         # emitting eos, the config's eos (0 = [OMIT]) is no end token of the grammar, and the stop group that the explicit eos turns on
         # is how the device scorer retires rows.  Without one, and for n_bars without the grammar that counts the bars, a beam call
         # keeps the refusal it has always had
-        no_rules = contrastive or num_beam_groups != 1 or (num_beams > 1 and not (device_beam and stop is not None))
+        # contrastive search likewise: its step runs on the device for 2..32 candidates (generate.contrastive_search_device) and takes
+        # the grammar and the key rule under the same condition; MXL_CONTRASTIVE_HOST=1 keeps the host-driven loop, which takes none
+        device_contrastive = (contrastive and top_k <= CONTRASTIVE_MAX and os.environ.get('MXL_CONTRASTIVE_HOST') != '1')
+        no_rules = ((contrastive and not (device_contrastive and stop is not None)) or num_beam_groups != 1
+                    or (num_beams > 1 and not (device_beam and stop is not None)))
         if n_pad is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('padded prompts (attention_mask with zeros) are supported for greedy decoding and sampling only, not '
                                'for beam, group-beam or contrastive search')
@@ -306,7 +319,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         if grammar is not None and no_rules:
             raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
-        if n_bars is not None and (no_rules or (num_beams > 1 and grammar is None)):
+        if n_bars is not None and (no_rules or contrastive or (num_beams > 1 and grammar is None)):
             raise MusicXLError('n_bars= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
         if (in_key is not None or key is not None) and no_rules:
@@ -318,6 +331,10 @@ class MyTransfoXLLMHeadModel(EngineModule):
         keys = key_config(in_key, key, input_ids.shape[0], self.config.vocab_size, num_return_sequences)
         if contrastive:
             dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
+            if device_contrastive:
+                return contrastive_search_device(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
+                                                 eos_token_id=eos_b, pad_token_id=pad_b, use_graph=use_graph, grammar=grammar,
+                                                 in_key=in_key, key=key)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
                                       eos_token_id=eos_b, pad_token_id=pad_b)
         if device_beam:
