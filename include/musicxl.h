@@ -601,6 +601,24 @@ int mxl_beam_step(const float* logp, int ldl, float* beam_scores, void* ids, int
                   int eos_id, int pad_id, float length_penalty, int early_stopping, void* hyp_ids, int* hyp_len, float* hyp_score,
                   int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved, int* words, int n_words, int word_stride,
                   void* stream);
+/* Diverse (group) beam search (HF 4.25.1 group_beam_search + HammingDiversityLogitsProcessor; the reference's 'beam' strategy runs
+ * num_beams=4, num_beam_groups=2): mxl_beam_step for ng groups of gs = nb / ng beams, rows g * gs .. g * gs + gs - 1 of the item,
+ * walked in order inside the item's workgroup.  Everything not said here is mxl_beam_step's: the store (one per item, capacity nb,
+ * shared by its groups), the order, dead rows, frozen items, ids and the words.
+ * score: (logp[j][v] - diversity_penalty * cnt[v]) + beam_scores[j], product, difference and sum each rounded to f32 on its own;
+ *   cnt[v] = how many rows of the EARLIER groups of this item continue with token v in this step (rows that continue at -inf do not
+ *   count).  For the first group, and with diversity_penalty == 0, the score is logp + beam_scores bit for bit.
+ * select: per group the 2 * gs best of its gs * V candidates, score descending, then flat index (j - g * gs) * V + v ascending.
+ * walk: per group as mxl_beam_step's with n = gs: an eos at rank < gs joins the store (a free slot of the nb, else it replaces the
+ *   worst entry if it beats it), an eos behind is skipped, the first gs others continue inside the group; done |= (the store holds
+ *   nb) && (early_stopping || worst stored score >= this group's rank-0 score / cur_len ** length_penalty).  The groups behind the
+ *   one that made the item done are not walked in that step: identity, pad_id, scores untouched.
+ * 2 <= nb <= 16, 2 <= ng <= nb, nb % ng == 0 (gs = 1 is legal), 0 <= diversity_penalty < inf; else MXL_EINVAL.  The K/V rings follow
+ * with mxl_beam_reorder as after mxl_beam_step. */
+int mxl_group_beam_step(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs, int nb,
+                        int ng, float diversity_penalty, int V, int eos_id, int pad_id, float length_penalty, int early_stopping,
+                        void* hyp_ids, int* hyp_len, float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved,
+                        int* words, int n_words, int word_stride, void* stream);
 /* Contiguous (rows, row_bytes) buffers follow beam_idx in place, item by item (the K/V rings of a decoder: HF _reorder_cache without
  * the second buffer).  buf: one buffer (n_bufs = 1), or table: a device array of n_bufs buffer addresses, one launch for all of them;
  * exactly one of the two is given.  A thread owns one 16-byte column of an item, reads the sources of the rows that change into

@@ -12,6 +12,12 @@ min..max of the tokens per second (new tokens of the best hypothesis per prompt:
 step of either path (the host path's torch launches -- topk, the index_select / copy_ pairs, the uploads -- come on top).
 
     python3 scripts/perf_beam.py                  # env: RUNS (5), NEW (256)
+
+GROUPS=2 (and DIVERSITY=1.5) measures diverse beam search instead, num_beam_groups = GROUPS with that diversity_penalty:
+generate.group_beam_search_device (mxl_group_beam_step in place of mxl_beam_step) against generate.group_beam_search, which runs
+the topk, the reads, the walk and the uploads once per group and step.
+
+    GROUPS=2 python3 scripts/perf_beam.py         # the reference's 'beam' strategy: num_beams=4, num_beam_groups=2
 """
 import os
 import statistics
@@ -25,11 +31,14 @@ from symbolic_music_generation_amd.transformer_xl import MyTransfoXLConfig, MyTr
 dev = torch.device('cuda:0')
 V, M, B, Tp, NB = 1190, 2048, 8, 256, 4
 NEW, RUNS = int(os.environ.get('NEW', 256)), int(os.environ.get('RUNS', 5))
+GROUPS, DIVERSITY = int(os.environ.get('GROUPS', 1)), float(os.environ.get('DIVERSITY', 1.5))
 L = Tp + NEW
 cfg = MyTransfoXLConfig('base', max_length=2048, vocab_size=V, mem_len=M, cutoffs=[])
 model = MyTransfoXLLMHeadModel(cfg, device=dev, seed=77).eval()
 ids = torch.randint(4, V, (B, Tp), generator=torch.Generator().manual_seed(77)).to(dev)
 kw = dict(input_ids=ids, max_length=L, num_beams=NB, early_stopping=True, eos_token_id=V + 1, pad_token_id=0)
+if GROUPS > 1:
+    kw.update(num_beam_groups=GROUPS, diversity_penalty=DIVERSITY)
 
 calls = [0]
 _check = ops.check
@@ -45,6 +54,7 @@ def run(host: bool, **extra):
         os.environ['MXL_BEAM_HOST'] = '1'
     else:
         os.environ.pop('MXL_BEAM_HOST', None)
+    os.environ['MXL_GROUP_BEAM_DEVICE'] = '1'         # (group beam search without a rule takes the device path only when asked to)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     out = model.generate(**{**kw, **extra})
@@ -70,13 +80,14 @@ with torch.no_grad():
     for _ in range(RUNS):
         for host in (False, True):
             times[host].append(run(host)[0])
-    print(f'beam search, C5 decode shape: {B} prompts x {Tp}, num_beams {NB} ({B * NB} rows), {NEW} new tokens, eos never fires; '
+    what = 'beam search' if GROUPS == 1 else f'group beam search ({GROUPS} groups, diversity_penalty {DIVERSITY})'
+    print(f'{what}, C5 decode shape: {B} prompts x {Tp}, num_beams {NB} ({B * NB} rows), {NEW} new tokens, eos never fires; '
           f'device ids == host ids: {same}')
     for host, name in ((False, 'device'), (True, 'host  ')):
         tps = sorted(B * NEW / t for t in times[host])
         print(f'{name}: {statistics.median(tps):9.1f} tok/s median of {RUNS} (min {tps[0]:.1f}, max {tps[-1]:.1f}); '
               f'{statistics.median(times[host]):.3f} s per call; {per_step[host]:.1f} library launches per step, '
-              f'{"3 host reads + 3 uploads + 1 sync per step" if host else "no host read per step, one graph replay"}')
+              f'{f"{3 * GROUPS} host reads + {3 * GROUPS} uploads + {GROUPS} sync per step" if host else "no host read per step, one graph replay"}')
     d, h = sorted(B * NEW / t for t in times[False]), sorted(B * NEW / t for t in times[True])
     gap = statistics.median(d) / statistics.median(h)
     clear = d[0] > h[-1]

@@ -45,6 +45,66 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
     return k;
 }
 
+// the max of `best` over the workgroup, in every thread; sh_part may be rewritten after the caller's next barrier
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long best, unsigned long long* sh_part) {
+    const int tid = threadIdx.x;
+    best = wave_max_u64(best);
+    if ((tid & 63) == 0) sh_part[tid >> 6] = best;
+    __syncthreads();
+    best = sh_part[0];
+#pragma unroll
+    for (int w = 1; w < BEAM_T / 64; w++) best = sh_part[w] > best ? sh_part[w] : best;
+    return best;
+}
+
+// What a step does once thread 0 has walked the candidates of an item (all of this in LDS, a barrier behind it): the added
+// hypotheses sh_add[slot] = source beam (or -1) are copied out before ids moves, ids and the packed rule words follow sh_src in
+// place when `mv`, the chosen tokens sh_tok go to column cur_len, and word 0 of the dead rows (or of every row when `clear`) is zeroed.
+__device__ __forceinline__ void beam_store_and_reorder(long long* ids, int ld_ids, int row0, int nb, int cur_len, long long* hyp_ids,
+                                                       const int* sh_add, const int* sh_src, const int* sh_tok, const int* sh_dead,
+                                                       int mv, int clear, int* words, int n_words, int word_stride) {
+    const int tid = threadIdx.x;
+    // the added hypotheses, before ids moves
+    for (int slot = 0; slot < nb; slot++) {
+        const int src = sh_add[slot];
+        if (src < 0) continue;
+        const long long* from = ids + (size_t)(row0 + src) * ld_ids;
+        long long* to = hyp_ids + (size_t)(row0 + slot) * ld_ids;
+        for (int c = tid; c < cur_len; c += BEAM_T) to[c] = from[c];
+    }
+    __syncthreads();
+
+    if (mv) {
+        int src[BEAM_MAX];
+#pragma unroll
+        for (int j = 0; j < BEAM_MAX; j++) src[j] = j < nb ? sh_src[j] : j;
+        for (int c = tid; c < cur_len; c += BEAM_T) {
+            long long v[BEAM_MAX];
+#pragma unroll
+            for (int j = 0; j < BEAM_MAX; j++)
+                if (j < nb && src[j] != j) v[j] = ids[(size_t)(row0 + src[j]) * ld_ids + c];
+#pragma unroll
+            for (int j = 0; j < BEAM_MAX; j++)
+                if (j < nb && src[j] != j) ids[(size_t)(row0 + j) * ld_ids + c] = v[j];
+        }
+        if (words && tid < n_words) {
+            int* w = words + (size_t)tid * word_stride + row0;
+            int v[BEAM_MAX];
+#pragma unroll
+            for (int j = 0; j < BEAM_MAX; j++)
+                if (j < nb && src[j] != j) v[j] = w[src[j]];
+#pragma unroll
+            for (int j = 0; j < BEAM_MAX; j++)
+                if (j < nb && src[j] != j) w[j] = v[j];
+        }
+    }
+    if (tid < nb) ids[(size_t)(row0 + tid) * ld_ids + cur_len] = sh_tok[tid];
+    if (words && tid == 0) {                                         // word 0 = unfinished; thread 0 moved it above
+        for (int j = 0; j < nb; j++)
+            if (sh_dead[j] || clear) words[row0 + j] = 0;
+    }
+}
+
 __global__ __launch_bounds__(BEAM_T) void beam_step_kernel(const float* logp, int ldl, float* beam_scores, long long* ids, int ld_ids,
                                                            const int* t_dev, int nb, int V, int eos_id, int pad_id,
                                                            float length_penalty, int early_stopping, long long* hyp_ids, int* hyp_len,
@@ -75,12 +135,7 @@ __global__ __launch_bounds__(BEAM_T) void beam_step_kernel(const float* logp, in
                     if (k < prev && k > best) best = k;
                 }
             }
-            best = wave_max_u64(best);
-            if ((tid & 63) == 0) sh_part[tid >> 6] = best;
-            __syncthreads();
-            best = sh_part[0];
-#pragma unroll
-            for (int w = 1; w < BEAM_T / 64; w++) best = sh_part[w] > best ? sh_part[w] : best;
+            best = block_max_u64(best, sh_part);
             if (tid == 0) sh_cand[round] = best;
             prev = best;
             __syncthreads();                                         // sh_part is rewritten by the next round
@@ -151,45 +206,132 @@ __global__ __launch_bounds__(BEAM_T) void beam_step_kernel(const float* logp, in
     }
     __syncthreads();
 
-    // the added hypotheses, before ids moves
-    for (int slot = 0; slot < nb; slot++) {
-        const int src = sh_add[slot];
-        if (src < 0) continue;
-        const long long* from = ids + (size_t)(row0 + src) * ld_ids;
-        long long* to = hyp_ids + (size_t)(row0 + slot) * ld_ids;
-        for (int c = tid; c < cur_len; c += BEAM_T) to[c] = from[c];
+    beam_store_and_reorder(ids, ld_ids, row0, nb, cur_len, hyp_ids, sh_add, sh_src, sh_tok, sh_dead, sh_moved, sh_clear, words, n_words,
+                           word_stride);
+}
+
+// Diverse (group) beam search, HF 4.25.1 `group_beam_search` with `HammingDiversityLogitsProcessor` as generate.group_beam_search
+// states it on the host: the nb rows of an item are ng groups of gs = nb / ng, walked in order inside the item's workgroup, since a
+// group's scores depend on the tokens the earlier groups chose in this step (kept in LDS) and all groups share the item's store.
+//   score    (logp[j][v] - pen * cnt[v]) + beam_scores[j], each operation rounded on its own as the host rounds it; cnt[v] = the live
+//            rows of the earlier groups that chose v in this step.  cnt = 0 or pen = 0 leaves logp + beam_scores bit for bit.
+//   select   the 2 * gs best of the group's gs * V candidates, by score descending, then flat index (j - g0) * V + v ascending
+//   walk     thread 0, _BeamHyps.walk with n = gs over the item's store of capacity nb; the done test takes this group's best
+//            score.  Once the item is done the groups behind are not walked: identity, pad, their scores stay.
+// The tail (copy out, beam_idx, reorder, tokens, dead rows, frozen items) is beam_step_kernel's.
+__global__ __launch_bounds__(BEAM_T) void group_beam_step_kernel(const float* logp, int ldl, float* beam_scores, long long* ids,
+                                                                 int ld_ids, const int* t_dev, int nb, int ng, float pen, int V,
+                                                                 int eos_id, int pad_id, float length_penalty, int early_stopping,
+                                                                 long long* hyp_ids, int* hyp_len, float* hyp_score, int* hyp_n,
+                                                                 int* done, int* n_done, int* beam_idx, int* moved, int* words,
+                                                                 int n_words, int word_stride) {
+    __shared__ unsigned long long sh_part[BEAM_T / 64];
+    __shared__ unsigned long long sh_cand[2 * BEAM_MAX];
+    __shared__ float sh_score[BEAM_MAX], hs[BEAM_MAX];
+    __shared__ int sh_src[BEAM_MAX], sh_tok[BEAM_MAX], sh_dead[BEAM_MAX], sh_add[BEAM_MAX], sh_prev[BEAM_MAX];
+    __shared__ int sh_moved, sh_done, sh_n, sh_nprev;
+    const int b = blockIdx.x, tid = threadIdx.x, row0 = b * nb, gs = nb / ng;
+    const int cur_len = *t_dev + 1;
+    if (cur_len < 1 || cur_len >= ld_ids) return;
+    const bool frozen = done[b] != 0;
+
+    if (tid < nb) {
+        sh_score[tid] = beam_scores[row0 + tid];
+        sh_src[tid] = tid; sh_tok[tid] = pad_id; sh_dead[tid] = 0; sh_add[tid] = -1;
+        hs[tid] = tid < hyp_n[b] ? hyp_score[row0 + tid] : 0.f;
     }
+    if (tid == 0) { sh_moved = 0; sh_done = frozen; sh_n = hyp_n[b]; sh_nprev = 0; }
     __syncthreads();
 
-    if (sh_moved) {
-        int src[BEAM_MAX];
-#pragma unroll
-        for (int j = 0; j < BEAM_MAX; j++) src[j] = j < nb ? sh_src[j] : j;
-        for (int c = tid; c < cur_len; c += BEAM_T) {
-            long long v[BEAM_MAX];
-#pragma unroll
-            for (int j = 0; j < BEAM_MAX; j++)
-                if (j < nb && src[j] != j) v[j] = ids[(size_t)(row0 + src[j]) * ld_ids + c];
-#pragma unroll
-            for (int j = 0; j < BEAM_MAX; j++)
-                if (j < nb && src[j] != j) ids[(size_t)(row0 + j) * ld_ids + c] = v[j];
+    for (int g = 0; g < ng; g++) {
+        if (sh_done) break;                                          // (written before the barrier that ends the last group)
+        const int g0 = g * gs, np = sh_nprev;
+        unsigned long long prev = ~0ull;
+        for (int round = 0; round < 2 * gs; round++) {
+            unsigned long long best = 0;
+            for (int v = tid; v < V; v += BEAM_T) {
+                int c = 0;
+                for (int i = 0; i < np; i++) c += sh_prev[i] == v;
+                const float off = __fmul_rn(pen, (float)c);
+                for (int j = 0; j < gs; j++) {
+                    const float lp = logp[(size_t)(row0 + g0 + j) * ldl + v];
+                    const float s = __fadd_rn(__fsub_rn(lp, off), sh_score[g0 + j]);
+                    const unsigned long long k = beam_key(s, (uint32_t)j * (uint32_t)V + (uint32_t)v);
+                    if (k < prev && k > best) best = k;
+                }
+            }
+            best = block_max_u64(best, sh_part);
+            if (tid == 0) sh_cand[round] = best;
+            prev = best;
+            __syncthreads();                                         // sh_part is rewritten by the next round
         }
-        if (words && tid < n_words) {
-            int* w = words + (size_t)tid * word_stride + row0;
-            int v[BEAM_MAX];
-#pragma unroll
-            for (int j = 0; j < BEAM_MAX; j++)
-                if (j < nb && src[j] != j) v[j] = w[src[j]];
-#pragma unroll
-            for (int j = 0; j < BEAM_MAX; j++)
-                if (j < nb && src[j] != j) w[j] = v[j];
+        if (tid == 0) {
+            int n = sh_n, cnt = 0, mv = sh_moved, npn = np;
+            const float norm = powf((float)cur_len, length_penalty);
+            for (int rank = 0; rank < 2 * gs && cnt < gs; rank++) {
+                const float s = beam_key_score(sh_cand[rank]);
+                const uint32_t idx = beam_key_index(sh_cand[rank]);
+                const int j = (int)(idx / (uint32_t)V), v = (int)(idx - (uint32_t)j * (uint32_t)V);
+                if (j >= gs) continue;                               // (no candidate was left for this round: not reached for V >= 2)
+                if (v == eos_id) {
+                    if (rank >= gs) continue;
+                    const float sc = s / norm;                       // _BeamHyps.add, into the store all groups share
+                    int slot = -1;
+                    if (n < nb) slot = n++;
+                    else {
+                        int worst = 0;
+                        for (int i = 1; i < nb; i++) if (hs[i] < hs[worst]) worst = i;
+                        if (sc > hs[worst]) slot = worst;
+                    }
+                    if (slot >= 0) { hs[slot] = sc; sh_add[slot] = g0 + j; }
+                } else {
+                    const bool dead = s == -INFINITY;
+                    const int r = g0 + cnt;
+                    sh_src[r] = g0 + j;
+                    sh_tok[r] = dead ? pad_id : v;
+                    sh_dead[r] = dead;
+                    sh_score[r] = s;                                 // (every old score of the group is in the keys by now)
+                    mv |= j != cnt;
+                    if (!dead) sh_prev[npn++] = v;                   // a dead row does not count in the Hamming term
+                    cnt++;
+                }
+            }
+            for (; cnt < gs; cnt++) {                                // (not reached: at most gs of 2 * gs candidates are eos)
+                const int r = g0 + cnt;
+                sh_src[r] = r; sh_tok[r] = pad_id; sh_dead[r] = 1; sh_score[r] = -INFINITY;
+            }
+            bool d = false;                                          // _BeamHyps.is_done
+            if (n >= nb) {
+                if (early_stopping) d = true;
+                else {
+                    float worst = hs[0];
+                    for (int i = 1; i < nb; i++) worst = fminf(worst, hs[i]);
+                    d = worst >= beam_key_score(sh_cand[0]) / norm;
+                }
+            }
+            sh_n = n; sh_moved = mv; sh_nprev = npn; sh_done = d;
         }
+        __syncthreads();
     }
-    if (tid < nb) ids[(size_t)(row0 + tid) * ld_ids + cur_len] = sh_tok[tid];
-    if (words && tid == 0) {                                         // word 0 = unfinished; thread 0 moved it above
-        for (int j = 0; j < nb; j++)
-            if (sh_dead[j] || sh_clear) words[row0 + j] = 0;
+
+    if (tid == 0) {
+        if (!frozen) {
+            for (int j = 0; j < nb; j++) {
+                beam_scores[row0 + j] = sh_score[j];
+                if (sh_add[j] >= 0) { hyp_score[row0 + j] = hs[j]; hyp_len[row0 + j] = cur_len; }
+            }
+            hyp_n[b] = sh_n;
+            if (sh_done) {
+                done[b] = 1;
+                atomicAdd(n_done, 1);
+            }
+        }
+        for (int j = 0; j < nb; j++) beam_idx[row0 + j] = row0 + sh_src[j];
+        moved[b] = sh_moved;
     }
+    __syncthreads();
+    beam_store_and_reorder(ids, ld_ids, row0, nb, cur_len, hyp_ids, sh_add, sh_src, sh_tok, sh_dead, sh_moved, sh_done, words, n_words,
+                           word_stride);
 }
 
 // One (rows, row_bytes) buffer, or each of a table of them, follows beam_idx in place, item by item.  grid (column blocks, items,
@@ -235,6 +377,25 @@ extern "C" int mxl_beam_step(const float* logp, int ldl, float* beam_scores, voi
     hipLaunchKernelGGL(beam_step_kernel, dim3(Bs), dim3(BEAM_T), 0, (hipStream_t)stream, logp, ldl, beam_scores, (long long*)ids, ld_ids,
                        t_dev, nb, V, eos_id, pad_id, length_penalty, early_stopping, (long long*)hyp_ids, hyp_len, hyp_score, hyp_n, done,
                        n_done, beam_idx, moved, words, n_words, word_stride);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_group_beam_step(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs,
+                                   int nb, int ng, float diversity_penalty, int V, int eos_id, int pad_id, float length_penalty,
+                                   int early_stopping, void* hyp_ids, int* hyp_len, float* hyp_score, int* hyp_n, int* done, int* n_done,
+                                   int* beam_idx, int* moved, int* words, int n_words, int word_stride, void* stream) {
+    MXL_CHECK_ARG(logp && beam_scores && ids && t_dev && beam_idx && moved);
+    MXL_CHECK_ARG(hyp_ids && hyp_len && hyp_score && hyp_n && done && n_done);
+    MXL_CHECK_ARG(Bs > 0 && nb >= 2 && nb <= BEAM_MAX && ng >= 2 && ng <= nb && nb % ng == 0);
+    MXL_CHECK_ARG(diversity_penalty >= 0.f && diversity_penalty < INFINITY);
+    MXL_CHECK_ARG(V >= 2 && ldl >= V && ld_ids >= 2);
+    MXL_CHECK_ARG((long long)nb * V < (1LL << 31) && (long long)Bs * nb < (1LL << 31));
+    MXL_CHECK_ARG((words == nullptr) == (n_words == 0));
+    MXL_CHECK_ARG(!words || (n_words >= 1 && n_words <= BEAM_T && (long long)word_stride >= (long long)Bs * nb));
+    hipLaunchKernelGGL(group_beam_step_kernel, dim3(Bs), dim3(BEAM_T), 0, (hipStream_t)stream, logp, ldl, beam_scores, (long long*)ids,
+                       ld_ids, t_dev, nb, ng, diversity_penalty, V, eos_id, pad_id, length_penalty, early_stopping, (long long*)hyp_ids,
+                       hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words, n_words, word_stride);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }

@@ -722,11 +722,12 @@ class BeamStore:
         self.beam_idx = torch.zeros(rows, device=dev, dtype=torch.int32)
         self.moved = torch.zeros(Bs, device=dev, dtype=torch.int32)
 
-    def start(self):
-        """an empty store; the first beam of every item starts at score 0, the others at -1e9 (HF beam_search)"""
+    def start(self, ng: int = 1):
+        """an empty store; the first beam of every item -- of every one of its ng groups -- starts at score 0, the others at -1e9
+        (HF beam_search / group_beam_search)"""
         self.ints.zero_()
         self.scores.fill_(-1e9)
-        self.scores.view(self.Bs, self.nb)[:, 0] = 0
+        self.scores.view(self.Bs, self.nb)[:, ::self.nb // ng] = 0
 
     def snapshot(self):
         return self.scores.clone(), self.hyp_ids.clone(), self.hyp_score.clone(), self.ints.clone()
@@ -990,21 +991,26 @@ class XLDecoder:
     # ---------------------------------------------------------------- beam search on the device (beam_search_device below)
     def beam_begin(self, prompt: torch.Tensor, max_length: int, nb: int, eos: int, pad: int, length_penalty: float,
                    early_stopping: bool, use_graph: bool = True, grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None,
-                   keys: Optional[torch.Tensor] = None) -> int:
+                   keys: Optional[torch.Tensor] = None, ng: int = 1, diversity_penalty: float = 0.0) -> int:
         """prompt pass (one row per beam, the rules started as `prefill` starts them, with the stop group (eos, pad, 0) always on:
         its `unfinished` word is how mxl_beam_step retires dead rows and done items) + the scorer's state + (use_graph) capture of
         one beam step; returns the number of `beam_replay_once()` calls before the last selection (`beam_select`).  The snapshot
-        that the warm-up and the capture consume is `begin`'s, joined by the hypothesis store and the running scores."""
+        that the warm-up and the capture consume is `begin`'s, joined by the hypothesis store and the running scores.
+        ng > 1: diverse beam search, the nb beams of an item in ng groups with `diversity_penalty` between them (mxl_group_beam_step
+        in place of mxl_beam_step); both are part of the graph key."""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         if nb < 2 or nb > BEAM_MAX or self.B % nb:
             raise MusicXLError(f'beam search on the device takes 2..{BEAM_MAX} beams and one decoder row per beam')
+        if ng < 1 or nb % ng or not 0.0 <= diversity_penalty < math.inf:
+            raise MusicXLError(f'group beam search on the device takes groups that divide the {nb} beams and a finite diversity_penalty '
+                               '>= 0')
         self.prefill(prompt, None, None, (int(eos), int(pad), 0), grammar, n_bars, in_key, keys)
         if self.beam is None or self.beam.nb != nb:
             self.beam = BeamStore(self.B // nb, nb, self.ids.shape[1], self.eng.dev)
             self.ring_table = ops.beam_table(self.kc + self.vc)
-        self.beam.start()
-        self._beam_args = (int(nb), int(eos), int(pad), float(length_penalty), bool(early_stopping))
+        self.beam.start(ng)
+        self._beam_args = (int(nb), int(eos), int(pad), float(length_penalty), bool(early_stopping), int(ng), float(diversity_penalty))
         self._use_graph = use_graph
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
@@ -1030,14 +1036,18 @@ class XLDecoder:
         return max(steps, 0)
 
     def beam_select(self):
-        """rules mask -> mxl_beam_step: the beams of every item chosen, finished hypotheses stored, ids and the rule words
-        reordered, the chosen tokens at column t + 1"""
+        """rules mask -> mxl_beam_step (mxl_group_beam_step under ng > 1): the beams of every item chosen, finished hypotheses
+        stored, ids and the rule words reordered, the chosen tokens at column t + 1"""
         V, st = self.eng.cfg.vocab_size, self.beam
-        nb, eos, pad, lp, early = self._beam_args
+        nb, eos, pad, lp, early, ng, pen = self._beam_args
         rules = ops.rules_in_force(**self.rules.kwargs())
         ops.rules_mask(self.logp, V, self.t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
-        ops.beam_step(self.logp, V, st.scores, self.ids, self.t_dev, nb, eos, pad, lp, early, st.hyp_ids, st.hyp_len, st.hyp_score,
-                      st.hyp_n, st.done, st.n_done, st.beam_idx, st.moved, words=self.rules.buf, n_words=len(RowRules.WORDS))
+        store = (st.hyp_ids, st.hyp_len, st.hyp_score, st.hyp_n, st.done, st.n_done, st.beam_idx, st.moved)
+        words = dict(words=self.rules.buf, n_words=len(RowRules.WORDS))
+        if ng > 1:
+            ops.group_beam_step(self.logp, V, st.scores, self.ids, self.t_dev, nb, ng, pen, eos, pad, lp, early, *store, **words)
+        else:
+            ops.beam_step(self.logp, V, st.scores, self.ids, self.t_dev, nb, eos, pad, lp, early, *store, **words)
         return rules
 
     def beam_step(self):
@@ -1423,7 +1433,8 @@ def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, 
 def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, early_stopping: bool = True,
                        length_penalty: float = 1.0, num_return_sequences: int = 1, eos_token_id: int = 0,
                        pad_token_id: Optional[int] = None, use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None,
-                       n_bars=None, in_key=None, key=None, return_scores: bool = False):
+                       n_bars=None, in_key=None, key=None, return_scores: bool = False, num_beam_groups: int = 1,
+                       diversity_penalty: float = 0.0):
     """`beam_search` (do_sample=False) with the scorer on the device: per step the rules mask, mxl_beam_step (select, walk, store,
     reorder ids and the rule words), mxl_beam_reorder over the K/V rings, the position advance, the rules advance and the model --
     no host read, captured once under use_graph (XLDecoder.beam_begin / beam_step).  The steps are replayed in chunks of
@@ -1433,7 +1444,8 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     grammar / n_bars / in_key / key: the rules of `XLDecoder.generate`, one value per prompt where they are per row (each prompt's
     is shared by its beams); a barred token is -inf before the running scores are added, the rules' words follow the beams, and a
     row that can only continue from a barred token is dead: it emits pad at score -inf and never returns.  An item that ends with
-    fewer than num_return_sequences hypotheses of finite score raises MusicXLError."""
+    fewer than num_return_sequences hypotheses of finite score raises MusicXLError.
+    num_beam_groups > 1 with diversity_penalty: the same loop over mxl_group_beam_step (group_beam_search_device)."""
     V = dec.eng.cfg.vocab_size
     nb = int(num_beams)
     pad = eos_token_id if pad_token_id is None else pad_token_id
@@ -1441,13 +1453,15 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     keep = int(num_return_sequences)
     if keep > nb:
         raise MusicXLError('num_return_sequences has to be smaller or equal to num_beams')
+    if n_bars is not None and num_beam_groups != 1:
+        raise MusicXLError('n_bars= is not supported under group beam search: the bar count is untested under several groups')
     rows = B0 * nb
     if dec.B != rows or max_length > dec.Tmax:
         raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, beam search needs {rows} x {max_length}')
     stop = (int(eos_token_id), int(pad), 0)
     n = dec.beam_begin(prompt.repeat_interleave(nb, 0).to(dec.eng.dev), max_length, nb, eos_token_id, pad, length_penalty,
                        early_stopping, use_graph, grammar, bar_count_config(n_bars, B0, grammar, stop, nb), in_key,
-                       key_config(in_key, key, B0, V, nb))
+                       key_config(in_key, key, B0, V, nb), int(num_beam_groups), float(diversity_penalty))
     st = dec.beam
     poll, issued, chunk = _AlivePoll(st.n_done, target=B0), 0, max(1, int(stop_chunk))
     while issued < n and not poll.wait(1):
@@ -1481,14 +1495,16 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
 def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 4, num_beam_groups: int = 2,
                       diversity_penalty: float = 0.0, early_stopping: bool = True, length_penalty: float = 1.0,
                       num_return_sequences: int = 1, eos_token_id: int = 0, pad_token_id: Optional[int] = None,
-                      return_scores: bool = False):
+                      return_scores: bool = False, allowed=None):
     """HF 4.25.1 `group_beam_search` (diverse beam search, Vijayakumar et al.) with `BeamSearchScorer(num_beam_groups=...)` and
     `HammingDiversityLogitsProcessor`, as `model.generate(num_beams=, num_beam_groups=, diversity_penalty=)` reaches them from
     the reference's 'beam' strategy (musicnlp/trainer/eval.py:303-317: num_beam_groups set => do_sample False).  One decoder row
     per beam; per step ONE forward for all beams, then the groups in order: group g's log-probabilities are lowered by
     diversity_penalty x (how many beams of the EARLIER groups of the same item chose that token at this step), its 2 x group_size
     best continuations go through the scorer walk (one hypothesis heap and one done flag per item, shared by its groups, as in
-    4.25.1), and its rows follow their beams.  The first beam of every group starts at score 0, the others at -1e9."""
+    4.25.1), and its rows follow their beams.  The first beam of every group starts at score 0, the others at -1e9.
+    allowed: as in `beam_search`, the host reference of the rules under group_beam_search_device: a token it bars is -inf before the
+    Hamming term and the running score are added, and a row that continues at -inf does not count in the Hamming frequency."""
     e, c = dec.eng, dec.eng.cfg
     dev, V = e.dev, c.vocab_size
     nb, ng = num_beams, num_beam_groups
@@ -1511,6 +1527,8 @@ def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int
     ident = torch.arange(rows, device=dev)
     while True:
         logp = dec.beam_logp()                                   # (rows, V), every beam of every group
+        if allowed is not None:
+            logp = logp.masked_fill(~torch.as_tensor(allowed(dec.ids[:, :cur_len])).to(logp.device, torch.bool), float('-inf'))
         current = torch.zeros(rows, dtype=torch.int64, device=dev)
         reorder = ident.clone()
         new_scores = beam_scores.clone()
@@ -1521,7 +1539,10 @@ def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int
             if diversity_penalty and diversity_penalty > 0.0 and g > 0:
                 # HammingDiversityLogitsProcessor: tokens the earlier groups of the same item have just chosen
                 prev = current.view(B0, nb)[:, :g0]
-                freq = torch.zeros(B0, V, device=dev).scatter_add_(1, prev, torch.ones_like(prev, dtype=torch.float32))
+                live = torch.ones_like(prev, dtype=torch.float32)
+                if allowed is not None:
+                    live = torch.isfinite(new_scores.view(B0, nb)[:, :g0]).to(torch.float32)
+                freq = torch.zeros(B0, V, device=dev).scatter_add_(1, prev, live)
                 sc = sc - diversity_penalty * freq.repeat_interleave(gs, 0)
             sc = sc + beam_scores.index_select(0, gidx)[:, None]
             top_s, top_i = sc.view(B0, gs * V).topk(2 * gs, dim=1, largest=True, sorted=True)
@@ -1545,6 +1566,24 @@ def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int
             break
         dec.beam_advance(cur_len)
     return _beam_finalize(hyps, nb, num_return_sequences, dec.ids, cur_len, beam_scores, max_length, eos_token_id, pad, return_scores)
+
+
+def group_beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 4, num_beam_groups: int = 2,
+                             diversity_penalty: float = 0.0, early_stopping: bool = True, length_penalty: float = 1.0,
+                             num_return_sequences: int = 1, eos_token_id: int = 0, pad_token_id: Optional[int] = None,
+                             use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None, in_key=None, key=None,
+                             return_scores: bool = False):
+    """`group_beam_search` with the scorer on the device: `beam_search_device`'s loop -- chunked replay of one captured step, the
+    number of done items read a chunk late, the last selection without a forward, `_beam_finalize` -- over mxl_group_beam_step, which
+    walks the groups of every item in order inside one launch.  dec: an XLDecoder with prompt rows x num_beams rows, num_beams <= 16
+    in num_beam_groups >= 2 groups, 0 <= diversity_penalty < inf (MusicXLError otherwise).  grammar / in_key / key as there (no n_bars: the exact-bar-count promise is untested under a
+    search with several groups); `group_beam_search(..., allowed=)` is the host reference."""
+    nb, ng = int(num_beams), int(num_beam_groups)
+    if ng < 2 or nb % ng != 0:
+        raise ValueError('`num_beams` should be divisible by `num_beam_groups` for group beam search.')      # HF's message
+    return beam_search_device(dec, prompt, max_length, nb, early_stopping, length_penalty, num_return_sequences, eos_token_id,
+                              pad_token_id, use_graph, stop_chunk, grammar, None, in_key, key, return_scores, ng,
+                              float(diversity_penalty or 0.0))
 
 
 def beam_generate(make_decoder, input_ids: torch.Tensor, max_length: int, *, num_beams: int, num_beam_groups: int, do_sample: bool,

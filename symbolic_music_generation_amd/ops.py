@@ -367,6 +367,33 @@ def budget_scan(ids, Tp, grammar, gbar, grem, first_bad):
                                 bud.need_free, bud.need_full, _p(gbar), _p(grem), _p(first_bad), _stream()), 'mxl_budget_scan')
 
 
+def _beam_step_args(name, logp, V, beam_scores, ids, nb, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words,
+                    n_words):
+    """the checks that beam_step and group_beam_step share; returns (rows, items)"""
+    rows = ids.shape[0]
+    _req(logp, torch.float32, f'{name} logp'); _req(beam_scores, torch.float32, f'{name} beam_scores')
+    _req(hyp_score, torch.float32, f'{name} hyp_score')
+    for t, what in ((hyp_len, 'hyp_len'), (hyp_n, 'hyp_n'), (done, 'done'), (n_done, 'n_done'), (beam_idx, 'beam_idx'), (moved, 'moved')):
+        _req(t, torch.int32, f'{name} {what}')
+    if nb < 1 or rows % nb or ids.dtype != torch.int64 or hyp_ids.dtype != torch.int64 or ids.stride(1) != 1 or logp.stride(1) != 1:
+        raise MusicXLError(f'{name}: ids and hyp_ids must be int64 rows of nb per item, logp with unit column stride')
+    Bs = rows // nb
+    if logp.shape[0] != rows or logp.shape[1] < V or beam_scores.numel() != rows or beam_idx.numel() != rows:
+        raise MusicXLError(f'{name}: logp must be ({rows}, >= {V}), beam_scores and beam_idx ({rows},)')
+    if (tuple(hyp_ids.shape) != (Bs, nb, ids.shape[1]) or not hyp_ids.is_contiguous() or ids.stride(0) != ids.shape[1]
+            or any(t.numel() != rows or not t.is_contiguous() for t in (hyp_len, hyp_score))
+            or any(t.numel() != Bs or not t.is_contiguous() for t in (hyp_n, done, moved)) or n_done.numel() != 1):
+        raise MusicXLError(f'{name}: the store must be hyp_ids ({Bs}, {nb}, {ids.shape[1]}), hyp_len / hyp_score ({Bs}, {nb}), '
+                           f'hyp_n / done / moved ({Bs},), n_done (1,), all contiguous, over contiguous ids')
+    if not beam_scores.is_contiguous() or not beam_idx.is_contiguous():
+        raise MusicXLError(f'{name}: beam_scores and beam_idx must be contiguous')
+    if words is not None:
+        _req(words, torch.int32, f'{name} words')
+        if n_words < 1 or words.numel() < n_words * rows or not words.is_contiguous():
+            raise MusicXLError(f'{name}: words must hold n_words x {rows} contiguous int32')
+    return rows, Bs
+
+
 def beam_step(logp, V, beam_scores, ids, t_dev, nb, eos_id, pad_id, length_penalty, early_stopping, hyp_ids, hyp_len, hyp_score, hyp_n,
               done, n_done, beam_idx, moved, words=None, n_words=0):
     """one step of beam search for every item (the nb rows of one prompt), one launch (mxl_beam_step): the 2 * nb best candidates of
@@ -374,31 +401,27 @@ def beam_step(logp, V, beam_scores, ids, t_dev, nb, eos_id, pad_id, length_penal
     finished hypotheses into the store hyp_ids (Bs, nb, ld) int64 / hyp_len / hyp_score (Bs, nb) / hyp_n / done (Bs,) / n_done (1,) --
     and ids (rows, ld) int64 reordered in place along beam_idx (rows,) int32 with the chosen tokens at column t + 1; moved (Bs,) int32.
     words: the packed per-row int32 rule words (RowRules.buf), n_words words of `rows` entries each, which follow beam_idx."""
-    rows = ids.shape[0]
-    _req(logp, torch.float32, 'beam_step logp'); _req(beam_scores, torch.float32, 'beam_step beam_scores')
-    _req(hyp_score, torch.float32, 'beam_step hyp_score')
-    for t, name in ((hyp_len, 'hyp_len'), (hyp_n, 'hyp_n'), (done, 'done'), (n_done, 'n_done'), (beam_idx, 'beam_idx'), (moved, 'moved')):
-        _req(t, torch.int32, f'beam_step {name}')
-    if nb < 1 or rows % nb or ids.dtype != torch.int64 or hyp_ids.dtype != torch.int64 or ids.stride(1) != 1 or logp.stride(1) != 1:
-        raise MusicXLError('beam_step: ids and hyp_ids must be int64 rows of nb per item, logp with unit column stride')
-    Bs = rows // nb
-    if logp.shape[0] != rows or logp.shape[1] < V or beam_scores.numel() != rows or beam_idx.numel() != rows:
-        raise MusicXLError(f'beam_step: logp must be ({rows}, >= {V}), beam_scores and beam_idx ({rows},)')
-    if (tuple(hyp_ids.shape) != (Bs, nb, ids.shape[1]) or not hyp_ids.is_contiguous() or ids.stride(0) != ids.shape[1]
-            or any(t.numel() != rows or not t.is_contiguous() for t in (hyp_len, hyp_score))
-            or any(t.numel() != Bs or not t.is_contiguous() for t in (hyp_n, done, moved)) or n_done.numel() != 1):
-        raise MusicXLError(f'beam_step: the store must be hyp_ids ({Bs}, {nb}, {ids.shape[1]}), hyp_len / hyp_score ({Bs}, {nb}), '
-                           f'hyp_n / done / moved ({Bs},), n_done (1,), all contiguous, over contiguous ids')
-    if not beam_scores.is_contiguous() or not beam_idx.is_contiguous():
-        raise MusicXLError('beam_step: beam_scores and beam_idx must be contiguous')
-    if words is not None:
-        _req(words, torch.int32, 'beam_step words')
-        if n_words < 1 or words.numel() < n_words * rows or not words.is_contiguous():
-            raise MusicXLError(f'beam_step: words must hold n_words x {rows} contiguous int32')
+    rows, Bs = _beam_step_args('beam_step', logp, V, beam_scores, ids, nb, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx,
+                               moved, words, n_words)
     check(lib().mxl_beam_step(_p(logp), logp.stride(0), _p(beam_scores), _p(ids), ids.stride(0), _p(t_dev), Bs, int(nb), int(V),
                               int(eos_id), int(pad_id), float(length_penalty), int(bool(early_stopping)), _p(hyp_ids), _p(hyp_len),
                               _p(hyp_score), _p(hyp_n), _p(done), _p(n_done), _p(beam_idx), _p(moved), _p(words),
                               int(n_words) if words is not None else 0, rows, _stream()), 'mxl_beam_step')
+
+
+def group_beam_step(logp, V, beam_scores, ids, t_dev, nb, ng, diversity_penalty, eos_id, pad_id, length_penalty, early_stopping,
+                    hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words=None, n_words=0):
+    """one step of diverse (group) beam search for every item, one launch (mxl_group_beam_step): `beam_step` for the ng groups of
+    nb / ng rows of every item, walked in order: group g's candidates score (logp - diversity_penalty * cnt) + beam_scores with cnt[v]
+    the live rows of the item's earlier groups that chose v in this step, its 2 * nb / ng best go through the walk over the item's
+    one store of nb slots, and its rows continue inside the group.  The tensors are beam_step's."""
+    rows, Bs = _beam_step_args('group_beam_step', logp, V, beam_scores, ids, nb, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done,
+                               beam_idx, moved, words, n_words)
+    check(lib().mxl_group_beam_step(_p(logp), logp.stride(0), _p(beam_scores), _p(ids), ids.stride(0), _p(t_dev), Bs, int(nb), int(ng),
+                                    float(diversity_penalty), int(V), int(eos_id), int(pad_id), float(length_penalty),
+                                    int(bool(early_stopping)), _p(hyp_ids), _p(hyp_len), _p(hyp_score), _p(hyp_n), _p(done), _p(n_done),
+                                    _p(beam_idx), _p(moved), _p(words), int(n_words) if words is not None else 0, rows, _stream()),
+          'mxl_group_beam_step')
 
 
 def beam_reorder(bufs, nb, beam_idx, moved, table=None):

@@ -7,6 +7,7 @@ int64, `mems` = list of n_layer tensors shaped (mem_len, B, d_model) (time-major
 `prediction_scores` = log-probabilities (B, T, V).
 """
 import json
+import math
 import os
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
@@ -225,8 +226,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
         processor would.  It combines with `num_return_sequences`, padded prompts, `eos_token_id` / `min_length` /
         `max_new_tokens`; the prompts must obey the grammar themselves (MusicXLError otherwise).  That constraint is syntactic;
         `tokenizer.grammar(bar_budget=True)` adds the bar budget, under which every channel of every generated bar is also exactly
-        as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Plain beam search and contrastive search take it too
-        (below); beam-sample and group-beam search take no grammar.
+        as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Plain beam search, group beam search and
+        contrastive search take it too (below); beam-sample takes no grammar.
 
         `n_bars` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): length in bars.  An int, or a
         sequence or tensor of one int per prompt (repeated per prompt under `num_return_sequences`); a negative entry leaves that
@@ -246,7 +247,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         prompts' keys.  The prompt only supplies the key: its own pitches are not judged.  A generated `Key_*` token sets the row's
         key from then on.  The key lives on the device beside the other rules' words and the mask sits in the same sampler launch,
         in the same place.  It needs no `grammar` and combines with everything greedy decoding and sampling take, and with
-        plain beam search and contrastive search (below); beam-sample and group-beam search take no `in_key`.
+        plain beam search, group beam search and contrastive search (below); beam-sample takes no `in_key`.
 
         `melody` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): here is a melody, write the bass
         under it.  A guide is the concatenation of the `<bar> <melody> ... <bass>` spans of its bars, each bar up to and including
@@ -268,6 +269,18 @@ class MyTransfoXLLMHeadModel(EngineModule):
         the running scores are added, and a prompt left with fewer than `num_return_sequences` hypotheses raises MusicXLError.
         `MXL_BEAM_HOST=1` keeps the host scorer (`generate.beam_search`), which takes no rules.
 
+        Group (diverse) beam search (`num_beam_groups` 2.., dividing `num_beams` 2..16, `diversity_penalty`, `do_sample=False` -- the
+        reference's 'beam' strategy runs `num_beams=4, num_beam_groups=2`) can run with its scorer on the device too
+        (`generate.group_beam_search_device`: mxl_group_beam_step, which walks the groups of every prompt in order inside one launch,
+        then mxl_beam_reorder, inside the captured step) and returns what the host path returns.  That path is taken when a rule is
+        given, or with `MXL_GROUP_BEAM_DEVICE=1`; a call without a rule keeps the host scorer until the device path has been measured
+        against it (profiles/group_beam_step.txt).  It takes `grammar` (with or without
+        a bar budget) and `in_key` / `key` with the checks above, given an explicit `eos_token_id=` (without one they stay refused):
+        per-prompt values are shared by the prompt's beams, a barred token is -inf before the diversity penalty and the running
+        scores are added, and a beam that continues at -inf does not count as a choice of its token.  `n_bars`, `melody` and padded
+        prompts stay refused.  `MXL_BEAM_HOST=1` keeps the host scorer here as well (`generate.group_beam_search`, no rules), as
+        does a `diversity_penalty` that is negative or infinite.
+
         Contrastive search (`penalty_alpha > 0`, `top_k` 2..32) runs with its whole step on the device
         (`generate.contrastive_search_device`: mxl_contrastive_topk / mxl_contrastive_step / mxl_ring_slot_broadcast inside the captured
         step; `use_graph` is honoured) and returns what the host path returns.  It takes `grammar` (with or without a bar budget) and
@@ -276,8 +289,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
         a barred candidate is never picked.  `n_bars`, `melody` and padded prompts stay refused.  `top_k > 32` or
         `MXL_CONTRASTIVE_HOST=1` keeps the host-driven loop (`generate.contrastive_search`), which takes no rules here."""
         from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, beam_search_device,
-                               check_grammar_args, contrastive_search, contrastive_search_device, key_config, left_pad_counts,
-                               melody_config, resolve_max_length, stop_config)
+                               check_grammar_args, contrastive_search, contrastive_search_device, group_beam_search_device, key_config,
+                               left_pad_counts, melody_config, resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -301,6 +314,16 @@ class MyTransfoXLLMHeadModel(EngineModule):
         # keeps the host scorer (generate.beam_search), which takes none
         device_beam = (num_beams > 1 and num_beam_groups == 1 and not do_sample and not contrastive and num_beams <= BEAM_MAX
                        and os.environ.get('MXL_BEAM_HOST') != '1')
+        # group beam search likewise (generate.group_beam_search_device), for groups that divide the beams; what the host path
+        # refuses with HF's ValueError goes there to be refused, and a negative or infinite diversity_penalty, which the kernel
+        # refuses, keeps the host path and what it does with it
+        device_group = (num_beam_groups > 1 and not do_sample and 1 < num_beams <= BEAM_MAX and num_beam_groups <= num_beams
+                        and num_beams % num_beam_groups == 0 and 0.0 <= float(diversity_penalty or 0.0) < math.inf
+                        and os.environ.get('MXL_BEAM_HOST') != '1')
+        # this path has not been measured against the host scorer yet (profiles/group_beam_step.txt), so it is taken when a rule
+        # asks for it, or with MXL_GROUP_BEAM_DEVICE=1; a call without a rule keeps the host scorer
+        device_group = device_group and (os.environ.get('MXL_GROUP_BEAM_DEVICE') == '1' or (
+            stop is not None and (grammar is not None or in_key is not None or key is not None)))
         # the rules under beam search need an explicit eos_token_id=, as n_bars and melody do everywhere: a hypothesis ends only by
         # emitting eos, the config's eos (0 = [OMIT]) is no end token of the grammar, and the stop group that the explicit eos turns on
         # is how the device scorer retires rows.  Without one, and for n_bars without the grammar that counts the bars, a beam call
@@ -308,8 +331,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
         # contrastive search likewise: its step runs on the device for 2..32 candidates (generate.contrastive_search_device) and takes
         # the grammar and the key rule under the same condition; MXL_CONTRASTIVE_HOST=1 keeps the host-driven loop, which takes none
         device_contrastive = (contrastive and top_k <= CONTRASTIVE_MAX and os.environ.get('MXL_CONTRASTIVE_HOST') != '1')
-        no_rules = ((contrastive and not (device_contrastive and stop is not None)) or num_beam_groups != 1
-                    or (num_beams > 1 and not (device_beam and stop is not None)))
+        no_rules = ((contrastive and not (device_contrastive and stop is not None))
+                    or ((num_beam_groups != 1 or num_beams > 1) and not ((device_beam or device_group) and stop is not None)))
         if n_pad is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
             raise MusicXLError('padded prompts (attention_mask with zeros) are supported for greedy decoding and sampling only, not '
                                'for beam, group-beam or contrastive search')
@@ -319,7 +342,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         if grammar is not None and no_rules:
             raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
-        if n_bars is not None and (no_rules or contrastive or (num_beams > 1 and grammar is None)):
+        if n_bars is not None and (no_rules or contrastive or num_beam_groups != 1 or (num_beams > 1 and grammar is None)):
             raise MusicXLError('n_bars= is supported for greedy decoding and sampling only, not for beam, group-beam or '
                                'contrastive search')
         if (in_key is not None or key is not None) and no_rules:
@@ -342,6 +365,11 @@ class MyTransfoXLLMHeadModel(EngineModule):
             return beam_search_device(dec, input_ids, max_length, num_beams, bool(early_stopping), length_penalty,
                                       num_return_sequences, eos_b, pad_b, use_graph=use_graph, grammar=grammar, n_bars=n_bars_arg,
                                       in_key=in_key, key=key)
+        if device_group:
+            dec = XLDecoder(self.engine, input_ids.shape[0] * num_beams, max_length, seed=seed)
+            return group_beam_search_device(dec, input_ids, max_length, num_beams, num_beam_groups, diversity_penalty or 0.0,
+                                            bool(early_stopping), length_penalty, num_return_sequences, eos_b, pad_b,
+                                            use_graph=use_graph, grammar=grammar, in_key=in_key, key=key)
         if num_beam_groups != 1 or num_beams > 1:
             return beam_generate(lambda rows: XLDecoder(self.engine, rows, max_length, seed=seed), input_ids, max_length,
                                  num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample,
