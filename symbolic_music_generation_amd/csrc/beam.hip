@@ -1,14 +1,21 @@
 // Beam search on the device (HF 4.25.1 `beam_search` + `BeamSearchScorer.process`, as generate.beam_search / _BeamHyps state them on
 // the host): one launch per decode step that selects, walks, stores and reorders, and one that makes the K/V rings follow their beams.
 //
-// An item is the nb decoder rows of one prompt, rows b * nb .. b * nb + nb - 1.  One workgroup per item:
-//   select   the 2 * nb best of the nb * V candidates logp[r][v] + beam_scores[r], ordered by score descending, then by flat index
-//            j * V + v ascending.  2 * nb rounds of a workgroup arg-max over the keys that come strictly after the previous round's
-//            key: score and index are packed into one 64-bit word whose unsigned order is that order, so a round is one max
-//            reduction, exact for any V, with no marking and no sort.  -inf takes part like any number and sorts last.
-//   walk     thread 0, over a handful of scalars in LDS: an eos among the first nb ranks joins the item's hypothesis store (a free
-//            slot, else it replaces the worst entry if it beats it), an eos behind them is skipped, the first nb other candidates
-//            continue; then the done test, both early_stopping arms.  A done item is frozen: identity, pad tokens, nothing else moves.
+// An item is the nb decoder rows of one prompt, rows b * nb .. b * nb + nb - 1, in ng groups of gs = nb / ng.  Plain beam search is
+// ng = 1; diverse (group) beam search, HF 4.25.1 `group_beam_search` with `HammingDiversityLogitsProcessor` as
+// generate.group_beam_search states it on the host, is ng >= 2 with a penalty `pen`.  Both run beam_step_kernel, one workgroup per
+// item, group after group:
+//   score    (logp[j][v] - pen * cnt[v]) + beam_scores[j], each operation rounded on its own as the host rounds it; cnt[v] = the live
+//            rows of the earlier groups that chose v in this step.  cnt = 0 or pen = 0 leaves logp + beam_scores bit for bit, which
+//            is every score of plain beam search.
+//   select   the 2 * gs best of the group's gs * V candidates, ordered by score descending, then by flat index (j - g0) * V + v
+//            ascending.  2 * gs rounds of a workgroup arg-max over the keys that come strictly after the previous round's key: score
+//            and index are packed into one 64-bit word whose unsigned order is that order, so a round is one max reduction, exact
+//            for any V, with no marking and no sort.  -inf takes part like any number and sorts last.
+//   walk     thread 0, over a handful of scalars in LDS, _BeamHyps.walk with n = gs over the item's store of capacity nb: an eos
+//            among the first gs ranks joins the store (a free slot, else it replaces the worst entry if it beats it), an eos behind
+//            them is skipped, the first gs other candidates continue; then the done test with this group's best score, both
+//            early_stopping arms.  A done item is frozen: identity, pad tokens, nothing else moves.
 //   copy     the added hypotheses ids[src][:cur_len] -> the store, by the whole workgroup, before anything in ids moves
 //   reorder  ids rows in place: a thread owns columns, reads the nb sources of a column into registers, then writes them, so a swap
 //            needs no second buffer; the chosen tokens go to column cur_len.  The packed per-row rule words follow the same way.
@@ -105,134 +112,22 @@ __device__ __forceinline__ void beam_store_and_reorder(long long* ids, int ld_id
     }
 }
 
+// One beam step of every item, for plain (ng = 1, pen = 0) and diverse beam search alike: the groups of an item are walked in order
+// inside its workgroup, since a group's scores depend on the tokens the earlier groups chose in this step (sh_prev) and all groups
+// share the item's store.  Once the item is done the groups behind are not walked: identity, pad, their scores stay.
 __global__ __launch_bounds__(BEAM_T) void beam_step_kernel(const float* logp, int ldl, float* beam_scores, long long* ids, int ld_ids,
-                                                           const int* t_dev, int nb, int V, int eos_id, int pad_id,
+                                                           const int* t_dev, int nb, int ng, float pen, int V, int eos_id, int pad_id,
                                                            float length_penalty, int early_stopping, long long* hyp_ids, int* hyp_len,
                                                            float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx,
                                                            int* moved, int* words, int n_words, int word_stride) {
     __shared__ unsigned long long sh_part[BEAM_T / 64];
     __shared__ unsigned long long sh_cand[2 * BEAM_MAX];
     __shared__ float sh_score[BEAM_MAX], hs[BEAM_MAX];               // hs: the scores of the item's store (thread 0)
-    __shared__ int sh_src[BEAM_MAX], sh_tok[BEAM_MAX], sh_dead[BEAM_MAX], sh_add[BEAM_MAX];
-    __shared__ int sh_moved, sh_clear;
-    const int b = blockIdx.x, tid = threadIdx.x, row0 = b * nb;
-    const int cur_len = *t_dev + 1;                                  // columns 0..cur_len-1 hold the rows; the new token goes to cur_len
-    if (cur_len < 1 || cur_len >= ld_ids) return;                    // (the host keeps max_length within the buffer)
-    const bool frozen = done[b] != 0;
-
-    if (!frozen) {
-        if (tid < nb) sh_score[tid] = beam_scores[row0 + tid];
-        __syncthreads();
-        unsigned long long prev = ~0ull;
-        for (int round = 0; round < 2 * nb; round++) {
-            unsigned long long best = 0;
-            for (int j = 0; j < nb; j++) {
-                const float* row = logp + (size_t)(row0 + j) * ldl;
-                const float bs = sh_score[j];
-                const uint32_t base = (uint32_t)j * (uint32_t)V;
-                for (int v = tid; v < V; v += BEAM_T) {
-                    const unsigned long long k = beam_key(row[v] + bs, base + v);
-                    if (k < prev && k > best) best = k;
-                }
-            }
-            best = block_max_u64(best, sh_part);
-            if (tid == 0) sh_cand[round] = best;
-            prev = best;
-            __syncthreads();                                         // sh_part is rewritten by the next round
-        }
-    }
-
-    if (tid == 0) {
-        int mv = 0;
-        if (frozen) {
-            for (int j = 0; j < nb; j++) { sh_src[j] = j; sh_tok[j] = pad_id; sh_dead[j] = 0; sh_add[j] = -1; }
-            sh_clear = 1;
-        } else {
-            int n = hyp_n[b], cnt = 0;
-            for (int j = 0; j < nb; j++) { hs[j] = j < n ? hyp_score[row0 + j] : 0.f; sh_add[j] = -1; }
-            const float norm = powf((float)cur_len, length_penalty);
-            for (int rank = 0; rank < 2 * nb && cnt < nb; rank++) {
-                const float s = beam_key_score(sh_cand[rank]);
-                const uint32_t idx = beam_key_index(sh_cand[rank]);
-                const int j = (int)(idx / (uint32_t)V), v = (int)(idx - (uint32_t)j * (uint32_t)V);
-                if (j >= nb) continue;                               // (no candidate was left for this round: not reached for V >= 2)
-                if (v == eos_id) {
-                    if (rank >= nb) continue;
-                    const float sc = s / norm;                       // _BeamHyps.add
-                    int slot = -1;
-                    if (n < nb) slot = n++;
-                    else {
-                        int worst = 0;
-                        for (int i = 1; i < nb; i++) if (hs[i] < hs[worst]) worst = i;
-                        if (sc > hs[worst]) slot = worst;
-                    }
-                    if (slot >= 0) { hs[slot] = sc; sh_add[slot] = j; }
-                } else {
-                    const bool dead = s == -INFINITY;
-                    sh_src[cnt] = j;
-                    sh_tok[cnt] = dead ? pad_id : v;
-                    sh_dead[cnt] = dead;
-                    sh_score[cnt] = s;                               // (every old score is in the keys by now)
-                    mv |= j != cnt;
-                    cnt++;
-                }
-            }
-            for (; cnt < nb; cnt++) {                                // (not reached: at most nb of 2 * nb candidates are eos)
-                sh_src[cnt] = cnt; sh_tok[cnt] = pad_id; sh_dead[cnt] = 1; sh_score[cnt] = -INFINITY;
-            }
-            bool d = false;                                          // _BeamHyps.is_done
-            if (n >= nb) {
-                if (early_stopping) d = true;
-                else {
-                    float worst = hs[0];
-                    for (int i = 1; i < nb; i++) worst = fminf(worst, hs[i]);
-                    d = worst >= beam_key_score(sh_cand[0]) / norm;
-                }
-            }
-            for (int j = 0; j < nb; j++) {
-                beam_scores[row0 + j] = sh_score[j];
-                if (sh_add[j] >= 0) { hyp_score[row0 + j] = hs[j]; hyp_len[row0 + j] = cur_len; }
-            }
-            hyp_n[b] = n;
-            if (d) {
-                done[b] = 1;
-                atomicAdd(n_done, 1);
-            }
-            sh_clear = d;
-        }
-        for (int j = 0; j < nb; j++) beam_idx[row0 + j] = row0 + sh_src[j];
-        moved[b] = mv;
-        sh_moved = mv;
-    }
-    __syncthreads();
-
-    beam_store_and_reorder(ids, ld_ids, row0, nb, cur_len, hyp_ids, sh_add, sh_src, sh_tok, sh_dead, sh_moved, sh_clear, words, n_words,
-                           word_stride);
-}
-
-// Diverse (group) beam search, HF 4.25.1 `group_beam_search` with `HammingDiversityLogitsProcessor` as generate.group_beam_search
-// states it on the host: the nb rows of an item are ng groups of gs = nb / ng, walked in order inside the item's workgroup, since a
-// group's scores depend on the tokens the earlier groups chose in this step (kept in LDS) and all groups share the item's store.
-//   score    (logp[j][v] - pen * cnt[v]) + beam_scores[j], each operation rounded on its own as the host rounds it; cnt[v] = the live
-//            rows of the earlier groups that chose v in this step.  cnt = 0 or pen = 0 leaves logp + beam_scores bit for bit.
-//   select   the 2 * gs best of the group's gs * V candidates, by score descending, then flat index (j - g0) * V + v ascending
-//   walk     thread 0, _BeamHyps.walk with n = gs over the item's store of capacity nb; the done test takes this group's best
-//            score.  Once the item is done the groups behind are not walked: identity, pad, their scores stay.
-// The tail (copy out, beam_idx, reorder, tokens, dead rows, frozen items) is beam_step_kernel's.
-__global__ __launch_bounds__(BEAM_T) void group_beam_step_kernel(const float* logp, int ldl, float* beam_scores, long long* ids,
-                                                                 int ld_ids, const int* t_dev, int nb, int ng, float pen, int V,
-                                                                 int eos_id, int pad_id, float length_penalty, int early_stopping,
-                                                                 long long* hyp_ids, int* hyp_len, float* hyp_score, int* hyp_n,
-                                                                 int* done, int* n_done, int* beam_idx, int* moved, int* words,
-                                                                 int n_words, int word_stride) {
-    __shared__ unsigned long long sh_part[BEAM_T / 64];
-    __shared__ unsigned long long sh_cand[2 * BEAM_MAX];
-    __shared__ float sh_score[BEAM_MAX], hs[BEAM_MAX];
     __shared__ int sh_src[BEAM_MAX], sh_tok[BEAM_MAX], sh_dead[BEAM_MAX], sh_add[BEAM_MAX], sh_prev[BEAM_MAX];
     __shared__ int sh_moved, sh_done, sh_n, sh_nprev;
     const int b = blockIdx.x, tid = threadIdx.x, row0 = b * nb, gs = nb / ng;
-    const int cur_len = *t_dev + 1;
-    if (cur_len < 1 || cur_len >= ld_ids) return;
+    const int cur_len = *t_dev + 1;                                  // columns 0..cur_len-1 hold the rows; the new token goes to cur_len
+    if (cur_len < 1 || cur_len >= ld_ids) return;                    // (the host keeps max_length within the buffer)
     const bool frozen = done[b] != 0;
 
     if (tid < nb) {
@@ -250,7 +145,7 @@ __global__ __launch_bounds__(BEAM_T) void group_beam_step_kernel(const float* lo
         for (int round = 0; round < 2 * gs; round++) {
             unsigned long long best = 0;
             for (int v = tid; v < V; v += BEAM_T) {
-                int c = 0;
+                int c = 0;                                           // (np = 0, no earlier group chose a token: off = +0, logp stays)
                 for (int i = 0; i < np; i++) c += sh_prev[i] == v;
                 const float off = __fmul_rn(pen, (float)c);
                 for (int j = 0; j < gs; j++) {
@@ -364,40 +259,43 @@ __global__ __launch_bounds__(BEAM_T) void beam_reorder_kernel(char* buf, char* c
 
 }  // namespace
 
-extern "C" int mxl_beam_step(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs, int nb,
-                             int V, int eos_id, int pad_id, float length_penalty, int early_stopping, void* hyp_ids, int* hyp_len,
-                             float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved, int* words, int n_words,
-                             int word_stride, void* stream) {
+// the argument checks both entries share, and the launch; nb, ng and pen are in the entry's own domain by now
+static int beam_step_launch(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs, int nb,
+                            int ng, float pen, int V, int eos_id, int pad_id, float length_penalty, int early_stopping, void* hyp_ids,
+                            int* hyp_len, float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved, int* words,
+                            int n_words, int word_stride, void* stream) {
     MXL_CHECK_ARG(logp && beam_scores && ids && t_dev && beam_idx && moved);
     MXL_CHECK_ARG(hyp_ids && hyp_len && hyp_score && hyp_n && done && n_done);
-    MXL_CHECK_ARG(Bs > 0 && nb >= 1 && nb <= BEAM_MAX && V >= 2 && ldl >= V && ld_ids >= 2);
+    MXL_CHECK_ARG(Bs > 0 && nb <= BEAM_MAX && V >= 2 && ldl >= V && ld_ids >= 2);
     MXL_CHECK_ARG((long long)nb * V < (1LL << 31) && (long long)Bs * nb < (1LL << 31));
     MXL_CHECK_ARG((words == nullptr) == (n_words == 0));
     MXL_CHECK_ARG(!words || (n_words >= 1 && n_words <= BEAM_T && (long long)word_stride >= (long long)Bs * nb));
     hipLaunchKernelGGL(beam_step_kernel, dim3(Bs), dim3(BEAM_T), 0, (hipStream_t)stream, logp, ldl, beam_scores, (long long*)ids, ld_ids,
-                       t_dev, nb, V, eos_id, pad_id, length_penalty, early_stopping, (long long*)hyp_ids, hyp_len, hyp_score, hyp_n, done,
-                       n_done, beam_idx, moved, words, n_words, word_stride);
+                       t_dev, nb, ng, pen, V, eos_id, pad_id, length_penalty, early_stopping, (long long*)hyp_ids, hyp_len, hyp_score,
+                       hyp_n, done, n_done, beam_idx, moved, words, n_words, word_stride);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
+}
+
+extern "C" int mxl_beam_step(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs, int nb,
+                             int V, int eos_id, int pad_id, float length_penalty, int early_stopping, void* hyp_ids, int* hyp_len,
+                             float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved, int* words, int n_words,
+                             int word_stride, void* stream) {
+    MXL_CHECK_ARG(nb >= 1);
+    return beam_step_launch(logp, ldl, beam_scores, ids, ld_ids, t_dev, Bs, nb, 1, 0.f, V, eos_id, pad_id, length_penalty,
+                            early_stopping, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words, n_words,
+                            word_stride, stream);
 }
 
 extern "C" int mxl_group_beam_step(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs,
                                    int nb, int ng, float diversity_penalty, int V, int eos_id, int pad_id, float length_penalty,
                                    int early_stopping, void* hyp_ids, int* hyp_len, float* hyp_score, int* hyp_n, int* done, int* n_done,
                                    int* beam_idx, int* moved, int* words, int n_words, int word_stride, void* stream) {
-    MXL_CHECK_ARG(logp && beam_scores && ids && t_dev && beam_idx && moved);
-    MXL_CHECK_ARG(hyp_ids && hyp_len && hyp_score && hyp_n && done && n_done);
-    MXL_CHECK_ARG(Bs > 0 && nb >= 2 && nb <= BEAM_MAX && ng >= 2 && ng <= nb && nb % ng == 0);
+    MXL_CHECK_ARG(nb >= 2 && ng >= 2 && ng <= nb && nb % ng == 0);
     MXL_CHECK_ARG(diversity_penalty >= 0.f && diversity_penalty < INFINITY);
-    MXL_CHECK_ARG(V >= 2 && ldl >= V && ld_ids >= 2);
-    MXL_CHECK_ARG((long long)nb * V < (1LL << 31) && (long long)Bs * nb < (1LL << 31));
-    MXL_CHECK_ARG((words == nullptr) == (n_words == 0));
-    MXL_CHECK_ARG(!words || (n_words >= 1 && n_words <= BEAM_T && (long long)word_stride >= (long long)Bs * nb));
-    hipLaunchKernelGGL(group_beam_step_kernel, dim3(Bs), dim3(BEAM_T), 0, (hipStream_t)stream, logp, ldl, beam_scores, (long long*)ids,
-                       ld_ids, t_dev, nb, ng, diversity_penalty, V, eos_id, pad_id, length_penalty, early_stopping, (long long*)hyp_ids,
-                       hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words, n_words, word_stride);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
+    return beam_step_launch(logp, ldl, beam_scores, ids, ld_ids, t_dev, Bs, nb, ng, diversity_penalty, V, eos_id, pad_id, length_penalty,
+                            early_stopping, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words, n_words,
+                            word_stride, stream);
 }
 
 extern "C" int mxl_beam_reorder(void* buf, const void* table, int n_bufs, int Bs, int nb, long long row_bytes, const int* beam_idx,

@@ -631,16 +631,19 @@ class _AlivePoll:
 
 
 def run_until_finished(decoders, n: int, chunk: int = STOP_CHUNK) -> list:
-    """Early exit without a per-step sync.  decoders: [(decoder, stream or None)] after `begin(..., stop=...)`; each one replays
-    up to n steps in chunks of `chunk` on its stream, its live-row count is copied back after the prompt pass and after every
-    chunk, and chunk i + 2 is enqueued only once chunk i's count has been read: a decoder stops when that count is 0.  At most two
-    chunks are in flight, and the steps beyond the last live one skip the ring attention.  The count after the prompt pass is
-    waited for, so a batch whose first tokens are all eos replays nothing.  Returns the steps issued per decoder."""
+    """Early exit without a per-step sync.  decoders: [(decoder, stream or None)] after a `begin` that stops: `begin(...,
+    stop=...)`, `beam_begin` or `contrastive_begin`.  A decoder names the device counter it is finished by and that counter's target
+    in `finished_by` -- XLDecoder's three begins set it: the live rows at 0, the done items of a beam search at their number, the
+    finished sequences of a contrastive search at theirs; a decoder without the attribute is finished by `alive` at 0.  Each one
+    replays up to n steps in chunks of `chunk` on its stream, the counter is copied back after the prompt pass and after every
+    chunk, and chunk i + 2 is enqueued only once chunk i's count has been read: a decoder stops when that count is the target.  At
+    most two chunks are in flight, and the steps beyond the last live one skip the ring attention.  The count after the prompt pass
+    is waited for, so a batch whose first tokens are all eos replays nothing.  Returns the steps issued per decoder."""
     chunk = max(1, int(chunk))
     polls = []
     for dec, s in decoders:
         with (torch.cuda.stream(s) if s is not None else nullcontext()):
-            p = _AlivePoll(dec.alive)
+            p = _AlivePoll(*getattr(dec, 'finished_by', (dec.alive, 0)))
             p.mark()
         polls.append(p)
     issued = [0] * len(decoders)
@@ -717,10 +720,14 @@ class BeamStore:
         self.hyp_ids = torch.zeros(Bs, nb, ld_ids, device=dev, dtype=torch.int64)
         self.hyp_score = torch.zeros(Bs, nb, device=dev, dtype=torch.float32)
         self.ints = torch.zeros(rows + 2 * Bs + 1, device=dev, dtype=torch.int32)
-        self.hyp_len = self.ints[:rows].view(Bs, nb)
-        self.hyp_n, self.done, self.n_done = self.ints[rows:rows + Bs], self.ints[rows + Bs:rows + 2 * Bs], self.ints[rows + 2 * Bs:]
+        self.hyp_len, self.hyp_n, self.done, self.n_done = self._words(self.ints)
         self.beam_idx = torch.zeros(rows, device=dev, dtype=torch.int32)
         self.moved = torch.zeros(Bs, device=dev, dtype=torch.int32)
+
+    def _words(self, ints: torch.Tensor) -> tuple:
+        """hyp_len, hyp_n, done, n_done in the word buffer, or in a copy of it"""
+        Bs, rows = self.Bs, self.Bs * self.nb
+        return ints[:rows].view(Bs, self.nb), ints[rows:rows + Bs], ints[rows + Bs:rows + 2 * Bs], ints[rows + 2 * Bs:]
 
     def start(self, ng: int = 1):
         """an empty store; the first beam of every item -- of every one of its ng groups -- starts at score 0, the others at -1e9
@@ -729,12 +736,10 @@ class BeamStore:
         self.scores.fill_(-1e9)
         self.scores.view(self.Bs, self.nb)[:, ::self.nb // ng] = 0
 
-    def snapshot(self):
-        return self.scores.clone(), self.hyp_ids.clone(), self.hyp_score.clone(), self.ints.clone()
-
-    def restore(self, saved):
-        for t, v in zip((self.scores, self.hyp_ids, self.hyp_score, self.ints), saved):
-            t.copy_(v)
+    def read(self) -> tuple:
+        """the host's copy once the steps have run: hyp_len, hyp_n, done and hyp_score as lists, scores as a tensor"""
+        hyp_len, hyp_n, done, _ = self._words(self.ints.cpu())
+        return hyp_len.tolist(), hyp_n.tolist(), done.tolist(), self.hyp_score.cpu().tolist(), self.scores.cpu()
 
 
 class ContrastiveStore:
@@ -994,8 +999,8 @@ class XLDecoder:
                    keys: Optional[torch.Tensor] = None, ng: int = 1, diversity_penalty: float = 0.0) -> int:
         """prompt pass (one row per beam, the rules started as `prefill` starts them, with the stop group (eos, pad, 0) always on:
         its `unfinished` word is how mxl_beam_step retires dead rows and done items) + the scorer's state + (use_graph) capture of
-        one beam step; returns the number of `beam_replay_once()` calls before the last selection (`beam_select`).  The snapshot
-        that the warm-up and the capture consume is `begin`'s, joined by the hypothesis store and the running scores.
+        one beam step (`_capture`; the hypothesis store, the running scores and the log-probabilities are this step's own state);
+        returns the number of `replay_once()` calls before the last selection (`beam_select`).
         ng > 1: diverse beam search, the nb beams of an item in ng groups with `diversity_penalty` between them (mxl_group_beam_step
         in place of mxl_beam_step); both are part of the graph key."""
         if max_length > self.Tmax:
@@ -1011,28 +1016,12 @@ class XLDecoder:
             self.ring_table = ops.beam_table(self.kc + self.vc)
         self.beam.start(ng)
         self._beam_args = (int(nb), int(eos), int(pad), float(length_penalty), bool(early_stopping), int(ng), float(diversity_penalty))
-        self._use_graph = use_graph
+        self._use_graph, self._step, self.finished_by = use_graph, ('beam_step',), (self.beam.n_done, self.beam.Bs)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
             key = ('beam',) + self._beam_args + (None if self.trace is None else self.trace.data_ptr(),) + self.rules.graph_key(self.eng.dev)
-            if self.graph is None or self._graph_key != key:
-                state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(), [k.clone() for k in self.kc + self.vc],
-                         self.rules.snapshot(), self.beam.snapshot(), self.logp.clone())
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self.beam_step()
-                torch.cuda.current_stream().wait_stream(s)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    self.beam_step()
-                self._graph_key = key
-                self.t_dev.copy_(state[0]); self.rng.copy_(state[1]); self.ids.copy_(state[2])
-                for a, b in zip(self.kc + self.vc, state[3]):
-                    a.copy_(b)
-                self.rules.restore(state[4])
-                self.beam.restore(state[5])
-                self.logp.copy_(state[6])             # (the step starts from the log-probabilities the last one left)
+            st = self.beam               # (logp: the step starts from the log-probabilities the last one left)
+            self._capture(key, (st.scores, st.hyp_ids, st.hyp_score, st.ints, self.logp))
         return max(steps, 0)
 
     def beam_select(self):
@@ -1061,20 +1050,14 @@ class XLDecoder:
             ops.rules_advance(self.ids, self.t_dev, **rules)
         self._forward_token()
 
-    def beam_replay_once(self):
-        if self._use_graph:
-            self.graph.replay()
-        else:
-            self.beam_step()
-
     # ---------------------------------------------------------------- contrastive search on the device (contrastive_search_device)
     def contrastive_begin(self, prompt: torch.Tensor, max_length: int, K: int, alpha: float, eos: Optional[int], pad: int,
                           use_graph: bool = True, grammar=None, in_key=None, keys: Optional[torch.Tensor] = None) -> int:
         """prompt pass (one row per candidate: the K rows of a sequence hold the same prompt; the rules started as `prefill` starts
         them, with the stop group (eos, pad, 0) always on -- eos None: -1, never emitted) + the store + (use_graph) capture of one
-        contrastive step + the first token, chosen by one step run here; returns the number of `contrastive_replay_once()` calls that
-        complete the generation to max_length.  Graph key, snapshot and restore around the warm-up and the capture are beam_begin's;
-        the store's words join the snapshot (its context rows need none: a step writes position t and reads those below it)."""
+        contrastive step (`_capture`) + the first token, chosen by one step run here; returns the number of `replay_once()` calls that
+        complete the generation to max_length.  The store's words and the log-probabilities are this step's own state (its context
+        rows need no snapshot: a step writes position t and reads those below it)."""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         if K < 2 or K > CONTRASTIVE_MAX or self.B % K:
@@ -1087,29 +1070,12 @@ class XLDecoder:
             self.ring_table = ops.beam_table(self.kc + self.vc)
         self.cs.start(self.eng._last.h[c.n_layer & 1].view(self.B, Tp, c.d_model)[::K])
         self._cs_args = (int(K), float(alpha), self.rules.stop[0], int(pad))
-        self._use_graph = use_graph
+        self._use_graph, self._step, self.finished_by = use_graph, ('contrastive_step',), (self.cs.n_done, self.cs.B0)
         steps = max_length - Tp - 1
         if steps > 0 and use_graph:
             key = (('contrastive',) + self._cs_args + (None if self.trace is None else self.trace.data_ptr(),)
                    + self.rules.graph_key(self.eng.dev))
-            if self.graph is None or self._graph_key != key:
-                state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(), [k.clone() for k in self.kc + self.vc],
-                         self.rules.snapshot(), self.cs.ints.clone(), self.logp.clone())
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self.contrastive_step()
-                torch.cuda.current_stream().wait_stream(s)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    self.contrastive_step()
-                self._graph_key = key
-                self.t_dev.copy_(state[0]); self.rng.copy_(state[1]); self.ids.copy_(state[2])
-                for a, b in zip(self.kc + self.vc, state[3]):
-                    a.copy_(b)
-                self.rules.restore(state[4])
-                self.cs.ints.copy_(state[5])
-                self.logp.copy_(state[6])             # (the step starts from the log-probabilities the last one left)
+            self._capture(key, (self.cs.ints, self.logp))
         self.contrastive_step()                       # the first token: column Tp
         return max(steps, 0)
 
@@ -1135,12 +1101,6 @@ class XLDecoder:
             ops.rules_advance(self.ids, self.t_dev, **rules)
         ops.ring_slot_broadcast(self.kc + self.vc, K, self.t_dev, cs.sel, table=self.ring_table)
 
-    def contrastive_replay_once(self):
-        if self._use_graph:
-            self.graph.replay()
-        else:
-            self.contrastive_step()
-
     def _trace(self):
         if self.trace is not None:
             self.trace.index_copy_(1, self.t_dev.to(torch.int64), self.logp.unsqueeze(1))
@@ -1163,8 +1123,7 @@ class XLDecoder:
         and a later generation with another guide that fits the buffer replays the same graph"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
-        self._sampling = sampling
-        self._use_graph = use_graph
+        self._use_graph, self._step, self.finished_by = use_graph, ('step', sampling), (self.alive, 0)
         self.prefill(prompt, sampling, n_pad, stop, grammar, n_bars, in_key, keys, melody)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
@@ -1172,35 +1131,43 @@ class XLDecoder:
             # itself is written by the captured launches): a graph captured without a trace would replay without writing one
             key = (tuple(sorted(sampling.items())), self.fused_sampler,
                    None if self.trace is None else self.trace.data_ptr()) + self.rules.graph_key(self.eng.dev)
-            if self.graph is None or self._graph_key != key:
-                # warm-up on a side stream (first launches set function attributes), then capture one step
-                state = (self.t_dev.clone(), self.rng.clone(), self.ids.clone(),
-                         [k.clone() for k in self.kc], [v.clone() for v in self.vc], self.h[0].clone(), self.rules.snapshot())
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self.step(sampling)
-                torch.cuda.current_stream().wait_stream(s)
-                self.graph = torch.cuda.CUDAGraph()       # hipGraph on ROCm
-                with torch.cuda.graph(self.graph):
-                    self.step(sampling)
-                self._graph_key = key
-                # restore the state the two extra steps consumed
-                self.t_dev.copy_(state[0]); self.rng.copy_(state[1]); self.ids.copy_(state[2])
-                for a, b in zip(self.kc, state[3]):
-                    a.copy_(b)
-                for a, b in zip(self.vc, state[4]):
-                    a.copy_(b)
-                self.h[0].copy_(state[5])         # (short chain: the next step's embedding row is step state too)
-                self.rules.restore(state[6])
+            self._capture(key, (self.h[0],))      # (short chain: the next step's embedding row is step state too)
         return max(steps, 0)
 
+    def _step_once(self):
+        """the step of the last begin: `_step` = (its method's name, its arguments).  The bound method itself, kept on the decoder,
+        would tie it into a reference cycle; a decoder then dies in the cycle collector, which may run inside another decoder's
+        capture, where freeing a graph and device memory aborts the process"""
+        getattr(self, self._step[0])(*self._step[1:])
+
+    def _capture(self, key: tuple, extra: tuple):
+        """one step captured in `graph` under `key`, unless the graph at hand was captured under that key: a warm-up step on a
+        side stream (first launches set function attributes), then the capture, and the state that the two extra steps consumed is
+        put back -- the position, the draw counter, ids, the rings, the rule words and `extra`, the tensors that only this step form
+        carries from one step to the next"""
+        if self.graph is not None and self._graph_key == key:
+            return
+        live = (self.t_dev, self.rng, self.ids, *self.kc, *self.vc, *extra)
+        saved, words = [t.clone() for t in live], self.rules.snapshot()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._step_once()
+        torch.cuda.current_stream().wait_stream(s)
+        self.graph = torch.cuda.CUDAGraph()       # hipGraph on ROCm
+        with torch.cuda.graph(self.graph):
+            self._step_once()
+        self._graph_key = key
+        for t, v in zip(live, saved):
+            t.copy_(v)
+        self.rules.restore(words)
+
     def replay_once(self):
-        """one more token for every row (on the current stream)"""
+        """one more step of what the last begin / beam_begin / contrastive_begin started (on the current stream)"""
         if self._use_graph:
             self.graph.replay()
         else:
-            self.step(self._sampling)
+            self._step_once()
 
     def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
@@ -1438,7 +1405,7 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     """`beam_search` (do_sample=False) with the scorer on the device: per step the rules mask, mxl_beam_step (select, walk, store,
     reorder ids and the rule words), mxl_beam_reorder over the K/V rings, the position advance, the rules advance and the model --
     no host read, captured once under use_graph (XLDecoder.beam_begin / beam_step).  The steps are replayed in chunks of
-    `stop_chunk`; the number of done items is read back one chunk late (as run_until_finished reads the live rows) and the loop
+    `stop_chunk`; the number of done items is read back one chunk late (run_until_finished) and the loop
     ends when every item is done or at max_length.  Then the store and the running scores are read once and `_beam_finalize`
     builds the output, as beam_search does.  dec: an XLDecoder with prompt rows x num_beams rows, num_beams <= 16.
     grammar / n_bars / in_key / key: the rules of `XLDecoder.generate`, one value per prompt where they are per row (each prompt's
@@ -1462,20 +1429,12 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     n = dec.beam_begin(prompt.repeat_interleave(nb, 0).to(dec.eng.dev), max_length, nb, eos_token_id, pad, length_penalty,
                        early_stopping, use_graph, grammar, bar_count_config(n_bars, B0, grammar, stop, nb), in_key,
                        key_config(in_key, key, B0, V, nb), int(num_beam_groups), float(diversity_penalty))
-    st = dec.beam
-    poll, issued, chunk = _AlivePoll(st.n_done, target=B0), 0, max(1, int(stop_chunk))
-    while issued < n and not poll.wait(1):
-        k = min(chunk, n - issued)
-        for _ in range(k):
-            dec.beam_replay_once()
-        poll.mark()
-        issued += k
+    issued, = run_until_finished([(dec, None)], n, stop_chunk)
     dec.beam_select()                   # the last selection needs no forward after it; items that are done ignore it
     dec.steps_run = issued
     cur_len = Tp + issued + 1
-    ints, hyp_score, final = st.ints.cpu(), st.hyp_score.cpu().tolist(), st.scores.cpu()
-    hyp_len = ints[:rows].view(B0, nb).tolist()
-    hyp_n, done = ints[rows:rows + B0].tolist(), ints[rows + B0:rows + 2 * B0].tolist()
+    st = dec.beam
+    hyp_len, hyp_n, done, hyp_score, final = st.read()
     hyps = []
     for b in range(B0):
         h = _BeamHyps(nb, length_penalty, early_stopping)
@@ -1691,7 +1650,7 @@ def contrastive_search_device(dec, prompt: torch.Tensor, max_length: int, top_k:
     """`contrastive_search` with the whole step on the device: per step the rules mask, mxl_contrastive_topk, the position advance,
     the model, mxl_contrastive_step, the rules advance and mxl_ring_slot_broadcast -- no host read, no whole-ring copy, captured once
     under use_graph (XLDecoder.contrastive_begin / contrastive_step).  The steps are replayed in chunks of `stop_chunk`; the number
-    of finished sequences is read back one chunk late (as beam_search_device reads its done items) and the loop ends when every
+    of finished sequences is read back one chunk late (run_until_finished) and the loop ends when every
     sequence has finished or at max_length.  Returns what the host path returns: ids[::K] cut at the step in which the last sequence
     finished, else at max_length; the steps run beyond it inside the last chunk emit pad and are cut off.  dec: an XLDecoder with
     prompt rows x top_k rows, 2 <= top_k <= 32.  grammar (with or without a bar budget) / in_key / key: the rules of
@@ -1710,15 +1669,8 @@ def contrastive_search_device(dec, prompt: torch.Tensor, max_length: int, top_k:
     pad = eos_token_id if pad_token_id is None else pad_token_id
     n = dec.contrastive_begin(prompt.repeat_interleave(K, 0).to(dec.eng.dev), max_length, K, penalty_alpha, eos_token_id,
                               0 if pad is None else pad, use_graph, grammar, in_key, key_config(in_key, key, B0, V, K))
-    poll, issued, chunk = _AlivePoll(dec.cs.n_done, target=B0), 0, max(1, int(stop_chunk))
-    poll.mark()
-    poll.wait(0)                        # the first token is chosen: sequences that all start with eos replay nothing
-    while issued < n and not poll.wait(1):
-        k = min(chunk, n - issued)
-        for _ in range(k):
-            dec.contrastive_replay_once()
-        poll.mark()
-        issued += k
+    # (the count is first read once the first token is chosen: sequences that all start with eos replay nothing)
+    issued, = run_until_finished([(dec, None)], n, stop_chunk)
     dec.steps_run = issued
     width = stop_width(dec.ids[::K], dec.unfinished[::K], Tp, max_length, dec.rules.stop[0])
     return dec.ids[::K, :width].clone()

@@ -6,7 +6,7 @@ import pytest
 import torch
 
 from symbolic_music_generation_amd.generate import (XLDecoder, bars_after_prompt, beam_search, beam_search_device, check_bar_lengths,
-                                                    check_grammar, check_in_key)
+                                                    check_grammar, check_in_key, contrastive_search_device)
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +58,27 @@ def test_generate_takes_either_path(plain, monkeypatch):
     assert dev_ids.shape == (4, host_ids.shape[1]) and torch.equal(dev_ids, host_ids)
     monkeypatch.delenv('MXL_BEAM_HOST')
     assert torch.equal(m.generate(**kw, use_graph=False), dev_ids)
+
+
+def test_one_decoder_through_every_strategy(plain):
+    """the strategies share one capture and one replay on a decoder: every call on a used decoder returns what it returns on a fresh
+    one, each recaptures (the graph key changes with the strategy), and nothing a search leaves behind reaches the next call"""
+    m, _ = plain                                                           # 4 prompts: greedy takes all, the searches the first ones
+    prompts = torch.randint(4, 1190, (4, TP), generator=torch.Generator().manual_seed(PROMPT_SEED)).to(m.engine.dev)
+    calls = (
+        lambda d: d.generate(prompts, L, use_graph=True, eos_token_id=EOS_NEVER, pad_token_id=0),
+        lambda d: beam_search_device(d, prompts[:2], L, num_beams=2, eos_token_id=EOS_NEVER, pad_token_id=0, use_graph=True),
+        lambda d: beam_search_device(d, prompts[:1], L, num_beams=4, num_beam_groups=2, diversity_penalty=1.5, eos_token_id=EOS_NEVER,
+                                     pad_token_id=0, use_graph=True),
+        lambda d: contrastive_search_device(d, prompts[:2], L, top_k=2, eos_token_id=EOS_NEVER, pad_token_id=0, use_graph=True))
+    calls += calls[:1]
+    dec, keys, outs = XLDecoder(m.engine, 4, L), [], []
+    for i, call in enumerate(calls):
+        outs.append(call(dec))
+        keys.append(dec._graph_key)
+        assert torch.equal(outs[-1], call(XLDecoder(m.engine, 4, L))), i
+    assert all(a != b for a, b in zip(keys, keys[1:])), keys
+    assert torch.equal(outs[4], outs[0])
 
 
 # ---------------------------------------------------------------------------------------------------------------- rules
