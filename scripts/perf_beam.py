@@ -18,6 +18,10 @@ generate.group_beam_search_device (mxl_group_beam_step in place of mxl_beam_step
 the topk, the reads, the walk and the uploads once per group and step.
 
     GROUPS=2 python3 scripts/perf_beam.py         # the reference's 'beam' strategy: num_beams=4, num_beam_groups=2
+
+SAMPLE=1 measures beam-sample (do_sample=True, top_k = 50: HF's `beam_sample`), which has the host loop only: one row.
+
+    SAMPLE=1 python3 scripts/perf_beam.py
 """
 import os
 import statistics
@@ -32,6 +36,7 @@ dev = torch.device('cuda:0')
 V, M, B, Tp, NB = 1190, 2048, 8, 256, 4
 NEW, RUNS = int(os.environ.get('NEW', 256)), int(os.environ.get('RUNS', 5))
 GROUPS, DIVERSITY = int(os.environ.get('GROUPS', 1)), float(os.environ.get('DIVERSITY', 1.5))
+SAMPLE = os.environ.get('SAMPLE') == '1'
 L = Tp + NEW
 cfg = MyTransfoXLConfig('base', max_length=2048, vocab_size=V, mem_len=M, cutoffs=[])
 model = MyTransfoXLLMHeadModel(cfg, device=dev, seed=77).eval()
@@ -63,6 +68,12 @@ def run(host: bool, **extra):
 
 
 with torch.no_grad():
+    if SAMPLE:
+        run(True, do_sample=True, top_k=50)                                       # warm-up
+        tps = sorted(B * NEW / run(True, do_sample=True, top_k=50)[0] for _ in range(RUNS))
+        print(f'beam-sample, C5 decode shape: {B} prompts x {Tp}, num_beams {NB} ({B * NB} rows), top_k 50, {NEW} new tokens, eos never fires')
+        print(f'host  : {statistics.median(tps):9.1f} tok/s median of {RUNS} (min {tps[0]:.1f}, max {tps[-1]:.1f})')
+        sys.exit(0)
     # library launches per step: one short eager call of either path, the prompt pass's share taken off with a second, shorter one
     ops.check = counting_check
     per_step = {}

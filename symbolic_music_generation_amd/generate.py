@@ -15,7 +15,7 @@ candidate: its whole step on the device, captured like the sampling step (contra
 """
 import math
 import os
-from collections import deque
+from collections import deque, namedtuple
 from contextlib import nullcontext
 from typing import Optional
 
@@ -187,6 +187,64 @@ def key_config(in_key, key, batch: int, vocab_size: int, repeat: int = 1) -> Opt
     if len(ks) != batch:
         raise ValueError(f'key holds {len(ks)} entries for {batch} prompts: give one key or one per prompt')
     return torch.tensor(ks, dtype=torch.int32).repeat_interleave(int(repeat), 0).contiguous()
+
+
+SearchPlan = namedtuple('SearchPlan', 'strategy device rules eos pad')
+
+
+def rules_refusal(what: str, searches: str = 'beam, group-beam or contrastive search') -> MusicXLError:
+    """the refusal of a rule (or of padded prompts) under a search that does not take it"""
+    return MusicXLError(f'{what} supported for greedy decoding and sampling only, not for {searches}')
+
+
+def plan_search(caps: dict, *, num_beams=1, num_beam_groups=1, do_sample=False, penalty_alpha=None, top_k=None, diversity_penalty=None,
+                eos_token_id=None, pad_token_id=None, config_eos=None, config_pad=None, padded=False, grammar=None, n_bars=None,
+                in_key=None, key=None, melody=None) -> SearchPlan:
+    """Which search a `generate` call runs -- a plain value: `strategy` = 'sample' (greedy decoding / sampling), 'beam', 'beam_sample',
+    'group_beam' or 'contrastive' (chosen as HF 4.25.1 `generate` does); `device`: with its scorer on the device; `rules`: it takes
+    grammar / n_bars / in_key / key; `eos`, `pad`: what the search arms stop at and fill with (the arguments, else the config's) --
+    or MusicXLError for the rules and the padded prompts that search does not take.  caps: the most beams of 'beam' and 'group_beam'
+    search and the most candidates of 'contrastive' search the model runs on the device; an absent key = host only.  The only reader
+    of the environment switches.  A strategy takes the rules if it is greedy decoding / sampling, or runs on the device with an
+    explicit eos_token_id=: a hypothesis ends only by emitting eos, the config's eos (0 = [OMIT]) is no end token of the grammar,
+    and the stop group that the explicit eos turns on is how the device scorers retire rows."""
+    nb, ng = num_beams, num_beam_groups
+    explicit_eos = eos_token_id is not None
+    host_scorer = os.environ.get('MXL_BEAM_HOST') == '1'
+    strategy, device = 'sample', False
+    if penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and not do_sample and nb == 1:
+        strategy = 'contrastive'
+        device = top_k <= caps.get('contrastive', 0) and os.environ.get('MXL_CONTRASTIVE_HOST') != '1'
+    elif ng != 1:
+        strategy = 'group_beam'
+        # on the device for groups that divide the beams; what the host path refuses with HF's ValueError goes there to be refused,
+        # and a negative or infinite diversity_penalty, which the kernel refuses, keeps the host path and what it does with it
+        device = (ng > 1 and not do_sample and 1 < nb <= caps.get('group_beam', 0) and ng <= nb and nb % ng == 0
+                  and 0.0 <= float(diversity_penalty or 0.0) < math.inf and not host_scorer)
+        # this path has not been measured against the host scorer yet (profiles/group_beam_step.txt), so it is taken when a rule
+        # asks for it, or with MXL_GROUP_BEAM_DEVICE=1; a call without a rule keeps the host scorer
+        device = device and (os.environ.get('MXL_GROUP_BEAM_DEVICE') == '1' or (
+            explicit_eos and (grammar is not None or in_key is not None or key is not None)))
+    elif nb > 1:
+        strategy = 'beam_sample' if do_sample else 'beam'
+        device = not do_sample and nb <= caps.get('beam', 0) and not host_scorer
+    is_search = strategy != 'sample'
+    # contrastive search called with num_beam_groups != 1 runs, but has never taken the rules
+    rules = not is_search or (device and explicit_eos and not (strategy == 'contrastive' and ng != 1))
+    # the bar count is untested under contrastive search and under several groups, and needs the grammar that counts the bars
+    no_bar_count = not rules or strategy in ('contrastive', 'group_beam') or (strategy == 'beam' and grammar is None)
+    if padded and is_search:                            # in this order: the first that applies is the one raised
+        raise rules_refusal('padded prompts (attention_mask with zeros) are')
+    if melody is not None and is_search:
+        raise rules_refusal('melody= is')
+    if grammar is not None and not rules:
+        raise rules_refusal('grammar= is')
+    if n_bars is not None and no_bar_count:
+        raise rules_refusal('n_bars= is')
+    if (in_key is not None or key is not None) and not rules:
+        raise rules_refusal('in_key= is')
+    return SearchPlan(strategy, device, rules, config_eos if eos_token_id is None else eos_token_id,
+                      config_pad if pad_token_id is None else pad_token_id)
 
 
 def _guides_per_row(melody, batch: int) -> list:
@@ -1033,10 +1091,7 @@ class XLDecoder:
         ops.rules_mask(self.logp, V, self.t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
         store = (st.hyp_ids, st.hyp_len, st.hyp_score, st.hyp_n, st.done, st.n_done, st.beam_idx, st.moved)
         words = dict(words=self.rules.buf, n_words=len(RowRules.WORDS))
-        if ng > 1:
-            ops.group_beam_step(self.logp, V, st.scores, self.ids, self.t_dev, nb, ng, pen, eos, pad, lp, early, *store, **words)
-        else:
-            ops.beam_step(self.logp, V, st.scores, self.ids, self.t_dev, nb, eos, pad, lp, early, *store, **words)
+        ops.beam_step(self.logp, V, st.scores, self.ids, self.t_dev, nb, eos, pad, lp, early, *store, **words, ng=ng, diversity_penalty=pen)
         return rules
 
     def beam_step(self):
@@ -1327,6 +1382,73 @@ def _beam_finalize(hyps, nb: int, keep: int, ids: torch.Tensor, cur_len: int, be
     return (out, torch.tensor(scores)) if return_scores else out
 
 
+def _beam_loop(dec, prompt: torch.Tensor, max_length: int, nb: int, ng: int, pen: float, Bs: int, keep: int, pick,
+               early_stopping: bool, length_penalty: float, eos: int, pad: Optional[int], return_scores: bool, allowed):
+    """The one host beam loop, under `beam_search` (ng = 1, pen = 0) and `group_beam_search`: Bs items of nb beams in ng groups, one
+    decoder row per beam.  Per step ONE forward for all beams (the kernels of `step`), then the groups in order: group g's
+    log-probabilities, lowered by pen x (how many beams of the EARLIER groups of the same item chose that token at this step;
+    HammingDiversityLogitsProcessor), plus the running scores give the 2 x group size candidates per item in score order -- the
+    best, or `pick(scores (Bs * group size, V))` -- the scorer walks them on the host (a data-dependent loop over a handful of
+    scalars, as in HF 4.25.1; one hypothesis heap and one done flag per item, shared by its groups), and the K/V rings and the id
+    history follow their beams (HF `_reorder_cache`).  The rows of a done item stay where they are, as mxl_beam_step leaves them,
+    filled with pad at running score 0; what they hold in `dec.ids` and in the running scores from then on is part of no contract:
+    `_beam_finalize` skips done items, so the returned ids and scores do not depend on it."""
+    dev, V, pad = dec.eng.dev, dec.eng.cfg.vocab_size, eos if pad is None else pad
+    (B0, Tp), gs, rows = prompt.shape, nb // ng, Bs * nb
+    if keep > nb:
+        raise MusicXLError('num_return_sequences has to be smaller or equal to num_beams')
+    if dec.B != rows or max_length > dec.Tmax:
+        raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, {"group " * (ng > 1)}beam search needs '
+                           f'{rows} x {max_length}')
+    dec.beam_prefill(prompt.repeat_interleave(rows // B0, 0).to(dev))
+    beam_scores = torch.tensor(([0.0] + [-1e9] * (gs - 1)) * (Bs * ng), device=dev)      # the first beam of every group leads
+    hyps = [_BeamHyps(nb, length_penalty, early_stopping) for _ in range(Bs)]
+    cur_len, ident = Tp, torch.arange(rows, device=dev)
+    group_rows = ident.view(Bs, ng, gs).transpose(0, 1).reshape(ng, Bs * gs)       # the decoder rows of every group, item by item
+    while True:
+        logp = dec.beam_logp()                                   # (rows, V), every beam of every group
+        if allowed is not None:
+            logp = logp.masked_fill(~torch.as_tensor(allowed(dec.ids[:, :cur_len])).to(logp.device, torch.bool), float('-inf'))
+        if ng > 1:                                               # this step's running scores, tokens and source rows, filled group by group
+            new_scores, tokens, beam_idx = beam_scores.clone(), torch.zeros(rows, dtype=torch.int64, device=dev), ident.clone()
+        for g in range(ng):
+            g0, gidx = g * gs, group_rows[g]
+            sc, run = logp, beam_scores                          # (one group: no gather)
+            if ng > 1:
+                sc, run = logp.index_select(0, gidx), beam_scores.index_select(0, gidx)
+            if pen > 0.0 and g > 0:
+                # the tokens the earlier groups of the same item have just chosen; under `allowed`, a -inf continuation is no choice
+                prev = tokens.view(Bs, nb)[:, :g0]
+                live = torch.ones_like(prev, dtype=torch.float32)
+                if allowed is not None:
+                    live = torch.isfinite(new_scores.view(Bs, nb)[:, :g0]).to(torch.float32)
+                sc = sc - pen * torch.zeros(Bs, V, device=dev).scatter_add_(1, prev, live).repeat_interleave(gs, 0)
+            sc = sc + run[:, None]
+            top_s, top_i = pick(sc) if pick is not None else sc.view(Bs, gs * V).topk(2 * gs, dim=1, largest=True, sorted=True)
+            top_b, top_t, top_sl = (top_i // V).tolist(), (top_i % V).tolist(), top_s.tolist()
+            # what a done item keeps: score 0, token pad, its rows where they are
+            n_s, n_t = [[0.0] * gs for _ in range(Bs)], [[pad] * gs for _ in range(Bs)]
+            n_i = [list(range(b * nb + g0, b * nb + g0 + gs)) for b in range(Bs)]
+            for b in range(Bs):
+                if not hyps[b].done:
+                    n_s[b], n_t[b], n_i[b] = hyps[b].walk(top_t[b], top_sl[b], [b * nb + g0 + j for j in top_b[b]], gs, eos, dec.ids,
+                                                          cur_len)
+            up = [torch.tensor(x, device=dev).view(-1) for x in (n_s, n_t, n_i)]
+            if ng == 1:
+                new_scores, tokens, beam_idx = up
+            else:
+                new_scores[gidx], tokens[gidx], beam_idx[gidx] = up
+        beam_scores = new_scores
+        if not torch.equal(beam_idx, ident):
+            dec.beam_reorder(beam_idx)
+        dec.ids[:, cur_len] = tokens
+        cur_len += 1
+        if all(h.done for h in hyps) or cur_len >= max_length:
+            break
+        dec.beam_advance(cur_len)
+    return _beam_finalize(hyps, nb, keep, dec.ids, cur_len, beam_scores, max_length, eos, pad, return_scores)
+
+
 def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, do_sample: bool = False,
                 top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: float = 1.0,
                 typical_p: Optional[float] = None, early_stopping: bool = True, length_penalty: float = 1.0,
@@ -1336,65 +1458,22 @@ def beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, 
     """HF 4.25.1 `beam_search` (do_sample=False) / `beam_sample` (do_sample=True) with `BeamSearchScorer.process / finalize`,
     as `model.generate(num_beams=...)` reaches them from musicnlp/trainer/eval.py:302-333.  `dec` is an XLDecoder or an
     rf_generate.RFDecoder (anything with beam_prefill / beam_logp / beam_reorder / beam_advance and `ids`) with one row per beam:
-    B * num_beams rows (times num_return_sequences for beam_sample, as HF expands).  Per step: the device computes the
-    log-probabilities of every beam's next token (the same kernels as `step`), the 2 * num_beams best (or sampled) continuations
-    per item are taken on the device, the scorer's walk over them runs on the host (it is a data-dependent loop over a handful
-    of scalars, as in HF), and the K/V rings and the id history follow their beams (HF `_reorder_cache`).
+    B * num_beams rows (times num_return_sequences for beam_sample, as HF expands its scorer batch, keeping one hypothesis of
+    each).  `_beam_loop` with one group: the 2 * num_beams best (or sampled) continuations per item, then the walk on the host.
     Returns (B * num_return_sequences, L) ids, padded with pad_token_id (= eos when the config has none, as HF does).
     allowed: None, or a callable (ids[:, :cur_len]) -> (rows, V) bool; a token it bars has its log-probability set to -inf before
     the running scores are added, as a logits processor would -- the host reference of the rules under beam_search_device."""
-    e, c = dec.eng, dec.eng.cfg
-    dev, V = e.dev, c.vocab_size
-    nb = num_beams
-    if nb < 2:
+    if num_beams < 2:
         raise MusicXLError('beam search needs num_beams > 1')
-    pad = eos_token_id if pad_token_id is None else pad_token_id
-    B0, Tp = prompt.shape
-    Bs = B0 * (num_return_sequences if do_sample else 1)              # scorer batch (HF: batch_size * num_return_sequences)
-    keep = 1 if do_sample else num_return_sequences
-    if keep > nb:
-        raise MusicXLError('num_return_sequences has to be smaller or equal to num_beams')
-    rows = Bs * nb
-    if dec.B != rows or max_length > dec.Tmax:
-        raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, beam search needs {rows} x {max_length}')
-    expanded = prompt.repeat_interleave(rows // B0, 0).to(dev)
-    dec.beam_prefill(expanded)
-    beam_scores = torch.zeros(Bs, nb, device=dev)
-    beam_scores[:, 1:] = -1e9
-    beam_scores = beam_scores.view(-1)
-    hyps = [_BeamHyps(nb, length_penalty, early_stopping) for _ in range(Bs)]
-    cur_len = Tp
-    ident = torch.arange(rows, device=dev)
-    while True:
-        sc = dec.beam_logp()
-        if allowed is not None:
-            sc = sc.masked_fill(~torch.as_tensor(allowed(dec.ids[:, :cur_len])).to(sc.device, torch.bool), float('-inf'))
-        sc = sc + beam_scores[:, None]
-        if do_sample:              # HF beam_sample: warp log p + beam score, renormalise, draw 2 * num_beams, sort
-            sc = _warp(sc, top_k, top_p, typical_p, temperature, min_keep=2, renormalize=renormalize_logits)
-            flat = sc.view(Bs, nb * V)
-            pick = torch.multinomial(torch.softmax(flat, -1), 2 * nb, generator=generator)
-            top_s, order = flat.gather(-1, pick).sort(descending=True, dim=1)
-            top_i = pick.gather(-1, order)
-        else:
-            top_s, top_i = sc.view(Bs, nb * V).topk(2 * nb, dim=1, largest=True, sorted=True)
-        top_b, top_t = (top_i // V).tolist(), (top_i % V).tolist()
-        top_sl = top_s.tolist()
-        n_s, n_t, n_i = [[0.0] * nb for _ in range(Bs)], [[pad] * nb for _ in range(Bs)], [[0] * nb for _ in range(Bs)]
-        for b in range(Bs):
-            if not hyps[b].done:
-                n_s[b], n_t[b], n_i[b] = hyps[b].walk(top_t[b], top_sl[b], [b * nb + j for j in top_b[b]], nb, eos_token_id, dec.ids,
-                                                      cur_len)
-        beam_scores = torch.tensor(n_s, device=dev).view(-1)
-        beam_idx = torch.tensor(n_i, device=dev).view(-1)
-        if not torch.equal(beam_idx, ident):
-            dec.beam_reorder(beam_idx)
-        dec.ids[:, cur_len] = torch.tensor(n_t, device=dev).view(-1)
-        cur_len += 1
-        if all(h.done for h in hyps) or cur_len >= max_length:
-            break
-        dec.beam_advance(cur_len)
-    return _beam_finalize(hyps, nb, keep, dec.ids, cur_len, beam_scores, max_length, eos_token_id, pad, return_scores)
+    Bs, keep = (prompt.shape[0] * num_return_sequences, 1) if do_sample else (prompt.shape[0], num_return_sequences)
+
+    def sampled(sc):                      # HF beam_sample: warp log p + beam score, renormalise, draw 2 * num_beams, sort
+        flat = _warp(sc, top_k, top_p, typical_p, temperature, min_keep=2, renormalize=renormalize_logits).view(Bs, -1)
+        pick = torch.multinomial(torch.softmax(flat, -1), 2 * num_beams, generator=generator)
+        top_s, order = flat.gather(-1, pick).sort(descending=True, dim=1)
+        return top_s, pick.gather(-1, order)
+    return _beam_loop(dec, prompt, max_length, num_beams, 1, 0.0, Bs, keep, sampled if do_sample else None, early_stopping, length_penalty,
+                      eos_token_id, pad_token_id, return_scores, allowed)
 
 
 def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, early_stopping: bool = True,
@@ -1457,74 +1536,14 @@ def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int
                       return_scores: bool = False, allowed=None):
     """HF 4.25.1 `group_beam_search` (diverse beam search, Vijayakumar et al.) with `BeamSearchScorer(num_beam_groups=...)` and
     `HammingDiversityLogitsProcessor`, as `model.generate(num_beams=, num_beam_groups=, diversity_penalty=)` reaches them from
-    the reference's 'beam' strategy (musicnlp/trainer/eval.py:303-317: num_beam_groups set => do_sample False).  One decoder row
-    per beam; per step ONE forward for all beams, then the groups in order: group g's log-probabilities are lowered by
-    diversity_penalty x (how many beams of the EARLIER groups of the same item chose that token at this step), its 2 x group_size
-    best continuations go through the scorer walk (one hypothesis heap and one done flag per item, shared by its groups, as in
-    4.25.1), and its rows follow their beams.  The first beam of every group starts at score 0, the others at -1e9.
+    the reference's 'beam' strategy (musicnlp/trainer/eval.py:303-317: num_beam_groups set => do_sample False): `_beam_loop` with
+    num_beam_groups groups and the Hamming term between them.
     allowed: as in `beam_search`, the host reference of the rules under group_beam_search_device: a token it bars is -inf before the
     Hamming term and the running score are added, and a row that continues at -inf does not count in the Hamming frequency."""
-    e, c = dec.eng, dec.eng.cfg
-    dev, V = e.dev, c.vocab_size
-    nb, ng = num_beams, num_beam_groups
-    if ng < 2 or nb % ng != 0:
+    if num_beam_groups < 2 or num_beams % num_beam_groups != 0:
         raise ValueError('`num_beams` should be divisible by `num_beam_groups` for group beam search.')      # HF's message
-    gs = nb // ng
-    pad = eos_token_id if pad_token_id is None else pad_token_id
-    B0, Tp = prompt.shape
-    if num_return_sequences > nb:
-        raise MusicXLError('num_return_sequences has to be smaller or equal to num_beams')
-    rows = B0 * nb
-    if dec.B != rows or max_length > dec.Tmax:
-        raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, group beam search needs {rows} x {max_length}')
-    dec.beam_prefill(prompt.repeat_interleave(nb, 0).to(dev))
-    beam_scores = torch.full((B0, nb), -1e9, device=dev)
-    beam_scores[:, ::gs] = 0
-    beam_scores = beam_scores.view(-1)
-    hyps = [_BeamHyps(nb, length_penalty, early_stopping) for _ in range(B0)]
-    cur_len = Tp
-    ident = torch.arange(rows, device=dev)
-    while True:
-        logp = dec.beam_logp()                                   # (rows, V), every beam of every group
-        if allowed is not None:
-            logp = logp.masked_fill(~torch.as_tensor(allowed(dec.ids[:, :cur_len])).to(logp.device, torch.bool), float('-inf'))
-        current = torch.zeros(rows, dtype=torch.int64, device=dev)
-        reorder = ident.clone()
-        new_scores = beam_scores.clone()
-        for g in range(ng):
-            g0 = g * gs
-            gidx = (torch.arange(B0, device=dev)[:, None] * nb + g0 + torch.arange(gs, device=dev)[None, :]).view(-1)
-            sc = logp.index_select(0, gidx)
-            if diversity_penalty and diversity_penalty > 0.0 and g > 0:
-                # HammingDiversityLogitsProcessor: tokens the earlier groups of the same item have just chosen
-                prev = current.view(B0, nb)[:, :g0]
-                live = torch.ones_like(prev, dtype=torch.float32)
-                if allowed is not None:
-                    live = torch.isfinite(new_scores.view(B0, nb)[:, :g0]).to(torch.float32)
-                freq = torch.zeros(B0, V, device=dev).scatter_add_(1, prev, live)
-                sc = sc - diversity_penalty * freq.repeat_interleave(gs, 0)
-            sc = sc + beam_scores.index_select(0, gidx)[:, None]
-            top_s, top_i = sc.view(B0, gs * V).topk(2 * gs, dim=1, largest=True, sorted=True)
-            top_b, top_t, top_sl = (top_i // V).tolist(), (top_i % V).tolist(), top_s.tolist()
-            n_s, n_t, n_i = [[0.0] * gs for _ in range(B0)], [[pad] * gs for _ in range(B0)], [[0] * gs for _ in range(B0)]
-            for b in range(B0):
-                if hyps[b].done:
-                    n_i[b] = [b * nb + g0 + j for j in range(gs)]
-                else:
-                    n_s[b], n_t[b], n_i[b] = hyps[b].walk(top_t[b], top_sl[b], [b * nb + g0 + j for j in top_b[b]], gs, eos_token_id,
-                                                          dec.ids, cur_len)
-            new_scores[gidx] = torch.tensor(n_s, device=dev).view(-1)
-            current[gidx] = torch.tensor(n_t, device=dev).view(-1)
-            reorder[gidx] = torch.tensor(n_i, device=dev).view(-1)
-        beam_scores = new_scores
-        if not torch.equal(reorder, ident):
-            dec.beam_reorder(reorder)
-        dec.ids[:, cur_len] = current
-        cur_len += 1
-        if all(h.done for h in hyps) or cur_len >= max_length:
-            break
-        dec.beam_advance(cur_len)
-    return _beam_finalize(hyps, nb, num_return_sequences, dec.ids, cur_len, beam_scores, max_length, eos_token_id, pad, return_scores)
+    return _beam_loop(dec, prompt, max_length, num_beams, num_beam_groups, float(diversity_penalty or 0.0), prompt.shape[0],
+                      num_return_sequences, None, early_stopping, length_penalty, eos_token_id, pad_token_id, return_scores, allowed)
 
 
 def group_beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 4, num_beam_groups: int = 2,

@@ -369,7 +369,7 @@ def budget_scan(ids, Tp, grammar, gbar, grem, first_bad):
 
 def _beam_step_args(name, logp, V, beam_scores, ids, nb, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words,
                     n_words):
-    """the checks that beam_step and group_beam_step share; returns (rows, items)"""
+    """the checks of beam_step, under either of its names; returns (rows, items)"""
     rows = ids.shape[0]
     _req(logp, torch.float32, f'{name} logp'); _req(beam_scores, torch.float32, f'{name} beam_scores')
     _req(hyp_score, torch.float32, f'{name} hyp_score')
@@ -395,33 +395,26 @@ def _beam_step_args(name, logp, V, beam_scores, ids, nb, hyp_ids, hyp_len, hyp_s
 
 
 def beam_step(logp, V, beam_scores, ids, t_dev, nb, eos_id, pad_id, length_penalty, early_stopping, hyp_ids, hyp_len, hyp_score, hyp_n,
-              done, n_done, beam_idx, moved, words=None, n_words=0):
+              done, n_done, beam_idx, moved, words=None, n_words=0, ng=1, diversity_penalty=0.0):
     """one step of beam search for every item (the nb rows of one prompt), one launch (mxl_beam_step): the 2 * nb best candidates of
     logp (rows, >= V) f32 + beam_scores (rows,) f32 in (score descending, flat index ascending) order, the scorer's walk over them --
     finished hypotheses into the store hyp_ids (Bs, nb, ld) int64 / hyp_len / hyp_score (Bs, nb) / hyp_n / done (Bs,) / n_done (1,) --
     and ids (rows, ld) int64 reordered in place along beam_idx (rows,) int32 with the chosen tokens at column t + 1; moved (Bs,) int32.
-    words: the packed per-row int32 rule words (RowRules.buf), n_words words of `rows` entries each, which follow beam_idx."""
-    rows, Bs = _beam_step_args('beam_step', logp, V, beam_scores, ids, nb, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx,
-                               moved, words, n_words)
-    check(lib().mxl_beam_step(_p(logp), logp.stride(0), _p(beam_scores), _p(ids), ids.stride(0), _p(t_dev), Bs, int(nb), int(V),
-                              int(eos_id), int(pad_id), float(length_penalty), int(bool(early_stopping)), _p(hyp_ids), _p(hyp_len),
-                              _p(hyp_score), _p(hyp_n), _p(done), _p(n_done), _p(beam_idx), _p(moved), _p(words),
-                              int(n_words) if words is not None else 0, rows, _stream()), 'mxl_beam_step')
-
-
-def group_beam_step(logp, V, beam_scores, ids, t_dev, nb, ng, diversity_penalty, eos_id, pad_id, length_penalty, early_stopping,
-                    hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words=None, n_words=0):
-    """one step of diverse (group) beam search for every item, one launch (mxl_group_beam_step): `beam_step` for the ng groups of
-    nb / ng rows of every item, walked in order: group g's candidates score (logp - diversity_penalty * cnt) + beam_scores with cnt[v]
-    the live rows of the item's earlier groups that chose v in this step, its 2 * nb / ng best go through the walk over the item's
-    one store of nb slots, and its rows continue inside the group.  The tensors are beam_step's."""
-    rows, Bs = _beam_step_args('group_beam_step', logp, V, beam_scores, ids, nb, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done,
-                               beam_idx, moved, words, n_words)
-    check(lib().mxl_group_beam_step(_p(logp), logp.stride(0), _p(beam_scores), _p(ids), ids.stride(0), _p(t_dev), Bs, int(nb), int(ng),
-                                    float(diversity_penalty), int(V), int(eos_id), int(pad_id), float(length_penalty),
-                                    int(bool(early_stopping)), _p(hyp_ids), _p(hyp_len), _p(hyp_score), _p(hyp_n), _p(done), _p(n_done),
-                                    _p(beam_idx), _p(moved), _p(words), int(n_words) if words is not None else 0, rows, _stream()),
-          'mxl_group_beam_step')
+    words: the packed per-row int32 rule words (RowRules.buf), n_words words of `rows` entries each, which follow beam_idx.
+    ng > 1: diverse (group) beam search (mxl_group_beam_step), the step for the ng groups of nb / ng rows of every item, walked in
+    order: group g's candidates score (logp - diversity_penalty * cnt) + beam_scores with cnt[v] the live rows of the item's earlier
+    groups that chose v in this step, its 2 * nb / ng best go through the walk over the item's one store of nb slots, and its rows
+    continue inside the group."""
+    name = 'beam_step' if ng == 1 else 'group_beam_step'
+    rows, Bs = _beam_step_args(name, logp, V, beam_scores, ids, nb, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved,
+                               words, n_words)
+    front = (_p(logp), logp.stride(0), _p(beam_scores), _p(ids), ids.stride(0), _p(t_dev), Bs, int(nb))
+    rest = (int(V), int(eos_id), int(pad_id), float(length_penalty), int(bool(early_stopping)), _p(hyp_ids), _p(hyp_len), _p(hyp_score),
+            _p(hyp_n), _p(done), _p(n_done), _p(beam_idx), _p(moved), _p(words), int(n_words) if words is not None else 0, rows, _stream())
+    if ng == 1:
+        check(lib().mxl_beam_step(*front, *rest), 'mxl_beam_step')
+    else:
+        check(lib().mxl_group_beam_step(*front, int(ng), float(diversity_penalty), *rest), 'mxl_group_beam_step')
 
 
 def beam_reorder(bufs, nb, beam_idx, moved, table=None):

@@ -187,32 +187,39 @@ class MyReformerModelWithLMHead(EngineModule):
         decoding and sampling; no n_bars or min_length beside it): every guided row is fed the `<bar> <melody> ... <bass>` spans
         of its guide (`tokenizer.melody_guide`) bar by bar and writes the bass under each, then ends, as
         MyTransfoXLLMHeadModel.generate -- here through the mask launch before the sampler and the advance after it."""
-        from .generate import (STOP_CHUNK, RowRules, bar_count_config, beam_generate, check_grammar_args, key_config, left_pad_counts,
-                               melody_config, resolve_max_length, sample_unfused, sampling_config, stop_config, stop_width)
+        from .generate import (STOP_CHUNK, RowRules, bar_count_config, beam_generate, check_grammar_args, key_config,
+                               left_pad_counts, melody_config, plan_search, resolve_max_length, rules_refusal, sample_unfused, sampling_config,
+                               stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
         check_grammar_args(grammar, self.config.vocab_size, stop)
-        if melody is not None and (num_beams > 1 or num_beam_groups != 1 or (penalty_alpha and not do_sample)):
-            raise MusicXLError('melody= is supported for greedy decoding and sampling only, not for beam, group-beam or contrastive '
-                               'search')
-        if grammar is not None and (num_beams > 1 or num_beam_groups != 1):
-            raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam or group-beam search')
-        if n_bars is not None and (num_beams > 1 or num_beam_groups != 1 or (penalty_alpha and not do_sample)):
-            raise MusicXLError('n_bars= is supported for greedy decoding and sampling only, not for beam, group-beam or contrastive '
-                               'search')
-        if (in_key is not None or key is not None) and (num_beams > 1 or num_beam_groups != 1 or (penalty_alpha and not do_sample)):
-            raise MusicXLError('in_key= is supported for greedy decoding and sampling only, not for beam, group-beam or contrastive '
-                               'search')
-        plan = melody_config(melody, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, n_bars, nrs)
-        n_bars = (bar_count_config(n_bars, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, nrs) if plan is None
-                  else plan.n_bars)
+        top_k = getattr(self.config, 'top_k', 50) if top_k is None else top_k        # HF fills it from the config: default 50
+        # the Reformer's own test for the refusals: whatever sets penalty_alpha without sampling counts as contrastive search, top_k or
+        # not, and the grammar refusal neither fires for it nor names it (a grammar reaches HF's contrastive failure below)
+        beams = num_beams > 1 or num_beam_groups != 1
+        search = beams or bool(penalty_alpha and not do_sample)
+        if melody is not None and search:
+            raise rules_refusal('melody= is')
+        if grammar is not None and beams:
+            raise rules_refusal('grammar= is', 'beam or group-beam search')
+        if n_bars is not None and search:
+            raise rules_refusal('n_bars= is')
+        if (in_key is not None or key is not None) and search:
+            raise rules_refusal('in_key= is')
+        # every search runs on the host here (no caps); the rules were settled above
+        plan = plan_search({}, num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample, penalty_alpha=penalty_alpha,
+                           top_k=top_k, eos_token_id=eos_token_id, pad_token_id=pad_token_id, config_eos=self.config.eos_token_id,
+                           config_pad=self.config.pad_token_id)
+        guide = melody_config(melody, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, n_bars, nrs)
+        n_bars = (bar_count_config(n_bars, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, nrs) if guide is None
+                  else guide.n_bars)
         keys = key_config(in_key, key, input_ids.shape[0] if input_ids is not None else 0, self.config.vocab_size, nrs)
         if attention_mask is not None and input_ids is not None and any(left_pad_counts(attention_mask, tuple(input_ids.shape))):
             # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
             raise MusicXLError(f'{type(self).__name__}.generate does not support padded prompts (attention_mask with zeros); '
                                'generate prompts of different lengths one length at a time')
-        top_k = getattr(self.config, 'top_k', 50) if top_k is None else top_k        # HF fills it from the config: default 50
+        # (not the plan's test: a call with several beams meets HF's failure too)
         if penalty_alpha and not do_sample and top_k is not None and top_k > 1:
             # HF 4.25.1 contrastive_search takes `past_buckets_states` as its cache and indexes past[0][0].shape: the bucket entry
             # of a local layer is None, so the reference stack fails there too; the ValueError is this package's
@@ -224,7 +231,7 @@ class MyReformerModelWithLMHead(EngineModule):
             input_ids = input_ids.repeat_interleave(nrs, 0)
         if max_new_tokens is not None:
             max_length = resolve_max_length(max_length, max_new_tokens, input_ids.shape[1], None)
-        if num_beams > 1 or num_beam_groups != 1:
+        if plan.strategy != 'sample':
             # the reference's 'beam' strategy (eval.py:302-321) and its diverse (group) form over the cached decoder's beam hooks,
             # with an explicit eos / pad in place of the config's
             self._maybe_resync()
@@ -235,8 +242,7 @@ class MyReformerModelWithLMHead(EngineModule):
                 return beam_generate(lambda rows: RFDecoder(self.engine, rows, max_length, rotations=rotations, seed=seed), input_ids,
                                      max_length, num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample,
                                      num_return_sequences=nrs,
-                                     eos_token_id=self.config.eos_token_id if eos_token_id is None else eos_token_id,
-                                     pad_token_id=self.config.pad_token_id if pad_token_id is None else pad_token_id, seed=seed,
+                                     eos_token_id=plan.eos, pad_token_id=plan.pad, seed=seed,
                                      top_k=top_k, top_p=top_p, temperature=temperature, typical_p=typical_p,
                                      early_stopping=early_stopping, renormalize_logits=renormalize_logits,
                                      length_penalty=float(length_penalty or 1.0), diversity_penalty=diversity_penalty)
@@ -270,7 +276,7 @@ class MyReformerModelWithLMHead(EngineModule):
                 dec.seed = seed
                 return dec.generate(ids0, max_length, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
                                     repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop, grammar=grammar, n_bars=n_bars,
-                                    in_key=in_key, key=keys, melody=plan)
+                                    in_key=in_key, key=keys, melody=guide)
             V = c.vocab_size
             pad = getattr(c, 'pad_token_id', None)
             pad = 0 if pad is None else int(pad)
@@ -279,7 +285,7 @@ class MyReformerModelWithLMHead(EngineModule):
             t_dev = torch.full((1,), Tp - 1, device=self.device, dtype=torch.int32)
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
             rules = RowRules(B, self.device)
-            rules.start(buf, Tp, V, stop, grammar, n_bars, in_key, keys, plan)
+            rules.start(buf, Tp, V, stop, grammar, n_bars, in_key, keys, guide)
             rules.check_prompt(buf)
             sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
             for cur in range(Tp, max_length):

@@ -7,7 +7,6 @@ int64, `mems` = list of n_layer tensors shaped (mem_len, B, d_model) (time-major
 `prediction_scores` = log-probabilities (B, T, V).
 """
 import json
-import math
 import os
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional
@@ -290,7 +289,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         `MXL_CONTRASTIVE_HOST=1` keeps the host-driven loop (`generate.contrastive_search`), which takes no rules here."""
         from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, beam_search_device,
                                check_grammar_args, contrastive_search, contrastive_search_device, group_beam_search_device, key_config,
-                               left_pad_counts, melody_config, resolve_max_length, stop_config)
+                               left_pad_counts, melody_config, plan_search, resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -304,79 +303,40 @@ class MyTransfoXLLMHeadModel(EngineModule):
             raise MusicXLError('padded prompts: max_new_tokens and stopping_criteria are not supported (give max_length; '
                                'eos_token_id stops rows)')
         stop = stop_config(eos_token_id, pad_token_id, min_length, self.config.pad_token_id)
-        eos_b = self.config.eos_token_id if eos_token_id is None else eos_token_id          # beam / group-beam / contrastive
-        pad_b = self.config.pad_token_id if pad_token_id is None else pad_token_id
         self._maybe_resync()
         max_length = resolve_max_length(max_length, max_new_tokens, input_ids.shape[1], self.config.max_length_)
         check_grammar_args(grammar, self.config.vocab_size, stop)
-        contrastive = penalty_alpha is not None and penalty_alpha > 0 and top_k is not None and top_k > 1 and not do_sample and num_beams == 1
-        # plain beam search runs with its scorer on the device and takes the rules (generate.beam_search_device); MXL_BEAM_HOST=1
-        # keeps the host scorer (generate.beam_search), which takes none
-        device_beam = (num_beams > 1 and num_beam_groups == 1 and not do_sample and not contrastive and num_beams <= BEAM_MAX
-                       and os.environ.get('MXL_BEAM_HOST') != '1')
-        # group beam search likewise (generate.group_beam_search_device), for groups that divide the beams; what the host path
-        # refuses with HF's ValueError goes there to be refused, and a negative or infinite diversity_penalty, which the kernel
-        # refuses, keeps the host path and what it does with it
-        device_group = (num_beam_groups > 1 and not do_sample and 1 < num_beams <= BEAM_MAX and num_beam_groups <= num_beams
-                        and num_beams % num_beam_groups == 0 and 0.0 <= float(diversity_penalty or 0.0) < math.inf
-                        and os.environ.get('MXL_BEAM_HOST') != '1')
-        # this path has not been measured against the host scorer yet (profiles/group_beam_step.txt), so it is taken when a rule
-        # asks for it, or with MXL_GROUP_BEAM_DEVICE=1; a call without a rule keeps the host scorer
-        device_group = device_group and (os.environ.get('MXL_GROUP_BEAM_DEVICE') == '1' or (
-            stop is not None and (grammar is not None or in_key is not None or key is not None)))
-        # the rules under beam search need an explicit eos_token_id=, as n_bars and melody do everywhere: a hypothesis ends only by
-        # emitting eos, the config's eos (0 = [OMIT]) is no end token of the grammar, and the stop group that the explicit eos turns on
-        # is how the device scorer retires rows.  Without one, and for n_bars without the grammar that counts the bars, a beam call
-        # keeps the refusal it has always had
-        # contrastive search likewise: its step runs on the device for 2..32 candidates (generate.contrastive_search_device) and takes
-        # the grammar and the key rule under the same condition; MXL_CONTRASTIVE_HOST=1 keeps the host-driven loop, which takes none
-        device_contrastive = (contrastive and top_k <= CONTRASTIVE_MAX and os.environ.get('MXL_CONTRASTIVE_HOST') != '1')
-        no_rules = ((contrastive and not (device_contrastive and stop is not None))
-                    or ((num_beam_groups != 1 or num_beams > 1) and not ((device_beam or device_group) and stop is not None)))
-        if n_pad is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
-            raise MusicXLError('padded prompts (attention_mask with zeros) are supported for greedy decoding and sampling only, not '
-                               'for beam, group-beam or contrastive search')
-        if melody is not None and (contrastive or num_beam_groups != 1 or num_beams > 1):
-            raise MusicXLError('melody= is supported for greedy decoding and sampling only, not for beam, group-beam or '
-                               'contrastive search')
-        if grammar is not None and no_rules:
-            raise MusicXLError('grammar= is supported for greedy decoding and sampling only, not for beam, group-beam or '
-                               'contrastive search')
-        if n_bars is not None and (no_rules or contrastive or num_beam_groups != 1 or (num_beams > 1 and grammar is None)):
-            raise MusicXLError('n_bars= is supported for greedy decoding and sampling only, not for beam, group-beam or '
-                               'contrastive search')
-        if (in_key is not None or key is not None) and no_rules:
-            raise MusicXLError('in_key= is supported for greedy decoding and sampling only, not for beam, group-beam or '
-                               'contrastive search')
-        n_bars_arg = n_bars                                 # (the device beam search repeats it per beam, not per returned sequence)
-        plan = melody_config(melody, input_ids.shape[0], grammar, stop, n_bars, num_return_sequences)
-        n_bars = bar_count_config(n_bars, input_ids.shape[0], grammar, stop, num_return_sequences) if plan is None else None
-        keys = key_config(in_key, key, input_ids.shape[0], self.config.vocab_size, num_return_sequences)
-        if contrastive:
-            dec = XLDecoder(self.engine, input_ids.shape[0] * top_k, max_length, seed=seed)
-            if device_contrastive:
-                return contrastive_search_device(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
-                                                 eos_token_id=eos_b, pad_token_id=pad_b, use_graph=use_graph, grammar=grammar,
-                                                 in_key=in_key, key=key)
-            return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha,
-                                      eos_token_id=eos_b, pad_token_id=pad_b)
-        if device_beam:
-            dec = XLDecoder(self.engine, input_ids.shape[0] * num_beams, max_length, seed=seed)
-            return beam_search_device(dec, input_ids, max_length, num_beams, bool(early_stopping), length_penalty,
-                                      num_return_sequences, eos_b, pad_b, use_graph=use_graph, grammar=grammar, n_bars=n_bars_arg,
-                                      in_key=in_key, key=key)
-        if device_group:
-            dec = XLDecoder(self.engine, input_ids.shape[0] * num_beams, max_length, seed=seed)
-            return group_beam_search_device(dec, input_ids, max_length, num_beams, num_beam_groups, diversity_penalty or 0.0,
-                                            bool(early_stopping), length_penalty, num_return_sequences, eos_b, pad_b,
-                                            use_graph=use_graph, grammar=grammar, in_key=in_key, key=key)
-        if num_beam_groups != 1 or num_beams > 1:
+        plan = plan_search(dict(beam=BEAM_MAX, group_beam=BEAM_MAX, contrastive=CONTRASTIVE_MAX),        # what runs on the device
+                           num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample, penalty_alpha=penalty_alpha,
+                           top_k=top_k, diversity_penalty=diversity_penalty, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                           config_eos=self.config.eos_token_id, config_pad=self.config.pad_token_id, padded=n_pad is not None,
+                           grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody)
+        B0 = input_ids.shape[0]
+        guide = melody_config(melody, B0, grammar, stop, n_bars, num_return_sequences)
+        bars = bar_count_config(n_bars, B0, grammar, stop, num_return_sequences) if guide is None else None
+        keys = key_config(in_key, key, B0, self.config.vocab_size, num_return_sequences)
+        ends = dict(eos_token_id=plan.eos, pad_token_id=plan.pad)
+        if plan.strategy == 'contrastive':
+            dec = XLDecoder(self.engine, B0 * top_k, max_length, seed=seed)
+            if plan.device:
+                return contrastive_search_device(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha, use_graph=use_graph,
+                                                 grammar=grammar, in_key=in_key, key=key, **ends)
+            return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha, **ends)
+        if plan.device:                                     # (the device searches repeat per-prompt values per beam themselves)
+            beams = dict(num_beams=num_beams, early_stopping=bool(early_stopping), length_penalty=length_penalty,
+                         num_return_sequences=num_return_sequences, use_graph=use_graph, grammar=grammar, in_key=in_key, key=key, **ends)
+            dec = XLDecoder(self.engine, B0 * num_beams, max_length, seed=seed)
+            if plan.strategy == 'beam':
+                return beam_search_device(dec, input_ids, max_length, n_bars=n_bars, **beams)
+            return group_beam_search_device(dec, input_ids, max_length, num_beam_groups=num_beam_groups,
+                                            diversity_penalty=diversity_penalty or 0.0, **beams)
+        if plan.strategy != 'sample':
             return beam_generate(lambda rows: XLDecoder(self.engine, rows, max_length, seed=seed), input_ids, max_length,
                                  num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample,
-                                 num_return_sequences=num_return_sequences, eos_token_id=eos_b, pad_token_id=pad_b, seed=seed,
-                                 top_k=top_k, top_p=top_p, temperature=temperature, typical_p=typical_p,
-                                 early_stopping=early_stopping, renormalize_logits=renormalize_logits,
-                                 length_penalty=length_penalty, diversity_penalty=diversity_penalty)
+                                 num_return_sequences=num_return_sequences, seed=seed, top_k=top_k, top_p=top_p,
+                                 temperature=temperature, typical_p=typical_p, early_stopping=early_stopping,
+                                 renormalize_logits=renormalize_logits, length_penalty=length_penalty,
+                                 diversity_penalty=diversity_penalty, **ends)
         if num_return_sequences > 1:
             if not do_sample:
                 raise ValueError('num_return_sequences has to be 1 when doing greedy search')       # HF's message
@@ -393,6 +353,6 @@ class MyTransfoXLLMHeadModel(EngineModule):
         dec.invalidate_tables()
         return dec.generate(input_ids.to(self.device), max_length, do_sample=do_sample, top_k=top_k, top_p=top_p,
                             temperature=temperature, repetition_penalty=repetition_penalty, typical_p=typical_p,
-                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device), grammar=grammar, n_bars=n_bars,
-                            in_key=in_key, key=keys, melody=plan,
+                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device), grammar=grammar, n_bars=bars,
+                            in_key=in_key, key=keys, melody=guide,
                             **({} if stop is None else dict(eos_token_id=stop[0], pad_token_id=stop[1], min_length=stop[2])))

@@ -1,0 +1,195 @@
+"""What `MyTransfoXLLMHeadModel.generate` and `MyReformerModelWithLMHead.generate` do with their arguments, recorded without a GPU:
+which search they reach (with which decoder rows, eos, pad, num_return_sequences and rules) or which refusal they raise (type and
+message), over a grid of strategy arguments x rules x environment switches.  tests/test_generate_dispatch_cpu.py asserts the table.
+
+Both methods are called unbound on a stub `self` (a config, no engine), with the decoders and the search functions of generate.py /
+rf_generate.py replaced by recorders that raise `Reached` naming what was reached and with what.
+
+The table is a record of behaviour, not a statement of what is right: regenerate it only at the commit BEFORE a change to the
+dispatch, and let the test show that the change leaves it as it was.
+
+    python tests/golden/make_generate_dispatch.py        # writes tests/golden/generate_dispatch.json
+"""
+import inspect
+import itertools
+import json
+import os
+import sys
+from types import SimpleNamespace
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+OUT = os.path.join(HERE, 'generate_dispatch.json')
+
+ENVS = ('MXL_BEAM_HOST', 'MXL_CONTRASTIVE_HOST', 'MXL_GROUP_BEAM_DEVICE')
+SEARCHES = ('beam_search', 'group_beam_search', 'beam_search_device', 'group_beam_search_device', 'contrastive_search',
+            'contrastive_search_device')
+DECODERS = (('generate', 'XLDecoder'), ('generate', 'XLDecoderLanes'), ('rf_generate', 'RFDecoder'))
+RULES = ('grammar', 'n_bars', 'in_key', 'key', 'melody', 'n_pad')
+SHOWN = ('do_sample', 'num_beams', 'num_beam_groups', 'diversity_penalty')
+MAX_LENGTH = 24
+ALL_RULES = ('none', 'grammar', 'budget', 'grammar+n_bars', 'n_bars', 'in_key', 'key', 'grammar+in_key', 'melody', 'padded',
+             'min_length+n_bars', 'max_new_tokens+max_length', 'padded+max_new_tokens')
+
+
+class Reached(Exception):
+    """a recorder was called: the message describes the call"""
+
+
+def _describe(name: str, rows: list, args: dict) -> str:
+    eos, pad = args.get('eos_token_id'), args.get('pad_token_id')
+    if args.get('stop') is not None:                       # RFDecoder.generate takes the stop group whole
+        eos, pad = args['stop'][:2]
+    given = ','.join(k for k in RULES if args.get(k) is not None)
+    shown = ' '.join(f'{k}={args[k]!r}' for k in SHOWN if k in args)
+    return f'{name} rows={rows} eos={eos} pad={pad} nrs={args.get("num_return_sequences")} rules=[{given}] {shown}'
+
+
+class _Decoder:
+    """stands for XLDecoder, XLDecoderLanes and RFDecoder: what `generate` and `beam_generate` touch before a search starts"""
+    built = []
+
+    def __init__(self, engine, batch, max_total_len, *a, **k):
+        self.B, self.Tmax = batch, max_total_len
+        self.eng = SimpleNamespace(dev=torch.device('cpu'))
+        _Decoder.built.append(batch)
+
+    def invalidate_tables(self):
+        pass
+
+    def generate(self, prompt, max_length, **kw):
+        raise Reached(_describe('sample' if kw.get('do_sample') else 'greedy', list(_Decoder.built), dict(kw, max_length=max_length)))
+
+
+def _recorder(name: str, real):
+    sig = inspect.signature(real)
+
+    def rec(*a, **k):
+        bound = sig.bind(*a, **k)
+        bound.apply_defaults()
+        raise Reached(_describe(name, list(_Decoder.built), dict(bound.arguments)))
+    return rec
+
+
+class patched:
+    """generate.py's and rf_generate.py's decoders and searches replaced by the recorders, restored on exit"""
+
+    def __enter__(self):
+        from symbolic_music_generation_amd import generate, rf_generate
+        mods = dict(generate=generate, rf_generate=rf_generate)
+        self.saved = [(mods[m], n, getattr(mods[m], n)) for m, n in DECODERS] + [(generate, n, getattr(generate, n)) for n in SEARCHES]
+        for mod, n, real in self.saved:
+            setattr(mod, n, _Decoder if (mod.__name__.rsplit('.', 1)[1], n) in DECODERS else _recorder(n, real))
+        return self
+
+    def __exit__(self, *exc):
+        for mod, n, real in self.saved:
+            setattr(mod, n, real)
+
+
+def _stub(name: str, config):
+    """a `self` for the unbound `generate`: the model's name (messages hold it), its config, no engine"""
+    return type(name, (), dict(config=config, engine=None, device=torch.device('cpu'), training=False,
+                               _maybe_resync=lambda self: None, eval=lambda self: self, train=lambda self, mode=True: self))()
+
+
+def fixtures() -> dict:
+    from symbolic_music_generation_amd.reformer import MyReformerConfig, MyReformerModelWithLMHead
+    from symbolic_music_generation_amd.transformer_xl import MyTransfoXLConfig, MyTransfoXLLMHeadModel
+    from symbolic_music_generation_amd.vocab import MusicVocabulary
+    voc = MusicVocabulary()
+    ids = lambda text: [voc.t2i(t) for t in text.split()]
+    prompt = torch.tensor([ids('TimeSig_2/4 Tempo_120 Key_CMajor <bar> <melody>'), ids('TimeSig_2/4 Tempo_96 Key_AMinor <bar> <melody>')])
+    g, gb, rule = voc.grammar(), voc.grammar(bar_budget=True), voc.key_rule()
+    mask = torch.ones_like(prompt)
+    mask[0, 0] = 0
+    rules = dict([
+        ('none', {}),
+        ('grammar', dict(grammar=g)),
+        ('budget', dict(grammar=gb)),
+        ('grammar+n_bars', dict(grammar=g, n_bars=2)),
+        ('n_bars', dict(n_bars=2)),
+        ('in_key', dict(in_key=rule)),
+        ('key', dict(key='CMajor')),
+        ('grammar+in_key', dict(grammar=gb, in_key=rule)),
+        ('melody', dict(grammar=gb, melody=ids('<bar> <melody> p_r d_2 <bass>'))),
+        ('padded', dict(attention_mask=mask)),
+        ('min_length+n_bars', dict(grammar=g, n_bars=2, min_length=3)),
+        ('max_new_tokens+max_length', dict(max_new_tokens=5)),
+        ('padded+max_new_tokens', dict(attention_mask=mask, max_new_tokens=5)),
+    ])
+    V = len(voc)
+    models = dict(
+        xl=(MyTransfoXLLMHeadModel, lambda: _stub('MyTransfoXLLMHeadModel', MyTransfoXLConfig('debug', vocab_size=V, cutoffs=[]))),
+        rf=(MyReformerModelWithLMHead, lambda: _stub('MyReformerModelWithLMHead', MyReformerConfig('debug', vocab_size=V))))
+    return dict(prompt=prompt, rules=rules, models=models, eos=voc.t2i('</s>'))
+
+
+def cases(eos: int):
+    """(label, model, env, rules name, keywords): the strategy product x the rules axis, then diversity_penalty on the group arms
+    and num_return_sequences, each over the strategy product x three of the rules, then what decides "contrastive search" -- top_k 1
+    and a penalty_alpha that is zero or negative beside the values above -- over the rules it is refused"""
+    strategy = list(itertools.product((1, 4, 17), (1, 2, 3), (False, True), (None, 0.6), (4, 33), (None, eos), (None,) + ENVS))
+    for model in ('xl', 'rf'):
+        for extra, names in (({}, None), ('diversity_penalty', ('none', 'grammar', 'in_key')),
+                             ('num_return_sequences', ('none', 'grammar', 'in_key'))):
+            for nb, ng, do_sample, alpha, top_k, e, env in strategy:
+                kw = dict(num_beams=nb, num_beam_groups=ng, do_sample=do_sample, penalty_alpha=alpha, top_k=top_k, eos_token_id=e)
+                if extra == 'diversity_penalty':
+                    more = [dict(diversity_penalty=p) for p in (0.5, -1.0, float('inf'))] if ng > 1 else []
+                elif extra == 'num_return_sequences':
+                    more = [dict(num_return_sequences=n) for n in (2, 5)]
+                else:
+                    more = [{}]
+                for m in more:
+                    for name in names or ALL_RULES:
+                        yield f'{model} {env} {name} {dict(kw, **m)}', model, env, name, dict(kw, **m)
+        for nb, ng, do_sample, alpha, top_k, e in itertools.product((1, 4), (1, 2), (False, True), (0.6, 0, -0.5), (1, 4), (None, eos)):
+            kw = dict(num_beams=nb, num_beam_groups=ng, do_sample=do_sample, penalty_alpha=alpha, top_k=top_k, eos_token_id=e)
+            for name in ('none', 'grammar', 'grammar+n_bars', 'n_bars', 'in_key', 'key', 'melody'):
+                yield f'{model} None {name} {kw}', model, None, name, kw
+
+
+def outcome(fx: dict, model: str, env, name: str, kw: dict) -> str:
+    cls, make = fx['models'][model]
+    saved = {k: os.environ.pop(k, None) for k in ENVS}
+    if env is not None:
+        os.environ[env] = '1'
+    _Decoder.built = []
+    try:
+        cls.generate(make(), input_ids=fx['prompt'], max_length=MAX_LENGTH, **kw, **fx['rules'][name])
+        return 'returned'
+    except Reached as r:
+        return str(r)
+    except Exception as x:
+        return f'{type(x).__name__}: {x}'
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
+def record() -> tuple:
+    """(labels, outcomes): one of each per case"""
+    fx = fixtures()
+    labels, out = [], []
+    with patched():
+        for label, model, env, name, kw in cases(fx['eos']):
+            labels.append(label)
+            out.append(outcome(fx, model, env, name, kw))
+    return labels, out
+
+
+if __name__ == '__main__':
+    _, out = record()
+    distinct = sorted(set(out))
+    at = {o: i for i, o in enumerate(distinct)}
+    with open(OUT, 'w') as f:
+        json.dump(dict(outcomes=distinct, cases=[at[o] for o in out]), f, separators=(',', ':'))
+        f.write('\n')
+    print(f'{len(out)} cases, {len(distinct)} outcomes -> {OUT} ({os.path.getsize(OUT)} bytes)')
+    for o in distinct:
+        print(f'{out.count(o):6d}  {o[:200]}')

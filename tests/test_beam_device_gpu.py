@@ -1,12 +1,13 @@
 """Beam search with the scorer on the device, end to end on TransfoXL: generate.beam_search_device against the host scorer
 generate.beam_search on a second decoder, the public `generate(num_beams=)` on either path, and the rules under beam search against
 the host scorer with a mask built from grammar.py's host walkers."""
-import numpy as np
 import pytest
 import torch
 
 from symbolic_music_generation_amd.generate import (XLDecoder, bars_after_prompt, beam_search, beam_search_device, check_bar_lengths,
                                                     check_grammar, check_in_key, contrastive_search_device)
+
+from tests.beam_ref import host_allowed
 
 pytestmark = pytest.mark.gpu
 
@@ -82,48 +83,6 @@ def test_one_decoder_through_every_strategy(plain):
 
 
 # ---------------------------------------------------------------------------------------------------------------- rules
-def host_allowed(grammar, Tp, n_bars=None, rule=None, keys=None):
-    """the `allowed` callable of generate.beam_search for these rules, from the host walkers: every row of ids[:, :cur_len] is walked
-    from its start by TokenGrammar.walk, walk_budget, walk_bars (the generated part, from n_bars) and KeyRule.walk, and the words
-    they end in admit what mxl_rules_mask admits.  A row that the walk itself rejects (the kept -inf continuation of a dead row) is
-    barred whole: it is dead on either side."""
-    V = (grammar.vocab_size if grammar is not None else rule.vocab_size)
-
-    def allowed(ids):
-        out = np.ones((ids.shape[0], V), dtype=bool)
-        for r, row in enumerate(ids.tolist()):
-            if grammar is not None:
-                cls = grammar.cls.astype(np.int64)
-                s, bad = grammar.walk(row)
-                if bad >= 0:
-                    out[r] = False
-                    continue
-                out[r] &= ((int(grammar.allow[s]) >> cls) & 1) == 1
-                bud = grammar.budget
-                if bud is not None:
-                    bar, rem, bad = grammar.walk_budget(row)
-                    if bad >= 0:
-                        out[r] = False
-                        continue
-                    if bar > 0:
-                        out[r] &= bud.slots.astype(np.int64) <= rem
-                        deny = bud.need_free if rem <= 0 else bud.need_full
-                        out[r] &= ((deny >> cls) & 1) == 0
-                if n_bars is not None:
-                    left, bad = grammar.walk_bars(row[Tp:], n_bars)
-                    if bad >= 0:
-                        out[r] = False
-                        continue
-                    cnt = grammar.bar_count
-                    deny = cnt.end if left > 0 else (cnt.count if left == 0 else 0)
-                    out[r] &= ((deny >> cls) & 1) == 0
-            if rule is not None:
-                key, _ = rule.walk(row, -1 if keys is None else keys[r], len(row))
-                out[r] &= rule.allowed(key)
-        return torch.from_numpy(out)
-    return allowed
-
-
 def _rules_case(dev, seed, budget, n_bars, in_key, nb=3, keep=2):
     from tests.test_key_rule_gpu import BAR_TOKENS, EOS, FULL_BAR, PAD, RULE, TOK, _model, _prompts
     m = _model(dev, seed, closing_bias=4.0)

@@ -1,13 +1,13 @@
 """`generate.group_beam_search` on the CPU, over tests/test_beam_cpu.py's stand-in decoder: the `allowed=` mask that makes it the
-host reference of the rules under group beam search on the device, and the one-step Python reference of
-tests/test_group_beam_step_gpu.py against it step for step -- which ties what the kernel test compares mxl_group_beam_step with to
-the host function, without a GPU."""
+host reference of the rules under group beam search on the device, and the one-step Python reference of tests/beam_ref.py against
+it and against `generate.beam_search` step for step -- which ties what the kernel tests compare mxl_beam_step and
+mxl_group_beam_step with to the host functions, without a GPU."""
 import pytest
 import torch
 
-from symbolic_music_generation_amd.generate import _beam_finalize, _BeamHyps, group_beam_search
+from symbolic_music_generation_amd.generate import _beam_finalize, _BeamHyps, beam_search, group_beam_search
 from tests.test_beam_cpu import CASES, L, TP, V, _finished_early, _model_and_prompt, _OracleDecoder
-from tests.test_group_beam_step_gpu import RefState, ref_group_step
+from tests.beam_ref import RefState, ref_step
 
 KW = dict(num_beams=4, num_beam_groups=2, num_return_sequences=2, return_scores=True)
 
@@ -60,25 +60,29 @@ class _Recorder(_OracleDecoder):
 
 
 @torch.no_grad()
-@pytest.mark.parametrize('nb,ng', [(4, 2), (4, 4), (6, 3)])
+@pytest.mark.parametrize('nb,ng', [(4, 2), (4, 4), (6, 3), (3, 1), (2, 1)])
 @pytest.mark.parametrize('diversity_penalty', [0.0, 0.8])
 @pytest.mark.parametrize('seed,eos,early', CASES)
 def test_the_one_step_reference_is_the_host_function(seed, eos, early, diversity_penalty, nb, ng):
-    """the kernel test's ref_group_step, fed the log-probabilities that group_beam_search ranked, leaves the ids that
-    group_beam_search left, step after step, and its store and running scores finalise to the returned rows and scores"""
+    """the kernel tests' ref_step, fed the log-probabilities that group_beam_search (ng = 1: beam_search, which the diversity
+    penalty does not reach) ranked, leaves the ids that the search left, step after step, and its store and running scores finalise
+    to the returned rows and scores"""
     model, prompt = _model_and_prompt(seed, eos)
     rows, gs = 2 * nb, nb // ng
     for stopping in (True, False):
         dec = _Recorder(model, rows, L)
-        want, w_sc = group_beam_search(dec, prompt, L, num_beams=nb, num_beam_groups=ng, diversity_penalty=diversity_penalty,
-                                       early_stopping=stopping, num_return_sequences=2, eos_token_id=eos, return_scores=True)
+        kw = dict(num_beams=nb, early_stopping=stopping, num_return_sequences=2, eos_token_id=eos, return_scores=True)
+        if ng == 1:
+            want, w_sc = beam_search(dec, prompt, L, **kw)
+        else:
+            want, w_sc = group_beam_search(dec, prompt, L, num_beam_groups=ng, diversity_penalty=diversity_penalty, **kw)
         scores = torch.full((2, nb), -1e9)
         scores[:, ::gs] = 0
         ref = RefState(dec.seen[0][1], scores.view(-1), 2, nb, torch.ones(1, rows, dtype=torch.int64))
         after = [ids for _, ids in dec.seen[1:]] + [dec.ids]
         for k, (logp, _) in enumerate(dec.seen):
             cur_len = TP + k
-            ref_group_step(ref, logp, V, cur_len, ng, diversity_penalty, eos, eos, 1.0, stopping)
+            ref_step(ref, logp, V, cur_len, eos, eos, 1.0, stopping, ng, diversity_penalty)
             assert torch.equal(ref.ids[:, :cur_len + 1], after[k][:, :cur_len + 1]), (stopping, k)
         hyps = []
         for b in range(2):

@@ -1,13 +1,14 @@
 """Diverse (group) beam search with the scorer on the device, end to end on TransfoXL: generate.group_beam_search_device against the
 host scorer generate.group_beam_search on a second decoder, the public `generate(num_beams=, num_beam_groups=)` on either path, and
 the grammar and the key rule under group beam search against the host scorer with a mask built from grammar.py's host walkers."""
-import numpy as np
 import pytest
 import torch
 
 from symbolic_music_generation_amd import generate as G
 from symbolic_music_generation_amd.generate import (XLDecoder, check_bar_lengths, check_grammar, check_in_key, group_beam_search,
                                                     group_beam_search_device)
+
+from tests.beam_ref import host_allowed
 
 pytestmark = pytest.mark.gpu
 
@@ -110,40 +111,6 @@ def test_generate_takes_either_path(plain, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------------------------- rules
-def host_allowed(grammar, rule=None, keys=None):
-    """the `allowed` callable of generate.group_beam_search for these rules, from the host walkers (tests/test_beam_device_gpu.py's,
-    without the bar count): every row of ids[:, :cur_len] is walked from its start by TokenGrammar.walk, walk_budget and
-    KeyRule.walk, and the words they end in admit what mxl_rules_mask admits.  A row that the walk itself rejects (the kept -inf
-    continuation of a dead row) is barred whole: it is dead on either side."""
-    V = (grammar.vocab_size if grammar is not None else rule.vocab_size)
-
-    def allowed(ids):
-        out = np.ones((ids.shape[0], V), dtype=bool)
-        for r, row in enumerate(ids.tolist()):
-            if grammar is not None:
-                cls = grammar.cls.astype(np.int64)
-                s, bad = grammar.walk(row)
-                if bad >= 0:
-                    out[r] = False
-                    continue
-                out[r] &= ((int(grammar.allow[s]) >> cls) & 1) == 1
-                bud = grammar.budget
-                if bud is not None:
-                    bar, rem, bad = grammar.walk_budget(row)
-                    if bad >= 0:
-                        out[r] = False
-                        continue
-                    if bar > 0:
-                        out[r] &= bud.slots.astype(np.int64) <= rem
-                        deny = bud.need_free if rem <= 0 else bud.need_full
-                        out[r] &= ((deny >> cls) & 1) == 0
-            if rule is not None:
-                key, _ = rule.walk(row, -1 if keys is None else keys[r], len(row))
-                out[r] &= rule.allowed(key)
-        return torch.from_numpy(out)
-    return allowed
-
-
 GROUPS = dict(num_beams=4, num_beam_groups=2, diversity_penalty=1.5, num_return_sequences=2, early_stopping=True)
 
 
@@ -157,7 +124,7 @@ def _rules_case(dev, seed, budget, in_key):
     rule = RULE if in_key else None
     kw = dict(GROUPS, eos_token_id=EOS, pad_token_id=PAD)
     got = m.generate(input_ids=ids, max_length=W, grammar=g, in_key=rule, **kw)
-    want = group_beam_search(XLDecoder(m.engine, ids.shape[0] * 4, W), ids, W, allowed=host_allowed(g, rule), **kw)
+    want = group_beam_search(XLDecoder(m.engine, ids.shape[0] * 4, W), ids, W, allowed=host_allowed(g, rule=rule), **kw)
     free = group_beam_search(XLDecoder(m.engine, ids.shape[0] * 4, W), ids, W, **kw)
     return got, want, free, g, rule, ids, EOS
 
@@ -203,7 +170,7 @@ def test_in_key_alone_under_group_beam_search(dev):
     free = m.generate(input_ids=ids, max_length=W, **kw)
     assert (check_in_key(free, RULE, prompt_len=Tp) >= Tp).all()           # the model leaves the key without the rule
     got = m.generate(input_ids=ids, max_length=W, in_key=RULE, **kw)
-    want = group_beam_search(XLDecoder(m.engine, 12, W), ids, W, allowed=host_allowed(None, RULE), **kw)
+    want = group_beam_search(XLDecoder(m.engine, 12, W), ids, W, allowed=host_allowed(None, rule=RULE), **kw)
     assert torch.equal(got, want) and check_in_key(got, RULE, prompt_len=Tp).tolist() == [-1] * 3
     keyed = m.generate(input_ids=ids, max_length=W, in_key=RULE, key=['GMajor', None, 'CMajor'], **kw)
     assert check_in_key(keyed, RULE, prompt_len=Tp, key=['GMajor', None, 'CMajor']).tolist() == [-1] * 3

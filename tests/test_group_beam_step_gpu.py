@@ -1,169 +1,12 @@
-"""mxl_group_beam_step at kernel level.  The reference of the step is a plain-Python restatement, below, of the inner loop of
-generate.group_beam_search for one item -- HF 4.25.1 group_beam_search + HammingDiversityLogitsProcessor + BeamSearchScorer.process
-with one store per item -- over a slot store, with the candidate order (score descending, flat index ascending) that the kernel
-promises.  tests/test_group_beam_cpu.py ties it to generate.group_beam_search step for step, without a GPU.  The scores are formed
-in f32 on both sides, product, difference and sum each rounded on its own, so indices, tokens, ids, words, running scores, store
-contents and flags are compared exactly and only the length-normalised scores (powf against Python's **) to rtol 1e-6."""
+"""mxl_group_beam_step at kernel level, against the one-step reference of tests/beam_ref.py (which tests/test_group_beam_cpu.py ties
+to generate.group_beam_search step for step, without a GPU)."""
 
 import pytest
 import torch
 
+from tests.beam_ref import MXL_EINVAL, NEG, DevState, RefState, compare as _compare, distinct_logp as _distinct_logp, ref_step
+
 pytestmark = pytest.mark.gpu
-
-NEG = float('-inf')
-MXL_EINVAL = -1
-
-
-# ---------------------------------------------------------------------------------------------------------------- reference
-class RefState:
-    """the state one step reads and writes, on the host: ids (rows, ld) int64, scores (rows,) f32, the store as per item a list of
-    [score, tokens] slots, done flags, words (n_words, rows) int"""
-
-    def __init__(self, ids, scores, Bs, nb, words):
-        self.ids, self.scores, self.Bs, self.nb = ids.clone(), scores.clone(), Bs, nb
-        self.hyp = [[] for _ in range(Bs)]
-        self.done = [False] * Bs
-        self.n_done = 0
-        self.words = words.clone()
-        self.events = set()
-
-
-def ref_group_step(st: RefState, logp: torch.Tensor, V: int, cur_len: int, ng: int, pen: float, eos: int, pad: int, lp: float,
-                   early: bool):
-    """one mxl_group_beam_step on the host; returns (beam_idx, moved).  Events, into st.events: 'hamming1' / 'hamming2' (a token
-    counted once / at least twice moved or left a group's 2 * gs best), 'added' / 'replaced' / 'rejected' / 'skipped' (an eos),
-    'cut' (the item became done in a group that is not its last: the groups behind are not walked), 'frozen', 'dead', and
-    'dead_uncounted' (a group scored under a penalty while an earlier group of the item holds a dead row)."""
-    nb, gs = st.nb, st.nb // ng
-    pen32 = torch.tensor(pen, dtype=torch.float32)
-    beam_idx, moved = [], []
-    new_ids, new_words, new_scores = st.ids.clone(), st.words.clone(), st.scores.clone()
-    for b in range(st.Bs):
-        r0 = b * nb
-        if st.done[b]:
-            st.events.add('frozen')
-            beam_idx += list(range(r0, r0 + nb))
-            moved.append(0)
-            new_ids[r0:r0 + nb, cur_len] = pad
-            new_words[0, r0:r0 + nb] = 0
-            continue
-        src, toks, dead = list(range(nb)), [pad] * nb, [False] * nb
-        scs = st.scores[r0:r0 + nb].tolist()
-        hyp, chosen, d = st.hyp[b], [], False
-        for g in range(ng):
-            if d:
-                st.events.add('cut')
-                break
-            g0 = g * gs
-            lo, hi = r0 + g0, r0 + g0 + gs
-            cnt = torch.zeros(V, dtype=torch.float32)
-            for t in chosen:
-                cnt[t] += 1
-            plain = logp[lo:hi, :V] + st.scores[lo:hi, None]
-            sums = (logp[lo:hi, :V] - pen32 * cnt) + st.scores[lo:hi, None]      # f32: the three roundings the kernel makes
-            flat = sums.reshape(-1).tolist()
-            order = sorted(range(gs * V), key=lambda i: (-(flat[i] + 0.0), i))[:2 * gs]
-            if chosen and pen > 0:
-                if any(dead[:g0]):
-                    st.events.add('dead_uncounted')
-                pl = plain.reshape(-1).tolist()
-                free = sorted(range(gs * V), key=lambda i: (-(pl[i] + 0.0), i))[:2 * gs]
-                for k, i in enumerate(free):
-                    if order[k] != i and cnt[i % V] > 0:
-                        st.events.add('hamming1' if cnt[i % V] == 1 else 'hamming2')
-            n_src, n_tok, n_sc, n_dead = [], [], [], []
-            for rank, i in enumerate(order):
-                j, v, s = i // V, i % V, flat[i]
-                if v == eos:
-                    if rank >= gs:
-                        st.events.add('skipped')
-                        continue
-                    sc = s / cur_len ** lp
-                    row = st.ids[lo + j, :cur_len].tolist()
-                    if len(hyp) < nb:
-                        hyp.append([sc, row])
-                        st.events.add('added')
-                    else:
-                        worst = min(range(nb), key=lambda k: (hyp[k][0], k))
-                        if sc > hyp[worst][0]:
-                            hyp[worst] = [sc, row]
-                            st.events.add('replaced')
-                        else:
-                            st.events.add('rejected')
-                else:
-                    n_src.append(g0 + j); n_sc.append(s); n_dead.append(s == NEG); n_tok.append(pad if s == NEG else v)
-                if len(n_src) == gs:
-                    break
-            assert len(n_src) == gs
-            src[g0:g0 + gs], toks[g0:g0 + gs], scs[g0:g0 + gs], dead[g0:g0 + gs] = n_src, n_tok, n_sc, n_dead
-            chosen += [t for t, x in zip(n_tok, n_dead) if not x]
-            if len(hyp) >= nb:
-                d = True if early else min(h[0] for h in hyp) >= flat[order[0]] / cur_len ** lp
-        for j in range(nb):
-            new_ids[r0 + j, :cur_len] = st.ids[r0 + src[j], :cur_len]
-            new_ids[r0 + j, cur_len] = toks[j]
-            new_words[:, r0 + j] = st.words[:, r0 + src[j]]
-            new_scores[r0 + j] = scs[j]
-        for j in range(nb):
-            if dead[j] or d:
-                new_words[0, r0 + j] = 0
-        if any(dead):
-            st.events.add('dead')
-        if d:
-            st.done[b] = True
-            st.n_done += 1
-        beam_idx += [r0 + j for j in src]
-        moved.append(int(src != list(range(nb))))
-    st.ids, st.words, st.scores = new_ids, new_words, new_scores
-    return beam_idx, moved
-
-
-# ---------------------------------------------------------------------------------------------------------------- device side
-class DevState:
-    def __init__(self, ref: RefState, ld: int, dev):
-        Bs, nb = ref.Bs, ref.nb
-        rows = Bs * nb
-        i32 = dict(device=dev, dtype=torch.int32)
-        self.ids, self.scores, self.words = ref.ids.to(dev), ref.scores.to(dev), ref.words.to(dev, torch.int32).contiguous()
-        self.hyp_ids = torch.full((Bs, nb, ld), -7, device=dev, dtype=torch.int64)
-        self.hyp_len, self.hyp_score = torch.zeros(Bs, nb, **i32), torch.zeros(Bs, nb, device=dev)
-        self.hyp_n, self.done, self.n_done = torch.zeros(Bs, **i32), torch.zeros(Bs, **i32), torch.zeros(1, **i32)
-        self.beam_idx, self.moved = torch.full((rows,), -1, **i32), torch.full((Bs,), -1, **i32)
-        self.t = torch.zeros(1, **i32)
-
-    def step(self, logp, V, cur_len, ng, pen, eos, pad, lp, early, words=True):
-        from symbolic_music_generation_amd import ops
-        self.t.fill_(cur_len - 1)
-        ops.group_beam_step(logp, V, self.scores, self.ids, self.t, self.hyp_len.shape[1], ng, pen, eos, pad, lp, early, self.hyp_ids,
-                            self.hyp_len, self.hyp_score, self.hyp_n, self.done, self.n_done, self.beam_idx, self.moved,
-                            words=self.words if words else None, n_words=self.words.shape[0] if words else 0)
-
-
-def _compare(ref: RefState, d: DevState, beam_idx, moved, what):
-    assert d.beam_idx.tolist() == beam_idx, what
-    assert d.moved.tolist() == moved, what
-    assert torch.equal(d.ids.cpu(), ref.ids), what
-    assert torch.equal(d.words.cpu().to(torch.int64), ref.words), what
-    got, want = d.scores.cpu(), ref.scores
-    assert torch.equal(got == NEG, want == NEG), what
-    fin = want != NEG
-    assert torch.equal(got[fin], want[fin]), what                          # the same three f32 roundings
-    assert d.done.tolist() == [int(x) for x in ref.done] and int(d.n_done) == ref.n_done, what
-    assert d.hyp_n.tolist() == [len(h) for h in ref.hyp], what
-    hyp_ids, hyp_len, hyp_score = d.hyp_ids.cpu(), d.hyp_len.tolist(), d.hyp_score.tolist()
-    for b, hyp in enumerate(ref.hyp):
-        for k, (sc, row) in enumerate(hyp):
-            assert hyp_len[b][k] == len(row) and hyp_ids[b, k, :len(row)].tolist() == row, (what, b, k)
-            if sc == NEG:
-                assert hyp_score[b][k] == NEG, (what, b, k)
-            else:
-                assert abs(hyp_score[b][k] - sc) <= 1e-6 * abs(sc), (what, b, k, hyp_score[b][k], sc)
-
-
-def _distinct_logp(rows, ldl, g):
-    """pairwise distinct values in (-6, -1), spaced 5 / (rows * ldl) apart"""
-    n = rows * ldl
-    return (-1.0 - 5.0 * torch.randperm(n, generator=g).to(torch.float64) / n).to(torch.float32).view(rows, ldl)
 
 
 # ---------------------------------------------------------------------------------------------------------------- the scorer
@@ -244,10 +87,10 @@ def test_group_beam_step_follows_the_scorer(dev):
             for step in range(STEPS):
                 logp = scenario(ref, step, nb, ng, V, a['ldl'], a['eos'], a['pad'], g)
                 had_cut = 'cut' in ref.events
-                beam_idx, moved = ref_group_step(ref, logp, V, Tp + step, ng, a['pen'], a['eos'], a['pad'], a['lp'], a['early'])
+                beam_idx, moved = ref_step(ref, logp, V, Tp + step, a['eos'], a['pad'], a['lp'], a['early'], ng, a['pen'])
                 if cut_at is None and not had_cut and 'cut' in ref.events:
                     cut_at = step
-                d.step(logp.to(dev), V, Tp + step, ng, a['pen'], a['eos'], a['pad'], a['lp'], a['early'])
+                d.step(logp.to(dev), V, Tp + step, a['eos'], a['pad'], a['lp'], a['early'], ng=ng, pen=a['pen'])
                 _compare(ref, d, beam_idx, moved, (nb, ng, V, step, a))
             what = (nb, ng, V, a, ref.events)
             assert {'added', 'replaced' if not a['early'] else 'added', 'cut', 'frozen'} <= ref.events, what
@@ -286,14 +129,14 @@ def test_ties_and_the_hamming_count(dev):
         logp[0, 6] = logp[1, 6] = -0.5                                    # group 0: a tie, flat indices 6 < 11 + 6
         logp[2, 6] = -0.25                                                # group 1: best when free, -1.25 under the penalty
         logp[2, 3] = logp[3, 0] = -1.0                                    # group 1: an exact tie, flat indices 3 < 11 + 0
-        beam_idx, moved = ref_group_step(ref, logp, V, 4, ng, pen, eos, pad, 1.0, True)
+        beam_idx, moved = ref_step(ref, logp, V, 4, eos, pad, 1.0, True, ng, pen)
         assert beam_idx[:2] == [0, 1] and ref.ids[:2, 4].tolist() == [6, 6]
         if pen:
             assert beam_idx[2:] == [2, 3] and ref.ids[2:, 4].tolist() == [3, 0] and 'hamming2' in ref.events
             assert ref.scores[2:].tolist() == [-2.0, -2.0]
         else:
             assert beam_idx[2:] == [2, 2] and ref.ids[2:, 4].tolist() == [6, 3]
-        d.step(logp.to(dev), V, 4, ng, pen, eos, pad, 1.0, True)
+        d.step(logp.to(dev), V, 4, eos, pad, 1.0, True, ng=ng, pen=pen)
         _compare(ref, d, beam_idx, moved, ('ties', pen))
 
 
@@ -310,22 +153,22 @@ def test_dead_rows_do_not_count(dev):
     logp[0:2, :V] = NEG
     logp[1, 4] = -0.25                                                    # item 0 group 0: row 1 token 4, then a -inf candidate
     logp[2, pad], logp[3, 4], logp[3, 5] = -0.5, -0.75, -1.0              # item 0 group 1: pad first; 4 is counted once, behind 5
-    beam_idx, moved = ref_group_step(ref, logp, V, 4, ng, pen, eos, pad, 1.0, True)
+    beam_idx, moved = ref_step(ref, logp, V, 4, eos, pad, 1.0, True, ng, pen)
     assert beam_idx[:2] == [1, 0] and ref.ids[:2, 4].tolist() == [4, pad] and ref.scores[1].item() == NEG
     assert {'dead', 'dead_uncounted', 'hamming1'} <= ref.events
     assert beam_idx[2] == 2 and ref.ids[2, 4].item() == pad and ref.scores[2].item() == -1.5
     assert beam_idx[3] == 3 and ref.ids[3, 4].item() == 5                 # ... while the live row's 4 did count
     assert beam_idx[6:] == [6, 6] and ref.ids[6:, 4].tolist() == [pad, pad]
-    d.step(logp.to(dev), V, 4, ng, pen, eos, pad, 1.0, True)
+    d.step(logp.to(dev), V, 4, eos, pad, 1.0, True, ng=ng, pen=pen)
     _compare(ref, d, beam_idx, moved, 'dead')
     assert d.scores[1].item() == NEG and d.words[0, 1].item() == 0
     assert d.words[1:, 1].tolist() == words[1:, 0].tolist()               # the other words are the source's
     # the next step: item 0's dead row is overwritten by a second child of its live neighbour; item 1's dead group stays dead
     logp = _distinct_logp(8, V + 3, g) - 10
-    beam_idx, moved = ref_group_step(ref, logp, V, 5, ng, pen, eos, pad, 1.0, True)
+    beam_idx, moved = ref_step(ref, logp, V, 5, eos, pad, 1.0, True, ng, pen)
     assert beam_idx[:2] == [0, 0] and ref.scores[1].item() > NEG
     assert ref.scores[6:].tolist() == [NEG, NEG] and ref.ids[6:, 5].tolist() == [pad, pad] and ref.words[0, 6:].tolist() == [0, 0]
-    d.step(logp.to(dev), V, 5, ng, pen, eos, pad, 1.0, True)
+    d.step(logp.to(dev), V, 5, eos, pad, 1.0, True, ng=ng, pen=pen)
     _compare(ref, d, beam_idx, moved, 'dead, next step')
 
 
@@ -335,14 +178,14 @@ def test_rule_words_follow_their_beams_inside_the_groups(dev):
     logp = _distinct_logp(nb, V + 3, g) - 10
     logp[1, 30], logp[0, 31] = -0.1, -0.2                                 # group 0: a swap
     logp[3, 5], logp[3, 6] = -0.1, -0.2                                   # group 1: a duplicate
-    beam_idx, moved = ref_group_step(ref, logp, V, 4, ng, 0.0, V - 1, 0, 1.0, True)
+    beam_idx, moved = ref_step(ref, logp, V, 4, V - 1, 0, 1.0, True, ng, 0.0)
     assert beam_idx == [1, 0, 3, 3] and moved == [1]
-    d.step(logp.to(dev), V, 4, ng, 0.0, V - 1, 0, 1.0, True)
+    d.step(logp.to(dev), V, 4, V - 1, 0, 1.0, True, ng=ng, pen=0.0)
     _compare(ref, d, beam_idx, moved, 'words')
     assert d.words.cpu().tolist() == words[:, [1, 0, 3, 3]].tolist()
     # without the word buffer the same step leaves it alone
     ref2, d2, _, _ = _small(dev, nb, V, [-1.0] * 4, 8, 9)
-    d2.step(logp.to(dev), V, 4, ng, 0.0, V - 1, 0, 1.0, True, words=False)
+    d2.step(logp.to(dev), V, 4, V - 1, 0, 1.0, True, words=False, ng=ng, pen=0.0)
     assert d2.beam_idx.tolist() == [1, 0, 3, 3] and torch.equal(d2.words.cpu().to(torch.int64), words)
     assert torch.equal(d2.ids.cpu(), ref.ids)
 
