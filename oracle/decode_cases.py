@@ -1,0 +1,478 @@
+"""ORACLE-side statement of the Transformer-XL decode-step kernels (test infrastructure, NOT product code): the first 350 lines of
+csrc/decode.hip (decode_embed_kernel, kv_append_kernel, decode_attn_kernel<16 / 32 / 64>, decode_bd_kernel), the mxl_decode_qkv
+epilogue of csrc/gemm_skinny.hip and the composite ops.relattn_decode (csrc/ = symbolic_music_generation_amd/csrc/).  Case tables,
+bf16-exact inputs generated on the CPU from zlib.crc32(case name), and for the two float kernels a reference in two forms:
+
+  float64 closed form  one decode-attention step: q' = bf16(q + r_w_bias); the score of ring slot s is
+                       (q' . k_s + BD[(t mod M - s) mod M]) scale; slots >= nvalid = min(t + 1, M) are zero memories (k = v = 0, the
+                       positional term alone) and count in the denominator; softmax over all M slots; out = sum_s p_s v_s.
+                       BD of the composite: bf16(q + r_r_bias) . rd[dist] (mxl_decode_bd / the batched GEMM).
+  rounded model        the same evaluation with the roundings the kernel source makes and every sum through ONE sequential float32
+                       accumulator (numpy cumsum).  It is NOT the expected value: gap(model, float64) is what the kernel's precision
+                       costs on a case, and 4 x the largest gap is the absolute term `b` of the rule of oracle/kernel_cases.py.
+
+Roundings modelled, with their sources (decode.hip):
+  q' = bf16(float32(q) + r_w_bias), one float32 sum, one bf16 rounding ........................................................ :137-139
+  score = (BD[dist] + sum_e q'_e k_se) scale in float32 (products of two bf16 values are exact; the model adds them in order) . :176-181
+  a never-written slot: score = BD[dist] scale ................................................................................ :204-208
+  the piece's own maximum m_k; p = __expf(score - m_k) in float32 (2^(x log2e), the product rounded) .......................... :222-232
+  l_k = float32 sum of the UNROUNDED p over the piece's written, then never-written slots .................................... :226-236
+  o_k = float32 sum of bf16(p) v over the written slots: P rounded to bf16 relative to the piece's own maximum ................ :247-249
+  one piece: out = o (1 / l) ................................................................................................. :236, :275
+  pieces: m = max m_k, out = (sum_k e^(m_k - m) o_k) / (sum_k e^(m_k - m) l_k) in piece order; an empty piece has m_k = -1e30,
+    o_k = l_k = 0 ............................................................................................................ :298-307
+  piece bounds: written part cut in pieces of ceil(nvalid / NS) rounded up to 32, never-written part in ceil((M - nvalid) / NS) :127-130
+  BD = float32 sum over dh = 64 of exact products (MFMA; the model adds them in order) ....................................... :338-342
+Bit-exact statements (no bound): ring slot t mod M <- the k / v thirds of the qkv row (decode.hip:50-56, gemm_skinny.hip:74-76, :99),
+qr = bf16(float32(q) + r_r_bias) (decode.hip:47, gemm_skinny.hip:98), embed = bf16(float32(E[id]) float32(scale)), an id outside [0, V)
+reads row 0 (decode.hip:22-28).
+
+Branches of the launch functions -> cases that take them (ST = 4 (64 / (dh / 8)) 16 slots per batch of the double-buffered loop):
+  decode_attn_kernel<64>  (ST = 512) ......... every d64_* / wrap_* / pc_mixed / pc_full / live_* / big_m16128 case
+  decode_attn_kernel<32>  (ST = 1024) ........ d32_*, m1000_dh32, pc_tail_empty
+  decode_attn_kernel<16>  (ST = 2048) ........ d16_*, pc_tiny
+  loop regime "one batch" (nvalid <= ST) ..... n1, n7, d64_n512_*, d32_n1024, d16_n2048
+  "kA then kB" (ST < nvalid <= 2 ST) ......... d64_n513_*, d64_n1024_*, d32_n1025, d16_n2049  (ST + 1: wave 0 alone takes kB)
+  "kA reloaded": the loop's second trip, kA alone (2 ST < nvalid <= 3 ST) ....... d64_n1025_*, d32_n2049, d16_n4097
+  the second trip takes kB as well (3 ST < nvalid <= 4 ST) ..................... d64_n1537_*, d32_n3073, d16_n6145
+  a third trip and more (nvalid > 4 ST) ......................................... d64_n2049_*, d32_n4097, d16_n8193, big_m16128 (32 batches)
+  nvalid = 1 / fewer keys than one wave ...... n1 / n7 (waves 1 to 3 hold nothing)
+  M = nvalid (no never-written slot) ......... d64_n*_full, wrap_*, pc_full, big_m16128
+  M not a multiple of 4, 32, 64 .............. m301, m1000_dh32, wrap_* (M = 301)
+  the shared-memory limit M = 16128 .......... big_m16128 (B = H = 1)
+  ring wrap t = M - 1, M, M + 1, 5 M + 3 ..... wrap_t300, wrap_t301, wrap_t302, wrap_t1508
+  pieces 1, 2, 3, 4, 8: every piece written and never-written / the last pieces without a written slot (EMPTY written pieces) /
+    no never-written slot / nvalid < pieces .. pc_mixed / pc_tail_empty / pc_full / pc_tiny
+  pieces longer than ST (lo != 0 in the loop) d64_n2049_above (2 pieces of 1056), d16_n8193 (4 of 2080), big_m16128 (8 of 2016)
+  live mask (mxl_relattn_decode_split_live) .. live_p1 (one piece), live_p4 (four pieces): finished rows are zero rows
+  decode_bd_kernel: batch fragments B = 1, 15, 16, 17, 48, 49, 64; M < 64, M & 3 != 0 (scalar stores), r + 3 >= M, ld_qr = d + 8 and
+    ld_rd = d + 16 ........................... BD_CASES
+  BD route mxl_decode_bd (dh = 64, B <= 64) .. cmp_bd (rd with a row stride of d + 16), qr_ready False and True
+  BD route batched GEMM ...................... cmp_gemm_dh32 (dh = 32), cmp_gemm_b65 (B = 65, M = 64)
+  mxl_decode_qkv with e0 != 0 ................ every QKV_CASES row with dh = 64 (e0 = 16, 32, 48) or dh = 32 (e0 = 16)
+
+Input families of the attention cases (`families(case, pieces)`):
+  random     everything drawn
+  edges<i>   the positional term favours a set of slots -- 0, nvalid - 1, t mod M (the newest), (t + 1) mod M (the oldest once the
+             ring has wrapped), the first and last slot of every written and never-written piece, lo + ST - 1, lo + ST, lo + 2 ST - 1,
+             lo + 2 ST of every piece -- whose value rows are large and mutually distinct; the set is cut into chunks of at most
+             EDGE_CHUNK slots (edges0, edges1, ..: same shape, the next part of the set), so that every favoured slot holds at least
+             1 / (2 |chunk|) of a row's probability and dropping any one of them leaves the bound
+  phantom    (nvalid < M) most of the mass on one never-written slot: the output is near zero, and only a correct denominator gives that
+"""
+import functools
+import math
+import zlib
+
+import numpy as np
+import torch
+
+from oracle.kernel_cases import bf16_exact, gap
+
+F32 = np.float32
+LOG2E_F32 = F32(1.4426950408889634)
+EDGE_CHUNK = 12
+M_LIMIT = 16128          # relattn_decode_launch: M * 4 + 1024 bytes of dynamic shared memory <= 64 KiB
+
+
+def _gen(name):
+    return torch.Generator().manual_seed(zlib.crc32(name.encode()))
+
+
+def _bf(x):
+    """numpy float32 -> the nearest bf16 value, as float32"""
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=F32)).to(torch.bfloat16).float().numpy()
+
+
+def _expf(x):
+    """the fast float32 exponential: 2^(x log2e), the product rounded to float32"""
+    with np.errstate(over='ignore', under='ignore'):
+        return np.exp2((x.astype(F32) * LOG2E_F32).astype(F32)).astype(F32)
+
+
+def _seqsum(x, axis=-1, dt=F32):
+    """ONE sequential accumulator along `axis` in `dt` (numpy's cumsum adds in order)"""
+    if x.shape[axis] == 0:
+        return np.zeros(np.delete(x.shape, axis), dtype=dt)
+    return np.take(np.cumsum(x, axis=axis, dtype=dt), -1, axis=axis)
+
+
+def steps_per_batch(dh):
+    """ST: the slots one batch of the double-buffered loop covers"""
+    return 4 * (64 // (dh // 8)) * 16
+
+
+def piece_bounds(nvalid, M, NS):
+    """the kernel's pieces: [(lo, hi, plo, phi)] -- written slots [lo, hi), never-written slots [plo, phi) of piece zi"""
+    piece = ((((nvalid + NS - 1) // NS) + 31) & ~31) if NS > 1 else nvalid
+    ppiece = (M - nvalid + NS - 1) // NS
+    out = []
+    for zi in range(NS):
+        lo = min(zi * piece, nvalid)
+        plo = min(nvalid + zi * ppiece, M)
+        out.append((lo, min(lo + piece, nvalid), plo, min(plo + ppiece, M)))
+    return out
+
+
+# ======================================================================================================================== attention cases
+def _a(name, dh, M, t, pieces=(1,), B=2, H=2, live=None):
+    return dict(name=name, dh=dh, M=M, t=t, pieces=tuple(pieces), B=B, H=H, live=live, nvalid=min(t + 1, M), tm=t % M)
+
+
+def _attn_cases():
+    rows = [_a('n1', 64, 96, 0), _a('n7', 64, 70, 6)]
+    for n in (512, 513, 1024, 1025, 1537, 2049):                     # ST, ST + 1, 2 ST, 2 ST + 1, 3 ST + 1, 4 ST + 1 for dh = 64
+        # (the longest also in two pieces: the second piece runs the kA / kB / kA-reloaded trips from lo = 1056)
+        rows += [_a(f'd64_n{n}_above', 64, n + 5, n - 1, B=2 + n % 2, H=3 - n % 2, pieces=(1, 2) if n == 2049 else (1,)),
+                 _a(f'd64_n{n}_full', 64, n, n - 1)]
+    for n in (1024, 1025, 2049, 3073, 4097):
+        rows.append(_a(f'd32_n{n}', 32, n + 63, n - 1))
+    for n in (2048, 2049, 4097, 6145, 8193):
+        rows.append(_a(f'd16_n{n}', 16, n + 63, n - 1, pieces=(1, 4) if n == 8193 else (1,)))
+    rows += [
+        _a('big_m16128', 64, M_LIMIT, M_LIMIT + 100, pieces=(1, 8), B=1, H=1),
+        _a('m301', 64, 301, 200, B=3), _a('m1000_dh32', 32, 1000, 700, H=3),
+        _a('wrap_t300', 64, 301, 300), _a('wrap_t301', 64, 301, 301), _a('wrap_t302', 64, 301, 302), _a('wrap_t1508', 64, 301, 1508, B=3),
+        _a('pc_mixed', 64, 1064, 1023, pieces=(1, 2, 3, 4, 8)),
+        _a('pc_tail_empty', 32, 128, 39, pieces=(1, 2, 3, 4, 8), H=3),
+        _a('pc_full', 64, 1000, 2003, pieces=(1, 2, 3, 4, 8)),
+        _a('pc_tiny', 16, 96, 2, pieces=(1, 2, 3, 4, 8), B=3),
+        _a('live_p1', 64, 301, 150, pieces=(1,), B=3, live=(1, 0, 1)),
+        _a('live_p4', 64, 1064, 1023, pieces=(4,), B=3, live=(0, 1, 1)),
+    ]
+    return {r['name']: r for r in rows}
+
+
+ATTN_CASES = _attn_cases()
+
+
+def favoured_slots(c, pieces):
+    """the slots where the kernel's index arithmetic changes, sorted"""
+    M, nv, ST = c['M'], c['nvalid'], steps_per_batch(c['dh'])
+    s = {0, nv - 1, c['tm'], (c['t'] + 1) % M}
+    for lo, hi, plo, phi in piece_bounds(nv, M, pieces):
+        if hi > lo:
+            s |= {lo, hi - 1} | {x for x in (lo + ST - 1, lo + ST, lo + 2 * ST - 1, lo + 2 * ST) if x < hi}
+        if phi > plo:
+            s |= {plo, phi - 1}
+    return sorted(s)
+
+
+def edge_chunks(c, pieces):
+    f = favoured_slots(c, pieces)
+    n = -(-len(f) // EDGE_CHUNK)
+    size = -(-len(f) // n)
+    return [f[i * size:(i + 1) * size] for i in range(n)]
+
+
+def phantom_slot(c):
+    """the never-written slot a phantom case favours"""
+    return (c['nvalid'] + c['M']) // 2
+
+
+def families(c, pieces):
+    out = ['random'] + [f'edges{i}' for i in range(len(edge_chunks(c, pieces)))]
+    return out + (['phantom'] if c['nvalid'] < c['M'] else [])
+
+
+def scale_of(dh):
+    """the float32 the C ABI receives"""
+    return float(F32(dh ** -0.5))
+
+
+@functools.lru_cache(maxsize=8)
+def attn_case(name, family, pieces=1):
+    """inputs of one attention case (`pieces` only selects the favoured set of an edges family): qkv (B, 3d) bf16 whose first third is
+    q, kc / vc (B, H, M, dh) bf16 with zeros in the never-written slots, bd (B, H, M) f32, rwb (H, dh) f32 -- all bf16-exact -- and
+    fav: the favoured slots"""
+    c = dict(ATTN_CASES[name])
+    B, H, dh, M, nv, tm = (c[k] for k in ('B', 'H', 'dh', 'M', 'nvalid', 'tm'))
+    d = H * dh
+    g = _gen(f'{name}/{family}/{pieces if family.startswith("edges") else 0}')
+    r = lambda *s: torch.randn(*s, generator=g)
+    scale = scale_of(dh)
+    qkv = bf16_exact(r(B, 3 * d)).float()
+    rwb = bf16_exact(r(H, dh) * 0.3).float()
+    v = r(B, H, M, dh)
+    fav = []
+    if family == 'random':
+        k, bd = r(B, H, M, dh), r(B, H, M) * 2
+    else:
+        # quiet background: content scores of a standard deviation of 1/8, positional scores of `scale`; the favoured slots sit
+        # ln(M) + 4 above it with a jitter of +-0.15, so that together they hold 98 % of a row and share it about evenly
+        k = r(B, H, M, dh) * (0.125 / (math.sqrt(dh) * scale))
+        bd = r(B, H, M)
+        fav = [phantom_slot(c)] if family == 'phantom' else edge_chunks(c, pieces)[int(family[5:])]
+        lift = (math.log(M) + (6.0 if family == 'phantom' else 4.0)) / scale
+        for i, s in enumerate(fav):
+            bd[:, :, (tm - s) % M] = lift + (torch.rand(B, H, generator=g) * 0.3 - 0.15) / scale
+            # large and mutually distinct value rows: magnitudes 2 .. 4, a sign pattern of their own
+            v[:, :, s] = (2.0 + 2.0 * torch.rand(B, H, dh, generator=g)) * torch.where(torch.rand(B, H, dh, generator=g) < 0.5, -1.0, 1.0)
+    k, v = bf16_exact(k).float(), bf16_exact(v).float()
+    k[:, :, nv:] = 0
+    v[:, :, nv:] = 0
+    c.update(d=d, scale=scale, family=family, qkv=qkv, q=qkv[:, :d].reshape(B, H, dh), rwb=rwb, kc=k, vc=v, bd=bf16_exact(bd).float(),
+             fav=fav)
+    return c
+
+
+def q_biased(q, bias):
+    """bf16(float32(q) + bias): (B, H, dh) float32 numpy"""
+    return _bf(q.numpy().astype(F32) + bias.numpy().astype(F32))
+
+
+def attn_ref64(c, bd=None, drop=(), shift=0, no_phantom_den=False, merge_as=None):
+    """float64 closed form -> (out (B, H, dh), p (B, H, M)) as float64 tensors.  `bd`: another positional term (the composite's).
+    Planted faults: `drop` a set of slots removed from the softmax; `shift` the distance off by that much; `no_phantom_den` the
+    never-written slots left out of the denominator; `merge_as` = (pieces, j): the merge of `pieces` pieces with piece j's maximum
+    taken for every piece's own.  (In exact arithmetic the subtrahend m of sum_k e^(m_k - m) o_k / sum_k e^(m_k - m) l_k cancels, so
+    a wrong GLOBAL maximum changes nothing but the range; the fault that does not cancel is m_j in the place of m_k in the factor,
+    i.e. partials that were scaled by different maxima added as they are.)"""
+    M, nv, tm = c['M'], c['nvalid'], c['tm']
+    qw = q_biased(c['q'], c['rwb']).astype(np.float64)
+    k, v = c['kc'].numpy().astype(np.float64), c['vc'].numpy().astype(np.float64)
+    bdv = (c['bd'] if bd is None else bd).numpy().astype(np.float64)
+    dist = (tm - np.arange(M) + shift) % M
+    s = (np.einsum('bhe,bhse->bhs', qw, k) + bdv[:, :, dist]) * c['scale']
+    if drop:
+        s[:, :, sorted(drop)] = -np.inf
+    if merge_as is None:
+        e = np.exp(s - s.max(-1, keepdims=True))
+        den = (e[:, :, :nv] if no_phantom_den else e).sum(-1, keepdims=True)
+        p = e / den
+        return torch.from_numpy(np.einsum('bhs,bhse->bhe', p, v)), torch.from_numpy(p)
+    pieces, j = merge_as
+    num, den = 0.0, 0.0
+    for lo, hi, plo, phi in piece_bounds(nv, M, pieces):
+        idx = np.r_[lo:hi, plo:phi]
+        if len(idx) == 0:
+            continue
+        e = np.exp(s[:, :, idx] - s[:, :, idx].max(-1, keepdims=True))
+        num = num + np.einsum('bhs,bhse->bhe', e, v[:, :, idx])
+        den = den + e.sum(-1, keepdims=True)
+    return torch.from_numpy(num / den), None
+
+
+def piece_maxima(c, pieces):
+    """float64 maxima of the pieces' scores -> (B, H, pieces); -inf for an empty piece"""
+    M, nv, tm = c['M'], c['nvalid'], c['tm']
+    qw = q_biased(c['q'], c['rwb']).astype(np.float64)
+    s = (np.einsum('bhe,bhse->bhs', qw, c['kc'].numpy().astype(np.float64)) + c['bd'].numpy().astype(np.float64)[:, :, (tm - np.arange(M)) % M])
+    s = s * c['scale']
+    out = np.full(s.shape[:2] + (pieces,), -np.inf)
+    for z, (lo, hi, plo, phi) in enumerate(piece_bounds(nv, M, pieces)):
+        idx = np.r_[lo:hi, plo:phi]
+        if len(idx):
+            out[:, :, z] = s[:, :, idx].max(-1)
+    return out
+
+
+def attn_model(c, pieces=1, bd=None):
+    """the rounded model of one launch with `pieces` pieces -> out (B, H, dh) float64 tensor, before the bf16 rounding of the output"""
+    M, nv, tm = c['M'], c['nvalid'], c['tm']
+    qw = q_biased(c['q'], c['rwb'])
+    k, v = c['kc'].numpy().astype(F32), c['vc'].numpy().astype(F32)
+    bdv = (c['bd'] if bd is None else bd).numpy().astype(F32)
+    scale = F32(c['scale'])
+    dist = (tm - np.arange(M)) % M
+    terms = np.concatenate([bdv[:, :, dist, None], qw[:, :, None, :] * k], -1)         # (a zero-memory slot adds zeros: BD alone)
+    sc = (_seqsum(terms) * scale).astype(F32)
+    parts = []
+    for lo, hi, plo, phi in piece_bounds(nv, M, pieces):
+        idx = np.r_[lo:hi, plo:phi]
+        if len(idx) == 0:
+            parts.append((np.full(sc.shape[:2], F32(-1e30)), np.zeros(sc.shape[:2] + (c['dh'],), F32), np.zeros(sc.shape[:2], F32)))
+            continue
+        mx = sc[:, :, idx].max(-1)
+        pw = _expf(sc[:, :, lo:hi] - mx[..., None])
+        pp = _expf(sc[:, :, plo:phi] - mx[..., None])
+        l = _seqsum(np.concatenate([pw, pp], -1))
+        o = _seqsum((_bf(pw)[..., None] * v[:, :, lo:hi]).astype(F32), axis=2)
+        parts.append((mx, o, l))
+    if pieces == 1:
+        mx, o, l = parts[0]
+        return torch.from_numpy((o * (F32(1) / l)[..., None]).astype(np.float64))
+    m = np.max(np.stack([p[0] for p in parts]), 0)
+    num, den = np.zeros_like(parts[0][1]), np.zeros_like(parts[0][2])
+    for mx, o, l in parts:
+        a = _expf(mx - m)
+        num = (num + (a[..., None] * o).astype(F32)).astype(F32)
+        den = (den + (a * l).astype(F32)).astype(F32)
+    return torch.from_numpy((num / den[..., None]).astype(np.float64))
+
+
+def live_zeroed(c, out):
+    """rows of finished sequences are zero rows"""
+    if c['live'] is None:
+        return out
+    return out * torch.tensor(c['live'], dtype=out.dtype).view(-1, 1, 1)
+
+
+def dense_check(c, bd=None):
+    """the same step through oracle/relattn_ref.relattn_dense in float64: one query at position 0 over M key positions -(M - 1) .. 0,
+    the key at distance D being ring slot (t mod M - D) mod M (zero memories where never written).  relattn_dense builds its
+    positional term from a table and a bias, so the given BD (B, H, M) rides in B extra head columns: the query of sequence b carries a
+    one in column dh + b, the table row of distance D carries BD[b, h, D] there, and the keys carry zeros -> out (B, H, dh)"""
+    from oracle.relattn_ref import relattn_dense
+    B, H, dh, M, tm = c['B'], c['H'], c['dh'], c['M'], c['tm']
+    qw = torch.from_numpy(q_biased(c['q'], c['rwb'])).double()
+    bdv = (c['bd'] if bd is None else bd).double()
+    slot_of_pos = (tm - (M - 1 - torch.arange(M))) % M                   # key j of the position order has distance M - 1 - j
+    z = torch.zeros(B, M, H, B, dtype=torch.float64)
+    k = torch.cat([c['kc'].double()[:, :, slot_of_pos].transpose(1, 2), z], -1)
+    v = torch.cat([c['vc'].double()[:, :, slot_of_pos].transpose(1, 2), z], -1)
+    q = torch.cat([torch.zeros(B, 1, H, dh, dtype=torch.float64), torch.eye(B, dtype=torch.float64)[:, None, None, :].expand(B, 1, H, B)], -1)
+    qk = torch.cat([qw[:, None], torch.zeros(B, 1, H, B, dtype=torch.float64)], -1)
+    rd = torch.cat([torch.zeros(M, H, dh, dtype=torch.float64), bdv.permute(2, 1, 0)], -1)
+    zero = torch.zeros(H, dh + B, dtype=torch.float64)
+    # relattn_dense adds ONE query to both biases; the content and positional operands differ here, so the biases carry the difference
+    outs = []
+    for b in range(B):
+        o, _ = relattn_dense(q[b:b + 1], k[b:b + 1], v[b:b + 1], rd, (qk[b, 0] - q[b, 0]), zero, M, scale=c['scale'], dtype=torch.float64)
+        outs.append(o[0, 0, :, :dh])
+    return torch.stack(outs)
+
+
+# ======================================================================================================================== mxl_decode_bd
+def _bd(B, M, H, strided):
+    return dict(name=f'bd_b{B}_m{M}_h{H}{"_ld" if strided else ""}', B=B, M=M, H=H, strided=strided)
+
+
+BD_CASES = {r['name']: r for r in [
+    _bd(1, 1, 1, False), _bd(15, 63, 3, True), _bd(16, 64, 1, False), _bd(17, 65, 3, True), _bd(48, 255, 1, True), _bd(49, 256, 3, False),
+    _bd(64, 257, 1, True), _bd(1, 300, 3, False), _bd(17, 301, 3, True), _bd(64, 1028, 3, False), _bd(49, 1028, 1, True),
+    _bd(16, 63, 3, False), _bd(48, 300, 1, True), _bd(15, 256, 1, False)]}
+
+
+@functools.lru_cache(maxsize=4)
+def bd_case(name):
+    """qr (B, d) and rd (M, d) bf16-exact; ld_qr = d + 8, ld_rd = d + 16 where `strided`"""
+    c = dict(BD_CASES[name])
+    g = _gen(name)
+    d = c['H'] * 64
+    c.update(d=d, dh=64, qr=bf16_exact(torch.randn(c['B'], d, generator=g)).float(), rd=bf16_exact(torch.randn(c['M'], d, generator=g)).float(),
+             ld_qr=d + (8 if c['strided'] else 0), ld_rd=d + (16 if c['strided'] else 0))
+    return c
+
+
+def bd_ref(qr, rd, H, dt=np.float64):
+    """BD[b, h, r] = sum_e qr[b, h, e] rd[r, h, e] -> (B, H, M) float64 tensor; float32: one sequential accumulator over e"""
+    B, M = qr.shape[0], rd.shape[0]
+    a = qr.numpy().astype(dt).reshape(B, H, 1, -1)
+    b = rd.numpy().astype(dt).reshape(M, H, -1).transpose(1, 0, 2)[None]
+    return torch.from_numpy(_seqsum(a * b, dt=dt).astype(np.float64))
+
+
+# ======================================================================================================================== ring writers
+# (B, d, dh, Mring, t): dh = 64 / 32 give e0 in {16, 32, 48} / {16}; B = 1 and 64; no Mring is a power of two; t below, at, beyond Mring
+QKV_CASES = [(1, 128, 64, 40, 0), (64, 128, 64, 40, 40), (5, 192, 64, 37, 100), (3, 96, 32, 24, 23), (64, 64, 32, 7, 38),
+             (2, 128, 64, 301, 301), (7, 128, 16, 40, 97)]
+
+
+def qkv_case(B, d, dh, Mring, t):
+    """x (B, d), w (3d, d) bf16; rrb (d,) f32 bf16-exact; prior ring contents kc0 / vc0 (B, H, Mring, dh) bf16"""
+    g = _gen(f'qkv_{B}_{d}_{dh}_{Mring}_{t}')
+    H = d // dh
+    return dict(x=bf16_exact(torch.randn(B, d, generator=g)), w=bf16_exact(torch.randn(3 * d, d, generator=g) * 0.1),
+                rrb=bf16_exact(torch.randn(d, generator=g) * 0.2).float(), kc0=bf16_exact(torch.randn(B, H, Mring, dh, generator=g)),
+                vc0=bf16_exact(torch.randn(B, H, Mring, dh, generator=g)))
+
+
+def ring_expect(qkv, ring0, third, t):
+    """plain indexing: ring[b, h, t mod M, e] = qkv[b, third d + h dh + e], every other slot as it was"""
+    B, H, M, dh = ring0.shape
+    d = H * dh
+    out = ring0.clone()
+    out[:, :, t % M] = qkv[:, third * d:(third + 1) * d].reshape(B, H, dh)
+    return out
+
+
+def qr_expect(qkv, rrb, d):
+    return (qkv[:, :d].float() + rrb.float()).to(torch.bfloat16)
+
+
+# ======================================================================================================================== mxl_decode_embed
+# (B, d, V, T columns of ids, ld_ids, t): t in the last column everywhere but the last row of the table
+EMBED_CASES = [(3, 8, 5, 4, 4, 3), (33, 520, 97, 6, 11, 5), (64, 768, 1190, 9, 16, 8), (2, 64, 7, 5, 9, 0)]
+
+
+def embed_case(B, d, V, T, ld, t):
+    """ids (B, ld) int64 whose first T columns are the row; column t names -1 in row 0 and V in the last row (both read table row 0)"""
+    g = _gen(f'emb_{B}_{d}_{V}_{T}_{ld}_{t}')
+    ids = torch.randint(0, V, (B, ld), generator=g)
+    ids[:, T:] = 10 ** 12                       # the columns past the row are never read
+    ids[0, t] = -1
+    ids[B - 1, t] = V
+    E = bf16_exact(torch.randn(V, d, generator=g))
+    scale = float(F32(math.sqrt(d)))
+    idc = ids[:, t].clone()
+    idc[(idc < 0) | (idc >= V)] = 0
+    want = (E.float()[idc] * torch.tensor(scale, dtype=torch.float32)).to(torch.bfloat16)
+    return dict(ids=ids, E=E, scale=scale, want=want)
+
+
+# ======================================================================================================================== composite
+def _cmp(name, dh, B, H, M, t, ld_rd_pad=0):
+    return dict(name=name, dh=dh, B=B, H=H, M=M, t=t, nvalid=min(t + 1, M), tm=t % M, live=None, ld_rd_pad=ld_rd_pad)
+
+
+COMPOSITE_CASES = {r['name']: r for r in [
+    _cmp('cmp_bd', 64, 3, 2, 301, 200, ld_rd_pad=16), _cmp('cmp_gemm_dh32', 32, 3, 2, 200, 120), _cmp('cmp_gemm_b65', 64, 65, 2, 64, 40)]}
+
+
+@functools.lru_cache(maxsize=2)
+def composite_case(name):
+    """ops.relattn_decode from q, rd, r_r_bias: the ring's newest slot holds the k / v thirds of the qkv row (as after kv_append)"""
+    c = dict(COMPOSITE_CASES[name])
+    B, H, dh, M, nv, tm = (c[k] for k in ('B', 'H', 'dh', 'M', 'nvalid', 'tm'))
+    d = H * dh
+    g = _gen(name)
+    r = lambda *s: torch.randn(*s, generator=g)
+    qkv = bf16_exact(r(B, 3 * d)).float()
+    k, v = bf16_exact(r(B, H, M, dh)).float(), bf16_exact(r(B, H, M, dh)).float()
+    k[:, :, nv:] = 0
+    v[:, :, nv:] = 0
+    k[:, :, tm] = qkv[:, d:2 * d].reshape(B, H, dh)
+    v[:, :, tm] = qkv[:, 2 * d:].reshape(B, H, dh)
+    c.update(d=d, scale=scale_of(dh), qkv=qkv, q=qkv[:, :d].reshape(B, H, dh), kc=k, vc=v, rwb=bf16_exact(r(H, dh) * 0.3).float(),
+             rrb=bf16_exact(r(H, dh) * 0.3).float(), rd=bf16_exact(r(M, d) * 0.5).float())
+    return c
+
+
+def composite_bd(c, dt=np.float64):
+    """BD (B, H, M) of the composite: bf16(q + r_r_bias) . rd[dist]"""
+    qr = torch.from_numpy(q_biased(c['q'], c['rrb'])).reshape(c['B'], c['d'])
+    return bd_ref(qr, c['rd'], c['H'], dt)
+
+
+def composite_ref64(c):
+    return attn_ref64(c, bd=composite_bd(c))[0]
+
+
+def composite_model(c):
+    return attn_model(c, 1, bd=composite_bd(c, F32))
+
+
+# ======================================================================================================================== gaps
+def attn_arms():
+    """every (case name, pieces, family) the tests run"""
+    for name, c in ATTN_CASES.items():
+        for p in c['pieces']:
+            for f in families(c, p):
+                yield name, p, f
+
+
+def attn_gap(name, pieces, family):
+    """gap of the rounded model of one arm against the float64 closed form, relative to max|ref|"""
+    c = attn_case(name, family, pieces)
+    return gap(attn_model(c, pieces), attn_ref64(c)[0])
+
+
+def bd_gap(name):
+    c = bd_case(name)
+    return gap(bd_ref(c['qr'], c['rd'], c['H'], F32), bd_ref(c['qr'], c['rd'], c['H']))
+
+
+def composite_gap(name):
+    c = composite_case(name)
+    return gap(composite_model(c), composite_ref64(c))
