@@ -6,7 +6,6 @@ tests/test_group_beam_cpu.py ties it to generate.beam_search and generate.group_
 are formed in f32 on both sides, product, difference and sum each rounded on its own (at ng = 1 the one sum), so indices, tokens,
 ids, words, running scores, store contents and flags are compared exactly and only the length-normalised scores (powf against
 Python's **) to rtol 1e-6."""
-import numpy as np
 import torch
 
 NEG = float('-inf')
@@ -163,46 +162,3 @@ def distinct_logp(rows, ldl, g):
     """pairwise distinct values in (-6, -1), spaced 5 / (rows * ldl) apart"""
     n = rows * ldl
     return (-1.0 - 5.0 * torch.randperm(n, generator=g).to(torch.float64) / n).to(torch.float32).view(rows, ldl)
-
-
-# ---------------------------------------------------------------------------------------------------------------- rules
-def host_allowed(grammar, Tp=0, n_bars=None, rule=None, keys=None):
-    """the `allowed` callable of generate.beam_search / group_beam_search for these rules, from the host walkers: every row of ids[:, :cur_len] is walked
-    from its start by TokenGrammar.walk, walk_budget, walk_bars (the generated part, from n_bars) and KeyRule.walk, and the words
-    they end in admit what mxl_rules_mask admits.  A row that the walk itself rejects (the kept -inf continuation of a dead row) is
-    barred whole: it is dead on either side."""
-    V = (grammar.vocab_size if grammar is not None else rule.vocab_size)
-
-    def allowed(ids):
-        out = np.ones((ids.shape[0], V), dtype=bool)
-        for r, row in enumerate(ids.tolist()):
-            if grammar is not None:
-                cls = grammar.cls.astype(np.int64)
-                s, bad = grammar.walk(row)
-                if bad >= 0:
-                    out[r] = False
-                    continue
-                out[r] &= ((int(grammar.allow[s]) >> cls) & 1) == 1
-                bud = grammar.budget
-                if bud is not None:
-                    bar, rem, bad = grammar.walk_budget(row)
-                    if bad >= 0:
-                        out[r] = False
-                        continue
-                    if bar > 0:
-                        out[r] &= bud.slots.astype(np.int64) <= rem
-                        deny = bud.need_free if rem <= 0 else bud.need_full
-                        out[r] &= ((deny >> cls) & 1) == 0
-                if n_bars is not None:
-                    left, bad = grammar.walk_bars(row[Tp:], n_bars)
-                    if bad >= 0:
-                        out[r] = False
-                        continue
-                    cnt = grammar.bar_count
-                    deny = cnt.end if left > 0 else (cnt.count if left == 0 else 0)
-                    out[r] &= ((deny >> cls) & 1) == 0
-            if rule is not None:
-                key, _ = rule.walk(row, -1 if keys is None else keys[r], len(row))
-                out[r] &= rule.allowed(key)
-        return torch.from_numpy(out)
-    return allowed

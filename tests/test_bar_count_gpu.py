@@ -17,6 +17,7 @@ from symbolic_music_generation_amd.generate import (bars_after_prompt, check_bar
                                                     sampling_config, stop_config, strip_left_pad)
 from symbolic_music_generation_amd.grammar import MUSIC_BAR_COUNT_CLASSES, MUSIC_CLASSES, MUSIC_TRANSITIONS, from_transitions, music_budget_tables
 from symbolic_music_generation_amd.vocab import MusicVocabulary
+from tests.rules_ref import Rules, Words, fresh_generate, keep_rows, move, token_ids
 
 pytestmark = pytest.mark.gpu
 
@@ -46,12 +47,8 @@ def _length(Tp, k):
     return Tp + BAR_TOKENS * (k + 1)
 
 
-def _ids(text):
-    return [VOC.t2i(t) for t in text.split()]
-
-
 def _heads(n, dev):
-    return torch.tensor([_ids(HEAD)] * n, dtype=torch.int64, device=dev)
+    return torch.tensor([token_ids(VOC, HEAD)] * n, dtype=torch.int64, device=dev)
 
 
 @pytest.fixture(scope='module')
@@ -65,11 +62,6 @@ def xl(dev):
 def _fresh(m, n, length, seed=5):
     from symbolic_music_generation_amd.generate import XLDecoder
     return XLDecoder(m.engine, n, length, seed=seed)
-
-
-def _gen(m, ids, **kw):
-    m._decoder = None
-    return m.generate(input_ids=ids, **kw)
 
 
 def _assert_rows_end_after_k_bars(out, g, ks, Tp, mask=None, width=True):
@@ -91,17 +83,20 @@ def _assert_rows_end_after_k_bars(out, g, ks, Tp, mask=None, width=True):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1. the op pair
+LEFTS = [-1, 0, 1, 3, 0]
+
+
 def test_mask_and_advance_equal_the_host_rule(dev):
     from symbolic_music_generation_amd import ops
     g = _grammar()
     cnt = g.bar_count
-    lefts = [-1, 0, 1, 3, 0]
+    lefts = LEFTS
     torch.manual_seed(3)
     logp = torch.randn(5, V + 3)
     lp = logp.to(dev)[:, :V]                                       # a row stride that is not V
     gleft = torch.tensor(lefts, device=dev, dtype=torch.int32)
     ops.rules_mask(lp, V, None, grammar=g, gleft=gleft)                # the count alone
-    keep = torch.tensor([[cnt.allows(left, int(g.cls[v])) for v in range(V)] for left in lefts])
+    keep = keep_rows(Rules(g, automaton=False, count=True), [Words(gleft=left) for left in lefts], V)
     got = lp.cpu()
     assert torch.equal(torch.isinf(got), ~keep) and torch.equal(got[keep], logp[:, :V][keep])
     assert keep[0].all() and not keep[1, BAR] and keep[1, EOS] and keep[2, BAR] and not keep[2, EOS] and not keep[3, EOS]
@@ -110,8 +105,8 @@ def test_mask_and_advance_equal_the_host_rule(dev):
     for tok in (BAR, EOS, VOC.t2i(PITCH), VOC.t2i('<melody>'), PAD):
         for unfinished in (live, None):
             ids = torch.zeros(5, 4, device=dev, dtype=torch.int64)
-            ids[:, 2] = tok
-            ids[3, 2] = V + 7 if tok == PAD else tok               # beyond the vocabulary: skipped
+            row_tok = [tok, tok, tok, V + 7 if tok == PAD else tok, tok]           # beyond the vocabulary: skipped
+            ids[:, 2] = torch.tensor(row_tok, device=dev)
             t = torch.full((1,), 2, device=dev, dtype=torch.int32)
             lefts2 = [-1, 0, 1, 3, 1]
             gleft = torch.tensor(lefts2, device=dev, dtype=torch.int32)
@@ -119,8 +114,9 @@ def test_mask_and_advance_equal_the_host_rule(dev):
             # the count alone; which rows chose their token is the stop group's word, here under an eos that no token is
             frozen = {} if u is None else dict(stop=(-1, PAD, 0), unfinished=u, alive=torch.zeros_like(t))
             ops.rules_advance(ids, t, grammar=g, gleft=gleft, **frozen)
-            c = int(g.cls[tok])
-            want = [cnt.move(left, c) if (unfinished is None or unfinished[b]) else left for b, left in enumerate(lefts2)]
+            rules = Rules(g, automaton=False, count=True, stop=None if u is None else (-1, PAD, 0))
+            want = [move(rules, Words(unfinished=1 if u is None else unfinished[b], gleft=left), k)[1].gleft
+                    for b, (left, k) in enumerate(zip(lefts2, row_tok))]
             assert gleft.tolist() == want, (tok, unfinished)
             if u is not None:
                 assert u.tolist() == live
@@ -224,14 +220,14 @@ def test_every_row_ends_after_its_number_of_bars(dev, xl, kw):
     ks = [0, 1, 2, 3]
     ids = _heads(4, dev)
     Tp = ids.shape[1]
-    out = _gen(xl, ids, max_length=_length(Tp, 3), grammar=g, n_bars=ks, seed=3, **STOP, **kw)
+    out = fresh_generate(xl, ids, max_length=_length(Tp, 3), grammar=g, n_bars=ks, seed=3, **STOP, **kw)
     assert torch.equal(out[:, :Tp], ids)
     _assert_rows_end_after_k_bars(out, g, ks, Tp)
     _assert_rows_end_after_k_bars(out.cpu(), g, ks, Tp)            # the host walks say the same
     # an int serves every row, and a tensor is taken as a list is
-    one = _gen(xl, ids, max_length=_length(Tp, 1), grammar=g, n_bars=1, seed=3, **STOP, **kw)
+    one = fresh_generate(xl, ids, max_length=_length(Tp, 1), grammar=g, n_bars=1, seed=3, **STOP, **kw)
     _assert_rows_end_after_k_bars(one, g, [1] * 4, Tp)
-    again = _gen(xl, ids, max_length=_length(Tp, 3), grammar=g, n_bars=torch.tensor(ks, device=dev), seed=3, **STOP, **kw)
+    again = fresh_generate(xl, ids, max_length=_length(Tp, 3), grammar=g, n_bars=torch.tensor(ks, device=dev), seed=3, **STOP, **kw)
     assert torch.equal(again, out)
 
 
@@ -241,8 +237,8 @@ def test_rows_without_a_limit_are_untouched(dev, xl):
     ids = _heads(4, dev)
     Tp = ids.shape[1]
     L = _length(Tp, 2)
-    out = _gen(xl, ids, max_length=L, grammar=g, n_bars=[2, -1, 0, -1], do_sample=False, **STOP)
-    free = _gen(xl, ids, max_length=L, grammar=g, do_sample=False, **STOP)
+    out = fresh_generate(xl, ids, max_length=L, grammar=g, n_bars=[2, -1, 0, -1], do_sample=False, **STOP)
+    free = fresh_generate(xl, ids, max_length=L, grammar=g, do_sample=False, **STOP)
     W = min(out.shape[1], free.shape[1])
     assert torch.equal(out[[1, 3], :W], free[[1, 3], :W])
     assert bars_after_prompt(out, g, prompt_len=Tp).tolist()[::2] == [2, 0]
@@ -253,7 +249,7 @@ def test_rows_without_a_limit_are_untouched(dev, xl):
 # ---------------------------------------------------------------------------------------------------------------- 5. it composes
 def test_left_padded_prompts(dev, xl):
     g = _grammar()
-    prompts = [torch.tensor(_ids(p)) for p in (HEAD, f'{HEAD} <melody> {PITCH} d_1',
+    prompts = [torch.tensor(token_ids(VOC, p)) for p in (HEAD, f'{HEAD} <melody> {PITCH} d_1',
                                                f'TimeSig_2/4 {TEMPO} {KEY} <bar> <melody> {PITCH} d_2 <bass>')]
     assert sorted(len(p) for p in prompts) == [3, 6, 8]
     ids, mask = left_pad(prompts, PAD)
@@ -261,7 +257,7 @@ def test_left_padded_prompts(dev, xl):
     Tp = ids.shape[1]
     ks = [1, 0, 2]
     for kw in (dict(do_sample=False), SAMPLE):
-        out = _gen(xl, ids, attention_mask=mask, max_length=_length(Tp, 2), grammar=g, n_bars=ks, **STOP, **kw)
+        out = fresh_generate(xl, ids, attention_mask=mask, max_length=_length(Tp, 2), grammar=g, n_bars=ks, **STOP, **kw)
         assert torch.equal(out[:, :Tp], ids)
         _assert_rows_end_after_k_bars(out, g, ks, Tp, mask)
         for row, p, k in zip(strip_left_pad(out, mask), prompts, ks):
@@ -275,11 +271,11 @@ def test_num_return_sequences(dev, xl):
     g = _grammar()
     ids = _heads(2, dev)
     Tp = ids.shape[1]
-    out = _gen(xl, ids, max_length=_length(Tp, 2), grammar=g, n_bars=[2, 0], num_return_sequences=2, **STOP, **SAMPLE)
+    out = fresh_generate(xl, ids, max_length=_length(Tp, 2), grammar=g, n_bars=[2, 0], num_return_sequences=2, **STOP, **SAMPLE)
     assert out.shape[0] == 4
     _assert_rows_end_after_k_bars(out, g, [2, 2, 0, 0], Tp)
     assert not torch.equal(out[0], out[1])                         # two continuations of the first prompt
-    out = _gen(xl, ids, max_new_tokens=BAR_TOKENS * 2, grammar=g, n_bars=[1, 0], num_return_sequences=2, **STOP, **SAMPLE)
+    out = fresh_generate(xl, ids, max_new_tokens=BAR_TOKENS * 2, grammar=g, n_bars=[1, 0], num_return_sequences=2, **STOP, **SAMPLE)
     _assert_rows_end_after_k_bars(out, g, [1, 1, 0, 0], Tp)
 
 
@@ -291,7 +287,7 @@ def test_two_lane_decoder(dev, xl):
     Tp = ids.shape[1]
     ks = [(i * 5) % 3 for i in range(n)]
     for kw in (dict(do_sample=False), SAMPLE):
-        out = _gen(xl, ids, max_length=_length(Tp, 2), grammar=g, n_bars=ks, **STOP, **kw)
+        out = fresh_generate(xl, ids, max_length=_length(Tp, 2), grammar=g, n_bars=ks, **STOP, **kw)
         assert isinstance(xl._decoder, XLDecoderLanes) and xl._decoder.n == 2
         _assert_rows_end_after_k_bars(out, g, ks, Tp)
         # each lane ran its own rows' counts: a lane alone gives the same rows
@@ -309,7 +305,7 @@ def test_graph_replay_equals_eager(dev, xl):
     ids = _heads(4, dev)
     Tp = ids.shape[1]
     for kw in (dict(do_sample=False), SAMPLE):
-        a, b = (_gen(xl, ids, max_length=_length(Tp, 3), grammar=g, n_bars=[3, 0, 1, 2], use_graph=graph, seed=8, **STOP, **kw)
+        a, b = (fresh_generate(xl, ids, max_length=_length(Tp, 3), grammar=g, n_bars=[3, 0, 1, 2], use_graph=graph, seed=8, **STOP, **kw)
                 for graph in (True, False))
         assert torch.equal(a, b)
         _assert_rows_end_after_k_bars(a, g, [3, 0, 1, 2], Tp)
@@ -355,7 +351,7 @@ def test_syntactic_grammar_bars_more_bars_and_an_early_end(dev, xl, kw):
     ids = _heads(4, dev)
     Tp = ids.shape[1]
     L = _length(Tp, 3)
-    out = _gen(xl, ids, max_length=L, grammar=g, n_bars=ks, seed=6, **STOP, **kw)
+    out = fresh_generate(xl, ids, max_length=L, grammar=g, n_bars=ks, seed=6, **STOP, **kw)
     assert out.shape[1] <= L and check_grammar(out, g).tolist() == [-1] * 4
     bars = bars_after_prompt(out, g, prompt_len=Tp).tolist()
     for b, row in enumerate(out[:, Tp:].tolist()):
@@ -412,8 +408,8 @@ def test_refusals_that_need_a_model(dev, xl):
     with pytest.raises(ValueError, match='no `end` token'):
         xl.generate(input_ids=ids, max_length=20, grammar=g, n_bars=1, eos_token_id=BAR)
     # a header without a bar: there is nothing to finish, and the only token that leads on is the <bar> that 0 bars
-    header = torch.tensor([_ids(f'TimeSig_2/4 {TEMPO} {KEY}')] * 2, device=dev)
+    header = torch.tensor([token_ids(VOC, f'TimeSig_2/4 {TEMPO} {KEY}')] * 2, device=dev)
     with pytest.raises(MusicXLError, match='n_bars = 0 for row 1'):
         xl.generate(input_ids=header, max_length=20, grammar=g, n_bars=[1, 0], **STOP)
-    out = _gen(xl, header, max_length=_length(3, 2), grammar=g, n_bars=[1, 2], do_sample=False, **STOP)
+    out = fresh_generate(xl, header, max_length=_length(3, 2), grammar=g, n_bars=[1, 2], do_sample=False, **STOP)
     assert bars_after_prompt(out, g, prompt_len=3).tolist() == [1, 2]

@@ -7,7 +7,7 @@ import torch
 from symbolic_music_generation_amd.generate import (XLDecoder, bars_after_prompt, beam_search, beam_search_device, check_bar_lengths,
                                                     check_grammar, check_in_key, contrastive_search_device)
 
-from tests.beam_ref import host_allowed
+from tests.rules_ref import host_allowed
 
 pytestmark = pytest.mark.gpu
 

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from symbolic_music_generation_amd.grammar import MUSIC_BAR_COUNT_CLASSES, BarCount
+from tests.rules_ref import Rules, Words, keep_rows, move
 from tests.test_bar_budget_gpu import BAR, EOS, PAD, V, VOC, _padded_grammar
 
 pytestmark = pytest.mark.gpu
@@ -19,28 +20,25 @@ def _grammar(vocab_size):
     return g
 
 
-def _allowed(g, state, bar, rem, left, v):
-    """the AND of the three host predicates for token v in a row at (state, bar, rem, left)"""
-    c = int(g.cls[v])
-    return bool((int(g.allow[state]) >> c) & 1) and g.budget.allows(bar, rem, c, int(g.budget.slots[v])) and g.bar_count.allows(left, c)
+#        state    bar rem left
+ROWS = [('B_D',    0,  0, -1),                                     # bar == 0: the budget leaves the row alone, and so does the count
+        ('B_D',   32,  0,  2),                                     # rem == 0: closers only; bars are owed, so no eos
+        ('M_P',   32,  5, -1),                                     # 0 < rem < bar: durations of at most 5 slots
+        ('B_D',   24,  0,  0),                                     # left == 0: no further bar, eos is the way on
+        ('M_T1',  32,  8,  3)]                                     # left > 0 inside a tuplet
 
 
 @pytest.mark.parametrize('vocab_size', [V, 2049])
 def test_mask_applies_every_group_in_one_pass(dev, vocab_size):
     """five rows, one per state of interest; a score row stride that is not V; min_length above and below the rows' length"""
     from symbolic_music_generation_amd import ops
-    g = _grammar(vocab_size)
-    #        state    bar rem left
-    rows = [('B_D',    0,  0, -1),                                 # bar == 0: the budget leaves the row alone, and so does the count
-            ('B_D',   32,  0,  2),                                 # rem == 0: closers only; bars are owed, so no eos
-            ('M_P',   32,  5, -1),                                 # 0 < rem < bar: durations of at most 5 slots
-            ('B_D',   24,  0,  0),                                 # left == 0: no further bar, eos is the way on
-            ('M_T1',  32,  8,  3)]                                 # left > 0 inside a tuplet
+    g, rows = _grammar(vocab_size), ROWS
     i32 = dict(device=dev, dtype=torch.int32)
     words = [torch.tensor(col, **i32) for col in zip(*[(g.state(s), bar, rem, left) for s, bar, rem, left in rows])]
     gstate, gbar, grem, gleft = words
     before = [w.clone() for w in words]
-    rule = torch.tensor([[_allowed(g, g.state(s), bar, rem, left, v) for v in range(vocab_size)] for s, bar, rem, left in rows])
+    host = [Words(gstate=g.state(s), gbar=bar, grem=rem, gleft=left) for s, bar, rem, left in rows]
+    rule = keep_rows(Rules(g, budget=True, count=True), host, vocab_size)
     assert rule[0, EOS] and not rule[1, EOS] and rule[1, BAR] and rule[3, EOS] and not rule[3, BAR] and not rule[4].all()
     assert 0 < int(rule[2].sum()) < int((torch.from_numpy(g.cls.astype('int64')) == g.class_names.index('duration')).sum())
     t = 6
@@ -51,9 +49,8 @@ def test_mask_applies_every_group_in_one_pass(dev, vocab_size):
         full = logp.to(dev)
         ops.rules_mask(full[:, :vocab_size], vocab_size, t_dev, stop=(EOS, PAD, min_length), grammar=g, gstate=gstate, gbar=gbar,
                        grem=grem, gleft=gleft)
-        keep = rule.clone()
-        if t + 1 < min_length:
-            keep[:, EOS] = False                                   # the eos bar
+        keep = keep_rows(Rules(g, budget=True, count=True, stop=(EOS, PAD, min_length)), host, vocab_size, cur_len=t + 1)
+        assert torch.equal(keep[:, EOS], rule[:, EOS] & (t + 1 >= min_length))            # the eos bar
         got = full.cpu()
         assert torch.equal(torch.isinf(got[:, :vocab_size]) & (got[:, :vocab_size] < 0), ~keep), min_length
         want = logp.clone()
@@ -68,7 +65,6 @@ def test_advance_moves_every_word_then_applies_the_stop_rule(dev):
     that were finished before the step, rows that emit eos in it, ids beyond the vocabulary"""
     from symbolic_music_generation_amd import ops
     g = _grammar(V)
-    bud, cnt = g.budget, g.bar_count
     toks = [VOC.t2i(t) for t in ('TimeSig_3/4', 'TimeSig_rare', '<melody>', '<bass>', 'd_1/8', 'd_6', 'd_rare', 'p_r', '<bar>', '</tup>',
                                  '</s>')] + [V + 7]
     n = 300
@@ -87,15 +83,11 @@ def test_advance_moves_every_word_then_applies_the_stop_rule(dev):
     alive = torch.full((1,), -5, **i32)
     ops.rules_advance(ids, t, stop=(EOS, PAD, 0), unfinished=unfinished, alive=alive, grammar=g, gstate=gstate, gbar=gbar, grem=grem,
                       gleft=gleft)
-    want_tok, want_words, want_live = [], [], []
-    for b, k in enumerate(row_tok):
-        words = (states[b],) + bars[b] + (lefts[b],)
-        if live[b] and k < V:                                      # the row chose a token of the vocabulary: its words move
-            c = int(g.cls[k])
-            words = (int(g.next[states[b], c]),) + bud.move(*bars[b], c, int(bud.slots[k]), int(bud.bars[k])) + (cnt.move(lefts[b], c),)
-        want_words.append(words)
-        want_tok.append(k if live[b] else PAD)                     # a finished row holds pad and its old words
-        want_live.append(1 if live[b] and k != EOS else 0)
+    rules = Rules(g, budget=True, count=True, stop=(EOS, PAD, 0))
+    want = [move(rules, Words(live[b], states[b], *bars[b], lefts[b]), k) for b, k in enumerate(row_tok)]
+    want_tok, want_words, want_live = [k for k, _ in want], [tuple(w[1:5]) for _, w in want], [w.unfinished for _, w in want]
+    b = toks.index(V + 7)                                          # a live row, an id beyond the vocabulary: no word moves
+    assert live[b] and want_words[b] == (states[b],) + bars[b] + (lefts[b],)
     assert list(zip(gstate.tolist(), gbar.tolist(), grem.tolist(), gleft.tolist())) == want_words
     assert unfinished.tolist() == want_live and alive.tolist() == [sum(want_live)]
     assert ids[:, 2].tolist() == want_tok

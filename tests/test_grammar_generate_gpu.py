@@ -10,6 +10,7 @@ import torch
 
 from symbolic_music_generation_amd.generate import finish_at_eos
 from symbolic_music_generation_amd.vocab import MusicVocabulary
+from tests.rules_ref import Rules, Words, keep
 from tests.test_grammar_cpu import GOLD, TABLE, token_class, walk
 
 pytestmark = pytest.mark.gpu
@@ -55,8 +56,9 @@ def _states(out):
 
 
 def _allowed_mask(state):
-    ok = set(TABLE[state])
-    return torch.tensor([c in ok for c in CLASS_OF])
+    """(V,) bool: the tokens the grammar allows in the state of this name (tests/test_rules_ref_cpu.py: equal to TABLE's)"""
+    g = VOC.grammar()
+    return torch.from_numpy(keep(Rules(g), Words(gstate=g.state(state)), V))
 
 
 def _fresh(m, B, L, seed=5):
@@ -92,7 +94,7 @@ def test_rows_walk_clean_only_with_the_grammar(dev, kw):
 
 # ---------------------------------------------------------------------------------------------------------------- exactness
 def _host_masked_loop(m, prompt, L, seed, sampling):
-    """the reference: per step the decoder's log-probabilities, masked on the host with the test's walker, through the existing
+    """the reference: per step the decoder's log-probabilities, masked on the host at the states of the test's walker, through the existing
     unfused sampler and counter advance"""
     from symbolic_music_generation_amd import ops
     dec = _fresh(m, prompt.shape[0], L, seed)

@@ -8,7 +8,7 @@ from symbolic_music_generation_amd import generate as G
 from symbolic_music_generation_amd.generate import (XLDecoder, check_bar_lengths, check_grammar, check_in_key, group_beam_search,
                                                     group_beam_search_device)
 
-from tests.beam_ref import host_allowed
+from tests.rules_ref import host_allowed
 
 pytestmark = pytest.mark.gpu
 

@@ -11,6 +11,7 @@ from symbolic_music_generation_amd.generate import (bars_after_prompt, check_bar
                                                     sampling_config)
 from symbolic_music_generation_amd.grammar import NO_KEY, NO_PITCH, key_ordinal
 from symbolic_music_generation_amd.vocab import MusicTokenizer
+from tests.rules_ref import Rules, Words, fresh_generate, i32, keep_rows, move, tail, token_ids
 
 pytestmark = pytest.mark.gpu
 
@@ -25,14 +26,6 @@ P = [int(np.flatnonzero(RULE.pcs == pc)[0]) for pc in range(12)]   # one pitch t
 D1, D2, DH = (VOC.t2i(t) for t in ('d_1', 'd_2', 'd_1/2'))         # 8, 16 and 4 slots
 STOP = dict(eos_token_id=EOS, pad_token_id=PAD)
 C_MAJOR = key_ordinal('CMajor')
-
-
-def _i32(x, dev):
-    return torch.tensor(x, device=dev, dtype=torch.int32)
-
-
-def _ids(text):
-    return [VOC.t2i(t) for t in text.split()]
 
 
 # ---------------------------------------------------------------------------------------------------------------- kernel level
@@ -59,52 +52,42 @@ def _case_guides():
     return [[] if c[1] is None else list(c[1]) for c in CASES]
 
 
+RULES = Rules(G, budget=True, count=True, key_rule=RULE, guide=True, stop=(EOS, PAD, 0))
+
+
+def _case_words():
+    """the eight words of every case, as rules_ref.Words"""
+    return [Words(live, G.state(s), bar, rem, left, key, pos, force) for _, _, s, bar, rem, left, key, pos, force, live in CASES]
+
+
 def _host_keep():
     """(NB, V) bool: what the host rules admit in every case -- the guide's one token in a fed row, else the grammar, the budget,
     the count and the key together -- and the fed token of every row (-1 = none)"""
-    keep, fed = [], []
-    for (_, _, s, bar, rem, left, key, pos, force, _), g in zip(CASES, _case_guides()):
-        f = GUIDE.forced(pos, force, g)
-        fed.append(f)
-        st = G.state(s)
-        keep.append([(v == f) if f >= 0 else
-                     (bool((int(G.allow[st]) >> int(G.cls[v])) & 1) and G.budget.allows(bar, rem, int(G.cls[v]), int(G.budget.slots[v]))
-                      and G.bar_count.allows(left, int(G.cls[v])) and RULE.allows(key, v)) for v in range(V)])
-    return torch.tensor(keep), fed
+    fed = [GUIDE.forced(w.gpos, w.gforce, g) for w, g in zip(_case_words(), _case_guides())]
+    return keep_rows(RULES, _case_words(), V, _case_guides()), fed
 
 
 def _host_words(toks):
     """the eight words of every case after it kept toks[b] (a finished row keeps its words)"""
-    out = []
-    for (_, _, s, bar, rem, left, key, pos, force, live), g, tok in zip(CASES, _case_guides(), toks):
-        st = G.state(s)
-        if live:
-            c = int(G.cls[tok])
-            st = int(G.next[st, c])
-            bar, rem = G.budget.move(bar, rem, c, int(G.budget.slots[tok]), int(G.budget.bars[tok]))
-            left = G.bar_count.move(left, c)
-            key = RULE.move(key, tok)
-            pos, force = GUIDE.move(pos, force, len(g), c)
-            live = int(tok != EOS)
-        out.append((live, st, bar, rem, left, key, pos, force))
-    return [list(col) for col in zip(*out)]
+    after = [move(RULES, w, tok, len(g))[1] for w, g, tok in zip(_case_words(), _case_guides(), toks)]
+    return [list(col) for col in zip(*after)]
 
 
 class _State:
     """device words and tables of CASES, with canaries around the guide table"""
 
     def __init__(self, dev):
-        cols = list(zip(*[(live, G.state(s), bar, rem, left, key, pos, force) for _, _, s, bar, rem, left, key, pos, force, live in CASES]))
+        cols = list(zip(*_case_words()))
         self.start = [list(c) for c in cols]
-        self.words = [_i32(c, dev) for c in cols]
+        self.words = [i32(c, dev) for c in cols]
         table = torch.full((NB + 2, LD), -7, dtype=torch.int32)
         for b, g in enumerate(_case_guides()):
             table[b + 1, :len(g)] = torch.tensor(g, dtype=torch.int32)
         self.table_host = table.clone()
         self.table = table.to(dev)
         self.glen_host = [len(g) for g in _case_guides()]
-        self.glen = _i32(self.glen_host, dev)
-        self.alive = _i32([-5], dev)
+        self.glen = i32(self.glen_host, dev)
+        self.alive = i32([-5], dev)
 
     def kwargs(self, stop=True):
         un, gs, gbar, grem, gleft, gkey, gpos, gforce = self.words
@@ -145,7 +128,7 @@ def test_mask_equals_the_host_rules(dev):
     scores = _scores(dev)
     want = scores.cpu().clone()
     want[:, :V][~keep] = float('-inf')
-    ops.rules_mask(scores[:, :V], V, _i32([2], dev), **{k: v for k, v in st.kwargs().items() if k not in ('unfinished', 'alive')})
+    ops.rules_mask(scores[:, :V], V, i32([2], dev), **{k: v for k, v in st.kwargs().items() if k not in ('unfinished', 'alive')})
     got = scores.cpu()
     assert torch.equal(torch.isinf(got[:, :V]) & (got[:, :V] < 0), ~keep)
     assert torch.equal(got.view(torch.int32), want.view(torch.int32))
@@ -163,27 +146,12 @@ def test_mask_equals_the_host_rules(dev):
 def test_one_step_keeps_the_guide_and_moves_the_words(dev, fused, kw):
     """one sampler tail over the cases, through mxl_guided_sample_step and through mxl_guided_rules_mask / sample /
     mxl_guided_rules_advance: the tokens, the eight words of every row, ids[:, t + 1], the embedding rows and the distribution"""
-    from symbolic_music_generation_amd import ops
-    sampling = sampling_config(**kw)
     keep, fed = _host_keep()
     st = _State(dev)
-    scores = _scores(dev)
-    gen = torch.Generator(device=dev).manual_seed(2)
-    E = torch.randn(V, 64, device=dev, generator=gen).to(torch.bfloat16)
-    emb = torch.zeros(NB, 64, device=dev, dtype=torch.bfloat16)
-    ids = torch.full((NB, 8), 9, device=dev, dtype=torch.int64)
-    t, rng, ctr = _i32([2], dev), torch.zeros(1, device=dev, dtype=torch.int64), _i32([0], dev)
-    probs = torch.full((NB, V), -1.0, device=dev)
-    sc = scores[:, :V]
-    if fused:
-        ops.sample_step(sc, V, ids, t, rng, 17, E, emb, 1.0, ctr, out_probs=probs, **st.kwargs(), **sampling)
-    else:
-        ops.rules_mask(sc, V, t, **{k: v for k, v in st.kwargs().items() if k not in ('unfinished', 'alive')})
-        ops.sample(sc, ids, t, rng, 17, out_probs=probs, **sampling)
-        ops.decode_advance(t, rng)
-        ops.rules_advance(ids, t, **st.kwargs())
-    assert t.tolist() == [3] and rng.tolist() == [1] and ctr.tolist() == [0]
-    toks = ids[:, 3].tolist()
+    toks, probs, emb, ids, (_, _, ctr), E = tail(dev, fused, _scores(dev)[:, :V], sampling_config(**kw), 2, width=64, seed=17, gen_seed=2,
+                                                 fill=9, **st.kwargs())
+    assert ctr.tolist() == [0]
+    toks = toks.tolist()
     assert (ids[:, :3] == 9).all() and (ids[:, 4:] == 9).all()
     live = [c[-1] for c in CASES]
     assert toks[-1] == PAD                                         # the finished row emits pad, whatever it is fed
@@ -196,13 +164,12 @@ def test_one_step_keeps_the_guide_and_moves_the_words(dev, fused, kw):
         assert toks[:-1] == want[:-1]
         assert want[1] == P[1] and _scores(dev)[1, :V].argmin().item() == P[1]             # the lowest score of its row, kept
     else:
-        p = probs.cpu()
-        assert (p[~keep] == 0).all() and torch.allclose(p.sum(1), torch.ones(NB), atol=1e-5)
+        assert (probs[~keep] == 0).all() and torch.allclose(probs.sum(1), torch.ones(NB), atol=1e-5)
         for b in range(NB):
             if fed[b] >= 0:                                        # exactly one-hot at the guide token
                 one = torch.zeros(V)
                 one[fed[b]] = 1.0
-                assert torch.equal(p[b], one), CASES[b][0]
+                assert torch.equal(probs[b], one), CASES[b][0]
     assert st.read() == _host_words(toks)
     assert st.alive.tolist() == [sum(int(l and tk != EOS) for l, tk in zip(live, toks))]
     assert st.tables_untouched()
@@ -243,17 +210,12 @@ def _model(dev, seed):
 def _prompts(kind, dev):
     """(ids, attention_mask or None) of 4 prompts"""
     if kind == 'header':
-        return torch.tensor([_ids(HEADER)] * 4, device=dev), None
+        return torch.tensor([token_ids(VOC, HEADER)] * 4, device=dev), None
     if kind == 'mid-bar':
-        return torch.tensor([_ids(MID_BAR)] * 4, device=dev), None
+        return torch.tensor([token_ids(VOC, MID_BAR)] * 4, device=dev), None
     texts = [HEADER, MID_BAR, HEADER + ' <bar> <melody> p_r d_2 <bass> p_r d_2', 'TimeSig_2/4 Tempo_96']
-    ids, mask = left_pad([torch.tensor(_ids(t)) for t in texts], PAD)
+    ids, mask = left_pad([torch.tensor(token_ids(VOC, t)) for t in texts], PAD)
     return ids.to(dev), mask.to(dev)
-
-
-def _gen(m, ids, **kw):
-    m._decoder = None
-    return m.generate(input_ids=ids, **kw)
 
 
 def _assert_follows(out, Tp, guides, n_bars, mask=None):
@@ -277,41 +239,31 @@ def _forced_by_the_host(m, ids, mask, L, guides, n_bars):
     samp = sampling_config(do_sample=False)
     n_pad = None if mask is None else (mask == 0).sum(1).to(torch.int32)
     dec.begin(ids, L, samp, False, n_pad, (EOS, PAD, 0), G, torch.tensor(n_bars, dtype=torch.int32))
-    words = [list(w) for w in zip(dec.gstate.tolist(), dec.gbar.tolist(), dec.grem.tolist(), dec.gleft.tolist())]
-    live, at = dec.unfinished.tolist(), [(0, 0)] * n
-    t = Tp
+    fed = Rules(G, budget=True, count=True, guide=True, stop=(EOS, PAD, 0))
+    free = fed._replace(automaton=False, budget=False, count=False)    # a row that chose: the device has moved those words itself
+    four = ('gstate', 'gbar', 'grem', 'gleft')
 
-    def keep(b, tok):
-        c = int(G.cls[tok])
-        at[b] = GUIDE.move(*at[b], len(guides[b]), c)
-        if tok == EOS:
-            live[b] = 0
+    def read():
+        return [dict(zip(four, w)) for w in zip(*(getattr(dec, k).tolist() for k in four))]
 
-    for b, tok in enumerate(dec.ids[:, t].tolist()):               # the first token, sampled by begin: rows start free
-        keep(b, tok)
-    while any(live) and t + 1 < L:
-        before = [list(w) for w in words]
+    t = Tp                                                         # the first token, sampled by begin: rows start free
+    rows = [move(free, Words(u, **w), tok, len(g))[1]
+            for u, w, tok, g in zip(dec.unfinished.tolist(), read(), dec.ids[:, t].tolist(), guides)]
+    while any(w.unfinished for w in rows) and t + 1 < L:
         dec.step(samp)
         t += 1
-        sampled, kept = dec.ids[:, t].tolist(), []
-        words = [list(w) for w in zip(dec.gstate.tolist(), dec.gbar.tolist(), dec.grem.tolist(), dec.gleft.tolist())]
-        for b in range(n):
-            if not live[b]:
-                kept.append(sampled[b])
-                continue
-            f = GUIDE.forced(*at[b], guides[b])
-            if f >= 0:
-                st, bar, rem, left = before[b]
-                c = int(G.cls[f])
-                bar, rem = G.budget.move(bar, rem, c, int(G.budget.slots[f]), int(G.budget.bars[f]))
-                words[b] = [int(G.next[st, c]), bar, rem, G.bar_count.move(left, c)]
-            kept.append(f if f >= 0 else sampled[b])
-            keep(b, kept[-1])
+        kept = dec.ids[:, t].tolist()
+        for b, (w, now, g) in enumerate(zip(rows, read(), guides)):
+            f = GUIDE.forced(w.gpos, w.gforce, g) if w.unfinished else -1
+            if f >= 0:                                             # every word from where the row stood before the step
+                kept[b], rows[b] = move(fed, w, f, len(g))
+            else:
+                rows[b] = move(free, w._replace(**now), kept[b], len(g))[1]
         dec.force_tokens(torch.tensor(kept, device=dev))
-        for w, col in zip((dec.gstate, dec.gbar, dec.grem, dec.gleft), zip(*words)):
-            w.copy_(_i32(list(col), dev))
-        dec.unfinished.copy_(_i32(live, dev))
-        dec.alive.fill_(sum(live))
+        for k in four:
+            getattr(dec, k).copy_(i32([getattr(w, k) for w in rows], dev))
+        dec.unfinished.copy_(i32([w.unfinished for w in rows], dev))
+        dec.alive.fill_(sum(w.unfinished for w in rows))
     return dec.ids[:, :t + 1].clone()
 
 
@@ -324,20 +276,20 @@ def test_greedy_generation_follows_the_guide_on_every_path(dev, kind, monkeypatc
     Tp = ids.shape[1]
     L = Tp + 32 + 3 * BAR_TOKENS + 1                               # the bass a prompt left open, three whole bars, </s>
     kw = dict(max_length=L, grammar=G, melody=GUIDES, do_sample=False, attention_mask=mask, **STOP)
-    base = _gen(m, ids, **kw)
+    base = fresh_generate(m, ids, **kw)
     assert m._decoder.fused_sampler and torch.equal(base[:, :Tp], ids)
     _assert_follows(base, Tp, GUIDES, N_BARS, mask)
     W = base.shape[1]
-    assert torch.equal(_gen(m, ids, use_graph=False, **kw), base)
+    assert torch.equal(fresh_generate(m, ids, use_graph=False, **kw), base)
     n_pad = None if mask is None else (mask == 0).sum(1).to(torch.int32)
     lanes = XLDecoderLanes(m.engine, 4, L, lanes=2)
     assert torch.equal(lanes.generate(ids, L, grammar=G, melody=GUIDES, n_pad=n_pad, **STOP), base)
     assert [d.rules.glen.tolist() for d in lanes.lanes] == [[len(g) for g in GUIDES[:2]], [len(g) for g in GUIDES[2:]]]
     monkeypatch.setenv('MXL_DECODE_UNFUSED', '1')
-    assert torch.equal(_gen(m, ids, **kw), base) and not m._decoder.fused_sampler
-    assert torch.equal(_gen(m, ids, use_graph=False, **kw), base)
+    assert torch.equal(fresh_generate(m, ids, **kw), base) and not m._decoder.fused_sampler
+    assert torch.equal(fresh_generate(m, ids, use_graph=False, **kw), base)
     monkeypatch.setenv('MXL_SAMPLE_LARGE', '1')
-    assert torch.equal(_gen(m, ids, **kw), base)
+    assert torch.equal(fresh_generate(m, ids, **kw), base)
     monkeypatch.delenv('MXL_SAMPLE_LARGE')
     monkeypatch.delenv('MXL_DECODE_UNFUSED')
     assert XLDecoder(m.engine, 2, 32).fused_sampler
@@ -354,15 +306,15 @@ def test_unguided_rows_sampling_and_graph_reuse(dev):
     sample = dict(do_sample=True, top_k=0, temperature=1.0)
     # a None row equals that row generated with no melody= under the same seed
     some = [GUIDES[0], None, GUIDES[1], None]
-    got = _gen(m, ids, max_length=L, grammar=G, melody=some, seed=5, **STOP, **sample)
+    got = fresh_generate(m, ids, max_length=L, grammar=G, melody=some, seed=5, **STOP, **sample)
     assert m._decoder.rules.glen.tolist() == [len(GUIDES[0]), 0, len(GUIDES[1]), 0] and m._decoder.gleft.tolist()[1::2] == [-1, -1]
-    free = _gen(m, ids, max_length=L, grammar=G, seed=5, **STOP, **sample)
+    free = fresh_generate(m, ids, max_length=L, grammar=G, seed=5, **STOP, **sample)
     Wc = min(got.shape[1], free.shape[1])
     assert torch.equal(got[[1, 3], :Wc], free[[1, 3], :Wc]) and not torch.equal(got[[0, 2], :Wc], free[[0, 2], :Wc])
     assert check_melody(got, G, some, prompt_len=Tp).tolist() == [-1] * 4
     assert check_melody(free, G, some, prompt_len=Tp)[[0, 2]].min() >= Tp                  # the model's own melodies are others
     # num_return_sequences: the guides are repeated per prompt; same melody spans, another bass
-    out = _gen(m, ids[:2], max_length=L, grammar=G, melody=GUIDES[:2], num_return_sequences=2, seed=6, **STOP, **sample)
+    out = fresh_generate(m, ids[:2], max_length=L, grammar=G, melody=GUIDES[:2], num_return_sequences=2, seed=6, **STOP, **sample)
     rep = [GUIDES[0], GUIDES[0], GUIDES[1], GUIDES[1]]
     assert out.shape[0] == 4
     _assert_follows(out, Tp, rep, [2, 2, 3, 3])
@@ -435,7 +387,7 @@ def test_refusals(dev):
     scores = torch.zeros(NB, V, device=dev)
     kw = {k: v for k, v in st.kwargs(stop=False).items()}
     with pytest.raises(MusicXLError, match='gpos must be'):
-        ops.rules_mask(scores, V, None, **{**kw, 'gpos': _i32([0] * (NB + 1), dev)})
+        ops.rules_mask(scores, V, None, **{**kw, 'gpos': i32([0] * (NB + 1), dev)})
     with pytest.raises(MusicXLError, match='gpos needs melody'):
         ops.rules_mask(scores, V, None, **{**kw, 'melody': TOK.grammar().guide})
     with pytest.raises(MusicXLError, match='rules_mask guide: expected'):
