@@ -619,6 +619,47 @@ int mxl_group_beam_step(const float* logp, int ldl, float* beam_scores, void* id
                         int ng, float diversity_penalty, int V, int eos_id, int pad_id, float length_penalty, int early_stopping,
                         void* hyp_ids, int* hyp_len, float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved,
                         int* words, int n_words, int word_stride, void* stream);
+/* ------------------------------------------------------------------------------------------------------------
+ * Beam-sample on the device (HF 4.25.1 beam_sample, the reference's default 'beam' strategy): per step mxl_rules_mask, then
+ * mxl_beam_sample_draw, then mxl_beam_sample_step, then what follows mxl_beam_step.  An item is the nb rows of one prompt as above.
+ *
+ * mxl_beam_sample_draw.  logp (rows = Bs * nb, ldl) f32, ldl >= V, already masked by the rules.  Per row r, unless dead:
+ *   warp: score[v] = fp32(logp[r][v] * fp32(1 / temperature)), ordered by score descending, ties by v ascending; HF's warpers in HF's
+ *     order with min_tokens_to_keep = 2: top_k > 0 keeps the first max(top_k, 2) of the order; 0 < top_p < 1 keeps an entry iff the
+ *     probability ordered before it is below top_p, and the two best in any case; 0 < typical_p < 1 orders what is left by
+ *     |-log p - H| ascending (ties by the first order) and keeps an entry iff the probability ordered before it is below typical_p,
+ *     and the first two of that order in any case; values >= 1 (top_k: 0) switch a warper off.  Then LogitNormalization:
+ *     w[r][v] = the log-probability renormalised over what is left, -inf outside it; logsumexp_v w[r][v] = 0.  The running score
+ *     plays no part: renormalised per row it drops out of the draw, and the step below takes w itself as the new running score.
+ *   dead row: beam_scores[r] == -inf (f32 (rows,), read only).  It contributes no candidate: w[r][.] = -inf.  So does a live row
+ *     whose logp is -inf throughout.  No NaN is written anywhere.
+ * Per item: 2 * nb of its nb * V candidates are drawn without replacement with probabilities softmax of the flattened w, as the
+ *   2 * nb largest of z = w - log(-log u) (Gumbel-top-k), ties by flat index j * V + v ascending (j = r % nb).  For candidate
+ *   (global row r, token v), with hash = mxl_hash32 (x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16),
+ *   all sums and products modulo 2^32, ctr = *rng_ctr (64 bits) and seed (64 bits):
+ *       h1   = hash(hi32(ctr * 0x9E3779B97F4A7C15) ^ hash(r + 0x85ebca6b * lo32(seed)))
+ *       h2   = hash(h1 + lo32(ctr) + hi32(seed))                      (the sampler's word of row r)
+ *       word = hash(h2 ^ (v * 0x9E3779B1 + 0x85EBCA77))
+ *       j24  = word >> 8,   u = (j24 + 0.5) / 2^24                   (never 0 or 1)
+ *   The Gumbel term -log(-log u) lies in [-2.85, 17.33]: a candidate more than about 20 nats under its item's best is never drawn.
+ *   Candidates with w = -inf have z = -inf and are not drawn; an item with fewer than 2 * nb finite candidates draws them all, and
+ *   mxl_beam_sample_step fills its ranks with -inf candidates in flat-index order, as mxl_beam_step's select treats -inf.
+ * drawn (rows, ldl) f32, output, not logp: columns 0..V-1 hold w[r][v] bit for bit at the item's drawn candidates and -inf
+ *   everywhere else; columns V.. are not touched.  out_warped (rows, V) f32, optional (NULL), a test hook: every row's whole w.
+ * *rng_ctr is read on the device and not advanced (mxl_decode_advance does that), so the step replays in a graph; the same
+ *   arguments give the same bytes.  2 <= V <= 2048, 2 <= nb <= 16, temperature > 0 and finite, top_k >= 0, top_p > 0,
+ *   typical_p > 0; anything else is MXL_EINVAL.  Two launches (one workgroup per row, then one per item), no workspace. */
+int mxl_beam_sample_draw(const float* logp, int ldl, int V, const float* beam_scores, int Bs, int nb,
+                         const unsigned long long* rng_ctr, unsigned long long seed, int top_k, float top_p, float temperature,
+                         float typical_p, float* drawn, float* out_warped, void* stream);
+/* mxl_beam_step over the matrix `drawn` of mxl_beam_sample_draw, with one difference: the score of candidate (j, v) is drawn[j][v]
+ * itself -- -inf when beam_scores[j] is -inf -- and not a sum with the running score; no arithmetic is done on it, so the new
+ * beam_scores are entries of `drawn` bit for bit.  Select (the 2 * nb best, score descending then flat index ascending, -inf
+ * taking part), walk, store, reorder, dead rows, frozen items, words and the argument domain are mxl_beam_step's. */
+int mxl_beam_sample_step(const float* drawn, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs, int nb,
+                         int V, int eos_id, int pad_id, float length_penalty, int early_stopping, void* hyp_ids, int* hyp_len,
+                         float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved, int* words, int n_words,
+                         int word_stride, void* stream);
 /* Contiguous (rows, row_bytes) buffers follow beam_idx in place, item by item (the K/V rings of a decoder: HF _reorder_cache without
  * the second buffer).  buf: one buffer (n_bufs = 1), or table: a device array of n_bufs buffer addresses, one launch for all of them;
  * exactly one of the two is given.  A thread owns one 16-byte column of an item, reads the sources of the rows that change into

@@ -19,7 +19,11 @@ the topk, the reads, the walk and the uploads once per group and step.
 
     GROUPS=2 python3 scripts/perf_beam.py         # the reference's 'beam' strategy: num_beams=4, num_beam_groups=2
 
-SAMPLE=1 measures beam-sample (do_sample=True, top_k = 50: HF's `beam_sample`), which has the host loop only: one row.
+SAMPLE=1 measures beam-sample with the reference's settings (num_beams = 3, do_sample=True, renormalize_logits=True, top_k = 50:
+HF's `beam_sample`), for one prompt and for eight: generate.beam_sample_device (`device_scorer=True`: rules mask, mxl_beam_sample_draw,
+mxl_beam_sample_step, mxl_beam_reorder, advance, model in one captured graph per step) against generate.beam_search(do_sample=True)
+(`_warp` on a (rows, V) matrix, torch.multinomial, three .tolist() reads, the walk, three uploads, index_select + copy_ over the
+rings).  The two draw from different random streams, so their ids differ; with an eos that never fires both emit NEW tokens per prompt.
 
     SAMPLE=1 python3 scripts/perf_beam.py
 """
@@ -69,10 +73,23 @@ def run(host: bool, **extra):
 
 with torch.no_grad():
     if SAMPLE:
-        run(True, do_sample=True, top_k=50)                                       # warm-up
-        tps = sorted(B * NEW / run(True, do_sample=True, top_k=50)[0] for _ in range(RUNS))
-        print(f'beam-sample, C5 decode shape: {B} prompts x {Tp}, num_beams {NB} ({B * NB} rows), top_k 50, {NEW} new tokens, eos never fires')
-        print(f'host  : {statistics.median(tps):9.1f} tok/s median of {RUNS} (min {tps[0]:.1f}, max {tps[-1]:.1f})')
+        arm = dict(num_beams=3, do_sample=True, top_k=50, renormalize_logits=True)
+        for n in (1, B):
+            sub = dict(arm, input_ids=ids[:n])
+            run(False, device_scorer=True, **sub), run(True, **sub)              # warm-up of both paths
+            times = {False: [], True: []}
+            for _ in range(RUNS):
+                times[False].append(run(False, device_scorer=True, **sub)[0])
+                times[True].append(run(True, **sub)[0])
+            print(f'beam-sample, C5 decode shape: {n} prompt(s) x {Tp}, num_beams 3 ({3 * n} rows), top_k 50, {NEW} new tokens, '
+                  'eos never fires')
+            d, h = sorted(n * NEW / t for t in times[False]), sorted(n * NEW / t for t in times[True])
+            for name, tps, ts in (('device', d, times[False]), ('host  ', h, times[True])):
+                print(f'{name}: {statistics.median(tps):9.1f} tok/s median of {RUNS} (min {tps[0]:.1f}, max {tps[-1]:.1f}); '
+                      f'{statistics.median(ts):.3f} s per call')
+            clear = d[0] > h[-1]
+            print(f'device / host = {statistics.median(d) / statistics.median(h):.3f}x; the slowest device run is '
+                  f'{"above" if clear else "NOT above"} the fastest host run ({d[0]:.1f} vs {h[-1]:.1f} tok/s)')
         sys.exit(0)
     # library launches per step: one short eager call of either path, the prompt pass's share taken off with a second, shorter one
     ops.check = counting_check

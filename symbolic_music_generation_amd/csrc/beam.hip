@@ -22,47 +22,16 @@
 //   dead     a row that continues from a -inf candidate (a barred token, or the child of a dead row) gets pad and keeps -inf; its
 //            `unfinished` word (word 0) is cleared, so the rules' advance launch -- with its stop group on -- leaves its words alone,
 //            the mask launch keeps finding a valid state, and the ring attention skips it.  The rows of a done item are cleared too.
+// Beam-sample (mxl_beam_sample_step) is a third entry of the same kernel: over the `drawn` matrix of beam_sample.hip, with a
+// candidate's score its entry itself; select, walk, copy, reorder and dead rows are the ones above.
 #include "common.h"
+#include "beam_key.h"
 #include "musicxl_internal.h"
 
 namespace {
 
 constexpr int BEAM_MAX = 16;                 // beams per item: the register rows of the reorder
 constexpr int BEAM_T = 256;
-
-// (score, flat index) -> a word whose unsigned order is "score ascending, then index descending": the best candidate is the max
-__device__ __forceinline__ unsigned long long beam_key(float s, uint32_t idx) {
-    uint32_t u = __float_as_uint(s + 0.0f);                          // (-0 -> +0: equal scores must tie)
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - idx);
-}
-__device__ __forceinline__ float beam_key_score(unsigned long long k) {
-    const uint32_t u = (uint32_t)(k >> 32);
-    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
-}
-__device__ __forceinline__ uint32_t beam_key_index(unsigned long long k) { return 0xFFFFFFFFu - (uint32_t)k; }
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)k, o, 64), hi = __shfl_xor((uint32_t)(k >> 32), o, 64);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        k = other > k ? other : k;
-    }
-    return k;
-}
-
-// the max of `best` over the workgroup, in every thread; sh_part may be rewritten after the caller's next barrier
-__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long best, unsigned long long* sh_part) {
-    const int tid = threadIdx.x;
-    best = wave_max_u64(best);
-    if ((tid & 63) == 0) sh_part[tid >> 6] = best;
-    __syncthreads();
-    best = sh_part[0];
-#pragma unroll
-    for (int w = 1; w < BEAM_T / 64; w++) best = sh_part[w] > best ? sh_part[w] : best;
-    return best;
-}
 
 // What a step does once thread 0 has walked the candidates of an item (all of this in LDS, a barrier behind it): the added
 // hypotheses sh_add[slot] = source beam (or -1) are copied out before ids moves, ids and the packed rule words follow sh_src in
@@ -115,6 +84,9 @@ __device__ __forceinline__ void beam_store_and_reorder(long long* ids, int ld_id
 // One beam step of every item, for plain (ng = 1, pen = 0) and diverse beam search alike: the groups of an item are walked in order
 // inside its workgroup, since a group's scores depend on the tokens the earlier groups chose in this step (sh_prev) and all groups
 // share the item's store.  Once the item is done the groups behind are not walked: identity, pad, their scores stay.
+// SAMPLE (beam-sample, ng = 1): logp is the `drawn` matrix of mxl_beam_sample_draw and a candidate's score is its entry itself -- -inf
+// in a row whose running score is -inf -- with no arithmetic on it; everything else is the same step.
+template <bool SAMPLE>
 __global__ __launch_bounds__(BEAM_T) void beam_step_kernel(const float* logp, int ldl, float* beam_scores, long long* ids, int ld_ids,
                                                            const int* t_dev, int nb, int ng, float pen, int V, int eos_id, int pad_id,
                                                            float length_penalty, int early_stopping, long long* hyp_ids, int* hyp_len,
@@ -150,12 +122,13 @@ __global__ __launch_bounds__(BEAM_T) void beam_step_kernel(const float* logp, in
                 const float off = __fmul_rn(pen, (float)c);
                 for (int j = 0; j < gs; j++) {
                     const float lp = logp[(size_t)(row0 + g0 + j) * ldl + v];
-                    const float s = __fadd_rn(__fsub_rn(lp, off), sh_score[g0 + j]);
+                    const float s = SAMPLE ? (sh_score[g0 + j] == -INFINITY ? -INFINITY : lp)
+                                           : __fadd_rn(__fsub_rn(lp, off), sh_score[g0 + j]);
                     const unsigned long long k = beam_key(s, (uint32_t)j * (uint32_t)V + (uint32_t)v);
                     if (k < prev && k > best) best = k;
                 }
             }
-            best = block_max_u64(best, sh_part);
+            best = block_max_u64<BEAM_T>(best, sh_part);
             if (tid == 0) sh_cand[round] = best;
             prev = best;
             __syncthreads();                                         // sh_part is rewritten by the next round
@@ -259,7 +232,8 @@ __global__ __launch_bounds__(BEAM_T) void beam_reorder_kernel(char* buf, char* c
 
 }  // namespace
 
-// the argument checks both entries share, and the launch; nb, ng and pen are in the entry's own domain by now
+// the argument checks all entries share, and the launch; nb, ng and pen are in the entry's own domain by now
+template <bool SAMPLE>
 static int beam_step_launch(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs, int nb,
                             int ng, float pen, int V, int eos_id, int pad_id, float length_penalty, int early_stopping, void* hyp_ids,
                             int* hyp_len, float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved, int* words,
@@ -270,7 +244,7 @@ static int beam_step_launch(const float* logp, int ldl, float* beam_scores, void
     MXL_CHECK_ARG((long long)nb * V < (1LL << 31) && (long long)Bs * nb < (1LL << 31));
     MXL_CHECK_ARG((words == nullptr) == (n_words == 0));
     MXL_CHECK_ARG(!words || (n_words >= 1 && n_words <= BEAM_T && (long long)word_stride >= (long long)Bs * nb));
-    hipLaunchKernelGGL(beam_step_kernel, dim3(Bs), dim3(BEAM_T), 0, (hipStream_t)stream, logp, ldl, beam_scores, (long long*)ids, ld_ids,
+    hipLaunchKernelGGL(beam_step_kernel<SAMPLE>, dim3(Bs), dim3(BEAM_T), 0, (hipStream_t)stream, logp, ldl, beam_scores, (long long*)ids, ld_ids,
                        t_dev, nb, ng, pen, V, eos_id, pad_id, length_penalty, early_stopping, (long long*)hyp_ids, hyp_len, hyp_score,
                        hyp_n, done, n_done, beam_idx, moved, words, n_words, word_stride);
     MXL_LAUNCH_CHECK();
@@ -282,9 +256,19 @@ extern "C" int mxl_beam_step(const float* logp, int ldl, float* beam_scores, voi
                              float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved, int* words, int n_words,
                              int word_stride, void* stream) {
     MXL_CHECK_ARG(nb >= 1);
-    return beam_step_launch(logp, ldl, beam_scores, ids, ld_ids, t_dev, Bs, nb, 1, 0.f, V, eos_id, pad_id, length_penalty,
+    return beam_step_launch<false>(logp, ldl, beam_scores, ids, ld_ids, t_dev, Bs, nb, 1, 0.f, V, eos_id, pad_id, length_penalty,
                             early_stopping, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words, n_words,
                             word_stride, stream);
+}
+
+extern "C" int mxl_beam_sample_step(const float* drawn, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs,
+                                    int nb, int V, int eos_id, int pad_id, float length_penalty, int early_stopping, void* hyp_ids,
+                                    int* hyp_len, float* hyp_score, int* hyp_n, int* done, int* n_done, int* beam_idx, int* moved,
+                                    int* words, int n_words, int word_stride, void* stream) {
+    MXL_CHECK_ARG(nb >= 1);
+    return beam_step_launch<true>(drawn, ldl, beam_scores, ids, ld_ids, t_dev, Bs, nb, 1, 0.f, V, eos_id, pad_id, length_penalty,
+                                  early_stopping, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words, n_words,
+                                  word_stride, stream);
 }
 
 extern "C" int mxl_group_beam_step(const float* logp, int ldl, float* beam_scores, void* ids, int ld_ids, const int* t_dev, int Bs,
@@ -293,7 +277,7 @@ extern "C" int mxl_group_beam_step(const float* logp, int ldl, float* beam_score
                                    int* beam_idx, int* moved, int* words, int n_words, int word_stride, void* stream) {
     MXL_CHECK_ARG(nb >= 2 && ng >= 2 && ng <= nb && nb % ng == 0);
     MXL_CHECK_ARG(diversity_penalty >= 0.f && diversity_penalty < INFINITY);
-    return beam_step_launch(logp, ldl, beam_scores, ids, ld_ids, t_dev, Bs, nb, ng, diversity_penalty, V, eos_id, pad_id, length_penalty,
+    return beam_step_launch<false>(logp, ldl, beam_scores, ids, ld_ids, t_dev, Bs, nb, ng, diversity_penalty, V, eos_id, pad_id, length_penalty,
                             early_stopping, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done, beam_idx, moved, words, n_words,
                             word_stride, stream);
 }

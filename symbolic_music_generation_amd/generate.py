@@ -199,7 +199,8 @@ def rules_refusal(what: str, searches: str = 'beam, group-beam or contrastive se
 
 def plan_search(caps: dict, *, num_beams=1, num_beam_groups=1, do_sample=False, penalty_alpha=None, top_k=None, diversity_penalty=None,
                 eos_token_id=None, pad_token_id=None, config_eos=None, config_pad=None, padded=False, grammar=None, n_bars=None,
-                in_key=None, key=None, melody=None) -> SearchPlan:
+                in_key=None, key=None, melody=None, device_scorer=False, repetition_penalty=None, renormalize_logits=None,
+                vocab_size=None) -> SearchPlan:
     """Which search a `generate` call runs -- a plain value: `strategy` = 'sample' (greedy decoding / sampling), 'beam', 'beam_sample',
     'group_beam' or 'contrastive' (chosen as HF 4.25.1 `generate` does); `device`: with its scorer on the device; `rules`: it takes
     grammar / n_bars / in_key / key; `eos`, `pad`: what the search arms stop at and fill with (the arguments, else the config's) --
@@ -207,7 +208,12 @@ def plan_search(caps: dict, *, num_beams=1, num_beam_groups=1, do_sample=False, 
     search and the most candidates of 'contrastive' search the model runs on the device; an absent key = host only.  The only reader
     of the environment switches.  A strategy takes the rules if it is greedy decoding / sampling, or runs on the device with an
     explicit eos_token_id=: a hypothesis ends only by emitting eos, the config's eos (0 = [OMIT]) is no end token of the grammar,
-    and the stop group that the explicit eos turns on is how the device scorers retire rows."""
+    and the stop group that the explicit eos turns on is how the device scorers retire rows.
+    device_scorer (opt-in, beam-sample only): the draw and the scorer of beam-sample on the device (`beam_sample_device`), which then
+    takes grammar / in_key / key like the other device searches.  It is no default because the device draw is another random stream
+    than torch.multinomial's: the same seed gives other ids.  caps['beam_sample'] = its most beams; with the keyword the call's
+    repetition_penalty, renormalize_logits and vocab_size are judged too: ValueError for a call that is no beam-sample or carries a
+    repetition penalty, MusicXLError for what the device path cannot run."""
     nb, ng = num_beams, num_beam_groups
     explicit_eos = eos_token_id is not None
     host_scorer = os.environ.get('MXL_BEAM_HOST') == '1'
@@ -228,11 +234,33 @@ def plan_search(caps: dict, *, num_beams=1, num_beam_groups=1, do_sample=False, 
     elif nb > 1:
         strategy = 'beam_sample' if do_sample else 'beam'
         device = not do_sample and nb <= caps.get('beam', 0) and not host_scorer
+    if device_scorer:
+        if strategy != 'beam_sample':
+            raise ValueError('device_scorer=True selects the device path of beam-sample (num_beams > 1, num_beam_groups=1, '
+                             f"do_sample=True); this call runs '{strategy}'")
+        if repetition_penalty is not None and repetition_penalty != 1.0:
+            raise ValueError('device_scorer=True: the beam arms apply no repetition_penalty and the device path must not differ; '
+                             'leave it None or 1.0')
+        if 'beam_sample' not in caps:
+            raise MusicXLError('device_scorer=True: this model runs no beam-sample on the device (the Reformer scores its beams on '
+                               'the host)')
+        if host_scorer:
+            raise MusicXLError('device_scorer=True contradicts MXL_BEAM_HOST=1, which keeps every beam scorer on the host')
+        if not renormalize_logits:
+            raise MusicXLError('device_scorer=True needs renormalize_logits=True: the device draw always renormalises the warped '
+                               'scores, as the reference does')
+        if vocab_size is not None and vocab_size > 2048:
+            raise MusicXLError(f'device_scorer=True: the device draw sorts a row in LDS, a vocabulary of {vocab_size} tokens is '
+                               'beyond its 2048')
+        if not 2 <= nb <= caps['beam_sample']:
+            raise MusicXLError(f"device_scorer=True: beam-sample on the device takes 2..{caps['beam_sample']} beams, not {nb}")
+        device = True
     is_search = strategy != 'sample'
     # contrastive search called with num_beam_groups != 1 runs, but has never taken the rules
     rules = not is_search or (device and explicit_eos and not (strategy == 'contrastive' and ng != 1))
-    # the bar count is untested under contrastive search and under several groups, and needs the grammar that counts the bars
-    no_bar_count = not rules or strategy in ('contrastive', 'group_beam') or (strategy == 'beam' and grammar is None)
+    # the bar count is untested under contrastive search, under several groups and under a sampled search, and needs the grammar
+    # that counts the bars
+    no_bar_count = not rules or strategy in ('contrastive', 'group_beam', 'beam_sample') or (strategy == 'beam' and grammar is None)
     if padded and is_search:                            # in this order: the first that applies is the one raised
         raise rules_refusal('padded prompts (attention_mask with zeros) are')
     if melody is not None and is_search:
@@ -869,6 +897,7 @@ class XLDecoder:
         self.trace = None
         self.steps_run = 0                              # decode steps issued by the last generate() (early exit: fewer)
         self.beam = None                                # BeamStore of a beam search on the device (beam_begin)
+        self.drawn = None                               # (B, V) f32: the drawn candidates of a beam-sample step (beam_begin, sample)
         self.cs = None                                  # ContrastiveStore of a contrastive search on the device (contrastive_begin)
         # the rules of the current generation (eos, grammar, bar budget, bar count) and their per-row words, which the sampler
         # launch reads and moves; the words are readable here under their names
@@ -1054,13 +1083,18 @@ class XLDecoder:
     # ---------------------------------------------------------------- beam search on the device (beam_search_device below)
     def beam_begin(self, prompt: torch.Tensor, max_length: int, nb: int, eos: int, pad: int, length_penalty: float,
                    early_stopping: bool, use_graph: bool = True, grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None,
-                   keys: Optional[torch.Tensor] = None, ng: int = 1, diversity_penalty: float = 0.0) -> int:
+                   keys: Optional[torch.Tensor] = None, ng: int = 1, diversity_penalty: float = 0.0, sample: bool = False,
+                   top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: float = 1.0,
+                   typical_p: Optional[float] = None) -> int:
         """prompt pass (one row per beam, the rules started as `prefill` starts them, with the stop group (eos, pad, 0) always on:
         its `unfinished` word is how mxl_beam_step retires dead rows and done items) + the scorer's state + (use_graph) capture of
         one beam step (`_capture`; the hypothesis store, the running scores and the log-probabilities are this step's own state);
         returns the number of `replay_once()` calls before the last selection (`beam_select`).
         ng > 1: diverse beam search, the nb beams of an item in ng groups with `diversity_penalty` between them (mxl_group_beam_step
-        in place of mxl_beam_step); both are part of the graph key."""
+        in place of mxl_beam_step); both are part of the graph key.
+        sample: beam-sample, ng = 1 -- the step draws its candidates (mxl_beam_sample_draw under the warpers top_k / top_p / temperature
+        / typical_p with the decoder's seed, into the decoder's `drawn` buffer) and walks them with mxl_beam_sample_step; the draw
+        counter starts at 0, so a seed gives one result.  The flag and the warpers are part of the graph key, `drawn` is step state."""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         if nb < 2 or nb > BEAM_MAX or self.B % nb:
@@ -1068,29 +1102,44 @@ class XLDecoder:
         if ng < 1 or nb % ng or not 0.0 <= diversity_penalty < math.inf:
             raise MusicXLError(f'group beam search on the device takes groups that divide the {nb} beams and a finite diversity_penalty '
                                '>= 0')
+        if sample and (ng != 1 or self.eng.cfg.vocab_size > 2048):
+            raise MusicXLError('beam-sample on the device takes one group and a vocabulary of at most 2048 tokens')
         self.prefill(prompt, None, None, (int(eos), int(pad), 0), grammar, n_bars, in_key, keys)
         if self.beam is None or self.beam.nb != nb:
             self.beam = BeamStore(self.B // nb, nb, self.ids.shape[1], self.eng.dev)
             self.ring_table = ops.beam_table(self.kc + self.vc)
         self.beam.start(ng)
-        self._beam_args = (int(nb), int(eos), int(pad), float(length_penalty), bool(early_stopping), int(ng), float(diversity_penalty))
+        self._beam_args = (int(nb), int(eos), int(pad), float(length_penalty), bool(early_stopping), int(ng), float(diversity_penalty),
+                           bool(sample), int(top_k or 0), float(1.0 if top_p is None else top_p),
+                           float(1.0 if temperature is None else temperature), float(1.0 if typical_p is None else typical_p))
+        extra = ()
+        if sample:
+            self.rng.zero_()
+            if self.drawn is None:
+                self.drawn = torch.empty_like(self.logp)
+            extra = (self.drawn,)
         self._use_graph, self._step, self.finished_by = use_graph, ('beam_step',), (self.beam.n_done, self.beam.Bs)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
             key = ('beam',) + self._beam_args + (None if self.trace is None else self.trace.data_ptr(),) + self.rules.graph_key(self.eng.dev)
             st = self.beam               # (logp: the step starts from the log-probabilities the last one left)
-            self._capture(key, (st.scores, st.hyp_ids, st.hyp_score, st.ints, self.logp))
+            self._capture(key, (st.scores, st.hyp_ids, st.hyp_score, st.ints, self.logp) + extra)
         return max(steps, 0)
 
     def beam_select(self):
-        """rules mask -> mxl_beam_step (mxl_group_beam_step under ng > 1): the beams of every item chosen, finished hypotheses
-        stored, ids and the rule words reordered, the chosen tokens at column t + 1"""
+        """rules mask -> mxl_beam_step (mxl_group_beam_step under ng > 1; under `sample` mxl_beam_sample_draw into `drawn`, then
+        mxl_beam_sample_step over it): the beams of every item chosen, finished hypotheses stored, ids and the rule words reordered,
+        the chosen tokens at column t + 1"""
         V, st = self.eng.cfg.vocab_size, self.beam
-        nb, eos, pad, lp, early, ng, pen = self._beam_args
+        nb, eos, pad, lp, early, ng, pen, sample, top_k, top_p, temperature, typical_p = self._beam_args
         rules = ops.rules_in_force(**self.rules.kwargs())
         ops.rules_mask(self.logp, V, self.t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
         store = (st.hyp_ids, st.hyp_len, st.hyp_score, st.hyp_n, st.done, st.n_done, st.beam_idx, st.moved)
         words = dict(words=self.rules.buf, n_words=len(RowRules.WORDS))
+        if sample:
+            ops.beam_sample_draw(self.logp, V, st.scores, nb, self.rng, self.seed, self.drawn, top_k, top_p, temperature, typical_p)
+            ops.beam_sample_step(self.drawn, V, st.scores, self.ids, self.t_dev, nb, eos, pad, lp, early, *store, **words)
+            return rules
         ops.beam_step(self.logp, V, st.scores, self.ids, self.t_dev, nb, eos, pad, lp, early, *store, **words, ng=ng, diversity_penalty=pen)
         return rules
 
@@ -1505,9 +1554,19 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     if dec.B != rows or max_length > dec.Tmax:
         raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, beam search needs {rows} x {max_length}')
     stop = (int(eos_token_id), int(pad), 0)
-    n = dec.beam_begin(prompt.repeat_interleave(nb, 0).to(dec.eng.dev), max_length, nb, eos_token_id, pad, length_penalty,
-                       early_stopping, use_graph, grammar, bar_count_config(n_bars, B0, grammar, stop, nb), in_key,
-                       key_config(in_key, key, B0, V, nb), int(num_beam_groups), float(diversity_penalty))
+    return _beam_device(dec, prompt, max_length, nb, keep, early_stopping, length_penalty, eos_token_id, pad, use_graph, stop_chunk,
+                        grammar, bar_count_config(n_bars, B0, grammar, stop, nb), in_key, key_config(in_key, key, B0, V, nb),
+                        return_scores, 'beam search', ng=int(num_beam_groups), diversity_penalty=float(diversity_penalty))
+
+
+def _beam_device(dec, items: torch.Tensor, max_length: int, nb: int, keep: int, early_stopping: bool, length_penalty: float, eos: int,
+                 pad: int, use_graph: bool, stop_chunk: int, grammar, n_bars, in_key, keys, return_scores: bool, what: str, **arm):
+    """The loop of the device beam searches over `items` (Bs, Tp), one prompt per item, nb decoder rows each: `beam_begin` (with
+    `arm`: the groups and their penalty, or the sample flag and its warpers; n_bars / keys one value per row), the chunked replay,
+    the last selection, one read of the store and `_beam_finalize` keeping `keep` hypotheses per item."""
+    B0, Tp = items.shape
+    n = dec.beam_begin(items.repeat_interleave(nb, 0).to(dec.eng.dev), max_length, nb, eos, pad, length_penalty, early_stopping,
+                       use_graph, grammar, n_bars, in_key, keys, **arm)
     issued, = run_until_finished([(dec, None)], n, stop_chunk)
     dec.beam_select()                   # the last selection needs no forward after it; items that are done ignore it
     dec.steps_run = issued
@@ -1524,10 +1583,41 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
         if not h.done:
             finite += sum(math.isfinite(x) for x in final[b * nb:(b + 1) * nb].tolist())
         if finite < keep:
-            raise MusicXLError(f'beam search found {finite} hypotheses for item {b}, fewer than num_return_sequences = {keep}: the '
+            raise MusicXLError(f'{what} found {finite} hypotheses for item {b}, fewer than num_return_sequences = {keep}: the '
                                'rules bar every continuation of its other beams')
         hyps.append(h)
-    return _beam_finalize(hyps, nb, keep, dec.ids, cur_len, final, max_length, eos_token_id, pad, return_scores)
+    return _beam_finalize(hyps, nb, keep, dec.ids, cur_len, final, max_length, eos, pad, return_scores)
+
+
+def beam_sample_device(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 3, top_k: Optional[int] = None,
+                       top_p: Optional[float] = None, temperature: float = 1.0, typical_p: Optional[float] = None,
+                       early_stopping: bool = True, length_penalty: float = 1.0, num_return_sequences: int = 1, eos_token_id: int = 0,
+                       pad_token_id: Optional[int] = None, use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None,
+                       in_key=None, key=None, return_scores: bool = False):
+    """`beam_search(do_sample=True)` (HF 4.25.1 `beam_sample` with renormalize_logits) with the draw and the scorer on the device:
+    `beam_search_device`'s loop -- chunked replay of one captured step, the number of done items read a chunk late, the last selection
+    without a forward, `_beam_finalize` -- whose step is the rules mask, mxl_beam_sample_draw (the warpers with two tokens kept, the
+    renormalisation and the draw of 2 * num_beams candidates per item without replacement, by Gumbel-top-k from the decoder's seed and
+    its draw counter) and mxl_beam_sample_step (the walk, with the warped value as the new running score).  As HF expands its scorer
+    batch, an item is one of prompts x num_return_sequences and keeps one hypothesis.  dec: an XLDecoder with prompts x
+    num_return_sequences x num_beams rows, 2 <= num_beams <= 16, a vocabulary of at most 2048 tokens.  grammar / in_key / key as in
+    `beam_search_device`, each prompt's value shared by its items and beams (no n_bars: the exact-bar-count promise is untested under
+    a sampled search).  The draw is another random stream than torch.multinomial's: a seed gives other ids than the host path's.
+    An item that ends with no hypothesis of finite score raises MusicXLError."""
+    V = dec.eng.cfg.vocab_size
+    nb, nrs = int(num_beams), int(num_return_sequences)
+    pad = eos_token_id if pad_token_id is None else pad_token_id
+    B0 = prompt.shape[0]
+    rows = B0 * nrs * nb
+    if V > 2048:
+        raise MusicXLError(f'beam-sample on the device sorts a row in LDS: a vocabulary of {V} tokens is beyond its 2048')
+    if nb < 2 or nb > BEAM_MAX:
+        raise MusicXLError(f'beam-sample on the device takes 2..{BEAM_MAX} beams, not {nb}')
+    if nrs < 1 or dec.B != rows or max_length > dec.Tmax:
+        raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, beam-sample needs {rows} x {max_length}')
+    return _beam_device(dec, prompt.repeat_interleave(nrs, 0), max_length, nb, 1, early_stopping, length_penalty, eos_token_id, pad,
+                        use_graph, stop_chunk, grammar, None, in_key, key_config(in_key, key, B0, V, nrs * nb), return_scores,
+                        'beam-sample', sample=True, top_k=top_k, top_p=top_p, temperature=temperature, typical_p=typical_p)
 
 
 def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 4, num_beam_groups: int = 2,

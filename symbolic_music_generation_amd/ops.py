@@ -417,6 +417,47 @@ def beam_step(logp, V, beam_scores, ids, t_dev, nb, eos_id, pad_id, length_penal
         check(lib().mxl_group_beam_step(*front, int(ng), float(diversity_penalty), *rest), 'mxl_group_beam_step')
 
 
+def beam_sample_draw(logp, V, beam_scores, nb, rng_ctr, seed, drawn, top_k=0, top_p=1.0, temperature=1.0, typical_p=1.0, out_warped=None):
+    """the draw of one beam-sample step (mxl_beam_sample_draw): every row of logp (rows, >= V) f32, already masked by the rules, goes
+    through HF's warpers with min_tokens_to_keep = 2 and is renormalised to w; every item (nb rows) draws 2 * nb of its nb * V
+    candidates without replacement with probabilities softmax(w), by Gumbel-top-k with a uniform hashed from (seed, *rng_ctr, row,
+    token).  drawn (rows, logp's row stride) f32: w at the drawn candidates, -inf elsewhere in columns 0..V-1.  A row with
+    beam_scores == -inf is dead and contributes nothing.  out_warped (rows, V) f32: every row's whole w (a test hook).  The counter is
+    read on the device and not advanced."""
+    rows = logp.shape[0]
+    for t, what in ((logp, 'logp'), (beam_scores, 'beam_scores'), (drawn, 'drawn')):
+        _req(t, torch.float32, f'beam_sample_draw {what}')
+    if V > 2048:
+        raise MusicXLError(f'beam_sample_draw: a vocabulary of {V} tokens is beyond the 2048 of the LDS sort')
+    if nb < 2 or rows % nb or logp.shape[1] < V or logp.stride(1) != 1 or beam_scores.numel() != rows or not beam_scores.is_contiguous():
+        raise MusicXLError(f'beam_sample_draw: logp must be (rows, >= {V}) with nb >= 2 rows per item, beam_scores (rows,)')
+    if drawn.shape[0] != rows or drawn.stride(0) != logp.stride(0) or drawn.stride(1) != 1 or drawn.shape[1] < V:
+        raise MusicXLError('beam_sample_draw: drawn must have the rows and the row stride of logp')
+    if rng_ctr.dtype != torch.int64 or not rng_ctr.is_cuda:
+        raise MusicXLError('beam_sample_draw: rng_ctr must be a device int64 counter')
+    if out_warped is not None:
+        _req(out_warped, torch.float32, 'beam_sample_draw out_warped')
+        if tuple(out_warped.shape) != (rows, V) or not out_warped.is_contiguous():
+            raise MusicXLError(f'beam_sample_draw: out_warped must be a contiguous ({rows}, {V})')
+    check(lib().mxl_beam_sample_draw(_p(logp), logp.stride(0), int(V), _p(beam_scores), rows // nb, int(nb), _p(rng_ctr),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(top_k or 0), float(top_p if top_p is not None else 1.0),
+                                     float(temperature if temperature is not None else 1.0),
+                                     float(typical_p if typical_p is not None else 1.0), _p(drawn), _p(out_warped), _stream()),
+          'mxl_beam_sample_draw')
+
+
+def beam_sample_step(drawn, V, beam_scores, ids, t_dev, nb, eos_id, pad_id, length_penalty, early_stopping, hyp_ids, hyp_len, hyp_score,
+                     hyp_n, done, n_done, beam_idx, moved, words=None, n_words=0):
+    """beam_step over the matrix `drawn` of beam_sample_draw (mxl_beam_sample_step): a candidate's score is its entry of `drawn` itself
+    (-inf in a row whose running score is -inf), not a sum with the running score; everything else is beam_step's."""
+    rows, Bs = _beam_step_args('beam_sample_step', drawn, V, beam_scores, ids, nb, hyp_ids, hyp_len, hyp_score, hyp_n, done, n_done,
+                               beam_idx, moved, words, n_words)
+    check(lib().mxl_beam_sample_step(_p(drawn), drawn.stride(0), _p(beam_scores), _p(ids), ids.stride(0), _p(t_dev), Bs, int(nb), int(V),
+                                     int(eos_id), int(pad_id), float(length_penalty), int(bool(early_stopping)), _p(hyp_ids), _p(hyp_len),
+                                     _p(hyp_score), _p(hyp_n), _p(done), _p(n_done), _p(beam_idx), _p(moved), _p(words),
+                                     int(n_words) if words is not None else 0, rows, _stream()), 'mxl_beam_sample_step')
+
+
 def beam_reorder(bufs, nb, beam_idx, moved, table=None):
     """rows follow their beams in place (mxl_beam_reorder): bufs = one contiguous (rows, ...) tensor, or a list of them of one shape
     with `table`, their addresses as a device int64 tensor (beam_table) -- one launch for all.  Items with moved[b] == 0 are skipped

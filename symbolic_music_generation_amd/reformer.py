@@ -154,7 +154,7 @@ class MyReformerModelWithLMHead(EngineModule):
                  num_beam_groups: int = 1, length_penalty: float = 1.0, diversity_penalty=None,
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
-                 grammar=None, n_bars=None, in_key=None, key=None, melody=None, **unsupported):
+                 grammar=None, n_bars=None, in_key=None, key=None, melody=None, device_scorer: bool = False, **unsupported):
         """`model.generate(...)` as the reference drives it (musicnlp/trainer/eval.py:277-333): greedy, or sampling with
         top-k / top-p / typical-p / temperature / repetition penalty (applied, as HF does, to the raw logits); token selection
         runs on the device (the TransfoXL decoder's sampler kernel).
@@ -210,7 +210,8 @@ class MyReformerModelWithLMHead(EngineModule):
         # every search runs on the host here (no caps); the rules were settled above
         plan = plan_search({}, num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample, penalty_alpha=penalty_alpha,
                            top_k=top_k, eos_token_id=eos_token_id, pad_token_id=pad_token_id, config_eos=self.config.eos_token_id,
-                           config_pad=self.config.pad_token_id)
+                           config_pad=self.config.pad_token_id, device_scorer=device_scorer, repetition_penalty=repetition_penalty,
+                           renormalize_logits=renormalize_logits, vocab_size=self.config.vocab_size)
         guide = melody_config(melody, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, n_bars, nrs)
         n_bars = (bar_count_config(n_bars, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, nrs) if guide is None
                   else guide.n_bars)

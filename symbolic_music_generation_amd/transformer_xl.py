@@ -199,7 +199,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  use_graph: bool = True, seed: int = 77, attention_mask: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
                  min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, melody=None,
-                 **unused) -> torch.Tensor:
+                 device_scorer: bool = False, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -226,7 +226,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         `max_new_tokens`; the prompts must obey the grammar themselves (MusicXLError otherwise).  That constraint is syntactic;
         `tokenizer.grammar(bar_budget=True)` adds the bar budget, under which every channel of every generated bar is also exactly
         as long as the row's time signature (rows with TimeSig_rare stay syntactic).  Plain beam search, group beam search and
-        contrastive search take it too (below); beam-sample takes no grammar.
+        contrastive search take it too (below); beam-sample takes it with `device_scorer=True` only.
 
         `n_bars` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): length in bars.  An int, or a
         sequence or tensor of one int per prompt (repeated per prompt under `num_return_sequences`); a negative entry leaves that
@@ -246,7 +246,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         prompts' keys.  The prompt only supplies the key: its own pitches are not judged.  A generated `Key_*` token sets the row's
         key from then on.  The key lives on the device beside the other rules' words and the mask sits in the same sampler launch,
         in the same place.  It needs no `grammar` and combines with everything greedy decoding and sampling take, and with
-        plain beam search, group beam search and contrastive search (below); beam-sample takes no `in_key`.
+        plain beam search, group beam search and contrastive search (below); beam-sample takes it with `device_scorer=True` only.
 
         `melody` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling): here is a melody, write the bass
         under it.  A guide is the concatenation of the `<bar> <melody> ... <bass>` spans of its bars, each bar up to and including
@@ -280,6 +280,19 @@ class MyTransfoXLLMHeadModel(EngineModule):
         prompts stay refused.  `MXL_BEAM_HOST=1` keeps the host scorer here as well (`generate.group_beam_search`, no rules), as
         does a `diversity_penalty` that is negative or infinite.
 
+        Beam-sample (`num_beams` 2.., `num_beam_groups=1`, `do_sample=True` -- the reference's default 'beam' settings) runs its
+        scorer on the host (`generate.beam_search(do_sample=True)`: `_warp`, torch.multinomial from a generator seeded with `seed`)
+        and takes no rules.  `device_scorer=True` (opt-in) runs it on the device instead (`generate.beam_sample_device`: the rules
+        mask, mxl_beam_sample_draw -- the warpers with two tokens kept, the renormalisation and the draw of `2 * num_beams`
+        candidates per item without replacement, by Gumbel-top-k -- and mxl_beam_sample_step inside the captured step).  It is no
+        default because its draw is another random stream than torch.multinomial's: the same `seed` returns other ids, while a call
+        without the keyword returns what it always did.  With the keyword the call takes `grammar` (with or without a bar budget)
+        and `in_key` / `key` with the checks above, given an explicit `eos_token_id=`; per-prompt values are shared by the
+        prompt's `num_return_sequences` items and their beams.  `n_bars`, `melody` and padded prompts stay refused.  The keyword
+        raises MusicXLError without `renormalize_logits=True` (the reference always sets it), for a vocabulary above 2048 tokens,
+        for `num_beams` outside 2..16 and under `MXL_BEAM_HOST=1`, and ValueError with any other strategy or with a
+        `repetition_penalty` other than None / 1.0 (the beam arms apply none).
+
         Contrastive search (`penalty_alpha > 0`, `top_k` 2..32) runs with its whole step on the device
         (`generate.contrastive_search_device`: mxl_contrastive_topk / mxl_contrastive_step / mxl_ring_slot_broadcast inside the captured
         step; `use_graph` is honoured) and returns what the host path returns.  It takes `grammar` (with or without a bar budget) and
@@ -287,7 +300,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
         values are shared by the prompt's `top_k` rows, a barred token is -inf before the top-k, where HF's logits processors sit, and
         a barred candidate is never picked.  `n_bars`, `melody` and padded prompts stay refused.  `top_k > 32` or
         `MXL_CONTRASTIVE_HOST=1` keeps the host-driven loop (`generate.contrastive_search`), which takes no rules here."""
-        from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, beam_search_device,
+        from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, beam_sample_device,
+                               beam_search_device,
                                check_grammar_args, contrastive_search, contrastive_search_device, group_beam_search_device, key_config,
                                left_pad_counts, melody_config, plan_search, resolve_max_length, stop_config)
         n_pad = None
@@ -306,11 +320,13 @@ class MyTransfoXLLMHeadModel(EngineModule):
         self._maybe_resync()
         max_length = resolve_max_length(max_length, max_new_tokens, input_ids.shape[1], self.config.max_length_)
         check_grammar_args(grammar, self.config.vocab_size, stop)
-        plan = plan_search(dict(beam=BEAM_MAX, group_beam=BEAM_MAX, contrastive=CONTRASTIVE_MAX),        # what runs on the device
+        plan = plan_search(dict(beam=BEAM_MAX, group_beam=BEAM_MAX, contrastive=CONTRASTIVE_MAX, beam_sample=BEAM_MAX),   # on the device
                            num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample, penalty_alpha=penalty_alpha,
                            top_k=top_k, diversity_penalty=diversity_penalty, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                            config_eos=self.config.eos_token_id, config_pad=self.config.pad_token_id, padded=n_pad is not None,
-                           grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody)
+                           grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody, device_scorer=device_scorer,
+                           repetition_penalty=repetition_penalty, renormalize_logits=renormalize_logits,
+                           vocab_size=self.config.vocab_size)
         B0 = input_ids.shape[0]
         guide = melody_config(melody, B0, grammar, stop, n_bars, num_return_sequences)
         bars = bar_count_config(n_bars, B0, grammar, stop, num_return_sequences) if guide is None else None
@@ -325,6 +341,10 @@ class MyTransfoXLLMHeadModel(EngineModule):
         if plan.device:                                     # (the device searches repeat per-prompt values per beam themselves)
             beams = dict(num_beams=num_beams, early_stopping=bool(early_stopping), length_penalty=length_penalty,
                          num_return_sequences=num_return_sequences, use_graph=use_graph, grammar=grammar, in_key=in_key, key=key, **ends)
+            if plan.strategy == 'beam_sample':
+                dec = XLDecoder(self.engine, B0 * num_return_sequences * num_beams, max_length, seed=seed)
+                return beam_sample_device(dec, input_ids, max_length, top_k=top_k, top_p=top_p, temperature=temperature,
+                                          typical_p=typical_p, **beams)
             dec = XLDecoder(self.engine, B0 * num_beams, max_length, seed=seed)
             if plan.strategy == 'beam':
                 return beam_search_device(dec, input_ids, max_length, n_bars=n_bars, **beams)
