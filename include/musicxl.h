@@ -428,11 +428,11 @@ int mxl_sample_large(const float* logprobs, int ldl, int V, void* ids, int ld_id
 /* t_dev += 1; rng_ctr += 1 */
 int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
 /* ------------------------------------------------------------------------------------------------------------
- * Rules of a generation.  Six optional groups of per-row state on the device, applied around every sampled token; three entries take
+ * Rules of a generation.  Seven optional groups of per-row state on the device, applied around every sampled token; three entries take
  * the first four as the same flat argument list (below): mxl_sample_step, mxl_rules_mask, mxl_rules_advance, their mxl_keyed_*
- * forms take the fifth after it and their mxl_guided_* forms the sixth after that.  A group is off when its state pointer is NULL:
- * unfinished (with alive), gstate (with allow, next), gbar (with grem, slots, bars), gleft, gkey (with keys, pcs, inkey), gpos (with
- * gforce, guide, glen).  Within a group either every pointer is given or none; the budget, the count and the guide need `cls`;
+ * forms take the fifth after it, their mxl_guided_* forms the sixth after that and their mxl_ranged_* forms the seventh after that.
+ * A group is off when its state pointer is NULL: unfinished (with alive), gstate (with allow, next), gbar (with grem, slots, bars),
+ * gleft, gkey (with keys, pcs, inkey), gpos (with gforce, guide, glen), gpart (with gfloor, grange, reg).  Within a group either every pointer is given or none; the budget, the count and the guide need `cls`;
  * anything else is MXL_EINVAL.
  *
  * stop: eos_id, pad_id, min_length, unfinished, alive -- stopping at eos (HF greedy_search / sample with an eos_token_id).
@@ -483,6 +483,24 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  *   += 1 -- it is the guide's own <bar>.  The words of every other group move along a forced token as along a chosen one.  The group
  *   does not stop a row: the caller sets gleft to the number of bars in the guide, so the count group bars the end while guided bars
  *   are owed and a further bar once none is.
+ * register: reg, grange, gpart, gfloor, gap (the mxl_ranged_* entries) -- every part stays in its register, and the bass under the
+ *   melody.  Per row three int32 words: grange, the row's bounds lo_melody, hi_melody, lo_bass, hi_bass as inclusive MIDI numbers, one
+ *   byte each from the lowest (fixed for the generation, never written; 0, 127, 0, 127 = unconstrained); gpart, 0 = no part is open,
+ *   1 = the melody, 2 = the bass; gfloor, the lowest melody pitch of the open bar, 128 = none yet.  One scalar for the launch: gap, -1
+ *   = the bass is not tied to the melody, g >= 0 = it is.  Table: reg (V,) uint8, pitch token -> MIDI number 0..127; 0x80 / 0x81 /
+ *   0x82 = the <melody> / <bass> / <bar> token; 0xFF = any other token, the rest and the rare-pitch token included.  In a row with
+ *   gpart = p > 0 token v with reg[v] <= 127 is barred iff reg[v] lies outside [lo_p, hi_p]; in the bass with gap >= 0 and gfloor <
+ *   128 the upper bound is min(hi_bass, gfloor - gap) -- gap 0 lets the bass touch the bar's lowest melody note, gap 1 keeps it strictly
+ *   below.  A row with gpart == 0 is untouched.  The group reads neither `cls` nor the grammar state and works with every other group
+ *   off; the token is -inf in the same place as under the other groups, and a token the guide forces is never barred.  A kept token
+ *   moves the row: 0x80 sets gpart = 1, 0x81 sets gpart = 2, 0x82 sets gpart = 0 and gfloor = 128, a pitch under gpart == 1 sets
+ *   gfloor = min(gfloor, pitch) -- a forced melody note is not judged but does lower the floor -- and nothing else moves the words.
+ *   The bound is per bar, not aligned in time: "under the lowest melody note of the bar" is sufficient to keep the parts from
+ *   crossing, not necessary.
+ *   No dead end: the rule judges pitches by their MIDI number alone and never bars a token whose reg entry is above 127.  The rest and
+ *   the rare-pitch token are such tokens and belong to the grammar's class `pitch`, and the budget judges a pitch by that class alone,
+ *   so wherever the grammar or the budget allows "a pitch" one of the two remains even when the bounds leave no pitched token (the
+ *   floor under lo_bass, say).  The key rule never bars them either.
  *
  * The words move along the token a row keeps, after the stop rule: a row that was finished before the step emits pad and keeps its
  * words; the step in which a row emits eos still moves them.  Each row's words are read and written for that row alone.
@@ -558,6 +576,35 @@ int mxl_guided_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int
                              int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
                              int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
                              int* gforce, void* stream);
+/* The guided entries with the register group after the guide group; with reg = grange = gpart = gfloor = NULL they are those entries
+ * (gap is then ignored).  In the fused launch the register group is one more variant, which stands alone like the key group. */
+int mxl_ranged_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                           unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                           float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                           int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
+                           const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
+                           unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
+                           int* gleft, const void* keys, const void* pcs, const void* inkey, int* gkey, const void* guide,
+                           int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos, int* gforce, const void* reg,
+                           const void* grange, int* gpart, int* gfloor, int gap, float* out_probs, void* stream);
+int mxl_ranged_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length,
+                          int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
+                          const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
+                          int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
+                          int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
+                          int* gforce, const void* reg, const void* grange, int* gpart, int* gfloor, int gap, void* stream);
+int mxl_ranged_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length,
+                             int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
+                             const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
+                             int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
+                             int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
+                             int* gforce, const void* reg, const void* grange, int* gpart, int* gfloor, int gap, void* stream);
+/* (gpart, gfloor) of every row after columns 0..Tp-1 of ids (B, ld_ids) int64, walked from the words gpart[b] / gfloor[b] hold at the
+ * launch under the bounds grange[b] and `gap` (the register group above).  Ids < 0 (left pads) and ids >= V are skipped.  Columns
+ * before `from` only move the words -- the prompt's pitches are not judged; first_bad[b] = the first column >= from that holds a pitch
+ * outside the bounds of the row's open part, where the walk of that row stops, -1 = none.  from = Tp: the words after the prompt. */
+int mxl_register_scan(const void* ids, int ld_ids, int Tp, int from, int B, int V, const void* reg, const void* grange, int gap,
+                      int* gpart, int* gfloor, int* first_bad, void* stream);
 /* Key of every row after columns 0..Tp-1 of ids (B, ld_ids) int64, walked from the key gkey[b] holds at the launch (-1 = none): a
  * key token sets it.  Ids < 0 (left pads) and ids >= V are skipped.  Columns before `from` only move the key -- a prompt supplies its
  * key, its pitches are not judged; first_bad[b] = the first column >= from that holds a pitch outside the row's key, where the walk

@@ -21,6 +21,13 @@ in C major, every row constrained), alternating as above; the tokens per second 
 
     python3 scripts/perf_decode_grammar.py --in-key
     python3 scripts/perf_decode_grammar.py --in-key --only key            # or plain
+
+`--register`: what `generate(register=)` costs, at the same shape, without a grammar: `plain` against `register` (the register rule
+with melody_range 55..84, bass_range 36..60 and bass_below 1 in every row), alternating as above; the rows that `check_register`
+finds clean are printed for each arm.
+
+    python3 scripts/perf_decode_grammar.py --register
+    python3 scripts/perf_decode_grammar.py --register --only register     # or plain
 """
 import os
 import statistics
@@ -38,6 +45,7 @@ ROUNDS, STEPS = int(os.environ.get('ROUNDS', 6)), int(os.environ.get('STEPS', 40
 ONLY = sys.argv[sys.argv.index('--only') + 1] if '--only' in sys.argv else None
 N_BARS = int(sys.argv[sys.argv.index('--n-bars') + 1]) if '--n-bars' in sys.argv else None
 IN_KEY = '--in-key' in sys.argv
+REGISTER = '--register' in sys.argv
 
 vocab = MusicVocabulary(pitch_kind='degree')
 assert len(vocab) == V
@@ -69,9 +77,9 @@ ids = prompts()
 samp = dict(do_sample=True, top_k=8, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0)
 
 
-def window(dec, g, steps, stop=None, n_bars=None, in_key=None):
+def window(dec, g, steps, stop=None, n_bars=None, in_key=None, register=None):
     """ms per replayed step over `steps` steps right after the prompt pass (ring slots Tp .. Tp + 20 + steps)"""
-    n = dec.begin(ids, L, samp, use_graph=True, grammar=g, stop=stop, n_bars=n_bars, in_key=in_key)
+    n = dec.begin(ids, L, samp, use_graph=True, grammar=g, stop=stop, n_bars=n_bars, in_key=in_key, register=register)
     assert n >= steps + 20
     for _ in range(20):
         dec.replay_once()
@@ -150,8 +158,42 @@ def key_arms():
     print(f'  key - plain = {d:+.4f} ms/step ({100 * d / med["plain"]:+.2f} %); run-to-run spread {max(spread.values()):.4f} ms')
 
 
+def register_arms():
+    """the --register comparison (module docstring)"""
+    from symbolic_music_generation_amd.generate import check_register, register_config
+    rule = vocab.register_rule()
+    bounds = dict(melody_range=(55, 84), bass_range=(36, 60), bass_below=1)
+    arms = {'plain': {}, 'register': dict(register=register_config(rule, batch=B, vocab_size=V, **bounds))}
+    if ONLY:
+        dec = XLDecoderLanes(model.engine, B, L, seed=5, lanes=2)
+        print(f'{ONLY}: {window(dec, None, 50, **arms[ONLY]):.3f} ms per step (50 steps)', flush=True)
+        return
+    decs = {k: XLDecoderLanes(model.engine, B, L, seed=5, lanes=2) for k in arms}
+    for name, dec in decs.items():                                  # warm-up: library attributes, workspaces, graph capture
+        window(dec, None, 20, **arms[name])
+    ms = {k: [] for k in arms}
+    for r in range(ROUNDS):
+        for name in (('plain', 'register') if r % 2 == 0 else ('register', 'plain')):
+            ms[name].append(window(decs[name], None, STEPS, **arms[name]))
+        print(f'round {r}: plain {ms["plain"][-1]:.4f} ms/step, register {ms["register"][-1]:.4f} ms/step', flush=True)
+    for k in arms:
+        out = torch.cat([d.ids[:, :Tp + 20 + STEPS] for d in decs[k].lanes], 0)
+        print(f'{k:8s}: rows clean under check_register {int((check_register(out, rule, **bounds, prompt_len=Tp) < 0).sum())} of {B}')
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = {k: max(v) - min(v) for k, v in ms.items()}
+    print(f'C5 decode step, {B} rows, 2 lanes, {STEPS} replayed steps x {ROUNDS} alternating rounds')
+    for k in arms:
+        print(f'  {k:8s} median {med[k]:.4f} ms/step = {1e3 * B / med[k]:.0f} tok/s  min {min(ms[k]):.4f}  max {max(ms[k]):.4f}  '
+              f'spread {spread[k]:.4f}')
+    d = med['register'] - med['plain']
+    print(f'  register - plain = {d:+.4f} ms/step ({100 * d / med["plain"]:+.2f} %); run-to-run spread {max(spread.values()):.4f} ms')
+
+
 with torch.no_grad():
     assert check_grammar(ids, grammar).tolist() == [-1] * B
+    if REGISTER:
+        register_arms()
+        sys.exit(0)
     if IN_KEY:
         key_arms()
         sys.exit(0)

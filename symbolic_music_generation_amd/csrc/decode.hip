@@ -363,12 +363,23 @@ constexpr int SORT_N = 2048;
 // token v under a row's words (rules_load below): its class under the allow word (c: a rule over classes is on), with the bar budget
 // the slots the row still has free, with the key rule the pitch classes of the row's key.  `inkey` has bits 12..31 set, and a token
 // that is no pitch has pcs 0xFF, which tests bit 31: one byte load and one shift, no branch.  `forced` >= 0 (gd: the guide group is
-// on): the row is fed that token from its guide -- it alone is allowed, whatever the other groups say.
+// on): the row is fed that token from its guide -- it alone is allowed, whatever the other groups say.  `rw` (rg: the register group
+// is on): the open part's bounds as register_word packs them; a pitch passes the one unsigned compare reg[v] - lo <= hi - lo, and a
+// token that is no pitch has bit 7 of its reg entry set, which is or-ed in: one byte load, no branch.
+struct RegWord {
+    const unsigned char* reg;
+    uint32_t lo, span;
+};
 __device__ __forceinline__ bool token_allowed(const unsigned char* cls, uint32_t allow, const unsigned short* slots, int remcap,
                                               const unsigned char* pcs, uint32_t inkey, long long v, bool c, bool bud, bool ink,
-                                              bool gd = false, int forced = -1) {
+                                              bool gd = false, int forced = -1, bool rg = false, RegWord rw = RegWord{nullptr, 0u, 127u}) {
     if (gd && forced >= 0) return v == forced;
-    return (!c || ((allow >> cls[v]) & 1u)) && (!bud || (int)slots[v] <= remcap) && (!ink || ((inkey >> (pcs[v] & 31)) & 1u));
+    bool ok = (!c || ((allow >> cls[v]) & 1u)) && (!bud || (int)slots[v] <= remcap) && (!ink || ((inkey >> (pcs[v] & 31)) & 1u));
+    if (rg) {
+        const uint32_t p = rw.reg[v];
+        ok = ok && ((uint32_t)(p - rw.lo <= rw.span) | (p >> 7));
+    }
+    return ok;
 }
 
 // the row's next token (returned to every thread of the workgroup).
@@ -381,14 +392,17 @@ __device__ __forceinline__ bool token_allowed(const unsigned char* cls, uint32_t
 // is -inf in the same place.
 // GD (with G): in a row with `forced` >= 0 every token but that one is -inf in the same place, the other groups and min_length
 // have no say, and the sampler -- greedy or not -- is left with a one-token support.
-template <bool G = false, bool BUD = false, bool INK = false, bool GD = false>
+// RG (with or without G): a pitch token whose MIDI number lies outside the bounds `rw` of the row's open part is -inf in the same
+// place.
+template <bool G = false, bool BUD = false, bool INK = false, bool GD = false, bool RG = false>
 __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, const long long* ids, int ld_ids,
                                           const int* t_dev, const unsigned long long* rng_ctr, unsigned long long seed,
                                           int do_sample, int top_k, float top_p, float temperature,
                                           float repetition_penalty, float typical_p, float* out_probs, int eos_id = -1,
                                           int min_length = 0, const unsigned char* gcls = nullptr, uint32_t gallow = 0u,
                                           const unsigned short* bslots = nullptr, int remcap = 0,
-                                          const unsigned char* pcs = nullptr, uint32_t inkey = ~0u, int forced = -1) {
+                                          const unsigned char* pcs = nullptr, uint32_t inkey = ~0u, int forced = -1,
+                                          RegWord rw = RegWord{nullptr, 0u, 127u}) {
     __shared__ float key[SORT_N];
     __shared__ int idx[SORT_N];
     __shared__ int sh_pick;
@@ -396,7 +410,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
     const float* row = logp + (size_t)b * ldl;
     const float invt = 1.f / temperature;
     for (int i = tid; i < SORT_N; i += 256) {
-        if (G || INK) key[i] = (i < V && token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, i, G, BUD, INK, GD, forced)) ? row[i] * invt : -INFINITY;
+        if (G || INK || RG) key[i] = (i < V && token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, i, G, BUD, INK, GD, forced, RG, rw)) ? row[i] * invt : -INFINITY;
         else key[i] = i < V ? row[i] * invt : -INFINITY;
         idx[i] = i;
     }
@@ -409,7 +423,7 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
         const long long* hist = ids + (size_t)b * ld_ids;
         for (int j = tid; j <= tcur; j += 256) {
             const long long tok = hist[j];
-            if (tok >= 0 && tok < V && (!(G || INK) || token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, tok, G, BUD, INK, GD, forced))) {
+            if (tok >= 0 && tok < V && (!(G || INK || RG) || token_allowed(gcls, gallow, bslots, remcap, pcs, inkey, tok, G, BUD, INK, GD, forced, RG, rw))) {
                 const float v = row[tok];
                 key[tok] = (v < 0.f ? v * repetition_penalty : v / repetition_penalty) * invt;
             }
@@ -589,9 +603,9 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The rules of one generation (include/musicxl.h, "Rules of a generation"), passed to kernels by value.  Six groups, each off when
-// its state pointer (unfinished / gstate / gbar / gleft / gkey / gpos) is NULL; the budget, the count and the guide read the token
-// classes `cls` of the grammar group and nothing else of it, the key reads nothing of it at all.
+// The rules of one generation (include/musicxl.h, "Rules of a generation"), passed to kernels by value.  Seven groups, each off when
+// its state pointer (unfinished / gstate / gbar / gleft / gkey / gpos / gpart) is NULL; the budget, the count and the guide read the
+// token classes `cls` of the grammar group and nothing else of it, the key and the register read nothing of it at all.
 //   stop     HF greedy_search / sample: a finished row emits pad, a live row that emits eos is finished; eos barred below min_length
 //   grammar  a token class automaton: cls (V,) token -> class, allow (S,) bit c = class c may follow in state s, next (S, C) successor
 //   budget   grammar.BarBudget: per row `bar` (bar length in slots, 0 = unconstrained) and `rem` (slots still free in the open
@@ -610,6 +624,12 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 //            that token is never barred: the group overrides every other one and min_length.  A kept token under force takes pos one
 //            on and, if its class is in `leave`, clears force; a kept `enter` token of a free row with pos < glen sets force and
 //            takes pos one on (it is the guide's own <bar>)
+//   register grammar.RegisterRule: per row `range` (the bounds lo_melody, hi_melody, lo_bass, hi_bass as MIDI numbers, one byte each
+//            from the lowest; fixed for the generation), `part` (0 = no open part, 1 = melody, 2 = bass) and `floor` (the lowest melody
+//            pitch of the open bar, 128 = none yet).  reg (V,) uint8: pitch token -> MIDI number 0..127, <melody> / <bass> / <bar> ->
+//            REG_MELODY / REG_BASS / REG_BAR, 0xFF = anything else (rests and the rare pitch included).  A pitch outside the open
+//            part's bounds is barred; in the bass, with gap >= 0 and a floor, the upper bound is min(hi_bass, floor - gap).  A kept part
+//            token sets part, <bar> clears part and floor, a melody pitch lowers floor
 // The next rule is one more group here, one line in each of rules_load / rules_move and one in make_rules.
 // ---------------------------------------------------------------------------------------------------------------
 struct DecodeRules {
@@ -638,6 +658,11 @@ struct DecodeRules {
     uint32_t enter, leave;
     int* gpos;
     int* gforce;
+    const unsigned char* reg;
+    const int* grange;
+    int* gpart;
+    int* gfloor;
+    int gap;
 };
 
 constexpr int BUDGET_NONE = 0xFFFF;          // slots: unknown length (beyond any rem); bars: not a time signature
@@ -669,20 +694,44 @@ constexpr int KEY_NONE = 0xFF;               // keys: no key token; pcs: no pitc
 __device__ __forceinline__ uint32_t key_word(const unsigned short* inkey, int key) {
     return (unsigned)key < (unsigned)N_KEYS ? ((uint32_t)inkey[key] | 0xFFFFF000u) : KEY_ANY;
 }
+constexpr int REG_MELODY = 0x80, REG_BASS = 0x81, REG_BAR = 0x82;   // reg: the tokens that move the row's part
+constexpr int FLOOR_NONE = 128;              // gfloor: no melody pitch in the open bar yet
+// the bounds of a row in `part` under `range`, `floor` and `gap`, as token_allowed reads them: lo and hi - lo; bounds that leave no
+// pitch (the floor under lo_bass) become lo = 256, which no reg entry reaches -- the rest and the rare pitch stay, see musicxl.h
+__device__ __forceinline__ RegWord register_word(const unsigned char* reg, uint32_t range, int part, int floor, int gap) {
+    int lo = 0, hi = 127;
+    if (part == 1) { lo = range & 0xFF; hi = (range >> 8) & 0xFF; }
+    else if (part == 2) {
+        lo = (range >> 16) & 0xFF;
+        hi = (range >> 24) & 0xFF;
+        if (gap >= 0 && floor < FLOOR_NONE) hi = min(hi, floor - gap);
+    }
+    return hi >= lo ? RegWord{reg, (uint32_t)lo, (uint32_t)(hi - lo)} : RegWord{reg, 256u, 0u};
+}
+// (part, floor) after a token with reg entry p (RegisterRule.move)
+__device__ __forceinline__ void register_move(int& part, int& floor, int p) {
+    if (p == REG_MELODY) part = 1;
+    else if (p == REG_BASS) part = 2;
+    else if (p == REG_BAR) { part = 0; floor = FLOOR_NONE; }
+    else if (p < 128 && part == 1) floor = min(floor, p);
+}
 
 // The words of row b and what they admit: `allow` has a bit per class the row may emit (every bit without a grammar), `remcap` is
 // the largest slots entry, `inkey` a bit per pitch class (key_word), `forced` the guide token the row is fed at this step (-1 = none:
-// the row chooses).  g / bud / cnt / ink / gd: which groups are on -- compile-time constants in the fused kernel, pointer tests in
-// the unfused pair; everything here inlines and folds on them.
+// the row chooses), `rw` the bounds of the open part (register_word).  g / bud / cnt / ink / gd / rg: which groups are on --
+// compile-time constants in the fused kernel, pointer tests in the unfused pair; everything here inlines and folds on them.
 struct RowWords {
     int gs, bar, rem, left;
     uint32_t allow;
     int remcap;
     uint32_t inkey;
     int pos, force, forced;
+    int part, floor;
+    RegWord rw;
 };
-__device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool g, bool bud, bool cnt, bool ink, bool gd = false) {
-    RowWords w{0, 0, 0, -1, ~0u, BUDGET_NONE, KEY_ANY, 0, 0, -1};
+__device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool g, bool bud, bool cnt, bool ink, bool gd = false,
+                                               bool rg = false) {
+    RowWords w{0, 0, 0, -1, ~0u, BUDGET_NONE, KEY_ANY, 0, 0, -1, 0, FLOOR_NONE, RegWord{nullptr, 0u, 127u}};
     if (g) { w.gs = r.gstate[b]; w.allow = r.allow[w.gs]; }
     if (bud) {
         w.bar = r.gbar[b];
@@ -697,12 +746,17 @@ __device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool
         w.force = r.gforce[b];
         if (w.force && w.pos >= 0 && w.pos < min(r.glen[b], r.ld_guide)) w.forced = r.guide[(size_t)b * r.ld_guide + w.pos];
     }
+    if (rg) {
+        w.part = r.gpart[b];
+        w.floor = r.gfloor[b];
+        w.rw = register_word(r.reg, (uint32_t)r.grange[b], w.part, w.floor, r.gap);
+    }
     return w;
 }
 // row b moves along `tok`, a token of the vocabulary that the row chose itself (a row finished before the step emits pad, which is
 // not its choice and need not be a token its state allows: such a row keeps its words)
 __device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int b, long long tok, bool g, bool bud, bool cnt, bool ink,
-                                           bool gd = false) {
+                                           bool gd = false, bool rg = false) {
     const int c = (g || bud || cnt || gd) ? r.cls[tok] : 0;
     if (g) r.gstate[b] = r.next[w.gs * r.C + c];
     if (bud) {
@@ -724,6 +778,11 @@ __device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int
             r.gforce[b] = 1;
         }
     }
+    if (rg) {                                        // RegisterRule.move
+        register_move(w.part, w.floor, r.reg[tok]);
+        r.gpart[b] = w.part;
+        r.gfloor[b] = w.floor;
+    }
 }
 
 __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl, int V, long long* ids, int ld_ids,
@@ -741,14 +800,14 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl,
 // head's raw logits instead of log-probabilities when no repetition penalty is in force: every other warper, the argmax and the
 // renormalised draw are invariant under the per-row shift log-softmax applies.
 //
-// G / BUD / CNT / INK / GD: the grammar, budget, count, key and guide groups of `r` as compile-time variants (BUD, CNT and GD ride on
-// G, INK stands alone); the stop group is the runtime test of r.unfinished it has always been.  The row's words select the allow word and remcap the sampler applies
-// (rules_load), and thread 0 moves them along the token the row keeps (rules_move).  The move sits AFTER the eos rule: a row that
+// G / BUD / CNT / INK / GD / RG: the grammar, budget, count, key, guide and register groups of `r` as compile-time variants (BUD, CNT
+// and GD ride on G, INK and RG stand alone); the stop group is the runtime test of r.unfinished it has always been.  The row's words
+// select the allow word, remcap, the key's pitch classes and the open part's bounds the sampler applies (rules_load), and thread 0 moves them along the token the row keeps (rules_move).  The move sits AFTER the eos rule: a row that
 // was finished before this step emits pad and its words stay frozen; the step in which a live row emits eos still moves them, so a
 // finished row of the music grammar rests in END.  The words are per-row: row b's workgroup is their only reader and writer within a
 // launch, and the next launch on the stream sees them by stream order -- there is no hand-off between workgroups here beyond the
 // arrival counter below.
-template <bool G, bool BUD, bool CNT, bool INK, bool GD>
+template <bool G, bool BUD, bool CNT, bool INK, bool GD, bool RG>
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, int ldl, int V, long long* ids, int ld_ids,
                                                           int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                           int do_sample, int top_k, float top_p, float temperature,
@@ -756,10 +815,10 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
                                                           int d, float scale, int* counter, float* out_probs, DecodeRules r) {
     static_assert(G || !(BUD || CNT || GD), "the bar budget, the bar count and the guide ride on the grammar");
     int* const unfinished = r.unfinished;
-    const RowWords w = rules_load(r, blockIdx.x, G, BUD, CNT, INK, GD);
-    int tok = sample_row<G, BUD, INK, GD>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
+    const RowWords w = rules_load(r, blockIdx.x, G, BUD, CNT, INK, GD, RG);
+    int tok = sample_row<G, BUD, INK, GD, RG>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
                                       repetition_penalty, typical_p, out_probs, unfinished ? r.eos_id : -1,
-                                      unfinished ? r.min_length : 0, r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, w.forced);
+                                      unfinished ? r.min_length : 0, r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, w.forced, w.rw);
     const int b = blockIdx.x, tid = threadIdx.x;
     __shared__ int sh_tok, sh_live;
     bool was_live = true;                       // (thread 0) the token is the row's own choice
@@ -778,7 +837,7 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         __syncthreads();
         tok = sh_tok;
     }
-    if ((G || INK) && tid == 0 && was_live && tok >= 0 && tok < V) rules_move(r, w, b, tok, G, BUD, CNT, INK, GD);
+    if ((G || INK || RG) && tid == 0 && was_live && tok >= 0 && tok < V) rules_move(r, w, b, tok, G, BUD, CNT, INK, GD, RG);
     if (tid == 0) ids[(size_t)b * ld_ids + *t_dev + 1] = tok;
     const int id = (tok < 0 || tok >= V) ? 0 : tok;
     for (int c = tid; c < (d >> 3); c += 256) {
@@ -826,12 +885,12 @@ __global__ __launch_bounds__(256) void rules_mask_kernel(float* scores, int ldl,
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long long)B * V) return;
     const int b = (int)(i / V), v = (int)(i - (long long)b * V);
-    const bool bud = r.gbar != nullptr, ink = r.gkey != nullptr, gd = r.gpos != nullptr;
+    const bool bud = r.gbar != nullptr, ink = r.gkey != nullptr, gd = r.gpos != nullptr, rg = r.gpart != nullptr;
     bool ok = true;
     int forced = -1;
-    if (r.cls || ink) {
-        const RowWords w = rules_load(r, b, r.gstate != nullptr, bud, r.gleft != nullptr, ink, gd);
-        ok = token_allowed(r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, v, r.cls != nullptr, bud, ink, gd, w.forced);
+    if (r.cls || ink || rg) {
+        const RowWords w = rules_load(r, b, r.gstate != nullptr, bud, r.gleft != nullptr, ink, gd, rg);
+        ok = token_allowed(r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, v, r.cls != nullptr, bud, ink, gd, w.forced, rg, w.rw);
         forced = w.forced;
     }
     if (forced < 0 && r.min_length > 0 && v == r.eos_id && *t_dev + 1 < r.min_length) ok = false;
@@ -846,13 +905,14 @@ __global__ __launch_bounds__(256) void rules_advance_kernel(long long* ids, int 
     const int tid = threadIdx.x;
     const int t = *t_dev;
     const bool g = r.gstate != nullptr, bud = r.gbar != nullptr, cnt = r.gleft != nullptr, ink = r.gkey != nullptr;
-    const bool gd = r.gpos != nullptr;
+    const bool gd = r.gpos != nullptr, rg = r.gpart != nullptr;
     int n = 0;
     for (int b = tid; b < B; b += 256) {
         long long* p = ids + (size_t)b * ld_ids + t;
         const long long tok = *p;
         int live = r.unfinished ? r.unfinished[b] : 1;
-        if (live && (r.cls || ink) && tok >= 0 && tok < V) rules_move(r, rules_load(r, b, g, bud, cnt, ink, gd), b, tok, g, bud, cnt, ink, gd);
+        if (live && (r.cls || ink || rg) && tok >= 0 && tok < V)
+            rules_move(r, rules_load(r, b, g, bud, cnt, ink, gd, rg), b, tok, g, bud, cnt, ink, gd, rg);
         if (r.unfinished) {
             if (!live) *p = r.pad_id;
             else if (tok == r.eos_id) live = 0;
@@ -953,6 +1013,36 @@ __global__ __launch_bounds__(64) void key_scan_kernel(const long long* ids, int 
         }
     }
     if (lane == 0) { gkey[b] = key; first_bad[b] = bad; }
+}
+
+// (part, floor) of every row after columns 0..Tp-1, from the words gpart[b] / gfloor[b] hold at the launch (RegisterRule.walk), as the
+// scans above: one wave per row, 64 columns at a time, the lanes load the reg entries and every lane walks them.  Ids < 0 (left
+// pads) and ids beyond the vocabulary are skipped.  Columns before `from` only move the words (the prompt's pitches are not judged);
+// first_bad[b] = the first column >= from holding a pitch outside the bounds of the row's open part, where the walk of that row
+// stops, -1 = none.
+__global__ __launch_bounds__(64) void register_scan_kernel(const long long* ids, int ld_ids, int Tp, int from, int B, int V,
+                                                           const unsigned char* reg, const int* grange, int gap, int* gpart,
+                                                           int* gfloor, int* first_bad) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const long long* row = ids + (size_t)b * ld_ids;
+    const uint32_t range = (uint32_t)grange[b];
+    int part = gpart[b], floor = gfloor[b], bad = -1;
+    for (int base = 0; base < Tp && bad < 0; base += 64) {
+        const int col = base + lane;
+        int p = 0xFF;
+        if (col < Tp) {
+            const long long tok = row[col];
+            if (tok >= 0 && tok < V) p = reg[tok];
+        }
+        const int n = min(64, Tp - base);
+        for (int j = 0; j < n; j++) {
+            const uint32_t pj = (uint32_t)__shfl(p, j, 64);
+            const RegWord rw = register_word(reg, range, part, floor, gap);
+            if (base + j >= from && !((uint32_t)(pj - rw.lo <= rw.span) | (pj >> 7))) { bad = base + j; break; }
+            register_move(part, floor, (int)pj);
+        }
+    }
+    if (lane == 0) { gpart[b] = part; gfloor[b] = floor; first_bad[b] = bad; }
 }
 
 }  // namespace
@@ -1089,11 +1179,15 @@ extern "C" int mxl_sample(const float* logprobs, int ldl, int V, void* ids, int 
 #define GUIDE_PARAMS const void *guide, int ld_guide, const void *glen, unsigned enter, unsigned leave, int *gpos, int *gforce
 #define GUIDE_ARGS guide, ld_guide, glen, enter, leave, gpos, gforce
 #define GUIDE_OFF nullptr, 0, nullptr, 0u, 0u, nullptr, nullptr
+// the register group, which follows the guide group in the mxl_ranged_* entries
+#define REG_PARAMS const void *reg, const void *grange, int *gpart, int *gfloor, int gap
+#define REG_ARGS reg, grange, gpart, gfloor, gap
+#define REG_OFF nullptr, nullptr, nullptr, nullptr, -1
 
 // the one check of those arguments, before any launch: within a group all pointers or none; budget, count and guide read `cls`.
 // fused: the launch that also samples -- budget, count and guide ride on the grammar there, and arrivals and live rows share one
 // 32-bit word
-static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS) {
+static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS) {
     MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr));
     MXL_CHECK_ARG((allow == nullptr) == (gstate == nullptr) && (next == nullptr) == (gstate == nullptr));
     MXL_CHECK_ARG(!gstate || (cls && C >= 1 && C <= 32));
@@ -1102,29 +1196,37 @@ static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS, KEY_PARAM
     MXL_CHECK_ARG((keys == nullptr) == (gkey == nullptr) && (pcs == nullptr) == (gkey == nullptr) && (inkey == nullptr) == (gkey == nullptr));
     MXL_CHECK_ARG((guide == nullptr) == (gpos == nullptr) && (glen == nullptr) == (gpos == nullptr) && (gforce == nullptr) == (gpos == nullptr));
     MXL_CHECK_ARG(!gpos || (cls && ld_guide >= 1));
+    MXL_CHECK_ARG((reg == nullptr) == (gpart == nullptr) && (grange == nullptr) == (gpart == nullptr) && (gfloor == nullptr) == (gpart == nullptr));
+    MXL_CHECK_ARG(!gpart || (gap >= -1 && gap <= 127));
     if (fused) MXL_CHECK_ARG(!(gbar || gleft || gpos) || gstate);
     if (fused && unfinished) MXL_CHECK_ARG(B <= 32767);
     if (!unfinished && fused) { eos_id = -1; pad_id = 0; min_length = 0; }
     *r = DecodeRules{eos_id, pad_id, min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
                      (const unsigned char*)next, C, gstate, (const unsigned short*)slots, (const unsigned short*)bars, opens, need_free,
                      need_full, gbar, grem, count, end, gleft, (const unsigned char*)keys, (const unsigned char*)pcs,
-                     (const unsigned short*)inkey, gkey, (const int*)guide, ld_guide, (const int*)glen, enter, leave, gpos, gforce};
+                     (const unsigned short*)inkey, gkey, (const int*)guide, ld_guide, (const int*)glen, enter, leave, gpos, gforce,
+                     (const unsigned char*)reg, (const int*)grange, gpart, gfloor, gap};
     return MXL_OK;
 }
 
-extern "C" int mxl_guided_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+extern "C" int mxl_ranged_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
                                       unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                                       float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, float* out_probs, void* stream) {
+                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS, float* out_probs, void* stream) {
     MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
     MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
     MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
     DecodeRules r;
-    if (const int e = make_rules(&r, B, true, RULES_ARGS, KEY_ARGS, GUIDE_ARGS)) return e;
-#define LAUNCH_K(G, BUD, CNT, INK, GD)                                                                                                   \
-    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT, INK, GD>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V,           \
+    if (const int e = make_rules(&r, B, true, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS)) return e;
+#define LAUNCH_R(G, BUD, CNT, INK, GD, RG)                                                                                               \
+    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT, INK, GD, RG>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V,       \
                        (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p, \
                        (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, out_probs, r)
+#define LAUNCH_K(G, BUD, CNT, INK, GD)                    \
+    do {                                                  \
+        if (gpart) LAUNCH_R(G, BUD, CNT, INK, GD, true);  \
+        else LAUNCH_R(G, BUD, CNT, INK, GD, false);       \
+    } while (0)
 #define LAUNCH_D(G, BUD, CNT, GD)                   \
     do {                                            \
         if (gkey) LAUNCH_K(G, BUD, CNT, true, GD);  \
@@ -1143,8 +1245,18 @@ extern "C" int mxl_guided_sample_step(const float* scores, int ldl, int V, void*
 #undef LAUNCH
 #undef LAUNCH_D
 #undef LAUNCH_K
+#undef LAUNCH_R
     MXL_LAUNCH_CHECK();
     return MXL_OK;
+}
+
+extern "C" int mxl_guided_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                                      unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                                      float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, float* out_probs, void* stream) {
+    return mxl_ranged_sample_step(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, B, do_sample, top_k, top_p, temperature,
+                                  repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_OFF,
+                                  out_probs, stream);
 }
 
 extern "C" int mxl_keyed_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
@@ -1164,17 +1276,22 @@ extern "C" int mxl_sample_step(const float* scores, int ldl, int V, void* ids, i
                                  repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_OFF, nullptr, stream);
 }
 
-extern "C" int mxl_guided_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                     void* stream) {
+extern "C" int mxl_ranged_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                     REG_PARAMS, void* stream) {
     MXL_CHECK_ARG(scores && B > 0 && V > 0 && ldl >= V && (t_dev || min_length <= 0));
     const long long n = (long long)B * V;
     MXL_CHECK_ARG(n <= (1LL << 38));
     DecodeRules r;
-    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS)) return e;
-    if (!r.cls && !r.gkey && (r.min_length <= 0 || r.eos_id < 0 || r.eos_id >= V)) return MXL_OK;          // nothing to bar
+    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS)) return e;
+    if (!r.cls && !r.gkey && !r.gpart && (r.min_length <= 0 || r.eos_id < 0 || r.eos_id >= V)) return MXL_OK;   // nothing to bar
     hipLaunchKernelGGL(rules_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V, t_dev, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
+}
+
+extern "C" int mxl_guided_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                     void* stream) {
+    return mxl_ranged_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_OFF, stream);
 }
 
 extern "C" int mxl_keyed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, void* stream) {
@@ -1185,15 +1302,20 @@ extern "C" int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t
     return mxl_keyed_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_OFF, stream);
 }
 
-extern "C" int mxl_guided_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                        void* stream) {
-    MXL_CHECK_ARG(ids && t_dev && B > 0 && (V > 0 || !(cls || gkey)));
+extern "C" int mxl_ranged_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                        REG_PARAMS, void* stream) {
+    MXL_CHECK_ARG(ids && t_dev && B > 0 && (V > 0 || !(cls || gkey || gpart)));
     DecodeRules r;
-    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS)) return e;
-    if (!r.cls && !r.gkey && !r.unfinished) return MXL_OK;                                       // nothing to move
+    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS)) return e;
+    if (!r.cls && !r.gkey && !r.gpart && !r.unfinished) return MXL_OK;                           // nothing to move
     hipLaunchKernelGGL(rules_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long long*)ids, ld_ids, t_dev, B, V, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
+}
+
+extern "C" int mxl_guided_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                        void* stream) {
+    return mxl_ranged_rules_advance(ids, ld_ids, t_dev, B, V, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_OFF, stream);
 }
 
 extern "C" int mxl_keyed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, void* stream) {
@@ -1211,6 +1333,19 @@ extern "C" int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B,
 #undef GUIDE_PARAMS
 #undef GUIDE_ARGS
 #undef GUIDE_OFF
+#undef REG_PARAMS
+#undef REG_ARGS
+#undef REG_OFF
+
+extern "C" int mxl_register_scan(const void* ids, int ld_ids, int Tp, int from, int B, int V, const void* reg, const void* grange, int gap,
+                                 int* gpart, int* gfloor, int* first_bad, void* stream) {
+    MXL_CHECK_ARG(ids && B > 0 && V > 0 && Tp >= 0 && ld_ids >= Tp && from >= 0 && reg && grange && gpart && gfloor && first_bad);
+    MXL_CHECK_ARG(gap >= -1 && gap <= 127);
+    hipLaunchKernelGGL(register_scan_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, (const long long*)ids, ld_ids, Tp, from, B, V,
+                       (const unsigned char*)reg, (const int*)grange, gap, gpart, gfloor, first_bad);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
 
 extern "C" int mxl_key_scan(const void* ids, int ld_ids, int Tp, int from, int B, int V, const void* keys, const void* pcs,
                             const void* inkey, int* gkey, int* first_bad, void* stream) {

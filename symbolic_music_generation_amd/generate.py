@@ -56,15 +56,18 @@ def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch
                    grammar=None, gstate: Optional[torch.Tensor] = None, gbar: Optional[torch.Tensor] = None,
                    grem: Optional[torch.Tensor] = None, gleft: Optional[torch.Tensor] = None, in_key=None,
                    gkey: Optional[torch.Tensor] = None, melody=None, guide: Optional[torch.Tensor] = None,
-                   glen: Optional[torch.Tensor] = None, gpos: Optional[torch.Tensor] = None, gforce: Optional[torch.Tensor] = None):
+                   glen: Optional[torch.Tensor] = None, gpos: Optional[torch.Tensor] = None, gforce: Optional[torch.Tensor] = None,
+                   register=None, grange: Optional[torch.Tensor] = None, gpart: Optional[torch.Tensor] = None,
+                   gfloor: Optional[torch.Tensor] = None, gap: int = -1):
     """The sampler tail as separate launches (what mxl_sample_step does in one): next token of every row from the first V columns
     of `scores` -> ids[:, t + 1], position and RNG counters advanced.  stop = (eos, pad, min_length) with unfinished / alive and
     grammar with gstate are optional, and a grammar with a bar budget takes gbar / grem as well; gleft (the bars every row may
     still open) turns the grammar's bar count on, in_key (a grammar.KeyRule) with gkey the key rule, melody (a grammar.MelodyGuide)
-    with guide / glen / gpos / gforce the guide rule (ops.rules_in_force).  The mask writes into `scores` in place.  Four launches, two
+    with guide / glen / gpos / gforce the guide rule, register (a grammar.RegisterRule) with grange / gpart / gfloor and gap the register
+    rule (ops.rules_in_force).  The mask writes into `scores` in place.  Four launches, two
     where no rule is in force."""
     rules = ops.rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos,
-                               gforce)
+                               gforce, register, grange, gpart, gfloor, gap)
     sc = scores[:, :V] if scores.shape[1] != V else scores
     # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the mask: -inf
     # stays -inf under it, so the result is the same
@@ -189,6 +192,77 @@ def key_config(in_key, key, batch: int, vocab_size: int, repeat: int = 1) -> Opt
     return torch.tensor(ks, dtype=torch.int32).repeat_interleave(int(repeat), 0).contiguous()
 
 
+class RegisterPlan:
+    """The register rule of one generation as the decoders take it (register_config): `rule` (a grammar.RegisterRule), `bounds`
+    (B,) int32 on the CPU, every row's lo_melody, hi_melody, lo_bass, hi_bass packed as the rule's `range` word, and `gap` (-1 = the
+    bass is not tied to the melody)"""
+
+    def __init__(self, rule, bounds: torch.Tensor, gap: int):
+        self.rule, self.bounds, self.gap = rule, bounds, int(gap)
+
+    @property
+    def B(self) -> int:
+        return self.bounds.numel()
+
+    def rows(self, lo: int, hi: int) -> 'RegisterPlan':
+        return RegisterPlan(self.rule, self.bounds[lo:hi].contiguous(), self.gap)
+
+
+def _ranges_per_row(r, batch: int, what: str) -> list:
+    """`melody_range` / `bass_range` as generate takes them -> one (lo, hi) per prompt: None = unconstrained, one pair of MIDI
+    numbers for every prompt, or a sequence of `batch` pairs with None for an unconstrained row"""
+    def pair(x):
+        if x is None:
+            return (0, 127)
+        x = x.tolist() if isinstance(x, torch.Tensor) else x
+        if isinstance(x, (str, bytes)) or not hasattr(x, '__len__') or len(x) != 2 or any(
+                isinstance(v, (bool, float, str)) or not hasattr(v, '__index__') for v in x):
+            raise ValueError(f'{what} is a pair (lo, hi) of MIDI numbers, None, or one of those per prompt')
+        lo, hi = int(x[0]), int(x[1])
+        if not (0 <= lo <= 127 and 0 <= hi <= 127):
+            raise ValueError(f'{what}: ({lo}, {hi}) lies outside the MIDI numbers 0..127')
+        if lo > hi:
+            raise ValueError(f'{what}: lo {lo} is above hi {hi}')
+        return (lo, hi)
+    if isinstance(r, torch.Tensor):
+        r = r.detach().cpu().tolist()
+    if r is None or (isinstance(r, (list, tuple)) and len(r) == 2 and all(hasattr(v, '__index__') and not isinstance(v, bool)
+                                                                            for v in r)):
+        return [pair(r)] * batch
+    if not isinstance(r, (list, tuple)):
+        raise ValueError(f'{what} is a pair (lo, hi) of MIDI numbers, None, or one of those per prompt')
+    if len(r) != batch:
+        raise ValueError(f'{what} holds {len(r)} entries for {batch} prompts: give one pair or one per prompt')
+    return [pair(x) for x in r]
+
+
+def register_config(register, melody_range, bass_range, bass_below, batch: int, vocab_size: int, repeat: int = 1) -> Optional[RegisterPlan]:
+    """`register` / `melody_range` / `bass_range` / `bass_below` of a generation as the decoders take them: None (no rule), or a
+    RegisterPlan over batch * repeat rows (`repeat` = num_return_sequences: every prompt's bounds repeated, as the prompts are).
+    melody_range / bass_range: one inclusive pair (lo, hi) of MIDI numbers or one per prompt, None = unconstrained.  bass_below: None
+    (the bass is not tied to the melody) or g >= 0: the bass stays at least g semitones under the lowest melody note of its bar.  A
+    RegisterPlan passes through.  Raises MusicXLError for a rule over another vocabulary and ValueError for lo > hi, a value outside
+    0..127, a wrong count, or a range or bass_below without the rule."""
+    from .grammar import pack_bounds
+    if isinstance(register, RegisterPlan):
+        if register.B != batch * int(repeat):
+            raise ValueError(f'the register plan holds {register.B} rows, the batch {batch * int(repeat)}')
+        return register
+    if register is None:
+        for v, name in ((melody_range, 'melody_range'), (bass_range, 'bass_range'), (bass_below, 'bass_below')):
+            if v is not None:
+                raise ValueError(f'{name}= needs register=, the register rule (tokenizer.register_rule())')
+        return None
+    if register.vocab_size != int(vocab_size):
+        raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the model has vocab_size {int(vocab_size)}')
+    if bass_below is not None and (isinstance(bass_below, (bool, float)) or not hasattr(bass_below, '__index__')
+                                   or not 0 <= int(bass_below) <= 127):
+        raise ValueError(f'bass_below is None or a number of semitones in 0..127, got {bass_below!r}')
+    mel, bass = _ranges_per_row(melody_range, batch, 'melody_range'), _ranges_per_row(bass_range, batch, 'bass_range')
+    bounds = torch.tensor([pack_bounds(m + b) for m, b in zip(mel, bass)], dtype=torch.int32)
+    return RegisterPlan(register, bounds.repeat_interleave(int(repeat), 0).contiguous(), -1 if bass_below is None else int(bass_below))
+
+
 SearchPlan = namedtuple('SearchPlan', 'strategy device rules eos pad')
 
 
@@ -200,10 +274,10 @@ def rules_refusal(what: str, searches: str = 'beam, group-beam or contrastive se
 def plan_search(caps: dict, *, num_beams=1, num_beam_groups=1, do_sample=False, penalty_alpha=None, top_k=None, diversity_penalty=None,
                 eos_token_id=None, pad_token_id=None, config_eos=None, config_pad=None, padded=False, grammar=None, n_bars=None,
                 in_key=None, key=None, melody=None, device_scorer=False, repetition_penalty=None, renormalize_logits=None,
-                vocab_size=None) -> SearchPlan:
+                vocab_size=None, register=None) -> SearchPlan:
     """Which search a `generate` call runs -- a plain value: `strategy` = 'sample' (greedy decoding / sampling), 'beam', 'beam_sample',
     'group_beam' or 'contrastive' (chosen as HF 4.25.1 `generate` does); `device`: with its scorer on the device; `rules`: it takes
-    grammar / n_bars / in_key / key; `eos`, `pad`: what the search arms stop at and fill with (the arguments, else the config's) --
+    grammar / n_bars / in_key / key / register; `eos`, `pad`: what the search arms stop at and fill with (the arguments, else the config's) --
     or MusicXLError for the rules and the padded prompts that search does not take.  caps: the most beams of 'beam' and 'group_beam'
     search and the most candidates of 'contrastive' search the model runs on the device; an absent key = host only.  The only reader
     of the environment switches.  A strategy takes the rules if it is greedy decoding / sampling, or runs on the device with an
@@ -230,7 +304,7 @@ def plan_search(caps: dict, *, num_beams=1, num_beam_groups=1, do_sample=False, 
         # this path has not been measured against the host scorer yet (profiles/group_beam_step.txt), so it is taken when a rule
         # asks for it, or with MXL_GROUP_BEAM_DEVICE=1; a call without a rule keeps the host scorer
         device = device and (os.environ.get('MXL_GROUP_BEAM_DEVICE') == '1' or (
-            explicit_eos and (grammar is not None or in_key is not None or key is not None)))
+            explicit_eos and (grammar is not None or in_key is not None or key is not None or register is not None)))
     elif nb > 1:
         strategy = 'beam_sample' if do_sample else 'beam'
         device = not do_sample and nb <= caps.get('beam', 0) and not host_scorer
@@ -271,6 +345,8 @@ def plan_search(caps: dict, *, num_beams=1, num_beam_groups=1, do_sample=False, 
         raise rules_refusal('n_bars= is')
     if (in_key is not None or key is not None) and not rules:
         raise rules_refusal('in_key= is')
+    if register is not None and not rules:
+        raise rules_refusal('register= is')
     return SearchPlan(strategy, device, rules, config_eos if eos_token_id is None else eos_token_id,
                       config_pad if pad_token_id is None else pad_token_id)
 
@@ -440,12 +516,13 @@ class RowRules:
     int32 buffer holds the words the sampler launches move -- unfinished (1 = live), gstate (automaton state), gbar / grem (bar
     length and free slots), gleft (bars the row may still open, < 0 = no limit), gkey (the row's key under `in_key`, a
     grammar.KeyRule; < 0 = none), gpos / gforce (the next index into the row's guide and whether the row is being fed from it, under
-    `melody`, a grammar.MelodyGuide), each (B,) -- then gbad (2, B), the first prompt
+    `melody`, a grammar.MelodyGuide), grange / gpart / gfloor (the row's bounds, its open part and the lowest melody pitch of its open bar,
+    under `register`, a grammar.RegisterRule, with the generation's `gap`), each (B,) -- then gbad (2, B), the first prompt
     column that breaks the grammar / the budget, and alive (1,), the live-row count.  The guide group also keeps two tables of its
     own here, `guide` (B, ld) int32 and `glen` (B,) int32, refilled by every `start` and regrown only for a longer guide, so that a
     captured step finds the next generation's guides where it found the last one's.  A further rule is a row here, a line in `start`
     and a key in `kwargs` / `graph_key`."""
-    WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey', 'gpos', 'gforce')
+    WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey', 'gpos', 'gforce', 'grange', 'gpart', 'gfloor')
     STATE = WORDS + ('alive',)
 
     def __init__(self, batch: int, dev):
@@ -458,21 +535,39 @@ class RowRules:
         self.unfinished.fill_(1)
         self.gleft.fill_(-1)
         self.gkey.fill_(-1)
-        self.stop = self.grammar = self.n_bars = self.in_key = self.melody = self.plan = None
-        self.bars = False
+        self.stop = self.grammar = self.n_bars = self.in_key = self.melody = self.plan = self.register = None
+        self.bars, self.gap = False, -1
+        self._reset_register()
         self.guide = torch.zeros(batch, 64, device=dev, dtype=torch.int32)
         self.glen = torch.zeros(batch, device=dev, dtype=torch.int32)
 
+    def _reset_register(self):
+        from .grammar import ANY_RANGE, NO_FLOOR, pack_bounds
+        self.grange.fill_(pack_bounds(ANY_RANGE))
+        self.gpart.zero_()
+        self.gfloor.fill_(NO_FLOOR)
+
     def start(self, ids: torch.Tensor, Tp: int, vocab_size: int, stop: Optional[tuple], grammar, n_bars: Optional[torch.Tensor],
-              in_key=None, keys: Optional[torch.Tensor] = None, melody: Optional[MelodyPlan] = None):
+              in_key=None, keys: Optional[torch.Tensor] = None, melody: Optional[MelodyPlan] = None,
+              register: Optional[RegisterPlan] = None):
         """the rules of a new generation over the prompts in columns 0..Tp-1 of ids (ids < 0: left pads, skipped): every row live,
         its grammar state and, under a bar budget, its bar length and free slots after its prompt computed on the device, gleft =
         n_bars ((B,) int32 from bar_count_config, or None: no bar count).  in_key (a grammar.KeyRule, or None: no key rule): gkey =
         keys ((B,) int32 from key_config), or, without them, the last key token of every row's prompt, found on the device (-1 in a
         row without one); the prompt's pitches are not judged.  melody (a MelodyPlan from melody_config, or None: no guide): the
         rows' guides and their lengths go to the device tables, every row starts free at guide index 0 -- a bar open at the end of
-        the prompt is finished freely, the guide engages at the next bar -- and n_bars must be the plan's."""
+        the prompt is finished freely, the guide engages at the next bar -- and n_bars must be the plan's.  register (a RegisterPlan
+        from register_config, or None: no register rule): grange = the plan's bounds, gpart and gfloor = the open part and the floor
+        every row's prompt leaves it in, found on the device; the prompt's pitches are not judged."""
         check_grammar_args(grammar, vocab_size, stop)
+        if register is not None and (register.rule.vocab_size != int(vocab_size) or register.B != self.B):
+            raise MusicXLError(f'the register rule must span the model\'s {int(vocab_size)} tokens and hold one entry per row '
+                               '(register_config)')
+        self.register, self.gap = (None, -1) if register is None else (register.rule, register.gap)
+        self._reset_register()
+        if register is not None:
+            self.grange.copy_(register.bounds)
+            ops.register_scan(ids, Tp, register.rule, self.grange, self.gpart, self.gfloor, torch.empty_like(self.gpart), self.gap)
         if melody is not None and (grammar is None or melody.rule is not getattr(grammar, 'guide', None) or melody.B != self.B
                                    or n_bars is None or n_bars.tolist() != melody.n_bars.tolist()):
             raise MusicXLError('melody needs the grammar its guide rule belongs to, one guide entry per row and n_bars = the bars '
@@ -533,12 +628,14 @@ class RowRules:
         """the rules keywords of ops.sample_step and sample_unfused"""
         return dict(stop=self.stop, unfinished=self.unfinished, alive=self.alive, grammar=self.grammar, gstate=self.gstate,
                     gbar=self.gbar, grem=self.grem, gleft=self.gleft if self.bars else None, in_key=self.in_key, gkey=self.gkey,
-                    melody=self.melody, guide=self.guide, glen=self.glen, gpos=self.gpos, gforce=self.gforce)
+                    melody=self.melody, guide=self.guide, glen=self.glen, gpos=self.gpos, gforce=self.gforce,
+                    register=self.register, grange=self.grange, gpart=self.gpart, gfloor=self.gfloor, gap=self.gap)
 
     def graph_key(self, dev) -> tuple:
         """what a captured sampler launch holds of the rules: which of them are on, the identity of the grammar's and the budget's
         device tables and their class masks, the presence of the key rule and the identity of its tables, the presence of the guide
-        rule with its class masks and the identity of its guide buffer.  The per-row words, the keys and the guide positions among
+        rule with its class masks and the identity of its guide buffer, the presence of the register rule with the identity of its
+        table and the gap.  The per-row words, the keys and the guide positions among
         them, and the guide tokens themselves are step state and not part of it."""
         g = self.grammar
         return (self.stop,
@@ -548,7 +645,8 @@ class RowRules:
                 (g.bar_count.count, g.bar_count.end) if self.bars else None,
                 None if self.in_key is None else tuple(t.data_ptr() for t in self.in_key.to(dev)),
                 None if self.melody is None else (self.melody.enter, self.melody.leave, self.guide.data_ptr(), self.guide.stride(0),
-                                                  self.glen.data_ptr()))
+                                                  self.glen.data_ptr()),
+                None if self.register is None else (self.register.to(dev).data_ptr(), self.gap))
 
     def snapshot(self) -> torch.Tensor:
         return self.buf.clone()
@@ -658,6 +756,37 @@ def check_in_key(ids: torch.Tensor, rule, prompt_len: Optional[int] = None, atte
     return torch.where(bad >= 0, bad + off, bad)
 
 
+def check_register(ids: torch.Tensor, rule, melody_range=None, bass_range=None, bass_below=None, prompt_len: Optional[int] = None,
+                   attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B,) int64 on the CPU, as check_in_key: for every row of ids (B, T) the first generated column (>= prompt_len) that holds a
+    pitch outside the bounds of its part under `rule` (a grammar.RegisterRule, `tokenizer.register_rule()`), -1 = none -- what
+    `generate(register=rule, ...)` keeps at -1.  melody_range / bass_range / bass_below: as generate's (one pair or one per row).  The
+    prompt only moves the row's open part and floor, its pitches are not judged.  prompt_len: the width of the prompt; default the
+    width of attention_mask, else 0 = every column is judged.  attention_mask (B, Tp): left-pad columns (0) are skipped.  Rows on the
+    GPU are walked there (mxl_register_scan), host tensors by RegisterRule.walk."""
+    from .grammar import NO_FLOOR
+    ids = torch.as_tensor(ids)
+    if ids.dim() == 1:
+        ids = ids.view(1, -1)
+    x = ids.to(torch.int64).clone()
+    if attention_mask is not None:
+        m = torch.as_tensor(attention_mask).to(x.device)
+        x[:, :m.shape[1]].masked_fill_(m == 0, -1)
+    if prompt_len is None:
+        prompt_len = 0 if attention_mask is None else int(torch.as_tensor(attention_mask).shape[1])
+    plan = register_config(rule, melody_range, bass_range, bass_below, x.shape[0], rule.vocab_size)
+    if not x.is_cuda:
+        unpack = lambda w: (w & 0xFF, (w >> 8) & 0xFF, (w >> 16) & 0xFF, (w >> 24) & 0xFF)
+        return torch.tensor([rule.walk(r, unpack(int(w)), plan.gap, check_from=int(prompt_len))[2]
+                             for r, w in zip(x, plan.bounds.tolist())], dtype=torch.int64)
+    x = x.contiguous()
+    grange = plan.bounds.to(x.device)
+    gpart, gfloor = torch.zeros_like(grange), torch.full_like(grange, NO_FLOOR)
+    first = torch.empty_like(grange)
+    ops.register_scan(x, x.shape[1], rule, grange, gpart, gfloor, first, plan.gap, check_from=int(prompt_len))
+    return first.cpu().to(torch.int64)
+
+
 def check_melody(ids: torch.Tensor, grammar, melody, prompt_len: Optional[int] = None,
                  attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(B,) int64 on the CPU, as check_grammar: for every row of ids (B, T) the first generated column (>= prompt_len) that departs
@@ -752,18 +881,18 @@ def run_until_finished(decoders, n: int, chunk: int = STOP_CHUNK) -> list:
 
 
 def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool, n_pad, stop, stop_chunk,
-                 grammar, n_bars=None, in_key=None, keys=None, melody=None) -> torch.Tensor:
+                 grammar, n_bars=None, in_key=None, keys=None, melody=None, register=None) -> torch.Tensor:
     """The body of `generate` for one decoder (lanes = [dec], streams = [None]) or for an XLDecoderLanes with its lanes and their
     streams: `dec.begin`, then every remaining step through `dec.replay_once` -- or, with stop = (eos, pad, min_length), each lane
     on its own until its rows have finished (run_until_finished) -- then the lanes' rows in order, cut to the width of the longest
     lane and right-filled with pad where a lane stopped earlier.  Sets `steps_run` on every lane and on dec (the most of any
     lane).  The prompt columns of left-padded prompts (n_pad) come back as given.  n_bars: None or one int32 per row
     (bar_count_config); each lane takes its rows' entries.  in_key / keys: the key rule and None or one int32 per row (key_config),
-    handed on the same way, as is melody (a MelodyPlan or None)."""
+    handed on the same way, as are melody (a MelodyPlan or None) and register (a RegisterPlan or None)."""
     Tp = prompt.shape[1]
     if max_length - Tp <= 0:
         return prompt[:, :max_length]
-    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar, n_bars, in_key, keys, melody)
+    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar, n_bars, in_key, keys, melody, register)
     if stop is None:
         for _ in range(n):
             dec.replay_once()
@@ -902,8 +1031,8 @@ class XLDecoder:
         # the rules of the current generation (eos, grammar, bar budget, bar count) and their per-row words, which the sampler
         # launch reads and moves; the words are readable here under their names
         self.rules = RowRules(batch, dev)
-        (self.unfinished, self.gstate, self.gbar, self.grem, self.gleft, self.gkey, self.gpos, self.gforce,
-         self.alive) = (getattr(self.rules, k) for k in RowRules.STATE)
+        for k in RowRules.STATE:
+            setattr(self, k, getattr(self.rules, k))
 
     def _tables(self):
         if self.rd is None:
@@ -923,7 +1052,7 @@ class XLDecoder:
     # ---------------------------------------------------------------- prompt
     def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None,
                 grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None,
-                melody: Optional[MelodyPlan] = None):
+                melody: Optional[MelodyPlan] = None, register: Optional[RegisterPlan] = None):
         """Whole prompt through the training-shape kernels with zero mems (upstream first step), rings filled from the
         per-layer qkv buffers, first new token sampled from the last position.
         n_pad: (B,) int32 device tensor, left-padded prompts: the first n_pad[b] columns of row b are pads.  Their K / V are zero
@@ -938,7 +1067,9 @@ class XLDecoder:
         in_key: a grammar.KeyRule or None; keys: None (every row starts in the key of its prompt, found on the device, pads
         skipped) or (B,) int32 from key_config; the start value of `gkey`, which a generated key token moves.
         melody: None or a MelodyPlan from melody_config (with n_bars = its bar counts): the rows' guides go to the device, and a
-        guide that does not fit its row's bar length raises with the prompt checks."""
+        guide that does not fit its row's bar length raises with the prompt checks.
+        register: None or a RegisterPlan from register_config: the rows' bounds go to the device, and the open part and the floor
+        every prompt leaves its row in are found there (one more scan launch)."""
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
@@ -953,7 +1084,7 @@ class XLDecoder:
             pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
             self.ids[:, :Tp].masked_fill_(pad, -1)
             x = x.masked_fill(pad, 0)
-        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars, in_key, keys, melody)
+        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars, in_key, keys, melody, register)
         sink_kc, sink_vc = self.kc, self.vc
 
         def kv_sink(l, qkv):
@@ -1085,7 +1216,7 @@ class XLDecoder:
                    early_stopping: bool, use_graph: bool = True, grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None,
                    keys: Optional[torch.Tensor] = None, ng: int = 1, diversity_penalty: float = 0.0, sample: bool = False,
                    top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: float = 1.0,
-                   typical_p: Optional[float] = None) -> int:
+                   typical_p: Optional[float] = None, register: Optional[RegisterPlan] = None) -> int:
         """prompt pass (one row per beam, the rules started as `prefill` starts them, with the stop group (eos, pad, 0) always on:
         its `unfinished` word is how mxl_beam_step retires dead rows and done items) + the scorer's state + (use_graph) capture of
         one beam step (`_capture`; the hypothesis store, the running scores and the log-probabilities are this step's own state);
@@ -1104,7 +1235,7 @@ class XLDecoder:
                                '>= 0')
         if sample and (ng != 1 or self.eng.cfg.vocab_size > 2048):
             raise MusicXLError('beam-sample on the device takes one group and a vocabulary of at most 2048 tokens')
-        self.prefill(prompt, None, None, (int(eos), int(pad), 0), grammar, n_bars, in_key, keys)
+        self.prefill(prompt, None, None, (int(eos), int(pad), 0), grammar, n_bars, in_key, keys, None, register)
         if self.beam is None or self.beam.nb != nb:
             self.beam = BeamStore(self.B // nb, nb, self.ids.shape[1], self.eng.dev)
             self.ring_table = ops.beam_table(self.kc + self.vc)
@@ -1150,13 +1281,14 @@ class XLDecoder:
         rules = self.beam_select()
         ops.beam_reorder(self.kc + self.vc, self._beam_args[0], self.beam.beam_idx, self.beam.moved, table=self.ring_table)
         ops.decode_advance(self.t_dev, self.rng)
-        if rules['grammar'] is not None or rules['in_key'] is not None:
+        if rules['grammar'] is not None or rules['in_key'] is not None or rules.get('register') is not None:
             ops.rules_advance(self.ids, self.t_dev, **rules)
         self._forward_token()
 
     # ---------------------------------------------------------------- contrastive search on the device (contrastive_search_device)
     def contrastive_begin(self, prompt: torch.Tensor, max_length: int, K: int, alpha: float, eos: Optional[int], pad: int,
-                          use_graph: bool = True, grammar=None, in_key=None, keys: Optional[torch.Tensor] = None) -> int:
+                          use_graph: bool = True, grammar=None, in_key=None, keys: Optional[torch.Tensor] = None,
+                          register: Optional[RegisterPlan] = None) -> int:
         """prompt pass (one row per candidate: the K rows of a sequence hold the same prompt; the rules started as `prefill` starts
         them, with the stop group (eos, pad, 0) always on -- eos None: -1, never emitted) + the store + (use_graph) capture of one
         contrastive step (`_capture`) + the first token, chosen by one step run here; returns the number of `replay_once()` calls that
@@ -1168,7 +1300,7 @@ class XLDecoder:
             raise MusicXLError(f'contrastive search on the device takes 2..{CONTRASTIVE_MAX} candidates and one decoder row per '
                                'candidate')
         c, Tp = self.eng.cfg, prompt.shape[1]
-        self.prefill(prompt, None, None, (-1 if eos is None else int(eos), int(pad), 0), grammar, None, in_key, keys)
+        self.prefill(prompt, None, None, (-1 if eos is None else int(eos), int(pad), 0), grammar, None, in_key, keys, None, register)
         if self.cs is None or self.cs.K != K:
             self.cs = ContrastiveStore(self.B // K, K, self.Tmax, c.d_model, self.eng.dev)
             self.ring_table = ops.beam_table(self.kc + self.vc)
@@ -1191,7 +1323,7 @@ class XLDecoder:
         c, cs = self.eng.cfg, self.cs
         K, alpha, eos, pad = self._cs_args
         rules = ops.rules_in_force(**self.rules.kwargs())
-        ruled = rules['grammar'] is not None or rules['in_key'] is not None
+        ruled = rules['grammar'] is not None or rules['in_key'] is not None or rules.get('register') is not None
         if ruled:
             ops.rules_mask(self.logp, c.vocab_size, self.t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
         ops.contrastive_topk(self.logp, c.vocab_size, cs.sel, self.ids, self.t_dev, cs.probs, cs.dead, self.unfinished, pad)
@@ -1213,7 +1345,7 @@ class XLDecoder:
     def begin(self, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool = True,
               n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None, grammar=None,
               n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None,
-              melody: Optional[MelodyPlan] = None) -> int:
+              melody: Optional[MelodyPlan] = None, register: Optional[RegisterPlan] = None) -> int:
         """prompt pass + first sampled token + (use_graph) capture of one decode step; returns the number of `replay_once()`
         calls that complete the generation to max_length.  n_pad: left-padded prompts (prefill); the decode step is the same,
         every row's last prompt token sits at column Tp - 1.  stop: (eos, pad, min_length) (stop_config) or None.  grammar: a
@@ -1224,11 +1356,13 @@ class XLDecoder:
         launch that reads the rule's tables, so its presence and their identity are in the key; the keys are step state (`gkey`).
         melody (prefill): the step captured under the guide rule is another launch that reads the decoder's guide buffer, so the
         rule's presence, its masks and the buffer's identity are in the key; the guide tokens and `gpos` / `gforce` are step state,
-        and a later generation with another guide that fits the buffer replays the same graph"""
+        and a later generation with another guide that fits the buffer replays the same graph.  register (prefill): the step captured
+        under the register rule is another launch that reads the rule's table and carries the gap, so its presence, the table's
+        identity and the gap are in the key; the bounds, the parts and the floors are step state"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         self._use_graph, self._step, self.finished_by = use_graph, ('step', sampling), (self.alive, 0)
-        self.prefill(prompt, sampling, n_pad, stop, grammar, n_bars, in_key, keys, melody)
+        self.prefill(prompt, sampling, n_pad, stop, grammar, n_bars, in_key, keys, melody, register)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
             # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
@@ -1277,7 +1411,8 @@ class XLDecoder:
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
                  typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
-                 stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None) -> torch.Tensor:
+                 stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None, register=None,
+                 melody_range=None, bass_range=None, bass_below=None) -> torch.Tensor:
         """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
         [OMIT]) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (prefill); the
         prompt columns, pads included, come back as given.
@@ -1297,13 +1432,17 @@ class XLDecoder:
         or ordinal, or one per row with None / -1 = unconstrained, overrides the prompts.  A generated key token sets the row's key.
         melody (one guide or one per row, None = unguided; needs grammar and eos_token_id, takes no n_bars or min_length): each
         guide is the `<bar> <melody> ... <bass>` spans of its bars (`tokenizer.melody_guide`); the row is fed them bar by bar inside
-        the sampler launch and chooses the bass under each, then ends (melody_config, MyTransfoXLLMHeadModel.generate)."""
+        the sampler launch and chooses the bass under each, then ends (melody_config, MyTransfoXLLMHeadModel.generate).
+        register (a grammar.RegisterRule, e.g. `tokenizer.register_rule()`; needs no grammar) with melody_range / bass_range (one
+        inclusive pair of MIDI numbers or one per row, None = unconstrained) and bass_below (None or g >= 0 semitones): the pitches
+        of every part stay inside its bounds, and the bass at least g under the lowest melody note of its bar (register_config)."""
         stop = stop_config(eos_token_id, pad_token_id, min_length)
         plan = melody_config(melody, self.B, grammar, stop, n_bars)
         return decode_lanes(self, [self], [None], prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
                             stop, stop_chunk, grammar, bar_count_config(n_bars if plan is None else plan.n_bars, self.B, grammar, stop),
-                            in_key, key_config(in_key, key, self.B, self.eng.cfg.vocab_size), plan)
+                            in_key, key_config(in_key, key, self.B, self.eng.cfg.vocab_size), plan,
+                            register_config(register, melody_range, bass_range, bass_below, self.B, self.eng.cfg.vocab_size))
 
 
 class XLDecoderLanes:
@@ -1327,12 +1466,13 @@ class XLDecoderLanes:
             d.invalidate_tables()
 
     def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None, grammar=None, n_bars=None, in_key=None,
-              keys=None, melody=None) -> int:
+              keys=None, melody=None, register=None) -> int:
         steps = [d.begin(prompt[self.offs[i]:self.offs[i + 1]], max_length, sampling, use_graph,
                          None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]], stop, grammar,
                          None if n_bars is None else n_bars[self.offs[i]:self.offs[i + 1]], in_key,
                          None if keys is None else keys[self.offs[i]:self.offs[i + 1]],
-                         None if melody is None else melody.rows(self.offs[i], self.offs[i + 1]))
+                         None if melody is None else melody.rows(self.offs[i], self.offs[i + 1]),
+                         None if register is None else register.rows(self.offs[i], self.offs[i + 1]))
                  for i, d in enumerate(self.lanes)]
         for s in self.streams:                       # the lanes start from the prompt passes and captures issued above
             s.wait_stream(torch.cuda.current_stream())
@@ -1349,7 +1489,8 @@ class XLDecoderLanes:
 
     def generate(self, prompt, max_length, do_sample=False, top_k=None, top_p=None, temperature=1.0, repetition_penalty=None,
                  typical_p=None, use_graph=True, n_pad=None, eos_token_id=None, pad_token_id=None, min_length=None,
-                 stop_chunk=STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None) -> torch.Tensor:
+                 stop_chunk=STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None, register=None,
+                 melody_range=None, bass_range=None, bass_below=None) -> torch.Tensor:
         """XLDecoder.generate over the lanes (each lane keeps the grammar state, the bar counts, the keys and the guides of its own rows).  With eos_token_id every lane stops
         on its own; the output is the lanes' rows cut to the common width and right-filled with pad where a lane stopped earlier."""
         stop = stop_config(eos_token_id, pad_token_id, min_length)
@@ -1357,7 +1498,8 @@ class XLDecoderLanes:
         return decode_lanes(self, self.lanes, self.streams, prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
                             stop, stop_chunk, grammar, bar_count_config(n_bars if plan is None else plan.n_bars, self.B, grammar, stop),
-                            in_key, key_config(in_key, key, self.B, self.lanes[0].eng.cfg.vocab_size), plan)
+                            in_key, key_config(in_key, key, self.B, self.lanes[0].eng.cfg.vocab_size), plan,
+                            register_config(register, melody_range, bass_range, bass_below, self.B, self.lanes[0].eng.cfg.vocab_size))
 
 
 class _BeamHyps:
@@ -1529,17 +1671,17 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
                        length_penalty: float = 1.0, num_return_sequences: int = 1, eos_token_id: int = 0,
                        pad_token_id: Optional[int] = None, use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None,
                        n_bars=None, in_key=None, key=None, return_scores: bool = False, num_beam_groups: int = 1,
-                       diversity_penalty: float = 0.0):
+                       diversity_penalty: float = 0.0, register=None, melody_range=None, bass_range=None, bass_below=None):
     """`beam_search` (do_sample=False) with the scorer on the device: per step the rules mask, mxl_beam_step (select, walk, store,
     reorder ids and the rule words), mxl_beam_reorder over the K/V rings, the position advance, the rules advance and the model --
     no host read, captured once under use_graph (XLDecoder.beam_begin / beam_step).  The steps are replayed in chunks of
     `stop_chunk`; the number of done items is read back one chunk late (run_until_finished) and the loop
     ends when every item is done or at max_length.  Then the store and the running scores are read once and `_beam_finalize`
     builds the output, as beam_search does.  dec: an XLDecoder with prompt rows x num_beams rows, num_beams <= 16.
-    grammar / n_bars / in_key / key: the rules of `XLDecoder.generate`, one value per prompt where they are per row (each prompt's
-    is shared by its beams); a barred token is -inf before the running scores are added, the rules' words follow the beams, and a
-    row that can only continue from a barred token is dead: it emits pad at score -inf and never returns.  An item that ends with
-    fewer than num_return_sequences hypotheses of finite score raises MusicXLError.
+    grammar / n_bars / in_key / key / register with melody_range, bass_range and bass_below: the rules of `XLDecoder.generate`, one
+    value per prompt where they are per row (each prompt's is shared by its beams); a barred token is -inf before the running scores
+    are added, the rules' words follow the beams, and a row that can only continue from a barred token is dead: it emits pad at score
+    -inf and never returns.  An item that ends with fewer than num_return_sequences hypotheses of finite score raises MusicXLError.
     num_beam_groups > 1 with diversity_penalty: the same loop over mxl_group_beam_step (group_beam_search_device)."""
     V = dec.eng.cfg.vocab_size
     nb = int(num_beams)
@@ -1556,7 +1698,8 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     stop = (int(eos_token_id), int(pad), 0)
     return _beam_device(dec, prompt, max_length, nb, keep, early_stopping, length_penalty, eos_token_id, pad, use_graph, stop_chunk,
                         grammar, bar_count_config(n_bars, B0, grammar, stop, nb), in_key, key_config(in_key, key, B0, V, nb),
-                        return_scores, 'beam search', ng=int(num_beam_groups), diversity_penalty=float(diversity_penalty))
+                        return_scores, 'beam search', ng=int(num_beam_groups), diversity_penalty=float(diversity_penalty),
+                        register=register_config(register, melody_range, bass_range, bass_below, B0, V, nb))
 
 
 def _beam_device(dec, items: torch.Tensor, max_length: int, nb: int, keep: int, early_stopping: bool, length_penalty: float, eos: int,
@@ -1593,7 +1736,8 @@ def beam_sample_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
                        top_p: Optional[float] = None, temperature: float = 1.0, typical_p: Optional[float] = None,
                        early_stopping: bool = True, length_penalty: float = 1.0, num_return_sequences: int = 1, eos_token_id: int = 0,
                        pad_token_id: Optional[int] = None, use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None,
-                       in_key=None, key=None, return_scores: bool = False):
+                       in_key=None, key=None, return_scores: bool = False, register=None, melody_range=None, bass_range=None,
+                       bass_below=None):
     """`beam_search(do_sample=True)` (HF 4.25.1 `beam_sample` with renormalize_logits) with the draw and the scorer on the device:
     `beam_search_device`'s loop -- chunked replay of one captured step, the number of done items read a chunk late, the last selection
     without a forward, `_beam_finalize` -- whose step is the rules mask, mxl_beam_sample_draw (the warpers with two tokens kept, the
@@ -1617,7 +1761,8 @@ def beam_sample_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
         raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, beam-sample needs {rows} x {max_length}')
     return _beam_device(dec, prompt.repeat_interleave(nrs, 0), max_length, nb, 1, early_stopping, length_penalty, eos_token_id, pad,
                         use_graph, stop_chunk, grammar, None, in_key, key_config(in_key, key, B0, V, nrs * nb), return_scores,
-                        'beam-sample', sample=True, top_k=top_k, top_p=top_p, temperature=temperature, typical_p=typical_p)
+                        'beam-sample', sample=True, top_k=top_k, top_p=top_p, temperature=temperature, typical_p=typical_p,
+                        register=register_config(register, melody_range, bass_range, bass_below, B0, V, nrs * nb))
 
 
 def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 4, num_beam_groups: int = 2,
@@ -1640,7 +1785,7 @@ def group_beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_bea
                              diversity_penalty: float = 0.0, early_stopping: bool = True, length_penalty: float = 1.0,
                              num_return_sequences: int = 1, eos_token_id: int = 0, pad_token_id: Optional[int] = None,
                              use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None, in_key=None, key=None,
-                             return_scores: bool = False):
+                             return_scores: bool = False, register=None, melody_range=None, bass_range=None, bass_below=None):
     """`group_beam_search` with the scorer on the device: `beam_search_device`'s loop -- chunked replay of one captured step, the
     number of done items read a chunk late, the last selection without a forward, `_beam_finalize` -- over mxl_group_beam_step, which
     walks the groups of every item in order inside one launch.  dec: an XLDecoder with prompt rows x num_beams rows, num_beams <= 16
@@ -1651,7 +1796,7 @@ def group_beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_bea
         raise ValueError('`num_beams` should be divisible by `num_beam_groups` for group beam search.')      # HF's message
     return beam_search_device(dec, prompt, max_length, nb, early_stopping, length_penalty, num_return_sequences, eos_token_id,
                               pad_token_id, use_graph, stop_chunk, grammar, None, in_key, key, return_scores, ng,
-                              float(diversity_penalty or 0.0))
+                              float(diversity_penalty or 0.0), register, melody_range, bass_range, bass_below)
 
 
 def beam_generate(make_decoder, input_ids: torch.Tensor, max_length: int, *, num_beams: int, num_beam_groups: int, do_sample: bool,
@@ -1755,7 +1900,8 @@ def contrastive_search(dec, prompt: torch.Tensor, max_length: int, top_k: int = 
 
 def contrastive_search_device(dec, prompt: torch.Tensor, max_length: int, top_k: int = 4, penalty_alpha: float = 0.6,
                               eos_token_id: Optional[int] = 0, pad_token_id: Optional[int] = None, use_graph: bool = True,
-                              stop_chunk: int = STOP_CHUNK, grammar=None, in_key=None, key=None) -> torch.Tensor:
+                              stop_chunk: int = STOP_CHUNK, grammar=None, in_key=None, key=None, register=None, melody_range=None,
+                              bass_range=None, bass_below=None) -> torch.Tensor:
     """`contrastive_search` with the whole step on the device: per step the rules mask, mxl_contrastive_topk, the position advance,
     the model, mxl_contrastive_step, the rules advance and mxl_ring_slot_broadcast -- no host read, no whole-ring copy, captured once
     under use_graph (XLDecoder.contrastive_begin / contrastive_step).  The steps are replayed in chunks of `stop_chunk`; the number
@@ -1777,7 +1923,8 @@ def contrastive_search_device(dec, prompt: torch.Tensor, max_length: int, top_k:
         return prompt.to(dec.eng.dev).clone()
     pad = eos_token_id if pad_token_id is None else pad_token_id
     n = dec.contrastive_begin(prompt.repeat_interleave(K, 0).to(dec.eng.dev), max_length, K, penalty_alpha, eos_token_id,
-                              0 if pad is None else pad, use_graph, grammar, in_key, key_config(in_key, key, B0, V, K))
+                              0 if pad is None else pad, use_graph, grammar, in_key, key_config(in_key, key, B0, V, K),
+                              register_config(register, melody_range, bass_range, bass_below, B0, V, K))
     # (the count is first read once the first token is chosen: sequences that all start with eos replay nothing)
     issued, = run_until_finished([(dec, None)], n, stop_chunk)
     dec.steps_run = issued

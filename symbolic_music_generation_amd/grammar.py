@@ -61,6 +61,22 @@ each span token by token and writes the bass under it.  Two more integers per ro
 
 A fed row may emit the guide's next token alone, whatever the grammar, the budget, the count and the key say -- `generate` checks the
 guide against the grammar and the budget on the host -- and the bar count, set to the number of bars in the guide, ends the row.
+
+`RegisterRule` (`MusicVocabulary.register_rule()` / `MusicTokenizer.register_rule()`) is the rule behind `generate(..., register=rule)`:
+every part stays in its register, and the bass under the melody.  Like the key rule it stands beside the grammar: it reads neither
+token classes nor the automaton state.  One table
+
+    reg        (V,)   uint8    pitch token -> MIDI number 0..127; REG_MELODY / REG_BASS / REG_BAR = the <melody> / <bass> / <bar> token;
+                               NO_PITCH = any other token (rests and the rare pitch included: they are never barred)
+
+three integers per row -- `range` (the bounds lo_melody, hi_melody, lo_bass, hi_bass, inclusive MIDI numbers, one byte each from the
+lowest, fixed for the generation), `part` (0 = no part is open, 1 = melody, 2 = bass) and `floor` (the lowest melody pitch of the open
+bar, NO_FLOOR = none yet) -- and one number for the generation, `gap` (-1 = the bass is not tied to the melody).  A pitch outside the
+bounds of the open part is barred; in the bass, with gap >= 0 and a floor, the upper bound is min(hi_bass, floor - gap): gap 0 lets the
+bass touch the bar's lowest melody note, gap 1 keeps it strictly below.  The bound is per bar, not aligned in time: it is sufficient to
+keep the parts from crossing, not necessary.  A part token sets `part`, <bar> clears `part` and `floor`, a melody pitch lowers `floor`.
+No dead end: the rest and the rare pitch are never barred and belong to the grammar's class `pitch`, so wherever a pitch may follow a
+token is left even when the bounds leave no pitched one.
 """
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -73,6 +89,9 @@ NO_SIG = 0xFFFF            # `bars` entry of a token that is no time signature
 NO_KEY = 0xFF              # `keys` entry of a token that is no key token
 NO_PITCH = 0xFF            # `pcs` entry of a token that is no pitch
 N_KEYS = 24
+REG_MELODY, REG_BASS, REG_BAR = 0x80, 0x81, 0x82   # `reg` entries of the tokens that move a row's part
+NO_FLOOR = 128             # `floor` of a row whose open bar holds no melody pitch yet
+ANY_RANGE = (0, 127, 0, 127)                       # the bounds of an unconstrained row
 
 
 class TokenGrammar:
@@ -635,6 +654,117 @@ class KeyRule:
 
     def __repr__(self):
         return f'KeyRule(V={self.vocab_size}, key tokens={int((self.keys != NO_KEY).sum())}, pitches={int((self.pcs != NO_PITCH).sum())})'
+
+
+def pack_bounds(bounds) -> int:
+    """(lo_melody, hi_melody, lo_bass, hi_bass) -> the row's `range` word: one byte each from the lowest"""
+    lm, hm, lb, hb = (int(x) for x in bounds)
+    return lm | (hm << 8) | (lb << 16) | (hb << 24)
+
+
+class RegisterRule:
+    def __init__(self, reg):
+        """The register rule (module docstring) from its table: reg (V,) with a MIDI number 0..127, REG_MELODY / REG_BASS / REG_BAR
+        or NO_PITCH per token.  Raises ValueError for any other entry."""
+        reg_a = np.asarray(reg)
+        if reg_a.ndim != 1 or reg_a.size == 0:
+            raise ValueError('reg must be a non-empty (V,) array: one entry per token')
+        if ((reg_a < 0) | ((reg_a > 127) & ~np.isin(reg_a, (REG_MELODY, REG_BASS, REG_BAR, NO_PITCH)))).any():
+            raise ValueError('reg holds an entry that is no MIDI number 0..127, part code or NO_PITCH')
+        self.reg = np.ascontiguousarray(reg_a, dtype=np.uint8)
+        self._dev: Dict[str, object] = {}
+
+    @property
+    def vocab_size(self) -> int:
+        return int(self.reg.shape[0])
+
+    # ---------------------------------------------------------------- the rule
+    @staticmethod
+    def bounds_of(part: int, floor: int, bounds, gap: int) -> Tuple[int, int]:
+        """(lo, hi) a pitch of a row in `part` must lie in; hi < lo = no pitched token is left"""
+        lm, hm, lb, hb = (int(x) for x in bounds)
+        if part == 1:
+            return lm, hm
+        if part == 2:
+            return lb, (min(hb, int(floor) - int(gap)) if gap >= 0 and floor < NO_FLOOR else hb)
+        return 0, 127
+
+    def allows(self, part: int, floor: int, bounds, gap: int, tok: int) -> bool:
+        """may token `tok` follow in a row at (part, floor) under `bounds` and `gap`?  (the other rules come on top)"""
+        p = int(self.reg[int(tok)])
+        lo, hi = self.bounds_of(part, floor, bounds, gap)
+        return p > 127 or lo <= p <= hi
+
+    def allowed(self, part: int, floor: int, bounds, gap: int) -> np.ndarray:
+        """(V,) bool: `allows(part, floor, bounds, gap, v)` for every token v"""
+        lo, hi = self.bounds_of(part, floor, bounds, gap)
+        return (self.reg > 127) | ((self.reg >= lo) & (self.reg <= hi))
+
+    def move(self, part: int, floor: int, tok: int) -> Tuple[int, int]:
+        """(part, floor) after token `tok`"""
+        p = int(self.reg[int(tok)])
+        if p == REG_MELODY:
+            return 1, int(floor)
+        if p == REG_BASS:
+            return 2, int(floor)
+        if p == REG_BAR:
+            return 0, NO_FLOOR
+        if p <= 127 and part == 1:
+            return 1, min(int(floor), p)
+        return int(part), int(floor)
+
+    # ---------------------------------------------------------------- host reference
+    def walk(self, ids, bounds=ANY_RANGE, gap: int = -1, part: int = 0, floor: int = NO_FLOOR, check_from: int = 0) -> Tuple[int, int, int]:
+        """(part, floor, index of the first pitch outside its part's bounds or -1) for a 1-D id sequence that starts at (part,
+        floor); the walk stops there.  Entries before `check_from` only move the words (the prompt's pitches are not judged).  Ids
+        < 0 (left pads) and ids beyond the vocabulary are skipped.  The host reference of mxl_register_scan."""
+        seq = ids.tolist() if hasattr(ids, 'tolist') else list(ids)
+        V, part, floor = self.vocab_size, int(part), int(floor)
+        for i, tok in enumerate(seq):
+            tok = int(tok)
+            if tok < 0 or tok >= V:
+                continue
+            if i >= check_from and not self.allows(part, floor, bounds, gap, tok):
+                return part, floor, i
+            part, floor = self.move(part, floor, tok)
+        return part, floor, -1
+
+    # ---------------------------------------------------------------- device table
+    def to(self, device):
+        """`reg` on `device`, uploaded once per device: uint8 (V,)"""
+        import torch
+        dk = str(torch.device(device))
+        if dk not in self._dev:
+            self._dev[dk] = torch.from_numpy(self.reg.copy()).to(device)
+        return self._dev[dk]
+
+    def __repr__(self):
+        return f'RegisterRule(V={self.vocab_size}, pitches={int((self.reg <= 127).sum())})'
+
+
+def music_register_rule(vocab) -> RegisterRule:
+    """the register rule of a MusicVocabulary of any pitch kind.  A pitch token's entry is its MIDI number, the `i` its name was built
+    from in `MusicVocabulary._pitches`: (octave + 1) * 12 + index - 1, where the `step` kind's B# (index 1, named an octave down) and
+    C- (index 12, named an octave up) have their octave put back; the scale-degree suffix of the `degree` kind is ignored.  The rest
+    and the rare pitch hold NO_PITCH."""
+    reg = np.full(len(vocab), NO_PITCH, dtype=np.uint8)
+    for tok, i in vocab.tok2id.items():
+        m = vocab._re_pitch.match(tok)
+        if m is None:
+            continue
+        idx, otv, name = int(m.group(1)), int(m.group(2)), m.group(3)
+        if vocab.pitch_kind == 'step':
+            if idx == 1 and name == 'B':
+                otv += 1
+            elif idx == 12 and name == 'C':
+                otv -= 1
+        midi = (otv + 1) * 12 + idx - 1
+        if not 0 <= midi <= 127:
+            raise ValueError(f'pitch token {tok!r} names MIDI number {midi}')
+        reg[i] = midi
+    for tok, code in ((vocab.start_of_melody, REG_MELODY), (vocab.start_of_bass, REG_BASS), (vocab.start_of_bar, REG_BAR)):
+        reg[vocab.tok2id[tok]] = code
+    return RegisterRule(reg)
 
 
 def in_key_masks(table) -> np.ndarray:

@@ -134,12 +134,13 @@ def decode_qkv(x, wqkv, qkv, kc, vc, t_dev, rrb, qr_out, dh):
 
 
 def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None,
-                   gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None) -> dict:
+                   gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None,
+                   gfloor=None, gap=-1) -> dict:
     """The rules of a generation as its decoders describe them -> the keywords of rules_mask / rules_advance, where a group is on
     exactly when its state tensor is given.  The decoders say which rules hold with `stop` (the eos rule), `grammar` (the grammar,
-    and its bar budget if it has one), `gleft` (the bar count), `in_key` (the key rule) and `melody` (the guide rule, a
-    grammar.MelodyGuide) and may hand over state tensors of rules that are off: those are dropped here, and a rule that is on without
-    its state raises."""
+    and its bar budget if it has one), `gleft` (the bar count), `in_key` (the key rule), `melody` (the guide rule, a
+    grammar.MelodyGuide) and `register` (the register rule, a grammar.RegisterRule, with the launch's `gap`) and may hand over state
+    tensors of rules that are off: those are dropped here, and a rule that is on without its state raises."""
     budget = grammar is not None and grammar.budget is not None
     if stop is not None and (unfinished is None or alive is None):
         raise MusicXLError('the eos rule needs unfinished and alive')
@@ -153,7 +154,12 @@ def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=
         raise MusicXLError('the key rule needs gkey')
     if melody is not None and (grammar is None or guide is None or glen is None or gpos is None or gforce is None):
         raise MusicXLError('the guide rides on a grammar and needs guide, glen, gpos and gforce')
+    if register is not None and (grange is None or gpart is None or gfloor is None):
+        raise MusicXLError('the register rule needs grange, gpart and gfloor')
     on = melody is not None
+    if register is not None:                # (a call without the rule carries no key of it: the guided entries, as before)
+        return dict(rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos,
+                                   gforce), register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=int(gap))
     return dict(stop=stop, unfinished=unfinished if stop is not None else None, alive=alive if stop is not None else None,
                 grammar=grammar, gstate=gstate if grammar is not None else None, gbar=gbar if budget else None,
                 grem=grem if budget else None, gleft=gleft, in_key=in_key, gkey=gkey if in_key is not None else None,
@@ -187,6 +193,30 @@ def _guide_args(what, device, B, V=None, *, grammar=None, melody=None, guide=Non
             raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
     # (glen[b] <= the row width is the caller's to keep; the kernels clamp to ld_guide as well)
     return [_p(guide), guide.stride(0), _p(glen), melody.enter, melody.leave, _p(gpos), _p(gforce)]
+
+
+REGISTER_KEYS = ('register', 'grange', 'gpart', 'gfloor', 'gap')
+
+
+def _register_args(what, device, B, V=None, *, register=None, grange=None, gpart=None, gfloor=None, gap=-1) -> list:
+    """the register group of the mxl_ranged_* entries (include/musicxl.h, "Rules of a generation"), checked: on exactly when gpart is
+    given, with its table from `register` (a grammar.RegisterRule), which must span the V tokens of the scores, the rows' bounds
+    grange and second word gfloor, and the launch's gap"""
+    if gpart is None:
+        return [None, None, None, None, -1]
+    if register is None:
+        raise MusicXLError(f'{what}: gpart needs register, the register rule that holds its table')
+    if grange is None or gfloor is None:
+        raise MusicXLError(f'{what}: the register group needs grange, gpart and gfloor')
+    if V is not None and register.vocab_size != int(V):
+        raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the scores span {int(V)}')
+    for t, name in ((grange, 'grange'), (gpart, 'gpart'), (gfloor, 'gfloor')):
+        _req(t, torch.int32, f'{what} {name}')
+        if t.numel() != B or not t.is_contiguous():
+            raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
+    if not -1 <= int(gap) <= 127:
+        raise MusicXLError(f'{what}: gap must lie in -1..127, got {gap}')
+    return [_p(register.to(device)), _p(grange), _p(gpart), _p(gfloor), int(gap)]
 
 
 def _key_args(what, device, B, V=None, *, in_key=None, gkey=None) -> list:
@@ -247,8 +277,8 @@ def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=No
 
 def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
                 grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None, melody=None, guide=None,
-                glen=None, gpos=None, gforce=None, do_sample=False, top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0,
-                typical_p=1.0, out_probs=None):
+                glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None, gfloor=None, gap=-1, do_sample=False,
+                top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0, out_probs=None):
     """sampler + embedding row of the sampled token (-> emb_out (B, d) bf16) + counter advance, one launch (V <= 2048).
     scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1.
     The rules of the generation ride on the same launch (rules_in_force): stop = (eos_id, pad_id, min_length) with unfinished (B,)
@@ -256,10 +286,14 @@ def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter
     advanced, with or without the eos rule; a grammar with a bar budget (grammar.budget) needs gbar and grem (B,) int32 as well;
     gleft (B,) int32, the bars every row may still open (< 0 = no limit), turns the grammar's bar count on; in_key (a grammar.KeyRule)
     with gkey (B,) int32, the key of every row (< 0 = none), bars the pitches outside it, with or without a grammar; melody (a
-    grammar.MelodyGuide, `grammar.guide`) with guide (B, ld) int32, glen, gpos and gforce (B,) int32 feeds rows from their guides.
+    grammar.MelodyGuide, `grammar.guide`) with guide (B, ld) int32, glen, gpos and gforce (B,) int32 feeds rows from their guides;
+    register (a grammar.RegisterRule) with grange, gpart and gfloor (B,) int32 and the scalar gap keeps the pitches of every row's open
+    part inside its bounds, with or without a grammar.
     out_probs (B, V) f32, with do_sample: the renormalised distribution the tokens were drawn from (test hook)."""
     B = scores.shape[0]
-    force = rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos, gforce)
+    force = rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos, gforce,
+                           register, grange, gpart, gfloor, gap)
+    ranged = _register_args('sample_step', scores.device, B, V, **{k: force.pop(k) for k in REGISTER_KEYS if k in force})
     keyed = _key_args('sample_step', scores.device, B, V, in_key=force.pop('in_key'), gkey=force.pop('gkey'))
     guided = _guide_args('sample_step', scores.device, B, V, grammar=grammar, **{k: force.pop(k) for k in GUIDE_KEYS})
     rules = _rules_args('sample_step', scores.device, B, V, guided=guided[0] is not None, **force)
@@ -267,21 +301,22 @@ def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter
         _req(out_probs, torch.float32, 'sample_step out_probs')
         if tuple(out_probs.shape) != (B, int(V)) or not out_probs.is_contiguous():
             raise MusicXLError(f'sample_step: out_probs must be contiguous ({B}, {int(V)}) f32')
-    check(lib().mxl_guided_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
+    check(lib().mxl_ranged_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
                                       int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
                                       float(repetition_penalty if repetition_penalty is not None else 1.0),
                                       float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
-                                      float(scale), _p(counter), *rules, *keyed, *guided, _p(out_probs), _stream()),
-          'mxl_guided_sample_step')
+                                      float(scale), _p(counter), *rules, *keyed, *guided, *ranged, _p(out_probs), _stream()),
+          'mxl_ranged_sample_step')
 
 
 def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None,
-               melody=None, guide=None, glen=None, gpos=None, gforce=None):
+               melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None, gfloor=None, gap=-1):
     """before sample: scores[b, v] = -inf in place for every token a rule bars (mxl_rules_mask).  A rule is applied exactly when its
     state is given: gstate (the grammar in state gstate[b]), gbar and grem (its bar budget), gleft (its bar count), each with
     `grammar` for the tables, gkey (the key rule in key gkey[b]) with `in_key` for its tables, and gpos with gforce, guide, glen and
-    `melody` (the guide rule: a row fed from its guide keeps that one token); stop = (eos, pad, min_length) bars eos while the rows are
-    shorter than min_length.  No launch when nothing is given."""
+    `melody` (the guide rule: a row fed from its guide keeps that one token), and gpart with gfloor, grange, gap and `register` (the
+    register rule); stop = (eos, pad, min_length) bars eos while the rows are shorter than min_length.  No launch when nothing is
+    given."""
     _req(scores, torch.float32, 'rules_mask scores')
     B = scores.shape[0]
     if scores.shape[1] < V or scores.stride(1) != 1:
@@ -290,12 +325,14 @@ def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=N
                         guided=gpos is not None)
     keyed = _key_args('rules_mask', scores.device, B, V, in_key=in_key, gkey=gkey)
     guided = _guide_args('rules_mask', scores.device, B, V, grammar=grammar, melody=melody, guide=guide, glen=glen, gpos=gpos, gforce=gforce)
-    check(lib().mxl_guided_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, *keyed, *guided, _stream()),
-          'mxl_guided_rules_mask')
+    ranged = _register_args('rules_mask', scores.device, B, V, register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=gap)
+    check(lib().mxl_ranged_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, *keyed, *guided, *ranged, _stream()),
+          'mxl_ranged_rules_mask')
 
 
 def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None,
-                  in_key=None, gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None):
+                  in_key=None, gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None,
+                  gpart=None, gfloor=None, gap=-1):
     """after sample + decode_advance: the words given (as rules_mask) move along the token at ids[b, t] in every row that chose it,
     then, with unfinished and alive, that token goes through the stop rule stop = (eos, pad, min_length): rows with unfinished[b] == 0
     get pad and keep their words (mxl_rules_advance).  No launch when nothing is given."""
@@ -309,8 +346,13 @@ def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar
     keyed = _key_args('rules_advance', ids.device, B, in_key=in_key, gkey=gkey)
     V = grammar.vocab_size if grammar is not None else (in_key.vocab_size if gkey is not None else 0)
     guided = _guide_args('rules_advance', ids.device, B, grammar=grammar, melody=melody, guide=guide, glen=glen, gpos=gpos, gforce=gforce)
-    check(lib().mxl_guided_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, *rules, *keyed, *guided, _stream()),
-          'mxl_guided_rules_advance')
+    ranged = _register_args('rules_advance', ids.device, B, register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=gap)
+    if gpart is not None:
+        if V and register.vocab_size != V:
+            raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the other rules {V}')
+        V = register.vocab_size
+    check(lib().mxl_ranged_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, *rules, *keyed, *guided, *ranged, _stream()),
+          'mxl_ranged_rules_advance')
 
 
 def key_scan(ids, Tp, in_key, gkey, first_bad, check_from=None):
@@ -326,6 +368,23 @@ def key_scan(ids, Tp, in_key, gkey, first_bad, check_from=None):
     keys, pcs, inkey = in_key.to(ids.device)
     check(lib().mxl_key_scan(_p(ids), ids.stride(0), int(Tp), int(Tp if check_from is None else check_from), B, in_key.vocab_size,
                              _p(keys), _p(pcs), _p(inkey), _p(gkey), _p(first_bad), _stream()), 'mxl_key_scan')
+
+
+def register_scan(ids, Tp, register, grange, gpart, gfloor, first_bad, gap=-1, check_from=None):
+    """(gpart[b], gfloor[b]) = the register words of row b after columns 0..Tp-1 of ids, walked from the words they hold now under
+    the bounds grange[b] and `gap` (ids < 0 skipped); columns before check_from (default Tp: none is judged) only move the words,
+    first_bad[b] = the first column from there on that holds a pitch outside the bounds of the row's open part, or -1
+    (mxl_register_scan); the host reference is RegisterRule.walk"""
+    B = ids.shape[0]
+    for t, name in ((grange, 'grange'), (gpart, 'gpart'), (gfloor, 'gfloor'), (first_bad, 'first_bad')):
+        _req(t, torch.int32, f'register_scan {name}')
+        if t.numel() != B or not t.is_contiguous():
+            raise MusicXLError(f'register_scan: {name} must be contiguous ({B},) int32')
+    if ids.dtype != torch.int64 or ids.stride(1) != 1 or Tp > ids.shape[1]:
+        raise MusicXLError('register_scan: ids must be (B, >= Tp) int64 with unit column stride')
+    check(lib().mxl_register_scan(_p(ids), ids.stride(0), int(Tp), int(Tp if check_from is None else check_from), B, register.vocab_size,
+                                  _p(register.to(ids.device)), _p(grange), int(gap), _p(gpart), _p(gfloor), _p(first_bad), _stream()),
+          'mxl_register_scan')
 
 
 def grammar_scan(ids, Tp, grammar, gstate, first_bad, start=None):

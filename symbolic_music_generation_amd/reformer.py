@@ -154,7 +154,8 @@ class MyReformerModelWithLMHead(EngineModule):
                  num_beam_groups: int = 1, length_penalty: float = 1.0, diversity_penalty=None,
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
-                 grammar=None, n_bars=None, in_key=None, key=None, melody=None, device_scorer: bool = False, **unsupported):
+                 grammar=None, n_bars=None, in_key=None, key=None, melody=None, device_scorer: bool = False, register=None,
+                 melody_range=None, bass_range=None, bass_below=None, **unsupported):
         """`model.generate(...)` as the reference drives it (musicnlp/trainer/eval.py:277-333): greedy, or sampling with
         top-k / top-p / typical-p / temperature / repetition penalty (applied, as HF does, to the raw logits); token selection
         runs on the device (the TransfoXL decoder's sampler kernel).
@@ -186,9 +187,15 @@ class MyReformerModelWithLMHead(EngineModule):
         melody (one guide for every prompt or a list of one per prompt, None = unguided; with grammar and eos_token_id, greedy
         decoding and sampling; no n_bars or min_length beside it): every guided row is fed the `<bar> <melody> ... <bass>` spans
         of its guide (`tokenizer.melody_guide`) bar by bar and writes the bass under each, then ends, as
-        MyTransfoXLLMHeadModel.generate -- here through the mask launch before the sampler and the advance after it."""
+        MyTransfoXLLMHeadModel.generate -- here through the mask launch before the sampler and the advance after it.
+
+        register (a `grammar.RegisterRule`, `tokenizer.register_rule()`) with melody_range / bass_range (an inclusive pair of MIDI
+        numbers or one per prompt, None = unconstrained) and bass_below (None or g >= 0 semitones): greedy decoding and sampling in
+        which every part keeps its pitches inside its bounds and the bass stays at least g under the lowest melody note of its bar,
+        as MyTransfoXLLMHeadModel.generate; it needs no grammar.  Every search here scores on the host and refuses it."""
         from .generate import (STOP_CHUNK, RowRules, bar_count_config, beam_generate, check_grammar_args, key_config,
-                               left_pad_counts, melody_config, plan_search, resolve_max_length, rules_refusal, sample_unfused, sampling_config,
+                               left_pad_counts, melody_config, plan_search, register_config, resolve_max_length, rules_refusal, sample_unfused,
+                               sampling_config,
                                stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
@@ -207,6 +214,8 @@ class MyReformerModelWithLMHead(EngineModule):
             raise rules_refusal('n_bars= is')
         if (in_key is not None or key is not None) and search:
             raise rules_refusal('in_key= is')
+        if register is not None and search:
+            raise rules_refusal('register= is')
         # every search runs on the host here (no caps); the rules were settled above
         plan = plan_search({}, num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample, penalty_alpha=penalty_alpha,
                            top_k=top_k, eos_token_id=eos_token_id, pad_token_id=pad_token_id, config_eos=self.config.eos_token_id,
@@ -216,6 +225,8 @@ class MyReformerModelWithLMHead(EngineModule):
         n_bars = (bar_count_config(n_bars, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, nrs) if guide is None
                   else guide.n_bars)
         keys = key_config(in_key, key, input_ids.shape[0] if input_ids is not None else 0, self.config.vocab_size, nrs)
+        span = register_config(register, melody_range, bass_range, bass_below, input_ids.shape[0] if input_ids is not None else 0,
+                               self.config.vocab_size, nrs)
         if attention_mask is not None and input_ids is not None and any(left_pad_counts(attention_mask, tuple(input_ids.shape))):
             # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
             raise MusicXLError(f'{type(self).__name__}.generate does not support padded prompts (attention_mask with zeros); '
@@ -277,7 +288,7 @@ class MyReformerModelWithLMHead(EngineModule):
                 dec.seed = seed
                 return dec.generate(ids0, max_length, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
                                     repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop, grammar=grammar, n_bars=n_bars,
-                                    in_key=in_key, key=keys, melody=guide)
+                                    in_key=in_key, key=keys, melody=guide, register=span)
             V = c.vocab_size
             pad = getattr(c, 'pad_token_id', None)
             pad = 0 if pad is None else int(pad)
@@ -286,7 +297,7 @@ class MyReformerModelWithLMHead(EngineModule):
             t_dev = torch.full((1,), Tp - 1, device=self.device, dtype=torch.int32)
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
             rules = RowRules(B, self.device)
-            rules.start(buf, Tp, V, stop, grammar, n_bars, in_key, keys, guide)
+            rules.start(buf, Tp, V, stop, grammar, n_bars, in_key, keys, guide, span)
             rules.check_prompt(buf)
             sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
             for cur in range(Tp, max_length):

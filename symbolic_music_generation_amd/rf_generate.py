@@ -26,7 +26,8 @@ import torch
 
 from . import ops
 from ._lib import MusicXLError
-from .generate import RowRules, bar_count_config, decode_lanes, key_config, melody_config, sample_unfused, sampling_config
+from .generate import (RowRules, bar_count_config, decode_lanes, key_config, melody_config, register_config, sample_unfused,
+                       sampling_config)
 
 
 class RFDecoder:
@@ -70,8 +71,8 @@ class RFDecoder:
         self.steps_run = 0
         # the rules of the current generation and their per-row words (generate.RowRules), readable here under their names
         self.rules = RowRules(batch, dev)
-        (self.unfinished, self.gstate, self.gbar, self.grem, self.gleft, self.gkey, self.gpos, self.gforce,
-         self.alive) = (getattr(self.rules, k) for k in RowRules.STATE)
+        for k in RowRules.STATE:
+            setattr(self, k, getattr(self.rules, k))
 
     # ---------------------------------------------------------------- hashing helpers
     def _factors(self, T_hint: Optional[int] = None):
@@ -101,14 +102,14 @@ class RFDecoder:
 
     # ---------------------------------------------------------------- prompt
     def prefill(self, prompt: torch.Tensor, sampling: dict, stop: Optional[tuple] = None, grammar=None,
-                n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None, melody=None):
+                n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None, melody=None, register=None):
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and 1 <= Tp <= self.Tmax
         d, H = c.hidden_size, c.num_attention_heads
         self.ids.zero_()
         self.ids[:, :Tp].copy_(prompt)
-        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars, in_key, keys, melody)
+        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars, in_key, keys, melody, register)
         for l in self.bk:
             self.n_bucketed[l] = 0
             self.bkmax[l].zero_()
@@ -254,7 +255,8 @@ class RFDecoder:
     def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
                  typical_p: Optional[float] = None, stop: Optional[tuple] = None, stop_chunk: int = 16,
-                 grammar=None, n_bars=None, in_key=None, key=None, melody=None) -> torch.Tensor:
+                 grammar=None, n_bars=None, in_key=None, key=None, melody=None, register=None, melody_range=None, bass_range=None,
+                 bass_below=None) -> torch.Tensor:
         """(B, max_length) ids = prompt + continuation.  stop = (eos, pad, min_length) (generate.stop_config): rows finish at eos
         and the loop ends once none is live -- the live-row count is read back every `stop_chunk` steps, one chunk late
         (generate.run_until_finished) -- and the output is cut to the longest row.  grammar: a grammar.TokenGrammar; every row may
@@ -263,22 +265,25 @@ class RFDecoder:
         opens exactly that many further bars (generate.XLDecoder.generate).  in_key (a grammar.KeyRule) with key: a row whose key is
         known emits only pitches of that key, kept by the same two launches (generate.XLDecoder.generate).  melody (one guide or one
         per row, or a generate.MelodyPlan): the rows are fed the `<bar> <melody> ... <bass>` spans of their guides and write the bass
-        under them, again by the same two launches (generate.melody_config)."""
+        under them, again by the same two launches (generate.melody_config).  register (a grammar.RegisterRule, or a
+        generate.RegisterPlan) with melody_range / bass_range / bass_below: every part keeps its pitches inside its bounds and the bass
+        under the melody of its bar, by the same two launches (generate.register_config)."""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         plan = melody_config(melody, self.B, grammar, stop, n_bars)
         return decode_lanes(self, [self], [None], prompt, max_length,
                             sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), False, None, stop,
                             stop_chunk, grammar, bar_count_config(n_bars if plan is None else plan.n_bars, self.B, grammar, stop),
-                            in_key, key_config(in_key, key, self.B, self.eng.cfg.vocab_size), plan)
+                            in_key, key_config(in_key, key, self.B, self.eng.cfg.vocab_size), plan,
+                            register_config(register, melody_range, bass_range, bass_below, self.B, self.eng.cfg.vocab_size))
 
     def begin(self, prompt, max_length, sampling, use_graph=False, n_pad=None, stop=None, grammar=None, n_bars=None, in_key=None,
-              keys=None, melody=None) -> int:
+              keys=None, melody=None, register=None) -> int:
         """generate.decode_lanes' entry: prompt pass and first token; returns the `replay_once()` calls left to max_length.  There
         is no graph to capture here, and padded prompts are not supported."""
         assert not use_graph and n_pad is None
         Tp = prompt.shape[1]
-        self.prefill(prompt.to(self.eng.dev), sampling, stop, grammar, n_bars, in_key, keys, melody)
+        self.prefill(prompt.to(self.eng.dev), sampling, stop, grammar, n_bars, in_key, keys, melody, register)
         self._next_t, self._sampling = Tp, sampling
         return max(max_length - 1 - Tp, 0)
 

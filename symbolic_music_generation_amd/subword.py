@@ -145,6 +145,10 @@ class PairMergeTokenizer(MusicTokenizer):
         raise NotImplementedError(f'{type(self).__name__}: a sub-word token may hold several pitches, so the key rule over single '
                                   'pitch tokens does not apply')
 
+    def register_rule(self):
+        raise NotImplementedError(f'{type(self).__name__}: a sub-word token may hold several pitches, so the register rule over '
+                                  'single pitch tokens does not apply')
+
     def melody_guide(self, ids, first_bar: int = 0, n_bars=None):
         raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders, so a melody '
                                   'guide over the token classes of the music grammar does not apply')
@@ -334,6 +338,10 @@ class WordPieceMusicTokenizer(MusicTokenizer):
     def key_rule(self):
         raise NotImplementedError(f'{type(self).__name__}: a sub-word token may hold several pitches, so the key rule over single '
                                   'pitch tokens does not apply')
+
+    def register_rule(self):
+        raise NotImplementedError(f'{type(self).__name__}: a sub-word token may hold several pitches, so the register rule over '
+                                  'single pitch tokens does not apply')
 
     def melody_guide(self, ids, first_bar: int = 0, n_bars=None):
         raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders, so a melody '

@@ -199,7 +199,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  use_graph: bool = True, seed: int = 77, attention_mask: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
                  min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, melody=None,
-                 device_scorer: bool = False, **unused) -> torch.Tensor:
+                 device_scorer: bool = False, register=None, melody_range=None, bass_range=None, bass_below=None,
+                 **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -262,6 +263,21 @@ class MyTransfoXLLMHeadModel(EngineModule):
         `in_key`: real melodies hold off-key notes, as prompts do.  It combines with everything `grammar` combines with;
         `generate.check_melody` verifies an output.  Beam, group-beam and contrastive search take no `melody`.
 
+        `register` (a `grammar.RegisterRule`, `tokenizer.register_rule()`) with `melody_range`, `bass_range` and `bass_below`: every
+        part stays in its register, and the bass under the melody.  A range is an inclusive pair `(lo, hi)` of MIDI numbers (60 =
+        `p_1/4`, middle C), one for every prompt or a sequence of one per prompt with None = unconstrained (repeated per prompt under
+        `num_return_sequences`); between `<melody>` and `<bass>` a row emits only pitches inside its melody range, between `<bass>`
+        and the next `<bar>` only pitches inside its bass range.  `bass_below=g` (g >= 0 semitones) also keeps every bass pitch at
+        least g under the lowest melody note of its bar: 0 lets the bass touch that note, 1 keeps it strictly below.  The bound is
+        per bar and not aligned in time -- "under the lowest melody note of the bar" is sufficient to keep the parts from crossing,
+        not necessary.  Rests and the rare-pitch token are never barred, so a row always has a token left where a pitch may follow,
+        even when its bounds leave no pitched one.  The prompt only sets the open part and the bar's lowest melody note, its pitches
+        are not judged; notes fed by `melody=` are not judged either but do set the bound of their bar, so `melody=` with
+        `bass_below=` writes the bass under the given melody.  The words live on the device beside the other rules' and the mask
+        sits in the same sampler launch, in the same place.  It needs no `grammar` and combines with everything `in_key` combines
+        with, the device searches included (given an explicit `eos_token_id=`); the host scorers refuse it.
+        `generate.check_register` verifies an output.
+
         Plain beam search (`num_beams` 2..16, `num_beam_groups=1`, `do_sample=False`) runs with its scorer on the device
         (`generate.beam_search_device`: mxl_beam_step / mxl_beam_reorder inside the captured step) and takes `grammar`, `n_bars` and
         `in_key` / `key` with the checks above, given an explicit `eos_token_id=` (without one they stay refused, as before); per-prompt values are shared by the prompt's beams, a barred token is -inf before
@@ -303,7 +319,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, beam_sample_device,
                                beam_search_device,
                                check_grammar_args, contrastive_search, contrastive_search_device, group_beam_search_device, key_config,
-                               left_pad_counts, melody_config, plan_search, resolve_max_length, stop_config)
+                               left_pad_counts, melody_config, plan_search, register_config, resolve_max_length, stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -326,21 +342,26 @@ class MyTransfoXLLMHeadModel(EngineModule):
                            config_eos=self.config.eos_token_id, config_pad=self.config.pad_token_id, padded=n_pad is not None,
                            grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody, device_scorer=device_scorer,
                            repetition_penalty=repetition_penalty, renormalize_logits=renormalize_logits,
-                           vocab_size=self.config.vocab_size)
+                           vocab_size=self.config.vocab_size, register=register)
         B0 = input_ids.shape[0]
         guide = melody_config(melody, B0, grammar, stop, n_bars, num_return_sequences)
         bars = bar_count_config(n_bars, B0, grammar, stop, num_return_sequences) if guide is None else None
         keys = key_config(in_key, key, B0, self.config.vocab_size, num_return_sequences)
+        ranges = dict(register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below)
+        span = register_config(**ranges, batch=B0, vocab_size=self.config.vocab_size, repeat=num_return_sequences)
+        if span is None:
+            ranges = {}                                     # (a call without the rule hands nothing of it on)
         ends = dict(eos_token_id=plan.eos, pad_token_id=plan.pad)
         if plan.strategy == 'contrastive':
             dec = XLDecoder(self.engine, B0 * top_k, max_length, seed=seed)
             if plan.device:
                 return contrastive_search_device(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha, use_graph=use_graph,
-                                                 grammar=grammar, in_key=in_key, key=key, **ends)
+                                                 grammar=grammar, in_key=in_key, key=key, **ranges, **ends)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha, **ends)
         if plan.device:                                     # (the device searches repeat per-prompt values per beam themselves)
             beams = dict(num_beams=num_beams, early_stopping=bool(early_stopping), length_penalty=length_penalty,
-                         num_return_sequences=num_return_sequences, use_graph=use_graph, grammar=grammar, in_key=in_key, key=key, **ends)
+                         num_return_sequences=num_return_sequences, use_graph=use_graph, grammar=grammar, in_key=in_key, key=key, **ranges,
+                         **ends)
             if plan.strategy == 'beam_sample':
                 dec = XLDecoder(self.engine, B0 * num_return_sequences * num_beams, max_length, seed=seed)
                 return beam_sample_device(dec, input_ids, max_length, top_k=top_k, top_p=top_p, temperature=temperature,
@@ -374,5 +395,5 @@ class MyTransfoXLLMHeadModel(EngineModule):
         return dec.generate(input_ids.to(self.device), max_length, do_sample=do_sample, top_k=top_k, top_p=top_p,
                             temperature=temperature, repetition_penalty=repetition_penalty, typical_p=typical_p,
                             use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device), grammar=grammar, n_bars=bars,
-                            in_key=in_key, key=keys, melody=guide,
+                            in_key=in_key, key=keys, melody=guide, **({} if span is None else {'register': span}),
                             **({} if stop is None else dict(eos_token_id=stop[0], pad_token_id=stop[1], min_length=stop[2])))

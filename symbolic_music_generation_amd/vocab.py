@@ -186,6 +186,12 @@ class MusicVocabulary:
         from .grammar import music_key_rule
         return music_key_rule(self)
 
+    def register_rule(self):
+        """the register rule over this vocabulary (grammar.music_register_rule), for `generate(register=...)`: every part keeps its
+        pitches inside the row's bounds, and the bass under the melody of its bar"""
+        from .grammar import music_register_rule
+        return music_register_rule(self)
+
 
 class MusicTokenizer:
     """Whitespace split -> `t2i`; `model_input_names = ['input_ids']` so no attention mask is ever produced
@@ -219,6 +225,10 @@ class MusicTokenizer:
     def key_rule(self):
         """the key rule (`MusicVocabulary.key_rule`), for `model.generate(in_key=...)`"""
         return self.vocab.key_rule()
+
+    def register_rule(self):
+        """the register rule (`MusicVocabulary.register_rule`), for `model.generate(register=...)`"""
+        return self.vocab.register_rule()
 
     def melody_guide(self, ids, first_bar: int = 0, n_bars: Optional[int] = None) -> List[int]:
         """the guide of `model.generate(melody=...)` from the token ids of a whole piece (a list or a 1-D tensor): over bars
