@@ -198,7 +198,14 @@ int mxl_relattn_drd_recompute(const void* dg, const void* qr, float* d_rd, int B
  * (delta[b][h][i] = sum_e dout . out: mxl_gemm_bf16_headdot forms it inside the GEMM that produces dout).  dq_rs, dq_bs multiples of 8.
  * defer_finish bit 0: the slab sum is left to the caller (mxl_relattn_dq_finish, same ws / oph / mph / lse / delta / dq / d_r_r_bias
  * arguments: with oph it also adds the phantom cells' part of d_r_r_bias, the column sums of their dq term; d_r_r_bias may be NULL).
- * dq and d_r_r_bias are complete only after it. */
+ * dq and d_r_r_bias are complete only after it.
+ * Owner mode (round 7): instead of one workgroup per 256-key block and the slabs, ONE workgroup per (sequence, head) walks its key
+ * blocks in order, carries the partial dq of a query tile in `ws` as fp32 (B T H 64 floats in tile order, no larger than the slabs:
+ * mxl_relattn_bwd_fused_ws_bytes stays the maximum of both modes; no zero-fill needed) and finishes dq and the phantom cells' part
+ * of d_r_r_bias itself -- no finishing kernel, one bf16 rounding per dq element.  dk, dv are bit-identical between the modes.
+ * defer_finish bit 2 forces owner mode, bit 3 per-block mode (both: MXL_EINVAL); bit 0 always means per-block mode.  Without a
+ * forcing bit owner mode is chosen when its B H equally long workgroups fill the usable compute units (all minus
+ * mxl_set_reserved_cus) without a long tail: B H / (ceil(B H / CUs) CUs) >= 0.9. */
 size_t mxl_relattn_bwd_fused_ws_bytes(int B, int T, int H, int dh, int M);
 int mxl_relattn_bwd_fused(const void* q, const void* k, const void* v, const void* rd, const float* r_w_bias,
                           const float* r_r_bias, const void* out, const void* dout, const float* lse, float* delta,

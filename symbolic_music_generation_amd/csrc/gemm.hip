@@ -1168,6 +1168,7 @@ static int gemm_n_cu() {
     const int left = n_cu - g_reserved_cus;
     return left >= 8 ? left : 8;
 }
+int mxl_usable_cus() { return gemm_n_cu(); }    // (for the other translation units: musicxl_internal.h)
 // which large-tile kernel the last K-contiguous product went to: 0 none of them, 1 eight waves x 256-wide tiles, 2 eight waves x 192-wide,
 // 3 four waves (tests: the shapes they mean to put on a kernel are on it)
 static int g_last_nt_kernel = 0;

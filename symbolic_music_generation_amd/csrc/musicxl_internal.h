@@ -14,3 +14,6 @@ struct Scope {
     ~Scope() { if (on) end(id, s); }
 };
 }  // namespace mxl_kt
+
+// compute units of the device minus what mxl_set_reserved_cus set aside, at least 8 (gemm.hip)
+int mxl_usable_cus();

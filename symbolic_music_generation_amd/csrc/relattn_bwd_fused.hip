@@ -15,10 +15,18 @@
 //   * dS crosses LDS once, in two images: X[key][query] (straight, 8-byte writes) and Y[query][distance - dlo] (un-skewed, 16-bit
 //     writes at lane-constant + immediate addresses: the rel-shift).  After the barrier every wave forms one 16 x 16 piece of
 //     dq[32 queries][64] = X^T K + Y Rd over the whole contraction (256 keys + 288 distances, v_mfma_f32_16x16x32_bf16), so the
-//     8 waves' pieces need no sum: the tile's partial dq goes out with plain stores into a per-key-block fp32 slab, and
-//     relattn_dq_finish_kernel adds the (at most M/256 + 1) slabs of a query, the forward's phantom value-sum term, rounds to
-//     bf16 once.  Plain stores run 4-5x the float-atomic rate (MI355X_MICROARCH.md, Global float atomics) and the sum is
-//     reproducible.
+//     8 waves' pieces need no sum.  A query tile is seen by up to M/256 + 1 key blocks, and its dq is their pieces' sum, formed in
+//     one of two ways (the host picks: fused_owner_fills):
+//       per-block mode  one workgroup per key block.  The tile's partial dq goes out with plain stores into a per-key-block bf16
+//                       slab, and relattn_dq_finish_kernel adds the slabs of a query, the forward's phantom value-sum term, and
+//                       rounds to bf16 once: 0.9 GB of slab writes and a 1.48 GB HBM-bound pass per layer at the bench shape.
+//       owner mode      one workgroup per (sequence, head) walks the key blocks in ascending order, so the same wave forms the same
+//                       piece in the same lanes on every visit of a tile: the partial is carried in fp32 in a scratch of the
+//                       workgroup's own (plain load, add, store; a lane reads back only what it wrote), and on the tile's last
+//                       visit the phantom term is added, the sum rounded to bf16 once and dq written -- no slabs, no finishing
+//                       pass, one rounding per element instead of one per key block.
+//     Either way plain stores, which run 4-5x the float-atomic rate (MI355X_MICROARCH.md, Global float atomics), and a
+//     reproducible sum.
 //   * dG never leaves the chip.  The 32-distance blocks of the tile's window slide down by one block per query tile; wave w
 //     keeps the fp32 accumulator of "its" block -- the one whose index is w mod 8 -- for the nine tiles the block stays in the
 //     window (dRd_blk += Y_blk^T Qr, 4 MFMAs per tile), then adds it to d_rd with 32 float atomic instructions (two 128-byte
@@ -32,7 +40,8 @@
 //
 // Zero memories (the reference's training, mode R): key positions below the first stored one exist only as distances.  Their
 // part of dq comes from the forward's value-sum over ALL such cells (mxl_relattn_fwd_phantom2, oph_all = 1), added by the
-// finishing kernel; their part of d_rd is rebuilt on MFMA from q, rd, lse, delta by mxl_relattn_drd_phantom (relattn_bwd.hip).
+// finishing kernel (owner mode: by the fused kernel on a tile's last visit, its column sums into d r_r_bias with the stored keys');
+// their part of d_rd is rebuilt on MFMA from q, rd, lse, delta by mxl_relattn_drd_phantom (relattn_drd_phantom.hip).
 #include <cstdlib>
 #include <type_traits>
 #include "common.h"
@@ -72,6 +81,9 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define PRIO_DOWN() do { if (FUSED_PRIO & 1) __builtin_amdgcn_s_setprio(0); } while (0)
 #define PRIO_UP_B(bit_) do { if (FUSED_PRIO & (bit_)) __builtin_amdgcn_s_setprio(1); } while (0)
 #define PRIO_DOWN_B(bit_) do { if (FUSED_PRIO & (bit_)) __builtin_amdgcn_s_setprio(0); } while (0)
+#ifndef FUSED_OWNER_LD_EARLY
+#define FUSED_OWNER_LD_EARLY 1                  // owner mode: the carried partial dq and the oph pairs requested ahead of barrier 1 (1) or behind dV / dK (0)
+#endif
 #ifndef FUSED_TRF_EARLY
 #define FUSED_TRF_EARLY 1                       // transposed dO / Qw fragments requested ahead of barrier 1 (1) or behind it (0)
 #endif
@@ -84,7 +96,7 @@ constexpr int RING_BLKS = 10;                   // Rd ring: ten 32-row blocks   
 constexpr int RBLK_BYTES = 32 * ROWB;
 constexpr int RING_BYTES = RING_BLKS * RBLK_BYTES;
 constexpr int QIMG = QT * ROWB;
-constexpr int QSET = 3 * QIMG + 2 * QT * 4;     // Qw, Qr, dO images + -lse (log2) + -scale*delta          12.25 KB, two sets
+constexpr int QSET = 3 * QIMG + 3 * QT * 4;     // Qw, Qr, dO images + -lse (log2) + -scale*delta + mph (owner mode)   12.4 KB, two sets
 constexpr int GP = 584;                         // fp16 skew buffer pitch (bytes): 288 columns + pad; 146 dwords = 2 mod 16
 constexpr int G_BYTES = QT * GP;
 constexpr int X_BYTES = KBLK * 64;              // X[key][32 queries] bf16
@@ -94,7 +106,7 @@ constexpr int YP = 608;                         // Y[query][288 columns + pad] b
 constexpr int Y_BYTES = QT * YP;
 constexpr int BIAS_BYTES = 2 * 64 * 4;
 constexpr int PARK_BYTES = FUSED_PARK ? 32 * 64 * 4 : 0;   // (FUSED_PARK) the dRd block that left the window in the previous tile: [32 distances][64] fp32
-constexpr int SMEM = K_BYTES + RING_BYTES + 2 * QSET + G_BYTES + X_BYTES + Y_BYTES + BIAS_BYTES + PARK_BYTES;   // 153 856 B (+ 8 KB with FUSED_PARK): one workgroup per CU
+constexpr int SMEM = K_BYTES + RING_BYTES + 2 * QSET + G_BYTES + X_BYTES + Y_BYTES + BIAS_BYTES + PARK_BYTES;   // 154 112 B (+ 8 KB with FUSED_PARK): one workgroup per CU
 constexpr int RING_OFF = 10240;                 // multiple of RING_BLKS added to (possibly negative) block indices before the modulo
 
 // In-kernel stamps (diagnostic builds only: scripts/ab_build.sh relattn_bwd_fused stamp -DMXL_STAMP; the shipped library has none).
@@ -128,6 +140,12 @@ struct FusedP {
     const float *rwb, *rrb, *lse, *delta;
     bf16_t *dk, *dv;
     slab_t* slab;         // [nslot][B][T][H*64] partial dq, slot = key block - first key block that sees the query tile
+                          // (owner mode: the same bytes as an fp32 scratch [B][H][T/32][8 waves][64 lanes][4])
+    bf16_t* dq;           // owner mode only: dq is finished in the kernel, from oph / mph (NULL: no phantom cells)
+    const bf16_t* oph;
+    const float* mph;
+    long long dq_bs;
+    int dq_rs;
     float* drd;           // (M, drd_ld) fp32, +=
     float *d_rwb, *d_rrb; // (H, 64) fp32, +=  (the stored keys' part)
     int B, T, H, M, Kc;
@@ -224,7 +242,11 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
 // operations on every path of the loop -- its staging loads, four atomics of the block parked in LDS, two slab stores -- also on the
 // last tiles (clamped tile index, stores into the image nobody reads any more) and in front of the loop (VM_PER_TILE dummy
 // atomics of 0.0), so the wait hipcc computes leaves the younger six in flight.
-constexpr int VM_PER_TILE = 6;                  // vector-memory operations a wave issues per tile behind its staging loads: 4 atomics + 2 slab stores
+// Owner mode has more of them, under the same rule: the load of the carried partial and the two oph loads, the store of the partial
+// and the two dq stores are issued on EVERY visit of a tile; those a visit does not want (first visit: the load; last visit: the
+// scratch store; every other: the oph loads and the dq stores) go out with a lane offset beyond the descriptor's records.
+constexpr int VM_PER_TILE_BLOCK = 6;            // vector-memory operations a wave issues per tile behind its staging loads: 4 atomics + 2 slab stores
+constexpr int VM_PER_TILE_OWNER = 10;           // owner mode: 3 loads (partial, 2 oph) + 3 stores (partial, 2 dq) + 4 atomics
 
 // delta[b,h,i] = sum_e dO[b,i,h,e] * O[b,i,h,e]   (dh = 64: 8 lanes per head, one wave per token row per sweep of 8 heads)
 __global__ __launch_bounds__(256) void fused_delta_kernel(const bf16_t* o, const bf16_t* dout, float* delta, int B, int T, int H,
@@ -265,8 +287,16 @@ __global__ __launch_bounds__(256) void fused_delta_kernel(const bf16_t* o, const
 //   barrier 2
 // Until round 5 phase B was three rounds "all reads of the round, wait, all MFMAs of the round" (256 registers hold one round), each
 // of which exposed a full LDS round trip with all eight waves reading at once, and dV / dK sat in front of barrier 1.
+//
+// OWNER = false (per-block mode): grid (Kc / 256, H, B), a workgroup owns ONE key block and writes its partial dq of every tile it
+// sees into that block's bf16 slab; relattn_dq_finish_kernel sums the slabs.  OWNER = true (owner mode): grid (1, H, B), a workgroup
+// walks all key blocks of its (sequence, head) -- prologue, tile sweep, dk / dv write and dRd flush per key block exactly as in
+// per-block mode, a workgroup barrier between key blocks -- carries the partial dq in an fp32 scratch of its own and finishes dq
+// itself on each tile's last visit: no slabs, no finishing pass, and the fp32 sum sees one bf16 rounding instead of one per key block.
+template <bool OWNER>
 __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
     constexpr int NT = 512;
+    constexpr int VM_PER_TILE = OWNER ? VM_PER_TILE_OWNER : VM_PER_TILE_BLOCK;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sK = smem;
     char* sR = sK + K_BYTES;
@@ -282,11 +312,13 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l = tid & 63, r = l & 31, hh = l >> 5;
     int bx_, h, b;
-    xcd_block(bx_, h, b);
+    xcd_block(bx_, h, b);                       // (owner mode: the grid is (1, H, B), bx_ = 0 is the first key block of the walk)
+    // (through readfirstlane: hipcc otherwise re-forms h * 64 on both sides of the divergent bias-load branch below, and the merged value --
+    // with it the dRd descriptor -- lands in vector registers: every atomic of the tile loop in a readfirstlane loop)
+    const int h64 = __builtin_amdgcn_readfirstlane(h * 64);
     const int T = p.T, M = p.M;
     const int p0 = T - p.Kc;                    // lowest stored key position (a multiple of 32)
-    const int P0 = p0 + KBLK * bx_;             // first key position of the workgroup
-    const int Pw = P0 + 32 * w;                 // first key position of the wave
+    const int nkb = (p.Kc + KBLK - 1) / KBLK;   // key blocks of a (sequence, head)
     const int kloc0 = 32 * w + r;               // this lane's key inside the workgroup
     const int MB = M >> 5;
 
@@ -297,62 +329,44 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
     const bf16_t* vbase = p.v + (size_t)b * p.kv_bs + (size_t)h * 64;
 
     // ---- lane constants.  gq / q4 / pp: the decomposition the transposed 8-byte reads use (16 lanes read 4 rows x 16 columns)
+    // Per-block mode forms them here.  Owner mode forms them anew behind every key block's prologue, from a lane id hipcc cannot see
+    // through: formed once, all fourteen would be live across the prologues' loads (the K rows, nine Rd blocks), which then spill.
+    const int eq = w >> 1, ih0 = w & 1;         // dq piece of this wave: elements 16 eq .. 16 eq + 15 of the 16-row half ih0 of the tile's queries
+    const int g16 = l >> 4;
+    int rowq, rows, tkb, xw, yt0, qb0, xa0, xa1, ka0, ka1, yq0, krow;
+    uint32_t gRb, yWb;
+    auto lane_consts = [&](const int l) {
+    const int r = l & 31, hh = l >> 5, kloc0 = 32 * w + r;
     const int gq = l >> 4, q4 = (l & 15) >> 2, pp = l & 3;
-    int rowq = qoff(r, hh);                                  // Q-set row fragment, k-step ks: rowq ^ (ks << 5)
-    int rows = r * ROWB + ((hh ^ sswz(r)) << 4);             // ring row fragment,   k-step ks: rows ^ (ks << 5)
+    rowq = qoff(r, hh);                                  // Q-set row fragment, k-step ks: rowq ^ (ks << 5)
+    rows = r * ROWB + ((hh ^ sswz(r)) << 4);             // ring row fragment,   k-step ks: rows ^ (ks << 5)
     // Q-set transposed pattern: rows 4 hh + q4 (+ 8: chunk bit 0 flips, + 16: nothing), elements 16 (gq & 1) + 4 pp .. + 3 (+ 32 e: chunk bit 2 flips)
-    int tkb = qeoff(4 * hh + q4, 16 * (gq & 1) + 4 * pp);
+    tkb = qeoff(4 * hh + q4, 16 * (gq & 1) + 4 * pp);
     // skew buffers
-    const uint32_t gRb = lds_addr(sG) + 4 * hh * (GP + 2) + (256 - kloc0) * 2;
-    const uint32_t yWb = lds_addr(sY) + 4 * hh * (YP + 2) + (256 - kloc0) * 2;
+    gRb = lds_addr(sG) + 4 * hh * (GP + 2) + (256 - kloc0) * 2;
+    yWb = lds_addr(sY) + 4 * hh * (YP + 2) + (256 - kloc0) * 2;
     // X[key][query]: 8-byte granule g of row p at g ^ ((p >> 1) & 7): this lane's group `grp` (queries 8 grp + 4 hh ..) at xw ^ (grp << 4)
     const int xf = (kloc0 >> 1) & 7;
-    int xw = kloc0 * 64 + ((((hh ^ (xf & 1)) | (xf & 6))) << 3);
+    xw = kloc0 * 64 + ((((hh ^ (xf & 1)) | (xf & 6))) << 3);
     // dRd operands (16x16x32, this wave's slice: distances 16 (w & 1) .. + 15 of a block, elements 16 (w >> 1) .. + 15): transposed reads
     // with the contraction index (the query) permuted -- lane group g reads image rows 4 g .. 4 g + 3 and 16 + 4 g .. 19 + 4 g, in Y and
     // in the Qr image alike -- so that the eight rows a 32-lane half touches are consecutive (conflict-free at this pitch)
-    int yt0 = (4 * (l >> 4) + ((l & 15) >> 2)) * YP + (16 * (w & 1) + 4 * pp) * 2;       // second read: + 16 YP; block v: + 64 v
-    int qb0 = qeoff(4 * (l >> 4) + ((l & 15) >> 2), 16 * (w >> 1) + 4 * pp);             // second read: + 2048 (sixteen rows on)
-    // dq piece of this wave: elements 16 eq .. 16 eq + 15 of the 16-row half ih0 of the tile's queries
-    const int eq = w >> 1, ih0 = w & 1;
+    yt0 = (4 * (l >> 4) + ((l & 15) >> 2)) * YP + (16 * (w & 1) + 4 * pp) * 2;       // second read: + 16 YP; block v: + 64 v
+    qb0 = qeoff(4 * (l >> 4) + ((l & 15) >> 2), 16 * (w >> 1) + 4 * pp);             // second read: + 2048 (sixteen rows on)
     const int g16 = l >> 4, q16 = (l & 15) >> 2;                   // 16x16x32 transposed pattern: rows 8 g16 + q16 (+4), 4 columns at 4 pp
-    int xa0 = ((8 * g16 + q16) * 64 + ((pp ^ ((4 * g16 + (q16 >> 1)) & 7)) << 3)) ^ (ih0 << 5);
-    int xa1 = ((8 * g16 + q16 + 4) * 64 + ((pp ^ ((4 * g16 + 2 + (q16 >> 1)) & 7)) << 3)) ^ (ih0 << 5);
+    xa0 = ((8 * g16 + q16) * 64 + ((pp ^ ((4 * g16 + (q16 >> 1)) & 7)) << 3)) ^ (ih0 << 5);
+    xa1 = ((8 * g16 + q16 + 4) * 64 + ((pp ^ ((4 * g16 + 2 + (q16 >> 1)) & 7)) << 3)) ^ (ih0 << 5);
     const int kch = 2 * eq + (pp >> 1);
     const int ksw = ((g16 & 1) << 2) | (((q16 >> 1) & 1) << 1);
-    int ka0 = (8 * g16 + q16) * ROWB + ((kch ^ ksw) << 4) + ((pp & 1) << 3);
-    int ka1 = (8 * g16 + q16 + 4) * ROWB + ((kch ^ (ksw | 1)) << 4) + ((pp & 1) << 3);
-    int yq0 = (16 * ih0 + (l & 15)) * YP + 16 * g16;         // Y row fragment (16x16x32 A): row = query
-    int krow = kloc0 * ROWB + ((hh ^ sswz(kloc0)) << 4);           // K image row fragment of the lane's key (B operand of S), k-step ks: krow ^ (ks << 5)
+    ka0 = (8 * g16 + q16) * ROWB + ((kch ^ ksw) << 4) + ((pp & 1) << 3);
+    ka1 = (8 * g16 + q16 + 4) * ROWB + ((kch ^ (ksw | 1)) << 4) + ((pp & 1) << 3);
+    yq0 = (16 * ih0 + (l & 15)) * YP + 16 * g16;         // Y row fragment (16x16x32 A): row = query
+    krow = kloc0 * ROWB + ((hh ^ sswz(kloc0)) << 4);           // K image row fragment of the lane's key (B operand of S), k-step ks: krow ^ (ks << 5)
+    };
+    if (!OWNER) lane_consts(l);
 
-    // ---- prologue: biases, K image, Y zeroed, V fragments (B operand of dP: lane = key, k = 16 ks + 8 hh + j)
-    if (tid < 128) sBias[tid] = (tid < 64) ? p.rwb[h * 64 + tid] : p.rrb[h * 64 + tid - 64];
-#pragma unroll
-    for (int n = 0; n < 2048 / NT; n++) {
-        const int c = tid + n * NT;
-        const int row = c >> 3, ch = c & 7;
-        const int srow = KBLK * bx_ + row;
-        u32x4 val = {0u, 0u, 0u, 0u};
-        if (srow < p.Kc) val = *reinterpret_cast<const u32x4*>(kbase + (size_t)srow * p.kv_rs + ch * 8);
-        *reinterpret_cast<u32x4*>(sK + soff(row, ch)) = val;
-    }
-    for (int i = tid; i < Y_BYTES / 16; i += NT) reinterpret_cast<u32x4*>(sY)[i] = u32x4{0u, 0u, 0u, 0u};
-    bf16x8 vf[4];
-    const bool kok = Pw + r < T;
-    {
-        const size_t srow = (size_t)(kok ? Pw + r - p0 : 0);
-        const bf16_t* vp = vbase + srow * p.kv_rs;
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) {
-            const bf16x8 vv = *reinterpret_cast<const bf16x8*>(vp + 16 * ks + 8 * hh);
-#pragma unroll
-            for (int j = 0; j < 8; j++) vf[ks][j] = kok ? vv[j] : (short)0;
-        }
-    }
-
-    // queries that can see any key of this workgroup: i in [P0, P0 + 255 + M - 1], clipped to [0, T)
-    const int i_lo = max(P0, 0), i_hi = min(P0 + KBLK - 1 + M - 1, T - 1);
-    const int it_lo = i_lo >> 5, it_hi = i_hi >> 5;
+    // ---- once per workgroup: the head's biases
+    if (tid < 128) sBias[tid] = (tid < 64) ? p.rwb[h64 + tid] : p.rrb[h64 + tid - 64];
 
     // ---- staging: every thread owns one 16-byte chunk (row (tid & 255) >> 3, chunk tid & 7) of two of the four 4 KB images a tile
     // needs: waves 0-3 the Qw image (from the q rows) and the new Rd block, waves 4-7 the Qr image (from the same q rows) and the dO
@@ -367,8 +381,13 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
     const __amdgpu_buffer_rsrc_t rs_2 = __builtin_amdgcn_make_buffer_rsrc((void*)(st_q ? rbase : dobase), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_lse = __builtin_amdgcn_make_buffer_rsrc((void*)(p.lse + ((size_t)b * p.H + h) * T), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_dl = __builtin_amdgcn_make_buffer_rsrc((void*)(p.delta + ((size_t)b * p.H + h) * T), 0, -1, 0x00020000);
+    // (owner mode) the phantom term's reference exponent mph rides with lse and delta; without phantom cells the descriptor has no
+    // records and the load returns 0
+    const bool has_ph = OWNER && p.oph != nullptr;
+    const __amdgpu_buffer_rsrc_t rs_mph = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(has_ph ? p.mph + ((size_t)b * p.H + h) * T : p.lse), 0, has_ph ? T * 4 : 0, 0x00020000);
     u32x4 tq = {0u, 0u, 0u, 0u}, t2 = {0u, 0u, 0u, 0u};
-    float tl = 0.f, tdl = 0.f;
+    float tl = 0.f, tdl = 0.f, tm = 0.f;
     // The staging indices are recomputed from the thread id at every use (the id goes through an empty asm, so hipcc cannot hoist what
     // is derived from it): held across the tile loop, their registers were what the kernel spilled.
 #define STG_IDS int tid_o = tid; asm volatile("" : "+v"(tid_o)); const int srow_ = (tid_o & 255) >> 3, sch_ = tid_o & 7;
@@ -383,6 +402,7 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
         t2 = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_2, vo2, so2, 0));
         tl = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_lse, (tid & 31) * 4, I * 4, 0));
         tdl = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_dl, (tid & 31) * 4, I * 4, 0));
+        if (OWNER) tm = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_mph, (tid & 31) * 4, I * 4, 0));
     };
     auto store_stage = [&](int buf, int slot) { // -> Q set `buf`, ring slot `slot`
         STG_IDS
@@ -410,7 +430,10 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
             for (int j = 0; j < 8; j++) dd[j] = f2bf(bf2f(src[j]) * p.scale);
             *reinterpret_cast<u32x4*>(sDO + qoff(srow_, sch_)) = wd;
         }
-        if (tid < 32) { sLse[tid] = -tl * LOG2E; sLse[QT + tid] = -p.scale * tdl; }
+        if (tid < 32) {
+            sLse[tid] = -tl * LOG2E; sLse[QT + tid] = -p.scale * tdl;
+            if (OWNER) sLse[2 * QT + tid] = tm;
+        }
     };
     // ring slots: block n sits in slot (n + RING_OFF) mod RING_BLKS.  rs0 = slot of the first block n0 of the current tile's window,
     // advanced by one per tile; the slots of the window's other blocks by add / compare / select (no division in the loop)
@@ -434,56 +457,13 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
         }
     };
 
-    int rs0;                                    // ring slot of the current tile's first distance block
-    {
-        const int n0 = (it_lo * QT - P0 - KBLK) >> 5;
-        rs0 = (n0 + RING_OFF) % RING_BLKS;
-        load_stage(it_lo, n0 + 8);
-        __syncthreads();                        // biases in LDS
-        store_stage(0, slot_add(rs0, 8));       // (block n0 + 8 is one of the nine loaded below: the same bytes twice)
-        // the nine Rd blocks of the first window: 9 x 256 sixteen-byte chunks, loads first
-        constexpr int NPR = (9 * 256 + NT - 1) / NT;
-        u32x4 pr_[NPR];
-#pragma unroll
-        for (int n = 0; n < NPR; n++) {
-            const int c = tid + n * NT;
-            int d = 32 * n0 + (c >> 3);
-            d = d < 0 ? 0 : (d > M - 1 ? M - 1 : d);
-            pr_[n] = (c < 9 * 256) ? *reinterpret_cast<const u32x4*>(rbase + (size_t)d * p.rd_rs + (c & 7) * 8) : u32x4{0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int n = 0; n < NPR; n++) {
-            const int c = tid + n * NT;
-            if (c < 9 * 256) {
-                const int slot = slot_add(rs0, c >> 8);
-                *reinterpret_cast<u32x4*>(sR + slot * RBLK_BYTES + soff((c >> 3) & 31, c & 7)) = pr_[n];
-            }
-        }
-    }
-    __syncthreads();
-    {                                           // the nine G blocks of the first tile: wave w takes block w, wave 0 also block 8
-        bf16x8 bq[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ks++) bq[ks] = *reinterpret_cast<const bf16x8*>(sQ + QIMG + (rowq ^ (ks << 5)));
-        gblock(w, rs0, bq);
-        if (w == 0) gblock(8, rs0, bq);
-    }
-    load_stage(min(it_lo + 1, it_hi), ((it_lo * QT - P0 - KBLK) >> 5) + 9);                      // stored at the top of the first tile
-    __syncthreads();
-
-    f32x16 ak[2], av[2];                        // dK^T, dV^T : [e half][e][key]
-#pragma unroll
-    for (int e = 0; e < 2; e++)
-#pragma unroll
-        for (int j = 0; j < 16; j++) { ak[e][j] = 0.f; av[e][j] = 0.f; }
+    f32x16 ak[2], av[2];                        // dK^T, dV^T : [e half][e][key]   (zeroed at the head of every key block)
     // dRd: racc[v] = this wave's 16 x 16 slice of the fp32 sum of the distance block at window position v.  The window slides by one
     // block per tile, so the MFMA of position v writes the registers of position v - 1 (an MFMA's destination need not be its C
     // operand): no register moves; position 0 leaves the window with the tile and goes to the park buffer, position 8 starts at zero.
     // Until round 5 a whole block lived in ONE wave (32 registers) for the nine tiles it stayed in the window, and that wave alone
     // wrote it out -- thirty-two memory operations at the end of its phase B once per tile, with seven waves waiting at barrier 2.
     f32x4 racc[9];
-#pragma unroll
-    for (int v = 0; v < 9; v++) racc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
     float cw = 0.f, cr = 0.f;                   // running column sums of this wave's dQw / dQr pieces (d r_w_bias / d r_r_bias)
 
     // dRd flush.  A block leaves the window once per tile, in the registers of ONE wave.  Thirty-two atomics from that wave stalled it
@@ -493,7 +473,7 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
     // where the blocks outside [0, M) go, so that every path still issues the same operations without adding zeros to memory:
     // until round 5 they went onto block 0, 0.4 GB of atomic traffic per layer onto one 8 KB target)
     const int ld4 = p.drd_ld * 4;
-    const __amdgpu_buffer_rsrc_t rs_drd = __builtin_amdgcn_make_buffer_rsrc((void*)(p.drd + h * 64), 0, (int)((32 * MB - 1) * ld4 + 256), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_drd = __builtin_amdgcn_make_buffer_rsrc((void*)(p.drd + h64), 0, (int)((32 * MB - 1) * ld4 + 256), 0x00020000);
     constexpr int DRD_OOB = 0x7ffff000;
     auto drd_park = [&](const f32x4& leave) {   // this wave's slice of the block that leaves the window -> sPark[distance][e]
 #pragma unroll
@@ -532,7 +512,7 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
             asm volatile("" :: "v"(pk[i]));
 #endif
     };
-    auto drd_flush_direct = [&](int nfirst) {   // after the sweep: the eight blocks still in registers (positions 0 .. 7 = blocks nfirst ..)
+    auto drd_flush_direct = [&](int nfirst, const int l) {      // after the sweep: the eight blocks still in registers (positions 0 .. 7 = blocks nfirst ..)
 #ifndef MXL_ABL_NO_ATOMICS
         const float f = 1.f / p.scale_log2e;
         const int vo = 4 * (l >> 4) * ld4 + (16 * (w >> 1) + (l & 15)) * 4;
@@ -547,6 +527,112 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
         }
 #endif
     };
+    // Owner mode: this workgroup walks ALL key blocks of its (sequence, head), so the partial dq of a query tile is formed by the same
+    // wave, in the same lanes, on every visit.  It is carried in fp32 in `ws`, tile-native: ((b H + h) T/32 + it) * 8 KB + w * 1 KB +
+    // lane * 16 B holds the lane's four values -- one contiguous 1 KB load and one 1 KB store per wave and visit, a lane only ever
+    // reads back what it wrote itself (no atomics, no fences, no zero-fill).  The tile's first visit starts from zero, its last visit
+    // adds the phantom term, rounds once and writes dq.  Every visit issues the SAME vector-memory operations (see VM_PER_TILE): the
+    // ones a visit does not want carry a lane offset beyond the descriptor's records -- such a load returns 0 (that IS the first
+    // visit's start value), such a store is dropped.
+    const __amdgpu_buffer_rsrc_t rs_sc = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)((char*)p.slab + (OWNER ? ((size_t)b * p.H + h) * (size_t)(T >> 5) * 8192 : 0)), 0, OWNER ? (T >> 5) * 8192 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_dq = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(OWNER ? p.dq + (size_t)b * p.dq_bs + (size_t)h * 64 + 16 * eq : (bf16_t*)p.slab), 0, OWNER ? T * p.dq_rs * 2 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_oph = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(has_ph ? p.oph + (size_t)b * p.o_bs + (size_t)h * 64 + 16 * eq : p.q), 0, has_ph ? T * p.o_rs * 2 : 0, 0x00020000);
+    auto owner_loads = [&](int it, bool first, bool last, f32x4& part, uint32_t (&ophw)[2]) {
+        part = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_sc, first ? DRD_OOB : l * 16, it * 8192 + w * 1024, 0));
+        const int vo = last ? (4 * g16 + ((l & 1) ? 2 : 0)) * p.o_rs * 2 + ((l & 15) >> 1) * 4 : DRD_OOB;
+#pragma unroll
+        for (int u = 0; u < 2; u++)
+            ophw[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs_oph, vo, (it * QT + 16 * ih0 + u) * p.o_rs * 2, 0);
+    };
+
+#pragma unroll 1
+    do {                                        // key blocks: this workgroup's one (per-block mode) or 0 .. nkb - 1 in ascending order (owner mode)
+    const int P0 = p0 + KBLK * bx_;             // first key position of the key block
+    const int Pw = P0 + 32 * w;                 // first key position of the wave
+    __syncthreads();                            // biases in LDS; (owner mode) every wave is done with the previous key block's images
+    // (owner mode: the prologue's addresses from a thread id hipcc cannot see through -- hoisted out of the key-block loop they were
+    // live across every tile loop, and spilled)
+    int tp = tid;
+    if (OWNER) asm volatile("" : "+v"(tp));
+    // ---- prologue of a key block: K image, Y zeroed, V fragments (B operand of dP: lane = key, k = 16 ks + 8 hh + j)
+#pragma unroll
+    for (int n = 0; n < 2048 / NT; n++) {
+        const int c = tp + n * NT;
+        const int row = c >> 3, ch = c & 7;
+        const int srow = KBLK * bx_ + row;
+        u32x4 val = {0u, 0u, 0u, 0u};
+        if (srow < p.Kc) val = *reinterpret_cast<const u32x4*>(kbase + (size_t)srow * p.kv_rs + ch * 8);
+        *reinterpret_cast<u32x4*>(sK + soff(row, ch)) = val;
+    }
+    for (int i = tp; i < Y_BYTES / 16; i += NT) reinterpret_cast<u32x4*>(sY)[i] = u32x4{0u, 0u, 0u, 0u};
+    bf16x8 vf[4];
+    const bool kok = Pw + r < T;
+    {
+        const size_t srow = (size_t)(kok ? Pw + r - p0 : 0);
+        const bf16_t* vp = vbase + srow * p.kv_rs;
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) {
+            const bf16x8 vv = *reinterpret_cast<const bf16x8*>(vp + 16 * ks + 8 * hh);
+#pragma unroll
+            for (int j = 0; j < 8; j++) vf[ks][j] = kok ? vv[j] : (short)0;
+        }
+    }
+
+    // queries that can see any key of this key block: i in [P0, P0 + 255 + M - 1], clipped to [0, T)
+    const int i_lo = max(P0, 0), i_hi = min(P0 + KBLK - 1 + M - 1, T - 1);
+    const int it_lo = i_lo >> 5, it_hi = i_hi >> 5;
+
+    int rs0;                                    // ring slot of the current tile's first distance block
+    {
+        const int n0 = (it_lo * QT - P0 - KBLK) >> 5;
+        rs0 = (n0 + RING_OFF) % RING_BLKS;
+        load_stage(it_lo, n0 + 8);
+        store_stage(0, slot_add(rs0, 8));       // (block n0 + 8 is one of the nine loaded below: the same bytes twice)
+        // the nine Rd blocks of the first window: 9 x 256 sixteen-byte chunks, loads first
+        constexpr int NPR = (9 * 256 + NT - 1) / NT;
+        u32x4 pr_[NPR];
+#pragma unroll
+        for (int n = 0; n < NPR; n++) {
+            const int c = tp + n * NT;
+            int d = 32 * n0 + (c >> 3);
+            d = d < 0 ? 0 : (d > M - 1 ? M - 1 : d);
+            pr_[n] = (c < 9 * 256) ? *reinterpret_cast<const u32x4*>(rbase + (size_t)d * p.rd_rs + (c & 7) * 8) : u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int n = 0; n < NPR; n++) {
+            const int c = tp + n * NT;
+            if (c < 9 * 256) {
+                const int slot = slot_add(rs0, c >> 8);
+                *reinterpret_cast<u32x4*>(sR + slot * RBLK_BYTES + soff((c >> 3) & 31, c & 7)) = pr_[n];
+            }
+        }
+    }
+    __syncthreads();
+    if (OWNER) {
+        int l_ = l;
+        asm volatile("" : "+v"(l_));
+        lane_consts(l_);
+    }
+    {                                           // the nine G blocks of the first tile: wave w takes block w, wave 0 also block 8
+        bf16x8 bq[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) bq[ks] = *reinterpret_cast<const bf16x8*>(sQ + QIMG + (rowq ^ (ks << 5)));
+        gblock(w, rs0, bq);
+        if (w == 0) gblock(8, rs0, bq);
+    }
+    load_stage(min(it_lo + 1, it_hi), ((it_lo * QT - P0 - KBLK) >> 5) + 9);                      // stored at the top of the first tile
+    __syncthreads();
+
+#pragma unroll
+    for (int e = 0; e < 2; e++)
+#pragma unroll
+        for (int j = 0; j < 16; j++) { ak[e][j] = 0.f; av[e][j] = 0.f; }
+#pragma unroll
+    for (int v = 0; v < 9; v++) racc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+
     // (the park buffer starts as zeros: the first tile adds them)
     if (FUSED_PARK) {
         for (int i = tid; i < PARK_BYTES / 4; i += NT) sPark[i] = 0.f;
@@ -726,6 +812,22 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
             }
         }
         if (FUSED_PARK) park_add(n0 - 1);       // the block that left the window with the previous tile
+        // (owner mode) which visit of the tile this is -- the key blocks kb_lo .. kb_hi see it (relattn_dq_finish_kernel has the same
+        // formulas); both predicates are wave-uniform.  The carried partial and, for the last visit, the tile's oph pairs are
+        // requested here and consumed at the end of phase B.
+        bool v_first = false, v_last = false;
+        f32x4 part = {0.f, 0.f, 0.f, 0.f};
+        uint32_t ophw[2] = {0u, 0u};
+        if (OWNER) {
+            const int x = I - M - 254 - p0;
+            const int kb_lo = x <= 0 ? 0 : (x + 255) >> 8;
+            const int kb_hi = min(nkb - 1, (I + 31 - p0) >> 8);
+            v_first = bx_ == kb_lo;
+            v_last = bx_ == kb_hi;
+#if FUSED_OWNER_LD_EARLY
+            owner_loads(it, v_first, v_last, part, ophw);
+#endif
+        }
         STAMP(3)
         lds_barrier();
         STAMP(4)
@@ -757,6 +859,9 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
             PRIO_UP();
             if (FUSED_DVDK_LATE && active) dvdk();
             PRIO_DOWN();
+#if !FUSED_OWNER_LD_EARLY
+            if (OWNER) owner_loads(it, v_first, v_last, part, ophw);
+#endif
             UNIT_FENCE();
             STAMP(5)
             f32x4 aw4[2], ar4[2];               // two independent accumulator chains per half of the contraction
@@ -792,7 +897,43 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
             }
             UNIT_FENCE();
             // this tile's partial dq -> slab of this key block (rows = queries 16 ih0 + 4 (l >> 4) + t, column = element 16 eq + (l & 15))
-            {
+            if (OWNER) {
+                // owner mode: carried partial + this visit's piece -> back to the scratch, or (last visit) + phantom term -> dq.  The
+                // pair packing is the bf16 slab store's: the even lane holds (row u, columns c, c + 1), the odd lane (row 2 + u,
+                // columns c - 1, c) -- and the oph pairs were loaded in that layout.
+#pragma unroll
+                for (int t = 0; t < 4; t++) { aw4[0][t] += aw4[1][t]; ar4[0][t] += ar4[1][t]; }
+                const bool odd = (l & 1) != 0;
+                float v[4], nb[4];
+#pragma unroll
+                for (int t = 0; t < 4; t++) v[t] = (aw4[0][t] + ar4[0][t]) + part[t];
+                __builtin_amdgcn_raw_buffer_store_b128(u32x4{__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
+                                                             __builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3])},
+                                                       rs_sc, v_last ? DRD_OOB : l * 16, it * 8192 + w * 1024, 0);
+#pragma unroll
+                for (int t = 0; t < 4; t++)
+                    nb[t] = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v[t]), 0xB1, 0xf, 0xf, true));   // lane ^ 1
+                const int rowl = 16 * ih0 + 4 * g16 + (odd ? 2 : 0);          // this lane's first row of the tile
+                const int vo = v_last ? (4 * g16 + (odd ? 2 : 0)) * p.dq_rs * 2 + ((l & 15) >> 1) * 4 : DRD_OOB;
+                float slo = 0.f, shi = 0.f;                                     // the phantom term of this lane's two (low, high) columns
+#pragma unroll
+                for (int u = 0; u < 2; u++) {
+                    float lo = odd ? nb[2 + u] : v[u], hi = odd ? v[2 + u] : nb[u];
+                    // -scale delta 2^(mph - lse log2 e) oph  (exponent clamped as in relattn_dq_finish_kernel: a query without phantom
+                    // cells has oph = 0, mph = 0, and the factor must stay finite)
+                    const float f = sLse[QT + rowl + u] * __builtin_amdgcn_exp2f(fminf(sLse[2 * QT + rowl + u] + sLse[rowl + u], 126.f));
+                    const float plo = f * __builtin_bit_cast(float, ophw[u] << 16), phi = f * __builtin_bit_cast(float, ophw[u] & 0xffff0000u);
+                    if (has_ph) { lo += plo; hi += phi; slo += plo; shi += phi; }
+                    __builtin_amdgcn_raw_buffer_store_b32((int)pack2bf(lo, hi), rs_dq, vo, (I + 16 * ih0 + u) * p.dq_rs * 2, 0);
+                }
+                cw += (aw4[0][0] + aw4[0][1]) + (aw4[0][2] + aw4[0][3]);
+                cr += (ar4[0][0] + ar4[0][1]) + (ar4[0][2] + ar4[0][3]);
+                // the phantom cells' part of d r_r_bias: column c of this lane = its own low (even lane) or high (odd lane) sums + the
+                // neighbour's of the same kind
+                const float want = odd ? slo : shi;                           // what the neighbour needs from this lane
+                const float got = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, want), 0xB1, 0xf, 0xf, true));
+                if (has_ph && v_last) cr += (odd ? shi : slo) + got;
+            } else {
 #pragma unroll
                 for (int t = 0; t < 4; t++) { aw4[0][t] += aw4[1][t]; ar4[0][t] += ar4[1][t]; }
                 const int x = I - M - 254 - p0;
@@ -875,21 +1016,16 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
         const int n0_end = ((it_hi + 1) * QT - P0 - KBLK) >> 5;
         if (FUSED_PARK && it_lo <= it_hi) { park_read(); park_add(n0_end - 1); }
     }
-    drd_flush_direct(((it_hi + 1) * QT - P0 - KBLK) >> 5);
+    // (owner mode: the epilogue's lane addresses from a lane id hipcc cannot see through -- formed ahead of the key-block loop they
+    // were twenty more registers live across it, and spilled)
+    int le = l;
+    if (OWNER) asm volatile("" : "+v"(le));
+    drd_flush_direct(((it_hi + 1) * QT - P0 - KBLK) >> 5, le);
     STAMP(13)
-    STAMP_FLUSH
 
-    // ---- epilogue: bias gradients (stored keys' part), dk, dv
-    {
-        float a = cw, c = cr;
-        a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
-        c += __shfl_xor(c, 16, 64); c += __shfl_xor(c, 32, 64);
-        if (l < 16) {
-            atomicAdd(p.d_rwb + h * 64 + 16 * eq + l, a);
-            atomicAdd(p.d_rrb + h * 64 + 16 * eq + l, c);
-        }
-    }
+    // ---- epilogue of a key block: dk, dv
     if (kok) {
+        const int r = le & 31, hh = le >> 5;
         const float fk = 1.f / p.scale_log2e, fv = 1.f / p.scale;      // dK was accumulated against scale*log2(e)*Qw, dV against scale*dO
         const size_t srow = (size_t)(Pw + r - p0);
         bf16_t* dkp = p.dk + (size_t)b * p.dkv_bs + srow * p.dkv_rs + (size_t)h * 64;
@@ -904,6 +1040,19 @@ __global__ __launch_bounds__(512, 1) void relattn_bwd_fused_kernel(FusedP p) {
                 *reinterpret_cast<u32x2*>(dkp + e0) = wk;
                 *reinterpret_cast<u32x2*>(dvp + e0) = wv;
             }
+        }
+    }
+    } while (OWNER && ++bx_ < nkb);
+    STAMP_FLUSH
+
+    // ---- epilogue of the workgroup: bias gradients (per-block mode: the stored keys' part; owner mode: the phantom cells' too)
+    {
+        float a = cw, c = cr;
+        a += __shfl_xor(a, 16, 64); a += __shfl_xor(a, 32, 64);
+        c += __shfl_xor(c, 16, 64); c += __shfl_xor(c, 32, 64);
+        if (l < 16) {
+            atomicAdd(p.d_rwb + h * 64 + 16 * eq + l, a);
+            atomicAdd(p.d_rrb + h * 64 + 16 * eq + l, c);
         }
     }
 }
@@ -1043,6 +1192,17 @@ extern "C" int mxl_debug_fused_stamps(unsigned long long* host_out16) {
 }
 #endif
 
+// Owner mode runs B H equally long workgroups, one per CU at a time: ceil(B H / CUs) rounds, the last one partly empty.  It is
+// chosen when the tail efficiency B H / (rounds * CUs) reaches FUSED_OWNER_MIN_FILL; below that the per-block grid (Kc / 256 times
+// as many, shorter workgroups) fills the chip better than the finishing pass costs.  (ops.fused_dq_owner_mode states the same rule.)
+#ifndef FUSED_OWNER_MIN_FILL
+#define FUSED_OWNER_MIN_FILL 0.9
+#endif
+static bool fused_owner_fills(int B, int H, int cus) {
+    const long long wgs = (long long)B * H, rounds = (wgs + cus - 1) / cus;
+    return (double)wgs >= FUSED_OWNER_MIN_FILL * (double)(rounds * cus);
+}
+
 extern "C" size_t mxl_relattn_bwd_fused_ws_bytes(int B, int T, int H, int dh, int M) {
     if (B <= 0 || T <= 0 || H <= 0 || dh != 64 || M <= 0) return 0;
     return (size_t)((M + KBLK - 1) / KBLK + 1) * (size_t)B * T * H * 64 * sizeof(slab_t);     // a query tile's M + 31 keys touch at most that many key blocks
@@ -1071,11 +1231,18 @@ extern "C" int mxl_relattn_bwd_fused(const void* q, const void* k, const void* v
     hipStream_t s = (hipStream_t)stream;
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&relattn_bwd_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&relattn_bwd_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+        if (e == hipSuccess)
+            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&relattn_bwd_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
     const bool delta_ready = (defer_finish & 2) != 0;       // the caller has filled `delta` (mxl_gemm_bf16_headdot)
+    // dq mode.  A deferred finish means slabs; bit 2 forces owner mode, bit 3 per-block mode; otherwise owner mode when its B H
+    // workgroups (one per CU at a time) fill the usable CUs without a long tail (fused_owner_fills).
+    MXL_CHECK_ARG((defer_finish & 12) != 12);
+    const bool owner = (defer_finish & 1) ? false : (defer_finish & 4) ? true : (defer_finish & 8) ? false
+                                                                               : fused_owner_fills(B, H, mxl_usable_cus());
     defer_finish &= 1;
     if (!delta_ready) {
         mxl_kt::Scope kt(MXL_KT_RELATTN_DELTA, s);
@@ -1090,12 +1257,15 @@ extern "C" int mxl_relattn_bwd_fused(const void* q, const void* k, const void* v
     p.q_bs = q_bs; p.kv_bs = kv_bs; p.o_bs = o_bs; p.dkv_bs = dkv_bs; p.slab_stride = (long long)B * T * H * 64;
     p.q_rs = q_rs; p.kv_rs = kv_rs; p.rd_rs = rd_rs; p.o_rs = o_rs; p.dkv_rs = dkv_rs; p.drd_ld = drd_ld;
     p.scale = scale; p.scale_log2e = scale * LOG2E;
+    p.dq = (bf16_t*)dq; p.dq_bs = dq_bs; p.dq_rs = dq_rs;
+    p.oph = (Kc < M + T) ? (const bf16_t*)oph : nullptr; p.mph = mph;
     {
         mxl_kt::Scope kt(MXL_KT_RELATTN_FUSED, s);
-        hipLaunchKernelGGL(relattn_bwd_fused_kernel, dim3((Kc + KBLK - 1) / KBLK, H, B), dim3(512), SMEM, s, p);
+        if (owner) hipLaunchKernelGGL(relattn_bwd_fused_kernel<true>, dim3(1, H, B), dim3(512), SMEM, s, p);
+        else hipLaunchKernelGGL(relattn_bwd_fused_kernel<false>, dim3((Kc + KBLK - 1) / KBLK, H, B), dim3(512), SMEM, s, p);
     }
     MXL_LAUNCH_CHECK();
-    if (defer_finish) return MXL_OK;
+    if (defer_finish || owner) return MXL_OK;            // owner mode has finished dq and d_r_r_bias in the kernel
     return mxl_relattn_dq_finish(ws, oph, mph, lse, delta, dq, d_r_r_bias, B, T, H, dh, M, Kc, o_bs, o_rs, dq_bs, dq_rs, scale, stream);
 }
 

@@ -654,7 +654,37 @@ def phantom_sum_applies(*, T, dh, M, Kc) -> bool:
 
 def set_reserved_cus(k: int) -> None:
     """compute units the persistent GEMM grids leave free (mxl_set_reserved_cus; dist.GradSync sets it from MXL_RESERVE_CUS)"""
+    global _RESERVED_CUS
     check(lib().mxl_set_reserved_cus(int(k)), 'mxl_set_reserved_cus')
+    _RESERVED_CUS = int(k)
+
+
+_RESERVED_CUS = 0
+_N_CUS = {}
+FUSED_OWNER_MIN_FILL = 0.9        # (csrc/relattn_bwd_fused.hip has the same constant for callers of the C ABI)
+
+
+def fused_dq_owner_mode(B, H, cus, reserved=0, env=None) -> bool:
+    """Which form of mxl_relattn_bwd_fused forms dq: True = owner mode (one workgroup per (sequence, head) walks every key block
+    and finishes dq itself, no slabs and no finishing pass), False = per-block mode (one workgroup per key block, bf16 slabs summed by
+    mxl_relattn_dq_finish).  Owner mode runs B H equally long workgroups, one per compute unit at a time, so it is chosen when they
+    fill the usable units (`cus` minus the `reserved` ones of set_reserved_cus, at least 8) without a long tail: tail efficiency
+    B H / (ceil(B H / usable) usable) >= FUSED_OWNER_MIN_FILL.  `env` (a mapping, e.g. os.environ): MXL_FUSED_OWNER = 0 / 1 overrides
+    the rule, for A/B runs.  Pure: no device, no library."""
+    ov = (env or {}).get('MXL_FUSED_OWNER')
+    if ov in ('0', '1'):
+        return ov == '1'
+    usable = max(int(cus) - int(reserved), 8)
+    wgs = int(B) * int(H)
+    rounds = (wgs + usable - 1) // usable
+    return wgs >= FUSED_OWNER_MIN_FILL * rounds * usable
+
+
+def _n_cus(device) -> int:
+    key = str(device)
+    if key not in _N_CUS:
+        _N_CUS[key] = int(torch.cuda.get_device_properties(device).multi_processor_count)
+    return _N_CUS[key]
 
 
 def fused_bwd_applies(*, T, dh, M, Kc, B=None, H=None) -> bool:
@@ -907,21 +937,30 @@ def gemm_headdot(a, b, c, M, N, K, o, T, delta, lda=None, ldb=None, ldc=None, ld
 
 def relattn_bwd_fused(q, k, v, rd, r_w_bias, r_r_bias, out, dout, lse, delta, dq, dk, dv, d_rd, d_rwb, d_rrb, ws, qr_buf, *,
                       B, T, H, dh, M, Kc, q_bs, q_rs, kv_bs, kv_rs, rd_rs, o_bs, o_rs, dq_bs, dq_rs, dkv_bs, dkv_rs,
-                      scale=None, oph=None, mph=None, defer_drd=False, ph_buf=None, ph_ready=False, delta_ready=False):
+                      scale=None, oph=None, mph=None, defer_drd=False, ph_buf=None, ph_ready=False, delta_ready=False, dq_mode=None):
     """Backward of relattn_fwd in one pass over the score cells (mxl_relattn_bwd_fused): dq, dk, dv written, d_rd (M, H*dh) f32 /
     d_rwb / d_rrb accumulated.  With zero memories (Kc < M + T) `oph` / `mph` must come from relattn_fwd(..., oph_all=True), and
     the phantom cells' part of d_rd is added by mxl_relattn_drd_phantom from per-tile records (`ph_buf`,
     mxl_relattn_drd_phantom_ws_bytes bytes; ph_ready: relattn_fwd(..., ph_buf=) has filled them, otherwise
     mxl_relattn_drd_phantom_prep does; without `ph_buf` one scratch per shape is cached; `qr_buf` is no longer used by this path);
-    their part of d_rrb comes out of the dq finishing kernel.  delta_ready: `delta` was filled by gemm_headdot."""
+    their part of d_rrb comes out of the dq finishing kernel (per-block mode) or of the fused kernel itself (owner mode).
+    delta_ready: `delta` was filled by gemm_headdot.  dq_mode: 'owner' / 'slabs' forces the form that produces dq; None leaves it
+    to fused_dq_owner_mode (MXL_FUSED_OWNER = 0 / 1, read at every call, overrides that rule)."""
     scale = scale if scale is not None else 1.0 / math.sqrt(dh)
     d = H * dh
+    if dq_mode is None:
+        owner = fused_dq_owner_mode(B, H, _n_cus(q.device), _RESERVED_CUS, os.environ)
+    else:
+        if dq_mode not in ('owner', 'slabs'):
+            raise ValueError(f'dq_mode must be None, "owner" or "slabs", not {dq_mode!r}')
+        owner = dq_mode == 'owner'
+    mode_bits = (2 if delta_ready else 0) | (4 if owner else 8)
     # (the slab sum on a side stream beside the phantom cells' dRd kernel measured 7.16 ms against 7.12 ms in sequence -- the HBM-bound
     # sum fills the chip by itself -- and left dq / d_rrb incomplete until the deferred call: removed in round 5)
     check(lib().mxl_relattn_bwd_fused(_p(q), _p(k), _p(v), _p(rd), _p(r_w_bias), _p(r_r_bias), _p(out), _p(dout), _p(lse), _p(delta),
                                       _p(dq), _p(dk), _p(dv), _p(d_rd), d_rd.stride(0), _p(d_rwb), _p(d_rrb), _p(oph), _p(mph), _p(ws),
                                       B, T, H, dh, M, Kc, q_bs, q_rs, kv_bs, kv_rs, rd_rs, o_bs, o_rs, dq_bs, dq_rs, dkv_bs, dkv_rs,
-                                      float(scale), 2 if delta_ready else 0, _stream()), 'mxl_relattn_bwd_fused')
+                                      float(scale), mode_bits, _stream()), 'mxl_relattn_bwd_fused')
 
     def phantom():
         if Kc < M + T:
