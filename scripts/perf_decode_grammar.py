@@ -35,7 +35,7 @@ import sys
 import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from symbolic_music_generation_amd.generate import XLDecoderLanes, check_grammar
+from symbolic_music_generation_amd.generate import XLDecoderLanes, check_grammar, rules_config
 from symbolic_music_generation_amd.transformer_xl import MyTransfoXLConfig, MyTransfoXLLMHeadModel
 from symbolic_music_generation_amd.vocab import MusicVocabulary
 
@@ -77,9 +77,10 @@ ids = prompts()
 samp = dict(do_sample=True, top_k=8, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0)
 
 
-def window(dec, g, steps, stop=None, n_bars=None, in_key=None, register=None):
-    """ms per replayed step over `steps` steps right after the prompt pass (ring slots Tp .. Tp + 20 + steps)"""
-    n = dec.begin(ids, L, samp, use_graph=True, grammar=g, stop=stop, n_bars=n_bars, in_key=in_key, register=register)
+def window(dec, g, steps, **rules):
+    """ms per replayed step over `steps` steps right after the prompt pass (ring slots Tp .. Tp + 20 + steps); rules: the arm's
+    keywords of generate.rules_config beside the grammar"""
+    n = dec.begin(ids, L, samp, use_graph=True, rules=rules_config(batch=B, vocab_size=V, grammar=g, **rules))
     assert n >= steps + 20
     for _ in range(20):
         dec.replay_once()
@@ -95,10 +96,10 @@ def window(dec, g, steps, stop=None, n_bars=None, in_key=None, register=None):
 
 def bars_arms():
     """the --n-bars comparison (module docstring)"""
-    from symbolic_music_generation_amd.generate import bar_count_config, bars_after_prompt, check_bar_lengths, stop_config
+    from symbolic_music_generation_amd.generate import bars_after_prompt, check_bar_lengths, stop_config
     g = vocab.grammar(bar_budget=True)
     stop = stop_config(vocab.t2i('</s>'), vocab.t2i('[PAD]'))
-    arms = {'budget': {}, 'budget+eos': dict(stop=stop[:2] + (L,)), 'bars': dict(stop=stop, n_bars=bar_count_config(N_BARS, B, g, stop))}
+    arms = {'budget': {}, 'budget+eos': dict(stop=stop[:2] + (L,)), 'bars': dict(stop=stop, n_bars=N_BARS)}
     assert check_bar_lengths(ids, g).tolist() == [-1] * B
     if ONLY:
         dec = XLDecoderLanes(model.engine, B, L, seed=5, lanes=2)
@@ -160,10 +161,10 @@ def key_arms():
 
 def register_arms():
     """the --register comparison (module docstring)"""
-    from symbolic_music_generation_amd.generate import check_register, register_config
+    from symbolic_music_generation_amd.generate import check_register
     rule = vocab.register_rule()
     bounds = dict(melody_range=(55, 84), bass_range=(36, 60), bass_below=1)
-    arms = {'plain': {}, 'register': dict(register=register_config(rule, batch=B, vocab_size=V, **bounds))}
+    arms = {'plain': {}, 'register': dict(register=rule, **bounds)}
     if ONLY:
         dec = XLDecoderLanes(model.engine, B, L, seed=5, lanes=2)
         print(f'{ONLY}: {window(dec, None, 50, **arms[ONLY]):.3f} ms per step (50 steps)', flush=True)

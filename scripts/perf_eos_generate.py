@@ -18,7 +18,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from symbolic_music_generation_amd.transformer_xl import MyTransfoXLConfig, MyTransfoXLLMHeadModel
-from symbolic_music_generation_amd.generate import XLDecoder, finish_at_eos
+from symbolic_music_generation_amd.generate import NO_RULES, XLDecoder, finish_at_eos
 
 dev = torch.device('cuda:0')
 V, M, B, Tp, L = 1190, 2048, 64, 256, 2048
@@ -44,7 +44,7 @@ def step_ms(live: bool, n: int = 200) -> float:
     """ms per replayed decode step of one 64-row decoder with the stop state on, right after the prompt pass (ring slots
     Tp .. Tp + n), every row live or every row finished"""
     dec = XLDecoder(model.engine, B, L, seed=5)
-    steps = dec.begin(ids, L, samp, use_graph=True, stop=(V + 1, 0, 0))    # an eos no row can emit
+    steps = dec.begin(ids, L, samp, use_graph=True, rules=NO_RULES.with_stop((V + 1, 0, 0)))    # an eos no row can emit
     assert steps >= n
     if not live:
         dec.unfinished.zero_()

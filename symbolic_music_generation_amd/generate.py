@@ -477,6 +477,62 @@ def melody_config(melody, batch: int, grammar, stop: Optional[tuple], n_bars=Non
     return plan if r == 1 else MelodyPlan(rule, [g for g in guides for _ in range(r)], [x for x in bars for _ in range(r)])
 
 
+class RulePlan(namedtuple('RulePlan', 'stop grammar n_bars in_key keys melody register B', defaults=(None,) * 8)):
+    """The rules of one generation as every layer between `generate` and RowRules.start hands them down (rules_config builds it):
+    `stop` = (eos, pad, min_length) or None, `grammar`, `n_bars` (None or (B,) int32 on the CPU), `in_key` with `keys` (None or (B,)
+    int32), `melody` (None or a MelodyPlan), `register` (None or a RegisterPlan), and `B`, the rows the per-row fields were built
+    for (None: no field is per row)."""
+    __slots__ = ()
+
+    def rows(self, lo: int, hi: int) -> 'RulePlan':
+        """the plan of rows lo..hi-1: every per-row field cut to them (how XLDecoderLanes hands each lane its own)"""
+        cut = lambda x: None if x is None else x[lo:hi]
+        part = lambda x: None if x is None else x.rows(lo, hi)
+        return self._replace(n_bars=cut(self.n_bars), keys=cut(self.keys), melody=part(self.melody), register=part(self.register),
+                             B=None if self.B is None else hi - lo)
+
+    def with_stop(self, stop: Optional[tuple]) -> 'RulePlan':
+        """the same rules under another stop group (the device searches keep (eos, pad, 0) on)"""
+        return self._replace(stop=stop)
+
+
+NO_RULES = RulePlan()
+
+
+def rules_config(*, batch: int, vocab_size: int, stop: Optional[tuple] = None, grammar=None, n_bars=None, in_key=None, key=None,
+                 melody=None, register=None, melody_range=None, bass_range=None, bass_below=None, repeat: int = 1) -> RulePlan:
+    """The rules arguments of one `generate` call over `batch` prompts -> the RulePlan of its batch * repeat rows (`repeat` =
+    num_return_sequences, or the rows a search keeps per prompt: every prompt's value repeated, as the prompts are).  The one place
+    the arguments are checked, in this order: check_grammar_args, melody_config, bar_count_config, key_config, register_config, which
+    say what each refuses.
+    stop = (eos, pad, min_length) (stop_config) or None: HF greedy_search / sample stopping -- a row that emits eos is finished and
+    emits pad from then on, the call ends once every row has finished, and the output is cut to the width of the longest row
+    (finish_at_eos); min_length bars eos below that width.
+    grammar (a grammar.TokenGrammar, e.g. `tokenizer.grammar()`): every row may only emit tokens its grammar state allows; the
+    state lives on the device and moves inside the sampler launch of the captured step.  The prompts must obey the grammar.
+    A grammar with a bar budget (`tokenizer.grammar(bar_budget=True)`) also keeps every channel of every generated bar exactly as
+    long as the row's time signature: the free slots of the open channel live and move beside the state.
+    n_bars (an int or one per prompt, negative = no limit; needs grammar and an eos): every row opens exactly that many further
+    bars -- the bar open at the end of its prompt is finished and not counted -- and, under a bar budget, emits eos when the last
+    of them is full.  Without a budget the rule bars a further bar and an early eos but cannot force the end.
+    in_key (a grammar.KeyRule, e.g. `tokenizer.key_rule()`; needs no grammar): a row whose key is known emits only pitches of
+    that key.  key=None: every row's key is the last key token of its prompt (none: the row is unconstrained); key = a key name
+    or ordinal, or one per prompt with None / -1 = unconstrained, overrides the prompts.  A generated key token sets the row's key.
+    melody (one guide or one per prompt, None = unguided, or a MelodyPlan; needs grammar and an eos, takes no n_bars or
+    min_length): each guide is the `<bar> <melody> ... <bass>` spans of its bars (`tokenizer.melody_guide`); the row is fed them bar
+    by bar inside the sampler launch and chooses the bass under each, then ends: the plan's bar counts become n_bars.
+    register (a grammar.RegisterRule, e.g. `tokenizer.register_rule()`, or a RegisterPlan; needs no grammar) with melody_range /
+    bass_range (one inclusive pair of MIDI numbers or one per prompt, None = unconstrained) and bass_below (None or g >= 0
+    semitones): the pitches of every part stay inside its bounds, and the bass at least g under the lowest melody note of its bar."""
+    check_grammar_args(grammar, vocab_size, stop)
+    guide = melody_config(melody, batch, grammar, stop, n_bars, repeat)
+    bars = bar_count_config(n_bars, batch, grammar, stop, repeat) if guide is None else guide.n_bars
+    keys = key_config(in_key, key, batch, vocab_size, repeat)
+    span = register_config(register, melody_range, bass_range, bass_below, batch, vocab_size, repeat)
+    per_row = any(x is not None for x in (bars, keys, guide, span))
+    return RulePlan(stop, grammar, bars, in_key, keys, guide, span, batch * int(repeat) if per_row else None)
+
+
 def check_bar_count_start(grammar, n_bars: torch.Tensor, gstate: torch.Tensor):
     """rows asked for n_bars = 0 whose prompt stops where only a bar can follow (BarCount.needs_bar: the music grammar's header
     states -- no bar is open yet, and a song has one): MusicXLError naming the row, since every token would be barred there.
@@ -520,8 +576,8 @@ class RowRules:
     under `register`, a grammar.RegisterRule, with the generation's `gap`), each (B,) -- then gbad (2, B), the first prompt
     column that breaks the grammar / the budget, and alive (1,), the live-row count.  The guide group also keeps two tables of its
     own here, `guide` (B, ld) int32 and `glen` (B,) int32, refilled by every `start` and regrown only for a longer guide, so that a
-    captured step finds the next generation's guides where it found the last one's.  A further rule is a row here, a line in `start`
-    and a key in `kwargs` / `graph_key`."""
+    captured step finds the next generation's guides where it found the last one's.  A further rule is a row here, a field in RulePlan,
+    a line in rules_config and `start`, and a key in `kwargs` / `graph_key` ("adding a rule")."""
     WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey', 'gpos', 'gforce', 'grange', 'gpart', 'gfloor')
     STATE = WORDS + ('alive',)
 
@@ -535,7 +591,7 @@ class RowRules:
         self.unfinished.fill_(1)
         self.gleft.fill_(-1)
         self.gkey.fill_(-1)
-        self.stop = self.grammar = self.n_bars = self.in_key = self.melody = self.plan = self.register = None
+        self.stop = self.grammar = self.n_bars = self.in_key = self.melody = self.melody_plan = self.register = None
         self.bars, self.gap = False, -1
         self._reset_register()
         self.guide = torch.zeros(batch, 64, device=dev, dtype=torch.int32)
@@ -547,18 +603,16 @@ class RowRules:
         self.gpart.zero_()
         self.gfloor.fill_(NO_FLOOR)
 
-    def start(self, ids: torch.Tensor, Tp: int, vocab_size: int, stop: Optional[tuple], grammar, n_bars: Optional[torch.Tensor],
-              in_key=None, keys: Optional[torch.Tensor] = None, melody: Optional[MelodyPlan] = None,
-              register: Optional[RegisterPlan] = None):
-        """the rules of a new generation over the prompts in columns 0..Tp-1 of ids (ids < 0: left pads, skipped): every row live,
-        its grammar state and, under a bar budget, its bar length and free slots after its prompt computed on the device, gleft =
-        n_bars ((B,) int32 from bar_count_config, or None: no bar count).  in_key (a grammar.KeyRule, or None: no key rule): gkey =
-        keys ((B,) int32 from key_config), or, without them, the last key token of every row's prompt, found on the device (-1 in a
-        row without one); the prompt's pitches are not judged.  melody (a MelodyPlan from melody_config, or None: no guide): the
-        rows' guides and their lengths go to the device tables, every row starts free at guide index 0 -- a bar open at the end of
-        the prompt is finished freely, the guide engages at the next bar -- and n_bars must be the plan's.  register (a RegisterPlan
-        from register_config, or None: no register rule): grange = the plan's bounds, gpart and gfloor = the open part and the floor
-        every row's prompt leaves it in, found on the device; the prompt's pitches are not judged."""
+    def start(self, ids: torch.Tensor, Tp: int, vocab_size: int, plan: RulePlan):
+        """the rules of a new generation (`plan`, from rules_config) over the prompts in columns 0..Tp-1 of ids (ids < 0: left pads,
+        skipped): every row live, its grammar state and, under a bar budget, its bar length and free slots after its prompt computed
+        on the device, gleft = the plan's n_bars (None: no bar count).  Under in_key gkey = the plan's keys or, without them, the last
+        key token of every row's prompt, found on the device (-1 in a row without one).  Under melody the rows' guides and their
+        lengths go to the device tables and every row starts free at guide index 0 -- a bar open at the end of the prompt is finished
+        freely, the guide engages at the next bar -- and n_bars must be the guides' own.  Under register grange = the plan's bounds,
+        gpart and gfloor = the open part and the floor every row's prompt leaves it in, found on the device.  No rule judges the
+        prompt's pitches.  A plan built for another decoder (row count, vocabulary, grammar) raises."""
+        stop, grammar, n_bars, in_key, keys, melody, register = plan[:7]
         check_grammar_args(grammar, vocab_size, stop)
         if register is not None and (register.rule.vocab_size != int(vocab_size) or register.B != self.B):
             raise MusicXLError(f'the register rule must span the model\'s {int(vocab_size)} tokens and hold one entry per row '
@@ -572,7 +626,7 @@ class RowRules:
                                    or n_bars is None or n_bars.tolist() != melody.n_bars.tolist()):
             raise MusicXLError('melody needs the grammar its guide rule belongs to, one guide entry per row and n_bars = the bars '
                                'of the guides (melody_config)')
-        self.plan, self.melody = melody, None if melody is None else melody.rule
+        self.melody_plan, self.melody = melody, None if melody is None else melody.rule
         self.gpos.zero_()
         self.gforce.zero_()
         if melody is not None:
@@ -614,11 +668,11 @@ class RowRules:
         """after `start`: raises for a prompt that breaks the grammar or the bar budget, or that leaves a row asked for 0 bars where
         only a bar can follow, or for a guide that does not fit the bar length of its row (one device read, one more only if some
         row has n_bars = 0)"""
-        if self.grammar is not None and self.plan is not None and self.grammar.budget is not None:
+        if self.grammar is not None and self.melody_plan is not None and self.grammar.budget is not None:
             host, n = self.buf.cpu(), len(self.WORDS)                 # the words and gbad in the one read
             raise_on_bad_prompt(self.grammar, ids, host[n * self.B:(n + 2) * self.B].view(2, self.B))
             at = self.WORDS.index('gbar') * self.B
-            self.plan.check_budget(self.grammar, host[at:at + self.B].tolist())
+            self.melody_plan.check_budget(self.grammar, host[at:at + self.B].tolist())
         elif self.grammar is not None:
             raise_on_bad_prompt(self.grammar, ids, self.gbad)
         if self.bars:
@@ -880,19 +934,17 @@ def run_until_finished(decoders, n: int, chunk: int = STOP_CHUNK) -> list:
     return issued
 
 
-def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool, n_pad, stop, stop_chunk,
-                 grammar, n_bars=None, in_key=None, keys=None, melody=None, register=None) -> torch.Tensor:
+def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool, n_pad, stop_chunk,
+                 rules: RulePlan) -> torch.Tensor:
     """The body of `generate` for one decoder (lanes = [dec], streams = [None]) or for an XLDecoderLanes with its lanes and their
-    streams: `dec.begin`, then every remaining step through `dec.replay_once` -- or, with stop = (eos, pad, min_length), each lane
-    on its own until its rows have finished (run_until_finished) -- then the lanes' rows in order, cut to the width of the longest
-    lane and right-filled with pad where a lane stopped earlier.  Sets `steps_run` on every lane and on dec (the most of any
-    lane).  The prompt columns of left-padded prompts (n_pad) come back as given.  n_bars: None or one int32 per row
-    (bar_count_config); each lane takes its rows' entries.  in_key / keys: the key rule and None or one int32 per row (key_config),
-    handed on the same way, as are melody (a MelodyPlan or None) and register (a RegisterPlan or None)."""
-    Tp = prompt.shape[1]
+    streams: `dec.begin` under `rules`, then every remaining step through `dec.replay_once` -- or, with a stop group in the plan,
+    each lane on its own until its rows have finished (run_until_finished) -- then the lanes' rows in order, cut to the width of
+    the longest lane and right-filled with pad where a lane stopped earlier.  Sets `steps_run` on every lane and on dec (the most
+    of any lane).  The prompt columns of left-padded prompts (n_pad) come back as given."""
+    Tp, stop = prompt.shape[1], rules.stop
     if max_length - Tp <= 0:
         return prompt[:, :max_length]
-    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, stop, grammar, n_bars, in_key, keys, melody, register)
+    n = dec.begin(prompt, max_length, sampling, use_graph, n_pad, rules)
     if stop is None:
         for _ in range(n):
             dec.replay_once()
@@ -916,6 +968,45 @@ def decode_lanes(dec, lanes, streams, prompt: torch.Tensor, max_length: int, sam
     if n_pad is not None:
         out[:, :Tp].copy_(prompt)
     return out
+
+
+class RuledGenerate:
+    """`generate` and `run` of XLDecoder, XLDecoderLanes and rf_generate.RFDecoder: greedy decoding and sampling under the rules.
+    A decoder brings `begin` / `replay_once`, `B`, and `lanes` with their `streams` where it is more than one decoder."""
+
+    def _admit(self, max_length: int):
+        """what a decoder refuses before the rules are judged"""
+
+    def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
+                 top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
+                 typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None,
+                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
+                 stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None, register=None,
+                 melody_range=None, bass_range=None, bass_below=None, stop: Optional[tuple] = None) -> torch.Tensor:
+        """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
+        [OMIT], SURVEY 3.4) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (XLDecoder.prefill);
+        the prompt columns, pads included, come back as given.  use_graph: one captured step replayed per token, where the decoder
+        captures one (RFDecoder does not).
+        eos_token_id (opt-in) with pad_token_id (default: eos) and min_length, or the group whole as stop = (eos, pad, min_length)
+        (stop_config): rows finish at eos.  The decode steps are replayed in chunks of `stop_chunk` with the live-row count read back
+        one chunk late (run_until_finished): no per-step host round trip.  Over lanes every lane stops on its own; the output is the
+        lanes' rows cut to the common width and right-filled with pad where a lane stopped earlier.
+        grammar, n_bars, in_key / key, melody, register with melody_range / bass_range / bass_below: the rules, one value per row
+        where they are per row, as rules_config describes and checks them; each lane keeps the words of its own rows."""
+        self._admit(max_length)
+        rules = rules_config(batch=self.B, vocab_size=getattr(self, 'lanes', [self])[0].eng.cfg.vocab_size,
+                             stop=stop_config(eos_token_id, pad_token_id, min_length) if stop is None else stop, grammar=grammar,
+                             n_bars=n_bars, in_key=in_key, key=key, melody=melody, register=register, melody_range=melody_range,
+                             bass_range=bass_range, bass_below=bass_below)
+        return self.run(prompt, max_length, sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), rules,
+                        use_graph, n_pad, stop_chunk)
+
+    @torch.no_grad()
+    def run(self, prompt: torch.Tensor, max_length: int, sampling: dict, rules: RulePlan = NO_RULES, use_graph: bool = True,
+            n_pad: Optional[torch.Tensor] = None, stop_chunk: int = STOP_CHUNK) -> torch.Tensor:
+        """`generate` from a finished plan: sampling from sampling_config, rules from rules_config over this decoder's B rows"""
+        return decode_lanes(self, getattr(self, 'lanes', [self]), getattr(self, 'streams', [None]), prompt, max_length, sampling,
+                            use_graph, n_pad, stop_chunk, rules)
 
 
 BEAM_MAX = 16            # beams per item of mxl_beam_step / mxl_beam_reorder
@@ -984,7 +1075,7 @@ class ContrastiveStore:
             ops.row_inv_norm(self.ctx[b, :Tp], self.inv[b, :Tp], Tp)
 
 
-class XLDecoder:
+class XLDecoder(RuledGenerate):
     def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77):
         self.eng = engine
         c = engine.cfg
@@ -1050,26 +1141,15 @@ class XLDecoder:
         self.graph = None
 
     # ---------------------------------------------------------------- prompt
-    def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None,
-                grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None,
-                melody: Optional[MelodyPlan] = None, register: Optional[RegisterPlan] = None):
+    def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, rules: RulePlan = NO_RULES):
         """Whole prompt through the training-shape kernels with zero mems (upstream first step), rings filled from the
         per-layer qkv buffers, first new token sampled from the last position.
         n_pad: (B,) int32 device tensor, left-padded prompts: the first n_pad[b] columns of row b are pads.  Their K / V are zero
         in every layer (= extra zero-memory slots, so each row computes what it computes alone), they are embedded as id 0 and
         held as -1 in `ids`, which the samplers' repetition penalty skips.
-        stop: (eos, pad, min_length) or None (stop_config); every row starts live, and the first token sampled here counts.
-        grammar: a grammar.TokenGrammar or None; every row's state after its prompt is computed on the device (pads skipped), and a
-        prompt that breaks the grammar raises.  With a bar budget the same holds for the rows' bar lengths and free slots, and a
-        prompt that overfills or underfills a bar raises.
-        n_bars: None, or (B,) int32 from bar_count_config: the bars every row may still open (the grammar's bar count); it is the
-        start value of `gleft`, which the sampler launches move.
-        in_key: a grammar.KeyRule or None; keys: None (every row starts in the key of its prompt, found on the device, pads
-        skipped) or (B,) int32 from key_config; the start value of `gkey`, which a generated key token moves.
-        melody: None or a MelodyPlan from melody_config (with n_bars = its bar counts): the rows' guides go to the device, and a
-        guide that does not fit its row's bar length raises with the prompt checks.
-        register: None or a RegisterPlan from register_config: the rows' bounds go to the device, and the open part and the floor
-        every prompt leaves its row in are found there (one more scan launch)."""
+        rules: the RulePlan of the generation (rules_config; RowRules.start sets the rows' words from it on the device, pads
+        skipped).  Every row starts live, and the first token sampled here counts.  A prompt that breaks the grammar, overfills or
+        underfills a bar under a bar budget, or a guide that does not fit its row's bar length raises (RowRules.check_prompt)."""
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
@@ -1084,7 +1164,7 @@ class XLDecoder:
             pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
             self.ids[:, :Tp].masked_fill_(pad, -1)
             x = x.masked_fill(pad, 0)
-        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars, in_key, keys, melody, register)
+        self.rules.start(self.ids, Tp, c.vocab_size, rules)
         sink_kc, sink_vc = self.kc, self.vc
 
         def kv_sink(l, qkv):
@@ -1213,11 +1293,10 @@ class XLDecoder:
 
     # ---------------------------------------------------------------- beam search on the device (beam_search_device below)
     def beam_begin(self, prompt: torch.Tensor, max_length: int, nb: int, eos: int, pad: int, length_penalty: float,
-                   early_stopping: bool, use_graph: bool = True, grammar=None, n_bars: Optional[torch.Tensor] = None, in_key=None,
-                   keys: Optional[torch.Tensor] = None, ng: int = 1, diversity_penalty: float = 0.0, sample: bool = False,
-                   top_k: Optional[int] = None, top_p: Optional[float] = None, temperature: float = 1.0,
-                   typical_p: Optional[float] = None, register: Optional[RegisterPlan] = None) -> int:
-        """prompt pass (one row per beam, the rules started as `prefill` starts them, with the stop group (eos, pad, 0) always on:
+                   early_stopping: bool, use_graph: bool = True, rules: RulePlan = NO_RULES, ng: int = 1,
+                   diversity_penalty: float = 0.0, sample: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None,
+                   temperature: float = 1.0, typical_p: Optional[float] = None) -> int:
+        """prompt pass (one row per beam, `rules` started as `prefill` starts them, with the stop group (eos, pad, 0) always on:
         its `unfinished` word is how mxl_beam_step retires dead rows and done items) + the scorer's state + (use_graph) capture of
         one beam step (`_capture`; the hypothesis store, the running scores and the log-probabilities are this step's own state);
         returns the number of `replay_once()` calls before the last selection (`beam_select`).
@@ -1235,7 +1314,7 @@ class XLDecoder:
                                '>= 0')
         if sample and (ng != 1 or self.eng.cfg.vocab_size > 2048):
             raise MusicXLError('beam-sample on the device takes one group and a vocabulary of at most 2048 tokens')
-        self.prefill(prompt, None, None, (int(eos), int(pad), 0), grammar, n_bars, in_key, keys, None, register)
+        self.prefill(prompt, None, None, rules.with_stop((int(eos), int(pad), 0)))
         if self.beam is None or self.beam.nb != nb:
             self.beam = BeamStore(self.B // nb, nb, self.ids.shape[1], self.eng.dev)
             self.ring_table = ops.beam_table(self.kc + self.vc)
@@ -1287,9 +1366,8 @@ class XLDecoder:
 
     # ---------------------------------------------------------------- contrastive search on the device (contrastive_search_device)
     def contrastive_begin(self, prompt: torch.Tensor, max_length: int, K: int, alpha: float, eos: Optional[int], pad: int,
-                          use_graph: bool = True, grammar=None, in_key=None, keys: Optional[torch.Tensor] = None,
-                          register: Optional[RegisterPlan] = None) -> int:
-        """prompt pass (one row per candidate: the K rows of a sequence hold the same prompt; the rules started as `prefill` starts
+                          use_graph: bool = True, rules: RulePlan = NO_RULES) -> int:
+        """prompt pass (one row per candidate: the K rows of a sequence hold the same prompt; `rules` started as `prefill` starts
         them, with the stop group (eos, pad, 0) always on -- eos None: -1, never emitted) + the store + (use_graph) capture of one
         contrastive step (`_capture`) + the first token, chosen by one step run here; returns the number of `replay_once()` calls that
         complete the generation to max_length.  The store's words and the log-probabilities are this step's own state (its context
@@ -1300,7 +1378,7 @@ class XLDecoder:
             raise MusicXLError(f'contrastive search on the device takes 2..{CONTRASTIVE_MAX} candidates and one decoder row per '
                                'candidate')
         c, Tp = self.eng.cfg, prompt.shape[1]
-        self.prefill(prompt, None, None, (-1 if eos is None else int(eos), int(pad), 0), grammar, None, in_key, keys, None, register)
+        self.prefill(prompt, None, None, rules.with_stop((-1 if eos is None else int(eos), int(pad), 0)))
         if self.cs is None or self.cs.K != K:
             self.cs = ContrastiveStore(self.B // K, K, self.Tmax, c.d_model, self.eng.dev)
             self.ring_table = ops.beam_table(self.kc + self.vc)
@@ -1343,26 +1421,18 @@ class XLDecoder:
 
     # ---------------------------------------------------------------- loop
     def begin(self, prompt: torch.Tensor, max_length: int, sampling: dict, use_graph: bool = True,
-              n_pad: Optional[torch.Tensor] = None, stop: Optional[tuple] = None, grammar=None,
-              n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None,
-              melody: Optional[MelodyPlan] = None, register: Optional[RegisterPlan] = None) -> int:
+              n_pad: Optional[torch.Tensor] = None, rules: RulePlan = NO_RULES) -> int:
         """prompt pass + first sampled token + (use_graph) capture of one decode step; returns the number of `replay_once()`
         calls that complete the generation to max_length.  n_pad: left-padded prompts (prefill); the decode step is the same,
-        every row's last prompt token sits at column Tp - 1.  stop: (eos, pad, min_length) (stop_config) or None.  grammar: a
-        grammar.TokenGrammar or None; the captured step reads its device tables and, under a bar budget, the budget's tables and
-        class masks, so their identity is part of the graph key.  n_bars: None or (B,) int32 (prefill); the step captured under the
-        bar count is another launch with two more class masks, so the presence of the rule and its masks are in the key too, while
-        the counts themselves are step state (`gleft`).  in_key / keys (prefill): the step captured under the key rule is another
-        launch that reads the rule's tables, so its presence and their identity are in the key; the keys are step state (`gkey`).
-        melody (prefill): the step captured under the guide rule is another launch that reads the decoder's guide buffer, so the
-        rule's presence, its masks and the buffer's identity are in the key; the guide tokens and `gpos` / `gforce` are step state,
-        and a later generation with another guide that fits the buffer replays the same graph.  register (prefill): the step captured
-        under the register rule is another launch that reads the rule's table and carries the gap, so its presence, the table's
-        identity and the gap are in the key; the bounds, the parts and the floors are step state"""
+        every row's last prompt token sits at column Tp - 1.  rules: the RulePlan of the generation (rules_config).  The captured
+        step is another launch under every rule, and it reads the rules' device tables: which rules are on, the identity of their
+        tables and their class masks, the guide buffer and the register gap are part of the graph key (RowRules.graph_key).  The
+        per-row values -- bar counts, keys, guide tokens and positions, bounds, parts and floors -- are step state, so a later
+        generation with other values, such as another guide that fits the buffer, replays the same graph"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         self._use_graph, self._step, self.finished_by = use_graph, ('step', sampling), (self.alive, 0)
-        self.prefill(prompt, sampling, n_pad, stop, grammar, n_bars, in_key, keys, melody, register)
+        self.prefill(prompt, sampling, n_pad, rules)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
             # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
@@ -1407,45 +1477,8 @@ class XLDecoder:
         else:
             self._step_once()
 
-    def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
-                 top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
-                 typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None,
-                 eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
-                 stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None, register=None,
-                 melody_range=None, bass_range=None, bass_below=None) -> torch.Tensor:
-        """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
-        [OMIT]) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (prefill); the
-        prompt columns, pads included, come back as given.
-        eos_token_id (opt-in): HF greedy_search / sample stopping -- a row that emits eos is finished and emits pad_token_id
-        (default: eos) from then on, the call ends once every row has finished, and the output is cut to the width of the
-        longest row (finish_at_eos); min_length bars eos below that width.  The decode steps are replayed in chunks of
-        `stop_chunk` with the live-row count read back one chunk late (run_until_finished): no per-step host round trip.
-        grammar (a grammar.TokenGrammar, e.g. `tokenizer.grammar()`): every row may only emit tokens its grammar state allows; the
-        state lives on the device and moves inside the sampler launch of the captured step.  The prompts must obey the grammar.
-        A grammar with a bar budget (`tokenizer.grammar(bar_budget=True)`) also keeps every channel of every generated bar exactly as
-        long as the row's time signature: the free slots of the open channel live and move beside the state.
-        n_bars (an int or one per row, negative = no limit; needs grammar and eos_token_id): every row opens exactly that many
-        further bars -- the bar open at the end of its prompt is finished and not counted -- and, under a bar budget, emits eos
-        when the last of them is full.  Without a budget the rule bars a further bar and an early eos but cannot force the end.
-        in_key (a grammar.KeyRule, e.g. `tokenizer.key_rule()`; needs no grammar): a row whose key is known emits only pitches of
-        that key.  key=None: every row's key is the last key token of its prompt (none: the row is unconstrained); key = a key name
-        or ordinal, or one per row with None / -1 = unconstrained, overrides the prompts.  A generated key token sets the row's key.
-        melody (one guide or one per row, None = unguided; needs grammar and eos_token_id, takes no n_bars or min_length): each
-        guide is the `<bar> <melody> ... <bass>` spans of its bars (`tokenizer.melody_guide`); the row is fed them bar by bar inside
-        the sampler launch and chooses the bass under each, then ends (melody_config, MyTransfoXLLMHeadModel.generate).
-        register (a grammar.RegisterRule, e.g. `tokenizer.register_rule()`; needs no grammar) with melody_range / bass_range (one
-        inclusive pair of MIDI numbers or one per row, None = unconstrained) and bass_below (None or g >= 0 semitones): the pitches
-        of every part stay inside its bounds, and the bass at least g under the lowest melody note of its bar (register_config)."""
-        stop = stop_config(eos_token_id, pad_token_id, min_length)
-        plan = melody_config(melody, self.B, grammar, stop, n_bars)
-        return decode_lanes(self, [self], [None], prompt, max_length,
-                            sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
-                            stop, stop_chunk, grammar, bar_count_config(n_bars if plan is None else plan.n_bars, self.B, grammar, stop),
-                            in_key, key_config(in_key, key, self.B, self.eng.cfg.vocab_size), plan,
-                            register_config(register, melody_range, bass_range, bass_below, self.B, self.eng.cfg.vocab_size))
 
-
-class XLDecoderLanes:
+class XLDecoderLanes(RuledGenerate):
     """The batch as `lanes` independent XLDecoders of B / lanes sequences, each with its own hipGraph, replayed on its own
     stream.  A decode step is ~100 small dependent launches around 12 ring-attention launches: alone, the small launches run at
     launch / latency cost with the chip idle and the ring streaming waits for them; with two lanes one lane's small launches
@@ -1465,15 +1498,9 @@ class XLDecoderLanes:
         for d in self.lanes:
             d.invalidate_tables()
 
-    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, stop=None, grammar=None, n_bars=None, in_key=None,
-              keys=None, melody=None, register=None) -> int:
-        steps = [d.begin(prompt[self.offs[i]:self.offs[i + 1]], max_length, sampling, use_graph,
-                         None if n_pad is None else n_pad[self.offs[i]:self.offs[i + 1]], stop, grammar,
-                         None if n_bars is None else n_bars[self.offs[i]:self.offs[i + 1]], in_key,
-                         None if keys is None else keys[self.offs[i]:self.offs[i + 1]],
-                         None if melody is None else melody.rows(self.offs[i], self.offs[i + 1]),
-                         None if register is None else register.rows(self.offs[i], self.offs[i + 1]))
-                 for i, d in enumerate(self.lanes)]
+    def begin(self, prompt, max_length, sampling, use_graph=True, n_pad=None, rules: RulePlan = NO_RULES) -> int:
+        steps = [d.begin(prompt[lo:hi], max_length, sampling, use_graph, None if n_pad is None else n_pad[lo:hi], rules.rows(lo, hi))
+                 for d, lo, hi in zip(self.lanes, self.offs, self.offs[1:])]
         for s in self.streams:                       # the lanes start from the prompt passes and captures issued above
             s.wait_stream(torch.cuda.current_stream())
         return steps[0]
@@ -1486,20 +1513,6 @@ class XLDecoderLanes:
     def join(self):
         for s in self.streams:
             torch.cuda.current_stream().wait_stream(s)
-
-    def generate(self, prompt, max_length, do_sample=False, top_k=None, top_p=None, temperature=1.0, repetition_penalty=None,
-                 typical_p=None, use_graph=True, n_pad=None, eos_token_id=None, pad_token_id=None, min_length=None,
-                 stop_chunk=STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None, register=None,
-                 melody_range=None, bass_range=None, bass_below=None) -> torch.Tensor:
-        """XLDecoder.generate over the lanes (each lane keeps the grammar state, the bar counts, the keys and the guides of its own rows).  With eos_token_id every lane stops
-        on its own; the output is the lanes' rows cut to the common width and right-filled with pad where a lane stopped earlier."""
-        stop = stop_config(eos_token_id, pad_token_id, min_length)
-        plan = melody_config(melody, self.B, grammar, stop, n_bars)
-        return decode_lanes(self, self.lanes, self.streams, prompt, max_length,
-                            sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), use_graph, n_pad,
-                            stop, stop_chunk, grammar, bar_count_config(n_bars if plan is None else plan.n_bars, self.B, grammar, stop),
-                            in_key, key_config(in_key, key, self.B, self.lanes[0].eng.cfg.vocab_size), plan,
-                            register_config(register, melody_range, bass_range, bass_below, self.B, self.lanes[0].eng.cfg.vocab_size))
 
 
 class _BeamHyps:
@@ -1678,7 +1691,7 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     `stop_chunk`; the number of done items is read back one chunk late (run_until_finished) and the loop
     ends when every item is done or at max_length.  Then the store and the running scores are read once and `_beam_finalize`
     builds the output, as beam_search does.  dec: an XLDecoder with prompt rows x num_beams rows, num_beams <= 16.
-    grammar / n_bars / in_key / key / register with melody_range, bass_range and bass_below: the rules of `XLDecoder.generate`, one
+    grammar / n_bars / in_key / key / register with melody_range, bass_range and bass_below: the rules as rules_config takes them, one
     value per prompt where they are per row (each prompt's is shared by its beams); a barred token is -inf before the running scores
     are added, the rules' words follow the beams, and a row that can only continue from a barred token is dead: it emits pad at score
     -inf and never returns.  An item that ends with fewer than num_return_sequences hypotheses of finite score raises MusicXLError.
@@ -1695,21 +1708,20 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     rows = B0 * nb
     if dec.B != rows or max_length > dec.Tmax:
         raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, beam search needs {rows} x {max_length}')
-    stop = (int(eos_token_id), int(pad), 0)
+    rules = rules_config(batch=B0, vocab_size=V, stop=(int(eos_token_id), int(pad), 0), grammar=grammar, n_bars=n_bars, in_key=in_key,
+                         key=key, register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below, repeat=nb)
     return _beam_device(dec, prompt, max_length, nb, keep, early_stopping, length_penalty, eos_token_id, pad, use_graph, stop_chunk,
-                        grammar, bar_count_config(n_bars, B0, grammar, stop, nb), in_key, key_config(in_key, key, B0, V, nb),
-                        return_scores, 'beam search', ng=int(num_beam_groups), diversity_penalty=float(diversity_penalty),
-                        register=register_config(register, melody_range, bass_range, bass_below, B0, V, nb))
+                        rules, return_scores, 'beam search', ng=int(num_beam_groups), diversity_penalty=float(diversity_penalty))
 
 
 def _beam_device(dec, items: torch.Tensor, max_length: int, nb: int, keep: int, early_stopping: bool, length_penalty: float, eos: int,
-                 pad: int, use_graph: bool, stop_chunk: int, grammar, n_bars, in_key, keys, return_scores: bool, what: str, **arm):
+                 pad: int, use_graph: bool, stop_chunk: int, rules: RulePlan, return_scores: bool, what: str, **arm):
     """The loop of the device beam searches over `items` (Bs, Tp), one prompt per item, nb decoder rows each: `beam_begin` (with
-    `arm`: the groups and their penalty, or the sample flag and its warpers; n_bars / keys one value per row), the chunked replay,
-    the last selection, one read of the store and `_beam_finalize` keeping `keep` hypotheses per item."""
+    `rules`, built for the Bs * nb rows, and `arm`: the groups and their penalty, or the sample flag and its warpers), the chunked
+    replay, the last selection, one read of the store and `_beam_finalize` keeping `keep` hypotheses per item."""
     B0, Tp = items.shape
     n = dec.beam_begin(items.repeat_interleave(nb, 0).to(dec.eng.dev), max_length, nb, eos, pad, length_penalty, early_stopping,
-                       use_graph, grammar, n_bars, in_key, keys, **arm)
+                       use_graph, rules, **arm)
     issued, = run_until_finished([(dec, None)], n, stop_chunk)
     dec.beam_select()                   # the last selection needs no forward after it; items that are done ignore it
     dec.steps_run = issued
@@ -1759,10 +1771,11 @@ def beam_sample_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
         raise MusicXLError(f'beam-sample on the device takes 2..{BEAM_MAX} beams, not {nb}')
     if nrs < 1 or dec.B != rows or max_length > dec.Tmax:
         raise MusicXLError(f'the decoder was built for {dec.B} rows x {dec.Tmax} positions, beam-sample needs {rows} x {max_length}')
+    rules = rules_config(batch=B0, vocab_size=V, grammar=grammar, in_key=in_key, key=key, register=register, melody_range=melody_range,
+                         bass_range=bass_range, bass_below=bass_below, repeat=nrs * nb)
     return _beam_device(dec, prompt.repeat_interleave(nrs, 0), max_length, nb, 1, early_stopping, length_penalty, eos_token_id, pad,
-                        use_graph, stop_chunk, grammar, None, in_key, key_config(in_key, key, B0, V, nrs * nb), return_scores,
-                        'beam-sample', sample=True, top_k=top_k, top_p=top_p, temperature=temperature, typical_p=typical_p,
-                        register=register_config(register, melody_range, bass_range, bass_below, B0, V, nrs * nb))
+                        use_graph, stop_chunk, rules, return_scores, 'beam-sample', sample=True, top_k=top_k, top_p=top_p,
+                        temperature=temperature, typical_p=typical_p)
 
 
 def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 4, num_beam_groups: int = 2,
@@ -1794,9 +1807,11 @@ def group_beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_bea
     nb, ng = int(num_beams), int(num_beam_groups)
     if ng < 2 or nb % ng != 0:
         raise ValueError('`num_beams` should be divisible by `num_beam_groups` for group beam search.')      # HF's message
-    return beam_search_device(dec, prompt, max_length, nb, early_stopping, length_penalty, num_return_sequences, eos_token_id,
-                              pad_token_id, use_graph, stop_chunk, grammar, None, in_key, key, return_scores, ng,
-                              float(diversity_penalty or 0.0), register, melody_range, bass_range, bass_below)
+    return beam_search_device(dec, prompt, max_length, num_beams=nb, early_stopping=early_stopping, length_penalty=length_penalty,
+                              num_return_sequences=num_return_sequences, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
+                              use_graph=use_graph, stop_chunk=stop_chunk, grammar=grammar, in_key=in_key, key=key,
+                              return_scores=return_scores, num_beam_groups=ng, diversity_penalty=float(diversity_penalty or 0.0),
+                              register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below)
 
 
 def beam_generate(make_decoder, input_ids: torch.Tensor, max_length: int, *, num_beams: int, num_beam_groups: int, do_sample: bool,
@@ -1908,8 +1923,8 @@ def contrastive_search_device(dec, prompt: torch.Tensor, max_length: int, top_k:
     of finished sequences is read back one chunk late (run_until_finished) and the loop ends when every
     sequence has finished or at max_length.  Returns what the host path returns: ids[::K] cut at the step in which the last sequence
     finished, else at max_length; the steps run beyond it inside the last chunk emit pad and are cut off.  dec: an XLDecoder with
-    prompt rows x top_k rows, 2 <= top_k <= 32.  grammar (with or without a bar budget) / in_key / key: the rules of
-    `XLDecoder.generate`, one value per prompt where they are per row (each prompt's is shared by its K rows); a barred token is -inf
+    prompt rows x top_k rows, 2 <= top_k <= 32.  grammar (with or without a bar budget) / in_key / key / register: the rules as
+    rules_config takes them, one value per prompt where they are per row (each prompt's is shared by its K rows); a barred token is -inf
     before the top-k, and a candidate that is barred is never picked."""
     V = dec.eng.cfg.vocab_size
     K = int(top_k)
@@ -1922,9 +1937,10 @@ def contrastive_search_device(dec, prompt: torch.Tensor, max_length: int, top_k:
     if max_length <= Tp:
         return prompt.to(dec.eng.dev).clone()
     pad = eos_token_id if pad_token_id is None else pad_token_id
+    rules = rules_config(batch=B0, vocab_size=V, grammar=grammar, in_key=in_key, key=key, register=register, melody_range=melody_range,
+                         bass_range=bass_range, bass_below=bass_below, repeat=K)
     n = dec.contrastive_begin(prompt.repeat_interleave(K, 0).to(dec.eng.dev), max_length, K, penalty_alpha, eos_token_id,
-                              0 if pad is None else pad, use_graph, grammar, in_key, key_config(in_key, key, B0, V, K),
-                              register_config(register, melody_range, bass_range, bass_below, B0, V, K))
+                              0 if pad is None else pad, use_graph, rules)
     # (the count is first read once the first token is chosen: sequences that all start with eos replay nothing)
     issued, = run_until_finished([(dec, None)], n, stop_chunk)
     dec.steps_run = issued

@@ -193,10 +193,8 @@ class MyReformerModelWithLMHead(EngineModule):
         numbers or one per prompt, None = unconstrained) and bass_below (None or g >= 0 semitones): greedy decoding and sampling in
         which every part keeps its pitches inside its bounds and the bass stays at least g under the lowest melody note of its bar,
         as MyTransfoXLLMHeadModel.generate; it needs no grammar.  Every search here scores on the host and refuses it."""
-        from .generate import (STOP_CHUNK, RowRules, bar_count_config, beam_generate, check_grammar_args, key_config,
-                               left_pad_counts, melody_config, plan_search, register_config, resolve_max_length, rules_refusal, sample_unfused,
-                               sampling_config,
-                               stop_config, stop_width)
+        from .generate import (STOP_CHUNK, RowRules, beam_generate, check_grammar_args, left_pad_counts, plan_search,
+                               resolve_max_length, rules_config, rules_refusal, sample_unfused, sampling_config, stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
@@ -221,12 +219,9 @@ class MyReformerModelWithLMHead(EngineModule):
                            top_k=top_k, eos_token_id=eos_token_id, pad_token_id=pad_token_id, config_eos=self.config.eos_token_id,
                            config_pad=self.config.pad_token_id, device_scorer=device_scorer, repetition_penalty=repetition_penalty,
                            renormalize_logits=renormalize_logits, vocab_size=self.config.vocab_size)
-        guide = melody_config(melody, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, n_bars, nrs)
-        n_bars = (bar_count_config(n_bars, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, nrs) if guide is None
-                  else guide.n_bars)
-        keys = key_config(in_key, key, input_ids.shape[0] if input_ids is not None else 0, self.config.vocab_size, nrs)
-        span = register_config(register, melody_range, bass_range, bass_below, input_ids.shape[0] if input_ids is not None else 0,
-                               self.config.vocab_size, nrs)
+        rules = rules_config(batch=input_ids.shape[0] if input_ids is not None else 0, vocab_size=self.config.vocab_size, stop=stop,
+                             grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody, register=register,
+                             melody_range=melody_range, bass_range=bass_range, bass_below=bass_below, repeat=nrs)
         if attention_mask is not None and input_ids is not None and any(left_pad_counts(attention_mask, tuple(input_ids.shape))):
             # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
             raise MusicXLError(f'{type(self).__name__}.generate does not support padded prompts (attention_mask with zeros); '
@@ -279,6 +274,7 @@ class MyReformerModelWithLMHead(EngineModule):
             raise ValueError('max_length exceeds max_position_embeddings')
         if max_length <= Tp:
             return ids0[:, :max_length]
+        sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
         try:
             if use_cache:
                 dec = getattr(self, '_decoder', None)
@@ -286,9 +282,7 @@ class MyReformerModelWithLMHead(EngineModule):
                     dec = self._decoder = RFDecoder(self.engine, B, max_length, seed=seed)
                 dec.rotations = rotations
                 dec.seed = seed
-                return dec.generate(ids0, max_length, do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
-                                    repetition_penalty=repetition_penalty, typical_p=typical_p, stop=stop, grammar=grammar, n_bars=n_bars,
-                                    in_key=in_key, key=keys, melody=guide, register=span)
+                return dec.run(ids0, max_length, sampling, rules, use_graph=False)
             V = c.vocab_size
             pad = getattr(c, 'pad_token_id', None)
             pad = 0 if pad is None else int(pad)
@@ -296,22 +290,21 @@ class MyReformerModelWithLMHead(EngineModule):
             buf[:, :Tp] = ids0
             t_dev = torch.full((1,), Tp - 1, device=self.device, dtype=torch.int32)
             rng = torch.zeros(1, device=self.device, dtype=torch.int64)
-            rules = RowRules(B, self.device)
-            rules.start(buf, Tp, V, stop, grammar, n_bars, in_key, keys, guide, span)
-            rules.check_prompt(buf)
-            sampling = sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p)
+            words = RowRules(B, self.device)
+            words.start(buf, Tp, V, rules)
+            words.check_prompt(buf)
             for cur in range(Tp, max_length):
                 Tf = cur if cur <= 64 else (cur + 63) // 64 * 64
                 out = self.engine.forward(buf[:, :Tf].contiguous(), labels=None, train=False)
                 last = out['logits'][:, cur - 1].contiguous()
-                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, **rules.kwargs())
+                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, **words.kwargs())
                 if Tf > cur:
                     buf[:, cur + 1:Tf] = pad          # keep the padding clean (the sampler wrote position `cur` only)
                 # a whole forward per token: reading the live-row count every STOP_CHUNK tokens costs nothing in comparison
-                if stop is not None and (cur - Tp) % STOP_CHUNK == 0 and int(rules.alive.item()) == 0:
+                if stop is not None and (cur - Tp) % STOP_CHUNK == 0 and int(words.alive.item()) == 0:
                     break
             if stop is not None:
-                return buf[:, :stop_width(buf, rules.unfinished, Tp, max_length, stop[0])].clone()
+                return buf[:, :stop_width(buf, words.unfinished, Tp, max_length, stop[0])].clone()
             return buf[:, :max_length].clone()
         finally:
             if was_training:

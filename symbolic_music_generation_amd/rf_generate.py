@@ -26,11 +26,10 @@ import torch
 
 from . import ops
 from ._lib import MusicXLError
-from .generate import (RowRules, bar_count_config, decode_lanes, key_config, melody_config, register_config, sample_unfused,
-                       sampling_config)
+from .generate import NO_RULES, RowRules, RuledGenerate, RulePlan, sample_unfused
 
 
-class RFDecoder:
+class RFDecoder(RuledGenerate):
     def __init__(self, engine, batch: int, max_total_len: int, rotations: Optional[Dict[int, torch.Tensor]] = None,
                  seed: int = 77):
         self.eng = engine
@@ -101,15 +100,14 @@ class RFDecoder:
         return r
 
     # ---------------------------------------------------------------- prompt
-    def prefill(self, prompt: torch.Tensor, sampling: dict, stop: Optional[tuple] = None, grammar=None,
-                n_bars: Optional[torch.Tensor] = None, in_key=None, keys: Optional[torch.Tensor] = None, melody=None, register=None):
+    def prefill(self, prompt: torch.Tensor, sampling: dict, rules: RulePlan = NO_RULES):
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and 1 <= Tp <= self.Tmax
         d, H = c.hidden_size, c.num_attention_heads
         self.ids.zero_()
         self.ids[:, :Tp].copy_(prompt)
-        self.rules.start(self.ids, Tp, c.vocab_size, stop, grammar, n_bars, in_key, keys, melody, register)
+        self.rules.start(self.ids, Tp, c.vocab_size, rules)
         for l in self.bk:
             self.n_bucketed[l] = 0
             self.bkmax[l].zero_()
@@ -251,39 +249,17 @@ class RFDecoder:
         self.step(cur_len - 1, None)
 
     # ---------------------------------------------------------------- loop
-    @torch.no_grad()
-    def generate(self, prompt: torch.Tensor, max_length: int, do_sample: bool = False, top_k: Optional[int] = None,
-                 top_p: Optional[float] = None, temperature: float = 1.0, repetition_penalty: Optional[float] = None,
-                 typical_p: Optional[float] = None, stop: Optional[tuple] = None, stop_chunk: int = 16,
-                 grammar=None, n_bars=None, in_key=None, key=None, melody=None, register=None, melody_range=None, bass_range=None,
-                 bass_below=None) -> torch.Tensor:
-        """(B, max_length) ids = prompt + continuation.  stop = (eos, pad, min_length) (generate.stop_config): rows finish at eos
-        and the loop ends once none is live -- the live-row count is read back every `stop_chunk` steps, one chunk late
-        (generate.run_until_finished) -- and the output is cut to the longest row.  grammar: a grammar.TokenGrammar; every row may
-        only emit tokens its grammar state allows (mask before the sampler, state advance after it, both on the device); a bar budget
-        on the grammar is kept the same way, and n_bars (an int or one per row, negative = no limit) turns its bar count on: every row
-        opens exactly that many further bars (generate.XLDecoder.generate).  in_key (a grammar.KeyRule) with key: a row whose key is
-        known emits only pitches of that key, kept by the same two launches (generate.XLDecoder.generate).  melody (one guide or one
-        per row, or a generate.MelodyPlan): the rows are fed the `<bar> <melody> ... <bass>` spans of their guides and write the bass
-        under them, again by the same two launches (generate.melody_config).  register (a grammar.RegisterRule, or a
-        generate.RegisterPlan) with melody_range / bass_range / bass_below: every part keeps its pitches inside its bounds and the bass
-        under the melody of its bar, by the same two launches (generate.register_config)."""
+    def _admit(self, max_length: int):
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
-        plan = melody_config(melody, self.B, grammar, stop, n_bars)
-        return decode_lanes(self, [self], [None], prompt, max_length,
-                            sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), False, None, stop,
-                            stop_chunk, grammar, bar_count_config(n_bars if plan is None else plan.n_bars, self.B, grammar, stop),
-                            in_key, key_config(in_key, key, self.B, self.eng.cfg.vocab_size), plan,
-                            register_config(register, melody_range, bass_range, bass_below, self.B, self.eng.cfg.vocab_size))
 
-    def begin(self, prompt, max_length, sampling, use_graph=False, n_pad=None, stop=None, grammar=None, n_bars=None, in_key=None,
-              keys=None, melody=None, register=None) -> int:
+    def begin(self, prompt, max_length, sampling, use_graph=False, n_pad=None, rules: RulePlan = NO_RULES) -> int:
         """generate.decode_lanes' entry: prompt pass and first token; returns the `replay_once()` calls left to max_length.  There
-        is no graph to capture here, and padded prompts are not supported."""
-        assert not use_graph and n_pad is None
+        is no graph to capture here (use_graph changes nothing), and padded prompts are not supported.  Under the rules the mask
+        runs before the sampler and the words advance after it, both on the device (generate.sample_unfused)."""
+        assert n_pad is None
         Tp = prompt.shape[1]
-        self.prefill(prompt.to(self.eng.dev), sampling, stop, grammar, n_bars, in_key, keys, melody, register)
+        self.prefill(prompt.to(self.eng.dev), sampling, rules)
         self._next_t, self._sampling = Tp, sampling
         return max(max_length - 1 - Tp, 0)
 

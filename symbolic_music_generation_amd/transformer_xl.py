@@ -316,10 +316,10 @@ class MyTransfoXLLMHeadModel(EngineModule):
         values are shared by the prompt's `top_k` rows, a barred token is -inf before the top-k, where HF's logits processors sit, and
         a barred candidate is never picked.  `n_bars`, `melody` and padded prompts stay refused.  `top_k > 32` or
         `MXL_CONTRASTIVE_HOST=1` keeps the host-driven loop (`generate.contrastive_search`), which takes no rules here."""
-        from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, bar_count_config, beam_generate, beam_sample_device,
-                               beam_search_device,
-                               check_grammar_args, contrastive_search, contrastive_search_device, group_beam_search_device, key_config,
-                               left_pad_counts, melody_config, plan_search, register_config, resolve_max_length, stop_config)
+        from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, beam_generate, beam_sample_device,
+                               beam_search_device, check_grammar_args, contrastive_search, contrastive_search_device,
+                               group_beam_search_device, left_pad_counts, plan_search, resolve_max_length, rules_config, sampling_config,
+                               stop_config)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -344,12 +344,10 @@ class MyTransfoXLLMHeadModel(EngineModule):
                            repetition_penalty=repetition_penalty, renormalize_logits=renormalize_logits,
                            vocab_size=self.config.vocab_size, register=register)
         B0 = input_ids.shape[0]
-        guide = melody_config(melody, B0, grammar, stop, n_bars, num_return_sequences)
-        bars = bar_count_config(n_bars, B0, grammar, stop, num_return_sequences) if guide is None else None
-        keys = key_config(in_key, key, B0, self.config.vocab_size, num_return_sequences)
         ranges = dict(register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below)
-        span = register_config(**ranges, batch=B0, vocab_size=self.config.vocab_size, repeat=num_return_sequences)
-        if span is None:
+        rules = rules_config(batch=B0, vocab_size=self.config.vocab_size, stop=stop, grammar=grammar, n_bars=n_bars, in_key=in_key,
+                             key=key, melody=melody, **ranges, repeat=num_return_sequences)
+        if rules.register is None:
             ranges = {}                                     # (a call without the rule hands nothing of it on)
         ends = dict(eos_token_id=plan.eos, pad_token_id=plan.pad)
         if plan.strategy == 'contrastive':
@@ -358,7 +356,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                 return contrastive_search_device(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha, use_graph=use_graph,
                                                  grammar=grammar, in_key=in_key, key=key, **ranges, **ends)
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha, **ends)
-        if plan.device:                                     # (the device searches repeat per-prompt values per beam themselves)
+        if plan.device:                                     # (the device searches plan per-prompt values per beam themselves)
             beams = dict(num_beams=num_beams, early_stopping=bool(early_stopping), length_penalty=length_penalty,
                          num_return_sequences=num_return_sequences, use_graph=use_graph, grammar=grammar, in_key=in_key, key=key, **ranges,
                          **ends)
@@ -392,8 +390,6 @@ class MyTransfoXLLMHeadModel(EngineModule):
             dec = self._decoder = (XLDecoderLanes(self.engine, B, max_length, seed=seed, lanes=lanes) if lanes > 1
                                    else XLDecoder(self.engine, B, max_length, seed=seed))
         dec.invalidate_tables()
-        return dec.generate(input_ids.to(self.device), max_length, do_sample=do_sample, top_k=top_k, top_p=top_p,
-                            temperature=temperature, repetition_penalty=repetition_penalty, typical_p=typical_p,
-                            use_graph=use_graph, n_pad=None if n_pad is None else n_pad.to(self.device), grammar=grammar, n_bars=bars,
-                            in_key=in_key, key=keys, melody=guide, **({} if span is None else {'register': span}),
-                            **({} if stop is None else dict(eos_token_id=stop[0], pad_token_id=stop[1], min_length=stop[2])))
+        return dec.run(input_ids.to(self.device), max_length,
+                       sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), rules, use_graph,
+                       None if n_pad is None else n_pad.to(self.device))

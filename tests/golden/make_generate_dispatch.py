@@ -40,7 +40,7 @@ class Reached(Exception):
 
 def _describe(name: str, rows: list, args: dict) -> str:
     eos, pad = args.get('eos_token_id'), args.get('pad_token_id')
-    if args.get('stop') is not None:                       # RFDecoder.generate takes the stop group whole
+    if args.get('stop') is not None:                       # the decoders take the stop group whole (RulePlan.stop)
         eos, pad = args['stop'][:2]
     given = ','.join(k for k in RULES if args.get(k) is not None)
     shown = ' '.join(f'{k}={args[k]!r}' for k in SHOWN if k in args)
@@ -48,8 +48,10 @@ def _describe(name: str, rows: list, args: dict) -> str:
 
 
 class _Decoder:
-    """stands for XLDecoder, XLDecoderLanes and RFDecoder: what `generate` and `beam_generate` touch before a search starts"""
+    """stands for XLDecoder, XLDecoderLanes and RFDecoder: what `generate` and `beam_generate` touch before a search starts, and
+    `run`, the entry greedy decoding and sampling end in"""
     built = []
+    lists_guide_bars = False
 
     def __init__(self, engine, batch, max_total_len, *a, **k):
         self.B, self.Tmax = batch, max_total_len
@@ -59,8 +61,17 @@ class _Decoder:
     def invalidate_tables(self):
         pass
 
-    def generate(self, prompt, max_length, **kw):
-        raise Reached(_describe('sample' if kw.get('do_sample') else 'greedy', list(_Decoder.built), dict(kw, max_length=max_length)))
+    def run(self, prompt, max_length, sampling, rules, use_graph=True, n_pad=None, stop_chunk=None):
+        """the decoders' entry under a finished generate.RulePlan, described in the keywords both models handed `generate` when the
+        table was recorded: the stop group whole, and the bar counts of a guide listed as n_bars by the Reformer alone"""
+        bars = rules.n_bars if rules.melody is None or self.lists_guide_bars else None
+        kw = dict(do_sample=sampling['do_sample'], stop=rules.stop, grammar=rules.grammar, n_bars=bars, in_key=rules.in_key,
+                  key=rules.keys, melody=rules.melody, n_pad=n_pad, max_length=max_length)
+        raise Reached(_describe('sample' if kw['do_sample'] else 'greedy', list(_Decoder.built), kw))
+
+
+class _RFDecoder(_Decoder):
+    lists_guide_bars = True
 
 
 def _recorder(name: str, real):
@@ -81,7 +92,8 @@ class patched:
         mods = dict(generate=generate, rf_generate=rf_generate)
         self.saved = [(mods[m], n, getattr(mods[m], n)) for m, n in DECODERS] + [(generate, n, getattr(generate, n)) for n in SEARCHES]
         for mod, n, real in self.saved:
-            setattr(mod, n, _Decoder if (mod.__name__.rsplit('.', 1)[1], n) in DECODERS else _recorder(n, real))
+            stub = _RFDecoder if n == 'RFDecoder' else _Decoder
+            setattr(mod, n, stub if (mod.__name__.rsplit('.', 1)[1], n) in DECODERS else _recorder(n, real))
         return self
 
     def __exit__(self, *exc):
