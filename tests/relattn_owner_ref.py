@@ -2,9 +2,9 @@
 
 oracle/relattn_cases.build_case takes a named shape, so the owner-mode shapes -- chosen for the visit logic: a query tile seen by
 one, two and three key blocks, a first visit that is not key block 0, M off the 256 grid, stored and phantom keys together, no
-phantom term -- get their inputs here, in the layout relattn_ref64 takes.  `dq_models` evaluates both summations on the CPU from
-the operand-rounded model of the fused arm: per-block mode rounds every key block's partial to bf16 in front of the float32 sum,
-owner mode carries the float32 sum; both round the finished dq to bf16 once.
+phantom term -- get their inputs here, in the layout relattn_ref64 takes.  `dq_models` (oracle/relattn_cases.py: arms 'fused' and
+'fused_owner' of the operand-rounded model) evaluates both summations on the CPU: per-block mode rounds every key block's partial to
+bf16 in front of the float32 sum, owner mode carries the float32 sum; both round the finished dq to bf16 once.
 """
 import functools
 import math
@@ -12,7 +12,7 @@ import math
 import torch
 
 from oracle.kernel_cases import bf16_exact
-from oracle.relattn_cases import relattn_ref64
+from oracle.relattn_cases import dq_models, relattn_ref64      # noqa: F401  (dq_models: for the users of this module)
 
 # name: (B, T, H, dh, M, Kc)
 OWNER_SHAPES = {
@@ -40,33 +40,6 @@ def owner_case_ref(name, seed=0):
     """-> (case, float64 reference): built once per process and shared; callers leave both unchanged"""
     c = build_owner_case(name, seed)
     return c, relattn_ref64(c)
-
-
-def _bf(x):
-    return x.float().to(torch.bfloat16).double()
-
-
-def dq_models(c):
-    """-> (dq of per-block mode, dq of owner mode), float64 values of the bf16 results, from the operand-rounded model"""
-    r = relattn_ref64(c, rounded=True, arm='fused')
-    B, T, H, dh, M, Kc = (c[n] for n in ('B', 'T', 'H', 'dh', 'M', 'Kc'))
-    J = M + T
-    kf = torch.zeros(B, J, H, dh, dtype=torch.float64)
-    kf[:, J - Kc:] = c['k'].double()
-    rd = c['rd'].double()
-    dSb, dG = _bf(r['dS']), r['dG']
-    jidx = torch.arange(T)[:, None] + M - torch.arange(M)[None, :]                 # column of (query, distance)
-    stored = (torch.arange(T)[:, None] - torch.arange(M)[None, :]) >= T - Kc       # key position i - d is a stored one
-    slabs = torch.zeros_like(r['dq'])
-    carried = torch.zeros_like(r['dq'])
-    for kb in range((Kc + 255) // 256):
-        col = torch.zeros(J, dtype=torch.bool)
-        col[J - Kc + 256 * kb: J - Kc + 256 * (kb + 1)] = True
-        part = torch.einsum('bhij,bjhe->bihe', dSb * col, kf) + torch.einsum('bhid,dhe->bihe', dG * (stored & col[jidx]), rd)
-        slabs = slabs + _bf(part)
-        carried = carried + part
-    phantom = r['dq'] - slabs                                                      # (the model's dq = slabs + phantom term)
-    return _bf(slabs + phantom), _bf(carried + phantom)
 
 
 def rel_l2(a, b):

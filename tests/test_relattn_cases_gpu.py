@@ -24,7 +24,11 @@ shows that a dropped band-edge cell, a dG tile shifted by one distance and a d_r
 
 Every launch also checks: outputs sit in NaN canary frames (row strides larger than H dh wherever the C ABI takes one), every
 element inside is finite and the frame is untouched; d_rd, d_rwb, d_rrb start from a non-zero pattern and must come back as
-pattern + reference; dk / dv of a key no query sees (position -M with full memory) are exactly zero.
+pattern + reference; dk / dv of a key no query sees (position -M with full memory) are exactly zero; the fused pass gets a
+workspace of exactly the size it asks for, NaN-filled between two NaN guards that must stay intact.
+
+The fused pass runs here in per-block mode, forced (dq_mode='slabs': neither the dispatch rule nor MXL_FUSED_OWNER decides);
+tests/test_relattn_owner_cases_gpu.py runs it in owner mode through the same `Run` / `run_backward`.
 """
 import math
 import os
@@ -81,6 +85,38 @@ class Flat:
         assert torch.isnan(self.full[:64]).all() and torch.isnan(self.full[-64:]).all(), f'{what}: wrote outside its window'
 
 
+class Packed:
+    """dq, dk, dv as the training engine passes them: column slices of one NaN-filled (B, Kc, 3 d) buffer, dq in its last T rows
+    (row stride 3 d for all three, batch stride Kc 3 d).  Afterwards the dq columns of the first Kc - T rows are still NaN and every
+    other element is finite."""
+
+    def __init__(self, dev, B, T, Kc, d):
+        self.full = torch.full((B, Kc, 3 * d), float('nan'), device=dev, dtype=torch.bfloat16)
+        self.T, self.Kc, self.d = T, Kc, d
+
+    def parts(self):
+        import types
+        T, Kc, d = self.T, self.Kc, self.d
+        views = (self.full[:, Kc - T:, :d], self.full[:, :, d:2 * d], self.full[:, :, 2 * d:])
+        return tuple(types.SimpleNamespace(view=v, rs=3 * d, bs=Kc * 3 * d, check=self.check) for v in views)
+
+    def check(self, what):
+        torch.cuda.synchronize()
+        f = self.full.float().clone()
+        assert torch.isnan(f[:, :self.Kc - self.T, :self.d]).all(), f'{what}: the dq columns of the memory rows were written'
+        f[:, :self.Kc - self.T, :self.d] = 0
+        assert torch.isfinite(f).all(), f'{what}: an element of the packed gradients is not finite (left unwritten?)'
+
+
+def check_ws(ws, used):
+    """the workspace of the fused backward (a Flat): its guards are untouched, and everything beyond the first `used` floats (owner
+    mode: the float32 carry, B T H 64 of them, whatever M is) is still the NaN it was filled with"""
+    torch.cuda.synchronize()
+    assert torch.isnan(ws.full[:64]).all() and torch.isnan(ws.full[-64:]).all(), 'ws: wrote outside the workspace'
+    if used is not None:
+        assert torch.isnan(ws.view[used:]).all(), 'ws: owner mode wrote beyond its carry'
+
+
 def _pattern(shape, seed):
     """the known non-zero float32 contents an accumulated output starts from: multiples of 2^-8 in +-[1/8, 5/8]"""
     g = torch.Generator().manual_seed(seed)
@@ -92,8 +128,9 @@ def _pattern(shape, seed):
 class Run:
     """the device buffers of one case: inputs, framed forward outputs, and `forward` / `backward` launches"""
 
-    def __init__(self, dev, c):
-        self.dev, self.c = dev, c
+    def __init__(self, dev, c, packed=False):
+        """packed: q, k, v are column slices of one (B, Kc, 3 d) buffer and dq, dk, dv of another, as the training engine passes them"""
+        self.dev, self.c, self.packed = dev, c, packed
         B, T, H, dh, M, Kc = (c[n] for n in ('B', 'T', 'H', 'dh', 'M', 'Kc'))
         d = H * dh
         self.d = d
@@ -109,6 +146,11 @@ class Run:
         self.st = dict(B=B, T=T, H=H, dh=dh, M=M, Kc=Kc, q_bs=T * d, q_rs=d, kv_bs=Kc * d, kv_rs=d, rd_rs=d, o_bs=self.out.bs,
                        o_rs=self.out.rs, scale=c['scale'])
         self.oph = self.mph = self.ph = None
+        if packed:       # the rows of the q columns that belong to memory positions stay NaN: nothing may read them
+            qkv = torch.full((B, Kc, 3 * d), float('nan'), device=dev, dtype=torch.bfloat16)
+            qkv[:, Kc - T:, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:] = self.q, self.k, self.v
+            self.q, self.k, self.v = qkv[:, Kc - T:, :d], qkv[:, :, d:2 * d], qkv[:, :, 2 * d:]
+            self.st.update(q_bs=Kc * 3 * d, q_rs=3 * d, kv_bs=Kc * 3 * d, kv_rs=3 * d)
 
     def forward(self, oph=None, ph_buf=False):
         """oph: None (mxl_relattn_fwd), 'blk' (mxl_relattn_fwd_phantom), 'all' (mxl_relattn_fwd_phantom2, with the records if ph_buf)"""
@@ -134,13 +176,18 @@ class Run:
             got['oph_raw'] = self.oph.view.float().cpu()
         return got
 
-    def backward(self, arm, dg_seqs=None, records='prep', delta_ready=False):
-        """arm: 'plain' / 'dq8' / 'sparse' / 'sparse_oph' (ops.relattn_bwd; the caller has set the knobs) or 'fused'"""
+    def backward(self, arm, dg_seqs=None, records='prep', delta_ready=False, dq_mode='slabs', delta_in=None, launch=None):
+        """arm: 'plain' / 'dq8' / 'sparse' / 'sparse_oph' (ops.relattn_bwd; the caller has set the knobs) or 'fused' (dq_mode: the form
+        that produces dq, 'slabs' = per-block mode or 'owner', forced: no environment variable and no dispatch rule decides; None
+        leaves it to the dispatch rule, and the caller reads the mode from the returned workspace.  delta_in: the delta a
+        delta_ready call supplies, instead of the host's float64 one.  launch: stands in for ops.relattn_bwd_fused)"""
         from symbolic_music_generation_amd import ops
         c, dev, d = self.c, self.dev, self.d
         B, T, H, dh, M, Kc = (c[n] for n in ('B', 'T', 'H', 'dh', 'M', 'Kc'))
         dq = Framed(dev, B, T, d, torch.bfloat16)
         dk, dv = Framed(dev, B, Kc, d, torch.bfloat16), Framed(dev, B, Kc, d, torch.bfloat16)
+        if self.packed:
+            dq, dk, dv = Packed(dev, B, T, Kc, d).parts()
         pat = dict(d_rd=_pattern((M, d), 1), d_rwb=_pattern((H, dh), 2), d_rrb=_pattern((H, dh), 3))
         d_rwb, d_rrb = Flat(dev, (H, dh), pat['d_rwb'].to(dev)), Flat(dev, (H, dh), pat['d_rrb'].to(dev))
         delta = Flat(dev, (B, H, T))
@@ -152,13 +199,18 @@ class Run:
             assert ops.fused_bwd_applies(T=T, dh=dh, M=M, Kc=Kc, B=B, H=H)
             d_rd = Framed(dev, None, M, d, torch.float32)           # the C ABI takes d_rd's row stride
             d_rd.view.copy_(pat['d_rd'])
-            ws = torch.full((ops.relattn_bwd_fused_ws_numel(B, T, H, dh, M),), float('nan'), device=dev)
+            assert dq_mode in (None, 'slabs', 'owner')
+            n_ws = ops.relattn_bwd_fused_ws_numel(B, T, H, dh, M)
+            assert n_ws * 4 == ((M + 255) // 256 + 1) * B * T * H * 128          # one bf16 slab per key block a tile can touch
+            ws = Flat(dev, (n_ws,))          # exactly the floats requested, NaN-filled, between two NaN guards
             if delta_ready:      # delta on the host, in float64 from the device's bf16 out, rounded to float32
                 dl = torch.einsum('bihe,bihe->bhi', self.dout.view.double().view(B, T, H, dh), self.out.view.double().view(B, T, H, dh))
-                delta.view.copy_(dl.float())
-            ops.relattn_bwd_fused(*args, d_rd.view, d_rwb.view, d_rrb.view, ws, qr_buf, oph=None if self.oph is None else self.oph.view,
-                                  mph=None if self.mph is None else self.mph.view, ph_buf=self.ph if records == 'fwd' else None,
-                                  ph_ready=records == 'fwd', delta_ready=delta_ready, **kw)
+                delta.view.copy_(dl.float() if delta_in is None else delta_in)
+            fused = launch or ops.relattn_bwd_fused
+            fused(*args, d_rd.view, d_rwb.view, d_rrb.view, ws.view, qr_buf, oph=None if self.oph is None else self.oph.view,
+                  mph=None if self.mph is None else self.mph.view, ph_buf=self.ph if records == 'fwd' else None,
+                  ph_ready=records == 'fwd', delta_ready=delta_ready, dq_mode=dq_mode, **kw)
+            check_ws(ws, B * T * H * 64 if dq_mode == 'owner' else None)
         else:
             d_rd = Flat(dev, (M, d), pat['d_rd'].to(dev))
             n = B if dg_seqs is None else dg_seqs
@@ -169,7 +221,10 @@ class Run:
         for nm, f in (('dq', dq), ('dk', dk), ('dv', dv), ('d_rd', d_rd), ('d_rwb', d_rwb), ('d_rrb', d_rrb), ('delta', delta)):
             f.check(nm)
         got = dict(dq=dq.view.double().cpu().view(B, T, H, dh), dk=dk.view.double().cpu().view(B, Kc, H, dh),
-                   dv=dv.view.double().cpu().view(B, Kc, H, dh))
+                   dv=dv.view.double().cpu().view(B, Kc, H, dh), delta=delta.view.cpu())
+        if arm == 'fused':
+            got['ws'] = ws
+            got['bits'] = {nm: f.view.cpu().contiguous().view(torch.int16) for nm, f in (('dq', dq), ('dk', dk), ('dv', dv))}
         # accumulated outputs: pattern + reference (`=` for `+=` or a double add shows as an error of the pattern's size, 1/8 .. 5/8 per
         # element, far above b max|ref| wherever the reference is small; the float32 add itself costs 2^-24 of that, inside b)
         for nm, f in (('d_rd', d_rd), ('d_rwb', d_rwb), ('d_rrb', d_rrb)):
@@ -202,8 +257,8 @@ def device_arms(c):
     return arms + [a for a in arms_of(c) if a != 'three']
 
 
-def run_backward(dev, shape, family, arm, setenv, **kw):
-    """forward + backward of one case on one arm, judged; `setenv(name, value)` sets a knob ops.py reads per call"""
+def run_backward(dev, shape, family, arm, setenv, packed=False, **kw):
+    """forward + backward of one case on one arm, judged; `setenv(name, value)` sets a knob ops.py reads per call.  -> the outputs"""
     from symbolic_music_generation_amd import ops
     c, ref = case_ref(shape, family)
     B, T, H, dh, M, Kc = (c[n] for n in ('B', 'T', 'H', 'dh', 'M', 'Kc'))
@@ -216,7 +271,7 @@ def run_backward(dev, shape, family, arm, setenv, **kw):
     real = ops.gemm_batched
     ops.gemm_batched = lambda *a, **k: (calls.append(1), real(*a, **k))[1]
     try:
-        run = Run(dev, c)
+        run = Run(dev, c, packed)
         if arm == 'sparse_oph':
             assert ops.phantom_sum_applies(T=T, dh=dh, M=M, Kc=Kc)
             fwd = run.forward(oph='blk')
@@ -233,8 +288,9 @@ def run_backward(dev, shape, family, arm, setenv, **kw):
         if arm in ('sparse', 'sparse_oph'):
             assert dh == 64 and T % 32 == 0 and M % 256 == 0 and zero_mem
     got.update(fwd)
-    model = case_model(shape, family, MODEL_ARM[arm])
-    _judge(f'{shape} {family} {arm} {kw or ""}', got, ref, model, ('out', 'lse') + GRADS)
+    model = case_model(shape, family, 'fused_owner' if kw.get('dq_mode') == 'owner' else MODEL_ARM[arm])
+    _judge(f'{shape} {family} {arm} {"packed " if packed else ""}{kw or ""}', got, ref, model, ('out', 'lse') + GRADS)
+    return got
 
 
 # ---------------------------------------------------------------------------------------------------------------- forward
@@ -285,8 +341,9 @@ BWD = [(s, f, a) for s, f in CASES if dims(s)['T'] > 1 for a in device_arms(dims
 def test_backward(dev, monkeypatch, shape, family, arm):
     """every case on every backward arm its shape can take: the plain three-kernel form (d_rrb from the query-owner kernel; the dRd
     contraction streaming or, off its shapes, the batched GEMM), the 8-wave form with the streaming mxl_relattn_drd, the sparse-dG
-    pair with mxl_relattn_drd_recompute, the same with the forward's phantom sum, and the fused pass (records from the prep pass)"""
-    run_backward(dev, shape, family, arm, monkeypatch.setenv)
+    pair with mxl_relattn_drd_recompute, the same with the forward's phantom sum, and the fused pass (records from the prep pass) in
+    per-block mode; tests/test_relattn_owner_cases_gpu.py runs the fused pass in owner mode"""
+    run_backward(dev, shape, family, arm, monkeypatch.setenv, **(dict(dq_mode='slabs') if arm == 'fused' else {}))
 
 
 @pytest.mark.parametrize('shape,family,arm', [('t320_m256_part', 'random', 'dq8'), ('t320_m256_part', 'far-edge', 'sparse'),
@@ -304,7 +361,7 @@ FUSED = [(s, f) for s, f in CASES if 'fused' in arms_of(dims(s))]
 def test_backward_fused_records_and_delta(dev, monkeypatch, shape, family, records, delta_ready):
     """mxl_relattn_bwd_fused with the phantom records written by the forward, and with `delta` supplied by the caller (computed on
     the host in float64 from the device's out, rounded to float32); test_backward covers the prep pass with the kernel's own delta"""
-    run_backward(dev, shape, family, 'fused', monkeypatch.setenv, records=records, delta_ready=delta_ready)
+    run_backward(dev, shape, family, 'fused', monkeypatch.setenv, records=records, delta_ready=delta_ready, dq_mode='slabs')
 
 
 def _balance_multipliers(T, M, Kc, B, H):
@@ -332,8 +389,8 @@ def test_backward_fused_with_balanced_phantom_groups_in_a_child_process(dev):
     code = ('import os, sys, torch\n'
             f'sys.path.insert(0, {ROOT!r})\n'
             'from tests import test_relattn_cases_gpu as t\n'
-            f't.run_backward(torch.device("cuda:0"), {shape!r}, "random", "fused", os.environ.__setitem__)\n'
-            f't.run_backward(torch.device("cuda:0"), {shape!r}, "far-edge", "fused", os.environ.__setitem__, records="fwd")\n')
+            f't.run_backward(torch.device("cuda:0"), {shape!r}, "random", "fused", os.environ.__setitem__, dq_mode="slabs")\n'
+            f't.run_backward(torch.device("cuda:0"), {shape!r}, "far-edge", "fused", os.environ.__setitem__, records="fwd", dq_mode="slabs")\n')
     r = subprocess.run([sys.executable, '-c', code], env=dict(os.environ, MXL_DRD_PH_BALANCE='1'), cwd=ROOT, capture_output=True, text=True,
                        timeout=300)
     print(r.stdout)

@@ -13,10 +13,12 @@ Bounds:
   dq elementwise  |got - ref| <= 2^-8 |ref| + B_DQ max|ref|, the limits tests/test_relattn_cases_gpu.py applies to the fused arm
   dq relative L2  owner against float64 no larger than per-block's on the same input, times (1 + L2_MARGIN).  Both share the final
                   bf16 rounding and the operand roundings; owner mode drops the per-key-block ones.  CPU model of both summations
-                  (relattn_owner_ref.dq_models, seeds 0 .. 2, all five shapes): owner / per-block error ratio between 0.859 and
+                  (oracle.relattn_cases.dq_models, seeds 0 .. 2, all five shapes): owner / per-block error ratio between 0.859 and
                   0.953 (errors 2.9e-3 .. 3.0e-3 against 3.0e-3 .. 3.5e-3), never above 1 -- no margin is needed, L2_MARGIN = 0.
   dq              bit-identical between two owner-mode runs (no atomics on its path)
 The workspace is filled with NaN before every call: a first visit that read it would show in dq.
+(Every output of owner mode element-wise against float64, in canary frames and from non-zero start patterns, with the forward's
+records, a caller's delta, the engine's layout and the dispatch rules: tests/test_relattn_owner_cases_gpu.py.)
 """
 import pytest
 import torch
