@@ -416,6 +416,28 @@ int mxl_relattn_decode_split(const void* qkv, const void* kcache, const void* vc
 int mxl_relattn_decode_split_live(const void* qkv, const void* kcache, const void* vcache, const float* bd, const float* r_w_bias,
                                   void* out, const int* t_dev, int B, int H, int dh, int M, float scale, int pieces, float* ws,
                                   int* arrived, const int* unfinished, void* stream);
+/* FP8 K/V rings (opt-in).  A ring (B, H, M, dh) of bf16 is held as kc8 (B, H, M, dh) uint8 of OCP e4m3fn bytes and ke (B, H, M)
+ * int8 exponents, one per slot and head (vc8 / ve alike); the stored value is fp8 * 2^e.  For a row x of dh elements with
+ * amax = max|x| = m 2^k, m in [0.5, 1): e = k - 9 if m <= 0.875, else k - 8 (the smallest e with amax 2^-e <= 448), clamped to
+ * [-126, 127]; amax = 0 gives e = 0 and zero bytes; byte j = e4m3fn(x_j 2^-e), round to nearest even, subnormals kept.  Every
+ * dequantised value is a bf16 value.  Zero bytes with e = 0 are a zero memory (never-written slots, left-pad columns).
+ * dh = 16, 32 or 64 (else MXL_EUNSUPPORTED, nothing launched); kc8 / vc8 16-byte aligned.
+ *
+ * mxl_kv_append_fp8: mxl_kv_append on such rings -- slot *t_dev mod M of all four tensors <- the quantised k / v thirds of the
+ * (B, 3d) qkv rows, every other slot untouched; qr_out (B, d) bf16 = q + r_r_bias bit for bit as mxl_kv_append writes it, or NULL.
+ * *t_dev is read on the device (capture-safe). */
+int mxl_kv_append_fp8(const void* qkv, void* kc8, void* ke, void* vc8, void* ve, const int* t_dev, int B, int M, int d, int dh,
+                      const float* r_r_bias, void* qr_out, void* stream);
+/* mxl_kv_fill on fp8 rings: slots (p mod M) <- the quantised K / V rows of the last min(T, M) positions p of a (B, T, 3d) qkv buffer */
+int mxl_kv_fill_fp8(const void* qkv, void* kc8, void* ke, void* vc8, void* ve, int B, int T, int M, int d, int dh, void* stream);
+/* mxl_relattn_decode_split_live on fp8 rings: pieces 1..8 with ws (mxl_relattn_decode_split_ws_bytes) and arrived (B * H ints,
+ * zero before the first call, left zero) for pieces > 1, unfinished (B,) int32 or NULL.  Same arithmetic as the bf16 entry on the
+ * dequantised rings: q' = bf16(q + r_w_bias), f32 scores with the bd term, never-written slots as the positional term alone and
+ * counted in the denominator, P rounded to bf16 before the P V sum, pieces merged in piece order; the summation order within a
+ * row differs (16 elements per lane).  M * 4 + 1024 bytes of shared memory <= 64 KiB (else MXL_EINVAL, nothing launched). */
+int mxl_relattn_decode_fp8(const void* qkv, const void* kc8, const void* ke, const void* vc8, const void* ve, const float* bd,
+                           const float* r_w_bias, void* out, const int* t_dev, int B, int H, int dh, int M, float scale, int pieces,
+                           float* ws, int* arrived, const int* unfinished, void* stream);
 /* next token from log-probs (B, ldl): repetition penalty over the ids already in the row (positions 0..*t_dev; HF's
  * RepetitionPenaltyLogitsProcessor, 1.0 = off), then greedy argmax (do_sample=0) or temperature -> top-k -> top-p ->
  * typical-p (HF's TypicalLogitsWarper, 1.0 = off) -> renormalise -> multinomial (do_sample=1), as HF's logits warpers with

@@ -1075,8 +1075,21 @@ class ContrastiveStore:
             ops.row_inv_norm(self.ctx[b, :Tp], self.inv[b, :Tp], Tp)
 
 
+KV_DTYPES = {None: None, 'bf16': None, 'fp8': 'fp8', 'fp8_e4m3': 'fp8'}
+
+
+def resolve_kv_dtype(kv_cache_dtype: Optional[str]) -> Optional[str]:
+    """the K/V ring format of a call: None / 'bf16' -> None (bf16 rings), 'fp8' / 'fp8_e4m3' -> 'fp8'; a call that names none takes
+    MXL_KV_DTYPE (an A/B knob: unset, nothing changes).  Anything else is a ValueError."""
+    if kv_cache_dtype is None:
+        kv_cache_dtype = os.environ.get('MXL_KV_DTYPE') or None
+    if kv_cache_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_cache_dtype={kv_cache_dtype!r}: expected None, 'bf16', 'fp8' or 'fp8_e4m3'")
+    return KV_DTYPES[kv_cache_dtype]
+
+
 class XLDecoder(RuledGenerate):
-    def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77):
+    def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77, kv_dtype: Optional[str] = None):
         self.eng = engine
         c = engine.cfg
         self.B, self.Tmax = batch, max_total_len
@@ -1084,8 +1097,21 @@ class XLDecoder(RuledGenerate):
         d, M, L, Fi = c.d_model, c.mem_len, c.n_layer, c.d_inner
         bf = dict(device=dev, dtype=torch.bfloat16)
         H, dh = c.n_head, c.d_head
-        self.kc = [torch.zeros(batch, H, M, dh, **bf) for _ in range(L)]    # head-major rings
-        self.vc = [torch.zeros(batch, H, M, dh, **bf) for _ in range(L)]
+        if kv_dtype not in (None, 'fp8'):
+            raise ValueError(f"kv_dtype={kv_dtype!r}: expected None (bf16 rings) or 'fp8'")
+        self.kv_dtype = kv_dtype
+        if kv_dtype == 'fp8':
+            # e4m3fn bytes with one int8 exponent per slot and head ("FP8 rings"): (dh + 1) / (2 dh) of the bf16 bytes
+            if dh not in (16, 32, 64):
+                raise MusicXLError(f'fp8 K/V rings need a head width of 16, 32 or 64, not {dh}')
+            self.kc = [torch.zeros(batch, H, M, dh, device=dev, dtype=torch.uint8) for _ in range(L)]
+            self.vc = [torch.zeros(batch, H, M, dh, device=dev, dtype=torch.uint8) for _ in range(L)]
+            self.ke = [torch.zeros(batch, H, M, device=dev, dtype=torch.int8) for _ in range(L)]
+            self.ve = [torch.zeros(batch, H, M, device=dev, dtype=torch.int8) for _ in range(L)]
+        else:
+            self.kc = [torch.zeros(batch, H, M, dh, **bf) for _ in range(L)]    # head-major rings
+            self.vc = [torch.zeros(batch, H, M, dh, **bf) for _ in range(L)]
+            self.ke = self.ve = []
         self.rd = None                                  # per-layer Rd tables (eval: no dropout on pos_emb)
         self.ids = torch.zeros(batch, max_total_len + 1, device=dev, dtype=torch.int64)
         self.t_dev = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -1154,7 +1180,7 @@ class XLDecoder(RuledGenerate):
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
         self._tables()
-        for k in self.kc + self.vc:
+        for k in self.kc + self.vc + self.ke + self.ve:     # (fp8: zero bytes with e = 0 are the zero memories)
             k.zero_()
         self.ids.zero_()
         self.ids[:, :Tp].copy_(prompt)
@@ -1165,10 +1191,13 @@ class XLDecoder(RuledGenerate):
             self.ids[:, :Tp].masked_fill_(pad, -1)
             x = x.masked_fill(pad, 0)
         self.rules.start(self.ids, Tp, c.vocab_size, rules)
-        sink_kc, sink_vc = self.kc, self.vc
+        sink_kc, sink_vc, sink_ke, sink_ve = self.kc, self.vc, self.ke, self.ve
 
         def kv_sink(l, qkv):
-            ops.kv_fill(qkv, sink_kc[l], sink_vc[l], Tp)
+            if sink_ke:
+                ops.kv_fill_fp8(qkv, sink_kc[l], sink_ke[l], sink_vc[l], sink_ve[l], Tp)
+            else:
+                ops.kv_fill(qkv, sink_kc[l], sink_vc[l], Tp)
 
         out = e.forward(x, mems=None, labels=None, train=False, want_logprobs=False, kv_sink=kv_sink, n_pad=n_pad)
         ws = e._last
@@ -1231,15 +1260,24 @@ class XLDecoder(RuledGenerate):
         for l in range(L):
             h_in, h_out = self.h[l & 1], self.h[(l + 1) & 1]
             rrb = e._lw(l, 'dec_attn.r_r_bias', e.P)
-            if B <= 64:      # projection, ring append and q + r_r_bias in one launch
+            live = None if self.rules.stop is None else self.unfinished
+            if self.kv_dtype == 'fp8':
+                # projection, then the quantising append (one launch more per layer than the fused bf16 form below), then the fp8 reader
+                G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
+                ops.kv_append_fp8(self.qkv, self.kc[l], self.ke[l], self.vc[l], self.ve[l], self.t_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
+                ops.relattn_decode_fp8(self.qkv, self.kc[l], self.ke[l], self.vc[l], self.ve[l], self.rd[l],
+                                       e._lw(l, 'dec_attn.r_w_bias', e.P), rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True,
+                                       split=self.split, pieces=self.pieces, unfinished=live)
+            elif B <= 64:      # projection, ring append and q + r_r_bias in one launch
                 ops.decode_qkv(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, self.kc[l], self.vc[l], self.t_dev,
                                rrb.reshape(-1), self.qr, dh)
             else:
                 G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
                 ops.kv_append(self.qkv, self.kc[l], self.vc[l], self.t_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
-            ops.relattn_decode(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P),
-                               rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces,
-                               unfinished=None if self.rules.stop is None else self.unfinished)
+            if self.kv_dtype != 'fp8':
+                ops.relattn_decode(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P),
+                                   rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces,
+                                   unfinished=live)
             G(self.av, e._lw(l, 'dec_attn.o_net.weight'), self.tmp, B, d, d)
             ops.ln_residual_fwd(self.tmp, h_in, e._lw(l, 'dec_attn.layer_norm.weight', e.P),
                                 e._lw(l, 'dec_attn.layer_norm.bias', e.P), self.h1, eps=c.layer_norm_epsilon)
@@ -1274,7 +1312,13 @@ class XLDecoder(RuledGenerate):
             ops.adaptive_logprob(self.logits, self.logp, B, c.vocab_size, tuple(c.cutoffs))
 
     # ---------------------------------------------------------------- beam-search hooks (see beam_search below)
+    def _bf16_rings_only(self, what: str):
+        """the searches move rings with mxl_beam_reorder / mxl_ring_slot_broadcast / index_select, which know the bf16 layout alone"""
+        if self.kv_dtype is not None:
+            raise ValueError(f'{what} does not take {self.kv_dtype} K/V rings')
+
     def beam_prefill(self, prompt: torch.Tensor):
+        self._bf16_rings_only('beam search')
         self.prefill(prompt, None)
 
     def beam_logp(self) -> torch.Tensor:
@@ -1305,6 +1349,7 @@ class XLDecoder(RuledGenerate):
         sample: beam-sample, ng = 1 -- the step draws its candidates (mxl_beam_sample_draw under the warpers top_k / top_p / temperature
         / typical_p with the decoder's seed, into the decoder's `drawn` buffer) and walks them with mxl_beam_sample_step; the draw
         counter starts at 0, so a seed gives one result.  The flag and the warpers are part of the graph key, `drawn` is step state."""
+        self._bf16_rings_only('beam search on the device')
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         if nb < 2 or nb > BEAM_MAX or self.B % nb:
@@ -1372,6 +1417,7 @@ class XLDecoder(RuledGenerate):
         contrastive step (`_capture`) + the first token, chosen by one step run here; returns the number of `replay_once()` calls that
         complete the generation to max_length.  The store's words and the log-probabilities are this step's own state (its context
         rows need no snapshot: a step writes position t and reads those below it)."""
+        self._bf16_rings_only('contrastive search')
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         if K < 2 or K > CONTRASTIVE_MAX or self.B % K:
@@ -1455,7 +1501,7 @@ class XLDecoder(RuledGenerate):
         carries from one step to the next"""
         if self.graph is not None and self._graph_key == key:
             return
-        live = (self.t_dev, self.rng, self.ids, *self.kc, *self.vc, *extra)
+        live = (self.t_dev, self.rng, self.ids, *self.kc, *self.vc, *self.ke, *self.ve, *extra)
         saved, words = [t.clone() for t in live], self.rules.snapshot()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -1485,13 +1531,13 @@ class XLDecoderLanes(RuledGenerate):
     overlap the other's ring streaming (sequences are independent: the lanes never synchronise until the generation ends).
     Same interface as XLDecoder for `generate` / `begin` / `replay_once`; rows keep their order."""
 
-    def __init__(self, engine, batch: int, max_total_len: int, seed: int = 1234, lanes: int = 2):
+    def __init__(self, engine, batch: int, max_total_len: int, seed: int = 1234, lanes: int = 2, kv_dtype: Optional[str] = None):
         assert 1 <= lanes <= batch
-        self.B, self.Tmax, self.n = batch, max_total_len, lanes
+        self.B, self.Tmax, self.n, self.kv_dtype = batch, max_total_len, lanes, kv_dtype
         self.sizes = [batch // lanes + (1 if i < batch % lanes else 0) for i in range(lanes)]
         self.offs = [sum(self.sizes[:i]) for i in range(lanes + 1)]
         # (the sampler draws per (seed, row, step): a different seed per lane keeps the lanes' draws independent)
-        self.lanes = [XLDecoder(engine, b, max_total_len, seed=seed + 7919 * i) for i, b in enumerate(self.sizes)]
+        self.lanes = [XLDecoder(engine, b, max_total_len, seed=seed + 7919 * i, kv_dtype=kv_dtype) for i, b in enumerate(self.sizes)]
         self.streams = [torch.cuda.Stream() for _ in range(lanes)]
 
     def invalidate_tables(self):

@@ -1018,6 +1018,31 @@ def kv_fill(qkv, kc, vc, T):
     check(lib().mxl_kv_fill(_p(qkv), _p(kc), _p(vc), B, T, M, H * dh, dh, _stream()), 'mxl_kv_fill')
 
 
+def _req_fp8_rings(kc8, ke, vc8, ve, what):
+    """fp8 rings: kc8 / vc8 (B, H, M, dh) uint8 of e4m3fn bytes, ke / ve (B, H, M) int8 exponents, all contiguous"""
+    for t, dt in ((kc8, torch.uint8), (vc8, torch.uint8), (ke, torch.int8), (ve, torch.int8)):
+        _req(t, dt, what)
+        if not t.is_contiguous():
+            raise MusicXLError(f'{what}: fp8 rings and their exponents must be contiguous')
+    if kc8.dim() != 4 or vc8.shape != kc8.shape or ke.shape != kc8.shape[:3] or ve.shape != kc8.shape[:3]:
+        raise MusicXLError(f'{what}: expected (B, H, M, dh) byte rings with (B, H, M) exponents')
+
+
+def kv_append_fp8(qkv, kc8, ke, vc8, ve, t_dev, rrb=None, qr_out=None):
+    """kv_append on fp8 rings (mxl_kv_append_fp8): slot t mod M of the bytes and exponents <- the quantised k / v of the qkv rows"""
+    _req_fp8_rings(kc8, ke, vc8, ve, 'kv_append_fp8')
+    B, H, M, dh = kc8.shape
+    check(lib().mxl_kv_append_fp8(_p(qkv), _p(kc8), _p(ke), _p(vc8), _p(ve), _p(t_dev), B, M, H * dh, dh, _p(rrb), _p(qr_out),
+                                  _stream()), 'mxl_kv_append_fp8')
+
+
+def kv_fill_fp8(qkv, kc8, ke, vc8, ve, T):
+    """kv_fill on fp8 rings (mxl_kv_fill_fp8)"""
+    _req_fp8_rings(kc8, ke, vc8, ve, 'kv_fill_fp8')
+    B, H, M, dh = kc8.shape
+    check(lib().mxl_kv_fill_fp8(_p(qkv), _p(kc8), _p(ke), _p(vc8), _p(ve), B, T, M, H * dh, dh, _stream()), 'mxl_kv_fill_fp8')
+
+
 def kv_zero_pad(qkv, n_pad, B, T, d):
     """left-padded prompt pass: k = v = 0 in the first n_pad[b] rows of every sequence of the (B, T, 3d) bf16 qkv buffer.
     n_pad: (B,) int32 on the device"""
@@ -1080,6 +1105,28 @@ def relattn_decode(qkv, kc, vc, rd, rwb, rrb, out, t_dev, H, dh, qr_buf, bd_buf,
         return
     check(lib().mxl_relattn_decode(_p(qkv), _p(kc), _p(vc), _p(bd_buf), _p(rwb), _p(out), _p(t_dev), B, H, dh, M,
                                    float(scale), _stream()), 'mxl_relattn_decode')
+
+
+def relattn_decode_fp8(qkv, kc8, ke, vc8, ve, rd, rwb, rrb, out, t_dev, H, dh, qr_buf, bd_buf, scale=None, qr_ready=False, split=None,
+                       pieces=1, unfinished=None):
+    """relattn_decode over fp8 rings (mxl_relattn_decode_fp8): the same BD launch, then the one fp8 attention entry"""
+    _req_fp8_rings(kc8, ke, vc8, ve, 'relattn_decode_fp8')
+    B, _, M, _ = kc8.shape
+    d = H * dh
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    if not qr_ready:
+        add_rowbias(qkv, 3 * d, 3 * d, rrb.reshape(-1), qr_buf, B, 1, d)
+    if dh == 64 and B <= 64:
+        check(lib().mxl_decode_bd(_p(qr_buf), _p(rd), _p(bd_buf), B, H, dh, M, d, rd.stride(0), _stream()), 'mxl_decode_bd')
+    else:
+        gemm_batched(qr_buf, rd, bd_buf, B, M, dh, lda=d, ldb=d, ldc=H * M, flags=GEMM_OUT_F32, batch=H, bdiv=1,
+                     sA=(dh, 0), sB=(dh, 0), sC=(M, 0))
+    if unfinished is not None:
+        _req(unfinished, torch.int32, 'relattn_decode_fp8 unfinished')
+    n = pieces if (split is not None and pieces > 1) else 1
+    check(lib().mxl_relattn_decode_fp8(_p(qkv), _p(kc8), _p(ke), _p(vc8), _p(ve), _p(bd_buf), _p(rwb), _p(out), _p(t_dev), B, H, dh, M,
+                                       float(scale), n, _p(split[0]) if n > 1 else 0, _p(split[1]) if n > 1 else 0,
+                                       _p(unfinished), _stream()), 'mxl_relattn_decode_fp8')
 
 
 _sample_scratch = {}

@@ -200,7 +200,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
                  min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, melody=None,
                  device_scorer: bool = False, register=None, melody_range=None, bass_range=None, bass_below=None,
-                 **unused) -> torch.Tensor:
+                 kv_cache_dtype: Optional[str] = None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -315,11 +315,21 @@ class MyTransfoXLLMHeadModel(EngineModule):
         `in_key` / `key` with the checks above, given an explicit `eos_token_id=` (without one they stay refused, as before): per-prompt
         values are shared by the prompt's `top_k` rows, a barred token is -inf before the top-k, where HF's logits processors sit, and
         a barred candidate is never picked.  `n_bars`, `melody` and padded prompts stay refused.  `top_k > 32` or
-        `MXL_CONTRASTIVE_HOST=1` keeps the host-driven loop (`generate.contrastive_search`), which takes no rules here."""
+        `MXL_CONTRASTIVE_HOST=1` keeps the host-driven loop (`generate.contrastive_search`), which takes no rules here.
+
+        `kv_cache_dtype` (greedy decoding and sampling): the format of the decoder's K/V rings.  None or 'bf16': bf16, as ever.  'fp8'
+        (alias 'fp8_e4m3'): OCP e4m3fn bytes with one power-of-two int8 exponent per ring slot and head (DESIGN.md, FP8 rings) --
+        (dh + 1) / (2 dh) of the ring memory and of the attention launch's bytes, at the price of K and V rounded to four
+        significant bits, so the output is another one than the bf16 rings give.  It combines with everything greedy decoding and
+        sampling take (rules, eos, padded prompts, `num_return_sequences`, the two-lane decoder, `use_graph`, the large-vocabulary
+        sampler).  Beam, beam-sample, group-beam and contrastive search refuse 'fp8' (ValueError): they move rings with
+        mxl_beam_reorder / mxl_ring_slot_broadcast, which know the bf16 layout alone.  Any other string is a ValueError.
+        `MXL_KV_DTYPE=fp8` sets the default of calls that do not pass the keyword (an A/B knob; unset, nothing changes)."""
         from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, beam_generate, beam_sample_device,
                                beam_search_device, check_grammar_args, contrastive_search, contrastive_search_device,
-                               group_beam_search_device, left_pad_counts, plan_search, resolve_max_length, rules_config, sampling_config,
-                               stop_config)
+                               group_beam_search_device, left_pad_counts, plan_search, resolve_kv_dtype, resolve_max_length,
+                               rules_config, sampling_config, stop_config)
+        kv_dtype = resolve_kv_dtype(kv_cache_dtype)
         n_pad = None
         if attention_mask is not None:
             pads = left_pad_counts(attention_mask, tuple(input_ids.shape))
@@ -343,6 +353,10 @@ class MyTransfoXLLMHeadModel(EngineModule):
                            grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody, device_scorer=device_scorer,
                            repetition_penalty=repetition_penalty, renormalize_logits=renormalize_logits,
                            vocab_size=self.config.vocab_size, register=register)
+        if kv_dtype is not None and plan.strategy != 'sample':
+            name = dict(beam='beam', beam_sample='beam-sample', group_beam='group-beam', contrastive='contrastive')[plan.strategy]
+            raise ValueError(f"kv_cache_dtype='{kv_dtype}' is not supported under {name} search: it moves rings with "
+                             'mxl_beam_reorder / mxl_ring_slot_broadcast, which take bf16 rings alone; greedy decoding and sampling do')
         B0 = input_ids.shape[0]
         ranges = dict(register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below)
         rules = rules_config(batch=B0, vocab_size=self.config.vocab_size, stop=stop, grammar=grammar, n_bars=n_bars, in_key=in_key,
@@ -386,9 +400,10 @@ class MyTransfoXLLMHeadModel(EngineModule):
         dec = getattr(self, '_decoder', None)
         # two free-running half-batch lanes from 32 rows on (generate.XLDecoderLanes); MXL_DECODE_LANES=1 keeps one decoder
         lanes = max(1, int(os.environ.get('MXL_DECODE_LANES', '2'))) if (B >= 32 and use_graph) else 1
-        if dec is None or dec.B != B or dec.Tmax < max_length or getattr(dec, 'n', 1) != lanes:
-            dec = self._decoder = (XLDecoderLanes(self.engine, B, max_length, seed=seed, lanes=lanes) if lanes > 1
-                                   else XLDecoder(self.engine, B, max_length, seed=seed))
+        if (dec is None or dec.B != B or dec.Tmax < max_length or getattr(dec, 'n', 1) != lanes
+                or getattr(dec, 'kv_dtype', None) != kv_dtype):
+            dec = self._decoder = (XLDecoderLanes(self.engine, B, max_length, seed=seed, lanes=lanes, kv_dtype=kv_dtype) if lanes > 1
+                                   else XLDecoder(self.engine, B, max_length, seed=seed, kv_dtype=kv_dtype))
         dec.invalidate_tables()
         return dec.run(input_ids.to(self.device), max_length,
                        sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), rules, use_graph,
