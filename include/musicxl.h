@@ -482,6 +482,11 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  *   `cls`.  In a row with bar > 0 a token is barred if its slots entry exceeds rem or its class is in need_free at rem == 0 or in
  *   need_full at rem > 0; rows with bar == 0 are untouched.  A token moves the row: a bars entry sets bar (rem = 0), a class in opens
  *   sets rem = bar, a slots entry k takes k from rem.  The rule never reads the grammar state.
+ *   Format of a slots entry k other than 0xFFFF: bits 0..14 are the slots the token TAKES from rem, and bit 15 set means it NEEDS one
+ *   more free than it takes: the token is barred unless (k & 0x7FFF) + (k >> 15) <= rem, and a kept one leaves rem - (k & 0x7FFF).
+ *   That is for a token that stands for several base tokens and ends on an open note start (grammar.subword_grammar: `pitch
+ *   duration pitch`), whose open pitch still needs a duration.  Entries below 0x8000 therefore mean what they always meant, and
+ *   0xFFFF stays "unknown length": barred in a row with bar > 0, admitted in a row with bar == 0.
  * count: count, end, gleft -- a row opens exactly as many further bars as it was asked for.  Per row one int32 word: gleft, the bars
  *   the row may still open; < 0 = no limit, the row is untouched.  count and end are class bit masks over the classes of `cls` (the
  *   music grammar: <bar> and </s>).  A class in count is barred at gleft == 0, a class in end while gleft > 0, and a kept token of a

@@ -361,7 +361,8 @@ __global__ __launch_bounds__(256) void decode_bd_kernel(const bf16_t* qr, const 
 constexpr int SORT_N = 2048;
 
 // token v under a row's words (rules_load below): its class under the allow word (c: a rule over classes is on), with the bar budget
-// the slots the row still has free, with the key rule the pitch classes of the row's key.  `inkey` has bits 12..31 set, and a token
+// the slots the row still has free (against what the token needs: slots_need), with the key rule the pitch classes of the row's
+// key.  `inkey` has bits 12..31 set, and a token
 // that is no pitch has pcs 0xFF, which tests bit 31: one byte load and one shift, no branch.  `forced` >= 0 (gd: the guide group is
 // on): the row is fed that token from its guide -- it alone is allowed, whatever the other groups say.  `rw` (rg: the register group
 // is on): the open part's bounds as register_word packs them; a pitch passes the one unsigned compare reg[v] - lo <= hi - lo, and a
@@ -370,11 +371,17 @@ struct RegWord {
     const unsigned char* reg;
     uint32_t lo, span;
 };
+// A `slots` entry k (DecodeRules, budget): bits 0..14 are the slots the token takes, bit 15 says that it needs one more free than it
+// takes (a sub-word token that ends on an open note start: the pitch it leaves open still needs a duration).  0xFFFF is not such a
+// pair but "unknown length", beyond every rem and within BUDGET_NONE alone.  Entries without bit 15 read as they always did.
+constexpr int SLOTS_RARE = 0xFFFF;
+__device__ __forceinline__ int slots_take(int k) { return k & 0x7FFF; }
+__device__ __forceinline__ int slots_need(int k) { return k == SLOTS_RARE ? k : (k & 0x7FFF) + (k >> 15); }
 __device__ __forceinline__ bool token_allowed(const unsigned char* cls, uint32_t allow, const unsigned short* slots, int remcap,
                                               const unsigned char* pcs, uint32_t inkey, long long v, bool c, bool bud, bool ink,
                                               bool gd = false, int forced = -1, bool rg = false, RegWord rw = RegWord{nullptr, 0u, 127u}) {
     if (gd && forced >= 0) return v == forced;
-    bool ok = (!c || ((allow >> cls[v]) & 1u)) && (!bud || (int)slots[v] <= remcap) && (!ink || ((inkey >> (pcs[v] & 31)) & 1u));
+    bool ok = (!c || ((allow >> cls[v]) & 1u)) && (!bud || slots_need(slots[v]) <= remcap) && (!ink || ((inkey >> (pcs[v] & 31)) & 1u));
     if (rg) {
         const uint32_t p = rw.reg[v];
         ok = ok && ((uint32_t)(p - rw.lo <= rw.span) | (p >> 7));
@@ -610,7 +617,10 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 //   grammar  a token class automaton: cls (V,) token -> class, allow (S,) bit c = class c may follow in state s, next (S, C) successor
 //   budget   grammar.BarBudget: per row `bar` (bar length in slots, 0 = unconstrained) and `rem` (slots still free in the open
 //            channel).  slots (V,) uint16: duration token -> slots, 0 = no duration, 0xFFFF = unknown length; bars (V,) uint16: time
-//            signature token -> bar length, 0xFFFF = no time signature; opens / need_free / need_full: class bit masks
+//            signature token -> bar length, 0xFFFF = no time signature; opens / need_free / need_full: class bit masks.  Any other
+//            slots entry is a pair: bits 0..14 = the slots the token takes from rem, bit 15 = it needs one more free than it takes
+//            (grammar.subword_grammar: a token over several base tokens that ends on an open note start); read by slots_take /
+//            slots_need in token_allowed, budget_move and budget_scan_kernel and nowhere else
 //   count    grammar.BarCount: per row `left`, the bars the row may still open (< 0 = no limit, the row is untouched).  A class in
 //            `count` (<bar>) is barred at left == 0, a class in `end` (</s>) while left > 0, and a kept token of a `count` class
 //            takes 1 from a positive left
@@ -671,13 +681,13 @@ constexpr int BUDGET_NONE = 0xFFFF;          // slots: unknown length (beyond an
 __device__ __forceinline__ uint32_t budget_deny(int bar, int rem, uint32_t need_free, uint32_t need_full) {
     return bar > 0 ? (rem > 0 ? need_full : need_free) : 0u;
 }
-// the largest `slots` entry the row admits
+// the largest need (slots_need) the row admits
 __device__ __forceinline__ int budget_remcap(int bar, int rem) { return bar > 0 ? rem : BUDGET_NONE; }
-// (bar, rem) after a token of class c with slots entry k and bars entry sig (BarBudget.move)
+// (bar, rem) after a token of class c with slots entry k and bars entry sig (BarBudget.move): the token takes slots_take(k)
 __device__ __forceinline__ void budget_move(int& bar, int& rem, int c, int k, int sig, uint32_t opens) {
     if (sig != BUDGET_NONE) { bar = sig; rem = 0; }
     if ((opens >> c) & 1u) rem = bar;
-    if (bar > 0 && k != BUDGET_NONE) rem = max(rem - k, 0);
+    if (bar > 0 && k != BUDGET_NONE) rem = max(rem - slots_take(k), 0);
 }
 // classes a row with `left` bars to go bars: the end while bars are owed, another bar once none is
 __device__ __forceinline__ uint32_t barcount_deny(int left, uint32_t count, uint32_t end) {
@@ -980,7 +990,7 @@ __global__ __launch_bounds__(64) void budget_scan_kernel(const long long* ids, i
             const int kj = __shfl(ks, j, 64);
             if (cj < 0) continue;
             const int k = kj & 0xFFFF, sig = (kj >> 16) & 0xFFFF;
-            if (((budget_deny(bar, rem, need_free, need_full) >> cj) & 1u) || k > budget_remcap(bar, rem)) { bad = base + j; break; }
+            if (((budget_deny(bar, rem, need_free, need_full) >> cj) & 1u) || slots_need(k) > budget_remcap(bar, rem)) { bad = base + j; break; }
             budget_move(bar, rem, cj, k, sig, opens);
         }
     }

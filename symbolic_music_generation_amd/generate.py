@@ -561,7 +561,7 @@ def raise_on_bad_prompt(grammar, ids: torch.Tensor, first_bad: torch.Tensor):
     for b, col in enumerate(over):
         if col >= 0:
             tok = int(ids[b, col])
-            how = 'overfills' if int(grammar.budget.slots[tok]) > 0 else 'underfills'
+            how = 'overfills' if grammar.budget.slots_need(int(grammar.budget.slots[tok])) > 0 else 'underfills'
             raise MusicXLError(f'the prompt of row {b} {how} a bar at column {col}: token {tok} does not fit the slots its time '
                                f'signature leaves there ({sum(1 for c in over if c >= 0)} of {len(over)} rows break the bar budget)')
 

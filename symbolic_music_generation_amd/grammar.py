@@ -30,6 +30,14 @@ slots still free in the open channel).  Its tables sit beside the grammar's:
 and a duration of k slots is allowed only if k <= rem.  The rule looks at the token's class and the two integers alone, never at the
 automaton state, so it needs no state of its own and composes with any mask the grammar applies.
 
+Format of a `slots` entry s other than RARE_SLOTS: bits 0..14 are the slots the token TAKES (`slots_take`), and bit 15 (`NEED_ONE_MORE`)
+says that it NEEDS one more free than it takes (`slots_need` = (s & 0x7FFF) + (s >> 15)): the token is allowed only if its need
+<= rem, and moves rem by its take.  No base vocabulary sets bit 15 -- a duration is far below 0x8000 slots -- so their tables read as
+they always did.  The bit is for `subword_grammar(base, pieces)`, the grammar of a sub-word tokenizer (`PairMergeTokenizer.grammar()`,
+`WordPieceMusicTokenizer.grammar()`): a sub-word id stands for a fixed sequence of base tokens, so it induces a partial function on
+the base automaton's states -- ids with the same function share a token class -- takes the sum of its durations' slots, and, where it
+ends on an open note start (`pitch duration pitch`), needs one more, because the pitch it leaves open still needs a duration.
+
 Both forms of the music grammar also carry a `BarCount` (`grammar.bar_count`), the rule behind `generate(..., n_bars=k)`: one more
 integer per row, `left` = the bars the row may still open (negative = no limit, the row is untouched), and two class bit masks
 
@@ -85,6 +93,7 @@ import numpy as np
 MAX_CLASSES = 32
 MAX_STATES = 256
 RARE_SLOTS = 0xFFFF        # `slots` entry of a duration token of unknown length: barred in a constrained bar
+NEED_ONE_MORE = 0x8000     # bit 15 of a `slots` entry other than RARE_SLOTS: the token needs one slot more free than it takes
 NO_SIG = 0xFFFF            # `bars` entry of a token that is no time signature
 NO_KEY = 0xFF              # `keys` entry of a token that is no key token
 NO_PITCH = 0xFF            # `pcs` entry of a token that is no pitch
@@ -286,11 +295,22 @@ class BarBudget:
         grammar.budget = self
 
     # ---------------------------------------------------------------- the rule
+    @staticmethod
+    def slots_take(k: int) -> int:
+        """the slots a token with `slots` entry k takes from rem (module docstring; RARE_SLOTS takes nothing: it is never kept
+        in a constrained row)"""
+        return 0 if k == RARE_SLOTS else k & (NEED_ONE_MORE - 1)
+
+    @staticmethod
+    def slots_need(k: int) -> int:
+        """the free slots a token with `slots` entry k needs: its take, one more with bit 15; RARE_SLOTS is beyond any rem"""
+        return k if k == RARE_SLOTS else (k & (NEED_ONE_MORE - 1)) + (k >> 15)
+
     def allows(self, bar: int, rem: int, c: int, k: int) -> bool:
         """may a token of class c and `slots` entry k follow in a row at (bar, rem)?  (what the grammar state says comes on top)"""
         if bar <= 0:
             return True
-        if k > rem:                                      # a duration that overfills the channel; RARE_SLOTS is beyond any rem
+        if self.slots_need(k) > rem:                     # a duration that overfills the channel; RARE_SLOTS is beyond any rem
             return False
         if (self.need_free >> c) & 1 and rem <= 0:
             return False
@@ -305,7 +325,7 @@ class BarBudget:
         if (self.opens >> c) & 1:
             rem = bar
         if bar > 0 and k != RARE_SLOTS:
-            rem = max(rem - k, 0)
+            rem = max(rem - self.slots_take(k), 0)
         return bar, rem
 
     def _reachable(self) -> Dict[Tuple[int, int, int], int]:
@@ -370,7 +390,8 @@ class BarBudget:
         return self._dev[key]
 
     def __repr__(self):
-        return f'BarBudget(bars={sorted(set(self.bars.tolist()) - {NO_SIG})}, durations={int(((self.slots > 0) & (self.slots < RARE_SLOTS)).sum())})'
+        timed = (self.slots != RARE_SLOTS) & ((self.slots & (NEED_ONE_MORE - 1)) > 0)
+        return f'BarBudget(bars={sorted(set(self.bars.tolist()) - {NO_SIG})}, durations={int(timed.sum())})'
 
 
 def _class_mask(grammar: TokenGrammar, x) -> int:
@@ -870,7 +891,8 @@ MUSIC_BUDGET_CLASSES = dict(opens=('<melody>', '<bass>'), need_free=('pitch', '<
 def music_budget_tables(vocab) -> dict:
     """slots and bars of a MusicVocabulary: a duration token d_x is x / (4 / 2**precision) slots (always whole: that is how the
     vocabulary lists its durations), d_rare is RARE_SLOTS; TimeSig_n/d is a bar of 2**precision * n / d slots, and TimeSig_rare or a
-    bar that is no whole number of slots is 0 = unconstrained"""
+    bar that is no whole number of slots is 0 = unconstrained.  Every duration is below NEED_ONE_MORE (checked): bit 15 of a `slots`
+    entry, "needs one more than it takes", is never set here -- only `subword_grammar` sets it"""
     from fractions import Fraction
     V = len(vocab)
     slot = Fraction(4, 2 ** vocab.precision)
@@ -879,7 +901,7 @@ def music_budget_tables(vocab) -> dict:
         typ = vocab.type(tok)
         if typ == 'duration':
             n = None if tok == vocab.rare_duration else Fraction(tok[2:]) / slot
-            if n is not None and (n.denominator != 1 or not 0 < n < RARE_SLOTS):
+            if n is not None and (n.denominator != 1 or not 0 < n < NEED_ONE_MORE):
                 raise ValueError(f'duration token {tok!r} is no whole number of slots')
             slots[i] = RARE_SLOTS if n is None else int(n)
         elif typ == 'time_sig':
@@ -905,3 +927,95 @@ def music_grammar(vocab, bar_budget: bool = False) -> TokenGrammar:
     return from_transitions(cls, MUSIC_CLASSES, MUSIC_TRANSITIONS, 'S0', accepting=['END'],
                             budget=music_budget_tables(vocab) if bar_budget else None, bar_count=MUSIC_BAR_COUNT_CLASSES,
                             guide=MUSIC_GUIDE_CLASSES)
+
+
+# -------------------------------------------------------------------- sub-word vocabularies
+def subword_grammar(base: TokenGrammar, pieces: Sequence[Sequence[int]]) -> TokenGrammar:
+    """`base` composed with a sub-word vocabulary: pieces[v] = the base ids that id v stands for (`id2base_ids()` of a sub-word
+    tokenizer).  The rule is defined on the DECODED stream: a row of ids is allowed iff the concatenation of its pieces is allowed
+    under `base` -- and its budget and bar count, which the result carries if `base` does (never its guide).
+
+    States, start and accepting states are the base's.  A single-base id keeps the class (index and name) of its base token, so the
+    class masks of the budget and the count carry over bit for bit.  A multi-base id gets the class of the partial function it
+    induces on the states -- `base.allow` / `base.next` walked over its pieces, undefined where a step is barred; ids with the same
+    function share a class, and one whose function is defined nowhere gets a class that no state allows.  More than MAX_CLASSES
+    classes: NotImplementedError.
+
+    Budget: a single keeps its `slots` and `bars` entries.  A multi has bars = NO_SIG and slots = the sum k of its durations' slots
+    (RARE_SLOTS if one of them is rare), with NEED_ONE_MORE on top where walking its pieces through the base budget needs k + 1
+    free -- which, for every sequence the base grammar admits anywhere, is: its last base token is of a `need_free` class (it ends
+    on an open note start).  The table cannot say more: a multi that holds a token of an `opens` or `need_full` class or a time
+    signature (under a bar count: of a `count` or `end` class) raises NotImplementedError naming the id and the token; a sum that
+    does not fit 15 bits raises ValueError."""
+    S, C0, V0 = base.n_states, base.n_classes, base.vocab_size
+    bud, cnt = base.budget, base.bar_count
+    cls = np.zeros(len(pieces), dtype=np.int64)
+    slots = np.zeros(len(pieces), dtype=np.uint16)
+    bars = np.full(len(pieces), NO_SIG, dtype=np.uint16)
+    names, funcs = list(base.class_names), {}                         # funcs: the function as a tuple over the states -> class
+    for v, seq in enumerate(pieces):
+        seq = [int(p) for p in seq]
+        if not seq or any(not 0 <= p < V0 for p in seq):
+            raise ValueError(f'sub-word id {v}: its pieces {seq} are no non-empty list of base ids below {V0}')
+        if len(seq) == 1:
+            cls[v] = base.cls[seq[0]]
+            if bud is not None:
+                slots[v], bars[v] = bud.slots[seq[0]], bud.bars[seq[0]]
+            continue
+        cs = [int(base.cls[p]) for p in seq]
+        fn = []
+        for s in range(S):
+            for c in cs:
+                if s < 0 or not (int(base.allow[s]) >> c) & 1:
+                    s = -1
+                    break
+                s = int(base.next[s, c])
+            fn.append(s)
+        fn = tuple(fn)
+        if fn not in funcs:
+            name = '+'.join(base.class_names[c] for c in cs)
+            funcs[fn] = len(names)
+            names.append(name if name not in names else f'{name}#{len(names)}')
+        cls[v] = funcs[fn]
+        fixed = 0 if bud is None else bud.opens | bud.need_full       # classes whose effect on (bar, rem) a slots entry cannot carry
+        fixed |= 0 if cnt is None else cnt.count | cnt.end            # ... and those the bar count reads: it sees the multi's class
+        for p, c in zip(seq, cs):
+            if (fixed >> c) & 1 or (bud is not None and int(bud.bars[p]) != NO_SIG):
+                raise NotImplementedError(f'sub-word id {v} holds base token {p} of class {base.class_names[c]!r} among its pieces '
+                                          f'{seq}: a token that opens or closes a channel or a bar, ends the stream or sets the time '
+                                          'signature must be a sub-word id of its own (a WordPiece tokenizer trained with '
+                                          'punctuate=True and independent_global_token=True keeps them apart)')
+        if bud is None:
+            continue
+        take, need, rare = 0, 0, False
+        for p, c in zip(seq, cs):
+            k = int(bud.slots[p])
+            if k == RARE_SLOTS:
+                rare = True
+                break
+            need = max(need, take + BarBudget.slots_need(k), take + ((bud.need_free >> c) & 1))
+            take += BarBudget.slots_take(k)
+        if rare:
+            slots[v] = RARE_SLOTS
+            continue
+        assert need in (take, take + 1)                               # a step needs its own take at most, or one slot for a note start
+        if take + (need - take) * NEED_ONE_MORE >= RARE_SLOTS or take >= NEED_ONE_MORE:
+            raise ValueError(f'sub-word id {v} with pieces {seq} takes {take} slots: a `slots` entry holds 15 bits of them')
+        slots[v] = take | (NEED_ONE_MORE if need > take else 0)
+    if len(names) > MAX_CLASSES:
+        raise NotImplementedError(f'{len(names)} token classes ({C0} of the base grammar and {len(names) - C0} distinct functions of '
+                                  f'multi-token ids on its states): a grammar has at most {MAX_CLASSES}')
+    allow = base.allow.astype(np.int64)
+    nxt = np.tile(np.arange(S, dtype=np.int64)[:, None], (1, len(names)))
+    nxt[:, :C0] = base.next
+    for fn, c in funcs.items():
+        for s, n in enumerate(fn):
+            if n >= 0:
+                allow[s] |= 1 << c
+                nxt[s, c] = n
+    g = TokenGrammar(cls, allow, nxt, base.start, base.accepting, names, base.state_names)
+    if bud is not None:
+        BarBudget(g, slots, bars, bud.opens, bud.need_free, bud.need_full)
+    if cnt is not None:
+        BarCount(g, cnt.count, cnt.end)
+    return g

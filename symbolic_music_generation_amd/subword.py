@@ -138,8 +138,19 @@ class PairMergeTokenizer(MusicTokenizer):
         return ret
 
     def grammar(self, bar_budget: bool = False):
-        raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders (a pitch with its '
-                                  'duration, a whole tuplet), so the music grammar over token classes does not apply')
+        """`MusicTokenizer.grammar` over this tokenizer's ids (grammar.subword_grammar): the music grammar, with bar_budget its
+        duration budget, and the bar count of `generate(n_bars=)`, all defined on the decoded stream -- a row of ids is allowed iff
+        the base tokens it stands for are.  It carries no melody guide, and the key and register rules stay refused: a token with
+        several pitches needs a pitch-class set and a range per token, which their one-byte tables do not hold.
+        The grammar is composed from the merged tokens, so a tokenizer without any (an untrained one: `added_tok2id` is empty) keeps
+        the refusal it always gave; its ids are the base vocabulary's, and `MusicTokenizer.grammar` is the grammar over those."""
+        if not self.added_tok2id:
+            raise NotImplementedError(f'{type(self).__name__} without merged tokens: sub-word tokens merge base tokens across class '
+                                      'borders (a pitch with its duration, a whole tuplet), and the grammar over sub-word ids is '
+                                      'composed from the trained ones; this tokenizer has none -- train it, or take '
+                                      'MusicTokenizer.grammar() over the base vocabulary')
+        from .grammar import music_grammar, subword_grammar
+        return subword_grammar(music_grammar(self.vocab, bar_budget), self.id2base_ids())
 
     def key_rule(self):
         raise NotImplementedError(f'{type(self).__name__}: a sub-word token may hold several pitches, so the key rule over single '
@@ -332,8 +343,12 @@ class WordPieceMusicTokenizer(MusicTokenizer):
         return ret
 
     def grammar(self, bar_budget: bool = False):
-        raise NotImplementedError(f'{type(self).__name__}: sub-word tokens merge base tokens across class borders (a pitch with its '
-                                  'duration, a whole tuplet), so the music grammar over token classes does not apply')
+        """`MusicTokenizer.grammar` over this tokenizer's ids (grammar.subword_grammar): the music grammar, with bar_budget its
+        duration budget, and the bar count of `generate(n_bars=)`, all defined on the decoded stream -- a row of ids is allowed iff
+        the base tokens it stands for are.  It carries no melody guide, and the key and register rules stay refused: a token with
+        several pitches needs a pitch-class set and a range per token, which their one-byte tables do not hold."""
+        from .grammar import music_grammar, subword_grammar
+        return subword_grammar(music_grammar(self.vocab, bar_budget), self.id2base_ids())
 
     def key_rule(self):
         raise NotImplementedError(f'{type(self).__name__}: a sub-word token may hold several pitches, so the key rule over single '
