@@ -416,6 +416,16 @@ int mxl_relattn_decode_split(const void* qkv, const void* kcache, const void* vc
 int mxl_relattn_decode_split_live(const void* qkv, const void* kcache, const void* vcache, const float* bd, const float* r_w_bias,
                                   void* out, const int* t_dev, int B, int H, int dh, int M, float scale, int pieces, float* ws,
                                   int* arrived, const int* unfinished, void* stream);
+/* mxl_relattn_decode_split_live over indexed rings (mxl_beam_owner_follow): the K row and the V row of a written slot s of row b are
+ * read from the ring of row (b / nb) * nb + owner[b][s]; owner (B, M) uint8, its row staged into shared memory at kernel entry.
+ * Never-written slots take the positional term alone, with no K / V read and no owner read.  Same arithmetic in the same order as
+ * mxl_relattn_decode / _split / _split_live: the output equals theirs bit for bit on rings gathered by the table, and on the same
+ * rings under the identity table.  An owner byte >= nb reads the item's last row.  pieces 1..8 with ws / arrived for pieces > 1
+ * (pieces = 1: both may be NULL), unfinished (B,) int32 or NULL.  owner non-null and 16-byte aligned, 1 <= nb <= 16, B % nb == 0,
+ * B <= 65535, M % 16 == 0, M * 5 + 1024 bytes of shared memory <= 64 KiB; else MXL_EINVAL.  dh 16 / 32 / 64, else MXL_EUNSUPPORTED. */
+int mxl_relattn_decode_owned(const void* qkv, const void* kcache, const void* vcache, const void* owner, int nb, const float* bd,
+                             const float* r_w_bias, void* out, const int* t_dev, int B, int H, int dh, int M, float scale,
+                             int pieces, float* ws, int* arrived, const int* unfinished, void* stream);
 /* FP8 K/V rings (opt-in).  A ring (B, H, M, dh) of bf16 is held as kc8 (B, H, M, dh) uint8 of OCP e4m3fn bytes and ke (B, H, M)
  * int8 exponents, one per slot and head (vc8 / ve alike); the stored value is fp8 * 2^e.  For a row x of dh elements with
  * amax = max|x| = m 2^k, m in [0.5, 1): e = k - 9 if m <= 0.875, else k - 8 (the smallest e with amax 2^-e <= 448), clamped to
@@ -749,6 +759,18 @@ int mxl_beam_sample_step(const float* drawn, int ldl, float* beam_scores, void* 
  * 16-byte aligned, nb <= 16, Bs and n_bufs <= 65535; else MXL_EINVAL. */
 int mxl_beam_reorder(void* buf, const void* table, int n_bufs, int Bs, int nb, long long row_bytes, const int* beam_idx,
                      const int* moved, void* stream);
+/* Indexed rings: the alternative to mxl_beam_reorder over the K/V rings.  A ring slot written for position p never changes, so a
+ * beam may point at the slot in its ancestor's ring instead of owning a copy.  owner: (Bs * nb, M) uint8 on the device;
+ * owner[r][s] = j, 0 <= j < nb, says that slot s of row r's history is held in the ring of row (r / nb) * nb + j; the identity
+ * owner[r][:] = r % nb after the prompt pass.  Launched where mxl_beam_reorder is, after the select and before mxl_decode_advance:
+ *   follow  an item with moved[b] != 0: owner[j][:] <- owner_old[beam_idx[j] - row0][:] for its nb rows, in place (a thread owns 16
+ *           slots, reads the sources of the rows that change into registers, then writes them; an index outside the item counts as j)
+ *   mark    every item, moved or not, dead and done rows too: owner[j][(*t_dev + 1) % M] = j -- the slot the coming forward pass
+ *           writes into row j's own ring.  On a wrap every row overwrites the slot in the same step and the position it held is
+ *           outside every window, so no other fix-up is needed.
+ * owner, beam_idx, moved, t_dev non-null, owner 16-byte aligned, 1 <= nb <= 16, M % 16 == 0, 1 <= Bs <= 65535; else MXL_EINVAL. */
+int mxl_beam_owner_follow(void* owner, int Bs, int nb, int M, const int* beam_idx, const int* moved, const int* t_dev,
+                          void* stream);
 /* Contrastive search (the reference's 'contrastive' strategy, musicnlp/trainer/eval.py:296-302, over the mems patch of
  * musicnlp/models/transformer_xl.py:229-234; HF 4.25.1 GenerationMixin.contrastive_search with `_ranking_fast`):
  *   score[b*K + k] = (1 - alpha) * probs[b*K + k] - alpha * max_{s < S} cos(hid[b*K + k], ctx[b][s]);  sel[b] = argmax_k score

@@ -26,6 +26,16 @@ mxl_beam_sample_step, mxl_beam_reorder, advance, model in one captured graph per
 rings).  The two draw from different random streams, so their ids differ; with an eos that never fires both emit NEW tokens per prompt.
 
     SAMPLE=1 python3 scripts/perf_beam.py
+
+RINGS=indexed measures the device path against itself: beam_rings='copied' (mxl_beam_reorder moves whole ring rows) against
+beam_rings='indexed' (the rings stay, mxl_beam_owner_follow keeps the owner table and mxl_relattn_decode_owned reads through it),
+alternated in one process, RUNS timed calls each after a warm-up call each, ids compared.  Also reports the mean share of decoder
+rows with src != j per step, counted in one eager 'copied' call: the copy's cost depends on it, and a randomly initialised model (the
+weights here: seed 77) may move few beams.  TP sets the prompt length: TP=2048 is the full-ring point, t >= M throughout, where the
+copy is largest.
+
+    RINGS=indexed python3 scripts/perf_beam.py
+    RINGS=indexed TP=2048 python3 scripts/perf_beam.py
 """
 import os
 import statistics
@@ -37,12 +47,13 @@ from symbolic_music_generation_amd import ops
 from symbolic_music_generation_amd.transformer_xl import MyTransfoXLConfig, MyTransfoXLLMHeadModel
 
 dev = torch.device('cuda:0')
-V, M, B, Tp, NB = 1190, 2048, 8, 256, 4
+V, M, B, Tp, NB = 1190, 2048, 8, int(os.environ.get('TP', 256)), 4
 NEW, RUNS = int(os.environ.get('NEW', 256)), int(os.environ.get('RUNS', 5))
 GROUPS, DIVERSITY = int(os.environ.get('GROUPS', 1)), float(os.environ.get('DIVERSITY', 1.5))
 SAMPLE = os.environ.get('SAMPLE') == '1'
+RINGS = os.environ.get('RINGS') == 'indexed'
 L = Tp + NEW
-cfg = MyTransfoXLConfig('base', max_length=2048, vocab_size=V, mem_len=M, cutoffs=[])
+cfg = MyTransfoXLConfig('base', max_length=max(2048, L), vocab_size=V, mem_len=M, cutoffs=[])
 model = MyTransfoXLLMHeadModel(cfg, device=dev, seed=77).eval()
 ids = torch.randint(4, V, (B, Tp), generator=torch.Generator().manual_seed(77)).to(dev)
 kw = dict(input_ids=ids, max_length=L, num_beams=NB, early_stopping=True, eos_token_id=V + 1, pad_token_id=0)
@@ -90,6 +101,42 @@ with torch.no_grad():
             clear = d[0] > h[-1]
             print(f'device / host = {statistics.median(d) / statistics.median(h):.3f}x; the slowest device run is '
                   f'{"above" if clear else "NOT above"} the fastest host run ({d[0]:.1f} vs {h[-1]:.1f} tok/s)')
+        sys.exit(0)
+    if RINGS:
+        from symbolic_music_generation_amd.generate import XLDecoder
+        # the share of rows that move: one eager 'copied' call, beam_idx != the row itself summed on the device after every select
+        real_select, seen = XLDecoder.beam_select, {}
+
+        def counting_select(dec):
+            r = real_select(dec)
+            rows = torch.arange(dec.B, device=dec.beam.beam_idx.device, dtype=torch.int32)
+            seen['rows'] = seen.get('rows', 0) + (dec.beam.beam_idx != rows).sum()
+            seen['items'] = seen.get('items', 0) + (dec.beam.moved != 0).sum()
+            seen['steps'] = seen.get('steps', 0) + 1
+            return r
+        XLDecoder.beam_select = counting_select
+        run(False, beam_rings='copied', use_graph=False)
+        XLDecoder.beam_select = real_select
+        share, items = float(seen['rows']) / (seen['steps'] * B * NB), float(seen['items']) / (seen['steps'] * B)
+        (_, a), (_, b) = run(False, beam_rings='copied'), run(False, beam_rings='indexed')      # warm-up; they return the same ids
+        same = torch.equal(a, b)
+        times = {'copied': [], 'indexed': []}
+        for _ in range(RUNS):
+            for mode in times:
+                times[mode].append(run(False, beam_rings=mode)[0])
+        what = 'beam search' if GROUPS == 1 else f'group beam search ({GROUPS} groups, diversity_penalty {DIVERSITY})'
+        print(f'{what} on the device, C5 decode shape: {B} prompts x {Tp}, num_beams {NB} ({B * NB} rows), {NEW} new tokens, eos never '
+              f'fires, weights: random initialisation (seed 77); indexed ids == copied ids: {same}')
+        print(f'rows with src != j: {100 * share:.1f} % per step on average, items that moved: {100 * items:.1f} % ({seen["steps"]} selects); '
+              f'slots written at the first step {min(Tp, M)} of {M}, at the last {min(L - 1, M)}')
+        tps = {m: sorted(B * NEW / t for t in ts) for m, ts in times.items()}
+        for m in times:
+            print(f'{m:7s}: {statistics.median(tps[m]):9.1f} tok/s median of {RUNS} (min {tps[m][0]:.1f}, max {tps[m][-1]:.1f}); '
+                  f'{statistics.median(times[m]):.3f} s per call')
+        clear = tps['indexed'][0] > tps['copied'][-1]
+        print(f'indexed / copied = {statistics.median(tps["indexed"]) / statistics.median(tps["copied"]):.3f}x; the slowest indexed run is '
+              f'{"above" if clear else "NOT above"} the fastest copied run ({tps["indexed"][0]:.1f} vs {tps["copied"][-1]:.1f} tok/s): the '
+              f'gap {"exceeds" if clear else "does not exceed"} the run-to-run spread')
         sys.exit(0)
     # library launches per step: one short eager call of either path, the prompt pass's share taken off with a second, shorter one
     ops.check = counting_check

@@ -24,6 +24,8 @@
 //            the mask launch keeps finding a valid state, and the ring attention skips it.  The rows of a done item are cleared too.
 // Beam-sample (mxl_beam_sample_step) is a third entry of the same kernel: over the `drawn` matrix of beam_sample.hip, with a
 // candidate's score its entry itself; select, walk, copy, reorder and dead rows are the ones above.
+// The rings follow either whole (beam_reorder_kernel) or not at all: beam_owner_follow_kernel keeps a table of which row of its item
+// holds each slot of a row's history, and the attention reads through it (decode_owned.hip).
 #include "common.h"
 #include "beam_key.h"
 #include "musicxl_internal.h"
@@ -230,6 +232,42 @@ __global__ __launch_bounds__(BEAM_T) void beam_reorder_kernel(char* buf, char* c
         if (src[j] != j) *reinterpret_cast<u32x4*>(base + (long long)(row0 + j) * row_bytes) = v[j];
 }
 
+// Indexed rings (mxl_beam_owner_follow): the rings stay where they are and the (rows, M) owner table follows the beams in their
+// place.  owner[r][s] = j: slot s of row r's history is held in the ring of row (r / nb) * nb + j.  grid (column blocks, items); a
+// thread owns 16 slots of its item, one 16-byte column: when the item moved it reads the source rows of the rows that change into
+// registers, then writes them, as beam_reorder_kernel does.  Then -- moved or not, dead and done rows too -- the thread that owns slot
+// (t + 1) mod M gives it to each row itself: the coming forward pass writes that slot into every row's own ring, so whatever owner a
+// row inherited for it (a stale one from before the wrap included) is no longer true.
+__global__ __launch_bounds__(BEAM_T) void beam_owner_follow_kernel(unsigned char* owner, int nb, int M, const int* beam_idx,
+                                                                   const int* moved, const int* t_dev) {
+    const int b = blockIdx.y, row0 = b * nb;
+    const int c = blockIdx.x * BEAM_T + threadIdx.x;
+    if (c >= (M >> 4)) return;
+    unsigned char* base = owner + (size_t)row0 * M + c * 16;
+    if (moved[b] != 0) {
+        int src[BEAM_MAX];
+#pragma unroll
+        for (int j = 0; j < BEAM_MAX; j++) {
+            src[j] = j;
+            if (j < nb) {
+                const int s = beam_idx[row0 + j] - row0;
+                if (s >= 0 && s < nb) src[j] = s;
+            }
+        }
+        u32x4 v[BEAM_MAX];
+#pragma unroll
+        for (int j = 0; j < BEAM_MAX; j++)
+            if (src[j] != j) v[j] = *reinterpret_cast<const u32x4*>(base + (size_t)src[j] * M);
+#pragma unroll
+        for (int j = 0; j < BEAM_MAX; j++)
+            if (src[j] != j) *reinterpret_cast<u32x4*>(base + (size_t)j * M) = v[j];
+    }
+    int slot = (*t_dev + 1) % M;
+    if (slot < 0) slot += M;
+    if ((slot >> 4) == c)
+        for (int j = 0; j < nb; j++) base[(size_t)j * M + (slot & 15)] = (unsigned char)j;
+}
+
 }  // namespace
 
 // the argument checks all entries share, and the launch; nb, ng and pen are in the entry's own domain by now
@@ -292,6 +330,17 @@ extern "C" int mxl_beam_reorder(void* buf, const void* table, int n_bufs, int Bs
     MXL_CHECK_ARG(blocks < (1LL << 31));
     hipLaunchKernelGGL(beam_reorder_kernel, dim3((unsigned)blocks, Bs, n_bufs), dim3(BEAM_T), 0, (hipStream_t)stream, (char*)buf,
                        (char* const*)table, row_bytes, nb, beam_idx, moved);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
+}
+
+extern "C" int mxl_beam_owner_follow(void* owner, int Bs, int nb, int M, const int* beam_idx, const int* moved, const int* t_dev,
+                                     void* stream) {
+    MXL_CHECK_ARG(owner && beam_idx && moved && t_dev && ((uintptr_t)owner % 16) == 0);
+    MXL_CHECK_ARG(Bs > 0 && Bs <= 65535 && nb >= 1 && nb <= BEAM_MAX && M > 0 && (M % 16) == 0);
+    const int blocks = ((M >> 4) + BEAM_T - 1) / BEAM_T;
+    hipLaunchKernelGGL(beam_owner_follow_kernel, dim3(blocks, Bs), dim3(BEAM_T), 0, (hipStream_t)stream, (unsigned char*)owner, nb, M,
+                       beam_idx, moved, t_dev);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }

@@ -1088,6 +1088,29 @@ def resolve_kv_dtype(kv_cache_dtype: Optional[str]) -> Optional[str]:
     return KV_DTYPES[kv_cache_dtype]
 
 
+BEAM_RINGS = ('copied', 'indexed')
+
+
+def resolve_beam_rings(beam_rings: Optional[str], applies: bool) -> str:
+    """how the K/V rings of a device beam search follow their beams: 'copied' (mxl_beam_reorder moves whole ring rows; None means
+    this) or 'indexed' (the rings stay and an owner table follows, mxl_beam_owner_follow / mxl_relattn_decode_owned).  A call that
+    names none takes MXL_BEAM_RINGS (an A/B knob: unset, nothing changes).  applies: the call is a beam, group-beam or beam-sample
+    search with its scorer on the device over bf16 rings of a mem_len that is a multiple of 16.  An explicit 'indexed' anywhere else is a ValueError, the environment's
+    is ignored there; any other string is a ValueError."""
+    explicit = beam_rings is not None
+    mode = beam_rings if explicit else (os.environ.get('MXL_BEAM_RINGS') or 'copied')
+    if mode not in BEAM_RINGS:
+        raise ValueError(f"beam_rings={mode!r}: expected None, 'copied' or 'indexed'")
+    if mode == 'indexed' and not applies:
+        if explicit:
+            raise ValueError("beam_rings='indexed' serves beam, group-beam and beam-sample search with the scorer on the device over "
+                             'bf16 rings: not greedy decoding, sampling or contrastive search, not the host scorers (MXL_BEAM_HOST=1, '
+                             "more than 16 beams, beam-sample without device_scorer=True), not kv_cache_dtype='fp8', not a mem_len "
+                             'that is no multiple of 16')
+        mode = 'copied'
+    return mode
+
+
 class XLDecoder(RuledGenerate):
     def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77, kv_dtype: Optional[str] = None):
         self.eng = engine
@@ -1143,6 +1166,10 @@ class XLDecoder(RuledGenerate):
         self.trace = None
         self.steps_run = 0                              # decode steps issued by the last generate() (early exit: fewer)
         self.beam = None                                # BeamStore of a beam search on the device (beam_begin)
+        # how the rings follow the beams of that search, fixed per beam_begin: 'copied' (mxl_beam_reorder) or 'indexed' -- the rings
+        # stay and `owner` (B, M) uint8 says which row of its item holds each slot of a row's history (mxl_beam_owner_follow)
+        self.beam_rings = 'copied'
+        self.owner = None
         self.drawn = None                               # (B, V) f32: the drawn candidates of a beam-sample step (beam_begin, sample)
         self.cs = None                                  # ContrastiveStore of a contrastive search on the device (contrastive_begin)
         # the rules of the current generation (eos, grammar, bar budget, bar count) and their per-row words, which the sampler
@@ -1180,6 +1207,7 @@ class XLDecoder(RuledGenerate):
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
         self._tables()
+        self.beam_rings = 'copied'                          # every row reads its own ring until a beam_begin says otherwise
         for k in self.kc + self.vc + self.ke + self.ve:     # (fp8: zero bytes with e = 0 are the zero memories)
             k.zero_()
         self.ids.zero_()
@@ -1255,6 +1283,8 @@ class XLDecoder(RuledGenerate):
         B, d, H, dh, M, Fi, L = self.B, c.d_model, c.n_head, c.d_head, c.mem_len, c.d_inner, c.n_layer
         E = e.w16('transformer.word_emb.emb_layers.0.weight')
         G = ops.gemm_skinny if B <= 64 else ops.gemm     # weight-streaming form for decode batches
+        # indexed rings: the attention of every layer reads a slot from the row the one table names (the append stays each row's own)
+        owned = dict(owner=self.owner, nb=self._beam_args[0]) if self.beam_rings == 'indexed' else {}
         if embed:
             ops.decode_embed(self.ids, self.t_dev, E, self.h[0], math.sqrt(d))
         for l in range(L):
@@ -1277,7 +1307,7 @@ class XLDecoder(RuledGenerate):
             if self.kv_dtype != 'fp8':
                 ops.relattn_decode(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P),
                                    rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces,
-                                   unfinished=live)
+                                   unfinished=live, **owned)
             G(self.av, e._lw(l, 'dec_attn.o_net.weight'), self.tmp, B, d, d)
             ops.ln_residual_fwd(self.tmp, h_in, e._lw(l, 'dec_attn.layer_norm.weight', e.P),
                                 e._lw(l, 'dec_attn.layer_norm.bias', e.P), self.h1, eps=c.layer_norm_epsilon)
@@ -1339,7 +1369,7 @@ class XLDecoder(RuledGenerate):
     def beam_begin(self, prompt: torch.Tensor, max_length: int, nb: int, eos: int, pad: int, length_penalty: float,
                    early_stopping: bool, use_graph: bool = True, rules: RulePlan = NO_RULES, ng: int = 1,
                    diversity_penalty: float = 0.0, sample: bool = False, top_k: Optional[int] = None, top_p: Optional[float] = None,
-                   temperature: float = 1.0, typical_p: Optional[float] = None) -> int:
+                   temperature: float = 1.0, typical_p: Optional[float] = None, beam_rings: str = 'copied') -> int:
         """prompt pass (one row per beam, `rules` started as `prefill` starts them, with the stop group (eos, pad, 0) always on:
         its `unfinished` word is how mxl_beam_step retires dead rows and done items) + the scorer's state + (use_graph) capture of
         one beam step (`_capture`; the hypothesis store, the running scores and the log-probabilities are this step's own state);
@@ -1348,8 +1378,16 @@ class XLDecoder(RuledGenerate):
         in place of mxl_beam_step); both are part of the graph key.
         sample: beam-sample, ng = 1 -- the step draws its candidates (mxl_beam_sample_draw under the warpers top_k / top_p / temperature
         / typical_p with the decoder's seed, into the decoder's `drawn` buffer) and walks them with mxl_beam_sample_step; the draw
-        counter starts at 0, so a seed gives one result.  The flag and the warpers are part of the graph key, `drawn` is step state."""
+        counter starts at 0, so a seed gives one result.  The flag and the warpers are part of the graph key, `drawn` is step state.
+        beam_rings: 'copied' -- the step moves whole ring rows with mxl_beam_reorder -- or 'indexed': the rings stay where the forward
+        pass wrote them, the `owner` table (identity after the prompt pass: every row holds its own prompt) follows the beams with
+        mxl_beam_owner_follow and the attention reads through it (mxl_relattn_decode_owned); M % 16 == 0.  The mode is part of the
+        graph key, the table is step state."""
         self._bf16_rings_only('beam search on the device')
+        if beam_rings not in BEAM_RINGS:
+            raise ValueError(f"beam_rings={beam_rings!r}: expected 'copied' or 'indexed'")
+        if beam_rings == 'indexed' and self.eng.cfg.mem_len % 16:
+            raise MusicXLError(f"beam_rings='indexed' takes a mem_len that is a multiple of 16, not {self.eng.cfg.mem_len}")
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
         if nb < 2 or nb > BEAM_MAX or self.B % nb:
@@ -1368,15 +1406,22 @@ class XLDecoder(RuledGenerate):
                            bool(sample), int(top_k or 0), float(1.0 if top_p is None else top_p),
                            float(1.0 if temperature is None else temperature), float(1.0 if typical_p is None else typical_p))
         extra = ()
+        self.beam_rings = beam_rings
+        if beam_rings == 'indexed':
+            if self.owner is None:
+                self.owner = torch.empty(self.B, self.eng.cfg.mem_len, device=self.eng.dev, dtype=torch.uint8)
+            self.owner.copy_((torch.arange(self.B, device=self.eng.dev) % nb).to(torch.uint8)[:, None].expand_as(self.owner))
+            extra = (self.owner,)
         if sample:
             self.rng.zero_()
             if self.drawn is None:
                 self.drawn = torch.empty_like(self.logp)
-            extra = (self.drawn,)
+            extra += (self.drawn,)
         self._use_graph, self._step, self.finished_by = use_graph, ('beam_step',), (self.beam.n_done, self.beam.Bs)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
-            key = ('beam',) + self._beam_args + (None if self.trace is None else self.trace.data_ptr(),) + self.rules.graph_key(self.eng.dev)
+            key = (('beam', beam_rings) + self._beam_args + (None if self.trace is None else self.trace.data_ptr(),)
+                   + self.rules.graph_key(self.eng.dev))
             st = self.beam               # (logp: the step starts from the log-probabilities the last one left)
             self._capture(key, (st.scores, st.hyp_ids, st.hyp_score, st.ints, self.logp) + extra)
         return max(steps, 0)
@@ -1400,10 +1445,14 @@ class XLDecoder(RuledGenerate):
 
     def beam_step(self):
         """one whole beam step, no host read: beam_select, the K/V rings of every layer follow their beams (one launch over a
-        table of the rings), the position moves on, the rule words move along the chosen tokens (rows that mxl_beam_step retired
-        keep theirs), and the chosen tokens go through the model"""
+        table of the rings; under beam_rings='indexed' the owner table follows in their place, M bytes per row), the position moves
+        on, the rule words move along the chosen tokens (rows that mxl_beam_step retired keep theirs), and the chosen tokens go
+        through the model"""
         rules = self.beam_select()
-        ops.beam_reorder(self.kc + self.vc, self._beam_args[0], self.beam.beam_idx, self.beam.moved, table=self.ring_table)
+        if self.beam_rings == 'indexed':
+            ops.beam_owner_follow(self.owner, self._beam_args[0], self.beam.beam_idx, self.beam.moved, self.t_dev)
+        else:
+            ops.beam_reorder(self.kc + self.vc, self._beam_args[0], self.beam.beam_idx, self.beam.moved, table=self.ring_table)
         ops.decode_advance(self.t_dev, self.rng)
         if rules['grammar'] is not None or rules['in_key'] is not None or rules.get('register') is not None:
             ops.rules_advance(self.ids, self.t_dev, **rules)
@@ -1730,7 +1779,8 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
                        length_penalty: float = 1.0, num_return_sequences: int = 1, eos_token_id: int = 0,
                        pad_token_id: Optional[int] = None, use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None,
                        n_bars=None, in_key=None, key=None, return_scores: bool = False, num_beam_groups: int = 1,
-                       diversity_penalty: float = 0.0, register=None, melody_range=None, bass_range=None, bass_below=None):
+                       diversity_penalty: float = 0.0, register=None, melody_range=None, bass_range=None, bass_below=None,
+                       beam_rings: str = 'copied'):
     """`beam_search` (do_sample=False) with the scorer on the device: per step the rules mask, mxl_beam_step (select, walk, store,
     reorder ids and the rule words), mxl_beam_reorder over the K/V rings, the position advance, the rules advance and the model --
     no host read, captured once under use_graph (XLDecoder.beam_begin / beam_step).  The steps are replayed in chunks of
@@ -1741,7 +1791,8 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     value per prompt where they are per row (each prompt's is shared by its beams); a barred token is -inf before the running scores
     are added, the rules' words follow the beams, and a row that can only continue from a barred token is dead: it emits pad at score
     -inf and never returns.  An item that ends with fewer than num_return_sequences hypotheses of finite score raises MusicXLError.
-    num_beam_groups > 1 with diversity_penalty: the same loop over mxl_group_beam_step (group_beam_search_device)."""
+    num_beam_groups > 1 with diversity_penalty: the same loop over mxl_group_beam_step (group_beam_search_device).
+    beam_rings: 'copied' or 'indexed', how the rings follow the beams (XLDecoder.beam_begin); the output is the same."""
     V = dec.eng.cfg.vocab_size
     nb = int(num_beams)
     pad = eos_token_id if pad_token_id is None else pad_token_id
@@ -1757,13 +1808,14 @@ def beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
     rules = rules_config(batch=B0, vocab_size=V, stop=(int(eos_token_id), int(pad), 0), grammar=grammar, n_bars=n_bars, in_key=in_key,
                          key=key, register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below, repeat=nb)
     return _beam_device(dec, prompt, max_length, nb, keep, early_stopping, length_penalty, eos_token_id, pad, use_graph, stop_chunk,
-                        rules, return_scores, 'beam search', ng=int(num_beam_groups), diversity_penalty=float(diversity_penalty))
+                        rules, return_scores, 'beam search', ng=int(num_beam_groups), diversity_penalty=float(diversity_penalty),
+                        beam_rings=beam_rings)
 
 
 def _beam_device(dec, items: torch.Tensor, max_length: int, nb: int, keep: int, early_stopping: bool, length_penalty: float, eos: int,
                  pad: int, use_graph: bool, stop_chunk: int, rules: RulePlan, return_scores: bool, what: str, **arm):
     """The loop of the device beam searches over `items` (Bs, Tp), one prompt per item, nb decoder rows each: `beam_begin` (with
-    `rules`, built for the Bs * nb rows, and `arm`: the groups and their penalty, or the sample flag and its warpers), the chunked
+    `rules`, built for the Bs * nb rows, and `arm`: the groups and their penalty, or the sample flag and its warpers, and beam_rings), the chunked
     replay, the last selection, one read of the store and `_beam_finalize` keeping `keep` hypotheses per item."""
     B0, Tp = items.shape
     n = dec.beam_begin(items.repeat_interleave(nb, 0).to(dec.eng.dev), max_length, nb, eos, pad, length_penalty, early_stopping,
@@ -1795,7 +1847,7 @@ def beam_sample_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
                        early_stopping: bool = True, length_penalty: float = 1.0, num_return_sequences: int = 1, eos_token_id: int = 0,
                        pad_token_id: Optional[int] = None, use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None,
                        in_key=None, key=None, return_scores: bool = False, register=None, melody_range=None, bass_range=None,
-                       bass_below=None):
+                       bass_below=None, beam_rings: str = 'copied'):
     """`beam_search(do_sample=True)` (HF 4.25.1 `beam_sample` with renormalize_logits) with the draw and the scorer on the device:
     `beam_search_device`'s loop -- chunked replay of one captured step, the number of done items read a chunk late, the last selection
     without a forward, `_beam_finalize` -- whose step is the rules mask, mxl_beam_sample_draw (the warpers with two tokens kept, the
@@ -1821,7 +1873,7 @@ def beam_sample_device(dec, prompt: torch.Tensor, max_length: int, num_beams: in
                          bass_range=bass_range, bass_below=bass_below, repeat=nrs * nb)
     return _beam_device(dec, prompt.repeat_interleave(nrs, 0), max_length, nb, 1, early_stopping, length_penalty, eos_token_id, pad,
                         use_graph, stop_chunk, rules, return_scores, 'beam-sample', sample=True, top_k=top_k, top_p=top_p,
-                        temperature=temperature, typical_p=typical_p)
+                        temperature=temperature, typical_p=typical_p, beam_rings=beam_rings)
 
 
 def group_beam_search(dec, prompt: torch.Tensor, max_length: int, num_beams: int = 4, num_beam_groups: int = 2,
@@ -1844,7 +1896,8 @@ def group_beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_bea
                              diversity_penalty: float = 0.0, early_stopping: bool = True, length_penalty: float = 1.0,
                              num_return_sequences: int = 1, eos_token_id: int = 0, pad_token_id: Optional[int] = None,
                              use_graph: bool = True, stop_chunk: int = STOP_CHUNK, grammar=None, in_key=None, key=None,
-                             return_scores: bool = False, register=None, melody_range=None, bass_range=None, bass_below=None):
+                             return_scores: bool = False, register=None, melody_range=None, bass_range=None, bass_below=None,
+                             beam_rings: str = 'copied'):
     """`group_beam_search` with the scorer on the device: `beam_search_device`'s loop -- chunked replay of one captured step, the
     number of done items read a chunk late, the last selection without a forward, `_beam_finalize` -- over mxl_group_beam_step, which
     walks the groups of every item in order inside one launch.  dec: an XLDecoder with prompt rows x num_beams rows, num_beams <= 16
@@ -1857,7 +1910,8 @@ def group_beam_search_device(dec, prompt: torch.Tensor, max_length: int, num_bea
                               num_return_sequences=num_return_sequences, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                               use_graph=use_graph, stop_chunk=stop_chunk, grammar=grammar, in_key=in_key, key=key,
                               return_scores=return_scores, num_beam_groups=ng, diversity_penalty=float(diversity_penalty or 0.0),
-                              register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below)
+                              register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below,
+                              beam_rings=beam_rings)
 
 
 def beam_generate(make_decoder, input_ids: torch.Tensor, max_length: int, *, num_beams: int, num_beam_groups: int, do_sample: bool,

@@ -539,6 +539,22 @@ def beam_reorder(bufs, nb, beam_idx, moved, table=None):
                                  row_bytes, _p(beam_idx), _p(moved), _stream()), 'mxl_beam_reorder')
 
 
+def beam_owner_follow(owner, nb, beam_idx, moved, t_dev):
+    """indexed rings in place of beam_reorder over the K/V rings (mxl_beam_owner_follow): owner (rows, M) uint8, owner[r, s] = j says
+    that slot s of row r is held in the ring of row (r // nb) * nb + j.  The rows of an item with moved[b] != 0 follow beam_idx in
+    place; then, in every item, each row takes slot (t + 1) % M for itself -- the slot the coming forward pass writes."""
+    _req(owner, torch.uint8, 'beam_owner_follow owner')
+    _req(beam_idx, torch.int32, 'beam_owner_follow beam_idx'); _req(moved, torch.int32, 'beam_owner_follow moved')
+    _req(t_dev, torch.int32, 'beam_owner_follow t_dev')
+    if owner.dim() != 2 or not owner.is_contiguous():
+        raise MusicXLError('beam_owner_follow: owner must be a contiguous (rows, M) uint8 table')
+    rows, M = owner.shape
+    if nb < 1 or rows % nb or beam_idx.numel() != rows or moved.numel() != rows // nb:
+        raise MusicXLError(f'beam_owner_follow: {rows} rows need nb rows per item, beam_idx ({rows},) and moved (rows / nb,)')
+    check(lib().mxl_beam_owner_follow(_p(owner), rows // nb, int(nb), M, _p(beam_idx), _p(moved), _p(t_dev), _stream()),
+          'mxl_beam_owner_follow')
+
+
 def beam_table(bufs) -> torch.Tensor:
     """the addresses of `bufs` as a device int64 tensor, the pointer table of beam_reorder"""
     return torch.tensor([t.data_ptr() for t in bufs], dtype=torch.int64, device=bufs[0].device)
@@ -1076,11 +1092,13 @@ def relattn_decode_split_scratch(B: int, H: int, dh: int, pieces: int, dev):
 
 
 def relattn_decode(qkv, kc, vc, rd, rwb, rrb, out, t_dev, H, dh, qr_buf, bd_buf, scale=None, qr_ready=False, split=None, pieces=1,
-                   unfinished=None):
+                   unfinished=None, owner=None, nb=1):
     """qr_buf (B, H*dh) bf16 and bd_buf (B, H, M) f32 are scratch: BD = (q + r_r_bias) . rd^T for the whole batch.
     qr_ready: qr_buf already holds q + r_r_bias (written by kv_append).  split = relattn_decode_split_scratch(...) with the same
     `pieces`: the ring of every (sequence, head) goes to that many workgroups.  unfinished: (B,) int32 device stop state of
-    generation -- finished rows (0) read no ring and get zeros in `out` (mxl_relattn_decode_split_live)."""
+    generation -- finished rows (0) read no ring and get zeros in `out` (mxl_relattn_decode_split_live).
+    owner: (B, M) uint8 with `nb` rows per item -- indexed rings: slot s of row b is read from the ring of row
+    (b // nb) * nb + owner[b, s] (mxl_relattn_decode_owned; the BD launch is the same)."""
     B, _, M, _ = kc.shape
     d = H * dh
     scale = scale if scale is not None else 1.0 / math.sqrt(dh)
@@ -1093,6 +1111,16 @@ def relattn_decode(qkv, kc, vc, rd, rwb, rrb, out, t_dev, H, dh, qr_buf, bd_buf,
                      sA=(dh, 0), sB=(dh, 0), sC=(M, 0))
     if unfinished is not None:
         _req(unfinished, torch.int32, 'relattn_decode unfinished')
+    if owner is not None:
+        _req(owner, torch.uint8, 'relattn_decode owner')
+        if tuple(owner.shape) != (B, M) or not owner.is_contiguous():
+            raise MusicXLError(f'relattn_decode: owner must be a contiguous ({B}, {M}) uint8 table')
+        n = pieces if (split is not None and pieces > 1) else 1
+        check(lib().mxl_relattn_decode_owned(_p(qkv), _p(kc), _p(vc), _p(owner), int(nb), _p(bd_buf), _p(rwb), _p(out), _p(t_dev), B, H,
+                                             dh, M, float(scale), n, _p(split[0]) if n > 1 else 0, _p(split[1]) if n > 1 else 0,
+                                             _p(unfinished), _stream()), 'mxl_relattn_decode_owned')
+        return
+    if unfinished is not None:
         n = pieces if (split is not None and pieces > 1) else 1
         check(lib().mxl_relattn_decode_split_live(_p(qkv), _p(kc), _p(vc), _p(bd_buf), _p(rwb), _p(out), _p(t_dev), B, H, dh, M,
                                                   float(scale), n, _p(split[0]) if n > 1 else 0, _p(split[1]) if n > 1 else 0,

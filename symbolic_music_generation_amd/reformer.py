@@ -197,8 +197,9 @@ class MyReformerModelWithLMHead(EngineModule):
                                resolve_max_length, rules_config, rules_refusal, sample_unfused, sampling_config, stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
-        if unsupported.get('kv_cache_dtype') is not None:      # (before any strategy is chosen: the searches here read no **unsupported)
-            raise NotImplementedError("generation options not covered: ['kv_cache_dtype']")
+        for opt in ('kv_cache_dtype', 'beam_rings'):           # (before any strategy is chosen: the searches here read no **unsupported)
+            if unsupported.get(opt) is not None:
+                raise NotImplementedError(f"generation options not covered: ['{opt}']")
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))
         check_grammar_args(grammar, self.config.vocab_size, stop)
         top_k = getattr(self.config, 'top_k', 50) if top_k is None else top_k        # HF fills it from the config: default 50

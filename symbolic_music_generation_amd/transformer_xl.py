@@ -200,7 +200,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
                  min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, melody=None,
                  device_scorer: bool = False, register=None, melody_range=None, bass_range=None, bass_below=None,
-                 kv_cache_dtype: Optional[str] = None, **unused) -> torch.Tensor:
+                 kv_cache_dtype: Optional[str] = None, beam_rings: Optional[str] = None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -324,10 +324,21 @@ class MyTransfoXLLMHeadModel(EngineModule):
         sampling take (rules, eos, padded prompts, `num_return_sequences`, the two-lane decoder, `use_graph`, the large-vocabulary
         sampler).  Beam, beam-sample, group-beam and contrastive search refuse 'fp8' (ValueError): they move rings with
         mxl_beam_reorder / mxl_ring_slot_broadcast, which know the bf16 layout alone.  Any other string is a ValueError.
-        `MXL_KV_DTYPE=fp8` sets the default of calls that do not pass the keyword (an A/B knob; unset, nothing changes)."""
+        `MXL_KV_DTYPE=fp8` sets the default of calls that do not pass the keyword (an A/B knob; unset, nothing changes).
+
+        `beam_rings` (plain beam, group beam and beam-sample with `device_scorer=True`, scorer on the device): how the K/V rings follow
+        the beams.  None or 'copied': every step copies whole ring rows (mxl_beam_reorder), as ever.  'indexed' (opt-in): the rings
+        stay where the forward pass wrote them; a ring slot written for a position never changes, so a beam points at the slot in
+        its ancestor's ring, an owner table of `mem_len` bytes per row follows the beams (mxl_beam_owner_follow) and the attention
+        reads through it (mxl_relattn_decode_owned; DESIGN.md, indexed rings).  The ids and scores are the ones 'copied' returns, with
+        every rule those paths take and with `use_graph` on and off; `mem_len` must be a multiple of 16.  An explicit 'indexed' is a
+        ValueError under greedy decoding, sampling and contrastive search, under the host scorers (`MXL_BEAM_HOST=1`, more than 16
+        beams, beam-sample without `device_scorer`) and with `kv_cache_dtype='fp8'`; any other string is a ValueError.
+        `MXL_BEAM_RINGS=indexed` sets the default of calls that do not pass the keyword and is ignored where 'indexed' does not apply."""
         from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, beam_generate, beam_sample_device,
                                beam_search_device, check_grammar_args, contrastive_search, contrastive_search_device,
-                               group_beam_search_device, left_pad_counts, plan_search, resolve_kv_dtype, resolve_max_length,
+                               group_beam_search_device, left_pad_counts, plan_search, resolve_beam_rings, resolve_kv_dtype,
+                               resolve_max_length,
                                rules_config, sampling_config, stop_config)
         kv_dtype = resolve_kv_dtype(kv_cache_dtype)
         n_pad = None
@@ -357,6 +368,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
             name = dict(beam='beam', beam_sample='beam-sample', group_beam='group-beam', contrastive='contrastive')[plan.strategy]
             raise ValueError(f"kv_cache_dtype='{kv_dtype}' is not supported under {name} search: it moves rings with "
                              'mxl_beam_reorder / mxl_ring_slot_broadcast, which take bf16 rings alone; greedy decoding and sampling do')
+        rings = resolve_beam_rings(beam_rings, plan.device and plan.strategy in ('beam', 'group_beam', 'beam_sample') and kv_dtype is None
+                                   and self.config.mem_len % 16 == 0)
         B0 = input_ids.shape[0]
         ranges = dict(register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below)
         rules = rules_config(batch=B0, vocab_size=self.config.vocab_size, stop=stop, grammar=grammar, n_bars=n_bars, in_key=in_key,
@@ -373,7 +386,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         if plan.device:                                     # (the device searches plan per-prompt values per beam themselves)
             beams = dict(num_beams=num_beams, early_stopping=bool(early_stopping), length_penalty=length_penalty,
                          num_return_sequences=num_return_sequences, use_graph=use_graph, grammar=grammar, in_key=in_key, key=key, **ranges,
-                         **ends)
+                         **ends, beam_rings=rings)
             if plan.strategy == 'beam_sample':
                 dec = XLDecoder(self.engine, B0 * num_return_sequences * num_beams, max_length, seed=seed)
                 return beam_sample_device(dec, input_ids, max_length, top_k=top_k, top_p=top_p, temperature=temperature,
