@@ -448,6 +448,17 @@ int mxl_kv_fill_fp8(const void* qkv, void* kc8, void* ke, void* vc8, void* ve, i
 int mxl_relattn_decode_fp8(const void* qkv, const void* kc8, const void* ke, const void* vc8, const void* ve, const float* bd,
                            const float* r_w_bias, void* out, const int* t_dev, int B, int H, int dh, int M, float scale, int pieces,
                            float* ws, int* arrived, const int* unfinished, void* stream);
+/* mxl_relattn_decode_fp8 over indexed rings (mxl_beam_owner_follow): the 16-byte K and V loads and the two exponents of a written slot
+ * s of row b are read from the rings of row (b / nb) * nb + owner[b][s]; owner (B, M) uint8, its row staged into shared memory
+ * before the first ring load.  Never-written slots take the positional term alone, with no ring byte and no owner byte read; a
+ * finished row reads neither and gets zeros.  Same arithmetic in the same order as mxl_relattn_decode_fp8: the output equals its
+ * output bit for bit on rings (bytes and exponents) gathered by the table, and on the same rings under the identity table.  An owner
+ * byte >= nb reads the item's last row.  pieces 1..8 with ws / arrived for pieces > 1 (pieces = 1: both may be NULL), unfinished
+ * (B,) int32 or NULL.  owner non-null and 16-byte aligned, 1 <= nb <= 16, B % nb == 0, B <= 65535, M % 16 == 0, M * 5 + 1024 bytes
+ * of shared memory <= 64 KiB; else MXL_EINVAL.  dh 16 / 32 / 64, else MXL_EUNSUPPORTED.  Nothing is launched on either. */
+int mxl_relattn_decode_fp8_owned(const void* qkv, const void* kc8, const void* ke, const void* vc8, const void* ve, const void* owner,
+                                 int nb, const float* bd, const float* r_w_bias, void* out, const int* t_dev, int B, int H, int dh,
+                                 int M, float scale, int pieces, float* ws, int* arrived, const int* unfinished, void* stream);
 /* next token from log-probs (B, ldl): repetition penalty over the ids already in the row (positions 0..*t_dev; HF's
  * RepetitionPenaltyLogitsProcessor, 1.0 = off), then greedy argmax (do_sample=0) or temperature -> top-k -> top-p ->
  * typical-p (HF's TypicalLogitsWarper, 1.0 = off) -> renormalise -> multinomial (do_sample=1), as HF's logits warpers with

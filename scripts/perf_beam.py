@@ -36,6 +36,13 @@ copy is largest.
 
     RINGS=indexed python3 scripts/perf_beam.py
     RINGS=indexed TP=2048 python3 scripts/perf_beam.py
+
+RINGS=indexed_fp8 measures beam_rings='indexed' (bf16 rings) against beam_rings='indexed_fp8' (FP8 rings, never moved either, read by
+mxl_relattn_decode_fp8_owned) by the same procedure.  K and V rounded to four significant bits give other scores, so the ids are not
+expected to be equal: the rows that differ are counted, not checked.  Also reports the ring bytes of either decoder.
+
+    RINGS=indexed_fp8 python3 scripts/perf_beam.py
+    RINGS=indexed_fp8 TP=2048 python3 scripts/perf_beam.py
 """
 import os
 import statistics
@@ -51,7 +58,9 @@ V, M, B, Tp, NB = 1190, 2048, 8, int(os.environ.get('TP', 256)), 4
 NEW, RUNS = int(os.environ.get('NEW', 256)), int(os.environ.get('RUNS', 5))
 GROUPS, DIVERSITY = int(os.environ.get('GROUPS', 1)), float(os.environ.get('DIVERSITY', 1.5))
 SAMPLE = os.environ.get('SAMPLE') == '1'
-RINGS = os.environ.get('RINGS') == 'indexed'
+RINGS = os.environ.get('RINGS')
+assert RINGS in (None, 'indexed', 'indexed_fp8'), RINGS
+PAIR = ('indexed', 'indexed_fp8') if RINGS == 'indexed_fp8' else ('copied', 'indexed')       # (the baseline, the mode measured)
 L = Tp + NEW
 cfg = MyTransfoXLConfig('base', max_length=max(2048, L), vocab_size=V, mem_len=M, cutoffs=[])
 model = MyTransfoXLLMHeadModel(cfg, device=dev, seed=77).eval()
@@ -118,24 +127,31 @@ with torch.no_grad():
         run(False, beam_rings='copied', use_graph=False)
         XLDecoder.beam_select = real_select
         share, items = float(seen['rows']) / (seen['steps'] * B * NB), float(seen['items']) / (seen['steps'] * B)
-        (_, a), (_, b) = run(False, beam_rings='copied'), run(False, beam_rings='indexed')      # warm-up; they return the same ids
+        base, new = PAIR
+        (_, a), (_, b) = run(False, beam_rings=base), run(False, beam_rings=new)   # warm-up; copied and indexed return the same ids
         same = torch.equal(a, b)
-        times = {'copied': [], 'indexed': []}
+        times = {base: [], new: []}
         for _ in range(RUNS):
             for mode in times:
                 times[mode].append(run(False, beam_rings=mode)[0])
         what = 'beam search' if GROUPS == 1 else f'group beam search ({GROUPS} groups, diversity_penalty {DIVERSITY})'
         print(f'{what} on the device, C5 decode shape: {B} prompts x {Tp}, num_beams {NB} ({B * NB} rows), {NEW} new tokens, eos never '
-              f'fires, weights: random initialisation (seed 77); indexed ids == copied ids: {same}')
+              f'fires, weights: random initialisation (seed 77); '
+              + (f'{new} ids == {base} ids: {same}' if RINGS == 'indexed' else
+                 f'{int((a != b).any(1).sum())} of {a.shape[0]} returned rows differ from the bf16 rings\' in an id (not expected equal)'))
+        if RINGS == 'indexed_fp8':
+            slots, dh = B * NB * cfg.n_layer * 2 * cfg.n_head * M, cfg.d_head
+            print(f'ring memory: bf16 {slots * dh * 2 / 1e9:.3f} GB, fp8 bytes and exponents {slots * (dh + 1) / 1e9:.3f} GB '
+                  f'({(dh + 1) / (2 * dh):.3f} of it)')
         print(f'rows with src != j: {100 * share:.1f} % per step on average, items that moved: {100 * items:.1f} % ({seen["steps"]} selects); '
               f'slots written at the first step {min(Tp, M)} of {M}, at the last {min(L - 1, M)}')
         tps = {m: sorted(B * NEW / t for t in ts) for m, ts in times.items()}
         for m in times:
-            print(f'{m:7s}: {statistics.median(tps[m]):9.1f} tok/s median of {RUNS} (min {tps[m][0]:.1f}, max {tps[m][-1]:.1f}); '
+            print(f'{m:11s}: {statistics.median(tps[m]):9.1f} tok/s median of {RUNS} (min {tps[m][0]:.1f}, max {tps[m][-1]:.1f}); '
                   f'{statistics.median(times[m]):.3f} s per call')
-        clear = tps['indexed'][0] > tps['copied'][-1]
-        print(f'indexed / copied = {statistics.median(tps["indexed"]) / statistics.median(tps["copied"]):.3f}x; the slowest indexed run is '
-              f'{"above" if clear else "NOT above"} the fastest copied run ({tps["indexed"][0]:.1f} vs {tps["copied"][-1]:.1f} tok/s): the '
+        clear = tps[new][0] > tps[base][-1]
+        print(f'{new} / {base} = {statistics.median(tps[new]) / statistics.median(tps[base]):.3f}x; the slowest {new} run is '
+              f'{"above" if clear else "NOT above"} the fastest {base} run ({tps[new][0]:.1f} vs {tps[base][-1]:.1f} tok/s): the '
               f'gap {"exceeds" if clear else "does not exceed"} the run-to-run spread')
         sys.exit(0)
     # library launches per step: one short eager call of either path, the prompt pass's share taken off with a second, shorter one

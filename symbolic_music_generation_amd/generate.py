@@ -1088,25 +1088,34 @@ def resolve_kv_dtype(kv_cache_dtype: Optional[str]) -> Optional[str]:
     return KV_DTYPES[kv_cache_dtype]
 
 
-BEAM_RINGS = ('copied', 'indexed')
+BEAM_RINGS = ('copied', 'indexed', 'indexed_fp8')         # what `generate(beam_rings=)` takes
+DECODER_BEAM_RINGS = BEAM_RINGS[:2]                        # what XLDecoder.beam_begin takes: 'indexed_fp8' is 'indexed' on an fp8 decoder
 
 
-def resolve_beam_rings(beam_rings: Optional[str], applies: bool) -> str:
+def resolve_beam_rings(beam_rings: Optional[str], applies: bool, d_head: int = 64) -> str:
     """how the K/V rings of a device beam search follow their beams: 'copied' (mxl_beam_reorder moves whole ring rows; None means
-    this) or 'indexed' (the rings stay and an owner table follows, mxl_beam_owner_follow / mxl_relattn_decode_owned).  A call that
-    names none takes MXL_BEAM_RINGS (an A/B knob: unset, nothing changes).  applies: the call is a beam, group-beam or beam-sample
-    search with its scorer on the device over bf16 rings of a mem_len that is a multiple of 16.  An explicit 'indexed' anywhere else is a ValueError, the environment's
-    is ignored there; any other string is a ValueError."""
+    this), 'indexed' (the rings stay and an owner table follows, mxl_beam_owner_follow / mxl_relattn_decode_owned) or 'indexed_fp8'
+    (the same over FP8 rings, mxl_relattn_decode_fp8_owned: the caller builds the search's decoder with kv_dtype='fp8' and runs its
+    'indexed' mode).  A call that names none takes MXL_BEAM_RINGS (an A/B knob: unset, nothing changes).  applies: the call is a
+    beam, group-beam or beam-sample search with its scorer on the device, without kv_cache_dtype, over a mem_len that is a multiple
+    of 16.  An explicit 'indexed' or 'indexed_fp8' anywhere else is a ValueError, the environment's is ignored there; any other
+    string is a ValueError.  d_head: FP8 rings take head widths 16, 32 and 64 -- an explicit 'indexed_fp8'
+    with another is a MusicXLError, the environment's is ignored."""
     explicit = beam_rings is not None
     mode = beam_rings if explicit else (os.environ.get('MXL_BEAM_RINGS') or 'copied')
     if mode not in BEAM_RINGS:
-        raise ValueError(f"beam_rings={mode!r}: expected None, 'copied' or 'indexed'")
-    if mode == 'indexed' and not applies:
+        raise ValueError(f"beam_rings={mode!r}: expected None, 'copied', 'indexed' or 'indexed_fp8'")
+    if mode != 'copied' and not applies:
         if explicit:
-            raise ValueError("beam_rings='indexed' serves beam, group-beam and beam-sample search with the scorer on the device over "
-                             'bf16 rings: not greedy decoding, sampling or contrastive search, not the host scorers (MXL_BEAM_HOST=1, '
+            raise ValueError(f"beam_rings='{mode}' serves beam, group-beam and beam-sample search with the scorer on the device"
+                             f"{' over bf16 rings' if mode == 'indexed' else ''}: "
+                             'not greedy decoding, sampling or contrastive search, not the host scorers (MXL_BEAM_HOST=1, '
                              "more than 16 beams, beam-sample without device_scorer=True), not kv_cache_dtype='fp8', not a mem_len "
                              'that is no multiple of 16')
+        mode = 'copied'
+    if mode == 'indexed_fp8' and d_head not in (16, 32, 64):
+        if explicit:
+            raise MusicXLError(f"beam_rings='indexed_fp8': fp8 K/V rings need a head width of 16, 32 or 64, not {d_head}")
         mode = 'copied'
     return mode
 
@@ -1297,7 +1306,7 @@ class XLDecoder(RuledGenerate):
                 ops.kv_append_fp8(self.qkv, self.kc[l], self.ke[l], self.vc[l], self.ve[l], self.t_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
                 ops.relattn_decode_fp8(self.qkv, self.kc[l], self.ke[l], self.vc[l], self.ve[l], self.rd[l],
                                        e._lw(l, 'dec_attn.r_w_bias', e.P), rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True,
-                                       split=self.split, pieces=self.pieces, unfinished=live)
+                                       split=self.split, pieces=self.pieces, unfinished=live, **owned)
             elif B <= 64:      # projection, ring append and q + r_r_bias in one launch
                 ops.decode_qkv(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, self.kc[l], self.vc[l], self.t_dev,
                                rrb.reshape(-1), self.qr, dh)
@@ -1382,10 +1391,17 @@ class XLDecoder(RuledGenerate):
         beam_rings: 'copied' -- the step moves whole ring rows with mxl_beam_reorder -- or 'indexed': the rings stay where the forward
         pass wrote them, the `owner` table (identity after the prompt pass: every row holds its own prompt) follows the beams with
         mxl_beam_owner_follow and the attention reads through it (mxl_relattn_decode_owned); M % 16 == 0.  The mode is part of the
-        graph key, the table is step state."""
-        self._bf16_rings_only('beam search on the device')
-        if beam_rings not in BEAM_RINGS:
+        graph key, the table is step state.
+        A decoder with kv_dtype='fp8' takes 'indexed': the prompt pass fills FP8 rings (mxl_kv_fill_fp8), every step appends to the
+        row's own slot (mxl_kv_append_fp8) -- the slot the follow kernel marks as the row's own -- and mxl_relattn_decode_fp8_owned
+        reads through the table, so no ring is ever moved.  'copied' on such a decoder is the reference of the tests and nothing else:
+        `beam_step` moves the four ring lists with torch.index_select, which is slow (a temporary copy of every ring per step), eager
+        only (MusicXLError under use_graph) and not reachable from `generate`."""
+        if beam_rings not in DECODER_BEAM_RINGS:
             raise ValueError(f"beam_rings={beam_rings!r}: expected 'copied' or 'indexed'")
+        if self.kv_dtype is not None and beam_rings == 'copied' and use_graph:
+            raise MusicXLError(f"beam search on the device moves {self.kv_dtype} K/V rings with index_select alone, the eager reference "
+                               "of the tests: use_graph=False, or beam_rings='indexed'")
         if beam_rings == 'indexed' and self.eng.cfg.mem_len % 16:
             raise MusicXLError(f"beam_rings='indexed' takes a mem_len that is a multiple of 16, not {self.eng.cfg.mem_len}")
         if max_length > self.Tmax:
@@ -1451,6 +1467,13 @@ class XLDecoder(RuledGenerate):
         rules = self.beam_select()
         if self.beam_rings == 'indexed':
             ops.beam_owner_follow(self.owner, self._beam_args[0], self.beam.beam_idx, self.beam.moved, self.t_dev)
+        elif self.kv_dtype is not None:
+            # the tests' reference for indexed fp8 rings (beam_begin): bytes and exponents follow their beams by index_select; the
+            # rows of an item with moved == 0 stay (its beam_idx is not valid)
+            nb, rows = self._beam_args[0], torch.arange(self.B, device=self.eng.dev)
+            src = torch.where(self.beam.moved.repeat_interleave(nb) != 0, self.beam.beam_idx.to(torch.int64), rows)
+            for ring in self.kc + self.vc + self.ke + self.ve:
+                ring.copy_(ring.index_select(0, src))
         else:
             ops.beam_reorder(self.kc + self.vc, self._beam_args[0], self.beam.beam_idx, self.beam.moved, table=self.ring_table)
         ops.decode_advance(self.t_dev, self.rng)

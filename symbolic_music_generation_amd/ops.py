@@ -1136,8 +1136,10 @@ def relattn_decode(qkv, kc, vc, rd, rwb, rrb, out, t_dev, H, dh, qr_buf, bd_buf,
 
 
 def relattn_decode_fp8(qkv, kc8, ke, vc8, ve, rd, rwb, rrb, out, t_dev, H, dh, qr_buf, bd_buf, scale=None, qr_ready=False, split=None,
-                       pieces=1, unfinished=None):
-    """relattn_decode over fp8 rings (mxl_relattn_decode_fp8): the same BD launch, then the one fp8 attention entry"""
+                       pieces=1, unfinished=None, owner=None, nb=1):
+    """relattn_decode over fp8 rings (mxl_relattn_decode_fp8): the same BD launch, then the one fp8 attention entry.
+    owner: (B, M) uint8 with `nb` rows per item -- indexed rings: the bytes and the exponents of slot s of row b are read from the
+    rings of row (b // nb) * nb + owner[b, s] (mxl_relattn_decode_fp8_owned)."""
     _req_fp8_rings(kc8, ke, vc8, ve, 'relattn_decode_fp8')
     B, _, M, _ = kc8.shape
     d = H * dh
@@ -1152,6 +1154,15 @@ def relattn_decode_fp8(qkv, kc8, ke, vc8, ve, rd, rwb, rrb, out, t_dev, H, dh, q
     if unfinished is not None:
         _req(unfinished, torch.int32, 'relattn_decode_fp8 unfinished')
     n = pieces if (split is not None and pieces > 1) else 1
+    if owner is not None:
+        _req(owner, torch.uint8, 'relattn_decode_fp8 owner')
+        if tuple(owner.shape) != (B, M) or not owner.is_contiguous():
+            raise MusicXLError(f'relattn_decode_fp8: owner must be a contiguous ({B}, {M}) uint8 table')
+        check(lib().mxl_relattn_decode_fp8_owned(_p(qkv), _p(kc8), _p(ke), _p(vc8), _p(ve), _p(owner), int(nb), _p(bd_buf), _p(rwb),
+                                                 _p(out), _p(t_dev), B, H, dh, M, float(scale), n, _p(split[0]) if n > 1 else 0,
+                                                 _p(split[1]) if n > 1 else 0, _p(unfinished), _stream()),
+              'mxl_relattn_decode_fp8_owned')
+        return
     check(lib().mxl_relattn_decode_fp8(_p(qkv), _p(kc8), _p(ke), _p(vc8), _p(ve), _p(bd_buf), _p(rwb), _p(out), _p(t_dev), B, H, dh, M,
                                        float(scale), n, _p(split[0]) if n > 1 else 0, _p(split[1]) if n > 1 else 0,
                                        _p(unfinished), _stream()), 'mxl_relattn_decode_fp8')

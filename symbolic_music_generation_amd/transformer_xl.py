@@ -334,7 +334,13 @@ class MyTransfoXLLMHeadModel(EngineModule):
         every rule those paths take and with `use_graph` on and off; `mem_len` must be a multiple of 16.  An explicit 'indexed' is a
         ValueError under greedy decoding, sampling and contrastive search, under the host scorers (`MXL_BEAM_HOST=1`, more than 16
         beams, beam-sample without `device_scorer`) and with `kv_cache_dtype='fp8'`; any other string is a ValueError.
-        `MXL_BEAM_RINGS=indexed` sets the default of calls that do not pass the keyword and is ignored where 'indexed' does not apply."""
+        `MXL_BEAM_RINGS=indexed` sets the default of calls that do not pass the keyword and is ignored where 'indexed' does not apply.
+        'indexed_fp8' (opt-in, the same searches): 'indexed' over FP8 rings -- the search's decoder is built with the ring format of
+        `kv_cache_dtype='fp8'`, the rings are never moved and mxl_relattn_decode_fp8_owned reads bytes and exponents through the owner
+        table: (dh + 1) / (2 dh) of the ring memory, so twice the beams, prompts or `mem_len` in the same memory.  K and V are rounded
+        to four significant bits, so ids and scores are other ones than the bf16 rings give.  It applies and is refused exactly where
+        'indexed' is (and `MXL_BEAM_RINGS=indexed_fp8` is ignored there); a `d_head` other than 16, 32 or 64 is a MusicXLError.  The
+        spelling is this one value: `kv_cache_dtype='fp8'` keeps raising under every search, with either `beam_rings`."""
         from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, beam_generate, beam_sample_device,
                                beam_search_device, check_grammar_args, contrastive_search, contrastive_search_device,
                                group_beam_search_device, left_pad_counts, plan_search, resolve_beam_rings, resolve_kv_dtype,
@@ -369,7 +375,10 @@ class MyTransfoXLLMHeadModel(EngineModule):
             raise ValueError(f"kv_cache_dtype='{kv_dtype}' is not supported under {name} search: it moves rings with "
                              'mxl_beam_reorder / mxl_ring_slot_broadcast, which take bf16 rings alone; greedy decoding and sampling do')
         rings = resolve_beam_rings(beam_rings, plan.device and plan.strategy in ('beam', 'group_beam', 'beam_sample') and kv_dtype is None
-                                   and self.config.mem_len % 16 == 0)
+                                   and self.config.mem_len % 16 == 0, self.config.d_head)
+        # 'indexed_fp8' is the decoder's 'indexed' mode on a decoder with FP8 rings; every other call builds the decoder it built
+        fp8_rings = dict(kv_dtype='fp8') if rings == 'indexed_fp8' else {}
+        rings = 'indexed' if fp8_rings else rings
         B0 = input_ids.shape[0]
         ranges = dict(register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below)
         rules = rules_config(batch=B0, vocab_size=self.config.vocab_size, stop=stop, grammar=grammar, n_bars=n_bars, in_key=in_key,
@@ -388,10 +397,10 @@ class MyTransfoXLLMHeadModel(EngineModule):
                          num_return_sequences=num_return_sequences, use_graph=use_graph, grammar=grammar, in_key=in_key, key=key, **ranges,
                          **ends, beam_rings=rings)
             if plan.strategy == 'beam_sample':
-                dec = XLDecoder(self.engine, B0 * num_return_sequences * num_beams, max_length, seed=seed)
+                dec = XLDecoder(self.engine, B0 * num_return_sequences * num_beams, max_length, seed=seed, **fp8_rings)
                 return beam_sample_device(dec, input_ids, max_length, top_k=top_k, top_p=top_p, temperature=temperature,
                                           typical_p=typical_p, **beams)
-            dec = XLDecoder(self.engine, B0 * num_beams, max_length, seed=seed)
+            dec = XLDecoder(self.engine, B0 * num_beams, max_length, seed=seed, **fp8_rings)
             if plan.strategy == 'beam':
                 return beam_search_device(dec, input_ids, max_length, n_bars=n_bars, **beams)
             return group_beam_search_device(dec, input_ids, max_length, num_beam_groups=num_beam_groups,
