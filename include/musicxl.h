@@ -818,6 +818,37 @@ int mxl_contrastive_step(void* ctx, long long ctx_bs, float* ctx_inv_norm, int i
                          int ld_ids, int* unfinished, int* n_done, int eos_id, int pad_id, int stop_later, void* stream);
 int mxl_ring_slot_broadcast(const void* table, int n_bufs, int B, int K, int H, int M, int dh, const int* t_dev, const int* sel,
                             void* stream);
+/* Shared rings under contrastive search (csrc/decode_shared.hip): the K rows of a prompt differ in the one ring slot the step wrote,
+ * so the B0 prompts keep one ring each, (B0, H, M, dh) bf16 per layer, and three capture-safe launches (no host read, no allocation)
+ * take the places of mxl_kv_append, mxl_relattn_decode_split_live and mxl_ring_slot_broadcast.  rows = B0 * K, 2 <= K <= 32.
+ *
+ * mxl_kv_stash: qr_out (B, d) bf16 = q + r_r_bias bit for bit as mxl_kv_append writes it (or NULL), and the k / v thirds of the
+ *   (B, 3d) qkv rows -> stash (B, 2d) bf16, k then v, the layer's slice of a (layers, rows, 2d) buffer that lives until the pick.  No
+ *   ring is touched.  d % 8 == 0, 16-byte aligned buffers.
+ * mxl_relattn_decode_shared: the ring attention of one step for the K queries of every prompt over the prompt's ring.  For the query
+ *   of row b*K + k a slot s != *t_dev mod M is read from ring b, and slot *t_dev mod M (K and V) from the row's own qkv row -- the k / v
+ *   that mxl_kv_append would have written there; the ring's slot *t_dev mod M is never read.  qkv (rows, 3d), bd (rows, H, M), out
+ *   (rows, H*dh), unfinished (rows) or NULL as in mxl_relattn_decode_split_live; a sequence with unfinished[b*K] == 0 reads no ring
+ *   byte and leaves zeros in its K rows.  Never-written slots take the positional term alone.  Same arithmetic per query in the same
+ *   order, the same pieces and merge: the output of row b*K + k equals what mxl_relattn_decode_split_live writes at the same `pieces`
+ *   on K copies of ring b whose slot *t_dev mod M holds candidate k's k / v.  A workgroup holds G = 8 queries (G = 4 for K <= 4) and a
+ *   K or V fragment it fetches serves all of them, so a ring is read ceil(K / G) times per launch.  pieces 1..8 with ws
+ *   (mxl_relattn_decode_split_ws_bytes(rows, ...)) and arrived (rows * H ints, zero before the first call) for pieces > 1.
+ *   Shared memory: mxl_relattn_decode_shared_lds_bytes = G * (cap * 4 + 20 * dh) bytes with cap = M for one piece, else
+ *   min(M, ceil(M / pieces) + 34), rounded up to a multiple of 4; it must not exceed 160 KiB.  K outside 2..32, pieces outside 1..8,
+ *   too much shared memory, B0 * ceil(K / G) > 65535 or a buffer that is not 16-byte aligned: MXL_EINVAL; dh other than 16 / 32 / 64:
+ *   MXL_EUNSUPPORTED; nothing is launched on either.  mxl_relattn_decode_shared_lds_bytes returns 0 for arguments outside the domain.
+ * mxl_kv_commit_shared, after mxl_contrastive_step and the rules advance: table = device array of 2 * n_layers addresses of (B0, H, M,
+ *   dh) bf16 rings, the K rings of the layers, then their V rings; stash (n_layers, rows, 2d) as mxl_kv_stash left it.  The stash of
+ *   row b*K + sel[b] goes into slot *t_dev mod M of ring b, for every layer, head and prompt, in one launch; *t_dev is read on the
+ *   device and no other slot is touched.  dh % 8 == 0, B0 and 2 * n_layers <= 65535. */
+size_t mxl_relattn_decode_shared_lds_bytes(int K, int dh, int M, int pieces);
+int mxl_kv_stash(const void* qkv, void* stash, int B, int d, const float* r_r_bias, void* qr_out, void* stream);
+int mxl_relattn_decode_shared(const void* qkv, const void* kcache, const void* vcache, const float* bd, const float* r_w_bias, void* out,
+                              const int* t_dev, int B0, int K, int H, int dh, int M, float scale, int pieces, float* ws, int* arrived,
+                              const int* unfinished, void* stream);
+int mxl_kv_commit_shared(const void* table, int n_layers, const void* stash, int B0, int K, int H, int M, int dh, const int* t_dev,
+                         const int* sel, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Reformer path (A6-A8): replaces HuggingFace modeling_reformer.py as reached through

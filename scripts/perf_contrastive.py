@@ -18,6 +18,15 @@ reads and writes it again), one slot per ring, head and row after.
 
     python3 scripts/perf_contrastive.py                  # env: RUNS (5), NEW (256), ONLY (ref | b4k8), MODE (device | eager | host:
                                                          # one call of that path alone, for a kernel trace)
+
+RINGS=shared compares the two ring modes of the device path instead (generate(contrastive_rings=)): 'copied', one set of rings per
+candidate row, and 'shared', one per prompt read by its K candidates (mxl_kv_stash / mxl_relattn_decode_shared /
+mxl_kv_commit_shared).  The two are alternated, RUNS calls each after a warm-up call each, with equal ids asserted, at four shapes:
+ref and b4k8 above, b8k16 (8 prompts x top_k 16, 256-token prompts) and b8k16full (the same with 2048-token prompts: a full ring from
+the first step).  Reports the median, the slowest and the fastest run of each mode, the ring memory of either decoder from its
+tensors, and whether the slowest shared run beats the fastest copied run (the criterion of profiles/beam_step.txt).
+
+    RINGS=shared python3 scripts/perf_contrastive.py     # env: RUNS (5), NEW (256), ONLY (ref | b4k8 | b8k16 | b8k16full)
 """
 import os
 import statistics
@@ -57,7 +66,63 @@ def run(kw, mode, **extra):
     return time.perf_counter() - t0, out
 
 
+def compare_rings():
+    from symbolic_music_generation_amd import generate as G
+    built = []
+    real = G.XLDecoder
+
+    class Recorded(real):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            built.append(self)
+    G.XLDecoder = Recorded
+    shapes = dict(SETTINGS, b8k16=(8, 16, 0.3), b8k16full=(8, 16, 0.3))
+    for name, (B, K, alpha) in shapes.items():
+        if os.environ.get('ONLY', name) != name:
+            continue
+        tp = M if name.endswith('full') else Tp
+        ids = torch.randint(4, V, (B, tp), generator=torch.Generator().manual_seed(77)).to(dev)
+        kw = dict(input_ids=ids, max_length=tp + NEW, top_k=K, penalty_alpha=alpha, eos_token_id=V + 1, pad_token_id=0)
+        outs, mem, pieces = {}, {}, {}
+        for mode in G.CONTRASTIVE_RINGS:                                        # warm-up of either mode
+            del built[:]
+            outs[mode] = run(kw, 'device', contrastive_rings=mode)[1]
+            dec = built[0]
+            mem[mode] = sum(t.numel() * t.element_size() for t in dec.kc + dec.vc + ([dec.stash] if dec.shared_K else []))
+            pieces[mode] = dec.pieces
+        del built[:], dec
+        # equal by construction where both decoders cut the ring alike; with other piece counts the attention outputs may differ in
+        # the last bf16 bit (mxl_relattn_decode_split), so a difference there is reported, not asserted away
+        same = torch.equal(outs['copied'], outs['shared'])
+        assert same or pieces['copied'] != pieces['shared'], f'{name}: the ids of the two ring modes differ at equal piece counts'
+        agree = int((outs['copied'] == outs['shared']).all(0).int().cumprod(0).sum()) - tp
+        times = {mode: [] for mode in G.CONTRASTIVE_RINGS}
+        for _ in range(RUNS):
+            for mode in G.CONTRASTIVE_RINGS:
+                t, out = run(kw, 'device', contrastive_rings=mode)
+                assert torch.equal(out, outs[mode])
+                times[mode].append(t)
+                del built[:]
+        tps = {mode: sorted(B * NEW / t for t in times[mode]) for mode in times}
+        print(f'contrastive search [{name}], C5 decode shape: {B} prompt(s) x {tp}, top_k {K} ({B * K} rows), penalty_alpha {alpha}, '
+              f'{NEW} new tokens, eos never fires, captured step; shared ids == copied ids: {same}'
+              + ('' if same else f' (the first {agree} of {NEW} generated columns agree)'))
+        for mode in times:
+            print(f'{mode:6s}: {statistics.median(tps[mode]):9.1f} tok/s median of {RUNS} (slowest {tps[mode][0]:.1f}, fastest '
+                  f'{tps[mode][-1]:.1f}); {statistics.median(times[mode]):.3f} s per call; rings{" + stash" if mode == "shared" else ""} '
+                  f'{mem[mode] / 1e6:.1f} MB, {pieces[mode]} ring piece(s) per attention workgroup set')
+        c, sh = tps['copied'], tps['shared']
+        verdict = 'faster' if sh[0] > c[-1] else ('slower' if sh[-1] < c[0] else 'level')
+        print(f'shared / copied = {statistics.median(sh) / statistics.median(c):.3f}x; the slowest shared run ({sh[0]:.1f} tok/s) against '
+              f'the fastest copied run ({c[-1]:.1f} tok/s): shared is {verdict}')
+    G.XLDecoder = real
+
+
 MODES = ('device', 'eager', 'host')
+if os.environ.get('RINGS') == 'shared':
+    with torch.no_grad():
+        compare_rings()
+    sys.exit(0)
 with torch.no_grad():
     for name, (B, K, alpha) in SETTINGS.items():
         if os.environ.get('ONLY', name) != name:

@@ -1120,8 +1120,35 @@ def resolve_beam_rings(beam_rings: Optional[str], applies: bool, d_head: int = 6
     return mode
 
 
+CONTRASTIVE_RINGS = ('copied', 'shared')                   # what `generate(contrastive_rings=)` takes
+
+
+def resolve_contrastive_rings(contrastive_rings: Optional[str], applies: bool) -> str:
+    """the K/V rings of a contrastive search on the device: 'copied' (one set of rings per candidate row, the step's slot follows the
+    pick with mxl_ring_slot_broadcast; None means this) or 'shared' (one set per prompt, read by its K candidates:
+    mxl_kv_stash / mxl_relattn_decode_shared / mxl_kv_commit_shared, XLDecoder(shared_rings=K)).  A call that names none takes
+    MXL_CONTRASTIVE_RINGS (an A/B knob: unset, nothing changes).  applies: the call is a contrastive search with its step on the device
+    (top_k <= 32, no MXL_CONTRASTIVE_HOST=1) over bf16 rings.  An explicit 'shared' anywhere else is a ValueError, the environment's
+    is ignored there; any other string is a ValueError."""
+    explicit = contrastive_rings is not None
+    mode = contrastive_rings if explicit else (os.environ.get('MXL_CONTRASTIVE_RINGS') or 'copied')
+    if mode not in CONTRASTIVE_RINGS:
+        raise ValueError(f"contrastive_rings={mode!r}: expected None, 'copied' or 'shared'")
+    if mode != 'copied' and not applies:
+        if explicit:
+            raise ValueError("contrastive_rings='shared' serves contrastive search with its step on the device over bf16 rings: not "
+                             'greedy decoding, sampling or a beam search, not the host-driven loop (top_k > 32, '
+                             "MXL_CONTRASTIVE_HOST=1), not kv_cache_dtype='fp8'")
+        mode = 'copied'
+    return mode
+
+
 class XLDecoder(RuledGenerate):
-    def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77, kv_dtype: Optional[str] = None):
+    def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77, kv_dtype: Optional[str] = None,
+                 shared_rings: int = 0):
+        """shared_rings = K > 0: a decoder for contrastive search alone (contrastive_begin) whose `batch` = B0 * K rows keep one set of
+        bf16 rings per prompt, (B0, H, M, dh) per layer, and a stash (L, batch, 2d) for the k / v of the step (csrc/decode_shared.hip);
+        everything per candidate stays `batch` rows.  0: every row owns its rings."""
         self.eng = engine
         c = engine.cfg
         self.B, self.Tmax = batch, max_total_len
@@ -1132,6 +1159,19 @@ class XLDecoder(RuledGenerate):
         if kv_dtype not in (None, 'fp8'):
             raise ValueError(f"kv_dtype={kv_dtype!r}: expected None (bf16 rings) or 'fp8'")
         self.kv_dtype = kv_dtype
+        self.shared_K = K = int(shared_rings)
+        ring_rows, attn_rows = batch, batch
+        if K:
+            if kv_dtype is not None:
+                raise ValueError(f'shared rings are bf16 rings: kv_dtype={kv_dtype!r} is not supported')
+            if K < 2 or K > CONTRASTIVE_MAX or batch % K:
+                raise MusicXLError(f'shared rings take 2..{CONTRASTIVE_MAX} candidates per prompt and one decoder row per candidate')
+            if dh not in (16, 32, 64):
+                raise MusicXLError(f'shared rings need a head width of 16, 32 or 64, not {dh}')
+            # the attention launch has one workgroup per (head, prompt, group of 8 candidates -- 4 for K <= 4) and ring piece
+            ring_rows = batch // K
+            attn_rows = ring_rows * (1 if K <= 4 else (K + 7) // 8)
+            self.stash = torch.empty(L, batch, 2 * d, **bf)
         if kv_dtype == 'fp8':
             # e4m3fn bytes with one int8 exponent per slot and head ("FP8 rings"): (dh + 1) / (2 dh) of the bf16 bytes
             if dh not in (16, 32, 64):
@@ -1141,8 +1181,8 @@ class XLDecoder(RuledGenerate):
             self.ke = [torch.zeros(batch, H, M, device=dev, dtype=torch.int8) for _ in range(L)]
             self.ve = [torch.zeros(batch, H, M, device=dev, dtype=torch.int8) for _ in range(L)]
         else:
-            self.kc = [torch.zeros(batch, H, M, dh, **bf) for _ in range(L)]    # head-major rings
-            self.vc = [torch.zeros(batch, H, M, dh, **bf) for _ in range(L)]
+            self.kc = [torch.zeros(ring_rows, H, M, dh, **bf) for _ in range(L)]    # head-major rings
+            self.vc = [torch.zeros(ring_rows, H, M, dh, **bf) for _ in range(L)]
             self.ke = self.ve = []
         self.rd = None                                  # per-layer Rd tables (eval: no dropout on pos_emb)
         self.ids = torch.zeros(batch, max_total_len + 1, device=dev, dtype=torch.int64)
@@ -1156,8 +1196,11 @@ class XLDecoder(RuledGenerate):
         self.slabs = torch.zeros(4, 64, d, device=dev, dtype=torch.float32)   # K-slice partials of the FFN output projection
         self.bd = torch.empty(batch, H, M, device=dev, dtype=torch.float32)
         # ring pieces per (sequence, head): the attention launch fills every CU with the same number of bytes (ops.decode_ring_pieces)
-        self.pieces = ops.decode_ring_pieces(batch, H, M)
+        self.pieces = ops.decode_ring_pieces(attn_rows, H, M)
         self.split = ops.relattn_decode_split_scratch(batch, H, dh, self.pieces, dev)
+        if K and not 0 < ops.relattn_decode_shared_lds_bytes(K, dh, M, self.pieces) <= ops.SHARED_LDS_MAX:
+            raise MusicXLError(f'shared rings: mem_len {M} in {self.pieces} piece(s) needs more than the {ops.SHARED_LDS_MAX >> 10} KiB of '
+                               f'shared memory a workgroup of {8 if K > 4 else 4} queries has for its scores')
         self.tmp = torch.empty(batch, d, **bf)
         self.h1 = torch.empty(batch, d, **bf)
         self.a = torch.empty(batch, Fi, **bf)
@@ -1215,6 +1258,8 @@ class XLDecoder(RuledGenerate):
         e, c = self.eng, self.eng.cfg
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
+        if self.shared_K:
+            raise MusicXLError('a decoder with shared rings serves contrastive search alone (contrastive_begin)')
         self._tables()
         self.beam_rings = 'copied'                          # every row reads its own ring until a beam_begin says otherwise
         for k in self.kc + self.vc + self.ke + self.ve:     # (fp8: zero bytes with e = 0 are the zero memories)
@@ -1251,6 +1296,37 @@ class XLDecoder(RuledGenerate):
         self.rules.check_prompt(self.ids)
         if sampling is not None:                       # None: the caller picks the token from self.logp (beam search)
             self._sample_advance(self.logp, sampling)  # t = Tp: position of the token just sampled
+        return out
+
+    def _prefill_shared(self, prompt: torch.Tensor, rules: RulePlan):
+        """the prompt pass of a decoder with shared rings: `prompt` (B0, Tp), one row per prompt, through the training-shape kernels
+        once -- B0 rows, not B0 * K -- into the B0 rings.  The log-probabilities of the last position go to rows b*K of `logp`, where
+        mxl_contrastive_topk reads them (sel starts at 0); ids and the rule words start in all B0 * K rows as `prefill` starts them."""
+        e, c, K = self.eng, self.eng.cfg, self.shared_K
+        B0, Tp = prompt.shape
+        assert B0 * K == self.B and Tp + 1 <= self.Tmax + 1
+        self._tables()
+        self.beam_rings = 'copied'
+        for k in self.kc + self.vc:
+            k.zero_()
+        x = prompt.to(e.dev)
+        self.ids.zero_()
+        self.ids[:, :Tp].copy_(x.repeat_interleave(K, 0))
+        self.rules.start(self.ids, Tp, c.vocab_size, rules)
+        out = e.forward(x, mems=None, labels=None, train=False, want_logprobs=False,
+                        kv_sink=lambda l, qkv: ops.kv_fill(qkv, self.kc[l], self.vc[l], Tp), n_pad=None)
+        ws = e._last
+        if ws.logits is None:       # bucketed (large-vocabulary) head: project the prompts' last hidden states in rows b*K
+            self.tmp.zero_()
+            self.tmp[::K].copy_(ws.hid.view(B0, Tp, -1)[:, Tp - 1])
+            self._head(self.tmp)
+        else:
+            logp = torch.empty(B0, c.vocab_size, device=e.dev, dtype=torch.float32)
+            ops.adaptive_logprob(ws.logits.view(B0, Tp, -1)[:, Tp - 1], logp, B0, c.vocab_size, tuple(c.cutoffs))
+            self.logp[::K].copy_(logp)
+        self.t_dev.fill_(Tp - 1)
+        self._trace()
+        self.rules.check_prompt(self.ids)
         return out
 
     def _sample_advance(self, scores, sampling: dict):
@@ -1307,13 +1383,21 @@ class XLDecoder(RuledGenerate):
                 ops.relattn_decode_fp8(self.qkv, self.kc[l], self.ke[l], self.vc[l], self.ve[l], self.rd[l],
                                        e._lw(l, 'dec_attn.r_w_bias', e.P), rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True,
                                        split=self.split, pieces=self.pieces, unfinished=live, **owned)
+            elif self.shared_K:
+                # shared rings: no ring write before the pick -- projection, then q + r_r_bias and the row's k / v into the layer's
+                # stash (for B <= 64 one launch more per layer than the fused form below), then the K queries of a prompt over its ring
+                G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
+                ops.kv_stash(self.qkv, self.stash[l], rrb=rrb.reshape(-1), qr_out=self.qr)
+                ops.relattn_decode_shared(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P), rrb, self.av,
+                                          self.t_dev, self.shared_K, H, dh, self.qr, self.bd, qr_ready=True, split=self.split,
+                                          pieces=self.pieces, unfinished=live)
             elif B <= 64:      # projection, ring append and q + r_r_bias in one launch
                 ops.decode_qkv(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, self.kc[l], self.vc[l], self.t_dev,
                                rrb.reshape(-1), self.qr, dh)
             else:
                 G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
                 ops.kv_append(self.qkv, self.kc[l], self.vc[l], self.t_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
-            if self.kv_dtype != 'fp8':
+            if self.kv_dtype != 'fp8' and not self.shared_K:
                 ops.relattn_decode(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P),
                                    rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces,
                                    unfinished=live, **owned)
@@ -1496,17 +1580,24 @@ class XLDecoder(RuledGenerate):
             raise MusicXLError(f'contrastive search on the device takes 2..{CONTRASTIVE_MAX} candidates and one decoder row per '
                                'candidate')
         c, Tp = self.eng.cfg, prompt.shape[1]
-        self.prefill(prompt, None, None, rules.with_stop((-1 if eos is None else int(eos), int(pad), 0)))
+        if self.shared_K and self.shared_K != K:
+            raise MusicXLError(f'the decoder shares a ring among {self.shared_K} candidates, the search has {K}')
+        stop = rules.with_stop((-1 if eos is None else int(eos), int(pad), 0))
+        if self.shared_K:           # the K rows of a prompt hold the same prompt: the pass runs on every K-th
+            self._prefill_shared(prompt[::K], stop)
+        else:
+            self.prefill(prompt, None, None, stop)
         if self.cs is None or self.cs.K != K:
             self.cs = ContrastiveStore(self.B // K, K, self.Tmax, c.d_model, self.eng.dev)
             self.ring_table = ops.beam_table(self.kc + self.vc)
-        self.cs.start(self.eng._last.h[c.n_layer & 1].view(self.B, Tp, c.d_model)[::K])
+        hid = self.eng._last.h[c.n_layer & 1]
+        self.cs.start(hid.view(self.B // K, Tp, c.d_model) if self.shared_K else hid.view(self.B, Tp, c.d_model)[::K])
         self._cs_args = (int(K), float(alpha), self.rules.stop[0], int(pad))
         self._use_graph, self._step, self.finished_by = use_graph, ('contrastive_step',), (self.cs.n_done, self.cs.B0)
         steps = max_length - Tp - 1
         if steps > 0 and use_graph:
-            key = (('contrastive',) + self._cs_args + (None if self.trace is None else self.trace.data_ptr(),)
-                   + self.rules.graph_key(self.eng.dev))
+            key = (('contrastive', 'shared' if self.shared_K else 'copied') + self._cs_args
+                   + (None if self.trace is None else self.trace.data_ptr(),) + self.rules.graph_key(self.eng.dev))
             self._capture(key, (self.cs.ints, self.logp))
         self.contrastive_step()                       # the first token: column Tp
         return max(steps, 0)
@@ -1515,7 +1606,8 @@ class XLDecoder(RuledGenerate):
         """one whole contrastive step, no host read: the rules mask on the log-probabilities, the K candidates of every sequence
         from its picked row (mxl_contrastive_topk), the position moves on, the candidates go through the model, one is picked and
         written to all K rows (mxl_contrastive_step), the rule words move along it, and the one ring slot the step wrote follows the
-        pick in every layer (mxl_ring_slot_broadcast; the invariant is stated in csrc/contrastive.hip)"""
+        pick in every layer (mxl_ring_slot_broadcast; the invariant is stated in csrc/contrastive.hip).  With shared rings the model
+        writes no ring: the step's k / v wait in the stash and the picked row's go into the prompt's rings (mxl_kv_commit_shared)"""
         c, cs = self.eng.cfg, self.cs
         K, alpha, eos, pad = self._cs_args
         rules = ops.rules_in_force(**self.rules.kwargs())
@@ -1531,7 +1623,10 @@ class XLDecoder(RuledGenerate):
                              self.unfinished, cs.n_done, eos, pad, stop_later=ruled)
         if ruled:
             ops.rules_advance(self.ids, self.t_dev, **rules)
-        ops.ring_slot_broadcast(self.kc + self.vc, K, self.t_dev, cs.sel, table=self.ring_table)
+        if self.shared_K:           # the picked row's k / v of the step become slot t mod M of the prompt's rings
+            ops.kv_commit_shared(self.kc + self.vc, self.stash, K, self.t_dev, cs.sel, table=self.ring_table)
+        else:
+            ops.ring_slot_broadcast(self.kc + self.vc, K, self.t_dev, cs.sel, table=self.ring_table)
 
     def _trace(self):
         if self.trace is not None:
@@ -2039,7 +2134,7 @@ def contrastive_search(dec, prompt: torch.Tensor, max_length: int, top_k: int = 
 def contrastive_search_device(dec, prompt: torch.Tensor, max_length: int, top_k: int = 4, penalty_alpha: float = 0.6,
                               eos_token_id: Optional[int] = 0, pad_token_id: Optional[int] = None, use_graph: bool = True,
                               stop_chunk: int = STOP_CHUNK, grammar=None, in_key=None, key=None, register=None, melody_range=None,
-                              bass_range=None, bass_below=None) -> torch.Tensor:
+                              bass_range=None, bass_below=None, contrastive_rings: Optional[str] = None) -> torch.Tensor:
     """`contrastive_search` with the whole step on the device: per step the rules mask, mxl_contrastive_topk, the position advance,
     the model, mxl_contrastive_step, the rules advance and mxl_ring_slot_broadcast -- no host read, no whole-ring copy, captured once
     under use_graph (XLDecoder.contrastive_begin / contrastive_step).  The steps are replayed in chunks of `stop_chunk`; the number
@@ -2048,11 +2143,21 @@ def contrastive_search_device(dec, prompt: torch.Tensor, max_length: int, top_k:
     finished, else at max_length; the steps run beyond it inside the last chunk emit pad and are cut off.  dec: an XLDecoder with
     prompt rows x top_k rows, 2 <= top_k <= 32.  grammar (with or without a bar budget) / in_key / key / register: the rules as
     rules_config takes them, one value per prompt where they are per row (each prompt's is shared by its K rows); a barred token is -inf
-    before the top-k, and a candidate that is barred is never picked."""
+    before the top-k, and a candidate that is barred is never picked.
+    contrastive_rings: None (what the decoder was built for), 'copied' or 'shared' -- it must name the decoder's mode: 'shared' takes
+    an XLDecoder(shared_rings=top_k), whose B0 rings serve the K candidates of their prompt (mxl_kv_stash /
+    mxl_relattn_decode_shared / mxl_kv_commit_shared in place of the ring append, the attention and the broadcast); the ids are the
+    ones 'copied' returns wherever both decoders cut their rings into the same number of pieces (XLDecoder.pieces)."""
     V = dec.eng.cfg.vocab_size
     K = int(top_k)
     if K < 2 or not penalty_alpha or penalty_alpha <= 0:
         raise ValueError('contrastive search needs top_k > 1 and penalty_alpha > 0')
+    if contrastive_rings is not None:
+        if contrastive_rings not in CONTRASTIVE_RINGS:
+            raise ValueError(f"contrastive_rings={contrastive_rings!r}: expected None, 'copied' or 'shared'")
+        if (contrastive_rings == 'shared') != bool(getattr(dec, 'shared_K', 0)):
+            raise ValueError(f"contrastive_rings='{contrastive_rings}' on a decoder built for the other ring mode "
+                             '(XLDecoder(shared_rings=top_k) is the shared one)')
     B0, Tp = prompt.shape
     rows = B0 * K
     if dec.B != rows or max_length > dec.Tmax:

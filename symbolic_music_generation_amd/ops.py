@@ -1292,6 +1292,77 @@ def ring_slot_broadcast(rings, K, t_dev, sel, table=None):
           'mxl_ring_slot_broadcast')
 
 
+def kv_stash(qkv, stash, rrb=None, qr_out=None):
+    """see mxl_kv_stash: the k / v thirds of the (B, 3d) bf16 qkv rows -> stash (B, 2d) bf16, one layer's slice of the stash that
+    kv_commit_shared reads; with `rrb` (d f32) and `qr_out` (B, d) bf16 the same launch writes q + r_r_bias as kv_append does"""
+    _req(qkv, torch.bfloat16, 'kv_stash qkv'); _req(stash, torch.bfloat16, 'kv_stash stash')
+    B, d = stash.shape[0], stash.shape[-1] // 2
+    if stash.dim() != 2 or tuple(qkv.shape) != (B, 3 * d) or not qkv.is_contiguous() or not stash.is_contiguous():
+        raise MusicXLError('kv_stash: expected contiguous (B, 3d) qkv rows and a (B, 2d) stash')
+    check(lib().mxl_kv_stash(_p(qkv), _p(stash), B, d, _p(rrb), _p(qr_out), _stream()), 'mxl_kv_stash')
+
+
+def relattn_decode_shared_lds_bytes(K: int, dh: int, M: int, pieces: int = 1) -> int:
+    """shared memory of one mxl_relattn_decode_shared workgroup (0: arguments outside its domain); the launch takes up to
+    SHARED_LDS_MAX bytes"""
+    return int(lib().mxl_relattn_decode_shared_lds_bytes(int(K), int(dh), int(M), int(pieces)))
+
+
+SHARED_LDS_MAX = 160 * 1024
+
+
+def relattn_decode_shared(qkv, kc, vc, rd, rwb, rrb, out, t_dev, K, H, dh, qr_buf, bd_buf, scale=None, qr_ready=False, split=None,
+                          pieces=1, unfinished=None):
+    """relattn_decode for the K candidate rows of every prompt over the prompt's one ring (mxl_relattn_decode_shared): kc / vc
+    (B0, H, M, dh), everything per row -- qkv, qr_buf, bd_buf, out, unfinished and the split scratch -- sized for B0 * K rows.  The BD
+    launch is relattn_decode's; slot t mod M of every row comes from its own qkv row."""
+    B0, _, M, _ = kc.shape
+    B, d = B0 * K, H * dh
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    if tuple(qkv.shape) != (B, 3 * d) or tuple(out.shape) != (B, d) or not qkv.is_contiguous() or not out.is_contiguous():
+        raise MusicXLError(f'relattn_decode_shared: expected contiguous ({B}, {3 * d}) qkv and ({B}, {d}) out for {B0} rings x {K} rows')
+    if not kc.is_contiguous() or not vc.is_contiguous() or vc.shape != kc.shape or bd_buf.numel() < B * H * M:
+        raise MusicXLError('relattn_decode_shared: the rings must be contiguous (B0, H, M, dh) and bd_buf hold (B0 * K, H, M) f32')
+    if not qr_ready:
+        add_rowbias(qkv, 3 * d, 3 * d, rrb.reshape(-1), qr_buf, B, 1, d)
+    if dh == 64 and B <= 64:
+        check(lib().mxl_decode_bd(_p(qr_buf), _p(rd), _p(bd_buf), B, H, dh, M, d, rd.stride(0), _stream()), 'mxl_decode_bd')
+    else:
+        gemm_batched(qr_buf, rd, bd_buf, B, M, dh, lda=d, ldb=d, ldc=H * M, flags=GEMM_OUT_F32, batch=H, bdiv=1,
+                     sA=(dh, 0), sB=(dh, 0), sC=(M, 0))
+    if unfinished is not None:
+        _req(unfinished, torch.int32, 'relattn_decode_shared unfinished')
+        if unfinished.numel() != B:
+            raise MusicXLError(f'relattn_decode_shared: unfinished must hold one word per row, {B}')
+    n = pieces if (split is not None and pieces > 1) else 1
+    check(lib().mxl_relattn_decode_shared(_p(qkv), _p(kc), _p(vc), _p(bd_buf), _p(rwb), _p(out), _p(t_dev), B0, int(K), H, dh, M,
+                                          float(scale), n, _p(split[0]) if n > 1 else 0, _p(split[1]) if n > 1 else 0,
+                                          _p(unfinished), _stream()), 'mxl_relattn_decode_shared')
+
+
+def kv_commit_shared(rings, stash, K, t_dev, sel, table=None):
+    """see mxl_kv_commit_shared: rings = the K rings of every layer, then the V rings, contiguous (B0, H, M, dh) bf16 of one shape,
+    with `table`, their addresses (beam_table); stash (layers, B0 * K, 2d) bf16 as kv_stash left it.  The stash of row b*K + sel[b]
+    -> slot t mod M of ring b, one launch for all layers"""
+    first = rings[0]
+    _req(sel, torch.int32, 'kv_commit_shared sel'); _req(stash, torch.bfloat16, 'kv_commit_shared stash')
+    if first.dim() != 4 or len(rings) % 2 or K < 2 or K > CONTRASTIVE_MAX or sel.numel() != first.shape[0] or not sel.is_contiguous():
+        raise MusicXLError(f'kv_commit_shared: K then V rings (B0, H, M, dh), K = 2..{CONTRASTIVE_MAX} rows per ring and sel (B0,)')
+    for t in rings:
+        if not t.is_cuda or not t.is_contiguous() or t.shape != first.shape or t.dtype != torch.bfloat16 or t.data_ptr() % 16:
+            raise MusicXLError('kv_commit_shared: the rings must be contiguous bf16 device tensors of one shape, 16-byte aligned')
+    B0, H, M, dh = first.shape
+    L = len(rings) // 2
+    if tuple(stash.shape) != (L, B0 * K, 2 * H * dh) or not stash.is_contiguous():
+        raise MusicXLError(f'kv_commit_shared: the stash must be contiguous ({L}, {B0 * K}, {2 * H * dh}) bf16')
+    if table is None:
+        table = beam_table(rings)
+    if table.dtype != torch.int64 or table.numel() != len(rings) or not table.is_cuda:
+        raise MusicXLError('kv_commit_shared: the table must hold one device address per ring (beam_table)')
+    check(lib().mxl_kv_commit_shared(_p(table), L, _p(stash), B0, int(K), H, M, dh, _p(t_dev), _p(sel), _stream()),
+          'mxl_kv_commit_shared')
+
+
 # ------------------------------------------------------------------ reformer
 def axial_embed_fwd(ids, E, W0, W1, out, A0, A1, drop_p=0.0, seed=0, site_emb=0, site_pos=1):
     B, T = ids.shape

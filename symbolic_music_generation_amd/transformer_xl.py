@@ -200,7 +200,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None,
                  min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, melody=None,
                  device_scorer: bool = False, register=None, melody_range=None, bass_range=None, bass_below=None,
-                 kv_cache_dtype: Optional[str] = None, beam_rings: Optional[str] = None, **unused) -> torch.Tensor:
+                 kv_cache_dtype: Optional[str] = None, beam_rings: Optional[str] = None,
+                 contrastive_rings: Optional[str] = None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -340,10 +341,26 @@ class MyTransfoXLLMHeadModel(EngineModule):
         table: (dh + 1) / (2 dh) of the ring memory, so twice the beams, prompts or `mem_len` in the same memory.  K and V are rounded
         to four significant bits, so ids and scores are other ones than the bf16 rings give.  It applies and is refused exactly where
         'indexed' is (and `MXL_BEAM_RINGS=indexed_fp8` is ignored there); a `d_head` other than 16, 32 or 64 is a MusicXLError.  The
-        spelling is this one value: `kv_cache_dtype='fp8'` keeps raising under every search, with either `beam_rings`."""
+        spelling is this one value: `kv_cache_dtype='fp8'` keeps raising under every search, with either `beam_rings`.
+
+        `contrastive_rings` (contrastive search with its step on the device): how the K/V rings are held.  None or 'copied': every one of
+        the `top_k` candidate rows of a prompt owns a full set of rings, and the one slot a step writes follows the pick
+        (mxl_ring_slot_broadcast), as ever.  'shared' (opt-in): those rows differ in that one slot alone, so a prompt keeps one set of
+        rings, (prompts, H, mem_len, dh) per layer -- 1 / `top_k` of the ring memory -- the prompt pass runs once per prompt, and the
+        attention of a step reads a prompt's ring once per group of 8 candidates (4 for `top_k` <= 4) for all of them, each taking the
+        step's own slot from its own row (mxl_kv_stash / mxl_relattn_decode_shared / mxl_kv_commit_shared; DESIGN.md, shared rings).
+        The attention output is the copied mode's bit for bit at the same number of ring pieces, so the ids are the ones 'copied'
+        returns with every rule that path takes and with `use_graph` on and off -- by construction for `mem_len` < 1024, where both
+        modes run one piece, and wherever else `generate.XLDecoder.pieces` agrees (MXL_DECODE_PIECES pins it); `d_head` must be 16, 32
+        or 64 and the scores of a workgroup must fit 160 KiB of shared memory (any `mem_len` up to 4096 does), else MusicXLError.  An
+        explicit 'shared' is a ValueError under greedy decoding, sampling and every beam arm, under the host-driven loop
+        (`top_k > 32`, `MXL_CONTRASTIVE_HOST=1`) and with `kv_cache_dtype='fp8'`; any other string is a ValueError.
+        `MXL_CONTRASTIVE_RINGS=shared` sets the default of calls that do not pass the keyword and is ignored where 'shared' does not
+        apply."""
         from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, beam_generate, beam_sample_device,
                                beam_search_device, check_grammar_args, contrastive_search, contrastive_search_device,
-                               group_beam_search_device, left_pad_counts, plan_search, resolve_beam_rings, resolve_kv_dtype,
+                               group_beam_search_device, left_pad_counts, plan_search, resolve_beam_rings, resolve_contrastive_rings,
+                               resolve_kv_dtype,
                                resolve_max_length,
                                rules_config, sampling_config, stop_config)
         kv_dtype = resolve_kv_dtype(kv_cache_dtype)
@@ -370,6 +387,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
                            grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody, device_scorer=device_scorer,
                            repetition_penalty=repetition_penalty, renormalize_logits=renormalize_logits,
                            vocab_size=self.config.vocab_size, register=register)
+        # (before the fp8 refusal: an explicit 'shared' beside kv_cache_dtype='fp8' is refused for what it asks, wherever it is asked)
+        shared = resolve_contrastive_rings(contrastive_rings, plan.strategy == 'contrastive' and plan.device and kv_dtype is None) == 'shared'
         if kv_dtype is not None and plan.strategy != 'sample':
             name = dict(beam='beam', beam_sample='beam-sample', group_beam='group-beam', contrastive='contrastive')[plan.strategy]
             raise ValueError(f"kv_cache_dtype='{kv_dtype}' is not supported under {name} search: it moves rings with "
@@ -387,10 +406,12 @@ class MyTransfoXLLMHeadModel(EngineModule):
             ranges = {}                                     # (a call without the rule hands nothing of it on)
         ends = dict(eos_token_id=plan.eos, pad_token_id=plan.pad)
         if plan.strategy == 'contrastive':
-            dec = XLDecoder(self.engine, B0 * top_k, max_length, seed=seed)
+            # shared rings are another decoder; every other call builds the decoder it built
+            dec = XLDecoder(self.engine, B0 * top_k, max_length, seed=seed, **(dict(shared_rings=top_k) if shared else {}))
             if plan.device:
                 return contrastive_search_device(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha, use_graph=use_graph,
-                                                 grammar=grammar, in_key=in_key, key=key, **ranges, **ends)
+                                                 grammar=grammar, in_key=in_key, key=key, **ranges, **ends,
+                                                 **(dict(contrastive_rings='shared') if shared else {}))
             return contrastive_search(dec, input_ids, max_length, top_k=top_k, penalty_alpha=penalty_alpha, **ends)
         if plan.device:                                     # (the device searches plan per-prompt values per beam themselves)
             beams = dict(num_beams=num_beams, early_stopping=bool(early_stopping), length_penalty=length_penalty,
