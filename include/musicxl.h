@@ -849,6 +849,37 @@ int mxl_relattn_decode_shared(const void* qkv, const void* kcache, const void* v
                               const int* unfinished, void* stream);
 int mxl_kv_commit_shared(const void* table, int n_layers, const void* stash, int B0, int K, int H, int M, int dh, const int* t_dev,
                          const int* sel, void* stream);
+/* One prompt ring shared by the n sampled variations of a prompt (csrc/decode_prefix.hip): the n rows of a prompt hold the same prompt,
+ * so per layer the B0 prompts keep one pair of prompt rings, (B0, H, M, dh) bf16, written once by the prompt pass (mxl_kv_fill: slot =
+ * position mod M) and never again, and every row a pair of tail rings, (rows, H, Mt, dh) bf16, rows = B0 * n, for the positions generated
+ * after the prompt: position p >= Tp of a row lives in tail slot (p - Tp) mod Mt.  Tp is read from the device (t0_dev, one int), so a
+ * captured step does not bake the prompt length in.  Mt a multiple of 16 in 16..M, and at least min(M, generated positions), so that no
+ * tail slot a window still holds is overwritten.  Both entries are capture-safe: no host read, no allocation.
+ *
+ * mxl_kv_append_tail, where mxl_kv_append sat: qr_out (B, d) bf16 = q + r_r_bias bit for bit as mxl_kv_append writes it (or NULL), and
+ *   the k / v thirds of row b of the (B, 3d) qkv rows -> slot (*t_dev - *t0_dev) mod Mt of row b's tail rings, no other byte; *t_dev <
+ *   *t0_dev writes no ring.  d % 8 == 0, dh % 8 == 0, d % dh == 0, Mt % 16 == 0 and >= 16, 16-byte aligned buffers; else MXL_EINVAL.
+ * mxl_relattn_decode_prefix: the ring attention of one step for the n queries of every prompt.  With t = *t_dev and Tp = *t0_dev, ring
+ *   slot s (0..M-1, in the slot order and lane assignment of mxl_relattn_decode) stands for position p = t - ((t - s) mod M), the latest
+ *   one <= t that maps to s: p < 0 was never written and takes the positional term alone (no K / V read); p >= Tp reads K and V from slot
+ *   (p - Tp) mod Mt of the row's own tail rings; any other p reads slot s of the prompt's rings.  qkv (rows, 3d), bd (rows, H, M), out
+ *   (rows, H*dh) as in mxl_relattn_decode_split_live.  unfinished (rows) or NULL is per row: a row with unfinished == 0 reads no tail
+ *   byte and leaves zeros in its output, a group without a live row reads no ring byte.  Same arithmetic per query in the same order,
+ *   the same pieces and merge: the output of row b*n + k equals what mxl_relattn_decode_split_live writes at the same `pieces` on the
+ *   ring that row would own had every position been appended to it.  A workgroup holds G = 8 queries of one prompt (G = 4 for n <= 4;
+ *   the last group of a prompt may be partial); a prompt-ring fragment it fetches serves all of them, tail fragments are fetched per
+ *   query.  pieces 1..8 with ws (mxl_relattn_decode_split_ws_bytes(rows, ...)) and arrived (rows * H ints, zero before the first call)
+ *   for pieces > 1.  Shared memory: mxl_relattn_decode_prefix_lds_bytes = G * (cap * 4 + 16 * dh) bytes, cap as for
+ *   mxl_relattn_decode_shared -- within that entry's G * (cap * 4 + 20 * dh); it must not exceed 160 KiB (any M up to 4096 fits).
+ *   M or Mt not a multiple of 16, Mt outside 16..M, n < 2, pieces outside 1..8, too much shared memory, B0 * ceil(n / G) > 65535 or a
+ *   buffer that is not 16-byte aligned: MXL_EINVAL; dh other than 16 / 32 / 64: MXL_EUNSUPPORTED; nothing is launched on either.
+ *   mxl_relattn_decode_prefix_lds_bytes returns 0 for arguments outside the domain. */
+size_t mxl_relattn_decode_prefix_lds_bytes(int n, int dh, int M, int pieces);
+int mxl_kv_append_tail(const void* qkv, void* ktail, void* vtail, const int* t_dev, const int* t0_dev, int B, int Mt, int d, int dh,
+                       const float* r_r_bias, void* qr_out, void* stream);
+int mxl_relattn_decode_prefix(const void* qkv, const void* kprompt, const void* vprompt, const void* ktail, const void* vtail,
+                              const float* bd, const float* r_w_bias, void* out, const int* t_dev, const int* t0_dev, int B0, int n, int H,
+                              int dh, int M, int Mt, float scale, int pieces, float* ws, int* arrived, const int* unfinished, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Reformer path (A6-A8): replaces HuggingFace modeling_reformer.py as reached through

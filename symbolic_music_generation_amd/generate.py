@@ -1143,10 +1143,57 @@ def resolve_contrastive_rings(contrastive_rings: Optional[str], applies: bool) -
     return mode
 
 
+PROMPT_RINGS = ('copied', 'shared')                        # what `generate(prompt_rings=)` takes
+
+
+def resolve_prompt_rings(prompt_rings: Optional[str], applies: bool) -> str:
+    """the K/V rings of sampling with num_return_sequences = n >= 2: 'copied' (every one of the n rows of a prompt owns a full set of
+    rings and the prompt pass runs on all of them; None means this) or 'shared' (one set of prompt rings per prompt, written once by a
+    prompt pass of the unexpanded batch, and a tail ring per row for what it generates: mxl_kv_append_tail /
+    mxl_relattn_decode_prefix, XLDecoder(prompt_rings=n)).  A call that names none takes MXL_PROMPT_RINGS (an A/B knob: unset, nothing
+    changes).  applies: the call samples (do_sample=True, one beam) with num_return_sequences >= 2 over bf16 rings.  An explicit
+    'shared' anywhere else is a ValueError, the environment's is ignored there; any other string is a ValueError."""
+    explicit = prompt_rings is not None
+    mode = prompt_rings if explicit else (os.environ.get('MXL_PROMPT_RINGS') or 'copied')
+    if mode not in PROMPT_RINGS:
+        raise ValueError(f"prompt_rings={mode!r}: expected None, 'copied' or 'shared'")
+    if mode != 'copied' and not applies:
+        if explicit:
+            raise ValueError("prompt_rings='shared' serves sampling with num_return_sequences >= 2 over bf16 rings: not "
+                             "num_return_sequences=1, greedy decoding, a beam search or contrastive search, not kv_cache_dtype='fp8'")
+        mode = 'copied'
+    return mode
+
+
+def prompt_rings_misfit(cfg, n: int, rows: int) -> Optional[str]:
+    """why a model cannot run prompt_rings='shared' with n rows per prompt in a decoder of `rows` rows (None: it can): the head width,
+    mem_len % 16 and the shared memory of the attention workgroup at the decoder's ring pieces"""
+    M, dh = cfg.mem_len, cfg.d_head
+    if dh not in (16, 32, 64):
+        return f'prompt rings need a head width of 16, 32 or 64, not {dh}'
+    if M % 16 or M < 16:
+        return f'prompt rings take a mem_len that is a multiple of 16, not {M}'
+    pieces = ops.decode_ring_pieces((rows // n) * ops.prefix_attn_groups(n), cfg.n_head, M)
+    if not 0 < ops.relattn_decode_prefix_lds_bytes(n, dh, M, pieces) <= ops.SHARED_LDS_MAX:
+        return (f'prompt rings: mem_len {M} in {pieces} piece(s) needs more than the {ops.SHARED_LDS_MAX >> 10} KiB of shared memory a '
+                f'workgroup of {8 if n > 4 else 4} queries has for its scores')
+    return None
+
+
+def prompt_tail_len(mem_len: int, generated: int) -> int:
+    """slots of a row's tail ring for `generated` positions after the prompt: that many rounded up to a multiple of 16, mem_len at most"""
+    return min(mem_len, max(16, (int(generated) + 15) // 16 * 16))
+
+
 class XLDecoder(RuledGenerate):
     def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77, kv_dtype: Optional[str] = None,
-                 shared_rings: int = 0):
-        """shared_rings = K > 0: a decoder for contrastive search alone (contrastive_begin) whose `batch` = B0 * K rows keep one set of
+                 shared_rings: int = 0, prompt_rings: int = 0, tail_len: Optional[int] = None):
+        """prompt_rings = n > 0: a decoder for sampling alone (begin / run) whose `batch` = B0 * n rows are n variations of each of B0
+        prompts: per layer one pair of bf16 prompt rings per prompt, kc / vc (B0, H, M, dh), written once by the prompt pass of the B0
+        prompts, and one pair of tail rings per row, kt / vt (batch, H, Mt, dh), for the positions generated after the prompt
+        (csrc/decode_prefix.hip); Mt = prompt_tail_len(M, tail_len), tail_len = the most positions a generation adds to its prompt (None:
+        a full ring).  `t0_dev` holds the prompt length of the generation at hand.  0: every row owns its rings.
+        shared_rings = K > 0: a decoder for contrastive search alone (contrastive_begin) whose `batch` = B0 * K rows keep one set of
         bf16 rings per prompt, (B0, H, M, dh) per layer, and a stash (L, batch, 2d) for the k / v of the step (csrc/decode_shared.hip);
         everything per candidate stays `batch` rows.  0: every row owns its rings."""
         self.eng = engine
@@ -1160,7 +1207,24 @@ class XLDecoder(RuledGenerate):
             raise ValueError(f"kv_dtype={kv_dtype!r}: expected None (bf16 rings) or 'fp8'")
         self.kv_dtype = kv_dtype
         self.shared_K = K = int(shared_rings)
+        self.prompt_n = n = int(prompt_rings)
+        self.kt = self.vt = []
         ring_rows, attn_rows = batch, batch
+        if n:
+            if kv_dtype is not None or K:
+                raise ValueError('prompt rings are bf16 rings under sampling: neither kv_dtype nor shared_rings goes with them')
+            if n < 2 or batch % n:
+                raise MusicXLError('prompt rings take 2 or more rows per prompt and one decoder row per variation')
+            misfit = prompt_rings_misfit(c, n, batch)
+            if misfit:
+                raise MusicXLError(misfit)
+            # the attention launch has one workgroup per (head, prompt, group of 8 rows -- 4 for n <= 4) and ring piece
+            ring_rows = batch // n
+            attn_rows = ring_rows * ops.prefix_attn_groups(n)
+            self.Mt = prompt_tail_len(M, M if tail_len is None else tail_len)
+            self.kt = [torch.zeros(batch, H, self.Mt, dh, **bf) for _ in range(L)]
+            self.vt = [torch.zeros(batch, H, self.Mt, dh, **bf) for _ in range(L)]
+            self.t0_dev = torch.zeros(1, device=dev, dtype=torch.int32)
         if K:
             if kv_dtype is not None:
                 raise ValueError(f'shared rings are bf16 rings: kv_dtype={kv_dtype!r} is not supported')
@@ -1260,6 +1324,10 @@ class XLDecoder(RuledGenerate):
         assert B == self.B and Tp + 1 <= self.Tmax + 1
         if self.shared_K:
             raise MusicXLError('a decoder with shared rings serves contrastive search alone (contrastive_begin)')
+        if self.prompt_n:
+            if sampling is None:
+                raise MusicXLError('a decoder with prompt rings serves sampling alone (begin / run), not a search')
+            return self._prefill_prefix(prompt, sampling, n_pad, rules)
         self._tables()
         self.beam_rings = 'copied'                          # every row reads its own ring until a beam_begin says otherwise
         for k in self.kc + self.vc + self.ke + self.ve:     # (fp8: zero bytes with e = 0 are the zero memories)
@@ -1329,6 +1397,48 @@ class XLDecoder(RuledGenerate):
         self.rules.check_prompt(self.ids)
         return out
 
+    def _prefill_prefix(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor], rules: RulePlan):
+        """the prompt pass of a decoder with prompt rings: `prompt` (B0 * n, Tp) holds every prompt n times over (repeat_interleave, as
+        `generate` expands it; n_pad likewise), and the pass runs on every n-th row -- B0 rows through the training-shape kernels, pad
+        K / V zeroed as in `prefill` -- into the B0 prompt rings, which no step writes again.  The log-probabilities of the last
+        position go to all n rows of their prompt; ids and the rule words start in all rows as `prefill` starts them, and the first
+        token of every row is drawn by the ordinary sampler launch (the draw is keyed by seed, row and step).  t0_dev <- Tp."""
+        e, c, n = self.eng, self.eng.cfg, self.prompt_n
+        B, Tp = prompt.shape
+        B0 = B // n
+        self._tables()
+        self.beam_rings = 'copied'
+        x = prompt.to(e.dev)
+        if not bool((x.view(B0, n, Tp) == x[::n, None]).all()):
+            raise MusicXLError(f'a decoder with prompt rings takes every prompt {n} times in a row (repeat_interleave)')
+        for k in self.kc + self.vc + self.kt + self.vt:
+            k.zero_()
+        self.ids.zero_()
+        self.ids[:, :Tp].copy_(x)
+        if n_pad is not None:
+            n_pad = n_pad.to(e.dev, torch.int32).contiguous()
+            pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
+            self.ids[:, :Tp].masked_fill_(pad, -1)
+            x = x.masked_fill(pad, 0)
+            n_pad = n_pad[::n].contiguous()
+        self.rules.start(self.ids, Tp, c.vocab_size, rules)
+        out = e.forward(x[::n].contiguous(), mems=None, labels=None, train=False, want_logprobs=False,
+                        kv_sink=lambda l, qkv: ops.kv_fill(qkv, self.kc[l], self.vc[l], Tp), n_pad=n_pad)
+        ws = e._last
+        if ws.logits is None:       # bucketed (large-vocabulary) head: project the last hidden state of every row's prompt
+            self.tmp.copy_(ws.hid.view(B0, Tp, -1)[:, Tp - 1].repeat_interleave(n, 0))
+            self._head(self.tmp)
+        else:
+            logp = torch.empty(B0, c.vocab_size, device=e.dev, dtype=torch.float32)
+            ops.adaptive_logprob(ws.logits.view(B0, Tp, -1)[:, Tp - 1], logp, B0, c.vocab_size, tuple(c.cutoffs))
+            self.logp.copy_(logp.repeat_interleave(n, 0))
+        self.t_dev.fill_(Tp - 1)
+        self.t0_dev.fill_(Tp)
+        self._trace()
+        self.rules.check_prompt(self.ids)
+        self._sample_advance(self.logp, sampling)      # t = Tp: position of the token just sampled
+        return out
+
     def _sample_advance(self, scores, sampling: dict):
         """next token of every row from `scores` (log-probabilities, or the head's logits: see mxl_sample_step) -> ids[:, t + 1];
         position and RNG counters advanced.  Short chain: the same launch leaves the token's embedding row in h[0] for the next step."""
@@ -1391,13 +1501,21 @@ class XLDecoder(RuledGenerate):
                 ops.relattn_decode_shared(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P), rrb, self.av,
                                           self.t_dev, self.shared_K, H, dh, self.qr, self.bd, qr_ready=True, split=self.split,
                                           pieces=self.pieces, unfinished=live)
+            elif self.prompt_n:
+                # prompt rings: projection, then q + r_r_bias and the row's k / v into its tail ring (for B <= 64 one launch more per
+                # layer than the fused form below), then the n queries of a prompt over its ring and their own tails
+                G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
+                ops.kv_append_tail(self.qkv, self.kt[l], self.vt[l], self.t_dev, self.t0_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
+                ops.relattn_decode_prefix(self.qkv, self.kc[l], self.vc[l], self.kt[l], self.vt[l], self.rd[l],
+                                          e._lw(l, 'dec_attn.r_w_bias', e.P), rrb, self.av, self.t_dev, self.t0_dev, self.prompt_n, H, dh,
+                                          self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces, unfinished=live)
             elif B <= 64:      # projection, ring append and q + r_r_bias in one launch
                 ops.decode_qkv(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, self.kc[l], self.vc[l], self.t_dev,
                                rrb.reshape(-1), self.qr, dh)
             else:
                 G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
                 ops.kv_append(self.qkv, self.kc[l], self.vc[l], self.t_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
-            if self.kv_dtype != 'fp8' and not self.shared_K:
+            if self.kv_dtype != 'fp8' and not self.shared_K and not self.prompt_n:
                 ops.relattn_decode(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P),
                                    rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces,
                                    unfinished=live, **owned)
@@ -1644,6 +1762,9 @@ class XLDecoder(RuledGenerate):
         generation with other values, such as another guide that fits the buffer, replays the same graph"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
+        if self.prompt_n and self.Mt < min(self.eng.cfg.mem_len, max_length - prompt.shape[1]):
+            raise MusicXLError(f'the tail rings of this decoder hold {self.Mt} generated positions, the call asks for '
+                               f'{max_length - prompt.shape[1]} (XLDecoder(tail_len=))')
         self._use_graph, self._step, self.finished_by = use_graph, ('step', sampling), (self.alive, 0)
         self.prefill(prompt, sampling, n_pad, rules)
         steps = max_length - prompt.shape[1] - 1
@@ -1652,6 +1773,8 @@ class XLDecoder(RuledGenerate):
             # itself is written by the captured launches): a graph captured without a trace would replay without writing one
             key = (tuple(sorted(sampling.items())), self.fused_sampler,
                    None if self.trace is None else self.trace.data_ptr()) + self.rules.graph_key(self.eng.dev)
+            if self.prompt_n:       # the ring mode: another set of launches over other buffers (the prompt length is step state, t0_dev)
+                key += (('prompt_rings', self.prompt_n, self.Mt),)
             self._capture(key, (self.h[0],))      # (short chain: the next step's embedding row is step state too)
         return max(steps, 0)
 
@@ -1668,7 +1791,7 @@ class XLDecoder(RuledGenerate):
         carries from one step to the next"""
         if self.graph is not None and self._graph_key == key:
             return
-        live = (self.t_dev, self.rng, self.ids, *self.kc, *self.vc, *self.ke, *self.ve, *extra)
+        live = (self.t_dev, self.rng, self.ids, *self.kc, *self.vc, *self.ke, *self.ve, *self.kt, *self.vt, *extra)
         saved, words = [t.clone() for t in live], self.rules.snapshot()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -1698,13 +1821,22 @@ class XLDecoderLanes(RuledGenerate):
     overlap the other's ring streaming (sequences are independent: the lanes never synchronise until the generation ends).
     Same interface as XLDecoder for `generate` / `begin` / `replay_once`; rows keep their order."""
 
-    def __init__(self, engine, batch: int, max_total_len: int, seed: int = 1234, lanes: int = 2, kv_dtype: Optional[str] = None):
-        assert 1 <= lanes <= batch
-        self.B, self.Tmax, self.n, self.kv_dtype = batch, max_total_len, lanes, kv_dtype
-        self.sizes = [batch // lanes + (1 if i < batch % lanes else 0) for i in range(lanes)]
+    def __init__(self, engine, batch: int, max_total_len: int, seed: int = 1234, lanes: int = 2, kv_dtype: Optional[str] = None,
+                 prompt_rings: int = 0, tail_len: Optional[int] = None):
+        """prompt_rings = n > 0: every lane is an XLDecoder(prompt_rings=n), and the lanes are cut at prompt boundaries -- the batch / n
+        prompts are dealt to the lanes as the rows are otherwise, so lanes <= batch / n.  The ids equal the default mode's exactly when
+        both put every row at the same index of the same lane (the draw is keyed by the lane's seed and the row's index in it): when
+        the default's cut falls between two prompts."""
+        unit = int(prompt_rings) or 1
+        assert batch % unit == 0 and 1 <= lanes <= batch // unit
+        self.B, self.Tmax, self.n, self.kv_dtype, self.prompt_n = batch, max_total_len, lanes, kv_dtype, int(prompt_rings)
+        units = batch // unit
+        self.sizes = [(units // lanes + (1 if i < units % lanes else 0)) * unit for i in range(lanes)]
         self.offs = [sum(self.sizes[:i]) for i in range(lanes + 1)]
+        more = dict(prompt_rings=prompt_rings, tail_len=tail_len) if prompt_rings else {}
         # (the sampler draws per (seed, row, step): a different seed per lane keeps the lanes' draws independent)
-        self.lanes = [XLDecoder(engine, b, max_total_len, seed=seed + 7919 * i, kv_dtype=kv_dtype) for i, b in enumerate(self.sizes)]
+        self.lanes = [XLDecoder(engine, b, max_total_len, seed=seed + 7919 * i, kv_dtype=kv_dtype, **more)
+                      for i, b in enumerate(self.sizes)]
         self.streams = [torch.cuda.Stream() for _ in range(lanes)]
 
     def invalidate_tables(self):

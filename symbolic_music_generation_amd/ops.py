@@ -1363,6 +1363,73 @@ def kv_commit_shared(rings, stash, K, t_dev, sel, table=None):
           'mxl_kv_commit_shared')
 
 
+def _req_tail_rings(kt, vt, B, H, dh, what):
+    """tail rings: contiguous (B, H, Mt, dh) bf16 pairs"""
+    _req(kt, torch.bfloat16, what); _req(vt, torch.bfloat16, what)
+    if kt.dim() != 4 or vt.shape != kt.shape or (kt.shape[0], kt.shape[1], kt.shape[3]) != (B, H, dh) or not kt.is_contiguous() \
+            or not vt.is_contiguous():
+        raise MusicXLError(f'{what}: the tail rings must be contiguous ({B}, {H}, Mt, {dh}) bf16, one row per sequence')
+
+
+def kv_append_tail(qkv, kt, vt, t_dev, t0_dev, rrb=None, qr_out=None):
+    """see mxl_kv_append_tail: kt / vt head-major tail rings (B, H, Mt, dh); the k / v of the (B, 3d) qkv rows -> tail slot
+    (t - t0) mod Mt, t and t0 (the prompt length) read on the device; with `rrb` (H*dh f32) and `qr_out` (B, H*dh) bf16 the same launch
+    writes q + r_r_bias as kv_append does"""
+    _req(qkv, torch.bfloat16, 'kv_append_tail qkv'); _req(t0_dev, torch.int32, 'kv_append_tail t0_dev')
+    if kt.dim() != 4:
+        raise MusicXLError('kv_append_tail: the tail rings must be (B, H, Mt, dh)')
+    B, H, Mt, dh = kt.shape
+    _req_tail_rings(kt, vt, B, H, dh, 'kv_append_tail')
+    if tuple(qkv.shape) != (B, 3 * H * dh) or not qkv.is_contiguous():
+        raise MusicXLError(f'kv_append_tail: expected contiguous ({B}, {3 * H * dh}) qkv rows')
+    check(lib().mxl_kv_append_tail(_p(qkv), _p(kt), _p(vt), _p(t_dev), _p(t0_dev), B, Mt, H * dh, dh, _p(rrb), _p(qr_out), _stream()),
+          'mxl_kv_append_tail')
+
+
+def relattn_decode_prefix_lds_bytes(n: int, dh: int, M: int, pieces: int = 1) -> int:
+    """shared memory of one mxl_relattn_decode_prefix workgroup (0: arguments outside its domain); the launch takes up to
+    SHARED_LDS_MAX bytes"""
+    return int(lib().mxl_relattn_decode_prefix_lds_bytes(int(n), int(dh), int(M), int(pieces)))
+
+
+def prefix_attn_groups(n: int) -> int:
+    """workgroups per (prompt, head, ring piece) of mxl_relattn_decode_prefix: groups of 8 rows, one group of 4 for n <= 4"""
+    return 1 if n <= 4 else (n + 7) // 8
+
+
+def relattn_decode_prefix(qkv, kp, vp, kt, vt, rd, rwb, rrb, out, t_dev, t0_dev, n, H, dh, qr_buf, bd_buf, scale=None, qr_ready=False,
+                          split=None, pieces=1, unfinished=None):
+    """relattn_decode for the n rows of every prompt over the prompt's rings kp / vp (B0, H, M, dh) and every row's own tail rings
+    kt / vt (B0 * n, H, Mt, dh) (mxl_relattn_decode_prefix): a slot whose position is t0 or later comes from the row's tail.
+    Everything per row -- qkv, qr_buf, bd_buf, out, unfinished and the split scratch -- is sized for B0 * n rows.  The BD launch is
+    relattn_decode's."""
+    B0, _, M, _ = kp.shape
+    B, d = B0 * n, H * dh
+    scale = scale if scale is not None else 1.0 / math.sqrt(dh)
+    if tuple(qkv.shape) != (B, 3 * d) or tuple(out.shape) != (B, d) or not qkv.is_contiguous() or not out.is_contiguous():
+        raise MusicXLError(f'relattn_decode_prefix: expected contiguous ({B}, {3 * d}) qkv and ({B}, {d}) out for {B0} prompts x {n} rows')
+    if tuple(kp.shape) != (B0, H, M, dh) or not kp.is_contiguous() or not vp.is_contiguous() or vp.shape != kp.shape \
+            or bd_buf.numel() < B * H * M:
+        raise MusicXLError('relattn_decode_prefix: the prompt rings must be contiguous (B0, H, M, dh) and bd_buf hold (B0 * n, H, M) f32')
+    _req_tail_rings(kt, vt, B, H, dh, 'relattn_decode_prefix')
+    _req(t0_dev, torch.int32, 'relattn_decode_prefix t0_dev')
+    if not qr_ready:
+        add_rowbias(qkv, 3 * d, 3 * d, rrb.reshape(-1), qr_buf, B, 1, d)
+    if dh == 64 and B <= 64:
+        check(lib().mxl_decode_bd(_p(qr_buf), _p(rd), _p(bd_buf), B, H, dh, M, d, rd.stride(0), _stream()), 'mxl_decode_bd')
+    else:
+        gemm_batched(qr_buf, rd, bd_buf, B, M, dh, lda=d, ldb=d, ldc=H * M, flags=GEMM_OUT_F32, batch=H, bdiv=1,
+                     sA=(dh, 0), sB=(dh, 0), sC=(M, 0))
+    if unfinished is not None:
+        _req(unfinished, torch.int32, 'relattn_decode_prefix unfinished')
+        if unfinished.numel() != B:
+            raise MusicXLError(f'relattn_decode_prefix: unfinished must hold one word per row, {B}')
+    np_ = pieces if (split is not None and pieces > 1) else 1
+    check(lib().mxl_relattn_decode_prefix(_p(qkv), _p(kp), _p(vp), _p(kt), _p(vt), _p(bd_buf), _p(rwb), _p(out), _p(t_dev), _p(t0_dev),
+                                          B0, int(n), H, dh, M, kt.shape[2], float(scale), np_, _p(split[0]) if np_ > 1 else 0,
+                                          _p(split[1]) if np_ > 1 else 0, _p(unfinished), _stream()), 'mxl_relattn_decode_prefix')
+
+
 # ------------------------------------------------------------------ reformer
 def axial_embed_fwd(ids, E, W0, W1, out, A0, A1, drop_p=0.0, seed=0, site_emb=0, site_pos=1):
     B, T = ids.shape

@@ -197,7 +197,7 @@ class MyReformerModelWithLMHead(EngineModule):
                                resolve_max_length, rules_config, rules_refusal, sample_unfused, sampling_config, stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
-        for opt in ('kv_cache_dtype', 'beam_rings', 'contrastive_rings'):           # (before any strategy is chosen: the searches here read no **unsupported)
+        for opt in ('kv_cache_dtype', 'beam_rings', 'contrastive_rings', 'prompt_rings'):         # (before any strategy is chosen: the searches here read no **unsupported)
             if unsupported.get(opt) is not None:
                 raise NotImplementedError(f"generation options not covered: ['{opt}']")
         stop = stop_config(eos_token_id, pad_token_id, min_length, getattr(self.config, 'pad_token_id', None))

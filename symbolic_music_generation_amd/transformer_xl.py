@@ -201,7 +201,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, melody=None,
                  device_scorer: bool = False, register=None, melody_range=None, bass_range=None, bass_below=None,
                  kv_cache_dtype: Optional[str] = None, beam_rings: Optional[str] = None,
-                 contrastive_rings: Optional[str] = None, **unused) -> torch.Tensor:
+                 contrastive_rings: Optional[str] = None, prompt_rings: Optional[str] = None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -356,11 +356,29 @@ class MyTransfoXLLMHeadModel(EngineModule):
         explicit 'shared' is a ValueError under greedy decoding, sampling and every beam arm, under the host-driven loop
         (`top_k > 32`, `MXL_CONTRASTIVE_HOST=1`) and with `kv_cache_dtype='fp8'`; any other string is a ValueError.
         `MXL_CONTRASTIVE_RINGS=shared` sets the default of calls that do not pass the keyword and is ignored where 'shared' does not
-        apply."""
+        apply.
+
+        `prompt_rings` (sampling with `num_return_sequences` = n >= 2): how the K/V rings of the n rows of a prompt are held.  None or
+        'copied': the batch is expanded and every row owns a full set of rings, filled by a prompt pass over all rows, as ever.
+        'shared' (opt-in): the rows of a prompt differ only in the positions generated after it, so a prompt keeps one set of prompt
+        rings, (prompts, H, mem_len, dh) per layer, written once by a prompt pass of the unexpanded batch, and every row a tail ring,
+        (rows, H, Mt, dh) with Mt = min(mem_len, max_length - prompt length rounded up to 16), for what it generates; the attention of
+        a step takes each ring slot from the one or the other by its position (mxl_kv_append_tail / mxl_relattn_decode_prefix;
+        DESIGN.md, prompt rings).  The attention output is the copied mode's bit for bit at the same number of ring pieces and the draw
+        is keyed by seed, row and step, so the ids are the ones 'copied' returns for the same seed, with every rule sampling takes
+        (`grammar`, `n_bars`, `in_key` / `key`, `register`, `melody`), eos / `min_length` / `max_new_tokens`, left-padded prompts,
+        `use_graph` on and off, the large-vocabulary sampler and the adaptive head -- below 32 rows, and from 32 rows on when the
+        default's half-batch lane cut falls between two prompts (the lanes here are cut between prompts; otherwise the lane seeds
+        differ and the output is another valid sample); and for `mem_len` >= 1024 wherever `generate.XLDecoder.pieces` agrees
+        (MXL_DECODE_PIECES pins it).  `d_head` must be 16, 32 or 64, `mem_len` a multiple of 16 whose scores fit 160 KiB of shared
+        memory (any `mem_len` up to 4096 does), else MusicXLError.  An explicit 'shared' is a ValueError with `num_return_sequences`
+        == 1, under greedy decoding, every beam arm and contrastive search, and with `kv_cache_dtype='fp8'`; any other string is a
+        ValueError.  `MXL_PROMPT_RINGS=shared` sets the default of calls that do not pass the keyword and is ignored where 'shared'
+        does not apply."""
         from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, beam_generate, beam_sample_device,
                                beam_search_device, check_grammar_args, contrastive_search, contrastive_search_device,
-                               group_beam_search_device, left_pad_counts, plan_search, resolve_beam_rings, resolve_contrastive_rings,
-                               resolve_kv_dtype,
+                               group_beam_search_device, left_pad_counts, plan_search, prompt_rings_misfit, prompt_tail_len,
+                               resolve_beam_rings, resolve_contrastive_rings, resolve_kv_dtype, resolve_prompt_rings,
                                resolve_max_length,
                                rules_config, sampling_config, stop_config)
         kv_dtype = resolve_kv_dtype(kv_cache_dtype)
@@ -389,6 +407,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
                            vocab_size=self.config.vocab_size, register=register)
         # (before the fp8 refusal: an explicit 'shared' beside kv_cache_dtype='fp8' is refused for what it asks, wherever it is asked)
         shared = resolve_contrastive_rings(contrastive_rings, plan.strategy == 'contrastive' and plan.device and kv_dtype is None) == 'shared'
+        per_prompt = resolve_prompt_rings(prompt_rings, plan.strategy == 'sample' and bool(do_sample) and num_return_sequences >= 2
+                                          and kv_dtype is None) == 'shared'
         if kv_dtype is not None and plan.strategy != 'sample':
             name = dict(beam='beam', beam_sample='beam-sample', group_beam='group-beam', contrastive='contrastive')[plan.strategy]
             raise ValueError(f"kv_cache_dtype='{kv_dtype}' is not supported under {name} search: it moves rings with "
@@ -443,10 +463,21 @@ class MyTransfoXLLMHeadModel(EngineModule):
         dec = getattr(self, '_decoder', None)
         # two free-running half-batch lanes from 32 rows on (generate.XLDecoderLanes); MXL_DECODE_LANES=1 keeps one decoder
         lanes = max(1, int(os.environ.get('MXL_DECODE_LANES', '2'))) if (B >= 32 and use_graph) else 1
+        # prompt rings (opt-in) are another decoder: one set of prompt rings per prompt, a tail ring per row, lanes cut between prompts
+        rings = {}
+        if per_prompt:
+            cut = min(lanes, B0)
+            misfit = prompt_rings_misfit(self.config, num_return_sequences, -(-B0 // cut) * num_return_sequences)
+            if misfit and prompt_rings is not None:
+                raise MusicXLError(misfit)
+            if not misfit:                                  # (the environment's default is ignored where the model does not fit)
+                lanes, rings = cut, dict(prompt_rings=num_return_sequences, tail_len=max_length - input_ids.shape[1])
+        tail = prompt_tail_len(self.config.mem_len, max_length - input_ids.shape[1]) if rings else None
         if (dec is None or dec.B != B or dec.Tmax < max_length or getattr(dec, 'n', 1) != lanes
-                or getattr(dec, 'kv_dtype', None) != kv_dtype):
-            dec = self._decoder = (XLDecoderLanes(self.engine, B, max_length, seed=seed, lanes=lanes, kv_dtype=kv_dtype) if lanes > 1
-                                   else XLDecoder(self.engine, B, max_length, seed=seed, kv_dtype=kv_dtype))
+                or getattr(dec, 'kv_dtype', None) != kv_dtype or getattr(dec, 'prompt_n', 0) != rings.get('prompt_rings', 0)
+                or getattr(getattr(dec, 'lanes', [dec])[0], 'Mt', None) != tail):
+            dec = self._decoder = (XLDecoderLanes(self.engine, B, max_length, seed=seed, lanes=lanes, kv_dtype=kv_dtype, **rings)
+                                   if lanes > 1 else XLDecoder(self.engine, B, max_length, seed=seed, kv_dtype=kv_dtype, **rings))
         dec.invalidate_tables()
         return dec.run(input_ids.to(self.device), max_length,
                        sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), rules, use_graph,
