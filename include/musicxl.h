@@ -478,12 +478,15 @@ int mxl_sample_large(const float* logprobs, int ldl, int V, void* ids, int ld_id
 /* t_dev += 1; rng_ctr += 1 */
 int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
 /* ------------------------------------------------------------------------------------------------------------
- * Rules of a generation.  Seven optional groups of per-row state on the device, applied around every sampled token; three entries take
+ * Rules of a generation.  Eight optional groups of per-row state on the device, applied around every sampled token; three entries take
  * the first four as the same flat argument list (below): mxl_sample_step, mxl_rules_mask, mxl_rules_advance, their mxl_keyed_*
- * forms take the fifth after it, their mxl_guided_* forms the sixth after that and their mxl_ranged_* forms the seventh after that.
+ * forms take the fifth after it, their mxl_guided_* forms the sixth after that, their mxl_ranged_* forms the seventh after that and
+ * their mxl_formed_* forms the eighth after that.
  * A group is off when its state pointer is NULL: unfinished (with alive), gstate (with allow, next), gbar (with grem, slots, bars),
- * gleft, gkey (with keys, pcs, inkey), gpos (with gforce, guide, glen), gpart (with gfloor, grange, reg).  Within a group either every pointer is given or none; the budget, the count and the guide need `cls`;
- * anything else is MXL_EINVAL.
+ * gleft, gkey (with keys, pcs, inkey), gpos (with gforce, guide, glen), gpart (with gfloor, grange, reg), gcopy (with gbars, gstop,
+ * plan, nplan, barcol).  Within a group either every pointer is given or none; the budget, the count, the guide and the repeat need
+ * `cls`; the repeat also needs the count and, where the words move, the stop group, and is never on beside the guide; anything else
+ * is MXL_EINVAL.
  *
  * stop: eos_id, pad_id, min_length, unfinished, alive -- stopping at eos (HF greedy_search / sample with an eos_token_id).
  *   unfinished (B,) int32 (1 = live; set to 1 before the first sampled token) and alive, one int32 = the number of live rows after
@@ -556,6 +559,36 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  *   the rare-pitch token are such tokens and belong to the grammar's class `pitch`, and the budget judges a pitch by that class alone,
  *   so wherever the grammar or the budget allows "a pitch" one of the two remains even when the bounds leave no pitched token (the
  *   floor under lo_bass, say).  The key rule never bars them either.
+ * repeat: plan, ld_plan, nplan, barcol, renter, rleave, span, gbars, gcopy, gstop (the mxl_formed_* entries) -- song form: a planned
+ *   bar repeats an earlier bar the row generated itself, token for token, out of the row's own id history.  A row's generated bars
+ *   are the bars it opens after its prompt, numbered 0, 1, ... in the order of their `enter` tokens; the bar open at the end of the
+ *   prompt is finished freely and has no number, as the count group counts.  Tables: plan (B, ld_plan) int32, plan[b][k] = -1:
+ *   generated bar k is free, j with 0 <= j < k: bar k repeats generated bar j; nplan (B,) int32, the planned bars of the row (<=
+ *   ld_plan), 0 = the row is untouched; barcol (B, ld_plan) int32, WRITTEN by the group: the column of ids that holds the `enter` token
+ *   of generated bar k; renter and rleave, class bit masks over the classes of `cls` (the music grammar: <bar> and <bass>); span, one
+ *   scalar for the launch: 0 = a repeat copies the whole source bar, melody and bass, 1 = it copies up to and including the first
+ *   `leave` token, so the row gets the same melody and writes a new bass under it.  Per row three int32 words: gbars, the bars opened
+ *   so far (starts at 0); gcopy, the column of the row's own history the next token is copied from, -1 = the row chooses (starts at
+ *   -1); gstop, the column where the copy ends, exclusive.  The history is ids (B, ld_ids) itself in the fused and the advance entry;
+ *   the mask entry, which sees no ids, takes it as hist / ld_hist.
+ *   In a row with nplan > 0 and gcopy >= 0 every token except ids[b][gcopy] is barred and that token is never barred: the group
+ *   overrides the grammar, the budget, the count, the key, the register and min_length exactly as the guide's forced token does, in
+ *   the same place (-inf where the row enters LDS, before the warpers), so greedy and sampled rows both keep it, and the RNG counter
+ *   advances as always.  A kept token of class c, written at column col, moves the row: with gcopy >= 0, gcopy += 1, and gcopy = -1
+ *   once gcopy >= gstop, or under span == 1 when c is in rleave; else, if c is in renter and gbars < nplan: k = gbars, barcol[b][k] =
+ *   col, gbars = k + 1, and with j = plan[b][k] >= 0, from = barcol[b][j] + 1 and stop = (j + 1 == k) ? col : barcol[b][j + 1], a
+ *   copy starts (gcopy = from, gstop = stop) if from < stop.  Nothing else moves the words; the words of every other group move along
+ *   a copied token as along a chosen one (a copied melody note lowers the register's floor).  The group does not stop a row: the
+ *   caller sets gleft = nplan, so the row opens exactly the planned bars and, under a bar budget, ends when the last one is full.
+ *   No dead end: a source bar is complete when its copy starts -- bar j + 1 has been opened, at the latest by the very `enter` token
+ *   that starts the copy -- so the copied span is a whole bar (span 0) or a whole melody channel with its <bass> (span 1) that the
+ *   grammar and the budget admitted once.  The source started from the automaton state BAR, which is where every `enter` token
+ *   leads, and so does its copy.  Time signature and key tokens occur in the header only (MUSIC_TRANSITIONS), so the bar length and,
+ *   for what the row chooses after a span-1 copy, the key are the source's: the copy fills its channels exactly as the source did,
+ *   and under span 1 it fills the melody channel, after which the row is in B_OPEN with a full budget, where any bass the budget
+ *   admits closes the bar.  A source that is itself a copy is fine: the history holds real tokens.  Sources are generated bars only
+ *   (j < k, columns the row wrote itself after its prompt), so a copy never reads a pad or a column not yet written: gcopy < gstop
+ *   <= col.
  *
  * The words move along the token a row keeps, after the stop rule: a row that was finished before the step emits pad and keeps its
  * words; the step in which a row emits eos still moves them.  Each row's words are read and written for that row alone.
@@ -566,7 +599,8 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  * writes *alive (counter: one int, zero before the first call, left zero).  `scores` (B, ldl) may be log-probabilities or, when
  * repetition_penalty == 1, the head's raw logits: argmax, top-k / top-p / typical-p and the renormalised draw do not change under the
  * per-row shift that separates the two.  The masks are applied where the row enters LDS.  V <= 2048; with the stop group B <= 32767;
- * the budget, the count and the guide need the grammar group here.  Without the stop group eos_id / pad_id / min_length are ignored. */
+ * the budget, the count, the guide and the repeat need the grammar group here.  Without the stop group eos_id / pad_id / min_length
+ * are ignored. */
 int mxl_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
                     unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                     float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
@@ -654,6 +688,37 @@ int mxl_ranged_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int
                              int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
                              int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
                              int* gforce, const void* reg, const void* grange, int* gpart, int* gfloor, int gap, void* stream);
+/* The ranged entries with the repeat group after the register group; with plan = nplan = barcol = gbars = gcopy = gstop = NULL they
+ * are those entries (renter, rleave, span, hist are then ignored).  In the fused launch the repeat group is one more variant on top
+ * of the grammar and the count; it feeds its token through the guide's arm of the sampler.  barcol and the state words are written by
+ * the row's thread 0 (fused) or the row's thread (advance). */
+int mxl_formed_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                           unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                           float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                           int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
+                           const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
+                           unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
+                           int* gleft, const void* keys, const void* pcs, const void* inkey, int* gkey, const void* guide,
+                           int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos, int* gforce, const void* reg,
+                           const void* grange, int* gpart, int* gfloor, int gap, const void* plan, int ld_plan, const void* nplan,
+                           int* barcol, unsigned renter, unsigned rleave, int span, int* gbars, int* gcopy, int* gstop,
+                           float* out_probs, void* stream);
+int mxl_formed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length,
+                          int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
+                          const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
+                          int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
+                          int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
+                          int* gforce, const void* reg, const void* grange, int* gpart, int* gfloor, int gap, const void* plan,
+                          int ld_plan, const void* nplan, int* barcol, unsigned renter, unsigned rleave, int span, int* gbars,
+                          int* gcopy, int* gstop, const void* hist, int ld_hist, void* stream);
+int mxl_formed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length,
+                             int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
+                             const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
+                             int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
+                             int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
+                             int* gforce, const void* reg, const void* grange, int* gpart, int* gfloor, int gap, const void* plan,
+                             int ld_plan, const void* nplan, int* barcol, unsigned renter, unsigned rleave, int span, int* gbars,
+                             int* gcopy, int* gstop, void* stream);
 /* (gpart, gfloor) of every row after columns 0..Tp-1 of ids (B, ld_ids) int64, walked from the words gpart[b] / gfloor[b] hold at the
  * launch under the bounds grange[b] and `gap` (the register group above).  Ids < 0 (left pads) and ids >= V are skipped.  Columns
  * before `from` only move the words -- the prompt's pitches are not judged; first_bad[b] = the first column >= from that holds a pitch

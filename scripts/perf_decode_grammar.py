@@ -28,6 +28,14 @@ finds clean are printed for each arm.
 
     python3 scripts/perf_decode_grammar.py --register
     python3 scripts/perf_decode_grammar.py --register --only register     # or plain
+
+`--form K`: what `generate(form=)` costs on top of the bar count, at the same shape, under `tokenizer.grammar(bar_budget=True)` over
+prompts whose bars are full: `bars` (the eos rule and n_bars = K for every row, the third arm of --n-bars) against `form` (a plan of K
+bars for every row in which every second bar repeats the bar before it, so that half of the bars a row writes are copies), alternating
+as above; give a K no row reaches inside the window, e.g. 1000.  The rows that `check_form` finds clean are printed for each arm.
+
+    python3 scripts/perf_decode_grammar.py --form 1000
+    python3 scripts/perf_decode_grammar.py --form 1000 --only form        # or bars: for rocprofv3 --kernel-trace --stats
 """
 import os
 import statistics
@@ -46,6 +54,8 @@ ONLY = sys.argv[sys.argv.index('--only') + 1] if '--only' in sys.argv else None
 N_BARS = int(sys.argv[sys.argv.index('--n-bars') + 1]) if '--n-bars' in sys.argv else None
 IN_KEY = '--in-key' in sys.argv
 REGISTER = '--register' in sys.argv
+FORM = int(sys.argv[sys.argv.index('--form') + 1]) if '--form' in sys.argv else None
+FULL_BARS = N_BARS is not None or FORM is not None
 
 vocab = MusicVocabulary(pitch_kind='degree')
 assert len(vocab) == V
@@ -66,9 +76,9 @@ def prompts():
         row = [t('TimeSig_4/4'), t('Tempo_120'), t('Key_CMajor')]
         while len(row) < Tp:
             row += [t('<bar>'), t('<melody>')]
-            for _ in range(4):                                     # (--n-bars: full bars, four quarter notes over one whole note)
-                row += [pick(pitch), pick(dur) if N_BARS is None else t('d_1')]
-            row += [t('<bass>'), pick(pitch), pick(dur) if N_BARS is None else t('d_4')]
+            for _ in range(4):                                     # (--n-bars, --form: full bars, four quarter notes over one whole note)
+                row += [pick(pitch), pick(dur) if not FULL_BARS else t('d_1')]
+            row += [t('<bass>'), pick(pitch), pick(dur) if not FULL_BARS else t('d_4')]
         rows.append(row[:Tp])
     return torch.tensor(rows, dtype=torch.int64, device=dev)
 
@@ -190,8 +200,46 @@ def register_arms():
     print(f'  register - plain = {d:+.4f} ms/step ({100 * d / med["plain"]:+.2f} %); run-to-run spread {max(spread.values()):.4f} ms')
 
 
+def form_arms():
+    """the --form comparison (module docstring)"""
+    from symbolic_music_generation_amd.generate import bars_after_prompt, check_bar_lengths, check_form, form_config, stop_config
+    g = vocab.grammar(bar_budget=True)
+    stop = stop_config(vocab.t2i('</s>'), vocab.t2i('[PAD]'))
+    plan = [-1 if k % 2 == 0 else k - 1 for k in range(FORM)]
+    arms = {'bars': dict(stop=stop, n_bars=FORM), 'form': dict(stop=stop, melody=form_config(plan, None, None, B, g, stop))}
+    assert check_bar_lengths(ids, g).tolist() == [-1] * B
+    if ONLY:
+        dec = XLDecoderLanes(model.engine, B, L, seed=5, lanes=2)
+        print(f'{ONLY}: {window(dec, g, 50, **arms[ONLY]):.3f} ms per step (50 steps)', flush=True)
+        return
+    decs = {k: XLDecoderLanes(model.engine, B, L, seed=5, lanes=2) for k in arms}
+    for name, dec in decs.items():                                  # warm-up: library attributes, workspaces, graph capture
+        window(dec, g, 20, **arms[name])
+    ms = {k: [] for k in arms}
+    for r in range(ROUNDS):
+        for name in (('bars', 'form') if r % 2 == 0 else ('form', 'bars')):
+            ms[name].append(window(decs[name], g, STEPS, **arms[name]))
+        print(f'round {r}: bars {ms["bars"][-1]:.4f} ms/step, form {ms["form"][-1]:.4f} ms/step', flush=True)
+    for k in arms:
+        out = torch.cat([d.ids[:, :Tp + 20 + STEPS] for d in decs[k].lanes], 0)
+        print(f'{k:5s}: rows whose bars are all full {int((check_bar_lengths(out, g) < 0).sum())} of {B}, rows clean under check_form '
+              f'{int((check_form(out, g, plan, prompt_len=Tp) < 0).sum())} of {B}, live rows {sum(int(d.alive) for d in decs[k].lanes)}, '
+              f'bars opened per row {bars_after_prompt(out, g, prompt_len=Tp).float().mean():.1f}')
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    spread = {k: max(v) - min(v) for k, v in ms.items()}
+    print(f'C5 decode step, {B} rows, 2 lanes, {STEPS} replayed steps x {ROUNDS} alternating rounds, a plan of {FORM} bars')
+    for k in arms:
+        print(f'  {k:5s} median {med[k]:.4f} ms/step = {1e3 * B / med[k]:.0f} tok/s  min {min(ms[k]):.4f}  max {max(ms[k]):.4f}  '
+              f'spread {spread[k]:.4f}')
+    d = med['form'] - med['bars']
+    print(f'  form - bars = {d:+.4f} ms/step ({100 * d / med["bars"]:+.2f} %); run-to-run spread {max(spread.values()):.4f} ms')
+
+
 with torch.no_grad():
     assert check_grammar(ids, grammar).tolist() == [-1] * B
+    if FORM is not None:
+        form_arms()
+        sys.exit(0)
     if REGISTER:
         register_arms()
         sys.exit(0)

@@ -610,9 +610,10 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The rules of one generation (include/musicxl.h, "Rules of a generation"), passed to kernels by value.  Seven groups, each off when
-// its state pointer (unfinished / gstate / gbar / gleft / gkey / gpos / gpart) is NULL; the budget, the count and the guide read the
-// token classes `cls` of the grammar group and nothing else of it, the key and the register read nothing of it at all.
+// The rules of one generation (include/musicxl.h, "Rules of a generation"), passed to kernels by value.  Eight groups, each off when
+// its state pointer (unfinished / gstate / gbar / gleft / gkey / gpos / gpart / gcopy) is NULL; the budget, the count, the guide and
+// the repeat read the token classes `cls` of the grammar group and nothing else of it, the key and the register read nothing of it at
+// all.
 //   stop     HF greedy_search / sample: a finished row emits pad, a live row that emits eos is finished; eos barred below min_length
 //   grammar  a token class automaton: cls (V,) token -> class, allow (S,) bit c = class c may follow in state s, next (S, C) successor
 //   budget   grammar.BarBudget: per row `bar` (bar length in slots, 0 = unconstrained) and `rem` (slots still free in the open
@@ -640,6 +641,15 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 //            REG_MELODY / REG_BASS / REG_BAR, 0xFF = anything else (rests and the rare pitch included).  A pitch outside the open
 //            part's bounds is barred; in the bass, with gap >= 0 and a floor, the upper bound is min(hi_bass, floor - gap).  A kept part
 //            token sets part, <bar> clears part and floor, a melody pitch lowers floor
+//   repeat   grammar.BarRepeat: per row `bars` (generated bars opened so far), `copy` (the column of the row's own history the next
+//            token is copied from, -1 = the row chooses) and `stop` (the column where the copy ends, exclusive).  plan (B, ld_plan)
+//            int32: plan[b][k] = -1, bar k is free, or j < k, bar k repeats generated bar j; nplan (B,) int32: planned bars, 0 = the
+//            row is untouched; barcol (B, ld_plan) int32, written here: the column of the `enter` token of generated bar k; renter /
+//            rleave: class bit masks (<bar> / <bass>); span: 0 = the whole bar is copied, 1 = up to its first `leave` token; hist
+//            (B, ld_hist) int64: the rows' ids.  A row with copy >= 0 may emit hist[b][copy] alone, as under the guide; a kept token
+//            under copy takes copy one on and ends the copy at `stop` or, under span 1, at a `leave` token; a kept `enter` token of a
+//            free row with bars < nplan records its column and, if the plan names a source, starts the copy behind the source's
+//            `enter` token
 // The next rule is one more group here, one line in each of rules_load / rules_move and one in make_rules.
 // ---------------------------------------------------------------------------------------------------------------
 struct DecodeRules {
@@ -673,6 +683,17 @@ struct DecodeRules {
     int* gpart;
     int* gfloor;
     int gap;
+    const int* plan;
+    int ld_plan;
+    const int* nplan;
+    int* barcol;
+    uint32_t renter, rleave;
+    int span;
+    int* gbars;
+    int* gcopy;
+    int* gstop;
+    const long long* hist;
+    int ld_hist;
 };
 
 constexpr int BUDGET_NONE = 0xFFFF;          // slots: unknown length (beyond any rem); bars: not a time signature
@@ -727,9 +748,10 @@ __device__ __forceinline__ void register_move(int& part, int& floor, int p) {
 }
 
 // The words of row b and what they admit: `allow` has a bit per class the row may emit (every bit without a grammar), `remcap` is
-// the largest slots entry, `inkey` a bit per pitch class (key_word), `forced` the guide token the row is fed at this step (-1 = none:
-// the row chooses), `rw` the bounds of the open part (register_word).  g / bud / cnt / ink / gd / rg: which groups are on --
-// compile-time constants in the fused kernel, pointer tests in the unfused pair; everything here inlines and folds on them.
+// the largest slots entry, `inkey` a bit per pitch class (key_word), `forced` the token the row is fed at this step, from its guide or
+// (rp) from its own history (-1 = none: the row chooses), `rw` the bounds of the open part (register_word).  g / bud / cnt / ink / gd /
+// rg / rp: which groups are on -- compile-time constants in the fused kernel, pointer tests in the unfused pair; everything here
+// inlines and folds on them.
 struct RowWords {
     int gs, bar, rem, left;
     uint32_t allow;
@@ -738,10 +760,11 @@ struct RowWords {
     int pos, force, forced;
     int part, floor;
     RegWord rw;
+    int nplan, nbars, copy, cstop;
 };
 __device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool g, bool bud, bool cnt, bool ink, bool gd = false,
-                                               bool rg = false) {
-    RowWords w{0, 0, 0, -1, ~0u, BUDGET_NONE, KEY_ANY, 0, 0, -1, 0, FLOOR_NONE, RegWord{nullptr, 0u, 127u}};
+                                               bool rg = false, bool rp = false) {
+    RowWords w{0, 0, 0, -1, ~0u, BUDGET_NONE, KEY_ANY, 0, 0, -1, 0, FLOOR_NONE, RegWord{nullptr, 0u, 127u}, 0, 0, -1, 0};
     if (g) { w.gs = r.gstate[b]; w.allow = r.allow[w.gs]; }
     if (bud) {
         w.bar = r.gbar[b];
@@ -761,13 +784,24 @@ __device__ __forceinline__ RowWords rules_load(const DecodeRules& r, int b, bool
         w.floor = r.gfloor[b];
         w.rw = register_word(r.reg, (uint32_t)r.grange[b], w.part, w.floor, r.gap);
     }
+    if (rp) {                                        // the copy reads a column the row wrote in an earlier launch: copy < stop <= t + 1
+        w.nplan = min(r.nplan[b], r.ld_plan);
+        w.nbars = r.gbars[b];
+        w.copy = r.gcopy[b];
+        w.cstop = r.gstop[b];
+        if (w.nplan > 0 && w.copy >= 0 && w.copy < r.ld_hist) {
+            const long long tk = r.hist[(size_t)b * r.ld_hist + w.copy];
+            w.forced = (tk >= 0 && tk <= 0x7fffffffLL) ? (int)tk : -1;
+        }
+    }
     return w;
 }
 // row b moves along `tok`, a token of the vocabulary that the row chose itself (a row finished before the step emits pad, which is
 // not its choice and need not be a token its state allows: such a row keeps its words)
+// `col` (rp): the column of the row's history that `tok` is written at
 __device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int b, long long tok, bool g, bool bud, bool cnt, bool ink,
-                                           bool gd = false, bool rg = false) {
-    const int c = (g || bud || cnt || gd) ? r.cls[tok] : 0;
+                                           bool gd = false, bool rg = false, int col = 0, bool rp = false) {
+    const int c = (g || bud || cnt || gd || rp) ? r.cls[tok] : 0;
     if (g) r.gstate[b] = r.next[w.gs * r.C + c];
     if (bud) {
         budget_move(w.bar, w.rem, c, r.slots[tok], r.bars[tok], r.opens);
@@ -793,6 +827,22 @@ __device__ __forceinline__ void rules_move(const DecodeRules& r, RowWords w, int
         r.gpart[b] = w.part;
         r.gfloor[b] = w.floor;
     }
+    if (rp) {                                        // BarRepeat.move
+        if (w.copy >= 0) {
+            const int nc = w.copy + 1;
+            r.gcopy[b] = (nc >= w.cstop || (r.span == 1 && ((r.rleave >> c) & 1u))) ? -1 : nc;
+        } else if (((r.renter >> c) & 1u) && w.nbars >= 0 && w.nbars < w.nplan) {
+            const int k = w.nbars;
+            int* cols = r.barcol + (size_t)b * r.ld_plan;
+            cols[k] = col;
+            r.gbars[b] = k + 1;
+            const int j = r.plan[(size_t)b * r.ld_plan + k];
+            if (j >= 0 && j < k) {
+                const int from = cols[j] + 1, stop = (j + 1 == k) ? col : cols[j + 1];
+                if (from >= 1 && from < stop && stop <= col) { r.gcopy[b] = from; r.gstop[b] = stop; }
+            }
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl, int V, long long* ids, int ld_ids,
@@ -810,23 +860,25 @@ __global__ __launch_bounds__(256) void sample_kernel(const float* logp, int ldl,
 // head's raw logits instead of log-probabilities when no repetition penalty is in force: every other warper, the argmax and the
 // renormalised draw are invariant under the per-row shift log-softmax applies.
 //
-// G / BUD / CNT / INK / GD / RG: the grammar, budget, count, key, guide and register groups of `r` as compile-time variants (BUD, CNT
-// and GD ride on G, INK and RG stand alone); the stop group is the runtime test of r.unfinished it has always been.  The row's words
+// G / BUD / CNT / INK / GD / RG / RP: the grammar, budget, count, key, guide, register and repeat groups of `r` as compile-time
+// variants (BUD, CNT, GD and RP ride on G, INK and RG stand alone; RP feeds its token through the sampler's GD arm and is never on
+// beside GD); the stop group is the runtime test of r.unfinished it has always been.  The row's words
 // select the allow word, remcap, the key's pitch classes and the open part's bounds the sampler applies (rules_load), and thread 0 moves them along the token the row keeps (rules_move).  The move sits AFTER the eos rule: a row that
 // was finished before this step emits pad and its words stay frozen; the step in which a live row emits eos still moves them, so a
 // finished row of the music grammar rests in END.  The words are per-row: row b's workgroup is their only reader and writer within a
 // launch, and the next launch on the stream sees them by stream order -- there is no hand-off between workgroups here beyond the
 // arrival counter below.
-template <bool G, bool BUD, bool CNT, bool INK, bool GD, bool RG>
+template <bool G, bool BUD, bool CNT, bool INK, bool GD, bool RG, bool RP = false>
 __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, int ldl, int V, long long* ids, int ld_ids,
                                                           int* t_dev, unsigned long long* rng_ctr, unsigned long long seed,
                                                           int do_sample, int top_k, float top_p, float temperature,
                                                           float repetition_penalty, float typical_p, const bf16_t* E, bf16_t* emb_out,
                                                           int d, float scale, int* counter, float* out_probs, DecodeRules r) {
-    static_assert(G || !(BUD || CNT || GD), "the bar budget, the bar count and the guide ride on the grammar");
+    static_assert(G || !(BUD || CNT || GD || RP), "the bar budget, the bar count, the guide and the repeat ride on the grammar");
+    static_assert(!(GD && RP), "a row is fed from its guide or from its own history, not both");
     int* const unfinished = r.unfinished;
-    const RowWords w = rules_load(r, blockIdx.x, G, BUD, CNT, INK, GD, RG);
-    int tok = sample_row<G, BUD, INK, GD, RG>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
+    const RowWords w = rules_load(r, blockIdx.x, G, BUD, CNT, INK, GD, RG, RP);
+    int tok = sample_row<G, BUD, INK, GD || RP, RG>(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature,
                                       repetition_penalty, typical_p, out_probs, unfinished ? r.eos_id : -1,
                                       unfinished ? r.min_length : 0, r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, w.forced, w.rw);
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -847,7 +899,8 @@ __global__ __launch_bounds__(256) void sample_step_kernel(const float* scores, i
         __syncthreads();
         tok = sh_tok;
     }
-    if ((G || INK || RG) && tid == 0 && was_live && tok >= 0 && tok < V) rules_move(r, w, b, tok, G, BUD, CNT, INK, GD, RG);
+    if ((G || INK || RG) && tid == 0 && was_live && tok >= 0 && tok < V)
+        rules_move(r, w, b, tok, G, BUD, CNT, INK, GD, RG, RP ? *t_dev + 1 : 0, RP);
     if (tid == 0) ids[(size_t)b * ld_ids + *t_dev + 1] = tok;
     const int id = (tok < 0 || tok >= V) ? 0 : tok;
     for (int c = tid; c < (d >> 3); c += 256) {
@@ -896,11 +949,12 @@ __global__ __launch_bounds__(256) void rules_mask_kernel(float* scores, int ldl,
     if (i >= (long long)B * V) return;
     const int b = (int)(i / V), v = (int)(i - (long long)b * V);
     const bool bud = r.gbar != nullptr, ink = r.gkey != nullptr, gd = r.gpos != nullptr, rg = r.gpart != nullptr;
+    const bool rp = r.gcopy != nullptr;
     bool ok = true;
     int forced = -1;
     if (r.cls || ink || rg) {
-        const RowWords w = rules_load(r, b, r.gstate != nullptr, bud, r.gleft != nullptr, ink, gd, rg);
-        ok = token_allowed(r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, v, r.cls != nullptr, bud, ink, gd, w.forced, rg, w.rw);
+        const RowWords w = rules_load(r, b, r.gstate != nullptr, bud, r.gleft != nullptr, ink, gd, rg, rp);
+        ok = token_allowed(r.cls, w.allow, r.slots, w.remcap, r.pcs, w.inkey, v, r.cls != nullptr, bud, ink, gd || rp, w.forced, rg, w.rw);
         forced = w.forced;
     }
     if (forced < 0 && r.min_length > 0 && v == r.eos_id && *t_dev + 1 < r.min_length) ok = false;
@@ -915,14 +969,14 @@ __global__ __launch_bounds__(256) void rules_advance_kernel(long long* ids, int 
     const int tid = threadIdx.x;
     const int t = *t_dev;
     const bool g = r.gstate != nullptr, bud = r.gbar != nullptr, cnt = r.gleft != nullptr, ink = r.gkey != nullptr;
-    const bool gd = r.gpos != nullptr, rg = r.gpart != nullptr;
+    const bool gd = r.gpos != nullptr, rg = r.gpart != nullptr, rp = r.gcopy != nullptr;
     int n = 0;
     for (int b = tid; b < B; b += 256) {
         long long* p = ids + (size_t)b * ld_ids + t;
         const long long tok = *p;
         int live = r.unfinished ? r.unfinished[b] : 1;
         if (live && (r.cls || ink || rg) && tok >= 0 && tok < V)
-            rules_move(r, rules_load(r, b, g, bud, cnt, ink, gd, rg), b, tok, g, bud, cnt, ink, gd, rg);
+            rules_move(r, rules_load(r, b, g, bud, cnt, ink, gd, rg, rp), b, tok, g, bud, cnt, ink, gd, rg, t, rp);
         if (r.unfinished) {
             if (!live) *p = r.pad_id;
             else if (tok == r.eos_id) live = 0;
@@ -1193,11 +1247,21 @@ extern "C" int mxl_sample(const float* logprobs, int ldl, int V, void* ids, int 
 #define REG_PARAMS const void *reg, const void *grange, int *gpart, int *gfloor, int gap
 #define REG_ARGS reg, grange, gpart, gfloor, gap
 #define REG_OFF nullptr, nullptr, nullptr, nullptr, -1
+// the repeat group, which follows the register group in the mxl_formed_* entries; the id history it copies from is the `ids` of the
+// fused and the advance entry and an argument of its own (HIST_PARAMS) where the mask entry, which sees no ids, takes it
+#define FORM_PARAMS \
+    const void *plan, int ld_plan, const void *nplan, int *barcol, unsigned renter, unsigned rleave, int span, int *gbars, int *gcopy, int *gstop
+#define FORM_ARGS plan, ld_plan, nplan, barcol, renter, rleave, span, gbars, gcopy, gstop
+#define FORM_OFF nullptr, 0, nullptr, nullptr, 0u, 0u, 0, nullptr, nullptr, nullptr
+#define HIST_PARAMS const void *hist, int ld_hist
 
-// the one check of those arguments, before any launch: within a group all pointers or none; budget, count and guide read `cls`.
-// fused: the launch that also samples -- budget, count and guide ride on the grammar there, and arrivals and live rows share one
-// 32-bit word
-static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS) {
+// the one check of those arguments, before any launch: within a group all pointers or none; budget, count, guide and repeat read
+// `cls`; the repeat needs the count, which ends its rows, its history, and the guide off: a row is fed from one place.
+// fused: the launch that also samples -- budget, count, guide and repeat ride on the grammar there, and arrivals and live rows share
+// one 32-bit word.  moves: the launch moves the words (all but the mask) -- the repeat then needs the stop group, whose finished rows
+// keep their words
+static int make_rules(DecodeRules* r, int B, bool fused, bool moves, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS, FORM_PARAMS,
+                      HIST_PARAMS) {
     MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr));
     MXL_CHECK_ARG((allow == nullptr) == (gstate == nullptr) && (next == nullptr) == (gstate == nullptr));
     MXL_CHECK_ARG(!gstate || (cls && C >= 1 && C <= 32));
@@ -1208,34 +1272,40 @@ static int make_rules(DecodeRules* r, int B, bool fused, RULES_PARAMS, KEY_PARAM
     MXL_CHECK_ARG(!gpos || (cls && ld_guide >= 1));
     MXL_CHECK_ARG((reg == nullptr) == (gpart == nullptr) && (grange == nullptr) == (gpart == nullptr) && (gfloor == nullptr) == (gpart == nullptr));
     MXL_CHECK_ARG(!gpart || (gap >= -1 && gap <= 127));
-    if (fused) MXL_CHECK_ARG(!(gbar || gleft || gpos) || gstate);
+    MXL_CHECK_ARG((plan == nullptr) == (gcopy == nullptr) && (nplan == nullptr) == (gcopy == nullptr) && (barcol == nullptr) == (gcopy == nullptr));
+    MXL_CHECK_ARG((gbars == nullptr) == (gcopy == nullptr) && (gstop == nullptr) == (gcopy == nullptr));
+    MXL_CHECK_ARG(!gcopy || (cls && gleft && !gpos && ld_plan >= 1 && hist && ld_hist >= 1 && (span == 0 || span == 1)));
+    MXL_CHECK_ARG(!gcopy || !moves || unfinished);
+    if (fused) MXL_CHECK_ARG(!(gbar || gleft || gpos || gcopy) || gstate);
     if (fused && unfinished) MXL_CHECK_ARG(B <= 32767);
     if (!unfinished && fused) { eos_id = -1; pad_id = 0; min_length = 0; }
     *r = DecodeRules{eos_id, pad_id, min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
                      (const unsigned char*)next, C, gstate, (const unsigned short*)slots, (const unsigned short*)bars, opens, need_free,
                      need_full, gbar, grem, count, end, gleft, (const unsigned char*)keys, (const unsigned char*)pcs,
                      (const unsigned short*)inkey, gkey, (const int*)guide, ld_guide, (const int*)glen, enter, leave, gpos, gforce,
-                     (const unsigned char*)reg, (const int*)grange, gpart, gfloor, gap};
+                     (const unsigned char*)reg, (const int*)grange, gpart, gfloor, gap, (const int*)plan, ld_plan, (const int*)nplan, barcol,
+                     renter, rleave, span, gbars, gcopy, gstop, (const long long*)hist, ld_hist};
     return MXL_OK;
 }
 
-extern "C" int mxl_ranged_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+extern "C" int mxl_formed_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
                                       unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                                       float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS, float* out_probs, void* stream) {
+                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS, FORM_PARAMS, float* out_probs,
+                                      void* stream) {
     MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
     MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
     MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
     DecodeRules r;
-    if (const int e = make_rules(&r, B, true, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS)) return e;
-#define LAUNCH_R(G, BUD, CNT, INK, GD, RG)                                                                                               \
-    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT, INK, GD, RG>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V,       \
+    if (const int e = make_rules(&r, B, true, true, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_ARGS, ids, ld_ids)) return e;
+#define LAUNCH_R(G, BUD, CNT, INK, GD, RG, RP)                                                                                           \
+    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT, INK, GD, RG, RP>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V,   \
                        (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p, \
                        (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, out_probs, r)
-#define LAUNCH_K(G, BUD, CNT, INK, GD)                    \
-    do {                                                  \
-        if (gpart) LAUNCH_R(G, BUD, CNT, INK, GD, true);  \
-        else LAUNCH_R(G, BUD, CNT, INK, GD, false);       \
+#define LAUNCH_K(G, BUD, CNT, INK, GD)                           \
+    do {                                                         \
+        if (gpart) LAUNCH_R(G, BUD, CNT, INK, GD, true, false);  \
+        else LAUNCH_R(G, BUD, CNT, INK, GD, false, false);       \
     } while (0)
 #define LAUNCH_D(G, BUD, CNT, GD)                   \
     do {                                            \
@@ -1247,17 +1317,37 @@ extern "C" int mxl_ranged_sample_step(const float* scores, int ldl, int V, void*
         if (gpos) LAUNCH_D(true, BUD, CNT, true);   \
         else LAUNCH_D(true, BUD, CNT, false);       \
     } while (0)
-    if (!gstate) LAUNCH_D(false, false, false, false);
+    // the repeat group rides on the grammar and the count and excludes the guide (make_rules): a variant over budget, key and register
+#define LAUNCH_P(BUD)                                                         \
+    do {                                                                      \
+        if (gkey && gpart) LAUNCH_R(true, BUD, true, true, false, true, true);  \
+        else if (gkey) LAUNCH_R(true, BUD, true, true, false, false, true);     \
+        else if (gpart) LAUNCH_R(true, BUD, true, false, false, true, true);    \
+        else LAUNCH_R(true, BUD, true, false, false, false, true);              \
+    } while (0)
+    if (gcopy && gbar) LAUNCH_P(true);
+    else if (gcopy) LAUNCH_P(false);
+    else if (!gstate) LAUNCH_D(false, false, false, false);
     else if (!gbar && !gleft) LAUNCH(false, false);
     else if (!gleft) LAUNCH(true, false);
     else if (!gbar) LAUNCH(false, true);
     else LAUNCH(true, true);
 #undef LAUNCH
+#undef LAUNCH_P
 #undef LAUNCH_D
 #undef LAUNCH_K
 #undef LAUNCH_R
     MXL_LAUNCH_CHECK();
     return MXL_OK;
+}
+
+extern "C" int mxl_ranged_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
+                                      unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
+                                      float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
+                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS, float* out_probs, void* stream) {
+    return mxl_formed_sample_step(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, B, do_sample, top_k, top_p, temperature,
+                                  repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS,
+                                  FORM_OFF, out_probs, stream);
 }
 
 extern "C" int mxl_guided_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
@@ -1286,17 +1376,22 @@ extern "C" int mxl_sample_step(const float* scores, int ldl, int V, void* ids, i
                                  repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_OFF, nullptr, stream);
 }
 
-extern "C" int mxl_ranged_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                     REG_PARAMS, void* stream) {
+extern "C" int mxl_formed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                     REG_PARAMS, FORM_PARAMS, HIST_PARAMS, void* stream) {
     MXL_CHECK_ARG(scores && B > 0 && V > 0 && ldl >= V && (t_dev || min_length <= 0));
     const long long n = (long long)B * V;
     MXL_CHECK_ARG(n <= (1LL << 38));
     DecodeRules r;
-    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS)) return e;
+    if (const int e = make_rules(&r, B, false, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_ARGS, hist, ld_hist)) return e;
     if (!r.cls && !r.gkey && !r.gpart && (r.min_length <= 0 || r.eos_id < 0 || r.eos_id >= V)) return MXL_OK;   // nothing to bar
     hipLaunchKernelGGL(rules_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V, t_dev, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
+}
+
+extern "C" int mxl_ranged_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                     REG_PARAMS, void* stream) {
+    return mxl_formed_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_OFF, nullptr, 0, stream);
 }
 
 extern "C" int mxl_guided_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
@@ -1312,15 +1407,20 @@ extern "C" int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t
     return mxl_keyed_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_OFF, stream);
 }
 
-extern "C" int mxl_ranged_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                        REG_PARAMS, void* stream) {
+extern "C" int mxl_formed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                        REG_PARAMS, FORM_PARAMS, void* stream) {
     MXL_CHECK_ARG(ids && t_dev && B > 0 && (V > 0 || !(cls || gkey || gpart)));
     DecodeRules r;
-    if (const int e = make_rules(&r, B, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS)) return e;
+    if (const int e = make_rules(&r, B, false, true, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_ARGS, ids, ld_ids)) return e;
     if (!r.cls && !r.gkey && !r.gpart && !r.unfinished) return MXL_OK;                           // nothing to move
     hipLaunchKernelGGL(rules_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long long*)ids, ld_ids, t_dev, B, V, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
+}
+
+extern "C" int mxl_ranged_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
+                                        REG_PARAMS, void* stream) {
+    return mxl_formed_rules_advance(ids, ld_ids, t_dev, B, V, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_OFF, stream);
 }
 
 extern "C" int mxl_guided_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
@@ -1346,6 +1446,10 @@ extern "C" int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B,
 #undef REG_PARAMS
 #undef REG_ARGS
 #undef REG_OFF
+#undef FORM_PARAMS
+#undef FORM_ARGS
+#undef FORM_OFF
+#undef HIST_PARAMS
 
 extern "C" int mxl_register_scan(const void* ids, int ld_ids, int Tp, int from, int B, int V, const void* reg, const void* grange, int gap,
                                  int* gpart, int* gfloor, int* first_bad, void* stream) {

@@ -58,20 +58,24 @@ def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch
                    gkey: Optional[torch.Tensor] = None, melody=None, guide: Optional[torch.Tensor] = None,
                    glen: Optional[torch.Tensor] = None, gpos: Optional[torch.Tensor] = None, gforce: Optional[torch.Tensor] = None,
                    register=None, grange: Optional[torch.Tensor] = None, gpart: Optional[torch.Tensor] = None,
-                   gfloor: Optional[torch.Tensor] = None, gap: int = -1):
+                   gfloor: Optional[torch.Tensor] = None, gap: int = -1, repeat=None, plan: Optional[torch.Tensor] = None,
+                   nplan: Optional[torch.Tensor] = None, barcol: Optional[torch.Tensor] = None, span: int = 0,
+                   gbars: Optional[torch.Tensor] = None, gcopy: Optional[torch.Tensor] = None, gstop: Optional[torch.Tensor] = None):
     """The sampler tail as separate launches (what mxl_sample_step does in one): next token of every row from the first V columns
     of `scores` -> ids[:, t + 1], position and RNG counters advanced.  stop = (eos, pad, min_length) with unfinished / alive and
     grammar with gstate are optional, and a grammar with a bar budget takes gbar / grem as well; gleft (the bars every row may
     still open) turns the grammar's bar count on, in_key (a grammar.KeyRule) with gkey the key rule, melody (a grammar.MelodyGuide)
     with guide / glen / gpos / gforce the guide rule, register (a grammar.RegisterRule) with grange / gpart / gfloor and gap the register
-    rule (ops.rules_in_force).  The mask writes into `scores` in place.  Four launches, two
+    rule, repeat (a grammar.BarRepeat) with plan / nplan / barcol / gbars / gcopy / gstop and span the repeat rule, whose mask reads
+    `ids` as the rows' history (ops.rules_in_force).  The mask writes into `scores` in place.  Four launches, two
     where no rule is in force."""
     rules = ops.rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos,
-                               gforce, register, grange, gpart, gfloor, gap)
+                               gforce, register, grange, gpart, gfloor, gap, repeat, plan, nplan, barcol, span, gbars, gcopy, gstop)
+    past = dict(hist=ids) if 'repeat' in rules else {}
     sc = scores[:, :V] if scores.shape[1] != V else scores
     # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the mask: -inf
     # stays -inf under it, so the result is the same
-    ops.rules_mask(sc, V, t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
+    ops.rules_mask(sc, V, t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')}, **past)
     ops.sample(sc, ids, t_dev, rng, seed, **sampling)
     ops.decode_advance(t_dev, rng)
     # the words move before the stop rule rewrites `unfinished`, which still tells which rows chose their token
@@ -274,7 +278,7 @@ def rules_refusal(what: str, searches: str = 'beam, group-beam or contrastive se
 def plan_search(caps: dict, *, num_beams=1, num_beam_groups=1, do_sample=False, penalty_alpha=None, top_k=None, diversity_penalty=None,
                 eos_token_id=None, pad_token_id=None, config_eos=None, config_pad=None, padded=False, grammar=None, n_bars=None,
                 in_key=None, key=None, melody=None, device_scorer=False, repetition_penalty=None, renormalize_logits=None,
-                vocab_size=None, register=None) -> SearchPlan:
+                vocab_size=None, register=None, form=None) -> SearchPlan:
     """Which search a `generate` call runs -- a plain value: `strategy` = 'sample' (greedy decoding / sampling), 'beam', 'beam_sample',
     'group_beam' or 'contrastive' (chosen as HF 4.25.1 `generate` does); `device`: with its scorer on the device; `rules`: it takes
     grammar / n_bars / in_key / key / register; `eos`, `pad`: what the search arms stop at and fill with (the arguments, else the config's) --
@@ -339,6 +343,8 @@ def plan_search(caps: dict, *, num_beams=1, num_beam_groups=1, do_sample=False, 
         raise rules_refusal('padded prompts (attention_mask with zeros) are')
     if melody is not None and is_search:
         raise rules_refusal('melody= is')
+    if form is not None and is_search:
+        raise rules_refusal('form= is')
     if grammar is not None and not rules:
         raise rules_refusal('grammar= is')
     if n_bars is not None and no_bar_count:
@@ -433,9 +439,12 @@ def melody_config(melody, batch: int, grammar, stop: Optional[tuple], n_bars=Non
     grammar does not accept after a token that opens a bar."""
     if melody is None:
         return None
-    if isinstance(melody, MelodyPlan):
+    if isinstance(melody, (MelodyPlan, FormPlan)):                    # (a FormPlan travels the same way: form_config)
         if melody.B != batch * int(repeat):
-            raise ValueError(f'the melody plan holds {melody.B} rows, the batch {batch * int(repeat)}')
+            raise ValueError(f'the {"melody" if isinstance(melody, MelodyPlan) else "form"} plan holds {melody.B} rows, the batch '
+                             f'{batch * int(repeat)}')
+        if n_bars is not None and isinstance(melody, FormPlan):
+            raise ValueError('n_bars together with form: the form sets the number of bars')
         return melody
     if grammar is None:
         raise ValueError('melody needs grammar=: the guide is fed by the token grammar (tokenizer.grammar(bar_budget=True))')
@@ -477,12 +486,122 @@ def melody_config(melody, batch: int, grammar, stop: Optional[tuple], n_bars=Non
     return plan if r == 1 else MelodyPlan(rule, [g for g in guides for _ in range(r)], [x for x in bars for _ in range(r)])
 
 
+def _forms_per_row(form, batch: int) -> list:
+    """`form` as generate takes it -> one entry per prompt, each None, a string of sections or a plan (a list of ints): one string
+    or one plan (a 1-D tensor or a flat sequence of ints) stands for every prompt, a sequence of them (None = that row has no plan)
+    gives one per prompt -- as _guides_per_row tells one guide from many"""
+    def one_plan(f):
+        if isinstance(f, torch.Tensor):
+            if f.dim() != 1 or f.is_floating_point() or f.dtype == torch.bool:
+                raise ValueError('a plan is a 1-D sequence of ints')
+            return [int(j) for j in f.detach().cpu().tolist()]
+        return f
+    if isinstance(form, str):
+        return [form] * batch
+    if isinstance(form, torch.Tensor) and form.dim() == 2:
+        form = list(form)
+    if isinstance(form, torch.Tensor) or (isinstance(form, (list, tuple)) and len(form) > 0
+                                          and all(hasattr(j, '__index__') and not isinstance(j, torch.Tensor) for j in form)):
+        return [one_plan(form)] * batch
+    if not isinstance(form, (list, tuple)):
+        raise ValueError('form is a string of sections, a plan (a sequence of ints) or a list of one of them per prompt')
+    if len(form) == 0:
+        raise ValueError('an empty form plans no bar')
+    if len(form) != batch:
+        raise ValueError(f'form holds {len(form)} entries for {batch} prompts: give one form or one per prompt')
+    return [one_plan(f) for f in form]
+
+
+class FormPlan:
+    """The forms of one generation as the decoders take them (form_config): `rule` (the grammar's BarRepeat), per row `plans` (None
+    or the row's plan: per generated bar -1 = free or the earlier generated bar it repeats), `span` (0 = a repeat copies the whole
+    bar, 1 = its melody), and `n_bars` (B,) int32, the start value of gleft: the length of the row's plan, -1 in a row without one"""
+
+    def __init__(self, rule, plans: list, span: int):
+        self.rule, self.plans, self.span = rule, plans, int(span)
+        self.n_bars = torch.tensor([-1 if p is None else len(p) for p in plans], dtype=torch.int32)
+
+    @property
+    def B(self) -> int:
+        return len(self.plans)
+
+    def rows(self, lo: int, hi: int) -> 'FormPlan':
+        return FormPlan(self.rule, self.plans[lo:hi], self.span)
+
+    def tables(self):
+        """(plan (B, W) int32, nplan (B,) int32) on the CPU: the rows' plans, right-filled with -1; W >= 1"""
+        W = max([1] + [len(p) for p in self.plans if p is not None])
+        plan = torch.full((self.B, W), -1, dtype=torch.int32)
+        for b, p in enumerate(self.plans):
+            if p is not None:
+                plan[b, :len(p)] = torch.tensor(p, dtype=torch.int32)
+        return plan, torch.tensor([0 if p is None else len(p) for p in self.plans], dtype=torch.int32)
+
+
+def form_config(form, section_bars, form_span, batch: int, grammar, stop: Optional[tuple], n_bars=None, melody=None,
+                min_length: Optional[int] = None, repeat: int = 1) -> Optional[FormPlan]:
+    """`form` / `section_bars` / `form_span` of a generation as the decoders take them: None, or a FormPlan over batch * repeat rows
+    (`repeat` = num_return_sequences: every prompt's plan repeated, as the prompts are).  form: one string of sections ('AABA'), one
+    plan, or a list of one string, plan or None per prompt (_forms_per_row; grammar.BarRepeat.plan_of makes and checks the plans); a
+    FormPlan passes through.  section_bars (default 1): the bars of a section of a string.  form_span (default 'bar'): 'bar' = a
+    repeat copies the whole bar, 'melody' = its melody, under which the row writes a new bass.  Raises ValueError for what the rule
+    cannot work with -- section_bars or form_span without form, no grammar, a grammar without a BarRepeat or a bar count, no explicit
+    eos, n_bars or melody beside it (the plan sets the count; a row is fed from one place), min_length, section_bars < 1, an empty
+    form, a plan entry outside -1..k-1, a wrong number of forms, another form_span."""
+    from .grammar import BarRepeat
+    if form is None:
+        if section_bars is not None or form_span is not None:
+            raise ValueError('section_bars= and form_span= need form=')
+        return None
+    if isinstance(form, FormPlan):
+        if form.B != batch * int(repeat):
+            raise ValueError(f'the form plan holds {form.B} rows, the batch {batch * int(repeat)}')
+        return form
+    if grammar is None:
+        raise ValueError('form needs grammar=: bars are told apart by the token grammar (tokenizer.grammar(bar_budget=True))')
+    rule = getattr(grammar, 'repeat', None)
+    if rule is None:
+        raise ValueError('form needs a grammar with a repeat rule (grammar.BarRepeat; the music grammar has one), this one has none')
+    if grammar.bar_count is None:
+        raise ValueError('form needs a grammar with a bar count (grammar.BarCount): the count of the planned bars ends the row')
+    if stop is None:
+        raise ValueError('form needs an explicit eos_token_id=: a row ends by emitting eos, and stopping at eos is opt-in')
+    if n_bars is not None:
+        raise ValueError('n_bars together with form: the form sets the number of bars')
+    if melody is not None:
+        raise ValueError('melody together with form: a row is fed from its guide or from its own bars, not both')
+    if stop[2] > 0 or (min_length or 0) > 0:
+        raise ValueError('form together with min_length: the bar count ends a planned row, and min_length may bar eos where '
+                         'nothing else is allowed')
+    span = BarRepeat.SPANS.get(form_span if form_span is not None else 'bar') if isinstance(form_span, (str, type(None))) else None
+    if span is None:
+        raise ValueError(f"form_span is 'bar' (a repeat copies the whole bar) or 'melody' (its melody alone), got {form_span!r}")
+    plans = [None if f is None else BarRepeat.plan_of(f, 1 if section_bars is None else section_bars)
+             for f in _forms_per_row(form, batch)]
+    BarRepeat.plan_of([-1], 1 if section_bars is None else section_bars)                # (section_bars is judged whatever the forms are)
+    plan = FormPlan(rule, plans, span)
+    bar_count_config(plan.n_bars, batch, grammar, stop)               # the eos must be an `end` token of the count
+    r = int(repeat)
+    return plan if r == 1 else FormPlan(rule, [p for p in plans for _ in range(r)], span)
+
+
 class RulePlan(namedtuple('RulePlan', 'stop grammar n_bars in_key keys melody register B', defaults=(None,) * 8)):
     """The rules of one generation as every layer between `generate` and RowRules.start hands them down (rules_config builds it):
     `stop` = (eos, pad, min_length) or None, `grammar`, `n_bars` (None or (B,) int32 on the CPU), `in_key` with `keys` (None or (B,)
-    int32), `melody` (None or a MelodyPlan), `register` (None or a RegisterPlan), and `B`, the rows the per-row fields were built
-    for (None: no field is per row)."""
+    int32), `melody` (None, a MelodyPlan or a FormPlan: what rows are fed from, their guides or their own earlier bars -- the two
+    exclude each other, so they share the field; `guide` and `form` tell them apart), `register` (None or a RegisterPlan), and `B`,
+    the rows the per-row fields were built for (None: no field is per row)."""
     __slots__ = ()
+
+    @property
+    def guide(self) -> Optional[MelodyPlan]:
+        """the MelodyPlan of a generation under melody=, else None"""
+        return self.melody if isinstance(self.melody, MelodyPlan) else None
+
+    @property
+    def form(self) -> Optional[FormPlan]:
+        """the FormPlan of a generation under form=, else None"""
+        return self.melody if isinstance(self.melody, FormPlan) else None
 
     def rows(self, lo: int, hi: int) -> 'RulePlan':
         """the plan of rows lo..hi-1: every per-row field cut to them (how XLDecoderLanes hands each lane its own)"""
@@ -523,7 +642,11 @@ def rules_config(*, batch: int, vocab_size: int, stop: Optional[tuple] = None, g
     by bar inside the sampler launch and chooses the bass under each, then ends: the plan's bar counts become n_bars.
     register (a grammar.RegisterRule, e.g. `tokenizer.register_rule()`, or a RegisterPlan; needs no grammar) with melody_range /
     bass_range (one inclusive pair of MIDI numbers or one per prompt, None = unconstrained) and bass_below (None or g >= 0
-    semitones): the pitches of every part stay inside its bounds, and the bass at least g under the lowest melody note of its bar."""
+    semitones): the pitches of every part stay inside its bounds, and the bass at least g under the lowest melody note of its bar.
+    A FormPlan as `melody` (form_config builds it from generate's form / section_bars / form_span and refuses what cannot stand beside
+    it) passes through like a MelodyPlan: song form -- a planned bar repeats an earlier bar the row generated, copied token by token
+    from the row's own ids inside the sampler launch; the plans' lengths become n_bars.  A row is fed from its guide or from its own
+    bars, never both, so the two plans share the field (RulePlan.guide / RulePlan.form)."""
     check_grammar_args(grammar, vocab_size, stop)
     guide = melody_config(melody, batch, grammar, stop, n_bars, repeat)
     bars = bar_count_config(n_bars, batch, grammar, stop, repeat) if guide is None else guide.n_bars
@@ -576,9 +699,13 @@ class RowRules:
     under `register`, a grammar.RegisterRule, with the generation's `gap`), each (B,) -- then gbad (2, B), the first prompt
     column that breaks the grammar / the budget, and alive (1,), the live-row count.  The guide group also keeps two tables of its
     own here, `guide` (B, ld) int32 and `glen` (B,) int32, refilled by every `start` and regrown only for a longer guide, so that a
-    captured step finds the next generation's guides where it found the last one's.  A further rule is a row here, a field in RulePlan,
-    a line in rules_config and `start`, and a key in `kwargs` / `graph_key` ("adding a rule")."""
-    WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey', 'gpos', 'gforce', 'grange', 'gpart', 'gfloor')
+    captured step finds the next generation's guides where it found the last one's.  The repeat group (`repeat`, a grammar.BarRepeat,
+    with the generation's `span`) has the words gbars / gcopy / gstop (bars opened, the column of the row's own ids the next token is
+    copied from, and where the copy ends) and three tables kept the same way: `plan` (B, ld) and `nplan` (B,) int32, uploaded by
+    `start`, and `barcol` (B, ld) int32, which the device writes.  A further rule is a row here, a field in RulePlan, a line in
+    rules_config and `start`, and a key in `kwargs` / `graph_key` ("adding a rule")."""
+    WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey', 'gpos', 'gforce', 'grange', 'gpart', 'gfloor', 'gbars', 'gcopy',
+             'gstop')
     STATE = WORDS + ('alive',)
 
     def __init__(self, batch: int, dev):
@@ -591,11 +718,15 @@ class RowRules:
         self.unfinished.fill_(1)
         self.gleft.fill_(-1)
         self.gkey.fill_(-1)
-        self.stop = self.grammar = self.n_bars = self.in_key = self.melody = self.melody_plan = self.register = None
-        self.bars, self.gap = False, -1
+        self.gcopy.fill_(-1)
+        self.stop = self.grammar = self.n_bars = self.in_key = self.melody = self.melody_plan = self.register = self.repeat = None
+        self.bars, self.gap, self.span = False, -1, 0
         self._reset_register()
         self.guide = torch.zeros(batch, 64, device=dev, dtype=torch.int32)
         self.glen = torch.zeros(batch, device=dev, dtype=torch.int32)
+        self.plan = torch.full((batch, 64), -1, device=dev, dtype=torch.int32)
+        self.barcol = torch.full((batch, 64), -1, device=dev, dtype=torch.int32)
+        self.nplan = torch.zeros(batch, device=dev, dtype=torch.int32)
 
     def _reset_register(self):
         from .grammar import ANY_RANGE, NO_FLOOR, pack_bounds
@@ -610,9 +741,12 @@ class RowRules:
         key token of every row's prompt, found on the device (-1 in a row without one).  Under melody the rows' guides and their
         lengths go to the device tables and every row starts free at guide index 0 -- a bar open at the end of the prompt is finished
         freely, the guide engages at the next bar -- and n_bars must be the guides' own.  Under register grange = the plan's bounds,
-        gpart and gfloor = the open part and the floor every row's prompt leaves it in, found on the device.  No rule judges the
-        prompt's pitches.  A plan built for another decoder (row count, vocabulary, grammar) raises."""
+        gpart and gfloor = the open part and the floor every row's prompt leaves it in, found on the device.  Under form the rows'
+        plans and their lengths go to the device tables, barcol is filled with -1, every row starts with no bar opened and no copy
+        under way -- a bar open at the end of the prompt is finished freely and has no number -- and n_bars must be the plans' own.
+        No rule judges the prompt's pitches.  A plan built for another decoder (row count, vocabulary, grammar) raises."""
         stop, grammar, n_bars, in_key, keys, melody, register = plan[:7]
+        form, melody = plan.form, plan.guide              # (the field `melody` holds the one or the other)
         check_grammar_args(grammar, vocab_size, stop)
         if register is not None and (register.rule.vocab_size != int(vocab_size) or register.B != self.B):
             raise MusicXLError(f'the register rule must span the model\'s {int(vocab_size)} tokens and hold one entry per row '
@@ -637,6 +771,26 @@ class RowRules:
             self.glen.copy_(glen)
         else:
             self.glen.zero_()
+        if form is not None and (grammar is None or form.rule is not getattr(grammar, 'repeat', None) or form.B != self.B or stop is None
+                                 or n_bars is None or n_bars.tolist() != form.n_bars.tolist()):
+            raise MusicXLError('form needs the grammar its repeat rule belongs to, the eos rule, one plan entry per row and n_bars = '
+                               'the lengths of the plans (form_config)')
+        self.repeat, self.span = (None, 0) if form is None else (form.rule, form.span)
+        self.gbars.zero_()
+        self.gcopy.fill_(-1)
+        self.gstop.zero_()
+        if form is not None:
+            tab, nplan = form.tables()
+            if tab.shape[1] > self.plan.shape[1]:
+                W = (tab.shape[1] + 63) // 64 * 64
+                self.plan = torch.empty(self.B, W, device=self.plan.device, dtype=torch.int32)
+                self.barcol = torch.empty_like(self.plan)
+            self.plan.fill_(-1)
+            self.plan[:, :tab.shape[1]].copy_(tab)
+            self.nplan.copy_(nplan)
+            self.barcol.fill_(-1)
+        else:
+            self.nplan.zero_()
         if in_key is not None and in_key.vocab_size != int(vocab_size):
             raise MusicXLError(f'the key rule spans {in_key.vocab_size} tokens, the model has vocab_size {int(vocab_size)}')
         if keys is not None and (in_key is None or keys.numel() != self.B):
@@ -683,14 +837,18 @@ class RowRules:
         return dict(stop=self.stop, unfinished=self.unfinished, alive=self.alive, grammar=self.grammar, gstate=self.gstate,
                     gbar=self.gbar, grem=self.grem, gleft=self.gleft if self.bars else None, in_key=self.in_key, gkey=self.gkey,
                     melody=self.melody, guide=self.guide, glen=self.glen, gpos=self.gpos, gforce=self.gforce,
-                    register=self.register, grange=self.grange, gpart=self.gpart, gfloor=self.gfloor, gap=self.gap)
+                    register=self.register, grange=self.grange, gpart=self.gpart, gfloor=self.gfloor, gap=self.gap,
+                    repeat=self.repeat, plan=self.plan, nplan=self.nplan, barcol=self.barcol, span=self.span, gbars=self.gbars,
+                    gcopy=self.gcopy, gstop=self.gstop)
 
     def graph_key(self, dev) -> tuple:
         """what a captured sampler launch holds of the rules: which of them are on, the identity of the grammar's and the budget's
         device tables and their class masks, the presence of the key rule and the identity of its tables, the presence of the guide
         rule with its class masks and the identity of its guide buffer, the presence of the register rule with the identity of its
-        table and the gap.  The per-row words, the keys and the guide positions among
-        them, and the guide tokens themselves are step state and not part of it."""
+        table and the gap, the presence of the repeat rule with its class masks, the span and the identity and stride of its
+        plan, nplan and barcol tables.  The per-row words, the keys and the guide positions among
+        them, the guide tokens and the plans themselves are step state and not part of it.  (A call without the repeat rule keeps
+        the key it had: the entry is appended only when the rule is on.)"""
         g = self.grammar
         return (self.stop,
                 None if g is None else tuple(t.data_ptr() for t in g.to(dev)) + (g.n_classes,),
@@ -700,13 +858,17 @@ class RowRules:
                 None if self.in_key is None else tuple(t.data_ptr() for t in self.in_key.to(dev)),
                 None if self.melody is None else (self.melody.enter, self.melody.leave, self.guide.data_ptr(), self.guide.stride(0),
                                                   self.glen.data_ptr()),
-                None if self.register is None else (self.register.to(dev).data_ptr(), self.gap))
+                None if self.register is None else (self.register.to(dev).data_ptr(), self.gap)) + (
+            () if self.repeat is None else ((self.repeat.enter, self.repeat.leave, self.span, self.plan.data_ptr(), self.plan.stride(0),
+                                             self.nplan.data_ptr(), self.barcol.data_ptr(), self.barcol.stride(0)),))
 
-    def snapshot(self) -> torch.Tensor:
-        return self.buf.clone()
+    def snapshot(self) -> tuple:
+        """everything the sampler launches write: the packed words and the repeat group's barcol"""
+        return self.buf.clone(), self.barcol.clone()
 
-    def restore(self, saved: torch.Tensor):
-        self.buf.copy_(saved)
+    def restore(self, saved: tuple):
+        self.buf.copy_(saved[0])
+        self.barcol.copy_(saved[1])
 
 
 def check_grammar(ids: torch.Tensor, grammar, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -873,6 +1035,53 @@ def check_melody(ids: torch.Tensor, grammar, melody, prompt_len: Optional[int] =
     return torch.tensor(out, dtype=torch.int64)
 
 
+def check_form(ids: torch.Tensor, grammar, form, section_bars: int = 1, form_span: str = 'bar', prompt_len: Optional[int] = None,
+               attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B,) int64 on the CPU, as check_melody: for every row of ids (B, T) the first generated column (>= prompt_len) that departs
+    from the row's plan, -1 = none -- what `generate(form=)` keeps at -1.  form / section_bars / form_span: as generate's (one form
+    or one per row, None = the row has no plan and is clean).  A column departs if, inside a repeat, it holds another token than the
+    source bar holds there (form_span='bar': the whole bar; 'melody': up to and including its `<bass>`), if it opens a bar beyond
+    the plan, or if it ends the row (a token of an `end` class of the grammar's bar count) while planned bars were never opened.  A
+    row cut by max_length is judged up to the cut.  prompt_len: the width of the prompt; default the width of attention_mask, else 0.
+    attention_mask (B, Tp): left-pad columns (0) are skipped.  The walk runs on the host (BarRepeat.walk)."""
+    from .grammar import BarRepeat
+    rule = getattr(grammar, 'repeat', None)
+    if rule is None or grammar.bar_count is None:
+        raise ValueError('check_form needs a grammar with a repeat rule and a bar count (the music grammar has both)')
+    if form_span not in BarRepeat.SPANS:
+        raise ValueError(f"form_span is 'bar' or 'melody', got {form_span!r}")
+    ids = torch.as_tensor(ids)
+    if ids.dim() == 1:
+        ids = ids.view(1, -1)
+    x = ids.to(torch.int64).cpu().clone()
+    if attention_mask is not None:
+        m = torch.as_tensor(attention_mask).cpu()
+        x[:, :m.shape[1]].masked_fill_(m == 0, -1)
+    if prompt_len is None:
+        prompt_len = 0 if attention_mask is None else int(torch.as_tensor(attention_mask).shape[1])
+    prompt_len = int(prompt_len)
+    cnt, cls, V = grammar.bar_count, grammar.cls, grammar.vocab_size
+    out = []
+    for row, f in zip(x.tolist(), _forms_per_row(form, x.shape[0])):
+        if f is None:
+            out.append(-1)
+            continue
+        plan = BarRepeat.plan_of(f, section_bars)
+        kind = lambda t, mask: 0 <= t < V and (mask >> int(cls[t])) & 1
+        end_at = next((i for i in range(prompt_len, len(row)) if kind(row[i], cnt.end)), None)
+        opened = [i for i in range(prompt_len, len(row) if end_at is None else end_at) if kind(row[i], cnt.count)]
+        cut = len(row) if end_at is None else end_at
+        if len(opened) > len(plan):                                   # a bar beyond the plan: judged up to it
+            cut = opened[len(plan)]
+        _, bad = rule.walk(row[:cut], plan, BarRepeat.SPANS[form_span], prompt_len)
+        if bad < 0 and len(opened) > len(plan):
+            bad = cut
+        if bad < 0 and end_at is not None and len(opened) < len(plan):
+            bad = end_at
+        out.append(bad)
+    return torch.tensor(out, dtype=torch.int64)
+
+
 class _AlivePoll:
     """live-row counts of one decoder read back without stalling its stream: after each chunk of steps a non-blocking copy of
     `alive` into pinned host memory and an event; `wait(keep)` blocks until at most `keep` such reads are outstanding"""
@@ -982,7 +1191,8 @@ class RuledGenerate:
                  typical_p: Optional[float] = None, use_graph: bool = True, n_pad: Optional[torch.Tensor] = None,
                  eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, min_length: Optional[int] = None,
                  stop_chunk: int = STOP_CHUNK, grammar=None, n_bars=None, in_key=None, key=None, melody=None, register=None,
-                 melody_range=None, bass_range=None, bass_below=None, stop: Optional[tuple] = None) -> torch.Tensor:
+                 melody_range=None, bass_range=None, bass_below=None, stop: Optional[tuple] = None, form=None, section_bars=None,
+                 form_span=None) -> torch.Tensor:
         """Returns (B, max_length) ids = prompt + continuation.  Like the reference (eos_token_id stays HF's default 0 =
         [OMIT], SURVEY 3.4) decoding runs to max_length.  n_pad: (B,) int32 device tensor of left-pad counts (XLDecoder.prefill);
         the prompt columns, pads included, come back as given.  use_graph: one captured step replayed per token, where the decoder
@@ -991,12 +1201,16 @@ class RuledGenerate:
         (stop_config): rows finish at eos.  The decode steps are replayed in chunks of `stop_chunk` with the live-row count read back
         one chunk late (run_until_finished): no per-step host round trip.  Over lanes every lane stops on its own; the output is the
         lanes' rows cut to the common width and right-filled with pad where a lane stopped earlier.
-        grammar, n_bars, in_key / key, melody, register with melody_range / bass_range / bass_below: the rules, one value per row
+        grammar, n_bars, in_key / key, melody, register with melody_range / bass_range / bass_below, form with section_bars /
+        form_span: the rules, one value per row
         where they are per row, as rules_config describes and checks them; each lane keeps the words of its own rows."""
         self._admit(max_length)
+        stop = stop_config(eos_token_id, pad_token_id, min_length) if stop is None else stop
+        feed = form_config(form, section_bars, form_span, self.B, grammar, stop, n_bars, melody)
         rules = rules_config(batch=self.B, vocab_size=getattr(self, 'lanes', [self])[0].eng.cfg.vocab_size,
-                             stop=stop_config(eos_token_id, pad_token_id, min_length) if stop is None else stop, grammar=grammar,
-                             n_bars=n_bars, in_key=in_key, key=key, melody=melody, register=register, melody_range=melody_range,
+                             stop=stop, grammar=grammar,
+                             n_bars=n_bars, in_key=in_key, key=key, melody=melody if feed is None else feed, register=register,
+                             melody_range=melody_range,
                              bass_range=bass_range, bass_below=bass_below)
         return self.run(prompt, max_length, sampling_config(do_sample, top_k, top_p, temperature, repetition_penalty, typical_p), rules,
                         use_graph, n_pad, stop_chunk)

@@ -85,6 +85,21 @@ bass touch the bar's lowest melody note, gap 1 keeps it strictly below.  The bou
 keep the parts from crossing, not necessary.  A part token sets `part`, <bar> clears `part` and `floor`, a melody pitch lowers `floor`.
 No dead end: the rest and the rare pitch are never barred and belong to the grammar's class `pitch`, so wherever a pitch may follow a
 token is left even when the bounds leave no pitched one.
+
+`BarRepeat` (`grammar.repeat`; both forms of the music grammar carry one) is the rule behind `generate(..., form='AABA')`: song form.
+A row's generated bars are the bars it opens after its prompt, numbered from 0; a plan says of each whether it is free (-1) or
+repeats an earlier generated bar j, and a repeating bar is copied token by token out of the row's own output.  Three more integers per
+row, `bars` = the bars opened so far, `copy` = the column of the row's ids the next token is copied from (-1 = the row chooses) and
+`stop` = the column where the copy ends, the table `barcol` (the column of every generated bar's `enter` token, written as the row
+goes), the same two class bit masks as the guide's
+
+    enter      class bit mask  classes that open a bar (<bar>): the row records the column and, if the plan names a source, copies
+                               from behind the source's own `enter` token
+    leave      class bit mask  classes that close the melody (<bass>): under span 1 the copy ends with it
+
+and one number for the generation, `span` (0 = the whole bar is repeated, 1 = its melody, under which the row writes a new bass).  A
+copying row may emit the one token of its history, whatever the other rules say, exactly as a guided row; the bar count, set to the
+length of the plan, ends the row.
 """
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
@@ -156,6 +171,7 @@ class TokenGrammar:
         self.budget: Optional['BarBudget'] = None        # the duration budget riding on this grammar (BarBudget attaches itself)
         self.bar_count: Optional['BarCount'] = None      # the bar count rule of generate(n_bars=) (BarCount attaches itself)
         self.guide: Optional['MelodyGuide'] = None       # the guide rule of generate(melody=) (MelodyGuide attaches itself)
+        self.repeat: Optional['BarRepeat'] = None        # the repeat rule of generate(form=) (BarRepeat attaches itself)
 
     # ---------------------------------------------------------------- shape
     @property
@@ -596,6 +612,105 @@ class MelodyGuide:
         return f'MelodyGuide(enter={names(self.enter)}, leave={names(self.leave)})'
 
 
+class BarRepeat:
+    SPANS = {'bar': 0, 'melody': 1}                      # generate's form_span -> the device's span
+
+    def __init__(self, grammar: TokenGrammar, enter, leave):
+        """The repeat rule of `grammar` (module docstring): `enter` and `leave`, each a class bit mask or an iterable of class
+        names.  Attaches itself as `grammar.repeat`."""
+        self.enter, self.leave = _class_mask(grammar, enter), _class_mask(grammar, leave)
+        if not self.enter or not self.leave:
+            raise ValueError('enter and leave each need at least one class')
+        if self.enter & self.leave:
+            raise ValueError('a class cannot both open a bar and close its melody')
+        self.grammar = grammar
+        grammar.repeat = self
+
+    # ---------------------------------------------------------------- plans
+    @staticmethod
+    def plan_of(form, section_bars: int = 1) -> List[int]:
+        """the plan of a form: plan[k] = -1, generated bar k is free, or j < k, it repeats generated bar j.  form: a string of
+        sections, one character each, `section_bars` bars a section -- the first occurrence of a character is free, a later one
+        copies the first bar by bar ('AABA', 2 -> [-1, -1, 0, 1, -1, -1, 0, 1]) -- or a sequence of ints, a plan itself, which is
+        validated: -1 <= plan[k] < k.  ValueError for an empty form, section_bars < 1 or a bad entry."""
+        if isinstance(section_bars, bool) or not hasattr(section_bars, '__index__') or int(section_bars) < 1:
+            raise ValueError(f'section_bars must be an int >= 1, got {section_bars!r}')
+        n = int(section_bars)
+        if isinstance(form, str):
+            if not form:
+                raise ValueError('an empty form plans no bar')
+            first, plan = {}, []
+            for i, ch in enumerate(form):
+                at = first.setdefault(ch, i)
+                plan += [-1 if at == i else at * n + r for r in range(n)]
+            return plan
+        if isinstance(form, bytes) or not hasattr(form, '__iter__'):
+            raise ValueError('a form is a string of sections or a plan, a sequence of ints')
+        seq = form.tolist() if hasattr(form, 'tolist') else list(form)
+        if any(isinstance(j, (bool, float, str)) or not hasattr(j, '__index__') for j in seq):
+            raise ValueError('a plan is a sequence of ints')
+        plan = [int(j) for j in seq]
+        if not plan:
+            raise ValueError('an empty form plans no bar')
+        for k, j in enumerate(plan):
+            if not -1 <= j < k:
+                raise ValueError(f'plan entry {k} is {j}: a bar is free (-1) or repeats an earlier generated bar (0..{k - 1})')
+        return plan
+
+    # ---------------------------------------------------------------- the rule
+    @staticmethod
+    def start(n: int) -> dict:
+        """the words of a row before its first generated token, with room for the columns of n bars"""
+        return dict(bars=0, copy=-1, stop=0, barcol=[-1] * int(n))
+
+    def forced(self, ids_row, gcopy: int) -> int:
+        """the token a row with the word gcopy is fed from its own ids at this step, -1 = none: the row chooses"""
+        return int(ids_row[gcopy]) if 0 <= gcopy < len(ids_row) and int(ids_row[gcopy]) >= 0 else -1
+
+    def move(self, words: dict, plan_row, c: int, col: int, span: int) -> dict:
+        """the words (bars, copy, stop, barcol) after a kept token of class c written at column col, under the row's plan"""
+        w = dict(words, barcol=list(words['barcol']))
+        if w['copy'] >= 0:
+            w['copy'] += 1
+            if w['copy'] >= w['stop'] or (span == 1 and (self.leave >> c) & 1):
+                w['copy'] = -1
+        elif (self.enter >> c) & 1 and w['bars'] < len(plan_row):
+            k = w['bars']
+            w['barcol'][k] = col
+            w['bars'] = k + 1
+            j = int(plan_row[k])
+            if j >= 0:
+                lo = w['barcol'][j] + 1
+                hi = col if j + 1 == k else w['barcol'][j + 1]
+                if lo < hi:
+                    w['copy'], w['stop'] = lo, hi
+        return w
+
+    # ---------------------------------------------------------------- host reference
+    def walk(self, ids, plan_row, span: int = 0, start: int = 0) -> Tuple[dict, int]:
+        """(words, index of the first token that departs from the plan or -1) for a 1-D id sequence whose generated part begins
+        at index `start` (the tokens before it are the prompt: they move nothing); the walk stops at a departure.  A token departs
+        if the row is copying and it is not the token of the row's own history at `copy`.  A sequence cut inside a copy is clean.
+        Ids < 0 (left pads) and ids beyond the vocabulary are skipped.  The host reference of the device rule."""
+        seq = [int(t) for t in (ids.tolist() if hasattr(ids, 'tolist') else list(ids))]
+        plan = [int(j) for j in (plan_row.tolist() if hasattr(plan_row, 'tolist') else list(plan_row))]
+        cls, V = self.grammar.cls, self.grammar.vocab_size
+        w = self.start(len(plan))
+        for i in range(int(start), len(seq)):
+            tok = seq[i]
+            if tok < 0 or tok >= V:
+                continue
+            f = self.forced(seq, w['copy']) if plan else -1
+            if f >= 0 and tok != f:
+                return w, i
+            w = self.move(w, plan, int(cls[tok]), i, span)
+        return w, -1
+
+    def __repr__(self):
+        names = lambda m: [n for i, n in enumerate(self.grammar.class_names) if (m >> i) & 1]
+        return f'BarRepeat(enter={names(self.enter)}, leave={names(self.leave)})'
+
+
 class KeyRule:
     def __init__(self, keys, pcs, inkey=None):
         """The key rule (module docstring) from explicit tables: keys / pcs (V,) with NO_KEY / NO_PITCH for "none", inkey (24,) bit
@@ -826,11 +941,12 @@ def music_key_rule(vocab) -> KeyRule:
 
 def from_transitions(cls, class_names: Sequence[str], transitions: Sequence[Tuple[str, str, str]], start: str,
                      accepting: Optional[Iterable[str]] = None, budget: Optional[dict] = None,
-                     bar_count: Optional[dict] = None, guide: Optional[dict] = None) -> TokenGrammar:
+                     bar_count: Optional[dict] = None, guide: Optional[dict] = None, repeat: Optional[dict] = None) -> TokenGrammar:
     """a TokenGrammar from (state, class, successor) triples by name; states are numbered in order of appearance, `start` first.
     budget: the explicit tables of a BarBudget to attach, as its keyword arguments (slots, bars, opens, need_free, need_full).
     bar_count: the classes of a BarCount to attach, as its keyword arguments (count, end).
-    guide: the classes of a MelodyGuide to attach, as its keyword arguments (enter, leave)"""
+    guide: the classes of a MelodyGuide to attach, as its keyword arguments (enter, leave)
+    repeat: the classes of a BarRepeat to attach, as its keyword arguments (enter, leave)"""
     states = [start]
     for a, _, b in transitions:
         for s in (a, b):
@@ -856,6 +972,8 @@ def from_transitions(cls, class_names: Sequence[str], transitions: Sequence[Tupl
         BarCount(g, **bar_count)
     if guide is not None:
         MelodyGuide(g, **guide)
+    if repeat is not None:
+        BarRepeat(g, **repeat)
     return g
 
 
@@ -915,7 +1033,8 @@ def music_grammar(vocab, bar_budget: bool = False) -> TokenGrammar:
     token ([PAD] and [OMIT] included) is a class of its own.  bar_budget: attach the duration budget (`grammar.budget`), so that
     every channel of a bar generated under the grammar is exactly as long as the prompt's time signature says.  Either form
     carries the bar count rule of `generate(n_bars=)` (`grammar.bar_count`: count = <bar>, end = </s>) and the guide rule of
-    `generate(melody=)` (`grammar.guide`: enter = <bar>, leave = <bass>)"""
+    `generate(melody=)` (`grammar.guide`: enter = <bar>, leave = <bass>) and the repeat rule of `generate(form=)` (`grammar.repeat`,
+    over the same two classes)"""
     cid = {c: i for i, c in enumerate(MUSIC_CLASSES)}
     cls = np.zeros(len(vocab), dtype=np.uint8)
     for tok, i in vocab.tok2id.items():
@@ -926,14 +1045,14 @@ def music_grammar(vocab, bar_budget: bool = False) -> TokenGrammar:
         cls[i] = cid[name]
     return from_transitions(cls, MUSIC_CLASSES, MUSIC_TRANSITIONS, 'S0', accepting=['END'],
                             budget=music_budget_tables(vocab) if bar_budget else None, bar_count=MUSIC_BAR_COUNT_CLASSES,
-                            guide=MUSIC_GUIDE_CLASSES)
+                            guide=MUSIC_GUIDE_CLASSES, repeat=MUSIC_GUIDE_CLASSES)
 
 
 # -------------------------------------------------------------------- sub-word vocabularies
 def subword_grammar(base: TokenGrammar, pieces: Sequence[Sequence[int]]) -> TokenGrammar:
     """`base` composed with a sub-word vocabulary: pieces[v] = the base ids that id v stands for (`id2base_ids()` of a sub-word
     tokenizer).  The rule is defined on the DECODED stream: a row of ids is allowed iff the concatenation of its pieces is allowed
-    under `base` -- and its budget and bar count, which the result carries if `base` does (never its guide).
+    under `base` -- and its budget and bar count, which the result carries if `base` does (never its guide or its repeat rule).
 
     States, start and accepting states are the base's.  A single-base id keeps the class (index and name) of its base token, so the
     class masks of the budget and the count carry over bit for bit.  A multi-base id gets the class of the partial function it

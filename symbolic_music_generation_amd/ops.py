@@ -135,12 +135,22 @@ def decode_qkv(x, wqkv, qkv, kc, vc, t_dev, rrb, qr_out, dh):
 
 def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None,
                    gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None,
-                   gfloor=None, gap=-1) -> dict:
+                   gfloor=None, gap=-1, repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None, gcopy=None,
+                   gstop=None) -> dict:
     """The rules of a generation as its decoders describe them -> the keywords of rules_mask / rules_advance, where a group is on
     exactly when its state tensor is given.  The decoders say which rules hold with `stop` (the eos rule), `grammar` (the grammar,
     and its bar budget if it has one), `gleft` (the bar count), `in_key` (the key rule), `melody` (the guide rule, a
-    grammar.MelodyGuide) and `register` (the register rule, a grammar.RegisterRule, with the launch's `gap`) and may hand over state
-    tensors of rules that are off: those are dropped here, and a rule that is on without its state raises."""
+    grammar.MelodyGuide), `register` (the register rule, a grammar.RegisterRule, with the launch's `gap`) and `repeat` (the repeat
+    rule, a grammar.BarRepeat, with the launch's `span`) and may hand over state tensors of rules that are off: those are dropped
+    here, and a rule that is on without its state raises."""
+    if repeat is not None:                  # (a call without the rule carries no key of it: the ranged entries, as before)
+        if grammar is None or gleft is None or stop is None or melody is not None:
+            raise MusicXLError('the repeat rule rides on a grammar, needs the bar count (gleft) and the eos rule, and excludes the guide')
+        if any(x is None for x in (plan, nplan, barcol, gbars, gcopy, gstop)):
+            raise MusicXLError('the repeat rule needs plan, nplan, barcol, gbars, gcopy and gstop')
+        return dict(rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos,
+                                   gforce, register, grange, gpart, gfloor, gap), repeat=repeat, plan=plan, nplan=nplan, barcol=barcol,
+                    span=int(span), gbars=gbars, gcopy=gcopy, gstop=gstop)
     budget = grammar is not None and grammar.budget is not None
     if stop is not None and (unfinished is None or alive is None):
         raise MusicXLError('the eos rule needs unfinished and alive')
@@ -196,6 +206,36 @@ def _guide_args(what, device, B, V=None, *, grammar=None, melody=None, guide=Non
 
 
 REGISTER_KEYS = ('register', 'grange', 'gpart', 'gfloor', 'gap')
+REPEAT_KEYS = ('repeat', 'plan', 'nplan', 'barcol', 'span', 'gbars', 'gcopy', 'gstop')
+
+
+def _repeat_args(what, device, B, V=None, *, grammar=None, repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None,
+                 gcopy=None, gstop=None) -> list:
+    """the repeat group of the mxl_formed_* entries (include/musicxl.h, "Rules of a generation"), checked: on exactly when gcopy is
+    given, with the class masks of `repeat` (a grammar.BarRepeat over `grammar`), the rows' plans plan (B, ld) int32 with their lengths
+    nplan (B,) int32, the table barcol (B, ld) int32 the device writes (same row stride as plan), the launch's span and the words
+    gbars and gstop"""
+    if gcopy is None:
+        if gbars is not None or gstop is not None:
+            raise MusicXLError(f'{what}: gbars and gstop need gcopy')
+        return [None, 0, None, None, 0, 0, 0, None, None, None]
+    if repeat is None or grammar is None or repeat.grammar is not grammar:
+        raise MusicXLError(f'{what}: gcopy needs repeat, the repeat rule of the grammar (grammar.repeat)')
+    if any(x is None for x in (plan, nplan, barcol, gbars, gstop)):
+        raise MusicXLError(f'{what}: the repeat group needs plan, nplan, barcol, gbars, gcopy and gstop')
+    if V is not None and grammar.vocab_size != int(V):
+        raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
+    for t, name in ((plan, 'plan'), (nplan, 'nplan'), (barcol, 'barcol'), (gbars, 'gbars'), (gcopy, 'gcopy'), (gstop, 'gstop')):
+        _req(t, torch.int32, f'{what} {name}')
+    for t, name in ((plan, 'plan'), (barcol, 'barcol')):           # one width serves both: it is the row stride and nplan's clamp
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous() or t.shape != plan.shape:
+            raise MusicXLError(f'{what}: {name} must be contiguous ({B}, >= 1) int32, plan and barcol of one shape')
+    for t, name in ((nplan, 'nplan'), (gbars, 'gbars'), (gcopy, 'gcopy'), (gstop, 'gstop')):
+        if t.numel() != B or not t.is_contiguous():
+            raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
+    if int(span) not in (0, 1):
+        raise MusicXLError(f'{what}: span is 0 (the whole bar) or 1 (up to the first `leave` token), got {span}')
+    return [_p(plan), plan.shape[1], _p(nplan), _p(barcol), repeat.enter, repeat.leave, int(span), _p(gbars), _p(gcopy), _p(gstop)]
 
 
 def _register_args(what, device, B, V=None, *, register=None, grange=None, gpart=None, gfloor=None, gap=-1) -> list:
@@ -277,7 +317,8 @@ def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=No
 
 def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
                 grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None, melody=None, guide=None,
-                glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None, gfloor=None, gap=-1, do_sample=False,
+                glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None, gfloor=None, gap=-1, repeat=None,
+                plan=None, nplan=None, barcol=None, span=0, gbars=None, gcopy=None, gstop=None, do_sample=False,
                 top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0, out_probs=None):
     """sampler + embedding row of the sampled token (-> emb_out (B, d) bf16) + counter advance, one launch (V <= 2048).
     scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1.
@@ -288,51 +329,61 @@ def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter
     with gkey (B,) int32, the key of every row (< 0 = none), bars the pitches outside it, with or without a grammar; melody (a
     grammar.MelodyGuide, `grammar.guide`) with guide (B, ld) int32, glen, gpos and gforce (B,) int32 feeds rows from their guides;
     register (a grammar.RegisterRule) with grange, gpart and gfloor (B,) int32 and the scalar gap keeps the pitches of every row's open
-    part inside its bounds, with or without a grammar.
+    part inside its bounds, with or without a grammar; repeat (a grammar.BarRepeat, `grammar.repeat`) with plan and barcol (B, ld)
+    int32, nplan, gbars, gcopy and gstop (B,) int32 and the scalar span makes planned bars repeat earlier bars of the row's own `ids`.
     out_probs (B, V) f32, with do_sample: the renormalised distribution the tokens were drawn from (test hook)."""
     B = scores.shape[0]
     force = rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos, gforce,
-                           register, grange, gpart, gfloor, gap)
+                           register, grange, gpart, gfloor, gap, repeat, plan, nplan, barcol, span, gbars, gcopy, gstop)
+    formed = _repeat_args('sample_step', scores.device, B, V, grammar=grammar, **{k: force.pop(k) for k in REPEAT_KEYS if k in force})
     ranged = _register_args('sample_step', scores.device, B, V, **{k: force.pop(k) for k in REGISTER_KEYS if k in force})
     keyed = _key_args('sample_step', scores.device, B, V, in_key=force.pop('in_key'), gkey=force.pop('gkey'))
     guided = _guide_args('sample_step', scores.device, B, V, grammar=grammar, **{k: force.pop(k) for k in GUIDE_KEYS})
-    rules = _rules_args('sample_step', scores.device, B, V, guided=guided[0] is not None, **force)
+    rules = _rules_args('sample_step', scores.device, B, V, guided=guided[0] is not None or formed[0] is not None, **force)
     if out_probs is not None:
         _req(out_probs, torch.float32, 'sample_step out_probs')
         if tuple(out_probs.shape) != (B, int(V)) or not out_probs.is_contiguous():
             raise MusicXLError(f'sample_step: out_probs must be contiguous ({B}, {int(V)}) f32')
-    check(lib().mxl_ranged_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
+    check(lib().mxl_formed_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
                                       int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
                                       float(repetition_penalty if repetition_penalty is not None else 1.0),
                                       float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
-                                      float(scale), _p(counter), *rules, *keyed, *guided, *ranged, _p(out_probs), _stream()),
-          'mxl_ranged_sample_step')
+                                      float(scale), _p(counter), *rules, *keyed, *guided, *ranged, *formed, _p(out_probs), _stream()),
+          'mxl_formed_sample_step')
 
 
 def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None,
-               melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None, gfloor=None, gap=-1):
+               melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None, gfloor=None, gap=-1,
+               repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None, gcopy=None, gstop=None, hist=None):
     """before sample: scores[b, v] = -inf in place for every token a rule bars (mxl_rules_mask).  A rule is applied exactly when its
     state is given: gstate (the grammar in state gstate[b]), gbar and grem (its bar budget), gleft (its bar count), each with
     `grammar` for the tables, gkey (the key rule in key gkey[b]) with `in_key` for its tables, and gpos with gforce, guide, glen and
     `melody` (the guide rule: a row fed from its guide keeps that one token), and gpart with gfloor, grange, gap and `register` (the
-    register rule); stop = (eos, pad, min_length) bars eos while the rows are shorter than min_length.  No launch when nothing is
+    register rule), and gcopy with gbars, gstop, plan, nplan, barcol, span, `repeat` and hist, the (B, ld) int64 ids of the rows (the
+    repeat rule: a row that copies keeps the one token of its own history); stop = (eos, pad, min_length) bars eos while the rows are shorter than min_length.  No launch when nothing is
     given."""
     _req(scores, torch.float32, 'rules_mask scores')
     B = scores.shape[0]
     if scores.shape[1] < V or scores.stride(1) != 1:
         raise MusicXLError('rules_mask: scores must be (B, >= V) with unit column stride')
     rules = _rules_args('rules_mask', scores.device, B, V, stop=stop, grammar=grammar, gstate=gstate, gbar=gbar, grem=grem, gleft=gleft,
-                        guided=gpos is not None)
+                        guided=gpos is not None or gcopy is not None)
+    formed = _repeat_args('rules_mask', scores.device, B, V, grammar=grammar, repeat=repeat, plan=plan, nplan=nplan, barcol=barcol,
+                          span=span, gbars=gbars, gcopy=gcopy, gstop=gstop)
+    if gcopy is not None and (hist is None or hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != B or hist.stride(1) != 1):
+        raise MusicXLError('rules_mask: the repeat group needs hist, the (B, .) int64 ids of the rows')
+    past = [_p(hist), hist.stride(0)] if gcopy is not None else [None, 0]
     keyed = _key_args('rules_mask', scores.device, B, V, in_key=in_key, gkey=gkey)
     guided = _guide_args('rules_mask', scores.device, B, V, grammar=grammar, melody=melody, guide=guide, glen=glen, gpos=gpos, gforce=gforce)
     ranged = _register_args('rules_mask', scores.device, B, V, register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=gap)
-    check(lib().mxl_ranged_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, *keyed, *guided, *ranged, _stream()),
-          'mxl_ranged_rules_mask')
+    check(lib().mxl_formed_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, *keyed, *guided, *ranged, *formed, *past,
+                                      _stream()), 'mxl_formed_rules_mask')
 
 
 def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None,
                   in_key=None, gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None,
-                  gpart=None, gfloor=None, gap=-1):
+                  gpart=None, gfloor=None, gap=-1, repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None, gcopy=None,
+                  gstop=None):
     """after sample + decode_advance: the words given (as rules_mask) move along the token at ids[b, t] in every row that chose it,
     then, with unfinished and alive, that token goes through the stop rule stop = (eos, pad, min_length): rows with unfinished[b] == 0
     get pad and keep their words (mxl_rules_advance).  No launch when nothing is given."""
@@ -340,7 +391,9 @@ def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar
     if ids.dtype != torch.int64:
         raise MusicXLError('rules_advance: ids must be (B, .) int64')
     rules = _rules_args('rules_advance', ids.device, B, stop=stop, unfinished=unfinished, alive=alive, grammar=grammar, gstate=gstate,
-                        gbar=gbar, grem=grem, gleft=gleft, guided=gpos is not None)
+                        gbar=gbar, grem=grem, gleft=gleft, guided=gpos is not None or gcopy is not None)
+    formed = _repeat_args('rules_advance', ids.device, B, grammar=grammar, repeat=repeat, plan=plan, nplan=nplan, barcol=barcol,
+                          span=span, gbars=gbars, gcopy=gcopy, gstop=gstop)
     if grammar is not None and in_key is not None and gkey is not None and grammar.vocab_size != in_key.vocab_size:
         raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the key rule spans {in_key.vocab_size}')
     keyed = _key_args('rules_advance', ids.device, B, in_key=in_key, gkey=gkey)
@@ -351,8 +404,8 @@ def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar
         if V and register.vocab_size != V:
             raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the other rules {V}')
         V = register.vocab_size
-    check(lib().mxl_ranged_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, *rules, *keyed, *guided, *ranged, _stream()),
-          'mxl_ranged_rules_advance')
+    check(lib().mxl_formed_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, *rules, *keyed, *guided, *ranged, *formed, _stream()),
+          'mxl_formed_rules_advance')
 
 
 def key_scan(ids, Tp, in_key, gkey, first_bad, check_from=None):

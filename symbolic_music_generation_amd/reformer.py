@@ -155,7 +155,7 @@ class MyReformerModelWithLMHead(EngineModule):
                  attention_mask: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, max_new_tokens: Optional[int] = None, min_length: Optional[int] = None,
                  grammar=None, n_bars=None, in_key=None, key=None, melody=None, device_scorer: bool = False, register=None,
-                 melody_range=None, bass_range=None, bass_below=None, **unsupported):
+                 melody_range=None, bass_range=None, bass_below=None, form=None, section_bars=None, form_span=None, **unsupported):
         """`model.generate(...)` as the reference drives it (musicnlp/trainer/eval.py:277-333): greedy, or sampling with
         top-k / top-p / typical-p / temperature / repetition penalty (applied, as HF does, to the raw logits); token selection
         runs on the device (the TransfoXL decoder's sampler kernel).
@@ -192,8 +192,13 @@ class MyReformerModelWithLMHead(EngineModule):
         register (a `grammar.RegisterRule`, `tokenizer.register_rule()`) with melody_range / bass_range (an inclusive pair of MIDI
         numbers or one per prompt, None = unconstrained) and bass_below (None or g >= 0 semitones): greedy decoding and sampling in
         which every part keeps its pitches inside its bounds and the bass stays at least g under the lowest melody note of its bar,
-        as MyTransfoXLLMHeadModel.generate; it needs no grammar.  Every search here scores on the host and refuses it."""
-        from .generate import (STOP_CHUNK, RowRules, beam_generate, check_grammar_args, left_pad_counts, plan_search,
+        as MyTransfoXLLMHeadModel.generate; it needs no grammar.  Every search here scores on the host and refuses it.
+
+        form (a string of sections such as 'AABA', a plan, or one of them per prompt, None = no plan; with grammar and eos_token_id,
+        greedy decoding and sampling; no n_bars, melody or min_length beside it) with section_bars (default 1) and form_span ('bar',
+        the default, or 'melody'): song form, as MyTransfoXLLMHeadModel.generate -- a planned bar repeats an earlier bar the row
+        generated, copied from the row's own ids through the mask launch before the sampler and the advance after it."""
+        from .generate import (STOP_CHUNK, RowRules, beam_generate, check_grammar_args, form_config, left_pad_counts, plan_search,
                                resolve_max_length, rules_config, rules_refusal, sample_unfused, sampling_config, stop_config, stop_width)
         from .rf_generate import RFDecoder
         num_beams, num_beam_groups, nrs = num_beams or 1, num_beam_groups or 1, int(num_return_sequences or 1)
@@ -209,6 +214,8 @@ class MyReformerModelWithLMHead(EngineModule):
         search = beams or bool(penalty_alpha and not do_sample)
         if melody is not None and search:
             raise rules_refusal('melody= is')
+        if form is not None and search:
+            raise rules_refusal('form= is')
         if grammar is not None and beams:
             raise rules_refusal('grammar= is', 'beam or group-beam search')
         if n_bars is not None and search:
@@ -222,9 +229,11 @@ class MyReformerModelWithLMHead(EngineModule):
                            top_k=top_k, eos_token_id=eos_token_id, pad_token_id=pad_token_id, config_eos=self.config.eos_token_id,
                            config_pad=self.config.pad_token_id, device_scorer=device_scorer, repetition_penalty=repetition_penalty,
                            renormalize_logits=renormalize_logits, vocab_size=self.config.vocab_size)
+        feed = form_config(form, section_bars, form_span, input_ids.shape[0] if input_ids is not None else 0, grammar, stop, n_bars,
+                           melody, min_length, nrs)
         rules = rules_config(batch=input_ids.shape[0] if input_ids is not None else 0, vocab_size=self.config.vocab_size, stop=stop,
-                             grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody, register=register,
-                             melody_range=melody_range, bass_range=bass_range, bass_below=bass_below, repeat=nrs)
+                             grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody if feed is None else feed,
+                             register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below, repeat=nrs)
         if attention_mask is not None and input_ids is not None and any(left_pad_counts(attention_mask, tuple(input_ids.shape))):
             # LSH buckets are not shift-invariant: a left pad is not an exact no-op here as it is for TransfoXL
             raise MusicXLError(f'{type(self).__name__}.generate does not support padded prompts (attention_mask with zeros); '

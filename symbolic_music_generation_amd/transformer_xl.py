@@ -201,7 +201,8 @@ class MyTransfoXLLMHeadModel(EngineModule):
                  min_length: Optional[int] = None, grammar=None, n_bars=None, in_key=None, key=None, melody=None,
                  device_scorer: bool = False, register=None, melody_range=None, bass_range=None, bass_below=None,
                  kv_cache_dtype: Optional[str] = None, beam_rings: Optional[str] = None,
-                 contrastive_rings: Optional[str] = None, prompt_rings: Optional[str] = None, **unused) -> torch.Tensor:
+                 contrastive_rings: Optional[str] = None, prompt_rings: Optional[str] = None, form=None, section_bars=None,
+                 form_span=None, **unused) -> torch.Tensor:
         """`model.generate(**inputs, **args)` as called at musicnlp/trainer/eval.py:333: the greedy, sample, contrastive and beam
         strategies (eval.py:277-321), beam search in its plain, sampling and diverse-group forms.  `num_return_sequences` expands the
         prompts as HF does (repeat_interleave).  Mode selection follows HF 4.25.1 `generate`: contrastive search when
@@ -278,6 +279,25 @@ class MyTransfoXLLMHeadModel(EngineModule):
         sits in the same sampler launch, in the same place.  It needs no `grammar` and combines with everything `in_key` combines
         with, the device searches included (given an explicit `eos_token_id=`); the host scorers refuse it.
         `generate.check_register` verifies an output.
+
+        `form` (with `grammar` and an explicit `eos_token_id`; greedy decoding and sampling) with `section_bars` (default 1) and
+        `form_span` ('bar', the default, or 'melody'): song form.  A row's generated bars are the bars it opens after its prompt,
+        numbered from 0 (the bar open at the end of the prompt is finished freely and has no number, as `n_bars` counts).  `form` is
+        a string of sections, one character each and `section_bars` bars long -- the first occurrence of a character is free, a
+        later one repeats the first bar by bar, so 'AABA' with `section_bars=2` is the plan [-1, -1, 0, 1, -1, -1, 0, 1] -- or such
+        a plan itself (entry k is -1 or an earlier bar j < k), or a list of one string, plan or None per prompt (repeated per prompt
+        under `num_return_sequences`), where None leaves that row without a plan and without a bar limit.  A repeating bar is not
+        sampled: behind its `<bar>` the row is fed the tokens of the source bar out of its own output -- on the device, inside the
+        sampler launch of the captured step, as the mask "every token but this one is barred", exactly as `melody=` feeds a guide, so
+        no launch and no host round trip is added -- with `form_span='bar'` the whole bar, with 'melody' up to and including its
+        `<bass>`, after which the row writes a new bass under the same melody (with `register=` and `bass_below=`, under it).  The
+        row opens exactly the planned bars and then ends: the plan sets the bar count, so `n_bars`, `melody` and `min_length` are
+        refused beside it (ValueError), as are `section_bars` / `form_span` without `form`, `section_bars < 1`, an empty form, a plan
+        entry outside -1..k-1, a wrong number of forms and any other `form_span`; under `tokenizer.grammar(bar_budget=True)` the row
+        emits eos exactly when its last bar is full.  Copied tokens are not judged by the other rules but move their words; a form
+        without repeats ('ABC') is `n_bars`.  Only generated bars can be sources, never bars of the prompt.  It combines with
+        everything `melody` combines with; `generate.check_form` verifies an output.  Beam, group-beam and contrastive search take no
+        `form`, nor do the sub-word tokenizers, whose grammar carries no repeat rule.
 
         Plain beam search (`num_beams` 2..16, `num_beam_groups=1`, `do_sample=False`) runs with its scorer on the device
         (`generate.beam_search_device`: mxl_beam_step / mxl_beam_reorder inside the captured step) and takes `grammar`, `n_bars` and
@@ -376,7 +396,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
         ValueError.  `MXL_PROMPT_RINGS=shared` sets the default of calls that do not pass the keyword and is ignored where 'shared'
         does not apply."""
         from .generate import (BEAM_MAX, CONTRASTIVE_MAX, XLDecoder, XLDecoderLanes, beam_generate, beam_sample_device,
-                               beam_search_device, check_grammar_args, contrastive_search, contrastive_search_device,
+                               beam_search_device, check_grammar_args, contrastive_search, contrastive_search_device, form_config,
                                group_beam_search_device, left_pad_counts, plan_search, prompt_rings_misfit, prompt_tail_len,
                                resolve_beam_rings, resolve_contrastive_rings, resolve_kv_dtype, resolve_prompt_rings,
                                resolve_max_length,
@@ -402,7 +422,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                            num_beams=num_beams, num_beam_groups=num_beam_groups, do_sample=do_sample, penalty_alpha=penalty_alpha,
                            top_k=top_k, diversity_penalty=diversity_penalty, eos_token_id=eos_token_id, pad_token_id=pad_token_id,
                            config_eos=self.config.eos_token_id, config_pad=self.config.pad_token_id, padded=n_pad is not None,
-                           grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody, device_scorer=device_scorer,
+                           grammar=grammar, n_bars=n_bars, in_key=in_key, key=key, melody=melody, form=form, device_scorer=device_scorer,
                            repetition_penalty=repetition_penalty, renormalize_logits=renormalize_logits,
                            vocab_size=self.config.vocab_size, register=register)
         # (before the fp8 refusal: an explicit 'shared' beside kv_cache_dtype='fp8' is refused for what it asks, wherever it is asked)
@@ -420,8 +440,9 @@ class MyTransfoXLLMHeadModel(EngineModule):
         rings = 'indexed' if fp8_rings else rings
         B0 = input_ids.shape[0]
         ranges = dict(register=register, melody_range=melody_range, bass_range=bass_range, bass_below=bass_below)
+        feed = form_config(form, section_bars, form_span, B0, grammar, stop, n_bars, melody, min_length, num_return_sequences)
         rules = rules_config(batch=B0, vocab_size=self.config.vocab_size, stop=stop, grammar=grammar, n_bars=n_bars, in_key=in_key,
-                             key=key, melody=melody, **ranges, repeat=num_return_sequences)
+                             key=key, melody=melody if feed is None else feed, **ranges, repeat=num_return_sequences)
         if rules.register is None:
             ranges = {}                                     # (a call without the rule hands nothing of it on)
         ends = dict(eos_token_id=plan.eos, pad_token_id=plan.pad)
