@@ -1,5 +1,5 @@
-"""ORACLE-side statement of the Transformer-XL decode-step kernels (test infrastructure, NOT product code): the first 350 lines of
-csrc/decode.hip (decode_embed_kernel, kv_append_kernel, decode_attn_kernel<16 / 32 / 64>, decode_bd_kernel), the mxl_decode_qkv
+"""ORACLE-side statement of the Transformer-XL decode-step kernels (test infrastructure, NOT product code): decode_embed_kernel,
+kv_append_kernel and decode_bd_kernel of csrc/decode.hip, decode_attn_kernel<16 / 32 / 64> of csrc/decode_attn.hip, the mxl_decode_qkv
 epilogue of csrc/gemm_skinny.hip and the composite ops.relattn_decode (csrc/ = symbolic_music_generation_amd/csrc/).  Case tables,
 bf16-exact inputs generated on the CPU from zlib.crc32(case name), and for the two float kernels a reference in two forms:
 

@@ -17,7 +17,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the translation units that hold the kernels of bench.py's roofline group: their hash goes into the record, and bench.py reports
 # the recorded traffic only while it still matches the sources (a changed kernel must be re-measured)
-GROUP_SOURCES = {'train': ['relattn_bwd_fused.hip', 'relattn_drd_phantom.hip', 'relattn_fwd.hip'], 'reformer': ['gemm.hip'], 'decode': ['decode.hip']}
+GROUP_SOURCES = {'train': ['relattn_bwd_fused.hip', 'relattn_drd_phantom.hip', 'relattn_fwd.hip'], 'reformer': ['gemm.hip'],
+                 'decode': ['decode.hip', 'decode_attn.hip', 'decode_attn.h']}
 
 
 def sources_sha16(kind):
@@ -51,7 +52,7 @@ def main(fetch_csv, write_csv, out_json, batch=32, kind='train', prompt_len=256)
            'group_sources': GROUP_SOURCES[kind], 'group_sources_sha16': sources_sha16(kind), 'kernels': out}
     if kind == 'decode':
         # eager decode window (bench.py --mode decode --eager --decode-steps 40): bytes of the kernels of the decode loop per step
-        loop = ['advance_kernel', 'decode_attn_kernel<64>', 'decode_bd_kernel', 'decode_embed_kernel', 'gemm_skinny_kernel',
+        loop = ['advance_kernel', 'decode_attn_kernel<64, false>', 'decode_bd_kernel', 'decode_embed_kernel', 'gemm_skinny_kernel',
                 'ln_res_fwd_kernel<2>', 'ln_res_partial_fwd_kernel<2>', 'logprob_full_kernel', 'sample_kernel', 'sample_step_kernel']
         # one launch per step (round 6: the sampler launch also advances the counters)
         steps = float(out['advance_kernel' if 'advance_kernel' in out else 'sample_step_kernel']['launches'])

@@ -25,7 +25,7 @@
 // Beam-sample (mxl_beam_sample_step) is a third entry of the same kernel: over the `drawn` matrix of beam_sample.hip, with a
 // candidate's score its entry itself; select, walk, copy, reorder and dead rows are the ones above.
 // The rings follow either whole (beam_reorder_kernel) or not at all: beam_owner_follow_kernel keeps a table of which row of its item
-// holds each slot of a row's history, and the attention reads through it (decode_owned.hip).
+// holds each slot of a row's history, and the attention reads through it (decode_attn.hip, decode_fp8.hip).
 #include "common.h"
 #include "beam_key.h"
 #include "musicxl_internal.h"

@@ -8,8 +8,9 @@
 // Never-written slots and the K / V of left-pad columns are zero bytes with e = 0.
 //
 // Writers: kv_append_fp8_kernel / kv_fill_fp8_kernel (kv_append_kernel / kv_fill_kernel of decode.hip with the row quantised on the
-// way).  Reader: decode_attn_fp8_kernel, decode_attn_kernel's contract on half the bytes.
-#include "common.h"
+// way).  Reader: decode_attn_fp8_kernel, decode_attn_kernel's contract (decode_attn.hip) on half the bytes, on the row's own rings or
+// through the owner table of the device beam searches.
+#include "decode_attn.h"
 #include "musicxl_internal.h"
 
 namespace {
@@ -18,6 +19,11 @@ namespace {
 // 16 more output floats per lane, the converted operands) and leaves one workgroup per CU; 12 takes 168 (three per CU, 12 KiB per
 // wave and batch in flight), 8 takes 126 (four per CU)
 constexpr int FP8_ATTN_U = 12;
+// the same under an owner table, where the source row of every load in flight costs registers: 12 takes 182 (two workgroups per CU),
+// 11 takes 168 again, 10 takes 162, 8 takes 128; none of them spills.  11 keeps the three workgroups, and measured (a lane at a full
+// ring, identity table, two passes per build: profiles/beam_fp8_rings.txt) it is 27.4 / 27.6 us against 28.3 / 28.5 for 12 and 27.8 /
+// 27.6 for 8.  The batch depth changes no bit: a lane visits its slots in ascending order whatever it is.
+constexpr int FP8_OWNED_U = 11;
 
 typedef float fp8_f2 __attribute__((ext_vector_type(2)));
 
@@ -125,7 +131,7 @@ __device__ __forceinline__ void fp8_unpack16(const u32x4 w, float (&f)[16]) {
     }
 }
 
-// decode_attn_kernel (decode.hip) on fp8 rings: same grid (head, batch row, ring piece), same pieces, partials, arrival counter and
+// decode_attn_kernel (decode_attn.hip) on fp8 rings: same grid (head, batch row, ring piece), same pieces, partials, arrival counter and
 // merge, same arithmetic contract -- q' = bf16(q + r_w_bias), f32 scores with the bd term, never-written slots as the positional
 // term alone and counted in the denominator, P rounded to bf16 before the P V sum.  A lane still loads 16 bytes, now 16 elements:
 // dh = 16 * LPK, LPK lanes share a key row, 64 / LPK keys per wave instruction, so a batch of U loads covers twice the slots.
@@ -133,11 +139,19 @@ __device__ __forceinline__ void fp8_unpack16(const u32x4 w, float (&f)[16]) {
 // row per (sequence, head)) while the first K batch is in flight; a lane scales its partial dot product by sc[s] before the lane
 // reduction (exact: a power of two) and the score then overwrites sc[s].  V: the softmax pass leaves bf16(p_s) 2^ve[s] in sc[s]
 // (exact as well), and the P V loop multiplies that with the bare fp8 values.
-template <int DH, int U>
+// OWNED (beam search with beam_rings='indexed' on a decoder with kv_dtype='fp8') is decode_attn_kernel's: the 16 K bytes, the 16 V
+// bytes and the two exponents of a written slot s of row b are read from the rings of row (b / nb) * nb + owner[b][s], the table
+// mxl_beam_owner_follow (beam.hip) keeps.  The writers do not change: every row appends to its own ring, which is the slot the follow
+// kernel marks as the row's own.  Everything but the source row of a load is one text, so on rings gathered by the table the plain
+// kernel gives the same bits, and the identity table gives its bits on the same rings (tests/test_beam_fp8_owned_ops_gpu.py).
+// Dynamic LDS: sc [M] f32, the output scratch [4][64] f32 and, OWNED, the row's M owner bytes (M % 16 == 0 and B % nb == 0 are the
+// entry's to check).
+template <int DH, int U, bool OWNED>
 __global__ __launch_bounds__(256) void decode_attn_fp8_kernel(const bf16_t* qkv, const unsigned char* kc8, const signed char* ke,
                                                               const unsigned char* vc8, const signed char* ve, const float* bd,
                                                               const float* rwb, bf16_t* out, const int* t_dev, int B, int H, int M,
-                                                              float scale, float* ws, int* arrived, const int* live) {
+                                                              float scale, float* ws, int* arrived, const int* live,
+                                                              const unsigned char* owner, int nb) {
     constexpr int LPK = DH / 16;         // lanes per key row
     constexpr int KPW = 64 / LPK;        // keys per wave per iteration
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -148,18 +162,15 @@ __global__ __launch_bounds__(256) void decode_attn_fp8_kernel(const bf16_t* qkv,
     const int tid = threadIdx.x, wid = tid >> 6, lane = tid & 63;
     const int c16 = lane % LPK, ksub = lane / LPK;
     const int d = H * DH;
-    if (live != nullptr && live[b] == 0) {               // a finished row: zeros from piece 0, no ring byte read, counter untouched
+    if (live != nullptr && live[b] == 0) {               // a finished row: zeros from piece 0, no ring or owner byte read, counter untouched
         if (blockIdx.z == 0 && tid < DH) out[(size_t)b * d + h * DH + tid] = f2bf(0.f);
         return;
     }
     const int t = *t_dev;
     const int tm = t % M;
-    const int nvalid = t + 1 < M ? t + 1 : M;
-    const int NS = gridDim.z, zi = blockIdx.z;
-    const int piece = NS > 1 ? ((((nvalid + NS - 1) / NS) + 31) & ~31) : nvalid;
-    const int lo = min(zi * piece, nvalid), hi = min(lo + piece, nvalid);
-    const int ppiece = (M - nvalid + NS - 1) / NS;
-    const int plo = min(nvalid + zi * ppiece, M), phi = min(plo + ppiece, M);
+    const int NS = gridDim.z;
+    const RingPiece pc = ring_piece(t, M);
+    const int lo = pc.lo, hi = pc.hi, plo = pc.plo, phi = pc.phi;
 
     float qw[16];
     {
@@ -167,16 +178,35 @@ __global__ __launch_bounds__(256) void decode_attn_fp8_kernel(const bf16_t* qkv,
         const bf16x8 q0 = *reinterpret_cast<const bf16x8*>(qp), q1 = *reinterpret_cast<const bf16x8*>(qp + 8);
 #pragma unroll
         for (int j = 0; j < 8; j++) {
-            qw[j] = bf2f(f2bf(bf2f((bf16_t)q0[j]) + rwb[h * DH + c16 * 16 + j]));
-            qw[8 + j] = bf2f(f2bf(bf2f((bf16_t)q1[j]) + rwb[h * DH + c16 * 16 + 8 + j]));
+            qw[j] = biased_query((bf16_t)q0[j], rwb[h * DH + c16 * 16 + j]);
+            qw[8 + j] = biased_query((bf16_t)q1[j], rwb[h * DH + c16 * 16 + 8 + j]);
         }
     }
-    const size_t ring = ((size_t)b * H + h) * M;
-    const float* bdrow = bd + ring;
+    const float* bdrow = bd + ((size_t)b * H + h) * M;
+    // kb / vb / ker / ver are head h of the row's own rings or, OWNED, of row 0's, and slot_at adds the slot: in slots for the
+    // exponents, times DH in bytes for K and V
+    const size_t ring = ((size_t)(OWNED ? 0 : b) * H + h) * M;
     const unsigned char* kb = kc8 + ring * DH + c16 * 16;
     const unsigned char* vb = vc8 + ring * DH + c16 * 16;
     const signed char* ker = ke + ring;
     const signed char* ver = ve + ring;
+    // OWNED: the row's M owner bytes, staged once behind `red`: 16 bytes per thread.  The K loads and the exponent staging need them,
+    // so the barrier stands before the first K batch is issued
+    const unsigned char* own = reinterpret_cast<const unsigned char*>(red + 4 * 64);
+    if constexpr (OWNED) {
+        const u32x4* from = reinterpret_cast<const u32x4*>(owner + (size_t)b * M);
+        u32x4* to = reinterpret_cast<u32x4*>(red + 4 * 64);
+        for (int i = tid; i < (M >> 4); i += 256) to[i] = from[i];
+        __syncthreads();
+    }
+    // OWNED: an owner byte beyond the item (mxl_beam_owner_follow writes none) is held to the item's last row, so no table sends a
+    // read outside the rings; no owner byte of a never-written slot is looked at
+    const size_t ring_stride = (size_t)H * M;
+    const int item0 = (b / nb) * nb;
+    auto slot_at = [&](int s) -> size_t {
+        if constexpr (OWNED) return (size_t)(item0 + min((int)own[s], nb - 1)) * ring_stride + (size_t)s;
+        else return (size_t)s;
+    };
 
     // pass 1: scores, in double-buffered batches of U key groups as in decode_attn_kernel (non-temporal 16-byte loads)
     float mx = -1e30f;
@@ -188,7 +218,7 @@ __global__ __launch_bounds__(256) void decode_attn_fp8_kernel(const bf16_t* qkv,
             for (int u = 0; u < U; u++) {
                 const int s = s0 + u * 4 * KPW + ksub;
                 const u32x4 z = {0u, 0u, 0u, 0u};
-                kv[u] = (s < hi) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + (size_t)s * DH)) : z;
+                kv[u] = (s < hi) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(kb + slot_at(s) * DH)) : z;
                 int dist = tm - s;
                 if (dist < 0) dist += M;
                 bv[u] = (s < hi && c16 == 0) ? bdrow[dist] : 0.f;
@@ -216,7 +246,7 @@ __global__ __launch_bounds__(256) void decode_attn_fp8_kernel(const bf16_t* qkv,
         constexpr int ST = 4 * KPW * U;
         int s0 = lo + wid * KPW;
         if (s0 < hi) load_k(s0, kA, bA);
-        for (int s = lo + tid; s < hi; s += 256) sc[s] = fp8_pow2((int)ker[s]);      // under the first batch's latency
+        for (int s = lo + tid; s < hi; s += 256) sc[s] = fp8_pow2((int)ker[slot_at(s)]);      // under the first batch's latency
         __syncthreads();
         for (; s0 < hi; s0 += 2 * ST) {
             if (s0 + ST < hi) load_k(s0 + ST, kB, bB);
@@ -240,7 +270,7 @@ __global__ __launch_bounds__(256) void decode_attn_fp8_kernel(const bf16_t* qkv,
         for (int u = 0; u < U; u++) {
             const int s = s0 + u * 4 * KPW + ksub;
             const u32x4 z = {0u, 0u, 0u, 0u};
-            vv[u] = (s < hi) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + (size_t)s * DH)) : z;
+            vv[u] = (s < hi) ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(vb + slot_at(s) * DH)) : z;
         }
     };
     if (lo + wid * KPW < hi) load_v(lo + wid * KPW, vA);
@@ -251,7 +281,7 @@ __global__ __launch_bounds__(256) void decode_attn_fp8_kernel(const bf16_t* qkv,
     float sum = 0.f;
     for (int s = lo + tid; s < hi; s += 256) {
         const float pv = __expf(sc[s] - mx);
-        sc[s] = bf2f(f2bf(pv)) * fp8_pow2((int)ver[s]);  // the P V operand: P rounded to bf16, times the row's 2^e
+        sc[s] = bf2f(f2bf(pv)) * fp8_pow2((int)ver[slot_at(s)]);      // the P V operand: P rounded to bf16, times the slot's 2^e
         sum += pv;
     }
     for (int s = plo + tid; s < phi; s += 256) sum += __expf(sc[s] - mx);      // (v = 0 there: only the denominator)
@@ -287,50 +317,13 @@ __global__ __launch_bounds__(256) void decode_attn_fp8_kernel(const bf16_t* qkv,
             }
         }
     }
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-#pragma unroll
-        for (int off = LPK; off < 64; off <<= 1) o[j] += __shfl_xor(o[j], off, 64);
-    }
-    if (ksub == 0) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) red[wid * DH + c16 * 16 + j] = o[j];
-    }
+    reduce_o<LPK>(o, red + wid * DH + c16 * 16, ksub);
     __syncthreads();
     if (NS == 1) {
-        if (tid < DH) {
-            const float v = (red[tid] + red[DH + tid] + red[2 * DH + tid] + red[3 * DH + tid]) * inv;
-            out[(size_t)b * d + h * DH + tid] = f2bf(v);
-        }
+        if (tid < DH) out[(size_t)b * d + h * DH + tid] = f2bf(red_sum(red, DH, tid) * inv);
         return;
     }
-    // ---- ring pieces: partials as agent-scope stores, the last arrival merges in piece order (decode_attn_kernel)
-    float* wsp = ws + ((size_t)b * H + h) * NS * (DH + 2);
-    if (tid < DH)
-        __hip_atomic_store(wsp + zi * (DH + 2) + tid, red[tid] + red[DH + tid] + red[2 * DH + tid] + red[3 * DH + tid], __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) {
-        __hip_atomic_store(wsp + zi * (DH + 2) + DH, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(wsp + zi * (DH + 2) + DH + 1, wred[4] + wred[5] + wred[6] + wred[7], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    __shared__ int s_last;
-    if (tid == 0) s_last = (__hip_atomic_fetch_add(arrived + (size_t)b * H + h, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == NS - 1) ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
-    if (tid < DH) {
-        float m = -1e30f;
-        for (int k = 0; k < NS; k++) m = fmaxf(m, __hip_atomic_load(wsp + k * (DH + 2) + DH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        float num = 0.f, den = 0.f;
-        for (int k = 0; k < NS; k++) {
-            const float a = __expf(__hip_atomic_load(wsp + k * (DH + 2) + DH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - m);
-            num += a * __hip_atomic_load(wsp + k * (DH + 2) + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            den += a * __hip_atomic_load(wsp + k * (DH + 2) + DH + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        out[(size_t)b * d + h * DH + tid] = f2bf(num / den);
-    }
-    if (tid == 0) __hip_atomic_store(arrived + (size_t)b * H + h, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    pieces_tail<DH>(ws, arrived, b, h, H, red, mx, wred + 4, out);
 }
 
 }  // namespace
@@ -362,21 +355,21 @@ extern "C" int mxl_kv_fill_fp8(const void* qkv, void* kc8, void* ke, void* vc8, 
     return MXL_OK;
 }
 
-extern "C" int mxl_relattn_decode_fp8(const void* qkv, const void* kc8, const void* ke, const void* vc8, const void* ve,
-                                      const float* bd, const float* r_w_bias, void* out, const int* t_dev, int B, int H, int dh, int M,
-                                      float scale, int pieces, float* ws, int* arrived, const int* unfinished, void* stream) {
-    MXL_CHECK_ARG(pieces >= 1 && pieces <= 8);
-    if (pieces > 1) MXL_CHECK_ARG(ws && arrived);
-    MXL_CHECK_ARG(qkv && kc8 && ke && vc8 && ve && bd && r_w_bias && out && t_dev && B > 0 && B <= 65535 && H > 0 && M > 0);
-    const size_t shm = (size_t)M * 4 + 4 * 64 * 4;
+namespace {
+
+template <bool OWNED>
+int relattn_decode_fp8_launch(const void* qkv, const void* kc8, const void* ke, const void* vc8, const void* ve, const void* owner, int nb,
+                              const float* bd, const float* r_w_bias, void* out, const int* t_dev, int B, int H, int dh, int M, float scale,
+                              int pieces, float* ws, int* arrived, const int* live, size_t shm, void* stream) {
     MXL_CHECK_ARG(shm <= 64 * 1024);
     if (dh != 16 && dh != 32 && dh != 64) return MXL_EUNSUPPORTED;
     MXL_CHECK_ARG(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)kc8 % 16) == 0 && ((uintptr_t)vc8 % 16) == 0);
     dim3 grid(H, B, pieces);
     hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(DH) hipLaunchKernelGGL((decode_attn_fp8_kernel<DH, FP8_ATTN_U>), grid, dim3(256), shm, s, (const bf16_t*)qkv,           \
-                                      (const unsigned char*)kc8, (const signed char*)ke, (const unsigned char*)vc8, (const signed char*)ve, \
-                                      bd, r_w_bias, (bf16_t*)out, t_dev, B, H, M, scale, ws, arrived, unfinished)
+#define LAUNCH(DH) hipLaunchKernelGGL((decode_attn_fp8_kernel<DH, OWNED ? FP8_OWNED_U : FP8_ATTN_U, OWNED>), grid, dim3(256), shm, s,        \
+                                      (const bf16_t*)qkv, (const unsigned char*)kc8, (const signed char*)ke, (const unsigned char*)vc8,     \
+                                      (const signed char*)ve, bd, r_w_bias, (bf16_t*)out, t_dev, B, H, M, scale, ws, arrived, live,         \
+                                      (const unsigned char*)owner, nb)
     switch (dh) {
         case 16: LAUNCH(16); break;
         case 32: LAUNCH(32); break;
@@ -385,4 +378,28 @@ extern "C" int mxl_relattn_decode_fp8(const void* qkv, const void* kc8, const vo
 #undef LAUNCH
     MXL_LAUNCH_CHECK();
     return MXL_OK;
+}
+
+}  // namespace
+
+extern "C" int mxl_relattn_decode_fp8(const void* qkv, const void* kc8, const void* ke, const void* vc8, const void* ve,
+                                      const float* bd, const float* r_w_bias, void* out, const int* t_dev, int B, int H, int dh, int M,
+                                      float scale, int pieces, float* ws, int* arrived, const int* unfinished, void* stream) {
+    MXL_CHECK_ARG(pieces >= 1 && pieces <= 8);
+    if (pieces > 1) MXL_CHECK_ARG(ws && arrived);
+    MXL_CHECK_ARG(qkv && kc8 && ke && vc8 && ve && bd && r_w_bias && out && t_dev && B > 0 && B <= 65535 && H > 0 && M > 0);
+    return relattn_decode_fp8_launch<false>(qkv, kc8, ke, vc8, ve, nullptr, 1, bd, r_w_bias, out, t_dev, B, H, dh, M, scale, pieces, ws,
+                                            arrived, unfinished, (size_t)M * 4 + 4 * 64 * 4, stream);
+}
+
+extern "C" int mxl_relattn_decode_fp8_owned(const void* qkv, const void* kc8, const void* ke, const void* vc8, const void* ve,
+                                            const void* owner, int nb, const float* bd, const float* r_w_bias, void* out,
+                                            const int* t_dev, int B, int H, int dh, int M, float scale, int pieces, float* ws,
+                                            int* arrived, const int* unfinished, void* stream) {
+    MXL_CHECK_ARG(qkv && kc8 && ke && vc8 && ve && owner && bd && r_w_bias && out && t_dev && ((uintptr_t)owner % 16) == 0);
+    MXL_CHECK_ARG(nb >= 1 && nb <= 16 && B > 0 && B <= 65535 && (B % nb) == 0 && H > 0 && M > 0 && (M % 16) == 0);
+    MXL_CHECK_ARG(pieces >= 1 && pieces <= 8);
+    if (pieces > 1) MXL_CHECK_ARG(ws && arrived);
+    return relattn_decode_fp8_launch<true>(qkv, kc8, ke, vc8, ve, owner, nb, bd, r_w_bias, out, t_dev, B, H, dh, M, scale, pieces, ws,
+                                           arrived, unfinished, (size_t)M * 4 + 4 * 64 * 4 + (size_t)M, stream);
 }

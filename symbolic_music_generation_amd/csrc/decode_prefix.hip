@@ -25,21 +25,13 @@
 // `unfinished` is per row here (the rows of a prompt finish on their own): a finished row reads no tail byte and leaves zeros, a group
 // without a live row reads nothing at all.  Inside a live group a finished query still rides along on the prompt fragments the others
 // need -- its numbers are dropped at the store.
-#include "common.h"
+#include "decode_attn.h"
 #include "musicxl_internal.h"
 
 namespace {
 
-constexpr int PF_LDS_MAX = 160 * 1024;      // LDS of a gfx950 CU
-
-// score slots of a piece, as decode_shared.hip counts them: all M in one piece, else ceil(M / pieces) + 34, a multiple of 4
-inline int prefix_cap(int M, int pieces) {
-    const int c = pieces > 1 ? (M + pieces - 1) / pieces + 34 : M;
-    return ((c < M ? c : M) + 3) & ~3;
-}
-inline int prefix_group(int n) { return n <= 4 ? 4 : 8; }
-// scores [G][cap] f32 and the output scratch [4][G][dh] f32: decode_shared's G * (cap * 4 + 20 * dh) without its G * 4 * dh of own k / v
-inline size_t prefix_lds(int G, int dh, int cap) { return (size_t)G * ((size_t)cap * 4 + 4 * dh * 4); }
+// scores [G][cap] f32 and the output scratch [4][G][dh] f32: decode_shared's without its G * 4 * dh bytes of own k / v
+inline size_t prefix_lds(int G, int dh, int cap) { return group_lds(G, dh, cap, 0); }
 
 // grid (head, prompt * groups + group, ring piece), 256 threads.  A group past the last row of a prompt (n % G != 0) runs its spare
 // queries on the prompt's last row and writes nothing for them.
@@ -61,11 +53,10 @@ __global__ __launch_bounds__(256, 2) void decode_attn_prefix_kernel(const bf16_t
     const int d = H * DH;
     const int nact = min(G, n - g0);                                 // queries of this group that are rows
     const int row0 = b * n + g0;
-    auto row_of = [&](int g) { return b * n + min(g0 + g, n - 1); };
     // the live rows of the group, one bit per query
     unsigned alive = 0;
 #pragma unroll
-    for (int g = 0; g < G; g++) alive |= (live == nullptr || live[row_of(g)] != 0) ? 1u << g : 0u;
+    for (int g = 0; g < G; g++) alive |= (live == nullptr || live[group_row(b, n, g0, g)] != 0) ? 1u << g : 0u;
     if (alive == 0) {                                                // no live row: no ring byte is read, piece 0 leaves zeros
         if (blockIdx.z == 0)
             for (int i = tid; i < nact * DH; i += 256) out[(size_t)(row0 + i / DH) * d + h * DH + i % DH] = f2bf(0.f);
@@ -73,13 +64,9 @@ __global__ __launch_bounds__(256, 2) void decode_attn_prefix_kernel(const bf16_t
     }
     const int t = *t_dev, Tp = *t0_dev;
     const int tm = t % M;
-    const int nvalid = t + 1 < M ? t + 1 : M;
-    // this piece's written slots [lo, hi) and never-written slots [plo, phi), as decode_attn_kernel cuts them
+    const RingPiece pc = ring_piece(t, M);
+    const int lo = pc.lo, hi = pc.hi, plo = pc.plo, phi = pc.phi;
     const int NS = gridDim.z, zi = blockIdx.z;
-    const int piece = NS > 1 ? ((((nvalid + NS - 1) / NS) + 31) & ~31) : nvalid;
-    const int lo = min(zi * piece, nvalid), hi = min(lo + piece, nvalid);
-    const int ppiece = (M - nvalid + NS - 1) / NS;
-    const int plo = min(nvalid + zi * ppiece, M), phi = min(plo + ppiece, M);
     const int nw = hi - lo;                                          // scores: written slot s at s - lo, never-written sp at nw + sp - plo
     // the tail slots: the nt slots that end at tm going round the ring (distance to tm below nt).  In ascending slot order the
     // written slots are three runs [lo, cx) [cx, cy) [cy, hi) of alternating source, the first one from the tail iff `tail_first`
@@ -97,15 +84,15 @@ __global__ __launch_bounds__(256, 2) void decode_attn_prefix_kernel(const bf16_t
     float qw[G][8];
 #pragma unroll
     for (int g = 0; g < G; g++) {
-        const bf16x8 qv = *reinterpret_cast<const bf16x8*>(qkv + (size_t)row_of(g) * 3 * d + h * DH + c8 * 8);
+        const bf16x8 qv = *reinterpret_cast<const bf16x8*>(qkv + (size_t)group_row(b, n, g0, g) * 3 * d + h * DH + c8 * 8);
 #pragma unroll
-        for (int j = 0; j < 8; j++) qw[g][j] = bf2f(f2bf(bf2f((bf16_t)qv[j]) + rwb[h * DH + c8 * 8 + j]));
+        for (int j = 0; j < 8; j++) qw[g][j] = biased_query((bf16_t)qv[j], rwb[h * DH + c8 * 8 + j]);
     }
     // the positional terms of the written slots wait where the score will go (decode_shared.hip)
     const float* bdh = bd + (size_t)h * M;
     size_t bdoff[G];
 #pragma unroll
-    for (int g = 0; g < G; g++) bdoff[g] = (size_t)row_of(g) * H * M;
+    for (int g = 0; g < G; g++) bdoff[g] = (size_t)group_row(b, n, g0, g) * H * M;
 #pragma clang loop vectorize(disable) unroll(disable)
     for (int i = tid; i < nw; i += 256) {
         int dist = tm - (lo + i);
@@ -117,7 +104,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_prefix_kernel(const bf16_t
     const bf16_t* kb = kp + ((size_t)b * H + h) * M * DH + c8 * 8;     // head-major ring of the prompt: rows are DH apart
     const bf16_t* vb = vp + ((size_t)b * H + h) * M * DH + c8 * 8;
     // head h of query g's tail ring: a workgroup-uniform base, to which a load adds a 32-bit lane offset (the scalar-base form)
-    auto tail_of = [&](const bf16_t* ring, int g) { return ring + ((size_t)row_of(g) * H + h) * Mt * DH; };
+    auto tail_of = [&](const bf16_t* ring, int g) { return ring + ((size_t)group_row(b, n, g0, g) * H + h) * Mt * DH; };
 
     // batch depth of the prompt runs: what the registers beside G queries and the G tail fragments leave without scratch (G = 8: 239
     // registers at depth 2, spills at 4; G = 4: 217 at depth 4).  The depth changes no bit: a lane visits its slots in ascending order.
@@ -199,17 +186,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_prefix_kernel(const bf16_t
             }
         }
     }
-#pragma clang loop vectorize(disable) unroll(disable)
-    for (int sp = plo + tid; sp < phi; sp += 256) {      // the never-written slots: score = scale * BD[distance]
-        int dist = tm - sp;
-        if (dist < 0) dist += M;
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            const float a = bdh[bdoff[g] + dist] * scale;
-            sc[g * cap + nw + sp - plo] = a;
-            mx[g] = fmaxf(mx[g], a);
-        }
-    }
+    group_score_unwritten<G>(sc, cap, bdh, bdoff, tm, nw, plo, phi, M, scale, mx);
 #pragma unroll
     for (int g = 0; g < G; g++) {
         const float m = wave_max(mx[g]);
@@ -251,11 +228,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_prefix_kernel(const bf16_t
 #pragma unroll
         for (int j = 0; j < 8; j++) o[g][j] = 0.f;
     {
-        auto add = [&](int g, const bf16x8& vv, int s, bool in) {
-            const float pv = in ? bf2f(f2bf(sc[g * cap + s - lo])) : 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; j++) o[g][j] += pv * bf2f((bf16_t)vv[j]);
-        };
+        auto add = [&](int g, const bf16x8& vv, int s, bool in) { group_add(sc, g * cap + s - lo, o[g], vv, in); };
 #pragma unroll 1
         for (int run = 0; run < 3; run++) {
             const int va = run == 0 ? lo : (run == 1 ? cx : cy), ve = run == 0 ? cx : (run == 1 ? cy : hi);
@@ -338,13 +311,12 @@ __global__ __launch_bounds__(256, 2) void decode_attn_prefix_kernel(const bf16_t
     for (int i = tid; i < nact * DH; i += 256) {
         const int g = i / DH, e = i % DH;
         if ((alive >> g) & 1)
-            __hip_atomic_store(ws + ((size_t)(row0 + g) * H + h) * NS * (DH + 2) + zi * (DH + 2) + e, red_of(g, e), __ATOMIC_RELAXED,
-                               __HIP_MEMORY_SCOPE_AGENT);
+            MXL_AGENT_STORE(ws + ((size_t)(row0 + g) * H + h) * NS * (DH + 2) + zi * (DH + 2) + e, red_of(g, e));
     }
     if (tid < nact && ((alive >> tid) & 1)) {
         float* wsp = ws + ((size_t)(row0 + tid) * H + h) * NS * (DH + 2) + zi * (DH + 2);
-        __hip_atomic_store(wsp + DH, max_of(tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(wsp + DH + 1, sum_of(tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        MXL_AGENT_STORE(wsp + DH, max_of(tid));
+        MXL_AGENT_STORE(wsp + DH + 1, sum_of(tid));
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -360,16 +332,16 @@ __global__ __launch_bounds__(256, 2) void decode_attn_prefix_kernel(const bf16_t
         }
         const float* wsp = ws + ((size_t)(row0 + g) * H + h) * NS * (DH + 2);
         float m = -1e30f;
-        for (int k = 0; k < NS; k++) m = fmaxf(m, __hip_atomic_load(wsp + k * (DH + 2) + DH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        for (int k = 0; k < NS; k++) m = fmaxf(m, MXL_AGENT_LOAD(wsp + k * (DH + 2) + DH));
         float num = 0.f, den = 0.f;
         for (int k = 0; k < NS; k++) {
-            const float a = __expf(__hip_atomic_load(wsp + k * (DH + 2) + DH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - m);
-            num += a * __hip_atomic_load(wsp + k * (DH + 2) + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            den += a * __hip_atomic_load(wsp + k * (DH + 2) + DH + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const float a = __expf(MXL_AGENT_LOAD(wsp + k * (DH + 2) + DH) - m);
+            num += a * MXL_AGENT_LOAD(wsp + k * (DH + 2) + e);
+            den += a * MXL_AGENT_LOAD(wsp + k * (DH + 2) + DH + 1);
         }
         out[(size_t)(row0 + g) * d + h * DH + e] = f2bf(num / den);
     }
-    if (tid == 0) __hip_atomic_store(arrived + (size_t)row0 * H + h, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) MXL_AGENT_STORE(arrived + (size_t)row0 * H + h, 0);
 }
 
 // qr[b] = q + r_r_bias as kv_append_kernel writes it, and tail slot (t - t0) mod Mt of row b <- (k, v) of the (B, 3d) qkv rows: one
@@ -399,30 +371,11 @@ __global__ void kv_append_tail_kernel(const bf16_t* qkv, bf16_t* kt, bf16_t* vt,
     *reinterpret_cast<u32x4*>(vt + o) = v;
 }
 
-template <int DH, int G>
-int launch_prefix(const void* qkv, const void* kp, const void* vp, const void* kt, const void* vt, const float* bd,
-                  const float* r_w_bias, void* out, const int* t_dev, const int* t0_dev, int B0, int n, int H, int M, int Mt, float scale,
-                  int pieces, float* ws, int* arrived, const int* live, int cap, size_t shm, hipStream_t s) {
-    static size_t attr = 64 * 1024;         // dynamic LDS this instantiation may take so far
-    if (shm > attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_attn_prefix_kernel<DH, G>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr = shm;
-    }
-    const int ngroups = (n + G - 1) / G;
-    hipLaunchKernelGGL((decode_attn_prefix_kernel<DH, G>), dim3(H, B0 * ngroups, pieces), dim3(256), shm, s, (const bf16_t*)qkv,
-                       (const bf16_t*)kp, (const bf16_t*)vp, (const bf16_t*)kt, (const bf16_t*)vt, bd, r_w_bias, (bf16_t*)out, t_dev,
-                       t0_dev, n, ngroups, H, M, Mt, scale, ws, arrived, live, cap);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
 }  // namespace
 
 extern "C" size_t mxl_relattn_decode_prefix_lds_bytes(int n, int dh, int M, int pieces) {
     if (n < 2 || dh <= 0 || M <= 0 || pieces < 1 || pieces > 8) return 0;
-    return prefix_lds(prefix_group(n), dh, prefix_cap(M, pieces));
+    return prefix_lds(group_size(n), dh, group_cap(M, pieces));
 }
 
 extern "C" int mxl_relattn_decode_prefix(const void* qkv, const void* kprompt, const void* vprompt, const void* ktail, const void* vtail,
@@ -435,12 +388,14 @@ extern "C" int mxl_relattn_decode_prefix(const void* qkv, const void* kprompt, c
     MXL_CHECK_ARG(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)kprompt % 16) == 0 && ((uintptr_t)vprompt % 16) == 0 &&
                   ((uintptr_t)ktail % 16) == 0 && ((uintptr_t)vtail % 16) == 0);
     if (dh != 16 && dh != 32 && dh != 64) return MXL_EUNSUPPORTED;
-    const int G = prefix_group(n), cap = prefix_cap(M, pieces);
+    const int G = group_size(n), cap = group_cap(M, pieces);
     const size_t shm = prefix_lds(G, dh, cap);
-    MXL_CHECK_ARG(shm <= (size_t)PF_LDS_MAX && (long long)B0 * ((n + G - 1) / G) <= 65535);
+    MXL_CHECK_ARG(shm <= (size_t)GROUP_LDS_MAX && (long long)B0 * ((n + G - 1) / G) <= 65535);
     hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(DH, GG) return launch_prefix<DH, GG>(qkv, kprompt, vprompt, ktail, vtail, bd, r_w_bias, out, t_dev, t0_dev, B0, n, H, M, Mt, \
-                                                    scale, pieces, ws, arrived, unfinished, cap, shm, s)
+    const int ngroups = (n + G - 1) / G;
+#define LAUNCH(DH, GG) return launch_big_lds<&decode_attn_prefix_kernel<DH, GG>>(                                                              \
+        dim3(H, B0 * ngroups, pieces), shm, s, (const bf16_t*)qkv, (const bf16_t*)kprompt, (const bf16_t*)vprompt, (const bf16_t*)ktail,      \
+        (const bf16_t*)vtail, bd, r_w_bias, (bf16_t*)out, t_dev, t0_dev, n, ngroups, H, M, Mt, scale, ws, arrived, unfinished, cap)
     if (G == 4) {
         switch (dh) {
             case 16: LAUNCH(16, 4);

@@ -8,7 +8,7 @@
 //                              row's own qkv row, the ring's slot t mod M is never read
 //   mxl_kv_commit_shared       after the pick: the stash of row b*K + sel[b] goes into slot t mod M of ring b, all layers in one launch
 //
-// The attention kernel is decode_attn_kernel of decode.hip run for G queries at once.  Per query nothing moves: bf16(q + r_w_bias),
+// The attention kernel is decode_attn_kernel of decode_attn.hip run for G queries at once.  Per query nothing moves: bf16(q + r_w_bias),
 // the f32 dot in the same lane order, the same slot-to-lane assignment (a lane's slots are lo + wid*KPW + ksub + m*4*KPW, whatever the
 // batch depth), the same pieces and merge order, P rounded to bf16 before P.V -- so every sum adds what it adds there in the order it adds
 // it there, and the output of row b*K + k equals, bit for bit, mxl_relattn_decode_split_live's at the same `pieces` on K copies of ring
@@ -25,23 +25,13 @@
 // Measured (profiles/contrastive_shared_rings.txt): the launch is bound by its per-query vector and LDS work, not by HBM -- at a full
 // ring it reads at 1.2 - 1.3 TB/s where the launch on the copies streams 6.6 -- so a second read of the ring costs little, and the
 // next step is fewer instructions per query and slot (the MFMA form, which changes the order of the sums), not a larger G.
-#include "common.h"
+#include "decode_attn.h"
 #include "musicxl_internal.h"
 
 namespace {
 
 constexpr int SH_KMAX = 32;
-constexpr int SH_LDS_MAX = 160 * 1024;      // LDS of a gfx950 CU
-
-// score slots a piece needs at most: its written slots [lo, hi) and its never-written slots [plo, phi) of decode_attn_kernel.
-// One piece: all M.  NS pieces: hi - lo <= ceil(nvalid / NS) + 31 and phi - plo <= ceil((M - nvalid) / NS), and the two ceilings
-// sum to less than M / NS + 2; never more than M.  A multiple of 4, so that what follows the scores in LDS stays 16-byte aligned.
-inline int shared_cap(int M, int pieces) {
-    const int c = pieces > 1 ? (M + pieces - 1) / pieces + 34 : M;
-    return ((c < M ? c : M) + 3) & ~3;
-}
-inline int shared_group(int K) { return K <= 4 ? 4 : 8; }
-inline size_t shared_lds(int G, int dh, int cap) { return (size_t)G * ((size_t)cap * 4 + 4 * dh * 4 + 2 * dh * 2); }
+inline size_t shared_lds(int G, int dh, int cap) { return group_lds(G, dh, cap, 2 * dh * 2); }      // (the queries' own k / v)
 
 // grid (head, prompt * groups + group, ring piece), 256 threads; dynamic LDS: scores [G][cap] f32, the output scratch [4][G][DH] f32,
 // the queries' own k / v [G][2][DH] bf16.  A group past the last candidate (K % G != 0) runs its spare queries on the prompt's last
@@ -64,7 +54,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_shared_kernel(const bf16_t
     const int d = H * DH;
     const int nact = min(G, K - g0);                                 // queries of this group that are candidates
     const int row0 = b * K + g0;
-    auto row_of = [&](int g) { return b * K + min(g0 + g, K - 1); };
+    auto row_of = [&](int g) { return group_row(b, K, g0, g); };      // (a lambda: called directly, the row changes the schedule)
     // a finished sequence (live[b*K] == 0; its K rows finish together): no ring byte is read, piece 0 leaves zeros
     if (live != nullptr && live[b * K] == 0) {
         if (blockIdx.z == 0)
@@ -73,13 +63,9 @@ __global__ __launch_bounds__(256, 2) void decode_attn_shared_kernel(const bf16_t
     }
     const int t = *t_dev;
     const int tm = t % M;
-    const int nvalid = t + 1 < M ? t + 1 : M;
-    // this piece's written slots [lo, hi) and never-written slots [plo, phi), as decode_attn_kernel cuts them
     const int NS = gridDim.z, zi = blockIdx.z;
-    const int piece = NS > 1 ? ((((nvalid + NS - 1) / NS) + 31) & ~31) : nvalid;
-    const int lo = min(zi * piece, nvalid), hi = min(lo + piece, nvalid);
-    const int ppiece = (M - nvalid + NS - 1) / NS;
-    const int plo = min(nvalid + zi * ppiece, M), phi = min(plo + ppiece, M);
+    const RingPiece pc = ring_piece(t, M);
+    const int lo = pc.lo, hi = pc.hi, plo = pc.plo, phi = pc.phi;
     const int nw = hi - lo;                                          // scores: written slot s at s - lo, never-written sp at nw + sp - plo
 
     float qw[G][8];
@@ -87,7 +73,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_shared_kernel(const bf16_t
     for (int g = 0; g < G; g++) {
         const bf16x8 qv = *reinterpret_cast<const bf16x8*>(qkv + (size_t)row_of(g) * 3 * d + h * DH + c8 * 8);
 #pragma unroll
-        for (int j = 0; j < 8; j++) qw[g][j] = bf2f(f2bf(bf2f((bf16_t)qv[j]) + rwb[h * DH + c8 * 8 + j]));
+        for (int j = 0; j < 8; j++) qw[g][j] = biased_query((bf16_t)qv[j], rwb[h * DH + c8 * 8 + j]);
     }
     // the step's own k / v of every query, and the positional terms of the written slots (decode_attn_kernel carries them in
     // registers beside the K batch; here they wait where the score will go)
@@ -168,17 +154,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_shared_kernel(const bf16_t
             for (int g = 0; g < G; g++) score(g, *reinterpret_cast<const bf16x8*>(own + (g * 2) * DH + c8 * 8), tm, true);
         }
     }
-#pragma clang loop vectorize(disable) unroll(disable)
-    for (int sp = plo + tid; sp < phi; sp += 256) {      // the never-written slots: score = scale * BD[distance]
-        int dist = tm - sp;
-        if (dist < 0) dist += M;
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-            const float a = bdh[bdoff[g] + dist] * scale;
-            sc[g * cap + nw + sp - plo] = a;
-            mx[g] = fmaxf(mx[g], a);
-        }
-    }
+    group_score_unwritten<G>(sc, cap, bdh, bdoff, tm, nw, plo, phi, M, scale, mx);
     // pass 2 walks the written slots in two ranges, [lo, tm) and (tm, hi), with the step's slot between them: a lane adds its
     // slots in ascending order there as here, and the lane that owns slot tm adds that term from the query's own v in its place.
     // What the cut changes is where lanes run `o += 0 * 0` for slots outside the range, which leaves o as it is.
@@ -236,11 +212,7 @@ __global__ __launch_bounds__(256, 2) void decode_attn_shared_kernel(const bf16_t
 #pragma unroll
         for (int j = 0; j < 8; j++) o[g][j] = 0.f;
     {
-        auto add = [&](int g, const bf16x8& vv, int s, bool in) {
-            const float pv = in ? bf2f(f2bf(sc[g * cap + s - lo])) : 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; j++) o[g][j] += pv * bf2f((bf16_t)vv[j]);
-        };
+        auto add = [&](int g, const bf16x8& vv, int s, bool in) { group_add(sc, g * cap + s - lo, o[g], vv, in); };
         auto use_v = [&](int s0, const bf16x8 (&vv)[U]) {
 #pragma unroll
             for (int u = 0; u < U; u++) {
@@ -299,13 +271,12 @@ __global__ __launch_bounds__(256, 2) void decode_attn_shared_kernel(const bf16_t
     // the group shares the arrival counter of its first row, and its last piece merges every query in piece order
     for (int i = tid; i < nact * DH; i += 256) {
         const int g = i / DH, e = i % DH;
-        __hip_atomic_store(ws + ((size_t)(row0 + g) * H + h) * NS * (DH + 2) + zi * (DH + 2) + e, red_of(g, e), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+        MXL_AGENT_STORE(ws + ((size_t)(row0 + g) * H + h) * NS * (DH + 2) + zi * (DH + 2) + e, red_of(g, e));
     }
     if (tid < nact) {
         float* wsp = ws + ((size_t)(row0 + tid) * H + h) * NS * (DH + 2) + zi * (DH + 2);
-        __hip_atomic_store(wsp + DH, max_of(tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(wsp + DH + 1, sum_of(tid), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        MXL_AGENT_STORE(wsp + DH, max_of(tid));
+        MXL_AGENT_STORE(wsp + DH + 1, sum_of(tid));
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -317,16 +288,16 @@ __global__ __launch_bounds__(256, 2) void decode_attn_shared_kernel(const bf16_t
         const int g = i / DH, e = i % DH;
         const float* wsp = ws + ((size_t)(row0 + g) * H + h) * NS * (DH + 2);
         float m = -1e30f;
-        for (int k = 0; k < NS; k++) m = fmaxf(m, __hip_atomic_load(wsp + k * (DH + 2) + DH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        for (int k = 0; k < NS; k++) m = fmaxf(m, MXL_AGENT_LOAD(wsp + k * (DH + 2) + DH));
         float num = 0.f, den = 0.f;
         for (int k = 0; k < NS; k++) {
-            const float a = __expf(__hip_atomic_load(wsp + k * (DH + 2) + DH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - m);
-            num += a * __hip_atomic_load(wsp + k * (DH + 2) + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            den += a * __hip_atomic_load(wsp + k * (DH + 2) + DH + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const float a = __expf(MXL_AGENT_LOAD(wsp + k * (DH + 2) + DH) - m);
+            num += a * MXL_AGENT_LOAD(wsp + k * (DH + 2) + e);
+            den += a * MXL_AGENT_LOAD(wsp + k * (DH + 2) + DH + 1);
         }
         out[(size_t)(row0 + g) * d + h * DH + e] = f2bf(num / den);
     }
-    if (tid == 0) __hip_atomic_store(arrived + (size_t)row0 * H + h, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) MXL_AGENT_STORE(arrived + (size_t)row0 * H + h, 0);
 }
 
 // qr[b] = q + r_r_bias as kv_append_kernel writes it, and stash[b] = (k, v) of the (B, 3d) qkv rows: one thread per 8 elements
@@ -365,30 +336,11 @@ __global__ __launch_bounds__(256) void kv_commit_shared_kernel(bf16_t* const* ta
     }
 }
 
-template <int DH, int G>
-int launch_shared(const void* qkv, const void* kcache, const void* vcache, const float* bd, const float* r_w_bias, void* out,
-                  const int* t_dev, int B0, int K, int H, int M, float scale, int pieces, float* ws, int* arrived, const int* live,
-                  int cap, size_t shm, hipStream_t s) {
-    static size_t attr = 64 * 1024;         // dynamic LDS this instantiation may take so far
-    if (shm > attr) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&decode_attn_shared_kernel<DH, G>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        if (e != hipSuccess) return (int)e;
-        attr = shm;
-    }
-    const int ngroups = (K + G - 1) / G;
-    hipLaunchKernelGGL((decode_attn_shared_kernel<DH, G>), dim3(H, B0 * ngroups, pieces), dim3(256), shm, s, (const bf16_t*)qkv,
-                       (const bf16_t*)kcache, (const bf16_t*)vcache, bd, r_w_bias, (bf16_t*)out, t_dev, K, ngroups, H, M, scale, ws,
-                       arrived, live, cap);
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
 }  // namespace
 
 extern "C" size_t mxl_relattn_decode_shared_lds_bytes(int K, int dh, int M, int pieces) {
     if (K < 2 || K > SH_KMAX || dh <= 0 || M <= 0 || pieces < 1 || pieces > 8) return 0;
-    return shared_lds(shared_group(K), dh, shared_cap(M, pieces));
+    return shared_lds(group_size(K), dh, group_cap(M, pieces));
 }
 
 extern "C" int mxl_relattn_decode_shared(const void* qkv, const void* kcache, const void* vcache, const float* bd,
@@ -399,12 +351,14 @@ extern "C" int mxl_relattn_decode_shared(const void* qkv, const void* kcache, co
     if (pieces > 1) MXL_CHECK_ARG(ws && arrived);
     MXL_CHECK_ARG(((uintptr_t)qkv % 16) == 0 && ((uintptr_t)kcache % 16) == 0 && ((uintptr_t)vcache % 16) == 0);
     if (dh != 16 && dh != 32 && dh != 64) return MXL_EUNSUPPORTED;
-    const int G = shared_group(K), cap = shared_cap(M, pieces);
+    const int G = group_size(K), cap = group_cap(M, pieces);
     const size_t shm = shared_lds(G, dh, cap);
-    MXL_CHECK_ARG(shm <= (size_t)SH_LDS_MAX && (long long)B0 * ((K + G - 1) / G) <= 65535);
+    MXL_CHECK_ARG(shm <= (size_t)GROUP_LDS_MAX && (long long)B0 * ((K + G - 1) / G) <= 65535);
     hipStream_t s = (hipStream_t)stream;
-#define LAUNCH(DH, GG) return launch_shared<DH, GG>(qkv, kcache, vcache, bd, r_w_bias, out, t_dev, B0, K, H, M, scale, pieces, ws, \
-                                                    arrived, unfinished, cap, shm, s)
+    const int ngroups = (K + G - 1) / G;
+#define LAUNCH(DH, GG) return launch_big_lds<&decode_attn_shared_kernel<DH, GG>>(                                                            \
+        dim3(H, B0 * ngroups, pieces), shm, s, (const bf16_t*)qkv, (const bf16_t*)kcache, (const bf16_t*)vcache, bd, r_w_bias, (bf16_t*)out, \
+        t_dev, K, ngroups, H, M, scale, ws, arrived, unfinished, cap)
     if (G == 4) {
         switch (dh) {
             case 16: LAUNCH(16, 4);

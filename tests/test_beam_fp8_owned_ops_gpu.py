@@ -1,4 +1,4 @@
-"""mxl_relattn_decode_fp8_owned (csrc/decode_fp8_owned.hip) through the C ABI: the ring attention over FP8 rings read through the owner
+"""mxl_relattn_decode_fp8_owned (csrc/decode_fp8.hip) through the C ABI: the ring attention over FP8 rings read through the owner
 table of indexed rings.
 
 The geometry of tests/test_beam_owner_ops_gpu.py: 2 items x nb = 3 rows, H = 2, M = 96, dh 16 / 32 / 64, t = 5 (a short ring with
@@ -33,7 +33,7 @@ BF = torch.bfloat16
 NB, ITEMS, H, M = 3, 2, 2, 96
 B = NB * ITEMS
 TS = (5, M - 2, M - 1, M + 7, 3 * M + 1)
-U_SHIPPED = 11                                                         # FP8_OWNED_U of csrc/decode_fp8_owned.hip
+U_SHIPPED = 11                                                         # FP8_OWNED_U of csrc/decode_fp8.hip
 M_DEEP = (2 * 4 * (64 // (64 // 16)) * U_SHIPPED // 16 + 1) * 16       # dh = 64: KPW = 64 / (dh / 16) = 16 keys per wave instruction
 DEEP = dict(dh=64, t=M_DEEP + 7, H=1, M=M_DEEP)
 POISON_BYTE, POISON_EXP = 0x7F, 127

@@ -1,4 +1,4 @@
-"""The two kernels of indexed rings through the C ABI: mxl_relattn_decode_owned (csrc/decode_owned.hip) and mxl_beam_owner_follow
+"""The two kernels of indexed rings through the C ABI: mxl_relattn_decode_owned (csrc/decode_attn.hip) and mxl_beam_owner_follow
 (csrc/beam.hip).
 
 Attention: 2 items x nb = 3 rows (a beam count that is no power of two), H = 2, M = 96, dh 16 / 32 / 64, t = 5 (a short ring with

@@ -1,5 +1,5 @@
-"""The Transformer-XL decode-step kernels (the first 350 lines of csrc/decode.hip, the mxl_decode_qkv epilogue of csrc/gemm_skinny.hip,
-ops.relattn_decode), every output element against the float64 closed form of oracle/decode_cases.py:
+"""The Transformer-XL decode-step kernels (the embed, append and BD kernels of csrc/decode.hip, decode_attn_kernel of csrc/decode_attn.hip, the
+mxl_decode_qkv epilogue of csrc/gemm_skinny.hip, ops.relattn_decode), every output element against the float64 closed form of oracle/decode_cases.py:
 
     |got - ref| <= a |ref| + b max|ref|        a = 2^-8 (bf16: the attention output) or 2^-24 (float32: BD)
 
