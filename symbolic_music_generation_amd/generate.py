@@ -23,6 +23,7 @@ import torch
 
 from . import ops
 from ._lib import MusicXLError
+from .rings import FP8Rings, PromptRings, RingLayout, SharedRings, prompt_tail_len        # noqa: F401 (prompt_tail_len: re-exported)
 
 
 STOP_CHUNK = 16          # decode steps per chunk between reads of the live-row count (run_until_finished)
@@ -1306,29 +1307,35 @@ BEAM_RINGS = ('copied', 'indexed', 'indexed_fp8')         # what `generate(beam_
 DECODER_BEAM_RINGS = BEAM_RINGS[:2]                        # what XLDecoder.beam_begin takes: 'indexed_fp8' is 'indexed' on an fp8 decoder
 
 
+def _resolve_opt_in(name: str, value: Optional[str], allowed: tuple, env: str, applies: bool, serves: str) -> str:
+    """the one body of the ring opt-ins: `value` of keyword `name`, one of `allowed` (the first, 'copied', is what None means); a call
+    that names none takes the environment's `env` (an A/B knob: unset, nothing changes).  Any other string is a ValueError; so is an
+    explicit opt-in where it does not apply ("<name>='<value>' serves <serves>"), while the environment's is ignored there."""
+    explicit = value is not None
+    mode = value if explicit else (os.environ.get(env) or allowed[0])
+    if mode not in allowed:
+        raise ValueError(f"{name}={mode!r}: expected None, {', '.join(map(repr, allowed[:-1]))} or {allowed[-1]!r}")
+    if mode != allowed[0] and not applies:
+        if explicit:
+            raise ValueError(f"{name}='{mode}' serves {serves}")
+        mode = allowed[0]
+    return mode
+
+
 def resolve_beam_rings(beam_rings: Optional[str], applies: bool, d_head: int = 64) -> str:
-    """how the K/V rings of a device beam search follow their beams: 'copied' (mxl_beam_reorder moves whole ring rows; None means
-    this), 'indexed' (the rings stay and an owner table follows, mxl_beam_owner_follow / mxl_relattn_decode_owned) or 'indexed_fp8'
-    (the same over FP8 rings, mxl_relattn_decode_fp8_owned: the caller builds the search's decoder with kv_dtype='fp8' and runs its
-    'indexed' mode).  A call that names none takes MXL_BEAM_RINGS (an A/B knob: unset, nothing changes).  applies: the call is a
-    beam, group-beam or beam-sample search with its scorer on the device, without kv_cache_dtype, over a mem_len that is a multiple
-    of 16.  An explicit 'indexed' or 'indexed_fp8' anywhere else is a ValueError, the environment's is ignored there; any other
-    string is a ValueError.  d_head: FP8 rings take head widths 16, 32 and 64 -- an explicit 'indexed_fp8'
-    with another is a MusicXLError, the environment's is ignored."""
-    explicit = beam_rings is not None
-    mode = beam_rings if explicit else (os.environ.get('MXL_BEAM_RINGS') or 'copied')
-    if mode not in BEAM_RINGS:
-        raise ValueError(f"beam_rings={mode!r}: expected None, 'copied', 'indexed' or 'indexed_fp8'")
-    if mode != 'copied' and not applies:
-        if explicit:
-            raise ValueError(f"beam_rings='{mode}' serves beam, group-beam and beam-sample search with the scorer on the device"
-                             f"{' over bf16 rings' if mode == 'indexed' else ''}: "
-                             'not greedy decoding, sampling or contrastive search, not the host scorers (MXL_BEAM_HOST=1, '
-                             "more than 16 beams, beam-sample without device_scorer=True), not kv_cache_dtype='fp8', not a mem_len "
-                             'that is no multiple of 16')
-        mode = 'copied'
+    """`generate(beam_rings=)`, which describes the modes: how the K/V rings of a device beam search follow their beams -- 'copied'
+    (None), 'indexed' or 'indexed_fp8' (the caller builds the search's decoder with kv_dtype='fp8' and runs its 'indexed' mode) -- by
+    _resolve_opt_in with MXL_BEAM_RINGS.  applies: the call is a beam, group-beam or beam-sample search with its scorer on the device,
+    without kv_cache_dtype, over a mem_len that is a multiple of 16.  d_head: FP8 rings take head widths 16, 32 and 64 -- an explicit
+    'indexed_fp8' with another is a MusicXLError, the environment's is ignored."""
+    mode = _resolve_opt_in('beam_rings', beam_rings, BEAM_RINGS, 'MXL_BEAM_RINGS', applies,
+                           'beam, group-beam and beam-sample search with the scorer on the device'
+                           f"{' over bf16 rings' if beam_rings == 'indexed' else ''}: "
+                           'not greedy decoding, sampling or contrastive search, not the host scorers (MXL_BEAM_HOST=1, '
+                           "more than 16 beams, beam-sample without device_scorer=True), not kv_cache_dtype='fp8', not a mem_len "
+                           'that is no multiple of 16')
     if mode == 'indexed_fp8' and d_head not in (16, 32, 64):
-        if explicit:
+        if beam_rings is not None:
             raise MusicXLError(f"beam_rings='indexed_fp8': fp8 K/V rings need a head width of 16, 32 or 64, not {d_head}")
         mode = 'copied'
     return mode
@@ -1338,131 +1345,48 @@ CONTRASTIVE_RINGS = ('copied', 'shared')                   # what `generate(cont
 
 
 def resolve_contrastive_rings(contrastive_rings: Optional[str], applies: bool) -> str:
-    """the K/V rings of a contrastive search on the device: 'copied' (one set of rings per candidate row, the step's slot follows the
-    pick with mxl_ring_slot_broadcast; None means this) or 'shared' (one set per prompt, read by its K candidates:
-    mxl_kv_stash / mxl_relattn_decode_shared / mxl_kv_commit_shared, XLDecoder(shared_rings=K)).  A call that names none takes
-    MXL_CONTRASTIVE_RINGS (an A/B knob: unset, nothing changes).  applies: the call is a contrastive search with its step on the device
-    (top_k <= 32, no MXL_CONTRASTIVE_HOST=1) over bf16 rings.  An explicit 'shared' anywhere else is a ValueError, the environment's
-    is ignored there; any other string is a ValueError."""
-    explicit = contrastive_rings is not None
-    mode = contrastive_rings if explicit else (os.environ.get('MXL_CONTRASTIVE_RINGS') or 'copied')
-    if mode not in CONTRASTIVE_RINGS:
-        raise ValueError(f"contrastive_rings={mode!r}: expected None, 'copied' or 'shared'")
-    if mode != 'copied' and not applies:
-        if explicit:
-            raise ValueError("contrastive_rings='shared' serves contrastive search with its step on the device over bf16 rings: not "
-                             'greedy decoding, sampling or a beam search, not the host-driven loop (top_k > 32, '
-                             "MXL_CONTRASTIVE_HOST=1), not kv_cache_dtype='fp8'")
-        mode = 'copied'
-    return mode
+    """`generate(contrastive_rings=)`, which describes the modes: the K/V rings of a contrastive search on the device -- 'copied' (None:
+    one set per candidate row) or 'shared' (one per prompt, XLDecoder(shared_rings=K)) -- by _resolve_opt_in with MXL_CONTRASTIVE_RINGS.
+    applies: the call is a contrastive search with its step on the device (top_k <= 32, no MXL_CONTRASTIVE_HOST=1) over bf16 rings."""
+    return _resolve_opt_in('contrastive_rings', contrastive_rings, CONTRASTIVE_RINGS, 'MXL_CONTRASTIVE_RINGS', applies,
+                           'contrastive search with its step on the device over bf16 rings: not greedy decoding, sampling or a beam '
+                           "search, not the host-driven loop (top_k > 32, MXL_CONTRASTIVE_HOST=1), not kv_cache_dtype='fp8'")
 
 
 PROMPT_RINGS = ('copied', 'shared')                        # what `generate(prompt_rings=)` takes
 
 
 def resolve_prompt_rings(prompt_rings: Optional[str], applies: bool) -> str:
-    """the K/V rings of sampling with num_return_sequences = n >= 2: 'copied' (every one of the n rows of a prompt owns a full set of
-    rings and the prompt pass runs on all of them; None means this) or 'shared' (one set of prompt rings per prompt, written once by a
-    prompt pass of the unexpanded batch, and a tail ring per row for what it generates: mxl_kv_append_tail /
-    mxl_relattn_decode_prefix, XLDecoder(prompt_rings=n)).  A call that names none takes MXL_PROMPT_RINGS (an A/B knob: unset, nothing
-    changes).  applies: the call samples (do_sample=True, one beam) with num_return_sequences >= 2 over bf16 rings.  An explicit
-    'shared' anywhere else is a ValueError, the environment's is ignored there; any other string is a ValueError."""
-    explicit = prompt_rings is not None
-    mode = prompt_rings if explicit else (os.environ.get('MXL_PROMPT_RINGS') or 'copied')
-    if mode not in PROMPT_RINGS:
-        raise ValueError(f"prompt_rings={mode!r}: expected None, 'copied' or 'shared'")
-    if mode != 'copied' and not applies:
-        if explicit:
-            raise ValueError("prompt_rings='shared' serves sampling with num_return_sequences >= 2 over bf16 rings: not "
-                             "num_return_sequences=1, greedy decoding, a beam search or contrastive search, not kv_cache_dtype='fp8'")
-        mode = 'copied'
-    return mode
+    """`generate(prompt_rings=)`, which describes the modes: the K/V rings of sampling with num_return_sequences = n >= 2 -- 'copied'
+    (None: a full set per row) or 'shared' (one set of prompt rings per prompt and a tail ring per row, XLDecoder(prompt_rings=n)) --
+    by _resolve_opt_in with MXL_PROMPT_RINGS.  applies: the call samples (do_sample=True, one beam) with n >= 2 over bf16 rings."""
+    return _resolve_opt_in('prompt_rings', prompt_rings, PROMPT_RINGS, 'MXL_PROMPT_RINGS', applies,
+                           'sampling with num_return_sequences >= 2 over bf16 rings: not num_return_sequences=1, greedy decoding, a '
+                           "beam search or contrastive search, not kv_cache_dtype='fp8'")
 
 
-def prompt_rings_misfit(cfg, n: int, rows: int) -> Optional[str]:
-    """why a model cannot run prompt_rings='shared' with n rows per prompt in a decoder of `rows` rows (None: it can): the head width,
-    mem_len % 16 and the shared memory of the attention workgroup at the decoder's ring pieces"""
-    M, dh = cfg.mem_len, cfg.d_head
-    if dh not in (16, 32, 64):
-        return f'prompt rings need a head width of 16, 32 or 64, not {dh}'
-    if M % 16 or M < 16:
-        return f'prompt rings take a mem_len that is a multiple of 16, not {M}'
-    pieces = ops.decode_ring_pieces((rows // n) * ops.prefix_attn_groups(n), cfg.n_head, M)
-    if not 0 < ops.relattn_decode_prefix_lds_bytes(n, dh, M, pieces) <= ops.SHARED_LDS_MAX:
-        return (f'prompt rings: mem_len {M} in {pieces} piece(s) needs more than the {ops.SHARED_LDS_MAX >> 10} KiB of shared memory a '
-                f'workgroup of {8 if n > 4 else 4} queries has for its scores')
-    return None
-
-
-def prompt_tail_len(mem_len: int, generated: int) -> int:
-    """slots of a row's tail ring for `generated` positions after the prompt: that many rounded up to a multiple of 16, mem_len at most"""
-    return min(mem_len, max(16, (int(generated) + 15) // 16 * 16))
+prompt_rings_misfit = PromptRings.misfit         # (cfg, n, rows): why a model cannot run prompt_rings='shared' so, None: it can
 
 
 class XLDecoder(RuledGenerate):
     def __init__(self, engine, batch: int, max_total_len: int, seed: int = 77, kv_dtype: Optional[str] = None,
                  shared_rings: int = 0, prompt_rings: int = 0, tail_len: Optional[int] = None):
-        """prompt_rings = n > 0: a decoder for sampling alone (begin / run) whose `batch` = B0 * n rows are n variations of each of B0
-        prompts: per layer one pair of bf16 prompt rings per prompt, kc / vc (B0, H, M, dh), written once by the prompt pass of the B0
-        prompts, and one pair of tail rings per row, kt / vt (batch, H, Mt, dh), for the positions generated after the prompt
-        (csrc/decode_prefix.hip); Mt = prompt_tail_len(M, tail_len), tail_len = the most positions a generation adds to its prompt (None:
-        a full ring).  `t0_dev` holds the prompt length of the generation at hand.  0: every row owns its rings.
-        shared_rings = K > 0: a decoder for contrastive search alone (contrastive_begin) whose `batch` = B0 * K rows keep one set of
-        bf16 rings per prompt, (B0, H, M, dh) per layer, and a stash (L, batch, 2d) for the k / v of the step (csrc/decode_shared.hip);
-        everything per candidate stays `batch` rows.  0: every row owns its rings."""
-        self.eng = engine
-        c = engine.cfg
-        self.B, self.Tmax = batch, max_total_len
-        dev = engine.dev
-        d, M, L, Fi = c.d_model, c.mem_len, c.n_layer, c.d_inner
+        """kv_dtype, shared_rings, prompt_rings and tail_len select the layout of the K/V rings (rings.py; `_layout`): bf16 or
+        kv_dtype='fp8' rings, one per row; shared_rings = K > 0, a decoder for contrastive search alone whose `batch` = B0 * K rows keep
+        one set of rings per prompt (rings.SharedRings); prompt_rings = n > 0, a decoder for sampling alone whose `batch` = B0 * n rows
+        keep one set of prompt rings per prompt and a tail ring of prompt_tail_len(M, tail_len) slots each (rings.PromptRings).
+        `self.layout` holds the rings and everything that differs between the modes; everything per row stays `batch` rows here, and
+        the layout's tensors and numbers are readable here under the names in RingLayout.SHOWN."""
+        self.eng, self.B, self.Tmax = engine, batch, max_total_len
+        c, dev = engine.cfg, engine.dev
+        d, M, Fi, H, dh = c.d_model, c.mem_len, c.d_inner, c.n_head, c.d_head
         bf = dict(device=dev, dtype=torch.bfloat16)
-        H, dh = c.n_head, c.d_head
-        if kv_dtype not in (None, 'fp8'):
-            raise ValueError(f"kv_dtype={kv_dtype!r}: expected None (bf16 rings) or 'fp8'")
-        self.kv_dtype = kv_dtype
-        self.shared_K = K = int(shared_rings)
-        self.prompt_n = n = int(prompt_rings)
-        self.kt = self.vt = []
-        ring_rows, attn_rows = batch, batch
-        if n:
-            if kv_dtype is not None or K:
-                raise ValueError('prompt rings are bf16 rings under sampling: neither kv_dtype nor shared_rings goes with them')
-            if n < 2 or batch % n:
-                raise MusicXLError('prompt rings take 2 or more rows per prompt and one decoder row per variation')
-            misfit = prompt_rings_misfit(c, n, batch)
-            if misfit:
-                raise MusicXLError(misfit)
-            # the attention launch has one workgroup per (head, prompt, group of 8 rows -- 4 for n <= 4) and ring piece
-            ring_rows = batch // n
-            attn_rows = ring_rows * ops.prefix_attn_groups(n)
-            self.Mt = prompt_tail_len(M, M if tail_len is None else tail_len)
-            self.kt = [torch.zeros(batch, H, self.Mt, dh, **bf) for _ in range(L)]
-            self.vt = [torch.zeros(batch, H, self.Mt, dh, **bf) for _ in range(L)]
-            self.t0_dev = torch.zeros(1, device=dev, dtype=torch.int32)
-        if K:
-            if kv_dtype is not None:
-                raise ValueError(f'shared rings are bf16 rings: kv_dtype={kv_dtype!r} is not supported')
-            if K < 2 or K > CONTRASTIVE_MAX or batch % K:
-                raise MusicXLError(f'shared rings take 2..{CONTRASTIVE_MAX} candidates per prompt and one decoder row per candidate')
-            if dh not in (16, 32, 64):
-                raise MusicXLError(f'shared rings need a head width of 16, 32 or 64, not {dh}')
-            # the attention launch has one workgroup per (head, prompt, group of 8 candidates -- 4 for K <= 4) and ring piece
-            ring_rows = batch // K
-            attn_rows = ring_rows * (1 if K <= 4 else (K + 7) // 8)
-            self.stash = torch.empty(L, batch, 2 * d, **bf)
-        if kv_dtype == 'fp8':
-            # e4m3fn bytes with one int8 exponent per slot and head (DESIGN 2, "FP8 rings"): (dh + 1) / (2 dh) of the bf16 bytes
-            if dh not in (16, 32, 64):
-                raise MusicXLError(f'fp8 K/V rings need a head width of 16, 32 or 64, not {dh}')
-            self.kc = [torch.zeros(batch, H, M, dh, device=dev, dtype=torch.uint8) for _ in range(L)]
-            self.vc = [torch.zeros(batch, H, M, dh, device=dev, dtype=torch.uint8) for _ in range(L)]
-            self.ke = [torch.zeros(batch, H, M, device=dev, dtype=torch.int8) for _ in range(L)]
-            self.ve = [torch.zeros(batch, H, M, device=dev, dtype=torch.int8) for _ in range(L)]
-        else:
-            self.kc = [torch.zeros(ring_rows, H, M, dh, **bf) for _ in range(L)]    # head-major rings
-            self.vc = [torch.zeros(ring_rows, H, M, dh, **bf) for _ in range(L)]
-            self.ke = self.ve = []
-        self.rd = None                                  # per-layer Rd tables (eval: no dropout on pos_emb)
+        self.layout = lay = self._layout(kv_dtype, shared_rings, prompt_rings, tail_len)
+        lay.build(c, batch, dev)
+        for k in RingLayout.SHOWN:
+            setattr(self, k, getattr(lay, k))
+        self.ring_spec = (lay.kv_dtype, lay.prompt_n, lay.Mt)       # what `generate` rebuilds its cached decoder for
+        self.rd = None                                 # per-layer Rd tables (eval: no dropout on pos_emb)
         self.ids = torch.zeros(batch, max_total_len + 1, device=dev, dtype=torch.int64)
         self.t_dev = torch.zeros(1, device=dev, dtype=torch.int32)
         self.rng = torch.zeros(1, device=dev, dtype=torch.int64)
@@ -1473,12 +1397,7 @@ class XLDecoder(RuledGenerate):
         self.qr = torch.empty(batch, d, **bf)
         self.slabs = torch.zeros(4, 64, d, device=dev, dtype=torch.float32)   # K-slice partials of the FFN output projection
         self.bd = torch.empty(batch, H, M, device=dev, dtype=torch.float32)
-        # ring pieces per (sequence, head): the attention launch fills every CU with the same number of bytes (ops.decode_ring_pieces)
-        self.pieces = ops.decode_ring_pieces(attn_rows, H, M)
-        self.split = ops.relattn_decode_split_scratch(batch, H, dh, self.pieces, dev)
-        if K and not 0 < ops.relattn_decode_shared_lds_bytes(K, dh, M, self.pieces) <= ops.SHARED_LDS_MAX:
-            raise MusicXLError(f'shared rings: mem_len {M} in {self.pieces} piece(s) needs more than the {ops.SHARED_LDS_MAX >> 10} KiB of '
-                               f'shared memory a workgroup of {8 if K > 4 else 4} queries has for its scores')
+        self.split = ops.relattn_decode_split_scratch(batch, H, dh, lay.pieces, dev)
         self.tmp = torch.empty(batch, d, **bf)
         self.h1 = torch.empty(batch, d, **bf)
         self.a = torch.empty(batch, Fi, **bf)
@@ -1508,6 +1427,22 @@ class XLDecoder(RuledGenerate):
         for k in RowRules.STATE:
             setattr(self, k, getattr(self.rules, k))
 
+    @staticmethod
+    def _layout(kv_dtype: Optional[str], shared_rings: int, prompt_rings: int, tail_len: Optional[int]) -> RingLayout:
+        """the ring layout (rings.py) of a decoder's ring arguments, not yet built: the one place that tells the modes apart"""
+        if kv_dtype not in (None, 'fp8'):
+            raise ValueError(f"kv_dtype={kv_dtype!r}: expected None (bf16 rings) or 'fp8'")
+        K, n = int(shared_rings), int(prompt_rings)
+        if n:
+            if kv_dtype is not None or K:
+                raise ValueError('prompt rings are bf16 rings under sampling: neither kv_dtype nor shared_rings goes with them')
+            return PromptRings(n, tail_len)
+        if K:
+            if kv_dtype is not None:
+                raise ValueError(f'shared rings are bf16 rings: kv_dtype={kv_dtype!r} is not supported')
+            return SharedRings(K)
+        return FP8Rings() if kv_dtype == 'fp8' else RingLayout()
+
     def _tables(self):
         if self.rd is None:
             e, c = self.eng, self.eng.cfg
@@ -1524,7 +1459,8 @@ class XLDecoder(RuledGenerate):
         self.graph = None
 
     # ---------------------------------------------------------------- prompt
-    def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, rules: RulePlan = NO_RULES):
+    def prefill(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor] = None, rules: RulePlan = NO_RULES,
+                search: str = 'beam'):
         """Whole prompt through the training-shape kernels with zero mems (upstream first step), rings filled from the
         per-layer qkv buffers, first new token sampled from the last position.
         n_pad: (B,) int32 device tensor, left-padded prompts: the first n_pad[b] columns of row b are pads.  Their K / V are zero
@@ -1532,100 +1468,21 @@ class XLDecoder(RuledGenerate):
         held as -1 in `ids`, which the samplers' repetition penalty skips.
         rules: the RulePlan of the generation (rules_config; RowRules.start sets the rows' words from it on the device, pads
         skipped).  Every row starts live, and the first token sampled here counts.  A prompt that breaks the grammar, overfills or
-        underfills a bar under a bar budget, or a guide that does not fit its row's bar length raises (RowRules.check_prompt)."""
-        e, c = self.eng, self.eng.cfg
+        underfills a bar under a bar budget, or a guide that does not fit its row's bar length raises (RowRules.check_prompt).
+        search: what a call without `sampling` is the prompt pass of, 'beam' or 'contrastive'; its caller picks the token from logp.
+        Under a layout with one ring per `unit` rows (rings.py) `prompt` and n_pad still hold all B rows, the pass runs on every
+        unit-th of them and the layout spreads the last position's log-probabilities; ids and the rule words start in all B rows."""
+        e, c, lay = self.eng, self.eng.cfg, self.layout
         B, Tp = prompt.shape
         assert B == self.B and Tp + 1 <= self.Tmax + 1
-        if self.shared_K:
-            raise MusicXLError('a decoder with shared rings serves contrastive search alone (contrastive_begin)')
-        if self.prompt_n:
-            if sampling is None:
-                raise MusicXLError('a decoder with prompt rings serves sampling alone (begin / run), not a search')
-            return self._prefill_prefix(prompt, sampling, n_pad, rules)
+        if lay.serves not in (None, 'sample' if sampling is not None else search):
+            raise MusicXLError(lay.alone)
+        u, rows = lay.unit, B // lay.unit
         self._tables()
         self.beam_rings = 'copied'                          # every row reads its own ring until a beam_begin says otherwise
-        for k in self.kc + self.vc + self.ke + self.ve:     # (fp8: zero bytes with e = 0 are the zero memories)
-            k.zero_()
-        self.ids.zero_()
-        self.ids[:, :Tp].copy_(prompt)
         x = prompt.to(e.dev)
-        if n_pad is not None:
-            n_pad = n_pad.to(e.dev, torch.int32).contiguous()
-            pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
-            self.ids[:, :Tp].masked_fill_(pad, -1)
-            x = x.masked_fill(pad, 0)
-        self.rules.start(self.ids, Tp, c.vocab_size, rules)
-        sink_kc, sink_vc, sink_ke, sink_ve = self.kc, self.vc, self.ke, self.ve
-
-        def kv_sink(l, qkv):
-            if sink_ke:
-                ops.kv_fill_fp8(qkv, sink_kc[l], sink_ke[l], sink_vc[l], sink_ve[l], Tp)
-            else:
-                ops.kv_fill(qkv, sink_kc[l], sink_vc[l], Tp)
-
-        out = e.forward(x, mems=None, labels=None, train=False, want_logprobs=False, kv_sink=kv_sink, n_pad=n_pad)
-        ws = e._last
-        N = B * Tp
-        # log-probs of the last prompt position only
-        if ws.logits is None:       # bucketed (large-vocabulary) head: the (N, V) logits were never formed; project B rows here
-            self.tmp.copy_(ws.hid.view(B, Tp, -1)[:, Tp - 1])
-            self._head(self.tmp)
-        else:
-            last = ws.logits.view(B, Tp, -1)[:, Tp - 1]
-            ops.adaptive_logprob(last, self.logp, B, c.vocab_size, tuple(c.cutoffs))
-        self.t_dev.fill_(Tp - 1)
-        self._trace()
-        self.rules.check_prompt(self.ids)
-        if sampling is not None:                       # None: the caller picks the token from self.logp (beam search)
-            self._sample_advance(self.logp, sampling)  # t = Tp: position of the token just sampled
-        return out
-
-    def _prefill_shared(self, prompt: torch.Tensor, rules: RulePlan):
-        """the prompt pass of a decoder with shared rings: `prompt` (B0, Tp), one row per prompt, through the training-shape kernels
-        once -- B0 rows, not B0 * K -- into the B0 rings.  The log-probabilities of the last position go to rows b*K of `logp`, where
-        mxl_contrastive_topk reads them (sel starts at 0); ids and the rule words start in all B0 * K rows as `prefill` starts them."""
-        e, c, K = self.eng, self.eng.cfg, self.shared_K
-        B0, Tp = prompt.shape
-        assert B0 * K == self.B and Tp + 1 <= self.Tmax + 1
-        self._tables()
-        self.beam_rings = 'copied'
-        for k in self.kc + self.vc:
-            k.zero_()
-        x = prompt.to(e.dev)
-        self.ids.zero_()
-        self.ids[:, :Tp].copy_(x.repeat_interleave(K, 0))
-        self.rules.start(self.ids, Tp, c.vocab_size, rules)
-        out = e.forward(x, mems=None, labels=None, train=False, want_logprobs=False,
-                        kv_sink=lambda l, qkv: ops.kv_fill(qkv, self.kc[l], self.vc[l], Tp), n_pad=None)
-        ws = e._last
-        if ws.logits is None:       # bucketed (large-vocabulary) head: project the prompts' last hidden states in rows b*K
-            self.tmp.zero_()
-            self.tmp[::K].copy_(ws.hid.view(B0, Tp, -1)[:, Tp - 1])
-            self._head(self.tmp)
-        else:
-            logp = torch.empty(B0, c.vocab_size, device=e.dev, dtype=torch.float32)
-            ops.adaptive_logprob(ws.logits.view(B0, Tp, -1)[:, Tp - 1], logp, B0, c.vocab_size, tuple(c.cutoffs))
-            self.logp[::K].copy_(logp)
-        self.t_dev.fill_(Tp - 1)
-        self._trace()
-        self.rules.check_prompt(self.ids)
-        return out
-
-    def _prefill_prefix(self, prompt: torch.Tensor, sampling: dict, n_pad: Optional[torch.Tensor], rules: RulePlan):
-        """the prompt pass of a decoder with prompt rings: `prompt` (B0 * n, Tp) holds every prompt n times over (repeat_interleave, as
-        `generate` expands it; n_pad likewise), and the pass runs on every n-th row -- B0 rows through the training-shape kernels, pad
-        K / V zeroed as in `prefill` -- into the B0 prompt rings, which no step writes again.  The log-probabilities of the last
-        position go to all n rows of their prompt; ids and the rule words start in all rows as `prefill` starts them, and the first
-        token of every row is drawn by the ordinary sampler launch (the draw is keyed by seed, row and step).  t0_dev <- Tp."""
-        e, c, n = self.eng, self.eng.cfg, self.prompt_n
-        B, Tp = prompt.shape
-        B0 = B // n
-        self._tables()
-        self.beam_rings = 'copied'
-        x = prompt.to(e.dev)
-        if not bool((x.view(B0, n, Tp) == x[::n, None]).all()):
-            raise MusicXLError(f'a decoder with prompt rings takes every prompt {n} times in a row (repeat_interleave)')
-        for k in self.kc + self.vc + self.kt + self.vt:
+        lay.check_prompt(x)
+        for k in lay.tensors():                             # (fp8: zero bytes with e = 0 are the zero memories)
             k.zero_()
         self.ids.zero_()
         self.ids[:, :Tp].copy_(x)
@@ -1634,23 +1491,28 @@ class XLDecoder(RuledGenerate):
             pad = torch.arange(Tp, device=e.dev)[None, :] < n_pad[:, None]
             self.ids[:, :Tp].masked_fill_(pad, -1)
             x = x.masked_fill(pad, 0)
-            n_pad = n_pad[::n].contiguous()
         self.rules.start(self.ids, Tp, c.vocab_size, rules)
-        out = e.forward(x[::n].contiguous(), mems=None, labels=None, train=False, want_logprobs=False,
-                        kv_sink=lambda l, qkv: ops.kv_fill(qkv, self.kc[l], self.vc[l], Tp), n_pad=n_pad)
+        if u > 1:                                           # one prompt row per ring
+            x, n_pad = x[::u].contiguous(), None if n_pad is None else n_pad[::u].contiguous()
+        out = e.forward(x, mems=None, labels=None, train=False, want_logprobs=False, kv_sink=lambda l, qkv: lay.kv_sink(l, qkv, Tp),
+                        n_pad=n_pad)
         ws = e._last
-        if ws.logits is None:       # bucketed (large-vocabulary) head: project the last hidden state of every row's prompt
-            self.tmp.copy_(ws.hid.view(B0, Tp, -1)[:, Tp - 1].repeat_interleave(n, 0))
+        # log-probs of the last prompt position only
+        if ws.logits is None:       # bucketed (large-vocabulary) head: the (N, V) logits were never formed; project B rows here
+            lay.spread(ws.hid.view(rows, Tp, -1)[:, Tp - 1], self.tmp)
             self._head(self.tmp)
         else:
-            logp = torch.empty(B0, c.vocab_size, device=e.dev, dtype=torch.float32)
-            ops.adaptive_logprob(ws.logits.view(B0, Tp, -1)[:, Tp - 1], logp, B0, c.vocab_size, tuple(c.cutoffs))
-            self.logp.copy_(logp.repeat_interleave(n, 0))
+            logp = self.logp if u == 1 else torch.empty(rows, c.vocab_size, device=e.dev, dtype=torch.float32)
+            ops.adaptive_logprob(ws.logits.view(rows, Tp, -1)[:, Tp - 1], logp, rows, c.vocab_size, tuple(c.cutoffs))
+            if u > 1:
+                lay.spread(logp, self.logp)
         self.t_dev.fill_(Tp - 1)
-        self.t0_dev.fill_(Tp)
+        if lay.t0_dev is not None:
+            lay.t0_dev.fill_(Tp)
         self._trace()
         self.rules.check_prompt(self.ids)
-        self._sample_advance(self.logp, sampling)      # t = Tp: position of the token just sampled
+        if sampling is not None:                       # None: the caller picks the token from self.logp (a search)
+            self._sample_advance(self.logp, sampling)  # t = Tp: position of the token just sampled
         return out
 
     def _sample_advance(self, scores, sampling: dict):
@@ -1689,50 +1551,17 @@ class XLDecoder(RuledGenerate):
         self.logp = log-probabilities of position t + 1 (want_logp=False: only self.logits, the head's raw rows).
         embed=False: h[0] already holds the token's embedding row (written by the previous step's sampler launch)."""
         e, c = self.eng, self.eng.cfg
-        B, d, H, dh, M, Fi, L = self.B, c.d_model, c.n_head, c.d_head, c.mem_len, c.d_inner, c.n_layer
+        B, d, Fi, L = self.B, c.d_model, c.d_inner, c.n_layer
         E = e.w16('transformer.word_emb.emb_layers.0.weight')
         G = ops.gemm_skinny if B <= 64 else ops.gemm     # weight-streaming form for decode batches
         # indexed rings: the attention of every layer reads a slot from the row the one table names (the append stays each row's own)
         owned = dict(owner=self.owner, nb=self._beam_args[0]) if self.beam_rings == 'indexed' else {}
+        live = None if self.rules.stop is None else self.unfinished
         if embed:
             ops.decode_embed(self.ids, self.t_dev, E, self.h[0], math.sqrt(d))
         for l in range(L):
             h_in, h_out = self.h[l & 1], self.h[(l + 1) & 1]
-            rrb = e._lw(l, 'dec_attn.r_r_bias', e.P)
-            live = None if self.rules.stop is None else self.unfinished
-            if self.kv_dtype == 'fp8':
-                # projection, then the quantising append (one launch more per layer than the fused bf16 form below), then the fp8 reader
-                G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
-                ops.kv_append_fp8(self.qkv, self.kc[l], self.ke[l], self.vc[l], self.ve[l], self.t_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
-                ops.relattn_decode_fp8(self.qkv, self.kc[l], self.ke[l], self.vc[l], self.ve[l], self.rd[l],
-                                       e._lw(l, 'dec_attn.r_w_bias', e.P), rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True,
-                                       split=self.split, pieces=self.pieces, unfinished=live, **owned)
-            elif self.shared_K:
-                # shared rings: no ring write before the pick -- projection, then q + r_r_bias and the row's k / v into the layer's
-                # stash (for B <= 64 one launch more per layer than the fused form below), then the K queries of a prompt over its ring
-                G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
-                ops.kv_stash(self.qkv, self.stash[l], rrb=rrb.reshape(-1), qr_out=self.qr)
-                ops.relattn_decode_shared(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P), rrb, self.av,
-                                          self.t_dev, self.shared_K, H, dh, self.qr, self.bd, qr_ready=True, split=self.split,
-                                          pieces=self.pieces, unfinished=live)
-            elif self.prompt_n:
-                # prompt rings: projection, then q + r_r_bias and the row's k / v into its tail ring (for B <= 64 one launch more per
-                # layer than the fused form below), then the n queries of a prompt over its ring and their own tails
-                G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
-                ops.kv_append_tail(self.qkv, self.kt[l], self.vt[l], self.t_dev, self.t0_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
-                ops.relattn_decode_prefix(self.qkv, self.kc[l], self.vc[l], self.kt[l], self.vt[l], self.rd[l],
-                                          e._lw(l, 'dec_attn.r_w_bias', e.P), rrb, self.av, self.t_dev, self.t0_dev, self.prompt_n, H, dh,
-                                          self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces, unfinished=live)
-            elif B <= 64:      # projection, ring append and q + r_r_bias in one launch
-                ops.decode_qkv(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, self.kc[l], self.vc[l], self.t_dev,
-                               rrb.reshape(-1), self.qr, dh)
-            else:
-                G(h_in, e._lw(l, 'dec_attn.qkv_net.weight'), self.qkv, B, 3 * d, d)
-                ops.kv_append(self.qkv, self.kc[l], self.vc[l], self.t_dev, rrb=rrb.reshape(-1), qr_out=self.qr)
-            if self.kv_dtype != 'fp8' and not self.shared_K and not self.prompt_n:
-                ops.relattn_decode(self.qkv, self.kc[l], self.vc[l], self.rd[l], e._lw(l, 'dec_attn.r_w_bias', e.P),
-                                   rrb, self.av, self.t_dev, H, dh, self.qr, self.bd, qr_ready=True, split=self.split, pieces=self.pieces,
-                                   unfinished=live, **owned)
+            self.layout.layer(self, l, h_in, live, owned)       # projection, ring append and ring attention: h_in -> self.av
             G(self.av, e._lw(l, 'dec_attn.o_net.weight'), self.tmp, B, d, d)
             ops.ln_residual_fwd(self.tmp, h_in, e._lw(l, 'dec_attn.layer_norm.weight', e.P),
                                 e._lw(l, 'dec_attn.layer_norm.bias', e.P), self.h1, eps=c.layer_norm_epsilon)
@@ -1769,8 +1598,8 @@ class XLDecoder(RuledGenerate):
     # ---------------------------------------------------------------- beam-search hooks (see beam_search below)
     def _bf16_rings_only(self, what: str):
         """the searches move rings with mxl_beam_reorder / mxl_ring_slot_broadcast / index_select, which know the bf16 layout alone"""
-        if self.kv_dtype is not None:
-            raise ValueError(f'{what} does not take {self.kv_dtype} K/V rings')
+        if not self.layout.movable:
+            raise ValueError(f'{what} does not take {self.layout.kv_dtype} K/V rings')
 
     def beam_prefill(self, prompt: torch.Tensor):
         self._bf16_rings_only('beam search')
@@ -1782,7 +1611,7 @@ class XLDecoder(RuledGenerate):
     def beam_reorder(self, beam_idx: torch.Tensor):
         """rows follow their beams: id history and both rings of every layer (HF `_reorder_cache`: index_select on the mems)"""
         self.ids.copy_(self.ids.index_select(0, beam_idx))
-        for ring in self.kc + self.vc:
+        for ring in self.layout.rings():
             ring.copy_(ring.index_select(0, beam_idx))
 
     def beam_advance(self, cur_len: int):
@@ -1808,15 +1637,14 @@ class XLDecoder(RuledGenerate):
         pass wrote them, the `owner` table (identity after the prompt pass: every row holds its own prompt) follows the beams with
         mxl_beam_owner_follow and the attention reads through it (mxl_relattn_decode_owned); M % 16 == 0.  The mode is part of the
         graph key, the table is step state.
-        A decoder with kv_dtype='fp8' takes 'indexed': the prompt pass fills FP8 rings (mxl_kv_fill_fp8), every step appends to the
-        row's own slot (mxl_kv_append_fp8) -- the slot the follow kernel marks as the row's own -- and mxl_relattn_decode_fp8_owned
-        reads through the table, so no ring is ever moved.  'copied' on such a decoder is the reference of the tests and nothing else:
-        `beam_step` moves the four ring lists with torch.index_select, which is slow (a temporary copy of every ring per step), eager
-        only (MusicXLError under use_graph) and not reachable from `generate`."""
+        A decoder with kv_dtype='fp8' takes 'indexed': every step appends to the row's own slot (mxl_kv_append_fp8) -- the slot the
+        follow kernel marks as the row's own -- and mxl_relattn_decode_fp8_owned reads through the table, so no ring is ever moved.
+        'copied' on such a decoder is the reference of the tests and nothing else (rings.FP8Rings.follow_beams: index_select, a temporary
+        copy of every ring per step): eager only (MusicXLError under use_graph) and not reachable from `generate`."""
         if beam_rings not in DECODER_BEAM_RINGS:
             raise ValueError(f"beam_rings={beam_rings!r}: expected 'copied' or 'indexed'")
-        if self.kv_dtype is not None and beam_rings == 'copied' and use_graph:
-            raise MusicXLError(f"beam search on the device moves {self.kv_dtype} K/V rings with index_select alone, the eager reference "
+        if not self.layout.movable and beam_rings == 'copied' and use_graph:
+            raise MusicXLError(f"beam search on the device moves {self.layout.kv_dtype} K/V rings with index_select alone, the eager reference "
                                "of the tests: use_graph=False, or beam_rings='indexed'")
         if beam_rings == 'indexed' and self.eng.cfg.mem_len % 16:
             raise MusicXLError(f"beam_rings='indexed' takes a mem_len that is a multiple of 16, not {self.eng.cfg.mem_len}")
@@ -1832,7 +1660,7 @@ class XLDecoder(RuledGenerate):
         self.prefill(prompt, None, None, rules.with_stop((int(eos), int(pad), 0)))
         if self.beam is None or self.beam.nb != nb:
             self.beam = BeamStore(self.B // nb, nb, self.ids.shape[1], self.eng.dev)
-            self.ring_table = ops.beam_table(self.kc + self.vc)
+            self.ring_table = ops.beam_table(self.layout.rings())
         self.beam.start(ng)
         self._beam_args = (int(nb), int(eos), int(pad), float(length_penalty), bool(early_stopping), int(ng), float(diversity_penalty),
                            bool(sample), int(top_k or 0), float(1.0 if top_p is None else top_p),
@@ -1852,7 +1680,7 @@ class XLDecoder(RuledGenerate):
         self._use_graph, self._step, self.finished_by = use_graph, ('beam_step',), (self.beam.n_done, self.beam.Bs)
         steps = max_length - prompt.shape[1] - 1
         if steps > 0 and use_graph:
-            key = (('beam', beam_rings) + self._beam_args + (None if self.trace is None else self.trace.data_ptr(),)
+            key = (('beam', beam_rings) + self.layout.key + self._beam_args + (None if self.trace is None else self.trace.data_ptr(),)
                    + self.rules.graph_key(self.eng.dev))
             st = self.beam               # (logp: the step starts from the log-probabilities the last one left)
             self._capture(key, (st.scores, st.hyp_ids, st.hyp_score, st.ints, self.logp) + extra)
@@ -1883,15 +1711,8 @@ class XLDecoder(RuledGenerate):
         rules = self.beam_select()
         if self.beam_rings == 'indexed':
             ops.beam_owner_follow(self.owner, self._beam_args[0], self.beam.beam_idx, self.beam.moved, self.t_dev)
-        elif self.kv_dtype is not None:
-            # the tests' reference for indexed fp8 rings (beam_begin): bytes and exponents follow their beams by index_select; the
-            # rows of an item with moved == 0 stay (its beam_idx is not valid)
-            nb, rows = self._beam_args[0], torch.arange(self.B, device=self.eng.dev)
-            src = torch.where(self.beam.moved.repeat_interleave(nb) != 0, self.beam.beam_idx.to(torch.int64), rows)
-            for ring in self.kc + self.vc + self.ke + self.ve:
-                ring.copy_(ring.index_select(0, src))
-        else:
-            ops.beam_reorder(self.kc + self.vc, self._beam_args[0], self.beam.beam_idx, self.beam.moved, table=self.ring_table)
+        else:                       # whole ring rows move: mxl_beam_reorder, or the fp8 layout's index_select reference
+            self.layout.follow_beams(self)
         ops.decode_advance(self.t_dev, self.rng)
         if rules['grammar'] is not None or rules['in_key'] is not None or rules.get('register') is not None:
             ops.rules_advance(self.ids, self.t_dev, **rules)
@@ -1912,23 +1733,18 @@ class XLDecoder(RuledGenerate):
             raise MusicXLError(f'contrastive search on the device takes 2..{CONTRASTIVE_MAX} candidates and one decoder row per '
                                'candidate')
         c, Tp = self.eng.cfg, prompt.shape[1]
-        if self.shared_K and self.shared_K != K:
-            raise MusicXLError(f'the decoder shares a ring among {self.shared_K} candidates, the search has {K}')
-        stop = rules.with_stop((-1 if eos is None else int(eos), int(pad), 0))
-        if self.shared_K:           # the K rows of a prompt hold the same prompt: the pass runs on every K-th
-            self._prefill_shared(prompt[::K], stop)
-        else:
-            self.prefill(prompt, None, None, stop)
+        self.layout.admit_candidates(K)     # (under shared rings the pass runs on every K-th row: the K of a prompt hold the same)
+        self.prefill(prompt, None, None, rules.with_stop((-1 if eos is None else int(eos), int(pad), 0)), search='contrastive')
         if self.cs is None or self.cs.K != K:
             self.cs = ContrastiveStore(self.B // K, K, self.Tmax, c.d_model, self.eng.dev)
-            self.ring_table = ops.beam_table(self.kc + self.vc)
-        hid = self.eng._last.h[c.n_layer & 1]
-        self.cs.start(hid.view(self.B // K, Tp, c.d_model) if self.shared_K else hid.view(self.B, Tp, c.d_model)[::K])
+            self.ring_table = ops.beam_table(self.layout.rings())
+        u = self.layout.unit        # the model saw every u-th row: the first row of every sequence is every (K / u)-th of those
+        self.cs.start(self.eng._last.h[c.n_layer & 1].view(self.B // u, Tp, c.d_model)[::K // u])
         self._cs_args = (int(K), float(alpha), self.rules.stop[0], int(pad))
         self._use_graph, self._step, self.finished_by = use_graph, ('contrastive_step',), (self.cs.n_done, self.cs.B0)
         steps = max_length - Tp - 1
         if steps > 0 and use_graph:
-            key = (('contrastive', 'shared' if self.shared_K else 'copied') + self._cs_args
+            key = (('contrastive',) + self.layout.key + self._cs_args
                    + (None if self.trace is None else self.trace.data_ptr(),) + self.rules.graph_key(self.eng.dev))
             self._capture(key, (self.cs.ints, self.logp))
         self.contrastive_step()                       # the first token: column Tp
@@ -1938,8 +1754,8 @@ class XLDecoder(RuledGenerate):
         """one whole contrastive step, no host read: the rules mask on the log-probabilities, the K candidates of every sequence
         from its picked row (mxl_contrastive_topk), the position moves on, the candidates go through the model, one is picked and
         written to all K rows (mxl_contrastive_step), the rule words move along it, and the one ring slot the step wrote follows the
-        pick in every layer (mxl_ring_slot_broadcast; the invariant is stated in csrc/contrastive.hip).  With shared rings the model
-        writes no ring: the step's k / v wait in the stash and the picked row's go into the prompt's rings (mxl_kv_commit_shared)"""
+        pick in every layer (mxl_ring_slot_broadcast; the invariant is stated in csrc/contrastive.hip) -- or, with shared rings, the
+        picked row's stashed k / v go into the prompt's rings (the layout's `settle`)"""
         c, cs = self.eng.cfg, self.cs
         K, alpha, eos, pad = self._cs_args
         rules = ops.rules_in_force(**self.rules.kwargs())
@@ -1955,10 +1771,7 @@ class XLDecoder(RuledGenerate):
                              self.unfinished, cs.n_done, eos, pad, stop_later=ruled)
         if ruled:
             ops.rules_advance(self.ids, self.t_dev, **rules)
-        if self.shared_K:           # the picked row's k / v of the step become slot t mod M of the prompt's rings
-            ops.kv_commit_shared(self.kc + self.vc, self.stash, K, self.t_dev, cs.sel, table=self.ring_table)
-        else:
-            ops.ring_slot_broadcast(self.kc + self.vc, K, self.t_dev, cs.sel, table=self.ring_table)
+        self.layout.settle(self, K)     # the slot of the step follows the pick, or the picked row's stash is committed to it
 
     def _trace(self):
         if self.trace is not None:
@@ -1976,7 +1789,7 @@ class XLDecoder(RuledGenerate):
         generation with other values, such as another guide that fits the buffer, replays the same graph"""
         if max_length > self.Tmax:
             raise MusicXLError(f'max_length {max_length} exceeds the decoder buffer {self.Tmax}')
-        if self.prompt_n and self.Mt < min(self.eng.cfg.mem_len, max_length - prompt.shape[1]):
+        if self.Mt is not None and self.Mt < min(self.eng.cfg.mem_len, max_length - prompt.shape[1]):
             raise MusicXLError(f'the tail rings of this decoder hold {self.Mt} generated positions, the call asks for '
                                f'{max_length - prompt.shape[1]} (XLDecoder(tail_len=))')
         self._use_graph, self._step, self.finished_by = use_graph, ('step', sampling), (self.alive, 0)
@@ -1986,9 +1799,7 @@ class XLDecoder(RuledGenerate):
             # step() picks its launches from the sampling keys, the sampler form and whether a trace is attached (the trace buffer
             # itself is written by the captured launches): a graph captured without a trace would replay without writing one
             key = (tuple(sorted(sampling.items())), self.fused_sampler,
-                   None if self.trace is None else self.trace.data_ptr()) + self.rules.graph_key(self.eng.dev)
-            if self.prompt_n:       # the ring mode: another set of launches over other buffers (the prompt length is step state, t0_dev)
-                key += (('prompt_rings', self.prompt_n, self.Mt),)
+                   None if self.trace is None else self.trace.data_ptr()) + self.rules.graph_key(self.eng.dev) + (self.layout.key,)
             self._capture(key, (self.h[0],))      # (short chain: the next step's embedding row is step state too)
         return max(steps, 0)
 
@@ -2005,7 +1816,7 @@ class XLDecoder(RuledGenerate):
         carries from one step to the next"""
         if self.graph is not None and self._graph_key == key:
             return
-        live = (self.t_dev, self.rng, self.ids, *self.kc, *self.vc, *self.ke, *self.ve, *self.kt, *self.vt, *extra)
+        live = (self.t_dev, self.rng, self.ids, *self.layout.tensors(), *extra)
         saved, words = [t.clone() for t in live], self.rules.snapshot()
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -2041,7 +1852,7 @@ class XLDecoderLanes(RuledGenerate):
         prompts are dealt to the lanes as the rows are otherwise, so lanes <= batch / n.  The ids equal the default mode's exactly when
         both put every row at the same index of the same lane (the draw is keyed by the lane's seed and the row's index in it): when
         the default's cut falls between two prompts."""
-        unit = int(prompt_rings) or 1
+        unit = XLDecoder._layout(kv_dtype, 0, prompt_rings, tail_len).unit        # the rows that share a ring stay in one lane
         assert batch % unit == 0 and 1 <= lanes <= batch // unit
         self.B, self.Tmax, self.n, self.kv_dtype, self.prompt_n = batch, max_total_len, lanes, kv_dtype, int(prompt_rings)
         units = batch // unit
@@ -2051,6 +1862,7 @@ class XLDecoderLanes(RuledGenerate):
         # (the sampler draws per (seed, row, step): a different seed per lane keeps the lanes' draws independent)
         self.lanes = [XLDecoder(engine, b, max_total_len, seed=seed + 7919 * i, kv_dtype=kv_dtype, **more)
                       for i, b in enumerate(self.sizes)]
+        self.ring_spec = self.lanes[0].ring_spec
         self.streams = [torch.cuda.Stream() for _ in range(lanes)]
 
     def invalidate_tables(self):

@@ -399,8 +399,7 @@ class MyTransfoXLLMHeadModel(EngineModule):
                                beam_search_device, check_grammar_args, contrastive_search, contrastive_search_device, form_config,
                                group_beam_search_device, left_pad_counts, plan_search, prompt_rings_misfit, prompt_tail_len,
                                resolve_beam_rings, resolve_contrastive_rings, resolve_kv_dtype, resolve_prompt_rings,
-                               resolve_max_length,
-                               rules_config, sampling_config, stop_config)
+                               resolve_max_length, rules_config, sampling_config, stop_config)
         kv_dtype = resolve_kv_dtype(kv_cache_dtype)
         n_pad = None
         if attention_mask is not None:
@@ -493,10 +492,9 @@ class MyTransfoXLLMHeadModel(EngineModule):
                 raise MusicXLError(misfit)
             if not misfit:                                  # (the environment's default is ignored where the model does not fit)
                 lanes, rings = cut, dict(prompt_rings=num_return_sequences, tail_len=max_length - input_ids.shape[1])
-        tail = prompt_tail_len(self.config.mem_len, max_length - input_ids.shape[1]) if rings else None
-        if (dec is None or dec.B != B or dec.Tmax < max_length or getattr(dec, 'n', 1) != lanes
-                or getattr(dec, 'kv_dtype', None) != kv_dtype or getattr(dec, 'prompt_n', 0) != rings.get('prompt_rings', 0)
-                or getattr(getattr(dec, 'lanes', [dec])[0], 'Mt', None) != tail):
+        # the ring format, the rows per prompt ring and the slots of a tail ring: what the cached decoder must have been built for
+        spec = (kv_dtype, rings.get('prompt_rings', 0), prompt_tail_len(self.config.mem_len, rings['tail_len']) if rings else None)
+        if dec is None or dec.B != B or dec.Tmax < max_length or getattr(dec, 'n', 1) != lanes or dec.ring_spec != spec:
             dec = self._decoder = (XLDecoderLanes(self.engine, B, max_length, seed=seed, lanes=lanes, kv_dtype=kv_dtype, **rings)
                                    if lanes > 1 else XLDecoder(self.engine, B, max_length, seed=seed, kv_dtype=kv_dtype, **rings))
         dec.invalidate_tables()

@@ -1,0 +1,485 @@
+"""What `generate.XLDecoder` launches for every K/V ring mode, recorded without a GPU: decoders built on torch.device('cpu') over a
+stub engine, with every launching function of `ops` replaced by a recorder that logs its name and its arguments -- tensors by the
+decoder attribute they are (`kc[1]`, `kt[0]`, `stash[1]`, `qkv`, `owner`, `unfinished`, ...), everything else by value.  Per decoder
+the record holds what it allocates, the launches of the prompt pass (with the prompt rows that reached the model and the rows of
+`logp` / `tmp` it wrote), of one `_forward_token` with and without a stop rule, of `beam_begin` / `beam_step`, of
+`contrastive_begin` / `contrastive_step`, which successive captures share a graph key, and every refusal with its type and message.
+tests/test_decoder_launches_cpu.py asserts the table.
+
+The table is a record of behaviour, not a statement of what is right: regenerate it only at the commit BEFORE a change to the
+decoder, and let the test show that the change leaves it as it was.
+
+    python tests/golden/make_decoder_launches.py        # writes tests/golden/decoder_launches.json
+"""
+import inspect
+import json
+import os
+import sys
+from types import SimpleNamespace
+
+import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+OUT = os.path.join(HERE, 'decoder_launches.json')
+
+CFG = dict(d_model=32, n_head=2, d_head=16, d_inner=64, n_layer=2, mem_len=32, vocab_size=40, cutoffs=[], clamp_len=-1,
+           layer_norm_epsilon=1e-5)
+HEAD_ROWS = 48           # the head's rows padded past the vocabulary
+TP, GEN = 3, 6           # prompt columns and generated positions of every call
+STOP = (39, 0, 0)
+ENVS = ('MXL_DECODE_UNFUSED', 'MXL_DECODE_PIECES')
+DECODERS = (('plain8', dict(batch=8)), ('plain65', dict(batch=65)), ('fp8', dict(batch=8, kv_dtype='fp8')),
+            ('shared4', dict(batch=8, shared_rings=4)), ('shared8', dict(batch=16, shared_rings=8)),
+            ('prompt4', dict(batch=8, prompt_rings=4, tail_len=10)), ('prompt8', dict(batch=16, prompt_rings=8)))
+RINGS = ('kc', 'vc', 'ke', 've', 'kt', 'vt')
+
+# the functions of `ops` a decoder launches: logged, not run
+LAUNCHES = ('gemm', 'gemm_skinny', 'gemm_skinny_partial', 'ln_residual_fwd', 'ln_residual_fwd_partial', 'decode_qkv', 'decode_embed',
+            'kv_append', 'kv_fill', 'kv_append_fp8', 'kv_fill_fp8', 'relattn_decode', 'relattn_decode_fp8', 'kv_stash',
+            'relattn_decode_shared', 'kv_commit_shared', 'kv_append_tail', 'relattn_decode_prefix', 'adaptive_logprob', 'sample_step',
+            'sample', 'decode_advance', 'rules_mask', 'rules_advance', 'beam_step', 'beam_sample_draw', 'beam_sample_step',
+            'beam_reorder', 'beam_owner_follow', 'beam_table', 'ring_slot_broadcast', 'contrastive_topk', 'contrastive_step',
+            'contrastive_select', 'row_inv_norm', 'sinusoid_table', 'grammar_scan', 'budget_scan', 'key_scan', 'register_scan')
+# host-side helpers of `ops` that launch nothing: left as they are
+PURE = ('mix_seed', 'rules_in_force', 'decode_ring_pieces', 'relattn_decode_split_scratch', 'prefix_attn_groups')
+# the two that ask the library: a stand-in that fits mem_len 32 and does not fit 512
+LDS = ('relattn_decode_shared_lds_bytes', 'relattn_decode_prefix_lds_bytes')
+
+
+class Recorder:
+    """the log of the launches, and the names of the tensors they are handed"""
+
+    def __init__(self):
+        self.log, self.dec, self.eng = [], None, None
+
+    def named(self) -> list:
+        """(name, tensor) of everything a launch may be handed: the decoder's buffers first, whole stores after their words"""
+        out, dec = [], self.dec
+
+        def add(name, v):
+            if isinstance(v, torch.Tensor):
+                out.append((name, v))
+            elif isinstance(v, (list, tuple)):
+                for i, t in enumerate(v):
+                    add(f'{name}[{i}]', t)
+        if dec is not None:
+            from symbolic_music_generation_amd.generate import RowRules
+            for k in RINGS + ('stash', 't0_dev', 'owner', 'ids', 't_dev', 'rng', 'h', 'qkv', 'av', 'qr', 'slabs', 'bd', 'tmp', 'h1', 'a',
+                              'logits', 'logp', 'step_ctr', 'drawn', 'ring_table', 'split', 'rd', 'trace') + RowRules.STATE:
+                add(k, getattr(dec, k, None))
+            for k in ('gbad', 'guide', 'glen', 'plan', 'nplan', 'barcol', 'buf'):
+                add(f'rules.{k}', getattr(dec.rules, k, None))
+            for store in ('beam', 'cs'):
+                for k, v in sorted(vars(getattr(dec, store, None) or SimpleNamespace()).items()):
+                    add(f'{store}.{k}', v)
+        for k, v in self.eng.tensors.items():
+            add(k, v)
+        return out
+
+    def name(self, v) -> str:
+        if isinstance(v, torch.Tensor):
+            return self.tensor_name(v)
+        if isinstance(v, (list, tuple)):
+            return '[' + ', '.join(self.name(x) for x in v) + ']'
+        if isinstance(v, dict):
+            return '{' + ', '.join(f'{k}: {self.name(x)}' for k, x in v.items()) + '}'
+        if v is None or isinstance(v, (bool, int, float, str)):
+            return repr(v)
+        return f'<{type(v).__name__}>'
+
+    def tensor_name(self, t: torch.Tensor) -> str:
+        where = t.untyped_storage().data_ptr()
+        near = None
+        for name, x in self.named():
+            if x.numel() == 0 or x.untyped_storage().data_ptr() != where:
+                continue
+            if x.storage_offset() == t.storage_offset() and x.shape == t.shape and x.stride() == t.stride():
+                return name
+            off = t.storage_offset() - x.storage_offset()
+            if (x.dim() == t.dim() + 1 and x.shape[1:] == t.shape and x.stride()[1:] == t.stride() and x.stride(0) > 0
+                    and off % x.stride(0) == 0 and 0 <= off // x.stride(0) < x.shape[0]):
+                return f'{name}[{off // x.stride(0)}]'
+            near = near or f'view({name}, {tuple(t.shape)}, stride {tuple(t.stride())}, at {off})'
+        return near or f'tmp({str(t.dtype)[6:]}, {tuple(t.shape)})'
+
+    def take(self) -> list:
+        out, self.log = self.log, []
+        return out
+
+
+REC = Recorder()
+
+
+def _effect(name: str, args: dict):
+    """what a stand-in leaves behind so that the record can tell where a result went"""
+    if name == 'adaptive_logprob':                     # row i of the output <- i + 1
+        out = args['out']
+        out.copy_(torch.arange(1, out.shape[0] + 1, dtype=out.dtype)[:, None].expand_as(out))
+    elif name == 'beam_step':                          # item 0 stays, every other item reverses its beams
+        idx, nb = args['beam_idx'], args['nb']
+        rows = torch.arange(idx.numel())
+        idx.copy_(((rows // nb) * nb + (nb - 1 - rows % nb)).to(idx.dtype))
+        args['moved'].fill_(1)
+        args['moved'][0] = 0
+    elif name == 'contrastive_topk':                   # where the prompt pass left its results, before the step's head overwrites them
+        src = lambda t: [int(v) for v in torch.nan_to_num(t[:, 0].float(), nan=0.0).tolist()]
+        REC.log.append(f'  (logp rows from {src(args["logp"])}, tmp rows from {src(REC.dec.tmp)})')
+    elif name == 'sinusoid_table':
+        return torch.zeros(args['M'], args['d'], dtype=torch.bfloat16)
+    elif name == 'row_inv_norm':
+        return args['out']
+    return None
+
+
+def _recorder(name: str, real):
+    sig = inspect.signature(real)
+
+    def rec(*a, **k):
+        bound = sig.bind(*a, **k)
+        bound.apply_defaults()
+        shown = ', '.join(f'{p}={REC.name(v)}' for p, v in bound.arguments.items()
+                          if not (v is sig.parameters[p].default or (not isinstance(v, torch.Tensor) and v == sig.parameters[p].default)))
+        REC.log.append(f'{name}({shown})')
+        if name == 'beam_table':
+            return real(*a, **k)
+        return _effect(name, dict(bound.arguments))
+    return rec
+
+
+def _unknown(name: str):
+    def refuse(*a, **k):
+        raise AssertionError(f'ops.{name} was called and the record does not know it')
+    return refuse
+
+
+class patched:
+    """every public function of `ops` replaced -- the launches by recorders, the two library queries by a stand-in, anything unknown by
+    a function that raises -- and the environment switches that pick launches removed; restored on exit"""
+
+    def __enter__(self):
+        from symbolic_music_generation_amd import ops
+        self.ops = ops
+        self.saved = {n: f for n, f in vars(ops).items() if inspect.isfunction(f) and f.__module__ == ops.__name__
+                      and not n.startswith('_') and n not in PURE}
+        for n, f in self.saved.items():
+            if n in LDS:
+                stub = lambda k, dh, M, pieces=1: int(M) * 1024
+            else:
+                stub = _recorder(n, f) if n in LAUNCHES else _unknown(n)
+            setattr(ops, n, stub)
+        self.env = {k: os.environ.pop(k, None) for k in ENVS}
+        return self
+
+    def __exit__(self, *exc):
+        for n, f in self.saved.items():
+            setattr(self.ops, n, f)
+        for k, v in self.env.items():
+            if v is not None:
+                os.environ[k] = v
+        REC.dec = REC.eng = None
+        REC.log = []
+
+
+class Engine:
+    """stands for the TransfoXL engine: a config, named weights, and a `forward` that hands every layer's qkv rows to `kv_sink` and
+    leaves `_last` -- hid rows hold 1 + the prompt row they belong to, so that what is copied from them tells its source"""
+
+    def __init__(self, bucketed: bool = False, **cfg):
+        self.cfg = SimpleNamespace(**dict(CFG, **cfg))
+        self.dev = torch.device('cpu')
+        self.bucketed = bucketed                    # the large-vocabulary head: `_last.logits` is None
+        d = self.cfg.d_model
+        self.layout = SimpleNamespace(n_head_rows=self.cfg.vocab_size, head_rows_padded=HEAD_ROWS,
+                                      entries={'crit.out_layers.0.bias': (0,)})
+        self.tensors = {}
+        self.W = self.tensors['W'] = torch.zeros(HEAD_ROWS * d, dtype=torch.bfloat16)
+        self.P = self.tensors['P'] = torch.zeros(HEAD_ROWS, dtype=torch.float32)
+        self.forwards = []
+
+    def _named(self, name: str, shape, dtype):
+        if name not in self.tensors:
+            self.tensors[name] = torch.zeros(shape, dtype=dtype)
+        return self.tensors[name]
+
+    def _lw(self, l, name, src=None):
+        c = self.cfg
+        return self._named(f'lw{l}.{name}', (c.n_head, c.d_head), torch.bfloat16 if src is None else torch.float32)
+
+    def w16(self, name):
+        return self._named(f'w16.{name}', (self.cfg.vocab_size, self.cfg.d_model), torch.bfloat16)
+
+    def forward(self, x, mems=None, labels=None, train=False, want_logprobs=False, kv_sink=None, n_pad=None):
+        c = self.cfg
+        B, T = x.shape
+        REC.log.append(f'forward(x={tuple(x.shape)} first column {x[:, 0].tolist()}, mems={mems!r}, '
+                       f'n_pad={None if n_pad is None else n_pad.tolist()})')
+        for k in [k for k in self.tensors if k.startswith(('fwd.', 'last.'))]:
+            del self.tensors[k]
+        for l in range(c.n_layer):
+            kv_sink(l, self._named(f'fwd.qkv[{l}]', (B * T, 3 * c.d_model), torch.bfloat16))
+        hid = self._named('last.hid', (B * T, c.d_model), torch.bfloat16)
+        hid.copy_((torch.arange(B * T) // T + 1)[:, None].expand_as(hid))
+        self._last = SimpleNamespace(logits=None if self.bucketed else self._named('last.logits', (B * T, HEAD_ROWS), torch.float32),
+                                     hid=hid, h=[self._named(f'last.h[{i}]', (B * T, c.d_model), torch.bfloat16) for i in range(2)])
+        return 'out'
+
+
+def decoder(kw: dict, bucketed: bool = False, tmax: int = TP + GEN, **cfg):
+    from symbolic_music_generation_amd.generate import XLDecoder
+    REC.dec, REC.eng = None, Engine(bucketed, **cfg)
+    REC.dec = XLDecoder(REC.eng, max_total_len=tmax, **kw)
+    REC.take()
+    return REC.dec
+
+
+def attempt(f):
+    """('ok', result) or ('refused', 'Type: message'); the log is taken either way"""
+    from symbolic_music_generation_amd._lib import MusicXLError
+    try:
+        return 'ok', f()
+    except (ValueError, MusicXLError) as x:
+        return 'refused', f'{type(x).__name__}: {x}'
+
+
+def unit_of(kw: dict) -> int:
+    return kw.get('prompt_rings', 0) or 1
+
+
+def prompt_of(kw: dict, Tp: int = TP) -> torch.Tensor:
+    """(batch, Tp) prompts, row b starting with token 1 + b mod 37; under prompt rings every prompt n times in a row"""
+    u = unit_of(kw)
+    first = torch.arange(kw['batch'] // u) % 37 + 1
+    return torch.cat([first[:, None], torch.full((first.numel(), Tp - 1), 2)], 1).repeat_interleave(u, 0)
+
+
+def after_pass(dec, bucketed: bool) -> dict:
+    """where the prompt pass left its results: the source row (1-based, 0 = not written) of every row of logp -- of tmp under the
+    bucketed head -- and the positions"""
+    src = dec.tmp[:, 0].float() if bucketed else torch.nan_to_num(dec.logp[:, 0], nan=0.0)
+    t0 = getattr(dec, 't0_dev', None)
+    return dict(rows=[int(v) for v in src.tolist()], t=int(dec.t_dev), t0=None if t0 is None else int(t0))
+
+
+def record_build(dec) -> dict:
+    shape = lambda t: None if t is None else [list(t.shape), str(t.dtype)[6:]]
+    out = {k: [len(getattr(dec, k))] + (shape(getattr(dec, k)[0]) if getattr(dec, k) else []) for k in RINGS}
+    out.update(stash=shape(getattr(dec, 'stash', None)), t0_dev=shape(getattr(dec, 't0_dev', None)), Mt=getattr(dec, 'Mt', None),
+               pieces=dec.pieces, split=dec.split is None, shared_K=dec.shared_K, prompt_n=dec.prompt_n, kv_dtype=dec.kv_dtype,
+               beam_rings=dec.beam_rings, owner=dec.owner is None)
+    return out
+
+
+def record_begin(kw: dict) -> dict:
+    """the prompt pass through `begin` (eager): plain, under a stop rule, with left pads, and under the bucketed head"""
+    from symbolic_music_generation_amd.generate import NO_RULES, RulePlan, sampling_config
+    out = {}
+    for label, rules, pads, bucketed in (('plain', NO_RULES, False, False), ('stop', RulePlan(stop=STOP), False, False),
+                                         ('padded', NO_RULES, True, False), ('bucketed', NO_RULES, False, True)):
+        dec = decoder(kw, bucketed)
+        dec.logp.fill_(float('nan'))
+        dec.tmp.zero_()
+        n_pad = (torch.arange(dec.B, dtype=torch.int32) // unit_of(kw)) % 2 if pads else None
+        how, res = attempt(lambda: dec.begin(prompt_of(kw), TP + GEN, sampling_config(), False, n_pad, rules))
+        out[label] = dict(how=how, result=res, log=REC.take())
+        if how == 'ok':
+            out[label].update(after_pass(dec, bucketed))
+            if pads:
+                out[label]['ids'] = dec.ids[:, :TP].tolist()
+    return out
+
+
+def record_forward_token(dec) -> dict:
+    out = {}
+    for label, stop in (('free', None), ('stop', STOP)):
+        dec.rules.stop = stop
+        dec._forward_token()
+        out[label] = REC.take()
+    return out
+
+
+def ring_rows(dec) -> dict:
+    """the first element of every row of the first ring of each kind"""
+    return {k: getattr(dec, k)[0].flatten(1)[:, 0].float().tolist() for k in RINGS if getattr(dec, k)}
+
+
+def mark_rings(dec):
+    for k in RINGS:
+        for t in getattr(dec, k):
+            t.copy_(torch.arange(t.shape[0]).view(-1, *[1] * (t.dim() - 1)).expand_as(t))
+
+
+def record_beam(kw: dict) -> dict:
+    """`beam_begin` and `beam_step` on the device's path (eager) under both beam_rings, then the host search's hooks"""
+    out = {}
+    nb = 5 if kw['batch'] % 4 else 4
+    for mode in ('copied', 'indexed'):
+        dec = decoder(kw)
+        how, res = attempt(lambda: dec.beam_begin(prompt_of(kw), TP + GEN, nb, 39, 0, 1.0, True, False, beam_rings=mode))
+        out[mode] = dict(how=how, result=res, begin=REC.take())
+        if how == 'ok':
+            mark_rings(dec)
+            dec.beam_step()
+            out[mode].update(step=REC.take(), rings=ring_rows(dec), token=record_forward_token(dec))
+    dec = decoder(kw)
+    how, res = attempt(lambda: dec.beam_prefill(prompt_of(kw)))
+    out['host'] = dict(how=how, result=res, prefill=REC.take())
+    if how == 'ok':
+        mark_rings(dec)
+        dec.beam_reorder(torch.arange(dec.B - 1, -1, -1))
+        out['host'].update(reorder=REC.take(), rings=ring_rows(dec))
+    return out
+
+
+def record_contrastive(kw: dict) -> dict:
+    """`contrastive_begin` (eager; it runs the first step) and one more `contrastive_step`, for the decoder's K and for another"""
+    out = {}
+    K = kw.get('shared_rings', 0) or (5 if kw['batch'] % 4 else 4)
+    for label, k, bucketed in (('own', K, False), ('other', 2, False), ('bucketed', K, True)):
+        dec = decoder(kw, bucketed)
+        dec.logp.fill_(float('nan'))
+        dec.tmp.zero_()
+        how, res = attempt(lambda: dec.contrastive_begin(prompt_of(kw), TP + GEN, k, 0.6, 39, 0, False))
+        out[label] = dict(how=how, result=res, begin=REC.take())
+        if how == 'ok':
+            dec.contrastive_step()
+            out[label]['step'] = REC.take()
+    return out
+
+
+def record_keys(kw: dict) -> dict:
+    """which captures one decoder would share: the begins below in order under use_graph, `_capture` replaced by a recorder; entry i
+    is the first begin whose graph key equals that of begin i (None: it captured nothing), with the extra tensors it snapshots"""
+    from symbolic_music_generation_amd.generate import NO_RULES, RulePlan, sampling_config
+    dec = decoder(kw)
+    keys, seen = [], []
+    dec._capture = lambda key, extra: seen.append((key, REC.name(list(extra))))
+    nb = 5 if kw['batch'] % 4 else 4
+    K = kw.get('shared_rings', 0) or nb
+    calls = (('begin', lambda: dec.begin(prompt_of(kw), TP + GEN, sampling_config(), True)),
+             ('begin longer prompt', lambda: dec.begin(prompt_of(kw, TP + 1), TP + GEN, sampling_config(), True)),
+             ('begin sampled', lambda: dec.begin(prompt_of(kw), TP + GEN, sampling_config(True, 5), True)),
+             ('begin stop', lambda: dec.begin(prompt_of(kw), TP + GEN, sampling_config(), True, None, RulePlan(stop=STOP))),
+             ('beam copied', lambda: dec.beam_begin(prompt_of(kw), TP + GEN, nb, 39, 0, 1.0, True, True, NO_RULES, beam_rings='copied')),
+             ('beam indexed', lambda: dec.beam_begin(prompt_of(kw), TP + GEN, nb, 39, 0, 1.0, True, True, NO_RULES, beam_rings='indexed')),
+             ('contrastive', lambda: dec.contrastive_begin(prompt_of(kw), TP + GEN, K, 0.6, 39, 0, True)))
+    out = {}
+    for label, call in calls:
+        seen.clear()
+        how, res = attempt(call)
+        REC.take()
+        same = extra = None
+        if seen:
+            key, extra = seen[0]
+            same = next((i for i, k in enumerate(keys) if k == key), len(keys))
+        keys.append(seen[0][0] if seen else object())
+        out[label] = dict(how=how, result=res, same_key_as=same, extra=extra)
+    return out
+
+
+def record_refusals() -> dict:
+    """what the constructor and the helpers around it refuse, and a few of the values they return"""
+    from symbolic_music_generation_amd.generate import prompt_rings_misfit, prompt_tail_len, sampling_config
+    out = {}
+    builds = dict([
+        ('kv_dtype int8', (dict(batch=8, kv_dtype='int8'), {})),
+        ('prompt rings + fp8', (dict(batch=8, prompt_rings=4, kv_dtype='fp8'), {})),
+        ('prompt rings + shared rings', (dict(batch=8, prompt_rings=4, shared_rings=4), {})),
+        ('prompt rings n=1', (dict(batch=8, prompt_rings=1), {})),
+        ('prompt rings batch 9', (dict(batch=9, prompt_rings=4), {})),
+        ('prompt rings d_head 24', (dict(batch=8, prompt_rings=4), dict(d_head=24, d_model=48))),
+        ('prompt rings mem_len 40', (dict(batch=8, prompt_rings=4), dict(mem_len=40))),
+        ('prompt rings mem_len 8', (dict(batch=8, prompt_rings=4), dict(mem_len=8))),
+        ('prompt rings mem_len 512', (dict(batch=8, prompt_rings=4), dict(mem_len=512))),
+        ('prompt rings n=8 mem_len 512', (dict(batch=16, prompt_rings=8), dict(mem_len=512))),
+        ('shared rings + fp8', (dict(batch=8, shared_rings=4, kv_dtype='fp8'), {})),
+        ('shared rings K=1', (dict(batch=8, shared_rings=1), {})),
+        ('shared rings K=33', (dict(batch=66, shared_rings=33), {})),
+        ('shared rings batch 9', (dict(batch=9, shared_rings=4), {})),
+        ('shared rings d_head 24', (dict(batch=8, shared_rings=4), dict(d_head=24, d_model=48))),
+        ('shared rings mem_len 512', (dict(batch=8, shared_rings=4), dict(mem_len=512))),
+        ('shared rings K=8 mem_len 512', (dict(batch=16, shared_rings=8), dict(mem_len=512))),
+        ('shared rings mem_len 40', (dict(batch=8, shared_rings=4), dict(mem_len=40))),
+        ('fp8 d_head 24', (dict(batch=8, kv_dtype='fp8'), dict(d_head=24, d_model=48))),
+        ('fp8 mem_len 40', (dict(batch=8, kv_dtype='fp8'), dict(mem_len=40))),
+        ('plain d_head 24', (dict(batch=8), dict(d_head=24, d_model=48))),
+    ])
+    for label, (kw, cfg) in builds.items():
+        how, res = attempt(lambda: record_build(decoder(kw, **cfg)))
+        out[f'build: {label}'] = dict(how=how, result=res)
+    cfg = lambda **k: SimpleNamespace(**dict(CFG, **k))
+    out['prompt_rings_misfit'] = [prompt_rings_misfit(cfg(**c), n, rows) for c, n, rows in (
+        ({}, 4, 8), ({}, 8, 16), (dict(d_head=24), 4, 8), (dict(mem_len=40), 4, 8), (dict(mem_len=0), 4, 8), (dict(mem_len=512), 4, 8),
+        (dict(mem_len=2048), 2, 8))]
+    out['prompt_tail_len'] = [prompt_tail_len(M, g) for M, g in ((32, 1), (32, 16), (32, 17), (32, 100), (64, 0), (1024, 33))]
+    # what the begins refuse on a decoder that could be built
+    dec = decoder(dict(batch=8, prompt_rings=4, tail_len=10))
+    out['prompt rings: prompts not repeated'] = attempt(lambda: dec.begin(prompt_of(dict(batch=8)), TP + GEN, sampling_config(), False))
+    dec = decoder(dict(batch=8, prompt_rings=4, tail_len=10), tmax=TP + 20)
+    out['prompt rings: tail too short'] = attempt(lambda: dec.begin(prompt_of(dict(batch=8, prompt_rings=4)), TP + 20, sampling_config(),
+                                                                    False))
+    dec = decoder(dict(batch=8))
+    out['begin: beyond the buffer'] = attempt(lambda: dec.begin(prompt_of(dict(batch=8)), TP + GEN + 1, sampling_config(), False))
+    dec = decoder(dict(batch=8, kv_dtype='fp8'))
+    out['fp8 beam copied under the graph'] = attempt(lambda: dec.beam_begin(prompt_of(dict(batch=8)), TP + GEN, 4, 39, 0, 1.0, True, True))
+    dec = decoder(dict(batch=8), mem_len=40)
+    out['beam indexed mem_len 40'] = attempt(lambda: dec.beam_begin(prompt_of(dict(batch=8)), TP + GEN, 4, 39, 0, 1.0, True, False,
+                                                                     beam_rings='indexed'))
+    dec = decoder(dict(batch=8))
+    out['beam_rings other'] = attempt(lambda: dec.beam_begin(prompt_of(dict(batch=8)), TP + GEN, 4, 39, 0, 1.0, True, False,
+                                                              beam_rings='indexed_fp8'))
+    REC.take()
+    return {k: list(v) if isinstance(v, tuple) else v for k, v in out.items()}
+
+
+def record() -> dict:
+    """the whole table as plain lists, dicts, strings and numbers"""
+    with patched():
+        out = {}
+        for name, kw in DECODERS:
+            dec = decoder(kw)
+            dec._tables()
+            REC.take()
+            out[name] = dict(build=record_build(dec), token=record_forward_token(dec), begin=record_begin(kw), beam=record_beam(kw),
+                             contrastive=record_contrastive(kw), keys=record_keys(kw))
+        out['refusals'] = record_refusals()
+        assert REC.log == []
+        return json.loads(json.dumps(out))
+
+
+def pack(rec) -> dict:
+    """the table with every string replaced by its index in a list of the distinct ones (the launches repeat a lot)"""
+    strings = {}
+
+    def walk(x):
+        if isinstance(x, str):
+            return {'s': strings.setdefault(x, len(strings))}
+        if isinstance(x, list):
+            return [walk(v) for v in x]
+        if isinstance(x, dict):
+            return {'d': [[k, walk(v)] for k, v in x.items()]}
+        return x
+    table = walk(rec)
+    return dict(strings=list(strings), table=table)
+
+
+def unpack(packed: dict):
+    strings = packed['strings']
+
+    def walk(x):
+        if isinstance(x, dict):
+            return strings[x['s']] if 's' in x else {k: walk(v) for k, v in x['d']}
+        if isinstance(x, list):
+            return [walk(v) for v in x]
+        return x
+    return walk(packed['table'])
+
+
+if __name__ == '__main__':
+    rec = record()
+    packed = pack(rec)
+    assert unpack(packed) == rec
+    with open(OUT, 'w') as f:
+        json.dump(packed, f, separators=(',', ':'))
+        f.write('\n')
+    print(f'{len(packed["strings"])} distinct strings -> {OUT} ({os.path.getsize(OUT)} bytes)')
