@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define MXL_ABI_VERSION 2
+#define MXL_ABI_VERSION 3
 
 int mxl_abi_version(void);
 /* human-readable text for a negative libmusicxl code or a positive hipError_t */
@@ -478,15 +478,15 @@ int mxl_sample_large(const float* logprobs, int ldl, int V, void* ids, int ld_id
 /* t_dev += 1; rng_ctr += 1 */
 int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
 /* ------------------------------------------------------------------------------------------------------------
- * Rules of a generation.  Eight optional groups of per-row state on the device, applied around every sampled token; three entries take
- * the first four as the same flat argument list (below): mxl_sample_step, mxl_rules_mask, mxl_rules_advance, their mxl_keyed_*
- * forms take the fifth after it, their mxl_guided_* forms the sixth after that, their mxl_ranged_* forms the seventh after that and
- * their mxl_formed_* forms the eighth after that.
+ * Rules of a generation.  Eight optional groups of per-row state on the device, applied around every sampled token.  They cross the
+ * ABI as one struct, mxl_rules (below), which three entries take by pointer: mxl_sample_step, mxl_rules_mask, mxl_rules_advance.  The
+ * struct is read during the call and handed to the kernel by value: the caller may reuse it at once.  A zero-initialised struct
+ * means every group is off.
  * A group is off when its state pointer is NULL: unfinished (with alive), gstate (with allow, next), gbar (with grem, slots, bars),
  * gleft, gkey (with keys, pcs, inkey), gpos (with gforce, guide, glen), gpart (with gfloor, grange, reg), gcopy (with gbars, gstop,
  * plan, nplan, barcol).  Within a group either every pointer is given or none; the budget, the count, the guide and the repeat need
- * `cls`; the repeat also needs the count and, where the words move, the stop group, and is never on beside the guide; anything else
- * is MXL_EINVAL.
+ * `cls`; the repeat also needs the count and, where the words move, the stop group, and is never on beside the guide; anything else,
+ * a NULL or misaligned `rules` included, is MXL_EINVAL.
  *
  * stop: eos_id, pad_id, min_length, unfinished, alive -- stopping at eos (HF greedy_search / sample with an eos_token_id).
  *   unfinished (B,) int32 (1 = live; set to 1 before the first sampled token) and alive, one int32 = the number of live rows after
@@ -516,7 +516,7 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  *   music grammar: <bar> and </s>).  A class in count is barred at gleft == 0, a class in end while gleft > 0, and a kept token of a
  *   count class takes 1 from a positive gleft.  Under a bar budget the end class is thereby the only one left when the last bar is
  *   full; without one the rule cannot force the end, it only bars a further bar and an early end.
- * key: keys, pcs, inkey, gkey (the mxl_keyed_* entries) -- a row whose key is known emits only pitches of that key.  Per row one int32
+ * key: keys, pcs, inkey, gkey -- a row whose key is known emits only pitches of that key.  Per row one int32
  *   word: gkey, -1 = the row has no key and is untouched, 0..23 = the ordinal of its key (the order of the reference's key enum, which
  *   the in-key ratio metric uses).  Tables: keys (V,) uint8, key token -> ordinal, 0xFF = any other token; pcs (V,) uint8, pitch token
  *   -> pitch class 0..11, 0xFF = anything the metric does not count as a pitch (rests and the rare-pitch token included: they are never
@@ -528,7 +528,7 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  *   step, degree), so wherever the grammar or the budget allows "a pitch" -- they judge the class of a token, never which pitch it is --
  *   a pitch of the row's key remains (besides the rest, which the rule never bars).  The host checks it when the tables are built: every
  *   key keeps at least one pitch token.
- * guide: guide, ld_guide, glen, enter, leave, gpos, gforce (the mxl_guided_* entries) -- part of a row's output is given, not chosen:
+ * guide: guide, ld_guide, glen, enter, leave, gpos, gforce -- part of a row's output is given, not chosen:
  *   in the music grammar the <bar> <melody> ... <bass> span of every bar, under which the row writes the bass.  Per row two int32
  *   words: gpos, the next index into the row's guide, and gforce, 1 = the row is being fed from its guide, 0 = it chooses freely.
  *   Tables: guide (B, ld_guide) int32, each row's guide tokens; glen (B,) int32, each row's guide length (<= ld_guide), 0 = the row
@@ -541,7 +541,7 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  *   += 1 -- it is the guide's own <bar>.  The words of every other group move along a forced token as along a chosen one.  The group
  *   does not stop a row: the caller sets gleft to the number of bars in the guide, so the count group bars the end while guided bars
  *   are owed and a further bar once none is.
- * register: reg, grange, gpart, gfloor, gap (the mxl_ranged_* entries) -- every part stays in its register, and the bass under the
+ * register: reg, grange, gpart, gfloor, gap -- every part stays in its register, and the bass under the
  *   melody.  Per row three int32 words: grange, the row's bounds lo_melody, hi_melody, lo_bass, hi_bass as inclusive MIDI numbers, one
  *   byte each from the lowest (fixed for the generation, never written; 0, 127, 0, 127 = unconstrained); gpart, 0 = no part is open,
  *   1 = the melody, 2 = the bass; gfloor, the lowest melody pitch of the open bar, 128 = none yet.  One scalar for the launch: gap, -1
@@ -559,7 +559,7 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  *   the rare-pitch token are such tokens and belong to the grammar's class `pitch`, and the budget judges a pitch by that class alone,
  *   so wherever the grammar or the budget allows "a pitch" one of the two remains even when the bounds leave no pitched token (the
  *   floor under lo_bass, say).  The key rule never bars them either.
- * repeat: plan, ld_plan, nplan, barcol, renter, rleave, span, gbars, gcopy, gstop (the mxl_formed_* entries) -- song form: a planned
+ * repeat: plan, ld_plan, nplan, barcol, renter, rleave, span, gbars, gcopy, gstop -- song form: a planned
  *   bar repeats an earlier bar the row generated itself, token for token, out of the row's own id history.  A row's generated bars
  *   are the bars it opens after its prompt, numbered 0, 1, ... in the order of their `enter` tokens; the bar open at the end of the
  *   prompt is finished freely and has no number, as the count group counts.  Tables: plan (B, ld_plan) int32, plan[b][k] = -1:
@@ -593,132 +593,78 @@ int mxl_decode_advance(int* t_dev, unsigned long long* rng_ctr, void* stream);
  * The words move along the token a row keeps, after the stop rule: a row that was finished before the step emits pad and keeps its
  * words; the step in which a row emits eos still moves them.  Each row's words are read and written for that row alone.
  * ---------------------------------------------------------------------------------------------------------- */
+/* The groups above, in that order, as the kernels take them.  `unsigned` is a 32-bit word.  With gpart NULL `gap` is ignored, with
+ * gcopy NULL renter / rleave / span / hist / ld_hist are.  The next rule is one more group at the end and a new MXL_ABI_VERSION. */
+typedef struct mxl_rules {
+    int eos_id, pad_id, min_length;     /* stop */
+    int* unfinished;
+    int* alive;
+    const unsigned char* cls;           /* grammar; the token classes also serve budget, count, guide and repeat */
+    const unsigned* allow;
+    const unsigned char* next;
+    int C;
+    int* gstate;
+    const unsigned short* slots;        /* budget */
+    const unsigned short* bars;
+    unsigned opens, need_free, need_full;
+    int* gbar;
+    int* grem;
+    unsigned count, end;                /* count */
+    int* gleft;
+    const unsigned char* keys;          /* key */
+    const unsigned char* pcs;
+    const unsigned short* inkey;
+    int* gkey;
+    const int* guide;                   /* guide */
+    int ld_guide;
+    const int* glen;
+    unsigned enter, leave;
+    int* gpos;
+    int* gforce;
+    const unsigned char* reg;           /* register */
+    const int* grange;
+    int* gpart;
+    int* gfloor;
+    int gap;
+    const int* plan;                    /* repeat */
+    int ld_plan;
+    const int* nplan;
+    int* barcol;
+    unsigned renter, rleave;
+    int span;
+    int* gbars;
+    int* gcopy;
+    int* gstop;
+    const long long* hist;              /* the rows' ids (B, ld_hist) int64, read by mxl_rules_mask alone */
+    int ld_hist;
+} mxl_rules;
+/* sizeof(mxl_rules) as the library was built: a binding that lays the struct out itself compares its own size with this */
+size_t mxl_rules_size(void);
 /* mxl_sample + mxl_decode_embed of the sampled token + mxl_decode_advance + the rules in one launch -- the tail of one decode step
  * and the head of the next.  The row's workgroup writes ids[b][t + 1] and emb_out[b] = E[token] * scale (bf16, (B, d)), the token
  * being the one after the stop rule (pad for a finished row); the workgroup that finishes last advances *t_dev and *rng_ctr and
  * writes *alive (counter: one int, zero before the first call, left zero).  `scores` (B, ldl) may be log-probabilities or, when
  * repetition_penalty == 1, the head's raw logits: argmax, top-k / top-p / typical-p and the renormalised draw do not change under the
  * per-row shift that separates the two.  The masks are applied where the row enters LDS.  V <= 2048; with the stop group B <= 32767;
- * the budget, the count, the guide and the repeat need the grammar group here.  Without the stop group eos_id / pad_id / min_length
- * are ignored. */
+ * the budget, the count, the guide and the repeat need the grammar group here, the key and the register group stand alone, and the
+ * repeat feeds its token through the guide's arm of the sampler.  Without the stop group eos_id / pad_id / min_length are ignored.
+ * The history of the repeat group is ids / ld_ids: rules->hist / ld_hist are ignored.  The state words and barcol are written by the
+ * row's thread 0.  out_probs (B, V) f32 optional, with do_sample: the renormalised distribution the rows were drawn from, as
+ * mxl_sample's (test hook). */
 int mxl_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
                     unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                     float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                    int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
-                    const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
-                    unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
-                    int* gleft, void* stream);
+                    int* counter, const mxl_rules* rules, float* out_probs, void* stream);
 /* The same rules around mxl_sample / mxl_sample_large, one launch on either side.  mxl_rules_mask, before the sampler:
  * scores[b][v] = -inf in place wherever an enabled group bars token v, one thread per score, every other score untouched (the
  * sampler's repetition penalty leaves -inf at -inf, so the result is that of masking after the penalty).  It reads no stop state:
  * eos_id is barred while *t_dev + 1 < min_length whenever min_length > 0.  No launch when nothing can be barred.
  * mxl_rules_advance, after the sampler and mxl_decode_advance (the token just written is ids[b][*t_dev]): every row that chose its
- * token moves its words along it, then the stop rule is applied to the token and *alive written.  No launch when every group is off. */
-int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length, int* unfinished,
-                   int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate, const void* slots,
-                   const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count,
-                   unsigned end, int* gleft, void* stream);
-int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length, int* unfinished,
-                      int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate, const void* slots,
-                      const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count,
-                      unsigned end, int* gleft, void* stream);
-/* The three entries above with the key group after the flat rules arguments; with keys = pcs = inkey = gkey = NULL they are those
- * entries.  In the fused launch the key group is a variant of its own and needs no grammar.  out_probs (B, V) f32 optional, with
- * do_sample: the renormalised distribution the rows were drawn from, as mxl_sample's (test hook). */
-int mxl_keyed_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                          unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                          float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                          int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
-                          const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
-                          unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
-                          int* gleft, const void* keys, const void* pcs, const void* inkey, int* gkey, float* out_probs, void* stream);
-int mxl_keyed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length,
-                         int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
-                         const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
-                         int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
-                         int* gkey, void* stream);
-int mxl_keyed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length,
-                            int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
-                            const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
-                            int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
-                            int* gkey, void* stream);
-/* The keyed entries with the guide group after the key group; with guide = glen = gpos = gforce = NULL they are those entries.  In
- * the fused launch the guide group is one more variant, on top of the grammar.  The state words are written by the row's thread 0. */
-int mxl_guided_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                           unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                           float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                           int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
-                           const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
-                           unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
-                           int* gleft, const void* keys, const void* pcs, const void* inkey, int* gkey, const void* guide,
-                           int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos, int* gforce, float* out_probs,
-                           void* stream);
-int mxl_guided_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length,
-                          int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
-                          const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
-                          int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
-                          int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
-                          int* gforce, void* stream);
-int mxl_guided_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length,
-                             int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
-                             const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
-                             int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
-                             int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
-                             int* gforce, void* stream);
-/* The guided entries with the register group after the guide group; with reg = grange = gpart = gfloor = NULL they are those entries
- * (gap is then ignored).  In the fused launch the register group is one more variant, which stands alone like the key group. */
-int mxl_ranged_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                           unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                           float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                           int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
-                           const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
-                           unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
-                           int* gleft, const void* keys, const void* pcs, const void* inkey, int* gkey, const void* guide,
-                           int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos, int* gforce, const void* reg,
-                           const void* grange, int* gpart, int* gfloor, int gap, float* out_probs, void* stream);
-int mxl_ranged_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length,
-                          int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
-                          const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
-                          int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
-                          int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
-                          int* gforce, const void* reg, const void* grange, int* gpart, int* gfloor, int gap, void* stream);
-int mxl_ranged_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length,
-                             int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
-                             const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
-                             int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
-                             int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
-                             int* gforce, const void* reg, const void* grange, int* gpart, int* gfloor, int gap, void* stream);
-/* The ranged entries with the repeat group after the register group; with plan = nplan = barcol = gbars = gcopy = gstop = NULL they
- * are those entries (renter, rleave, span, hist are then ignored).  In the fused launch the repeat group is one more variant on top
- * of the grammar and the count; it feeds its token through the guide's arm of the sampler.  barcol and the state words are written by
- * the row's thread 0 (fused) or the row's thread (advance). */
-int mxl_formed_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                           unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                           float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                           int* counter, int eos_id, int pad_id, int min_length, int* unfinished, int* alive, const void* cls,
-                           const void* allow, const void* next, int C, int* gstate, const void* slots, const void* bars,
-                           unsigned opens, unsigned need_free, unsigned need_full, int* gbar, int* grem, unsigned count, unsigned end,
-                           int* gleft, const void* keys, const void* pcs, const void* inkey, int* gkey, const void* guide,
-                           int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos, int* gforce, const void* reg,
-                           const void* grange, int* gpart, int* gfloor, int gap, const void* plan, int ld_plan, const void* nplan,
-                           int* barcol, unsigned renter, unsigned rleave, int span, int* gbars, int* gcopy, int* gstop,
-                           float* out_probs, void* stream);
-int mxl_formed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, int eos_id, int pad_id, int min_length,
-                          int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
-                          const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
-                          int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
-                          int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
-                          int* gforce, const void* reg, const void* grange, int* gpart, int* gfloor, int gap, const void* plan,
-                          int ld_plan, const void* nplan, int* barcol, unsigned renter, unsigned rleave, int span, int* gbars,
-                          int* gcopy, int* gstop, const void* hist, int ld_hist, void* stream);
-int mxl_formed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, int eos_id, int pad_id, int min_length,
-                             int* unfinished, int* alive, const void* cls, const void* allow, const void* next, int C, int* gstate,
-                             const void* slots, const void* bars, unsigned opens, unsigned need_free, unsigned need_full, int* gbar,
-                             int* grem, unsigned count, unsigned end, int* gleft, const void* keys, const void* pcs, const void* inkey,
-                             int* gkey, const void* guide, int ld_guide, const void* glen, unsigned enter, unsigned leave, int* gpos,
-                             int* gforce, const void* reg, const void* grange, int* gpart, int* gfloor, int gap, const void* plan,
-                             int ld_plan, const void* nplan, int* barcol, unsigned renter, unsigned rleave, int span, int* gbars,
-                             int* gcopy, int* gstop, void* stream);
+ * token moves its words along it, then the stop rule is applied to the token and *alive written.  No launch when every group is off.
+ * The mask, which sees no ids, reads the repeat group's history from rules->hist / ld_hist; the advance takes it from ids / ld_ids
+ * and ignores the two fields, and writes the state words and barcol from the row's thread. */
+int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, const mxl_rules* rules, void* stream);
+int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, const mxl_rules* rules, void* stream);
 /* (gpart, gfloor) of every row after columns 0..Tp-1 of ids (B, ld_ids) int64, walked from the words gpart[b] / gfloor[b] hold at the
  * launch under the bounds grange[b] and `gap` (the register group above).  Ids < 0 (left pads) and ids >= V are skipped.  Columns
  * before `from` only move the words -- the prompt's pitches are not judged; first_bad[b] = the first column >= from that holds a pitch

@@ -46,6 +46,39 @@ def declared_functions(header_path: str = HEADER_PATH):
     return out
 
 
+def declared_structs(header_path: str = HEADER_PATH):
+    """Parse the `typedef struct mxl_x { ... } mxl_x;` blocks of `include/musicxl.h` -> {name: ctypes.Structure class}: a field
+    with a `*` is a c_void_p, a scalar goes through _CTYPE, and one line may declare several fields (`int eos_id, pad_id;`)."""
+    src = open(header_path).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    out = {}
+    for m in re.finditer(r'typedef\s+struct\s+(mxl_\w+)\s*\{(.*?)\}\s*\1\s*;', src, flags=re.S):
+        fields = []
+        for decl in m.group(2).split(';'):
+            decl = ' '.join(decl.split())
+            if not decl:
+                continue
+            first, *more = [d.strip() for d in decl.split(',')]
+            ty, name = first.rsplit(' ', 1)                    # `const unsigned char* cls` / `int eos_id`: the type, the first name
+            ctype = C.c_void_p if '*' in first else _CTYPE[ty.replace('const ', '')]
+            if '*' in first and more:
+                raise MusicXLError(f'{m.group(1)}: one pointer field per declaration ({decl!r})')
+            fields += [(n.lstrip('*'), ctype) for n in [name] + more]
+        out[m.group(1)] = type(m.group(1), (C.Structure,), {'_fields_': fields})
+    return out
+
+
+_structs = None
+
+
+def struct(name: str):
+    """the ctypes class of a struct the header declares (parsed once)"""
+    global _structs
+    if _structs is None:
+        _structs = declared_structs()
+    return _structs[name]
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -62,8 +95,11 @@ def lib():
             fn = getattr(_lib, name)  # AttributeError if the header declares something the .so lacks
             fn.restype = restype
             fn.argtypes = argtypes
-        if _lib.mxl_abi_version() != 2:
+        if _lib.mxl_abi_version() != 3:
             raise MusicXLError('libmusicxl ABI version mismatch')
+        if C.sizeof(struct('mxl_rules')) != _lib.mxl_rules_size():
+            raise MusicXLError(f'mxl_rules is {C.sizeof(struct("mxl_rules"))} bytes as parsed from the header, '
+                               f'{_lib.mxl_rules_size()} in the library')
     return _lib
 
 

@@ -428,51 +428,9 @@ __device__ __forceinline__ int sample_row(const float* logp, int ldl, int V, con
 //            under copy takes copy one on and ends the copy at `stop` or, under span 1, at a `leave` token; a kept `enter` token of a
 //            free row with bars < nplan records its column and, if the plan names a source, starts the copy behind the source's
 //            `enter` token
-// The next rule is one more group here, one line in each of rules_load / rules_move and one in make_rules.
+// The next rule is one more group of mxl_rules, one line in each of rules_load / rules_move and one in make_rules.
 // ---------------------------------------------------------------------------------------------------------------
-struct DecodeRules {
-    int eos_id, pad_id, min_length;
-    int* unfinished;
-    int* alive;
-    const unsigned char* cls;
-    const uint32_t* allow;
-    const unsigned char* next;
-    int C;
-    int* gstate;
-    const unsigned short* slots;
-    const unsigned short* bars;
-    uint32_t opens, need_free, need_full;
-    int* gbar;
-    int* grem;
-    uint32_t count, end;
-    int* gleft;
-    const unsigned char* keys;
-    const unsigned char* pcs;
-    const unsigned short* inkey;
-    int* gkey;
-    const int* guide;
-    int ld_guide;
-    const int* glen;
-    uint32_t enter, leave;
-    int* gpos;
-    int* gforce;
-    const unsigned char* reg;
-    const int* grange;
-    int* gpart;
-    int* gfloor;
-    int gap;
-    const int* plan;
-    int ld_plan;
-    const int* nplan;
-    int* barcol;
-    uint32_t renter, rleave;
-    int span;
-    int* gbars;
-    int* gcopy;
-    int* gstop;
-    const long long* hist;
-    int ld_hist;
-};
+using DecodeRules = mxl_rules;               // the struct of the C ABI is the kernels' argument: no second layout, no copy step
 
 constexpr int BUDGET_NONE = 0xFFFF;          // slots: unknown length (beyond any rem); bars: not a time signature
 
@@ -952,228 +910,98 @@ extern "C" int mxl_sample(const float* logprobs, int ldl, int V, void* ids, int 
     return MXL_OK;
 }
 
-// the flat rules arguments of the three entries that take them (include/musicxl.h), in the header's order
-#define RULES_PARAMS                                                                                                              \
-    int eos_id, int pad_id, int min_length, int *unfinished, int *alive, const void *cls, const void *allow, const void *next, int C, \
-        int *gstate, const void *slots, const void *bars, unsigned opens, unsigned need_free, unsigned need_full, int *gbar,        \
-        int *grem, unsigned count, unsigned end, int *gleft
-#define RULES_ARGS \
-    eos_id, pad_id, min_length, unfinished, alive, cls, allow, next, C, gstate, slots, bars, opens, need_free, need_full, gbar, grem, count, end, gleft
-// the key group, which follows them in the mxl_keyed_* entries
-#define KEY_PARAMS const void *keys, const void *pcs, const void *inkey, int *gkey
-#define KEY_ARGS keys, pcs, inkey, gkey
-#define KEY_OFF nullptr, nullptr, nullptr, nullptr
-// the guide group, which follows the key group in the mxl_guided_* entries
-#define GUIDE_PARAMS const void *guide, int ld_guide, const void *glen, unsigned enter, unsigned leave, int *gpos, int *gforce
-#define GUIDE_ARGS guide, ld_guide, glen, enter, leave, gpos, gforce
-#define GUIDE_OFF nullptr, 0, nullptr, 0u, 0u, nullptr, nullptr
-// the register group, which follows the guide group in the mxl_ranged_* entries
-#define REG_PARAMS const void *reg, const void *grange, int *gpart, int *gfloor, int gap
-#define REG_ARGS reg, grange, gpart, gfloor, gap
-#define REG_OFF nullptr, nullptr, nullptr, nullptr, -1
-// the repeat group, which follows the register group in the mxl_formed_* entries; the id history it copies from is the `ids` of the
-// fused and the advance entry and an argument of its own (HIST_PARAMS) where the mask entry, which sees no ids, takes it
-#define FORM_PARAMS \
-    const void *plan, int ld_plan, const void *nplan, int *barcol, unsigned renter, unsigned rleave, int span, int *gbars, int *gcopy, int *gstop
-#define FORM_ARGS plan, ld_plan, nplan, barcol, renter, rleave, span, gbars, gcopy, gstop
-#define FORM_OFF nullptr, 0, nullptr, nullptr, 0u, 0u, 0, nullptr, nullptr, nullptr
-#define HIST_PARAMS const void *hist, int ld_hist
+extern "C" size_t mxl_rules_size(void) { return sizeof(mxl_rules); }
 
-// the one check of those arguments, before any launch: within a group all pointers or none; budget, count, guide and repeat read
-// `cls`; the repeat needs the count, which ends its rows, its history, and the guide off: a row is fed from one place.
+// the one check of the rules (include/musicxl.h, mxl_rules), before any launch, and the struct the kernel gets: within a group all
+// pointers or none; budget, count, guide and repeat read `cls`; the repeat needs the count, which ends its rows, its history, and the
+// guide off: a row is fed from one place.
 // fused: the launch that also samples -- budget, count, guide and repeat ride on the grammar there, and arrivals and live rows share
 // one 32-bit word.  moves: the launch moves the words (all but the mask) -- the repeat then needs the stop group, whose finished rows
-// keep their words
-static int make_rules(DecodeRules* r, int B, bool fused, bool moves, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS, FORM_PARAMS,
-                      HIST_PARAMS) {
-    MXL_CHECK_ARG((unfinished == nullptr) == (alive == nullptr));
-    MXL_CHECK_ARG((allow == nullptr) == (gstate == nullptr) && (next == nullptr) == (gstate == nullptr));
-    MXL_CHECK_ARG(!gstate || (cls && C >= 1 && C <= 32));
-    MXL_CHECK_ARG((slots == nullptr) == (gbar == nullptr) && (bars == nullptr) == (gbar == nullptr) && (grem == nullptr) == (gbar == nullptr));
-    MXL_CHECK_ARG(!(gbar || gleft) || cls);
-    MXL_CHECK_ARG((keys == nullptr) == (gkey == nullptr) && (pcs == nullptr) == (gkey == nullptr) && (inkey == nullptr) == (gkey == nullptr));
-    MXL_CHECK_ARG((guide == nullptr) == (gpos == nullptr) && (glen == nullptr) == (gpos == nullptr) && (gforce == nullptr) == (gpos == nullptr));
-    MXL_CHECK_ARG(!gpos || (cls && ld_guide >= 1));
-    MXL_CHECK_ARG((reg == nullptr) == (gpart == nullptr) && (grange == nullptr) == (gpart == nullptr) && (gfloor == nullptr) == (gpart == nullptr));
-    MXL_CHECK_ARG(!gpart || (gap >= -1 && gap <= 127));
-    MXL_CHECK_ARG((plan == nullptr) == (gcopy == nullptr) && (nplan == nullptr) == (gcopy == nullptr) && (barcol == nullptr) == (gcopy == nullptr));
-    MXL_CHECK_ARG((gbars == nullptr) == (gcopy == nullptr) && (gstop == nullptr) == (gcopy == nullptr));
-    MXL_CHECK_ARG(!gcopy || (cls && gleft && !gpos && ld_plan >= 1 && hist && ld_hist >= 1 && (span == 0 || span == 1)));
-    MXL_CHECK_ARG(!gcopy || !moves || unfinished);
-    if (fused) MXL_CHECK_ARG(!(gbar || gleft || gpos || gcopy) || gstate);
-    if (fused && unfinished) MXL_CHECK_ARG(B <= 32767);
-    if (!unfinished && fused) { eos_id = -1; pad_id = 0; min_length = 0; }
-    *r = DecodeRules{eos_id, pad_id, min_length, unfinished, alive, (const unsigned char*)cls, (const uint32_t*)allow,
-                     (const unsigned char*)next, C, gstate, (const unsigned short*)slots, (const unsigned short*)bars, opens, need_free,
-                     need_full, gbar, grem, count, end, gleft, (const unsigned char*)keys, (const unsigned char*)pcs,
-                     (const unsigned short*)inkey, gkey, (const int*)guide, ld_guide, (const int*)glen, enter, leave, gpos, gforce,
-                     (const unsigned char*)reg, (const int*)grange, gpart, gfloor, gap, (const int*)plan, ld_plan, (const int*)nplan, barcol,
-                     renter, rleave, span, gbars, gcopy, gstop, (const long long*)hist, ld_hist};
+// keep their words.  ids / ld_ids: the history where the launch has the rows' ids itself (all but the mask, which takes the struct's)
+static int make_rules(mxl_rules* out, const mxl_rules* rules, int B, bool fused, bool moves, const void* ids = nullptr, int ld_ids = 0) {
+    MXL_CHECK_ARG(rules && ((uintptr_t)rules % alignof(mxl_rules)) == 0);   // (a misaligned pointer is no mxl_rules: refused, not read)
+    mxl_rules r = *rules;
+    if (moves) { r.hist = (const long long*)ids; r.ld_hist = ld_ids; }
+    MXL_CHECK_ARG((r.unfinished == nullptr) == (r.alive == nullptr));
+    MXL_CHECK_ARG((r.allow == nullptr) == (r.gstate == nullptr) && (r.next == nullptr) == (r.gstate == nullptr));
+    MXL_CHECK_ARG(!r.gstate || (r.cls && r.C >= 1 && r.C <= 32));
+    MXL_CHECK_ARG((r.slots == nullptr) == (r.gbar == nullptr) && (r.bars == nullptr) == (r.gbar == nullptr) && (r.grem == nullptr) == (r.gbar == nullptr));
+    MXL_CHECK_ARG(!(r.gbar || r.gleft) || r.cls);
+    MXL_CHECK_ARG((r.keys == nullptr) == (r.gkey == nullptr) && (r.pcs == nullptr) == (r.gkey == nullptr) && (r.inkey == nullptr) == (r.gkey == nullptr));
+    MXL_CHECK_ARG((r.guide == nullptr) == (r.gpos == nullptr) && (r.glen == nullptr) == (r.gpos == nullptr) && (r.gforce == nullptr) == (r.gpos == nullptr));
+    MXL_CHECK_ARG(!r.gpos || (r.cls && r.ld_guide >= 1));
+    MXL_CHECK_ARG((r.reg == nullptr) == (r.gpart == nullptr) && (r.grange == nullptr) == (r.gpart == nullptr) && (r.gfloor == nullptr) == (r.gpart == nullptr));
+    MXL_CHECK_ARG(!r.gpart || (r.gap >= -1 && r.gap <= 127));
+    MXL_CHECK_ARG((r.plan == nullptr) == (r.gcopy == nullptr) && (r.nplan == nullptr) == (r.gcopy == nullptr) && (r.barcol == nullptr) == (r.gcopy == nullptr));
+    MXL_CHECK_ARG((r.gbars == nullptr) == (r.gcopy == nullptr) && (r.gstop == nullptr) == (r.gcopy == nullptr));
+    MXL_CHECK_ARG(!r.gcopy || (r.cls && r.gleft && !r.gpos && r.ld_plan >= 1 && r.hist && r.ld_hist >= 1 && (r.span == 0 || r.span == 1)));
+    MXL_CHECK_ARG(!r.gcopy || !moves || r.unfinished);
+    if (fused) MXL_CHECK_ARG(!(r.gbar || r.gleft || r.gpos || r.gcopy) || r.gstate);
+    if (fused && r.unfinished) MXL_CHECK_ARG(B <= 32767);
+    if (!r.unfinished && fused) { r.eos_id = -1; r.pad_id = 0; r.min_length = 0; }
+    *out = r;
     return MXL_OK;
 }
 
-extern "C" int mxl_formed_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                                      unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                                      float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS, FORM_PARAMS, float* out_probs,
-                                      void* stream) {
-    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
-    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
-    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
-    DecodeRules r;
-    if (const int e = make_rules(&r, B, true, true, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_ARGS, ids, ld_ids)) return e;
-#define LAUNCH_R(G, BUD, CNT, INK, GD, RG, RP)                                                                                           \
-    hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT, INK, GD, RG, RP>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl, V,   \
-                       (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty, typical_p, \
-                       (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, out_probs, r)
-#define LAUNCH_K(G, BUD, CNT, INK, GD)                           \
-    do {                                                         \
-        if (gpart) LAUNCH_R(G, BUD, CNT, INK, GD, true, false);  \
-        else LAUNCH_R(G, BUD, CNT, INK, GD, false, false);       \
-    } while (0)
-#define LAUNCH_D(G, BUD, CNT, GD)                   \
-    do {                                            \
-        if (gkey) LAUNCH_K(G, BUD, CNT, true, GD);  \
-        else LAUNCH_K(G, BUD, CNT, false, GD);      \
-    } while (0)
-#define LAUNCH(BUD, CNT)                            \
-    do {                                            \
-        if (gpos) LAUNCH_D(true, BUD, CNT, true);   \
-        else LAUNCH_D(true, BUD, CNT, false);       \
-    } while (0)
-    // the repeat group rides on the grammar and the count and excludes the guide (make_rules): a variant over budget, key and register
-#define LAUNCH_P(BUD)                                                         \
-    do {                                                                      \
-        if (gkey && gpart) LAUNCH_R(true, BUD, true, true, false, true, true);  \
-        else if (gkey) LAUNCH_R(true, BUD, true, true, false, false, true);     \
-        else if (gpart) LAUNCH_R(true, BUD, true, false, false, true, true);    \
-        else LAUNCH_R(true, BUD, true, false, false, false, true);              \
-    } while (0)
-    if (gcopy && gbar) LAUNCH_P(true);
-    else if (gcopy) LAUNCH_P(false);
-    else if (!gstate) LAUNCH_D(false, false, false, false);
-    else if (!gbar && !gleft) LAUNCH(false, false);
-    else if (!gleft) LAUNCH(true, false);
-    else if (!gbar) LAUNCH(false, true);
-    else LAUNCH(true, true);
-#undef LAUNCH
-#undef LAUNCH_P
-#undef LAUNCH_D
-#undef LAUNCH_K
-#undef LAUNCH_R
-    MXL_LAUNCH_CHECK();
-    return MXL_OK;
-}
-
-extern "C" int mxl_ranged_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                                      unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                                      float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, REG_PARAMS, float* out_probs, void* stream) {
-    return mxl_formed_sample_step(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, B, do_sample, top_k, top_p, temperature,
-                                  repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS,
-                                  FORM_OFF, out_probs, stream);
-}
-
-extern "C" int mxl_guided_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                                      unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                                      float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                                      int* counter, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS, float* out_probs, void* stream) {
-    return mxl_ranged_sample_step(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, B, do_sample, top_k, top_p, temperature,
-                                  repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_OFF,
-                                  out_probs, stream);
-}
-
-extern "C" int mxl_keyed_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
-                                     unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
-                                     float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                                     int* counter, RULES_PARAMS, KEY_PARAMS, float* out_probs, void* stream) {
-    return mxl_guided_sample_step(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, B, do_sample, top_k, top_p, temperature,
-                                  repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_ARGS, GUIDE_OFF, out_probs,
-                                  stream);
+// f(std::bool_constant<flags>{}...): runtime flags as compile-time ones, one branch per flag
+template <class F>
+static void with_flags(F&& f) { f(); }
+template <class F, class... Rest>
+static void with_flags(F&& f, bool first, Rest... rest) {
+    if (first) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 extern "C" int mxl_sample_step(const float* scores, int ldl, int V, void* ids, int ld_ids, int* t_dev, unsigned long long* rng_ctr,
                                unsigned long long seed, int B, int do_sample, int top_k, float top_p, float temperature,
                                float repetition_penalty, float typical_p, const void* E, void* emb_out, int d, float scale,
-                               int* counter, RULES_PARAMS, void* stream) {
-    return mxl_keyed_sample_step(scores, ldl, V, ids, ld_ids, t_dev, rng_ctr, seed, B, do_sample, top_k, top_p, temperature,
-                                 repetition_penalty, typical_p, E, emb_out, d, scale, counter, RULES_ARGS, KEY_OFF, nullptr, stream);
+                               int* counter, const mxl_rules* rules, float* out_probs, void* stream) {
+    MXL_CHECK_ARG(scores && ids && t_dev && rng_ctr && E && emb_out && counter && B > 0 && V > 0 && V <= SORT_N && temperature > 0.f);
+    MXL_CHECK_ARG(repetition_penalty > 0.f && typical_p > 0.f && d > 0 && (d % 8) == 0);
+    MXL_CHECK_ARG(((uintptr_t)E % 16) == 0 && ((uintptr_t)emb_out % 16) == 0);
+    mxl_rules r;
+    if (const int e = make_rules(&r, rules, B, true, true, ids, ld_ids)) return e;
+    // one instantiation per set of groups the kernel's static_asserts admit -- the budget, the count, the guide and the repeat ride on
+    // the grammar, the repeat on the count as well and never beside the guide (make_rules lets no other set through): 4 without the
+    // grammar, 32 with it, 8 with the repeat
+    bool launched = false;
+    with_flags([&](auto G, auto BUD, auto CNT, auto INK, auto GD, auto RG, auto RP) {
+        if constexpr ((G || !(BUD || CNT || GD || RP)) && !(GD && RP) && (!RP || CNT)) {
+            hipLaunchKernelGGL((sample_step_kernel<G, BUD, CNT, INK, GD, RG, RP>), dim3(B), dim3(256), 0, (hipStream_t)stream, scores, ldl,
+                               V, (long long*)ids, ld_ids, t_dev, rng_ctr, seed, do_sample, top_k, top_p, temperature, repetition_penalty,
+                               typical_p, (const bf16_t*)E, (bf16_t*)emb_out, d, scale, counter, out_probs, r);
+            launched = true;
+        }
+    }, r.gstate != nullptr, r.gbar != nullptr, r.gleft != nullptr, r.gkey != nullptr, r.gpos != nullptr, r.gpart != nullptr,
+       r.gcopy != nullptr);
+    MXL_CHECK_ARG(launched);
+    MXL_LAUNCH_CHECK();
+    return MXL_OK;
 }
 
-extern "C" int mxl_formed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                     REG_PARAMS, FORM_PARAMS, HIST_PARAMS, void* stream) {
-    MXL_CHECK_ARG(scores && B > 0 && V > 0 && ldl >= V && (t_dev || min_length <= 0));
+extern "C" int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, const mxl_rules* rules, void* stream) {
+    MXL_CHECK_ARG(rules && ((uintptr_t)rules % alignof(mxl_rules)) == 0);   // (a misaligned pointer is no mxl_rules: refused, not read)
+    MXL_CHECK_ARG(scores && B > 0 && V > 0 && ldl >= V && (t_dev || rules->min_length <= 0));
     const long long n = (long long)B * V;
     MXL_CHECK_ARG(n <= (1LL << 38));
-    DecodeRules r;
-    if (const int e = make_rules(&r, B, false, false, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_ARGS, hist, ld_hist)) return e;
+    mxl_rules r;
+    if (const int e = make_rules(&r, rules, B, false, false)) return e;
     if (!r.cls && !r.gkey && !r.gpart && (r.min_length <= 0 || r.eos_id < 0 || r.eos_id >= V)) return MXL_OK;   // nothing to bar
     hipLaunchKernelGGL(rules_mask_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scores, ldl, B, V, t_dev, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
 
-extern "C" int mxl_ranged_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                     REG_PARAMS, void* stream) {
-    return mxl_formed_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_OFF, nullptr, 0, stream);
-}
-
-extern "C" int mxl_guided_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                     void* stream) {
-    return mxl_ranged_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_OFF, stream);
-}
-
-extern "C" int mxl_keyed_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, KEY_PARAMS, void* stream) {
-    return mxl_guided_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_ARGS, GUIDE_OFF, stream);
-}
-
-extern "C" int mxl_rules_mask(float* scores, int ldl, int B, int V, const int* t_dev, RULES_PARAMS, void* stream) {
-    return mxl_keyed_rules_mask(scores, ldl, B, V, t_dev, RULES_ARGS, KEY_OFF, stream);
-}
-
-extern "C" int mxl_formed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                        REG_PARAMS, FORM_PARAMS, void* stream) {
-    MXL_CHECK_ARG(ids && t_dev && B > 0 && (V > 0 || !(cls || gkey || gpart)));
-    DecodeRules r;
-    if (const int e = make_rules(&r, B, false, true, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_ARGS, ids, ld_ids)) return e;
+extern "C" int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, const mxl_rules* rules, void* stream) {
+    MXL_CHECK_ARG(rules && ((uintptr_t)rules % alignof(mxl_rules)) == 0);   // (a misaligned pointer is no mxl_rules: refused, not read)
+    MXL_CHECK_ARG(ids && t_dev && B > 0 && (V > 0 || !(rules->cls || rules->gkey || rules->gpart)));
+    mxl_rules r;
+    if (const int e = make_rules(&r, rules, B, false, true, ids, ld_ids)) return e;
     if (!r.cls && !r.gkey && !r.gpart && !r.unfinished) return MXL_OK;                           // nothing to move
     hipLaunchKernelGGL(rules_advance_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (long long*)ids, ld_ids, t_dev, B, V, r);
     MXL_LAUNCH_CHECK();
     return MXL_OK;
 }
-
-extern "C" int mxl_ranged_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                        REG_PARAMS, void* stream) {
-    return mxl_formed_rules_advance(ids, ld_ids, t_dev, B, V, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_ARGS, FORM_OFF, stream);
-}
-
-extern "C" int mxl_guided_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, GUIDE_PARAMS,
-                                        void* stream) {
-    return mxl_ranged_rules_advance(ids, ld_ids, t_dev, B, V, RULES_ARGS, KEY_ARGS, GUIDE_ARGS, REG_OFF, stream);
-}
-
-extern "C" int mxl_keyed_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, KEY_PARAMS, void* stream) {
-    return mxl_guided_rules_advance(ids, ld_ids, t_dev, B, V, RULES_ARGS, KEY_ARGS, GUIDE_OFF, stream);
-}
-
-extern "C" int mxl_rules_advance(void* ids, int ld_ids, const int* t_dev, int B, int V, RULES_PARAMS, void* stream) {
-    return mxl_keyed_rules_advance(ids, ld_ids, t_dev, B, V, RULES_ARGS, KEY_OFF, stream);
-}
-#undef RULES_PARAMS
-#undef RULES_ARGS
-#undef KEY_PARAMS
-#undef KEY_ARGS
-#undef KEY_OFF
-#undef GUIDE_PARAMS
-#undef GUIDE_ARGS
-#undef GUIDE_OFF
-#undef REG_PARAMS
-#undef REG_ARGS
-#undef REG_OFF
-#undef FORM_PARAMS
-#undef FORM_ARGS
-#undef FORM_OFF
-#undef HIST_PARAMS
 
 extern "C" int mxl_register_scan(const void* ids, int ld_ids, int Tp, int from, int B, int V, const void* reg, const void* grange, int gap,
                                  int* gpart, int* gfloor, int* first_bad, void* stream) {

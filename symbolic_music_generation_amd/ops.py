@@ -10,7 +10,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from ._lib import lib, check, MusicXLError
+from ._lib import lib, check, struct, MusicXLError
 
 GEMM_OUT_F32 = 0x01
 GEMM_OUT_F32_ATOMIC = 0x02
@@ -143,7 +143,7 @@ def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=
     grammar.MelodyGuide), `register` (the register rule, a grammar.RegisterRule, with the launch's `gap`) and `repeat` (the repeat
     rule, a grammar.BarRepeat, with the launch's `span`) and may hand over state tensors of rules that are off: those are dropped
     here, and a rule that is on without its state raises."""
-    if repeat is not None:                  # (a call without the rule carries no key of it: the ranged entries, as before)
+    if repeat is not None:                  # (a call without the rule carries no key of it)
         if grammar is None or gleft is None or stop is None or melody is not None:
             raise MusicXLError('the repeat rule rides on a grammar, needs the bar count (gleft) and the eos rule, and excludes the guide')
         if any(x is None for x in (plan, nplan, barcol, gbars, gcopy, gstop)):
@@ -167,7 +167,7 @@ def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=
     if register is not None and (grange is None or gpart is None or gfloor is None):
         raise MusicXLError('the register rule needs grange, gpart and gfloor')
     on = melody is not None
-    if register is not None:                # (a call without the rule carries no key of it: the guided entries, as before)
+    if register is not None:                # (a call without the rule carries no key of it)
         return dict(rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos,
                                    gforce), register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=int(gap))
     return dict(stop=stop, unfinished=unfinished if stop is not None else None, alive=alive if stop is not None else None,
@@ -177,131 +177,40 @@ def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=
                 gforce=gforce if on else None)
 
 
-GUIDE_KEYS = ('melody', 'guide', 'glen', 'gpos', 'gforce')
-
-
-def _guide_args(what, device, B, V=None, *, grammar=None, melody=None, guide=None, glen=None, gpos=None, gforce=None) -> list:
-    """the guide group of the mxl_guided_* entries (include/musicxl.h, "Rules of a generation"), checked: on exactly when gpos is
-    given, with the class masks of `melody` (a grammar.MelodyGuide over `grammar`), the rows' guide tokens guide (B, ld) int32 and
-    their lengths glen (B,) int32, and the second word gforce"""
-    if gpos is None:
-        if gforce is not None:
-            raise MusicXLError(f'{what}: gforce needs gpos')
-        return [None, 0, None, 0, 0, None, None]
-    if melody is None or grammar is None or melody.grammar is not grammar:
-        raise MusicXLError(f'{what}: gpos needs melody, the guide rule of the grammar (grammar.guide)')
-    if guide is None or glen is None or gforce is None:
-        raise MusicXLError(f'{what}: the guide group needs guide, glen, gpos and gforce')
-    if V is not None and grammar.vocab_size != int(V):
-        raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
-    for t, name in ((guide, 'guide'), (glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
-        _req(t, torch.int32, f'{what} {name}')
-    if guide.dim() != 2 or guide.shape[0] != B or guide.shape[1] < 1 or guide.stride(1) != 1 or guide.stride(0) < guide.shape[1]:
-        raise MusicXLError(f'{what}: guide must be ({B}, >= 1) int32 rows with unit column stride')
-    for t, name in ((glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
-        if t.numel() != B or not t.is_contiguous():
-            raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
-    # (glen[b] <= the row width is the caller's to keep; the kernels clamp to ld_guide as well)
-    return [_p(guide), guide.stride(0), _p(glen), melody.enter, melody.leave, _p(gpos), _p(gforce)]
-
-
-REGISTER_KEYS = ('register', 'grange', 'gpart', 'gfloor', 'gap')
-REPEAT_KEYS = ('repeat', 'plan', 'nplan', 'barcol', 'span', 'gbars', 'gcopy', 'gstop')
-
-
-def _repeat_args(what, device, B, V=None, *, grammar=None, repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None,
-                 gcopy=None, gstop=None) -> list:
-    """the repeat group of the mxl_formed_* entries (include/musicxl.h, "Rules of a generation"), checked: on exactly when gcopy is
-    given, with the class masks of `repeat` (a grammar.BarRepeat over `grammar`), the rows' plans plan (B, ld) int32 with their lengths
-    nplan (B,) int32, the table barcol (B, ld) int32 the device writes (same row stride as plan), the launch's span and the words
-    gbars and gstop"""
-    if gcopy is None:
-        if gbars is not None or gstop is not None:
-            raise MusicXLError(f'{what}: gbars and gstop need gcopy')
-        return [None, 0, None, None, 0, 0, 0, None, None, None]
-    if repeat is None or grammar is None or repeat.grammar is not grammar:
-        raise MusicXLError(f'{what}: gcopy needs repeat, the repeat rule of the grammar (grammar.repeat)')
-    if any(x is None for x in (plan, nplan, barcol, gbars, gstop)):
-        raise MusicXLError(f'{what}: the repeat group needs plan, nplan, barcol, gbars, gcopy and gstop')
-    if V is not None and grammar.vocab_size != int(V):
-        raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
-    for t, name in ((plan, 'plan'), (nplan, 'nplan'), (barcol, 'barcol'), (gbars, 'gbars'), (gcopy, 'gcopy'), (gstop, 'gstop')):
-        _req(t, torch.int32, f'{what} {name}')
-    for t, name in ((plan, 'plan'), (barcol, 'barcol')):           # one width serves both: it is the row stride and nplan's clamp
-        if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous() or t.shape != plan.shape:
-            raise MusicXLError(f'{what}: {name} must be contiguous ({B}, >= 1) int32, plan and barcol of one shape')
-    for t, name in ((nplan, 'nplan'), (gbars, 'gbars'), (gcopy, 'gcopy'), (gstop, 'gstop')):
-        if t.numel() != B or not t.is_contiguous():
-            raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
-    if int(span) not in (0, 1):
-        raise MusicXLError(f'{what}: span is 0 (the whole bar) or 1 (up to the first `leave` token), got {span}')
-    return [_p(plan), plan.shape[1], _p(nplan), _p(barcol), repeat.enter, repeat.leave, int(span), _p(gbars), _p(gcopy), _p(gstop)]
-
-
-def _register_args(what, device, B, V=None, *, register=None, grange=None, gpart=None, gfloor=None, gap=-1) -> list:
-    """the register group of the mxl_ranged_* entries (include/musicxl.h, "Rules of a generation"), checked: on exactly when gpart is
-    given, with its table from `register` (a grammar.RegisterRule), which must span the V tokens of the scores, the rows' bounds
-    grange and second word gfloor, and the launch's gap"""
-    if gpart is None:
-        return [None, None, None, None, -1]
-    if register is None:
-        raise MusicXLError(f'{what}: gpart needs register, the register rule that holds its table')
-    if grange is None or gfloor is None:
-        raise MusicXLError(f'{what}: the register group needs grange, gpart and gfloor')
-    if V is not None and register.vocab_size != int(V):
-        raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the scores span {int(V)}')
-    for t, name in ((grange, 'grange'), (gpart, 'gpart'), (gfloor, 'gfloor')):
-        _req(t, torch.int32, f'{what} {name}')
-        if t.numel() != B or not t.is_contiguous():
-            raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
-    if not -1 <= int(gap) <= 127:
-        raise MusicXLError(f'{what}: gap must lie in -1..127, got {gap}')
-    return [_p(register.to(device)), _p(grange), _p(gpart), _p(gfloor), int(gap)]
-
-
-def _key_args(what, device, B, V=None, *, in_key=None, gkey=None) -> list:
-    """the key group of the mxl_keyed_* entries (include/musicxl.h, "Rules of a generation"), checked: on exactly when gkey is given,
-    with its tables from `in_key` (a grammar.KeyRule), which must span the V tokens of the scores"""
-    if gkey is None:
-        return [None, None, None, None]
-    if in_key is None:
-        raise MusicXLError(f'{what}: gkey needs in_key, the key rule that holds its tables')
-    if V is not None and in_key.vocab_size != int(V):
-        raise MusicXLError(f'the key rule spans {in_key.vocab_size} tokens, the scores span {int(V)}')
-    _req(gkey, torch.int32, f'{what} gkey')
-    if gkey.numel() != B or not gkey.is_contiguous():
-        raise MusicXLError(f'{what}: gkey must be contiguous ({B},) int32')
-    return [_p(t) for t in in_key.to(device)] + [_p(gkey)]
-
-
-def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None,
-                gleft=None, guided=False) -> list:
-    """the flat rules arguments of mxl_sample_step / mxl_rules_mask / mxl_rules_advance (include/musicxl.h, "Rules of a generation"),
-    checked: a group is on exactly when its state tensor is given -- unfinished (with alive and stop = (eos, pad, min_length)),
-    gstate, gbar (with grem), gleft; the last three take their tables from `grammar`, which must classify the V tokens of the scores.
-    guided: the guide group is on (_guide_args), which reads the token classes as well"""
+def _rules_struct(what, device, B, V=None, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None,
+                  gleft=None, in_key=None, gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None,
+                  grange=None, gpart=None, gfloor=None, gap=-1, repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None,
+                  gcopy=None, gstop=None):
+    """the mxl_rules of mxl_sample_step / mxl_rules_mask / mxl_rules_advance (include/musicxl.h, "Rules of a generation"), checked
+    and filled by field name: a group is on exactly when its state tensor is given -- unfinished (with alive and stop = (eos, pad,
+    min_length)), gstate, gbar (with grem), gleft, gkey, gpos (with gforce), gpart (with gfloor), gcopy (with gbars, gstop) -- and
+    takes its tables from `grammar`, `in_key`, `melody`, `register` and `repeat`, which must span the V tokens of the scores.  A field
+    that is not set stays zero: its group is off.  (hist / ld_hist, which the mask alone reads, are rules_mask's to set.)"""
     eos, pad, min_length = stop if stop is not None else (-1, 0, 0)
+    f = dict(eos_id=int(eos), pad_id=int(pad), min_length=int(min_length or 0))
+    # stop, grammar, budget, count
     if unfinished is not None:
         if stop is None:
             raise MusicXLError(f'{what}: unfinished needs stop = (eos, pad, min_length)')
         _req(unfinished, torch.int32, f'{what} unfinished')
-    cls = allow = nxt = slots = bars = None
-    bud = cnt = None
-    if gstate is not None or gbar is not None or grem is not None or gleft is not None or guided:
+    f.update(unfinished=_p(unfinished), alive=_p(alive))
+    if gstate is not None or gbar is not None or grem is not None or gleft is not None or gpos is not None or gcopy is not None:
         if grammar is None:
             raise MusicXLError(f'{what}: gstate, gbar / grem, gleft and the guide ride on a grammar')
         if V is not None and grammar.vocab_size != int(V):
             raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
         cls, allow, nxt = grammar.to(device)
-    if gstate is None:
-        allow = nxt = None
-    else:
+        f.update(cls=_p(cls), C=grammar.n_classes)
+    if gstate is not None:
         _req(gstate, torch.int32, f'{what} gstate')
         if gstate.numel() != B:
             raise MusicXLError(f'gstate holds {gstate.numel()} rows, the scores {B}')
+        f.update(allow=_p(allow), next=_p(nxt), gstate=_p(gstate))
     if gbar is not None or grem is not None:
         bud = grammar.budget
         slots, bars = _budget_state(bud, device, B, gbar, grem, what)
+        f.update(slots=_p(slots), bars=_p(bars), opens=bud.opens, need_free=bud.need_free, need_full=bud.need_full, gbar=_p(gbar),
+                 grem=_p(grem))
     if gleft is not None:
         cnt = grammar.bar_count
         if cnt is None:
@@ -309,10 +218,76 @@ def _rules_args(what, device, B, V=None, *, stop=None, unfinished=None, alive=No
         _req(gleft, torch.int32, f'{what} gleft')
         if gleft.numel() != B or not gleft.is_contiguous():
             raise MusicXLError(f'{what}: gleft must be contiguous ({B},) int32')
-    masks = (bud.opens, bud.need_free, bud.need_full) if bud is not None else (0, 0, 0)
-    ends = (cnt.count, cnt.end) if cnt is not None else (0, 0)
-    return [int(eos), int(pad), int(min_length or 0), _p(unfinished), _p(alive), _p(cls), _p(allow), _p(nxt),
-            grammar.n_classes if cls is not None else 0, _p(gstate), _p(slots), _p(bars), *masks, _p(gbar), _p(grem), *ends, _p(gleft)]
+        f.update(count=cnt.count, end=cnt.end, gleft=_p(gleft))
+    # repeat: the class masks of `repeat` (a grammar.BarRepeat over `grammar`), the rows' plans plan (B, ld) int32 with their lengths
+    # nplan (B,) int32, the table barcol (B, ld) int32 the device writes (same row stride as plan), the launch's span, gbars and gstop
+    if gcopy is None:
+        if gbars is not None or gstop is not None:
+            raise MusicXLError(f'{what}: gbars and gstop need gcopy')
+    else:
+        if repeat is None or repeat.grammar is not grammar:
+            raise MusicXLError(f'{what}: gcopy needs repeat, the repeat rule of the grammar (grammar.repeat)')
+        if any(x is None for x in (plan, nplan, barcol, gbars, gstop)):
+            raise MusicXLError(f'{what}: the repeat group needs plan, nplan, barcol, gbars, gcopy and gstop')
+        for t, name in ((plan, 'plan'), (nplan, 'nplan'), (barcol, 'barcol'), (gbars, 'gbars'), (gcopy, 'gcopy'), (gstop, 'gstop')):
+            _req(t, torch.int32, f'{what} {name}')
+        for t, name in ((plan, 'plan'), (barcol, 'barcol')):           # one width serves both: it is the row stride and nplan's clamp
+            if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous() or t.shape != plan.shape:
+                raise MusicXLError(f'{what}: {name} must be contiguous ({B}, >= 1) int32, plan and barcol of one shape')
+        for t, name in ((nplan, 'nplan'), (gbars, 'gbars'), (gcopy, 'gcopy'), (gstop, 'gstop')):
+            if t.numel() != B or not t.is_contiguous():
+                raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
+        if int(span) not in (0, 1):
+            raise MusicXLError(f'{what}: span is 0 (the whole bar) or 1 (up to the first `leave` token), got {span}')
+        f.update(plan=_p(plan), ld_plan=plan.shape[1], nplan=_p(nplan), barcol=_p(barcol), renter=repeat.enter, rleave=repeat.leave,
+                 span=int(span), gbars=_p(gbars), gcopy=_p(gcopy), gstop=_p(gstop))
+    # key: the tables of `in_key` (a grammar.KeyRule)
+    if gkey is not None:
+        if in_key is None:
+            raise MusicXLError(f'{what}: gkey needs in_key, the key rule that holds its tables')
+        if V is not None and in_key.vocab_size != int(V):
+            raise MusicXLError(f'the key rule spans {in_key.vocab_size} tokens, the scores span {int(V)}')
+        _req(gkey, torch.int32, f'{what} gkey')
+        if gkey.numel() != B or not gkey.is_contiguous():
+            raise MusicXLError(f'{what}: gkey must be contiguous ({B},) int32')
+        keys, pcs, inkey = in_key.to(device)
+        f.update(keys=_p(keys), pcs=_p(pcs), inkey=_p(inkey), gkey=_p(gkey))
+    # guide: the class masks of `melody` (a grammar.MelodyGuide over `grammar`), the rows' guide tokens guide (B, ld) int32 and their
+    # lengths glen (B,) int32, and the second word gforce
+    if gpos is None:
+        if gforce is not None:
+            raise MusicXLError(f'{what}: gforce needs gpos')
+    else:
+        if melody is None or melody.grammar is not grammar:
+            raise MusicXLError(f'{what}: gpos needs melody, the guide rule of the grammar (grammar.guide)')
+        if guide is None or glen is None or gforce is None:
+            raise MusicXLError(f'{what}: the guide group needs guide, glen, gpos and gforce')
+        for t, name in ((guide, 'guide'), (glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
+            _req(t, torch.int32, f'{what} {name}')
+        if guide.dim() != 2 or guide.shape[0] != B or guide.shape[1] < 1 or guide.stride(1) != 1 or guide.stride(0) < guide.shape[1]:
+            raise MusicXLError(f'{what}: guide must be ({B}, >= 1) int32 rows with unit column stride')
+        for t, name in ((glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
+            if t.numel() != B or not t.is_contiguous():
+                raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
+        # (glen[b] <= the row width is the caller's to keep; the kernels clamp to ld_guide as well)
+        f.update(guide=_p(guide), ld_guide=guide.stride(0), glen=_p(glen), enter=melody.enter, leave=melody.leave, gpos=_p(gpos),
+                 gforce=_p(gforce))
+    # register: the table of `register` (a grammar.RegisterRule), the rows' bounds grange, the second word gfloor, the launch's gap
+    if gpart is not None:
+        if register is None:
+            raise MusicXLError(f'{what}: gpart needs register, the register rule that holds its table')
+        if grange is None or gfloor is None:
+            raise MusicXLError(f'{what}: the register group needs grange, gpart and gfloor')
+        if V is not None and register.vocab_size != int(V):
+            raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the scores span {int(V)}')
+        for t, name in ((grange, 'grange'), (gpart, 'gpart'), (gfloor, 'gfloor')):
+            _req(t, torch.int32, f'{what} {name}')
+            if t.numel() != B or not t.is_contiguous():
+                raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
+        if not -1 <= int(gap) <= 127:
+            raise MusicXLError(f'{what}: gap must lie in -1..127, got {gap}')
+        f.update(reg=_p(register.to(device)), grange=_p(grange), gpart=_p(gpart), gfloor=_p(gfloor), gap=int(gap))
+    return struct('mxl_rules')(**f)
 
 
 def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
@@ -335,21 +310,16 @@ def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter
     B = scores.shape[0]
     force = rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos, gforce,
                            register, grange, gpart, gfloor, gap, repeat, plan, nplan, barcol, span, gbars, gcopy, gstop)
-    formed = _repeat_args('sample_step', scores.device, B, V, grammar=grammar, **{k: force.pop(k) for k in REPEAT_KEYS if k in force})
-    ranged = _register_args('sample_step', scores.device, B, V, **{k: force.pop(k) for k in REGISTER_KEYS if k in force})
-    keyed = _key_args('sample_step', scores.device, B, V, in_key=force.pop('in_key'), gkey=force.pop('gkey'))
-    guided = _guide_args('sample_step', scores.device, B, V, grammar=grammar, **{k: force.pop(k) for k in GUIDE_KEYS})
-    rules = _rules_args('sample_step', scores.device, B, V, guided=guided[0] is not None or formed[0] is not None, **force)
+    rules = _rules_struct('sample_step', scores.device, B, V, **force)
     if out_probs is not None:
         _req(out_probs, torch.float32, 'sample_step out_probs')
         if tuple(out_probs.shape) != (B, int(V)) or not out_probs.is_contiguous():
             raise MusicXLError(f'sample_step: out_probs must be contiguous ({B}, {int(V)}) f32')
-    check(lib().mxl_formed_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
-                                      int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
-                                      float(repetition_penalty if repetition_penalty is not None else 1.0),
-                                      float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
-                                      float(scale), _p(counter), *rules, *keyed, *guided, *ranged, *formed, _p(out_probs), _stream()),
-          'mxl_formed_sample_step')
+    check(lib().mxl_sample_step(_p(scores), scores.stride(0), int(V), _p(ids), ids.stride(0), _p(t_dev), _p(rng_ctr), seed, B,
+                                int(do_sample), int(top_k or 0), float(top_p if top_p is not None else 1.0), float(temperature),
+                                float(repetition_penalty if repetition_penalty is not None else 1.0),
+                                float(typical_p if typical_p is not None else 1.0), _p(E), _p(emb_out), emb_out.shape[1],
+                                float(scale), _p(counter), C.byref(rules), _p(out_probs), _stream()), 'mxl_sample_step')
 
 
 def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None,
@@ -366,18 +336,15 @@ def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=N
     B = scores.shape[0]
     if scores.shape[1] < V or scores.stride(1) != 1:
         raise MusicXLError('rules_mask: scores must be (B, >= V) with unit column stride')
-    rules = _rules_args('rules_mask', scores.device, B, V, stop=stop, grammar=grammar, gstate=gstate, gbar=gbar, grem=grem, gleft=gleft,
-                        guided=gpos is not None or gcopy is not None)
-    formed = _repeat_args('rules_mask', scores.device, B, V, grammar=grammar, repeat=repeat, plan=plan, nplan=nplan, barcol=barcol,
+    rules = _rules_struct('rules_mask', scores.device, B, V, stop=stop, grammar=grammar, gstate=gstate, gbar=gbar, grem=grem, gleft=gleft,
+                          in_key=in_key, gkey=gkey, melody=melody, guide=guide, glen=glen, gpos=gpos, gforce=gforce, register=register,
+                          grange=grange, gpart=gpart, gfloor=gfloor, gap=gap, repeat=repeat, plan=plan, nplan=nplan, barcol=barcol,
                           span=span, gbars=gbars, gcopy=gcopy, gstop=gstop)
-    if gcopy is not None and (hist is None or hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != B or hist.stride(1) != 1):
-        raise MusicXLError('rules_mask: the repeat group needs hist, the (B, .) int64 ids of the rows')
-    past = [_p(hist), hist.stride(0)] if gcopy is not None else [None, 0]
-    keyed = _key_args('rules_mask', scores.device, B, V, in_key=in_key, gkey=gkey)
-    guided = _guide_args('rules_mask', scores.device, B, V, grammar=grammar, melody=melody, guide=guide, glen=glen, gpos=gpos, gforce=gforce)
-    ranged = _register_args('rules_mask', scores.device, B, V, register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=gap)
-    check(lib().mxl_formed_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), *rules, *keyed, *guided, *ranged, *formed, *past,
-                                      _stream()), 'mxl_formed_rules_mask')
+    if gcopy is not None:
+        if hist is None or hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != B or hist.stride(1) != 1:
+            raise MusicXLError('rules_mask: the repeat group needs hist, the (B, .) int64 ids of the rows')
+        rules.hist, rules.ld_hist = _p(hist), hist.stride(0)
+    check(lib().mxl_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), C.byref(rules), _stream()), 'mxl_rules_mask')
 
 
 def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None,
@@ -390,22 +357,19 @@ def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar
     B = ids.shape[0]
     if ids.dtype != torch.int64:
         raise MusicXLError('rules_advance: ids must be (B, .) int64')
-    rules = _rules_args('rules_advance', ids.device, B, stop=stop, unfinished=unfinished, alive=alive, grammar=grammar, gstate=gstate,
-                        gbar=gbar, grem=grem, gleft=gleft, guided=gpos is not None or gcopy is not None)
-    formed = _repeat_args('rules_advance', ids.device, B, grammar=grammar, repeat=repeat, plan=plan, nplan=nplan, barcol=barcol,
-                          span=span, gbars=gbars, gcopy=gcopy, gstop=gstop)
+    rules = _rules_struct('rules_advance', ids.device, B, stop=stop, unfinished=unfinished, alive=alive, grammar=grammar, gstate=gstate,
+                          gbar=gbar, grem=grem, gleft=gleft, in_key=in_key, gkey=gkey, melody=melody, guide=guide, glen=glen, gpos=gpos,
+                          gforce=gforce, register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=gap, repeat=repeat, plan=plan,
+                          nplan=nplan, barcol=barcol, span=span, gbars=gbars, gcopy=gcopy, gstop=gstop)
+    # V: what the rules in force span, which must agree on it
     if grammar is not None and in_key is not None and gkey is not None and grammar.vocab_size != in_key.vocab_size:
         raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the key rule spans {in_key.vocab_size}')
-    keyed = _key_args('rules_advance', ids.device, B, in_key=in_key, gkey=gkey)
     V = grammar.vocab_size if grammar is not None else (in_key.vocab_size if gkey is not None else 0)
-    guided = _guide_args('rules_advance', ids.device, B, grammar=grammar, melody=melody, guide=guide, glen=glen, gpos=gpos, gforce=gforce)
-    ranged = _register_args('rules_advance', ids.device, B, register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=gap)
     if gpart is not None:
         if V and register.vocab_size != V:
             raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the other rules {V}')
         V = register.vocab_size
-    check(lib().mxl_formed_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, *rules, *keyed, *guided, *ranged, *formed, _stream()),
-          'mxl_formed_rules_advance')
+    check(lib().mxl_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, C.byref(rules), _stream()), 'mxl_rules_advance')
 
 
 def key_scan(ids, Tp, in_key, gkey, first_bad, check_from=None):

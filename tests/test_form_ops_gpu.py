@@ -1,8 +1,10 @@
 """The repeat group on the device (`generate(form=...)`; include/musicxl.h, "Rules of a generation", group `repeat`), kernel level: the
-mask and the move of the unfused pair (mxl_formed_rules_mask / mxl_formed_rules_advance) and of the fused sampler launch
-(mxl_formed_sample_step) against the host rule grammar.BarRepeat composed with the host references of the other groups
+mask and the move of the unfused pair (mxl_rules_mask / mxl_rules_advance) and of the fused sampler launch
+(mxl_sample_step) against the host rule grammar.BarRepeat composed with the host references of the other groups
 (tests/form_ref.py), one launch over a handful of rows that each stand at another point of a plan, with every other group on.  Every
-test here fails without the feature: the entries and the keywords do not exist.  Whole generations are tests/test_form_generate_gpu.py."""
+test here fails without the feature: the struct's fields and the keywords do not exist.  Whole generations are tests/test_form_generate_gpu.py."""
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -170,7 +172,7 @@ def test_cases_cover_what_they_say():
 
 @pytest.mark.parametrize('span', [0, 1])
 def test_mask_equals_the_host_rules(dev, span):
-    """mxl_formed_rules_mask: the -inf set is exactly what the host rules bar, every other score keeps its bits, and no word, no
+    """mxl_rules_mask with the repeat group: the -inf set is exactly what the host rules bar, every other score keeps its bits, and no word, no
     table, no history column and no score column beyond V is written"""
     from symbolic_music_generation_amd import ops
     keep = _host_keep()
@@ -185,7 +187,7 @@ def test_mask_equals_the_host_rules(dev, span):
     assert torch.equal(got.view(torch.int32), want.view(torch.int32))
     assert st.words() == st.start() and st.fixed_untouched() and st.alive.tolist() == [-5]
     assert torch.equal(st.barcol.cpu(), st.barcol_host) and torch.equal(st.ids.cpu(), st.ids_host)
-    # with the group off the same call is the ranged mask: the copying rows are judged by the other groups again
+    # with the group off the same call is the mask of the other groups: the copying rows are judged by the other groups again
     scores = _scores(dev)
     off = {k: v for k, v in kw.items() if k not in ('repeat', 'plan', 'nplan', 'barcol', 'span', 'gbars', 'gcopy', 'gstop')}
     ops.rules_mask(scores[:, :V], V, i32([T0], dev), **off)
@@ -197,8 +199,8 @@ def test_mask_equals_the_host_rules(dev, span):
 @pytest.mark.parametrize('kw', [dict(do_sample=False), dict(do_sample=True, top_k=8, temperature=0.9)], ids=['greedy', 'sample'])
 @pytest.mark.parametrize('fused', [True, False], ids=['fused', 'unfused'])
 def test_one_step_keeps_the_copy_and_moves_the_words(dev, fused, kw, span):
-    """one sampler tail over the cases, through mxl_formed_sample_step and through mxl_formed_rules_mask / sample /
-    mxl_formed_rules_advance: the tokens, every word of every row, barcol, ids[:, T0 + 1] alone, the embedding rows, the distribution"""
+    """one sampler tail over the cases, through mxl_sample_step and through mxl_rules_mask / sample /
+    mxl_rules_advance: the tokens, every word of every row, barcol, ids[:, T0 + 1] alone, the embedding rows, the distribution"""
     keep, fed = _host_keep(), _fed()
     st = _State(dev)
     toks, probs, emb, E = form_ref.tail(dev, fused, _scores(dev)[:, :V], sampling_config(**kw), st.ids, T0, width=64, seed=17, gen_seed=2,
@@ -245,44 +247,45 @@ def test_argument_checks(dev):
     st = _State(dev)
     kw = st.kwargs(0)
     scores, t = torch.zeros(NB, V, device=dev), i32([T0], dev)
-    rules = ops._rules_args('t', dev, NB, V, stop=STOP, unfinished=st.un, alive=st.alive, grammar=G, gstate=st.gs, gbar=st.gbar,
-                            grem=st.grem, gleft=st.gleft, guided=True)
-    keyed = ops._key_args('t', dev, NB, V, in_key=RULE, gkey=st.gkey)
-    ranged = ops._register_args('t', dev, NB, V, register=REG, grange=st.grange, gpart=st.gpart, gfloor=st.gfloor, gap=1)
-    formed = ops._repeat_args('t', dev, NB, V, grammar=G, **{k: kw[k] for k in ops.REPEAT_KEYS})
-    no_guide = ops._guide_args('t', dev, NB, V, grammar=G)
+    rules = ops._rules_struct('t', dev, NB, V, **kw)                            # every group but the guide
+    rules.hist, rules.ld_hist = ptr(st.ids), LD_IDS                                # (read by the mask alone)
     table, zeros = torch.zeros(NB, 8, device=dev, dtype=torch.int32), i32([0] * NB, dev)
-    guide = ops._guide_args('t', dev, NB, V, grammar=G, melody=G.guide, guide=table, glen=zeros, gpos=zeros.clone(), gforce=zeros.clone())
-    UNFINISHED, ALIVE, CLS, GSTATE, GLEFT = 3, 4, 5, 9, 19        # positions in the flat rules arguments (include/musicxl.h)
-    PLAN, NPLAN, BARCOL, SPAN, GBARS, GCOPY, GSTOP = 0, 2, 3, 6, 7, 8, 9
+    gpos, gforce = zeros.clone(), zeros.clone()                                    # (held here: the struct keeps addresses only)
+    guided = ops._rules_struct('t', dev, NB, V, grammar=G, gstate=st.gs, melody=G.guide, guide=table, glen=zeros, gpos=gpos, gforce=gforce)
+    guide = {k: getattr(guided, k) for k in ('guide', 'ld_guide', 'glen', 'enter', 'leave', 'gpos', 'gforce')}
+    assert all(guide.values())
+    REPEAT = ('plan', 'nplan', 'barcol', 'gbars', 'gcopy', 'gstop')                # the group's pointers
 
-    def without(args, *at, **put):
-        out = list(args)
-        for i in at:
-            out[i] = None
-        for i, v in put.items():
-            out[int(i[1:])] = v
-        return out
+    def without(*names, **put):
+        """a copy of `rules` with the named pointers NULL and the fields of `put` set"""
+        r = type(rules).from_buffer_copy(rules)
+        for k in names:
+            assert getattr(r, k), k
+            setattr(r, k, None)
+        for k, v in put.items():
+            assert hasattr(r, k), k
+            setattr(r, k, v)
+        return r
 
-    def mask(rules=rules, guided=no_guide, formed=formed, hist=st.ids):
-        return lib().mxl_formed_rules_mask(ptr(scores), scores.stride(0), NB, V, ptr(t), *rules, *keyed, *guided, *ranged, *formed,
-                                           ptr(hist), LD_IDS if hist is not None else 0, None)
+    def mask(r=rules):
+        return lib().mxl_rules_mask(ptr(scores), scores.stride(0), NB, V, ptr(t), ctypes.byref(r), None)
 
-    def advance(rules=rules, guided=no_guide, formed=formed):
-        return lib().mxl_formed_rules_advance(ptr(st.ids), LD_IDS, ptr(t), NB, V, *rules, *keyed, *guided, *ranged, *formed, None)
+    def advance(r=rules):
+        return lib().mxl_rules_advance(ptr(st.ids), LD_IDS, ptr(t), NB, V, ctypes.byref(r), None)
 
     for call in (mask, advance):
-        assert call(rules=without(rules, GLEFT)) == EINVAL                        # the group without the count
-        assert call(rules=without(rules, CLS)) == EINVAL                          # ... without the token classes
-        assert call(guided=guide) == EINVAL                                       # guide and repeat together
-        for at in (PLAN, NPLAN, BARCOL, GBARS, GCOPY, GSTOP):                     # half a group
-            assert call(formed=without(formed, at)) == EINVAL, at
-        assert call(formed=without(formed, **{f'i{SPAN}': 2})) == EINVAL and call(formed=without(formed, **{f'i{SPAN}': -1})) == EINVAL
-        assert call(formed=without(formed, i1=0)) == EINVAL                       # ld_plan
-    assert mask(hist=None) == EINVAL                                              # the mask sees no ids: it needs the history
-    assert advance(rules=without(rules, UNFINISHED, ALIVE)) == EINVAL             # where the words move, the stop group
+        assert call(without('gleft')) == EINVAL                                   # the group without the count
+        assert call(without('cls')) == EINVAL                                     # ... without the token classes
+        assert call(without(**guide)) == EINVAL                                   # guide and repeat together
+        for name in REPEAT:                                                       # half a group
+            assert call(without(name)) == EINVAL, name
+        assert call(without(span=2)) == EINVAL and call(without(span=-1)) == EINVAL
+        assert call(without(ld_plan=0)) == EINVAL
+    assert mask(without('hist', ld_hist=0)) == EINVAL                             # the mask sees no ids: it needs the history
+    assert advance(without('unfinished', 'alive')) == EINVAL                      # where the words move, the stop group
     assert st.words() == st.start() and torch.equal(st.barcol.cpu(), st.barcol_host) and torch.equal(st.ids.cpu(), st.ids_host)
-    assert mask(rules=without(rules, UNFINISHED, ALIVE)) == 0 and mask(guided=guide, formed=ops._repeat_args('t', dev, NB)) == 0
+    assert mask(without('unfinished', 'alive')) == 0
+    assert mask(without(*REPEAT, ld_plan=0, renter=0, rleave=0, span=0, **guide)) == 0
     torch.cuda.synchronize()
     for bad, what in ((dict(gcopy=None), 'gbars and gstop need gcopy'), (dict(repeat=None), 'gcopy needs repeat'),
                       (dict(repeat=TOK.grammar().repeat), 'gcopy needs repeat'), (dict(gstop=None), 'the repeat group needs'),

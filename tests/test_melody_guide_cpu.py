@@ -1,6 +1,6 @@
 """The guide rule behind `generate(melody=...)` on the host (grammar.MelodyGuide): the rule on a hand-written stream,
 `tokenizer.melody_guide` on a grammar-clean piece, generate.melody_config's refusals, generate.check_melody, and the argument checks
-of the three mxl_guided_* entries, which run before any launch.  The device side is tests/test_melody_guide_gpu.py."""
+of the three entries that take the guide group (mxl_sample_step, mxl_rules_mask, mxl_rules_advance), which run before any launch.  The device side is tests/test_melody_guide_gpu.py."""
 import numpy as np
 import pytest
 import torch
@@ -181,35 +181,35 @@ def test_check_melody():
 
 
 def _rules(**given):
-    """the flat rules arguments, the key group and the guide group (include/musicxl.h) with every group off, then `given`; pointers
-    are never followed before a launch, so any non-zero value stands for one"""
-    r = dict(eos_id=3, pad_id=1, min_length=0, unfinished=None, alive=None, cls=None, allow=None, next=None, C=0, gstate=None,
-             slots=None, bars=None, opens=0, need_free=0, need_full=0, gbar=None, grem=None, count=0, end=0, gleft=None,
-             keys=None, pcs=None, inkey=None, gkey=None, guide=None, ld_guide=0, glen=None, enter=0, leave=0, gpos=None, gforce=None)
-    assert set(given) <= set(r)
-    r.update(given)
-    return list(r.values())
+    """an mxl_rules (include/musicxl.h) with every group off, then `given` by field name; pointers are never followed before a
+    launch, so any non-zero value stands for one"""
+    import ctypes
+    from symbolic_music_generation_amd import _lib
+    r = _lib.struct('mxl_rules')(eos_id=3, pad_id=1)
+    for k, v in given.items():
+        assert hasattr(r, k), k
+        setattr(r, k, v)
+    return ctypes.byref(r)
 
 
 def test_guided_argument_errors_without_gpu():
-    """the one check of the rules arguments runs before any launch, in all three mxl_guided_* entries"""
+    """the one check of the rules runs before any launch, in all three entries, with the guide group in the struct"""
     from symbolic_music_generation_amd import _lib
     L = _lib.lib()
     decl = _lib.declared_functions()
     assert [n for n in decl if n.startswith('mxl_sample_step')] == ['mxl_sample_step']
-    for name in ('mxl_guided_sample_step', 'mxl_guided_rules_mask', 'mxl_guided_rules_advance'):
-        assert name in decl
-    # each takes the keyed argument list, then the guide group, where the keyed entry ends (out_probs and / or the stream)
-    for name, tail in (('sample_step', 2), ('rules_mask', 1), ('rules_advance', 1)):
-        keyed, guided = decl[f'mxl_keyed_{name}'][1], decl[f'mxl_guided_{name}'][1]
-        assert guided[:len(keyed) - tail] == keyed[:-tail] and guided[-tail:] == keyed[-tail:] and len(guided) == len(keyed) + 7
+    # the guide group crosses the ABI inside mxl_rules, behind the key group: no entry of its own
+    assert not [n for n in decl if 'guided' in n or 'keyed' in n]
+    fields = [f for f, _ in _lib.struct('mxl_rules')._fields_]
+    at = fields.index('gkey') + 1
+    assert fields[at:at + 7] == ['guide', 'ld_guide', 'glen', 'enter', 'leave', 'gpos', 'gforce']
     Pt = 4096                                                      # stands for a device pointer
     step = [Pt, 16, 16, Pt, 8, Pt, Pt, 0, 2, 0, 0, 1.0, 1.0, 1.0, 1.0, Pt, Pt, 8, 1.0, Pt]
-    entries = {'mxl_guided_sample_step': lambda r: L.mxl_guided_sample_step(*step, *r, None, None),
-               'mxl_guided_rules_mask': lambda r: L.mxl_guided_rules_mask(Pt, 16, 2, 16, Pt, *r, None),
-               'mxl_guided_rules_advance': lambda r: L.mxl_guided_rules_advance(Pt, 8, Pt, 2, 16, *r, None)}
+    entries = {'mxl_sample_step': lambda r: L.mxl_sample_step(*step, r, None, None),
+               'mxl_rules_mask': lambda r: L.mxl_rules_mask(Pt, 16, 2, 16, Pt, r, None),
+               'mxl_rules_advance': lambda r: L.mxl_rules_advance(Pt, 8, Pt, 2, 16, r, None)}
     # nothing in force: the unfused pair returns before any launch, so 0 here means the arguments passed the check
-    assert entries['mxl_guided_rules_mask'](_rules()) == 0 and entries['mxl_guided_rules_advance'](_rules()) == 0
+    assert entries['mxl_rules_mask'](_rules()) == 0 and entries['mxl_rules_advance'](_rules()) == 0
     grammar = dict(cls=Pt, allow=Pt, next=Pt, C=12, gstate=Pt)
     guide = dict(guide=Pt, ld_guide=8, glen=Pt, enter=1, leave=2, gpos=Pt, gforce=Pt)
     bad = {'gpos without gforce': {**grammar, **guide, 'gforce': None},
@@ -224,5 +224,5 @@ def test_guided_argument_errors_without_gpu():
         for name, call in entries.items():
             assert call(_rules(**given)) == -1, (what, name)
     # the fused launch alone: the guide rides on the grammar there
-    assert entries['mxl_guided_sample_step'](_rules(cls=Pt, **guide)) == -1
-    assert L.mxl_guided_sample_step(None, *step[1:], *_rules(**grammar, **guide), None, None) == -1            # NULL scores
+    assert entries['mxl_sample_step'](_rules(cls=Pt, **guide)) == -1
+    assert L.mxl_sample_step(None, *step[1:], _rules(**grammar, **guide), None, None) == -1                    # NULL scores
