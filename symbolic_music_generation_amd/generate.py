@@ -53,34 +53,20 @@ def sampling_config(do_sample: bool = False, top_k: Optional[int] = None, top_p:
 
 
 def sample_unfused(scores: torch.Tensor, V: int, ids: torch.Tensor, t_dev: torch.Tensor, rng: torch.Tensor, seed: int, sampling: dict,
-                   stop: Optional[tuple] = None, unfinished: Optional[torch.Tensor] = None, alive: Optional[torch.Tensor] = None,
-                   grammar=None, gstate: Optional[torch.Tensor] = None, gbar: Optional[torch.Tensor] = None,
-                   grem: Optional[torch.Tensor] = None, gleft: Optional[torch.Tensor] = None, in_key=None,
-                   gkey: Optional[torch.Tensor] = None, melody=None, guide: Optional[torch.Tensor] = None,
-                   glen: Optional[torch.Tensor] = None, gpos: Optional[torch.Tensor] = None, gforce: Optional[torch.Tensor] = None,
-                   register=None, grange: Optional[torch.Tensor] = None, gpart: Optional[torch.Tensor] = None,
-                   gfloor: Optional[torch.Tensor] = None, gap: int = -1, repeat=None, plan: Optional[torch.Tensor] = None,
-                   nplan: Optional[torch.Tensor] = None, barcol: Optional[torch.Tensor] = None, span: int = 0,
-                   gbars: Optional[torch.Tensor] = None, gcopy: Optional[torch.Tensor] = None, gstop: Optional[torch.Tensor] = None):
+                   rules: Optional[ops.RuleState] = None):
     """The sampler tail as separate launches (what mxl_sample_step does in one): next token of every row from the first V columns
-    of `scores` -> ids[:, t + 1], position and RNG counters advanced.  stop = (eos, pad, min_length) with unfinished / alive and
-    grammar with gstate are optional, and a grammar with a bar budget takes gbar / grem as well; gleft (the bars every row may
-    still open) turns the grammar's bar count on, in_key (a grammar.KeyRule) with gkey the key rule, melody (a grammar.MelodyGuide)
-    with guide / glen / gpos / gforce the guide rule, register (a grammar.RegisterRule) with grange / gpart / gfloor and gap the register
-    rule, repeat (a grammar.BarRepeat) with plan / nplan / barcol / gbars / gcopy / gstop and span the repeat rule, whose mask reads
-    `ids` as the rows' history (ops.rules_in_force).  The mask writes into `scores` in place.  Four launches, two
-    where no rule is in force."""
-    rules = ops.rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos,
-                               gforce, register, grange, gpart, gfloor, gap, repeat, plan, nplan, barcol, span, gbars, gcopy, gstop)
-    past = dict(hist=ids) if 'repeat' in rules else {}
+    of `scores` -> ids[:, t + 1], position and RNG counters advanced, under those of `rules` (an ops.RuleState) that are in force;
+    the repeat rule's mask reads `ids` as the rows' history.  The mask writes into `scores` in place.  Four launches, two where no
+    rule is in force."""
+    rules = (ops.RuleState() if rules is None else rules).in_force()
     sc = scores[:, :V] if scores.shape[1] != V else scores
     # HF's processor order is penalty, min_length, grammar, warpers; here the penalty runs inside the sampler, after the mask: -inf
     # stays -inf under it, so the result is the same
-    ops.rules_mask(sc, V, t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')}, **past)
+    ops.rules_mask(sc, V, t_dev, rules, hist=ids if rules.repeat is not None else None)
     ops.sample(sc, ids, t_dev, rng, seed, **sampling)
     ops.decode_advance(t_dev, rng)
     # the words move before the stop rule rewrites `unfinished`, which still tells which rows chose their token
-    ops.rules_advance(ids, t_dev, **rules)
+    ops.rules_advance(ids, t_dev, rules)
 
 
 def resolve_max_length(max_length: Optional[int], max_new_tokens: Optional[int], prompt_len: int, default: int) -> int:
@@ -703,8 +689,8 @@ class RowRules:
     captured step finds the next generation's guides where it found the last one's.  The repeat group (`repeat`, a grammar.BarRepeat,
     with the generation's `span`) has the words gbars / gcopy / gstop (bars opened, the column of the row's own ids the next token is
     copied from, and where the copy ends) and three tables kept the same way: `plan` (B, ld) and `nplan` (B,) int32, uploaded by
-    `start`, and `barcol` (B, ld) int32, which the device writes.  A further rule is a row here, a field in RulePlan, a line in
-    rules_config and `start`, and a key in `kwargs` / `graph_key` ("adding a rule")."""
+    `start`, and `barcol` (B, ld) int32, which the device writes.  A further rule is a row here, a field in RulePlan and in
+    ops.RuleState, and a line in rules_config, `start`, `state` and `graph_key` ("adding a rule")."""
     WORDS = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey', 'gpos', 'gforce', 'grange', 'gpart', 'gfloor', 'gbars', 'gcopy',
              'gstop')
     STATE = WORDS + ('alive',)
@@ -721,7 +707,7 @@ class RowRules:
         self.gkey.fill_(-1)
         self.gcopy.fill_(-1)
         self.stop = self.grammar = self.n_bars = self.in_key = self.melody = self.melody_plan = self.register = self.repeat = None
-        self.bars, self.gap, self.span = False, -1, 0
+        self.bars, self.gap, self.span, self._state = False, -1, 0, None
         self._reset_register()
         self.guide = torch.zeros(batch, 64, device=dev, dtype=torch.int32)
         self.glen = torch.zeros(batch, device=dev, dtype=torch.int32)
@@ -748,6 +734,7 @@ class RowRules:
         No rule judges the prompt's pitches.  A plan built for another decoder (row count, vocabulary, grammar) raises."""
         stop, grammar, n_bars, in_key, keys, melody, register = plan[:7]
         form, melody = plan.form, plan.guide              # (the field `melody` holds the one or the other)
+        self._state = None
         check_grammar_args(grammar, vocab_size, stop)
         if register is not None and (register.rule.vocab_size != int(vocab_size) or register.B != self.B):
             raise MusicXLError(f'the register rule must span the model\'s {int(vocab_size)} tokens and hold one entry per row '
@@ -833,14 +820,17 @@ class RowRules:
         if self.bars:
             check_bar_count_start(self.grammar, self.n_bars, self.gstate)
 
-    def kwargs(self) -> dict:
-        """the rules keywords of ops.sample_step and sample_unfused"""
-        return dict(stop=self.stop, unfinished=self.unfinished, alive=self.alive, grammar=self.grammar, gstate=self.gstate,
-                    gbar=self.gbar, grem=self.grem, gleft=self.gleft if self.bars else None, in_key=self.in_key, gkey=self.gkey,
-                    melody=self.melody, guide=self.guide, glen=self.glen, gpos=self.gpos, gforce=self.gforce,
-                    register=self.register, grange=self.grange, gpart=self.gpart, gfloor=self.gfloor, gap=self.gap,
-                    repeat=self.repeat, plan=self.plan, nplan=self.nplan, barcol=self.barcol, span=self.span, gbars=self.gbars,
-                    gcopy=self.gcopy, gstop=self.gstop)
+    def state(self) -> ops.RuleState:
+        """the rules and their state as ops.sample_step and sample_unfused take them, gathered once per `start`: every member is
+        fixed from there on, the regrown guide / plan / barcol included -- a rule attribute assigned after `start` does not reach it"""
+        if self._state is None:
+            self._state = ops.RuleState(
+                stop=self.stop, unfinished=self.unfinished, alive=self.alive, grammar=self.grammar, gstate=self.gstate, gbar=self.gbar,
+                grem=self.grem, gleft=self.gleft if self.bars else None, in_key=self.in_key, gkey=self.gkey, melody=self.melody,
+                guide=self.guide, glen=self.glen, gpos=self.gpos, gforce=self.gforce, register=self.register, grange=self.grange,
+                gpart=self.gpart, gfloor=self.gfloor, gap=self.gap, repeat=self.repeat, plan=self.plan, nplan=self.nplan,
+                barcol=self.barcol, span=self.span, gbars=self.gbars, gcopy=self.gcopy, gstop=self.gstop)
+        return self._state
 
     def graph_key(self, dev) -> tuple:
         """what a captured sampler launch holds of the rules: which of them are on, the identity of the grammar's and the budget's
@@ -1519,13 +1509,13 @@ class XLDecoder(RuledGenerate):
         """next token of every row from `scores` (log-probabilities, or the head's logits: see mxl_sample_step) -> ids[:, t + 1];
         position and RNG counters advanced.  Short chain: the same launch leaves the token's embedding row in h[0] for the next step."""
         c = self.eng.cfg
-        state = self.rules.kwargs()
+        state = self.rules.state()
         if self.fused_sampler:      # the masks, the stop rule, the live-row count and the state advance ride on the sampler launch
             ops.sample_step(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed,
                             self.eng.w16('transformer.word_emb.emb_layers.0.weight'), self.h[0], math.sqrt(c.d_model), self.step_ctr,
-                            **state, **sampling)
+                            state, **sampling)
         else:
-            sample_unfused(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, **state)
+            sample_unfused(scores, c.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, state)
 
     # ---------------------------------------------------------------- one token
     def force_tokens(self, tokens: torch.Tensor):
@@ -1692,8 +1682,8 @@ class XLDecoder(RuledGenerate):
         the chosen tokens at column t + 1"""
         V, st = self.eng.cfg.vocab_size, self.beam
         nb, eos, pad, lp, early, ng, pen, sample, top_k, top_p, temperature, typical_p = self._beam_args
-        rules = ops.rules_in_force(**self.rules.kwargs())
-        ops.rules_mask(self.logp, V, self.t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
+        rules = self.rules.state().in_force()
+        ops.rules_mask(self.logp, V, self.t_dev, rules)
         store = (st.hyp_ids, st.hyp_len, st.hyp_score, st.hyp_n, st.done, st.n_done, st.beam_idx, st.moved)
         words = dict(words=self.rules.buf, n_words=len(RowRules.WORDS))
         if sample:
@@ -1714,8 +1704,8 @@ class XLDecoder(RuledGenerate):
         else:                       # whole ring rows move: mxl_beam_reorder, or the fp8 layout's index_select reference
             self.layout.follow_beams(self)
         ops.decode_advance(self.t_dev, self.rng)
-        if rules['grammar'] is not None or rules['in_key'] is not None or rules.get('register') is not None:
-            ops.rules_advance(self.ids, self.t_dev, **rules)
+        if rules.moves_words:
+            ops.rules_advance(self.ids, self.t_dev, rules)
         self._forward_token()
 
     # ---------------------------------------------------------------- contrastive search on the device (contrastive_search_device)
@@ -1758,10 +1748,10 @@ class XLDecoder(RuledGenerate):
         picked row's stashed k / v go into the prompt's rings (the layout's `settle`)"""
         c, cs = self.eng.cfg, self.cs
         K, alpha, eos, pad = self._cs_args
-        rules = ops.rules_in_force(**self.rules.kwargs())
-        ruled = rules['grammar'] is not None or rules['in_key'] is not None or rules.get('register') is not None
+        rules = self.rules.state().in_force()
+        ruled = rules.moves_words
         if ruled:
-            ops.rules_mask(self.logp, c.vocab_size, self.t_dev, **{k: v for k, v in rules.items() if k not in ('unfinished', 'alive')})
+            ops.rules_mask(self.logp, c.vocab_size, self.t_dev, rules)
         ops.contrastive_topk(self.logp, c.vocab_size, cs.sel, self.ids, self.t_dev, cs.probs, cs.dead, self.unfinished, pad)
         ops.decode_advance(self.t_dev, self.rng)
         self._forward_token()
@@ -1770,7 +1760,7 @@ class XLDecoder(RuledGenerate):
         ops.contrastive_step(cs.ctx, cs.inv, self.t_dev, self.h[c.n_layer & 1], cs.probs, cs.dead, alpha, cs.score, cs.sel, self.ids,
                              self.unfinished, cs.n_done, eos, pad, stop_later=ruled)
         if ruled:
-            ops.rules_advance(self.ids, self.t_dev, **rules)
+            ops.rules_advance(self.ids, self.t_dev, rules)
         self.layout.settle(self, K)     # the slot of the step follows the pick, or the picked row's stash is committed to it
 
     def _trace(self):

@@ -6,7 +6,7 @@ from libmusicxl.so and raises if the library is missing or a launch fails.  No C
 import ctypes as C
 import math
 import os
-from typing import Optional, Sequence
+from typing import Any, NamedTuple, Optional, Sequence
 
 import torch
 
@@ -133,184 +133,214 @@ def decode_qkv(x, wqkv, qkv, kc, vc, t_dev, rrb, qr_out, dh):
                                _stream()), 'mxl_decode_qkv')
 
 
-def rules_in_force(stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None,
-                   gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None,
-                   gfloor=None, gap=-1, repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None, gcopy=None,
-                   gstop=None) -> dict:
-    """The rules of a generation as its decoders describe them -> the keywords of rules_mask / rules_advance, where a group is on
-    exactly when its state tensor is given.  The decoders say which rules hold with `stop` (the eos rule), `grammar` (the grammar,
-    and its bar budget if it has one), `gleft` (the bar count), `in_key` (the key rule), `melody` (the guide rule, a
-    grammar.MelodyGuide), `register` (the register rule, a grammar.RegisterRule, with the launch's `gap`) and `repeat` (the repeat
-    rule, a grammar.BarRepeat, with the launch's `span`) and may hand over state tensors of rules that are off: those are dropped
-    here, and a rule that is on without its state raises."""
-    if repeat is not None:                  # (a call without the rule carries no key of it)
-        if grammar is None or gleft is None or stop is None or melody is not None:
-            raise MusicXLError('the repeat rule rides on a grammar, needs the bar count (gleft) and the eos rule, and excludes the guide')
-        if any(x is None for x in (plan, nplan, barcol, gbars, gcopy, gstop)):
-            raise MusicXLError('the repeat rule needs plan, nplan, barcol, gbars, gcopy and gstop')
-        return dict(rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos,
-                                   gforce, register, grange, gpart, gfloor, gap), repeat=repeat, plan=plan, nplan=nplan, barcol=barcol,
-                    span=int(span), gbars=gbars, gcopy=gcopy, gstop=gstop)
-    budget = grammar is not None and grammar.budget is not None
-    if stop is not None and (unfinished is None or alive is None):
-        raise MusicXLError('the eos rule needs unfinished and alive')
-    if grammar is None and gleft is not None:
-        raise MusicXLError('the bar count rides on a grammar')
-    if grammar is not None and gstate is None:
-        raise MusicXLError('a grammar needs gstate')
-    if budget and (gbar is None or grem is None):
-        raise MusicXLError('a grammar with a bar budget needs gbar and grem')
-    if in_key is not None and gkey is None:
-        raise MusicXLError('the key rule needs gkey')
-    if melody is not None and (grammar is None or guide is None or glen is None or gpos is None or gforce is None):
-        raise MusicXLError('the guide rides on a grammar and needs guide, glen, gpos and gforce')
-    if register is not None and (grange is None or gpart is None or gfloor is None):
-        raise MusicXLError('the register rule needs grange, gpart and gfloor')
-    on = melody is not None
-    if register is not None:                # (a call without the rule carries no key of it)
-        return dict(rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos,
-                                   gforce), register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=int(gap))
-    return dict(stop=stop, unfinished=unfinished if stop is not None else None, alive=alive if stop is not None else None,
-                grammar=grammar, gstate=gstate if grammar is not None else None, gbar=gbar if budget else None,
-                grem=grem if budget else None, gleft=gleft, in_key=in_key, gkey=gkey if in_key is not None else None,
-                melody=melody, guide=guide if on else None, glen=glen if on else None, gpos=gpos if on else None,
-                gforce=gforce if on else None)
+_T = Optional[torch.Tensor]
+_REPEAT_STATE = ('plan', 'nplan', 'barcol', 'gbars', 'gcopy', 'gstop')          # the tensors of RuleState's repeat group
 
 
-def _rules_struct(what, device, B, V=None, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None,
-                  gleft=None, in_key=None, gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None,
-                  grange=None, gpart=None, gfloor=None, gap=-1, repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None,
-                  gcopy=None, gstop=None):
-    """the mxl_rules of mxl_sample_step / mxl_rules_mask / mxl_rules_advance (include/musicxl.h, "Rules of a generation"), checked
-    and filled by field name: a group is on exactly when its state tensor is given -- unfinished (with alive and stop = (eos, pad,
-    min_length)), gstate, gbar (with grem), gleft, gkey, gpos (with gforce), gpart (with gfloor), gcopy (with gbars, gstop) -- and
-    takes its tables from `grammar`, `in_key`, `melody`, `register` and `repeat`, which must span the V tokens of the scores.  A field
-    that is not set stays zero: its group is off.  (hist / ld_hist, which the mask alone reads, are rules_mask's to set.)"""
-    eos, pad, min_length = stop if stop is not None else (-1, 0, 0)
-    f = dict(eos_id=int(eos), pad_id=int(pad), min_length=int(min_length or 0))
-    # stop, grammar, budget, count
-    if unfinished is not None:
-        if stop is None:
-            raise MusicXLError(f'{what}: unfinished needs stop = (eos, pad, min_length)')
-        _req(unfinished, torch.int32, f'{what} unfinished')
-    f.update(unfinished=_p(unfinished), alive=_p(alive))
-    if gstate is not None or gbar is not None or grem is not None or gleft is not None or gpos is not None or gcopy is not None:
-        if grammar is None:
-            raise MusicXLError(f'{what}: gstate, gbar / grem, gleft and the guide ride on a grammar')
-        if V is not None and grammar.vocab_size != int(V):
-            raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
-        cls, allow, nxt = grammar.to(device)
-        f.update(cls=_p(cls), C=grammar.n_classes)
-    if gstate is not None:
-        _req(gstate, torch.int32, f'{what} gstate')
-        if gstate.numel() != B:
-            raise MusicXLError(f'gstate holds {gstate.numel()} rows, the scores {B}')
-        f.update(allow=_p(allow), next=_p(nxt), gstate=_p(gstate))
-    if gbar is not None or grem is not None:
-        bud = grammar.budget
-        slots, bars = _budget_state(bud, device, B, gbar, grem, what)
-        f.update(slots=_p(slots), bars=_p(bars), opens=bud.opens, need_free=bud.need_free, need_full=bud.need_full, gbar=_p(gbar),
-                 grem=_p(grem))
-    if gleft is not None:
-        cnt = grammar.bar_count
-        if cnt is None:
-            raise MusicXLError(f'{what}: the grammar carries no bar count (grammar.BarCount; the music grammar has one)')
-        _req(gleft, torch.int32, f'{what} gleft')
-        if gleft.numel() != B or not gleft.is_contiguous():
-            raise MusicXLError(f'{what}: gleft must be contiguous ({B},) int32')
-        f.update(count=cnt.count, end=cnt.end, gleft=_p(gleft))
-    # repeat: the class masks of `repeat` (a grammar.BarRepeat over `grammar`), the rows' plans plan (B, ld) int32 with their lengths
-    # nplan (B,) int32, the table barcol (B, ld) int32 the device writes (same row stride as plan), the launch's span, gbars and gstop
-    if gcopy is None:
-        if gbars is not None or gstop is not None:
-            raise MusicXLError(f'{what}: gbars and gstop need gcopy')
-    else:
-        if repeat is None or repeat.grammar is not grammar:
-            raise MusicXLError(f'{what}: gcopy needs repeat, the repeat rule of the grammar (grammar.repeat)')
-        if any(x is None for x in (plan, nplan, barcol, gbars, gstop)):
-            raise MusicXLError(f'{what}: the repeat group needs plan, nplan, barcol, gbars, gcopy and gstop')
-        for t, name in ((plan, 'plan'), (nplan, 'nplan'), (barcol, 'barcol'), (gbars, 'gbars'), (gcopy, 'gcopy'), (gstop, 'gstop')):
-            _req(t, torch.int32, f'{what} {name}')
-        for t, name in ((plan, 'plan'), (barcol, 'barcol')):           # one width serves both: it is the row stride and nplan's clamp
-            if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous() or t.shape != plan.shape:
-                raise MusicXLError(f'{what}: {name} must be contiguous ({B}, >= 1) int32, plan and barcol of one shape')
-        for t, name in ((nplan, 'nplan'), (gbars, 'gbars'), (gcopy, 'gcopy'), (gstop, 'gstop')):
-            if t.numel() != B or not t.is_contiguous():
-                raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
-        if int(span) not in (0, 1):
-            raise MusicXLError(f'{what}: span is 0 (the whole bar) or 1 (up to the first `leave` token), got {span}')
-        f.update(plan=_p(plan), ld_plan=plan.shape[1], nplan=_p(nplan), barcol=_p(barcol), renter=repeat.enter, rleave=repeat.leave,
-                 span=int(span), gbars=_p(gbars), gcopy=_p(gcopy), gstop=_p(gstop))
-    # key: the tables of `in_key` (a grammar.KeyRule)
-    if gkey is not None:
-        if in_key is None:
-            raise MusicXLError(f'{what}: gkey needs in_key, the key rule that holds its tables')
-        if V is not None and in_key.vocab_size != int(V):
-            raise MusicXLError(f'the key rule spans {in_key.vocab_size} tokens, the scores span {int(V)}')
-        _req(gkey, torch.int32, f'{what} gkey')
-        if gkey.numel() != B or not gkey.is_contiguous():
-            raise MusicXLError(f'{what}: gkey must be contiguous ({B},) int32')
-        keys, pcs, inkey = in_key.to(device)
-        f.update(keys=_p(keys), pcs=_p(pcs), inkey=_p(inkey), gkey=_p(gkey))
-    # guide: the class masks of `melody` (a grammar.MelodyGuide over `grammar`), the rows' guide tokens guide (B, ld) int32 and their
-    # lengths glen (B,) int32, and the second word gforce
-    if gpos is None:
-        if gforce is not None:
-            raise MusicXLError(f'{what}: gforce needs gpos')
-    else:
-        if melody is None or melody.grammar is not grammar:
-            raise MusicXLError(f'{what}: gpos needs melody, the guide rule of the grammar (grammar.guide)')
-        if guide is None or glen is None or gforce is None:
-            raise MusicXLError(f'{what}: the guide group needs guide, glen, gpos and gforce')
-        for t, name in ((guide, 'guide'), (glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
-            _req(t, torch.int32, f'{what} {name}')
-        if guide.dim() != 2 or guide.shape[0] != B or guide.shape[1] < 1 or guide.stride(1) != 1 or guide.stride(0) < guide.shape[1]:
-            raise MusicXLError(f'{what}: guide must be ({B}, >= 1) int32 rows with unit column stride')
-        for t, name in ((glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
-            if t.numel() != B or not t.is_contiguous():
-                raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
-        # (glen[b] <= the row width is the caller's to keep; the kernels clamp to ld_guide as well)
-        f.update(guide=_p(guide), ld_guide=guide.stride(0), glen=_p(glen), enter=melody.enter, leave=melody.leave, gpos=_p(gpos),
-                 gforce=_p(gforce))
-    # register: the table of `register` (a grammar.RegisterRule), the rows' bounds grange, the second word gfloor, the launch's gap
-    if gpart is not None:
-        if register is None:
-            raise MusicXLError(f'{what}: gpart needs register, the register rule that holds its table')
-        if grange is None or gfloor is None:
-            raise MusicXLError(f'{what}: the register group needs grange, gpart and gfloor')
-        if V is not None and register.vocab_size != int(V):
-            raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the scores span {int(V)}')
-        for t, name in ((grange, 'grange'), (gpart, 'gpart'), (gfloor, 'gfloor')):
-            _req(t, torch.int32, f'{what} {name}')
-            if t.numel() != B or not t.is_contiguous():
-                raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
-        if not -1 <= int(gap) <= 127:
-            raise MusicXLError(f'{what}: gap must lie in -1..127, got {gap}')
-        f.update(reg=_p(register.to(device)), grange=_p(grange), gpart=_p(gpart), gfloor=_p(gfloor), gap=int(gap))
-    return struct('mxl_rules')(**f)
+class RuleState(NamedTuple):
+    """The rules of one generation and their per-row state on the device, as the sampler launches take them (sample_step, rules_mask,
+    rules_advance; on the device the mxl_rules of include/musicxl.h, "Rules of a generation").  Eight groups; each has a rule the
+    decoder names and state tensors, (B,) int32 unless said otherwise, and a launch applies a group exactly when its state is given:
+      stop      stop = (eos_id, pad_id, min_length), with unfinished (1 = live) and alive (1,) int32, the live-row count
+      grammar   grammar (a grammar.TokenGrammar), with gstate: barred tokens masked and gstate advanced, with or without the eos rule
+      budget    the grammar's bar budget (grammar.budget), with gbar and grem, the bar's length and its free slots
+      count     the grammar's bar count (grammar.bar_count), with gleft, the bars a row may still open (< 0 = no limit)
+      key       in_key (a grammar.KeyRule), with gkey, the row's key (< 0 = none): pitches outside it barred, with or without a grammar
+      guide     melody (a grammar.MelodyGuide, `grammar.guide`), with guide (B, ld) int32, glen, gpos and gforce: rows fed from their guides
+      register  register (a grammar.RegisterRule) and the scalar gap, with grange, gpart and gfloor: the open part's pitches kept in bounds
+      repeat    repeat (a grammar.BarRepeat, `grammar.repeat`) and the scalar span, with plan and barcol (B, ld) int32, nplan, gbars,
+                gcopy and gstop: planned bars repeat earlier bars of the row's own ids
+    A decoder says which rules hold with stop, grammar, gleft, in_key, melody, register and repeat and may carry state of rules that
+    are off (`in_force` drops it); `struct` turns a group on by its state tensor -- unfinished, gstate, gbar, gleft, gkey, gpos, gpart,
+    gcopy.  The three entries also take these fields as flat keywords, in this order, in place of the object.  It is a tuple: the
+    order of the fields is part of the contract (`struct` unpacks them by position), and it is compared with `is`, never with ==."""
+    stop: Optional[tuple] = None; unfinished: _T = None; alive: _T = None
+    grammar: Any = None; gstate: _T = None
+    gbar: _T = None; grem: _T = None
+    gleft: _T = None
+    in_key: Any = None; gkey: _T = None
+    melody: Any = None; guide: _T = None; glen: _T = None; gpos: _T = None; gforce: _T = None
+    register: Any = None; grange: _T = None; gpart: _T = None; gfloor: _T = None; gap: int = -1
+    repeat: Any = None; plan: _T = None; nplan: _T = None; barcol: _T = None; span: int = 0
+    gbars: _T = None; gcopy: _T = None; gstop: _T = None
+
+    def in_force(self) -> 'RuleState':
+        """these rules with every group that is off back at its defaults; a rule on without its state, or beside one it excludes, raises"""
+        s = self
+        budget = s.grammar is not None and s.grammar.budget is not None
+        if s.repeat is not None:
+            if s.grammar is None or s.gleft is None or s.stop is None or s.melody is not None:
+                raise MusicXLError('the repeat rule rides on a grammar, needs the bar count (gleft) and the eos rule, and excludes the guide')
+            if any(getattr(s, k) is None for k in _REPEAT_STATE):
+                raise MusicXLError('the repeat rule needs plan, nplan, barcol, gbars, gcopy and gstop')
+        if s.stop is not None and (s.unfinished is None or s.alive is None):
+            raise MusicXLError('the eos rule needs unfinished and alive')
+        if s.grammar is None and s.gleft is not None:
+            raise MusicXLError('the bar count rides on a grammar')
+        if s.grammar is not None and s.gstate is None:
+            raise MusicXLError('a grammar needs gstate')
+        if budget and (s.gbar is None or s.grem is None):
+            raise MusicXLError('a grammar with a bar budget needs gbar and grem')
+        if s.in_key is not None and s.gkey is None:
+            raise MusicXLError('the key rule needs gkey')
+        if s.melody is not None and (s.grammar is None or s.guide is None or s.glen is None or s.gpos is None or s.gforce is None):
+            raise MusicXLError('the guide rides on a grammar and needs guide, glen, gpos and gforce')
+        if s.register is not None and (s.grange is None or s.gpart is None or s.gfloor is None):
+            raise MusicXLError('the register rule needs grange, gpart and gfloor')
+        groups = ((s.stop is not None, ('unfinished', 'alive')), (s.grammar is not None, ('gstate',)),
+                  (budget, ('gbar', 'grem')), (s.in_key is not None, ('gkey',)),            # (the count's one tensor, gleft, is its own switch)
+                  (s.melody is not None, ('guide', 'glen', 'gpos', 'gforce')),
+                  (s.register is not None, ('grange', 'gpart', 'gfloor', 'gap')),
+                  (s.repeat is not None, _REPEAT_STATE + ('span',)))
+        off = [k for on, names in groups if not on for k in names]
+        return s._replace(**{k: s._field_defaults[k] for k in off})
+
+    @property
+    def moves_words(self) -> bool:
+        """a rule that keeps words of its own is on (the stop rule alone needs no mask and no advance launch of a search)"""
+        return self.grammar is not None or self.in_key is not None or self.register is not None
+
+    @property
+    def vocab_size(self) -> int:
+        """what the rules in force span, which must agree on it (0: no rule with a vocabulary is on)"""
+        s = self
+        if s.grammar is not None and s.in_key is not None and s.gkey is not None and s.grammar.vocab_size != s.in_key.vocab_size:
+            raise MusicXLError(f'the grammar classifies {s.grammar.vocab_size} tokens, the key rule spans {s.in_key.vocab_size}')
+        V = s.grammar.vocab_size if s.grammar is not None else (s.in_key.vocab_size if s.gkey is not None else 0)
+        if s.gpart is not None:
+            if V and s.register.vocab_size != V:
+                raise MusicXLError(f'the register rule spans {s.register.vocab_size} tokens, the other rules {V}')
+            V = s.register.vocab_size
+        return V
+
+    def struct(self, what, device, B, V=None):
+        """the mxl_rules of mxl_sample_step / mxl_rules_mask / mxl_rules_advance, checked and filled by field name: a group is on
+        exactly when its state tensor is given and takes its tables from `grammar`, `in_key`, `melody`, `register` and `repeat`,
+        which must span the V tokens of the scores.  A field that is not set stays zero: its group is off.  (hist / ld_hist, which
+        the mask alone reads, are rules_mask's to set.)"""
+        (stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos, gforce, register, grange,
+         gpart, gfloor, gap, repeat, plan, nplan, barcol, span, gbars, gcopy, gstop) = self
+        eos, pad, min_length = stop if stop is not None else (-1, 0, 0)
+        f = dict(eos_id=int(eos), pad_id=int(pad), min_length=int(min_length or 0))
+        # stop, grammar, budget, count
+        if unfinished is not None:
+            if stop is None:
+                raise MusicXLError(f'{what}: unfinished needs stop = (eos, pad, min_length)')
+            _req(unfinished, torch.int32, f'{what} unfinished')
+        f.update(unfinished=_p(unfinished), alive=_p(alive))
+        if gstate is not None or gbar is not None or grem is not None or gleft is not None or gpos is not None or gcopy is not None:
+            if grammar is None:
+                raise MusicXLError(f'{what}: gstate, gbar / grem, gleft and the guide ride on a grammar')
+            if V is not None and grammar.vocab_size != int(V):
+                raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the scores span {int(V)}')
+            cls, allow, nxt = grammar.to(device)
+            f.update(cls=_p(cls), C=grammar.n_classes)
+        if gstate is not None:
+            _req(gstate, torch.int32, f'{what} gstate')
+            if gstate.numel() != B:
+                raise MusicXLError(f'gstate holds {gstate.numel()} rows, the scores {B}')
+            f.update(allow=_p(allow), next=_p(nxt), gstate=_p(gstate))
+        if gbar is not None or grem is not None:
+            bud = grammar.budget
+            slots, bars = _budget_state(bud, device, B, gbar, grem, what)
+            f.update(slots=_p(slots), bars=_p(bars), opens=bud.opens, need_free=bud.need_free, need_full=bud.need_full, gbar=_p(gbar),
+                     grem=_p(grem))
+        if gleft is not None:
+            cnt = grammar.bar_count
+            if cnt is None:
+                raise MusicXLError(f'{what}: the grammar carries no bar count (grammar.BarCount; the music grammar has one)')
+            _req(gleft, torch.int32, f'{what} gleft')
+            if gleft.numel() != B or not gleft.is_contiguous():
+                raise MusicXLError(f'{what}: gleft must be contiguous ({B},) int32')
+            f.update(count=cnt.count, end=cnt.end, gleft=_p(gleft))
+        # repeat: the class masks of `repeat` (over `grammar`), the rows' plans with their lengths nplan, the table barcol the device
+        # writes (same row stride as plan), the launch's span and the words
+        if gcopy is None:
+            if gbars is not None or gstop is not None:
+                raise MusicXLError(f'{what}: gbars and gstop need gcopy')
+        else:
+            if repeat is None or repeat.grammar is not grammar:
+                raise MusicXLError(f'{what}: gcopy needs repeat, the repeat rule of the grammar (grammar.repeat)')
+            group = [(getattr(self, k), k) for k in _REPEAT_STATE]
+            if any(t is None for t, _ in group):
+                raise MusicXLError(f'{what}: the repeat group needs plan, nplan, barcol, gbars, gcopy and gstop')
+            for t, name in group:
+                _req(t, torch.int32, f'{what} {name}')
+            for t, name in [g for g in group if g[1] in ('plan', 'barcol')]:    # one width serves both: the row stride, nplan's clamp
+                if t.dim() != 2 or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous() or t.shape != plan.shape:
+                    raise MusicXLError(f'{what}: {name} must be contiguous ({B}, >= 1) int32, plan and barcol of one shape')
+            for t, name in [g for g in group if g[1] not in ('plan', 'barcol')]:
+                if t.numel() != B or not t.is_contiguous():
+                    raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
+            if int(span) not in (0, 1):
+                raise MusicXLError(f'{what}: span is 0 (the whole bar) or 1 (up to the first `leave` token), got {span}')
+            f.update(plan=_p(plan), ld_plan=plan.shape[1], nplan=_p(nplan), barcol=_p(barcol), renter=repeat.enter, rleave=repeat.leave,
+                     span=int(span), gbars=_p(gbars), gcopy=_p(gcopy), gstop=_p(gstop))
+        # key: the tables of `in_key`
+        if gkey is not None:
+            if in_key is None:
+                raise MusicXLError(f'{what}: gkey needs in_key, the key rule that holds its tables')
+            if V is not None and in_key.vocab_size != int(V):
+                raise MusicXLError(f'the key rule spans {in_key.vocab_size} tokens, the scores span {int(V)}')
+            _req(gkey, torch.int32, f'{what} gkey')
+            if gkey.numel() != B or not gkey.is_contiguous():
+                raise MusicXLError(f'{what}: gkey must be contiguous ({B},) int32')
+            keys, pcs, inkey = in_key.to(device)
+            f.update(keys=_p(keys), pcs=_p(pcs), inkey=_p(inkey), gkey=_p(gkey))
+        # guide: the class masks of `melody` (over `grammar`), the rows' guide tokens and their lengths glen, and the second word gforce
+        if gpos is None:
+            if gforce is not None:
+                raise MusicXLError(f'{what}: gforce needs gpos')
+        else:
+            if melody is None or melody.grammar is not grammar:
+                raise MusicXLError(f'{what}: gpos needs melody, the guide rule of the grammar (grammar.guide)')
+            if guide is None or glen is None or gforce is None:
+                raise MusicXLError(f'{what}: the guide group needs guide, glen, gpos and gforce')
+            for t, name in ((guide, 'guide'), (glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
+                _req(t, torch.int32, f'{what} {name}')
+            if guide.dim() != 2 or guide.shape[0] != B or guide.shape[1] < 1 or guide.stride(1) != 1 or guide.stride(0) < guide.shape[1]:
+                raise MusicXLError(f'{what}: guide must be ({B}, >= 1) int32 rows with unit column stride')
+            for t, name in ((glen, 'glen'), (gpos, 'gpos'), (gforce, 'gforce')):
+                if t.numel() != B or not t.is_contiguous():
+                    raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
+            # (glen[b] <= the row width is the caller's to keep; the kernels clamp to ld_guide as well)
+            f.update(guide=_p(guide), ld_guide=guide.stride(0), glen=_p(glen), enter=melody.enter, leave=melody.leave, gpos=_p(gpos),
+                     gforce=_p(gforce))
+        # register: the table of `register`, the rows' bounds grange, the second word gfloor, the launch's gap
+        if gpart is not None:
+            if register is None:
+                raise MusicXLError(f'{what}: gpart needs register, the register rule that holds its table')
+            if grange is None or gfloor is None:
+                raise MusicXLError(f'{what}: the register group needs grange, gpart and gfloor')
+            if V is not None and register.vocab_size != int(V):
+                raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the scores span {int(V)}')
+            for t, name in ((grange, 'grange'), (gpart, 'gpart'), (gfloor, 'gfloor')):
+                _req(t, torch.int32, f'{what} {name}')
+                if t.numel() != B or not t.is_contiguous():
+                    raise MusicXLError(f'{what}: {name} must be contiguous ({B},) int32')
+            if not -1 <= int(gap) <= 127:
+                raise MusicXLError(f'{what}: gap must lie in -1..127, got {gap}')
+            f.update(reg=_p(register.to(device)), grange=_p(grange), gpart=_p(gpart), gfloor=_p(gfloor), gap=int(gap))
+        return struct('mxl_rules')(**f)
 
 
-def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, *, stop=None, unfinished=None, alive=None,
-                grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None, melody=None, guide=None,
-                glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None, gfloor=None, gap=-1, repeat=None,
-                plan=None, nplan=None, barcol=None, span=0, gbars=None, gcopy=None, gstop=None, do_sample=False,
-                top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0, out_probs=None):
+def _rule_state(rules: Optional[RuleState], flat: dict) -> RuleState:
+    """the `rules` of an entry, or the same object from the flat keywords the entry takes in its place (an unknown one: TypeError)"""
+    if rules is None:
+        return RuleState(**flat)
+    if flat:
+        raise TypeError(f'rules= and the flat rule keywords ({", ".join(flat)}) exclude each other')
+    return rules
+
+
+def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter, rules: Optional[RuleState] = None, *, do_sample=False,
+                top_k=0, top_p=1.0, temperature=1.0, repetition_penalty=1.0, typical_p=1.0, out_probs=None, **flat):
     """sampler + embedding row of the sampled token (-> emb_out (B, d) bf16) + counter advance, one launch (V <= 2048).
     scores (B, >= V) f32: log-probabilities, or raw logits when repetition_penalty == 1.
-    The rules of the generation ride on the same launch (rules_in_force): stop = (eos_id, pad_id, min_length) with unfinished (B,)
-    int32 and alive (1,) int32 on the device; grammar (a grammar.TokenGrammar) with gstate (B,) int32, barred tokens masked and gstate
-    advanced, with or without the eos rule; a grammar with a bar budget (grammar.budget) needs gbar and grem (B,) int32 as well;
-    gleft (B,) int32, the bars every row may still open (< 0 = no limit), turns the grammar's bar count on; in_key (a grammar.KeyRule)
-    with gkey (B,) int32, the key of every row (< 0 = none), bars the pitches outside it, with or without a grammar; melody (a
-    grammar.MelodyGuide, `grammar.guide`) with guide (B, ld) int32, glen, gpos and gforce (B,) int32 feeds rows from their guides;
-    register (a grammar.RegisterRule) with grange, gpart and gfloor (B,) int32 and the scalar gap keeps the pitches of every row's open
-    part inside its bounds, with or without a grammar; repeat (a grammar.BarRepeat, `grammar.repeat`) with plan and barcol (B, ld)
-    int32, nplan, gbars, gcopy and gstop (B,) int32 and the scalar span makes planned bars repeat earlier bars of the row's own `ids`.
+    The rules of the generation ride on the same launch: `rules` (a RuleState, or its fields as keywords), those in force applied.
     out_probs (B, V) f32, with do_sample: the renormalised distribution the tokens were drawn from (test hook)."""
     B = scores.shape[0]
-    force = rules_in_force(stop, unfinished, alive, grammar, gstate, gbar, grem, gleft, in_key, gkey, melody, guide, glen, gpos, gforce,
-                           register, grange, gpart, gfloor, gap, repeat, plan, nplan, barcol, span, gbars, gcopy, gstop)
-    rules = _rules_struct('sample_step', scores.device, B, V, **force)
+    rules = _rule_state(rules, flat).in_force().struct('sample_step', scores.device, B, V)
     if out_probs is not None:
         _req(out_probs, torch.float32, 'sample_step out_probs')
         if tuple(out_probs.shape) != (B, int(V)) or not out_probs.is_contiguous():
@@ -322,54 +352,38 @@ def sample_step(scores, V, ids, t_dev, rng_ctr, seed, E, emb_out, scale, counter
                                 float(scale), _p(counter), C.byref(rules), _p(out_probs), _stream()), 'mxl_sample_step')
 
 
-def rules_mask(scores, V, t_dev, *, stop=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None, in_key=None, gkey=None,
-               melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None, gpart=None, gfloor=None, gap=-1,
-               repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None, gcopy=None, gstop=None, hist=None):
-    """before sample: scores[b, v] = -inf in place for every token a rule bars (mxl_rules_mask).  A rule is applied exactly when its
-    state is given: gstate (the grammar in state gstate[b]), gbar and grem (its bar budget), gleft (its bar count), each with
-    `grammar` for the tables, gkey (the key rule in key gkey[b]) with `in_key` for its tables, and gpos with gforce, guide, glen and
-    `melody` (the guide rule: a row fed from its guide keeps that one token), and gpart with gfloor, grange, gap and `register` (the
-    register rule), and gcopy with gbars, gstop, plan, nplan, barcol, span, `repeat` and hist, the (B, ld) int64 ids of the rows (the
-    repeat rule: a row that copies keeps the one token of its own history); stop = (eos, pad, min_length) bars eos while the rows are shorter than min_length.  No launch when nothing is
-    given."""
+def rules_mask(scores, V, t_dev, rules: Optional[RuleState] = None, *, hist=None, **flat):
+    """before sample: scores[b, v] = -inf in place for every token a rule bars (mxl_rules_mask).  `rules` (a RuleState, or its fields
+    as keywords) less unfinished / alive, which the mask does not read and the flat form does not take: a group is applied exactly
+    when its state is given, a row fed from its guide or copying a bar keeps that one token, and stop = (eos, pad, min_length) bars eos
+    while the rows are shorter than min_length.  hist: with the repeat group, the (B, ld) int64 ids of the rows, whose own history a
+    row copies from.  No launch when nothing is given."""
+    if 'unfinished' in flat or 'alive' in flat:
+        raise TypeError('rules_mask takes no unfinished / alive keyword: the stop rule moves in rules_advance')
+    rules = _rule_state(rules, flat)._replace(unfinished=None, alive=None)
     _req(scores, torch.float32, 'rules_mask scores')
     B = scores.shape[0]
     if scores.shape[1] < V or scores.stride(1) != 1:
         raise MusicXLError('rules_mask: scores must be (B, >= V) with unit column stride')
-    rules = _rules_struct('rules_mask', scores.device, B, V, stop=stop, grammar=grammar, gstate=gstate, gbar=gbar, grem=grem, gleft=gleft,
-                          in_key=in_key, gkey=gkey, melody=melody, guide=guide, glen=glen, gpos=gpos, gforce=gforce, register=register,
-                          grange=grange, gpart=gpart, gfloor=gfloor, gap=gap, repeat=repeat, plan=plan, nplan=nplan, barcol=barcol,
-                          span=span, gbars=gbars, gcopy=gcopy, gstop=gstop)
-    if gcopy is not None:
+    st = rules.struct('rules_mask', scores.device, B, V)
+    if rules.gcopy is not None:
         if hist is None or hist.dtype != torch.int64 or hist.dim() != 2 or hist.shape[0] != B or hist.stride(1) != 1:
             raise MusicXLError('rules_mask: the repeat group needs hist, the (B, .) int64 ids of the rows')
-        rules.hist, rules.ld_hist = _p(hist), hist.stride(0)
-    check(lib().mxl_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), C.byref(rules), _stream()), 'mxl_rules_mask')
+        st.hist, st.ld_hist = _p(hist), hist.stride(0)
+    check(lib().mxl_rules_mask(_p(scores), scores.stride(0), B, int(V), _p(t_dev), C.byref(st), _stream()), 'mxl_rules_mask')
 
 
-def rules_advance(ids, t_dev, *, stop=None, unfinished=None, alive=None, grammar=None, gstate=None, gbar=None, grem=None, gleft=None,
-                  in_key=None, gkey=None, melody=None, guide=None, glen=None, gpos=None, gforce=None, register=None, grange=None,
-                  gpart=None, gfloor=None, gap=-1, repeat=None, plan=None, nplan=None, barcol=None, span=0, gbars=None, gcopy=None,
-                  gstop=None):
-    """after sample + decode_advance: the words given (as rules_mask) move along the token at ids[b, t] in every row that chose it,
-    then, with unfinished and alive, that token goes through the stop rule stop = (eos, pad, min_length): rows with unfinished[b] == 0
-    get pad and keep their words (mxl_rules_advance).  No launch when nothing is given."""
+def rules_advance(ids, t_dev, rules: Optional[RuleState] = None, **flat):
+    """after sample + decode_advance: the words of `rules` (a RuleState, or its fields as keywords; the groups as rules_mask finds
+    them) move along the token at ids[b, t] in every row that chose it, then, with unfinished and alive, that token goes through the
+    stop rule stop = (eos, pad, min_length): rows with unfinished[b] == 0 get pad and keep their words (mxl_rules_advance).  No launch
+    when nothing is given."""
+    rules = _rule_state(rules, flat)
     B = ids.shape[0]
     if ids.dtype != torch.int64:
         raise MusicXLError('rules_advance: ids must be (B, .) int64')
-    rules = _rules_struct('rules_advance', ids.device, B, stop=stop, unfinished=unfinished, alive=alive, grammar=grammar, gstate=gstate,
-                          gbar=gbar, grem=grem, gleft=gleft, in_key=in_key, gkey=gkey, melody=melody, guide=guide, glen=glen, gpos=gpos,
-                          gforce=gforce, register=register, grange=grange, gpart=gpart, gfloor=gfloor, gap=gap, repeat=repeat, plan=plan,
-                          nplan=nplan, barcol=barcol, span=span, gbars=gbars, gcopy=gcopy, gstop=gstop)
-    # V: what the rules in force span, which must agree on it
-    if grammar is not None and in_key is not None and gkey is not None and grammar.vocab_size != in_key.vocab_size:
-        raise MusicXLError(f'the grammar classifies {grammar.vocab_size} tokens, the key rule spans {in_key.vocab_size}')
-    V = grammar.vocab_size if grammar is not None else (in_key.vocab_size if gkey is not None else 0)
-    if gpart is not None:
-        if V and register.vocab_size != V:
-            raise MusicXLError(f'the register rule spans {register.vocab_size} tokens, the other rules {V}')
-        V = register.vocab_size
-    check(lib().mxl_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, V, C.byref(rules), _stream()), 'mxl_rules_advance')
+    st = rules.struct('rules_advance', ids.device, B)
+    check(lib().mxl_rules_advance(_p(ids), ids.stride(0), _p(t_dev), B, rules.vocab_size, C.byref(st), _stream()), 'mxl_rules_advance')
 
 
 def key_scan(ids, Tp, in_key, gkey, first_bad, check_from=None):

@@ -309,7 +309,7 @@ class MyReformerModelWithLMHead(EngineModule):
                 Tf = cur if cur <= 64 else (cur + 63) // 64 * 64
                 out = self.engine.forward(buf[:, :Tf].contiguous(), labels=None, train=False)
                 last = out['logits'][:, cur - 1].contiguous()
-                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, **words.kwargs())
+                sample_unfused(last, V, buf, t_dev, rng, seed, sampling, words.state())
                 if Tf > cur:
                     buf[:, cur + 1:Tf] = pad          # keep the padding clean (the sampler wrote position `cur` only)
                 # a whole forward per token: reading the live-row count every STOP_CHUNK tokens costs nothing in comparison

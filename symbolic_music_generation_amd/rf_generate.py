@@ -146,7 +146,7 @@ class RFDecoder(RuledGenerate):
         if sampling is None:                 # the caller picks the token (beam search)
             return
         # (min_length and the grammar mask write into the logits: after the trace above)
-        sample_unfused(logits, self.eng.cfg.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, **self.rules.kwargs())
+        sample_unfused(logits, self.eng.cfg.vocab_size, self.ids, self.t_dev, self.rng, self.seed, sampling, self.rules.state())
 
     # ---------------------------------------------------------------- one token
     def step(self, t: int, sampling: dict):

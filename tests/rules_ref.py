@@ -168,8 +168,13 @@ def tail(dev, fused, scores, sampling, t0, *, width, seed, gen_seed, fill, stop=
     """one sampler tail over `scores` (B, V) at position t0; fused: the one launch (ops.sample_step), else mask / sample / advance.
     Returns (tokens = ids[:, t0 + 1] and out_probs, both on the host, emb, ids, (t, rng, ctr), E).  The embedding table E (V, width)
     is drawn from a generator seeded gen_seed, ids (B, 8) starts filled with `fill`, `seed` is the sampler's, and `rules` are the
-    rule keywords of ops.sample_step as they are.  The mask writes into `scores`, and the words given move in place."""
+    rule keywords of ops.sample_step as they are -- or rules=, an ops.RuleState that holds them all, the stop group included.  The
+    mask writes into `scores`, and the words given move in place."""
     from symbolic_music_generation_amd import ops
+    if 'rules' not in rules:
+        rules = dict(rules, stop=stop, unfinished=unfinished, alive=alive)
+    assert 'rules' not in rules or (len(rules) == 1 and stop is None and unfinished is None and alive is None), 'rules= holds every group'
+    mask = {k: v for k, v in rules.items() if k not in ('unfinished', 'alive')}
     n, vocab = scores.shape
     gen = torch.Generator(device=dev).manual_seed(gen_seed)
     E = torch.randn(vocab, width, device=dev, generator=gen).to(torch.bfloat16)
@@ -178,12 +183,11 @@ def tail(dev, fused, scores, sampling, t0, *, width, seed, gen_seed, fill, stop=
     t, rng, ctr = i32([t0], dev), torch.zeros(1, device=dev, dtype=torch.int64), i32([0], dev)
     probs = torch.full((n, vocab), -1.0, device=dev)
     if fused:
-        ops.sample_step(scores, vocab, ids, t, rng, seed, E, emb, 1.0, ctr, stop=stop, unfinished=unfinished, alive=alive, out_probs=probs,
-                        **rules, **sampling)
+        ops.sample_step(scores, vocab, ids, t, rng, seed, E, emb, 1.0, ctr, out_probs=probs, **rules, **sampling)
     else:
-        ops.rules_mask(scores, vocab, t, stop=stop, **rules)
+        ops.rules_mask(scores, vocab, t, **mask)
         ops.sample(scores, ids, t, rng, seed, out_probs=probs, **sampling)
         ops.decode_advance(t, rng)
-        ops.rules_advance(ids, t, stop=stop, unfinished=unfinished, alive=alive, **rules)
+        ops.rules_advance(ids, t, **rules)
     assert t.tolist() == [t0 + 1] and rng.tolist() == [1]
     return ids[:, t0 + 1].cpu(), probs.cpu(), emb, ids, (t, rng, ctr), E

@@ -161,8 +161,8 @@ def _fused_and_unfused(dev, g, kw, stop, ks):
         ops.sample_step(scores.clone(), V, f['ids'], f['t'], f['rng'], seed, E, emb, 1.0, ctr, stop=stop, unfinished=f['unfinished'],
                         alive=f['alive'], grammar=g, gstate=f['gstate'], gbar=f['gbar'], grem=f['grem'],
                         gleft=None if ks is None else f['gleft'], **sampling)
-        sample_unfused(scores.clone(), V, u['ids'], u['t'], u['rng'], seed, sampling, stop, u['unfinished'], u['alive'], g,
-                       u['gstate'], u['gbar'], u['grem'], None if ks is None else u['gleft'])
+        sample_unfused(scores.clone(), V, u['ids'], u['t'], u['rng'], seed, sampling,
+                       ops.RuleState(stop, u['unfinished'], u['alive'], g, u['gstate'], u['gbar'], u['grem'], None if ks is None else u['gleft']))
         for k in f:
             assert torch.equal(f[k], u[k]), (step, k, f[k].tolist()[:8], u[k].tolist()[:8])
     off = (['unfinished', 'alive'] if stop is None else []) + (['gstate'] if g is None else []) + ([] if budget else ['gbar', 'grem']) \

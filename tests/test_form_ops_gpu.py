@@ -247,11 +247,11 @@ def test_argument_checks(dev):
     st = _State(dev)
     kw = st.kwargs(0)
     scores, t = torch.zeros(NB, V, device=dev), i32([T0], dev)
-    rules = ops._rules_struct('t', dev, NB, V, **kw)                            # every group but the guide
+    rules = ops.RuleState(**kw).struct('t', dev, NB, V)                         # every group but the guide
     rules.hist, rules.ld_hist = ptr(st.ids), LD_IDS                                # (read by the mask alone)
     table, zeros = torch.zeros(NB, 8, device=dev, dtype=torch.int32), i32([0] * NB, dev)
     gpos, gforce = zeros.clone(), zeros.clone()                                    # (held here: the struct keeps addresses only)
-    guided = ops._rules_struct('t', dev, NB, V, grammar=G, gstate=st.gs, melody=G.guide, guide=table, glen=zeros, gpos=gpos, gforce=gforce)
+    guided = ops.RuleState(grammar=G, gstate=st.gs, melody=G.guide, guide=table, glen=zeros, gpos=gpos, gforce=gforce).struct('t', dev, NB, V)
     guide = {k: getattr(guided, k) for k in ('guide', 'ld_guide', 'glen', 'enter', 'leave', 'gpos', 'gforce')}
     assert all(guide.values())
     REPEAT = ('plan', 'nplan', 'barcol', 'gbars', 'gcopy', 'gstop')                # the group's pointers
@@ -296,7 +296,54 @@ def test_argument_checks(dev):
         with pytest.raises(MusicXLError, match=what):
             ops.rules_mask(scores, V, t, **args)
     with pytest.raises(MusicXLError, match='excludes the guide'):
-        ops.rules_in_force(**{**kw, 'melody': G.guide, 'guide': table, 'glen': zeros, 'gpos': zeros, 'gforce': zeros})
+        ops.RuleState(**{**kw, 'melody': G.guide, 'guide': table, 'glen': zeros, 'gpos': zeros, 'gforce': zeros}).in_force()
     with pytest.raises(MusicXLError, match='needs the bar count'):
-        ops.rules_in_force(**{**kw, 'gleft': None})
-    assert 'repeat' not in ops.rules_in_force(**{**kw, 'repeat': None}) and 'repeat' in ops.rules_in_force(**kw)
+        ops.RuleState(**{**kw, 'gleft': None}).in_force()
+    assert ops.RuleState(**{**kw, 'repeat': None}).in_force().repeat is None and ops.RuleState(**kw).in_force().repeat is not None
+
+
+@pytest.mark.parametrize('fused', [True, False], ids=['fused', 'unfused'])
+def test_a_rule_state_is_its_flat_keywords(dev, fused):
+    """one sampler tail given the rules as rules=ops.RuleState(...) and one given the same fields as flat keywords, over cloned state:
+    the tokens, the distribution, the embedding rows, every word of the packed buffer, alive and the counters are equal -- three
+    rows under the stop, grammar, budget, count, key and register groups (tests/rules_ref.py's tail), then the cases above under the
+    repeat group as well, whose mask reads the history (tests/form_ref.py's tail)."""
+    from symbolic_music_generation_amd import ops
+    from tests import rules_ref
+    sampling = sampling_config(do_sample=True, top_k=8, temperature=0.9)
+    rows = [CASES[b] for b in (0, 3, 10)]           # opens a bar, mid-melody with a floor, inside the bass: none needs the plan
+    NAMES6 = ('unfinished', 'gstate', 'gbar', 'grem', 'gleft', 'gkey', 'grange', 'gpart', 'gfloor')
+    start = [[c['words'][k] for c in rows] for k in range(6)]
+    start += [[pack_bounds(c['reg'].bounds) for c in rows], [c['reg'].part for c in rows], [c['reg'].floor for c in rows], [3]]
+    start[0][2] = 0                                  # the third row finished before the step: pad, and its words stay
+    keep = torch.from_numpy(np.stack([form_ref.keep(RULES, c['words'], Form(), [], c['ids'], V, REG, c['reg'], 1) for c in rows]))
+    assert keep.any(1).all() and not keep.all(1).any()
+
+    def six():
+        """the packed words of the three rows, (9, 3) and alive, and the keywords over them"""
+        buf = i32([x for word in start for x in word], dev)
+        words = dict(zip(NAMES6, buf[:-1].view(len(NAMES6), 3)))
+        return buf, dict(stop=(EOS, PAD, 0), alive=buf[-1:], grammar=G, in_key=RULE, register=REG, gap=1, **words)
+
+    gen = torch.Generator(device=dev).manual_seed(31)
+    scores = 2.0 * torch.randn(3, V, device=dev, generator=gen)
+    out = []
+    for as_object in (False, True):
+        buf, kw = six()
+        given = dict(rules=ops.RuleState(**kw)) if as_object else kw
+        toks, probs, emb, ids, counters, _ = rules_ref.tail(dev, fused, scores.clone(), sampling, 2, width=64, seed=17, gen_seed=2, fill=FILL,
+                                                            **given)
+        out.append((toks, probs, emb.cpu(), ids.cpu(), [c.tolist() for c in counters], buf.cpu()))
+    for flat, obj in zip(*out):
+        assert torch.equal(flat, obj) if isinstance(flat, torch.Tensor) else flat == obj
+    toks, words = out[1][0].tolist(), out[1][5].tolist()
+    assert all(keep[b, toks[b]] for b in (0, 1)) and toks[2] == PAD
+    assert words != [x for word in start for x in word] and words[-1] == 2 - toks[:2].count(EOS)      # the words moved, alive counted
+    # the repeat group beside them, with the history
+    a, b = _State(dev), _State(dev)
+    flat = form_ref.tail(dev, fused, _scores(dev)[:, :V], sampling, a.ids, T0, width=64, seed=17, gen_seed=2, **a.kwargs(1))
+    obj = form_ref.tail(dev, fused, _scores(dev)[:, :V], sampling, b.ids, T0, width=64, seed=17, gen_seed=2, rules=ops.RuleState(**b.kwargs(1)))
+    assert all(torch.equal(x.cpu(), y.cpu()) for x, y in zip(flat, obj))
+    assert a.words() == b.words() != a.start() and a.alive.tolist() == b.alive.tolist() != [-5]
+    assert torch.equal(a.barcol, b.barcol) and not torch.equal(a.barcol.cpu(), a.barcol_host) and torch.equal(a.ids, b.ids)
+    assert a.fixed_untouched() and b.fixed_untouched()
